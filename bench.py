@@ -14,9 +14,12 @@ N > 1  : the same map and workload with the bank (and the .bow matrix) sharded b
 `python bench.py --gpus N` without a launcher starts the N ranks itself (before any GPU call) through
 torch.distributed.run and relays rank 0's JSON line; under a launcher a rank insists on WORLD_SIZE == --gpus.
 
-Prints ONE JSON line (rank 0).  `roofline` = the dominant kernel family (K1 Hamming 2-NN) measured live, one launch
-in flight, on the FULL 20 M-row bank of the same map (SURVEY 8d cfg 3); `cpu_baseline` = the C oracle timed on this
-host's cores on a bounded sample of the same workload (N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the headline
+(`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes the results of the last timed step as .npy files.
+`--full` adds everything else, after the timed region: `identical_to_single_flight`, `latency_ms`, `stage_ms`,
+`roofline` = the dominant kernel family (K1 Hamming 2-NN) measured live, one launch in flight, on the FULL 20 M-row bank
+of the same map (SURVEY 8d cfg 3); `cpu_baseline` = the C oracle timed on this host's cores on a bounded sample of the
+same workload (N = 1 only); the `image_in` legs; at N > 1 the `replicas` leg.
 """
 import argparse
 import json
@@ -61,6 +64,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: stage split, single-flight latency and bit-identity of the timed results, "
+                         "roofline scans, CPU baseline, image-in legs, the replicas leg at --gpus N (the --no-* options "
+                         "below leave parts of it out).  Without it a run sets up, warms up, times the steps and prints "
+                         "the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the path returned for every query of the LAST timed step "
+                         "(pose fields and inlier pairs, without stage timings) as DIR/<name>.npy, float64")
     ap.add_argument("--batch", type=int, default=256, help="queries per step (and per all-gather when --gpus > 1)")
     ap.add_argument("--views", type=int, default=10000)
     ap.add_argument("--desc-per-view", type=int, default=2000)
@@ -104,7 +115,8 @@ def parse(argv=None):
     ap.add_argument("--no-image-in", action="store_true",
                     help="skip the image-in leg (frame -> AKAZE + M-LDB -> BoW vector from the image -> shortlist -> path -> "
                          "pose on a map whose bank was extracted from rendered views)")
-    ap.add_argument("--image-in-only", action="store_true", help="run only the image-in leg (development)")
+    ap.add_argument("--image-in-only", action="store_true",
+                    help="run only the image-in leg of --full, without the headline (development)")
     ap.add_argument("--image-tiles", type=int, default=8,
                     help="image-in leg: the plane is tiles x tiles places of 16 m x 16 m with a texture each")
     ap.add_argument("--image-views", type=int, default=0,
@@ -787,12 +799,20 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
     busy = [False] * nctx
 
     q_of = [0] * nctx
+    i_of = [0] * nctx
+    # --dump-outputs: the results of queries >= last[0] of the timed run, by query index (None: nothing is kept)
+    last = [None, {}]
+
+    def keep(i, res):
+        if last[0] is not None and i >= last[0]:
+            last[1][i] = res
 
     def finish(k):
         pose, pq, pl = ctxs[k].end()
         lat.append(time.perf_counter() - t_begin[k])
         n_ok[0] += int(pose.ok)
         fps.append((q_of[k], fingerprint(pose, pq, pl)))
+        keep(i_of[k], (pose, pq, pl))
         busy[k] = False
 
     def begin(k, i):
@@ -816,6 +836,8 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
             t_mark = [t_mark[1], now]
             n_ok[0] += sum(int(r["ok"]) for r in res.values())
             fps.extend((b[j] % len(dqs), r["fingerprint"]) for j, r in res.items())
+            for j, r in res.items():
+                keep(b[j], r)
 
     def run_threads(first, count):
         import threading
@@ -836,6 +858,7 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
                     pose, pq, pl = c.end()
                     lat_l.append(time.perf_counter() - tb[k])
                     fp_l.append((i % len(dqs), fingerprint(pose, pq, pl)))
+                    keep(i, (pose, pq, pl))
                     ok += int(pose.ok)
                 cur[k] = []
                 return ok
@@ -868,12 +891,14 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
             tb = {k: 0.0 for k in mine}
             bz = {k: False for k in mine}
             qi = {k: 0 for k in mine}
+            ia = {k: 0 for k in mine}
             lat_l, ok_l, fp_l = [], 0, []
 
             def fin(k):
                 pose, pq, pl = ctxs[k].end()
                 lat_l.append(time.perf_counter() - tb[k])
                 fp_l.append((qi[k], fingerprint(pose, pq, pl)))
+                keep(ia[k], (pose, pq, pl))
                 return int(pose.ok)
 
             for n, i in enumerate(range(first + phase + t * stride, first + count, nthr * stride)):
@@ -883,6 +908,7 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
                 tb[k] = time.perf_counter()
                 begin(k, i)
                 qi[k] = i % len(dqs)
+                ia[k] = i
                 bz[k] = True
             for k in mine:
                 if bz[k]:
@@ -912,6 +938,7 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
             t_begin[k] = time.perf_counter()
             begin(k, i)
             q_of[k] = i % len(dqs)
+            i_of[k] = i
             busy[k] = True
 
     def drain():
@@ -971,6 +998,8 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
                     lat.extend([time.perf_counter() - t1] * len(idx))
                     n_ok[0] += sum(oks)
                     fps.extend((i % len(dqs), fingerprint(*e)) for i, e in zip(idx, ends))
+                    for i, e in zip(idx, ends):
+                        keep(i, e)
                     n_feat[0] = len(feats[0][0])
 
         def run_images(first, count):
@@ -993,11 +1022,14 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
     lat.clear()
     fps.clear()
     n_ok[0] = 0
+    if a.dump_outputs:
+        last[0] = (a.steps - 1) * a.batch
     fence()
     t0 = time.perf_counter()
     run(0, n_timed)
     fence()
     dt = time.perf_counter() - t0
+    last[0] = None
     fps_timed = list(fps)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
@@ -1011,8 +1043,23 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
         n_ok_timed = int(ok_t.item())
     if sharded is not None:
         xchg = sharded.counters()
+    if a.dump_outputs:
+        res_last = last[1]
+        if dist is not None and world > 1:    # every rank holds the results of its own queries of the step
+            parts = [None] * world
+            dist.all_gather_object(parts, {i: _result_arrays(r) for i, r in res_last.items()})
+            res_last = {i: r for p in parts for i, r in p.items()}
+        if rank == 0:
+            dump_outputs(a.dump_outputs, res_last, (a.steps - 1) * a.batch, a.batch, len(dqs), a.nq)
+    if not a.full:
+        out = None
+        if rank == 0:
+            out = headline(a, world, n_timed, dt, m, shortlist, sharded, nctx, gang, replicas, n_ok_timed, t_gen, diag,
+                           img_mode)
+        measure_close(img_mode, members, ctxs, sharded, dqs, dev_map)
+        return out
 
-    # ---- outside the timed region -------------------------------------------------------------------------------
+    # ---- outside the timed region (--full) ----------------------------------------------------------------------
     # (a) stage split and the in-path K1 launches: the same queries again with every stage bracketed by HIP events
     dev_map.set_profile(1)
     dev_map.stats_reset()
@@ -1069,37 +1116,9 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
         if shortlist and sharded is None:
             sel0 = dev_map.bow_select(qbow[0], a.bow_knn)
             sel_rows = int(sum(int(m.view_off[v + 1] - m.view_off[v]) for v in sel0))
-        out = {
-            "metric": "query images localized/sec",
-            "value": n_timed / dt,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u32 popcount (Hamming); f64 geometry",
-            "data": "synthetic",
-            "config": {"workload": (f"BASELINE configs[{2 if world == 1 else 3}]: " if (shortlist and a.views == 10000) else "")
-                                   + f"{a.views}-image / {m.n_rows}-descriptor synthetic map, {a.nq} feats/query, "
-                                   + (f"BoW shortlist of {a.bow_knn} views (exact L2 over the {a.views} x 500 .bow matrix) then "
-                                      if shortlist else "")
-                                   + "the whole per-query path: brute-force Hamming 2-NN + Lowe ratio -> >=16 filter -> "
-                                   "F-matrix AC-RANSAC (25 rounds) -> 2D-3D set -> P3P AC-RANSAC (4096) -> pose; "
-                                   f"one step = a batch of {a.batch} queries, {nctx} in flight per GPU",
-                       "views": a.views, "rows": int(m.n_rows), "nq": a.nq, "bow_knn": a.bow_knn, "batch": a.batch,
-                       "queries_per_step": a.batch, "queries_timed": n_timed, "in_flight_per_gpu": nctx,
-                       "host_threads": max(1, a.threads) if sharded is None else 1,
-                       **({"queries_per_launch": gang} if sharded is not None else {}),
-                       "parallelism": ((f"replicas x{world}: every rank holds the whole bank, query i of a batch on rank i mod "
-                                        f"{world}, no collective") if (replicas and world > 1) else
-                                       (f"bank + .bow sharded by view x{world}; per {a.batch}-query batch one all-gather of "
-                                        "per-shard k-best BoW keys and ONE all-gather of candidate parts (RCCL), P3P of "
-                                        "query i on rank i mod N") if world > 1 else "1 GPU, whole bank"),
-                       "queries_localised": f"{n_ok_timed}/{n_timed}",
-                       "map_generation_s": round(t_gen, 1), **({"DIAGNOSTIC_OVERRIDES_NOT_THE_METRIC": diag} if diag else {})},
+        out = headline(a, world, n_timed, dt, m, shortlist, sharded, nctx, gang, replicas, n_ok_timed, t_gen, diag,
+                       img_mode)
+        out.update({
             "identical_to_single_flight": f"{n_same}/{n_cmp}",
             "latency_ms": {"p50": float(np.percentile(lat_single or lat_throughput, 50) * 1e3),
                            "p95": float(np.percentile(lat_single or lat_throughput, 95) * 1e3),
@@ -1112,7 +1131,7 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
                          "putMatch(K1+K2)": (st.total_ms[0] + st.total_ms[1]) / max(1, n_prof),
                          "geoMatch(K3)": st.total_ms[2] / max(1, n_prof), "matchSet(K4)": st.total_ms[3] / max(1, n_prof),
                          "PnP(K5)": st.total_ms[4] / max(1, n_prof)},
-        }
+        })
         if lat_single:
             out["latency_ms"]["stage_seconds_last_query"] = dict(zip(
                 ["selectBeacon", "selectBow", "extFeat", "putMatch", "geoMatch", "PnP", "others"], stage_seconds))
@@ -1185,13 +1204,67 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
                 out["roofline"]["in_path_scan"] = {
                     "rows_per_query": sel_rows, "event_bracket_ms": st.total_ms[0] / st.launches[0],
                     "note": "side note only: brackets of overlapping launches contain queue wait"}
-        if img_mode is not None:
-            out["config"]["workload"] += ("; image-in mode: each query first runs AKAZE + M-LDB extraction of a 640x480 "
-                                          f"synthetic image on the GPU ({img_mode['n_feat'][0]} keypoints), "
-                                          f"{img_mode['frames_per_turn']} frames per worker turn")
         if not a.no_cpu_baseline and world == 1:   # the CPU leg is timed on rank 0 of the single-GPU run only
             out["cpu_baseline"] = (cpu_baseline_shortlist(m, queries, bow, qbow, a.bow_knn, a.cpu_seconds)
                                    if shortlist else cpu_baseline(m, queries, a.cpu_seconds))
+    measure_close(img_mode, members, ctxs, sharded, dqs, dev_map)
+    if rank == 0:
+        # the image in front of the path, on a map of its own (the headline's map and contexts are gone by now)
+        if world == 1 and not a.no_image_in and not a.from_images and shortlist:
+            del m, queries, bow, qbow
+            out["image_in"] = image_in_phase(a, S, local_rank, log)
+            rb = out["image_in"].pop("k1_full_scan_of_this_map", None)
+            if rb is not None and "roofline" in out:
+                out["roofline"]["real_bank"] = rb
+            if not a.no_image_in_1080p:
+                out["image_in_1080p"] = image_in_phase(a, S, local_rank, log, hd=True)
+        return out
+    return None
+
+
+def headline(a, world, n_timed, dt, m, shortlist, sharded, nctx, gang, replicas, n_ok_timed, t_gen, diag, img_mode):
+    """The result line's headline part: the metric over the timed steps and the configuration it was measured on."""
+    out = {
+        "metric": "query images localized/sec",
+        "value": n_timed / dt,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u32 popcount (Hamming); f64 geometry",
+        "data": "synthetic",
+        "config": {"workload": (f"BASELINE configs[{2 if world == 1 else 3}]: " if (shortlist and a.views == 10000) else "")
+                               + f"{a.views}-image / {m.n_rows}-descriptor synthetic map, {a.nq} feats/query, "
+                               + (f"BoW shortlist of {a.bow_knn} views (exact L2 over the {a.views} x 500 .bow matrix) then "
+                                  if shortlist else "")
+                               + "the whole per-query path: brute-force Hamming 2-NN + Lowe ratio -> >=16 filter -> "
+                               "F-matrix AC-RANSAC (25 rounds) -> 2D-3D set -> P3P AC-RANSAC (4096) -> pose; "
+                               f"one step = a batch of {a.batch} queries, {nctx} in flight per GPU",
+                   "views": a.views, "rows": int(m.n_rows), "nq": a.nq, "bow_knn": a.bow_knn, "batch": a.batch,
+                   "queries_per_step": a.batch, "queries_timed": n_timed, "in_flight_per_gpu": nctx,
+                   "host_threads": max(1, a.threads) if sharded is None else 1,
+                   **({"queries_per_launch": gang} if sharded is not None else {}),
+                   "parallelism": ((f"replicas x{world}: every rank holds the whole bank, query i of a batch on rank i mod "
+                                    f"{world}, no collective") if (replicas and world > 1) else
+                                   (f"bank + .bow sharded by view x{world}; per {a.batch}-query batch one all-gather of "
+                                    "per-shard k-best BoW keys and ONE all-gather of candidate parts (RCCL), P3P of "
+                                    "query i on rank i mod N") if world > 1 else "1 GPU, whole bank"),
+                   "queries_localised": f"{n_ok_timed}/{n_timed}",
+                   "map_generation_s": round(t_gen, 1), **({"DIAGNOSTIC_OVERRIDES_NOT_THE_METRIC": diag} if diag else {})},
+    }
+    if img_mode is not None:
+        out["config"]["workload"] += ("; image-in mode: each query first runs AKAZE + M-LDB extraction of a 640x480 "
+                                      f"synthetic image on the GPU ({img_mode['n_feat'][0]} keypoints), "
+                                      f"{img_mode['frames_per_turn']} frames per worker turn")
+    return out
+
+
+def measure_close(img_mode, members, ctxs, sharded, dqs, dev_map):
+    """Releases what measure() created on the device, members before the contexts they share a stream with."""
     if img_mode is not None:
         for e in img_mode["extractors"]:
             e.close()
@@ -1207,22 +1280,61 @@ def measure(a, rank, world, local_rank, dist, torch, replicas):
     for dq in dqs:
         dq.close()
     dev_map.close()
-    if rank == 0:
-        # the image in front of the path, on a map of its own (the headline's map and contexts are gone by now)
-        if world == 1 and not a.no_image_in and not a.from_images and shortlist:
-            del m, queries, bow, qbow
-            out["image_in"] = image_in_phase(a, S, local_rank, log)
-            rb = out["image_in"].pop("k1_full_scan_of_this_map", None)
-            if rb is not None and "roofline" in out:
-                out["roofline"]["real_bank"] = rb
-            if not a.no_image_in_1080p:
-                out["image_in_1080p"] = image_in_phase(a, S, local_rank, log, hd=True)
-        return out
-    return None
+
+
+# a Pose's fields as --dump-outputs writes them (stage_seconds, the timings, are left out)
+POSE_SCALARS = ("ok", "n_inliers", "n_matches_2d3d", "iterations", "status", "n_putative_views", "n_geometric_views",
+                "nfa", "error_max")
+POSE_ARRAYS = {"P": (3, 4), "K": (3, 3), "R": (3, 3), "t": (3,), "center": (3,)}
+
+
+def _result_arrays(res):
+    """One query's result as its caller received it -- (Pose, pair_qfeat, pair_landmark) from Context.end, or the sharded
+    path's result dict -- as ({field: float64 array}, pair_qfeat, pair_landmark)."""
+    import numpy as np
+    if isinstance(res, dict):
+        f = {k: np.asarray(res[k], np.float64) for k in ("ok", "n_inliers", "P", "R", "center")}
+        return f, np.asarray(res["pair_qfeat"]), np.asarray(res["pair_landmark"])
+    pose, pq, pl = res
+    if isinstance(pose, dict):        # converted already (gathered from the ranks)
+        return res
+    f = {k: np.float64(getattr(pose, k)) for k in POSE_SCALARS}
+    f.update({k: np.array(getattr(pose, k), np.float64).reshape(s) for k, s in POSE_ARRAYS.items()})
+    return f, pq, pl
+
+
+def dump_outputs(path, res, first, batch, n_distinct, nq, limit=64 << 20):
+    """--dump-outputs: the results of the last timed step (queries first .. first + batch - 1), one row per query in step
+    order, as path/<field>.npy in float64; `query` = which distinct synthetic query, `step_position` = its place in the
+    step; the inlier pairs of all rows concatenated, row r's at pair_offsets[r]:pair_offsets[r + 1].  At most `limit`
+    bytes: a larger step is written as a seeded sample of its rows, chosen from the arguments alone."""
+    import numpy as np
+    idx = [i for i in range(first, first + batch) if i in res]
+    row_bytes = 8 * (len(POSE_SCALARS) + 12 + 9 + 9 + 3 + 3 + 3) + 16 * max(1, nq)   # a query has at most nq inlier pairs
+    cap = max(1, limit // row_bytes)
+    if len(idx) > cap:
+        pick = np.sort(np.random.default_rng(0).choice(len(idx), cap, replace=False))
+        idx = [idx[p] for p in pick]
+    recs = [_result_arrays(res[i]) for i in idx]
+    cols = {"query": np.array([i % n_distinct for i in idx]), "step_position": np.array([i - first for i in idx])}
+    for k in (recs[0][0] if recs else {}):
+        cols[k] = np.stack([r[0][k] for r in recs])
+    cols["pair_offsets"] = np.concatenate([[0], np.cumsum([len(r[1]) for r in recs])])
+    cols["pair_qfeat"] = np.concatenate([np.asarray(r[1]).ravel() for r in recs] or [np.zeros(0)])
+    cols["pair_landmark"] = np.concatenate([np.asarray(r[2]).ravel() for r in recs] or [np.zeros(0)])
+    os.makedirs(path, exist_ok=True)
+    for k, v in cols.items():
+        np.save(os.path.join(path, k + ".npy"), np.asarray(v, np.float64))
+    print(f"[bench] --dump-outputs: {len(idx)} of the last step's {batch} results, {len(cols)} arrays -> {path}",
+          file=sys.stderr, flush=True)
 
 
 def main():
     a = parse()
+    if a.dump_outputs and a.image_in_only:
+        sys.exit("bench.py: --dump-outputs writes the headline path's results; --image-in-only does not run it")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a))   # before torch / HIP are touched in this process
     rank = int(os.environ.get("RANK", "0"))
@@ -1311,11 +1423,12 @@ class Watchdog:
 
 def run_all(a, rank, world, local_rank, dist, torch):
     out = measure(argparse.Namespace(**vars(a)), rank, world, local_rank, dist, torch, a.replicas)
-    if world > 1 and not a.replicas and not a.no_replica_leg and not a.image_in_only:
+    if a.full and world > 1 and not a.replicas and not a.no_replica_leg and not a.image_in_only:
         # the comparison SCALE runs need: N independent replicas of the whole map, same queries, no exchange
         b = argparse.Namespace(**vars(a))
         b.no_cpu_baseline = b.no_roofline_phase = b.no_image_in = True
         b.threads = b.in_flight = 0
+        b.dump_outputs = None
         rep = measure(b, rank, world, local_rank, dist, torch, True)
         if rank == 0:
             out["replicas"] = {k: rep[k] for k in ("value", "unit", "ms_per_step", "identical_to_single_flight", "latency_ms")}

@@ -74,3 +74,44 @@ def test_plan_of_a_run():
     a = bench.parse(["--bow-knn", "0", "--views", "1000"])
     shortlist, _, _, _, nctx, _ = bench.plan(a, 1, False)
     assert not shortlist and nctx == 4
+
+
+def test_plain_run_and_full_options():
+    """A plain run measures the headline only; --full turns the side measurements on, --dump-outputs names a folder."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs: one float64 row per query of the last step in step order, the inlier pairs concatenated with
+    offsets, the stage timings left out; a step too large for the limit is written as the same seeded sample of rows."""
+    from sfmlocalization_amd import capi
+    res = {}
+    for i in range(8, 16):          # the last step of --steps 2 --batch 8 (queries 8 .. 15) among 5 distinct queries
+        p = capi.Pose()
+        p.ok, p.n_inliers, p.status, p.nfa = i % 2, i - 7, 3, -1.5 * i
+        p.R[:] = [float(i)] * 9
+        p.center[:] = [i, -i, 0.5]
+        p.stage_seconds[:] = [9.0] * 7
+        res[i] = (p, np.arange(i - 7, dtype=np.uint32), np.arange(i - 7, dtype=np.uint32) + 100 * i)
+    res[3] = res[8]                 # an earlier query's result is not part of the step
+    bench.dump_outputs(str(tmp_path / "d"), res, 8, 8, 5, 300)
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert all(f.endswith(".npy") for f in os.listdir(tmp_path / "d"))
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert "stage_seconds" not in got
+    np.testing.assert_array_equal(got["step_position"], np.arange(8))
+    np.testing.assert_array_equal(got["query"], np.arange(8, 16) % 5)
+    np.testing.assert_array_equal(got["ok"], np.arange(8, 16) % 2)
+    assert got["R"].shape == (8, 3, 3) and got["P"].shape == (8, 3, 4) and got["center"].shape == (8, 3)
+    np.testing.assert_array_equal(got["center"][:, 1], -np.arange(8, 16))
+    off = got["pair_offsets"].astype(int)
+    assert off[0] == 0 and off[-1] == len(got["pair_qfeat"]) == len(got["pair_landmark"]) == sum(range(1, 9))
+    np.testing.assert_array_equal(got["pair_landmark"][off[3]:off[4]], np.arange(4) + 100 * 11)
+    # a small limit: a seeded sample of the rows, the same on every call
+    bench.dump_outputs(str(tmp_path / "s1"), res, 8, 8, 5, 300, limit=3 * 8 * (16 + 300 * 2))
+    bench.dump_outputs(str(tmp_path / "s2"), res, 8, 8, 5, 300, limit=3 * 8 * (16 + 300 * 2))
+    s1, s2 = np.load(tmp_path / "s1" / "step_position.npy"), np.load(tmp_path / "s2" / "step_position.npy")
+    assert 0 < len(s1) < 8 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)

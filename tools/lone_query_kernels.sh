@@ -1,6 +1,7 @@
 # per-kernel median duration over the lone headline queries of a short bench run (one query in flight)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pb2
-rocprofv3 --kernel-trace --output-format csv -d /tmp/pb2 -o b -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --batch 64 --in-flight 1 --no-image-in --no-cpu-baseline --no-real-stats --no-roofline-phase > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/pb2 -o b -- python3 $ROOT/bench.py --full --steps 1 --warmup 1 --batch 64 --in-flight 1 --no-image-in --no-cpu-baseline --no-real-stats --no-roofline-phase > /dev/null 2>&1
 python3 - <<PY
 import csv, glob, statistics
 f = glob.glob("/tmp/pb2/**/*kernel_trace.csv", recursive=True)[0]

@@ -10,7 +10,7 @@ ROOT=$GRAFT_REPO_ROOT
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-22}
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=$?; echo "pytest exit $rc" >> $O/pytest_gpu.log; tail -3 $O/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 900 python bench.py > $O/bench_default.json 2> $O/bench_default.log || exit 1
+timeout -k 10 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.log || exit 1
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench_default.json") if l.startswith("{")][-1])
@@ -20,12 +20,12 @@ print("headline", round(d["value"]), d["identical_to_single_flight"], "p50", rou
       "p50", round(d["image_in"]["latency_ms"]["p50"],2), "| 1080p", round(d["image_in_1080p"]["value"]), d["image_in_1080p"]["identical_to_single_flight"])
 PY
 cd /tmp && export TMPDIR=/tmp
-PB="$ROOT/bench.py --steps 2 --warmup 1 --image-steps 2 --image-steps-1080p 1 --no-cpu-baseline --no-real-stats --image-oracle-frames 1"
+PB="$ROOT/bench.py --full --steps 2 --warmup 1 --image-steps 2 --image-steps-1080p 1 --no-cpu-baseline --no-real-stats --image-oracle-frames 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -o bench -- python3 $PB > $ROOT/$O/bench_prof_run.log 2>&1 || exit 1
 cp $(find /tmp/prof_bench -name "*kernel_stats.csv" | head -1) $ROOT/$O/bench_kernel_stats.csv
 T=$(find /tmp/prof_bench -name "*kernel_trace.csv" | head -1)
 python3 $ROOT/tools/trace_busy.py $T "P3pFinish|k_p3p_finish" > $ROOT/$O/kernel_time_per_result_busiest_window.txt 2>&1
-PP="$ROOT/bench.py --steps 1 --warmup 0 --batch 16 --no-cpu-baseline --no-real-stats --no-image-in"
+PP="$ROOT/bench.py --full --steps 1 --warmup 0 --batch 16 --no-cpu-baseline --no-real-stats --no-image-in"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmc_fetch -- python3 $PP > $ROOT/$O/pmc_fetch.log 2>&1 || exit 1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /tmp/pmc_write -- python3 $PP > $ROOT/$O/pmc_write.log 2>&1 || exit 1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d /tmp/pmc_sq -- python3 $PP > $ROOT/$O/pmc_sq.log 2>&1 || exit 1

@@ -1,9 +1,9 @@
-mkdir -p gpurun_out
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export TRACE_DIR=$(mktemp -d)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_lat -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --batch 16 --in-flight 1 --no-cpu-baseline --no-roofline-phase $BENCH_ARGS > /dev/null 2>&1
-cd $GRAFT_REPO_ROOT; python - <<'PY'
-import csv,glob,re
-f=glob.glob("gpurun_out/prof_lat/*/*kernel_trace.csv")[0]
+rocprofv3 --kernel-trace --output-format csv -d $TRACE_DIR/prof_lat -- python3 $ROOT/bench.py --full --steps 1 --warmup 1 --batch 16 --in-flight 1 --no-cpu-baseline --no-roofline-phase $BENCH_ARGS > /dev/null 2>&1
+cd $ROOT; python - <<'PY'
+import csv,glob,os,re
+f=glob.glob(os.environ["TRACE_DIR"] + "/prof_lat/*/*kernel_trace.csv")[0]
 rows=list(csv.DictReader(open(f)))
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
 # last query: find last k_hamming_screen
