@@ -571,6 +571,57 @@ const void *sfmloc_imgbow_vector_dev(const sfmloc_imgbow *ib);
  * context's stream wait for everything the extractor has queued so far (call it before sfmloc_localize_bow_begin) */
 int sfmloc_imgbow_order_before(sfmloc_imgbow *ib, sfmloc_context *ctx);
 
+/* Vocabulary training (TrainBoW/src/TrainBoW.cpp): the device-resident training sample, PCA and k-means behind
+ * BOWfile.yml / PCAfile.yml.  All work is queued on the trainer's own non-blocking stream; every reduction runs in a
+ * fixed order, so two runs give the same bytes.  Fixed arithmetic (the test restates it):
+ *   rows are f32 [n x dim], dim <= 64; "chunk" = 1024 consecutive rows;
+ *   moments: Sx, Sxx summed in f64 sequentially within a chunk, chunks added in order (exact for integer rows);
+ *     mean = Sx / N, cov = (Sxx - N * (mean_i * mean_j)) / N (cv::PCA, CV_COVAR_SCALE); cyclic Jacobi on the host,
+ *     eigenvalues descending, each eigenvector's largest-magnitude component positive (first such on ties);
+ *   projection: bof_device.h, the arithmetic of sfmloc_bof_compute's PCA step (project, divide by the eigenvalue);
+ *   distance = sum_d (x_d - c_d)^2 in f32, dimension order, unfused; ties to the lower centre index;
+ *   k-means++ (generateCentersPP, 3 local trials): first centre next() % N; a trial draws u = (double)rng and takes the
+ *     first i whose running sum R_i >= u * total, R_i = (sum of the partials of the chunks before i's) + (sum within
+ *     i's chunk up to i), each sum f64 and sequential (N - 1 if none); total = the chunk partials added in order;
+ *   Lloyd (cv::kmeans, OpenCV 3 shape): centre sums in f64 (per chunk sequential, chunks in order), divided by the
+ *     count in f64, rounded to f32; an empty cluster takes the biggest cluster's (first on ties) farthest point (the
+ *     last on ties) from that cluster's centre (f32 of sum / count); squared shift in f64; stop when ++iter ==
+ *     max(max_iter, 2) or the largest shift <= eps^2; the min distances and compactness (their f64 chunked sum) are
+ *     those of the last assignment, the labels those of the last assignment after the last centre step's empty-cluster
+ *     moves (as cv::kmeans returns them); best of `attempts`, the first wins ties.
+ *   cv::RNG: state = (u64)(u32)state * 4164903690 + (state >> 32), next() = (u32)state; uniform(0.f, 1.f) =
+ *     (float)next() * 2^-32; (double)rng = ((u64)next() << 32 | next()) * 2^-64; state 0 means 0xffffffff. */
+typedef struct sfmloc_bowtrain sfmloc_bowtrain;
+/* cap_rows: sample capacity; dim: row length (61 for the dense M-LDB rows) */
+int sfmloc_bowtrain_create(int device, uint32_t dim, uint32_t cap_rows, sfmloc_bowtrain **out);
+void sfmloc_bowtrain_destroy(sfmloc_bowtrain *t);
+int sfmloc_bowtrain_reset(sfmloc_bowtrain *t); /* empty the sample (dim back to the created one) */
+int sfmloc_bowtrain_add_rows(sfmloc_bowtrain *t, const float *rows, uint32_t n); /* host rows [n x dim] */
+/* getRandomTrainFeatures' body for one draw (TrainBoW.cpp:106-125): the image's dense descriptors (the chain of
+ * sfmloc_dense_gray + sfmloc_akaze_compute on the 300 x 300 dense grid, 61 bytes as f32), then n_pick rows
+ * k = min((int)(rows * uniform(0.f, 1.f)), rows - 1) drawn from *rng_state and gathered on the device.  bgr == NULL:
+ * an image without descriptors -- its n_pick rows stay zero and nothing is drawn.  The descriptors of the last image are
+ * kept: the same image again (same bytes) is not extracted again (the reference extracts it again: same bits). */
+int sfmloc_bowtrain_add_image(sfmloc_bowtrain *t, const uint8_t *bgr, uint32_t w, uint32_t h, uint32_t channels,
+                              uint32_t n_pick, uint64_t *rng_state);
+int sfmloc_bowtrain_size(const sfmloc_bowtrain *t, uint32_t *n, uint32_t *dim);
+int sfmloc_bowtrain_read(sfmloc_bowtrain *t, float *rows, uint64_t cap_floats); /* the sample [n x dim], synchronises */
+/* cv::PCA(sample, noArray(), DATA_AS_ROW) (PcaWrapper.cpp:31-46): f64 results (each pointer may be NULL):
+ * mean [dim], cov [dim x dim], eigvec [dim x dim] (rows), eigval [dim] */
+int sfmloc_bowtrain_pca64(sfmloc_bowtrain *t, double *mean, double *cov, double *eigvec, double *eigval);
+/* the same as PCAfile.yml holds it: MeanPCA [1 x dim], EigenVectorsPCA [dim x dim], EigenValuesPCA [dim x 1] f32 */
+int sfmloc_bowtrain_pca(sfmloc_bowtrain *t, float *mean, float *eigvec, float *eigval);
+/* PcaWrapper::calcPcaProject (TrainBoW.cpp:213): sample -> pca->n_pca columns, in place (pca->in_dim == dim) */
+int sfmloc_bowtrain_project(sfmloc_bowtrain *t, const sfmloc_bof_desc *pca);
+/* BoFSpatialPyramids::trainKMeans (BoFSpatialPyramids.cpp:95-106): cv::kmeans(sample, min(K, n), labels,
+ * TermCriteria(COUNT + EPS, max_iter, eps), attempts, KMEANS_PP_CENTERS), k-means++ draws from cv::RNG(seed).
+ * min(K, n) x dim x 8 + min(K, n) x 4 bytes must fit 64 KB (the centre sums' workgroup memory): K <= 132 at dim 61,
+ * K <= 248 at dim 32; SFMLOC_EINVAL otherwise.  centers [min(K, n) x dim]; labels [n], min_dist [n] (f32 distance to
+ * the assigned centre), compactness, iterations (assignments run, all attempts together): each may be NULL. */
+int sfmloc_bowtrain_kmeans(sfmloc_bowtrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, double eps,
+                           uint64_t seed, float *centers, int32_t *labels, float *min_dist, double *compactness,
+                           uint32_t *iterations);
+
 /* ------------------------------------------------------------------------- */
 /* Map-side matching: the reference's matchAKAZE /         */
 /* trackAKAZE on the same kernels.  Views are addressed by their index in the  */

@@ -124,6 +124,9 @@ SYMBOLS = [
     "sfmloc_imgbow_create", "sfmloc_imgbow_destroy", "sfmloc_imgbow_dim", "sfmloc_imgbow_share_stream", "sfmloc_imgbow_compute", "sfmloc_imgbow_compute_batch", "sfmloc_imgbow_vector_read",
     "sfmloc_shard_batch_bow_keys", "sfmloc_shard_batch_begin_bow", "sfmloc_shard_batch_begin", "sfmloc_merge_batch_begin",
     "sfmloc_imgbow_vector_dev", "sfmloc_imgbow_order_before", "sfmloc_akaze_detect_resident", "sfmloc_akaze_detect_resident_batch", "sfmloc_akaze_resident_arrays",
+    "sfmloc_bowtrain_create", "sfmloc_bowtrain_destroy", "sfmloc_bowtrain_reset", "sfmloc_bowtrain_add_rows",
+    "sfmloc_bowtrain_add_image", "sfmloc_bowtrain_size", "sfmloc_bowtrain_read", "sfmloc_bowtrain_pca64",
+    "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
 ]
 
 _bound = False
@@ -330,6 +333,21 @@ def _L():
         L.sfmloc_akaze_detect_resident.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), U32P]
         L.sfmloc_akaze_detect_resident_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint8)), C.c_uint32, U32P]
         L.sfmloc_akaze_resident_arrays.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
+        F32P = C.POINTER(C.c_float)
+        L.sfmloc_bowtrain_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.sfmloc_bowtrain_destroy.restype = None
+        L.sfmloc_bowtrain_destroy.argtypes = [C.c_void_p]
+        L.sfmloc_bowtrain_reset.argtypes = [C.c_void_p]
+        L.sfmloc_bowtrain_add_rows.argtypes = [C.c_void_p, F32P, C.c_uint32]
+        L.sfmloc_bowtrain_add_image.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.POINTER(C.c_uint64)]
+        L.sfmloc_bowtrain_size.argtypes = [C.c_void_p, U32P, U32P]
+        L.sfmloc_bowtrain_read.argtypes = [C.c_void_p, F32P, C.c_uint64]
+        L.sfmloc_bowtrain_pca64.argtypes = [C.c_void_p, F64P, F64P, F64P, F64P]
+        L.sfmloc_bowtrain_pca.argtypes = [C.c_void_p, F32P, F32P, F32P]
+        L.sfmloc_bowtrain_project.argtypes = [C.c_void_p, C.POINTER(BofDesc)]
+        L.sfmloc_bowtrain_kmeans.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, F32P,
+                                             C.POINTER(C.c_int32), F32P, F64P, U32P]
         _bound = True
     return L
 
@@ -1004,6 +1022,103 @@ class BofModel:
         if self._h is not None:
             _L().sfmloc_bof_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BowTrainer:
+    """sfmloc_bowtrain: TrainBoW's training (TrainBoW.cpp) on the device -- the resident sample (host rows or the drawn dense
+    rows of images), cv::PCA, the projection, cv::kmeans.  The fixed arithmetic is stated in include/sfmloc.h."""
+
+    def __init__(self, dim=61, cap_rows=300000, device=0):
+        self._h = None
+        h = C.c_void_p()
+        _check(_L().sfmloc_bowtrain_create(int(device), int(dim), int(cap_rows), C.byref(h)))
+        self._h = h
+
+    def reset(self):
+        _check(_L().sfmloc_bowtrain_reset(self._h))
+
+    def size(self):
+        """-> (rows, dim) of the sample"""
+        n, d = C.c_uint32(0), C.c_uint32(0)
+        _check(_L().sfmloc_bowtrain_size(self._h, C.byref(n), C.byref(d)))
+        return int(n.value), int(d.value)
+
+    def add_rows(self, rows):
+        rows = np.ascontiguousarray(rows, np.float32)
+        _check(_L().sfmloc_bowtrain_add_rows(self._h, _ptr(rows.reshape(-1), C.c_float), rows.shape[0]))
+
+    def add_image(self, image, n_pick, rng_state):
+        """the dense rows of one image (h x w x 3 BGR or h x w gray; None = no descriptors) at n_pick draws of the cv::RNG
+        state -> the state after the draws"""
+        st = C.c_uint64(int(rng_state))
+        if image is None:
+            _check(_L().sfmloc_bowtrain_add_image(self._h, None, 0, 0, 3, int(n_pick), C.byref(st)))
+            return int(st.value)
+        img = np.ascontiguousarray(image, np.uint8)
+        h, w = img.shape[:2]
+        ch = 1 if img.ndim == 2 else img.shape[2]
+        _check(_L().sfmloc_bowtrain_add_image(self._h, _ptr(img.reshape(-1), C.c_uint8), w, h, ch, int(n_pick), C.byref(st)))
+        return int(st.value)
+
+    def read(self):
+        n, d = self.size()
+        out = np.zeros((n, d), np.float32)
+        _check(_L().sfmloc_bowtrain_read(self._h, _ptr(out.reshape(-1), C.c_float), out.size))
+        return out
+
+    def pca64(self):
+        """-> (mean [d], cov [d, d], eigvec [d, d] rows, eigval [d]) in float64"""
+        d = self.size()[1]
+        m, c, v, e = np.zeros(d), np.zeros((d, d)), np.zeros((d, d)), np.zeros(d)
+        _check(_L().sfmloc_bowtrain_pca64(self._h, *[_ptr(a.reshape(-1), C.c_double) for a in (m, c, v, e)]))
+        return m, c, v, e
+
+    def pca(self):
+        """-> PCAfile.yml's arrays: MeanPCA [1, d], EigenVectorsPCA [d, d], EigenValuesPCA [d, 1] float32"""
+        d = self.size()[1]
+        m, v, e = np.zeros((1, d), np.float32), np.zeros((d, d), np.float32), np.zeros((d, 1), np.float32)
+        _check(_L().sfmloc_bowtrain_pca(self._h, *[_ptr(a.reshape(-1), C.c_float) for a in (m, v, e)]))
+        return m, v, e
+
+    def project(self, mean, eigvec, eigval, n_pca):
+        """the sample -> its first n_pca PCA coordinates divided by the eigenvalues, in place"""
+        d, keep = _bof_desc(np.zeros((1, 1), np.float32), self.size()[1], pca_mean=mean, pca_eigvec=eigvec,
+                            pca_eigval=eigval, n_pca=int(n_pca))
+        _check(_L().sfmloc_bowtrain_project(self._h, C.byref(d)))
+
+    def kmeans(self, K, attempts=3, max_iter=100, eps=float(np.finfo(np.float32).eps), seed=0xFFFFFFFF, want_labels=True,
+               stats=None):
+        """-> (centers [min(K, n), d] f32, labels [n] i32 or None, compactness).  stats (a dict): also "min_dist" [n] f32
+        (the last assignment's) and "iterations" (assignments run, all attempts together)"""
+        n, d = self.size()
+        kc = min(int(K), n)
+        cen = np.zeros((kc, d), np.float32)
+        lab = np.zeros(n, np.int32) if want_labels else None
+        mind = np.zeros(n, np.float32) if stats is not None else None
+        comp, iters = C.c_double(0.0), C.c_uint32(0)
+        _check(_L().sfmloc_bowtrain_kmeans(self._h, int(K), int(attempts), int(max_iter), float(eps), int(seed),
+                                           _ptr(cen.reshape(-1), C.c_float), _ptr(lab, C.c_int32), _ptr(mind, C.c_float),
+                                           C.byref(comp), C.byref(iters)))
+        if stats is not None:
+            stats["min_dist"], stats["iterations"] = mind, int(iters.value)
+        return cen, lab, float(comp.value)
+
+    def close(self):
+        if self._h is not None:
+            _L().sfmloc_bowtrain_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
     def __del__(self):
         try:

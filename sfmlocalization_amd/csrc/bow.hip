@@ -10,6 +10,7 @@
 // for K7) so that ranks and bins can be compared bit for bit.
 #include <math.h>
 
+#include "bof_device.h"
 #include "chain_device.h"
 #include "sfmloc_internal.h"
 
@@ -290,15 +291,7 @@ __global__ __launch_bounds__(256) void k_bof_assign(const float *__restrict__ de
   const int cdim = n_pca > 0 ? n_pca : in_dim;
   float y[128];
   if (n_pca > 0) {
-    for (int d = 0; d < n_pca; ++d) {
-      float acc = 0.0f;
-      for (int i = 0; i < in_dim; ++i) {
-        const float c = x[i] - pca_mean[i];
-        const float pr = c * pca_evec[(size_t)d * in_dim + i];
-        acc = acc + pr;
-      }
-      y[d] = acc / pca_eval[d];
-    }
+    for (int d = 0; d < n_pca; ++d) y[d] = bof_pca_component(x, pca_mean, pca_evec + (size_t)d * in_dim, in_dim, pca_eval[d]);
   } else {
     for (int i = 0; i < in_dim; ++i) y[i] = x[i];
   }
@@ -395,14 +388,7 @@ struct BofAssignTiledBody {
   if (n_pca > 0) {
     for (int e = tid; e < rows * n_pca; e += 256) {
       const int r = e / n_pca, d = e - r * n_pca;
-      const float *x = sx + (size_t)r * in_dim, *ev = sevec + (size_t)d * in_dim;
-      float acc = 0.0f;
-      for (int i = 0; i < in_dim; ++i) {
-        const float c = x[i] - smean[i];
-        const float pr = c * ev[i];
-        acc = acc + pr;
-      }
-      sy[(size_t)r * cdim + d] = acc / seval[d];
+      sy[(size_t)r * cdim + d] = bof_pca_component(sx + (size_t)r * in_dim, smean, sevec + (size_t)d * in_dim, in_dim, seval[d]);
     }
   } else {
     for (int e = tid; e < rows * in_dim; e += 256) sy[e] = sx[e];

@@ -50,6 +50,24 @@ struct ImgBow {
 
 using namespace sfmloc;
 
+// DenseFeatureDetector.cpp:44-69 with the constants of DenseLocalFeatureWrapper.h:32-38: per scale level s a regular grid
+// (x fastest), size = 4 * 1.5^s, class_id = s.  The query chain and the vocabulary trainer (trainbow.hip) both take it.
+void sfmloc::dense_grid_build(int size, std::vector<float> *grid, std::vector<float> *kxy) {
+  float fs = 4.0f;
+  for (int s = 0; s < 4; ++s) {
+    for (int y = 0; y < size; y += 6)
+      for (int x = 0; x < size; x += 6) {
+        const float g[4] = {(float)x, (float)y, fs, (float)s};
+        grid->insert(grid->end(), g, g + 4);
+        if (kxy) {
+          kxy->push_back((float)x);
+          kxy->push_back((float)y);
+        }
+      }
+    fs = fs * 1.5f;
+  }
+}
+
 extern "C" {
 
 void sfmloc_imgbow_destroy(sfmloc_imgbow *p) {
@@ -94,18 +112,8 @@ int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t widt
   if (!rc) rc = dense_gray_plan_create(&ib->plan, (int)width, (int)height, (int)channels, size);
   std::vector<float> grid, kxy;
   if (!rc) {
-    try {  // DenseFeatureDetector.cpp:44-69 with the constants of DenseLocalFeatureWrapper.h:32-38
-      float fs = 4.0f;
-      for (int s = 0; s < 4; ++s) {
-        for (int y = 0; y < size; y += 6)
-          for (int x = 0; x < size; x += 6) {
-            const float g[4] = {(float)x, (float)y, fs, (float)s};
-            grid.insert(grid.end(), g, g + 4);
-            kxy.push_back((float)x);
-            kxy.push_back((float)y);
-          }
-        fs = fs * 1.5f;
-      }
+    try {
+      dense_grid_build(size, &grid, &kxy);
     } catch (const std::bad_alloc &) {
       set_error("sfmloc_imgbow_create: out of host memory");
       rc = SFMLOC_ENOMEM;

@@ -407,6 +407,9 @@ GangMember *akaze_member(Akaze *a);          // the extractor as a gang member (
 // scale space of the image ALREADY in akaze_gray_dev (written on akaze_stream_now) + orientation and M-LDB at the
 // device-resident keypoints d_kin [n x 4] (x, y, size, class_id); asynchronous
 int akaze_compute_resident(Akaze *a, const float *d_kin, unsigned int n, int need_levels /*0: all*/);
+// imgbow.hip: the dense grid of the BoW front end [n x 4] (x, y, size, class_id) and its points [n x 2] (kxy may be null);
+// throws std::bad_alloc
+void dense_grid_build(int size, std::vector<float> *grid, std::vector<float> *kxy);
 
 // acransac.hip
 int launch_fill_log10(double *d_L10, int n, hipStream_t s);
