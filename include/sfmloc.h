@@ -623,6 +623,104 @@ int sfmloc_bowtrain_kmeans(sfmloc_bowtrain *t, uint32_t K, uint32_t attempts, ui
                            uint32_t *iterations);
 
 /* ------------------------------------------------------------------------- */
+/* Re-resection and structure cleanup of a whole sfm_data (OpenMVG_BA/src/adjust_sfm_data.cpp without -c, the call   */
+/* the reference's merge loop makes once per candidate merge).  The sfm_data stays resident on the device: view table, */
+/* intrinsics, poses, landmark X and the observations in CSR by landmark.  Semantics restated (OpenMVG 1.1 points are */
+/* unpinned readings; each says which reading was chosen):                                                             */
+/*   views       a view is resected iff it has more than 10 observations (MINIMUM_VIEW_NUM_TO_ESTIMATAE_CAMERA_POSE, */
+/*               test ">", :118); the others are left untouched and the tool warns "there is/are frames with too few  */
+/*               matches" (:148-150).  Its correspondences are (obs.x, X) in ascending landmark id (std::map order of */
+/*               Landmarks, :100-107), built on the device by a stable radix sort of the observations by view.        */
+/*   raw pixels  (quirk kept) resection_data.pt2D holds the RAW obs.x (:107-115); the undistorted pt2D of :125-131 is   */
+/*               never used, so P3P gets raw pixels and K = (f, ppx, ppy) of the view's intrinsic even for            */
+/*               pinhole_radial_k3.                                                                                    */
+/*   resection   K5 (SfM_Localizer::Localize: P3P AC-RANSAC, params.p3p_max_iteration = 4096, error_max infinite) with */
+/*               its own gate vec_inliers > 2.5 * 3, i.e. >= 8 inliers (params.min_inliers = 7; the localiser's       */
+/*               MINUM_NUMBER_OF_INLIER_RESECTION does not apply; params.min_resection_points = 10: the view rule).   */
+/*               The sampling stream is the view's id_view, so a view's result does not depend on the batch.          */
+/*   success     pose[id_pose] = Pose3(R, -R^T t) of KRt_From_P(P) (:138-142), inserted if the pose id had none.      */
+/*               Views sharing a pose id: the last view in ascending id wins (the reference races, :91).              */
+/*   limit       (divergence) a view with more than 65 536 observations is refused (SFMLOC_ECAP): its list must fit  */
+/*               a K5 context's 2D-3D buffers.  The reference has no such limit.                                      */
+/*   failure     (divergence) the reference stores a pose built from an uninitialised Mat34 (Localize never sets the */
+/*               projection matrix on failure); here the view keeps its input pose, or stays without one.             */
+/*   residual    RemoveOutliers_PixelResidualError(4.0): an observation goes when                                     */
+/*               sqrt(dx*dx + dy*dy) > 4.0, (dx, dy) = obs.x - cam2ima(add_disto(hnormalized(R (X - C)))) of its     */
+/*               view's pose and intrinsic; a landmark left with fewer than 2 observations goes.  Arithmetic (f64,     */
+/*               unfused, in this order): d = X - C; Xc_i = (R_i0 d0 + R_i1 d1) + R_i2 d2; p = (Xc0 / Xc2, Xc1 / Xc2);*/
+/*               radial: r2 = p0 p0 + p1 p1, r4 = r2 r2, r6 = r4 r2, p *= ((1 + k1 r2) + k2 r4) + k3 r6;           */
+/*               proj = f p + pp.  An observation whose view has no pose is an error (GetPoseOrDie throws).          */
+/*   angle       RemoveOutliers_AngleError(2.0): a landmark goes when the largest angle over all pairs of its        */
+/*               remaining observations is < 2 degrees.  Reading chosen: the bearing undistorts first (get_ud_pixel, */
+/*               the bisection of geom_device.h), b = (u, v, 1) with (u, v) = ((x - ppx) / f, (y - ppy) / f),         */
+/*               normalised by sqrt((u u + v v) + 1); ray = R^T b (ray_i = (R_0i b0 + R_1i b1) + R_2i b2); per pair */
+/*               c = dot / (|r1| |r2|) (dot and squared norms summed x, y, z in order), clamped as OpenMVG's         */
+/*               clamp does, max(lo, min(c, hi)) with lo = -1 + 1e-8, hi = 1 - 1e-8 (a NaN cosine becomes lo: 180    */
+/*               degrees, the track stays); the landmark keeps the minimum c and goes when acos(c) * 180 / pi < 2.    */
+/*               (A NaN residual norm is not > 4.0: the observation stays.)                                          */
+/*   unstable    (-r=1) eraseUnstablePosesAndObservations(6, 2): erase every pose with fewer than 6 observations     */
+/*               (counted per id_pose; a pose nobody observes has 0), then every observation whose view's pose is    */
+/*               gone and every landmark left with fewer than 2; repeat while observations were removed.            */
+/* No float atomics and no order-dependent atomics: two runs give the same bits.                                        */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_sfm_desc {
+  uint32_t n_views;
+  const uint32_t *view_id;         /* [n_views] id_view, strictly ascending (Views is a std::map) */
+  const uint32_t *view_intrinsic;  /* [n_views] index into the intrinsic table */
+  const uint32_t *view_pose;       /* [n_views] index into the pose table (the view's id_pose) */
+  uint32_t n_intrinsics;
+  const uint32_t *intrinsic_type;  /* [n_intrinsics] 0 pinhole, 3 pinhole_radial_k3; any other: SFMLOC_EIO */
+  const double *intrinsic;         /* [n_intrinsics*6] focal, ppx, ppy, k1, k2, k3 (zeros for pinhole) */
+  uint32_t n_poses;                /* the pose table: every extrinsic key and every view's id_pose, ascending id */
+  const uint8_t *pose_valid;       /* [n_poses] 1 = the input has this extrinsic */
+  const double *pose_R;            /* [n_poses*9] rotation, row major */
+  const double *pose_C;            /* [n_poses*3] centre */
+  uint32_t n_landmarks;
+  const uint32_t *landmark_id;     /* [n_landmarks] strictly ascending (Landmarks is a std::map) */
+  const double *landmark_X;        /* [n_landmarks*3] */
+  const uint64_t *obs_off;         /* [n_landmarks+1] CSR by landmark, obs_off[0] = 0 */
+  const uint32_t *obs_view;        /* [n_obs] view index (into the view table) */
+  const double *obs_x;             /* [n_obs*2] pixel */
+} sfmloc_sfm_desc;
+
+typedef struct sfmloc_sfm_view_result {
+  int32_t ran;         /* 1 = resected (more than 10 observations) */
+  int32_t ok;          /* 1 = Localize succeeded (>= 8 inliers): the view's pose was replaced */
+  int32_t n_obs;       /* correspondences of the view */
+  int32_t n_inliers;   /* AC-RANSAC's inlier count, success or not (0 when no model has a negative NFA) */
+  int32_t iterations;  /* AC-RANSAC iterations run */
+  int32_t reserved;
+  double error_max, nfa;
+  double P[12];        /* K [R|t] of AC-RANSAC's best model, success or not (zeros without inliers) */
+  double R[9], center[3];  /* KRt_From_P(P), R and -R^T t: only when ok (zeros otherwise; the reference would store
+                              a pose of an uninitialised matrix, see "failure") */
+} sfmloc_sfm_view_result;
+
+typedef struct sfmloc_sfm sfmloc_sfm;
+/* params of the tool: sfmloc_default_params + min_resection_points 10, min_inliers 7, p3p_max_iteration 4096 */
+void sfmloc_sfm_default_params(sfmloc_params *p);
+int sfmloc_sfm_create(const sfmloc_sfm_desc *desc, const sfmloc_params *params, sfmloc_sfm **out);
+void sfmloc_sfm_destroy(sfmloc_sfm *h);
+/* re-resects every view with more than 10 observations (gang sessions of 32 contexts); n_ran / n_ok may be NULL */
+int sfmloc_sfm_resect(sfmloc_sfm *h, uint32_t *n_ran, uint32_t *n_ok);
+int sfmloc_sfm_resect_read(const sfmloc_sfm *h, sfmloc_sfm_view_result *out /*[n_views]*/);
+/* the inliers of view k as indices into its correspondence list (ascending landmark id), AC-RANSAC order: for every
+ * view that ran, a failed one included (its best model's n_inliers inliers); empty for a view that did not run */
+int sfmloc_sfm_resect_inliers(const sfmloc_sfm *h, uint32_t k, uint32_t *idx, uint32_t cap, uint32_t *n);
+/* residual + angle filters (+ the unstable-pose loop when rm_unstable); counts = landmarks before, after the residual
+ * filter, after the angle filter, after cleanup.  SFMLOC_EINVAL (text names the view) when an observation's view has
+ * no pose. */
+int sfmloc_sfm_clean(sfmloc_sfm *h, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts /*[4]*/);
+/* poses [n_poses] (valid, R, C) and keep masks [n_obs] / [n_landmarks]; any pointer may be NULL */
+int sfmloc_sfm_read(sfmloc_sfm *h, uint8_t *pose_valid, double *pose_R, double *pose_C, uint8_t *obs_keep,
+                    uint8_t *landmark_keep);
+/* debug: residual norm per observation (NaN where not evaluated), minimum clamped cosine per landmark (NaN where the
+ * angle filter did not look at it) */
+int sfmloc_sfm_debug_read(sfmloc_sfm *h, double *residual, double *min_cos);
+/* host only: parse a JSON file and write it back as Python's json.dump does (the tool's writer) */
+int sfmloc_sfm_json_rewrite(const char *in_path, const char *out_path);
+
+/* ------------------------------------------------------------------------- */
 /* Map-side matching: the reference's matchAKAZE /         */
 /* trackAKAZE on the same kernels.  Views are addressed by their index in the  */
 /* map's view table (ascending view id).                                       */

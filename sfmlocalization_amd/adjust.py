@@ -1,0 +1,228 @@
+"""OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) without -c, over the C ABI: the call the reference's merge loop makes
+once per candidate merge (hulo_sfm/sfmMergeGraph.py:297, hulo_bow/sfmMergeGraphBOW.py:226,
+hulo_ibeacon/sfmMergeGraphIBeacon.py:322).
+
+    python -m sfmlocalization_amd.adjust <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [--device=0]
+
+Every view with more than 10 observations is re-resected on the device, <folder of sfm_data>/sfm_data_b4bd.json is
+written with the new poses and the structure untouched, the structure is cleaned (residual 4 px, angle 2 degrees, the
+unstable poses with -r=1) and the result goes to sfm_data_out (in place works).  Both files are json.dump of the
+document: views, intrinsics, root_path and key order as in the input, extrinsics in ascending pose id, control_points
+[].  bin/OpenMVG_BA (csrc/adjust_cli.cpp) is the same program and writes the same bytes.  -c (the Ceres bundle
+adjustment) is not supported yet: refused with status 1, nothing written.  The semantics are stated in include/sfmloc.h.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+RESIDUAL_PX, ANGLE_DEG = 4.0, 2.0          # STRUCTURE_CLEANUP_RESIDUAL_ERROR / _ANGLE_ERROR (adjust_sfm_data.cpp:40-41)
+INTRINSIC_TYPES = {"pinhole": 0, "pinhole_radial_k3": 3}
+UNSUPPORTED_TYPE = 0xFFFFFFFF                # any other intrinsic type (sfmloc_sfm_create refuses it)
+
+USAGE = ("Execute bundle adjustment for sfm_data.json\n"
+         "Usage: OpenMVG_BA [params] sfm_data sfm_data_out\n"
+         "\t-c, --command\n\t\tCommand for order of bundle adjustment (not supported yet: only the default, no BD)\n"
+         "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n")
+
+
+def _u32(v):
+    if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= 0xFFFFFFFF:
+        raise ValueError("malformed id")
+    return v
+
+
+def sfm_arrays(doc):
+    """sfm_data document -> the arrays of sfmloc_sfm_desc, the pose ids of the pose table and the input's extrinsic
+    values (None for a pose id only a view names).  Raises ValueError on what the tool refuses."""
+    views, intrs = doc["views"], doc["intrinsics"]
+    exts, st = doc.get("extrinsics", []), doc.get("structure", [])
+    type_names, intr_index, intr_type, intr = {}, {}, [], []
+    for e in intrs:                        # cereal names a polymorphic type at its first occurrence only
+        val = e["value"]
+        pid = _u32(val["polymorphic_id"]) & 0x7FFFFFFF
+        if "polymorphic_name" in val:
+            type_names[pid] = val["polymorphic_name"]
+        t = type_names.get(pid, "")
+        k = [0.0] * 6
+        if t in INTRINSIC_TYPES:        # (any other type goes to sfmloc_sfm_create, which refuses it: SFMLOC_EIO)
+            data = val["ptr_wrapper"]["data"]
+            pin = data["value0"] if t == "pinhole_radial_k3" else data
+            k = [float(pin["focal_length"]), float(pin["principal_point"][0]), float(pin["principal_point"][1]), 0.0, 0.0,
+                 0.0]
+            if t == "pinhole_radial_k3":
+                k[3:] = [float(x) for x in data["disto_k3"]]
+        intr_index[_u32(e["key"])] = len(intr_type)
+        intr_type.append(INTRINSIC_TYPES.get(t, UNSUPPORTED_TYPE))
+        intr.append(k)
+    ext_by_id = {_u32(e["key"]): e["value"] for e in exts}
+    view_id, view_intr, view_pose_id, view_index = [], [], [], {}
+    for e in views:
+        data = e["value"]["ptr_wrapper"]["data"]
+        vid = _u32(data["id_view"])
+        if view_id and vid <= view_id[-1]:
+            raise ValueError("views are not in ascending id_view")
+        ii = _u32(data["id_intrinsic"])
+        if ii not in intr_index:
+            raise ValueError(f"view {vid}: no intrinsic {ii}")
+        view_index[vid] = len(view_id)
+        view_id.append(vid)
+        view_intr.append(intr_index[ii])
+        view_pose_id.append(_u32(data["id_pose"]))
+    pose_id = sorted(set(ext_by_id) | set(view_pose_id))
+    pose_index = {p: i for i, p in enumerate(pose_id)}
+    pose_valid = np.zeros(len(pose_id), np.uint8)
+    pose_R = np.zeros((len(pose_id), 9))
+    pose_C = np.zeros((len(pose_id), 3))
+    pose_src = []
+    for i, p in enumerate(pose_id):
+        src = ext_by_id.get(p)
+        pose_src.append(src)
+        if src is not None:
+            pose_valid[i] = 1
+            pose_R[i] = np.array(src["rotation"], np.float64).reshape(9)
+            pose_C[i] = np.array(src["center"], np.float64).reshape(3)
+    lm_id, lm_X, obs_off, obs_view, obs_x = [], [], [0], [], []
+    for e in st:
+        lid = _u32(e["key"])
+        if lm_id and lid <= lm_id[-1]:
+            raise ValueError("structure is not in ascending landmark id")
+        lm_id.append(lid)
+        lm_X.append([float(x) for x in e["value"]["X"]])
+        for o in e["value"]["observations"]:
+            vid = _u32(o["key"])
+            if vid not in view_index:
+                raise ValueError(f"landmark {lid}: observation of unknown view {vid}")
+            obs_view.append(view_index[vid])
+            obs_x.append([float(x) for x in o["value"]["x"]])
+        obs_off.append(len(obs_view))
+    arrays = dict(view_id=np.array(view_id, np.uint32), view_intrinsic=np.array(view_intr, np.uint32),
+                  view_pose=np.array([pose_index[p] for p in view_pose_id], np.uint32),
+                  intrinsic_type=np.array(intr_type, np.uint32), intrinsic=np.array(intr, np.float64).reshape(-1, 6),
+                  pose_valid=pose_valid, pose_R=pose_R, pose_C=pose_C, landmark_id=np.array(lm_id, np.uint32),
+                  landmark_X=np.array(lm_X, np.float64).reshape(-1, 3), obs_off=np.array(obs_off, np.uint64),
+                  obs_view=np.array(obs_view, np.uint32), obs_x=np.array(obs_x, np.float64).reshape(-1, 2))
+    return arrays, pose_id, pose_src
+
+
+def _extrinsics(pose_id, pose_src, valid, R, C, replaced):
+    out = []
+    for i, p in enumerate(pose_id):
+        if not valid[i]:
+            continue
+        if pose_src[i] is not None and not replaced[i]:
+            out.append({"key": p, "value": pose_src[i]})
+        else:
+            out.append({"key": p, "value": {"rotation": [[float(x) for x in row] for row in np.asarray(R[i]).reshape(3, 3)],
+                                            "center": [float(x) for x in C[i]]}})
+    return out
+
+
+def _with(doc, **items):
+    out = dict(doc)
+    for k, v in items.items():
+        out[k] = v
+    return out
+
+
+def _write(path, doc):
+    with open(path, "w") as fh:
+        json.dump(doc, fh)
+
+
+def run(in_path, out_path, rm_unstable=False, device=0, log=print):
+    """The tool's body.  Returns 0, or 1 after an error message on stderr."""
+    from . import capi as S
+    log("Start bundle adjustment over sfm_data.json.")
+    log(f"Reading sfm_data.json file : {in_path}")
+    try:
+        with open(in_path) as fh:
+            doc = json.load(fh)
+        arrays, pose_id, pose_src = sfm_arrays(doc)
+    except (OSError, ValueError, KeyError, TypeError, IndexError) as e:
+        print(f"\nThe input sfm_data.json file \"{in_path}\" cannot be read. ({e})", file=sys.stderr)
+        return 1
+    try:
+        h = S.Sfm(**arrays, params=S.sfm_default_params(device=int(device)))
+    except S.SfmlocError as e:
+        print(f"OpenMVG_BA: {e.message}", file=sys.stderr)
+        return 1
+    try:
+        h.resect()
+        res = h.resect_read()
+        replaced = np.zeros(len(pose_id), bool)
+        for k, r in enumerate(res):
+            if r.ok:
+                replaced[arrays["view_pose"][k]] = True
+        if any(not r.ran for r in res):
+            log("Warning: there is/are frames with too few matches.")
+        p = h.read(masks=False)
+        b4 = _with(doc, extrinsics=_extrinsics(pose_id, pose_src, p["pose_valid"], p["pose_R"], p["pose_C"], replaced),
+                   control_points=[])
+        _write(os.path.join(os.path.dirname(in_path), "sfm_data_b4bd.json"), b4)
+        counts = h.clean(RESIDUAL_PX, ANGLE_DEG, rm_unstable)
+        q = h.read(masks=True)
+    except S.SfmlocError as e:
+        print(f"OpenMVG_BA: {e.message}", file=sys.stderr)
+        return 1
+    finally:
+        h.close()
+    log(f"Number of points before cleanup : {counts[0]}")
+    log(f"Number of points residual error : {counts[1]}")
+    log(f"Number of points angle error : {counts[2]}")
+    log(f"Number of points after cleanup : {counts[3]}")
+    off = arrays["obs_off"]
+    structure = []
+    for l, e in enumerate(doc.get("structure", [])):
+        if not q["landmark_keep"][l]:
+            continue
+        obs = [o for j, o in enumerate(e["value"]["observations"]) if q["obs_keep"][int(off[l]) + j]]
+        structure.append(_with(e, value=_with(e["value"], observations=obs)))
+    out = _with(doc, extrinsics=_extrinsics(pose_id, pose_src, q["pose_valid"], p["pose_R"], p["pose_C"], replaced))
+    if "structure" in doc:
+        out["structure"] = structure
+    out["control_points"] = []
+    _write(out_path, out)
+    return 0
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) < 1:
+        sys.stderr.write(USAGE)
+        return 1
+    pos, command, rm_unstable, device = [], "", 0, 0
+    for a in argv:
+        if a in ("-h", "--help"):
+            sys.stderr.write(USAGE)
+            return 1
+        if a.startswith("-c=") or a.startswith("--command="):
+            command = a.split("=", 1)[1]
+        elif a.startswith("-r=") or a.startswith("--rm_unstable="):
+            try:
+                rm_unstable = int(a.split("=", 1)[1])
+            except ValueError:
+                rm_unstable = 0
+        elif a.startswith("--device="):
+            device = int(a.split("=", 1)[1])
+        elif a.startswith("-"):
+            sys.stderr.write(USAGE)
+            return 1
+        else:
+            pos.append(a)
+    if len(pos) < 2 or not pos[0] or not pos[1]:
+        sys.stderr.write(USAGE)
+        return 1
+    if command:
+        print(f"OpenMVG_BA: -c={command}: the bundle adjustment command (-c) is not supported yet; nothing was written",
+              file=sys.stderr)
+        return 1
+
+    def log(s):
+        print(s, flush=True)
+    return run(pos[0], pos[1], rm_unstable=rm_unstable != 0, device=device, log=log)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -17,6 +17,7 @@ class SfmlocError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"sfmloc error {code}: {msg}")
         self.code = code
+        self.message = msg  # the library's text alone (sfmloc_last_error)
 
 
 class Params(C.Structure):
@@ -88,6 +89,22 @@ class ScanInfo(C.Structure):
                 ("desc_fnv1a", C.c_uint64), ("kpt_sum", C.c_double), ("row_landmark_sum", C.c_int64)]
 
 
+class SfmDesc(C.Structure):
+    _fields_ = [("n_views", C.c_uint32), ("view_id", C.POINTER(C.c_uint32)), ("view_intrinsic", C.POINTER(C.c_uint32)),
+                ("view_pose", C.POINTER(C.c_uint32)), ("n_intrinsics", C.c_uint32),
+                ("intrinsic_type", C.POINTER(C.c_uint32)), ("intrinsic", C.POINTER(C.c_double)),
+                ("n_poses", C.c_uint32), ("pose_valid", C.POINTER(C.c_uint8)), ("pose_R", C.POINTER(C.c_double)),
+                ("pose_C", C.POINTER(C.c_double)), ("n_landmarks", C.c_uint32), ("landmark_id", C.POINTER(C.c_uint32)),
+                ("landmark_X", C.POINTER(C.c_double)), ("obs_off", C.POINTER(C.c_uint64)),
+                ("obs_view", C.POINTER(C.c_uint32)), ("obs_x", C.POINTER(C.c_double))]
+
+
+class SfmViewResult(C.Structure):
+    _fields_ = [("ran", C.c_int32), ("ok", C.c_int32), ("n_obs", C.c_int32), ("n_inliers", C.c_int32),
+                ("iterations", C.c_int32), ("reserved", C.c_int32), ("error_max", C.c_double), ("nfa", C.c_double),
+                ("P", C.c_double * 12), ("R", C.c_double * 9), ("center", C.c_double * 3)]
+
+
 class KernelStats(C.Structure):
     _fields_ = [("total_ms", C.c_double * K_COUNT), ("launches", C.c_uint64 * K_COUNT),
                 ("hamming_pairs", C.c_uint64), ("hamming_alg_bytes", C.c_uint64),
@@ -127,6 +144,8 @@ SYMBOLS = [
     "sfmloc_bowtrain_create", "sfmloc_bowtrain_destroy", "sfmloc_bowtrain_reset", "sfmloc_bowtrain_add_rows",
     "sfmloc_bowtrain_add_image", "sfmloc_bowtrain_size", "sfmloc_bowtrain_read", "sfmloc_bowtrain_pca64",
     "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
+    "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
+    "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
 ]
 
 _bound = False
@@ -348,6 +367,19 @@ def _L():
         L.sfmloc_bowtrain_project.argtypes = [C.c_void_p, C.POINTER(BofDesc)]
         L.sfmloc_bowtrain_kmeans.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, F32P,
                                              C.POINTER(C.c_int32), F32P, F64P, U32P]
+        U8P = C.POINTER(C.c_uint8)
+        L.sfmloc_sfm_default_params.restype = None
+        L.sfmloc_sfm_default_params.argtypes = [C.POINTER(Params)]
+        L.sfmloc_sfm_create.argtypes = [C.POINTER(SfmDesc), C.POINTER(Params), C.POINTER(C.c_void_p)]
+        L.sfmloc_sfm_destroy.restype = None
+        L.sfmloc_sfm_destroy.argtypes = [C.c_void_p]
+        L.sfmloc_sfm_resect.argtypes = [C.c_void_p, U32P, U32P]
+        L.sfmloc_sfm_resect_read.argtypes = [C.c_void_p, C.POINTER(SfmViewResult)]
+        L.sfmloc_sfm_resect_inliers.argtypes = [C.c_void_p, C.c_uint32, U32P, C.c_uint32, U32P]
+        L.sfmloc_sfm_clean.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]
+        L.sfmloc_sfm_read.argtypes = [C.c_void_p, U8P, F64P, F64P, U8P, U8P]
+        L.sfmloc_sfm_debug_read.argtypes = [C.c_void_p, F64P, F64P]
+        L.sfmloc_sfm_json_rewrite.argtypes = [C.c_char_p, C.c_char_p]
         _bound = True
     return L
 
@@ -1021,6 +1053,115 @@ class BofModel:
     def close(self):
         if self._h is not None:
             _L().sfmloc_bof_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sfm_default_params(**overrides):
+    """sfmloc_sfm_default_params: the re-resection's gates (min_resection_points 10, min_inliers 7, 4 096 iterations)"""
+    p = Params()
+    _L().sfmloc_sfm_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def sfm_json_rewrite(in_path, out_path):
+    """sfmloc_sfm_json_rewrite (host only): the C++ JSON writer of OpenMVG_BA on a parsed file"""
+    _check(_L().sfmloc_sfm_json_rewrite(os.fsencode(in_path), os.fsencode(out_path)))
+
+
+class Sfm:
+    """sfmloc_sfm: OpenMVG_BA's re-resection and structure cleanup on a device-resident sfm_data (include/sfmloc.h states
+    the semantics).  Arrays as sfmloc_sfm_desc: views ascending, a pose table (ascending pose id), landmarks ascending
+    with their observations in CSR (obs_off, obs_view = view index, obs_x)."""
+
+    def __init__(self, view_id, view_intrinsic, view_pose, intrinsic_type, intrinsic, pose_valid, pose_R, pose_C,
+                 landmark_id, landmark_X, obs_off, obs_view, obs_x, params=None):
+        self._h = None
+        a = self._keep = dict(
+            view_id=np.ascontiguousarray(view_id, np.uint32), view_intrinsic=np.ascontiguousarray(view_intrinsic, np.uint32),
+            view_pose=np.ascontiguousarray(view_pose, np.uint32), intrinsic_type=np.ascontiguousarray(intrinsic_type, np.uint32),
+            intrinsic=np.ascontiguousarray(intrinsic, np.float64).reshape(-1, 6),
+            pose_valid=np.ascontiguousarray(pose_valid, np.uint8), pose_R=np.ascontiguousarray(pose_R, np.float64).reshape(-1, 9),
+            pose_C=np.ascontiguousarray(pose_C, np.float64).reshape(-1, 3),
+            landmark_id=np.ascontiguousarray(landmark_id, np.uint32),
+            landmark_X=np.ascontiguousarray(landmark_X, np.float64).reshape(-1, 3),
+            obs_off=np.ascontiguousarray(obs_off, np.uint64), obs_view=np.ascontiguousarray(obs_view, np.uint32),
+            obs_x=np.ascontiguousarray(obs_x, np.float64).reshape(-1, 2))
+        d = SfmDesc()
+        d.n_views, d.n_intrinsics = len(a["view_id"]), len(a["intrinsic_type"])
+        d.n_poses, d.n_landmarks = len(a["pose_valid"]), len(a["landmark_id"])
+        for f, t in (("view_id", C.c_uint32), ("view_intrinsic", C.c_uint32), ("view_pose", C.c_uint32),
+                     ("intrinsic_type", C.c_uint32), ("intrinsic", C.c_double), ("pose_valid", C.c_uint8),
+                     ("pose_R", C.c_double), ("pose_C", C.c_double), ("landmark_id", C.c_uint32),
+                     ("landmark_X", C.c_double), ("obs_off", C.c_uint64), ("obs_view", C.c_uint32), ("obs_x", C.c_double)):
+            setattr(d, f, _ptr(a[f].reshape(-1) if a[f].size else np.zeros(1, a[f].dtype), t))
+        self.n_views, self.n_poses, self.n_landmarks = d.n_views, d.n_poses, d.n_landmarks
+        self.n_obs = int(a["obs_off"][-1])
+        h = C.c_void_p()
+        _check(_L().sfmloc_sfm_create(C.byref(d), C.byref(params if params is not None else sfm_default_params()),
+                                      C.byref(h)))
+        self._h = h
+
+    def resect(self):
+        """-> (views resected, views whose pose was replaced)"""
+        ran, ok = C.c_uint32(0), C.c_uint32(0)
+        _check(_L().sfmloc_sfm_resect(self._h, C.byref(ran), C.byref(ok)))
+        return int(ran.value), int(ok.value)
+
+    def resect_read(self):
+        """-> list of SfmViewResult, one per view"""
+        out = (SfmViewResult * self.n_views)()
+        _check(_L().sfmloc_sfm_resect_read(self._h, out))
+        return list(out)
+
+    def resect_inliers(self, k):
+        n = C.c_uint32(0)
+        _check(_L().sfmloc_sfm_resect_inliers(self._h, int(k), None, 0, C.byref(n)))
+        idx = np.zeros(max(1, n.value), np.uint32)
+        _check(_L().sfmloc_sfm_resect_inliers(self._h, int(k), _ptr(idx, C.c_uint32), idx.size, C.byref(n)))
+        return idx[:n.value].copy()
+
+    def clean(self, residual_px=4.0, angle_deg=2.0, rm_unstable=False):
+        """-> the four landmark counts: before, after the residual filter, after the angle filter, after cleanup"""
+        counts = (C.c_uint64 * 4)()
+        _check(_L().sfmloc_sfm_clean(self._h, float(residual_px), float(angle_deg), 1 if rm_unstable else 0, counts))
+        return [int(c) for c in counts]
+
+    def read(self, masks=True):
+        """-> dict(pose_valid, pose_R [n,3,3], pose_C [n,3], obs_keep, landmark_keep) (masks after clean())"""
+        pv = np.zeros(max(1, self.n_poses), np.uint8)
+        R = np.zeros((max(1, self.n_poses), 9))
+        Cc = np.zeros((max(1, self.n_poses), 3))
+        ok_ = np.zeros(max(1, self.n_obs), np.uint8) if masks else None
+        lk = np.zeros(max(1, self.n_landmarks), np.uint8) if masks else None
+        _check(_L().sfmloc_sfm_read(self._h, _ptr(pv, C.c_uint8), _ptr(R, C.c_double), _ptr(Cc, C.c_double),
+                                    _ptr(ok_, C.c_uint8), _ptr(lk, C.c_uint8)))
+        out = {"pose_valid": pv[:self.n_poses].astype(bool), "pose_R": R[:self.n_poses].reshape(-1, 3, 3),
+               "pose_C": Cc[:self.n_poses]}
+        if masks:
+            out["obs_keep"] = ok_[:self.n_obs].astype(bool)
+            out["landmark_keep"] = lk[:self.n_landmarks].astype(bool)
+        return out
+
+    def debug_read(self):
+        """-> (residual norm per observation, minimum clamped cosine per landmark); NaN where not evaluated"""
+        res = np.zeros(max(1, self.n_obs))
+        mc = np.zeros(max(1, self.n_landmarks))
+        _check(_L().sfmloc_sfm_debug_read(self._h, _ptr(res, C.c_double), _ptr(mc, C.c_double)))
+        return res[:self.n_obs], mc[:self.n_landmarks]
+
+    def close(self):
+        if self._h:
+            _L().sfmloc_sfm_destroy(self._h)
             self._h = None
 
     def __del__(self):

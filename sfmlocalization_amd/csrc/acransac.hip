@@ -3774,9 +3774,10 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.pair_qfeat = c->d_pair_qfeat;
   A.pair_landmark = c->d_pair_landmark;
   A.inlier_idx = c->d_inlier_idx;
-  A.focal = m->focal;
-  A.ppx = m->ppx;
-  A.ppy = m->ppy;
+  // (a context that resects map views (adjust.hip) carries the view's own intrinsic; the query path uses the map's)
+  A.focal = c->p3p_own_K ? c->p3p_K[0] : m->focal;
+  A.ppx = c->p3p_own_K ? c->p3p_K[1] : m->ppx;
+  A.ppy = c->p3p_own_K ? c->p3p_K[2] : m->ppy;
   A.max_iteration = m->params.p3p_max_iteration;
   A.min_resection_points = m->params.min_resection_points;
   A.min_inliers = m->params.min_inliers;
@@ -3806,7 +3807,7 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.adapt_quarters = env_quarters;
   A.adapt_floor = env_floor;
   A.seed = m->params.seed;
-  A.stream = 0;
+  A.stream = c->p3p_stream;  // the AC-RANSAC sampling stream: 0 on the query path, the view id in adjust.hip
   return A;
 }
 

@@ -1,0 +1,789 @@
+// sfmloc_sfm: OpenMVG_BA without -c (OpenMVG_BA/src/adjust_sfm_data.cpp:89-155,245-260) on a device-resident
+// sfm_data -- every view re-resected with K5, then the structure cleaned.  The semantics are stated in
+// include/sfmloc.h; the kernels below name the paragraph of that statement they implement.
+//
+//   transpose   the observations (CSR by landmark) become per-view correspondence lists in ascending landmark id: a
+//               stable LSD radix sort of the observation indices by view index, 8 bits per pass.  Each pass is a
+//               per-block digit histogram, one exclusive scan over (digit, block) and a scatter whose rank inside the
+//               block comes from wave ballots -- no atomic decides a position, so two runs give the same lists.
+//   resection   the lists go straight into the 2D-3D buffers of K5's contexts (k_adj_fill stands where
+//               k_match_set_finish stands on the query path) and K5 runs unchanged: init, rounds, finish; 32 views per
+//               gang session, the view's id_view as the sampling stream and its own intrinsic.
+//   cleanup     f64, unfused (the library's -ffp-contract=off): residual per observation, the clamped cosine of every
+//               pair of a landmark's remaining observations (minimum kept), and the -r fixed point as one workgroup's
+//               loop over pose counts (integer atomics: a count does not depend on order).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "geom_device.h"
+#include "sfm_json.h"
+#include "sfmloc_internal.h"
+
+namespace sfmloc {
+namespace {
+
+constexpr int kRadixBlock = 1024;           // elements per block of a radix pass (16 waves)
+constexpr uint32_t kAdjGang = 32;           // contexts per gang session (kGangMembers)
+constexpr uint32_t kAdjMaxViewObs = 65536;  // a view's list must fit a context's 2D-3D buffers (make_ctx: 65 536)
+
+struct Sfm {
+  int device = 0;
+  sfmloc_params params{};
+  hipStream_t s = nullptr;
+  uint32_t n_views = 0, n_intr = 0, n_poses = 0, n_lm = 0;
+  uint64_t n_obs = 0;
+  // host copies of what the host-side rules need (the pose check of the cleanup, the per-view launches)
+  std::vector<uint32_t> h_view_id, h_view_intr, h_view_pose, h_intr_type;
+  std::vector<double> h_intr;
+  std::vector<uint8_t> h_pose_valid;
+  std::vector<double> h_pose_R, h_pose_C;
+  std::vector<uint64_t> h_obs_off;
+  std::vector<uint32_t> h_obs_view;
+  std::vector<uint32_t> h_view_off;  // per-view list offsets (read back after the device transpose)
+  std::vector<sfmloc_sfm_view_result> res;
+  std::vector<std::vector<uint32_t>> inliers;
+  bool resected = false, cleaned = false;
+  // device
+  uint32_t *d_view_id = nullptr, *d_view_intr = nullptr, *d_view_pose = nullptr, *d_intr_type = nullptr;
+  double *d_intr = nullptr;
+  uint8_t *d_pose_valid = nullptr;
+  double *d_pose_R = nullptr, *d_pose_C = nullptr;
+  uint32_t *d_lm_id = nullptr;
+  double *d_lm_X = nullptr;
+  uint64_t *d_obs_off = nullptr;
+  uint32_t *d_obs_view = nullptr, *d_obs_lm = nullptr;
+  double *d_obs_x = nullptr;
+  uint32_t *d_vlist = nullptr, *d_vkey = nullptr, *d_view_off = nullptr, *d_hist = nullptr;
+  uint32_t *d_tmp_k = nullptr, *d_tmp_v = nullptr;
+  double *d_res = nullptr, *d_ray = nullptr, *d_mincos = nullptr;
+  uint8_t *d_obs_keep = nullptr, *d_lm_stage = nullptr;
+  uint32_t *d_pose_cnt = nullptr, *d_passes = nullptr;
+  // K5's contexts hang off a map without descriptors: its log10 table, parameters and launch heuristics
+  sfmloc_map *map = nullptr;
+  std::vector<sfmloc_context *> ctx;
+};
+
+template <class T>
+int sfm_alloc(T **p, size_t n) {
+  SFM_HIP(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
+  return SFMLOC_OK;
+}
+template <class T>
+int sfm_upload(T **p, const T *h, size_t n, hipStream_t s) {
+  int rc = sfm_alloc(p, n);
+  if (rc) return rc;
+  if (n) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+  return SFMLOC_OK;
+}
+
+void sfm_free(Sfm *h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  if (h->s) hipStreamSynchronize(h->s);
+  for (sfmloc_context *c : h->ctx) sfmloc_context_destroy(c);
+  if (h->map) sfmloc_map_destroy(h->map);
+  void *ptrs[] = {h->d_view_id,  h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,     h->d_pose_valid,
+                  h->d_pose_R,   h->d_pose_C,    h->d_lm_id,     h->d_lm_X,      h->d_obs_off,  h->d_obs_view,
+                  h->d_obs_lm,   h->d_obs_x,     h->d_vlist,     h->d_vkey,      h->d_view_off, h->d_hist,
+                  h->d_tmp_k,    h->d_tmp_v,     h->d_res,       h->d_ray,       h->d_mincos,   h->d_obs_keep,
+                  h->d_lm_stage, h->d_pose_cnt,  h->d_passes};
+  for (void *p : ptrs)
+    if (p) hipFree(p);
+  if (h->s) hipStreamDestroy(h->s);
+  delete h;
+}
+
+// ---- transpose: observations by landmark -> per-view lists in ascending landmark id (sfmloc.h "views") -------------
+
+__global__ __launch_bounds__(256) void k_adj_obs_landmark(const uint64_t *__restrict__ obs_off, uint32_t n_lm,
+                                                          uint32_t *__restrict__ obs_lm, uint32_t *__restrict__ vlist) {
+  const uint32_t l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= n_lm) return;
+  for (uint64_t o = obs_off[l]; o < obs_off[l + 1]; ++o) {
+    obs_lm[o] = l;
+    vlist[o] = (uint32_t)o;  // the sort's payload starts as the identity (landmark order)
+  }
+}
+
+// digit histogram of one block of kRadixBlock elements -> hist[digit * nb + block]
+__global__ __launch_bounds__(kRadixBlock) void k_radix_hist(const uint32_t *__restrict__ key, uint32_t n, int shift,
+                                                            uint32_t *__restrict__ hist, uint32_t nb) {
+  __shared__ uint32_t h[256];
+  for (int i = threadIdx.x; i < 256; i += kRadixBlock) h[i] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kRadixBlock + threadIdx.x;
+  if (i < n) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);  // (a count: the same whatever the order)
+  __syncthreads();
+  for (int d = threadIdx.x; d < 256; d += kRadixBlock) hist[(uint32_t)d * nb + blockIdx.x] = h[d];
+}
+
+// exclusive prefix sum of a[0..n) in place: one workgroup, chunks of 1024 in order
+__global__ __launch_bounds__(1024) void k_scan_excl(uint32_t *__restrict__ a, uint32_t n) {
+  __shared__ uint32_t s[1024];
+  __shared__ uint32_t carry;
+  const int t = threadIdx.x;
+  if (t == 0) carry = 0;
+  __syncthreads();
+  for (uint32_t base = 0; base < n; base += 1024) {
+    const uint32_t v = (base + t < n) ? a[base + t] : 0u;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const uint32_t x = t >= off ? s[t - off] : 0u;
+      __syncthreads();
+      s[t] += x;
+      __syncthreads();
+    }
+    if (base + t < n) a[base + t] = carry + s[t] - v;
+    __syncthreads();
+    if (t == 0) carry += s[1023];
+    __syncthreads();
+  }
+}
+
+// stable scatter: an element's place = its digit's offset for this block + the elements of the same digit before it in
+// the block (its wave's lanes below it, from a ballot match over the digit's bits, then the earlier waves' counts)
+__global__ __launch_bounds__(kRadixBlock) void k_radix_scatter(const uint32_t *__restrict__ kin,
+                                                               const uint32_t *__restrict__ vin, uint32_t n, int shift,
+                                                               const uint32_t *__restrict__ off, uint32_t nb,
+                                                               uint32_t *__restrict__ kout, uint32_t *__restrict__ vout) {
+  constexpr int kWaves = kRadixBlock / 64;
+  __shared__ uint32_t wc[kWaves][257];  // (digit 256: the lanes past the end)
+  for (int i = threadIdx.x; i < kWaves * 257; i += kRadixBlock) (&wc[0][0])[i] = 0;
+  __syncthreads();
+  const uint32_t i = blockIdx.x * kRadixBlock + threadIdx.x;
+  const bool valid = i < n;
+  const uint32_t d = valid ? ((kin[i] >> shift) & 255u) : 256u;
+  unsigned long long mask = ~0ull;
+  for (int b = 0; b < 9; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const unsigned long long bb = __ballot(bit);
+    mask &= bit ? bb : ~bb;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  const uint32_t rank = (uint32_t)__popcll(mask & below);
+  if ((mask & below) == 0ull) wc[w][d] = (uint32_t)__popcll(mask);  // the lowest lane of each digit group
+  __syncthreads();
+  if (!valid) return;
+  uint32_t r = rank;
+  for (int ww = 0; ww < w; ++ww) r += wc[ww][d];
+  const uint32_t dst = off[d * nb + blockIdx.x] + r;
+  kout[dst] = kin[i];
+  vout[dst] = vin[i];
+}
+
+// view_off[v] = first position of view v in the sorted keys (lower bound), v = 0..n_views
+__global__ __launch_bounds__(256) void k_adj_view_off(const uint32_t *__restrict__ key, uint32_t n, uint32_t n_views,
+                                                      uint32_t *__restrict__ view_off) {
+  const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+  if (v > n_views) return;
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (key[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  view_off[v] = lo;
+}
+
+// ---- resection: a view's list into a context's 2D-3D buffers (sfmloc.h "raw pixels": obs.x as it is) -------------
+struct AdjFillBody {
+  static constexpr int kGangThreads = 256;
+  static __device__ __forceinline__ void run(const uint32_t *vlist, const uint32_t *view_off, uint32_t v,
+                                             const uint32_t *obs_lm, const double *obs_x, const double *lm_X,
+                                             const uint32_t *lm_id, uint32_t *ms_n, uint32_t *ms_qfeat,
+                                             uint32_t *ms_landmark, double *pt2d, double *pt3d) {
+    const uint32_t b = view_off[v], n = view_off[v + 1] - b;
+    for (uint32_t k = threadIdx.x; k < n; k += 256) {
+      const uint32_t o = vlist[b + k], l = obs_lm[o];
+      pt2d[2 * k] = obs_x[2 * (size_t)o];
+      pt2d[2 * k + 1] = obs_x[2 * (size_t)o + 1];
+      pt3d[3 * k] = lm_X[3 * (size_t)l];
+      pt3d[3 * k + 1] = lm_X[3 * (size_t)l + 1];
+      pt3d[3 * k + 2] = lm_X[3 * (size_t)l + 2];
+      ms_qfeat[k] = k;  // the inlier pairs then name positions in the view's list
+      ms_landmark[k] = lm_id[l];
+    }
+    if (threadIdx.x == 0) *ms_n = n;
+  }
+};
+__global__ __launch_bounds__(256) void k_adj_fill(const uint32_t *vlist, const uint32_t *view_off, uint32_t v,
+                                                  const uint32_t *obs_lm, const double *obs_x, const double *lm_X,
+                                                  const uint32_t *lm_id, uint32_t *ms_n, uint32_t *ms_qfeat,
+                                                  uint32_t *ms_landmark, double *pt2d, double *pt3d) {
+  AdjFillBody::run(vlist, view_off, v, obs_lm, obs_x, lm_X, lm_id, ms_n, ms_qfeat, ms_landmark, pt2d, pt3d);
+}
+
+// ---- cleanup --------------------------------------------------------------------------------------------------------
+
+// per observation: the residual norm (sfmloc.h "residual") and the world ray with its norm (sfmloc.h "angle")
+__global__ __launch_bounds__(256) void k_adj_residual(uint64_t n_obs, const uint32_t *__restrict__ obs_lm,
+                                                      const uint32_t *__restrict__ obs_view, const double *__restrict__ obs_x,
+                                                      const double *__restrict__ lm_X, const uint32_t *__restrict__ view_intr,
+                                                      const uint32_t *__restrict__ view_pose,
+                                                      const uint32_t *__restrict__ intr_type, const double *__restrict__ intr,
+                                                      const double *__restrict__ pose_R, const double *__restrict__ pose_C,
+                                                      double thr, double *__restrict__ res, double *__restrict__ ray,
+                                                      uint8_t *__restrict__ keep) {
+  const uint64_t o = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= n_obs) return;
+  const uint32_t l = obs_lm[o], v = obs_view[o];
+  const uint32_t pi = view_pose[v], ii = view_intr[v];
+  const double *R = pose_R + 9 * (size_t)pi;
+  const double *C = pose_C + 3 * (size_t)pi;
+  const double *K = intr + 6 * (size_t)ii;
+  const bool radial = intr_type[ii] == 3;
+  const double f = K[0], ppx = K[1], ppy = K[2];
+  const double x = obs_x[2 * o], y = obs_x[2 * o + 1];
+  // obs.x - cam2ima(add_disto(hnormalized(R (X - C))))
+  const double d0 = lm_X[3 * (size_t)l] - C[0], d1 = lm_X[3 * (size_t)l + 1] - C[1], d2 = lm_X[3 * (size_t)l + 2] - C[2];
+  const double X0 = (R[0] * d0 + R[1] * d1) + R[2] * d2;
+  const double X1 = (R[3] * d0 + R[4] * d1) + R[5] * d2;
+  const double X2 = (R[6] * d0 + R[7] * d1) + R[8] * d2;
+  double p0 = X0 / X2, p1 = X1 / X2;
+  if (radial) {
+    const double r2 = p0 * p0 + p1 * p1;
+    const double r4 = r2 * r2, r6 = r4 * r2;
+    const double rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
+    p0 = p0 * rc;
+    p1 = p1 * rc;
+  }
+  const double ex = x - (f * p0 + ppx), ey = y - (f * p1 + ppy);
+  const double nrm = sqrt(ex * ex + ey * ey);
+  res[o] = nrm;
+  keep[o] = (nrm > thr) ? 0 : 1;
+  // bearing: get_ud_pixel (radial), K^-1 (x, y, 1), normalised, then R^T
+  double ux = x, uy = y;
+  if (radial) geom::ud_pixel_k3(f, ppx, ppy, K[3], K[4], K[5], x, y, &ux, &uy);
+  const double b0 = (ux - ppx) / f, b1 = (uy - ppy) / f, b2 = 1.0;
+  const double bn = sqrt((b0 * b0 + b1 * b1) + b2 * b2);
+  const double c0 = b0 / bn, c1 = b1 / bn, c2 = b2 / bn;
+  const double r0 = (R[0] * c0 + R[3] * c1) + R[6] * c2;
+  const double r1 = (R[1] * c0 + R[4] * c1) + R[7] * c2;
+  const double r2 = (R[2] * c0 + R[5] * c1) + R[8] * c2;
+  ray[4 * o] = r0;
+  ray[4 * o + 1] = r1;
+  ray[4 * o + 2] = r2;
+  ray[4 * o + 3] = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
+}
+
+// per landmark: fewer than 2 observations left -> stage 0 (residual filter); else the minimum clamped cosine over all
+// pairs -> stage 1 when acos(c) * 180 / pi < angle_deg (angle filter), else 3 (kept)
+__global__ __launch_bounds__(256) void k_adj_landmarks(uint32_t n_lm, const uint64_t *__restrict__ obs_off,
+                                                       const uint8_t *__restrict__ keep, const double *__restrict__ ray,
+                                                       double angle_deg, double *__restrict__ mincos,
+                                                       uint8_t *__restrict__ stage) {
+  const uint32_t l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= n_lm) return;
+  const uint64_t a = obs_off[l], b = obs_off[l + 1];
+  uint32_t k = 0;
+  for (uint64_t o = a; o < b; ++o) k += keep[o];
+  if (k < 2) {
+    stage[l] = 0;
+    mincos[l] = geom::q_nan();
+    return;
+  }
+  const double lo = -1.0 + 1.e-8, hi = 1.0 - 1.e-8;
+  double cmin = hi;
+  for (uint64_t i = a; i < b; ++i) {
+    if (!keep[i]) continue;
+    const double *r1 = ray + 4 * i;
+    for (uint64_t j = i + 1; j < b; ++j) {
+      if (!keep[j]) continue;
+      const double *r2 = ray + 4 * j;
+      const double dot = (r1[0] * r2[0] + r1[1] * r2[1]) + r1[2] * r2[2];
+      const double mag = r1[3] * r2[3];
+      double c = dot / mag;
+      const double m = (hi < c) ? hi : c;  // std::max(lo, std::min(c, hi)): a NaN cosine becomes lo (180 degrees)
+      c = (lo < m) ? m : lo;
+      cmin = c < cmin ? c : cmin;
+    }
+  }
+  mincos[l] = cmin;
+  stage[l] = (acos(cmin) * 180.0 / 3.14159265358979323846 < angle_deg) ? 1 : 3;
+}
+
+// eraseUnstablePosesAndObservations(6, 2) as one workgroup's fixed-point loop (sfmloc.h "unstable"); stage 2 = a
+// landmark this loop removed
+__global__ __launch_bounds__(1024) void k_adj_unstable(uint32_t n_lm, const uint64_t *__restrict__ obs_off,
+                                                       const uint32_t *__restrict__ obs_view,
+                                                       const uint32_t *__restrict__ view_pose, uint32_t n_poses,
+                                                       uint8_t *pose_valid, uint32_t *pose_cnt, uint8_t *keep,
+                                                       uint8_t *stage, uint32_t min_pose, uint32_t min_lm,
+                                                       uint32_t *passes) {
+  __shared__ int erased, removed;
+  const uint32_t t = threadIdx.x;
+  uint32_t pass = 0;
+  for (;;) {
+    for (uint32_t p = t; p < n_poses; p += 1024) pose_cnt[p] = 0;
+    __syncthreads();
+    for (uint32_t l = t; l < n_lm; l += 1024) {
+      if (stage[l] != 3) continue;
+      for (uint64_t o = obs_off[l]; o < obs_off[l + 1]; ++o)
+        if (keep[o]) atomicAdd(&pose_cnt[view_pose[obs_view[o]]], 1u);
+    }
+    if (t == 0) {
+      erased = 0;
+      removed = 0;
+    }
+    __syncthreads();
+    ++pass;
+    for (uint32_t p = t; p < n_poses; p += 1024)
+      if (pose_valid[p] && pose_cnt[p] < min_pose) {
+        pose_valid[p] = 0;
+        atomicOr(&erased, 1);
+      }
+    __syncthreads();
+    if (!erased) break;
+    for (uint32_t l = t; l < n_lm; l += 1024) {
+      if (stage[l] != 3) continue;
+      uint32_t k = 0;
+      for (uint64_t o = obs_off[l]; o < obs_off[l + 1]; ++o) {
+        if (!keep[o]) continue;
+        if (!pose_valid[view_pose[obs_view[o]]]) {
+          keep[o] = 0;
+          atomicOr(&removed, 1);
+        } else {
+          ++k;
+        }
+      }
+      if (k < min_lm) stage[l] = 2;
+    }
+    __syncthreads();
+    if (!removed) break;
+  }
+  if (t == 0) *passes = pass;
+}
+
+int sfm_transpose(Sfm *h) {
+  const uint32_t n = (uint32_t)h->n_obs;
+  hipStream_t s = h->s;
+  if (h->n_lm)
+    hipLaunchKernelGGL(k_adj_obs_landmark, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->d_obs_off, h->n_lm,
+                       h->d_obs_lm, h->d_vlist);
+  SFM_HIP(hipGetLastError());
+  if (n) SFM_HIP(hipMemcpyAsync(h->d_vkey, h->d_obs_view, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  int bits = 0;
+  while (bits < 32 && ((h->n_views - 1) >> bits) != 0) ++bits;
+  const uint32_t nb = (n + kRadixBlock - 1) / kRadixBlock;
+  uint32_t *kin = h->d_vkey, *vin = h->d_vlist, *kout = h->d_tmp_k, *vout = h->d_tmp_v;
+  for (int shift = 0; shift < bits && n > 0; shift += 8) {
+    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(kRadixBlock), 0, s, kin, n, shift, h->d_hist, nb);
+    hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, h->d_hist, 256u * nb);
+    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kRadixBlock), 0, s, kin, vin, n, shift, h->d_hist, nb, kout, vout);
+    SFM_HIP(hipGetLastError());
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  if (kin != h->d_vkey) {  // (an odd number of passes: the result is in the scratch pair)
+    std::swap(h->d_vkey, h->d_tmp_k);
+    std::swap(h->d_vlist, h->d_tmp_v);
+  }
+  hipLaunchKernelGGL(k_adj_view_off, dim3((h->n_views + 1 + 255) / 256), dim3(256), 0, s, h->d_vkey, n, h->n_views,
+                     h->d_view_off);
+  SFM_HIP(hipGetLastError());
+  h->h_view_off.assign((size_t)h->n_views + 1, 0);
+  SFM_HIP(hipMemcpyAsync(h->h_view_off.data(), h->d_view_off, ((size_t)h->n_views + 1) * sizeof(uint32_t),
+                         hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  return SFMLOC_OK;
+}
+
+int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *h) {
+  SFM_CHECK(d->n_views > 0 && d->view_id && d->view_intrinsic && d->view_pose, SFMLOC_EINVAL,
+            "sfmloc_sfm_create: no views");
+  SFM_CHECK(d->n_intrinsics > 0 && d->intrinsic_type && d->intrinsic, SFMLOC_EINVAL, "sfmloc_sfm_create: no intrinsics");
+  SFM_CHECK(d->n_poses > 0 && d->pose_valid && d->pose_R && d->pose_C, SFMLOC_EINVAL, "sfmloc_sfm_create: no pose table");
+  SFM_CHECK(d->obs_off && (d->n_landmarks == 0 || (d->landmark_id && d->landmark_X)), SFMLOC_EINVAL,
+            "sfmloc_sfm_create: landmark arrays missing");
+  SFM_CHECK(d->obs_off[0] == 0, SFMLOC_EINVAL, "sfmloc_sfm_create: obs_off[0] must be 0");
+  for (uint32_t l = 0; l < d->n_landmarks; ++l) {
+    SFM_CHECK(d->obs_off[l] <= d->obs_off[l + 1], SFMLOC_EINVAL, "sfmloc_sfm_create: obs_off not monotone at %u", l);
+    SFM_CHECK(l == 0 || d->landmark_id[l - 1] < d->landmark_id[l], SFMLOC_EINVAL,
+              "sfmloc_sfm_create: landmark_id must be strictly ascending at %u", l);
+  }
+  const uint64_t n_obs = d->obs_off[d->n_landmarks];
+  SFM_CHECK(n_obs < (1ull << 31), SFMLOC_EINVAL, "sfmloc_sfm_create: more than 2^31 observations");
+  SFM_CHECK(n_obs == 0 || (d->obs_view && d->obs_x), SFMLOC_EINVAL, "sfmloc_sfm_create: observation arrays missing");
+  for (uint32_t v = 0; v < d->n_views; ++v) {
+    SFM_CHECK(v == 0 || d->view_id[v - 1] < d->view_id[v], SFMLOC_EINVAL,
+              "sfmloc_sfm_create: view_id must be strictly ascending at %u", v);
+    SFM_CHECK(d->view_intrinsic[v] < d->n_intrinsics, SFMLOC_EINVAL,
+              "sfmloc_sfm_create: view %u: intrinsic index out of range", d->view_id[v]);
+    SFM_CHECK(d->view_pose[v] < d->n_poses, SFMLOC_EINVAL, "sfmloc_sfm_create: view %u: pose index out of range",
+              d->view_id[v]);
+  }
+  for (uint32_t i = 0; i < d->n_intrinsics; ++i)
+    SFM_CHECK(d->intrinsic_type[i] == 0 || d->intrinsic_type[i] == 3, SFMLOC_EIO,
+              "sfmloc_sfm_create: intrinsic %u (table index): type %u is not supported (0 pinhole, 3 pinhole_radial_k3)", i, d->intrinsic_type[i]);
+  for (uint64_t o = 0; o < n_obs; ++o)
+    SFM_CHECK(d->obs_view[o] < d->n_views, SFMLOC_EINVAL, "sfmloc_sfm_create: obs_view[%llu] out of range",
+              (unsigned long long)o);
+
+  sfmloc_params p;
+  if (params) p = *params;
+  else sfmloc_sfm_default_params(&p);
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
+  SFM_CHECK(p.device >= 0 && p.device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", p.device, ndev - 1);
+  SFM_HIP(hipSetDevice(p.device));
+  h->device = p.device;
+  h->params = p;
+  h->n_views = d->n_views;
+  h->n_intr = d->n_intrinsics;
+  h->n_poses = d->n_poses;
+  h->n_lm = d->n_landmarks;
+  h->n_obs = n_obs;
+  h->h_view_id.assign(d->view_id, d->view_id + d->n_views);
+  h->h_view_intr.assign(d->view_intrinsic, d->view_intrinsic + d->n_views);
+  h->h_view_pose.assign(d->view_pose, d->view_pose + d->n_views);
+  h->h_intr_type.assign(d->intrinsic_type, d->intrinsic_type + d->n_intrinsics);
+  h->h_intr.assign(d->intrinsic, d->intrinsic + 6 * (size_t)d->n_intrinsics);
+  h->h_pose_valid.assign(d->pose_valid, d->pose_valid + d->n_poses);
+  for (uint8_t &v : h->h_pose_valid) v = v ? 1 : 0;
+  h->h_pose_R.assign(d->pose_R, d->pose_R + 9 * (size_t)d->n_poses);
+  h->h_pose_C.assign(d->pose_C, d->pose_C + 3 * (size_t)d->n_poses);
+  h->h_obs_off.assign(d->obs_off, d->obs_off + (size_t)d->n_landmarks + 1);
+  h->h_obs_view.assign(d->obs_view, d->obs_view + n_obs);
+  SFM_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+  hipStream_t s = h->s;
+  int rc = SFMLOC_OK;
+#define ADJ_TRY(x)     \
+  do {                 \
+    rc = (x);          \
+    if (rc) return rc; \
+  } while (0)
+  ADJ_TRY(sfm_upload(&h->d_view_id, d->view_id, d->n_views, s));
+  ADJ_TRY(sfm_upload(&h->d_view_intr, d->view_intrinsic, d->n_views, s));
+  ADJ_TRY(sfm_upload(&h->d_view_pose, d->view_pose, d->n_views, s));
+  ADJ_TRY(sfm_upload(&h->d_intr_type, d->intrinsic_type, d->n_intrinsics, s));
+  ADJ_TRY(sfm_upload(&h->d_intr, d->intrinsic, 6 * (size_t)d->n_intrinsics, s));
+  ADJ_TRY(sfm_upload(&h->d_pose_valid, h->h_pose_valid.data(), d->n_poses, s));
+  ADJ_TRY(sfm_upload(&h->d_pose_R, d->pose_R, 9 * (size_t)d->n_poses, s));
+  ADJ_TRY(sfm_upload(&h->d_pose_C, d->pose_C, 3 * (size_t)d->n_poses, s));
+  ADJ_TRY(sfm_upload(&h->d_lm_id, d->landmark_id, d->n_landmarks, s));
+  ADJ_TRY(sfm_upload(&h->d_lm_X, d->landmark_X, 3 * (size_t)d->n_landmarks, s));
+  ADJ_TRY(sfm_upload(&h->d_obs_off, d->obs_off, (size_t)d->n_landmarks + 1, s));
+  ADJ_TRY(sfm_upload(&h->d_obs_view, d->obs_view, n_obs, s));
+  ADJ_TRY(sfm_upload(&h->d_obs_x, d->obs_x, 2 * n_obs, s));
+  ADJ_TRY(sfm_alloc(&h->d_obs_lm, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_vlist, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_vkey, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_tmp_k, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_tmp_v, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_hist, 256 * ((n_obs + kRadixBlock - 1) / kRadixBlock)));
+  ADJ_TRY(sfm_alloc(&h->d_view_off, (size_t)d->n_views + 1));
+  ADJ_TRY(sfm_alloc(&h->d_res, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_ray, 4 * n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_obs_keep, n_obs));
+  ADJ_TRY(sfm_alloc(&h->d_mincos, d->n_landmarks));
+  ADJ_TRY(sfm_alloc(&h->d_lm_stage, d->n_landmarks));
+  ADJ_TRY(sfm_alloc(&h->d_pose_cnt, d->n_poses));
+  ADJ_TRY(sfm_alloc(&h->d_passes, 1));
+  ADJ_TRY(sfm_transpose(h));
+  const uint32_t vid0 = 0, voff[2] = {0, 0};
+  sfmloc_map_desc md;
+  memset(&md, 0, sizeof md);
+  md.n_views = 1;
+  md.view_id = &vid0;
+  md.view_off = voff;
+  md.focal = 1.0;
+  ADJ_TRY(sfmloc_map_create(&md, &h->params, &h->map));
+#undef ADJ_TRY
+  h->res.assign(d->n_views, sfmloc_sfm_view_result{});
+  h->inliers.assign(d->n_views, std::vector<uint32_t>());
+  return SFMLOC_OK;
+}
+
+int sfm_ensure_contexts(Sfm *h, uint32_t n) {
+  while (h->ctx.size() < n) {  // the first has a stream of its own, the others work on it (gang members)
+    sfmloc_context *c = nullptr;
+    const int rc = sfmloc_context_create_merge(h->map, h->ctx.empty() ? nullptr : h->ctx[0], &c);
+    if (rc) return rc;
+    h->ctx.push_back(c);
+  }
+  return SFMLOC_OK;
+}
+
+int sfm_resect_impl(Sfm *h, uint32_t *n_ran, uint32_t *n_ok) {
+  std::vector<uint32_t> todo;
+  for (uint32_t k = 0; k < h->n_views; ++k) {
+    const uint32_t n = h->h_view_off[k + 1] - h->h_view_off[k];
+    sfmloc_sfm_view_result &r = h->res[k];
+    memset(&r, 0, sizeof r);
+    r.n_obs = (int32_t)n;
+    h->inliers[k].clear();
+    if (n > 10) {  // MINIMUM_VIEW_NUM_TO_ESTIMATAE_CAMERA_POSE, test ">" (adjust_sfm_data.cpp:118)
+      SFM_CHECK(n <= kAdjMaxViewObs, SFMLOC_ECAP, "view %u has %u observations (at most %u per view)", h->h_view_id[k],
+                n, kAdjMaxViewObs);
+      todo.push_back(k);
+    }
+  }
+  int rc = sfm_ensure_contexts(h, std::min<uint32_t>(kAdjGang, (uint32_t)todo.size()));
+  if (rc) return rc;
+  uint32_t ran = 0, ok = 0;
+  for (size_t g0 = 0; g0 < todo.size(); g0 += kAdjGang) {
+    const uint32_t m = (uint32_t)std::min<size_t>(kAdjGang, todo.size() - g0);
+    for (uint32_t i = 0; i < m; ++i) {  // (a regrowth synchronises: before the session records anything)
+      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
+      const uint32_t k = todo[g0 + i];
+      rc = ctx_p3p_reserve(c, h->h_view_off[k + 1] - h->h_view_off[k]);
+      if (rc) return rc;
+      const double *K = &h->h_intr[6 * (size_t)h->h_view_intr[k]];
+      c->p3p_stream = h->h_view_id[k];  // the view's own sampling stream: independent of the batch
+      c->p3p_own_K = true;
+      c->p3p_K[0] = K[0];
+      c->p3p_K[1] = K[1];
+      c->p3p_K[2] = K[2];
+    }
+    rc = sfmloc_gang_begin(h->ctx.data(), m);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < m && rc == SFMLOC_OK; ++i) {
+      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
+      sfm_launch<AdjFillBody>(c, k_adj_fill, dim3(1), dim3(256), 0, (const uint32_t *)h->d_vlist,
+                              (const uint32_t *)h->d_view_off, todo[g0 + i], (const uint32_t *)h->d_obs_lm,
+                              (const double *)h->d_obs_x, (const double *)h->d_lm_X, (const uint32_t *)h->d_lm_id,
+                              c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark, c->d_pt2d, c->d_pt3d);
+      c->p3p_init_fused = false;  // K5's init reads the count k_adj_fill wrote
+      rc = ctx_resection_begin(c);
+    }
+    const int rc_end = sfmloc_gang_end(h->ctx.data(), m);
+    if (rc) return rc;
+    if (rc_end) return rc_end;
+    std::vector<uint32_t> failed;  // members whose view failed with a non-empty inlier set
+    for (uint32_t i = 0; i < m; ++i) {
+      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
+      const uint32_t k = todo[g0 + i];
+      rc = ctx_resection_wait_done(c);
+      if (rc) return rc;
+      const HostResult *hr = reinterpret_cast<const HostResult *>(c->h_result);
+      const Pose &p = hr->pose;
+      SFM_CHECK((p.status & 4) == 0, SFMLOC_ECAP, "view %u: more correspondences than the P3P workspace holds",
+                h->h_view_id[k]);
+      sfmloc_sfm_view_result &r = h->res[k];
+      r.ran = 1;
+      r.ok = p.ok;
+      r.n_inliers = p.n_inliers;
+      r.iterations = p.iterations;
+      r.error_max = p.error_max;
+      r.nfa = p.nfa;
+      memcpy(r.P, p.P, sizeof r.P);
+      memcpy(r.R, p.R, sizeof r.R);
+      memcpy(r.center, p.center, sizeof r.center);
+      ++ran;
+      const uint32_t ni = p.n_inliers > 0 ? (uint32_t)p.n_inliers : 0u;
+      std::vector<uint32_t> &inl = h->inliers[k];
+      inl.resize(ni);
+      if (!p.ok) {
+        // sfmloc.h "failure": the view keeps its input pose (or stays without one).  K5 publishes no pair list for a
+        // failed query; its inlier set is the best model's list, read after the gang's last wait (below)
+        if (ni) failed.push_back(i);
+        continue;
+      }
+      ++ok;
+      if (c->p3p_cap > (uint32_t)kP3pMaxN)  // (a regrown workspace keeps its pair lists outside the result record)
+        SFM_HIP(hipMemcpy(inl.data(), c->d_pair_qfeat, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      else
+        memcpy(inl.data(), hr->pair_qfeat, ni * sizeof(uint32_t));
+      // Pose3(R, -R^T t) (adjust_sfm_data.cpp:138-142); a pose id without an entry gets one
+      const uint32_t pi = h->h_view_pose[k];
+      h->h_pose_valid[pi] = 1;
+      memcpy(&h->h_pose_R[9 * (size_t)pi], p.R, 9 * sizeof(double));
+      memcpy(&h->h_pose_C[3 * (size_t)pi], p.center, 3 * sizeof(double));
+    }
+    // (best_inl holds the final model's inliers in AC-RANSAC order, the list k_p3p_finish turns into pairs on success;
+    // the list positions are the view's correspondence indices.  One wait for the gang's failed views together.)
+    for (uint32_t i : failed) {
+      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
+      std::vector<uint32_t> &inl = h->inliers[todo[g0 + i]];
+      SFM_HIP(hipMemcpyAsync(inl.data(), c->d_best_inl, inl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s));
+    }
+    if (!failed.empty()) {
+      // (h->s is not the contexts' stream: order it after their work, which the waits above have seen finish)
+      SFM_HIP(hipStreamSynchronize(h->s));
+    }
+  }
+  for (sfmloc_context *cc : h->ctx) reinterpret_cast<Ctx *>(cc)->p3p_own_K = false;
+  SFM_HIP(hipMemcpyAsync(h->d_pose_valid, h->h_pose_valid.data(), h->n_poses, hipMemcpyHostToDevice, h->s));
+  SFM_HIP(hipMemcpyAsync(h->d_pose_R, h->h_pose_R.data(), 9 * (size_t)h->n_poses * sizeof(double),
+                         hipMemcpyHostToDevice, h->s));
+  SFM_HIP(hipMemcpyAsync(h->d_pose_C, h->h_pose_C.data(), 3 * (size_t)h->n_poses * sizeof(double),
+                         hipMemcpyHostToDevice, h->s));
+  SFM_HIP(hipStreamSynchronize(h->s));
+  h->resected = true;
+  if (n_ran) *n_ran = ran;
+  if (n_ok) *n_ok = ok;
+  return SFMLOC_OK;
+}
+
+int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
+  // GetPoseOrDie: the first observation (landmark order) whose view has no pose stops the reference's cleanup
+  for (uint32_t l = 0; l < h->n_lm; ++l)
+    for (uint64_t o = h->h_obs_off[l]; o < h->h_obs_off[l + 1]; ++o) {
+      const uint32_t v = h->h_obs_view[o];
+      SFM_CHECK(h->h_pose_valid[h->h_view_pose[v]], SFMLOC_EINVAL,
+                "view %u has observations but no pose (GetPoseOrDie): the structure cannot be cleaned", h->h_view_id[v]);
+    }
+  hipStream_t s = h->s;
+  if (h->n_obs)
+    hipLaunchKernelGGL(k_adj_residual, dim3((unsigned)((h->n_obs + 255) / 256)), dim3(256), 0, s, h->n_obs, h->d_obs_lm,
+                       h->d_obs_view, h->d_obs_x, h->d_lm_X, h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,
+                       h->d_pose_R, h->d_pose_C, residual_px, h->d_res, h->d_ray, h->d_obs_keep);
+  SFM_HIP(hipGetLastError());
+  if (h->n_lm)
+    hipLaunchKernelGGL(k_adj_landmarks, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->n_lm, h->d_obs_off,
+                       h->d_obs_keep, h->d_ray, angle_deg, h->d_mincos, h->d_lm_stage);
+  SFM_HIP(hipGetLastError());
+  if (rm_unstable) {
+    hipLaunchKernelGGL(k_adj_unstable, dim3(1), dim3(1024), 0, s, h->n_lm, h->d_obs_off, h->d_obs_view, h->d_view_pose,
+                       h->n_poses, h->d_pose_valid, h->d_pose_cnt, h->d_obs_keep, h->d_lm_stage, 6u, 2u, h->d_passes);
+    SFM_HIP(hipGetLastError());
+  }
+  std::vector<uint8_t> stage(h->n_lm);
+  if (h->n_lm) SFM_HIP(hipMemcpyAsync(stage.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipMemcpyAsync(h->h_pose_valid.data(), h->d_pose_valid, h->n_poses, hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  if (counts) {
+    counts[0] = h->n_lm;
+    counts[1] = counts[2] = counts[3] = 0;
+    for (uint8_t st : stage) {
+      counts[1] += st >= 1;
+      counts[2] += st >= 2;
+      counts[3] += st == 3;
+    }
+  }
+  h->cleaned = true;
+  return SFMLOC_OK;
+}
+
+}  // namespace
+}  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" {
+
+void sfmloc_sfm_default_params(sfmloc_params *p) {
+  if (!p) return;
+  sfmloc_default_params(p);
+  p->min_resection_points = 10;  // MINIMUM_VIEW_NUM_TO_ESTIMATAE_CAMERA_POSE (adjust_sfm_data.cpp:39,118)
+  p->min_inliers = 7;            // Localize's own gate: vec_inliers > 2.5 * 3
+  p->p3p_max_iteration = 4096;   // Image_Localizer_Match_Data::max_iteration
+}
+
+int sfmloc_sfm_create(const sfmloc_sfm_desc *desc, const sfmloc_params *params, sfmloc_sfm **out) {
+  SFM_CHECK(desc && out, SFMLOC_EINVAL, "sfmloc_sfm_create: null argument");
+  *out = nullptr;
+  Sfm *h = new (std::nothrow) Sfm();
+  SFM_CHECK(h, SFMLOC_ENOMEM, "out of host memory");
+  int rc;
+  try {
+    rc = sfm_create_impl(desc, params, h);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_create: out of host memory");
+    rc = SFMLOC_ENOMEM;
+  }
+  if (rc) {
+    sfm_free(h);
+    return rc;
+  }
+  *out = reinterpret_cast<sfmloc_sfm *>(h);
+  return SFMLOC_OK;
+}
+
+void sfmloc_sfm_destroy(sfmloc_sfm *h) { sfm_free(reinterpret_cast<Sfm *>(h)); }
+
+int sfmloc_sfm_resect(sfmloc_sfm *hh, uint32_t *n_ran, uint32_t *n_ok) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_resect: null handle");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_CHECK(!h->resected && !h->cleaned, SFMLOC_EINVAL, "sfmloc_sfm_resect: runs once, before the cleanup");
+  SFM_HIP(hipSetDevice(h->device));
+  try {
+    return sfm_resect_impl(h, n_ran, n_ok);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_resect: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+}
+
+int sfmloc_sfm_resect_read(const sfmloc_sfm *hh, sfmloc_sfm_view_result *out) {
+  SFM_CHECK(hh && out, SFMLOC_EINVAL, "sfmloc_sfm_resect_read: null argument");
+  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
+  memcpy(out, h->res.data(), h->res.size() * sizeof(sfmloc_sfm_view_result));
+  return SFMLOC_OK;
+}
+
+int sfmloc_sfm_resect_inliers(const sfmloc_sfm *hh, uint32_t k, uint32_t *idx, uint32_t cap, uint32_t *n) {
+  SFM_CHECK(hh && n, SFMLOC_EINVAL, "sfmloc_sfm_resect_inliers: null argument");
+  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
+  SFM_CHECK(k < h->n_views, SFMLOC_EINVAL, "sfmloc_sfm_resect_inliers: view index %u out of range", k);
+  const std::vector<uint32_t> &v = h->inliers[k];
+  *n = (uint32_t)v.size();
+  SFM_CHECK(!idx || cap >= v.size(), SFMLOC_ECAP, "sfmloc_sfm_resect_inliers: %u entries, %zu inliers", cap, v.size());
+  if (idx && !v.empty()) memcpy(idx, v.data(), v.size() * sizeof(uint32_t));
+  return SFMLOC_OK;
+}
+
+int sfmloc_sfm_clean(sfmloc_sfm *hh, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_clean: null handle");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_CHECK(!h->cleaned, SFMLOC_EINVAL, "sfmloc_sfm_clean: runs once");
+  SFM_HIP(hipSetDevice(h->device));
+  return sfm_clean_impl(h, residual_px, angle_deg, rm_unstable, counts);
+}
+
+int sfmloc_sfm_read(sfmloc_sfm *hh, uint8_t *pose_valid, double *pose_R, double *pose_C, uint8_t *obs_keep,
+                    uint8_t *landmark_keep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_read: null handle");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_CHECK(h->cleaned || (!obs_keep && !landmark_keep), SFMLOC_EINVAL,
+            "sfmloc_sfm_read: the keep masks exist after the cleanup");
+  SFM_HIP(hipSetDevice(h->device));
+  if (pose_valid) memcpy(pose_valid, h->h_pose_valid.data(), h->n_poses);
+  if (pose_R) memcpy(pose_R, h->h_pose_R.data(), 9 * (size_t)h->n_poses * sizeof(double));
+  if (pose_C) memcpy(pose_C, h->h_pose_C.data(), 3 * (size_t)h->n_poses * sizeof(double));
+  if (obs_keep && h->n_obs) SFM_HIP(hipMemcpy(obs_keep, h->d_obs_keep, h->n_obs, hipMemcpyDeviceToHost));
+  if (landmark_keep && h->n_lm) {
+    std::vector<uint8_t> st(h->n_lm);
+    SFM_HIP(hipMemcpy(st.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost));
+    for (uint32_t l = 0; l < h->n_lm; ++l) landmark_keep[l] = st[l] == 3 ? 1 : 0;
+  }
+  return SFMLOC_OK;
+}
+
+int sfmloc_sfm_debug_read(sfmloc_sfm *hh, double *residual, double *min_cos) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_debug_read: null handle");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_CHECK(h->cleaned, SFMLOC_EINVAL, "sfmloc_sfm_debug_read: after the cleanup only");
+  SFM_HIP(hipSetDevice(h->device));
+  if (residual && h->n_obs) SFM_HIP(hipMemcpy(residual, h->d_res, h->n_obs * sizeof(double), hipMemcpyDeviceToHost));
+  if (min_cos && h->n_lm) SFM_HIP(hipMemcpy(min_cos, h->d_mincos, h->n_lm * sizeof(double), hipMemcpyDeviceToHost));
+  return SFMLOC_OK;
+}
+
+int sfmloc_sfm_json_rewrite(const char *in_path, const char *out_path) {
+  SFM_CHECK(in_path && out_path, SFMLOC_EINVAL, "sfmloc_sfm_json_rewrite: null argument");
+  try {
+    std::string text, err, out;
+    SFM_CHECK(sfmjson::read_file(in_path, &text), SFMLOC_EIO, "%s: cannot be read", in_path);
+    sfmjson::Value v;
+    SFM_CHECK(sfmjson::parse(text, &v, &err), SFMLOC_EIO, "%s: %s", in_path, err.c_str());
+    sfmjson::dump(v, &out);
+    SFM_CHECK(sfmjson::write_file(out_path, out), SFMLOC_EIO, "%s: cannot be written", out_path);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_json_rewrite: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+  return SFMLOC_OK;
+}
+
+}  // extern "C"

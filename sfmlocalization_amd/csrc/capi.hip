@@ -786,6 +786,9 @@ int ctx_localize_end(Ctx *c, sfmloc_pose *out, uint32_t *pair_qfeat, uint32_t *p
 
 }  // namespace
 
+int ctx_resection_begin(Ctx *c) { return ctx_resection_enqueue(c, true); }
+int ctx_resection_wait_done(Ctx *c) { return ctx_resection_wait(c); }
+
 // gang.h: issue what the members of a gang session have recorded -- the heads of their lists that are the same kernel
 // on the same grid as ONE launch, a head without a partner as a plain launch
 int gang_flush(GangState *g) {

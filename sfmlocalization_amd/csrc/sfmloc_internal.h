@@ -261,6 +261,9 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   bool p3p_small = false;  // this query's P3P rounds go out in the small form (decided when the first ones are queued)
   bool p3p_seq = false;    // this query's AC-RANSAC went out in the sequential form (one launch; acransac.hip k_p3p_seq)
   uint32_t p3p_query_n = 0;  // features of the query K5 is about to run for (ctx_p3p_reserve): launch shape of the rounds
+  uint32_t p3p_stream = 0;   // K5's sampling stream (Philox key): 0 for queries; the view id when adjust.hip resects a view
+  bool p3p_own_K = false;    // K5 uses p3p_K (focal, ppx, ppy) instead of the map's intrinsic (adjust.hip: per view)
+  double p3p_K[3] = {0.0, 0.0, 0.0};
   uint32_t *d_pair_qfeat_big = nullptr, *d_pair_landmark_big = nullptr;
   uint64_t *d_p3p_ws_key = nullptr;
   uint32_t *d_p3p_ws_idx = nullptr;
@@ -436,5 +439,10 @@ int launch_p3p_init(Ctx *c);
 int launch_p3p_round(Ctx *c, int batch);
 int launch_p3p_seq(Ctx *c);     // the sequential form: the query's whole AC-RANSAC in one workgroup (GPU shared)
 int launch_p3p_finish(Ctx *c);
+// capi.hip: K5 on correspondences the caller has already written into the context's 2D-3D buffers (d_ms_n, d_pt2d,
+// d_pt3d, d_ms_qfeat, d_ms_landmark) -- ctx_p3p_reserve first; _begin queues init + rounds + finish, _wait drains
+// the stream and queues more rounds until the state machine is done (the query path's own ctx_resection_* steps)
+int ctx_resection_begin(Ctx *c);
+int ctx_resection_wait_done(Ctx *c);
 
 }  // namespace sfmloc

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/sfmloc.h"
+#include "sfm_json.h"
 
 namespace {
 
@@ -97,41 +98,8 @@ uint32_t draw_index(uint32_t n, float r) {  // a float32 product, truncated, cla
   return k < n ? k : n - 1;
 }
 
-// a double as Python's repr() writes it: the shortest text that reads back as the same double; positional notation for
-// decimal exponents -4 < e <= 16 (with ".0" for an integer), else d[.ddd]e+XX
-std::string py_repr(double v) {
-  if (std::isnan(v)) return "nan";
-  if (std::isinf(v)) return v < 0 ? "-inf" : "inf";
-  if (v == 0.0) return std::signbit(v) ? "-0.0" : "0.0";
-  char buf[64];
-  for (int p = 1; p <= 17; ++p) {
-    snprintf(buf, sizeof buf, "%.*e", p - 1, v);
-    if (strtod(buf, nullptr) == v) break;
-  }
-  std::string s(buf);
-  const bool neg = s[0] == '-';
-  if (neg) s = s.substr(1);
-  const size_t e = s.find('e');
-  const int exp10 = atoi(s.c_str() + e + 1);
-  std::string digits;
-  for (size_t i = 0; i < e; ++i)
-    if (s[i] != '.') digits += s[i];
-  while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
-  const int decpt = exp10 + 1;  // value = 0.d1 d2 ... x 10^decpt
-  std::string out;
-  if (decpt > -4 && decpt <= 16) {
-    if (decpt <= 0) out = "0." + std::string(-decpt, '0') + digits;
-    else if (decpt >= (int)digits.size()) out = digits + std::string(decpt - digits.size(), '0') + ".0";
-    else out = digits.substr(0, decpt) + "." + digits.substr(decpt);
-  } else {
-    out = digits.substr(0, 1);
-    if (digits.size() > 1) out += "." + digits.substr(1);
-    char eb[16];
-    snprintf(eb, sizeof eb, "e%c%02d", exp10 < 0 ? '-' : '+', exp10 < 0 ? -exp10 : exp10);
-    out += eb;
-  }
-  return (neg ? "-" : "") + out;
-}
+// floats as Python's repr() writes them: the one copy shared with OpenMVG_BA's JSON writer
+using sfmjson::py_repr;
 
 // fileio.write_cv_yaml's layout: "%YAML:1.0", then per key an int, a quoted string or an f32 !!opencv-matrix on one line
 struct YamlOut {

@@ -30,6 +30,8 @@ LOCALIZE_PROJECT = "OpenMVGLocalization_AKAZE"          # ReconstructParam.py:35
 EXTRACT_FEATURE_MATCH_PROJECT = "ExtFeatAndMatch"        # ReconstructParam.py:34
 LOCALIZE_PROJECT_PATH = os.path.join(_BIN, LOCALIZE_PROJECT)
 EXTRACT_FEATURE_MATCH_PROJECT_PATH = os.path.join(_BIN, EXTRACT_FEATURE_MATCH_PROJECT)
+BUNDLE_ADJUSTMENT_PROJECT = "OpenMVG_BA"                # ReconstructParam.py:36 (run per merge, sfmMergeGraph.py:297)
+BUNDLE_ADJUSTMENT_PROJECT_PATH = os.path.join(_BIN, BUNDLE_ADJUSTMENT_PROJECT)
 
 
 class LocalizeParam:                                     # hulo_param/LocalizeParam.py:23-35

@@ -1,0 +1,232 @@
+"""OpenMVG_BA twin on the device (sfmloc_sfm, bin/OpenMVG_BA, python -m sfmlocalization_amd.adjust) against the CPU
+statement: the oracle's P3P resection of every view (raw obs.x, ascending landmark id, stream = id_view) and the NumPy
+restatement of the cleanup (adjust_np) on the oracle's poses.  The inputs are those of test_adjust_cpu's margin test."""
+import json
+import os
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+
+import adjust_np as AN  # noqa: E402
+import adjust_scene as AS  # noqa: E402
+import synthdata  # noqa: E402
+from sfmlocalization_amd import adjust  # noqa: E402
+from sfmlocalization_amd import capi as S  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BIN = os.path.join(ROOT, "sfmlocalization_amd", "bin", "OpenMVG_BA")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.fixture(scope="module")
+def scene():
+    from oracle import oracle_c
+    oracle_c.build()
+    doc, m = AS.make_doc()
+    a, _, _ = adjust.sfm_arrays(doc)
+    exp, pv, R, C = AS.oracle_resect(a, oracle_c)
+    return doc, a, exp, pv, R, C, oracle_c
+
+
+def test_resection_matches_oracle(scene):
+    doc, a, exp, pv, R, C, oracle_c = scene
+    h = S.Sfm(**a)
+    ran, ok = h.resect()
+    res = h.resect_read()
+    assert ran == sum(e["ran"] for e in exp) and ok == sum(e["ok"] for e in exp)
+    for k, (r, e) in enumerate(zip(res, exp)):
+        assert bool(r.ran) == e["ran"] and r.n_obs == e["n_obs"], k
+        if not e["ran"]:
+            assert len(h.resect_inliers(k)) == 0
+            continue
+        # every view that ran, failed or not: iterations, NFA, the best model's P, its inliers
+        assert bool(r.ok) == (e["n"] >= 8), k
+        assert r.iterations == e["iters"] and r.nfa == e["nfa"], k
+        np.testing.assert_array_equal(bits(np.array(r.P)), bits(e["P"].ravel()), err_msg=str(k))
+        inl = h.resect_inliers(k)
+        assert len(inl) == r.n_inliers, k
+        if e["n"] > 0:                  # Localize's gate passed: the wrapper's count and list
+            assert r.n_inliers == e["n"], k
+            np.testing.assert_array_equal(inl, e["inliers"])
+        else:                           # below the gate the oracle's count is not reported: its list's prefix
+            assert 0 <= r.n_inliers <= 7, k
+            np.testing.assert_array_equal(inl, e["inl_raw"][:r.n_inliers])
+            assert (r.n_inliers == 0) == (not np.any(e["P"])), k
+        if r.n_inliers > 0:             # errmax is the n_inliers-th smallest residual: pins the count as well
+            assert r.error_max == e["errmax"], k
+        if e["ok"]:
+            np.testing.assert_array_equal(bits(np.array(r.R)), bits(e["R"].ravel()))
+            np.testing.assert_array_equal(bits(np.array(r.center)), bits(e["center"]))
+        else:                           # sfmloc.h: R and centre only on success
+            assert not np.any(np.array(r.R)) and not np.any(np.array(r.center)), k
+    p = h.read(masks=False)
+    np.testing.assert_array_equal(p["pose_valid"], pv)
+    np.testing.assert_array_equal(bits(p["pose_R"].reshape(-1, 9)), bits(R))
+    np.testing.assert_array_equal(bits(p["pose_C"]), bits(C))
+    # skipped and failed views keep their input pose bits
+    for k in AS.FEW_VIEWS + (AS.WEAK_VIEW, AS.FAIL_VIEW):
+        pi = a["view_pose"][k]
+        np.testing.assert_array_equal(bits(p["pose_R"][pi].ravel()), bits(a["pose_R"][pi]))
+        np.testing.assert_array_equal(bits(p["pose_C"][pi]), bits(a["pose_C"][pi]))
+    assert res[AS.FAIL_VIEW].ran and not res[AS.FAIL_VIEW].ok
+    # the raw-pixel quirk: on a radial view the pose is not the one the undistorted points give
+    k = 50
+    idx = AS.view_lists(a)[k]
+    obs_lm = np.repeat(np.arange(len(a["landmark_id"])), np.diff(a["obs_off"].astype(np.int64)))
+    K = a["intrinsic"][a["view_intrinsic"][k]]
+    assert a["intrinsic_type"][a["view_intrinsic"][k]] == 3
+    ud = np.array([AN.ud_pixel_k3(*K, *xy) for xy in a["obs_x"][idx]])
+    u = oracle_c.p3p_localize(ud, a["landmark_X"][obs_lm[idx]], K[0], K[1], K[2], 4096, AS.SEED, stream=int(a["view_id"][k]))
+    assert not np.array_equal(bits(u["P"].ravel()), bits(np.array(res[k].P)))
+    h.close()
+
+
+@pytest.mark.parametrize("rm_unstable", [False, True])
+def test_cleanup_matches_restatement(scene, rm_unstable):
+    doc, a, exp, pv, R, C, _ = scene
+    want = AN.clean(a, pv, R, C, rm_unstable=rm_unstable)
+    h = S.Sfm(**a)
+    h.resect()
+    counts = h.clean(4.0, 2.0, rm_unstable)
+    res, mc = h.debug_read()
+    got = h.read()
+    h.close()
+    print("counts", counts, "restated", want["counts"])
+    np.testing.assert_array_equal(bits(res), bits(want["res"]))
+    fin = np.isfinite(want["min_cos"])
+    np.testing.assert_array_equal(np.isfinite(mc), fin)
+    np.testing.assert_array_equal(bits(mc[fin]), bits(want["min_cos"][fin]))
+    np.testing.assert_array_equal(got["obs_keep"], want["obs_keep"])
+    np.testing.assert_array_equal(got["landmark_keep"], want["landmark_keep"])
+    np.testing.assert_array_equal(got["pose_valid"], want["pose_valid"])
+    assert counts == want["counts"]
+
+
+def test_unstable_two_passes_on_device():
+    """-r=1 whose fixed point needs two erasing passes (adjust_scene.two_pass_case), on the device against adjust_np"""
+    a = AS.two_pass_case()
+    want = AN.clean(a, a["pose_valid"], a["pose_R"], a["pose_C"], rm_unstable=True)
+    assert want["passes"] == 3 and want["pose_valid"].tolist() == [False, False, True, False, True]
+    assert want["counts"] == [26, 26, 26, 20]
+    h = S.Sfm(**a)
+    counts = h.clean(4.0, 2.0, True)
+    res, mc = h.debug_read()
+    got = h.read()
+    h.close()
+    np.testing.assert_array_equal(bits(res), bits(want["res"]))
+    np.testing.assert_array_equal(bits(mc), bits(want["min_cos"]))
+    np.testing.assert_array_equal(got["pose_valid"], want["pose_valid"])
+    np.testing.assert_array_equal(got["obs_keep"], want["obs_keep"])
+    np.testing.assert_array_equal(got["landmark_keep"], want["landmark_keep"])
+    assert counts == want["counts"]
+
+
+def _run(prog, args, cwd):
+    return subprocess.run(prog + args, capture_output=True, text=True, cwd=cwd, timeout=300)
+
+
+def test_whole_tool(scene, tmp_path):
+    doc, a, exp, pv, R, C, _ = scene
+    outs = {}
+    for name, prog in (("cpp", [BIN]), ("py", [sys.executable, "-m", "sfmlocalization_amd.adjust"])):
+        for rm in ("0", "1"):
+            d = tmp_path / f"{name}{rm}"
+            d.mkdir()
+            src = d / "sfm_data.json"
+            src.write_text(json.dumps(doc))
+            r = _run(prog, [str(src), str(d / "out.json"), "-r=" + rm], ROOT)
+            assert r.returncode == 0, r.stderr
+            assert "Warning: there is/are frames with too few matches." in r.stdout
+            assert "Number of points after cleanup :" in r.stdout
+            outs[name, rm] = ((d / "out.json").read_bytes(), (d / "sfm_data_b4bd.json").read_bytes(), r.stdout)
+            # in place, as the merge loop calls it
+            r2 = _run(prog, [str(src), str(src), "-r=" + rm], ROOT)
+            assert r2.returncode == 0, r2.stderr
+            assert src.read_bytes() == outs[name, rm][0]
+    for rm in ("0", "1"):
+        assert outs["cpp", rm][0] == outs["py", rm][0] and outs["cpp", rm][1] == outs["py", rm][1]
+        lines = [[ln for ln in outs[n, rm][2].splitlines() if not ln.startswith("Reading")] for n in ("cpp", "py")]
+        assert lines[0] == lines[1]
+        out = json.loads(outs["cpp", rm][0])
+        b4 = json.loads(outs["cpp", rm][1])
+        assert json.dumps(out) == outs["cpp", rm][0].decode()            # json.dump's bytes
+        for f in ("views", "intrinsics", "root_path", "sfm_data_version"):
+            assert out[f] == doc[f] and b4[f] == doc[f]
+        assert list(out) == list(doc) and out["control_points"] == [] and b4["control_points"] == []
+        assert b4["structure"] == doc["structure"]
+        keys = [e["key"] for e in b4["extrinsics"]]
+        assert keys == sorted(keys)
+        for k, e in enumerate(exp):                                       # the new poses
+            if e["ok"]:
+                ext = next(x for x in b4["extrinsics"] if x["key"] == int(a["view_id"][k]))
+                np.testing.assert_array_equal(bits(np.array(ext["value"]["rotation"]).ravel()), bits(e["R"].ravel()))
+                np.testing.assert_array_equal(bits(np.array(ext["value"]["center"])), bits(e["center"]))
+        want = AN.clean(a, pv, R, C, rm_unstable=rm == "1")
+        assert len(out["structure"]) == want["counts"][3]
+        assert ("Number of points after cleanup : %d" % want["counts"][3]) in outs["cpp", rm][2]
+        ext_keys = {e["key"] for e in out["extrinsics"]}
+        assert (AS.ORPHAN_POSE in ext_keys) == (rm == "0")
+    # two runs, same bytes
+    d = tmp_path / "again"
+    d.mkdir()
+    (d / "sfm_data.json").write_text(json.dumps(doc))
+    assert _run([BIN], [str(d / "sfm_data.json"), str(d / "out.json"), "-r=1"], ROOT).returncode == 0
+    assert (d / "out.json").read_bytes() == outs["cpp", "1"][0]
+
+
+def test_output_localises(tmp_path):
+    """The cleaned map opens with sfmloc_open and localises a query where the input map does.  The localiser reads the
+    landmarks and their observations only.  This map has no planted outliers, but the cleanup still removes landmarks:
+    those with fewer than two observations (synthdata keeps landmarks that one view or none observes) and tracks under
+    2 degrees.  A removed landmark drops out of the query's 2D-3D set, which moves the AC-RANSAC pose a little; the bound
+    is 1 cm / 1e-3 in the rotation, far below the map's scale (metres) and the query's planted 1 px noise.  The test
+    prints how many landmarks went."""
+    m = synthdata.make_map(62, n_views=20, desc_per_view=600, views_per_place=20, landmarks_per_place=500,
+                           obs_per_view=250)
+    sfm_dir, match_dir = tmp_path / "sfm", tmp_path / "matches"
+    synthdata.write_map_to_disk(m, str(sfm_dir), str(match_dir))
+    src = sfm_dir / "sfm_data.json"
+    shutil.copy(src, tmp_path / "orig.json")
+    q = synthdata.make_query(m, 620, n_feat=1500, n_copies=250, outlier_frac=0.2)
+    poses = []
+    for stage in ("before", "after"):
+        if stage == "after":
+            r = _run([BIN], [str(src), str(src), "-r=1"], ROOT)
+            assert r.returncode == 0, r.stderr
+            print("\n".join(ln for ln in r.stdout.splitlines() if ln.startswith("Number of points")))
+        dm = S.Map.open(str(sfm_dir), str(match_dir), S.default_params(ransac_round=25))
+        dq = dm.query(q.desc, q.kpt_xy, q.width, q.height)
+        pose, _, _ = dm.localize(dq)
+        assert pose.ok
+        poses.append((np.array(pose.R).reshape(3, 3), np.array(pose.center)))
+        dq.close()
+        dm.close()
+    print("centre moved by", np.abs(poses[0][1] - poses[1][1]).max(), "rotation by", np.abs(poses[0][0] - poses[1][0]).max())
+    assert np.abs(poses[0][1] - poses[1][1]).max() < 1e-2
+    assert np.abs(poses[0][0] - poses[1][0]).max() < 1e-3
+    assert np.abs(poses[1][1] - q.C_true).max() < 0.2
+
+
+def test_view_without_pose(scene, tmp_path):
+    doc, a, *_ = scene
+    d = json.loads(json.dumps(doc))
+    vid = int(a["view_id"][AS.FEW_VIEWS[0]])
+    d["extrinsics"] = [e for e in d["extrinsics"] if e["key"] != vid]
+    for name, prog in (("cpp", [BIN]), ("py", [sys.executable, "-m", "sfmlocalization_amd.adjust"])):
+        w = tmp_path / name
+        w.mkdir()
+        (w / "sfm_data.json").write_text(json.dumps(d))
+        r = _run(prog, [str(w / "sfm_data.json"), str(w / "out.json")], ROOT)
+        assert r.returncode != 0 and f"view {vid} " in r.stderr, r.stderr
+        assert (w / "sfm_data_b4bd.json").exists() and not (w / "out.json").exists()
