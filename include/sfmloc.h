@@ -78,6 +78,13 @@ typedef struct sfmloc_params {
                                builder's default, ReconstructParam.py:71): every pair that passes the F-matrix AC-RANSAC
                                has its matches replaced by OpenMVG's Geometry_guided_matching under the estimated F
                                (MatchUtils.cpp:413-415) */
+  int k1_mfma;              /* 1 (default) = unsliced scans of a view list (every shortlist scan while the GPU is shared,
+                               long view lists) take their Hamming distances from the matrix cores
+                               (k_hamming_screen_mfma: e2m1 +-1 operands, exact); 0 = the popcount form
+                               (k_hamming_screen_shortlist).  Same matches either way; the full-bank scan, the sliced
+                               scan of a lone query, short queries and exact_rows = 1 are popcount in both settings.
+                               (The field occupies what was tail padding of the struct: size and the offsets of the
+                               other fields are those of ABI version 2.) */
 } sfmloc_params;
 
 void sfmloc_default_params(sfmloc_params *p);
@@ -788,8 +795,12 @@ typedef struct sfmloc_kernel_stats {
   uint64_t hamming_pairs;      /* bank rows x query rows compared since reset */
   uint64_t hamming_alg_bytes;  /* 64*rows + 64*Nq + 12*matches is finalised by the caller */
   uint64_t hamming_lane_ops;       /* VALU lane-instructions K1 issued for those pairs (35 per exact pair; fewer when
-                                      the screening kernel rejects a pair on its prefix distance) */
-  uint64_t hamming_pairs_finished; /* screened pairs whose full distance had to be computed */
+                                      the screening kernel rejects a pair on its prefix distance).  For scans on the
+                                      matrix cores (params.k1_mfma) it counts what that kernel issues on the VALU --
+                                      operand expansion and the running maximum, 2.25 per pair -- the MFMA work itself
+                                      is not in it */
+  uint64_t hamming_pairs_finished; /* screened pairs whose full distance had to be computed (popcount form only: the
+                                      matrix-core form computes every distance in full and counts none here) */
   uint64_t hamming_rows_flagged;   /* bank rows the screening kernel handed to the exact kernel */
 } sfmloc_kernel_stats;
 int sfmloc_stats_read(sfmloc_map *map, sfmloc_kernel_stats *out); /* synchronises */

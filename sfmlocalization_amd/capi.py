@@ -36,6 +36,7 @@ class Params(C.Structure):
         ("profile", C.c_int),
         ("exact_rows", C.c_int),
         ("guided_matching", C.c_int),
+        ("k1_mfma", C.c_int),  # 1 = view-list scans on the matrix cores (default), 0 = the popcount form; same matches
     ]
 
 

@@ -945,6 +945,7 @@ void sfmloc_default_params(sfmloc_params *p) {
   p->device = 0;
   p->profile = 0;
   p->exact_rows = 0;
+  p->k1_mfma = 1;
   p->guided_matching = 0;       // -gm: false (localization.cpp:82, computeFeaturesAndMatches.cpp:63)
 }
 

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "chain_device.h"
+#include "k1_mfma_expand.h"
 #include "sfmloc_internal.h"
 
 namespace sfmloc {
@@ -121,6 +122,57 @@ __global__ __launch_bounds__(8 * 64) void k_hamming_screen_shortlist(
     const uint2 *__restrict__ head_part) {
   constexpr int WAVES = 8, NW = 10, kScreenBatch = 1;
 #include "hamming_screen.body.inc"
+}
+
+// The scan of a view list on the matrix cores (hamming_screen_mfma.body.inc): the contract of k_hamming_screen_shortlist
+// with the distances from v_mfma_scale_f32_32x32x64_f8f6f4 on e2m1 +-1 operands.  It flags a superset of the rows the
+// popcount form flags (its threshold is the one that form starts from), k_hamming_rows and K2 run after it unchanged,
+// so the match lists are the same.  Measured: profiles/k1mfma_lab.jsonl (the form's ceiling), DESIGN.md K1.
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+// kE2m1AllPlusOne in a VGPR the compiler cannot see through: it would fold the constant back into a second literal,
+// which v_and_or_b32 cannot take beside the mask, and split every and-or into v_and + v_or -- 10 instead of 7
+// instructions per descriptor dword.  Measured on the screening loop (tools/mfma_hamming_lab.hip, both forms,
+// profiles/k1mfma_lab.jsonl): 5.8 -> 6.6 T pairs/s at 4 waves per SIMD, 3.9 -> 5.0 at one.  The one line of inline
+// assembly is a plain vector move.
+__device__ __forceinline__ uint32_t k1_mfma_plus_one_reg() {
+  uint32_t v;
+  asm("v_mov_b32 %0, 0x22222222" : "=v"(v));
+  return v;
+}
+// an FP4 operand occupies the first 4 of the 8 dwords
+__device__ __forceinline__ v8i k1_mfma_operand(uint32_t w, uint32_t all_plus_one) {
+  uint32_t e[4];
+  k1_mfma_expand(w, e, all_plus_one);
+  const v8i r = {(int)e[0], (int)e[1], (int)e[2], (int)e[3], 0, 0, 0, 0};
+  return r;
+}
+__device__ __forceinline__ v16f k1_mfma_step(v8i a, v8i b, v16f c) {
+  constexpr int kFp4 = 4;                                  // cbsz / blgp: both operands e2m1
+  constexpr int kScales = (int)(kE8m0One * 0x01010101u);  // 2^0 for every block of either operand
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, kFp4, kFp4, 0, kScales, 0, kScales);
+}
+struct HammingScreenMfmaBody {
+  static constexpr int kGangThreads = 8 * 64;
+  static constexpr int kGangMinWaves = 4;
+  static __device__ __forceinline__ void run(
+    const uint4 *__restrict__ bank, const uint32_t *__restrict__ block_list, uint32_t n_work_blocks,
+    const uint4 *__restrict__ qdesc, uint32_t nq, uint32_t lds_rows, const uint16_t *__restrict__ ratio_cnt,
+    unsigned long long *__restrict__ flagmask, uint2 *__restrict__ flagged, uint32_t *__restrict__ n_flagged,
+    unsigned long long *__restrict__ counters, uint32_t head, uint4 *__restrict__ flagged_desc, uint32_t flagged_desc_cap,
+    const uint2 *__restrict__ head_part) {
+    constexpr int WAVES = 8;
+#include "hamming_screen_mfma.body.inc"
+  }
+};
+__global__ __launch_bounds__(8 * 64, 4) void k_hamming_screen_mfma(
+    const uint4 *__restrict__ bank, const uint32_t *__restrict__ block_list, uint32_t n_work_blocks,
+    const uint4 *__restrict__ qdesc, uint32_t nq, uint32_t lds_rows, const uint16_t *__restrict__ ratio_cnt,
+    unsigned long long *__restrict__ flagmask, uint2 *__restrict__ flagged, uint32_t *__restrict__ n_flagged,
+    unsigned long long *__restrict__ counters, uint32_t head, uint4 *__restrict__ flagged_desc, uint32_t flagged_desc_cap,
+    const uint2 *__restrict__ head_part) {
+  constexpr int WAVES = 8;
+#include "hamming_screen_mfma.body.inc"
 }
 
 // Exact top-2 of the flagged rows.  64 flagged rows x all query rows is ~130 k pairs: on ONE compute unit that is
@@ -331,7 +383,7 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
     const double places = (double)((batched ? 3 : 4) * m->n_cu);
     double best = 1e30;
     for (uint32_t s = 1; s <= 8; ++s) {
-      if (s > 1 && (q->n - head) / s < 3 * head) break;  // (a slice keeps at least three heads of query rows)
+      if (s > 1 && (q->n <= head || (q->n - head) / s < 3 * head)) break;  // (a slice keeps at least three heads of query rows)
       const double g = (double)wg_per_slice * s / places;
       const double full = floor(g), r = g - full;
       const double cost = (full + (r > 0.0 ? 0.45 + 0.55 * r : 0.0)) / s * (1.0 + 0.012 * s);
@@ -364,6 +416,7 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
   // queries' latency-bound stages more of the register file, +1.6 % queries/s; alone the two are equal.
   // SFMLOC_K1_SCREEN_BATCH = 4 / 1 forces one of them.)
   static const int env_batch = [] { const char *e = getenv("SFMLOC_K1_SCREEN_BATCH"); return e ? atoi(e) : 0; }();
+  bool mfma_form = false;
   const bool batched_tail = env_batch ? env_batch == 4 : c->k1_may_slice;
   if (nw == 10 && batched_tail && n_work_blocks < 16u * (uint32_t)m->n_cu) {  // fewer than four waves per SIMD: batched tail
     sfm_launch<HammingScreenBody<WAVES, 10, 4>>(
@@ -371,7 +424,15 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
         (uint32_t)lds_bytes, m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
         m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, head, c->d_flagged_desc,
         c->rows_chunk_cap * 64, head_part);
-  } else if (nw == 10 && use_list) {  // any other scan of a view list (a shortlist while the GPU is shared, a long list)
+  } else if (nw == 10 && use_list && qsplit == 1 && m->params.k1_mfma != 0) {
+    // any other unsliced scan of a view list (a shortlist while the GPU is shared, a long list): on the matrix cores
+    mfma_form = true;
+    const size_t lds_mfma = (size_t)(lds_rows + 1) * 64;  // (four planes of lds_rows + 1 sixteen-byte pieces)
+    sfm_launch<HammingScreenMfmaBody>(
+        c, k_hamming_screen_mfma, dim3((n_work_blocks + WAVES - 1) / WAVES, 1), dim3(WAVES * 64), (uint32_t)lds_mfma,
+        m->d_bank, c->d_block_list, n_work_blocks, q->d_desc, q->n, lds_rows, m->d_ratio_cnt, c->d_flagmask, c->d_flagged,
+        c->d_n_flagged, c->d_k1_counters, head, c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);
+  } else if (nw == 10 && use_list) {  // params.k1_mfma = 0, or a sliced scan of a view list: the popcount form
     sfm_launch<HammingScreenBody<WAVES, 10, 1>>(
         c, k_hamming_screen_shortlist, dim3((n_work_blocks + WAVES - 1) / WAVES, qsplit), dim3(WAVES * 64),
         (uint32_t)lds_bytes, m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
@@ -387,8 +448,17 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
   // pair, screened tail 2*nw+1, plus (sfmloc_stats_read) 2*(16-nw)+5 per finished pair
   const uint64_t rows = (uint64_t)n_work_blocks * kBlockRows;
   // (a sliced scan shares ONE head)
-  c->stats.hamming_lane_ops += rows * head * 35 + rows * (q->n - head) * (uint64_t)(2 * nw + 1);
-  c->k1_finish_ops = 2 * (16 - nw) + 5;
+  if (mfma_form) {
+    // what the matrix-core form issues on the VALU (the MFMA work itself is not lane-ops): per 64 bank rows x 32 query
+    // rows 8 x 7 expansion + 16 v_max3 instructions = 2.25 lane-ops per pair; the head's value-only top-2 adds 64
+    // instructions per such step (2 per pair); expanding a wave's bank rows once is 112 instructions (112 per row)
+    const uint64_t nq32 = ((uint64_t)q->n + 31) & ~31ull, head32 = ((uint64_t)head + 31) & ~31ull;
+    c->stats.hamming_lane_ops += rows * nq32 * 9 / 4 + rows * (head32 < nq32 ? head32 : nq32) * 2 + rows * 112;
+    c->k1_finish_ops = 0;
+  } else {
+    c->stats.hamming_lane_ops += rows * head * 35 + rows * (q->n - head) * (uint64_t)(2 * nw + 1);
+    c->k1_finish_ops = 2 * (16 - nw) + 5;
+  }
   SFM_HIP(hipGetLastError());
   // the exact pass over the flagged rows: chunks of 64 rows x kRowSlices query slices, see k_hamming_rows
   constexpr int RW = 4, RS = 8;
