@@ -1463,6 +1463,9 @@ constexpr int kP3pSmallN = 512;
 // of the bin's upper end against the bin's lowest k: weaker again, still necessary), which keeps the table at 8 KB.
 // ---------------------------------------------------------------------------------------------------
 constexpr int kP3pFilterBins = 1024;
+// (the filter runs for next_pow2(n) >= this, i.e. from 257 correspondences on: below that a model's register sort costs
+// about what the filter does)
+constexpr int kP3pFilterMinP = 512;
 struct P3pFilterLds {  // lives in P3pShared::key (32 KB), which is idle until a model is sorted in LDS
   double T[kP3pFilterBins];            // T' at each bin's upper end
   uint32_t hist[4][kP3pFilterBins + 4];
@@ -1667,11 +1670,13 @@ __device__ __forceinline__ bool p3p_filter_model_block(P3pFilterLds &F, const do
 
 // one model evaluated by one wave in its registers: residuals of elements r * 64 + lane, register sort, NFA minimum;
 // the sorted indices go to iw[] (LDS).  -> r (NFA, k) and the k-th smallest residual.
-// first_hit (or null): P3pState::first_hit -- the wave gives up between its steps once an EARLIER hypothesis of the round
+// first_hit: P3pState::first_hit -- the wave gives up between its steps once an EARLIER hypothesis of the round
 // is known to change the index set (the replay will not look at this one); the value is read by every lane from the same
 // address and taken from the first lane, so the wave decides as one.
 __device__ __forceinline__ bool p3p_overtaken(const unsigned *first_hit, int b) {
-  if (!first_hit) return false;
+  // (nothing is in front of the round's first hypothesis; with this uniform early-out k_p3p_round_small also keeps the
+  // 624 bytes of scratch it had while first_hit could be null -- 672 without it)
+  if (b == 0) return false;
   const unsigned v = __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return (unsigned)__builtin_amdgcn_readfirstlane((int)v) < (unsigned)b;
 }
@@ -1679,7 +1684,7 @@ template <int E>
 __device__ __forceinline__ void p3p_eval_regs(const double (&M)[12], NfaBest &r, double &r_err, const double *__restrict__ pt3d,
                                               const double *__restrict__ xn, const float *__restrict__ logc_n,
                                               const float *__restrict__ logc_k, uint32_t *iw, int lane, int n, double logalpha0,
-                                              double loge0, int stamp_round, int b, const unsigned *first_hit = nullptr) {
+                                              double loge0, int stamp_round, int b, const unsigned *first_hit) {
   uint64_t key[E];
   uint32_t idx[E];
   float cn[E], ck[E];
@@ -1959,9 +1964,8 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   const double loge0 = det_log10(4.0 * (double)(n - s));
   // the NFA filter (above): only once a model exists, only while its tables fit the idle part of the LDS
   const double nfa_to_beat = st.min_nfa;
-  // (from 257 correspondences on: below that a model's register sort costs about what the filter does)
   // (the small form has no LDS for the tables: its models are sorted, which gives the same result)
-  const bool filter = !kSmall && A.nfa_filter && nfa_to_beat < pos_inf() && n <= kP3pMaxN && P >= A.nfa_filter_min_p;
+  const bool filter = !kSmall && nfa_to_beat < pos_inf() && n <= kP3pMaxN && P >= kP3pFilterMinP;
   P3pFilterLds &F = *reinterpret_cast<P3pFilterLds *>(S.key);
   // "Prepared ahead" (p3p_prepare_ahead, below): the models of this hypothesis may be there already
   const bool have = st.prep_iter == st.iter && b < st.prep_n;
@@ -1988,7 +1992,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
     S.nm = p3p_kneip_prepare(x, X, S.prep);
   }
   if (tid == 0)
-    s_first_hit = A.skip_overtaken ? __hip_atomic_load(&A.state->first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0u;
+    s_first_hit = __hip_atomic_load(&A.state->first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   STAMP_P3P(stamp_round, b, 2);
   if (s_first_hit < (unsigned)b) {  // (uniform: one lane's read, seen by all behind the barrier)
@@ -2041,12 +2045,10 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   if (single) {
     // one model per workgroup: the four waves share the model (p3p_eval_coop4 / _multi; every set the LDS forms hold)
     // (behind the filter once more: has an earlier hypothesis been found to change the index set meanwhile?)
-    if (A.skip_overtaken) {  // (uniform)
-      __syncthreads();
-      if (tid == 0) s_first_hit = __hip_atomic_load(&A.state->first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if (s_first_hit < (unsigned)b) pass_mask = 0;
-    }
+    __syncthreads();
+    if (tid == 0) s_first_hit = __hip_atomic_load(&A.state->first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_first_hit < (unsigned)b) pass_mask = 0;
     if ((pass_mask >> mdl) & 1) {  // (uniform over the workgroup)
       double M[12];
 #pragma unroll
@@ -2088,7 +2090,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
       const double *pt3d = A.pt3d, *xn = A.xn;
       const float *logc_n = A.logc_n, *logc_k = A.logc_k;
       if constexpr (kSmall) {
-        const unsigned *first_hit = A.skip_overtaken ? &A.state->first_hit : nullptr;
+        const unsigned *first_hit = &A.state->first_hit;
         // (inlined: 152 VGPRs for the whole kernel, against 212 with the evaluation as a called function)
 #ifndef SFMLOC_STAMPS
         const int stamp_round = 0;
@@ -2603,506 +2605,6 @@ __global__ __launch_bounds__(kThreads, 4) void k_p3p_round_small(P3pArgs A, int 
 #include "p3p_round.body.inc"
 }
 
-// ---------------------------------------------------------------------------------------------------
-// K5, the SEQUENTIAL form (k_p3p_seq): the whole AC-RANSAC of a query in ONE workgroup and ONE launch -- the form a
-// query takes while the GPU is shared.
-//
-// The round form above buys latency with speculation: a round evaluates 64-256 hypotheses side by side and everything
-// behind the round's first index-changing iteration is thrown away -- 1 040 hypotheses evaluated for the 410 iterations a
-// headline query needs (tools/k5_policy_sim.py: no schedule gets below 850), in 9 launches of 64+ workgroups whose waves
-// mostly wait on their own dependent f64 chains while holding a quarter of a SIMD's registers each.  When other queries
-// fill the chip that speculation is pure cost.  Here NW waves (8 or 16) walk the iterations in order, `slots` models per
-// step (a model is evaluated by W = next_pow2(n) / 256 waves: one wave's register sort up to 256 correspondences, W sorted
-// runs of 256 merged through LDS beyond), the sequential rule of OpenMVG's ACRANSAC (restated in
-// oracle/sfm_oracle_geom.c acransac()) is applied model by model in LDS, and a change of the index set costs a barrier, not a
-// launch: at most slots - 1 models are evaluated for nothing per change.  Hypotheses are solved (Kneip) kSeqPool at a
-// time, four lanes per hypothesis -- all four run the common part, each then its root's model.  Nobody waits for another
-// workgroup; the loop advances by at least one iteration per step and n_iter is bounded, so every wave reaches the end.
-// Same arithmetic per model as the round form (err_resection, the (key, index) order, det_log10, the first minimum),
-// same rule: the result is the round form's bit for bit (tests/test_gpu_geom.py, fuzz_parity with SFMLOC_P3P_SEQ=2,
-// bench.py's identical_to_single_flight: timed queries take this form, the single-flight reference the round form).
-// ---------------------------------------------------------------------------------------------------
-constexpr int kSeqPool = 64;          // hypotheses solved per refill (4 lanes each: the first four waves)
-constexpr int kSeqRun = 256;          // correspondences one wave sorts (E = 4 registers per lane)
-constexpr int kSeqPtsLds = 1024;      // up to this many correspondences the points live in LDS for the whole launch
-struct P3pSeqLds {
-  uint32_t pool, nm, res, key, low, vec, best, pts, ftab, hist, total;
-};
-__host__ __device__ inline P3pSeqLds p3p_seq_lds(int nw, int cap) {
-  P3pSeqLds L;
-  uint32_t o = 0;
-  const uint32_t cpts = cap < kSeqPtsLds ? (uint32_t)cap : (uint32_t)kSeqPtsLds;
-  L.pool = o; o += kSeqPool * 48 * sizeof(double);
-  L.nm = o;   o += kSeqPool * sizeof(int);
-  L.res = o;  o += 1024;                                          // per-slot results, reductions, the best model
-  L.key = o;  o += cap > kSeqRun ? (uint32_t)nw * kSeqRun * sizeof(uint64_t) : 0u;  // sorted runs / merged keys (W > 1 only)
-  L.low = o;  o += (uint32_t)nw * kSeqRun * sizeof(uint32_t);    // wave_sort_fast's parking space, then sorted indices
-  L.vec = o;  o += (uint32_t)cap * sizeof(int32_t);              // the index set sampling draws from
-  L.best = o; o += (uint32_t)cap * sizeof(int32_t);              // inliers of the best model so far
-  L.pts = o;  o += cpts * 5 * sizeof(double);                    // X | Y | Z | x | y of the correspondences (n <= kSeqPtsLds)
-  L.ftab = o; o += (kP3pFilterBins + 8) * sizeof(double);        // the NFA filter's thresholds T'
-  // its counts, one table per model slot: in the merged keys' space when there is one (the filter runs before the merge)
-  if (cap > kSeqRun) {
-    L.hist = L.key;
-  } else {
-    L.hist = o; o += ((uint32_t)nw * (kSeqRun + 1) + 8) * sizeof(uint32_t);
-  }
-  L.total = o;
-  return L;
-}
-struct P3pSeqRes {
-  double nfa[16], err[16], red_nfa[16], best_model[12];
-  int k[16], red_k[16];
-};
-static_assert(sizeof(P3pSeqRes) <= 1024, "P3pSeqLds::res");
-
-// entries of a sorted run of kSeqRun keys that come before x: those < x, or (le) those <= x
-__device__ __forceinline__ int seq_run_count(const uint64_t *run, uint64_t x, bool le) {
-  int lo = 0, hi = kSeqRun;
-#pragma unroll
-  for (int it = 0; it < 9; ++it) {  // kSeqRun + 1 = 257 possible answers: nine halvings
-    const int mid = (lo + hi) >> 1;
-    const uint64_t v = run[mid < kSeqRun ? mid : kSeqRun - 1];
-    const bool open = lo < hi;
-    const bool before = le ? (v <= x) : (v < x);
-    lo = (open && before) ? mid + 1 : lo;
-    hi = (open && !before) ? mid : hi;
-  }
-  return lo;
-}
-
-// one hypothesis of the pool by four lanes: all four sample and run Kneip's common part (the same bits in each), lane
-// `root` then its root's model.  Out of line: the solver's registers (~150) are not the loop's.
-__device__ __noinline__ void seq_solve(const int32_t *vec_index, int n_index, uint64_t seed, uint32_t stream, uint32_t it,
-                                       const double *__restrict__ xn, const double *__restrict__ pt3d, int root,
-                                       double *models_h, int *nm_h) {
-  int32_t smp[3];
-  ac_sample<3>(vec_index, n_index, seed, STAGE_P3P, stream, it, smp);
-  double x[6], X[9];
-  for (int i = 0; i < 3; ++i) {
-    x[2 * i] = xn[2 * smp[i]];
-    x[2 * i + 1] = xn[2 * smp[i] + 1];
-    X[3 * i] = pt3d[3 * smp[i]];
-    X[3 * i + 1] = pt3d[3 * smp[i] + 1];
-    X[3 * i + 2] = pt3d[3 * smp[i] + 2];
-  }
-  P3pPrep prep;
-  const int nm = p3p_kneip_prepare(x, X, prep);
-  if (root < nm) {
-    double Mr[12];
-    p3p_kneip_model(prep, root, Mr);
-#pragma unroll
-    for (int q = 0; q < 12; ++q) models_h[12 * root + q] = Mr[q];
-  }
-  if (root == 0) *nm_h = nm;
-}
-
-// The NFA filter's thresholds for the sequential form (the table of "The NFA filter" above, same formula and margin):
-// T'[j] for the bins j = 0 .. nb - 1, recomputed whenever the best NFA B has changed.  All NT threads; barriers inside.
-template <int NT>
-__device__ __forceinline__ void seq_filter_table(double *T, int n, int s, double B, double logalpha0, double loge0,
-                                                 const float *__restrict__ logc_n, const float *__restrict__ logc_k) {
-  const int sh = p3p_filter_shift(n), w = 1 << sh;
-  const int nb = (n >> sh) + 1;
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int jb = tid; jb < nb; jb += NT) {
-    double m = 0.0;
-    for (int k = jb << sh; k < (jb << sh) + w; ++k)
-      if (k > s && k <= n) {
-        const double x = (B - loge0 - (double)logc_n[k] - (double)logc_k[k]) / (double)(k - s) - logalpha0 + 1e-7;
-        const double t = x > 300.0 ? pos_inf() : exp10(x);
-        m = t > m ? t : m;
-      }
-    T[jb] = m;
-  }
-  __syncthreads();
-  if (tid < 64) {  // running maximum, one wave: a contiguous run of bins per lane, then across the lanes
-    const int per = (nb + 63) >> 6;
-    double run = 0.0;
-    for (int i = 0; i < per; ++i) {
-      const int jb = lane * per + i;
-      const double x = jb < nb ? T[jb] : 0.0;
-      run = x > run ? x : run;
-    }
-    double inc = run;
-    for (int off = 1; off < 64; off <<= 1) {
-      const double o = __shfl_up(inc, off, 64);
-      if (lane >= off) inc = o > inc ? o : inc;
-    }
-    double before = __shfl_up(inc, 1, 64);
-    if (lane == 0) before = 0.0;
-    run = before;
-    for (int i = 0; i < per; ++i) {
-      const int jb = lane * per + i;
-      if (jb < nb) {
-        const double x = T[jb];
-        run = x > run ? x : run;
-        T[jb] = run;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-template <int NW>
-__device__ __forceinline__ void p3p_seq_run(const P3pArgs &A, int cap) {
-  P3pState &st = *A.state;
-  if (st.done) return;
-  const int n = st.n;
-  const int P = next_pow2(n);
-  const int W = P <= kSeqRun ? 1 : P / kSeqRun;  // waves per model
-  // a set this launch is not built for: not its business (nothing is touched; the host queues the round form)
-  if (n > cap || W > NW) return;
-  extern __shared__ unsigned char smem_raw[];
-  const P3pSeqLds L = p3p_seq_lds(NW, cap);
-  double *const s_pool = reinterpret_cast<double *>(smem_raw + L.pool);
-  int *const s_nm = reinterpret_cast<int *>(smem_raw + L.nm);
-  P3pSeqRes &R = *reinterpret_cast<P3pSeqRes *>(smem_raw + L.res);
-  uint64_t *const s_key = reinterpret_cast<uint64_t *>(smem_raw + L.key);
-  uint32_t *const s_low = reinterpret_cast<uint32_t *>(smem_raw + L.low);
-  int32_t *const s_vec = reinterpret_cast<int32_t *>(smem_raw + L.vec);
-  int32_t *const s_best = reinterpret_cast<int32_t *>(smem_raw + L.best);
-  double *const s_pts = reinterpret_cast<double *>(smem_raw + L.pts);
-  double *const s_T = reinterpret_cast<double *>(smem_raw + L.ftab);
-  uint32_t *const s_hist = reinterpret_cast<uint32_t *>(smem_raw + L.hist);
-  constexpr int NT = NW * 64;
-  constexpr int E = kSeqRun / 64;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int slots = NW / W;          // models evaluated per step
-  const int grp = wv / W, j = wv - grp * W;  // this wave's model slot and its rank among the slot's waves
-  const int base = j * kSeqRun;      // first element of this wave's run
-  constexpr int s = 3;
-  const double logalpha0 = det_log10(3.14159265358979323846);
-  const double loge0 = det_log10(4.0 * (double)(n - s));
-  const double *const pt3d = A.pt3d, *const xn = A.xn;
-  const float *const logc_n = A.logc_n, *const logc_k = A.logc_k;
-  const bool pts_lds = n <= kSeqPtsLds && n <= cap;
-  const int np = pts_lds ? n : 0;
-  // the state machine (every thread carries it; uniform)
-  long iter = st.iter, n_iter = st.n_iter, n_reserve = st.n_reserve;
-  double min_nfa = st.min_nfa, errmax = st.errmax;
-  int n_in = st.n_in, n_index = st.n_index, identity = st.identity;
-  int better = 0, steps = 0;
-  // (a state some rounds have already advanced: its index set and best model)
-  if (!identity)
-    for (int p = tid; p < n_index; p += NT) s_vec[p] = A.vec_index[p];
-  for (int p = tid; p < n_in; p += NT) s_best[p] = A.best_inl[p];
-  if (tid < 12) R.best_model[tid] = st.model[tid];
-  for (int p = tid; p < np; p += NT) {
-    s_pts[p] = pt3d[3 * p];
-    s_pts[np + p] = pt3d[3 * p + 1];
-    s_pts[2 * np + p] = pt3d[3 * p + 2];
-    s_pts[3 * np + p] = xn[2 * p];
-    s_pts[4 * np + p] = xn[2 * p + 1];
-  }
-  // the two table entries of the sorted positions this lane reads in the NFA scan (k = position + 1)
-  float cn[E], ck[E];
-#pragma unroll
-  for (int rr = 0; rr < E; ++rr) {
-    const int kk = base + (rr << 6) + lane + 1;
-    cn[rr] = kk <= n ? logc_n[kk] : 0.0f;
-    ck[rr] = kk <= n ? logc_k[kk] : 0.0f;
-  }
-  // the NFA filter (section above): from the first finite best NFA on, a model is sorted only if it can beat it
-  const int f_sh = p3p_filter_shift(n);
-  const int f_nb = (n >> f_sh) + 1;
-  int f_steps = 0;
-  while ((1 << f_steps) < f_nb + 1) ++f_steps;
-  uint32_t *const hist = s_hist + (size_t)grp * (W * kSeqRun + 1);
-  double table_for = pos_inf();  // the best NFA the table in s_T was built for (+inf: none)
-  long pool_it0 = 0;
-  int pool_n = 0, g0 = 0;
-#ifdef SFMLOC_SEQ_TIMING  // diagnostic build (make EXTRA=-DSFMLOC_SEQ_TIMING ...): where a launch's time goes, by thread 0's clock
-  unsigned long long tq[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq0 = wall_clock64(), tq1;
-  int n_refill = 0, n_pass = 0;
-#define SEQ_T(k) do { tq1 = wall_clock64(); tq[k] += tq1 - tq0; tq0 = tq1; } while (0)
-#else
-#define SEQ_T(k) do {} while (0)
-#endif
-  __syncthreads();
-  SEQ_T(0);
-  while (iter < n_iter) {
-    if (g0 >= 4 * pool_n) {
-      // ---- solve the next hypotheses: iterations iter .. iter + pool_n - 1 from the current index set
-      pool_it0 = iter;
-      pool_n = (int)((n_iter - iter) < (long)kSeqPool ? (n_iter - iter) : (long)kSeqPool);
-      g0 = 0;
-      if (tid < 4 * pool_n)
-        seq_solve(identity ? nullptr : s_vec, n_index, A.seed, A.stream, (uint32_t)(pool_it0 + (tid >> 2)), xn, pt3d, tid & 3,
-                  s_pool + 48 * (tid >> 2), s_nm + (tid >> 2));
-      __syncthreads();
-      SEQ_T(1);
-#ifdef SFMLOC_SEQ_TIMING
-      ++n_refill;
-#endif
-    }
-    const bool filter = A.nfa_filter && min_nfa < pos_inf();
-    if (filter && table_for != min_nfa) {
-      seq_filter_table<NT>(s_T, n, s, min_nfa, logalpha0, loge0, logc_n, logc_k);
-      table_for = min_nfa;
-    }
-    // ---- evaluate models g0 .. g0 + slots - 1 (model m of pool hypothesis h is g = 4 h + m), one per slot
-    const int g_mine = g0 + grp;
-    const int h_mine = g_mine >> 2, m_mine = g_mine & 3;
-    const bool active = h_mine < pool_n && pool_it0 + h_mine < n_iter && m_mine < s_nm[h_mine < pool_n ? h_mine : 0];
-    uint64_t key[E];
-    uint32_t idx[E];
-    {
-      double M[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) M[q] = s_pool[48 * (active ? h_mine : 0) + 12 * m_mine + q];
-#pragma unroll
-      for (int rr = 0; rr < E; ++rr) {
-        const int p = base + (rr << 6) + lane;
-        const int pc = p < n ? p : n - 1;
-        double X, Y, Z, x, y;
-        if (pts_lds) {
-          X = s_pts[pc], Y = s_pts[np + pc], Z = s_pts[2 * np + pc], x = s_pts[3 * np + pc], y = s_pts[4 * np + pc];
-        } else {
-          X = pt3d[3 * pc], Y = pt3d[3 * pc + 1], Z = pt3d[3 * pc + 2], x = xn[2 * pc], y = xn[2 * pc + 1];
-        }
-        const double e = err_resection(M, X, Y, Z, x, y);
-        key[rr] = (active && p < n) ? d2u(e) : ~0ull;
-        idx[rr] = 0u;
-      }
-    }
-    bool pass = active;
-    SEQ_T(2);
-    if (filter) {  // (uniform)
-      for (int jb = j * 64 + lane; jb < f_nb; jb += W * 64) hist[jb] = 0u;
-      __syncthreads();
-      if (active) {
-        int lo[E], hi[E];
-        double rv[E];
-#pragma unroll
-        for (int rr = 0; rr < E; ++rr) {
-          rv[rr] = u2d(key[rr]) + (double)FLT_EPSILON;
-          lo[rr] = 0;
-          hi[rr] = f_nb;
-        }
-        // first bin whose threshold exceeds the residual (f_nb: none); T' is non-decreasing
-        for (int it = 0; it < f_steps; ++it) {
-#pragma unroll
-          for (int rr = 0; rr < E; ++rr) {
-            const int mid = (lo[rr] + hi[rr]) >> 1;
-            const bool below = mid < f_nb && rv[rr] < s_T[mid < f_nb ? mid : f_nb - 1];
-            const bool open = lo[rr] < hi[rr];
-            hi[rr] = (open && below) ? mid : hi[rr];
-            lo[rr] = (open && !below) ? mid + 1 : lo[rr];
-          }
-        }
-#pragma unroll
-        for (int rr = 0; rr < E; ++rr)
-          if (base + (rr << 6) + lane < n && lo[rr] < f_nb) atomicAdd(&hist[lo[rr]], 1u);
-      }
-      __syncthreads();
-      // running counts over the slot's table (every wave of the slot walks it and reaches the same verdict): the model
-      // can beat the best NFA only if some bin's running count reaches the bin's lowest k
-      const int per = (f_nb + 63) >> 6;
-      uint32_t sum = 0;
-      for (int i = 0; i < per; ++i) {
-        const int jb = lane * per + i;
-        sum += jb < f_nb ? hist[jb] : 0u;
-      }
-      uint32_t inc = sum;
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-      }
-      uint32_t run = inc - sum;
-      bool any = false;
-      for (int i = 0; i < per; ++i) {
-        const int jb = lane * per + i;
-        if (jb < f_nb) {
-          run += hist[jb];
-          const int k_lo = (jb << f_sh) > s + 1 ? (jb << f_sh) : s + 1;  // lowest k of the bin that NFA ranges over
-          const int k_hi = (jb << f_sh) + (1 << f_sh) - 1;
-          if (k_hi > s && k_lo <= n && run >= (uint32_t)k_lo) any = true;
-        }
-      }
-      pass = active && __ballot(any) != 0ull;
-    }
-    SEQ_T(3);
-#ifdef SFMLOC_SEQ_TIMING
-    n_pass += pass ? 1 : 0;
-#endif
-    if (W == 1) {
-      NfaBest r{pos_inf(), 0x7FFFFFFF};
-      double r_err = pos_inf();
-      if (pass) {
-        uint32_t *iw = s_low + (size_t)wv * kSeqRun;
-        wave_sort_fast<E>(key, idx, iw);
-#pragma unroll
-        for (int rr = 0; rr < E; ++rr) iw[(rr << 6) + lane] = idx[rr];
-        r = best_nfa_regs_ilp<E>(key, n, s, pos_inf(), logalpha0, 1.0, loge0, cn, ck);
-        if (r.k != 0x7FFFFFFF) r_err = u2d(sorted_key_at<E>(key, r.k - 1));
-      }
-      if (lane == 0) {
-        R.nfa[grp] = r.nfa;
-        R.k[grp] = r.k;
-        R.err[grp] = r_err;
-      }
-    } else if (__syncthreads_or(pass ? 1 : 0)) {
-      // W waves, one model: wave j sorts elements 256 j .. 256 j + 255 in its registers, the W sorted runs are merged
-      // by rank -- an element's final position is its position in its own run plus, per other run, the number of that
-      // run's elements that come before it in the (key, index) order: runs of lower element indices win ties.  (Every
-      // slot walks through the barriers; a slot whose model failed the filter reports +inf at the end.)
-      wave_sort_fast<E>(key, idx, s_low + (size_t)wv * kSeqRun);
-      uint64_t *const runs = s_key + (size_t)grp * W * kSeqRun;  // the slot's W runs, then its merged keys
-      uint32_t *const fidx = s_low + (size_t)grp * W * kSeqRun;  // the slot's merged element indices
-#pragma unroll
-      for (int rr = 0; rr < E; ++rr) runs[base + (rr << 6) + lane] = key[rr];
-      __syncthreads();
-      int rank[E];
-#pragma unroll
-      for (int rr = 0; rr < E; ++rr) rank[rr] = (rr << 6) + lane;
-      for (int u = 0; u < W; ++u) {
-        if (u == j) continue;  // (uniform over the wave)
-#pragma unroll
-        for (int rr = 0; rr < E; ++rr) rank[rr] += seq_run_count(runs + u * kSeqRun, key[rr], u < j);
-      }
-      __syncthreads();  // every rank is known: the runs may be overwritten
-#pragma unroll
-      for (int rr = 0; rr < E; ++rr) {
-        runs[rank[rr]] = key[rr];
-        fidx[rank[rr]] = (uint32_t)base + idx[rr];
-      }
-      __syncthreads();
-      // bestNFA over the merged order: position pos holds e_(pos + 1); the same candidates and the same first minimum
-      // as best_nfa_regs_ilp
-      double lb = pos_inf();
-      int lk = 0x7FFFFFFF;
-      if (pass) {
-#pragma unroll
-        for (int rr = 0; rr < E; ++rr) {
-          const int kk = base + (rr << 6) + lane + 1;
-          if (kk > s && kk <= n) {
-            const double ek = u2d(runs[kk - 1]);
-            const double logalpha = logalpha0 + 1.0 * det_log10_inline(ek + (double)FLT_EPSILON);
-            const double nfa = loge0 + logalpha * (double)(kk - s) + (double)cn[rr] + (double)ck[rr];
-            if (nfa < lb) {
-              lb = nfa;
-              lk = kk;
-            }
-          }
-        }
-      }
-      const NfaBest wr = wave_reduce_nfa(lb, lk);
-      if (lane == 0) {
-        R.red_nfa[wv] = wr.nfa;
-        R.red_k[wv] = wr.k;
-      }
-      __syncthreads();
-      if (j == 0 && lane == 0) {
-        NfaBest r{pos_inf(), 0x7FFFFFFF};
-        for (int u = 0; u < W; ++u) {
-          const double o = R.red_nfa[wv + u];
-          const int ok = R.red_k[wv + u];
-          if (o < r.nfa || (o == r.nfa && ok < r.k)) {
-            r.nfa = o;
-            r.k = ok;
-          }
-        }
-        R.nfa[grp] = r.nfa;
-        R.k[grp] = r.k;
-        R.err[grp] = r.k != 0x7FFFFFFF ? u2d(runs[r.k - 1]) : pos_inf();
-      }
-    } else if (j == 0 && lane == 0) {
-      R.nfa[grp] = pos_inf();  // no slot's model can beat the best NFA
-    }
-    __syncthreads();
-    SEQ_T(4);
-    // ---- the sequential rule over this step's models, in order (acransac(): per model "is it better", per hypothesis
-    // -- behind its last model -- "does the index set change / does the budget end")
-    int best_slot = -1;
-    bool index_changed = false;
-    for (int sl = 0; sl < slots; ++sl) {
-      const int g = g0 + sl;
-      const int h = g >> 2, m = g & 3;
-      const long it = pool_it0 + h;
-      if (h >= pool_n || it >= n_iter) break;
-      if (m < s_nm[h]) {
-        const double nfa = R.nfa[sl];
-        if (nfa < min_nfa) {
-          better = 1;
-          min_nfa = nfa;
-          n_in = R.k[sl];
-          errmax = R.err[sl];
-          best_slot = sl;
-        }
-      }
-      if (m == 3) {
-        if ((better && min_nfa < 0.0) || (it + 1 == n_iter && n_reserve)) {
-          if (n_in == 0) {
-            n_iter++;
-            n_reserve--;
-          } else {
-            index_changed = true;
-            n_index = n_in;
-            identity = 0;
-            if (n_reserve) {
-              n_iter = it + 1 + n_reserve;
-              n_reserve = 0;
-            }
-          }
-        }
-        better = 0;
-        iter = it + 1;
-        if (index_changed) break;
-      }
-    }
-    if (best_slot >= 0) {
-      const uint32_t *src = s_low + (size_t)best_slot * W * kSeqRun;
-      for (int p = tid; p < n_in; p += NT) s_best[p] = (int32_t)src[p];
-      const int g = g0 + best_slot;
-      if (tid < 12) R.best_model[tid] = s_pool[48 * (g >> 2) + 12 * (g & 3) + tid];
-    }
-    __syncthreads();
-    if (index_changed) {
-      for (int p = tid; p < n_in; p += NT) s_vec[p] = s_best[p];
-      pool_n = 0;  // what was solved ahead sampled from the old index set
-      g0 = 0;
-      __syncthreads();
-    } else {
-      g0 += slots;
-    }
-    ++steps;
-    SEQ_T(5);
-  }
-#ifdef SFMLOC_SEQ_TIMING
-  if (tid == 0)
-    printf("seq NW=%d n=%d W=%d: %d steps, %d refills, wave0 passed %d | us: setup %.1f refill %.1f resid %.1f filter %.1f sort+nfa %.1f replay %.1f\n",
-           NW, n, W, steps, n_refill, n_pass, tq[0] * 0.01, tq[1] * 0.01, tq[2] * 0.01, tq[3] * 0.01, tq[4] * 0.01, tq[5] * 0.01);
-#endif
-  // ---- the state k_p3p_finish reads
-  for (int p = tid; p < n_in; p += NT) A.best_inl[p] = s_best[p];
-  if (tid == 0) {
-    st.iter = (int)iter;
-    st.n_iter = (int)n_iter;
-    st.n_reserve = (int)n_reserve;
-    st.min_nfa = min_nfa;
-    st.errmax = errmax;
-    st.n_in = n_in;
-    st.n_index = n_index;
-    st.identity = identity;
-    st.rounds += steps;
-    st.prep_n = 0;
-    for (int q = 0; q < 12; ++q) st.model[q] = R.best_model[q];
-    st.done = 1;
-  }
-}
-template <int NW>
-struct P3pSeqBody {
-  static constexpr int kGangThreads = NW * 64;
-  static __device__ __forceinline__ void run(P3pArgs A, int cap) { p3p_seq_run<NW>(A, cap); }
-};
-// (min. 4 waves per SIMD = at most 128 VGPRs, whatever NW: the workgroup takes NW / 4 wave slots and NW / 4 x 128 registers of
-// each SIMD and leaves the rest of the compute unit to the scans)
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 4) void k_p3p_seq(P3pArgs A, int cap) {
-  p3p_seq_run<NW>(A, cap);
-}
-
 // ACRANSAC's epilogue + SfM_Localizer::Localize + localization.cpp:511-547, once per query after the last round
 // what the host reads after the stream has drained: the record's head (state -- "done?" --, pose, status, view counts)
 // and, of a finished query, the inlier pairs.  Written by the kernel itself into the pinned host record: a copy launch
@@ -3464,27 +2966,23 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
     A.large_list = c->fl_list;
   }
   // views with <= kF2MaxM putative matches take the wave-parallel kernel, the rest (if any: the second launch
-  // returns at once for the others) the block-wide one; SFMLOC_K3_FAST=0 sends every view to the latter
-  static const bool fast = [] {
-    const char *e = getenv("SFMLOC_K3_FAST");
-    return !(e && atoi(e) == 0);
-  }();
-  A.skip_le = fast ? kF2MaxM : -1;
+  // returns at once for the others) the block-wide one
+  A.skip_le = kF2MaxM;
   A.fast_min = -1;
   A.merge = MergeMaskedArgs{};
   // The wide form (one workgroup per iteration of a view's first batch, fmatrix_fast.body.inc) for a query alone on the GPU
   // with a short view list: its 1 024-match instance takes every view the register forms hold, in one launch.
   // SFMLOC_K3_WIDE = 0 never, 2 always (tests, campaigns).
-  static const int env_wide = [] { const char *e = getenv("SFMLOC_K3_WIDE"); return e ? atoi(e) : 1; }();
+  static const int env_wide = env_int("SFMLOC_K3_WIDE", 1);
   const int n_uniform = m->params.ransac_round - m->params.ransac_round / 10;
   const int wide_b0 = n_uniform < kF2Batch ? n_uniform : kF2Batch;
-  const bool wide = fast && wide_b0 >= 2 && n_sel <= (uint32_t)kK3WideViews &&
+  const bool wide = wide_b0 >= 2 && n_sel <= (uint32_t)kK3WideViews &&
                     (env_wide == 2 || (env_wide == 1 && c->k1_may_slice && c->stream.gang == nullptr));
   A.spec = nullptr;
   A.spec_arrive = nullptr;
   if (c->merge_is_deferred) {  // K2 was left to this stage (launch_merge_ratio_compact)
     c->merge_is_deferred = false;
-    if (fast && !wide) {
+    if (!wide) {
       A.merge = c->deferred_merge;  // k_fmatrix_fast runs on every selected view, whatever its size
     } else {  // (the wide form's workgroups of a view all need the view's lists: K2 as a launch of its own)
       int rc = launch_merge_masked_now(c, n_sel);
@@ -3504,7 +3002,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
     // (views of 1 025 .. 2 048 matches -- 32 residuals per lane in the register sort, one workgroup per compute unit --
     // only while the map's queries have had such views lately, Map::k3_huge_credit; SFMLOC_K3_WIDE_2048 = 0 never, 2 always:
     // k_fmatrix_filter's block-wide sort took 0.6 of a lone 1080p frame's 0.95 ms in this stage)
-    static const int env_2048 = [] { const char *e = getenv("SFMLOC_K3_WIDE_2048"); return e ? atoi(e) : 1; }();
+    static const int env_2048 = env_int("SFMLOC_K3_WIDE_2048", 1);
     const bool huge = env_2048 == 2 || (env_2048 == 1 && m->k3_huge_credit.load(std::memory_order_relaxed) > 0);
     auto go_wide = [&](auto m_tag) {
       constexpr int MaxM = decltype(m_tag)::value;
@@ -3522,10 +3020,10 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
     SFM_HIP(ew);
     SFM_HIP(hipGetLastError());
     A.skip_le = huge ? 2048 : 1024;
-  } else if (fast) {
+  } else {
     // waves per view (F2SharedT): 16 for a query alone on the GPU, 4 when other contexts have work queued
-    static const int env_waves = [] { const char *e = getenv("SFMLOC_K3_WAVES_SHARED"); return e ? atoi(e) : 4; }();
-    static const int env_waves_alone = [] { const char *e = getenv("SFMLOC_K3_WAVES_ALONE"); return e ? atoi(e) : 16; }();
+    static const int env_waves = env_int("SFMLOC_K3_WAVES_SHARED", 4);
+    static const int env_waves_alone = env_int("SFMLOC_K3_WAVES_ALONE", 16);
     const int waves = c->k1_may_slice ? env_waves_alone : env_waves;
     auto go = [&](auto w_tag) {
       constexpr int W = decltype(w_tag)::value;
@@ -3544,7 +3042,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
     // views with 513 .. 1 024 putative matches (a query that nearly duplicates a map frame): the same kernel with 16
     // residuals per lane -- while the map's queries have had such views lately (Map::k3_big_credit, set from the largest
     // view of every finished query: a launch whose 100 workgroups all leave at once still costs a launch)
-    static const int env_big = [] { const char *e = getenv("SFMLOC_K3_BIG"); return e ? atoi(e) : 1; }();
+    static const int env_big = env_int("SFMLOC_K3_BIG", 1);
     if (env_big == 2 || (env_big == 1 && m->k3_big_credit.load(std::memory_order_relaxed) > 0)) {
       FFilterArgs B = A;
       B.merge.enabled = 0;  // (the lists exist: the launch above built them)
@@ -3788,22 +3286,13 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.refine_pose = m->params.refine_pose;
   // a context that is not alone on the map's GPU (other contexts have work queued, ctx_mark_busy) spends fewer
   // speculative hypotheses per round; SFMLOC_P3P_ADAPTIVE=0/1 overrides (measurements)
-  static const int env_adaptive = [] {
-    const char *e = getenv("SFMLOC_P3P_ADAPTIVE");
-    return e ? atoi(e) : -1;
-  }();
-  static const int env_filter = [] { const char *e = getenv("SFMLOC_P3P_FILTER"); return e ? atoi(e) : 1; }();
-  A.nfa_filter = env_filter;  // (0: every model is sorted, as before round 3 -- comparison runs and tests)
-  static const int env_filter_p = [] { const char *e = getenv("SFMLOC_P3P_FILTER_MIN_P"); return e ? atoi(e) : 512; }();
-  A.nfa_filter_min_p = env_filter_p;
+  static const int env_adaptive = env_int("SFMLOC_P3P_ADAPTIVE", -1);
   A.adaptive_batch = env_adaptive >= 0 ? env_adaptive : (c->k1_may_slice ? 0 : 1);
   // (SFMLOC_P3P_PREP_AHEAD: 0 never, 1 when the GPU is shared -- the default --, 2 always: comparison runs and tests)
-  static const int env_prep = [] { const char *e = getenv("SFMLOC_P3P_PREP_AHEAD"); return e ? atoi(e) : 1; }();
+  static const int env_prep = env_int("SFMLOC_P3P_PREP_AHEAD", 1);
   A.prep_ahead = env_prep == 2 || (env_prep == 1 && A.adaptive_batch);
-  static const int env_quarters = [] { const char *e = getenv("SFMLOC_P3P_ADAPT_QUARTERS"); return e ? atoi(e) : 12; }();
-  static const int env_floor = [] { const char *e = getenv("SFMLOC_P3P_ADAPT_FLOOR"); return e ? atoi(e) : 64; }();
-  static const int env_skip = [] { const char *e = getenv("SFMLOC_P3P_SKIP_OVERTAKEN"); return e ? atoi(e) : 1; }();
-  A.skip_overtaken = env_skip;  // (0: every hypothesis of a round is evaluated, as before round 4 -- comparison runs)
+  static const int env_quarters = env_int("SFMLOC_P3P_ADAPT_QUARTERS", 12);
+  static const int env_floor = env_int("SFMLOC_P3P_ADAPT_FLOOR", 64);
   A.adapt_quarters = env_quarters;
   A.adapt_floor = env_floor;
   A.seed = m->params.seed;
@@ -3838,15 +3327,15 @@ int launch_p3p_round(Ctx *c, int batch) {
   // (SFMLOC_P3P_WIDE_ALONE=1: also for any query alone on the GPU -- measured and not the default: with 4 x 256 workgroups
   // the chip is NOT idle, four waves per SIMD share its f64 pipe and a headline round takes 47 us instead of 29,
   // profiles/r04_k5_forms.txt)
-  static const int env_wide_alone = [] { const char *e = getenv("SFMLOC_P3P_WIDE_ALONE"); return e ? atoi(e) : 0; }();
+  static const int env_wide_alone = env_int("SFMLOC_P3P_WIDE_ALONE", 0);
   const int wide = ((c->p3p_query_n > 512 && c->map->p3p_wide_credit.load(std::memory_order_relaxed) > 0) ||
                     (env_wide_alone == 2 || (env_wide_alone == 1 && c->k1_may_slice && !c->stream.gang))) ? 1 : 0;
   if (wide && batch > kP3pSlots / 4) batch = kP3pSlots / 4;
   // (wide rounds are nominally 128 hypotheses, not 256: on large sets most rounds evaluate 16 .. 64 -- p3p_next_batch_limit --
   // and every workgroup of the 4 x batch launched has to be dispatched with its LDS and registers even to find that it has
   // nothing to do: image-in frames 0.86 -> 0.71 ms of PnP alone, 1 229 -> 1 302 images/s, profiles/r04_k5_forms.txt)
-  static const int env_wide_batch = [] { const char *e = getenv("SFMLOC_P3P_WIDE_BATCH"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 256 ? v : 128; }();
-  if (wide && batch > env_wide_batch) batch = env_wide_batch;
+  constexpr int kP3pWideBatch = 128;
+  if (wide && batch > kP3pWideBatch) batch = kP3pWideBatch;
   // (a wide launch sized for fewer hypotheses than the nominal batch, each workgroup taking several in turn, was tried:
   // the empty workgroups of a 4 x 256 launch cost ~20-50 us per round on large sets, but the loop cost the small form's
   // text 10 % of a headline round; not kept, profiles/r04_k5_forms.txt)
@@ -3860,38 +3349,6 @@ int launch_p3p_round(Ctx *c, int batch) {
   }
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
-}
-
-// the sequential form (k_p3p_seq): one workgroup of `nw` waves takes the query's whole AC-RANSAC.  cap bounds the LDS
-// index lists: the query's feature count rounded up (a query has at most one correspondence per feature).
-int p3p_seq_waves() {
-  static const int v = [] {
-    const char *e = getenv("SFMLOC_P3P_SEQ_WAVES");
-    const int w = e ? atoi(e) : 8;
-    return w == 16 ? 16 : (w == 4 ? 4 : 8);
-  }();
-  return v;
-}
-template <int NW>
-static int launch_p3p_seq_nw(Ctx *c, const P3pArgs &A, int cap) {
-  const uint32_t lds = p3p_seq_lds(NW, cap).total;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p3p_seq<NW>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)p3p_seq_lds(NW, kP3pMaxN).total);
-  SFM_HIP(attr);
-  sfm_launch<P3pSeqBody<NW>>(c, k_p3p_seq<NW>, dim3(1), dim3(NW * 64), lds, A, cap);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
-}
-int launch_p3p_seq(Ctx *c) {
-  P3pArgs A = make_p3p_args(c);
-  int cap = 256;
-  while (cap < (int)c->p3p_query_n && cap < kP3pMaxN) cap <<= 1;
-  switch (p3p_seq_waves()) {
-    case 16: return launch_p3p_seq_nw<16>(c, A, cap);
-    case 4: return launch_p3p_seq_nw<4>(c, A, cap);
-    default: return launch_p3p_seq_nw<8>(c, A, cap);
-  }
 }
 
 int launch_p3p_finish(Ctx *c) {

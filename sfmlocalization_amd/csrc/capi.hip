@@ -512,47 +512,27 @@ int ctx_resection_enqueue(Ctx *c, bool first_call) {
     // the form of this query's rounds (acransac.hip, at P3pShared: the small form holds sets of at most 512
     // correspondences in a fraction of the registers): a prediction from the map's last queries -- or a certainty, when
     // the query has no more features than that --; ctx_resection_wait corrects it if the set turns out larger
-    static const int env_small = [] { const char *e = getenv("SFMLOC_P3P_SMALL"); return e ? atoi(e) : 1; }();
+    static const int env_small = env_int("SFMLOC_P3P_SMALL", 1);
     c->p3p_small = env_small == 2 || (env_small == 1 && (c->p3p_query_n <= 512 ||
                                                          c->map->p3p_small_credit.load(std::memory_order_relaxed) >= 8));
-    // The sequential form (acransac.hip, k_p3p_seq: the whole AC-RANSAC as ONE launch of one workgroup, no speculative
-    // hypotheses, no rounds) -- built, bit-exact, measured and NOT the default: one workgroup walks a headline query's 410
-    // iterations in 2.2-2.5 ms where the rounds take 0.25 (profiles/r04_k5_sequential_form.txt).  SFMLOC_P3P_SEQ: 0 never
-    // (default), 1 while the GPU is shared, 2 always.
-    static const int env_seq = [] { const char *e = getenv("SFMLOC_P3P_SEQ"); return e ? atoi(e) : 0; }();
-    c->p3p_seq = env_seq == 2 || (env_seq == 1 && (!c->k1_may_slice || c->stream.gang != nullptr));
-    if (c->p3p_seq) {
-      rc = launch_p3p_seq(c);
-      if (rc == SFMLOC_OK) rc = launch_p3p_finish(c);
-      return rc;
-    }
   }
   // typically 6-8 rounds end the stage (one per improvement of the model); rounds enqueued past the end return at
-  // once but still cost two launches each, so the first call queues 9 and ctx_resection_wait adds more if needed
-  static const int env_batch = [] {  // tuning hooks: hypotheses per later round / rounds queued by the first call
-    const char *e = getenv("SFMLOC_P3P_BATCH");
-    const int v = e ? atoi(e) : 0;
-    // 256 per later round: as many rounds as with 512 (an improvement of the model comes early in a round or not at
-    // all), 3-5 % more queries per second because fewer speculative hypotheses are evaluated for nothing
-    return (v >= 16 && v <= kP3pBatchMax) ? v : 256;
-  }();
-  // the first round's size while the GPU is shared (a query alone: 64): after the geometric filter the first hypothesis is
+  // once but still cost two launches each, so the first call queues 9 and ctx_resection_wait adds more if needed.
+  // 256 hypotheses per later round: as many rounds as with 512 (an improvement of the model comes early in a round or not at
+  // all), 3-5 % more queries per second because fewer speculative hypotheses are evaluated for nothing
+  constexpr int kLaterBatch = 256;
+  // the first round's size, alone or while the GPU is shared: after the geometric filter the first hypothesis is
   // nearly always the one that switches sampling to its inliers, and everything behind it is thrown away
-  static const int env_first_shared = [] {
-    const char *e = getenv("SFMLOC_P3P_FIRST_BATCH");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 4 && v <= 256) ? v : 64;
-  }();
-  static const int env_rounds = [] {
-    const char *e = getenv("SFMLOC_P3P_ROUNDS");
-    const int v = e ? atoi(e) : 0;
+  constexpr int kFirstBatch = 64;
+  static const int env_rounds = [] {  // tuning hook: rounds queued by the first call
+    const int v = env_int("SFMLOC_P3P_ROUNDS", 9);
     return (v >= 1 && v <= 64) ? v : 9;
   }();
   // (in a gang session a surplus round costs a fraction of a launch, and a member that needs more than were queued gets
   // them alone on the gang's stream: three more up front)
   const int rounds = first_call ? (c->stream.gang ? std::max(env_rounds, 12) : env_rounds) : 6;
   for (int r = 0; r < rounds && rc == SFMLOC_OK; ++r)
-    rc = launch_p3p_round(c, (first_call && r == 0) ? (c->k1_may_slice ? 64 : env_first_shared) : env_batch);
+    rc = launch_p3p_round(c, (first_call && r == 0) ? kFirstBatch : kLaterBatch);
   if (rc == SFMLOC_OK) rc = launch_p3p_finish(c);  // pose + inlier pairs once the state says "done"; a no-op before
   return rc;
 }
@@ -653,8 +633,6 @@ int ctx_resection_wait(Ctx *c) {
     }
     // (the small rounds of a set that turned out larger than the form holds all returned at once: the full form now)
     if (c->p3p_small && h->state.n > 512) c->p3p_small = false;
-    // (a set the sequential launch is not built for -- more correspondences than its waves hold -- came back untouched)
-    c->p3p_seq = false;
     int rc;
     {
       EventScope ev(c, SFMLOC_K_P3P);
@@ -681,10 +659,7 @@ int ctx_localize_begin(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_se
 // SFMLOC_DIAG_STOP_AFTER = 1 (putative matches) / 2 (geometric filter) / 3 (2D-3D set): measurements only -- the chain
 // ends there and sfmloc_localize_end returns an empty pose (bench.py marks such a line as not the metric)
 static int diag_stop_after() {
-  static const int v = [] {
-    const char *e = getenv("SFMLOC_DIAG_STOP_AFTER");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = env_int("SFMLOC_DIAG_STOP_AFTER", 0);
   return v;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -16,6 +17,13 @@
 namespace sfmloc {
 
 void set_error(const char *fmt, ...);
+
+// an integer switch of the environment (INTEGRATION.md lists them); callers keep the value in a function-local
+// `static const`, so it is read once per process
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 #define SFM_HIP(call)                                                                          \
   do {                                                                                         \
@@ -110,9 +118,6 @@ struct P3pArgs {
   double *ws_terms;  // [max_n / 2 + 1]
   double focal, ppx, ppy;
   int max_iteration, min_resection_points, min_inliers, max_n, refine_pose;
-  int nfa_filter;      // 1 = models that cannot beat the round's starting NFA are not sorted (acransac.hip, "The NFA filter")
-  int nfa_filter_min_p;  // ... for next_pow2(n) >= this
-  int skip_overtaken;  // 1: workgroups / waves give up behind a known index-changing hypothesis (P3pState::first_hit)
   int adaptive_batch;  // other queries share the GPU: trade rounds for fewer speculative hypotheses
   int adapt_quarters, adapt_floor;  // next batch = max(floor, quarters/4 * iterations since the switch)
   uint64_t seed;
@@ -259,7 +264,6 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   uint32_t p3p_cap = kP3pMaxN;
   uint64_t p3p_bytes = 0;  // bytes of the regrowable P3P arrays currently held (part of hbm_bytes)
   bool p3p_small = false;  // this query's P3P rounds go out in the small form (decided when the first ones are queued)
-  bool p3p_seq = false;    // this query's AC-RANSAC went out in the sequential form (one launch; acransac.hip k_p3p_seq)
   uint32_t p3p_query_n = 0;  // features of the query K5 is about to run for (ctx_p3p_reserve): launch shape of the rounds
   uint32_t p3p_stream = 0;   // K5's sampling stream (Philox key): 0 for queries; the view id when adjust.hip resects a view
   bool p3p_own_K = false;    // K5 uses p3p_K (focal, ppx, ppy) instead of the map's intrinsic (adjust.hip: per view)
@@ -437,7 +441,6 @@ int ctx_p3p_reserve(Ctx *c, uint32_t n_query_rows);  // capi.hip: grow the P3P w
 int launch_merge_masked_now(Ctx *c, uint32_t n_sel);  // hamming.hip: the deferred K2 as a launch of its own
 int launch_p3p_init(Ctx *c);
 int launch_p3p_round(Ctx *c, int batch);
-int launch_p3p_seq(Ctx *c);     // the sequential form: the query's whole AC-RANSAC in one workgroup (GPU shared)
 int launch_p3p_finish(Ctx *c);
 // capi.hip: K5 on correspondences the caller has already written into the context's 2D-3D buffers (d_ms_n, d_pt2d,
 // d_pt3d, d_ms_qfeat, d_ms_landmark) -- ctx_p3p_reserve first; _begin queues init + rounds + finish, _wait drains

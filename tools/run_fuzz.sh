@@ -2,14 +2,13 @@
 # round's prefix).  ROUND=r04 tags the output directory; SEED0 moves every campaign to fresh seeds; FORMS=shared repeats the
 # localisation / sharded / gang / large-set campaigns with the forms the path takes while the GPU is shared forced for every
 # query (K5 small rounds + prepared hypotheses + shared-GPU round sizes, K3 with 4 waves per view); FORMS=wide forces one
-# workgroup per model for every query (SFMLOC_P3P_WIDE_ALONE=2); FORMS=seq the sequential form of K5.
+# workgroup per model for every query (SFMLOC_P3P_WIDE_ALONE=2).
 R=${ROUND:-r04}; S=${SEED0:-0}; F=${FORMS:-default}
 O=gpurun_out/${R}_fuzz; mkdir -p $O
 sfx=""
 case $F in
   shared) export SFMLOC_P3P_SMALL=2 SFMLOC_P3P_PREP_AHEAD=2 SFMLOC_P3P_ADAPTIVE=1 SFMLOC_K3_WAVES_ALONE=4 SFMLOC_K3_WAVES_SHARED=4; sfx=_shared_forms;;
   wide) export SFMLOC_P3P_WIDE_ALONE=2; sfx=_wide_forms;;
-  seq) export SFMLOC_P3P_SEQ=2 SFMLOC_P3P_SEQ_WAVES=${SEQ_WAVES:-8}; sfx=_sequential_form;;
 esac
 run() { name=$1; lim=$2; shift 2
   timeout -k 10 $lim "$@" > $O/fuzz_${name}${sfx}.txt 2>&1; rc=$?; tail -1 $O/fuzz_${name}${sfx}.txt; [ $rc -eq 0 ] || exit $rc; }
