@@ -728,6 +728,85 @@ int sfmloc_sfm_debug_read(sfmloc_sfm *h, double *residual, double *min_cos);
 int sfmloc_sfm_json_rewrite(const char *in_path, const char *out_path);
 
 /* ------------------------------------------------------------------------- */
+/* Merging two maps (hulo_sfm/mergeSfM.py: mergeModel's RANSAC over 3D-3D matches, findMedianThres /                  */
+/* findMedianStructurePointsThres, merge_sfm_data / transform_sfm_data), the step between the localiser and           */
+/* OpenMVG_BA in the reference's mergeOneModel.  Points are host arrays [n*3]; A = model A's landmark, B = model B's, */
+/* a match's model is M (3 x 4, row major) with A ~ M [B; 1].  Every solver uses + - * / sqrt in f64 only, unfused,   */
+/* with fixed iteration counts, so tests/merge_np.py reproduces the bits.  Readings chosen and divergences:           */
+/*   sampling    round r draws 4 distinct matches with ac_sample<4> (OpenMVG UniformSample over Philox4x32-10,        */
+/*               key = params.seed, stage 3, the caller's stream, iteration r).  The reference uses Python's unseeded */
+/*               random.sample: which rounds are drawn differs, the rule for the winner does not.                     */
+/*   inlier      sqrt((dx dx + dy dy) + dz dz) < thres with d_i = (((m_i0 x0 + m_i1 x1) + m_i2 x2) + m_i3) - a_i.     */
+/*               A match with a non-finite coordinate (mergeSfM.get3DPointloc: inf for a missing id) is never an      */
+/*               inlier, and a sample that contains one counts nothing.                                               */
+/*   winner      the round with the most inliers among those that pass the ratio test and have a finite model and at  */
+/*               least one inlier; on ties the lowest round (the reference's sequential loop with its strict ">").    */
+/*               Rounds are reduced with one integer maximum of (count << 32 | 0xFFFFFFFF - round): no float atomics, */
+/*               the result does not depend on the launch geometry (params.rounds_per_launch).                        */
+/*   jacobi      eigen-decompositions are cyclic Jacobi, 10 sweeps over (p, q) in row order, theta = (a_qq - a_pp) /  */
+/*               (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta theta + 1)) (sign(0) = +1), c = 1 / sqrt(t t + 1), */
+/*               s = t c; columns, then rows, then a_pq = a_qp = 0; a zero a_pq skips its rotation.                   */
+/*   similarity  (model 0, build-defined reading: the reference imports Gohlke's transformations.py, whose text is    */
+/*               not in its tree) both sets centred on their means (sum / count), S_ij = sum b0_i a0_j, the rotation  */
+/*               maximising trace(R^T sum a0 b0^T) over proper rotations as Horn's unit quaternion: the eigenvector   */
+/*               of the largest eigenvalue (first on ties) of the 4 x 4 matrix N(S), normalised; scale =              */
+/*               sqrt(sum |a0|^2 / sum |b0|^2) (Gohlke's, not Umeyama's); t = mean(a) - s R mean(b).  The ratio of    */
+/*               singular values of s R is 1 by construction: a finite model passes the ratio test.                   */
+/*   affine      (model 1, mergeSfM.ransacAffineTransform) 4 points: [B; 1]^T X = A^T by Gaussian elimination with    */
+/*               partial pivoting (in column k the rows below are compared with row k in order and swapped when       */
+/*               strictly larger in magnitude), M = X^T.  The ratio test takes the singular values of M[:, :3] as     */
+/*               square roots of the eigenvalues of L^T L (jacobi): sqrt(max) / sqrt(min) < svd_ratio.                */
+/*   zero pivot  (divergence) a zero pivot makes the round count nothing, and makes the final fit fail (has_model 0): */
+/*               numpy.linalg.lstsq returns the minimum-norm answer on such degenerate (coplanar) samples instead.    */
+/*   final fit   on the winner's inliers (at least 4, else no model), ascending index: every sum is 256 partial sums  */
+/*               (partial t adds elements t, t + 256, ... in order, from 0.0) joined by a pairwise tree (t += t + 128,*/
+/*               then 64, ... 1).  Similarity: the means first, then the centred moments.  Affine: the 4 x 4 normal  */
+/*               equations ([B; 1][B; 1]^T) X = [B; 1] A^T through the same elimination (lstsq uses an SVD; the two   */
+/*               agree to rounding on well-conditioned sets).  The 4-point fits add their four terms in order.        */
+/*   median      nearest other point: min over j != i of (dx dx + dy dy) + dz dz, one square root of the minimum      */
+/*               (a duplicate at another index gives 0); the exact median of the n distances by a radix select on     */
+/*               their bit patterns, (lo + hi) / 2 for even n; 0 for n < 2; non-finite coordinates: SFMLOC_EINVAL.    */
+/*   transform   R' = M[:, :3] R, r'_ij = (m_i0 r_0j + m_i1 r_1j) + m_i2 r_2j (for a similarity that is s R: the      */
+/*               reference's quirk, kept); X' = ((m_i0 x0 + m_i1 x1) + m_i2 x2) + m_i3.                               */
+/*   caps        n > 2^24 or rounds >= 2^32: SFMLOC_ECAP, checked before anything else is touched.  n < 4: status 0, */
+/*               no model.                                                                                             */
+/* ------------------------------------------------------------------------- */
+enum { SFMLOC_MERGE_SIMILARITY = 0, SFMLOC_MERGE_AFFINE = 1 };
+
+typedef struct sfmloc_merge_params {
+  uint64_t seed;              /* sampling key, as sfmloc_params.seed (same default) */
+  int device;                 /* HIP device ordinal */
+  uint32_t rounds_per_launch; /* RANSAC rounds per kernel launch; 0 = the library's choice.  Same result either way */
+  int profile;                /* 1 = HIP events around the call's kernels: sfmloc_merge_last_ms */
+  int reserved;
+} sfmloc_merge_params;
+
+typedef struct sfmloc_merge_result {
+  double M[12];       /* the final fit on the winner's inliers; zeros when has_model = 0 */
+  uint32_t has_model; /* 1 = a round won, it has at least 4 inliers and the final fit is finite */
+  uint32_t round;     /* the winning round and its count (0, 0 when no round counted anything) */
+  uint32_t count;
+  uint32_t n_inliers; /* = count: the winner's inliers, listed in ascending index */
+} sfmloc_merge_result;
+
+void sfmloc_merge_default_params(sfmloc_merge_params *p);
+/* ransacTransform (mergeSfM.py:344-399) with `rounds` rounds (the callers pass n * ransacRoundMul).  inliers may be
+ * NULL; otherwise cap entries (SFMLOC_ECAP when the list is longer).  params may be NULL (the defaults). */
+int sfmloc_merge_ransac(const double *A, const double *B, uint64_t n, double thres, uint64_t rounds, double svd_ratio,
+                        int model, uint32_t stream, const sfmloc_merge_params *params, sfmloc_merge_result *out,
+                        uint32_t *inliers, uint32_t cap);
+/* getInliersByAffineTransform (mergeSfM.py:405-416): ascending indices of the matches within thres of M */
+int sfmloc_merge_inliers(const double *A, const double *B, uint64_t n, const double *M /*[12]*/, double thres,
+                         const sfmloc_merge_params *params, uint32_t *idx, uint32_t cap, uint32_t *n_out);
+/* the median of every point's distance to its nearest other point (findMedianThres / ...StructurePointsThres / k) */
+int sfmloc_merge_median_nn(const double *X, uint64_t n, const sfmloc_merge_params *params, double *median);
+/* M applied in place to nR rotations [nR*9] and nX points [nX*3] (merge_sfm_data, transform_sfm_data) */
+int sfmloc_merge_transform(const double *M /*[12]*/, double *R, uint64_t nR, double *X, uint64_t nX,
+                           const sfmloc_merge_params *params);
+/* device milliseconds between the events of the calling thread's last sfmloc_merge_* call made with profile = 1 */
+double sfmloc_merge_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
 /* Map-side matching: the reference's matchAKAZE /         */
 /* trackAKAZE on the same kernels.  Views are addressed by their index in the  */
 /* map's view table (ascending view id).                                       */

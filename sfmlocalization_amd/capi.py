@@ -106,6 +106,20 @@ class SfmViewResult(C.Structure):
                 ("P", C.c_double * 12), ("R", C.c_double * 9), ("center", C.c_double * 3)]
 
 
+class MergeParams(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("device", C.c_int), ("rounds_per_launch", C.c_uint32), ("profile", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class MergeResult(C.Structure):
+    _fields_ = [("M", C.c_double * 12), ("has_model", C.c_uint32), ("round", C.c_uint32), ("count", C.c_uint32),
+                ("n_inliers", C.c_uint32)]
+
+
+MERGE_SIMILARITY, MERGE_AFFINE = 0, 1
+MERGE_MODELS = {"similarity": MERGE_SIMILARITY, "affine": MERGE_AFFINE}
+
+
 class KernelStats(C.Structure):
     _fields_ = [("total_ms", C.c_double * K_COUNT), ("launches", C.c_uint64 * K_COUNT),
                 ("hamming_pairs", C.c_uint64), ("hamming_alg_bytes", C.c_uint64),
@@ -147,6 +161,8 @@ SYMBOLS = [
     "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
     "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
+    "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
+    "sfmloc_merge_transform", "sfmloc_merge_last_ms",
 ]
 
 _bound = False
@@ -381,6 +397,16 @@ def _L():
         L.sfmloc_sfm_read.argtypes = [C.c_void_p, U8P, F64P, F64P, U8P, U8P]
         L.sfmloc_sfm_debug_read.argtypes = [C.c_void_p, F64P, F64P]
         L.sfmloc_sfm_json_rewrite.argtypes = [C.c_char_p, C.c_char_p]
+        MPP = C.POINTER(MergeParams)
+        L.sfmloc_merge_default_params.restype = None
+        L.sfmloc_merge_default_params.argtypes = [MPP]
+        L.sfmloc_merge_ransac.argtypes = [F64P, F64P, C.c_uint64, C.c_double, C.c_uint64, C.c_double, C.c_int, C.c_uint32,
+                                          MPP, C.POINTER(MergeResult), U32P, C.c_uint32]
+        L.sfmloc_merge_inliers.argtypes = [F64P, F64P, C.c_uint64, F64P, C.c_double, MPP, U32P, C.c_uint32, U32P]
+        L.sfmloc_merge_median_nn.argtypes = [F64P, C.c_uint64, MPP, F64P]
+        L.sfmloc_merge_transform.argtypes = [F64P, F64P, C.c_uint64, F64P, C.c_uint64, MPP]
+        L.sfmloc_merge_last_ms.restype = C.c_double
+        L.sfmloc_merge_last_ms.argtypes = []
         _bound = True
     return L
 
@@ -1170,6 +1196,72 @@ class Sfm:
             self.close()
         except Exception:
             pass
+
+
+def merge_default_params(**overrides):
+    """sfmloc_merge_default_params: seed as default_params, device 0, rounds_per_launch 0 (the library's choice)"""
+    p = MergeParams()
+    _L().sfmloc_merge_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _pts(a):
+    return np.ascontiguousarray(a, np.float64).reshape(-1, 3)
+
+
+def merge_ransac(A, B, thres, rounds, svd_ratio=1.75, model=MERGE_SIMILARITY, stream=0, params=None):
+    """sfmloc_merge_ransac on matches A[n, 3] ~ M [B[n, 3]; 1] -> dict(M [3, 4] or None, round, count, inliers
+    ascending uint32)"""
+    A, B = _pts(A), _pts(B)
+    if A.shape != B.shape:
+        raise ValueError("A and B differ in shape")
+    n = A.shape[0]
+    res = MergeResult()
+    idx = np.empty(max(n, 1), np.uint32)
+    _check(_L().sfmloc_merge_ransac(_ptr(A, C.c_double), _ptr(B, C.c_double), n, float(thres), int(rounds), float(svd_ratio),
+                                    int(model), int(stream), C.byref(params) if params is not None else None, C.byref(res),
+                                    _ptr(idx, C.c_uint32), idx.size))
+    return {"M": np.array(res.M, np.float64).reshape(3, 4) if res.has_model else None, "round": int(res.round),
+            "count": int(res.count), "inliers": idx[:res.n_inliers].copy()}
+
+
+def merge_inliers(A, B, M, thres, params=None):
+    """sfmloc_merge_inliers: ascending indices of the matches within thres of M"""
+    A, B = _pts(A), _pts(B)
+    M = np.ascontiguousarray(M, np.float64).reshape(12)
+    idx = np.empty(max(A.shape[0], 1), np.uint32)
+    n = C.c_uint32(0)
+    _check(_L().sfmloc_merge_inliers(_ptr(A, C.c_double), _ptr(B, C.c_double), A.shape[0], _ptr(M, C.c_double), float(thres),
+                                     C.byref(params) if params is not None else None, _ptr(idx, C.c_uint32), idx.size,
+                                     C.byref(n)))
+    return idx[:n.value].copy()
+
+
+def merge_median_nn(X, params=None):
+    """sfmloc_merge_median_nn: the median distance to the nearest other point (0.0 for fewer than 2 points)"""
+    X = _pts(X)
+    out = C.c_double(0.0)
+    _check(_L().sfmloc_merge_median_nn(_ptr(X, C.c_double), X.shape[0], C.byref(params) if params is not None else None,
+                                       C.byref(out)))
+    return out.value
+
+
+def merge_transform(M, R=None, X=None, params=None):
+    """sfmloc_merge_transform -> (M[:, :3] R for every rotation [k, 3, 3], M [X; 1] for every point [k, 3])"""
+    M = np.ascontiguousarray(M, np.float64).reshape(12)
+    R = np.array(np.zeros((0, 3, 3)) if R is None else R, np.float64).reshape(-1, 3, 3)
+    X = np.array(np.zeros((0, 3)) if X is None else X, np.float64).reshape(-1, 3)
+    _check(_L().sfmloc_merge_transform(_ptr(M, C.c_double), _ptr(R, C.c_double), R.shape[0], _ptr(X, C.c_double), X.shape[0],
+                                       C.byref(params) if params is not None else None))
+    return R, X
+
+
+def merge_last_ms():
+    return float(_L().sfmloc_merge_last_ms())
 
 
 class BowTrainer:

@@ -19,6 +19,7 @@ GD uint64_t d2u(double x) { return (uint64_t)__double_as_longlong(x); }
 GD double u2d(uint64_t u) { return __longlong_as_double((long long)u); }
 GD bool is_nan(double x) { return (d2u(x) & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull; }
 GD bool is_inf(double x) { return (d2u(x) & 0x7FFFFFFFFFFFFFFFull) == 0x7FF0000000000000ull; }
+GD bool is_finite(double x) { return (d2u(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull; }
 GD double pos_inf() { return u2d(0x7FF0000000000000ull); }
 GD double q_nan() { return u2d(0x7FF8000000000000ull); }
 GD double dabs(double x) { return x < 0.0 ? -x : x; }
@@ -155,7 +156,7 @@ GD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   }
 }
 
-enum { STAGE_FMATRIX = 1, STAGE_P3P = 2 };
+enum { STAGE_FMATRIX = 1, STAGE_P3P = 2, STAGE_MERGE = 3 };
 
 GD uint32_t ac_draw(uint64_t seed, uint32_t stage, uint32_t stream, uint32_t iter, uint32_t i) {
   uint32_t c[4] = {iter, stream, i >> 2, stage};
