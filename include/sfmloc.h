@@ -190,6 +190,11 @@ void sfmloc_query_destroy(sfmloc_query *q);
  * LocalizeEngine.cc:337-340): sfmloc_localize_bow_begin / sfmloc_shard_bow_keys then take query_bow = NULL and no
  * per-call upload happens.  Synchronous. */
 int sfmloc_query_set_bow(sfmloc_query *q, const float *query_bow);
+/* Marks the query as taken by a camera nobody calibrated ("Uncalibrated queries" below); on = 0 clears the mark.  The
+ * property is the query's, not the map's: the same map serves marked and unmarked queries, also within one batch.  Any
+ * query that carries its image size can be marked, one over the caller's device arrays (sfmloc_query_create_view)
+ * included. */
+int sfmloc_query_set_uncalibrated(sfmloc_query *q, int on);
 /* A query over arrays that already ARE in device memory and stay the caller's -- e.g. slices of the buffer an all-gather
  * of extracted features wrote (images in on several ranks: the rank that owns a query extracts it, every rank matches
  * it).  Nothing is allocated or copied; the arrays must stay valid and unchanged while the query is in use.
@@ -849,8 +854,82 @@ void sfmloc_matches_destroy(sfmloc_matches *m);
 
 /* Parity probe: runs one of the f64 device building blocks over n items (tests compare with the oracle).
  * op: 0 log10, 1 sqrt+div, 2 cubic, 3 quartic, 4 seven-point, 5 P3P, 6 KRt_From_P, 7 sample,
- *     8 seven-point, wave-parallel form (K3's fast kernel; layout of op 4) */
+ *     8 seven-point, wave-parallel form (K3's fast kernel; layout of op 4), 11 six-point resection (below) */
 int sfmloc_debug_math(int device, int op, const double *in, int n, int in_stride, double *out, int out_stride);
+/* ------------------------------------------------------------------------- */
+/* Uncalibrated queries: the six-point resection ("resect6").                  */
+/* RESTATED, UNVERIFIED AGAINST OpenMVG: the library's sources were not at     */
+/* hand.  This section is what the code computes; tests/resect6_np.py restates */
+/* every operation in NumPy and the GPU tests compare bits with it.            */
+/*                                                                             */
+/* sfm::SfM_Localizer::Localize without an intrinsic: AC-RANSAC over           */
+/* ACKernelAdaptorResection<SixPointResectionSolver, ...>, then KRt_From_P on  */
+/* the winning projection matrix.  For a query marked with                     */
+/* sfmloc_query_set_uncalibrated, sfmloc_match_set, sfmloc_resection,          */
+/* sfmloc_localize, sfmloc_localize_bow, sfmloc_localize[_bow]_begin / _end    */
+/* and sfmloc_localize_batch do this instead of P3P.  Readings chosen:         */
+/*   2D points   the query's raw feature pixels: get_ud_pixel is not applied,  */
+/*               nothing of the map's intrinsic is used.                       */
+/*   N1          NormalizePoints in the (width, height) form: x' = (x - w/2)   */
+/*               / sqrt(w h), y' = (y - h/2) / sqrt(w h), computed as          */
+/*               x * (1/f) + (-(w/2) * (1/f)) with f = sqrt(w h) -- the same   */
+/*               expression the calibrated path evaluates with K.              */
+/*   sample      six distinct correspondences, one model: the counter-based    */
+/*               sampler of K5 (Philox4x32-10 keyed by params.seed, counter    */
+/*               {iteration, stream 0, draw / 4, stage 4}), sorted positions.  */
+/*   design      the 3D points are translated so that the first sampled one is */
+/*               the origin (X' = X - X0); two rows per point,                 */
+/*                 [X' Y' Z' 1  0 0 0 0  -xX' -xY' -xZ' -x]                     */
+/*                 [0 0 0 0  X' Y' Z' 1  -yX' -yY' -yZ' -y],  12 x 12.          */
+/*   null vector G = D^T D (every entry the sum over the 12 rows in row order, */
+/*               zeros included), then cyclic Jacobi on G: 10 sweeps over      */
+/*               (p, q) in row order, the rotation of `jacobi` in the          */
+/*               sfmloc_merge section, a zero g_pq skipped.  The model is the  */
+/*               column of V of the smallest diagonal entry (the first on      */
+/*               ties), row major 3 x 4, then P = P' [I | -X0].                */
+/*   rank        no model for the sample when the second smallest diagonal     */
+/*               entry is <= 1e-12 x the largest (coplanar or repeated points: */
+/*               the null space is not a line) or an entry of P is not finite. */
+/*   sign        P is negated when more than three of the six sampled points   */
+/*               have negative depth p3 . (X, 1).                              */
+/*   residual    squared reprojection error against the normalised points;     */
+/*               logalpha0 = log10(pi); NFA with MAX_MODELS 1, sample size 6.  */
+/*   AC-RANSAC   K5's: params.p3p_max_iteration, the 10 % reserve and the      */
+/*               early-iteration reduction, residual order (error, index).     */
+/*   refinement  params.refine_pose = 1: after KRt_From_P, R and t are refined  */
+/*               on the inliers' raw pixels (the calibrated path's Levenberg-  */
+/*               Marquardt, at most 20 steps) under the recovered K -- fx,     */
+/*               skew, cx, fy, cy -- held fixed; pose.K stays the recovered    */
+/*               one and pose.P = K [R|t] of the refined pose.                 */
+/*   afterwards  P = N1^-1 M; error_max = sqrt(e) * sqrt(w h) (pixels); more   */
+/*               than 2.5 * 6 inliers, then params.min_inliers (">");          */
+/*               KRt_From_P: pose.K is the RECOVERED intrinsic; center = -R^T  */
+/*               t.  A query with <= max(min_resection_points, 6) 2D-3D        */
+/*               matches is not localised (ok = 0, no error).                  */
+/* Divergences / left out:                                                     */
+/*   - the null vector comes from the fixed-sweep Jacobi of D^T D, not from an */
+/*     SVD of D: the bits differ from Eigen's, the tie rule is this one's.     */
+/*   - the rank rule and the majority form of the sign rule are this           */
+/*     library's.                                                              */
+/*   - the translation of the sample's 3D points to its first point before D   */
+/*     is built, undone by P = P' [I | -X0], is this library's conditioning of */
+/*     the 3D side; the sampled image points are NOT conditioned again per     */
+/*     sample (N1 of the image is the only conditioning of the 2D side).       */
+/*   - a scene in which no sample ever has a model ends with nfa = error_max = */
+/*     +inf and a zero pose, as a calibrated query without a model does.       */
+/*   - gang sessions (a marked query begun on a context inside                 */
+/*     sfmloc_gang_begin / _end) and the sharded entry points                  */
+/*     (sfmloc_shard_begin, sfmloc_shard_bow_keys, sfmloc_shard_begin_bow,     */
+/*     sfmloc_merge_begin[_packed] and their _batch forms): SFMLOC_EINVAL for  */
+/*     a marked query; sfmloc_last_error says so.                              */
+/* An unmarked query's result is bit for bit what it was.                      */
+/* ------------------------------------------------------------------------- */
+/* Parity probe of the whole stage: the six-point AC-RANSAC on the given n 2D-3D correspondences (pixels, world) of an
+ * image of width x height, on the map's own context with the map's params; the inliers' indices (AC-RANSAC's order)
+ * into inlier_idx when the pose is ok.  sfmloc_debug_math op 11 is the solver alone: a row of x[12] (six image points)
+ * and X[18] in, the model count (0 / 1) and the 12 model entries out. */
+int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d, uint32_t n, uint32_t width,
+                         uint32_t height, sfmloc_pose *out, uint32_t *inlier_idx, uint32_t cap);
 /* Test hook: allocation k (0..11) of the NEXT regrowth of a context's P3P workspace fails with SFMLOC_ENOMEM (one shot;
  * -1 disarms).  The regrowth has no counterpart in the reference (localization.cpp:479-509 has no size limit). */
 void sfmloc_debug_fail_p3p_alloc(int k);

@@ -67,8 +67,8 @@ class LocalizeEngine {
  public:
   LocalizeEngine(const std::string &sfmDataDir, const std::string &matchDir, const std::string &AmatFile,
                  double secondTestRatio, int ransacRound, double ransacPrecision, bool guidedMatching,
-                 int beaconKnnNum = 0, int bowKnnNum = 0, int device = 0)
-      : mMatchDir(matchDir), mBowKnnNum(bowKnnNum), mDevice(device) {
+                 int beaconKnnNum = 0, int bowKnnNum = 0, int device = 0, bool uncalibrated = false)
+      : mMatchDir(matchDir), mBowKnnNum(bowKnnNum), mDevice(device), mUncalibrated(uncalibrated) {
     if (beaconKnnNum) throw std::invalid_argument("iBeacon view pre-selection is out of scope");
     sfmloc_params p;
     sfmloc_default_params(&p);
@@ -184,6 +184,11 @@ class LocalizeEngine {
     sfmloc_query *q = nullptr;
     if (sfmloc_query_create(mMap, desc, kptXY, n, (uint32_t)width, (uint32_t)height, &q))
       throw std::runtime_error(sfmloc_last_error());
+    // (uncalibrated: the queries' camera has no intrinsic -- six-point resection, sfmloc.h "Uncalibrated queries")
+    if (mUncalibrated && sfmloc_query_set_uncalibrated(q, 1)) {
+      sfmloc_query_destroy(q);
+      throw std::runtime_error(sfmloc_last_error());
+    }
     sfmloc_pose pose;
     std::memset(&pose, 0, sizeof(pose));
     std::vector<uint32_t> pq(65536), pl(65536);  // a query has at most 65 535 features, hence inliers
@@ -301,6 +306,7 @@ class LocalizeEngine {
   double mA[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   bool mHaveA = false;
   int mBowKnnNum = 0, mDevice = 0;
+  bool mUncalibrated = false;
   int mProfile = 0;          // params.profile outside a timed call
   double mLastTotal = 0.0;   // wall time of the last localize call with bReturnTime
   float mThres = 0.001f;

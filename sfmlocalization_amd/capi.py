@@ -163,6 +163,7 @@ SYMBOLS = [
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
     "sfmloc_merge_transform", "sfmloc_merge_last_ms",
+    "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
 ]
 
 _bound = False
@@ -339,6 +340,9 @@ def _L():
         L.sfmloc_stats_reset.argtypes = [C.c_void_p]
         L.sfmloc_set_profile.argtypes = [C.c_void_p, C.c_int]
         L.sfmloc_query_set_bow.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.sfmloc_query_set_uncalibrated.argtypes = [C.c_void_p, C.c_int]
+        L.sfmloc_debug_resect6.argtypes = [C.c_void_p, F64P, F64P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Pose),
+                                           C.POINTER(C.c_uint32), C.c_uint32]
         L.sfmloc_context_signal.argtypes = [C.c_void_p, C.c_void_p]
         L.sfmloc_context_wait.argtypes = [C.c_void_p, C.c_void_p]
         L.sfmloc_shard_bow_keys.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p]
@@ -843,6 +847,19 @@ class Map:
 
     def resection(self, q):
         _check(_L().sfmloc_resection(self._h, q._h))
+
+    def debug_resect6(self, pt2d, pt3d, width, height):
+        """sfmloc_debug_resect6: the uncalibrated query's resection stage on given 2D-3D correspondences;
+        -> (Pose, inlier indices in AC-RANSAC's order)."""
+        p2 = np.ascontiguousarray(pt2d, dtype=np.float64).reshape(-1, 2)
+        p3 = np.ascontiguousarray(pt3d, dtype=np.float64).reshape(-1, 3)
+        assert p2.shape[0] == p3.shape[0]
+        pose = Pose()
+        ii = np.zeros(max(p2.shape[0], 1), np.uint32)
+        _check(_L().sfmloc_debug_resect6(self._h, _ptr(p2, C.c_double), _ptr(p3, C.c_double), p2.shape[0], int(width),
+                                         int(height), C.byref(pose), _ptr(ii, C.c_uint32), ii.size))
+        k = pose.n_inliers if pose.ok else 0
+        return pose, ii[:k].copy()
 
     def pose_read(self, cap=65536):
         pose = Pose()
@@ -1603,6 +1620,11 @@ class Query:
         """sfmloc_query_set_bow: the query's BoW vector becomes resident with it."""
         b = np.ascontiguousarray(bow, dtype=np.float32).ravel()
         _check(_L().sfmloc_query_set_bow(self._h, _ptr(b, C.c_float)))
+
+    def set_uncalibrated(self, on=True):
+        """sfmloc_query_set_uncalibrated: no intrinsic is assumed for this query's camera -- the six-point resection
+        instead of P3P, and the pose's K is the recovered one (include/sfmloc.h "Uncalibrated queries")."""
+        _check(_L().sfmloc_query_set_uncalibrated(self._h, 1 if on else 0))
 
     @classmethod
     def _over_device_arrays(cls, m, desc_ptr, kpt_ptr, kpt6_ptr, bow_ptr, n, width, height):

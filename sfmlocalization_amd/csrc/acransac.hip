@@ -1329,7 +1329,7 @@ __device__ void p3p_init_block(const P3pArgs &A, int n, int n_threads, double *s
     for (int i = 0; i < 12; ++i) st.model[i] = 0.0;
     go = 1;
     // localization.cpp:506 "cpt > MINUM_NUMBER_OF_POINT_RESECTION"; ACRANSAC: nData <= sizeSample -> nothing
-    if (n <= A.min_resection_points || n <= 3) {
+    if (n <= A.min_resection_points || n <= (A.uncal ? 6 : 3)) {
       st.done = 1;
       st.finished = 1;  // nothing to estimate: the result record written below is final
       go = 0;
@@ -1370,7 +1370,7 @@ __device__ void p3p_init_block(const P3pArgs &A, int n, int n_threads, double *s
     A.xn[2 * i + 1] = A.pt2d[2 * i + 1] * inv_f + cy;
   }
   // (the table pass wants n / 2 + 1 doubles of scratch: LDS up to kP3pMaxN correspondences, global beyond)
-  logcombi_tables_block(3, n, A.L10, n > kP3pMaxN ? A.ws_terms : s_terms, A.logc_n, A.logc_k, n_threads);
+  logcombi_tables_block(A.uncal ? 6 : 3, n, A.L10, n > kP3pMaxN ? A.ws_terms : s_terms, A.logc_n, A.logc_k, n_threads);
 }
 struct P3pInitBody {
   static constexpr int kGangThreads = kThreads;
@@ -1680,7 +1680,7 @@ __device__ __forceinline__ bool p3p_overtaken(const unsigned *first_hit, int b) 
   const unsigned v = __hip_atomic_load(first_hit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return (unsigned)__builtin_amdgcn_readfirstlane((int)v) < (unsigned)b;
 }
-template <int E>
+template <int E, int S = 3>  // S: the kernel's sample size (3: P3P, 6: the six-point resection)
 __device__ __forceinline__ void p3p_eval_regs(const double (&M)[12], NfaBest &r, double &r_err, const double *__restrict__ pt3d,
                                               const double *__restrict__ xn, const float *__restrict__ logc_n,
                                               const float *__restrict__ logc_k, uint32_t *iw, int lane, int n, double logalpha0,
@@ -1707,7 +1707,7 @@ __device__ __forceinline__ void p3p_eval_regs(const double (&M)[12], NfaBest &r,
   if (p3p_overtaken(first_hit, b)) return;
 #pragma unroll
   for (int rr = 0; rr < E; ++rr) iw[(rr << 6) + lane] = idx[rr];
-  r = best_nfa_regs_ilp<E>(key, n, 3, pos_inf(), logalpha0, 1.0, loge0, cn, ck);
+  r = best_nfa_regs_ilp<E>(key, n, S, pos_inf(), logalpha0, 1.0, loge0, cn, ck);
   if (r.k != 0x7FFFFFFF) r_err = u2d(sorted_key_at<E>(key, r.k - 1));
 }
 
@@ -1921,7 +1921,20 @@ __device__ __forceinline__ void p3p_eval_coop4_multi(const double (&M)[12], NfaB
 // hypothesis's models wait for each other; with a workgroup per model it is 8 per thread, four times as many waves on the
 // compute unit, and the four models of a hypothesis side by side.  Results go to slot 4 b + m; the replay takes the
 // best model of each hypothesis (the first on ties, as the sequential loop over a hypothesis's models does).
-template <int kForm>  // 0: the full form (k_p3p_round), 1: small (k_p3p_round_small)
+// While no model exists at all (n_in == 0) the sequential rule, arriving at the end of the main phase, moves one
+// iteration from the reserve to the budget and goes on: the iterations up to n_iter + n_reserve are then all run from
+// the same (identity) index set.  P3P nearly always has a model after its first iteration; the six-point kernel on a
+// degenerate scene (every sample coplanar) never has one, and a round that stopped at n_iter would hand the reserve
+// over one iteration per round.  Its rounds (kSolver 1) therefore evaluate up to the end of the reserve while n_in == 0;
+// the replay consumes them by the same rule, so the result is the sequential one.
+template <int kSolver>
+__device__ __forceinline__ long p3p_eval_end(const P3pState &st) {
+  return (long)st.n_iter + ((kSolver == 1 && st.n_in == 0) ? (long)st.n_reserve : 0l);
+}
+// kSolver 0: P3P (three points, up to four models).  1: the six-point resection of an uncalibrated query ("resect6"
+// below: six points, one model, solved ahead of the round by k_resect6_prepare -- a hypothesis always finds its model
+// in prep_models); everything behind the solver is the same text with the sample size and the model count changed.
+template <int kForm, int kSolver = 0>  // kForm 0: the full form (k_p3p_round), 1: small (k_p3p_round_small)
 __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch, int wide, unsigned char *smem_raw, int b,
                                                     int mdl) {
   constexpr bool kSmall = kForm == 1;
@@ -1929,10 +1942,10 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   const int n = st.n;
   if (b >= p3p_round_batch(n, batch) || b >= st.batch_limit) return;
   const long it = (long)st.iter + b;
-  if (it >= st.n_iter) return;
+  if (it >= p3p_eval_end<kSolver>(st)) return;
   P3pShared &S = *reinterpret_cast<P3pShared *>(smem_raw);
   const int tid = threadIdx.x;
-  constexpr int s = 3;
+  constexpr int s = kSolver == 1 ? 6 : 3;
   const int P = next_pow2(n);
   // An earlier hypothesis of this round is already known to change the index set: whatever this one finds, the replay
   // will not look at it (it stops at the FIRST such hypothesis, which is that one or an earlier one).  Nothing is
@@ -1942,7 +1955,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   // (the decision is taken behind the barrier that follows the solver / the fetch of the prepared models, below)
   __shared__ unsigned s_first_hit;
   // one model per workgroup: a wide launch with enough correspondences (and the LDS forms: n <= kP3pMaxN)
-  const bool single = !kSmall && wide && n <= kP3pMaxN;
+  const bool single = kSolver == 0 && !kSmall && wide && n <= kP3pMaxN;
   // (a wide launch that is not in single mode runs workgroups 0 .. batch - 1 only -- p3p_round.body.inc -- and is a plain
   // round: slot b, so that the inlier lists of a set above kP3pMaxN, whose stride is max_n, stay inside the 64 lists
   // ctx_p3p_reserve sizes them for)
@@ -1961,7 +1974,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   const bool fast = kSmall || P <= 256;
   constexpr int wave_seg = kSmall ? kP3pSmallN : kP3pWaveSeg;  // entries of S.idx a wave owns
   const double logalpha0 = det_log10(3.14159265358979323846);
-  const double loge0 = det_log10(4.0 * (double)(n - s));
+  const double loge0 = det_log10((kSolver == 1 ? 1.0 : 4.0) * (double)(n - s));  // log10(MAX_MODELS (n - s))
   // the NFA filter (above): only once a model exists, only while its tables fit the idle part of the LDS
   const double nfa_to_beat = st.min_nfa;
   // (the small form has no LDS for the tables: its models are sorted, which gives the same result)
@@ -1977,6 +1990,13 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
   if (have) {
     if (tid < 48) S.models[tid] = A.prep_models[48 * (size_t)b + tid];
     if (tid == 0) S.nm = A.prep_nm[b];
+  } else if (kSolver == 1) {
+    // (cannot happen: k_resect6_prepare covers exactly the hypotheses of the round that follows it.  Reported, not
+    // papered over: the query ends with SFMLOC_EHIP)
+    if (tid == 0) {
+      atomicOr(&A.state->status, 8);
+      S.nm = 0;
+    }
   } else if (tid == 0) {
     int32_t smp[3];
     ac_sample<3>(st.identity ? nullptr : A.vec_index, st.n_index, A.seed, STAGE_P3P, A.stream, (uint32_t)it, smp);
@@ -2004,7 +2024,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
     if (tid == 0) store_through(A.hyp_nfa + slot, pos_inf());
     return;
   }
-  if (!have && tid < nm) p3p_kneip_model(S.prep, tid, S.models + 12 * tid);  // the four roots' models side by side
+  if (kSolver == 0 && !have && tid < nm) p3p_kneip_model(S.prep, tid, S.models + 12 * tid);  // the four roots' models side by side
   if (filter) p3p_filter_scan(F, n);  // (two barriers inside: the models are visible behind them too)
   else __syncthreads();
   STAMP_P3P(stamp_round, b, 3);
@@ -2096,10 +2116,10 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
         const int stamp_round = 0;
 #endif
         switch (P >> 6) {
-          case 1: p3p_eval_regs<1>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
-          case 2: p3p_eval_regs<2>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
-          case 4: p3p_eval_regs<4>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
-          default: p3p_eval_regs<8>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
+          case 1: p3p_eval_regs<1, s>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
+          case 2: p3p_eval_regs<2, s>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
+          case 4: p3p_eval_regs<4, s>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
+          default: p3p_eval_regs<8, s>(M, r, r_err, pt3d, xn, logc_n, logc_k, iw, lane, n, logalpha0, loge0, stamp_round, b, first_hit); break;
         }
       } else {
         // (a lambda the compiler keeps out of line -- the text of p3p_eval_regs once more: with a call to that function in
@@ -2127,7 +2147,7 @@ __device__ __forceinline__ void p3p_eval_hypothesis(const P3pArgs &A, int batch,
           STAMP_P3P(stamp_round, b, 7);
 #pragma unroll
           for (int rr = 0; rr < E; ++rr) iw[(rr << 6) + lane] = idx[rr];
-          r = best_nfa_regs_ilp<E>(key, n, 3, pos_inf(), logalpha0, 1.0, loge0, cn, ck);
+          r = best_nfa_regs_ilp<E>(key, n, s, pos_inf(), logalpha0, 1.0, loge0, cn, ck);
           if (r.k != 0x7FFFFFFF) r_err = u2d(sorted_key_at<E>(key, r.k - 1));
         };
         switch (P >> 6) {
@@ -2213,9 +2233,12 @@ struct RefineShared {
   double delta[6];
 };
 
+// kGenK: the intrinsic is a general upper-triangular K with K(2,2) = 1 -- what KRt_From_P recovers for an uncalibrated
+// query -- given as Kg = {fx, skew, cx, fy, cy}; f / ppx / ppy are then unused.  The calibrated form is the text it was.
+template <bool kGenK = false>
 __device__ void normal_equations_wave0(const double *pt2d, const double *pt3d, const int32_t *inl, int n, double f,
                                        double ppx, double ppy, const double *Rm, const double *tv,
-                                       RefineShared &S) {
+                                       RefineShared &S, const double *Kg = nullptr) {
   const int tid = threadIdx.x;
   if (tid < 64) {
     const int k = tid >> 4, col = tid & 15;
@@ -2234,7 +2257,20 @@ __device__ void normal_equations_wave0(const double *pt2d, const double *pt3d, c
         const double iz = 1.0 / zc;
         // d(u or v)/d(Xc)
         double g0, g1, g2, res;
-        if ((row & 1) == 0) {
+        if (kGenK) {
+          if ((row & 1) == 0) {  // u = (fx xc + skew yc) / zc + cx
+            const double num = Kg[0] * xc + Kg[1] * yc;
+            g0 = Kg[0] * iz;
+            g1 = Kg[1] * iz;
+            g2 = -num * iz * iz;
+            res = (num * iz + Kg[2]) - pt2d[2 * p];
+          } else {  // v = fy yc / zc + cy
+            g0 = 0.0;
+            g1 = Kg[3] * iz;
+            g2 = -Kg[3] * yc * iz * iz;
+            res = (Kg[3] * yc * iz + Kg[4]) - pt2d[2 * p + 1];
+          }
+        } else if ((row & 1) == 0) {
           g0 = f * iz;
           g1 = 0.0;
           g2 = -f * xc * iz * iz;
@@ -2288,10 +2324,12 @@ __device__ void rotate_left(const double *w, const double *Rm, double *out) {
 }
 
 // returns the final cost; Rm/tv are updated in place (identically in every thread)
+template <bool kGenK = false>
 __device__ double refine_pose_block(const double *pt2d, const double *pt3d, const int32_t *inl, int n, double f,
-                                    double ppx, double ppy, double *Rm, double *tv, int max_iter, int *iters_out) {
+                                    double ppx, double ppy, double *Rm, double *tv, int max_iter, int *iters_out,
+                                    const double *Kg = nullptr) {
   __shared__ RefineShared S;
-  normal_equations_wave0(pt2d, pt3d, inl, n, f, ppx, ppy, Rm, tv, S);
+  normal_equations_wave0<kGenK>(pt2d, pt3d, inl, n, f, ppx, ppy, Rm, tv, S, Kg);
   double H[6][6], g[6], cost = S.H[6][6];
   for (int i = 0; i < 6; ++i) {
     g[i] = S.H[i][6];
@@ -2340,7 +2378,7 @@ __device__ double refine_pose_block(const double *pt2d, const double *pt3d, cons
     tn[1] = tv[1] + d[4];
     tn[2] = tv[2] + d[5];
     __syncthreads();  // S.H of the previous pass has been read by every thread
-    normal_equations_wave0(pt2d, pt3d, inl, n, f, ppx, ppy, Rn, tn, S);
+    normal_equations_wave0<kGenK>(pt2d, pt3d, inl, n, f, ppx, ppy, Rn, tn, S, Kg);
     const double c_new = S.H[6][6];
     if (c_new < cost) {
       const double rel = (cost - c_new) / cost;
@@ -2378,11 +2416,14 @@ struct P3pReplayShared {
 };
 // wide4: the launch has four result slots per hypothesis (4 b + m) and all four were written (one model per workgroup);
 // a wide launch whose query turned out small wrote slot 4 b only, a plain launch slot b
+template <int kSolver>
 __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int wide4, int slot_mul, P3pReplayShared &RS);
+template <int kSolver = 0>
 __device__ __forceinline__ void p3p_replay(const P3pArgs &A, int batch, int single_mode, P3pReplayShared &RS) {
   // (four result slots per hypothesis only in single mode; any other launch, wide or not, wrote slot b)
-  p3p_replay_impl(A, batch, single_mode, single_mode ? 4 : 1, RS);
+  p3p_replay_impl<kSolver>(A, batch, single_mode, single_mode ? 4 : 1, RS);
 }
+template <int kSolver>
 __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int wide, int slot_mul, P3pReplayShared &RS) {
   P3pState &st = *A.state;
   const int tid = threadIdx.x;
@@ -2396,7 +2437,7 @@ __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int
   // every thread replays the same scalar state machine; only the copies are cooperative
   long iter0 = st.iter, n_iter = st.n_iter, n_reserve = st.n_reserve;
   const long switch_iter0 = st.switch_iter;
-  const long n_iter_evaluated = n_iter;  // k_p3p_eval ran hypotheses iter0 <= it < min(iter0+batch, n_iter)
+  const long n_iter_evaluated = p3p_eval_end<kSolver>(st);  // the round ran hypotheses iter0 <= it < min(iter0+batch, this)
   double min_nfa = st.min_nfa, errmax = st.errmax;
   int n_in = st.n_in, n_index = st.n_index, identity = st.identity;
   const int identity0 = identity;  // still sampling uniformly when the round began
@@ -2408,7 +2449,7 @@ __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int
   double *const s_err = RS.err;
   int *const s_k = RS.k;
   for (int b = tid; b < batch && b < kP3pBatchMax; b += kThreads) {
-    const bool live = iter0 + b < n_iter;
+    const bool live = iter0 + b < n_iter_evaluated;
     int slot = slot_mul * b;
     if (wide && live) {  // the hypothesis's best model: strictly smaller NFA, the first model on ties
       slot = 4 * b;
@@ -2581,12 +2622,12 @@ struct P3pRoundBody {
   static constexpr int kGangThreads = kThreads;
   static constexpr int kGangMinWaves = 4;  // (128 VGPRs, as k_p3p_round)
   static __device__ __forceinline__ void run(P3pArgs A, int batch, int wide) {
-    constexpr int kForm = 0;
+    constexpr int kForm = 0, kSolver = 0;
 #include "p3p_round.body.inc"
   }
 };
 __global__ __launch_bounds__(kThreads, 4) void k_p3p_round(P3pArgs A, int batch, int wide) {
-  constexpr int kForm = 0;
+  constexpr int kForm = 0, kSolver = 0;
 #include "p3p_round.body.inc"
 }
 // the small form (above, at P3pShared): at most kP3pSmallN correspondences, a fraction of the registers
@@ -2594,14 +2635,207 @@ struct P3pRoundSmallBody {
   static constexpr int kGangThreads = kThreads;
   static constexpr int kGangMinWaves = 4;
   static __device__ __forceinline__ void run(P3pArgs A, int batch, int wide) {
-    constexpr int kForm = 1;
+    constexpr int kForm = 1, kSolver = 0;
 #include "p3p_round.body.inc"
   }
 };
 // (min. 4 waves per SIMD = at most 128 VGPRs: Kneip's solver spills -- one lane's chain, once per workgroup -- and the
 // round fits beside four workgroups of the lean shortlist scan, 4 x 96 VGPRs per SIMD, without evicting one)
 __global__ __launch_bounds__(kThreads, 4) void k_p3p_round_small(P3pArgs A, int batch, int wide) {
-  constexpr int kForm = 1;
+  constexpr int kForm = 1, kSolver = 0;
+#include "p3p_round.body.inc"
+}
+
+// ---------------------------------------------------------------------------------------------------
+// resect6: the six-point DLT resection of an uncalibrated query (include/sfmloc.h "Uncalibrated queries";
+// tests/resect6_np.py restates every operation and the GPU tests compare bits).  A hypothesis is six 2D-3D
+// correspondences: the 12 x 12 design matrix D (two rows per point, the 3D points translated so that the first sampled
+// one is the origin), G = D^T D, a cyclic Jacobi eigen-solve of G with a FIXED number of sweeps (merge.hip's
+// jacobi_fixed, written for N = 12), the eigenvector of the smallest eigenvalue as the 3 x 4 model.  Only + - * / sqrt.
+//
+// Four lanes per hypothesis, sixteen hypotheses per wave.  G and V (2 x 144 doubles per hypothesis) do not fit a lane's
+// registers next to anything else (576 VGPRs); they live in LDS (D, dead once G is formed, shares V's space: 39 KB per
+// wave), hypothesis-minor with a row pitch of 13 entries, and the lanes of a group are 16 apart (lane = 16 g + h): one
+// half of the wave -- what a 64-bit LDS access serves at once -- then holds two values of g whose entries are an odd
+// number of 16-double rows apart (13 in the column phase, 1 in the row phase), i.e. 32 distinct doubles, all banks, no
+// conflict.  Lane g of a group owns the rows
+// (and, in the row phase, the columns) k = g, g + 4, g + 8 of every rotation's update, so the dependent chain of a sweep is
+// a third of one lane's.  Every lane of a group computes the rotation's c and s itself from the same three entries (the
+// same bits); the phases of a rotation are separated by wave-level LDS fences (a wave's LDS operations execute in
+// order: only the compiler has to be kept from moving them).  Which lane computes an entry never changes its value.
+// ---------------------------------------------------------------------------------------------------
+constexpr int kR6Sweeps = 10;
+constexpr int kR6PerWave = 16;          // hypotheses per wave (four lanes each)
+constexpr double kR6RankTol = 1e-12;    // no model when the second smallest eigenvalue <= this * the largest
+constexpr int kR6Pitch = 13;            // entries per matrix row in LDS (12 used)
+struct R6Lds {
+  double G[12 * kR6Pitch * kR6PerWave];  // [row * kR6Pitch + col][hypothesis]
+  double V[12 * kR6Pitch * kR6PerWave];  // first the design matrix D, then V
+};
+static_assert(sizeof(R6Lds) <= 64 * 1024, "resect6: one wave's matrices in static LDS");
+
+// x: the six sampled image points (normalised), X: their 3D points; every lane of the group holds the same values.
+// Returns the number of models (0 or 1) and the model in M -- in every lane of the group.  Executed by the whole wave
+// (slots without a hypothesis run on zeros).
+__device__ __forceinline__ int resect6_solve_wave(R6Lds &L, const double (&x)[12], const double (&X)[18], double (&M)[12]) {
+  const int lane = threadIdx.x & 63, h = lane & 15, g = lane >> 4;
+  auto at = [h](int i, int j) { return (i * kR6Pitch + j) * kR6PerWave + h; };
+  double *const LD = L.V;  // the design matrix, until G is formed
+  const double X0 = X[0], Y0 = X[1], Z0 = X[2];
+#pragma unroll 1
+  for (int r = g; r < 12; r += 4) {  // rows 2 i and 2 i + 1: point i
+    const int i = r >> 1;
+    const double Xi = X[3 * i] - X0, Yi = X[3 * i + 1] - Y0, Zi = X[3 * i + 2] - Z0;
+    const double u = (r & 1) ? x[2 * i + 1] : x[2 * i];
+    const int o = (r & 1) ? 4 : 0, z = (r & 1) ? 0 : 4;
+    LD[at(r, o)] = Xi;
+    LD[at(r, o + 1)] = Yi;
+    LD[at(r, o + 2)] = Zi;
+    LD[at(r, o + 3)] = 1.0;
+    LD[at(r, z)] = 0.0;
+    LD[at(r, z + 1)] = 0.0;
+    LD[at(r, z + 2)] = 0.0;
+    LD[at(r, z + 3)] = 0.0;
+    LD[at(r, 8)] = -(u * Xi);
+    LD[at(r, 9)] = -(u * Yi);
+    LD[at(r, 10)] = -(u * Zi);
+    LD[at(r, 11)] = -u;
+  }
+  wave_lds_sync();
+#pragma unroll 1
+  for (int i = g; i < 12; i += 4)
+#pragma unroll 1
+    for (int j = 0; j < 12; ++j) {
+      double acc = LD[at(0, i)] * LD[at(0, j)];
+      for (int r = 1; r < 12; ++r) acc = acc + LD[at(r, i)] * LD[at(r, j)];
+      L.G[at(i, j)] = acc;
+    }
+  wave_lds_sync();  // D has been read by every lane: its space becomes V
+#pragma unroll 1
+  for (int i = g; i < 12; i += 4)
+    for (int j = 0; j < 12; ++j) L.V[at(i, j)] = i == j ? 1.0 : 0.0;
+  wave_lds_sync();
+#pragma unroll 1
+  for (int sw = 0; sw < kR6Sweeps; ++sw)
+#pragma unroll 1
+    for (int p = 0; p < 11; ++p)
+#pragma unroll 1
+      for (int q = p + 1; q < 12; ++q) {
+        const double apq = L.G[at(p, q)];
+        const bool skip = apq == 0.0;
+        const double theta = (L.G[at(q, q)] - L.G[at(p, p)]) / (2.0 * apq);
+        const double ath = theta < 0.0 ? -theta : theta;
+        const double t = (theta < 0.0 ? -1.0 : 1.0) / (ath + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0);
+        const double s = t * c;
+        wave_lds_sync();  // every lane has read the three entries
+        for (int k = g; k < 12; k += 4) {  // G J: columns p and q
+          const double akp = L.G[at(k, p)], akq = L.G[at(k, q)];
+          const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
+          L.G[at(k, p)] = skip ? akp : np_;
+          L.G[at(k, q)] = skip ? akq : nq_;
+        }
+        wave_lds_sync();
+        for (int k = g; k < 12; k += 4) {  // J^T (G J): rows p and q
+          const double apk = L.G[at(p, k)], aqk = L.G[at(q, k)];
+          const double np_ = c * apk - s * aqk, nq_ = s * apk + c * aqk;
+          L.G[at(p, k)] = skip ? apk : np_;
+          L.G[at(q, k)] = skip ? aqk : nq_;
+        }
+        wave_lds_sync();
+        if (g == 0 && !skip) {
+          L.G[at(p, q)] = 0.0;
+          L.G[at(q, p)] = 0.0;
+        }
+        for (int k = g; k < 12; k += 4) {  // (rows of V: a lane's own, no other lane reads them before the end)
+          const double vkp = L.V[at(k, p)], vkq = L.V[at(k, q)];
+          const double np_ = c * vkp - s * vkq, nq_ = s * vkp + c * vkq;
+          L.V[at(k, p)] = skip ? vkp : np_;
+          L.V[at(k, q)] = skip ? vkq : nq_;
+        }
+        wave_lds_sync();
+      }
+  // the smallest eigenvalue (the first on ties), the smallest of the others, the largest
+  int imin = 0;
+  double dmin = L.G[at(0, 0)], dmax_ = dmin;
+  for (int i = 1; i < 12; ++i) {
+    const double d = L.G[at(i, i)];
+    if (d < dmin) {
+      dmin = d;
+      imin = i;
+    }
+    dmax_ = d > dmax_ ? d : dmax_;
+  }
+  double dsec = pos_inf();
+  for (int i = 0; i < 12; ++i) {
+    const double d = L.G[at(i, i)];
+    if (i != imin && d < dsec) dsec = d;
+  }
+  double Pn[12];
+  for (int k = 0; k < 12; ++k) Pn[k] = L.V[at(k, imin)];
+  // back to the untranslated 3D frame: P = P' [I | -X0]
+  for (int r = 0; r < 3; ++r)
+    Pn[4 * r + 3] = Pn[4 * r + 3] - ((Pn[4 * r] * X0 + Pn[4 * r + 1] * Y0) + Pn[4 * r + 2] * Z0);
+  int behind = 0;
+  for (int i = 0; i < 6; ++i) {
+    const double w = ((Pn[8] * X[3 * i] + Pn[9] * X[3 * i + 1]) + Pn[10] * X[3 * i + 2]) + Pn[11];
+    behind += w < 0.0 ? 1 : 0;
+  }
+  bool ok = dsec > kR6RankTol * dmax_;  // (false for NaN)
+  for (int k = 0; k < 12; ++k) {
+    ok = ok && is_finite(Pn[k]);
+    M[k] = behind > 3 ? -Pn[k] : Pn[k];
+  }
+  return ok ? 1 : 0;
+}
+
+// the models of the round that follows on the stream: hypotheses st.iter .. st.iter + (what that round evaluates) - 1,
+// into prep_models / prep_nm, which p3p_eval_hypothesis reads ("Prepared ahead": the same hand-over)
+__global__ __launch_bounds__(64) void k_resect6_prepare(P3pArgs A, int batch) {
+  __shared__ R6Lds L;
+  P3pState &st = *A.state;
+  if (st.done) return;
+  const int n = st.n;
+  long lim = p3p_round_batch(n, batch);
+  if (lim > st.batch_limit) lim = st.batch_limit;
+  if (lim > p3p_eval_end<1>(st) - st.iter) lim = p3p_eval_end<1>(st) - st.iter;
+  if (lim > kP3pBatchMax) lim = kP3pBatchMax;
+  const int lane = threadIdx.x & 63;
+  const int h = (int)blockIdx.x * kR6PerWave + (lane & 15);
+  if ((long)blockIdx.x * kR6PerWave >= lim) return;  // (uniform: nothing for this wave)
+  const bool valid = h < lim;
+  double x[12], X[18], M[12];
+  for (int i = 0; i < 12; ++i) x[i] = 0.0;
+  for (int i = 0; i < 18; ++i) X[i] = 0.0;
+  if (valid) {
+    int32_t smp[6];
+    ac_sample<6>(st.identity ? nullptr : A.vec_index, st.n_index, A.seed, STAGE_RESECT6, A.stream, (uint32_t)(st.iter + h), smp);
+    for (int i = 0; i < 6; ++i) {
+      x[2 * i] = A.xn[2 * smp[i]];
+      x[2 * i + 1] = A.xn[2 * smp[i] + 1];
+      X[3 * i] = A.pt3d[3 * smp[i]];
+      X[3 * i + 1] = A.pt3d[3 * smp[i] + 1];
+      X[3 * i + 2] = A.pt3d[3 * smp[i] + 2];
+    }
+  }
+  const int nm = resect6_solve_wave(L, x, X, M);
+  if (valid && (lane >> 4) == 0) {
+    for (int q = 0; q < 12; ++q) A.prep_models[48 * (size_t)h + q] = M[q];
+    A.prep_nm[h] = nm;
+  }
+  if (blockIdx.x == 0 && lane == 0) {  // (the other workgroups read neither word)
+    st.prep_iter = st.iter;
+    st.prep_n = (int)lim;
+  }
+}
+
+// the rounds of an uncalibrated query: k_p3p_round / k_p3p_round_small with the six-point kernel's constants
+__global__ __launch_bounds__(kThreads, 4) void k_resect6_round(P3pArgs A, int batch, int wide) {
+  constexpr int kForm = 0, kSolver = 1;
+#include "p3p_round.body.inc"
+}
+__global__ __launch_bounds__(kThreads, 4) void k_resect6_round_small(P3pArgs A, int batch, int wide) {
+  constexpr int kForm = 1, kSolver = 1;
 #include "p3p_round.body.inc"
 }
 
@@ -2645,7 +2879,7 @@ struct P3pFinishBody {
     __syncthreads();
     int n_final = n_in;
     if (min_nfa >= 0.0) n_final = 0;
-    const bool resection = (double)n_final > 2.5 * 3;
+    const bool resection = (double)n_final > 2.5 * (A.uncal ? 6 : 3);  // 2.5 * MINIMUM_SAMPLES
     const bool ok = resection && n_final > A.min_inliers;
     Pose &R = *A.result;
     if (ok)
@@ -2670,7 +2904,19 @@ struct P3pFinishBody {
     int refine_iters = 0;
     if (ok) {
       krt_from_p(Pm, Kq, Rq, tq);
-      if (A.refine_pose) {
+      if (A.refine_pose && A.uncal) {
+        // an uncalibrated query: R and t refined on the raw pixels with the RECOVERED K held fixed; P = K [R|t] again
+        __syncthreads();
+        const double Kg[5] = {Kq[0], Kq[1], Kq[2], Kq[4], Kq[5]};
+        refine_cost = refine_pose_block<true>(A.pt2d, A.pt3d, A.best_inl, n_final, 0.0, 0.0, 0.0, Rq, tq, 20, &refine_iters,
+                                              Kg);
+        for (int j = 0; j < 4; ++j) {
+          const double c0 = j < 3 ? Rq[j] : tq[0], c1 = j < 3 ? Rq[3 + j] : tq[1], c2 = j < 3 ? Rq[6 + j] : tq[2];
+          Pm[j] = (Kg[0] * c0 + Kg[1] * c1) + Kg[2] * c2;
+          Pm[4 + j] = Kg[3] * c1 + Kg[4] * c2;
+          Pm[8 + j] = c2;
+        }
+      } else if (A.refine_pose) {
         __syncthreads();  // inlier_idx written above by all threads
         refine_cost = refine_pose_block(A.pt2d, A.pt3d, A.best_inl, n_final, A.focal, A.ppx, A.ppy, Rq, tq, 20,
                                         &refine_iters);
@@ -2823,6 +3069,26 @@ __global__ __launch_bounds__(64) void k_debug_sort(const double *in, int n_rows,
   }
 }
 
+// op 11: resect6_solve_wave, four lanes per row; in: x[12] (six image points), X[18]; out: the model count, the model
+__global__ __launch_bounds__(64) void k_debug_resect6(const double *in, int n, int in_stride, double *out, int out_stride) {
+  __shared__ R6Lds L;
+  const int lane = threadIdx.x & 63;
+  const int i = (int)blockIdx.x * kR6PerWave + (lane & 15);
+  double x[12], X[18], M[12];
+  for (int k = 0; k < 12; ++k) x[k] = 0.0;
+  for (int k = 0; k < 18; ++k) X[k] = 0.0;
+  if (i < n) {
+    for (int k = 0; k < 12; ++k) x[k] = in[(size_t)i * in_stride + k];
+    for (int k = 0; k < 18; ++k) X[k] = in[(size_t)i * in_stride + 12 + k];
+  }
+  const int nm = resect6_solve_wave(L, x, X, M);
+  if (i < n && (lane >> 4) == 0) {
+    double *o = out + (size_t)i * out_stride;
+    o[0] = (double)nm;
+    for (int k = 0; k < 12; ++k) o[1 + k] = M[k];
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
@@ -2840,6 +3106,9 @@ int launch_debug_math(int op, const double *d_in, int n, int in_stride, double *
     hipLaunchKernelGGL(k_debug_wave7, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride);
   else if (op == 9)
     hipLaunchKernelGGL(k_debug_sort, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride);
+  else if (op == 11)
+    hipLaunchKernelGGL(k_debug_resect6, dim3((n + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, d_in, n, in_stride, d_out,
+                       out_stride);
   else
     hipLaunchKernelGGL(k_debug_math, dim3((n + 63) / 64), dim3(64), 0, s, op, d_in, n, in_stride, d_out, out_stride);
   SFM_HIP(hipGetLastError());
@@ -3230,7 +3499,7 @@ int launch_select_candidates(Ctx *c, const Query *q, const unsigned char *parts,
   }
   sfm_launch<MatchSetFinishBody>(c, k_match_set_finish, dim3(1), dim3(1024), 0, parts, n_parts, part_bytes, cap,
                                  c->d_best64, c->d_winner, q->n, q->d_kpt, c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark,
-                                 c->d_pt2d, c->d_pt3d, c->map->intrinsic_type == 3 ? 1 : 0, c->map->focal, c->map->ppx,
+                                 c->d_pt2d, c->d_pt3d, (c->map->intrinsic_type == 3 && !c->p3p_uncal) ? 1 : 0, c->map->focal, c->map->ppx,
                                  c->map->ppy, c->map->k1, c->map->k2, c->map->k3, L, make_p3p_args(c));
   SFM_HIP(hipGetLastError());
   c->p3p_init_fused = true;  // launch_p3p_init is then a no-op for this query
@@ -3276,6 +3545,15 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.focal = c->p3p_own_K ? c->p3p_K[0] : m->focal;
   A.ppx = c->p3p_own_K ? c->p3p_K[1] : m->ppx;
   A.ppy = c->p3p_own_K ? c->p3p_K[2] : m->ppy;
+  // an uncalibrated query: no intrinsic at all.  The conditioning N1 of its image (sfmloc.h "Uncalibrated queries") has
+  // the form of a K^-1 -- x / f - pp / f with f = sqrt(w h), pp = the image centre --, so the normalisation, the
+  // un-normalisation of the model and of the error are the calibrated path's with these three numbers
+  A.uncal = c->p3p_uncal ? 1 : 0;
+  if (c->p3p_uncal) {
+    A.focal = c->p3p_N[0];
+    A.ppx = c->p3p_N[1];
+    A.ppy = c->p3p_N[2];
+  }
   A.max_iteration = m->params.p3p_max_iteration;
   A.min_resection_points = m->params.min_resection_points;
   A.min_inliers = m->params.min_inliers;
@@ -3291,6 +3569,7 @@ static P3pArgs make_p3p_args(Ctx *c) {
   // (SFMLOC_P3P_PREP_AHEAD: 0 never, 1 when the GPU is shared -- the default --, 2 always: comparison runs and tests)
   static const int env_prep = env_int("SFMLOC_P3P_PREP_AHEAD", 1);
   A.prep_ahead = env_prep == 2 || (env_prep == 1 && A.adaptive_batch);
+  if (A.uncal) A.prep_ahead = 0;  // (the replay's hand-over solves P3P; k_resect6_prepare is the six-point kernel's)
   static const int env_quarters = env_int("SFMLOC_P3P_ADAPT_QUARTERS", 12);
   static const int env_floor = env_int("SFMLOC_P3P_ADAPT_FLOOR", 64);
   A.adapt_quarters = env_quarters;
@@ -3319,6 +3598,23 @@ int launch_p3p_round(Ctx *c, int batch) {
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p3p_round),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
   SFM_HIP(attr);
+  if (A.uncal) {
+    // an uncalibrated query (never in a gang session: capi.hip refuses): its round's models first, sixteen hypotheses
+    // per wave, then the round in the plain shape -- one model per hypothesis, nothing for a wide launch to spread
+    static const hipError_t attr6 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resect6_round),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
+    SFM_HIP(attr6);
+    hipStream_t s = (hipStream_t)c->stream;
+    hipLaunchKernelGGL(k_resect6_prepare, dim3((batch + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, A, batch);
+    if (c->p3p_small) {
+      constexpr size_t lds_small = std::max(offsetof(P3pShared, idx) + 4 * kP3pSmallN * sizeof(uint32_t), sizeof(P3pReplayShared));
+      hipLaunchKernelGGL(k_resect6_round_small, dim3(batch), dim3(kThreads), (uint32_t)lds_small, s, A, batch, 0);
+    } else {
+      hipLaunchKernelGGL(k_resect6_round, dim3(batch), dim3(kThreads), (uint32_t)lds, s, A, batch, 0);
+    }
+    SFM_HIP(hipGetLastError());
+    return SFMLOC_OK;
+  }
   // from 513 features on a query may have that many correspondences: four workgroups per hypothesis, one model each
   // (p3p_eval_hypothesis); the result slots then are 4 b + m, of which there are kP3pSlots
   // -- and only while queries of this map HAVE had that many lately (Map::p3p_wide_credit, refreshed by every finished

@@ -502,6 +502,27 @@ int ctx_match_set(Ctx *c, Query *q) {
   return launch_match_set(c, q, c->last_n_sel, c->last_all_views);
 }
 
+}  // namespace
+
+// Which camera K5 assumes for the query the context is about to serve (sfmloc.h "Uncalibrated queries"): the map's
+// intrinsic, or none -- the six-point resection on points conditioned by N1 of the query's image.
+void ctx_set_uncalibrated_camera(Ctx *c, uint32_t width, uint32_t height) {
+  c->p3p_uncal = true;  // N1 of the image: x' = (x - w / 2) / sqrt(w h)
+  c->p3p_N[0] = sqrt((double)width * (double)height);
+  c->p3p_N[1] = 0.5 * (double)width;
+  c->p3p_N[2] = 0.5 * (double)height;
+}
+int ctx_set_query_camera(Ctx *c, const Query *q, const char *who) {
+  c->p3p_uncal = false;
+  if (!q->uncalibrated) return SFMLOC_OK;
+  SFM_CHECK(!c->stream.gang, SFMLOC_EINVAL, "%s: an uncalibrated query is not supported in a gang session", who);
+  SFM_CHECK(q->width > 0 && q->height > 0, SFMLOC_EINVAL, "%s: query image size missing", who);
+  ctx_set_uncalibrated_camera(c, q->width, q->height);
+  return SFMLOC_OK;
+}
+
+namespace {
+
 // Enqueues P3P AC-RANSAC rounds.  The device-side state machine turns surplus rounds into no-ops, so a fixed
 // number is enqueued without synchronising.
 int ctx_resection_enqueue(Ctx *c, bool first_call) {
@@ -624,6 +645,7 @@ int ctx_resection_wait(Ctx *c) {
     SFM_HIP(hipStreamSynchronize(c->stream));
     c->stream.dirty = false;
     if (h->state.done) {
+      SFM_CHECK((h->pose.status & 8) == 0, SFMLOC_EHIP, "six-point resection: a round found no prepared model (internal)");
       // what the next queries' rounds look like (launch_p3p_round): this one's number of correspondences
       if (h->state.n > 512) c->map->p3p_wide_credit.store(64, std::memory_order_relaxed);
       else if (c->map->p3p_wide_credit.load(std::memory_order_relaxed) > 0) c->map->p3p_wide_credit.fetch_sub(1, std::memory_order_relaxed);
@@ -666,7 +688,9 @@ static int diag_stop_after() {
 static int ctx_localize_begin_impl(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel) {
   c->t_begin = now_s();
   ClearedScope cs{c};
-  int rc = ctx_p3p_reserve(c, q->n);
+  int rc = ctx_set_query_camera(c, q, "sfmloc_localize");
+  if (rc) return rc;
+  rc = ctx_p3p_reserve(c, q->n);
   if (rc) return rc;
   rc = ctx_reset_for_query(c, q);
   if (rc) return rc;
@@ -1295,6 +1319,13 @@ int sfmloc_query_set_bow(sfmloc_query *query, const float *query_bow) {
   return SFMLOC_OK;
 }
 
+int sfmloc_query_set_uncalibrated(sfmloc_query *query, int on) {
+  SFM_CHECK(query, SFMLOC_EINVAL, "sfmloc_query_set_uncalibrated: null argument");
+  Query *q = reinterpret_cast<Query *>(query);
+  q->uncalibrated = on != 0;
+  return SFMLOC_OK;
+}
+
 // ----- stage-level API on the map's own context -------------------------------------------------------
 
 int sfmloc_match_putative(sfmloc_map *map, sfmloc_query *query, const uint32_t *view_sel, uint32_t n_sel) {
@@ -1462,6 +1493,8 @@ int sfmloc_match_set(sfmloc_map *map, sfmloc_query *query) {
   int rc = check_stage(m->ctx0, q, "sfmloc_match_set");
   if (rc) return rc;
   SFM_HIP(hipSetDevice(m->device));
+  rc = ctx_set_query_camera(m->ctx0, q, "sfmloc_match_set");
+  if (rc) return rc;
   rc = ctx_p3p_reserve(m->ctx0, q->n);  // K5's start runs at the end of this stage (k_match_set_finish)
   if (rc) return rc;
   return ctx_match_set(m->ctx0, q);
@@ -1497,6 +1530,8 @@ int sfmloc_resection(sfmloc_map *map, sfmloc_query *query) {
   int rc = check_stage(c, q, "sfmloc_resection");
   if (rc) return rc;
   SFM_HIP(hipSetDevice(m->device));
+  rc = ctx_set_query_camera(c, q, "sfmloc_resection");
+  if (rc) return rc;
   rc = ctx_p3p_reserve(c, q->n);
   if (rc) return rc;
   {
@@ -1603,6 +1638,8 @@ int sfmloc_shard_begin(sfmloc_context *ctx, sfmloc_query *query, const uint32_t 
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   Query *q = reinterpret_cast<Query *>(query);
   SFM_CHECK(q->map == c->map, SFMLOC_EINVAL, "sfmloc_shard_begin: query belongs to another map");
+  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
+            "sfmloc_shard_begin: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_begin: context has a query in flight");
   SFM_HIP(hipSetDevice(c->map->device));
   ctx_mark_busy(c);  // until sfmloc_context_sync
@@ -1636,6 +1673,8 @@ int sfmloc_shard_bow_keys(sfmloc_context *ctx, sfmloc_query *query, const float 
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
   SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: query belongs to another map");
+  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
+            "sfmloc_shard_bow_keys: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
   SFM_CHECK(m->bow_dim > 0 && m->d_bow, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: the map has no .bow vectors");
   SFM_CHECK(query_bow || q->d_bow, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: no BoW vector");
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: context has a query in flight");
@@ -1656,6 +1695,8 @@ int sfmloc_shard_begin_bow(sfmloc_context *ctx, sfmloc_query *query, const void 
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
   SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: query belongs to another map");
+  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
+            "sfmloc_shard_begin_bow: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: context has a query in flight");
   SFM_CHECK(!c->merge_only, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: this context was created for sfmloc_merge_begin only");
   if (part_stride_keys == 0) part_stride_keys = knn;
@@ -1794,6 +1835,8 @@ static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
   SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_merge_begin: query belongs to another map");
+  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
+            "sfmloc_merge_begin: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_merge_begin: context has a query in flight");
   SFM_CHECK(m->focal > 0.0, SFMLOC_EINVAL, "sfmloc_merge_begin: the map has no intrinsic");
   SFM_CHECK(q->n == 0 || q->d_kpt, SFMLOC_EINVAL, "sfmloc_merge_begin: the query was created without keypoints");
@@ -1805,6 +1848,7 @@ static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void
   // pipeline of dist.py -- K5 takes its shared-GPU round sizes; sfmloc_localize_end uncounts)
   ctx_mark_busy(c);
   {
+    c->p3p_uncal = false;  // (refused above; the context may have served an uncalibrated query before)
     const int rcr = ctx_p3p_reserve(c, q->n);
     if (rcr) {
       ctx_mark_idle(c);
@@ -2116,6 +2160,40 @@ int sfmloc_merge_batch_begin(sfmloc_context *const *ctxs, uint32_t n, sfmloc_que
     rc = sfmloc_merge_begin_packed(ctxs[k], queries[k], packed_all_dev, n_parts, part_stride, n_queries, budget, query_index[k]);
   const int rc_end = n > 1 ? sfmloc_gang_end(ctxs, n) : SFMLOC_OK;
   return rc ? rc : rc_end;
+}
+
+int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d, uint32_t n, uint32_t width,
+                         uint32_t height, sfmloc_pose *out, uint32_t *inlier_idx, uint32_t cap) {
+  SFM_CHECK(map && pt2d && pt3d && out && n > 0 && width > 0 && height > 0, SFMLOC_EINVAL, "sfmloc_debug_resect6: bad argument");
+  SFM_CHECK(n <= 65536u, SFMLOC_EINVAL, "sfmloc_debug_resect6: more than 65536 correspondences");
+  Map *m = reinterpret_cast<Map *>(map);
+  Ctx *c = m->ctx0;
+  SFM_CHECK(c->in_flight == nullptr && !c->stream.gang, SFMLOC_EINVAL, "sfmloc_debug_resect6: the map's context is busy");
+  SFM_HIP(hipSetDevice(m->device));
+  int rc = ctx_p3p_reserve(c, n);
+  if (rc) return rc;
+  std::vector<uint32_t> iota(n);
+  for (uint32_t i = 0; i < n; ++i) iota[i] = i;
+  SFM_HIP(hipStreamSynchronize(c->stream));
+  SFM_HIP(hipMemcpy(c->d_pt2d, pt2d, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice));
+  SFM_HIP(hipMemcpy(c->d_pt3d, pt3d, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice));
+  SFM_HIP(hipMemcpy(c->d_ms_qfeat, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  SFM_HIP(hipMemcpy(c->d_ms_landmark, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  SFM_HIP(hipMemcpy(c->d_ms_n, &n, sizeof(uint32_t), hipMemcpyHostToDevice));
+  ctx_set_uncalibrated_camera(c, width, height);
+  c->p3p_init_fused = false;  // K5's init reads the count written above
+  rc = ctx_resection_begin(c);
+  if (!rc) rc = ctx_resection_wait_done(c);
+  c->p3p_uncal = false;
+  if (rc) return rc;
+  const HostResult *h = reinterpret_cast<const HostResult *>(c->h_result);
+  *out = h->pose;
+  SFM_CHECK((out->status & 4) == 0, SFMLOC_ECAP, "more than %u 2D-3D correspondences (P3P workspace)", c->p3p_cap);
+  if (inlier_idx && out->ok && out->n_inliers > 0) {
+    SFM_CHECK(cap >= (uint32_t)out->n_inliers, SFMLOC_ECAP, "sfmloc_debug_resect6: cap %u < %d inliers", cap, out->n_inliers);
+    SFM_HIP(hipMemcpy(inlier_idx, c->d_inlier_idx, (size_t)out->n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return SFMLOC_OK;
 }
 
 void sfmloc_debug_fail_p3p_alloc(int k) { sfmloc::g_test_fail_alloc.store(k, std::memory_order_relaxed); }

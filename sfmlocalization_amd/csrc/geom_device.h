@@ -156,7 +156,7 @@ GD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   }
 }
 
-enum { STAGE_FMATRIX = 1, STAGE_P3P = 2, STAGE_MERGE = 3 };
+enum { STAGE_FMATRIX = 1, STAGE_P3P = 2, STAGE_MERGE = 3, STAGE_RESECT6 = 4 };
 
 GD uint32_t ac_draw(uint64_t seed, uint32_t stage, uint32_t stream, uint32_t iter, uint32_t i) {
   uint32_t c[4] = {iter, stream, i >> 2, stage};

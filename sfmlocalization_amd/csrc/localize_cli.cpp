@@ -373,7 +373,7 @@ int main(int argc, char **argv) {
   const Args a = parse_args(argc, argv);
   if (a.pos.size() < 4 || a.opt.count("h") || a.opt.count("help")) {
     printf("usage: OpenMVGLocalization_AKAZE <queryImage|dir> <sfmDataDir> <matchDir> <outputFolder> [-f=0.6] [-r=200] "
-           "[-k=0] [-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR]\n");
+           "[-k=0] [-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated]\n");
     return 1;
   }
   const std::string query = a.pos[0], sfm_dir = a.pos[1], match_dir = a.pos[2], out_dir = a.pos[3];
@@ -392,6 +392,11 @@ int main(int argc, char **argv) {
   std::string gm = a.get({"gm", "guidedMatch"}, "false");   // localization.cpp:82,183
   for (char &ch : gm) ch = (char)tolower(ch);
   const bool guided = gm == "1" || gm == "true" || gm == "yes";
+  // -u: the query images come from a camera nobody calibrated -- six-point resection, the result's K is the recovered
+  // one (sfmloc.h "Uncalibrated queries"); not in the reference's tool, whose Localize call always passes the intrinsic
+  std::string un = a.get({"u", "uncalibrated"}, "false");
+  for (char &ch : un) ch = (char)tolower(ch);
+  const bool uncalibrated = un == "1" || un == "true" || un == "yes";
   const std::string featdir_opt = a.get({"featdir"}, "");
   const int device = atoi(a.get({"device"}, "0").c_str());
   if (every <= 0) every = 1;
@@ -550,7 +555,8 @@ int main(int argc, char **argv) {
         }
       }
       sfmloc_query *q = nullptr;
-      if (sfmloc_query_create(map, desc.data(), xy.data(), nq, (uint32_t)w, (uint32_t)h, &q)) {
+      if (sfmloc_query_create(map, desc.data(), xy.data(), nq, (uint32_t)w, (uint32_t)h, &q) ||
+          (uncalibrated && sfmloc_query_set_uncalibrated(q, 1))) {
         // as for any error on ONE image: this image gets the failure form, the run goes on (the reference writes a
         // result file for every image, localization.cpp:441,530)
         fprintf(stderr, "%s: %s\n", img.c_str(), sfmloc_last_error());

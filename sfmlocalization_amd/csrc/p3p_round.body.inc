@@ -3,7 +3,8 @@
 // before the inlining, and the scan lost 20 % that way)
   P3pState &st = *A.state;
   if (st.done) return;
-  // (kForm: a constant of the including function -- 0 the full form, 1 the small form k_p3p_round_small)
+  // (kForm: a constant of the including function -- 0 the full form, 1 the small form k_p3p_round_small; kSolver: 0 P3P,
+  // 1 the six-point resection of an uncalibrated query)
   // a small round on a set it is not built for: not this launch's business (every workgroup leaves, nothing is counted or
   // written; the host queues the query's rounds again in the full form)
   if (kForm == 1 && st.n > kP3pSmallN) return;
@@ -19,7 +20,7 @@
   extern __shared__ unsigned char smem_raw[];
   {
     const int per_model = wide ? (int)(gridDim.x >> 2) : (int)gridDim.x;  // hypotheses of the launch
-    p3p_eval_hypothesis<kForm>(A, batch, wide, smem_raw, (int)blockIdx.x % per_model, (int)blockIdx.x / per_model);
+    p3p_eval_hypothesis<kForm, kSolver>(A, batch, wide, smem_raw, (int)blockIdx.x % per_model, (int)blockIdx.x / per_model);
   }
   __shared__ unsigned s_ticket;
   // producer rule (MI355X_MICROARCH.md, hand-over table): EVERY wave that stored results waits for its own stores to
@@ -31,4 +32,4 @@
   __syncthreads();
   if (s_ticket != expected_arrivals - 1u) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // nothing cached here predates the other workgroups' results
-  p3p_replay(A, batch, single_mode, *reinterpret_cast<P3pReplayShared *>(smem_raw));
+  p3p_replay<kSolver>(A, batch, single_mode, *reinterpret_cast<P3pReplayShared *>(smem_raw));

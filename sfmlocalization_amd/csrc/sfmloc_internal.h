@@ -122,6 +122,7 @@ struct P3pArgs {
   int adapt_quarters, adapt_floor;  // next batch = max(floor, quarters/4 * iterations since the switch)
   uint64_t seed;
   uint32_t stream;
+  int uncal;  // the query is uncalibrated: six-point resection (acransac.hip "resect6"); focal / ppx / ppy hold N1
 };
 
 // what a finished query copies back in one asynchronous transfer
@@ -268,6 +269,8 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   uint32_t p3p_stream = 0;   // K5's sampling stream (Philox key): 0 for queries; the view id when adjust.hip resects a view
   bool p3p_own_K = false;    // K5 uses p3p_K (focal, ppx, ppy) instead of the map's intrinsic (adjust.hip: per view)
   double p3p_K[3] = {0.0, 0.0, 0.0};
+  bool p3p_uncal = false;    // the query K5 is about to run for is uncalibrated (Query::uncalibrated): six-point resection
+  double p3p_N[3] = {1.0, 0.0, 0.0};  // ... normalised by N1 of its image: {sqrt(w h), w / 2, h / 2}
   uint32_t *d_pair_qfeat_big = nullptr, *d_pair_landmark_big = nullptr;
   uint64_t *d_p3p_ws_key = nullptr;
   uint32_t *d_p3p_ws_idx = nullptr;
@@ -350,6 +353,7 @@ struct Query {
   float *d_bow = nullptr;    // the query's BoW vector, resident (sfmloc_query_set_bow), [bow_dim] or null
   std::vector<float> h_kpt;
   bool is_view = false;  // the device arrays belong to the caller (sfmloc_query_create_view)
+  bool uncalibrated = false;  // sfmloc_query_set_uncalibrated: no intrinsic is assumed for this query's camera
 };
 
 // capi.hip: K1 + K2 of the selected views against q on context c (sfmloc_match_putative's body)
@@ -447,5 +451,8 @@ int launch_p3p_finish(Ctx *c);
 // the stream and queues more rounds until the state machine is done (the query path's own ctx_resection_* steps)
 int ctx_resection_begin(Ctx *c);
 int ctx_resection_wait_done(Ctx *c);
+// capi.hip: K5 of context c runs for q next -- calibrated or not (Ctx::p3p_uncal, p3p_N)
+int ctx_set_query_camera(Ctx *c, const Query *q, const char *who);
+void ctx_set_uncalibrated_camera(Ctx *c, uint32_t width, uint32_t height);  // ... from here on uncalibrated, image w x h
 
 }  // namespace sfmloc

@@ -54,10 +54,13 @@ class LocalizeEngine:
     guidedMatching, beaconKnnNum=0, bowKnnNum=0)   -- LocalizeEngine.h:75-77."""
 
     def __init__(self, sfm_data_dir, match_dir, amat_file=None, second_test_ratio=0.6, ransac_round=25,
-                 ransac_precision=4.0, guided_matching=False, beacon_knn_num=0, bow_knn_num=0, device=0, profile=0):
+                 ransac_precision=4.0, guided_matching=False, beacon_knn_num=0, bow_knn_num=0, device=0, profile=0,
+                 uncalibrated=False):
         if beacon_knn_num:
             raise NotImplementedError("iBeacon view pre-selection is out of scope (SURVEY.md 2.1)")
         self.sfm_data_dir, self.match_dir = sfm_data_dir, match_dir
+        # queries come from a camera nobody calibrated: six-point resection, the pose's K is the recovered one
+        self.uncalibrated = bool(uncalibrated)
         self.params = capi.default_params(dist_ratio=second_test_ratio, ransac_round=ransac_round,
                                           geom_precision=ransac_precision, bow_knn=bow_knn_num, device=device,
                                           profile=profile, guided_matching=int(bool(guided_matching)))
@@ -135,6 +138,8 @@ class LocalizeEngine:
                 return [], {}
         knn = int(self.params.bow_knn)
         q = self.map.query(desc, kpt_xy, width, height)
+        if self.uncalibrated:
+            q.set_uncalibrated()
         prof = int(self.map.params.profile)
         if return_time and prof != 1:
             self.map.set_profile(1)          # the reference's `times` come from this query's per-stage events
@@ -281,6 +286,7 @@ KEYS = [  # localization.cpp:64-82
     (("z", "cenLocZ"), "0.0", float), (("d", "cenRadius"), "-1.0", float), (("a", "bowModelFile"), "", str),
     (("p", "pcaModelFile"), "", str), (("i", "locEvryNFrame"), "1", int), (("g", "geomLimit"), "4.0", float),
     (("gm", "guidedMatch"), "false", _b), (("featdir",), "", str), (("device",), "0", int),
+    (("u", "uncalibrated"), "false", _b),
 ]
 
 
@@ -289,7 +295,7 @@ def main(argv=None):
     pos, o = parse_cv_args(argv, KEYS)
     if len(pos) < 4 or "h" in argv or "--help" in argv:
         print("usage: localize <queryImage|dir> <sfmDataDir> <matchDir> <outputFolder> [-f=0.6] [-r=200] [-k=0] "
-              "[-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR]")
+              "[-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated]")
         return 1
     query, sfm_dir, match_dir, out_dir = pos[:4]
     print("Start localizing input image.")
@@ -310,7 +316,7 @@ def main(argv=None):
     sfm_json = sfm_dir if packed else os.path.join(sfm_dir, "sfm_data.json")
     try:
         eng = LocalizeEngine(sfm_dir, match_dir, None, o["fDistRatio"], o["ransacRound"], o["geomLimit"],
-                             o["guidedMatch"], 0, o["knnbow"], device=o["device"])
+                             o["guidedMatch"], 0, o["knnbow"], device=o["device"], uncalibrated=o["uncalibrated"])
     except capi.SfmlocError as e:
         print(str(e), file=sys.stderr)
         return 1
