@@ -3195,7 +3195,7 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
   return SFMLOC_OK;
 }
 
-int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views, int min_putative) {
+int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, int min_putative) {
   Map *m = c->map;
   if (n_sel == 0) return SFMLOC_OK;
   FFilterArgs A;
@@ -3230,7 +3230,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
     // (a memset on the context's stream would end a gang session's recording: every real map has views above 2 048 rows,
     // and with this line a session of image-in frames issued 93 launches, none of them shared -- the query's reset
     // kernel clears the counter; only the staged API, which has no reset kernel, clears it here)
-    if (!c->cleared && !fresh) SFM_HIP(hipMemsetAsync(c->fl_count, 0, sizeof(uint32_t), c->stream));
+    if (!pass.cleared && !fresh) SFM_HIP(hipMemsetAsync(c->fl_count, 0, sizeof(uint32_t), c->stream));
     A.large_count = c->fl_count;
     A.large_list = c->fl_list;
   }
@@ -3249,12 +3249,12 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
                     (env_wide == 2 || (env_wide == 1 && c->k1_may_slice && c->stream.gang == nullptr));
   A.spec = nullptr;
   A.spec_arrive = nullptr;
-  if (c->merge_is_deferred) {  // K2 was left to this stage (launch_merge_ratio_compact)
-    c->merge_is_deferred = false;
+  if (pass.merge_deferred) {  // K2 was left to this stage (launch_merge_ratio_compact)
+    pass.merge_deferred = false;
     if (!wide) {
-      A.merge = c->deferred_merge;  // k_fmatrix_fast runs on every selected view, whatever its size
+      A.merge = pass.merge;  // k_fmatrix_fast runs on every selected view, whatever its size
     } else {  // (the wide form's workgroups of a view all need the view's lists: K2 as a launch of its own)
-      int rc = launch_merge_masked_now(c, n_sel);
+      int rc = launch_merge_masked_now(c, pass.merge, n_sel);
       if (rc) return rc;
     }
   }
@@ -3360,9 +3360,9 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views
   return SFMLOC_OK;
 }
 
-int launch_emit_candidates(Ctx *c, const Query *q, uint32_t n_sel, bool all_views) {
+int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views) {
   Map *m = c->map;
-  if (!c->cleared) {
+  if (!pass.cleared) {
     SFM_HIP(hipMemsetAsync(c->d_cand_part, 0, kPartHeaderBytes, c->stream));
     SFM_HIP(hipMemsetAsync(c->d_view_stats, 0, 3 * sizeof(uint32_t), c->stream));
     SFM_HIP(hipMemsetAsync(c->d_best64, 0xFF, (size_t)(q->n ? q->n : 1) * sizeof(unsigned long long), c->stream));
@@ -3476,12 +3476,12 @@ __global__ __launch_bounds__(256) void k_select_reset(unsigned long long *__rest
   SelectResetBody::run(best64, nq, ms_n, status);
 }
 
-int launch_select_candidates(Ctx *c, const Query *q, const unsigned char *parts, uint32_t n_parts,
+int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, const unsigned char *parts, uint32_t n_parts,
                              uint64_t part_bytes, uint32_t cap, uint32_t packed_b, uint32_t packed_qi, bool reset_status) {
   PartLayout L;
   L.packed_b = packed_b;
   L.qi = packed_qi;
-  if (!c->cleared) {  // (one launch, and one that a gang session can carry, instead of three memsets)
+  if (!pass.cleared) {  // (one launch, and one that a gang session can carry, instead of three memsets)
     const uint32_t nq1 = q->n ? q->n : 1;
     sfm_launch<SelectResetBody>(c, k_select_reset, dim3((nq1 + 255) / 256), dim3(256), 0, c->d_best64, nq1, c->d_ms_n,
                                 reset_status ? c->d_status : (int *)nullptr);
@@ -3491,7 +3491,7 @@ int launch_select_candidates(Ctx *c, const Query *q, const unsigned char *parts,
   const dim3 grid(16, n_parts < 64 ? n_parts : 64);
   // the context's own part (single GPU: the emission just ran on this stream) already holds exactly the winners and
   // d_best64 their keys, so the minimum pass would change nothing
-  const bool own_part = (parts == c->d_cand_part && n_parts == 1 && packed_b == 0 && c->cleared);
+  const bool own_part = (parts == c->d_cand_part && n_parts == 1 && packed_b == 0 && pass.cleared);
   if (!own_part) {
     sfm_launch<CandidatesMinBody>(c, k_candidates_min, grid, dim3(256), 0, parts, n_parts, part_bytes, cap, q->n,
                                   c->d_best64, c->d_status, L);
@@ -3506,10 +3506,10 @@ int launch_select_candidates(Ctx *c, const Query *q, const unsigned char *parts,
   return SFMLOC_OK;
 }
 
-int launch_match_set(Ctx *c, const Query *q, uint32_t n_sel, bool all_views) {
-  int rc = launch_emit_candidates(c, q, n_sel, all_views);
+int launch_match_set(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views) {
+  int rc = launch_emit_candidates(c, q, pass, n_sel, all_views);
   if (rc) return rc;
-  return launch_select_candidates(c, q, c->d_cand_part, 1, kPartHeaderBytes + (uint64_t)c->cand_cap * sizeof(Candidate),
+  return launch_select_candidates(c, q, pass, c->d_cand_part, 1, kPartHeaderBytes + (uint64_t)c->cand_cap * sizeof(Candidate),
                                   c->cand_cap);
 }
 

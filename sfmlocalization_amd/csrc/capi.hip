@@ -291,7 +291,7 @@ void free_map(Map *m) {
 
 // Every counter / flag the stages of one query start from, cleared by ONE launch instead of eight memsets (each a
 // separate ~5 us dispatch on the query's critical path).  The stage functions keep their own memsets for callers
-// that drive them one at a time (Ctx::cleared says which applies).
+// that drive them one at a time (QueryPass::cleared says which applies).
 struct QueryResetBody {
   static constexpr int kGangThreads = 256;
   static __device__ __forceinline__ void run(QueryResetArgs R) {
@@ -318,17 +318,17 @@ QueryResetArgs make_reset_args(Ctx *c, const Query *q) {
   return R;
 }
 
-int ctx_reset_for_query(Ctx *c, const Query *q) {
+int ctx_reset_for_query(Ctx *c, const Query *q, QueryPass &pass) {
   Map *m = c->map;
-  if (c->chain_done) {  // the shortlist's workgroup already did it (chain_after_shortlist)
-    c->cleared = true;
+  if (pass.chain_done) {  // the shortlist's workgroup already did it (chain_after_shortlist)
+    pass.cleared = true;
     return SFMLOC_OK;
   }
   const uint32_t nq = q->n ? q->n : 1;
   const uint32_t n = m->n_views + 1 > nq ? m->n_views + 1 : nq;
   sfm_launch<QueryResetBody>(c, k_query_reset, dim3((n + 255) / 256), dim3(256), 0, make_reset_args(c, q));
   SFM_HIP(hipGetLastError());
-  c->cleared = true;
+  pass.cleared = true;
   return SFMLOC_OK;
 }
 
@@ -349,11 +349,6 @@ ChainArgs make_chain_args(Ctx *c, const Query *q, const uint32_t *d_sel, uint32_
   return C;
 }
 
-struct ClearedScope {  // the flag must not outlive the call that set it
-  Ctx *c;
-  ~ClearedScope() { c->cleared = false; }
-};
-
 // A short scan is cut into query slices (more waves, better balance, ~7 % more arithmetic) only when the GPU has
 // nothing else to fill it with, i.e. when no other context of the map has work queued.
 static void ctx_mark_busy(Ctx *c) {
@@ -371,16 +366,11 @@ static void ctx_mark_idle(Ctx *c) {
   }
 }
 
-int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel = nullptr);
-int ctx_localize_begin(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel = nullptr);
-
-// d_sel: a selection that lives on the device (ascending view indices, n_sel of them; the BoW shortlist of
-// sfmloc_localize_bow_begin) -- the block list is then built by a kernel and the host never sees the views
-int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel) {
+int ctx_match_putative(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
   Map *m = c->map;
   SFM_CHECK(!c->merge_only, SFMLOC_EINVAL, "this context was created for sfmloc_merge_begin only (sfmloc_context_create_merge)");
-  const bool all_views = (view_sel == nullptr && d_sel == nullptr);
-  if (all_views) n_sel = m->n_views;
+  const bool all_views = sel.kind == ViewSel::kAll;
+  const uint32_t n_sel = all_views ? m->n_views : sel.n;
   SFM_CHECK(n_sel <= m->n_views, SFMLOC_EINVAL, "view selection: n_sel %u > n_views %u", n_sel, m->n_views);
 
   // selected views -> ascending list of the 64-row bank blocks they overlap, plus per selected view the
@@ -388,16 +378,14 @@ int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_se
   uint32_t n_work_blocks = m->n_blocks;
   c->last_blocks.clear();
   c->last_blocks_on_device = false;
-  c->flagmask_zeroed = false;
-  c->merge_is_deferred = false;  // (a merge left to a K3 that never ran belongs to an abandoned query)
-  if (d_sel) {
+  if (sel.kind == ViewSel::kDevice) {
     // launch bound the host can know: every selected view overlaps at most max_view_blocks blocks
     const uint64_t bound = std::min<uint64_t>(m->n_blocks, (uint64_t)n_sel * m->max_view_blocks);
     n_work_blocks = (uint32_t)bound;
-    if (n_sel && c->chain_done) {
-      c->flagmask_zeroed = true;  // (built by the shortlist's workgroup, chain_after_shortlist)
+    if (n_sel && pass.chain_done) {
+      pass.flagmask_zeroed = true;  // (built by the shortlist's workgroup, chain_after_shortlist)
     } else if (n_sel) {
-      int rc = launch_blocks_from_views(c, d_sel, n_sel, n_work_blocks);
+      int rc = launch_blocks_from_views(c, pass, sel.views, n_sel, n_work_blocks);
       if (rc) return rc;
     }
     c->last_blocks_on_device = true;
@@ -408,9 +396,9 @@ int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_se
     uint32_t *h_blk = c->h_pinned + 2 * (size_t)m->n_views;
     uint32_t nb = 0;
     for (uint32_t k = 0; k < n_sel; ++k) {
-      const uint32_t v = view_sel[k];
+      const uint32_t v = sel.views[k];
       SFM_CHECK(v < m->n_views, SFMLOC_EINVAL, "view selection: index %u out of range", v);
-      SFM_CHECK(k == 0 || view_sel[k - 1] < v, SFMLOC_EINVAL, "view selection must be strictly ascending");
+      SFM_CHECK(k == 0 || sel.views[k - 1] < v, SFMLOC_EINVAL, "view selection must be strictly ascending");
       h_sel[k] = v;
       h_w0[k] = 0;
       const uint32_t r0 = m->h_view_off[v], r1 = m->h_view_off[v + 1];
@@ -446,7 +434,7 @@ int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_se
       split *= 2;
   }
 
-  if (!c->cleared) SFM_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
+  if (!pass.cleared) SFM_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
   c->last_split = split;
   c->last_nq = q->n;
   c->last_n_sel = n_sel;
@@ -458,14 +446,14 @@ int ctx_match_putative(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_se
   int rc;
   {
     EventScope ev(c, SFMLOC_K_HAMMING);
-    rc = launch_hamming_top2(c, q, n_work_blocks, !all_views, split);
+    rc = launch_hamming_top2(c, q, pass, n_work_blocks, !all_views, split);
   }
   if (rc) return rc;
   c->stats.hamming_pairs += (uint64_t)n_work_blocks * kBlockRows * q->n;
   c->stats.hamming_alg_bytes += (uint64_t)n_work_blocks * kBlockRows * 64 + (uint64_t)q->n * 64;
   {
     EventScope ev(c, SFMLOC_K_COMPACT);
-    rc = launch_merge_ratio_compact(c, q, n_sel, all_views, split, n_work_blocks);
+    rc = launch_merge_ratio_compact(c, q, pass, n_sel, all_views, split, n_work_blocks);
   }
   return rc;
 }
@@ -482,24 +470,46 @@ int check_stage(Ctx *c, Query *q, const char *who) {
   return SFMLOC_OK;
 }
 
-int ctx_geometric_filter(Ctx *c, Query *q) {
+int ctx_geometric_filter(Ctx *c, Query *q, QueryPass &pass) {
   Map *m = c->map;
-  if (!c->cleared) {
+  if (!pass.cleared) {
     SFM_HIP(hipMemsetAsync(c->d_geo_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
     SFM_HIP(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));
   }
   if (q->n == 0 || c->last_n_sel == 0) return SFMLOC_OK;
   EventScope ev(c, SFMLOC_K_FMATRIX);
-  int rc = launch_fmatrix_filter(c, q, c->last_n_sel, c->last_all_views);
+  int rc = launch_fmatrix_filter(c, q, pass, c->last_n_sel, c->last_all_views);
   if (rc) return rc;
   // -gm (MatchUtils.cpp:413-415): the surviving views' matches are re-derived under the estimated F
   if (m->params.guided_matching) rc = launch_guided_matching(c, q, c->last_n_sel, c->last_all_views);
   return rc;
 }
 
-int ctx_match_set(Ctx *c, Query *q) {
+int ctx_match_set(Ctx *c, Query *q, const QueryPass &pass) {
   EventScope ev(c, SFMLOC_K_MATCHSET);
-  return launch_match_set(c, q, c->last_n_sel, c->last_all_views);
+  return launch_match_set(c, q, pass, c->last_n_sel, c->last_all_views);
+}
+
+// What every begin starts with: the query's counters cleared, K1 + K2 of the selection and, unless the chain is cut
+// after them (k3 = false: measurements), K3 -- whose per-view workgroups then build their own match lists where they can
+int ctx_match_and_filter(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel, const char *who, bool k3 = true) {
+  int rc = ctx_reset_for_query(c, q, pass);
+  if (rc) return rc;
+  pass.k3_follows = k3;
+  rc = ctx_match_putative(c, q, pass, sel);
+  if (rc) return rc;
+  rc = check_stage(c, q, who);
+  if (rc || !k3) return rc;
+  return ctx_geometric_filter(c, q, pass);
+}
+
+// What the entry points of the sharded path check first (in_flight = false: the caller checks that later itself)
+int check_sharded(const Ctx *c, const Query *q, const char *who, bool in_flight = true) {
+  SFM_CHECK(q->map == c->map, SFMLOC_EINVAL, "%s: query belongs to another map", who);
+  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
+            "%s: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path", who);
+  SFM_CHECK(!in_flight || c->in_flight == nullptr, SFMLOC_EINVAL, "%s: context has a query in flight", who);
+  return SFMLOC_OK;
 }
 
 }  // namespace
@@ -668,12 +678,12 @@ int ctx_resection_wait(Ctx *c) {
   return SFMLOC_EHIP;
 }
 
-static int ctx_localize_begin_impl(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel);
+static int ctx_localize_begin_impl(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel);
 
-int ctx_localize_begin(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel) {
+int ctx_localize_begin(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_localize_begin: context already has a query in flight");
   ctx_mark_busy(c);
-  const int rc = ctx_localize_begin_impl(c, q, view_sel, n_sel, d_sel);
+  const int rc = ctx_localize_begin_impl(c, q, pass, sel);
   if (rc) ctx_mark_idle(c);
   return rc;
 }
@@ -685,28 +695,17 @@ static int diag_stop_after() {
   return v;
 }
 
-static int ctx_localize_begin_impl(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel, const uint32_t *d_sel) {
+static int ctx_localize_begin_impl(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
   c->t_begin = now_s();
-  ClearedScope cs{c};
   int rc = ctx_set_query_camera(c, q, "sfmloc_localize");
   if (rc) return rc;
   rc = ctx_p3p_reserve(c, q->n);
   if (rc) return rc;
-  rc = ctx_reset_for_query(c, q);
-  if (rc) return rc;
   const int stop = diag_stop_after();
-  c->defer_merge = stop != 1;  // K3 follows on this context: its per-view workgroups build their own match lists
-  rc = ctx_match_putative(c, q, view_sel, n_sel, d_sel);
-  c->defer_merge = false;
+  rc = ctx_match_and_filter(c, q, pass, sel, "sfmloc_localize", stop != 1);
   if (rc) return rc;
-  rc = check_stage(c, q, "sfmloc_localize");
-  if (rc) return rc;
-  if (stop != 1) {
-    rc = ctx_geometric_filter(c, q);
-    if (rc) return rc;
-  }
   if (stop == 0 || stop > 2) {
-    rc = ctx_match_set(c, q);
+    rc = ctx_match_set(c, q, pass);
     if (rc) return rc;
   }
   if (stop == 0) {
@@ -911,7 +910,8 @@ void gang_member_free(GangMember *m) {
 }
 
 int match_putative_on(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel) {
-  return ctx_match_putative(c, q, view_sel, n_sel);
+  QueryPass pass;
+  return ctx_match_putative(c, q, pass, ViewSel::host(view_sel, n_sel));
 }
 }  // namespace sfmloc
 
@@ -1334,7 +1334,8 @@ int sfmloc_match_putative(sfmloc_map *map, sfmloc_query *query, const uint32_t *
   Query *q = reinterpret_cast<Query *>(query);
   SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_match_putative: query belongs to another map");
   SFM_HIP(hipSetDevice(m->device));
-  return ctx_match_putative(m->ctx0, q, view_sel, n_sel);
+  QueryPass pass;
+  return ctx_match_putative(m->ctx0, q, pass, ViewSel::host(view_sel, n_sel));
 }
 
 int sfmloc_putative_read(sfmloc_map *map, uint32_t *view_count, uint32_t *match_i, uint32_t *match_j,
@@ -1424,7 +1425,8 @@ int sfmloc_geometric_filter(sfmloc_map *map, sfmloc_query *query) {
   int rc = check_stage(m->ctx0, q, "sfmloc_geometric_filter");
   if (rc) return rc;
   SFM_HIP(hipSetDevice(m->device));
-  return ctx_geometric_filter(m->ctx0, q);
+  QueryPass pass;
+  return ctx_geometric_filter(m->ctx0, q, pass);
 }
 
 int sfmloc_geometric_read(sfmloc_map *map, uint32_t *geo_count, uint32_t *geo_idx, uint64_t cap) {
@@ -1497,7 +1499,7 @@ int sfmloc_match_set(sfmloc_map *map, sfmloc_query *query) {
   if (rc) return rc;
   rc = ctx_p3p_reserve(m->ctx0, q->n);  // K5's start runs at the end of this stage (k_match_set_finish)
   if (rc) return rc;
-  return ctx_match_set(m->ctx0, q);
+  return ctx_match_set(m->ctx0, q, QueryPass{});
 }
 
 int sfmloc_match_set_read(sfmloc_map *map, uint32_t *n, uint32_t *qfeat, uint32_t *landmark_id, double *pt2d,
@@ -1573,7 +1575,8 @@ int sfmloc_localize_begin(sfmloc_context *ctx, sfmloc_query *query, const uint32
   Query *q = reinterpret_cast<Query *>(query);
   SFM_CHECK(q->map == c->map, SFMLOC_EINVAL, "sfmloc_localize_begin: query belongs to another map");
   SFM_HIP(hipSetDevice(c->map->device));
-  return ctx_localize_begin(c, q, view_sel, n_sel);
+  QueryPass pass;
+  return ctx_localize_begin(c, q, pass, ViewSel::host(view_sel, n_sel));
 }
 
 int sfmloc_localize_bow_begin(sfmloc_context *ctx, sfmloc_query *query, const float *query_bow, uint32_t knn,
@@ -1593,7 +1596,8 @@ int sfmloc_localize_bow_begin(sfmloc_context *ctx, sfmloc_query *query, const fl
   SFM_HIP(hipSetDevice(m->device));
   // "if (knnbow > 0 && viewList.size() > knnbow)" (localization.cpp:346, LocalizeEngine.cc:342): otherwise every
   // candidate is matched
-  if (knn == 0 || n_cand <= knn) return ctx_localize_begin(c, q, cand_views, cand_views ? n_cand : 0);
+  QueryPass pass;
+  if (knn == 0 || n_cand <= knn) return ctx_localize_begin(c, q, pass, ViewSel::host(cand_views, n_cand));
   if (cand_views) {
     for (uint32_t i = 0; i < n_cand; ++i) {
       SFM_CHECK(cand_views[i] < m->n_views, SFMLOC_EINVAL, "sfmloc_localize_bow_begin: view index out of range");
@@ -1614,11 +1618,8 @@ int sfmloc_localize_bow_begin(sfmloc_context *ctx, sfmloc_query *query, const fl
   }
   if (rc) return rc;
   // K8 leaves the knn views in ascending order in d_bow_sel; everything downstream reads the selection on the device
-  uint32_t dummy = 0;
-  c->chain_done = true;
-  rc = ctx_localize_begin(c, q, &dummy, knn, c->d_bow_sel);
-  c->chain_done = false;
-  return rc;
+  pass.chain_done = true;
+  return ctx_localize_begin(c, q, pass, ViewSel::device(c->d_bow_sel, knn));
 }
 
 int sfmloc_localize_end(sfmloc_context *ctx, sfmloc_pose *out, uint32_t *pair_qfeat, uint32_t *pair_landmark,
@@ -1637,25 +1638,15 @@ int sfmloc_shard_begin(sfmloc_context *ctx, sfmloc_query *query, const uint32_t 
   SFM_CHECK(ctx && query, SFMLOC_EINVAL, "sfmloc_shard_begin: null argument");
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   Query *q = reinterpret_cast<Query *>(query);
-  SFM_CHECK(q->map == c->map, SFMLOC_EINVAL, "sfmloc_shard_begin: query belongs to another map");
-  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
-            "sfmloc_shard_begin: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
-  SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_begin: context has a query in flight");
+  int rc = check_sharded(c, q, "sfmloc_shard_begin");
+  if (rc) return rc;
   SFM_HIP(hipSetDevice(c->map->device));
   ctx_mark_busy(c);  // until sfmloc_context_sync
-  ClearedScope cs{c};
-  int rc = ctx_reset_for_query(c, q);
-  if (rc) return rc;
-  c->defer_merge = true;  // K3 follows on this context
-  rc = ctx_match_putative(c, q, view_sel, n_sel);
-  c->defer_merge = false;
-  if (rc) return rc;
-  rc = check_stage(c, q, "sfmloc_shard_begin");
-  if (rc) return rc;
-  rc = ctx_geometric_filter(c, q);
+  QueryPass pass;
+  rc = ctx_match_and_filter(c, q, pass, ViewSel::host(view_sel, n_sel), "sfmloc_shard_begin");
   if (rc) return rc;
   EventScope ev(c, SFMLOC_K_MATCHSET);
-  return launch_emit_candidates(c, q, c->last_n_sel, c->last_all_views);
+  return launch_emit_candidates(c, q, pass, c->last_n_sel, c->last_all_views);
 }
 
 int sfmloc_shard_export(sfmloc_context *ctx, void *dst_dev, uint32_t cap) {
@@ -1672,9 +1663,8 @@ int sfmloc_shard_bow_keys(sfmloc_context *ctx, sfmloc_query *query, const float 
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
-  SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: query belongs to another map");
-  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
-            "sfmloc_shard_bow_keys: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
+  int rc = check_sharded(c, q, "sfmloc_shard_bow_keys", /*in_flight=*/false);
+  if (rc) return rc;
   SFM_CHECK(m->bow_dim > 0 && m->d_bow, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: the map has no .bow vectors");
   SFM_CHECK(query_bow || q->d_bow, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: no BoW vector");
   SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_bow_keys: context has a query in flight");
@@ -1694,21 +1684,17 @@ int sfmloc_shard_begin_bow(sfmloc_context *ctx, sfmloc_query *query, const void 
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
-  SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: query belongs to another map");
-  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
-            "sfmloc_shard_begin_bow: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
-  SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: context has a query in flight");
+  int rc = check_sharded(c, q, "sfmloc_shard_begin_bow");
+  if (rc) return rc;
   SFM_CHECK(!c->merge_only, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: this context was created for sfmloc_merge_begin only");
   if (part_stride_keys == 0) part_stride_keys = knn;
   SFM_CHECK(part_stride_keys >= knn, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: part_stride_keys < knn");
   SFM_CHECK(m->bow_dim > 0 && c->d_bow_sel, SFMLOC_EINVAL, "sfmloc_shard_begin_bow: the map has no BoW vectors");
   SFM_HIP(hipSetDevice(m->device));
   ctx_mark_busy(c);  // until sfmloc_context_sync
-  ClearedScope cs{c};
   // this shard's part of the global knn best: ascending local view indices, padded with the phantom view up to
   // n_pad = min(knn, n_views) entries -- the launch sizes below depend on n_pad only, never on the outcome
   const uint32_t n_pad = knn < m->n_views ? knn : m->n_views;
-  int rc;
   {
     EventScope ev(c, SFMLOC_K_BOW);
     // the workgroup that merges the key lists also clears the query's counters and builds the block list
@@ -1717,20 +1703,12 @@ int sfmloc_shard_begin_bow(sfmloc_context *ctx, sfmloc_query *query, const void 
                                  part_stride_keys, knn, n_pad, c->d_bow_sel, n_pad ? &chain : nullptr);
   }
   if (rc) return rc;
-  c->chain_done = n_pad != 0;
-  rc = ctx_reset_for_query(c, q);
-  uint32_t dummy = 0;
-  c->defer_merge = true;  // K3 follows on this context
-  if (!rc) rc = ctx_match_putative(c, q, &dummy, n_pad, c->d_bow_sel);
-  c->defer_merge = false;
-  c->chain_done = false;
-  if (rc) return rc;
-  rc = check_stage(c, q, "sfmloc_shard_begin_bow");
-  if (rc) return rc;
-  rc = ctx_geometric_filter(c, q);
+  QueryPass pass;
+  pass.chain_done = n_pad != 0;
+  rc = ctx_match_and_filter(c, q, pass, ViewSel::device(c->d_bow_sel, n_pad), "sfmloc_shard_begin_bow");
   if (rc) return rc;
   EventScope ev(c, SFMLOC_K_MATCHSET);
-  return launch_emit_candidates(c, q, c->last_n_sel, c->last_all_views);
+  return launch_emit_candidates(c, q, pass, c->last_n_sel, c->last_all_views);
 }
 
 int sfmloc_context_signal(sfmloc_context *ctx, void *hip_stream) {
@@ -1834,10 +1812,8 @@ static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   Query *q = reinterpret_cast<Query *>(query);
   Map *m = c->map;
-  SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_merge_begin: query belongs to another map");
-  SFM_CHECK(!q->uncalibrated, SFMLOC_EINVAL,
-            "sfmloc_merge_begin: an uncalibrated query (sfmloc_query_set_uncalibrated) is not supported on the sharded path");
-  SFM_CHECK(c->in_flight == nullptr, SFMLOC_EINVAL, "sfmloc_merge_begin: context has a query in flight");
+  int rc = check_sharded(c, q, "sfmloc_merge_begin");
+  if (rc) return rc;
   SFM_CHECK(m->focal > 0.0, SFMLOC_EINVAL, "sfmloc_merge_begin: the map has no intrinsic");
   SFM_CHECK(q->n == 0 || q->d_kpt, SFMLOC_EINVAL, "sfmloc_merge_begin: the query was created without keypoints");
   if (part_stride == 0) part_stride = sfmloc_part_bytes(cap);
@@ -1855,11 +1831,10 @@ static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void
       return rcr;
     }
   }
-  int rc;
   {
     EventScope ev(c, SFMLOC_K_MATCHSET);
-    rc = launch_select_candidates(c, q, reinterpret_cast<const unsigned char *>(parts_dev), n_parts, part_stride, cap,
-                                  packed_b, packed_qi, /*reset_status=*/true);
+    rc = launch_select_candidates(c, q, QueryPass{}, reinterpret_cast<const unsigned char *>(parts_dev), n_parts, part_stride,
+                                  cap, packed_b, packed_qi, /*reset_status=*/true);
   }
   if (!rc) {
     EventScope ev(c, SFMLOC_K_P3P);
@@ -1881,7 +1856,8 @@ int sfmloc_localize(sfmloc_map *map, sfmloc_query *query, const uint32_t *view_s
   Query *q = reinterpret_cast<Query *>(query);
   SFM_CHECK(q->map == m, SFMLOC_EINVAL, "sfmloc_localize: query belongs to another map");
   SFM_HIP(hipSetDevice(m->device));
-  int rc = ctx_localize_begin(m->ctx0, q, view_sel, n_sel);
+  QueryPass pass;
+  int rc = ctx_localize_begin(m->ctx0, q, pass, ViewSel::host(view_sel, n_sel));
   if (rc) {
     m->ctx0->in_flight = nullptr;
     return rc;
@@ -1928,7 +1904,8 @@ int sfmloc_localize_batch(sfmloc_map *map, sfmloc_query *const *queries, uint32_
     if (i >= n_contexts) finish(i - n_contexts);
     Ctx *c = m->batch_ctx[i % n_contexts];
     Query *q = reinterpret_cast<Query *>(queries[i]);
-    int rc = (q && q->map == m) ? ctx_localize_begin(c, q, nullptr, 0) : SFMLOC_EINVAL;
+    QueryPass pass;
+    int rc = (q && q->map == m) ? ctx_localize_begin(c, q, pass, ViewSel{}) : SFMLOC_EINVAL;
     if (rc) {
       if (!first_err) {
         first_err = rc;

@@ -406,8 +406,8 @@ int main(int argc, char **argv) {
           flat.push_back(idx_of[p.first]);
           flat.push_back(idx_of[p.second]);
         }
-      uint32_t dummy[2] = {0, 0};
-      rc = sfmloc_match_pairs(map, flat.empty() ? dummy : flat.data(), (uint32_t)(flat.size() / 2), &h);
+      uint32_t none[2] = {0, 0};
+      rc = sfmloc_match_pairs(map, flat.empty() ? none : flat.data(), (uint32_t)(flat.size() / 2), &h);
     }
     PairMatches put;
     if (rc || !take_matches(h, views, &put) || !write_matches(put_path, put)) {
@@ -438,9 +438,9 @@ int main(int argc, char **argv) {
     }
     printf("\n");
     sfmloc_matches *h = nullptr;
-    uint32_t dummy[2] = {0, 0};
-    rc = sfmloc_geometric_pairs(map, pairs.empty() ? dummy : pairs.data(), (uint32_t)n_kept, offsets.data(),
-                                mi.empty() ? dummy : mi.data(), mj.empty() ? dummy : mj.data(), &h);
+    uint32_t none[2] = {0, 0};
+    rc = sfmloc_geometric_pairs(map, pairs.empty() ? none : pairs.data(), (uint32_t)n_kept, offsets.data(),
+                                mi.empty() ? none : mi.data(), mj.empty() ? none : mj.data(), &h);
     PairMatches geo;
     if (rc || !take_matches(h, views, &geo)) {
       fprintf(stderr, "geometric matching failed: %s\n", sfmloc_last_error());

@@ -339,7 +339,7 @@ int launch_tile_bank(const uint4 *d_rows, uint64_t row0, uint64_t n_rows_chunk, 
   return SFMLOC_OK;
 }
 
-static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_list) {
+static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_work_blocks, bool use_list) {
   Map *m = c->map;
   constexpr int WAVES = 8;
   // Prefix length of the lower bound, in dwords.  With 10 of 16 the "some lane still below its threshold" vote
@@ -357,7 +357,7 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
   }();
   const uint32_t lds_rows = 512;
   const size_t lds_bytes = (size_t)lds_rows * 64;
-  if (!c->cleared) SFM_HIP(hipMemsetAsync(c->d_n_flagged, 0, sizeof(uint32_t), c->stream));
+  if (!pass.cleared) SFM_HIP(hipMemsetAsync(c->d_n_flagged, 0, sizeof(uint32_t), c->stream));
   // query slices for a short block list: aim at 8 waves per SIMD (3 200 blocks in one slice leave the fullest SIMDs 4
   // waves and the average 3.1: 0.39 ms; four slices: 0.33 ms although each pays its own exact head), every slice at
   // least 6 heads long so that screening still pays
@@ -401,9 +401,9 @@ static int launch_hamming_screened(Ctx *c, const Query *q, uint32_t n_work_block
     if (rc) return rc;
     head_part = c->d_part;
   }
-  if (qsplit > 1 && !c->flagmask_zeroed)
+  if (qsplit > 1 && !pass.flagmask_zeroed)
     SFM_HIP(hipMemsetAsync(c->d_flagmask, 0, (size_t)n_work_blocks * sizeof(unsigned long long), c->stream));
-  c->flagmask_zeroed = false;
+  pass.flagmask_zeroed = false;  // (this scan writes it)
 #define K1_SCREEN(NW)                                                                                              \
   case NW:                                                                                                        \
     sfm_launch<HammingScreenBody<WAVES, NW, 1>>(                                                                  \
@@ -495,16 +495,16 @@ __global__ __launch_bounds__(1024) void k_blocks_from_views(const uint32_t *__re
   BlocksFromViewsBody::run(sel, n_sel, view_off, view_sel_out, widx0, block_list, bound, flagmask);
 }
 
-int launch_blocks_from_views(Ctx *c, const uint32_t *d_sel, uint32_t n_sel, uint32_t bound) {
+int launch_blocks_from_views(Ctx *c, QueryPass &pass, const uint32_t *d_sel, uint32_t n_sel, uint32_t bound) {
   Map *m = c->map;
   sfm_launch<BlocksFromViewsBody>(c, k_blocks_from_views, dim3(1), dim3(1024), 0, d_sel, n_sel, m->d_view_off,
                                   c->d_view_sel, c->d_view_widx0, c->d_block_list, bound, c->d_flagmask);
   SFM_HIP(hipGetLastError());
-  c->flagmask_zeroed = true;
+  pass.flagmask_zeroed = true;
   return SFMLOC_OK;
 }
 
-int launch_hamming_top2(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_list, uint32_t split) {
+int launch_hamming_top2(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_work_blocks, bool use_list, uint32_t split) {
   Map *m = c->map;
   if (n_work_blocks == 0 || q->n == 0) return SFMLOC_OK;
   // (below ~12 heads' worth of query rows the exact head and the second launch eat the saving:
@@ -512,7 +512,7 @@ int launch_hamming_top2(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use
   c->last_screened = false;
   if (split == 1 && m->params.exact_rows == 0 && q->n >= 12 * kScreenHead && !k1_override().r) {
     c->last_screened = true;
-    return launch_hamming_screened(c, q, n_work_blocks, use_list);
+    return launch_hamming_screened(c, q, pass, n_work_blocks, use_list);
   }
   int R, W, L;
   c->stats.hamming_lane_ops += (uint64_t)n_work_blocks * kBlockRows * q->n * 35;
@@ -550,7 +550,7 @@ int launch_hamming_top2(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use
   return SFMLOC_EINVAL;
 }
 
-int launch_merge_ratio_compact(Ctx *c, const Query *q, uint32_t n_sel, bool all_views, uint32_t split,
+int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, uint32_t split,
                                uint32_t n_work_blocks) {
   (void)q;
   Map *m = c->map;
@@ -567,9 +567,9 @@ int launch_merge_ratio_compact(Ctx *c, const Query *q, uint32_t n_sel, bool all_
     M.view_count = c->d_view_count;
     M.match_i = c->d_match_i;
     M.match_key = c->d_match_key;
-    if (c->defer_merge) {  // the caller runs K3 next on this context: its per-view workgroups merge their own views
-      c->deferred_merge = M;
-      c->merge_is_deferred = true;
+    if (pass.k3_follows) {  // the caller runs K3 next on this context: its per-view workgroups merge their own views
+      pass.merge = M;
+      pass.merge_deferred = true;
       return SFMLOC_OK;
     }
     sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel);
@@ -584,8 +584,8 @@ int launch_merge_ratio_compact(Ctx *c, const Query *q, uint32_t n_sel, bool all_
   return SFMLOC_OK;
 }
 
-int launch_merge_masked_now(Ctx *c, uint32_t n_sel) {
-  sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, c->deferred_merge, n_sel);
+int launch_merge_masked_now(Ctx *c, const MergeMaskedArgs &M, uint32_t n_sel) {
+  sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel);
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }

@@ -384,7 +384,8 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
       hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream);
       // no >=16 rule here: OpenMVG's Robust_model_estimation takes every pair it is given (the caller has applied
       // ExtFeatAndMatch's minMatch, computeFeaturesAndMatches.cpp:211-221)
-      rc = launch_fmatrix_filter(c, q, (uint32_t)sel.size(), false, 0);
+      QueryPass pass;  // (a stage on its own: the memsets above are its reset)
+      rc = launch_fmatrix_filter(c, q, pass, (uint32_t)sel.size(), false, 0);
     }
     const bool guided = m->params.guided_matching != 0;
     std::vector<uint32_t> passed(sel.size(), 0);

@@ -287,7 +287,11 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   hipEvent_t pinned_busy = nullptr;  // recorded after the last upload out of h_pinned
   hipEvent_t xev_out = nullptr, xev_in = nullptr;  // ordering against a caller's stream (sfmloc_context_signal / _wait)
 
-  // state of the last putative call
+  // What the context remembers from one call to the next.  last_*: the last putative call, which the staged API's
+  // later stages and readers work on.  k1_may_slice (and p3p_small above) hold from a query's begin to its end;
+  // p3p_init_fused (like p3p_uncal, p3p_N, p3p_own_K, p3p_stream, p3p_query_n above) is carried from the match set to the
+  // resection, also across staged calls and by adjust.hip.  What holds for one entry-point call only is not here: the
+  // call passes it down as a QueryPass.
   uint32_t last_split = 0;
   uint32_t last_nq = 0;
   uint32_t last_n_sel = 0;
@@ -295,15 +299,9 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   uint32_t last_n_work_blocks = 0;
   std::vector<uint32_t> last_blocks;  // host copy of the block list (empty = all)
   bool last_blocks_on_device = false; // the list was built by k_blocks_from_views: fetch it when a reader needs it
-  bool flagmask_zeroed = false;       // k_blocks_from_views has just cleared d_flagmask for the coming scan
   bool counted_busy = false;          // this context is counted in Map::busy_ctx
   bool k1_may_slice = true;           // no other context had work queued when this query began
   bool p3p_init_fused = false;        // k_match_set_finish has run K5's initialisation for the query in hand
-  bool chain_done = false;            // the shortlist kernel already cleared the counters and built the block list
-  bool defer_merge = false;           // the caller runs K3 right after K1 on this context: K2 may be left to K3
-  bool merge_is_deferred = false;     // ... and was: launch_fmatrix_filter passes deferred_merge to k_fmatrix_fast
-  MergeMaskedArgs deferred_merge{};
-  bool cleared = false;  // k_query_reset already cleared this query's counters: the stages skip their own memsets
   struct Query *last_query = nullptr;  // query of the last putative call
   struct Query *in_flight = nullptr;   // query of a begun, not yet ended, localisation
   double t_begin = 0.0;
@@ -356,14 +354,36 @@ struct Query {
   bool uncalibrated = false;  // sfmloc_query_set_uncalibrated: no intrinsic is assumed for this query's camera
 };
 
+// What ONE entry-point call has decided or already done for its query: created on the entry point's stack and passed
+// down to the stages and launchers that act on it, so nothing of it outlives the call.  The staged entry points, which
+// drive one stage per call, pass a default-constructed one.
+struct QueryPass {
+  bool chain_done = false;       // the shortlist kernel already cleared the counters and built the block list
+  bool cleared = false;          // this query's counters are cleared (k_query_reset or that chain): the stages skip their memsets
+  bool k3_follows = false;       // the caller runs K3 right after K1 on this context: K2 may be left to K3
+  bool flagmask_zeroed = false;  // d_flagmask has just been cleared (with the device-built block list) for the coming scan
+  bool merge_deferred = false;   // K2 was left to K3: launch_fmatrix_filter passes `merge` to k_fmatrix_fast
+  MergeMaskedArgs merge{};
+};
+
+// The views a putative call matches against: all of the map, or ascending view indices in host or in device memory
+// (device: the BoW shortlist -- the block list is then built by a kernel and the host never sees the views).
+struct ViewSel {
+  enum Kind { kAll, kHost, kDevice } kind = kAll;
+  const uint32_t *views = nullptr;
+  uint32_t n = 0;
+  static ViewSel host(const uint32_t *v, uint32_t n) { return v ? ViewSel{kHost, v, n} : ViewSel{}; }  // (C ABI: null = all)
+  static ViewSel device(const uint32_t *d, uint32_t n) { return ViewSel{kDevice, d, n}; }
+};
+
 // capi.hip: K1 + K2 of the selected views against q on context c (sfmloc_match_putative's body)
 int match_putative_on(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel);
 
 // hamming.hip
 int launch_tile_bank(const uint4 *d_rows, uint64_t row0, uint64_t n_rows_chunk, uint4 *d_bank, hipStream_t s);
-int launch_hamming_top2(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_list, uint32_t split);
-int launch_blocks_from_views(Ctx *c, const uint32_t *d_sel, uint32_t n_sel, uint32_t bound);
-int launch_merge_ratio_compact(Ctx *c, const Query *q, uint32_t n_sel, bool all_views, uint32_t split,
+int launch_hamming_top2(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_work_blocks, bool use_list, uint32_t split);
+int launch_blocks_from_views(Ctx *c, QueryPass &pass, const uint32_t *d_sel, uint32_t n_sel, uint32_t bound);
+int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, uint32_t split,
                                uint32_t n_work_blocks);
 
 
@@ -426,23 +446,23 @@ void dense_grid_build(int size, std::vector<float> *grid, std::vector<float> *kx
 int launch_fill_log10(double *d_L10, int n, hipStream_t s);
 int launch_debug_math(int op, const double *d_in, int n, int in_stride, double *d_out, int out_stride, hipStream_t s);
 // min_putative < 0: the map's params.min_putative (the query path's >=16 rule, localization.cpp:408-415)
-int launch_fmatrix_filter(Ctx *c, const Query *q, uint32_t n_sel, bool all_views, int min_putative = -1);
-int launch_match_set(Ctx *c, const Query *q, uint32_t n_sel, bool all_views);
+int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, int min_putative = -1);
+int launch_match_set(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views);
 // guided.hip: GeometricFilter_FMatrix_AC::Geometry_guided_matching for the views that passed K3 (their geo lists are
 // replaced by (map feature, query feature) lists in d_geo_idx / d_geo_j)
 int ensure_guided_workspace(Ctx *c);
 int launch_guided_matching(Ctx *c, const Query *q, uint32_t n_sel, bool all_views);
-int launch_emit_candidates(Ctx *c, const Query *q, uint32_t n_sel, bool all_views);
+int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views);
 int launch_export_part(Ctx *c, void *dst_dev, uint32_t cap);
 // packed_b > 0: `parts` are packed batch parts of packed_b queries (acransac.hip PartLayout), cap = their budget,
 // and this query is number packed_qi of the batch
-int launch_select_candidates(Ctx *c, const Query *q, const unsigned char *parts, uint32_t n_parts,
+int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, const unsigned char *parts, uint32_t n_parts,
                              uint64_t part_bytes, uint32_t cap, uint32_t packed_b = 0, uint32_t packed_qi = 0,
                              bool reset_status = false);  // (also clear the context's status word: sfmloc_merge_begin)
 int launch_export_packed(Ctx *c, void *dst_dev, uint32_t n_queries, uint32_t budget, uint32_t qi);
 uint64_t packed_part_bytes(uint32_t n_queries, uint32_t budget);
 int ctx_p3p_reserve(Ctx *c, uint32_t n_query_rows);  // capi.hip: grow the P3P workspace to a query's feature count
-int launch_merge_masked_now(Ctx *c, uint32_t n_sel);  // hamming.hip: the deferred K2 as a launch of its own
+int launch_merge_masked_now(Ctx *c, const MergeMaskedArgs &M, uint32_t n_sel);  // hamming.hip: a deferred K2 as a launch of its own
 int launch_p3p_init(Ctx *c);
 int launch_p3p_round(Ctx *c, int batch);
 int launch_p3p_finish(Ctx *c);
