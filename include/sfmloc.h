@@ -812,6 +812,45 @@ int sfmloc_merge_transform(const double *M /*[12]*/, double *R, uint64_t nR, dou
 double sfmloc_merge_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
+/* Thinning a map fixed to world coordinates (PyEvaluateAccuracy/src/localizeGlobalCoordinateRefPoint.py:81-118,      */
+/* reduceClosePointsKDTree(sfmData, Amat, thres, knn), which --reduce-points runs with thres 0.01 and knn 1000):       */
+/* landmarks closer than thres in world coordinates are folded into the one of lowest index.  Points are a host array */
+/* [n*3] in structure order; the host appends observation lists in `order`.  f64, unfused, one expression per value, */
+/* so tests/globalcoord_np.py reproduces the bits over an all-pairs matrix.  Readings chosen and divergences:         */
+/*   global      G_i = ((a_i0 x0 + a_i1 x1) + a_i2 x2) + a_i3 (the "transform" arithmetic of sfmloc_merge); A = NULL  */
+/*               is the identity through the same expression.                                                         */
+/*   distance    d(i, j) = sqrt((dx dx + dy dy) + dz dz) on G (NumPy's norm may differ in the last bit).              */
+/*   neighbours  N(i) = the min(knn, n) points nearest to i, i itself included, in ascending (d, index).  cKDTree's   */
+/*               order among equal distances is unspecified: this reading is build-defined.                           */
+/*   close set   C(i) = { j in N(i) : j > i and d(i, j) < thres }: only the lower index's list counts, as there.      */
+/*   greedy      in ascending i an unabsorbed i is a keeper and absorbs every j of C(i) that is still unabsorbed, in  */
+/*               N(i)'s order; that is: i is a keeper iff no keeper k < i has i in C(k), and an absorbed j belongs to */
+/*               the smallest such keeper.  Not transitive: d(0,1) < thres, d(1,2) < thres, d(0,2) >= thres absorbs 1 */
+/*               and keeps 2.  (The reference's brute-force reduceClosePoints agrees wherever knn does not bind.)      */
+/*   outputs     owner[i] = i for a keeper, else its keeper; dist[i] = d(owner[i], i), 0 for a keeper; order = the    */
+/*               absorbed points grouped by ascending owner, inside a group by (dist, index): the order in which the  */
+/*               reference appends their observations; the other n - n_absorbed entries are 0xFFFFFFFF.  n_pairs =    */
+/*               the sum of |C(i)|; rounds = the passes of the greedy resolution (a point is decided in the pass      */
+/*               after the last of the points that list it; 1 when no point lists another).  None of it depends on    */
+/*               params.rounds_per_launch (here: resolution passes between two host checks; 0 = the library's).       */
+/*   method      a uniform grid of cell thres (1 + 2^-10) over the bounding box of G, hashed; points within thres are */
+/*               always the nearest ones, so nothing outside a point's 27 cells is needed.                            */
+/*   n < 2       (divergence) nothing is absorbed, rounds 0; the reference's query fails on k = 1.                     */
+/*   refusals    non-finite A, X or thres, thres <= 0: SFMLOC_EINVAL.  n > 2^24, more than 2^21 cells on an axis      */
+/*               (which includes a world coordinate that overflows), more than 2^28 close pairs: SFMLOC_ECAP.  Every  */
+/*               check happens before owner, order, dist or *out is written.                                          */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_reduce_result {
+  uint64_t n_keep, n_absorbed, n_pairs;
+  uint32_t rounds, reserved;
+} sfmloc_reduce_result;
+int sfmloc_reduce_points(const double *X /*[n*3]*/, uint64_t n, const double *A /*[12] or NULL = identity*/, double thres,
+                         uint32_t knn, const sfmloc_merge_params *params, uint32_t *owner /*[n]*/, uint32_t *order /*[n]*/,
+                         double *dist /*[n]*/, sfmloc_reduce_result *out);
+/* device milliseconds between the events of the calling thread's last sfmloc_reduce_points made with profile = 1 */
+double sfmloc_reduce_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
 /* Map-side matching: the reference's matchAKAZE /         */
 /* trackAKAZE on the same kernels.  Views are addressed by their index in the  */
 /* map's view table (ascending view id).                                       */

@@ -116,6 +116,11 @@ class MergeResult(C.Structure):
                 ("n_inliers", C.c_uint32)]
 
 
+class ReduceResult(C.Structure):
+    _fields_ = [("n_keep", C.c_uint64), ("n_absorbed", C.c_uint64), ("n_pairs", C.c_uint64), ("rounds", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 MERGE_SIMILARITY, MERGE_AFFINE = 0, 1
 MERGE_MODELS = {"similarity": MERGE_SIMILARITY, "affine": MERGE_AFFINE}
 
@@ -162,7 +167,7 @@ SYMBOLS = [
     "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
-    "sfmloc_merge_transform", "sfmloc_merge_last_ms",
+    "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
 ]
 
@@ -411,6 +416,10 @@ def _L():
         L.sfmloc_merge_transform.argtypes = [F64P, F64P, C.c_uint64, F64P, C.c_uint64, MPP]
         L.sfmloc_merge_last_ms.restype = C.c_double
         L.sfmloc_merge_last_ms.argtypes = []
+        L.sfmloc_reduce_points.argtypes = [F64P, C.c_uint64, F64P, C.c_double, C.c_uint32, MPP, U32P, U32P, F64P,
+                                           C.POINTER(ReduceResult)]
+        L.sfmloc_reduce_last_ms.restype = C.c_double
+        L.sfmloc_reduce_last_ms.argtypes = []
         _bound = True
     return L
 
@@ -1279,6 +1288,26 @@ def merge_transform(M, R=None, X=None, params=None):
 
 def merge_last_ms():
     return float(_L().sfmloc_merge_last_ms())
+
+
+def reduce_points(X, A=None, thres=0.01, knn=1000, params=None, out=None):
+    """sfmloc_reduce_points on landmarks X[n, 3] -> dict(owner uint32 [n], order uint32 [n_absorbed], dist f64 [n],
+    n_keep, n_absorbed, n_pairs, rounds).  A: 3 x 4 or None (the identity).  out: (owner, order, dist) arrays to write
+    into (each [n]; the tests watch them on a refused call)."""
+    X = _pts(X)
+    n = X.shape[0]
+    A = None if A is None else np.ascontiguousarray(A, np.float64).reshape(12)
+    owner, order, dist = out if out is not None else (np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.float64))
+    res = ReduceResult()
+    _check(_L().sfmloc_reduce_points(_ptr(X, C.c_double), n, None if A is None else _ptr(A, C.c_double), float(thres),
+                                     int(knn), C.byref(params) if params is not None else None, _ptr(owner, C.c_uint32),
+                                     _ptr(order, C.c_uint32), _ptr(dist, C.c_double), C.byref(res)))
+    return {"owner": owner, "order": order[:res.n_absorbed], "dist": dist, "n_keep": int(res.n_keep),
+            "n_absorbed": int(res.n_absorbed), "n_pairs": int(res.n_pairs), "rounds": int(res.rounds)}
+
+
+def reduce_last_ms():
+    return float(_L().sfmloc_reduce_last_ms())
 
 
 class BowTrainer:

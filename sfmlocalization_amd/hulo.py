@@ -49,6 +49,8 @@ class ReconstructParam:                                  # hulo_param/Reconstruc
     locFeatDistRatio = 0.6
     locRansacRound = 25
     locSkipFrame = 3
+    ransacThresTransformWorldCoordinateRefImage = 0.3    # :221 (localizeGlobalCoordinate.py:210)
+    ransacThresTransformWorldCoordinateRefPoint = 0.1    # :226 (localizeGlobalCoordinateRefPoint.py:192)
 
 
 class LocalizeBOWParam:                                  # hulo_bow/LocalizeBOWParam.py:34
