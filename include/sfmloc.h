@@ -733,6 +733,37 @@ int sfmloc_sfm_debug_read(sfmloc_sfm *h, double *residual, double *min_cos);
 int sfmloc_sfm_json_rewrite(const char *in_path, const char *out_path);
 
 /* ------------------------------------------------------------------------- */
+/* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */
+/* reference runs after every reconstruction and merge): which view each landmark takes its colour from.  The greedy  */
+/* cover runs on the structure exactly as sfmloc_sfm_create received it (the keep masks of sfmloc_sfm_clean and the   */
+/* poses play no part); the host then reads the images in plan order and samples (sfmlocalization_amd/colorize.py,    */
+/* csrc/colorize_cli.cpp).  OpenMVG 1.1 points are unpinned readings; each says which reading was chosen:             */
+/*   counts      card[v] = the observations in view v of landmarks not coloured yet (every remaining landmark adds one */
+/*               per observation, as the reference's recount does).  A landmark names a view once in the reference    */
+/*               (Observations is a std::map); here one that names it twice counts twice.                             */
+/*   choice      the view with the largest card; among equals the lowest view index (divergence: the reference sorts  */
+/*               the counts with an unstable std::sort and takes the first, so its pick among equals is unspecified). */
+/*   colouring   the chosen view colours every uncoloured landmark it observes, at that observation (the first one    */
+/*               in CSR order when the landmark names the view twice).                                                */
+/*   stop        when the largest card is 0.  A view without uncoloured observations is never chosen.  (Divergence:   */
+/*               a landmark without observations makes the reference index an empty vector; here it stays uncoloured  */
+/*               and the tools write it black.)                                                                       */
+/*   arithmetic  integers only.  In one iteration a landmark is claimed by one lane only, and the decrements of card  */
+/*               are atomicSub on uint32_t, the same result in any order: two runs give the same arrays.              */
+/* The host enqueues SFMLOC_COLOR_CHUNK iterations at a time and reads the remaining-landmark count once per chunk;   */
+/* launches queued behind the last iteration return at once.                                                          */
+/* ------------------------------------------------------------------------- */
+#define SFMLOC_COLOR_CHUNK 64u
+/* order[k]   = view index chosen in iteration k, k < *n_order (n_order <= n_views; order holds n_views entries)
+ * lm_iter[l] = iteration in which landmark l was coloured (every landmark with at least one observation gets one;
+ *              0xFFFFFFFF for a landmark without observations)
+ * lm_obs[l]  = index into obs_view / obs_x of the observation the colour is read at (0 for an uncoloured landmark)
+ * lm_iter and lm_obs hold n_landmarks entries and may be NULL when there are none. */
+int sfmloc_sfm_color_plan(sfmloc_sfm *h, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs);
+/* device milliseconds of the calling thread's last sfmloc_sfm_color_plan (HIP events around its kernels) */
+double sfmloc_sfm_color_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
 /* Merging two maps (hulo_sfm/mergeSfM.py: mergeModel's RANSAC over 3D-3D matches, findMedianThres /                  */
 /* findMedianStructurePointsThres, merge_sfm_data / transform_sfm_data), the step between the localiser and           */
 /* OpenMVG_BA in the reference's mergeOneModel.  Points are host arrays [n*3]; A = model A's landmark, B = model B's, */

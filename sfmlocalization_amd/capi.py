@@ -166,6 +166,7 @@ SYMBOLS = [
     "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
     "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
+    "sfmloc_sfm_color_plan", "sfmloc_sfm_color_last_ms",
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
     "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
@@ -406,6 +407,9 @@ def _L():
         L.sfmloc_sfm_read.argtypes = [C.c_void_p, U8P, F64P, F64P, U8P, U8P]
         L.sfmloc_sfm_debug_read.argtypes = [C.c_void_p, F64P, F64P]
         L.sfmloc_sfm_json_rewrite.argtypes = [C.c_char_p, C.c_char_p]
+        L.sfmloc_sfm_color_plan.argtypes = [C.c_void_p, U32P, U32P, U32P, C.POINTER(C.c_uint64)]
+        L.sfmloc_sfm_color_last_ms.restype = C.c_double
+        L.sfmloc_sfm_color_last_ms.argtypes = []
         MPP = C.POINTER(MergeParams)
         L.sfmloc_merge_default_params.restype = None
         L.sfmloc_merge_default_params.argtypes = [MPP]
@@ -1126,6 +1130,15 @@ def sfm_default_params(**overrides):
     return p
 
 
+COLOR_CHUNK = 64                # SFMLOC_COLOR_CHUNK: iterations of the colouring plan enqueued per host read
+COLOR_UNSET = 0xFFFFFFFF        # lm_iter of a landmark without observations
+
+
+def sfm_color_last_ms():
+    """device milliseconds of this thread's last Sfm.color_plan"""
+    return float(_L().sfmloc_sfm_color_last_ms())
+
+
 def sfm_json_rewrite(in_path, out_path):
     """sfmloc_sfm_json_rewrite (host only): the C++ JSON writer of OpenMVG_BA on a parsed file"""
     _check(_L().sfmloc_sfm_json_rewrite(os.fsencode(in_path), os.fsencode(out_path)))
@@ -1211,6 +1224,17 @@ class Sfm:
         mc = np.zeros(max(1, self.n_landmarks))
         _check(_L().sfmloc_sfm_debug_read(self._h, _ptr(res, C.c_double), _ptr(mc, C.c_double)))
         return res[:self.n_obs], mc[:self.n_landmarks]
+
+    def color_plan(self):
+        """sfmloc_sfm_color_plan -> (order [n_order] view indices, lm_iter [n_landmarks] (COLOR_UNSET without
+        observations), lm_obs [n_landmarks] observation index): which view each landmark takes its colour from"""
+        order = np.zeros(max(1, self.n_views), np.uint32)
+        it = np.full(max(1, self.n_landmarks), COLOR_UNSET, np.uint32)
+        ob = np.zeros(max(1, self.n_landmarks), np.uint64)
+        n = C.c_uint32(0)
+        _check(_L().sfmloc_sfm_color_plan(self._h, _ptr(order, C.c_uint32), C.byref(n), _ptr(it, C.c_uint32),
+                                          _ptr(ob, C.c_uint64)))
+        return order[:n.value].copy(), it[:self.n_landmarks], ob[:self.n_landmarks]
 
     def close(self):
         if self._h:

@@ -666,6 +666,15 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
 }
 
 }  // namespace
+
+void sfm_color_view(const sfmloc_sfm *hh, SfmColorView *out) {
+  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
+  uint32_t longest = 0;
+  for (uint32_t v = 0; v < h->n_views; ++v) longest = std::max(longest, h->h_view_off[v + 1] - h->h_view_off[v]);
+  *out = SfmColorView{h->device,    h->s,          h->n_views,  h->n_lm,     longest,
+                      h->d_obs_off, h->d_obs_view, h->d_obs_lm, h->d_vlist, h->d_view_off};
+}
+
 }  // namespace sfmloc
 
 using namespace sfmloc;

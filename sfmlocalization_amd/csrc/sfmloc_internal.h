@@ -475,4 +475,16 @@ int ctx_resection_wait_done(Ctx *c);
 int ctx_set_query_camera(Ctx *c, const Query *q, const char *who);
 void ctx_set_uncalibrated_camera(Ctx *c, uint32_t width, uint32_t height);  // ... from here on uncalibrated, image w x h
 
+// adjust.hip: what the colouring plan (colorize.hip) reads of a device-resident sfm_data -- the structure as
+// sfmloc_sfm_create received it: the CSR by landmark and the per-view lists of the transpose (vlist = observation
+// indices sorted by view, ascending inside a view; view_off [n_views + 1]; obs_lm = an observation's landmark)
+struct SfmColorView {
+  int device;
+  hipStream_t s;
+  uint32_t n_views, n_lm, max_view_obs;  // max_view_obs: the longest per-view list
+  const uint64_t *d_obs_off;
+  const uint32_t *d_obs_view, *d_obs_lm, *d_vlist, *d_view_off;
+};
+void sfm_color_view(const sfmloc_sfm *h, SfmColorView *out);
+
 }  // namespace sfmloc

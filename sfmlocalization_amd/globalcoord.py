@@ -4,7 +4,7 @@ map pipeline between OpenMVG_BA and the server, which reads the Amat.yml written
 
     python -m sfmlocalization_amd.globalcoord <project_dir> <matches_dir> <sfm_data_dir> [-t test_project_dir]
                                               [-o loc_global.json] [--bow] [--reduce-points] [--ref-points]
-                                              [--model=similarity|affine] [--seed=N] [--device=0]
+                                              [--model=similarity|affine] [--seed=N] [--device=0] [--ply]
 
   1. Amat (3 x 4, world ~ Amat [map; 1]) by RANSAC (sfmloc_merge_ransac, 1000 rounds) over <project_dir>/Ref: with
      --ref-points the landmarks of Ref/refpoints.json ({"refpoints": [{"key": landmark, "X": world}, ...]}) against
@@ -14,15 +14,17 @@ map pipeline between OpenMVG_BA and the server, which reads the Amat.yml written
   2. --reduce-points: landmarks closer than 1 cm in world coordinates are folded into the one of lowest index
      (sfmloc_reduce_points); sfm_data.json is rewritten, the original kept as sfm_data_b4rp.json.
   3. sfm_data_global.json: the map in world coordinates (sfmloc_merge_transform).
+     --ply: colorized_global.ply, colorized_global_camera.ply and colorized_global_structure.ply beside it
+     (localizeGlobalCoordinate.py:229-231, through sfmlocalization_amd.colorize); the images of the map must be readable.
   4. -t: every <test_project_dir>/<folder>/inputImg is localised into <folder>/loc (center.txt, <test_project_dir>/log.txt)
      and <folder>/loc/<-o> holds every result with t and R in world coordinates (t_relative, R_relative: the map's).
 
 The fit, the transform and the thinning run on the device; the dictionary work is host Python.  Every function takes
 `ops`, as sfmlocalization_amd.merge does (default: the C ABI; there is no host fallback in this package).
 
-Left out: the PLY files (colorized_global*.ply) -- they start from openMVG_main_ComputeSfM_DataColor, an external
-program this package does not have; PlyUtils.addPointToPly, which appends the localised centres to
-colorized_global_structure.ply, runs only where that file already exists.  --beacon is refused, as elsewhere.
+The PLY files are opt-in (--ply): without the flag nothing is coloured, and PlyUtils.addPointToPly, which appends
+the localised centres to colorized_global_structure.ply, runs only where that file already exists.  --beacon is
+refused, as elsewhere.
 """
 import argparse
 import glob
@@ -33,7 +35,7 @@ import sys
 
 import numpy as np
 
-from . import hulo, merge
+from . import colorize, hulo, merge
 
 REDUCE_THRES, REDUCE_KNN = 0.01, 1000        # localizeGlobalCoordinateRefPoint.py:221
 RANSAC_ROUNDS = 1000                         # :192, localizeGlobalCoordinate.py:210
@@ -224,7 +226,8 @@ def image_correspondences(ref_loc, names):
 
 
 def run(project_dir, matches_dir, sfm_data_dir, test_project_dir=None, output_json_filename="loc_global.json",
-        use_bow=False, reduce_points=False, ref_points=False, model="similarity", seed=None, device=0, ops=None, log=print):
+        use_bow=False, reduce_points=False, ref_points=False, model="similarity", seed=None, device=0, ops=None, log=print,
+        ply=False):
     """main() of the two scripts -> 0, or 1 when nothing could be fitted (the reference returns silently)"""
     ops = _ops(ops, seed=seed, device=device)
     ref_folder = project_dir + "/Ref"
@@ -250,7 +253,14 @@ def run(project_dir, matches_dir, sfm_data_dir, test_project_dir=None, output_js
         with open(sfm_json, "w") as fh:
             json.dump(doc, fh)
         log("finish reducing 3D points.")
-    save_global_sfm(sfm_json, amat_txt, os.path.join(sfm_data_dir, "sfm_data_global.json"), ops=ops)
+    sfm_global = os.path.join(sfm_data_dir, "sfm_data_global.json")
+    save_global_sfm(sfm_json, amat_txt, sfm_global, ops=ops)
+    if ply:                                                     # localizeGlobalCoordinate.py:229-231
+        if (colorize.run(sfm_global, os.path.join(sfm_data_dir, "colorized_global.ply"), device)
+                or colorize.save_camera_ply(sfm_global, os.path.join(sfm_data_dir, "colorized_global_camera.ply"), device)
+                or colorize.save_structure_ply(sfm_global, os.path.join(sfm_data_dir, "colorized_global_structure.ply"),
+                                               device)):
+            return 1
     if not test_project_dir:
         return 0
     total = done = 0                                            # :239-378
@@ -296,6 +306,7 @@ def parse_args(argv):
     ap.add_argument("--model", choices=sorted(merge.MODELS), default="similarity")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=None)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--ply", action="store_true")
     return ap.parse_args(argv)
 
 
@@ -307,7 +318,8 @@ def main(argv=None, ops=None):
     from . import capi
     try:
         return run(a.project_dir, a.matches_dir, a.sfm_data_dir, a.test_project_dir, a.output_json_filename, a.bow,
-                   a.reduce_points, a.ref_points, a.model, a.seed, a.device, ops=ops, log=lambda s: print(s, flush=True))
+                   a.reduce_points, a.ref_points, a.model, a.seed, a.device, ops=ops, log=lambda s: print(s, flush=True),
+                   ply=a.ply)
     except capi.SfmlocError as e:
         print(f"globalcoord: {e.message}", file=sys.stderr)
         return 1

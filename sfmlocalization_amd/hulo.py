@@ -32,6 +32,8 @@ LOCALIZE_PROJECT_PATH = os.path.join(_BIN, LOCALIZE_PROJECT)
 EXTRACT_FEATURE_MATCH_PROJECT_PATH = os.path.join(_BIN, EXTRACT_FEATURE_MATCH_PROJECT)
 BUNDLE_ADJUSTMENT_PROJECT = "OpenMVG_BA"                # ReconstructParam.py:36 (run per merge, sfmMergeGraph.py:297)
 BUNDLE_ADJUSTMENT_PROJECT_PATH = os.path.join(_BIN, BUNDLE_ADJUSTMENT_PROJECT)
+COLORIZE_PROJECT = "openMVG_main_ComputeSfM_DataColor"   # called by its bare name (reconstructGraph.py:182, PlyUtils.py:35)
+COLORIZE_PROJECT_PATH = os.path.join(_BIN, COLORIZE_PROJECT)
 
 
 class LocalizeParam:                                     # hulo_param/LocalizeParam.py:23-35
