@@ -733,6 +733,60 @@ int sfmloc_sfm_debug_read(sfmloc_sfm *h, double *residual, double *min_cos);
 int sfmloc_sfm_json_rewrite(const char *in_path, const char *out_path);
 
 /* ------------------------------------------------------------------------- */
+/* The separable commands of OpenMVG_BA -c (adjust_sfm_data.cpp:158-244): structure alone (s), or the poses alone      */
+/* (r, t, rt), on the resident sfm_data.  With the other side and the intrinsics fixed every landmark (3 parameters)   */
+/* or every pose (3 or 6) is a problem of its own with a unique minimum; the joint commands (structure with a pose      */
+/* part, anything with intrinsics) are refused.  Semantics restated from OpenMVG 1.1's Bundle_Adjustment_Ceres::Adjust  */
+/* (all unpinned readings; each says which reading was chosen):                                                         */
+/*   blocks      reading chosen, unpinned: a pose is [angle-axis of R (3), t (3)] with t = -R C, t_i =                  */
+/*               -((R_i0 C0 + R_i1 C1) + R_i2 C2).  r holds t constant (not C: the centre moves), t holds the rotation  */
+/*               constant (its R keeps its bits).  Views that share an id_pose share one block.  After the call        */
+/*               C = -R^T t, C_i = -((R_0i t0 + R_1i t1) + R_2i t2).                                                   */
+/*   residual    reading chosen, unpinned: two values per observation, proj - obs.x, with the arithmetic of the        */
+/*               cleaning residual ("residual" above) on Xc_i = ((R_i0 X0 + R_i1 X1) + R_i2 X2) + t_i: p = (Xc0 / Xc2, */
+/*               Xc1 / Xc2), the radial factor ((1 + k1 r2) + k2 r4) + k3 r6 for pinhole_radial_k3, proj = f p + pp.    */
+/*               The intrinsics are constants.                                                                          */
+/*   loss        reading chosen, unpinned: Ceres HuberLoss(a), a = Square(4.0) = 16 (the squared 4.0 is the reference's */
+/*               quirk, kept), on s = |r|^2: rho(s) = s for s <= a^2, else 2 a sqrt(s) - a^2.  cost = 1/2 sum rho.       */
+/*   entering    reading chosen, unpinned: the kept observations of kept landmarks (all of them before the first        */
+/*               sfmloc_sfm_clean).  One whose view has no pose: SFMLOC_EINVAL, the text names the view.  A pose or a   */
+/*               landmark no entering observation refers to keeps its bits.                                             */
+/*   solver      reading chosen, unpinned: Levenberg-Marquardt on each block's normal equations (A + lambda D) d = -g,  */
+/*               D = diag(A) clamped to [1e-6, 1e32], lambda = 1e-4 at the start; a step is accepted when (cost -       */
+/*               cost') / (model decrease) > 1e-3, then lambda *= max(1/3, 1 - (2 q - 1)^3); a rejected step multiplies */
+/*               lambda by 2, 4, 8, ...; at most 500 steps tried per block.  The loss enters as the first-order        */
+/*               reweighting: residual and Jacobian rows times sqrt(rho'), no second-order (Triggs) correction.  A     */
+/*               rotation steps in the tangent space at the current R, R <- exp([w]x) R (divergence: Ceres steps in    */
+/*               the angle-axis itself; the path differs, the minimum does not).                                       */
+/*   stopping    (divergence) Ceres runs one joint LM with one trust region and stops on the total cost               */
+/*               (function_tolerance 1e-6).  Here every block stops on its own: after an accepted step whose relative   */
+/*               cost decrease is <= 1e-14, or a rejected one whose model decrease is <= 1e-14 of the cost (the f64     */
+/*               floor: below it the cost's own rounding decides), so every block is at least as converged as Ceres     */
+/*               leaves it.  A step that does not lower the block's cost is never applied (no block ends above its     */
+/*               input cost); a non-finite step or cost counts as rejected.                                           */
+/*   order       sums run lane-strided and then through a fixed in-wave butterfly; no float atomics: two runs give    */
+/*               the same bits.  The report's totals are summed on the host in ascending block index.                  */
+/* ------------------------------------------------------------------------- */
+#define SFMLOC_BA_ROTATION 1u
+#define SFMLOC_BA_TRANSLATION 2u
+#define SFMLOC_BA_INTRINSICS 4u
+#define SFMLOC_BA_STRUCTURE 8u
+typedef struct sfmloc_ba_report {
+  double cost_initial, cost_final; /* 1/2 sum rho over the entering observations, before and after */
+  uint32_t n_blocks;               /* blocks with at least one entering observation */
+  uint32_t n_at_cap;               /* blocks that tried 500 steps without meeting the stopping rule */
+  uint32_t n_unchanged;            /* blocks left at their input (no accepted step) */
+  uint32_t max_iterations;         /* the largest number of steps one block tried */
+} sfmloc_ba_report;
+/* what: 0 (nothing), ROTATION, TRANSLATION, ROTATION | TRANSLATION or STRUCTURE; any other value: SFMLOC_EINVAL, the
+ * handle untouched.  rep may be NULL.  A bounded number of launches, no host round trip per iteration.
+ * sfmloc_sfm_clean may follow an adjust (and the next adjust a clean): a later clean works on what the earlier one
+ * kept, as the reference's second cleanup works on the reduced structure (counts[0] = the landmarks kept so far). */
+int sfmloc_sfm_adjust(sfmloc_sfm *h, uint32_t what, sfmloc_ba_report *rep);
+/* the landmarks' X as they are now; sfmloc_sfm_read gives the poses */
+int sfmloc_sfm_read_structure(sfmloc_sfm *h, double *X /*[n_landmarks*3]*/);
+
+/* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */
 /* reference runs after every reconstruction and merge): which view each landmark takes its colour from.  The greedy  */
 /* cover runs on the structure exactly as sfmloc_sfm_create received it (the keep masks of sfmloc_sfm_clean and the   */

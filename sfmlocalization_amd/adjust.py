@@ -1,6 +1,6 @@
-"""OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) without -c, over the C ABI: the call the reference's merge loop makes
-once per candidate merge (hulo_sfm/sfmMergeGraph.py:297, hulo_bow/sfmMergeGraphBOW.py:226,
-hulo_ibeacon/sfmMergeGraphIBeacon.py:322).
+"""OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) over the C ABI: the call the reference's merge loop makes once per
+candidate merge (hulo_sfm/sfmMergeGraph.py:297, hulo_bow/sfmMergeGraphBOW.py:226,
+hulo_ibeacon/sfmMergeGraphIBeacon.py:322), and the separable commands of its -c switch.
 
     python -m sfmlocalization_amd.adjust <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [--device=0]
 
@@ -8,8 +8,16 @@ Every view with more than 10 observations is re-resected on the device, <folder 
 written with the new poses and the structure untouched, the structure is cleaned (residual 4 px, angle 2 degrees, the
 unstable poses with -r=1) and the result goes to sfm_data_out (in place works).  Both files are json.dump of the
 document: views, intrinsics, root_path and key order as in the input, extrinsics in ascending pose id, control_points
-[].  bin/OpenMVG_BA (csrc/adjust_cli.cpp) is the same program and writes the same bytes.  -c (the Ceres bundle
-adjustment) is not supported yet: refused with status 1, nothing written.  The semantics are stated in include/sfmloc.h.
+[].  bin/OpenMVG_BA (csrc/adjust_cli.cpp) is the same program and writes the same bytes.
+
+-c=item,item,... (adjust_sfm_data.cpp:158-244): after the re-resection and sfm_data_b4bd.json every item is run in
+order: s adjusts the structure alone, r / t / rt the rotations / translations / both alone (sfmloc_sfm_adjust: every
+landmark or pose is a problem of its own), and a c in the item cleans afterwards (4 px, 2 degrees, -r) and prints the
+four counts.  An item with none of r t i s adjusts nothing.  With a non-empty -c there is no final cleanup of its own
+(the reference cleans in the else branch only), and the output holds the adjusted poses (C = -R^T t) and X.  The joint
+commands -- structure together with a pose part (rs, rst, ...) and anything with i -- are not supported yet: every item
+is checked before anything is opened, and one refused item ends the run with status 1 and nothing written.  The
+semantics are stated in include/sfmloc.h.
 """
 import json
 import os
@@ -23,7 +31,10 @@ UNSUPPORTED_TYPE = 0xFFFFFFFF                # any other intrinsic type (sfmloc_
 
 USAGE = ("Execute bundle adjustment for sfm_data.json\n"
          "Usage: OpenMVG_BA [params] sfm_data sfm_data_out\n"
-         "\t-c, --command\n\t\tCommand for order of bundle adjustment (not supported yet: only the default, no BD)\n"
+         "\t-c, --command\n\t\tCommand for order of bundle adjustment (BD) [default=no BD] [options:r = rotation, "
+         "t = translation, s = structure, c = clean]. Usage example: c=r,tc,s means BD with rotation only, then BD with "
+         "translation follow by cleaning, then BD with structure. Not supported yet: i (intrinsic), and s together "
+         "with r or t.\n"
          "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n")
 
 
@@ -131,9 +142,30 @@ def _write(path, doc):
         json.dump(doc, fh)
 
 
-def run(in_path, out_path, rm_unstable=False, device=0, log=print):
+def command_items(command):
+    """-c split on commas as the reference's getline loop splits it (no item after a trailing comma)"""
+    items = command.split(",") if command else []
+    if items and items[-1] == "":
+        items.pop()
+    return items
+
+
+def refused_item(items):
+    """the first item that is not separable (structure with a pose part, or intrinsics), or None"""
+    for item in items:
+        if "i" in item or ("s" in item and ("r" in item or "t" in item)):
+            return item
+    return None
+
+
+def _bits_differ(a, b):
+    return (np.ascontiguousarray(a, np.float64).view(np.uint64) != np.ascontiguousarray(b, np.float64).view(np.uint64))
+
+
+def run(in_path, out_path, rm_unstable=False, device=0, log=print, command=""):
     """The tool's body.  Returns 0, or 1 after an error message on stderr."""
     from . import capi as S
+    items = command_items(command)
     log("Start bundle adjustment over sfm_data.json.")
     log(f"Reading sfm_data.json file : {in_path}")
     try:
@@ -161,24 +193,49 @@ def run(in_path, out_path, rm_unstable=False, device=0, log=print):
         b4 = _with(doc, extrinsics=_extrinsics(pose_id, pose_src, p["pose_valid"], p["pose_R"], p["pose_C"], replaced),
                    control_points=[])
         _write(os.path.join(os.path.dirname(in_path), "sfm_data_b4bd.json"), b4)
-        counts = h.clean(RESIDUAL_PX, ANGLE_DEG, rm_unstable)
-        q = h.read(masks=True)
+
+        def clean():
+            counts = h.clean(RESIDUAL_PX, ANGLE_DEG, rm_unstable)
+            log(f"Number of points before cleanup : {counts[0]}")
+            log(f"Number of points residual error : {counts[1]}")
+            log(f"Number of points angle error : {counts[2]}")
+            log(f"Number of points after cleanup : {counts[3]}")
+        cleaned = False
+        for item in items:
+            rot, trn, stru = "r" in item, "t" in item, "s" in item
+            log("\nBundle adjustment over " + ("rotations, " if rot else "") + ("translations, " if trn else "")
+                + ("structure, " if stru else ""))
+            h.adjust((S.BA_ROTATION if rot else 0) | (S.BA_TRANSLATION if trn else 0) | (S.BA_STRUCTURE if stru else 0))
+            if "c" in item:
+                clean()
+                cleaned = True
+        if not items:
+            clean()
+            cleaned = True
+        q = h.read(masks=cleaned)
+        X = h.read_structure() if items else None
     except S.SfmlocError as e:
         print(f"OpenMVG_BA: {e.message}", file=sys.stderr)
         return 1
     finally:
         h.close()
-    log(f"Number of points before cleanup : {counts[0]}")
-    log(f"Number of points residual error : {counts[1]}")
-    log(f"Number of points angle error : {counts[2]}")
-    log(f"Number of points after cleanup : {counts[3]}")
+    if items:          # a pose or a landmark the adjustment moved is written from the arrays, the others as they were
+        moved = _bits_differ(q["pose_R"].reshape(-1, 9), p["pose_R"].reshape(-1, 9)).any(1) | \
+            _bits_differ(q["pose_C"], p["pose_C"]).any(1)
+        replaced = replaced | moved
+        p = q
     off = arrays["obs_off"]
     structure = []
     for l, e in enumerate(doc.get("structure", [])):
-        if not q["landmark_keep"][l]:
+        if cleaned and not q["landmark_keep"][l]:
             continue
-        obs = [o for j, o in enumerate(e["value"]["observations"]) if q["obs_keep"][int(off[l]) + j]]
-        structure.append(_with(e, value=_with(e["value"], observations=obs)))
+        val = e["value"]
+        if cleaned:
+            obs = [o for j, o in enumerate(val["observations"]) if q["obs_keep"][int(off[l]) + j]]
+            val = _with(val, observations=obs)
+        if X is not None and _bits_differ(X[l], arrays["landmark_X"][l]).any():
+            val = _with(val, X=[float(x) for x in X[l]])
+        structure.append(_with(e, value=val))
     out = _with(doc, extrinsics=_extrinsics(pose_id, pose_src, q["pose_valid"], p["pose_R"], p["pose_C"], replaced))
     if "structure" in doc:
         out["structure"] = structure
@@ -214,14 +271,15 @@ def main(argv=None):
     if len(pos) < 2 or not pos[0] or not pos[1]:
         sys.stderr.write(USAGE)
         return 1
-    if command:
-        print(f"OpenMVG_BA: -c={command}: the bundle adjustment command (-c) is not supported yet; nothing was written",
-              file=sys.stderr)
+    bad = refused_item(command_items(command))
+    if bad is not None:
+        print(f"OpenMVG_BA: -c={command}: item \"{bad}\" is not supported yet (-c adjusts the structure alone, or "
+              "rotations / translations alone; no intrinsics); nothing was written", file=sys.stderr)
         return 1
 
     def log(s):
         print(s, flush=True)
-    return run(pos[0], pos[1], rm_unstable=rm_unstable != 0, device=device, log=log)
+    return run(pos[0], pos[1], rm_unstable=rm_unstable != 0, device=device, log=log, command=command)
 
 
 if __name__ == "__main__":

@@ -106,6 +106,14 @@ class SfmViewResult(C.Structure):
                 ("P", C.c_double * 12), ("R", C.c_double * 9), ("center", C.c_double * 3)]
 
 
+class BaReport(C.Structure):
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_blocks", C.c_uint32),
+                ("n_at_cap", C.c_uint32), ("n_unchanged", C.c_uint32), ("max_iterations", C.c_uint32)]
+
+
+BA_ROTATION, BA_TRANSLATION, BA_INTRINSICS, BA_STRUCTURE = 1, 2, 4, 8
+
+
 class MergeParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("device", C.c_int), ("rounds_per_launch", C.c_uint32), ("profile", C.c_int),
                 ("reserved", C.c_int)]
@@ -166,7 +174,7 @@ SYMBOLS = [
     "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
     "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
-    "sfmloc_sfm_color_plan", "sfmloc_sfm_color_last_ms",
+    "sfmloc_sfm_color_plan", "sfmloc_sfm_color_last_ms", "sfmloc_sfm_adjust", "sfmloc_sfm_read_structure",
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
     "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
@@ -410,6 +418,8 @@ def _L():
         L.sfmloc_sfm_color_plan.argtypes = [C.c_void_p, U32P, U32P, U32P, C.POINTER(C.c_uint64)]
         L.sfmloc_sfm_color_last_ms.restype = C.c_double
         L.sfmloc_sfm_color_last_ms.argtypes = []
+        L.sfmloc_sfm_adjust.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaReport)]
+        L.sfmloc_sfm_read_structure.argtypes = [C.c_void_p, F64P]
         MPP = C.POINTER(MergeParams)
         L.sfmloc_merge_default_params.restype = None
         L.sfmloc_merge_default_params.argtypes = [MPP]
@@ -1217,6 +1227,19 @@ class Sfm:
             out["obs_keep"] = ok_[:self.n_obs].astype(bool)
             out["landmark_keep"] = lk[:self.n_landmarks].astype(bool)
         return out
+
+    def adjust(self, what):
+        """sfmloc_sfm_adjust: the separable bundle adjustment -- what = BA_STRUCTURE, BA_ROTATION, BA_TRANSLATION or
+        BA_ROTATION | BA_TRANSLATION (0: nothing) -> BaReport"""
+        rep = BaReport()
+        _check(_L().sfmloc_sfm_adjust(self._h, int(what), C.byref(rep)))
+        return rep
+
+    def read_structure(self):
+        """-> the landmarks' X [n_landmarks, 3] as they are now"""
+        X = np.zeros((max(1, self.n_landmarks), 3))
+        _check(_L().sfmloc_sfm_read_structure(self._h, _ptr(X, C.c_double)))
+        return X[:self.n_landmarks]
 
     def debug_read(self):
         """-> (residual norm per observation, minimum clamped cosine per landmark); NaN where not evaluated"""

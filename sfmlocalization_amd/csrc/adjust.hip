@@ -11,7 +11,10 @@
 //               gang session, the view's id_view as the sampling stream and its own intrinsic.
 //   cleanup     f64, unfused (the library's -ffp-contract=off): residual per observation, the clamped cosine of every
 //               pair of a landmark's remaining observations (minimum kept), and the -r fixed point as one workgroup's
-//               loop over pose counts (integer atomics: a count does not depend on order).
+//               loop over pose counts (integer atomics: a count does not depend on order).  A later cleanup works on
+//               what the earlier ones kept.
+//   adjustment  the separable commands of -c (sfmloc_sfm_adjust): this file checks the poses and hands the resident
+//               arrays to ba_separable.hip, whose kernels move X or the poses in place.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -65,6 +68,11 @@ struct Sfm {
   double *d_res = nullptr, *d_ray = nullptr, *d_mincos = nullptr;
   uint8_t *d_obs_keep = nullptr, *d_lm_stage = nullptr;
   uint32_t *d_pose_cnt = nullptr, *d_passes = nullptr;
+  // the separable adjustment (ba_separable.hip): t = -R C per pose, every pose's views (CSR by pose, ascending view
+  // index), a block's costs and outcome; host copies of the keep masks for the pose check of a call after a cleanup
+  double *d_pose_t = nullptr, *d_blk_cost = nullptr;
+  uint32_t *d_pose_view_off = nullptr, *d_pose_views = nullptr, *d_blk_info = nullptr;
+  std::vector<uint8_t> h_obs_keep, h_lm_stage;
   // K5's contexts hang off a map without descriptors: its log10 table, parameters and launch heuristics
   sfmloc_map *map = nullptr;
   std::vector<sfmloc_context *> ctx;
@@ -93,7 +101,8 @@ void sfm_free(Sfm *h) {
                   h->d_pose_R,   h->d_pose_C,    h->d_lm_id,     h->d_lm_X,      h->d_obs_off,  h->d_obs_view,
                   h->d_obs_lm,   h->d_obs_x,     h->d_vlist,     h->d_vkey,      h->d_view_off, h->d_hist,
                   h->d_tmp_k,    h->d_tmp_v,     h->d_res,       h->d_ray,       h->d_mincos,   h->d_obs_keep,
-                  h->d_lm_stage, h->d_pose_cnt,  h->d_passes};
+                  h->d_lm_stage, h->d_pose_cnt,  h->d_passes,    h->d_pose_t,    h->d_blk_cost, h->d_pose_view_off,
+                  h->d_pose_views, h->d_blk_info};
   for (void *p : ptrs)
     if (p) hipFree(p);
   if (h->s) hipStreamDestroy(h->s);
@@ -231,8 +240,8 @@ __global__ __launch_bounds__(256) void k_adj_residual(uint64_t n_obs, const uint
                                                       const uint32_t *__restrict__ view_pose,
                                                       const uint32_t *__restrict__ intr_type, const double *__restrict__ intr,
                                                       const double *__restrict__ pose_R, const double *__restrict__ pose_C,
-                                                      double thr, double *__restrict__ res, double *__restrict__ ray,
-                                                      uint8_t *__restrict__ keep) {
+                                                      double thr, int again, double *__restrict__ res,
+                                                      double *__restrict__ ray, uint8_t *__restrict__ keep) {
   const uint64_t o = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= n_obs) return;
   const uint32_t l = obs_lm[o], v = obs_view[o];
@@ -259,7 +268,8 @@ __global__ __launch_bounds__(256) void k_adj_residual(uint64_t n_obs, const uint
   const double ex = x - (f * p0 + ppx), ey = y - (f * p1 + ppy);
   const double nrm = sqrt(ex * ex + ey * ey);
   res[o] = nrm;
-  keep[o] = (nrm > thr) ? 0 : 1;
+  const uint8_t was = again ? keep[o] : 1;  // (a later cleanup: what an earlier one removed stays removed)
+  keep[o] = (nrm > thr) ? 0 : was;
   // bearing: get_ud_pixel (radial), K^-1 (x, y, 1), normalised, then R^T
   double ux = x, uy = y;
   if (radial) geom::ud_pixel_k3(f, ppx, ppy, K[3], K[4], K[5], x, y, &ux, &uy);
@@ -276,13 +286,19 @@ __global__ __launch_bounds__(256) void k_adj_residual(uint64_t n_obs, const uint
 }
 
 // per landmark: fewer than 2 observations left -> stage 0 (residual filter); else the minimum clamped cosine over all
-// pairs -> stage 1 when acos(c) * 180 / pi < angle_deg (angle filter), else 3 (kept)
+// pairs -> stage 1 when acos(c) * 180 / pi < angle_deg (angle filter), else 3 (kept).  A later cleanup (again): a
+// landmark an earlier one removed becomes stage 4 (gone before this cleanup began) and is not looked at
 __global__ __launch_bounds__(256) void k_adj_landmarks(uint32_t n_lm, const uint64_t *__restrict__ obs_off,
                                                        const uint8_t *__restrict__ keep, const double *__restrict__ ray,
-                                                       double angle_deg, double *__restrict__ mincos,
+                                                       double angle_deg, int again, double *__restrict__ mincos,
                                                        uint8_t *__restrict__ stage) {
   const uint32_t l = blockIdx.x * 256 + threadIdx.x;
   if (l >= n_lm) return;
+  if (again && stage[l] != 3) {
+    stage[l] = 4;
+    mincos[l] = geom::q_nan();
+    return;
+  }
   const uint64_t a = obs_off[l], b = obs_off[l + 1];
   uint32_t k = 0;
   for (uint64_t o = a; o < b; ++o) k += keep[o];
@@ -489,6 +505,19 @@ int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *
   ADJ_TRY(sfm_alloc(&h->d_lm_stage, d->n_landmarks));
   ADJ_TRY(sfm_alloc(&h->d_pose_cnt, d->n_poses));
   ADJ_TRY(sfm_alloc(&h->d_passes, 1));
+  {
+    std::vector<uint32_t> pv_off((size_t)d->n_poses + 1, 0), pv(d->n_views);
+    for (uint32_t v = 0; v < d->n_views; ++v) ++pv_off[d->view_pose[v] + 1];
+    for (uint32_t p = 0; p < d->n_poses; ++p) pv_off[p + 1] += pv_off[p];
+    std::vector<uint32_t> at(pv_off.begin(), pv_off.end() - 1);
+    for (uint32_t v = 0; v < d->n_views; ++v) pv[at[d->view_pose[v]]++] = v;  // (ascending view index inside a pose)
+    ADJ_TRY(sfm_upload(&h->d_pose_view_off, pv_off.data(), pv_off.size(), s));
+    ADJ_TRY(sfm_upload(&h->d_pose_views, pv.data(), pv.size(), s));
+    SFM_HIP(hipStreamSynchronize(s));  // (the vectors leave scope)
+  }
+  ADJ_TRY(sfm_alloc(&h->d_pose_t, 3 * (size_t)d->n_poses));
+  ADJ_TRY(sfm_alloc(&h->d_blk_cost, 2 * (size_t)std::max(d->n_poses, d->n_landmarks)));
+  ADJ_TRY(sfm_alloc(&h->d_blk_info, (size_t)std::max(d->n_poses, d->n_landmarks)));
   ADJ_TRY(sfm_transpose(h));
   const uint32_t vid0 = 0, voff[2] = {0, 0};
   sfmloc_map_desc md;
@@ -625,23 +654,46 @@ int sfm_resect_impl(Sfm *h, uint32_t *n_ran, uint32_t *n_ok) {
   return SFMLOC_OK;
 }
 
-int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
-  // GetPoseOrDie: the first observation (landmark order) whose view has no pose stops the reference's cleanup
-  for (uint32_t l = 0; l < h->n_lm; ++l)
+// the keep masks of the last cleanup on the host (what a later cleanup or adjustment checks the poses against)
+int sfm_fetch_masks(Sfm *h) {
+  if (!h->cleaned) return SFMLOC_OK;
+  h->h_obs_keep.resize(h->n_obs);
+  h->h_lm_stage.resize(h->n_lm);
+  if (h->n_obs) SFM_HIP(hipMemcpyAsync(h->h_obs_keep.data(), h->d_obs_keep, h->n_obs, hipMemcpyDeviceToHost, h->s));
+  if (h->n_lm) SFM_HIP(hipMemcpyAsync(h->h_lm_stage.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost, h->s));
+  SFM_HIP(hipStreamSynchronize(h->s));
+  return SFMLOC_OK;
+}
+
+// GetPoseOrDie: the first observation (landmark order) still in the structure whose view has no pose
+int sfm_check_poses(Sfm *h, const char *what) {
+  const int rc = sfm_fetch_masks(h);
+  if (rc) return rc;
+  for (uint32_t l = 0; l < h->n_lm; ++l) {
+    if (h->cleaned && h->h_lm_stage[l] != 3) continue;
     for (uint64_t o = h->h_obs_off[l]; o < h->h_obs_off[l + 1]; ++o) {
+      if (h->cleaned && !h->h_obs_keep[o]) continue;
       const uint32_t v = h->h_obs_view[o];
       SFM_CHECK(h->h_pose_valid[h->h_view_pose[v]], SFMLOC_EINVAL,
-                "view %u has observations but no pose (GetPoseOrDie): the structure cannot be cleaned", h->h_view_id[v]);
+                "view %u has observations but no pose (GetPoseOrDie): the structure cannot be %s", h->h_view_id[v], what);
     }
+  }
+  return SFMLOC_OK;
+}
+
+int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
+  const int rc_pose = sfm_check_poses(h, "cleaned");
+  if (rc_pose) return rc_pose;
+  const int again = h->cleaned ? 1 : 0;  // a later cleanup works on what the earlier ones kept
   hipStream_t s = h->s;
   if (h->n_obs)
     hipLaunchKernelGGL(k_adj_residual, dim3((unsigned)((h->n_obs + 255) / 256)), dim3(256), 0, s, h->n_obs, h->d_obs_lm,
                        h->d_obs_view, h->d_obs_x, h->d_lm_X, h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,
-                       h->d_pose_R, h->d_pose_C, residual_px, h->d_res, h->d_ray, h->d_obs_keep);
+                       h->d_pose_R, h->d_pose_C, residual_px, again, h->d_res, h->d_ray, h->d_obs_keep);
   SFM_HIP(hipGetLastError());
   if (h->n_lm)
     hipLaunchKernelGGL(k_adj_landmarks, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->n_lm, h->d_obs_off,
-                       h->d_obs_keep, h->d_ray, angle_deg, h->d_mincos, h->d_lm_stage);
+                       h->d_obs_keep, h->d_ray, angle_deg, again, h->d_mincos, h->d_lm_stage);
   SFM_HIP(hipGetLastError());
   if (rm_unstable) {
     hipLaunchKernelGGL(k_adj_unstable, dim3(1), dim3(1024), 0, s, h->n_lm, h->d_obs_off, h->d_obs_view, h->d_view_pose,
@@ -653,15 +705,56 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
   SFM_HIP(hipMemcpyAsync(h->h_pose_valid.data(), h->d_pose_valid, h->n_poses, hipMemcpyDeviceToHost, s));
   SFM_HIP(hipStreamSynchronize(s));
   if (counts) {
-    counts[0] = h->n_lm;
-    counts[1] = counts[2] = counts[3] = 0;
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
     for (uint8_t st : stage) {
+      if (st == 4) continue;  // (gone before this cleanup)
+      ++counts[0];
       counts[1] += st >= 1;
       counts[2] += st >= 2;
       counts[3] += st == 3;
     }
   }
   h->cleaned = true;
+  return SFMLOC_OK;
+}
+
+int sfm_adjust_impl(Sfm *h, uint32_t what, sfmloc_ba_report *rep) {
+  const int rc = sfm_check_poses(h, "adjusted");
+  if (rc) return rc;
+  SfmBaView v;
+  v.s = h->s;
+  v.n_views = h->n_views;
+  v.n_poses = h->n_poses;
+  v.n_lm = h->n_lm;
+  v.d_view_intr = h->d_view_intr;
+  v.d_view_pose = h->d_view_pose;
+  v.d_intr_type = h->d_intr_type;
+  v.d_intr = h->d_intr;
+  v.d_pose_R = h->d_pose_R;
+  v.d_pose_C = h->d_pose_C;
+  v.d_pose_t = h->d_pose_t;
+  v.d_lm_X = h->d_lm_X;
+  v.d_obs_off = h->d_obs_off;
+  v.d_obs_view = h->d_obs_view;
+  v.d_obs_lm = h->d_obs_lm;
+  v.d_vlist = h->d_vlist;
+  v.d_view_off = h->d_view_off;
+  v.d_obs_x = h->d_obs_x;
+  v.d_obs_keep = h->cleaned ? h->d_obs_keep : nullptr;
+  v.d_lm_stage = h->cleaned ? h->d_lm_stage : nullptr;
+  v.d_pose_view_off = h->d_pose_view_off;
+  v.d_pose_views = h->d_pose_views;
+  v.d_blk_cost = h->d_blk_cost;
+  v.d_blk_info = h->d_blk_info;
+  const int rc_run = ba_separable_run(v, what, rep);
+  if (rc_run) return rc_run;
+  if (what != SFMLOC_BA_STRUCTURE) {  // the host's copy of the pose table follows (sfmloc_sfm_read reads it)
+    SFM_HIP(hipMemcpyAsync(h->h_pose_R.data(), h->d_pose_R, 9 * (size_t)h->n_poses * sizeof(double),
+                           hipMemcpyDeviceToHost, h->s));
+    SFM_HIP(hipMemcpyAsync(h->h_pose_C.data(), h->d_pose_C, 3 * (size_t)h->n_poses * sizeof(double),
+                           hipMemcpyDeviceToHost, h->s));
+    SFM_HIP(hipStreamSynchronize(h->s));
+  }
   return SFMLOC_OK;
 }
 
@@ -745,9 +838,35 @@ int sfmloc_sfm_resect_inliers(const sfmloc_sfm *hh, uint32_t k, uint32_t *idx, u
 int sfmloc_sfm_clean(sfmloc_sfm *hh, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
   SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_clean: null handle");
   Sfm *h = reinterpret_cast<Sfm *>(hh);
-  SFM_CHECK(!h->cleaned, SFMLOC_EINVAL, "sfmloc_sfm_clean: runs once");
   SFM_HIP(hipSetDevice(h->device));
   return sfm_clean_impl(h, residual_px, angle_deg, rm_unstable, counts);
+}
+
+int sfmloc_sfm_adjust(sfmloc_sfm *hh, uint32_t what, sfmloc_ba_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust: null handle");
+  SFM_CHECK(what == 0 || what == SFMLOC_BA_ROTATION || what == SFMLOC_BA_TRANSLATION ||
+                what == (SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION) || what == SFMLOC_BA_STRUCTURE,
+            SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust: what = %u: only the separable commands (-c) are supported: structure alone, or "
+            "rotations / translations alone; nothing with intrinsics, no structure together with a pose part", what);
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  if (what == 0) return SFMLOC_OK;
+  SFM_HIP(hipSetDevice(h->device));
+  try {
+    return sfm_adjust_impl(h, what, rep);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_adjust: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+}
+
+int sfmloc_sfm_read_structure(sfmloc_sfm *hh, double *X) {
+  SFM_CHECK(hh && X, SFMLOC_EINVAL, "sfmloc_sfm_read_structure: null argument");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_HIP(hipSetDevice(h->device));
+  if (h->n_lm) SFM_HIP(hipMemcpy(X, h->d_lm_X, 3 * (size_t)h->n_lm * sizeof(double), hipMemcpyDeviceToHost));
+  return SFMLOC_OK;
 }
 
 int sfmloc_sfm_read(sfmloc_sfm *hh, uint8_t *pose_valid, double *pose_R, double *pose_C, uint8_t *obs_keep,

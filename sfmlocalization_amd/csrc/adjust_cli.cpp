@@ -1,4 +1,4 @@
-// OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) without -c as a C++ host program over the C ABI (plain g++):
+// OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) as a C++ host program over the C ABI (plain g++):
 //
 //   OpenMVG_BA <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [--device=0]
 //
@@ -8,7 +8,14 @@
 // unstable poses with -r=1; :245-260) and the result is written to sfm_data_out (which may be sfm_data itself: the
 // merge loop calls it in place).  Both files are what Python's json.dump writes for the document: views, intrinsics,
 // root_path and key order as in the input, extrinsics in ascending pose id, control_points [] (Save without
-// CONTROL_POINTS).  -c (the Ceres bundle adjustment, :158-240) is not supported yet: refused, nothing written.
+// CONTROL_POINTS).
+//
+// -c=item,item,... (:158-244): after the re-resection and sfm_data_b4bd.json every item runs in order -- s adjusts the
+// structure alone, r / t / rt the rotations / translations / both alone (sfmloc_sfm_adjust), a c in the item cleans
+// afterwards and prints the four counts; an item with none of r t i s adjusts nothing.  With a non-empty -c there is no
+// final cleanup of its own (the reference cleans in the else branch only) and the output holds the adjusted poses and X.
+// The joint commands (s with r or t, anything with i) are not supported yet: every item is checked before anything is
+// opened, one refused item ends the run with status 1 and nothing written.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +39,10 @@ void usage() {
   fprintf(stderr,
           "Execute bundle adjustment for sfm_data.json\n"
           "Usage: OpenMVG_BA [params] sfm_data sfm_data_out\n"
-          "\t-c, --command\n\t\tCommand for order of bundle adjustment (not supported yet: only the default, no BD)\n"
+          "\t-c, --command\n\t\tCommand for order of bundle adjustment (BD) [default=no BD] [options:r = rotation, "
+          "t = translation, s = structure, c = clean]. Usage example: c=r,tc,s means BD with rotation only, then BD with "
+          "translation follow by cleaning, then BD with structure. Not supported yet: i (intrinsic), and s together "
+          "with r or t.\n"
           "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n");
 }
 
@@ -87,6 +97,26 @@ std::string folder_of(const std::string &p) {
   return k == std::string::npos ? std::string() : p.substr(0, k + 1);
 }
 
+// -c split on commas as the reference's getline loop splits it (no item after a trailing comma)
+std::vector<std::string> command_items(const std::string &command) {
+  std::vector<std::string> items;
+  size_t at = 0;
+  while (at < command.size()) {
+    const size_t k = command.find(',', at);
+    if (k == std::string::npos) {
+      items.push_back(command.substr(at));
+      break;
+    }
+    items.push_back(command.substr(at, k - at));
+    at = k + 1;
+  }
+  return items;
+}
+
+bool has(const std::string &item, char c) { return item.find(c) != std::string::npos; }
+
+bool bits_differ(const double *a, const double *b, size_t n) { return memcmp(a, b, n * sizeof(double)) != 0; }
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -119,11 +149,15 @@ int main(int argc, char **argv) {
     usage();
     return 1;
   }
-  if (!command.empty()) {
-    fprintf(stderr, "OpenMVG_BA: -c=%s: the bundle adjustment command (-c) is not supported yet; nothing was written\n",
-            command.c_str());
-    return 1;
-  }
+  const std::vector<std::string> items = command_items(command);
+  for (const std::string &item : items)
+    if (has(item, 'i') || (has(item, 's') && (has(item, 'r') || has(item, 't')))) {
+      fprintf(stderr,
+              "OpenMVG_BA: -c=%s: item \"%s\" is not supported yet (-c adjusts the structure alone, or rotations / "
+              "translations alone; no intrinsics); nothing was written\n",
+              command.c_str(), item.c_str());
+      return 1;
+    }
   const std::string in = pos[0], out_path = pos[1];
   printf("Start bundle adjustment over sfm_data.json.\n");
   printf("Reading sfm_data.json file : %s\n", in.c_str());
@@ -174,19 +208,52 @@ int main(int argc, char **argv) {
     sfmloc_sfm_destroy(h);
     return 1;
   }
-  uint64_t counts[4];
-  rc = sfmloc_sfm_clean(h, kResidualPx, kAngleDeg, rm_unstable != 0, counts);
-  std::vector<uint8_t> obs_keep(d.obs_view.size()), lm_keep(d.lm_id.size());
-  if (rc == 0) rc = sfmloc_sfm_read(h, valid.data(), nullptr, nullptr, obs_keep.data(), lm_keep.data());
+  bool cleaned = false;
+  auto clean = [&]() {
+    uint64_t counts[4];
+    const int rcc = sfmloc_sfm_clean(h, kResidualPx, kAngleDeg, rm_unstable != 0, counts);
+    if (rcc) return rcc;
+    cleaned = true;
+    printf("Number of points before cleanup : %llu\n", (unsigned long long)counts[0]);
+    printf("Number of points residual error : %llu\n", (unsigned long long)counts[1]);
+    printf("Number of points angle error : %llu\n", (unsigned long long)counts[2]);
+    printf("Number of points after cleanup : %llu\n", (unsigned long long)counts[3]);
+    return 0;
+  };
+  for (size_t k = 0; k < items.size() && rc == 0; ++k) {
+    const std::string &item = items[k];
+    const bool rot = has(item, 'r'), trn = has(item, 't'), stru = has(item, 's');
+    printf("\nBundle adjustment over %s%s%s\n", rot ? "rotations, " : "", trn ? "translations, " : "",
+           stru ? "structure, " : "");
+    fflush(stdout);
+    rc = sfmloc_sfm_adjust(h, (rot ? SFMLOC_BA_ROTATION : 0u) | (trn ? SFMLOC_BA_TRANSLATION : 0u) |
+                                  (stru ? SFMLOC_BA_STRUCTURE : 0u), nullptr);
+    if (rc == 0 && has(item, 'c')) rc = clean();
+  }
+  if (rc == 0 && items.empty()) rc = clean();
+  std::vector<uint8_t> obs_keep(d.obs_view.size(), 1), lm_keep(d.lm_id.size(), 1);
+  std::vector<double> X;
+  if (rc == 0 && !items.empty()) {  // a pose or a landmark the adjustment moved is written from the arrays
+    std::vector<double> R2(R.size()), C2(C.size());
+    X.resize(d.lm_X.size());
+    rc = sfmloc_sfm_read(h, nullptr, R2.data(), C2.data(), nullptr, nullptr);
+    if (rc == 0 && !X.empty()) rc = sfmloc_sfm_read_structure(h, X.data());
+    if (rc == 0) {
+      for (uint32_t p = 0; p < desc.n_poses; ++p)
+        if (bits_differ(&R2[9 * (size_t)p], &R[9 * (size_t)p], 9) || bits_differ(&C2[3 * (size_t)p], &C[3 * (size_t)p], 3))
+          replaced[p] = 1;
+      R.swap(R2);
+      C.swap(C2);
+    }
+  }
+  if (rc == 0)
+    rc = sfmloc_sfm_read(h, valid.data(), nullptr, nullptr, cleaned ? obs_keep.data() : nullptr,
+                         cleaned ? lm_keep.data() : nullptr);
   sfmloc_sfm_destroy(h);
   if (rc) {
     fprintf(stderr, "OpenMVG_BA: %s\n", sfmloc_last_error());
     return 1;
   }
-  printf("Number of points before cleanup : %llu\n", (unsigned long long)counts[0]);
-  printf("Number of points residual error : %llu\n", (unsigned long long)counts[1]);
-  printf("Number of points angle error : %llu\n", (unsigned long long)counts[2]);
-  printf("Number of points after cleanup : %llu\n", (unsigned long long)counts[3]);
   Value outd = d.root;
   set_key(&outd, "extrinsics", extrinsics(d, valid, R, C, replaced));
   Value *st = outd.get("structure");
@@ -195,6 +262,11 @@ int main(int argc, char **argv) {
     for (size_t l = 0; l < st->a.size(); ++l) {
       if (!lm_keep[l]) continue;
       Value e = std::move(st->a[l]);
+      if (!X.empty() && bits_differ(&X[3 * l], &d.lm_X[3 * l], 3)) {
+        Value xs = Value::make_arr();
+        for (int j = 0; j < 3; ++j) xs.a.push_back(Value::make_float(X[3 * l + j]));
+        set_key(e.get("value"), "X", xs);
+      }
       Value *obs = e.get("value")->get("observations");
       Value ko = Value::make_arr();
       for (size_t j = 0; j < obs->a.size(); ++j)

@@ -1,0 +1,529 @@
+// The separable commands of OpenMVG_BA -c on a device-resident sfm_data (sfmloc_sfm_adjust): structure alone, or the
+// poses alone.  The semantics are stated in include/sfmloc.h ("blocks" .. "order"); every block -- a landmark's X, or a
+// pose's rotation / translation / both -- is a Levenberg-Marquardt problem of its own and all of its iterations run
+// inside one launch.
+//
+//   k_ba_structure   kBaGroup = 8 lanes per landmark (eight landmarks per wave) stride over the landmark's CSR range;
+//                    the 3x3 normal matrix (6 values), the gradient (3) and the cost (1) go through a three-level
+//                    in-wave butterfly, after which every lane of the group holds the same bits and solves the same
+//                    damped system by Cholesky.
+//   k_ba_motion      one wave per pose strides over the view-sorted lists of the pose's views (ascending view index) and
+//                    gathers the landmarks; 21 + 6 + 1 doubles go through a six-level butterfly; 6x6 Cholesky for rt,
+//                    3x3 for r or t.  The rotation steps in the tangent space at the current R.
+//
+// f64, unfused (the library's -ffp-contract=off).  No LDS, no atomics: a block's sums depend on its own observations'
+// order only, so two runs give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "sfmloc_internal.h"
+
+namespace sfmloc {
+namespace {
+
+constexpr int kBaGroup = 8;        // lanes per landmark
+constexpr int kBaMaxSteps = 500;   // steps tried per block
+constexpr double kBaFtol = 1e-14;  // sfmloc.h "stopping"
+constexpr double kHuberA = 16.0;   // HuberLoss(Square(4.0))
+constexpr uint32_t kInfoEntered = 1u << 29, kInfoMoved = 1u << 30, kInfoCap = 1u << 31;
+
+// one observation at camera coordinates Xc: the weighted residual r (2), the weighted d r / d Xc (2 x 3, rows J0 J1)
+// and rho / 2 (sfmloc.h "residual", "loss"; first-order reweighting: both times sqrt(rho'))
+__device__ __forceinline__ double ba_observation(const double *__restrict__ K, bool radial, const double Xc[3],
+                                                  double ox, double oy, double r[2], double J0[3], double J1[3]) {
+  const double f = K[0];
+  const double iz = 1.0 / Xc[2];
+  const double p0 = Xc[0] / Xc[2], p1 = Xc[1] / Xc[2];
+  double rc = 1.0, drc = 0.0;
+  if (radial) {
+    const double r2 = p0 * p0 + p1 * p1;
+    const double r4 = r2 * r2, r6 = r4 * r2;
+    rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
+    drc = (K[3] + 2.0 * K[4] * r2) + 3.0 * K[5] * r4;
+  }
+  r[0] = (f * (p0 * rc) + K[1]) - ox;
+  r[1] = (f * (p1 * rc) + K[2]) - oy;
+  // d q / d p of q = p rc(|p|^2), then d p / d Xc = [[iz, 0, -p0 iz], [0, iz, -p1 iz]]
+  const double q00 = rc + 2.0 * drc * p0 * p0, q01 = 2.0 * drc * p0 * p1, q11 = rc + 2.0 * drc * p1 * p1;
+  J0[0] = f * q00 * iz;
+  J0[1] = f * q01 * iz;
+  J0[2] = -f * (q00 * p0 + q01 * p1) * iz;
+  J1[0] = f * q01 * iz;
+  J1[1] = f * q11 * iz;
+  J1[2] = -f * (q01 * p0 + q11 * p1) * iz;
+  const double s = r[0] * r[0] + r[1] * r[1];
+  if (s > kHuberA * kHuberA) {
+    const double sq = sqrt(s);
+    const double w = sqrt(kHuberA / sq);
+    r[0] *= w;
+    r[1] *= w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      J0[k] *= w;
+      J1[k] *= w;
+    }
+    return 0.5 * (2.0 * kHuberA * sq - kHuberA * kHuberA);
+  }
+  return 0.5 * s;
+}
+
+// the sum over the W lanes of a group (W = 8: a landmark's lanes, W = 64: the wave) as a butterfly: the same tree on
+// every run, and every lane of the group ends with the same bits (a + b and b + a round alike)
+template <int W>
+__device__ __forceinline__ double ba_group_sum(double v) {
+#pragma unroll
+  for (int m = W / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// (A + lam D) d = -g by Cholesky, D = diag(A) clamped to [1e-6, 1e32]; A symmetric, full storage.  Returns false when a
+// pivot is not positive or the step is not finite.  *model = -(g.d + d.A d / 2), the decrease the quadratic model promises.
+template <int N>
+__device__ __forceinline__ bool ba_solve(const double (&A)[N][N], const double (&g)[N], double lam, double (&d)[N],
+                                         double *model) {
+  double L[N][N];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      double s = A[i][j];
+      if (i == j) {
+        const double dd = fmin(fmax(A[i][i], 1e-6), 1e32);
+        s += lam * dd;
+      }
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+      if (i == j) {
+        ok = ok && (s > 0.0);
+        L[i][i] = sqrt(s);
+      } else {
+        L[i][j] = s / L[j][j];
+      }
+    }
+  }
+  double y[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    double s = -g[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= L[i][k] * y[k];
+    y[i] = s / L[i][i];
+  }
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = i + 1; k < N; ++k) s -= L[k][i] * d[k];
+    d[i] = s / L[i][i];
+  }
+  double gd = 0.0, dAd = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    gd += g[i] * d[i];
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) s += A[i][j] * d[j];
+    dAd += d[i] * s;
+    ok = ok && isfinite(d[i]);
+  }
+  *model = -(gd + 0.5 * dAd);
+  return ok && (*model > 0.0);
+}
+
+struct BaLm {
+  double lam = 1e-4, nu = 2.0;
+  // after a trial: true = stop.  accepted: the caller has taken the trial point.
+  __device__ __forceinline__ bool accepted(double c, double cn, double model) {
+    const double q = (c - cn) / model;
+    const double e = 2.0 * q - 1.0;
+    lam = fmax(lam * fmax(1.0 / 3.0, 1.0 - e * e * e), 1e-32);
+    nu = 2.0;
+    return (c - cn) <= kBaFtol * c;
+  }
+  __device__ __forceinline__ bool rejected(double c, double model) {
+    if (isfinite(model) && model <= kBaFtol * c) return true;
+    lam *= nu;
+    nu *= 2.0;
+    return !(lam < 1e32);
+  }
+};
+
+struct BaDev {
+  uint32_t n_views, n_poses, n_lm;
+  const uint32_t *view_intr, *view_pose, *intr_type;
+  const double *intr;
+  double *pose_R, *pose_C, *pose_t, *lm_X;
+  const uint64_t *obs_off;
+  const uint32_t *obs_view, *obs_lm, *vlist, *view_off;
+  const double *obs_x;
+  const uint8_t *obs_keep, *lm_stage;
+  const uint32_t *pose_view_off, *pose_views;
+  double *blk_cost;
+  uint32_t *blk_info;
+};
+
+// t = -R C of every pose (sfmloc.h "blocks")
+__global__ __launch_bounds__(256) void k_ba_pose_t(uint32_t n_poses, const double *__restrict__ R,
+                                                   const double *__restrict__ C, double *__restrict__ t) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_poses) return;
+  const double *r = R + 9 * (size_t)p, *c = C + 3 * (size_t)p;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[3 * (size_t)p + i] = -((r[3 * i] * c[0] + r[3 * i + 1] * c[1]) + r[3 * i + 2] * c[2]);
+}
+
+// ---- structure -----------------------------------------------------------------------------------------------------
+
+// the group's sums at X over the landmark's entering observations [a, b): A (3 x 3), g (3), cost; *n = how many entered
+__device__ __forceinline__ void ba_structure_eval(const BaDev &v, uint64_t a, uint64_t b, int sub, const double X[3],
+                                                  double (&A)[3][3], double (&g)[3], double *cost, uint32_t *n) {
+  double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  uint32_t cnt = 0;
+  for (uint64_t o = a + sub; o < b; o += kBaGroup) {
+    if (v.obs_keep && !v.obs_keep[o]) continue;
+    const uint32_t vw = v.obs_view[o];
+    const uint32_t pi = v.view_pose[vw], ii = v.view_intr[vw];
+    const double *R = v.pose_R + 9 * (size_t)pi, *t = v.pose_t + 3 * (size_t)pi;
+    double Xc[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) Xc[i] = ((R[3 * i] * X[0] + R[3 * i + 1] * X[1]) + R[3 * i + 2] * X[2]) + t[i];
+    double r[2], J0[3], J1[3];
+    acc[9] += ba_observation(v.intr + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
+                             J1);
+    double j0[3], j1[3];  // d r / d X = (d r / d Xc) R
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      j0[k] = (J0[0] * R[k] + J0[1] * R[3 + k]) + J0[2] * R[6 + k];
+      j1[k] = (J1[0] * R[k] + J1[1] * R[3 + k]) + J1[2] * R[6 + k];
+    }
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = i; j < 3; ++j) acc[q++] += j0[i] * j0[j] + j1[i] * j1[j];
+      acc[6 + i] += j0[i] * r[0] + j1[i] * r[1];
+    }
+    ++cnt;
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) acc[k] = ba_group_sum<kBaGroup>(acc[k]);
+  if (n) {
+#pragma unroll
+    for (int m = kBaGroup / 2; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+    *n = cnt;
+  }
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = i; j < 3; ++j) {
+      A[i][j] = acc[q];
+      A[j][i] = acc[q++];
+    }
+    g[i] = acc[6 + i];
+  }
+  *cost = acc[9];
+}
+
+__global__ __launch_bounds__(256) void k_ba_structure(BaDev v) {
+  const uint32_t l = (blockIdx.x * 256 + threadIdx.x) / kBaGroup;
+  const int sub = threadIdx.x & (kBaGroup - 1);
+  if (l >= v.n_lm) return;  // (the whole group leaves: its lanes share l)
+  uint32_t info = 0;
+  double c0 = 0.0, c = 0.0;
+  if (!v.lm_stage || v.lm_stage[l] == 3) {
+    const uint64_t a = v.obs_off[l], b = v.obs_off[l + 1];
+    double X[3] = {v.lm_X[3 * (size_t)l], v.lm_X[3 * (size_t)l + 1], v.lm_X[3 * (size_t)l + 2]};
+    double A[3][3], g[3];
+    uint32_t n = 0;
+    ba_structure_eval(v, a, b, sub, X, A, g, &c, &n);
+    c0 = c;
+    if (n) {
+      info = kInfoEntered;
+      BaLm lm;
+      uint32_t steps = 0;
+      bool stop = false, moved = false;
+      while (!stop && steps < (uint32_t)kBaMaxSteps) {
+        ++steps;
+        double d[3], model;
+        bool ok = ba_solve<3>(A, g, lm.lam, d, &model);
+        double Xn[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
+        double An[3][3], gn[3], cn = 0.0;
+        if (ok) {
+          ba_structure_eval(v, a, b, sub, Xn, An, gn, &cn, nullptr);
+          ok = isfinite(cn) && cn < c && (c - cn) / model > 1e-3;
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) ok = ok && isfinite(An[i][j]);
+        }
+        if (ok) {
+          stop = lm.accepted(c, cn, model);
+          c = cn;
+          moved = true;
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+            X[i] = Xn[i];
+            g[i] = gn[i];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) A[i][j] = An[i][j];
+          }
+        } else {
+          stop = lm.rejected(c, model);
+        }
+      }
+      info |= steps | (moved ? kInfoMoved : 0u) | (stop ? 0u : kInfoCap);
+      if (moved && sub == 0) {
+        v.lm_X[3 * (size_t)l] = X[0];
+        v.lm_X[3 * (size_t)l + 1] = X[1];
+        v.lm_X[3 * (size_t)l + 2] = X[2];
+      }
+    }
+  }
+  if (sub == 0) {
+    v.blk_cost[2 * (size_t)l] = c0;
+    v.blk_cost[2 * (size_t)l + 1] = c;
+    v.blk_info[l] = info;
+  }
+}
+
+// ---- motion ----------------------------------------------------------------------------------------------------------
+
+// the wave's sums at (R, t) over the entering observations of pose p: A (6 x 6 over [rotation, translation]), g, cost
+__device__ __forceinline__ void ba_motion_eval(const BaDev &v, uint32_t p, int lane, const double R[9], const double t[3],
+                                               double (&A)[6][6], double (&g)[6], double *cost, uint32_t *n) {
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+  uint32_t cnt = 0;
+  for (uint32_t vi = v.pose_view_off[p]; vi < v.pose_view_off[p + 1]; ++vi) {
+    const uint32_t vw = v.pose_views[vi];
+    const uint32_t ii = v.view_intr[vw];
+    const double *K = v.intr + 6 * (size_t)ii;
+    const bool radial = v.intr_type[ii] == 3;
+    const uint32_t b0 = v.view_off[vw], nv = v.view_off[vw + 1] - b0;
+    for (uint32_t k = lane; k < nv; k += 64) {
+      const uint32_t o = v.vlist[b0 + k], l = v.obs_lm[o];
+      if (v.obs_keep && (!v.obs_keep[o] || v.lm_stage[l] != 3)) continue;
+      const double *X = v.lm_X + 3 * (size_t)l;
+      double Y[3], Xc[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        Y[i] = (R[3 * i] * X[0] + R[3 * i + 1] * X[1]) + R[3 * i + 2] * X[2];
+        Xc[i] = Y[i] + t[i];
+      }
+      double r[2], J0[3], J1[3];
+      acc[27] += ba_observation(K, radial, Xc, v.obs_x[2 * (size_t)o], v.obs_x[2 * (size_t)o + 1], r, J0, J1);
+      // d Xc / d w = -[Y]x for R <- exp([w]x) R, d Xc / d t = I
+      const double j0[6] = {J0[2] * Y[1] - J0[1] * Y[2], J0[0] * Y[2] - J0[2] * Y[0], J0[1] * Y[0] - J0[0] * Y[1],
+                            J0[0],                       J0[1],                       J0[2]};
+      const double j1[6] = {J1[2] * Y[1] - J1[1] * Y[2], J1[0] * Y[2] - J1[2] * Y[0], J1[1] * Y[0] - J1[0] * Y[1],
+                            J1[0],                       J1[1],                       J1[2]};
+      int q = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) acc[q++] += j0[i] * j0[j] + j1[i] * j1[j];
+        acc[21 + i] += j0[i] * r[0] + j1[i] * r[1];
+      }
+      ++cnt;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = ba_group_sum<64>(acc[k]);
+  if (n) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+    *n = cnt;
+  }
+  int q = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = i; j < 6; ++j) {
+      A[i][j] = acc[q];
+      A[j][i] = acc[q++];
+    }
+    g[i] = acc[21 + i];
+  }
+  *cost = acc[27];
+}
+
+// Rn = exp([w]x) R
+__device__ __forceinline__ void ba_rotate(const double w[3], const double R[9], double Rn[9]) {
+  const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  const double th = sqrt(th2);
+  const bool small = th < 1e-4;
+  const double a = small ? 1.0 - th2 / 6.0 : sin(th) / th;
+  const double b = small ? 0.5 - th2 / 24.0 : (1.0 - cos(th)) / th2;
+  // E = I + a K + b K^2, K = [w]x, K^2 = w w^T - th2 I
+  double E[9];
+  E[0] = 1.0 + b * (w[0] * w[0] - th2);
+  E[4] = 1.0 + b * (w[1] * w[1] - th2);
+  E[8] = 1.0 + b * (w[2] * w[2] - th2);
+  E[1] = b * (w[0] * w[1]) - a * w[2];
+  E[3] = b * (w[0] * w[1]) + a * w[2];
+  E[2] = b * (w[0] * w[2]) + a * w[1];
+  E[6] = b * (w[0] * w[2]) - a * w[1];
+  E[5] = b * (w[1] * w[2]) - a * w[0];
+  E[7] = b * (w[1] * w[2]) + a * w[0];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j]) + E[3 * i + 2] * R[6 + j];
+}
+
+// N free parameters starting at row kOff of [rotation (3), translation (3)]: (3, 0) = r, (3, 3) = t, (6, 0) = rt
+template <int N, int kOff>
+__global__ __launch_bounds__(256) void k_ba_motion(BaDev v) {
+  const uint32_t p = (blockIdx.x * 256 + threadIdx.x) / 64;
+  const int lane = threadIdx.x & 63;
+  if (p >= v.n_poses) return;  // (the whole wave leaves)
+  constexpr bool kRot = kOff == 0, kTrn = (N + kOff) == 6;
+  double R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = v.pose_R[9 * (size_t)p + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) t[i] = v.pose_t[3 * (size_t)p + i];
+  double A6[6][6], g6[6], c = 0.0;
+  uint32_t n = 0, info = 0;
+  ba_motion_eval(v, p, lane, R, t, A6, g6, &c, &n);
+  const double c0 = c;
+  if (n) {
+    info = kInfoEntered;
+    BaLm lm;
+    uint32_t steps = 0;
+    bool stop = false, moved = false;
+    while (!stop && steps < (uint32_t)kBaMaxSteps) {
+      ++steps;
+      double A[N][N], g[N], d[N], model;
+#pragma unroll
+      for (int i = 0; i < N; ++i) {
+        g[i] = g6[kOff + i];
+#pragma unroll
+        for (int j = 0; j < N; ++j) A[i][j] = A6[kOff + i][kOff + j];
+      }
+      bool ok = ba_solve<N>(A, g, lm.lam, d, &model);
+      double Rn[9], tn[3], An[6][6], gn[6], cn = 0.0;
+      if (ok) {
+        if (kRot) {
+          const double w[3] = {d[0], d[1], d[2]};
+          ba_rotate(w, R, Rn);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 9; ++i) Rn[i] = R[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tn[i] = kTrn ? t[i] + d[N - 3 + i] : t[i];
+        ba_motion_eval(v, p, lane, Rn, tn, An, gn, &cn, nullptr);
+        ok = isfinite(cn) && cn < c && (c - cn) / model > 1e-3;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+          for (int j = 0; j < 6; ++j) ok = ok && isfinite(An[i][j]);
+      }
+      if (ok) {
+        stop = lm.accepted(c, cn, model);
+        c = cn;
+        moved = true;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = tn[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          g6[i] = gn[i];
+#pragma unroll
+          for (int j = 0; j < 6; ++j) A6[i][j] = An[i][j];
+        }
+      } else {
+        stop = lm.rejected(c, model);
+      }
+    }
+    info |= steps | (moved ? kInfoMoved : 0u) | (stop ? 0u : kInfoCap);
+    if (moved && lane == 0) {
+      if (kRot) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) v.pose_R[9 * (size_t)p + i] = R[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)  // C = -R^T t
+        v.pose_C[3 * (size_t)p + i] = -((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
+    }
+  }
+  if (lane == 0) {
+    v.blk_cost[2 * (size_t)p] = c0;
+    v.blk_cost[2 * (size_t)p + 1] = c;
+    v.blk_info[p] = info;
+  }
+}
+
+}  // namespace
+
+int ba_separable_run(const SfmBaView &s, uint32_t what, sfmloc_ba_report *rep) {
+  BaDev v;
+  v.n_views = s.n_views;
+  v.n_poses = s.n_poses;
+  v.n_lm = s.n_lm;
+  v.view_intr = s.d_view_intr;
+  v.view_pose = s.d_view_pose;
+  v.intr_type = s.d_intr_type;
+  v.intr = s.d_intr;
+  v.pose_R = s.d_pose_R;
+  v.pose_C = s.d_pose_C;
+  v.pose_t = s.d_pose_t;
+  v.lm_X = s.d_lm_X;
+  v.obs_off = s.d_obs_off;
+  v.obs_view = s.d_obs_view;
+  v.obs_lm = s.d_obs_lm;
+  v.vlist = s.d_vlist;
+  v.view_off = s.d_view_off;
+  v.obs_x = s.d_obs_x;
+  v.obs_keep = s.d_obs_keep;
+  v.lm_stage = s.d_lm_stage;
+  v.pose_view_off = s.d_pose_view_off;
+  v.pose_views = s.d_pose_views;
+  v.blk_cost = s.d_blk_cost;
+  v.blk_info = s.d_blk_info;
+  const bool structure = what == SFMLOC_BA_STRUCTURE;
+  const uint32_t nb = structure ? s.n_lm : s.n_poses;
+  sfmloc_ba_report r{};
+  if (nb) {
+    hipLaunchKernelGGL(k_ba_pose_t, dim3((s.n_poses + 255) / 256), dim3(256), 0, s.s, s.n_poses,
+                       (const double *)s.d_pose_R, (const double *)s.d_pose_C, s.d_pose_t);
+    SFM_HIP(hipGetLastError());
+    if (structure) {
+      const uint32_t per = 256 / kBaGroup;
+      hipLaunchKernelGGL(k_ba_structure, dim3((nb + per - 1) / per), dim3(256), 0, s.s, v);
+    } else {
+      const dim3 grid((nb + 3) / 4);
+      if (what == SFMLOC_BA_ROTATION) hipLaunchKernelGGL((k_ba_motion<3, 0>), grid, dim3(256), 0, s.s, v);
+      else if (what == SFMLOC_BA_TRANSLATION) hipLaunchKernelGGL((k_ba_motion<3, 3>), grid, dim3(256), 0, s.s, v);
+      else hipLaunchKernelGGL((k_ba_motion<6, 0>), grid, dim3(256), 0, s.s, v);
+    }
+    SFM_HIP(hipGetLastError());
+    std::vector<double> cost(2 * (size_t)nb);
+    std::vector<uint32_t> info(nb);
+    SFM_HIP(hipMemcpyAsync(cost.data(), s.d_blk_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost, s.s));
+    SFM_HIP(hipMemcpyAsync(info.data(), s.d_blk_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s.s));
+    SFM_HIP(hipStreamSynchronize(s.s));
+    for (uint32_t b = 0; b < nb; ++b) {  // (ascending block index: the totals' order is fixed)
+      if (!(info[b] & kInfoEntered)) continue;
+      ++r.n_blocks;
+      r.cost_initial += cost[2 * (size_t)b];
+      r.cost_final += cost[2 * (size_t)b + 1];
+      r.n_at_cap += (info[b] & kInfoCap) != 0;
+      r.n_unchanged += (info[b] & kInfoMoved) == 0;
+      const uint32_t steps = info[b] & 0xFFFFu;
+      if (steps > r.max_iterations) r.max_iterations = steps;
+    }
+  }
+  if (rep) *rep = r;
+  return SFMLOC_OK;
+}
+
+}  // namespace sfmloc

@@ -487,4 +487,23 @@ struct SfmColorView {
 };
 void sfm_color_view(const sfmloc_sfm *h, SfmColorView *out);
 
+// ba_separable.hip: what the separable adjustment (sfmloc_sfm_adjust) works on -- adjust.hip's resident sfm_data.
+// obs_keep / lm_stage are null before the first cleanup (every observation enters); pose_view_off / pose_views list
+// every pose's views in ascending view index (CSR by pose).  pose_t [n_poses*3] is scratch.
+struct SfmBaView {
+  hipStream_t s;
+  uint32_t n_views, n_poses, n_lm;
+  const uint32_t *d_view_intr, *d_view_pose, *d_intr_type;
+  const double *d_intr;
+  double *d_pose_R, *d_pose_C, *d_pose_t, *d_lm_X;
+  const uint64_t *d_obs_off;
+  const uint32_t *d_obs_view, *d_obs_lm, *d_vlist, *d_view_off;
+  const double *d_obs_x;
+  const uint8_t *d_obs_keep, *d_lm_stage;
+  const uint32_t *d_pose_view_off, *d_pose_views;
+  double *d_blk_cost;   // [2 * n_blocks] a block's cost before and after
+  uint32_t *d_blk_info;  // [n_blocks] steps tried | entered << 29 | moved << 30 | at the cap << 31
+};
+int ba_separable_run(const SfmBaView &v, uint32_t what, sfmloc_ba_report *rep);
+
 }  // namespace sfmloc
