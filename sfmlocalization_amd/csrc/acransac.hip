@@ -875,8 +875,11 @@ constexpr int kK3WideViews = 256;  // view lists the wide form takes (its result
 // (W = waves per view: 16 for a query alone on the GPU -- a view's latency --, 4 when the GPU is shared: a workgroup of 16
 // waves at 124 VGPRs is a compute unit's whole register file, i.e. it starts only on a compute unit nothing else runs on
 // and nothing else runs beside it; at 8 the Hamming scans of the other queries keep three of their waves per SIMD, at
-// 4 all of them.  Measured at 20 queries in flight: 16 / 8 / 4 waves 3 259 / 3 413 / 3 460 queries/s -- K3 costs the
-// others 13 us per query instead of 36.)
+// 4 all of them.  Measured at 20 queries in flight in round 3, when the popcount scan filled the chip: 16 / 8 / 4 waves
+// 3 259 / 3 413 / 3 460 queries/s -- K3 costs the others 13 us per query instead of 36.  With the matrix-core scan, on four
+// hardware queues, the order is the opposite: 4 / 8 / 16 waves 3 695 / 3 924 / 4 115 queries/s, and the wide form 4 114
+// (profiles/k3k5_candidates.txt): the chip has room and a query's time is the length of its chain.  A shared GPU now takes
+// the wide form, launch_fmatrix_filter; W serves the lists it does not take and gang sessions.)
 // (M = putative matches per view the form holds: 512 -- at most 8 residuals per lane in the register sort, 124 VGPRs --
 // or, round 3, 1 024 for the views of a query that nearly duplicates a map frame: 16 per lane, more registers, launched
 // only while such queries come, Map::k3_big_credit; they took the block-wide LDS form before, 0.4 ms per frame)
@@ -1398,9 +1401,12 @@ __device__ __forceinline__ int p3p_round_batch(int n, int batch) {
 // random sequence: t iterations after the switch the next improvement is within the next m with probability m/(t+m).
 // Evaluating 3t (at least 64) instead of a full batch finds it three times out of four and otherwise just advances; the
 // acceptance rule is replayed exactly for any partition into rounds, so only the cost changes: ~2x fewer hypotheses
-// evaluated for ~1.3x the rounds (+8 % queries per second at 12 in flight; the policy's constants hardly matter,
-// profiles/r02_p3p_adaptive_policy.txt).  A query alone on the GPU keeps full batches: rounds are what its latency is
-// made of.
+// evaluated for ~1.3x the rounds (+8 % queries per second at 12 in flight in round 2, on the popcount scan; the policy's
+// constants hardly matter, profiles/r02_p3p_adaptive_policy.txt).  A query alone on the GPU keeps full batches: rounds
+// are what its latency is made of.  With the matrix-core scan (20 in flight, four hardware queues, K3 wide; queries/s,
+// profiles/k3k5_candidates.txt): this rule with the hypotheses prepared ahead 4 043, full batches 4 277, full batches
+// prepared ahead 3 646, this rule WITHOUT preparing ahead 4 451 -- the shared GPU's rule now (make_p3p_args); floor 32 /
+// 128, slope 2 / 6 and 12 rounds queued instead of 9 all within 1 % of it.
 __device__ __forceinline__ int p3p_next_batch_limit(const P3pArgs &A, int identity, long iter, long switch_iter, int n) {
   // (more than 512 correspondences: a model that passes the NFA filter costs a block-wide sort, and right after the
   // switch nearly every hypothesis passes -- its reference is the FIRST meaningful model -- while everything behind the
@@ -2555,6 +2561,7 @@ __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int
   int n_prep = 0;
   if (A.prep_ahead && !done) {
     n_prep = next_limit < kP3pBatchMax ? next_limit : kP3pBatchMax;
+    if (n_prep > kP3pLaterBatch) n_prep = kP3pLaterBatch;  // (full batches: the limit is "none", the launch's size is not)
     n_prep = p3p_round_batch(st.n, n_prep);
     if ((long)n_prep > n_iter - iter_next) n_prep = (int)(n_iter - iter_next);
   }
@@ -2581,7 +2588,7 @@ __device__ __forceinline__ void p3p_replay_impl(const P3pArgs &A, int batch, int
   STAMP_SEL(stamp_round, 2);
   // Prepared ahead.  In a round every workgroup spends its first 8-11 us with ONE lane solving its hypothesis's P3P --
   // a chain of ~2 500 dependent f64 instructions -- while the other 255 lanes wait, and a lone lane costs its SIMD as
-  // many issue cycles as a full wave.  When the GPU is shared (prep_ahead) the workgroup that has just replayed the round
+  // many issue cycles as a full wave.  With prep_ahead (gang sessions; make_p3p_args) the workgroup that has just replayed the round
   // solves the COMING round's hypotheses instead, one per lane (the same scalar code on the same inputs: the same bits):
   // it knows the state they sample from, its 256 lanes take as long as one did, and the coming round's workgroups find
   // their four models in memory (p3p_eval_hypothesis: `have`).  Whatever the coming launch does not cover by these
@@ -3239,21 +3246,34 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
   A.skip_le = kF2MaxM;
   A.fast_min = -1;
   A.merge = MergeMaskedArgs{};
-  // The wide form (one workgroup per iteration of a view's first batch, fmatrix_fast.body.inc) for a query alone on the GPU
-  // with a short view list: its 1 024-match instance takes every view the register forms hold, in one launch.
+  // The wide form (one workgroup per iteration of a view's first batch, fmatrix_fast.body.inc) for a short view list,
+  // whether or not other contexts have work queued: its 1 024-match instance takes every view the register forms hold, in
+  // one launch, K2 included.  (Until the matrix-core scan it was a lone query's form: the popcount scan filled the chip
+  // and K3's registers were the scans'.  Since then the chip is mostly idle under load and a query's time is the length
+  // of its chain, DESIGN.md 4 "Where the time goes after the matrix-core scan".)  Gang sessions keep the plain form.
   // SFMLOC_K3_WIDE = 0 never, 2 always (tests, campaigns).
   static const int env_wide = env_int("SFMLOC_K3_WIDE", 1);
   const int n_uniform = m->params.ransac_round - m->params.ransac_round / 10;
   const int wide_b0 = n_uniform < kF2Batch ? n_uniform : kF2Batch;
   const bool wide = wide_b0 >= 2 && n_sel <= (uint32_t)kK3WideViews &&
-                    (env_wide == 2 || (env_wide == 1 && c->k1_may_slice && c->stream.gang == nullptr));
+                    (env_wide == 2 || (env_wide == 1 && c->stream.gang == nullptr));
+  // (views of 1 025 .. 2 048 matches -- 32 residuals per lane in the register sort, one workgroup per compute unit --
+  // only while the map's queries have had such views lately, Map::k3_huge_credit; SFMLOC_K3_WIDE_2048 = 0 never, 2 always:
+  // k_fmatrix_filter's block-wide sort took 0.6 of a lone 1080p frame's 0.95 ms in this stage)
+  static const int env_2048 = env_int("SFMLOC_K3_WIDE_2048", 1);
+  const bool huge = wide && (env_2048 == 2 || (env_2048 == 1 && m->k3_huge_credit.load(std::memory_order_relaxed) > 0));
   A.spec = nullptr;
   A.spec_arrive = nullptr;
   if (pass.merge_deferred) {  // K2 was left to this stage (launch_merge_ratio_compact)
     pass.merge_deferred = false;
-    if (!wide) {
-      A.merge = pass.merge;  // k_fmatrix_fast runs on every selected view, whatever its size
-    } else {  // (the wide form's workgroups of a view all need the view's lists: K2 as a launch of its own)
+    if (!huge) {
+      // k_fmatrix_fast runs on every selected view, whatever its size; in the wide form every workgroup of a view that
+      // can be the kernel's builds the view's lists for itself (fmatrix_fast.body.inc)
+      A.merge = pass.merge;
+    } else {
+      // (the 2 048-match instance keeps K2 as a launch of its own: its workgroups are one per compute unit, the views of
+      // the frames that bring it have thousands of rows and hundreds of flagged ones, and ~23 workgroups per view each
+      // reading the view's flag words or repeating its merge cost a lone 1080p frame 0.12 ms in this stage)
       int rc = launch_merge_masked_now(c, pass.merge, n_sel);
       if (rc) return rc;
     }
@@ -3262,17 +3282,13 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     if (!c->d_k3_spec) {
       SFM_HIP(hipMalloc((void **)&c->d_k3_spec, (size_t)kK3WideViews * kF2Batch * sizeof(K3Spec)));
       SFM_HIP(hipMalloc((void **)&c->d_k3_arrive, (size_t)kK3WideViews * sizeof(unsigned int)));
-      SFM_HIP(hipMemset(c->d_k3_arrive, 0, (size_t)kK3WideViews * sizeof(unsigned int)));  // (the last arrival clears its slot)
-      SFM_HIP(hipStreamSynchronize(nullptr));  // (null stream: not ordered with the context's stream otherwise)
+      // (the last arrival clears its slot.  On the stream the launch below goes to, so that nothing waits for the device:
+      // every context of a busy map gets here once.  Nothing a gang member has recorded touches the new buffer.)
+      SFM_HIP(hipMemsetAsync(c->d_k3_arrive, 0, (size_t)kK3WideViews * sizeof(unsigned int), c->stream.unordered()));
       c->hbm_bytes += (size_t)kK3WideViews * (kF2Batch * sizeof(K3Spec) + sizeof(unsigned int));
     }
     A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec);
     A.spec_arrive = c->d_k3_arrive;
-    // (views of 1 025 .. 2 048 matches -- 32 residuals per lane in the register sort, one workgroup per compute unit --
-    // only while the map's queries have had such views lately, Map::k3_huge_credit; SFMLOC_K3_WIDE_2048 = 0 never, 2 always:
-    // k_fmatrix_filter's block-wide sort took 0.6 of a lone 1080p frame's 0.95 ms in this stage)
-    static const int env_2048 = env_int("SFMLOC_K3_WIDE_2048", 1);
-    const bool huge = env_2048 == 2 || (env_2048 == 1 && m->k3_huge_credit.load(std::memory_order_relaxed) > 0);
     auto go_wide = [&](auto m_tag) {
       constexpr int MaxM = decltype(m_tag)::value;
       using Sh = F2SharedT<4, MaxM>;
@@ -3290,6 +3306,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     SFM_HIP(hipGetLastError());
     A.skip_le = huge ? 2048 : 1024;
   } else {
+    // (what the wide form does not take: view lists above kK3WideViews, gang sessions, SFMLOC_K3_WIDE = 0)
     // waves per view (F2SharedT): 16 for a query alone on the GPU, 4 when other contexts have work queued
     static const int env_waves = env_int("SFMLOC_K3_WAVES_SHARED", 4);
     static const int env_waves_alone = env_int("SFMLOC_K3_WAVES_ALONE", 16);
@@ -3562,13 +3579,19 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.ws_idx = c->d_p3p_ws_idx;
   A.ws_terms = c->d_p3p_terms;
   A.refine_pose = m->params.refine_pose;
-  // a context that is not alone on the map's GPU (other contexts have work queued, ctx_mark_busy) spends fewer
-  // speculative hypotheses per round; SFMLOC_P3P_ADAPTIVE=0/1 overrides (measurements)
+  // K5's own rule for a shared GPU (Ctx::others_busy: other contexts of the map had work queued when the query began,
+  // ctx_mark_busy; what K1 makes of the same fact is Ctx::k1_may_slice).  Such a context spends fewer speculative
+  // hypotheses per round; SFMLOC_P3P_ADAPTIVE=0/1 overrides (measurements)
+  const bool shared = c->others_busy;
   static const int env_adaptive = env_int("SFMLOC_P3P_ADAPTIVE", -1);
-  A.adaptive_batch = env_adaptive >= 0 ? env_adaptive : (c->k1_may_slice ? 0 : 1);
-  // (SFMLOC_P3P_PREP_AHEAD: 0 never, 1 when the GPU is shared -- the default --, 2 always: comparison runs and tests)
-  static const int env_prep = env_int("SFMLOC_P3P_PREP_AHEAD", 1);
-  A.prep_ahead = env_prep == 2 || (env_prep == 1 && A.adaptive_batch);
+  A.adaptive_batch = env_adaptive >= 0 ? env_adaptive : (shared ? 1 : 0);
+  // The coming round's hypotheses solved by the replaying workgroup ("Prepared ahead", p3p_replay_impl) save issue cycles
+  // and cost the query's chain the 10-20 us the lone workgroup takes over them.  While the popcount scan filled the chip
+  // the cycles were what counted; since the matrix-core scan the chip is mostly idle under load and the chain's length is
+  // what a query's time is made of: only a gang session, whose launches carry up to 32 queries' rounds,
+  // still prepares ahead.  SFMLOC_P3P_PREP_AHEAD: 0 never, 1 whenever the GPU is shared (the default until then), 2 always.
+  static const int env_prep = env_int("SFMLOC_P3P_PREP_AHEAD", -1);
+  A.prep_ahead = env_prep == 2 || (A.adaptive_batch && (env_prep == 1 || (env_prep < 0 && c->stream.gang != nullptr)));
   if (A.uncal) A.prep_ahead = 0;  // (the replay's hand-over solves P3P; k_resect6_prepare is the six-point kernel's)
   static const int env_quarters = env_int("SFMLOC_P3P_ADAPT_QUARTERS", 12);
   static const int env_floor = env_int("SFMLOC_P3P_ADAPT_FLOOR", 64);

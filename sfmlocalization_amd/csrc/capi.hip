@@ -353,7 +353,8 @@ ChainArgs make_chain_args(Ctx *c, const Query *q, const uint32_t *d_sel, uint32_
 // nothing else to fill it with, i.e. when no other context of the map has work queued.
 static void ctx_mark_busy(Ctx *c) {
   Map *m = c->map;
-  c->k1_may_slice = m->busy_ctx.load(std::memory_order_relaxed) - (c->counted_busy ? 1 : 0) <= 0;
+  c->others_busy = m->busy_ctx.load(std::memory_order_relaxed) - (c->counted_busy ? 1 : 0) > 0;
+  c->k1_may_slice = !c->others_busy;
   if (!c->counted_busy) {
     c->counted_busy = true;
     m->busy_ctx.fetch_add(1, std::memory_order_relaxed);
@@ -549,9 +550,7 @@ int ctx_resection_enqueue(Ctx *c, bool first_call) {
   }
   // typically 6-8 rounds end the stage (one per improvement of the model); rounds enqueued past the end return at
   // once but still cost two launches each, so the first call queues 9 and ctx_resection_wait adds more if needed.
-  // 256 hypotheses per later round: as many rounds as with 512 (an improvement of the model comes early in a round or not at
-  // all), 3-5 % more queries per second because fewer speculative hypotheses are evaluated for nothing
-  constexpr int kLaterBatch = 256;
+  constexpr int kLaterBatch = kP3pLaterBatch;  // (sfmloc_internal.h)
   // the first round's size, alone or while the GPU is shared: after the geometric filter the first hypothesis is
   // nearly always the one that switches sampling to its inliers, and everything behind it is thrown away
   constexpr int kFirstBatch = 64;

@@ -136,6 +136,29 @@ struct MergeMaskedArgs {
   const uint16_t *ratio_cnt;
   uint32_t *view_count, *match_i, *match_key;
 };
+// the flag word of block `rel` of a view (rows [off, end), first block blk0, first flag word widx0) without the rows of
+// the block that belong to neighbouring views
+__device__ __forceinline__ unsigned long long merge_view_flag_word(const MergeMaskedArgs &M, uint32_t widx0, uint32_t blk0,
+                                                                   uint32_t rel, uint32_t off, uint32_t end) {
+  unsigned long long w = M.flagmask[widx0 + rel];
+  const uint64_t r_lo = (uint64_t)(blk0 + rel) << 6;
+  if (r_lo < off) w &= ~0ull << (off - r_lo);
+  if (r_lo + 64 > end) w &= (end > r_lo) ? (~0ull >> (r_lo + 64 - end)) : 0ull;
+  return w;
+}
+// How many rows of a view are flagged, by one wave (every lane gets the total): an upper bound of what the merge below
+// accepts -- it looks at flagged rows only --, for the price of the view's flag words alone.
+__device__ __forceinline__ uint32_t merge_flagged_rows_view(const MergeMaskedArgs &M, uint32_t gw, uint32_t lane) {
+  const uint32_t v = M.view_sel ? M.view_sel[gw] : gw;
+  const uint32_t off = M.view_off[v], end = M.view_off[v + 1];
+  const uint32_t blk0 = off >> 6;
+  const uint32_t widx0 = M.view_sel ? M.view_widx0[gw] : blk0;
+  const uint32_t n_blk = (end > off) ? (((end - 1) >> 6) - blk0 + 1) : 0;
+  uint32_t mine = 0;
+  for (uint32_t rel = lane; rel < n_blk; rel += 64) mine += (uint32_t)__popcll(merge_view_flag_word(M, widx0, blk0, rel, off, end));
+  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d, 64);
+  return mine;
+}
 __device__ __forceinline__ void merge_ratio_masked_view(const MergeMaskedArgs &M, uint32_t gw, uint32_t lane) {
   constexpr uint32_t kNoMatch = 0xFFFFFFFFu;  // SFMLOC_NOMATCH
   const uint32_t v = M.view_sel ? M.view_sel[gw] : gw;
@@ -147,13 +170,7 @@ __device__ __forceinline__ void merge_ratio_masked_view(const MergeMaskedArgs &M
   for (uint32_t c0 = 0; c0 < n_blk; c0 += 64) {  // 64 blocks (4096 rows) per pass
     const uint32_t rel = c0 + lane;
     unsigned long long w = 0;
-    if (rel < n_blk) {
-      w = M.flagmask[widx0 + rel];
-      // rows of the block that belong to neighbouring views
-      const uint64_t r_lo = (uint64_t)(blk0 + rel) << 6;
-      if (r_lo < off) w &= ~0ull << (off - r_lo);
-      if (r_lo + 64 > end) w &= (end > r_lo) ? (~0ull >> (r_lo + 64 - end)) : 0ull;
-    }
+    if (rel < n_blk) w = merge_view_flag_word(M, widx0, blk0, rel, off, end);
     // pass 1: count the accepted rows of my block
     uint32_t mine = 0;
     unsigned long long acc_bits = 0;

@@ -9,6 +9,19 @@
   STAMP_F(1);
   const uint32_t v = A.view_sel ? A.view_sel[blockIdx.x] : blockIdx.x;
   if (A.merge.enabled) {  // K2 for this view (chain_device.h), by one wave; the others wait for its lists
+    // The wide form: EVERY workgroup of the view builds the view's lists for itself and reads back what it wrote.  The
+    // merge is one wave's deterministic work on inputs that no workgroup of this launch writes (flag words, partial
+    // results), so the view's workgroups store the same values to the same places of match_i / match_key / view_count,
+    // in whatever order: a workgroup that reads them after its own barrier finds those values whichever store landed
+    // last, and nobody waits for anybody.  So that the ~97 of 100 listed views with nothing in them do not cost a merge
+    // per workgroup, all but the first count the view's flagged rows first: the merge accepts flagged rows only, so
+    // fewer of them than the smallest view this kernel takes proves that the view is not its own (the test below would
+    // send this workgroup away with the same m).  The first workgroup always merges: later stages read view_count.
+    if constexpr (kF2Wide) {
+      if (blockIdx.y > 0 &&
+          merge_flagged_rows_view(A.merge, blockIdx.x, (uint32_t)lane) < (uint32_t)(A.min_putative > 8 ? A.min_putative : 8))
+        return;
+    }
     if (wv == 0) merge_ratio_masked_view(A.merge, blockIdx.x, (uint32_t)lane);
     __syncthreads();
   }

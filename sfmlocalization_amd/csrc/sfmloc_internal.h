@@ -59,6 +59,10 @@ constexpr uint32_t kBlockRows = 64;
 constexpr int kK1CounterSlots = 64;  // Ctx::d_k1_counters
 constexpr int kP3pMaxN = 4096;     // 2D-3D correspondences the P3P LDS sort holds
 constexpr int kP3pBatchMax = 512;  // hypotheses evaluated per round
+// hypotheses a launch of a query's rounds carries after the first (capi.hip ctx_resection_enqueue): as many rounds as with
+// 512 (an improvement of the model comes early in a round or not at all), 3-5 % more queries per second because fewer
+// speculative hypotheses are evaluated for nothing
+constexpr int kP3pLaterBatch = 256;
 // result slots of a round: one per hypothesis (at most kP3pBatchMax), or (wide launches, at most kP3pSlots / 4 = 128
 // hypotheses -- their nominal size since round 4) four, one per model.  A slot's inlier list is kP3pMaxN ints: 8 MB per
 // context (16 MB while wide rounds could be 256 hypotheses: ADVICE r03)
@@ -300,7 +304,8 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   std::vector<uint32_t> last_blocks;  // host copy of the block list (empty = all)
   bool last_blocks_on_device = false; // the list was built by k_blocks_from_views: fetch it when a reader needs it
   bool counted_busy = false;          // this context is counted in Map::busy_ctx
-  bool k1_may_slice = true;           // no other context had work queued when this query began
+  bool others_busy = false;           // other contexts of the map had work queued when this query began (ctx_mark_busy)
+  bool k1_may_slice = true;           // K1's use of it: a short scan may be cut into query slices (= !others_busy)
   bool p3p_init_fused = false;        // k_match_set_finish has run K5's initialisation for the query in hand
   struct Query *last_query = nullptr;  // query of the last putative call
   struct Query *in_flight = nullptr;   // query of a begun, not yet ended, localisation
