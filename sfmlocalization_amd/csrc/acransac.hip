@@ -495,7 +495,6 @@ __device__ __forceinline__ int next_pow2(int n) {
 // ---------------------------------------------------------------------------------------------------
 // K3: F-matrix AC-RANSAC, one workgroup per selected view
 // ---------------------------------------------------------------------------------------------------
-constexpr int kFMaxM = 2048;  // putative matches per view the LDS sort holds
 constexpr int kFPre = 64;     // hypotheses solved speculatively per batch while sampling is still uniform
 
 // (a write-through store: see "A round's results go from the workgroup that computed them ..." at K5)
@@ -868,9 +867,7 @@ __global__ __launch_bounds__(kThreads) void k_fmatrix_large(FFilterArgsPacked P,
 //     evaluate the (up to 3) models side by side.
 // Results are bit-identical to k_fmatrix_filter (same samples, same arithmetic per value, same tie rules).
 // ---------------------------------------------------------------------------------------------------
-constexpr int kF2MaxM = 512;   // putative matches per view (one wave sorts one model's residuals)
-constexpr int kF2Batch = 32;   // uniform iterations solved speculatively per batch
-constexpr int kK3WideViews = 256;  // view lists the wide form takes (its result slots: 2 MB per context)
+// (kF2MaxM = 512 putative matches per view, kF2Batch = 32 uniform iterations per batch, kK3WideViews: forms.h)
 
 // (W = waves per view: 16 for a query alone on the GPU -- a view's latency --, 4 when the GPU is shared: a workgroup of 16
 // waves at 124 VGPRs is a compute unit's whole register file, i.e. it starts only on a compute unit nothing else runs on
@@ -882,8 +879,8 @@ constexpr int kK3WideViews = 256;  // view lists the wide form takes (its result
 // the wide form, launch_fmatrix_filter; W serves the lists it does not take and gang sessions.)
 // (M = putative matches per view the form holds: 512 -- at most 8 residuals per lane in the register sort, 124 VGPRs --
 // or, round 3, 1 024 for the views of a query that nearly duplicates a map frame: 16 per lane, more registers, launched
-// only while such queries come, Map::k3_big_credit; they took the block-wide LDS form before, 0.4 ms per frame)
-template <int W, int MaxM = 512>
+// only while such queries come, forms.h; they took the block-wide LDS form before, 0.4 ms per frame)
+template <int W, int MaxM = kF2MaxM>
 struct F2SharedT {
   static constexpr int kF2MaxM = MaxM;
   uint32_t idx[W][kF2MaxM];  // sorted match indices of the model each wave evaluated last
@@ -933,7 +930,7 @@ __device__ void bitonic_sort_wave(uint64_t *kw, uint32_t *iw, int P) {
   }
 }
 
-template <int W, int MaxM = 512, bool Wide = false>
+template <int W, int MaxM = kF2MaxM, bool Wide = false>
 struct FmatrixFastBody {
   static constexpr int kGangThreads = W * 64;
   static __device__ __forceinline__ void run(FFilterArgsPacked packed) {
@@ -944,7 +941,7 @@ struct FmatrixFastBody {
 #include "fmatrix_fast.body.inc"
   }
 };
-template <int W, int MaxM = 512, bool Wide = false>
+template <int W, int MaxM = kF2MaxM, bool Wide = false>
 __global__ __launch_bounds__(W * 64) void k_fmatrix_fast(FFilterArgsPacked packed) {
   const FFilterArgs A = ffilter_expand(packed);
   constexpr int kF2Waves = W, kF2Threads = W * 64, kF2MaxM = MaxM;
@@ -988,7 +985,7 @@ struct EmitMinBody {
     if (threadIdx.x == 0) {  // the counts the reference prints (localization.cpp:416,458)
       if (put_count[v] >= min_putative) atomicAdd(&view_stats[0], 1u);
       if (ng > 0) atomicAdd(&view_stats[1], 1u);
-      if (put_count[v] > 512u) atomicMax(&view_stats[2], put_count[v]);  // (the host's hint for K3's launch forms)
+      if (put_count[v] > (uint32_t)kF2MaxM) atomicMax(&view_stats[2], put_count[v]);  // (the host's hint for K3's launch forms)
     }
     if (ng == 0) return;
     const uint32_t off = view_off[v];
@@ -1391,7 +1388,6 @@ constexpr int kP3pWaveSeg = kP3pMaxN / 4;  // elements one wave sorts when the f
 // frame with thousands of landmarks gets there): the residual sort of a hypothesis runs in a global-memory segment
 // instead of LDS, and a round evaluates only the first kP3pLargeBatch hypotheses (that many segments exist).  Both
 // kernels derive the round's size and the inlier-list stride from the same device-side n.
-constexpr int kP3pLargeBatch = 64;
 __device__ __forceinline__ int p3p_round_batch(int n, int batch) {
   return (n > kP3pMaxN && batch > kP3pLargeBatch) ? kP3pLargeBatch : batch;
 }
@@ -1439,11 +1435,10 @@ struct P3pShared {
 // four waves of the Hamming scan (68 VGPRs) that other queries in flight are running, for the 30-90 us a round lasts,
 // and a round is 64-256 workgroups.  That, not K5's instructions (a tenth of the scan's) nor its LDS, is what K5 cost
 // the other queries.  The small form is the same code with the large cases compiled out.  The host queues a query's
-// rounds before it knows the set's size (Map::p3p_small_credit: the map's last queries were all small); a small round
+// rounds before it knows the set's size (forms.h: the map's last queries were all small); a small round
 // that finds a larger set returns at once, state untouched -- as if it had not been launched --, and
 // ctx_resection_wait queues that query's rounds again in the full form.  The partition into rounds and the form of a
 // launch change nothing in the result.
-constexpr int kP3pSmallN = 512;
 
 // A round's results go from the workgroup that computed them to the one that replays the round, which may sit on
 // another XCD (another L2): they are written through (agent-scope stores), so that delivering them needs no L2
@@ -3202,6 +3197,20 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
   return SFMLOC_OK;
 }
 
+// one launch of k_fmatrix_fast<W, MaxM, kWide>: a workgroup per view, or (wide) per view and iteration of its first batch
+template <int W, int MaxM, bool kWide>
+static hipError_t launch_fmatrix_fast(Ctx *c, const FFilterArgs &A, int wide_b0) {
+  using Sh = F2SharedT<W, MaxM>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<W, MaxM, kWide>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh));
+  if (attr != hipSuccess) return attr;
+  FFilterArgsPacked P;
+  if (k3_pack(c, A, &P) != SFMLOC_OK) return hipErrorOutOfMemory;
+  sfm_launch<FmatrixFastBody<W, MaxM, kWide>>(c, k_fmatrix_fast<W, MaxM, kWide>, dim3(A.n_sel, (unsigned)wide_b0),
+                                              dim3(W * 64), (uint32_t)sizeof(Sh), P);
+  return hipSuccess;
+}
+
 int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, int min_putative) {
   Map *m = c->map;
   if (n_sel == 0) return SFMLOC_OK;
@@ -3241,44 +3250,28 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     A.large_count = c->fl_count;
     A.large_list = c->fl_list;
   }
-  // views with <= kF2MaxM putative matches take the wave-parallel kernel, the rest (if any: the second launch
-  // returns at once for the others) the block-wide one
-  A.skip_le = kF2MaxM;
+  // which texts of k_fmatrix_fast run in front of k_fmatrix_filter, and on what (forms.h)
+  K3In in;
+  in.n_sel = n_sel;
+  in.ransac_round = m->params.ransac_round;
+  in.gang = c->stream.gang != nullptr;
+  in.alone = c->k1_may_slice;
+  in.merge_deferred = pass.merge_deferred;
+  in.huge_credit = m->credits.k3_huge.load(std::memory_order_relaxed);
+  in.big_credit = m->credits.k3_big.load(std::memory_order_relaxed);
+  const K3Plan P = plan_k3(in, knobs());
+  A.skip_le = P.skip_le;
   A.fast_min = -1;
   A.merge = MergeMaskedArgs{};
-  // The wide form (one workgroup per iteration of a view's first batch, fmatrix_fast.body.inc) for a short view list,
-  // whether or not other contexts have work queued: its 1 024-match instance takes every view the register forms hold, in
-  // one launch, K2 included.  (Until the matrix-core scan it was a lone query's form: the popcount scan filled the chip
-  // and K3's registers were the scans'.  Since then the chip is mostly idle under load and a query's time is the length
-  // of its chain, DESIGN.md 4 "Where the time goes after the matrix-core scan".)  Gang sessions keep the plain form.
-  // SFMLOC_K3_WIDE = 0 never, 2 always (tests, campaigns).
-  static const int env_wide = env_int("SFMLOC_K3_WIDE", 1);
-  const int n_uniform = m->params.ransac_round - m->params.ransac_round / 10;
-  const int wide_b0 = n_uniform < kF2Batch ? n_uniform : kF2Batch;
-  const bool wide = wide_b0 >= 2 && n_sel <= (uint32_t)kK3WideViews &&
-                    (env_wide == 2 || (env_wide == 1 && c->stream.gang == nullptr));
-  // (views of 1 025 .. 2 048 matches -- 32 residuals per lane in the register sort, one workgroup per compute unit --
-  // only while the map's queries have had such views lately, Map::k3_huge_credit; SFMLOC_K3_WIDE_2048 = 0 never, 2 always:
-  // k_fmatrix_filter's block-wide sort took 0.6 of a lone 1080p frame's 0.95 ms in this stage)
-  static const int env_2048 = env_int("SFMLOC_K3_WIDE_2048", 1);
-  const bool huge = wide && (env_2048 == 2 || (env_2048 == 1 && m->k3_huge_credit.load(std::memory_order_relaxed) > 0));
   A.spec = nullptr;
   A.spec_arrive = nullptr;
-  if (pass.merge_deferred) {  // K2 was left to this stage (launch_merge_ratio_compact)
-    pass.merge_deferred = false;
-    if (!huge) {
-      // k_fmatrix_fast runs on every selected view, whatever its size; in the wide form every workgroup of a view that
-      // can be the kernel's builds the view's lists for itself (fmatrix_fast.body.inc)
-      A.merge = pass.merge;
-    } else {
-      // (the 2 048-match instance keeps K2 as a launch of its own: its workgroups are one per compute unit, the views of
-      // the frames that bring it have thousands of rows and hundreds of flagged ones, and ~23 workgroups per view each
-      // reading the view's flag words or repeating its merge cost a lone 1080p frame 0.12 ms in this stage)
-      int rc = launch_merge_masked_now(c, pass.merge, n_sel);
-      if (rc) return rc;
-    }
+  pass.merge_deferred = false;
+  if (P.k2 == K3Merge::kFolded) A.merge = pass.merge;
+  if (P.k2 == K3Merge::kInFront) {
+    int rc = launch_merge_masked_now(c, pass.merge, n_sel);
+    if (rc) return rc;
   }
-  if (wide) {
+  if (P.wide) {
     if (!c->d_k3_spec) {
       SFM_HIP(hipMalloc((void **)&c->d_k3_spec, (size_t)kK3WideViews * kF2Batch * sizeof(K3Spec)));
       SFM_HIP(hipMalloc((void **)&c->d_k3_arrive, (size_t)kK3WideViews * sizeof(unsigned int)));
@@ -3289,65 +3282,24 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     }
     A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec);
     A.spec_arrive = c->d_k3_arrive;
-    auto go_wide = [&](auto m_tag) {
-      constexpr int MaxM = decltype(m_tag)::value;
-      using Sh = F2SharedT<4, MaxM>;
-      static const hipError_t attrw = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<4, MaxM, true>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh));
-      if (attrw != hipSuccess) return attrw;
-      FFilterArgsPacked P;
-      if (k3_pack(c, A, &P) != SFMLOC_OK) return hipErrorOutOfMemory;
-      sfm_launch<FmatrixFastBody<4, MaxM, true>>(c, k_fmatrix_fast<4, MaxM, true>, dim3(n_sel, (unsigned)wide_b0), dim3(256),
-                                                 (uint32_t)sizeof(Sh), P);
-      return hipSuccess;
-    };
-    const hipError_t ew = huge ? go_wide(std::integral_constant<int, 2048>{}) : go_wide(std::integral_constant<int, 1024>{});
-    SFM_HIP(ew);
+    const hipError_t e = P.max_m == kF2HugeM ? launch_fmatrix_fast<4, kF2HugeM, true>(c, A, P.wide_b0)
+                                             : launch_fmatrix_fast<4, kF2BigM, true>(c, A, P.wide_b0);
+    SFM_HIP(e);
     SFM_HIP(hipGetLastError());
-    A.skip_le = huge ? 2048 : 1024;
   } else {
-    // (what the wide form does not take: view lists above kK3WideViews, gang sessions, SFMLOC_K3_WIDE = 0)
-    // waves per view (F2SharedT): 16 for a query alone on the GPU, 4 when other contexts have work queued
-    static const int env_waves = env_int("SFMLOC_K3_WAVES_SHARED", 4);
-    static const int env_waves_alone = env_int("SFMLOC_K3_WAVES_ALONE", 16);
-    const int waves = c->k1_may_slice ? env_waves_alone : env_waves;
-    auto go = [&](auto w_tag) {
-      constexpr int W = decltype(w_tag)::value;
-      static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<W>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(F2SharedT<W>));
-      if (attr2 != hipSuccess) return attr2;
-      FFilterArgsPacked P;
-      if (k3_pack(c, A, &P) != SFMLOC_OK) return hipErrorOutOfMemory;
-      sfm_launch<FmatrixFastBody<W>>(c, k_fmatrix_fast<W>, dim3(n_sel), dim3(W * 64), (uint32_t)sizeof(F2SharedT<W>), P);
-      return hipSuccess;
-    };
-    const hipError_t e2 = waves == 16 ? go(std::integral_constant<int, 16>{})
-                          : waves == 4 ? go(std::integral_constant<int, 4>{}) : go(std::integral_constant<int, 8>{});
-    SFM_HIP(e2);
+    const hipError_t e = P.waves == 16  ? launch_fmatrix_fast<16, kF2MaxM, false>(c, A, 1)
+                         : P.waves == 4 ? launch_fmatrix_fast<4, kF2MaxM, false>(c, A, 1)
+                                        : launch_fmatrix_fast<8, kF2MaxM, false>(c, A, 1);
+    SFM_HIP(e);
     SFM_HIP(hipGetLastError());
-    // views with 513 .. 1 024 putative matches (a query that nearly duplicates a map frame): the same kernel with 16
-    // residuals per lane -- while the map's queries have had such views lately (Map::k3_big_credit, set from the largest
-    // view of every finished query: a launch whose 100 workgroups all leave at once still costs a launch)
-    static const int env_big = env_int("SFMLOC_K3_BIG", 1);
-    if (env_big == 2 || (env_big == 1 && m->k3_big_credit.load(std::memory_order_relaxed) > 0)) {
+    if (P.big) {
       FFilterArgs B = A;
       B.merge.enabled = 0;  // (the lists exist: the launch above built them)
       B.fast_min = kF2MaxM;
-      auto go_big = [&](auto w_tag) {
-        constexpr int W = decltype(w_tag)::value;
-        using Sh = F2SharedT<W, 1024>;
-        static const hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<W, 1024>),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh));
-        if (attr3 != hipSuccess) return attr3;
-        FFilterArgsPacked P;
-        if (k3_pack(c, B, &P) != SFMLOC_OK) return hipErrorOutOfMemory;
-        sfm_launch<FmatrixFastBody<W, 1024>>(c, k_fmatrix_fast<W, 1024>, dim3(n_sel), dim3(W * 64), (uint32_t)sizeof(Sh), P);
-        return hipSuccess;
-      };
-      const hipError_t e3 = c->k1_may_slice ? go_big(std::integral_constant<int, 8>{}) : go_big(std::integral_constant<int, 4>{});
-      SFM_HIP(e3);
+      const hipError_t eb = P.big_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, false>(c, B, 1)
+                                             : launch_fmatrix_fast<4, kF2BigM, false>(c, B, 1);
+      SFM_HIP(eb);
       SFM_HIP(hipGetLastError());
-      A.skip_le = 1024;
     }
   }
   const size_t lds = sizeof(FShared);
@@ -3473,7 +3425,7 @@ int launch_export_packed(Ctx *c, void *dst_dev, uint32_t n_queries, uint32_t bud
   return SFMLOC_OK;
 }
 
-static P3pArgs make_p3p_args(Ctx *c);
+static P3pArgs make_p3p_args(Ctx *c, const K5In &in);
 
 // what a query's 2D-3D selection starts from when no k_query_reset ran for it (sfmloc_merge_begin, the staged API)
 struct SelectResetBody {
@@ -3517,7 +3469,7 @@ int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, cons
   sfm_launch<MatchSetFinishBody>(c, k_match_set_finish, dim3(1), dim3(1024), 0, parts, n_parts, part_bytes, cap,
                                  c->d_best64, c->d_winner, q->n, q->d_kpt, c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark,
                                  c->d_pt2d, c->d_pt3d, (c->map->intrinsic_type == 3 && !c->p3p_uncal) ? 1 : 0, c->map->focal, c->map->ppx,
-                                 c->map->ppy, c->map->k1, c->map->k2, c->map->k3, L, make_p3p_args(c));
+                                 c->map->ppy, c->map->k1, c->map->k2, c->map->k3, L, make_p3p_args(c, k5_in(c)));
   SFM_HIP(hipGetLastError());
   c->p3p_init_fused = true;  // launch_p3p_init is then a no-op for this query
   return SFMLOC_OK;
@@ -3530,7 +3482,7 @@ int launch_match_set(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_s
                                   c->cand_cap);
 }
 
-static P3pArgs make_p3p_args(Ctx *c) {
+static P3pArgs make_p3p_args(Ctx *c, const K5In &in) {
   Map *m = c->map;
   P3pArgs A;
   A.state = c->d_p3p_state;
@@ -3579,24 +3531,11 @@ static P3pArgs make_p3p_args(Ctx *c) {
   A.ws_idx = c->d_p3p_ws_idx;
   A.ws_terms = c->d_p3p_terms;
   A.refine_pose = m->params.refine_pose;
-  // K5's own rule for a shared GPU (Ctx::others_busy: other contexts of the map had work queued when the query began,
-  // ctx_mark_busy; what K1 makes of the same fact is Ctx::k1_may_slice).  Such a context spends fewer speculative
-  // hypotheses per round; SFMLOC_P3P_ADAPTIVE=0/1 overrides (measurements)
-  const bool shared = c->others_busy;
-  static const int env_adaptive = env_int("SFMLOC_P3P_ADAPTIVE", -1);
-  A.adaptive_batch = env_adaptive >= 0 ? env_adaptive : (shared ? 1 : 0);
-  // The coming round's hypotheses solved by the replaying workgroup ("Prepared ahead", p3p_replay_impl) save issue cycles
-  // and cost the query's chain the 10-20 us the lone workgroup takes over them.  While the popcount scan filled the chip
-  // the cycles were what counted; since the matrix-core scan the chip is mostly idle under load and the chain's length is
-  // what a query's time is made of: only a gang session, whose launches carry up to 32 queries' rounds,
-  // still prepares ahead.  SFMLOC_P3P_PREP_AHEAD: 0 never, 1 whenever the GPU is shared (the default until then), 2 always.
-  static const int env_prep = env_int("SFMLOC_P3P_PREP_AHEAD", -1);
-  A.prep_ahead = env_prep == 2 || (A.adaptive_batch && (env_prep == 1 || (env_prep < 0 && c->stream.gang != nullptr)));
-  if (A.uncal) A.prep_ahead = 0;  // (the replay's hand-over solves P3P; k_resect6_prepare is the six-point kernel's)
-  static const int env_quarters = env_int("SFMLOC_P3P_ADAPT_QUARTERS", 12);
-  static const int env_floor = env_int("SFMLOC_P3P_ADAPT_FLOOR", 64);
-  A.adapt_quarters = env_quarters;
-  A.adapt_floor = env_floor;
+  const K5QueryPlan Q = plan_k5_query(in, knobs());  // the shared-GPU round policy (forms.h)
+  A.adaptive_batch = Q.adaptive_batch;
+  A.prep_ahead = Q.prep_ahead;
+  A.adapt_quarters = Q.adapt_quarters;
+  A.adapt_floor = Q.adapt_floor;
   A.seed = m->params.seed;
   A.stream = c->p3p_stream;  // the AC-RANSAC sampling stream: 0 on the query path, the view id in adjust.hip
   return A;
@@ -3607,71 +3546,47 @@ int launch_p3p_init(Ctx *c) {
     c->p3p_init_fused = false;
     return SFMLOC_OK;
   }
-  P3pArgs A = make_p3p_args(c);
+  P3pArgs A = make_p3p_args(c, k5_in(c));
   sfm_launch<P3pInitBody>(c, k_p3p_init, dim3(1), dim3(kThreads), 0, A);
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }
 
 int launch_p3p_round(Ctx *c, int batch) {
-  P3pArgs A = make_p3p_args(c);
+  const K5In in = k5_in(c);
+  P3pArgs A = make_p3p_args(c, in);
   const size_t lds = sizeof(P3pShared);
+  constexpr size_t lds_small = std::max(offsetof(P3pShared, idx) + 4 * kP3pSmallN * sizeof(uint32_t), sizeof(P3pReplayShared));
   static_assert(sizeof(P3pReplayShared) <= sizeof(P3pShared), "the replay reuses the round's LDS");
   // (a function-local static with an initialiser: set once, safely, whichever host thread gets here first)
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p3p_round),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
   SFM_HIP(attr);
-  if (A.uncal) {
+  const K5RoundPlan P = plan_k5_round(in, batch, knobs());
+  if (P.six_point) {
     // an uncalibrated query (never in a gang session: capi.hip refuses): its round's models first, sixteen hypotheses
-    // per wave, then the round in the plain shape -- one model per hypothesis, nothing for a wide launch to spread
+    // per wave, then the round
     static const hipError_t attr6 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resect6_round),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
     SFM_HIP(attr6);
     hipStream_t s = (hipStream_t)c->stream;
-    hipLaunchKernelGGL(k_resect6_prepare, dim3((batch + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, A, batch);
-    if (c->p3p_small) {
-      constexpr size_t lds_small = std::max(offsetof(P3pShared, idx) + 4 * kP3pSmallN * sizeof(uint32_t), sizeof(P3pReplayShared));
-      hipLaunchKernelGGL(k_resect6_round_small, dim3(batch), dim3(kThreads), (uint32_t)lds_small, s, A, batch, 0);
-    } else {
-      hipLaunchKernelGGL(k_resect6_round, dim3(batch), dim3(kThreads), (uint32_t)lds, s, A, batch, 0);
-    }
-    SFM_HIP(hipGetLastError());
-    return SFMLOC_OK;
-  }
-  // from 513 features on a query may have that many correspondences: four workgroups per hypothesis, one model each
-  // (p3p_eval_hypothesis); the result slots then are 4 b + m, of which there are kP3pSlots
-  // -- and only while queries of this map HAVE had that many lately (Map::p3p_wide_credit, refreshed by every finished
-  // query that did): the idle workgroups of a wide launch cost a small query ~15 us and 3 % of the throughput, and the
-  // host cannot know the match set's size when it queues the rounds.  Either launch shape gives the same bits.
-  // (SFMLOC_P3P_WIDE_ALONE=1: also for any query alone on the GPU -- measured and not the default: with 4 x 256 workgroups
-  // the chip is NOT idle, four waves per SIMD share its f64 pipe and a headline round takes 47 us instead of 29,
-  // profiles/r04_k5_forms.txt)
-  static const int env_wide_alone = env_int("SFMLOC_P3P_WIDE_ALONE", 0);
-  const int wide = ((c->p3p_query_n > 512 && c->map->p3p_wide_credit.load(std::memory_order_relaxed) > 0) ||
-                    (env_wide_alone == 2 || (env_wide_alone == 1 && c->k1_may_slice && !c->stream.gang))) ? 1 : 0;
-  if (wide && batch > kP3pSlots / 4) batch = kP3pSlots / 4;
-  // (wide rounds are nominally 128 hypotheses, not 256: on large sets most rounds evaluate 16 .. 64 -- p3p_next_batch_limit --
-  // and every workgroup of the 4 x batch launched has to be dispatched with its LDS and registers even to find that it has
-  // nothing to do: image-in frames 0.86 -> 0.71 ms of PnP alone, 1 229 -> 1 302 images/s, profiles/r04_k5_forms.txt)
-  constexpr int kP3pWideBatch = 128;
-  if (wide && batch > kP3pWideBatch) batch = kP3pWideBatch;
-  // (a wide launch sized for fewer hypotheses than the nominal batch, each workgroup taking several in turn, was tried:
-  // the empty workgroups of a 4 x 256 launch cost ~20-50 us per round on large sets, but the loop cost the small form's
-  // text 10 % of a headline round; not kept, profiles/r04_k5_forms.txt)
-  const int wide_groups = batch;
-  // the small form (above, at P3pShared) when this query's rounds were queued on that prediction and nothing has refuted it
-  if (!wide && c->p3p_small) {
-    constexpr size_t lds_small = std::max(offsetof(P3pShared, idx) + 4 * kP3pSmallN * sizeof(uint32_t), sizeof(P3pReplayShared));
-    sfm_launch<P3pRoundSmallBody>(c, k_p3p_round_small, dim3(batch), dim3(kThreads), (uint32_t)lds_small, A, batch, 0);
-  } else {
-    sfm_launch<P3pRoundBody>(c, k_p3p_round, dim3(wide ? 4 * wide_groups : batch), dim3(kThreads), (uint32_t)lds, A, batch, wide);
+    hipLaunchKernelGGL(k_resect6_prepare, dim3((P.batch + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, A, P.batch);
+    if (P.form == K5Form::kSmall)
+      hipLaunchKernelGGL(k_resect6_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, s, A, P.batch, 0);
+    else
+      hipLaunchKernelGGL(k_resect6_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, s, A, P.batch, 0);
+  } else if (P.form == K5Form::kSmall) {
+    sfm_launch<P3pRoundSmallBody>(c, k_p3p_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, A, P.batch, 0);
+  } else {  // either launch shape gives the same bits
+    sfm_launch<P3pRoundBody>(c, k_p3p_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, A, P.batch,
+                             P.form == K5Form::kWide ? 1 : 0);
   }
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }
 
 int launch_p3p_finish(Ctx *c) {
-  P3pArgs A = make_p3p_args(c);
+  P3pArgs A = make_p3p_args(c, k5_in(c));
   sfm_launch<P3pFinishBody>(c, k_p3p_finish, dim3(1), dim3(kThreads), 0, A);
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;

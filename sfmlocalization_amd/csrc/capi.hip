@@ -541,28 +541,12 @@ int ctx_resection_enqueue(Ctx *c, bool first_call) {
   if (first_call) {
     rc = launch_p3p_init(c);
     if (rc) return rc;
-    // the form of this query's rounds (acransac.hip, at P3pShared: the small form holds sets of at most 512
-    // correspondences in a fraction of the registers): a prediction from the map's last queries -- or a certainty, when
-    // the query has no more features than that --; ctx_resection_wait corrects it if the set turns out larger
-    static const int env_small = env_int("SFMLOC_P3P_SMALL", 1);
-    c->p3p_small = env_small == 2 || (env_small == 1 && (c->p3p_query_n <= 512 ||
-                                                         c->map->p3p_small_credit.load(std::memory_order_relaxed) >= 8));
   }
-  // typically 6-8 rounds end the stage (one per improvement of the model); rounds enqueued past the end return at
-  // once but still cost two launches each, so the first call queues 9 and ctx_resection_wait adds more if needed.
-  constexpr int kLaterBatch = kP3pLaterBatch;  // (sfmloc_internal.h)
-  // the first round's size, alone or while the GPU is shared: after the geometric filter the first hypothesis is
-  // nearly always the one that switches sampling to its inliers, and everything behind it is thrown away
-  constexpr int kFirstBatch = 64;
-  static const int env_rounds = [] {  // tuning hook: rounds queued by the first call
-    const int v = env_int("SFMLOC_P3P_ROUNDS", 9);
-    return (v >= 1 && v <= 64) ? v : 9;
-  }();
-  // (in a gang session a surplus round costs a fraction of a launch, and a member that needs more than were queued gets
-  // them alone on the gang's stream: three more up front)
-  const int rounds = first_call ? (c->stream.gang ? std::max(env_rounds, 12) : env_rounds) : 6;
+  const K5QueryPlan P = plan_k5_query(k5_in(c), knobs());  // forms.h
+  if (first_call) c->p3p_small = P.small;  // (ctx_resection_wait corrects it if the set turns out larger)
+  const int rounds = first_call ? P.first_rounds : P.later_rounds;
   for (int r = 0; r < rounds && rc == SFMLOC_OK; ++r)
-    rc = launch_p3p_round(c, (first_call && r == 0) ? kFirstBatch : kLaterBatch);
+    rc = launch_p3p_round(c, (first_call && r == 0) ? kP3pFirstBatch : kP3pLaterBatch);
   if (rc == SFMLOC_OK) rc = launch_p3p_finish(c);  // pose + inlier pairs once the state says "done"; a no-op before
   return rc;
 }
@@ -587,7 +571,7 @@ int ctx_p3p_reserve(Ctx *c, uint32_t n) {
   uint32_t cap = c->p3p_cap;
   while (cap < n) cap <<= 1;
   // hypothesis inlier lists: kP3pBatchMax lists of kP3pMaxN, or (more correspondences) kP3pLargeBatch lists of cap
-  const size_t large_batch = 64;  // acransac.hip kP3pLargeBatch
+  const size_t large_batch = kP3pLargeBatch;
   const size_t hyp = std::max<size_t>((size_t)kP3pSlots * kP3pMaxN, large_batch * cap);
   const size_t bytes[12] = {(size_t)cap * 2 * sizeof(double),      ((size_t)cap + 1) * sizeof(float),
                             ((size_t)cap + 1) * sizeof(float),     (size_t)cap * sizeof(int32_t),
@@ -655,15 +639,10 @@ int ctx_resection_wait(Ctx *c) {
     c->stream.dirty = false;
     if (h->state.done) {
       SFM_CHECK((h->pose.status & 8) == 0, SFMLOC_EHIP, "six-point resection: a round found no prepared model (internal)");
-      // what the next queries' rounds look like (launch_p3p_round): this one's number of correspondences
-      if (h->state.n > 512) c->map->p3p_wide_credit.store(64, std::memory_order_relaxed);
-      else if (c->map->p3p_wide_credit.load(std::memory_order_relaxed) > 0) c->map->p3p_wide_credit.fetch_sub(1, std::memory_order_relaxed);
-      if (h->state.n > 512) c->map->p3p_small_credit.store(0, std::memory_order_relaxed);
-      else if (c->map->p3p_small_credit.load(std::memory_order_relaxed) < 64) c->map->p3p_small_credit.fetch_add(1, std::memory_order_relaxed);
+      c->map->credits.note_p3p_set(h->state.n);  // what the next queries' rounds look like
       return SFMLOC_OK;
     }
-    // (the small rounds of a set that turned out larger than the form holds all returned at once: the full form now)
-    if (c->p3p_small && h->state.n > 512) c->p3p_small = false;
+    if (k5_small_refuted(h->state.n)) c->p3p_small = false;
     int rc;
     {
       EventScope ev(c, SFMLOC_K_P3P);
@@ -734,14 +713,7 @@ int ctx_localize_end(Ctx *c, sfmloc_pose *out, uint32_t *pair_qfeat, uint32_t *p
   out->status |= h->status;
   out->n_putative_views = (int32_t)h->view_stats[0];
   out->n_geometric_views = (int32_t)h->view_stats[1];
-  // the form of the next queries' K3 (launch_geometric_filter): was this one's largest view one for the 1 024-match
-  // register form?  (A query with a still larger view gains nothing from it: the launches run one after the other, and
-  // the block-wide form of its largest view is what it waits for either way -- measured on the dense lab frames, +0.2 ms.)
-  if (h->view_stats[2] > 1024u && h->view_stats[2] <= 2048u) c->map->k3_huge_credit.store(64, std::memory_order_relaxed);
-  else if (c->map->k3_huge_credit.load(std::memory_order_relaxed) > 0) c->map->k3_huge_credit.fetch_sub(1, std::memory_order_relaxed);
-  if (h->view_stats[2] > 1024u) c->map->k3_big_credit.store(0, std::memory_order_relaxed);
-  else if (h->view_stats[2] > 512u) c->map->k3_big_credit.store(64, std::memory_order_relaxed);
-  else if (c->map->k3_big_credit.load(std::memory_order_relaxed) > 0) c->map->k3_big_credit.fetch_sub(1, std::memory_order_relaxed);
+  c->map->credits.note_k3_largest_view(h->view_stats[2]);  // the form of the next queries' K3
   // (none of these can be reached with data the reference accepts: a view's matches beyond 65 536, an internal
   // inconsistency of the candidate part, more correspondences than the query has features)
   SFM_CHECK((out->status & 1) == 0, SFMLOC_ECAP, "a view has more than 65536 putative matches");

@@ -122,10 +122,10 @@
       case 2: return eval_e(Mp, std::integral_constant<int, 2>{});
       case 4: return eval_e(Mp, std::integral_constant<int, 4>{});
       default:
-        if constexpr (kF2MaxM > 1024) {
+        if constexpr (kF2MaxM > kF2BigM) {
           if ((P >> 6) > 16) return eval_e(Mp, std::integral_constant<int, 32>{});
         }
-        if constexpr (kF2MaxM > 512) {
+        if constexpr (kF2MaxM > sfmloc::kF2MaxM) {  // (this instance's size against the base instance's, forms.h)
           if ((P >> 6) > 8) return eval_e(Mp, std::integral_constant<int, 16>{});
         }
         return eval_e(Mp, std::integral_constant<int, 8>{});

@@ -78,7 +78,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_hamming_top2(
 // percent) are redone exactly by k_hamming_rows.  Results are bit-identical to k_hamming_top2 + K2; per pair
 // the loop issues 2*NW + 1 VALU instructions instead of 35.
 // ---------------------------------------------------------------------------------------------------
-constexpr uint32_t kScreenHead = 64;  // measured: 64 and 128 within 1 %, 256+ slower (profiles/r01_k1_screen_sweep.txt)
 
 template <int WAVES, int NW, int kScreenBatch>
 struct HammingScreenBody {
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(8 * 64) void k_hamming_screen_shortlist(
     unsigned long long *__restrict__ flagmask, uint2 *__restrict__ flagged, uint32_t *__restrict__ n_flagged,
     unsigned long long *__restrict__ counters, uint32_t head, uint4 *__restrict__ flagged_desc, uint32_t flagged_desc_cap,
     const uint2 *__restrict__ head_part) {
-  constexpr int WAVES = 8, NW = 10, kScreenBatch = 1;
+  constexpr int WAVES = 8, NW = kScreenNW, kScreenBatch = 1;
 #include "hamming_screen.body.inc"
 }
 
@@ -314,20 +313,6 @@ int launch_hamming_t(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_li
   return SFMLOC_OK;
 }
 
-// tuning hook: SFMLOC_K1_GEOM="R,WAVES,LDS_ROWS" overrides the geometry choice (read once)
-struct K1Geom {
-  int r = 0, waves = 0, lds_rows = 0;
-};
-const K1Geom &k1_override() {
-  static K1Geom g = [] {
-    K1Geom x;
-    const char *e = getenv("SFMLOC_K1_GEOM");
-    if (e) sscanf(e, "%d,%d,%d", &x.r, &x.waves, &x.lds_rows);
-    return x;
-  }();
-  return g;
-}
-
 }  // namespace
 
 int launch_tile_bank(const uint4 *d_rows, uint64_t row0, uint64_t n_rows_chunk, uint4 *d_bank, hipStream_t s) {
@@ -339,126 +324,36 @@ int launch_tile_bank(const uint4 *d_rows, uint64_t row0, uint64_t n_rows_chunk, 
   return SFMLOC_OK;
 }
 
-static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_work_blocks, bool use_list) {
+static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, const K1Plan &P, uint32_t n_work_blocks,
+                                   bool use_list) {
   Map *m = c->map;
-  constexpr int WAVES = 8;
-  // Prefix length of the lower bound, in dwords.  With 10 of 16 the "some lane still below its threshold" vote
-  // fires for ~3 % of the pairs on the bench data at ratio 0.6 (9 is past the cliff: half the lanes pass);
-  // SFMLOC_K1_SCREEN_NW={8..13} / SFMLOC_K1_SCREEN_HEAD override the two knobs for tuning.
-  static const int nw = [] {
-    const char *e = getenv("SFMLOC_K1_SCREEN_NW");
-    const int v = e ? atoi(e) : 10;
-    return (v >= 8 && v <= 13) ? v : 10;
-  }();
-  static const uint32_t head = [] {
-    const char *e = getenv("SFMLOC_K1_SCREEN_HEAD");
-    const int v = e ? atoi(e) : (int)kScreenHead;
-    return (uint32_t)((v >= 2 && v <= 4 * (int)kScreenHead) ? v : (int)kScreenHead);
-  }();
+  constexpr int WAVES = kScreenWaves, NW = kScreenNW;
   const uint32_t lds_rows = 512;
   const size_t lds_bytes = (size_t)lds_rows * 64;
   if (!pass.cleared) SFM_HIP(hipMemsetAsync(c->d_n_flagged, 0, sizeof(uint32_t), c->stream));
-  // query slices for a short block list: aim at 8 waves per SIMD (3 200 blocks in one slice leave the fullest SIMDs 4
-  // waves and the average 3.1: 0.39 ms; four slices: 0.33 ms although each pays its own exact head), every slice at
-  // least 6 heads long so that screening still pays
-  static const int qsplit_env = [] {
-    const char *e = getenv("SFMLOC_K1_QSPLIT");
-    return e ? atoi(e) : 0;
-  }();
-  // The head is shared: one exact pass over the first `head` query rows (k_hamming_top2) seeds every slice, so a slice
-  // costs no head of its own.  Four slices remain the optimum all the same (profiles/r02_k1_qsplit_sweep.txt: a
-  // shortlisted query takes 0.95 / 0.93 / 0.89 / 1.02 / 1.29 ms with 1 / 2 / 4 / 8 / 16 slices): a workgroup's fixed
-  // costs -- its bank rows, its query slice into LDS, two barriers -- stop amortising below ~500 query rows per slice.
-  // Round 4: HOW MANY slices is chosen for the launch's last generation of workgroups.  A lone query's 3 150 blocks in four
-  // slices are 1 576 workgroups for 768 places (three of the batched form per compute unit): two full generations and 40
-  // stragglers that start when the second ends and run a third of a generation alone -- 48 of the scan's 268 us.  With s
-  // slices a workgroup takes 1 / s of the time and the launch G(s) generations, the last one -- a fraction r of the places
-  // -- about 0.45 + 0.55 r of a full one (fewer waves per SIMD run faster, not proportionally); each slice costs its
-  // workgroups' fixed part (~1 %).  Measured on the headline's lone query, putMatch with 4 / 5 / 7 / 8 / 10 / 14 slices:
-  // 0.323 / 0.301 / 0.291 / 0.300 / 0.296 / 0.294 ms.
-  uint32_t qsplit = 1;
-  if ((uint64_t)n_work_blocks < 32ull * (uint64_t)m->n_cu) {
-    const uint32_t wg_per_slice = (n_work_blocks + WAVES - 1) / WAVES;
-    const bool batched = n_work_blocks < 16u * (uint32_t)m->n_cu;  // (the form chosen below: 68 VGPRs, three per compute unit)
-    const double places = (double)((batched ? 3 : 4) * m->n_cu);
-    double best = 1e30;
-    for (uint32_t s = 1; s <= 8; ++s) {
-      if (s > 1 && (q->n <= head || (q->n - head) / s < 3 * head)) break;  // (a slice keeps at least three heads of query rows)
-      const double g = (double)wg_per_slice * s / places;
-      const double full = floor(g), r = g - full;
-      const double cost = (full + (r > 0.0 ? 0.45 + 0.55 * r : 0.0)) / s * (1.0 + 0.012 * s);
-      if (cost < best) {
-        best = cost;
-        qsplit = s;
-      }
-    }
-  }
-  if (!c->k1_may_slice) qsplit = 1;  // other queries are queued on the GPU: their scans fill it, slices only add work
-  if (qsplit_env >= 1 && qsplit_env <= 16) qsplit = (uint32_t)qsplit_env;
   const uint2 *head_part = nullptr;
-  if (qsplit > 1) {
-    int rc = launch_hamming_t<1, 8>(c, q, n_work_blocks, use_list, 1, 512, head);
+  if (P.shared_head) {
+    int rc = launch_hamming_t<1, 8>(c, q, n_work_blocks, use_list, 1, 512, P.head);
     if (rc) return rc;
     head_part = c->d_part;
   }
-  if (qsplit > 1 && !pass.flagmask_zeroed)
+  if (P.clear_flagmask && !pass.flagmask_zeroed)
     SFM_HIP(hipMemsetAsync(c->d_flagmask, 0, (size_t)n_work_blocks * sizeof(unsigned long long), c->stream));
   pass.flagmask_zeroed = false;  // (this scan writes it)
-#define K1_SCREEN(NW)                                                                                              \
-  case NW:                                                                                                        \
-    sfm_launch<HammingScreenBody<WAVES, NW, 1>>(                                                                  \
-        c, k_hamming_screen<WAVES, NW, 1>, dim3((n_work_blocks + WAVES - 1) / WAVES, qsplit), dim3(WAVES * 64),   \
-        (uint32_t)lds_bytes, m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n,     \
-        lds_rows, m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, head,            \
-        c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);                                                    \
-    break;
-  // (the batched-tail form <.., 4> has 68 VGPRs against 48: while the GPU is shared the lean one leaves the other
-  // queries' latency-bound stages more of the register file, +1.6 % queries/s; alone the two are equal.
-  // SFMLOC_K1_SCREEN_BATCH = 4 / 1 forces one of them.)
-  static const int env_batch = [] { const char *e = getenv("SFMLOC_K1_SCREEN_BATCH"); return e ? atoi(e) : 0; }();
-  bool mfma_form = false;
-  const bool batched_tail = env_batch ? env_batch == 4 : c->k1_may_slice;
-  if (nw == 10 && batched_tail && n_work_blocks < 16u * (uint32_t)m->n_cu) {  // fewer than four waves per SIMD: batched tail
-    sfm_launch<HammingScreenBody<WAVES, 10, 4>>(
-        c, k_hamming_screen<WAVES, 10, 4>, dim3((n_work_blocks + WAVES - 1) / WAVES, qsplit), dim3(WAVES * 64),
-        (uint32_t)lds_bytes, m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
-        m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, head, c->d_flagged_desc,
-        c->rows_chunk_cap * 64, head_part);
-  } else if (nw == 10 && use_list && qsplit == 1 && m->params.k1_mfma != 0) {
-    // any other unsliced scan of a view list (a shortlist while the GPU is shared, a long list): on the matrix cores
-    mfma_form = true;
-    const size_t lds_mfma = (size_t)(lds_rows + 1) * 64;  // (four planes of lds_rows + 1 sixteen-byte pieces)
-    sfm_launch<HammingScreenMfmaBody>(
-        c, k_hamming_screen_mfma, dim3((n_work_blocks + WAVES - 1) / WAVES, 1), dim3(WAVES * 64), (uint32_t)lds_mfma,
-        m->d_bank, c->d_block_list, n_work_blocks, q->d_desc, q->n, lds_rows, m->d_ratio_cnt, c->d_flagmask, c->d_flagged,
-        c->d_n_flagged, c->d_k1_counters, head, c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);
-  } else if (nw == 10 && use_list) {  // params.k1_mfma = 0, or a sliced scan of a view list: the popcount form
-    sfm_launch<HammingScreenBody<WAVES, 10, 1>>(
-        c, k_hamming_screen_shortlist, dim3((n_work_blocks + WAVES - 1) / WAVES, qsplit), dim3(WAVES * 64),
-        (uint32_t)lds_bytes, m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
-        m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, head, c->d_flagged_desc,
-        c->rows_chunk_cap * 64, head_part);
-  } else {
-    switch (nw) {
-      K1_SCREEN(8) K1_SCREEN(9) K1_SCREEN(10) K1_SCREEN(11) K1_SCREEN(12) K1_SCREEN(13)
-    }
+  auto screen = [&](auto body, auto kern, size_t lds) {
+    sfm_launch<decltype(body)>(c, kern, dim3((n_work_blocks + WAVES - 1) / WAVES, P.slices), dim3(WAVES * 64), (uint32_t)lds,
+                               m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
+                               m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, P.head,
+                               c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);
+  };
+  switch (P.form) {
+    case K1Form::kBatchedTail: screen(HammingScreenBody<WAVES, NW, 4>{}, k_hamming_screen<WAVES, NW, 4>, lds_bytes); break;
+    // (four planes of lds_rows + 1 sixteen-byte pieces)
+    case K1Form::kMfma: screen(HammingScreenMfmaBody{}, k_hamming_screen_mfma, (size_t)(lds_rows + 1) * 64); break;
+    case K1Form::kShortlist: screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen_shortlist, lds_bytes); break;
+    default: screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen<WAVES, NW, 1>, lds_bytes); break;
   }
-#undef K1_SCREEN
-  // executed VALU lane-ops, deterministic part (the finished pairs are counted on the device): exact head 35 per
-  // pair, screened tail 2*nw+1, plus (sfmloc_stats_read) 2*(16-nw)+5 per finished pair
-  const uint64_t rows = (uint64_t)n_work_blocks * kBlockRows;
-  // (a sliced scan shares ONE head)
-  if (mfma_form) {
-    // what the matrix-core form issues on the VALU (the MFMA work itself is not lane-ops): per 64 bank rows x 32 query
-    // rows 8 x 7 expansion + 16 v_max3 instructions = 2.25 lane-ops per pair; the head's value-only top-2 adds 64
-    // instructions per such step (2 per pair); expanding a wave's bank rows once is 112 instructions (112 per row)
-    const uint64_t nq32 = ((uint64_t)q->n + 31) & ~31ull, head32 = ((uint64_t)head + 31) & ~31ull;
-    c->stats.hamming_lane_ops += rows * nq32 * 9 / 4 + rows * (head32 < nq32 ? head32 : nq32) * 2 + rows * 112;
-    c->k1_finish_ops = 0;
-  } else {
-    c->stats.hamming_lane_ops += rows * head * 35 + rows * (q->n - head) * (uint64_t)(2 * nw + 1);
-    c->k1_finish_ops = 2 * (16 - nw) + 5;
-  }
+  c->k1_finish_ops = P.finish_ops;
   SFM_HIP(hipGetLastError());
   // the exact pass over the flagged rows: chunks of 64 rows x kRowSlices query slices, see k_hamming_rows
   constexpr int RW = 4, RS = 8;
@@ -507,47 +402,21 @@ int launch_blocks_from_views(Ctx *c, QueryPass &pass, const uint32_t *d_sel, uin
 int launch_hamming_top2(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_work_blocks, bool use_list, uint32_t split) {
   Map *m = c->map;
   if (n_work_blocks == 0 || q->n == 0) return SFMLOC_OK;
-  // (below ~12 heads' worth of query rows the exact head and the second launch eat the saving:
-  // profiles/r01_k1_screen_on_akaze_descriptors.jsonl)
-  c->last_screened = false;
-  if (split == 1 && m->params.exact_rows == 0 && q->n >= 12 * kScreenHead && !k1_override().r) {
-    c->last_screened = true;
-    return launch_hamming_screened(c, q, pass, n_work_blocks, use_list);
-  }
-  int R, W, L;
-  c->stats.hamming_lane_ops += (uint64_t)n_work_blocks * kBlockRows * q->n * 35;
-  const K1Geom &o = k1_override();
-  if (o.r) {
-    R = o.r;
-    W = o.waves;
-    L = o.lds_rows;
-  } else {
-    // Measured on MI355X (profiles/r01_valu_rates.jsonl, profiles/r01_k1_lab.txt): v_xor_b32 issues at 2
-    // cycles per wave64, v_bcnt_u32_b32 / v_med3 / v_lshl_or at ~4, and one wave alone gets an instruction
-    // only every ~4.8 cycles, so the loop reaches the VALU issue rate of its instruction mix only with >= 4
-    // waves per SIMD.  LDS vs scalar-cache query reads, register prefetch of the query row and split popcount
-    // chains all time within 5 % of each other: the loop is VALU-issue bound.  Geometry: one bank block per wave
-    // (42 VGPRs), 8-wave workgroups, 32 KiB LDS slices -> 4 workgroups = 32 waves per CU.
-    const uint64_t wave_blocks = (uint64_t)n_work_blocks * split;
-    if (wave_blocks >= (uint64_t)m->n_cu * 32) {
-      R = 1; W = 8; L = 512;
-    } else {
-      R = 1; W = 4; L = 512;
-    }
-  }
-#define K1_CASE(r, w)   if (R == r && W == w) return launch_hamming_t<r, w>(c, q, n_work_blocks, use_list, split, (uint32_t)L);
-  K1_CASE(4, 16)
-  K1_CASE(2, 16)
-  K1_CASE(1, 16)
-  K1_CASE(4, 8)
-  K1_CASE(2, 8)
-  K1_CASE(1, 8)
-  K1_CASE(4, 4)
-  K1_CASE(2, 4)
-  K1_CASE(1, 4)
-#undef K1_CASE
-  set_error("unsupported K1 geometry R=%d WAVES=%d", R, W);
-  return SFMLOC_EINVAL;
+  K1In in;
+  in.nq = q->n;
+  in.n_work_blocks = n_work_blocks;
+  in.split = split;
+  in.n_cu = m->n_cu;
+  in.use_list = use_list;
+  in.exact_rows = m->params.exact_rows != 0;
+  in.k1_mfma = m->params.k1_mfma != 0;
+  in.may_slice = c->k1_may_slice;
+  const K1Plan P = plan_k1(in, knobs());
+  c->last_screened = P.screened();
+  c->stats.hamming_lane_ops += (uint64_t)n_work_blocks * kBlockRows * P.lane_ops_per_row;
+  if (P.screened()) return launch_hamming_screened(c, q, pass, P, n_work_blocks, use_list);
+  return P.exact_waves == 8 ? launch_hamming_t<1, 8>(c, q, n_work_blocks, use_list, split, 512)
+                            : launch_hamming_t<1, 4>(c, q, n_work_blocks, use_list, split, 512);
 }
 
 int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, uint32_t split,

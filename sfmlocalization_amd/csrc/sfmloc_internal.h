@@ -12,14 +12,15 @@
 
 #include "../../include/sfmloc.h"
 #include "chain_device.h"
+#include "forms.h"
 #include "gang.h"
 
 namespace sfmloc {
 
 void set_error(const char *fmt, ...);
 
-// an integer switch of the environment (INTEGRATION.md lists them); callers keep the value in a function-local
-// `static const`, so it is read once per process
+// an integer switch of the environment (INTEGRATION.md lists them; the K1 / K3 / K5 ones are read in forms.h); callers keep
+// the value in a function-local `static const`, so it is read once per process
 inline int env_int(const char *name, int dflt) {
   const char *e = getenv(name);
   return e ? atoi(e) : dflt;
@@ -59,14 +60,7 @@ constexpr uint32_t kBlockRows = 64;
 constexpr int kK1CounterSlots = 64;  // Ctx::d_k1_counters
 constexpr int kP3pMaxN = 4096;     // 2D-3D correspondences the P3P LDS sort holds
 constexpr int kP3pBatchMax = 512;  // hypotheses evaluated per round
-// hypotheses a launch of a query's rounds carries after the first (capi.hip ctx_resection_enqueue): as many rounds as with
-// 512 (an improvement of the model comes early in a round or not at all), 3-5 % more queries per second because fewer
-// speculative hypotheses are evaluated for nothing
-constexpr int kP3pLaterBatch = 256;
-// result slots of a round: one per hypothesis (at most kP3pBatchMax), or (wide launches, at most kP3pSlots / 4 = 128
-// hypotheses -- their nominal size since round 4) four, one per model.  A slot's inlier list is kP3pMaxN ints: 8 MB per
-// context (16 MB while wide rounds could be 256 hypotheses: ADVICE r03)
-constexpr int kP3pSlots = 512;
+// (kP3pSlots, the batch sizes of a round and every other threshold the choice of a kernel form depends on: forms.h)
 constexpr uint32_t kPartHeaderBytes = 16;  // candidate part: {u32 n_cand, pad[3]} then the candidates
 
 using Pose = sfmloc_pose;
@@ -153,14 +147,7 @@ struct Map {
   uint32_t max_view_blocks = 0;  // most 64-row blocks any one view overlaps (launch bound of a device-side selection)
   uint32_t max_view_rows = 0;    // most rows of any one view
   std::atomic<int> busy_ctx{0};  // contexts with work queued (begin .. end / sync): K1 slices a short scan only when alone
-  // > 0 while recent queries had more than 512 2D-3D correspondences: K5's rounds are then launched wide (four
-  // workgroups per hypothesis, acransac.hip).  Set to 64 by a finished query that had, counted down by the others.
-  std::atomic<int> p3p_wide_credit{0};
-  std::atomic<int> k3_huge_credit{0};  // ... with 1 025 .. 2 048 (the wide form's 2 048-match instance, a query alone)
-  std::atomic<int> k3_big_credit{0};  // finished queries ago that one had a view with more than 512 putative matches (64 = just now)
-  // finished queries in a row whose 2D-3D set had at most 512 correspondences (acransac.hip kP3pSmallN): from 8 on a
-  // query's P3P rounds are queued in the small form (ctx_resection_enqueue)
-  std::atomic<int> p3p_small_credit{0};
+  FormCredits credits;  // the sizes its finished queries had: what the next ones' K3 / K5 launches are shaped for (forms.h)
   uint32_t n_views = 0;
   uint32_t n_landmarks = 0;
   std::vector<uint32_t> h_view_id, h_view_off, h_view_wh;
@@ -345,6 +332,19 @@ inline void sfm_launch(GangMember *c, void (*single)(Ts...), dim3 grid, dim3 blo
   r.block = block;
   r.shmem = shmem;
   gang_store_args<Ts...>(r.args, std::index_sequence_for<Ts...>{}, as...);
+}
+
+// what K5's plans (forms.h) are made from: the query the context is about to resect for
+inline K5In k5_in(const Ctx *c) {
+  K5In in;
+  in.query_n = c->p3p_query_n;
+  in.uncal = c->p3p_uncal;
+  in.gang = c->stream.gang != nullptr;
+  in.others_busy = c->others_busy;
+  in.small = c->p3p_small;
+  in.small_credit = c->map->credits.p3p_small.load(std::memory_order_relaxed);
+  in.wide_credit = c->map->credits.p3p_wide.load(std::memory_order_relaxed);
+  return in;
 }
 
 struct Query {

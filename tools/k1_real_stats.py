@@ -17,7 +17,7 @@ def main():
     q, big, out = synth.mldb_like_bank(S)
     view_off = np.arange(0, len(big) + 1, len(big) // 200, dtype=np.uint32)
     view_off[-1] = len(big)
-    nw = int(os.environ.get("SFMLOC_K1_SCREEN_NW", "10"))    # read once per process by the library
+    nw = 10  # dwords of the screening prefix (csrc/forms.h kScreenNW)
     for exact in (0, 1):
         p = S.default_params(profile=1, exact_rows=exact)
         with S.Map(np.arange(len(view_off) - 1, dtype=np.uint32), view_off, big, params=p) as dm:
