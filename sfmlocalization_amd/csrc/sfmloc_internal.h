@@ -346,6 +346,8 @@ inline K5In k5_in(const Ctx *c) {
   in.wide_credit = c->map->credits.p3p_wide.load(std::memory_order_relaxed);
   return in;
 }
+// acransac.hip: K5's kernel arguments for that query (K4's last kernel starts K5 and takes them too); library-internal
+__attribute__((visibility("hidden"))) P3pArgs make_p3p_args(Ctx *c, const K5In &in);
 
 struct Query {
   Map *map = nullptr;
@@ -452,14 +454,15 @@ int launch_fill_log10(double *d_L10, int n, hipStream_t s);
 int launch_debug_math(int op, const double *d_in, int n, int in_stride, double *d_out, int out_stride, hipStream_t s);
 // min_putative < 0: the map's params.min_putative (the query path's >=16 rule, localization.cpp:408-415)
 int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, int min_putative = -1);
-int launch_match_set(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views);
 // guided.hip: GeometricFilter_FMatrix_AC::Geometry_guided_matching for the views that passed K3 (their geo lists are
 // replaced by (map feature, query feature) lists in d_geo_idx / d_geo_j)
 int ensure_guided_workspace(Ctx *c);
 int launch_guided_matching(Ctx *c, const Query *q, uint32_t n_sel, bool all_views);
+// k4_matchset.hip
+int launch_match_set(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views);
 int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views);
 int launch_export_part(Ctx *c, void *dst_dev, uint32_t cap);
-// packed_b > 0: `parts` are packed batch parts of packed_b queries (acransac.hip PartLayout), cap = their budget,
+// packed_b > 0: `parts` are packed batch parts of packed_b queries (k4_matchset.hip PartLayout), cap = their budget,
 // and this query is number packed_qi of the batch
 int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, const unsigned char *parts, uint32_t n_parts,
                              uint64_t part_bytes, uint32_t cap, uint32_t packed_b = 0, uint32_t packed_qi = 0,
@@ -468,6 +471,7 @@ int launch_export_packed(Ctx *c, void *dst_dev, uint32_t n_queries, uint32_t bud
 uint64_t packed_part_bytes(uint32_t n_queries, uint32_t budget);
 int ctx_p3p_reserve(Ctx *c, uint32_t n_query_rows);  // capi.hip: grow the P3P workspace to a query's feature count
 int launch_merge_masked_now(Ctx *c, const MergeMaskedArgs &M, uint32_t n_sel);  // hamming.hip: a deferred K2 as a launch of its own
+// acransac.hip
 int launch_p3p_init(Ctx *c);
 int launch_p3p_round(Ctx *c, int batch);
 int launch_p3p_finish(Ctx *c);
