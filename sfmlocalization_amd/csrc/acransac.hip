@@ -2650,17 +2650,19 @@ static int ensure_fmatrix_large(Ctx *c) {
   while (slot_m < (int)m->max_view_rows && slot_m < kFLargeMaxM) slot_m <<= 1;
   c->fl_slot_m = slot_m;
   const size_t n = (size_t)kFLargeSlots * slot_m, n1 = (size_t)kFLargeSlots * (slot_m + 1);
-  SFM_HIP(hipMalloc((void **)&c->fl_key, n * sizeof(uint64_t)));
-  SFM_HIP(hipMalloc((void **)&c->fl_idx, n * sizeof(uint32_t)));
-  SFM_HIP(hipMalloc((void **)&c->fl_vec_index, n * sizeof(int32_t)));
-  SFM_HIP(hipMalloc((void **)&c->fl_best_inl, n * sizeof(int32_t)));
-  SFM_HIP(hipMalloc((void **)&c->fl_logc_n, n1 * sizeof(float)));
-  SFM_HIP(hipMalloc((void **)&c->fl_logc_k, n1 * sizeof(float)));
-  SFM_HIP(hipMalloc((void **)&c->fl_count, sizeof(uint32_t)));
+  DevGroup g(&c->hbm_bytes);  // (all eight or none: fl_key stands for the set)
+  g.add(c->fl_key, n);
+  g.add(c->fl_idx, n);
+  g.add(c->fl_vec_index, n);
+  g.add(c->fl_best_inl, n);
+  g.add(c->fl_logc_n, n1);
+  g.add(c->fl_logc_k, n1);
+  g.add(c->fl_count, 1);
+  g.add(c->fl_list, (size_t)m->n_views + 1);
+  if (!g.ok()) return g.rc();
+  g.commit();
   SFM_HIP(hipMemset(c->fl_count, 0, sizeof(uint32_t)));  // (from the next query on the query's reset kernel clears it)
   SFM_HIP(hipStreamSynchronize(nullptr));                // (null stream: not ordered with the context's stream otherwise)
-  SFM_HIP(hipMalloc((void **)&c->fl_list, ((size_t)m->n_views + 1) * sizeof(uint32_t)));
-  c->hbm_bytes += n * 20 + n1 * 8 + ((size_t)m->n_views + 2) * 4;
   return SFMLOC_OK;
 }
 
@@ -2695,7 +2697,10 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
   T.merge.enabled = 0;
   T.merge.view_sel = nullptr;
   T.merge.view_widx0 = nullptr;
-  if (!c->d_k3_static) SFM_HIP(hipMalloc(&c->d_k3_static, sizeof(c->k3_static_host)));
+  if (!c->d_k3_static) {
+    int rc = c->d_k3_static.alloc(&c->hbm_bytes, sizeof(c->k3_static_host));
+    if (rc) return rc;
+  }
   if (!c->k3_static_valid || memcmp(&T, c->k3_static_host, sizeof(T)) != 0) {
     memcpy(c->k3_static_host, &T, sizeof(T));
     // (ahead of whatever a recording member has recorded -- nothing recorded reads the block before this call's launches
@@ -2705,7 +2710,7 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
     SFM_HIP(hipStreamSynchronize(s));
     c->k3_static_valid = true;
   }
-  P->st = reinterpret_cast<const FFilterStatic *>(c->d_k3_static);
+  P->st = reinterpret_cast<const FFilterStatic *>(c->d_k3_static.get());
   P->view_sel = A.view_sel;
   P->q_kpt6 = A.q_kpt6;
   P->merge_view_sel = A.merge.view_sel;
@@ -2798,14 +2803,16 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
   }
   if (P.wide) {
     if (!c->d_k3_spec) {
-      SFM_HIP(hipMalloc((void **)&c->d_k3_spec, (size_t)kK3WideViews * kF2Batch * sizeof(K3Spec)));
-      SFM_HIP(hipMalloc((void **)&c->d_k3_arrive, (size_t)kK3WideViews * sizeof(unsigned int)));
+      DevGroup g(&c->hbm_bytes);
+      g.add(c->d_k3_spec, (size_t)kK3WideViews * kF2Batch * sizeof(K3Spec));
+      g.add(c->d_k3_arrive, (size_t)kK3WideViews);
+      if (!g.ok()) return g.rc();
+      g.commit();
       // (the last arrival clears its slot.  On the stream the launch below goes to, so that nothing waits for the device:
       // every context of a busy map gets here once.  Nothing a gang member has recorded touches the new buffer.)
       SFM_HIP(hipMemsetAsync(c->d_k3_arrive, 0, (size_t)kK3WideViews * sizeof(unsigned int), c->stream.unordered()));
-      c->hbm_bytes += (size_t)kK3WideViews * (kF2Batch * sizeof(K3Spec) + sizeof(unsigned int));
     }
-    A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec);
+    A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec.get());
     A.spec_arrive = c->d_k3_arrive;
     const hipError_t e = P.max_m == kF2HugeM ? launch_fmatrix_fast<4, kF2HugeM, true>(c, A, P.wide_b0)
                                              : launch_fmatrix_fast<4, kF2BigM, true>(c, A, P.wide_b0);
@@ -2860,7 +2867,7 @@ P3pArgs make_p3p_args(Ctx *c, const K5In &in) {
   P3pArgs A;
   A.state = c->d_p3p_state;
   A.result = c->d_pose;
-  A.record = reinterpret_cast<const HostResult *>(c->d_result);
+  A.record = reinterpret_cast<const HostResult *>(c->d_result.get());
   A.host = reinterpret_cast<HostResult *>(c->h_result);
   A.ms_n = c->d_ms_n;
   A.ms_qfeat = c->d_ms_qfeat;

@@ -35,21 +35,101 @@ double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-template <typename T>
-int dev_alloc(uint64_t *acct, T **p, size_t n) {
+// test hook (sfmloc_debug_fail_p3p_alloc(k)): the k-th allocation of the NEXT regrowth fails; one shot, consumed atomically
+// by the regrowth that sees it (no environment variable: a stray one must not be able to fail a production allocation).
+// That regrowth arms g_fail_countdown for its own allocations (ctx_p3p_reserve).
+std::atomic<int> g_test_fail_alloc{-1};
+thread_local int g_fail_countdown = -1;
+thread_local hipError_t g_raw_alloc_err = hipSuccess;  // why the last dev_raw_alloc of this thread failed
+
+}  // namespace
+
+// devmem.h: every DevBuf allocates and frees through these two
+int dev_raw_alloc(void **p, size_t bytes) {
   *p = nullptr;
-  if (n == 0) return SFMLOC_OK;
-  SFM_HIP(hipMalloc((void **)p, n * sizeof(T)));
-  *acct += n * sizeof(T);
-  return SFMLOC_OK;
+  const bool injected = g_fail_countdown >= 0 && g_fail_countdown-- == 0;
+  const hipError_t e = injected ? hipErrorOutOfMemory : hipMalloc(p, bytes);
+  g_raw_alloc_err = e;
+  if (e == hipSuccess) return SFMLOC_OK;
+  if (!injected) (void)hipGetLastError();
+  *p = nullptr;
+  set_error("hipMalloc(%zu bytes) -> %s", bytes, hipGetErrorString(e));
+  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SFMLOC_ENODEV
+         : (e == hipErrorOutOfMemory)                          ? SFMLOC_ENOMEM
+                                                               : SFMLOC_EHIP;
+}
+void dev_raw_free(void *p) { (void)hipFree(p); }
+hipError_t dev_raw_alloc_error() { return g_raw_alloc_err; }
+
+namespace {
+
+template <typename T>
+int dev_alloc(uint64_t *acct, DevBuf<T> &p, size_t n) {
+  return p.alloc(acct, n);
 }
 
 template <typename T>
-int dev_upload(uint64_t *acct, T **p, const T *h, size_t n, hipStream_t s) {
+int dev_upload(uint64_t *acct, DevBuf<T> &p, const T *h, size_t n, hipStream_t s) {
   int rc = dev_alloc(acct, p, n);
   if (rc) return rc;
-  if (n) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+  if (n) SFM_HIP(hipMemcpyAsync(p.get(), h, n * sizeof(T), hipMemcpyHostToDevice, s));
   return SFMLOC_OK;
+}
+
+// BofModel (bow.hip) keeps raw pointers; h null: allocate only
+template <typename T>
+int bof_upload(T **p, const T *h, size_t n, hipStream_t s) {
+  *p = nullptr;
+  if (n == 0) return SFMLOC_OK;
+  SFM_HIP(hipMalloc((void **)p, n * sizeof(T)));
+  if (h) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
+  return SFMLOC_OK;
+}
+
+// The P3P arrays that grow with a query's feature count, for `cap` correspondences, as one all-or-nothing set: a new
+// context's (cap = kP3pMaxN: the pair lists are inside HostResult and a hypothesis sorts in LDS, so those five arrays
+// are not made) and every regrowth's (ctx_p3p_reserve).  The new set is complete before the stream is drained --
+// kernels of the previous query may still read the old arrays -- and the old set is let go; on failure the context is
+// exactly as it was.
+int ctx_p3p_workspace(Ctx *c, uint32_t cap) {
+  const bool big = cap > (uint32_t)kP3pMaxN;
+  const size_t large = (size_t)kP3pLargeBatch * cap;  // hypotheses of a round beyond kP3pMaxN x their sort segments
+  DevGroup g(&c->hbm_bytes);
+  g.add(c->d_xn, (size_t)cap * 2);
+  g.add(c->d_logc_n, (size_t)cap + 1);
+  g.add(c->d_logc_k, (size_t)cap + 1);
+  g.add(c->d_vec_index, (size_t)cap);
+  g.add(c->d_best_inl, (size_t)cap);
+  g.add(c->d_hyp_inl, std::max<size_t>((size_t)kP3pSlots * kP3pMaxN, large));  // kP3pSlots lists of kP3pMaxN, or `large`
+  g.add(c->d_inlier_idx, (size_t)cap);
+  if (big) {
+    g.add(c->d_pair_qfeat_big, (size_t)cap);
+    g.add(c->d_pair_landmark_big, (size_t)cap);
+    g.add(c->d_p3p_ws_key, large);
+    g.add(c->d_p3p_ws_idx, large);
+    g.add(c->d_p3p_terms, (size_t)cap / 2 + 2);
+  }
+  if (!g.ok()) {
+    if (!big) return g.rc();  // (a new context's first set: the allocation's own code and text, like its other arrays)
+    set_error("P3P workspace for %u correspondences: allocation %d of 12 (%zu bytes) failed: %s", cap, g.failed_index(),
+              g.failed_bytes(), hipGetErrorString(g_raw_alloc_err));
+    return SFMLOC_ENOMEM;
+  }
+  if (c->d_xn) SFM_HIP(hipStreamSynchronize(c->stream));
+  g.commit();
+  if (big) {  // no longer inside the HostResult record
+    c->d_pair_qfeat = c->d_pair_qfeat_big;
+    c->d_pair_landmark = c->d_pair_landmark_big;
+  }
+  c->p3p_cap = cap;
+  return SFMLOC_OK;
+}
+
+// sfmloc_map_info::hbm_bytes: the map's own buffers and what each context it owns holds now
+uint64_t map_hbm_bytes(const Map *m) {
+  uint64_t b = m->hbm_bytes + (m->ctx0 ? m->ctx0->hbm_bytes : 0);
+  for (const Ctx *c : m->pool) b += c->hbm_bytes;
+  return b;
 }
 
 // number of d0 in [0,512] for which the reference's expression holds (MatchUtils.cpp:347):
@@ -125,27 +205,16 @@ void free_ctx(Ctx *c) {
     hipEventDestroy(e.first);
     hipEventDestroy(e.second);
   }
-  void *ptrs[] = {c->d_part,      c->d_view_sel,  c->d_view_widx0, c->d_block_list, c->d_view_count, c->d_match_i,
-                  c->d_match_key, c->d_geo_count, c->d_geo_idx,    c->d_result,     c->d_cand_part,
-                  c->d_best64,    c->d_winner,    c->d_ms_n,       c->d_ms_qfeat,   c->d_ms_landmark, c->d_pt2d,
-                  c->d_pt3d,      c->d_xn,        c->d_logc_n,     c->d_logc_k,     c->d_vec_index,  c->d_best_inl,
-                  c->d_hyp_nfa,   c->d_hyp_err,   c->d_hyp_model,  c->d_hyp_k,      c->d_hyp_inl,
-                  c->d_inlier_idx, c->d_prep_models, c->d_prep_nm,
-                  c->d_bow_query, c->d_bow_dist,  c->d_bow_cand,   c->d_bow_sel,    c->d_flagged,    c->d_n_flagged,  c->d_k1_counters, c->d_flagmask, c->d_rows_scratch, c->d_rows_arrivals, c->d_flagged_desc,
-                  c->d_geo_model, c->d_geo_j,     c->d_guided_row, c->d_geo_dist,
-                  c->fl_key, c->fl_idx, c->fl_count, c->fl_list, c->d_k3_spec, c->d_k3_arrive, c->d_k3_static, c->fl_vec_index, c->fl_best_inl, c->fl_logc_n, c->fl_logc_k,
-                  c->d_pair_qfeat_big, c->d_pair_landmark_big, c->d_p3p_ws_key, c->d_p3p_ws_idx, c->d_p3p_terms};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
   if (c->h_pinned) hipHostFree(c->h_pinned);
   if (c->h_result) hipHostFree(c->h_result);
   if (c->pinned_busy) hipEventDestroy(c->pinned_busy);
   if (c->xev_out) hipEventDestroy(c->xev_out);
   if (c->xev_in) hipEventDestroy(c->xev_in);
   gang_member_free(c);
-  if (c->stream.own && !c->stream_borrowed) hipStreamDestroy(c->stream.own);
+  hipStream_t own = c->stream_borrowed ? nullptr : c->stream.own;
   Ctx *lender = c->lender;
-  delete c;
+  delete c;  // (every DevBuf frees its array here: before the stream goes)
+  if (own) hipStreamDestroy(own);
   if (lender && --lender->borrowers == 0 && lender->zombie) free_ctx(lender);
 }
 
@@ -186,32 +255,32 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
   // a context that only ever merges candidate parts and runs P3P (sfmloc_context_create_merge) has no use for the
   // per-bank-row arrays of the matching stages: 30 B per row and the 32 MB of the flagged-row pass
   const bool full = !merge_only;
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_part, (size_t)n_pad));
-  CTX_TRY(dev_alloc(acct, &c->d_view_sel, (size_t)m->n_views + 1));
-  CTX_TRY(dev_alloc(acct, &c->d_view_widx0, (size_t)m->n_views + 1));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_block_list, (size_t)m->n_blocks));
-  CTX_TRY(dev_alloc(acct, &c->d_view_count, (size_t)m->n_views + 1));  // + the phantom view (sfmloc_internal.h)
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_match_i, (size_t)m->n_rows));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_match_key, (size_t)m->n_rows));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_flagged, (size_t)n_pad));
-  CTX_TRY(dev_alloc(acct, &c->d_n_flagged, (size_t)1));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_flagmask, (size_t)m->n_blocks + 1));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_part, (size_t)n_pad));
+  CTX_TRY(dev_alloc(acct, c->d_view_sel, (size_t)m->n_views + 1));
+  CTX_TRY(dev_alloc(acct, c->d_view_widx0, (size_t)m->n_views + 1));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_block_list, (size_t)m->n_blocks));
+  CTX_TRY(dev_alloc(acct, c->d_view_count, (size_t)m->n_views + 1));  // + the phantom view (sfmloc_internal.h)
+  if (full) CTX_TRY(dev_alloc(acct, c->d_match_i, (size_t)m->n_rows));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_match_key, (size_t)m->n_rows));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_flagged, (size_t)n_pad));
+  CTX_TRY(dev_alloc(acct, c->d_n_flagged, (size_t)1));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_flagmask, (size_t)m->n_blocks + 1));
   c->rows_chunk_cap = m->n_blocks < 4096 ? (m->n_blocks ? m->n_blocks : 1) : 4096;  // 4096 chunks = 262 k flagged rows, 16 MB
   if (full) {
-    CTX_TRY(dev_alloc(acct, &c->d_rows_scratch, (size_t)c->rows_chunk_cap * 8 * 64));
-    CTX_TRY(dev_alloc(acct, &c->d_rows_arrivals, (size_t)c->rows_chunk_cap));
-    CTX_TRY(dev_alloc(acct, &c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
+    CTX_TRY(dev_alloc(acct, c->d_rows_scratch, (size_t)c->rows_chunk_cap * 8 * 64));
+    CTX_TRY(dev_alloc(acct, c->d_rows_arrivals, (size_t)c->rows_chunk_cap));
+    CTX_TRY(dev_alloc(acct, c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
     CTX_HIP(hipMemset(c->d_rows_arrivals, 0, (size_t)c->rows_chunk_cap * sizeof(uint32_t)));
   }
-  CTX_TRY(dev_alloc(acct, &c->d_k1_counters, (size_t)2 * kK1CounterSlots));
+  CTX_TRY(dev_alloc(acct, c->d_k1_counters, (size_t)2 * kK1CounterSlots));
   CTX_HIP(hipMemset(c->d_k1_counters, 0, 2 * kK1CounterSlots * sizeof(unsigned long long)));
-  CTX_TRY(dev_alloc(acct, &c->d_geo_count, (size_t)m->n_views + 1));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_geo_idx, (size_t)m->n_rows));
-  CTX_TRY(dev_alloc(acct, &c->d_geo_model, ((size_t)m->n_views + 1) * 10));
+  CTX_TRY(dev_alloc(acct, c->d_geo_count, (size_t)m->n_views + 1));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_geo_idx, (size_t)m->n_rows));
+  CTX_TRY(dev_alloc(acct, c->d_geo_model, ((size_t)m->n_views + 1) * 10));
   // everything a finished query reports lives in ONE device record laid out as HostResult: one D2H copy per query
-  CTX_TRY(dev_alloc(acct, &c->d_result, sizeof(HostResult)));
+  CTX_TRY(dev_alloc(acct, c->d_result, sizeof(HostResult)));
   {
-    HostResult *r = reinterpret_cast<HostResult *>(c->d_result);
+    HostResult *r = reinterpret_cast<HostResult *>(c->d_result.get());
     c->d_p3p_state = &r->state;
     c->d_pose = &r->pose;
     c->d_status = &r->status;
@@ -219,36 +288,27 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
     c->d_pair_qfeat = r->pair_qfeat;
     c->d_pair_landmark = r->pair_landmark;
   }
-  CTX_TRY(dev_alloc(acct, &c->d_cand_part, (size_t)kPartHeaderBytes + (size_t)c->cand_cap * sizeof(Candidate)));
-  if (full) CTX_TRY(dev_alloc(acct, &c->d_geo_dist, (size_t)m->n_rows));
-  CTX_TRY(dev_alloc(acct, &c->d_best64, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, &c->d_winner, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, &c->d_ms_n, (size_t)1));
-  CTX_TRY(dev_alloc(acct, &c->d_ms_qfeat, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, &c->d_ms_landmark, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, &c->d_pt2d, (size_t)65536 * 2));
-  CTX_TRY(dev_alloc(acct, &c->d_pt3d, (size_t)65536 * 3));
-  CTX_TRY(dev_alloc(acct, &c->d_xn, (size_t)kP3pMaxN * 2));
-  CTX_TRY(dev_alloc(acct, &c->d_logc_n, (size_t)kP3pMaxN + 1));
-  CTX_TRY(dev_alloc(acct, &c->d_logc_k, (size_t)kP3pMaxN + 1));
-  CTX_TRY(dev_alloc(acct, &c->d_vec_index, (size_t)kP3pMaxN));
-  CTX_TRY(dev_alloc(acct, &c->d_best_inl, (size_t)kP3pMaxN));
-  CTX_TRY(dev_alloc(acct, &c->d_hyp_nfa, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, &c->d_hyp_err, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, &c->d_hyp_model, (size_t)kP3pSlots * 12));
-  CTX_TRY(dev_alloc(acct, &c->d_hyp_k, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, &c->d_prep_models, (size_t)kP3pBatchMax * 48));
-  CTX_TRY(dev_alloc(acct, &c->d_prep_nm, (size_t)kP3pBatchMax));
-  CTX_TRY(dev_alloc(acct, &c->d_hyp_inl, (size_t)kP3pSlots * kP3pMaxN));
-  CTX_TRY(dev_alloc(acct, &c->d_inlier_idx, (size_t)kP3pMaxN));
-  // the regrowable P3P set as allocated above (ctx_p3p_reserve replaces it and keeps the accounts)
-  c->p3p_bytes = (uint64_t)kP3pMaxN * (2 * sizeof(double) + 3 * sizeof(int32_t)) + 2 * ((uint64_t)kP3pMaxN + 1) * sizeof(float) +
-                 (uint64_t)kP3pSlots * kP3pMaxN * sizeof(int32_t);
+  CTX_TRY(dev_alloc(acct, c->d_cand_part, (size_t)kPartHeaderBytes + (size_t)c->cand_cap * sizeof(Candidate)));
+  if (full) CTX_TRY(dev_alloc(acct, c->d_geo_dist, (size_t)m->n_rows));
+  CTX_TRY(dev_alloc(acct, c->d_best64, (size_t)65536));
+  CTX_TRY(dev_alloc(acct, c->d_winner, (size_t)65536));
+  CTX_TRY(dev_alloc(acct, c->d_ms_n, (size_t)1));
+  CTX_TRY(dev_alloc(acct, c->d_ms_qfeat, (size_t)65536));
+  CTX_TRY(dev_alloc(acct, c->d_ms_landmark, (size_t)65536));
+  CTX_TRY(dev_alloc(acct, c->d_pt2d, (size_t)65536 * 2));
+  CTX_TRY(dev_alloc(acct, c->d_pt3d, (size_t)65536 * 3));
+  CTX_TRY(dev_alloc(acct, c->d_hyp_nfa, (size_t)kP3pSlots));
+  CTX_TRY(dev_alloc(acct, c->d_hyp_err, (size_t)kP3pSlots));
+  CTX_TRY(dev_alloc(acct, c->d_hyp_model, (size_t)kP3pSlots * 12));
+  CTX_TRY(dev_alloc(acct, c->d_hyp_k, (size_t)kP3pSlots));
+  CTX_TRY(dev_alloc(acct, c->d_prep_models, (size_t)kP3pBatchMax * 48));
+  CTX_TRY(dev_alloc(acct, c->d_prep_nm, (size_t)kP3pBatchMax));
+  CTX_TRY(ctx_p3p_workspace(c, kP3pMaxN));  // the arrays that ctx_p3p_reserve regrows
   if (m->bow_dim) {
-    CTX_TRY(dev_alloc(acct, &c->d_bow_query, (size_t)m->bow_dim));
-    CTX_TRY(dev_alloc(acct, &c->d_bow_dist, (size_t)m->n_views));
-    CTX_TRY(dev_alloc(acct, &c->d_bow_cand, (size_t)m->n_views));
-    CTX_TRY(dev_alloc(acct, &c->d_bow_sel, (size_t)m->n_views + 1));
+    CTX_TRY(dev_alloc(acct, c->d_bow_query, (size_t)m->bow_dim));
+    CTX_TRY(dev_alloc(acct, c->d_bow_dist, (size_t)m->n_views));
+    CTX_TRY(dev_alloc(acct, c->d_bow_cand, (size_t)m->n_views));
+    CTX_TRY(dev_alloc(acct, c->d_bow_sel, (size_t)m->n_views + 1));
   }
   CTX_HIP(hipHostMalloc((void **)&c->h_pinned, ((size_t)2 * m->n_views + m->n_blocks + 16) * sizeof(uint32_t),
                         hipHostMallocDefault));
@@ -280,11 +340,7 @@ void free_map(Map *m) {
   hipSetDevice(m->device);
   for (Ctx *c : m->pool) free_ctx(c);
   free_ctx(m->ctx0);
-  void *ptrs[] = {m->d_bank,         m->d_view_off,   m->d_view_id, m->d_view_wh, m->d_kpt, m->d_row_landmark,
-                  m->d_landmark_id,  m->d_landmark_X, m->d_bow,     m->d_L10,     m->d_ratio_cnt};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  delete m;
+  delete m;  // (its DevBufs free their arrays)
 }
 
 // ----- stages on a context --------------------------------------------------------------------------
@@ -311,7 +367,7 @@ QueryResetArgs make_reset_args(Ctx *c, const Query *q) {
   R.nq = q->n ? q->n : 1;
   R.n_flagged = c->d_n_flagged;
   R.status = c->d_status;
-  R.cand_header = reinterpret_cast<uint32_t *>(c->d_cand_part);
+  R.cand_header = reinterpret_cast<uint32_t *>(c->d_cand_part.get());
   R.view_stats = c->d_view_stats;
   R.ms_n = c->d_ms_n;
   R.fl_count = c->fl_count;
@@ -554,71 +610,19 @@ int ctx_resection_enqueue(Ctx *c, bool first_call) {
 }  // namespace
 
 // Grows the P3P workspace of a context to hold `n` correspondences (a query has at most one per feature).  Rare: only a
-// query with more than kP3pMaxN features gets here.  The new set is allocated first and swapped in only when every
-// allocation has succeeded: on failure the context keeps its old arrays and capacity and the caller gets SFMLOC_ENOMEM
-// (the old code freed first and left null pointers behind a stale p3p_cap).  The stream is drained before
-// the old arrays are freed (kernels of the previous query may still read them); a context that is recording for a gang
-// session never gets here with work recorded -- the reserve is the first thing a query's stage does -- but if it does,
-// reading c->stream issues what was recorded first (gang.h), so stream order is still call order.
-namespace {
-// test hook (sfmloc_debug_fail_p3p_alloc(k)): the k-th allocation of the NEXT regrowth fails; one shot, consumed atomically
-// by the regrowth that sees it (no environment variable: a stray one must not be able to fail a production allocation)
-std::atomic<int> g_test_fail_alloc{-1};
-}
+// query with more than kP3pMaxN features gets here.  On failure the context keeps its old arrays and capacity and the
+// caller gets SFMLOC_ENOMEM (ctx_p3p_workspace).  A context that is recording for a gang session never gets here with
+// work recorded -- the reserve is the first thing a query's stage does -- but if it does, reading c->stream issues
+// what was recorded first (gang.h), so stream order is still call order.
 int ctx_p3p_reserve(Ctx *c, uint32_t n) {
   c->p3p_query_n = n;
   if (n <= c->p3p_cap) return SFMLOC_OK;
   uint32_t cap = c->p3p_cap;
   while (cap < n) cap <<= 1;
-  // hypothesis inlier lists: kP3pBatchMax lists of kP3pMaxN, or (more correspondences) kP3pLargeBatch lists of cap
-  const size_t large_batch = kP3pLargeBatch;
-  const size_t hyp = std::max<size_t>((size_t)kP3pSlots * kP3pMaxN, large_batch * cap);
-  const size_t bytes[12] = {(size_t)cap * 2 * sizeof(double),      ((size_t)cap + 1) * sizeof(float),
-                            ((size_t)cap + 1) * sizeof(float),     (size_t)cap * sizeof(int32_t),
-                            (size_t)cap * sizeof(int32_t),         hyp * sizeof(int32_t),
-                            (size_t)cap * sizeof(uint32_t),        (size_t)cap * sizeof(uint32_t),
-                            (size_t)cap * sizeof(uint32_t),        large_batch * cap * sizeof(uint64_t),
-                            large_batch * cap * sizeof(uint32_t),  ((size_t)cap / 2 + 2) * sizeof(double)};
-  const int test_fail_alloc = g_test_fail_alloc.exchange(-1, std::memory_order_relaxed);
-  void *fresh[12] = {nullptr};
-  uint64_t total = 0;
-  for (int i = 0; i < 12; ++i) {
-    hipError_t err = (i == test_fail_alloc) ? hipErrorOutOfMemory : hipMalloc(&fresh[i], bytes[i]);
-    if (err != hipSuccess) {
-      if (i != test_fail_alloc) (void)hipGetLastError();
-      for (int k = 0; k < i; ++k) (void)hipFree(fresh[k]);
-      set_error("P3P workspace for %u correspondences: allocation %d of 12 (%zu bytes) failed: %s", cap, i, bytes[i],
-                hipGetErrorString(err));
-      return SFMLOC_ENOMEM;
-    }
-    total += bytes[i];
-  }
-  SFM_HIP(hipStreamSynchronize(c->stream));
-  void *old[12] = {c->d_xn,        c->d_logc_n,        c->d_logc_k,           c->d_vec_index,  c->d_best_inl,   c->d_hyp_inl,
-                   c->d_inlier_idx, c->d_pair_qfeat_big, c->d_pair_landmark_big, c->d_p3p_ws_key, c->d_p3p_ws_idx, c->d_p3p_terms};
-  for (void *p : old)
-    if (p) (void)hipFree(p);
-  c->d_xn = (double *)fresh[0];
-  c->d_logc_n = (float *)fresh[1];
-  c->d_logc_k = (float *)fresh[2];
-  c->d_vec_index = (int32_t *)fresh[3];
-  c->d_best_inl = (int32_t *)fresh[4];
-  c->d_hyp_inl = (int32_t *)fresh[5];
-  c->d_inlier_idx = (uint32_t *)fresh[6];
-  c->d_pair_qfeat_big = (uint32_t *)fresh[7];
-  c->d_pair_landmark_big = (uint32_t *)fresh[8];
-  c->d_p3p_ws_key = (uint64_t *)fresh[9];
-  c->d_p3p_ws_idx = (uint32_t *)fresh[10];
-  c->d_p3p_terms = (double *)fresh[11];
-  c->d_pair_qfeat = c->d_pair_qfeat_big;  // no longer inside the HostResult record
-  c->d_pair_landmark = c->d_pair_landmark_big;
-  // accounting: the regrown set replaces the previous one (the first set was counted by make_ctx through dev_alloc)
-  const uint64_t before = c->p3p_bytes;
-  c->p3p_bytes = total;
-  c->hbm_bytes += total - before;
-  if (c->map) c->map->hbm_bytes += total - before;
-  c->p3p_cap = cap;
-  return SFMLOC_OK;
+  g_fail_countdown = g_test_fail_alloc.exchange(-1, std::memory_order_relaxed);
+  const int rc = ctx_p3p_workspace(c, cap);
+  g_fail_countdown = -1;
+  return rc;
 }
 
 namespace {
@@ -1023,7 +1027,7 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
 
   // bank: upload row-major chunks and re-tile on the device
   const uint64_t n_pad = (uint64_t)m->n_blocks * kBlockRows;
-  SFM_TRY(dev_alloc(acct, &m->d_bank, (size_t)n_pad * 4));
+  SFM_TRY(dev_alloc(acct, m->d_bank, (size_t)n_pad * 4));
   if (n_pad) {
     MAP_HIP(hipMemsetAsync(m->d_bank, 0, n_pad * 64, s));
     const uint64_t chunk = 16ull << 20;  // rows per staging chunk (1 GiB)
@@ -1055,33 +1059,34 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
     std::vector<uint32_t> off(d->view_off, d->view_off + d->n_views + 1), id(d->view_id, d->view_id + d->n_views);
     off.push_back((uint32_t)d->n_rows);
     id.push_back(0xFFFFFFu);
-    SFM_TRY(dev_upload(acct, &m->d_view_off, off.data(), off.size(), s));
-    SFM_TRY(dev_upload(acct, &m->d_view_id, id.data(), id.size(), s));
+    SFM_TRY(dev_upload(acct, m->d_view_off, off.data(), off.size(), s));
+    SFM_TRY(dev_upload(acct, m->d_view_id, id.data(), id.size(), s));
     if (d->view_wh) {
       std::vector<uint32_t> wh(d->view_wh, d->view_wh + 2 * (size_t)d->n_views);
       wh.push_back(1);
       wh.push_back(1);
-      SFM_TRY(dev_upload(acct, &m->d_view_wh, wh.data(), wh.size(), s));
+      SFM_TRY(dev_upload(acct, m->d_view_wh, wh.data(), wh.size(), s));
     }
     MAP_HIP(hipStreamSynchronize(s));  // the staging vectors go out of scope
   }
-  if (d->kpt_xy) SFM_TRY(dev_upload(acct, (float **)&m->d_kpt, d->kpt_xy, (size_t)d->n_rows * 2, s));
+  if (d->kpt_xy)
+    SFM_TRY(dev_upload(acct, m->d_kpt, reinterpret_cast<const float2 *>(d->kpt_xy), (size_t)d->n_rows, s));
   if (d->row_landmark) {
-    SFM_TRY(dev_upload(acct, &m->d_row_landmark, d->row_landmark, (size_t)d->n_rows, s));
-    SFM_TRY(dev_upload(acct, &m->d_landmark_id, d->landmark_id, (size_t)d->n_landmarks, s));
-    SFM_TRY(dev_upload(acct, &m->d_landmark_X, d->landmark_X, (size_t)d->n_landmarks * 3, s));
+    SFM_TRY(dev_upload(acct, m->d_row_landmark, d->row_landmark, (size_t)d->n_rows, s));
+    SFM_TRY(dev_upload(acct, m->d_landmark_id, d->landmark_id, (size_t)d->n_landmarks, s));
+    SFM_TRY(dev_upload(acct, m->d_landmark_X, d->landmark_X, (size_t)d->n_landmarks * 3, s));
   }
   if (d->bow && d->bow_dim) {
     m->bow_dim = d->bow_dim;
-    SFM_TRY(dev_upload(acct, &m->d_bow, d->bow, (size_t)d->n_views * d->bow_dim, s));
+    SFM_TRY(dev_upload(acct, m->d_bow, d->bow, (size_t)d->n_views * d->bow_dim, s));
   }
   m->have_geometry = d->view_wh && d->kpt_xy && d->row_landmark && d->focal > 0.0;
-  SFM_TRY(dev_alloc(acct, &m->d_L10, (size_t)65538));
+  SFM_TRY(dev_alloc(acct, m->d_L10, (size_t)65538));
   SFM_TRY(launch_fill_log10(m->d_L10, 65538, s));
   {
     uint16_t tab[513];
     build_ratio_table(p.dist_ratio, tab);
-    SFM_TRY(dev_alloc(acct, &m->d_ratio_cnt, (size_t)513));
+    SFM_TRY(dev_alloc(acct, m->d_ratio_cnt, (size_t)513));
     MAP_HIP(hipMemcpyAsync(m->d_ratio_cnt, tab, sizeof(tab), hipMemcpyHostToDevice, s));
     MAP_HIP(hipStreamSynchronize(s));  // tab lives on the stack
     m->ratio_cnt_for = p.dist_ratio;
@@ -1090,7 +1095,6 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
   hipStreamDestroy(s);
   s = nullptr;
   SFM_TRY(make_ctx(m, &m->ctx0));
-  m->hbm_bytes += m->ctx0->hbm_bytes;
 #undef SFM_TRY
 #undef MAP_HIP
   *out = reinterpret_cast<sfmloc_map *>(m);
@@ -1105,7 +1109,7 @@ int sfmloc_map_get_info(const sfmloc_map *map, sfmloc_map_info *info) {
   info->n_rows = m->n_rows;
   info->n_views = m->n_views;
   info->n_landmarks = m->n_landmarks;
-  info->hbm_bytes = m->hbm_bytes;
+  info->hbm_bytes = map_hbm_bytes(m);
   info->device = m->device;
   return SFMLOC_OK;
 }
@@ -1118,7 +1122,6 @@ int sfmloc_context_create(sfmloc_map *map, sfmloc_context **out) {
   int rc = make_ctx(m, &c);
   if (rc) return rc;
   m->pool.push_back(c);
-  m->hbm_bytes += c->hbm_bytes;
   *out = reinterpret_cast<sfmloc_context *>(c);
   return SFMLOC_OK;
 }
@@ -1133,7 +1136,6 @@ int sfmloc_context_create_sharing(sfmloc_map *map, sfmloc_context *lender, sfmlo
   int rc = make_ctx(m, &c, l);
   if (rc) return rc;
   m->pool.push_back(c);
-  m->hbm_bytes += c->hbm_bytes;
   *out = reinterpret_cast<sfmloc_context *>(c);
   return SFMLOC_OK;
 }
@@ -1148,7 +1150,6 @@ int sfmloc_context_create_merge(sfmloc_map *map, sfmloc_context *lender, sfmloc_
   int rc = make_ctx(m, &c, l, /*merge_only=*/true);
   if (rc) return rc;
   m->pool.push_back(c);
-  m->hbm_bytes += c->hbm_bytes;
   *out = reinterpret_cast<sfmloc_context *>(c);
   return SFMLOC_OK;
 }
@@ -1163,7 +1164,6 @@ void sfmloc_context_destroy(sfmloc_context *ctx) {
   if (it != m->pool.end()) m->pool.erase(it);
   auto ib = std::find(m->batch_ctx.begin(), m->batch_ctx.end(), c);
   if (ib != m->batch_ctx.end()) m->batch_ctx.erase(ib);
-  m->hbm_bytes -= c->hbm_bytes;
   free_ctx(c);
 }
 
@@ -1186,7 +1186,7 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
   hipError_t e = hipSuccess;
   hipStream_t s = m->ctx0->stream;
   if (n_pad) {
-    e = hipMalloc((void **)&q->d_desc, n_pad * 64);
+    e = query_array(q->d_desc, n_pad * 4);
     if (e == hipSuccess) e = hipMemsetAsync(q->d_desc, 0, n_pad * 64, s);
     if (e == hipSuccess) e = hipMemcpyAsync(q->d_desc, desc, (size_t)n * 64, hipMemcpyHostToDevice, s);
     std::vector<float> k6;
@@ -1196,13 +1196,9 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
       // (6 significant digits, AKAZEOpenCV.cpp:80-81) and the F-matrix filter reads them back through
       // Regions::Load (:106-111); pt2D keeps the unrounded values (:77-79).  Reproduce the round trip.
       k6.resize(2 * (size_t)n);
-      char buf[64];
-      for (size_t i = 0; i < 2 * (size_t)n; ++i) {
-        snprintf(buf, sizeof(buf), "%.6g", (double)kpt_xy[i]);
-        k6[i] = strtof(buf, nullptr);
-      }
-      e = hipMalloc((void **)&q->d_kpt, (size_t)n * sizeof(float2));
-      if (e == hipSuccess) e = hipMalloc((void **)&q->d_kpt6, (size_t)n * sizeof(float2));
+      sfmloc_feat_round_trip(kpt_xy, 2 * (uint64_t)n, k6.data());
+      e = query_array(q->d_kpt, n);
+      if (e == hipSuccess) e = query_array(q->d_kpt6, n);
       if (e == hipSuccess) e = hipMemcpyAsync(q->d_kpt, kpt_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
       if (e == hipSuccess)
         e = hipMemcpyAsync(q->d_kpt6, k6.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
@@ -1211,10 +1207,7 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
   }
   if (e != hipSuccess) {
     set_error("sfmloc_query_create: %s", hipGetErrorString(e));
-    if (q->d_desc) hipFree(q->d_desc);
-    if (q->d_kpt) hipFree(q->d_kpt);
-    if (q->d_kpt6) hipFree(q->d_kpt6);
-    delete q;
+    delete q;  // (with the arrays it owns)
     return e == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
   }
   *out = reinterpret_cast<sfmloc_query *>(q);
@@ -1223,7 +1216,7 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
 
 void sfmloc_feat_round_trip(const float *kpt_xy, uint64_t n_values, float *out) {
   char buf[64];
-  for (uint64_t i = 0; i < n_values; ++i) {  // (the same two lines as in sfmloc_query_create)
+  for (uint64_t i = 0; i < n_values; ++i) {
     snprintf(buf, sizeof(buf), "%.6g", (double)kpt_xy[i]);
     out[i] = strtof(buf, nullptr);
   }
@@ -1246,10 +1239,10 @@ int sfmloc_query_create_view(sfmloc_map *map, const void *desc_dev, const void *
   q->width = width;
   q->height = height;
   q->is_view = true;
-  q->d_desc = reinterpret_cast<uint4 *>(const_cast<void *>(desc_dev));
-  q->d_kpt = reinterpret_cast<float2 *>(const_cast<void *>(kpt_dev));
-  q->d_kpt6 = reinterpret_cast<float2 *>(const_cast<void *>(kpt6_dev));
-  q->d_bow = reinterpret_cast<float *>(const_cast<void *>(bow_dev));
+  q->d_desc.borrow(desc_dev);  // (the caller's arrays: never freed here)
+  q->d_kpt.borrow(kpt_dev);
+  q->d_kpt6.borrow(kpt6_dev);
+  q->d_bow.borrow(bow_dev);
   *out = reinterpret_cast<sfmloc_query *>(q);
   return SFMLOC_OK;
 }
@@ -1269,13 +1262,7 @@ void sfmloc_query_destroy(sfmloc_query *query) {
         if (c->last_query == q) c->last_query = nullptr;
       }
   }
-  if (!q->is_view) {  // (a view's arrays are the caller's)
-    if (q->d_desc) hipFree(q->d_desc);
-    if (q->d_kpt) hipFree(q->d_kpt);
-    if (q->d_kpt6) hipFree(q->d_kpt6);
-    if (q->d_bow) hipFree(q->d_bow);
-  }
-  delete q;
+  delete q;  // (frees the arrays it owns; a view's are borrowed)
 }
 
 int sfmloc_query_set_bow(sfmloc_query *query, const float *query_bow) {
@@ -1285,7 +1272,7 @@ int sfmloc_query_set_bow(sfmloc_query *query, const float *query_bow) {
   SFM_CHECK(m && m->bow_dim > 0, SFMLOC_EINVAL, "sfmloc_query_set_bow: the map has no .bow vectors");
   SFM_CHECK(!q->is_view, SFMLOC_EINVAL, "sfmloc_query_set_bow: a view's BoW vector is given to sfmloc_query_create_view");
   SFM_HIP(hipSetDevice(m->device));
-  if (!q->d_bow) SFM_HIP(hipMalloc((void **)&q->d_bow, (size_t)m->bow_dim * sizeof(float)));
+  if (!q->d_bow) SFM_HIP(query_array(q->d_bow, m->bow_dim));
   SFM_HIP(hipMemcpy(q->d_bow, query_bow, (size_t)m->bow_dim * sizeof(float), hipMemcpyHostToDevice));
   return SFMLOC_OK;
 }
@@ -1862,7 +1849,6 @@ int sfmloc_localize_batch(sfmloc_map *map, sfmloc_query *const *queries, uint32_
     if (rc) return rc;
     m->pool.push_back(c);
     m->batch_ctx.push_back(c);
-    m->hbm_bytes += c->hbm_bytes;
   }
   int first_err = SFMLOC_OK;
   auto finish = [&](uint32_t i) {
@@ -1971,19 +1957,18 @@ int sfmloc_bof_create(const sfmloc_bof_desc *d, int device, sfmloc_bof **out) {
   b->norm_type = d->norm_type;
   b->cells = 0;
   for (int l = 0; l < b->levels; ++l) b->cells += (l == 0) ? 1 : (l == 2 ? 3 : (l + 1) * (l + 1));
-  uint64_t acct = 0;
   int rc = SFMLOC_OK;
   // (the model's own stream is created by the first sfmloc_bof_compute: a model inside a sfmloc_imgbow works on that
   // object's stream and needs none -- an idle stream still shares a hardware queue with streams that work; the uploads
   // here go through the null stream)
-  if (!rc) rc = dev_upload(&acct, &b->d_centers, d->centers, (size_t)d->K * b->cdim, b->stream);
+  if (!rc) rc = bof_upload(&b->d_centers, d->centers, (size_t)d->K * b->cdim, b->stream);
   if (!rc && d->n_pca > 0) {
-    rc = dev_upload(&acct, &b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, b->stream);
-    if (!rc) rc = dev_upload(&acct, &b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, b->stream);
-    if (!rc) rc = dev_upload(&acct, &b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, b->stream);
+    rc = bof_upload(&b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, b->stream);
+    if (!rc) rc = bof_upload(&b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, b->stream);
+    if (!rc) rc = bof_upload(&b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, b->stream);
   }
-  if (!rc) rc = dev_alloc(&acct, &b->d_counts, (size_t)b->K * b->cells);
-  if (!rc) rc = dev_alloc(&acct, &b->d_out, (size_t)b->K * b->cells);
+  if (!rc) rc = bof_upload(&b->d_counts, (const uint32_t *)nullptr, (size_t)b->K * b->cells, b->stream);
+  if (!rc) rc = bof_upload(&b->d_out, (const double *)nullptr, (size_t)b->K * b->cells, b->stream);
   if (!rc && hipStreamSynchronize(b->stream) != hipSuccess) rc = SFMLOC_EHIP;
   if (rc) {
     sfmloc_bof_destroy(reinterpret_cast<sfmloc_bof *>(b));

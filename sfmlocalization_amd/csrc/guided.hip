@@ -169,14 +169,11 @@ __global__ __launch_bounds__(256) void k_guided_compact(const uint32_t *__restri
 int ensure_guided_workspace(Ctx *c) {
   if (c->d_geo_j && c->d_guided_row) return SFMLOC_OK;
   const size_t n = c->map->n_rows ? (size_t)c->map->n_rows : 1;
-  if (!c->d_geo_j) {
-    SFM_HIP(hipMalloc((void **)&c->d_geo_j, n * sizeof(uint32_t)));
-    c->hbm_bytes += n * sizeof(uint32_t);
-  }
-  if (!c->d_guided_row) {
-    SFM_HIP(hipMalloc((void **)&c->d_guided_row, n * sizeof(uint32_t)));
-    c->hbm_bytes += n * sizeof(uint32_t);
-  }
+  DevGroup g(&c->hbm_bytes);
+  g.add(c->d_geo_j, n);
+  g.add(c->d_guided_row, n);
+  if (!g.ok()) return g.rc();
+  g.commit();
   return SFMLOC_OK;
 }
 

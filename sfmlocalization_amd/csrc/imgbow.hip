@@ -194,7 +194,7 @@ int sfmloc_imgbow_compute(sfmloc_imgbow *p, const uint8_t *image, sfmloc_query *
     SFM_CHECK(q->map->device == ib->device, SFMLOC_EINVAL, "sfmloc_imgbow_compute: query and extractor on different devices");
   }
   SFM_HIP(hipSetDevice(ib->device));
-  if (q && !q->d_bow) SFM_HIP(hipMalloc((void **)&q->d_bow, dim * sizeof(float)));  // (once per query object)
+  if (q && !q->d_bow) SFM_HIP(query_array(q->d_bow, dim));  // (once per query object)
   Akaze *a = reinterpret_cast<Akaze *>(ib->ak);
   const size_t n_src = (size_t)ib->w * ib->h * ib->channels;
   // the staging buffer is free once the previous call's upload has left it

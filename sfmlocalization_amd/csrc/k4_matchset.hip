@@ -375,7 +375,7 @@ int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32
                           c->d_match_key, c->d_geo_count, c->d_geo_idx, gj, m->d_row_landmark, m->d_landmark_id,
                           m->d_landmark_X, c->d_best64, c->d_geo_dist,
                           reinterpret_cast<Candidate *>(c->d_cand_part + kPartHeaderBytes), c->cand_cap,
-                          reinterpret_cast<uint32_t *>(c->d_cand_part), c->d_status);
+                          reinterpret_cast<uint32_t *>(c->d_cand_part.get()), c->d_status);
   SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }

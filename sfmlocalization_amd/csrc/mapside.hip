@@ -112,7 +112,7 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
   hipError_t e = hipSuccess;
   hipStream_t s = m->ctx0->stream;
   if (n_pad) {
-    e = hipMalloc((void **)&q->d_desc, (size_t)n_pad * 64);
+    e = query_array(q->d_desc, (size_t)n_pad * 4);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_untile_view, dim3((n_pad * 4 + 255) / 256), dim3(256), 0, s, m->d_bank, r0, n, n_pad,
                          q->d_desc);
@@ -120,8 +120,8 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
     }
     if (e == hipSuccess && m->d_kpt) {
       // the map's keypoints are the .feat values already (6 significant digits), for both uses
-      e = hipMalloc((void **)&q->d_kpt, (size_t)n * sizeof(float2));
-      if (e == hipSuccess) e = hipMalloc((void **)&q->d_kpt6, (size_t)n * sizeof(float2));
+      e = query_array(q->d_kpt, n);
+      if (e == hipSuccess) e = query_array(q->d_kpt6, n);
       if (e == hipSuccess)
         e = hipMemcpyAsync(q->d_kpt, m->d_kpt + r0, (size_t)n * sizeof(float2), hipMemcpyDeviceToDevice, s);
       if (e == hipSuccess)
@@ -131,22 +131,11 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
   }
   if (e != hipSuccess) {
     set_error("sfmloc_query_from_view: %s", hipGetErrorString(e));
-    if (q->d_desc) hipFree(q->d_desc);
-    if (q->d_kpt) hipFree(q->d_kpt);
-    if (q->d_kpt6) hipFree(q->d_kpt6);
-    delete q;
+    delete q;  // (with the arrays it owns)
     return e == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
   }
   *out = q;
   return SFMLOC_OK;
-}
-
-void free_query(Query *q) {
-  if (!q) return;
-  if (q->d_desc) hipFree(q->d_desc);
-  if (q->d_kpt) hipFree(q->d_kpt);
-  if (q->d_kpt6) hipFree(q->d_kpt6);
-  delete q;
 }
 
 // K1 + K2 + the one-to-one filter of every selected view (ascending indices) against q, on the map's own context
@@ -260,7 +249,7 @@ int sfmloc_match_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pairs,
     }
     hipStreamSynchronize(m->ctx0->stream);
     if (m->ctx0->last_query == q) m->ctx0->last_query = nullptr;
-    free_query(q);
+    delete q;
     if (rc) return rc;
   }
   Matches *M = flatten(pm);
@@ -291,7 +280,7 @@ int sfmloc_track(sfmloc_map *map, uint32_t max_frame_dist, sfmloc_matches **out)
       if (rc == SFMLOC_OK) rc = read_view_list(m, f, &mi, &mj);
       hipStreamSynchronize(m->ctx0->stream);
       if (m->ctx0->last_query == q) m->ctx0->last_query = nullptr;
-      free_query(q);
+      delete q;
       if (rc) return rc;
       pm[{f, f + 1}] = {std::move(mi), std::move(mj)};
     }
@@ -427,7 +416,7 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
     int status = 0;
     hipMemcpy(&status, c->d_status, sizeof(int), hipMemcpyDeviceToHost);
     if (c->last_query == q) c->last_query = nullptr;
-    free_query(q);
+    delete q;
     if (rc) return rc;
     SFM_CHECK((status & 1) == 0, SFMLOC_ECAP, "a pair has more than 65536 putative matches");
   }

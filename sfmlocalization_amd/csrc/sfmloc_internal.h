@@ -12,6 +12,7 @@
 
 #include "../../include/sfmloc.h"
 #include "chain_device.h"
+#include "devmem.h"
 #include "forms.h"
 #include "gang.h"
 
@@ -153,26 +154,26 @@ struct Map {
   std::vector<uint32_t> h_view_id, h_view_off, h_view_wh;
   std::vector<double> h_view_center;     // [n_views*3], maps opened from sfm_data.json only
   std::vector<std::string> h_view_file;  // view filenames, same
-  uint4 *d_bank = nullptr;         // tiled64, n_blocks*64 rows (zero padded)
+  DevBuf<uint4> d_bank;  // tiled64, n_blocks*64 rows (zero padded)
   // The view tables carry one extra, EMPTY view at index n_views ("phantom": no rows, id 0xFFFFFF): a device-built
   // selection whose length the host cannot know (the sharded BoW shortlist) is padded with it, and every kernel
   // treats it as a view without descriptors.  Per-view arrays of a context are sized n_views + 1 for the same reason.
-  uint32_t *d_view_off = nullptr;  // [n_views+2]  (view_off[n_views+1] = view_off[n_views] = n_rows)
-  uint32_t *d_view_id = nullptr;   // [n_views+1]
-  uint32_t *d_view_wh = nullptr;   // [(n_views+1)*2]
-  float2 *d_kpt = nullptr;         // [n_rows]
-  int32_t *d_row_landmark = nullptr;
-  uint32_t *d_landmark_id = nullptr;
-  double *d_landmark_X = nullptr;
+  DevBuf<uint32_t> d_view_off;  // [n_views+2]  (view_off[n_views+1] = view_off[n_views] = n_rows)
+  DevBuf<uint32_t> d_view_id;  // [n_views+1]
+  DevBuf<uint32_t> d_view_wh;  // [(n_views+1)*2]
+  DevBuf<float2> d_kpt;  // [n_rows]
+  DevBuf<int32_t> d_row_landmark;
+  DevBuf<uint32_t> d_landmark_id;
+  DevBuf<double> d_landmark_X;
   double focal = 0, ppx = 0, ppy = 0, k1 = 0, k2 = 0, k3 = 0;
   uint32_t intrinsic_type = 0;  // 0 pinhole, 3 pinhole_radial_k3
   uint32_t bow_dim = 0;
-  float *d_bow = nullptr;
-  double *d_L10 = nullptr;          // [65538] log10(i)
-  uint16_t *d_ratio_cnt = nullptr;  // [513]
+  DevBuf<float> d_bow;
+  DevBuf<double> d_L10;  // [65538] log10(i)
+  DevBuf<uint16_t> d_ratio_cnt;  // [513]
   float ratio_cnt_for = -1.0f;      // ratio the table was built for
   bool have_geometry = false;       // kpts + landmarks + view sizes + intrinsic were supplied
-  uint64_t hbm_bytes = 0;
+  uint64_t hbm_bytes = 0;  // what the map's own buffers above hold (its contexts keep their own figure: map_hbm_bytes)
 
   Ctx *ctx0 = nullptr;              // the handle's own context (stage-level API)
   std::vector<Ctx *> pool;          // every other context of this map (owned by the map)
@@ -189,72 +190,72 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   bool merge_only = false;         // no workspace of the matching stages (sfmloc_context_create_merge)
   int borrowers = 0;               // contexts working on this one's stream
   bool zombie = false;             // destroyed while lent out: freed with its last borrower
-  uint64_t hbm_bytes = 0;
+  uint64_t hbm_bytes = 0;          // what the buffers below hold now (every DevBuf of the context is charged to it)
 
   // --- putative stage ---
   uint32_t max_split = 8;
-  uint2 *d_part = nullptr;          // [n_blocks*64] partial (best0,best1), laid out [split][work block][lane]
-  uint32_t *d_view_sel = nullptr;   // [n_views] selected view indices
-  uint32_t *d_view_widx0 = nullptr; // [n_views] work-block index of each selected view's first bank block
-  uint32_t *d_block_list = nullptr; // [n_blocks]
+  DevBuf<uint2> d_part;  // [n_blocks*64] partial (best0,best1), laid out [split][work block][lane]
+  DevBuf<uint32_t> d_view_sel;  // [n_views] selected view indices
+  DevBuf<uint32_t> d_view_widx0;  // [n_views] work-block index of each selected view's first bank block
+  DevBuf<uint32_t> d_block_list;  // [n_blocks]
   uint32_t *h_pinned = nullptr;     // pinned staging: view_sel | view_widx0 | block_list
-  uint32_t *d_view_count = nullptr; // [n_views]
-  uint32_t *d_match_i = nullptr;    // [n_rows]
-  uint32_t *d_match_key = nullptr;  // [n_rows]  (d0<<16)|j0
-  uint2 *d_flagged = nullptr;       // [n_blocks*64] rows the screening kernel could not reject {part index, bank row}
-  uint32_t *d_n_flagged = nullptr;
-  unsigned long long *d_flagmask = nullptr;  // [n_blocks] per work block: rows whose d_part slot is valid (screened scan)
+  DevBuf<uint32_t> d_view_count;  // [n_views]
+  DevBuf<uint32_t> d_match_i;  // [n_rows]
+  DevBuf<uint32_t> d_match_key;  // [n_rows]  (d0<<16)|j0
+  DevBuf<uint2> d_flagged;  // [n_blocks*64] rows the screening kernel could not reject {part index, bank row}
+  DevBuf<uint32_t> d_n_flagged;
+  DevBuf<unsigned long long> d_flagmask;  // [n_blocks] per work block: rows whose d_part slot is valid (screened scan)
   bool last_screened = false;
-  uint2 *d_rows_scratch = nullptr;      // [rows_chunk_cap][8 slices][64] partial top-2 of the flagged-row pass
-  uint32_t *d_rows_arrivals = nullptr;  // [rows_chunk_cap] arrival counters of that pass (self-resetting)
-  uint4 *d_flagged_desc = nullptr;      // [rows_chunk_cap][4][64] descriptors of the flagged rows (tiled like the bank)
+  DevBuf<uint2> d_rows_scratch;  // [rows_chunk_cap][8 slices][64] partial top-2 of the flagged-row pass
+  DevBuf<uint32_t> d_rows_arrivals;  // [rows_chunk_cap] arrival counters of that pass (self-resetting)
+  DevBuf<uint4> d_flagged_desc;  // [rows_chunk_cap][4][64] descriptors of the flagged rows (tiled like the bank)
   uint32_t rows_chunk_cap = 0;          // chunks of 64 flagged rows the sliced pass has scratch for (rest: fallback)
   // [kK1CounterSlots][2] finished wave-pairs, flagged rows (since stats reset): a wave adds to slot (its block & 63) -- one
   // pair of words for every wave of a scan was 300 000 atomics on the same address per full-bank scan
-  unsigned long long *d_k1_counters = nullptr;
+  DevBuf<unsigned long long> d_k1_counters;
   int k1_finish_ops = 0;
 
   // --- geometric stages ---
-  uint32_t *d_geo_count = nullptr;  // [n_views]
-  uint32_t *d_geo_idx = nullptr;    // [n_rows]
-  double *d_geo_model = nullptr;    // [(n_views+1)*10] per view: AC-RANSAC's F (normalised frame, 9) + errorMax
+  DevBuf<uint32_t> d_geo_count;  // [n_views]
+  DevBuf<uint32_t> d_geo_idx;  // [n_rows]
+  DevBuf<double> d_geo_model;  // [(n_views+1)*10] per view: AC-RANSAC's F (normalised frame, 9) + errorMax
   // guided matching (-gm): allocated on first use
-  uint32_t *d_geo_j = nullptr;        // [n_rows] query feature of each guided match (geo_idx then holds the map feature)
-  uint32_t *d_guided_row = nullptr;   // [n_rows] per bank row: its guided query feature or SFMLOC_NOMATCH
+  DevBuf<uint32_t> d_geo_j;  // [n_rows] query feature of each guided match (geo_idx then holds the map feature)
+  DevBuf<uint32_t> d_guided_row;  // [n_rows] per bank row: its guided query feature or SFMLOC_NOMATCH
   bool geo_is_pairs = false;          // the last geometric stage left (i, j) lists, not indices into the putative lists
   // K3 for views with more putative matches than its LDS form holds (acransac.hip k_fmatrix_large): allocated on first use
-  uint64_t *fl_key = nullptr;
-  uint32_t *fl_idx = nullptr, *fl_count = nullptr, *fl_list = nullptr;
-  void *d_k3_static = nullptr;          // K3's per-context argument block on the device (FFilterStatic, acransac.hip) ...
+  DevBuf<uint64_t> fl_key;
+  DevBuf<uint32_t> fl_idx, fl_count, fl_list;
+  DevBuf<unsigned char> d_k3_static;  // K3's per-context argument block on the device (FFilterStatic, acransac.hip) ...
   unsigned char k3_static_host[256] = {};  // ... and what was last written there
   bool k3_static_valid = false;
-  void *d_k3_spec = nullptr;            // k_fmatrix_fast's wide form: the first batch's results per view slot (lazily)
-  unsigned int *d_k3_arrive = nullptr;  // ... and the arrivals
-  int32_t *fl_vec_index = nullptr, *fl_best_inl = nullptr;
-  float *fl_logc_n = nullptr, *fl_logc_k = nullptr;
+  DevBuf<unsigned char> d_k3_spec;  // k_fmatrix_fast's wide form: the first batch's K3Spec results per view slot (lazily)
+  DevBuf<unsigned int> d_k3_arrive;  // ... and the arrivals
+  DevBuf<int32_t> fl_vec_index, fl_best_inl;
+  DevBuf<float> fl_logc_n, fl_logc_k;
   int fl_slot_m = 0;
-  int *d_status = nullptr;
-  unsigned char *d_cand_part = nullptr;  // this context's candidate part: header + cand_cap candidates (one per query
-                                         // feature at most, so 2^16 can never overflow)
+  int *d_status = nullptr;  // (raw: inside d_result)
+  DevBuf<unsigned char> d_cand_part;  // this context's candidate part: header + cand_cap candidates (one per query
+                                      // feature at most, so 2^16 can never overflow)
   uint32_t cand_cap = 1u << 16;
-  uint16_t *d_geo_dist = nullptr;        // [n_rows] per geometric match: its featDist, or 0xFFFF = not a candidate
-  unsigned long long *d_best64 = nullptr;  // [65536]
-  uint32_t *d_winner = nullptr;            // [65536]
-  uint32_t *d_ms_n = nullptr, *d_ms_qfeat = nullptr, *d_ms_landmark = nullptr;  // [65536]
-  double *d_pt2d = nullptr, *d_pt3d = nullptr;                                  // [65536*2], [65536*3]
-  double *d_xn = nullptr;                                                       // [kP3pMaxN*2]
-  float *d_logc_n = nullptr, *d_logc_k = nullptr;                               // [kP3pMaxN+1]
-  int32_t *d_vec_index = nullptr, *d_best_inl = nullptr;                        // [kP3pMaxN]
-  double *d_hyp_nfa = nullptr, *d_hyp_err = nullptr, *d_hyp_model = nullptr, *d_prep_models = nullptr;
-  int *d_prep_nm = nullptr;
-  int *d_hyp_k = nullptr;
-  int32_t *d_hyp_inl = nullptr;  // [kP3pBatchMax * kP3pMaxN]
-  uint32_t *d_pair_qfeat = nullptr, *d_pair_landmark = nullptr, *d_inlier_idx = nullptr;  // [p3p_cap]
+  DevBuf<uint16_t> d_geo_dist;  // [n_rows] per geometric match: its featDist, or 0xFFFF = not a candidate
+  DevBuf<unsigned long long> d_best64;  // [65536]
+  DevBuf<uint32_t> d_winner;  // [65536]
+  DevBuf<uint32_t> d_ms_n, d_ms_qfeat, d_ms_landmark;  // [65536]
+  DevBuf<double> d_pt2d, d_pt3d;  // [65536*2], [65536*3]
+  DevBuf<double> d_xn;  // [kP3pMaxN*2]
+  DevBuf<float> d_logc_n, d_logc_k;  // [kP3pMaxN+1]
+  DevBuf<int32_t> d_vec_index, d_best_inl;  // [kP3pMaxN]
+  DevBuf<double> d_hyp_nfa, d_hyp_err, d_hyp_model, d_prep_models;
+  DevBuf<int> d_prep_nm;
+  DevBuf<int> d_hyp_k;
+  DevBuf<int32_t> d_hyp_inl;  // [kP3pBatchMax * kP3pMaxN]
+  uint32_t *d_pair_qfeat = nullptr, *d_pair_landmark = nullptr;  // [p3p_cap] raw: inside d_result, or the *_big arrays
+  DevBuf<uint32_t> d_inlier_idx;  // [p3p_cap]
   // the P3P arrays hold p3p_cap correspondences: kP3pMaxN to begin with, regrown (ctx_p3p_reserve) when a query with
   // more features arrives; beyond kP3pMaxN the pair lists leave HostResult for buffers of their own and the sort of a
   // hypothesis gets a global-memory segment
   uint32_t p3p_cap = kP3pMaxN;
-  uint64_t p3p_bytes = 0;  // bytes of the regrowable P3P arrays currently held (part of hbm_bytes)
   bool p3p_small = false;  // this query's P3P rounds go out in the small form (decided when the first ones are queued)
   uint32_t p3p_query_n = 0;  // features of the query K5 is about to run for (ctx_p3p_reserve): launch shape of the rounds
   uint32_t p3p_stream = 0;   // K5's sampling stream (Philox key): 0 for queries; the view id when adjust.hip resects a view
@@ -262,18 +263,20 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   double p3p_K[3] = {0.0, 0.0, 0.0};
   bool p3p_uncal = false;    // the query K5 is about to run for is uncalibrated (Query::uncalibrated): six-point resection
   double p3p_N[3] = {1.0, 0.0, 0.0};  // ... normalised by N1 of its image: {sqrt(w h), w / 2, h / 2}
-  uint32_t *d_pair_qfeat_big = nullptr, *d_pair_landmark_big = nullptr;
-  uint64_t *d_p3p_ws_key = nullptr;
-  uint32_t *d_p3p_ws_idx = nullptr;
-  double *d_p3p_terms = nullptr;
-  P3pState *d_p3p_state = nullptr;
+  DevBuf<uint32_t> d_pair_qfeat_big, d_pair_landmark_big;
+  DevBuf<uint64_t> d_p3p_ws_key;
+  DevBuf<uint32_t> d_p3p_ws_idx;
+  DevBuf<double> d_p3p_terms;
+  P3pState *d_p3p_state = nullptr;  // (raw: inside d_result)
   Pose *d_pose = nullptr;
-  unsigned char *d_result = nullptr;  // one HostResult record; the six pointers below alias into it
-  uint32_t *d_view_stats = nullptr;  // [3] HostResult::view_stats
-  float *d_bow_query = nullptr;      // [bow_dim]
-  uint32_t *d_bow_dist = nullptr;    // [n_views]
-  uint32_t *d_bow_cand = nullptr;    // [n_views]
-  uint32_t *d_bow_sel = nullptr;     // [n_views]
+  // one HostResult record; d_p3p_state, d_pose, d_status, d_view_stats (and, up to kP3pMaxN correspondences, d_pair_qfeat /
+  // d_pair_landmark) are raw pointers into it
+  DevBuf<unsigned char> d_result;
+  uint32_t *d_view_stats = nullptr;  // [3] HostResult::view_stats (raw: inside d_result)
+  DevBuf<float> d_bow_query;  // [bow_dim]
+  DevBuf<uint32_t> d_bow_dist;  // [n_views]
+  DevBuf<uint32_t> d_bow_cand;  // [n_views]
+  DevBuf<uint32_t> d_bow_sel;  // [n_views]
   void *h_result = nullptr;  // pinned: what a finished query copies back in one go (capi.hip HostResult)
   hipEvent_t pinned_busy = nullptr;  // recorded after the last upload out of h_pinned
   hipEvent_t xev_out = nullptr, xev_in = nullptr;  // ordering against a caller's stream (sfmloc_context_signal / _wait)
@@ -352,14 +355,21 @@ __attribute__((visibility("hidden"))) P3pArgs make_p3p_args(Ctx *c, const K5In &
 struct Query {
   Map *map = nullptr;
   uint32_t n = 0, width = 0, height = 0;
-  uint4 *d_desc = nullptr;  // [n_pad*4], row major, zero padded to a multiple of 64 rows
-  float2 *d_kpt = nullptr;   // full precision (locFeat, AKAZEOpenCV.cpp:77-79): used for pt2D
-  float2 *d_kpt6 = nullptr;  // after the .feat text round trip (6 significant digits): used by the F-matrix filter
-  float *d_bow = nullptr;    // the query's BoW vector, resident (sfmloc_query_set_bow), [bow_dim] or null
+  DevBuf<uint4> d_desc;  // [n_pad*4], row major, zero padded to a multiple of 64 rows
+  DevBuf<float2> d_kpt;  // full precision (locFeat, AKAZEOpenCV.cpp:77-79): used for pt2D
+  DevBuf<float2> d_kpt6;  // after the .feat text round trip (6 significant digits): used by the F-matrix filter
+  DevBuf<float> d_bow;  // the query's BoW vector, resident (sfmloc_query_set_bow), [bow_dim] or null
   std::vector<float> h_kpt;
-  bool is_view = false;  // the device arrays belong to the caller (sfmloc_query_create_view)
+  bool is_view = false;  // the device arrays are borrowed from the caller (sfmloc_query_create_view)
   bool uncalibrated = false;  // sfmloc_query_set_uncalibrated: no intrinsic is assumed for this query's camera
 };
+
+// one of a query's own arrays (not part of any memory figure), for the hipError_t chains of the functions that fill them
+hipError_t dev_raw_alloc_error();  // capi.hip: what hipMalloc answered to this thread's last dev_raw_alloc
+template <class T>
+inline hipError_t query_array(DevBuf<T> &b, size_t n) {
+  return b.alloc(nullptr, n) == SFMLOC_OK ? hipSuccess : dev_raw_alloc_error();
+}
 
 // What ONE entry-point call has decided or already done for its query: created on the entry point's stack and passed
 // down to the stages and launchers that act on it, so nothing of it outlives the call.  The staged entry points, which

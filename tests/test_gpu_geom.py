@@ -541,6 +541,32 @@ def test_guided_matching_in_the_query_path(oracle_c):
         dm.close()
 
 
+def test_map_memory_figure_counts_lazy_buffers_and_returns_with_the_context():
+    """sfmloc_map_info::hbm_bytes is the map's own buffers plus what each of its contexts holds NOW: the two per-row
+    arrays guided matching makes on a context's first query (4 bytes per bank row each) are in it, and closing the context
+    gives back exactly what the context held -- the figure before the context existed, twice in a row.  (While the
+    figure was kept by hand the lazy arrays were subtracted at the close without ever having been added: it ended below
+    its starting value and, being unsigned, would wrap.)"""
+    m = make_scene(61)
+    dm = dev_map(m, guided_matching=1)
+    q = synth.make_query(m, 640, n_feat=700, n_copies=230, outlier_frac=0.3, place=0)
+    dq = dm.query(q.desc, q.kpt_xy, q.width, q.height)
+    b0 = dm.info()["hbm_bytes"]
+    for _ in range(2):
+        ctx = dm.context()
+        b_created = dm.info()["hbm_bytes"]
+        assert b_created > b0
+        ctx.begin(dq)
+        ctx.end()
+        b_used = dm.info()["hbm_bytes"]
+        print("hbm_bytes: before", b0, "context created", b_created, "after its first query", b_used)
+        assert b_used - b_created >= 2 * 4 * int(m.view_off[-1])     # d_geo_j + d_guided_row, one word per bank row each
+        ctx.close()
+        assert dm.info()["hbm_bytes"] == b0
+    dq.close()
+    dm.close()
+
+
 def test_sharded_map_equals_unsharded(oracle_c):
     """Two shards of one map on one GPU: parts exported by sfmloc_shard_begin/_export, concatenated as the
     all-gather would, merged by sfmloc_merge_begin -> exactly the unsharded sfmloc_localize result; the exported
