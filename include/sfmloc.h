@@ -787,6 +787,66 @@ int sfmloc_sfm_adjust(sfmloc_sfm *h, uint32_t what, sfmloc_ba_report *rep);
 int sfmloc_sfm_read_structure(sfmloc_sfm *h, double *X /*[n_landmarks*3]*/);
 
 /* ------------------------------------------------------------------------- */
+/* The joint commands of OpenMVG_BA -c (rs, rst, rsti, anything with i; adjust_sfm_data.cpp:158-244): poses,           */
+/* intrinsics and structure in one problem with one trust region, as Bundle_Adjustment_Ceres::Adjust solves it          */
+/* (ITERATIVE_SCHUR, SCHUR_JACOBI; adjust_sfm_data.cpp:175-176).  A new entry point: sfmloc_sfm_adjust keeps refusing  */
+/* these commands.  The readings "blocks", "residual", "loss", "entering" and "order" of the separable block above     */
+/* carry over word for word (the intrinsics are constants only where the command does not name i).  Added readings:    */
+/*   parameters  reading chosen, unpinned: a pose contributes 3 free values for r or t and 6 for rt (r holds t, t      */
+/*               holds R's bits).  An intrinsic is free under i: {f, ppx, ppy} for pinhole, plus {k1, k2, k3} for       */
+/*               pinhole_radial_k3 (OpenMVG's ADJUST_ALL).  A landmark contributes X under s.  Views that share an      */
+/*               id_pose share one block; views that share an id_intrinsic share one block.  A pose, an intrinsic or a  */
+/*               landmark no entering observation refers to keeps its bits, and so does everything the command does    */
+/*               not name.                                                                                              */
+/*   solver      reading chosen, unpinned: one Levenberg-Marquardt loop over the whole problem with one lambda; the    */
+/*               start value 1e-4, D = diag(J^T J) clamped to [1e-6, 1e32], the acceptance ratio 1e-3 and the lambda   */
+/*               update are those of "solver" above; first-order reweighting, no Triggs correction; rotations step as  */
+/*               R <- exp([w]x) R (divergence: Ceres steps in the angle-axis).  With s the landmarks are eliminated    */
+/*               (C_l = Jx^T Jx + lambda D inverted by Cholesky) and the reduced system over poses and intrinsics is    */
+/*               solved by preconditioned conjugate gradients from x = 0, matrix-free through the observations; without */
+/*               s the same PCG runs on Jc^T Jc + lambda D.  The preconditioner is block diagonal, one 6 x 6 block per  */
+/*               pose and per intrinsic: J^T J + lambda D minus the block's own -(J^T Jx) C_l^-1 (Jx^T J) terms, taken  */
+/*               per observation (divergence: SCHUR_JACOBI also has the cross terms of two observations of one          */
+/*               landmark inside one block; they are left out, which weakens the preconditioner and leaves the system   */
+/*               solved unchanged).  (divergence) PCG stops at |r| <= pcg_tolerance |r0| in the Euclidean norm, after   */
+/*               max_pcg iterations, or when p.Ap is not positive; Ceres has its own Q-based test.  The model decrease  */
+/*               is computed from the step actually taken, -(g.d) - |J d|^2 / 2, in one pass over the observations.     */
+/*               A step that does not lower the total cost is never applied; a non-finite step or cost counts as        */
+/*               rejected.  No gauge fixing (neither OpenMVG 1.1 nor the reference fixes one): the damping carries the  */
+/*               7-dimensional null space of rst.                                                                       */
+/*   stopping    reading chosen, unpinned: stop 0 after an accepted step with (cost - cost') <= function_tolerance *    */
+/*               cost, or after a rejected one whose positive model decrease is itself <= function_tolerance * cost;    */
+/*               stop 1 after max_steps steps tried; stop 2 when lambda passes 1e32.                                    */
+/*   order       per-pose sums go lane-strided through the in-wave butterfly; per-intrinsic sums and the PCG's scalar   */
+/*               products are written as partials (per view, per block, per workgroup) and summed by a fixed tree:      */
+/*               store, then sum.  No float atomics: two runs give the same bits.                                       */
+/*   after       C = -R^T t for the poses that moved.  sfmloc_sfm_clean, sfmloc_sfm_adjust and further joint calls see  */
+/*               the adjusted intrinsics: a later clean uses them.  sfmloc_sfm_resect has already run and is            */
+/*               unaffected.                                                                                            */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_ba_joint_options {
+  uint32_t max_steps;          /* LM steps tried;      default 50  (Ceres max_num_iterations)                */
+  uint32_t max_pcg;            /* PCG iterations/step; default 500 (Ceres max_linear_solver_iterations)      */
+  double function_tolerance;   /* default 1e-6 (Ceres): stop after an accepted step with
+                                  (cost - cost') <= tol * cost                                              */
+  double pcg_tolerance;        /* default 0.1 (Ceres eta): stop PCG at |r| <= tol * |r0|                    */
+} sfmloc_ba_joint_options;
+typedef struct sfmloc_ba_joint_report {
+  double cost_initial, cost_final;
+  uint32_t n_pose_blocks, n_intrinsic_blocks, n_landmark_blocks;  /* free blocks with an entering observation */
+  uint32_t steps_tried, steps_accepted, pcg_total, pcg_max;
+  uint32_t stop;               /* 0 tolerance met, 1 max_steps, 2 lambda overflow / no model decrease       */
+} sfmloc_ba_joint_report;
+void sfmloc_ba_joint_default_options(sfmloc_ba_joint_options *o);
+/* what: any non-zero combination of the four SFMLOC_BA_ bits (the separable ones too: solved as one joint problem);
+ * any other bit: SFMLOC_EINVAL.  A view of an entering observation without a pose: SFMLOC_EINVAL, the text names the
+ * view.  opt NULL = the defaults; rep may be NULL.  One small read-back per LM step and per chunk of 32 PCG iterations;
+ * no host round trip per PCG iteration. */
+int sfmloc_sfm_adjust_joint(sfmloc_sfm *h, uint32_t what, const sfmloc_ba_joint_options *opt, sfmloc_ba_joint_report *rep);
+/* the intrinsics as they are now: f, ppx, ppy, k1, k2, k3 per intrinsic */
+int sfmloc_sfm_read_intrinsics(sfmloc_sfm *h, double *K /*[n_intrinsics*6]*/);
+
+/* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */
 /* reference runs after every reconstruction and merge): which view each landmark takes its colour from.  The greedy  */
 /* cover runs on the structure exactly as sfmloc_sfm_create received it (the keep masks of sfmloc_sfm_clean and the   */

@@ -2,7 +2,7 @@
 candidate merge (hulo_sfm/sfmMergeGraph.py:297, hulo_bow/sfmMergeGraphBOW.py:226,
 hulo_ibeacon/sfmMergeGraphIBeacon.py:322), and the separable commands of its -c switch.
 
-    python -m sfmlocalization_amd.adjust <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [--device=0]
+    python -m sfmlocalization_amd.adjust <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [-j=0|1] [--device=0]
 
 Every view with more than 10 observations is re-resected on the device, <folder of sfm_data>/sfm_data_b4bd.json is
 written with the new poses and the structure untouched, the structure is cleaned (residual 4 px, angle 2 degrees, the
@@ -18,6 +18,11 @@ four counts.  An item with none of r t i s adjusts nothing.  With a non-empty -c
 commands -- structure together with a pose part (rs, rst, ...) and anything with i -- are not supported yet: every item
 is checked before anything is opened, and one refused item ends the run with status 1 and nothing written.  The
 semantics are stated in include/sfmloc.h.
+
+-j=1 (--joint=1, in any position) opts in to the joint adjustment: no item is refused, an item that would be goes to
+sfmloc_sfm_adjust_joint with the default options (one Levenberg-Marquardt problem over everything the item names), a
+separable item still goes to sfmloc_sfm_adjust (-c=rt,sc -j=1 gives the bytes of -c=rt,sc).  An intrinsic whose bits
+changed is written from the arrays (focal_length, principal_point, disto_k3); sfm_data_b4bd.json keeps the input's.
 """
 import json
 import os
@@ -35,7 +40,9 @@ USAGE = ("Execute bundle adjustment for sfm_data.json\n"
          "t = translation, s = structure, c = clean]. Usage example: c=r,tc,s means BD with rotation only, then BD with "
          "translation follow by cleaning, then BD with structure. Not supported yet: i (intrinsic), and s together "
          "with r or t.\n"
-         "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n")
+         "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n"
+         "\t-j, --joint (value:0)\n\t\tWith 1, run the items that are not supported yet (i, and s together with r or t) as "
+         "one joint bundle adjustment\n")
 
 
 def _u32(v):
@@ -162,7 +169,23 @@ def _bits_differ(a, b):
     return (np.ascontiguousarray(a, np.float64).view(np.uint64) != np.ascontiguousarray(b, np.float64).view(np.uint64))
 
 
-def run(in_path, out_path, rm_unstable=False, device=0, log=print, command=""):
+def _intrinsics(doc, arrays, K):
+    """the document's intrinsics with every entry whose bits changed written from K (f, ppx, ppy, k1, k2, k3)"""
+    out = []
+    for i, e in enumerate(doc["intrinsics"]):
+        if _bits_differ(K[i], arrays["intrinsic"][i]).any():
+            radial = int(arrays["intrinsic_type"][i]) == 3
+            val = e["value"]
+            data = val["ptr_wrapper"]["data"]
+            pin = data["value0"] if radial else data
+            pin = _with(pin, focal_length=float(K[i][0]), principal_point=[float(K[i][1]), float(K[i][2])])
+            data = _with(data, value0=pin, disto_k3=[float(x) for x in K[i][3:]]) if radial else pin
+            e = _with(e, value=_with(val, ptr_wrapper=_with(val["ptr_wrapper"], data=data)))
+        out.append(e)
+    return out
+
+
+def run(in_path, out_path, rm_unstable=False, device=0, log=print, command="", joint=False):
     """The tool's body.  Returns 0, or 1 after an error message on stderr."""
     from . import capi as S
     items = command_items(command)
@@ -202,10 +225,15 @@ def run(in_path, out_path, rm_unstable=False, device=0, log=print, command=""):
             log(f"Number of points after cleanup : {counts[3]}")
         cleaned = False
         for item in items:
-            rot, trn, stru = "r" in item, "t" in item, "s" in item
+            rot, trn, intr, stru = "r" in item, "t" in item, joint and "i" in item, "s" in item
             log("\nBundle adjustment over " + ("rotations, " if rot else "") + ("translations, " if trn else "")
-                + ("structure, " if stru else ""))
-            h.adjust((S.BA_ROTATION if rot else 0) | (S.BA_TRANSLATION if trn else 0) | (S.BA_STRUCTURE if stru else 0))
+                + ("intrinsic params, " if intr else "") + ("structure, " if stru else ""))
+            what = (S.BA_ROTATION if rot else 0) | (S.BA_TRANSLATION if trn else 0) | \
+                (S.BA_INTRINSICS if intr else 0) | (S.BA_STRUCTURE if stru else 0)
+            if joint and refused_item([item]) is not None:
+                h.adjust_joint(what)
+            else:
+                h.adjust(what)
             if "c" in item:
                 clean()
                 cleaned = True
@@ -214,6 +242,7 @@ def run(in_path, out_path, rm_unstable=False, device=0, log=print, command=""):
             cleaned = True
         q = h.read(masks=cleaned)
         X = h.read_structure() if items else None
+        K = h.read_intrinsics() if items and joint else None
     except S.SfmlocError as e:
         print(f"OpenMVG_BA: {e.message}", file=sys.stderr)
         return 1
@@ -237,6 +266,8 @@ def run(in_path, out_path, rm_unstable=False, device=0, log=print, command=""):
             val = _with(val, X=[float(x) for x in X[l]])
         structure.append(_with(e, value=val))
     out = _with(doc, extrinsics=_extrinsics(pose_id, pose_src, q["pose_valid"], p["pose_R"], p["pose_C"], replaced))
+    if K is not None:
+        out["intrinsics"] = _intrinsics(doc, arrays, K)
     if "structure" in doc:
         out["structure"] = structure
     out["control_points"] = []
@@ -249,7 +280,7 @@ def main(argv=None):
     if len(argv) < 1:
         sys.stderr.write(USAGE)
         return 1
-    pos, command, rm_unstable, device = [], "", 0, 0
+    pos, command, rm_unstable, device, joint = [], "", 0, 0, 0
     for a in argv:
         if a in ("-h", "--help"):
             sys.stderr.write(USAGE)
@@ -261,6 +292,11 @@ def main(argv=None):
                 rm_unstable = int(a.split("=", 1)[1])
             except ValueError:
                 rm_unstable = 0
+        elif a.startswith("-j=") or a.startswith("--joint="):
+            try:
+                joint = int(a.split("=", 1)[1])
+            except ValueError:
+                joint = 0
         elif a.startswith("--device="):
             device = int(a.split("=", 1)[1])
         elif a.startswith("-"):
@@ -271,7 +307,7 @@ def main(argv=None):
     if len(pos) < 2 or not pos[0] or not pos[1]:
         sys.stderr.write(USAGE)
         return 1
-    bad = refused_item(command_items(command))
+    bad = None if joint else refused_item(command_items(command))
     if bad is not None:
         print(f"OpenMVG_BA: -c={command}: item \"{bad}\" is not supported yet (-c adjusts the structure alone, or "
               "rotations / translations alone; no intrinsics); nothing was written", file=sys.stderr)
@@ -279,7 +315,7 @@ def main(argv=None):
 
     def log(s):
         print(s, flush=True)
-    return run(pos[0], pos[1], rm_unstable=rm_unstable != 0, device=device, log=log, command=command)
+    return run(pos[0], pos[1], rm_unstable=rm_unstable != 0, device=device, log=log, command=command, joint=joint != 0)
 
 
 if __name__ == "__main__":

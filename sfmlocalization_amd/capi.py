@@ -114,6 +114,17 @@ class BaReport(C.Structure):
 BA_ROTATION, BA_TRANSLATION, BA_INTRINSICS, BA_STRUCTURE = 1, 2, 4, 8
 
 
+class BaJointOptions(C.Structure):
+    _fields_ = [("max_steps", C.c_uint32), ("max_pcg", C.c_uint32), ("function_tolerance", C.c_double),
+                ("pcg_tolerance", C.c_double)]
+
+
+class BaJointReport(C.Structure):
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_pose_blocks", C.c_uint32),
+                ("n_intrinsic_blocks", C.c_uint32), ("n_landmark_blocks", C.c_uint32), ("steps_tried", C.c_uint32),
+                ("steps_accepted", C.c_uint32), ("pcg_total", C.c_uint32), ("pcg_max", C.c_uint32), ("stop", C.c_uint32)]
+
+
 class MergeParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("device", C.c_int), ("rounds_per_launch", C.c_uint32), ("profile", C.c_int),
                 ("reserved", C.c_int)]
@@ -175,6 +186,7 @@ SYMBOLS = [
     "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
     "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
     "sfmloc_sfm_color_plan", "sfmloc_sfm_color_last_ms", "sfmloc_sfm_adjust", "sfmloc_sfm_read_structure",
+    "sfmloc_ba_joint_default_options", "sfmloc_sfm_adjust_joint", "sfmloc_sfm_read_intrinsics",
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
     "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
@@ -420,6 +432,10 @@ def _L():
         L.sfmloc_sfm_color_last_ms.argtypes = []
         L.sfmloc_sfm_adjust.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaReport)]
         L.sfmloc_sfm_read_structure.argtypes = [C.c_void_p, F64P]
+        L.sfmloc_ba_joint_default_options.restype = None
+        L.sfmloc_ba_joint_default_options.argtypes = [C.POINTER(BaJointOptions)]
+        L.sfmloc_sfm_adjust_joint.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaJointOptions), C.POINTER(BaJointReport)]
+        L.sfmloc_sfm_read_intrinsics.argtypes = [C.c_void_p, F64P]
         MPP = C.POINTER(MergeParams)
         L.sfmloc_merge_default_params.restype = None
         L.sfmloc_merge_default_params.argtypes = [MPP]
@@ -1149,6 +1165,13 @@ def sfm_color_last_ms():
     return float(_L().sfmloc_sfm_color_last_ms())
 
 
+def ba_joint_default_options():
+    """sfmloc_ba_joint_default_options -> BaJointOptions"""
+    o = BaJointOptions()
+    _L().sfmloc_ba_joint_default_options(C.byref(o))
+    return o
+
+
 def sfm_json_rewrite(in_path, out_path):
     """sfmloc_sfm_json_rewrite (host only): the C++ JSON writer of OpenMVG_BA on a parsed file"""
     _check(_L().sfmloc_sfm_json_rewrite(os.fsencode(in_path), os.fsencode(out_path)))
@@ -1234,6 +1257,24 @@ class Sfm:
         rep = BaReport()
         _check(_L().sfmloc_sfm_adjust(self._h, int(what), C.byref(rep)))
         return rep
+
+    def adjust_joint(self, what, **options):
+        """sfmloc_sfm_adjust_joint: poses, intrinsics and structure in one Levenberg-Marquardt problem -- what = any
+        non-zero combination of the BA_ bits; options = fields of BaJointOptions over the defaults -> BaJointReport"""
+        opt = ba_joint_default_options()
+        for k, val in options.items():
+            if k not in ("max_steps", "max_pcg", "function_tolerance", "pcg_tolerance"):
+                raise TypeError(f"adjust_joint: unknown option {k}")
+            setattr(opt, k, val)
+        rep = BaJointReport()
+        _check(_L().sfmloc_sfm_adjust_joint(self._h, int(what), C.byref(opt), C.byref(rep)))
+        return rep
+
+    def read_intrinsics(self):
+        """-> the intrinsics [n_intrinsics, 6] (f, ppx, ppy, k1, k2, k3) as they are now"""
+        K = np.zeros((len(self._keep["intrinsic_type"]), 6))
+        _check(_L().sfmloc_sfm_read_intrinsics(self._h, _ptr(K, C.c_double)))
+        return K
 
     def read_structure(self):
         """-> the landmarks' X [n_landmarks, 3] as they are now"""

@@ -14,7 +14,8 @@
 //               loop over pose counts (integer atomics: a count does not depend on order).  A later cleanup works on
 //               what the earlier ones kept.
 //   adjustment  the separable commands of -c (sfmloc_sfm_adjust): this file checks the poses and hands the resident
-//               arrays to ba_separable.hip, whose kernels move X or the poses in place.
+//               arrays to ba_separable.hip, whose kernels move X or the poses in place.  The joint commands
+//               (sfmloc_sfm_adjust_joint) go to ba_joint.hip the same way; that path moves the intrinsics too.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -718,9 +719,7 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
   return SFMLOC_OK;
 }
 
-int sfm_adjust_impl(Sfm *h, uint32_t what, sfmloc_ba_report *rep) {
-  const int rc = sfm_check_poses(h, "adjusted");
-  if (rc) return rc;
+void sfm_ba_view(Sfm *h, SfmBaView *out) {
   SfmBaView v;
   v.s = h->s;
   v.n_views = h->n_views;
@@ -746,16 +745,52 @@ int sfm_adjust_impl(Sfm *h, uint32_t what, sfmloc_ba_report *rep) {
   v.d_pose_views = h->d_pose_views;
   v.d_blk_cost = h->d_blk_cost;
   v.d_blk_info = h->d_blk_info;
+  *out = v;
+}
+
+// the host's copy of the pose table follows the device's (sfmloc_sfm_read reads it)
+int sfm_fetch_poses(Sfm *h) {
+  SFM_HIP(hipMemcpyAsync(h->h_pose_R.data(), h->d_pose_R, 9 * (size_t)h->n_poses * sizeof(double),
+                         hipMemcpyDeviceToHost, h->s));
+  SFM_HIP(hipMemcpyAsync(h->h_pose_C.data(), h->d_pose_C, 3 * (size_t)h->n_poses * sizeof(double),
+                         hipMemcpyDeviceToHost, h->s));
+  SFM_HIP(hipStreamSynchronize(h->s));
+  return SFMLOC_OK;
+}
+
+int sfm_adjust_impl(Sfm *h, uint32_t what, sfmloc_ba_report *rep) {
+  const int rc = sfm_check_poses(h, "adjusted");
+  if (rc) return rc;
+  SfmBaView v;
+  sfm_ba_view(h, &v);
   const int rc_run = ba_separable_run(v, what, rep);
   if (rc_run) return rc_run;
-  if (what != SFMLOC_BA_STRUCTURE) {  // the host's copy of the pose table follows (sfmloc_sfm_read reads it)
-    SFM_HIP(hipMemcpyAsync(h->h_pose_R.data(), h->d_pose_R, 9 * (size_t)h->n_poses * sizeof(double),
-                           hipMemcpyDeviceToHost, h->s));
-    SFM_HIP(hipMemcpyAsync(h->h_pose_C.data(), h->d_pose_C, 3 * (size_t)h->n_poses * sizeof(double),
-                           hipMemcpyDeviceToHost, h->s));
-    SFM_HIP(hipStreamSynchronize(h->s));
-  }
+  if (what != SFMLOC_BA_STRUCTURE) return sfm_fetch_poses(h);
   return SFMLOC_OK;
+}
+
+int sfm_adjust_joint_impl(Sfm *h, uint32_t what, const sfmloc_ba_joint_options &opt, sfmloc_ba_joint_report *rep) {
+  const int rc = sfm_check_poses(h, "adjusted");  // (fetches the keep masks of the last cleanup)
+  if (rc) return rc;
+  SfmBaView v;
+  sfm_ba_view(h, &v);
+  SfmJointHost hs;
+  hs.n_intr = h->n_intr;
+  hs.n_obs = h->n_obs;
+  hs.d_intr = h->d_intr;
+  hs.view_intr = h->h_view_intr.data();
+  hs.view_pose = h->h_view_pose.data();
+  hs.obs_view = h->h_obs_view.data();
+  hs.obs_off = h->h_obs_off.data();
+  hs.obs_keep = h->cleaned ? h->h_obs_keep.data() : nullptr;
+  hs.lm_stage = h->cleaned ? h->h_lm_stage.data() : nullptr;
+  const int rc_run = ba_joint_run(v, hs, what, opt, rep);
+  if (rc_run) return rc_run;
+  if (what & SFMLOC_BA_INTRINSICS) {
+    SFM_HIP(hipMemcpyAsync(h->h_intr.data(), h->d_intr, 6 * (size_t)h->n_intr * sizeof(double), hipMemcpyDeviceToHost,
+                           h->s));
+  }
+  return sfm_fetch_poses(h);
 }
 
 }  // namespace
@@ -859,6 +894,45 @@ int sfmloc_sfm_adjust(sfmloc_sfm *hh, uint32_t what, sfmloc_ba_report *rep) {
     set_error("sfmloc_sfm_adjust: out of host memory");
     return SFMLOC_ENOMEM;
   }
+}
+
+void sfmloc_ba_joint_default_options(sfmloc_ba_joint_options *o) {
+  if (!o) return;
+  o->max_steps = 50;            // Ceres max_num_iterations
+  o->max_pcg = 500;             // Ceres max_linear_solver_iterations
+  o->function_tolerance = 1e-6;
+  o->pcg_tolerance = 0.1;       // Ceres eta
+}
+
+int sfmloc_sfm_adjust_joint(sfmloc_sfm *hh, uint32_t what, const sfmloc_ba_joint_options *opt,
+                            sfmloc_ba_joint_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust_joint: null handle");
+  const uint32_t all = SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION | SFMLOC_BA_INTRINSICS | SFMLOC_BA_STRUCTURE;
+  SFM_CHECK(what != 0 && (what & ~all) == 0, SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust_joint: what = %u: a non-zero combination of the four SFMLOC_BA_ bits (-c's r, t, i, s)",
+            what);
+  sfmloc_ba_joint_options o;
+  if (opt) o = *opt;
+  else sfmloc_ba_joint_default_options(&o);
+  SFM_CHECK(o.max_steps > 0 && o.function_tolerance >= 0.0 && o.pcg_tolerance >= 0.0, SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust_joint: max_steps must be positive and the tolerances not negative");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  SFM_HIP(hipSetDevice(h->device));
+  try {
+    return sfm_adjust_joint_impl(h, what, o, rep);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_adjust_joint: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+}
+
+int sfmloc_sfm_read_intrinsics(sfmloc_sfm *hh, double *K) {
+  SFM_CHECK(hh && K, SFMLOC_EINVAL, "sfmloc_sfm_read_intrinsics: null argument");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SFM_HIP(hipSetDevice(h->device));
+  SFM_HIP(hipMemcpy(K, h->d_intr, 6 * (size_t)h->n_intr * sizeof(double), hipMemcpyDeviceToHost));
+  return SFMLOC_OK;
 }
 
 int sfmloc_sfm_read_structure(sfmloc_sfm *hh, double *X) {

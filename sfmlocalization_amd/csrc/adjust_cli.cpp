@@ -1,6 +1,6 @@
 // OpenMVG_BA (OpenMVG_BA/src/adjust_sfm_data.cpp) as a C++ host program over the C ABI (plain g++):
 //
-//   OpenMVG_BA <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [--device=0]
+//   OpenMVG_BA <sfm_data> <sfm_data_out> [-c=...] [-r=0|1] [-j=0|1] [--device=0]
 //
 // The same program as sfmlocalization_amd/adjust.py, and the same bytes: every view with more than 10 observations is
 // re-resected on the device (sfmloc_sfm_resect), <folder of sfm_data>/sfm_data_b4bd.json is written with the new poses
@@ -16,6 +16,11 @@
 // final cleanup of its own (the reference cleans in the else branch only) and the output holds the adjusted poses and X.
 // The joint commands (s with r or t, anything with i) are not supported yet: every item is checked before anything is
 // opened, one refused item ends the run with status 1 and nothing written.
+//
+// -j=1 (--joint=1, in any position) opts in to the joint adjustment: no item is refused, an item that would be goes to
+// sfmloc_sfm_adjust_joint with the default options (one Levenberg-Marquardt problem over everything the item names), a
+// separable item still goes to sfmloc_sfm_adjust (-c=rt,sc -j=1 gives the bytes of -c=rt,sc).  An intrinsic whose bits
+// changed is written from the arrays (focal_length, principal_point, disto_k3); sfm_data_b4bd.json keeps the input's.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -43,7 +48,9 @@ void usage() {
           "t = translation, s = structure, c = clean]. Usage example: c=r,tc,s means BD with rotation only, then BD with "
           "translation follow by cleaning, then BD with structure. Not supported yet: i (intrinsic), and s together "
           "with r or t.\n"
-          "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n");
+          "\t-r, --rm_unstable (value:0)\n\t\tRemove unstable pose and observation\n"
+          "\t-j, --joint (value:0)\n\t\tWith 1, run the items that are not supported yet (i, and s together with r or t) as "
+          "one joint bundle adjustment\n");
 }
 
 void set_key(Value *obj, const char *k, Value v) {
@@ -117,6 +124,32 @@ bool has(const std::string &item, char c) { return item.find(c) != std::string::
 
 bool bits_differ(const double *a, const double *b, size_t n) { return memcmp(a, b, n * sizeof(double)) != 0; }
 
+// an item the separable path refuses: structure with a pose part, or intrinsics
+bool joint_item(const std::string &item) {
+  return has(item, 'i') || (has(item, 's') && (has(item, 'r') || has(item, 't')));
+}
+
+// intrinsic i of the document (array order) from K = f, ppx, ppy, k1, k2, k3
+void set_intrinsic(Value *root, size_t i, uint32_t type, const double *K) {
+  Value *list = root->get("intrinsics");
+  Value *val = list ? list->a[i].get("value") : nullptr;
+  Value *pw = val ? val->get("ptr_wrapper") : nullptr;
+  Value *data = pw ? pw->get("data") : nullptr;
+  if (!data) return;
+  Value *pin = type == 3 ? data->get("value0") : data;
+  if (!pin) return;
+  set_key(pin, "focal_length", Value::make_float(K[0]));
+  Value pp = Value::make_arr();
+  pp.a.push_back(Value::make_float(K[1]));
+  pp.a.push_back(Value::make_float(K[2]));
+  set_key(pin, "principal_point", pp);
+  if (type == 3) {
+    Value k3 = Value::make_arr();
+    for (int j = 3; j < 6; ++j) k3.a.push_back(Value::make_float(K[j]));
+    set_key(data, "disto_k3", k3);
+  }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -126,7 +159,7 @@ int main(int argc, char **argv) {
   }
   std::vector<std::string> pos;
   std::string command;
-  int rm_unstable = 0, device = 0;
+  int rm_unstable = 0, device = 0, joint = 0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "-h" || a == "--help") {
@@ -136,6 +169,8 @@ int main(int argc, char **argv) {
       command = a.substr(a.find('=') + 1);
     } else if (a.rfind("-r=", 0) == 0 || a.rfind("--rm_unstable=", 0) == 0) {
       rm_unstable = atoi(a.c_str() + a.find('=') + 1);
+    } else if (a.rfind("-j=", 0) == 0 || a.rfind("--joint=", 0) == 0) {
+      joint = atoi(a.c_str() + a.find('=') + 1);
     } else if (a.rfind("--device=", 0) == 0) {
       device = atoi(a.c_str() + 9);
     } else if (!a.empty() && a[0] == '-') {
@@ -151,7 +186,7 @@ int main(int argc, char **argv) {
   }
   const std::vector<std::string> items = command_items(command);
   for (const std::string &item : items)
-    if (has(item, 'i') || (has(item, 's') && (has(item, 'r') || has(item, 't')))) {
+    if (!joint && joint_item(item)) {
       fprintf(stderr,
               "OpenMVG_BA: -c=%s: item \"%s\" is not supported yet (-c adjusts the structure alone, or rotations / "
               "translations alone; no intrinsics); nothing was written\n",
@@ -222,17 +257,23 @@ int main(int argc, char **argv) {
   };
   for (size_t k = 0; k < items.size() && rc == 0; ++k) {
     const std::string &item = items[k];
-    const bool rot = has(item, 'r'), trn = has(item, 't'), stru = has(item, 's');
-    printf("\nBundle adjustment over %s%s%s\n", rot ? "rotations, " : "", trn ? "translations, " : "",
-           stru ? "structure, " : "");
+    const bool rot = has(item, 'r'), trn = has(item, 't'), intr = joint && has(item, 'i'), stru = has(item, 's');
+    printf("\nBundle adjustment over %s%s%s%s\n", rot ? "rotations, " : "", trn ? "translations, " : "",
+           intr ? "intrinsic params, " : "", stru ? "structure, " : "");
     fflush(stdout);
-    rc = sfmloc_sfm_adjust(h, (rot ? SFMLOC_BA_ROTATION : 0u) | (trn ? SFMLOC_BA_TRANSLATION : 0u) |
-                                  (stru ? SFMLOC_BA_STRUCTURE : 0u), nullptr);
+    const uint32_t what = (rot ? SFMLOC_BA_ROTATION : 0u) | (trn ? SFMLOC_BA_TRANSLATION : 0u) |
+                          (intr ? SFMLOC_BA_INTRINSICS : 0u) | (stru ? SFMLOC_BA_STRUCTURE : 0u);
+    if (joint && joint_item(item)) rc = sfmloc_sfm_adjust_joint(h, what, nullptr, nullptr);
+    else rc = sfmloc_sfm_adjust(h, what, nullptr);
     if (rc == 0 && has(item, 'c')) rc = clean();
   }
   if (rc == 0 && items.empty()) rc = clean();
   std::vector<uint8_t> obs_keep(d.obs_view.size(), 1), lm_keep(d.lm_id.size(), 1);
-  std::vector<double> X;
+  std::vector<double> X, K;
+  if (rc == 0 && joint && !items.empty()) {
+    K.resize(d.intr.size());
+    rc = sfmloc_sfm_read_intrinsics(h, K.data());
+  }
   if (rc == 0 && !items.empty()) {  // a pose or a landmark the adjustment moved is written from the arrays
     std::vector<double> R2(R.size()), C2(C.size());
     X.resize(d.lm_X.size());
@@ -256,6 +297,8 @@ int main(int argc, char **argv) {
   }
   Value outd = d.root;
   set_key(&outd, "extrinsics", extrinsics(d, valid, R, C, replaced));
+  for (size_t i = 0; i < d.intr_type.size() && !K.empty(); ++i)  // an intrinsic the adjustment moved: from the arrays
+    if (bits_differ(&K[6 * i], &d.intr[6 * i], 6)) set_intrinsic(&outd, i, d.intr_type[i], &K[6 * i]);
   Value *st = outd.get("structure");
   if (st) {
     Value kept = Value::make_arr();

@@ -525,4 +525,18 @@ struct SfmBaView {
 };
 int ba_separable_run(const SfmBaView &v, uint32_t what, sfmloc_ba_report *rep);
 
+// ba_joint.hip: the joint adjustment (sfmloc_sfm_adjust_joint) works on the same resident arrays, moves the intrinsics
+// too (d_intr: the handle's array, not const on this path) and decides on the host which observations enter: the
+// host's copies of the index arrays and of the keep masks (null before the first cleanup)
+struct SfmJointHost {
+  uint32_t n_intr;
+  uint64_t n_obs;
+  double *d_intr;
+  const uint32_t *view_intr, *view_pose, *obs_view;
+  const uint64_t *obs_off;
+  const uint8_t *obs_keep, *lm_stage;
+};
+int ba_joint_run(const SfmBaView &v, const SfmJointHost &hs, uint32_t what, const sfmloc_ba_joint_options &opt,
+                 sfmloc_ba_joint_report *rep);
+
 }  // namespace sfmloc
