@@ -847,6 +847,93 @@ int sfmloc_sfm_adjust_joint(sfmloc_sfm *h, uint32_t what, const sfmloc_ba_joint_
 int sfmloc_sfm_read_intrinsics(sfmloc_sfm *h, double *K /*[n_intrinsics*6]*/);
 
 /* ------------------------------------------------------------------------- */
+/* Structure from known poses (openMVG_main_ComputeStructureFromKnownPoses, and the last stage of                      */
+/* openMVG_main_GlobalSfM, reconstructGraph.py:171): feature tracks from the pairwise matches (sfmloc_tracks), then     */
+/* every track triangulated from the views' poses on a resident sfmloc_sfm (sfmloc_sfm_triangulate).  OpenMVG's source  */
+/* was not at hand: every point below is a reading chosen here, and tests/structure_np.py restates each operation.      */
+/* sfmloc_tracks (TracksBuilder::Build + Filter):                                                                       */
+/*   nodes       a node is a global feature row, view_off[v] + feature; an edge joins the two nodes of a match.  The    */
+/*               pair list has the layout of sfmloc_geometric_pairs (pair k = views (pairs[2k], pairs[2k+1]) owns       */
+/*               match_i/j[offsets[k] .. offsets[k+1])).  view_use (may be NULL: all) masks views out: a pair with a    */
+/*               masked-out view contributes nothing (the tool masks the views without a pose or an intrinsic).         */
+/*   components  union of the two nodes of every match; a component's label is its smallest node row.  Hooking with an   */
+/*               integer atomicMin on roots plus pointer jumping until a pass changes nothing: the fixed point does not  */
+/*               depend on scheduling, two runs give the same arrays.  A match listed twice counts once.                 */
+/*   filter      a component with two different features of one view is dropped whole (OpenMVG's conflict rule); then   */
+/*               a component with fewer than min_length nodes (the tools pass 2; 0 counts as 1); a node no match        */
+/*               touches is not a track.                                                                                */
+/*   order       track ids 0, 1, 2, ... in ascending label; inside a track the observations ascend by view, which is    */
+/*               ascending node row.  (OpenMVG numbers tracks by union-find root, which is not reproducible; every       */
+/*               consumer in the reference renumbers.)                                                                   */
+/*   errors      all checked before anything is launched: a view index out of range, a pair naming one view twice, a    */
+/*               feature index out of range (the text names the pair and the match): SFMLOC_EINVAL; more than 2^32 - 2  */
+/*               feature rows or matches: SFMLOC_ECAP.                                                                   */
+/* sfmloc_sfm_triangulate (SfM_Data_Structure_Computation_Robust / _Blind) works on the handle's observations, poses    */
+/* and intrinsics, and overwrites the resident X and the keep masks; sfmloc_sfm_clean, sfmloc_sfm_adjust[_joint],       */
+/* sfmloc_sfm_read and sfmloc_sfm_read_structure follow on the same handle as after a cleanup (a later cleanup works on */
+/* what was kept).  The handle may hold tracks with landmark_X all zero, or a map whose structure is to be rebuilt.      */
+/* Per landmark, f64, unfused, only + - * / sqrt:                                                                        */
+/*   posed       n = the observations whose view has a valid pose; the others are not kept and otherwise ignored (no    */
+/*               GetPoseOrDie here).  n < 2: the landmark fails ("too few posed observations").                          */
+/*   ray         the pixel is undistorted with get_ud_pixel (the bisection of "angle" above) for pinhole_radial_k3.     */
+/*   projection  P = K [R | t], t_i = -((R_i0 C0 + R_i1 C1) + R_i2 C2): P_0j = f M_0j + ppx M_2j, P_1j = f M_1j +       */
+/*               ppy M_2j, P_2j = M_2j with M = [R | t].                                                                 */
+/*   hypothesis  two views: G = A^T A of the four rows x P_2 - P_0, y P_2 - P_1 ((x, y) the undistorted pixel), upper   */
+/*               triangle, from 0.0, per observation G_ij = (G_ij + a_i a_j) + b_i b_j in list order, mirrored; the     */
+/*               cyclic Jacobi of "jacobi" (sfmloc_merge section; 10 sweeps); the eigenvector of the smallest diagonal  */
+/*               entry (the first on ties), divided by its w.  A zero or non-finite w or a non-finite point: no         */
+/*               hypothesis.                                                                                             */
+/*   rounds      mode SFMLOC_TRI_ROBUST: 2 n rounds, round r draws 2 distinct positions of the posed list with           */
+/*               ac_sample<2> (Philox4x32-10 keyed by params.seed, stage 5, stream = the landmark's id, iteration r):   */
+/*               a landmark's result does not depend on the batch.  n = 2: one round, the pair itself.                   */
+/*   inliers     of a point: the posed observations with depth Xc_2 > 0 and sqrt(ex ex + ey ey) <= residual_px, the     */
+/*               arithmetic of "residual" above, distortion applied, against the raw pixel.  A NaN is no inlier.         */
+/*   winner      the round with the most inliers; on a tie the smaller sum of the inliers' ex ex + ey ey (added in list */
+/*               order from 0.0); on a further tie the earlier round.  No round with a hypothesis: the landmark fails   */
+/*               ("no valid hypothesis").                                                                                */
+/*   final point G over the winner's inliers in list order (fewer than 2: "too few inliers"), the same eigen-solve (no  */
+/*               point: "no valid hypothesis"), and its inliers evaluated once.                                          */
+/*   keep rule   kept when the final inliers number at least min_inliers, or 2 when n = 2 and allow_pairs; otherwise     */
+/*               "too few inliers".  A kept landmark's obs_keep is its final inlier mask; a failed landmark has X = 0,   */
+/*               landmark_keep 0 and no observation kept.                                                                */
+/*   blind       mode SFMLOC_TRI_BLIND: no rounds; G over every posed observation, then "inliers" with the depth test   */
+/*               only, and the same keep rule.                                                                           */
+/* No float atomics, no order-dependent atomics: two runs give the same bits.                                            */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_tracks sfmloc_tracks;
+int sfmloc_tracks_build(int device, const uint64_t *view_off /*[n_views+1]*/, uint32_t n_views,
+                        const uint8_t *view_use /*[n_views] or NULL*/, const uint32_t *pairs, uint32_t n_pairs,
+                        const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j, uint32_t min_length,
+                        sfmloc_tracks **out);
+/* components, dropped for conflict, dropped for length, kept (= the number of tracks) */
+int sfmloc_tracks_counts(const sfmloc_tracks *t, uint64_t *counts /*[4]*/);
+/* off [n_tracks+1] (sfmloc_tracks_counts gives n_tracks; off may be read alone first), view index and feature index of
+ * every observation [off[n_tracks]]; any pointer may be NULL */
+int sfmloc_tracks_read(const sfmloc_tracks *t, uint64_t *off, uint32_t *view, uint32_t *feat);
+void sfmloc_tracks_destroy(sfmloc_tracks *t);
+/* device milliseconds of the calling thread's last sfmloc_tracks_build (HIP events around its kernels and copies) */
+double sfmloc_tracks_last_ms(void);
+
+enum { SFMLOC_TRI_ROBUST = 0, SFMLOC_TRI_BLIND = 1 };
+typedef struct sfmloc_triangulate_options {
+  uint32_t mode;         /* SFMLOC_TRI_ROBUST (default) or SFMLOC_TRI_BLIND */
+  uint32_t min_inliers;  /* default 3 (at least 2) */
+  uint32_t allow_pairs;  /* default 1: a landmark with two posed observations is kept on 2 inliers */
+  uint32_t reserved;
+  double residual_px;    /* default 4.0 */
+} sfmloc_triangulate_options;
+typedef struct sfmloc_triangulate_report {
+  uint64_t landmarks_in, landmarks_kept;
+  uint64_t failed_posed, failed_hypothesis, failed_inliers; /* too few posed observations / no valid hypothesis / too few inliers */
+  uint64_t obs_in, obs_kept;
+  uint64_t rounds;       /* rounds run, all landmarks together */
+  double device_ms;      /* HIP events around the call's kernels */
+} sfmloc_triangulate_report;
+void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o);
+/* opt NULL = the defaults; rep may be NULL */
+int sfmloc_sfm_triangulate(sfmloc_sfm *h, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep);
+
+/* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */
 /* reference runs after every reconstruction and merge): which view each landmark takes its colour from.  The greedy  */
 /* cover runs on the structure exactly as sfmloc_sfm_create received it (the keep masks of sfmloc_sfm_clean and the   */

@@ -125,6 +125,20 @@ class BaJointReport(C.Structure):
                 ("steps_accepted", C.c_uint32), ("pcg_total", C.c_uint32), ("pcg_max", C.c_uint32), ("stop", C.c_uint32)]
 
 
+TRI_ROBUST, TRI_BLIND = 0, 1
+
+
+class TriangulateOptions(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("min_inliers", C.c_uint32), ("allow_pairs", C.c_uint32), ("reserved", C.c_uint32),
+                ("residual_px", C.c_double)]
+
+
+class TriangulateReport(C.Structure):
+    _fields_ = [("landmarks_in", C.c_uint64), ("landmarks_kept", C.c_uint64), ("failed_posed", C.c_uint64),
+                ("failed_hypothesis", C.c_uint64), ("failed_inliers", C.c_uint64), ("obs_in", C.c_uint64),
+                ("obs_kept", C.c_uint64), ("rounds", C.c_uint64), ("device_ms", C.c_double)]
+
+
 class MergeParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("device", C.c_int), ("rounds_per_launch", C.c_uint32), ("profile", C.c_int),
                 ("reserved", C.c_int)]
@@ -190,6 +204,8 @@ SYMBOLS = [
     "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
     "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
+    "sfmloc_tracks_build", "sfmloc_tracks_counts", "sfmloc_tracks_read", "sfmloc_tracks_destroy", "sfmloc_tracks_last_ms",
+    "sfmloc_triangulate_default_options", "sfmloc_sfm_triangulate",
 ]
 
 _bound = False
@@ -436,6 +452,18 @@ def _L():
         L.sfmloc_ba_joint_default_options.argtypes = [C.POINTER(BaJointOptions)]
         L.sfmloc_sfm_adjust_joint.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaJointOptions), C.POINTER(BaJointReport)]
         L.sfmloc_sfm_read_intrinsics.argtypes = [C.c_void_p, F64P]
+        U64P = C.POINTER(C.c_uint64)
+        L.sfmloc_tracks_build.argtypes = [C.c_int, U64P, C.c_uint32, U8P, U32P, C.c_uint32, U64P, U32P, U32P, C.c_uint32,
+                                          C.POINTER(C.c_void_p)]
+        L.sfmloc_tracks_counts.argtypes = [C.c_void_p, U64P]
+        L.sfmloc_tracks_read.argtypes = [C.c_void_p, U64P, U32P, U32P]
+        L.sfmloc_tracks_destroy.restype = None
+        L.sfmloc_tracks_destroy.argtypes = [C.c_void_p]
+        L.sfmloc_tracks_last_ms.restype = C.c_double
+        L.sfmloc_tracks_last_ms.argtypes = []
+        L.sfmloc_triangulate_default_options.restype = None
+        L.sfmloc_triangulate_default_options.argtypes = [C.POINTER(TriangulateOptions)]
+        L.sfmloc_sfm_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.POINTER(TriangulateReport)]
         MPP = C.POINTER(MergeParams)
         L.sfmloc_merge_default_params.restype = None
         L.sfmloc_merge_default_params.argtypes = [MPP]
@@ -1270,6 +1298,18 @@ class Sfm:
         _check(_L().sfmloc_sfm_adjust_joint(self._h, int(what), C.byref(opt), C.byref(rep)))
         return rep
 
+    def triangulate(self, **options):
+        """sfmloc_sfm_triangulate: X and the keep masks rebuilt from the poses -- options = fields of TriangulateOptions
+        over the defaults (mode TRI_ROBUST / TRI_BLIND, min_inliers, allow_pairs, residual_px) -> TriangulateReport"""
+        opt = triangulate_default_options()
+        for k, val in options.items():
+            if k not in ("mode", "min_inliers", "allow_pairs", "residual_px"):
+                raise TypeError(f"triangulate: unknown option {k}")
+            setattr(opt, k, val)
+        rep = TriangulateReport()
+        _check(_L().sfmloc_sfm_triangulate(self._h, C.byref(opt), C.byref(rep)))
+        return rep
+
     def read_intrinsics(self):
         """-> the intrinsics [n_intrinsics, 6] (f, ppx, ppy, k1, k2, k3) as they are now"""
         K = np.zeros((len(self._keep["intrinsic_type"]), 6))
@@ -1310,6 +1350,74 @@ class Sfm:
             self.close()
         except Exception:
             pass
+
+
+def triangulate_default_options():
+    """sfmloc_triangulate_default_options -> TriangulateOptions (robust, 3 inliers, pairs allowed, 4 px)"""
+    o = TriangulateOptions()
+    _L().sfmloc_triangulate_default_options(C.byref(o))
+    return o
+
+
+def pair_arrays(matches, view_index=None):
+    """{(I, J): (i[], j[])} -> (pairs [n, 2] uint32, offsets [n + 1] uint64, match_i, match_j): the pair list layout of
+    sfmloc_geometric_pairs and sfmloc_tracks_build, pairs in ascending (I, J); view_index maps a key to a view index"""
+    keys = sorted(matches)
+    ix = (lambda k: k) if view_index is None else (lambda k: view_index[k])
+    pairs = np.array([[ix(a), ix(b)] for a, b in keys], np.uint32).reshape(-1, 2)
+    off = np.zeros(len(keys) + 1, np.uint64)
+    for k, key in enumerate(keys):
+        off[k + 1] = off[k] + np.uint64(len(matches[key][0]))
+    cat = (lambda c: np.concatenate([np.asarray(matches[k][c], np.uint32) for k in keys]) if keys
+           else np.zeros(0, np.uint32))
+    return pairs, off, cat(0), cat(1)
+
+
+def tracks_last_ms():
+    """device milliseconds of this thread's last Tracks()"""
+    return float(_L().sfmloc_tracks_last_ms())
+
+
+class Tracks:
+    """sfmloc_tracks: feature tracks of a pair list (include/sfmloc.h states the semantics).  view_off [n_views + 1]
+    feature rows per view; pairs [n, 2] view indices, offsets [n + 1], match_i / match_j as pair_arrays returns them;
+    view_use [n_views] masks views out.  -> counts (components, dropped for conflict, dropped for length, kept),
+    off [n_tracks + 1], view, feat."""
+
+    def __init__(self, view_off, pairs, offsets, match_i, match_j, view_use=None, min_length=2, device=0):
+        view_off = np.ascontiguousarray(view_off, np.uint64)
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
+        if view_use is not None:
+            view_use = np.ascontiguousarray(view_use, np.uint8)
+            if len(view_use) != len(view_off) - 1:
+                raise ValueError("view_use must have one entry per view")
+        if len(offsets) != len(pairs) + 1 or len(match_i) != len(match_j) or \
+                (len(pairs) and int(offsets[-1]) != len(match_i)):
+            raise ValueError("pair list arrays differ in length")
+        h = C.c_void_p()
+        _check(_L().sfmloc_tracks_build(int(device), _ptr(view_off, C.c_uint64), len(view_off) - 1,
+                                        _ptr(view_use, C.c_uint8), _ptr(pairs.reshape(-1), C.c_uint32), len(pairs),
+                                        _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32),
+                                        int(min_length), C.byref(h)))
+        try:
+            counts = (C.c_uint64 * 4)()
+            _check(_L().sfmloc_tracks_counts(h, counts))
+            self.counts = [int(c) for c in counts]
+            self.off = np.zeros(self.counts[3] + 1, np.uint64)
+            _check(_L().sfmloc_tracks_read(h, _ptr(self.off, C.c_uint64), None, None))
+            n = int(self.off[-1])
+            self.view, self.feat = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint32)
+            _check(_L().sfmloc_tracks_read(h, None, _ptr(self.view, C.c_uint32), _ptr(self.feat, C.c_uint32)))
+            self.view, self.feat = self.view[:n], self.feat[:n]
+            self.ms = tracks_last_ms()
+        finally:
+            _L().sfmloc_tracks_destroy(h)
+
+    @property
+    def n_tracks(self):
+        return self.counts[3]
 
 
 def merge_default_params(**overrides):

@@ -2177,7 +2177,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_p3p_round_small(P3pArgs A, int 
 // resect6: the six-point DLT resection of an uncalibrated query (include/sfmloc.h "Uncalibrated queries";
 // tests/resect6_np.py restates every operation and the GPU tests compare bits).  A hypothesis is six 2D-3D
 // correspondences: the 12 x 12 design matrix D (two rows per point, the 3D points translated so that the first sampled
-// one is the origin), G = D^T D, a cyclic Jacobi eigen-solve of G with a FIXED number of sweeps (merge.hip's
+// one is the origin), G = D^T D, a cyclic Jacobi eigen-solve of G with a FIXED number of sweeps (geom_device.h's
 // jacobi_fixed, written for N = 12), the eigenvector of the smallest eigenvalue as the 3 x 4 model.  Only + - * / sqrt.
 //
 // Four lanes per hypothesis, sixteen hypotheses per wave.  G and V (2 x 144 doubles per hypothesis) do not fit a lane's

@@ -5,7 +5,8 @@
 //   transpose   the observations (CSR by landmark) become per-view correspondence lists in ascending landmark id: a
 //               stable LSD radix sort of the observation indices by view index, 8 bits per pass.  Each pass is a
 //               per-block digit histogram, one exclusive scan over (digit, block) and a scatter whose rank inside the
-//               block comes from wave ballots -- no atomic decides a position, so two runs give the same lists.
+//               block comes from wave ballots -- no atomic decides a position, so two runs give the same lists
+//               (radix_sort.h, shared with tracks.hip).
 //   resection   the lists go straight into the 2D-3D buffers of K5's contexts (k_adj_fill stands where
 //               k_match_set_finish stands on the query path) and K5 runs unchanged: init, rounds, finish; 32 views per
 //               gang session, the view's id_view as the sampling stream and its own intrinsic.
@@ -16,6 +17,8 @@
 //   adjustment  the separable commands of -c (sfmloc_sfm_adjust): this file checks the poses and hands the resident
 //               arrays to ba_separable.hip, whose kernels move X or the poses in place.  The joint commands
 //               (sfmloc_sfm_adjust_joint) go to ba_joint.hip the same way; that path moves the intrinsics too.
+//   structure   sfmloc_sfm_triangulate: the same hand-over to triangulate.hip, which rebuilds X and the keep masks from
+//               the poses; from then on the handle behaves as after a cleanup.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -27,13 +30,13 @@
 #include <vector>
 
 #include "geom_device.h"
+#include "radix_sort.h"
 #include "sfm_json.h"
 #include "sfmloc_internal.h"
 
 namespace sfmloc {
 namespace {
 
-constexpr int kRadixBlock = 1024;           // elements per block of a radix pass (16 waves)
 constexpr uint32_t kAdjGang = 32;           // contexts per gang session (kGangMembers)
 constexpr uint32_t kAdjMaxViewObs = 65536;  // a view's list must fit a context's 2D-3D buffers (make_ctx: 65 536)
 
@@ -120,74 +123,6 @@ __global__ __launch_bounds__(256) void k_adj_obs_landmark(const uint64_t *__rest
     obs_lm[o] = l;
     vlist[o] = (uint32_t)o;  // the sort's payload starts as the identity (landmark order)
   }
-}
-
-// digit histogram of one block of kRadixBlock elements -> hist[digit * nb + block]
-__global__ __launch_bounds__(kRadixBlock) void k_radix_hist(const uint32_t *__restrict__ key, uint32_t n, int shift,
-                                                            uint32_t *__restrict__ hist, uint32_t nb) {
-  __shared__ uint32_t h[256];
-  for (int i = threadIdx.x; i < 256; i += kRadixBlock) h[i] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * kRadixBlock + threadIdx.x;
-  if (i < n) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);  // (a count: the same whatever the order)
-  __syncthreads();
-  for (int d = threadIdx.x; d < 256; d += kRadixBlock) hist[(uint32_t)d * nb + blockIdx.x] = h[d];
-}
-
-// exclusive prefix sum of a[0..n) in place: one workgroup, chunks of 1024 in order
-__global__ __launch_bounds__(1024) void k_scan_excl(uint32_t *__restrict__ a, uint32_t n) {
-  __shared__ uint32_t s[1024];
-  __shared__ uint32_t carry;
-  const int t = threadIdx.x;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < n; base += 1024) {
-    const uint32_t v = (base + t < n) ? a[base + t] : 0u;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const uint32_t x = t >= off ? s[t - off] : 0u;
-      __syncthreads();
-      s[t] += x;
-      __syncthreads();
-    }
-    if (base + t < n) a[base + t] = carry + s[t] - v;
-    __syncthreads();
-    if (t == 0) carry += s[1023];
-    __syncthreads();
-  }
-}
-
-// stable scatter: an element's place = its digit's offset for this block + the elements of the same digit before it in
-// the block (its wave's lanes below it, from a ballot match over the digit's bits, then the earlier waves' counts)
-__global__ __launch_bounds__(kRadixBlock) void k_radix_scatter(const uint32_t *__restrict__ kin,
-                                                               const uint32_t *__restrict__ vin, uint32_t n, int shift,
-                                                               const uint32_t *__restrict__ off, uint32_t nb,
-                                                               uint32_t *__restrict__ kout, uint32_t *__restrict__ vout) {
-  constexpr int kWaves = kRadixBlock / 64;
-  __shared__ uint32_t wc[kWaves][257];  // (digit 256: the lanes past the end)
-  for (int i = threadIdx.x; i < kWaves * 257; i += kRadixBlock) (&wc[0][0])[i] = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * kRadixBlock + threadIdx.x;
-  const bool valid = i < n;
-  const uint32_t d = valid ? ((kin[i] >> shift) & 255u) : 256u;
-  unsigned long long mask = ~0ull;
-  for (int b = 0; b < 9; ++b) {
-    const bool bit = (d >> b) & 1u;
-    const unsigned long long bb = __ballot(bit);
-    mask &= bit ? bb : ~bb;
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  const uint32_t rank = (uint32_t)__popcll(mask & below);
-  if ((mask & below) == 0ull) wc[w][d] = (uint32_t)__popcll(mask);  // the lowest lane of each digit group
-  __syncthreads();
-  if (!valid) return;
-  uint32_t r = rank;
-  for (int ww = 0; ww < w; ++ww) r += wc[ww][d];
-  const uint32_t dst = off[d * nb + blockIdx.x] + r;
-  kout[dst] = kin[i];
-  vout[dst] = vin[i];
 }
 
 // view_off[v] = first position of view v in the sorted keys (lower bound), v = 0..n_views
@@ -388,22 +323,12 @@ int sfm_transpose(Sfm *h) {
                        h->d_obs_lm, h->d_vlist);
   SFM_HIP(hipGetLastError());
   if (n) SFM_HIP(hipMemcpyAsync(h->d_vkey, h->d_obs_view, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  int bits = 0;
-  while (bits < 32 && ((h->n_views - 1) >> bits) != 0) ++bits;
-  const uint32_t nb = (n + kRadixBlock - 1) / kRadixBlock;
-  uint32_t *kin = h->d_vkey, *vin = h->d_vlist, *kout = h->d_tmp_k, *vout = h->d_tmp_v;
-  for (int shift = 0; shift < bits && n > 0; shift += 8) {
-    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(kRadixBlock), 0, s, kin, n, shift, h->d_hist, nb);
-    hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, h->d_hist, 256u * nb);
-    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kRadixBlock), 0, s, kin, vin, n, shift, h->d_hist, nb, kout, vout);
-    SFM_HIP(hipGetLastError());
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
-  if (kin != h->d_vkey) {  // (an odd number of passes: the result is in the scratch pair)
+  // (an odd number of passes leaves the result in the scratch pair)
+  if (radix_sort_pairs(h->d_vkey, h->d_vlist, h->d_tmp_k, h->d_tmp_v, n, radix_key_bits(h->n_views - 1), h->d_hist, s)) {
     std::swap(h->d_vkey, h->d_tmp_k);
     std::swap(h->d_vlist, h->d_tmp_v);
   }
+  SFM_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_adj_view_off, dim3((h->n_views + 1 + 255) / 256), dim3(256), 0, s, h->d_vkey, n, h->n_views,
                      h->d_view_off);
   SFM_HIP(hipGetLastError());
@@ -925,6 +850,54 @@ int sfmloc_sfm_adjust_joint(sfmloc_sfm *hh, uint32_t what, const sfmloc_ba_joint
     set_error("sfmloc_sfm_adjust_joint: out of host memory");
     return SFMLOC_ENOMEM;
   }
+}
+
+void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->mode = SFMLOC_TRI_ROBUST;
+  o->min_inliers = 3;
+  o->allow_pairs = 1;
+  o->residual_px = 4.0;
+}
+
+int sfmloc_sfm_triangulate(sfmloc_sfm *hh, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_triangulate: null handle");
+  sfmloc_triangulate_options o;
+  if (opt) o = *opt;
+  else sfmloc_triangulate_default_options(&o);
+  SFM_CHECK(o.mode == SFMLOC_TRI_ROBUST || o.mode == SFMLOC_TRI_BLIND, SFMLOC_EINVAL,
+            "sfmloc_sfm_triangulate: mode = %u (0 robust, 1 blind)", o.mode);
+  SFM_CHECK(o.min_inliers >= 2 && o.residual_px >= 0.0, SFMLOC_EINVAL,
+            "sfmloc_sfm_triangulate: min_inliers must be at least 2 and residual_px not negative");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  SFM_HIP(hipSetDevice(h->device));
+  SfmTriView v;
+  v.s = h->s;
+  v.seed = h->params.seed;
+  v.n_views = h->n_views;
+  v.n_lm = h->n_lm;
+  v.n_obs = h->n_obs;
+  v.d_view_intr = h->d_view_intr;
+  v.d_view_pose = h->d_view_pose;
+  v.d_intr_type = h->d_intr_type;
+  v.d_intr = h->d_intr;
+  v.d_pose_valid = h->d_pose_valid;
+  v.d_pose_R = h->d_pose_R;
+  v.d_pose_C = h->d_pose_C;
+  v.d_lm_id = h->d_lm_id;
+  v.d_lm_X = h->d_lm_X;
+  v.d_obs_off = h->d_obs_off;
+  v.d_obs_view = h->d_obs_view;
+  v.d_obs_x = h->d_obs_x;
+  v.d_ud = h->d_ray;  // (the cleanup's ray scratch, 4 doubles per observation: it is rewritten by every cleanup)
+  v.d_obs_keep = h->d_obs_keep;
+  v.d_lm_stage = h->d_lm_stage;
+  const int rc = triangulate_run(v, o, rep);
+  if (rc) return rc;
+  h->cleaned = true;  // the masks exist: a cleanup or an adjustment that follows works on what was kept
+  return SFMLOC_OK;
 }
 
 int sfmloc_sfm_read_intrinsics(sfmloc_sfm *hh, double *K) {

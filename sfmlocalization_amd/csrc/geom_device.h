@@ -156,7 +156,7 @@ GD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
   }
 }
 
-enum { STAGE_FMATRIX = 1, STAGE_P3P = 2, STAGE_MERGE = 3, STAGE_RESECT6 = 4 };
+enum { STAGE_FMATRIX = 1, STAGE_P3P = 2, STAGE_MERGE = 3, STAGE_RESECT6 = 4, STAGE_TRIANGULATE = 5 };
 
 GD uint32_t ac_draw(uint64_t seed, uint32_t stage, uint32_t stream, uint32_t iter, uint32_t i) {
   uint32_t c[4] = {iter, stream, i >> 2, stage};
@@ -911,6 +911,58 @@ GD void krt_from_p(const double *P, double *Kout, double *Rout, double *tout) {
 GD void center_from_rt(const double *R, const double *t, double *c) {
   #pragma unroll
   for (int i = 0; i < 3; ++i) c[i] = -((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
+}
+
+// sfmloc.h "jacobi" (the sfmloc_merge section): every fixed-sweep eigen-decomposition of a small symmetric matrix
+// (merge.hip 3 x 3 and 4 x 4, triangulate.hip 4 x 4)
+constexpr int kJacobiSweeps = 10;
+// cyclic Jacobi on a symmetric N x N matrix, kJacobiSweeps sweeps over (p, q) in row order; A ends (nearly) diagonal and the
+// columns of V are the eigenvectors.  A zero a_pq skips its rotation.
+template <int N>
+GD void jacobi_fixed(double (&A)[N][N], double (&V)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int sw = 0; sw < kJacobiSweeps; ++sw) {
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        const double apq = A[p][q];
+        const bool skip = apq == 0.0;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double at = theta < 0.0 ? -theta : theta;
+        const double t = (theta < 0.0 ? -1.0 : 1.0) / (at + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0);
+        const double s = t * c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {  // A J: columns p and q
+          const double akp = A[k][p], akq = A[k][q];
+          const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
+          A[k][p] = skip ? akp : np_;
+          A[k][q] = skip ? akq : nq_;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {  // J^T (A J): rows p and q
+          const double apk = A[p][k], aqk = A[q][k];
+          const double np_ = c * apk - s * aqk, nq_ = s * apk + c * aqk;
+          A[p][k] = skip ? apk : np_;
+          A[q][k] = skip ? aqk : nq_;
+        }
+        A[p][q] = skip ? A[p][q] : 0.0;
+        A[q][p] = skip ? A[q][p] : 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          const double np_ = c * vkp - s * vkq, nq_ = s * vkp + c * vkq;
+          V[k][p] = skip ? vkp : np_;
+          V[k][q] = skip ? vkq : nq_;
+        }
+      }
+    }
+  }
 }
 
 #undef GD

@@ -28,7 +28,6 @@
 namespace sfmloc {
 namespace {
 
-constexpr int kMergeSweeps = 10;            // cyclic Jacobi sweeps of every eigen-decomposition here (3x3 and 4x4)
 constexpr uint32_t kMergeBlock = 256;       // lanes (= rounds) per workgroup of the round kernel
 constexpr uint32_t kMergeTile = 512;        // matches per LDS tile (48 B each), less when the device's LDS is smaller
 constexpr uint32_t kMergeLaunchRounds = 1u << 20;  // rounds per launch when the caller leaves the choice (0)
@@ -39,54 +38,8 @@ thread_local double g_merge_last_ms = 0.0;
 
 // ---- solvers (sfmloc.h "jacobi", "similarity", "affine") ----------------------------------------------------------------
 
-// cyclic Jacobi on a symmetric N x N matrix, kMergeSweeps sweeps over (p, q) in row order; A ends (nearly) diagonal and the
-// columns of V are the eigenvectors.  A zero a_pq skips its rotation.
-template <int N>
-__device__ __forceinline__ void jacobi_fixed(double (&A)[N][N], double (&V)[N][N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-#pragma unroll 1
-  for (int sw = 0; sw < kMergeSweeps; ++sw) {
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = A[p][q];
-        const bool skip = apq == 0.0;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double at = theta < 0.0 ? -theta : theta;
-        const double t = (theta < 0.0 ? -1.0 : 1.0) / (at + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0);
-        const double s = t * c;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {  // A J: columns p and q
-          const double akp = A[k][p], akq = A[k][q];
-          const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
-          A[k][p] = skip ? akp : np_;
-          A[k][q] = skip ? akq : nq_;
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) {  // J^T (A J): rows p and q
-          const double apk = A[p][k], aqk = A[q][k];
-          const double np_ = c * apk - s * aqk, nq_ = s * apk + c * aqk;
-          A[p][k] = skip ? apk : np_;
-          A[q][k] = skip ? aqk : nq_;
-        }
-        A[p][q] = skip ? A[p][q] : 0.0;
-        A[q][p] = skip ? A[q][p] : 0.0;
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          const double np_ = c * vkp - s * vkq, nq_ = s * vkp + c * vkq;
-          V[k][p] = skip ? vkp : np_;
-          V[k][q] = skip ? vkq : nq_;
-        }
-      }
-    }
-  }
-}
+// (the cyclic Jacobi of sfmloc.h "jacobi" is geom::jacobi_fixed, geom_device.h: kJacobiSweeps sweeps)
+using geom::jacobi_fixed;
 
 __device__ __forceinline__ bool finite12(const double *m) {
   bool f = true;

@@ -56,10 +56,8 @@ struct Doc {
   std::vector<double> obs_x;
 };
 
-inline bool load(const std::string &path, Doc *d, std::string *err) {
-  std::string text;
-  if (!sfmjson::read_file(path.c_str(), &text)) return *err = "cannot be read", false;
-  if (!sfmjson::parse(text, &d->root, err)) return false;
+// the arrays of a document already parsed into d->root (structure_cli.cpp empties `structure` first)
+inline bool build(Doc *d, std::string *err) {
   const Value &r = d->root;
   const Value *views = r.get("views"), *intrs = r.get("intrinsics"), *exts = r.get("extrinsics"),
               *st = r.get("structure");
@@ -166,6 +164,13 @@ inline bool load(const std::string &path, Doc *d, std::string *err) {
     d->obs_off.push_back(d->obs_view.size());
   }
   return true;
+}
+
+inline bool load(const std::string &path, Doc *d, std::string *err) {
+  std::string text;
+  if (!sfmjson::read_file(path.c_str(), &text)) return *err = "cannot be read", false;
+  if (!sfmjson::parse(text, &d->root, err)) return false;
+  return build(d, err);
 }
 
 // the desc over a loaded document (the document must outlive it)

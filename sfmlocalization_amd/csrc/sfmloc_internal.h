@@ -539,4 +539,25 @@ struct SfmJointHost {
 int ba_joint_run(const SfmBaView &v, const SfmJointHost &hs, uint32_t what, const sfmloc_ba_joint_options &opt,
                  sfmloc_ba_joint_report *rep);
 
+// triangulate.hip: what sfmloc_sfm_triangulate works on -- adjust.hip's resident sfm_data.  It overwrites lm_X and the
+// keep masks (obs_keep, lm_stage in the cleanup's coding: 3 = kept, 0 = not); ud [2 * n_obs] is scratch.
+struct SfmTriView {
+  hipStream_t s;
+  uint64_t seed;  // the sampling key (sfmloc_params.seed of the handle)
+  uint32_t n_views, n_lm;
+  uint64_t n_obs;
+  const uint32_t *d_view_intr, *d_view_pose, *d_intr_type;
+  const double *d_intr;
+  const uint8_t *d_pose_valid;
+  const double *d_pose_R, *d_pose_C;
+  const uint32_t *d_lm_id;
+  double *d_lm_X;
+  const uint64_t *d_obs_off;
+  const uint32_t *d_obs_view;
+  const double *d_obs_x;
+  double *d_ud;
+  uint8_t *d_obs_keep, *d_lm_stage;
+};
+int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep);
+
 }  // namespace sfmloc

@@ -1,0 +1,401 @@
+// sfmloc_tracks: feature tracks from pairwise matches (OpenMVG's TracksBuilder::Build + Filter), the first half of
+// openMVG_main_ComputeStructureFromKnownPoses.  The semantics are stated in include/sfmloc.h ("sfmloc_tracks"); the
+// kernels below name the paragraph they implement.
+//
+//   components  every match is an edge between two global feature rows.  parent[x] <= x always: a pass hooks, for every
+//               edge whose ends have different roots, the larger root under the smaller one (atomicMin on the root's
+//               parent, an integer minimum: the same whatever the order), then every node jumps to its root.  Passes
+//               repeat until one hooks nothing; then every edge has both ends under one root and a root is the smallest
+//               row of its component.  The fixed point does not depend on scheduling; only the number of passes does,
+//               and nothing reports it.
+//   order       the touched rows are compacted in ascending row (a scan, no atomic decides a position) and sorted by
+//               label with the stable radix sort of radix_sort.h: components ascend by label, rows ascend inside one.
+//   filter      two neighbours of one component in the same view are a conflict (rows of a view are contiguous, so
+//               two features of one view are neighbours after the sort); flags by atomicOr, counts by atomicAdd on
+//               integers.  Track ids and offsets are exclusive scans over the kept components.
+// The result is read back once and kept on the host: its consumer, sfmloc_sfm_create, takes host arrays.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <string>
+#include <vector>
+
+#include "radix_sort.h"
+#include "sfmloc_internal.h"
+#include "tracks_host.h"
+
+namespace sfmloc {
+namespace {
+
+thread_local double g_tracks_last_ms = 0.0;
+
+struct Tracks {
+  uint64_t counts[4] = {0, 0, 0, 0};  // components, dropped for conflict, dropped for length, kept
+  std::vector<uint64_t> off;          // [n_tracks + 1]
+  std::vector<uint32_t> view, feat;   // [off[n_tracks]]
+};
+
+__global__ __launch_bounds__(256) void k_trk_init(uint32_t *__restrict__ parent, uint32_t *__restrict__ touched,
+                                                  uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) parent[i] = i;
+  if (i <= n) touched[i] = 0;  // (entry n: where the scan leaves the total)
+}
+
+// (every writer stores the same 1)
+__global__ __launch_bounds__(256) void k_trk_mark(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
+                                                  uint32_t m, uint32_t *__restrict__ touched) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= m) return;
+  touched[ea[e]] = 1;
+  touched[eb[e]] = 1;
+}
+
+// the root of x; parent[] descends strictly until it, whatever other lanes hook meanwhile
+__device__ __forceinline__ uint32_t trk_find(const uint32_t *parent, uint32_t x) {
+  for (;;) {
+    const uint32_t p = __atomic_load_n(parent + x, __ATOMIC_RELAXED);
+    if (p == x) return x;
+    x = p;
+  }
+}
+
+// sfmloc.h "components": hook.  A root that another lane hooks at the same time keeps the smaller of the two parents;
+// the edge that lost is met again in the next pass, which is why the loop ends on a pass without a hook.
+__global__ __launch_bounds__(256) void k_trk_hook(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
+                                                  uint32_t m, uint32_t *parent, uint32_t *changed) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= m) return;
+  const uint32_t ra = trk_find(parent, ea[e]), rb = trk_find(parent, eb[e]);
+  if (ra == rb) return;
+  atomicMin(parent + (ra > rb ? ra : rb), ra > rb ? rb : ra);
+  *changed = 1;
+}
+
+// sfmloc.h "components": pointer jumping, all the way (no hook runs beside it: the roots stand still)
+__global__ __launch_bounds__(256) void k_trk_jump(uint32_t *parent, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = trk_find(parent, i);
+  __atomic_store_n(parent + i, r, __ATOMIC_RELAXED);
+}
+
+// ---- exclusive scan of a[0..n) in place over several workgroups: per-block scan + block totals, the totals scanned by
+// radix_sort.h's one-workgroup k_scan_excl, then added back
+__global__ __launch_bounds__(1024) void k_trk_scan_block(uint32_t *__restrict__ a, uint32_t n, uint32_t *__restrict__ sums) {
+  __shared__ uint32_t s[1024];
+  const int t = threadIdx.x;
+  const uint32_t i = blockIdx.x * 1024u + t;
+  const uint32_t v = i < n ? a[i] : 0u;
+  s[t] = v;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const uint32_t x = t >= off ? s[t - off] : 0u;
+    __syncthreads();
+    s[t] += x;
+    __syncthreads();
+  }
+  if (i < n) a[i] = s[t] - v;
+  if (t == 1023) sums[blockIdx.x] = s[1023];
+}
+__global__ __launch_bounds__(1024) void k_trk_scan_add(uint32_t *__restrict__ a, uint32_t n, const uint32_t *__restrict__ sums) {
+  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+  if (i < n) a[i] += sums[blockIdx.x];
+}
+
+// the touched rows in ascending row with their labels (pos = the scanned touched flags, [n + 1])
+__global__ __launch_bounds__(256) void k_trk_compact(const uint32_t *__restrict__ pos, const uint32_t *__restrict__ parent,
+                                                     uint32_t n, uint32_t *__restrict__ key, uint32_t *__restrict__ node) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || pos[i + 1] == pos[i]) return;
+  key[pos[i]] = parent[i];
+  node[pos[i]] = i;
+}
+
+// head[p] = 1 where a component starts in the sorted list; head[m] = 0 (where the scan leaves the component count)
+__global__ __launch_bounds__(256) void k_trk_heads(const uint32_t *__restrict__ key, uint32_t m, uint32_t *__restrict__ head) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p > m) return;
+  head[p] = (p < m && (p == 0 || key[p] != key[p - 1])) ? 1u : 0u;
+}
+
+// the view of a global feature row: the last v with view_off[v] <= row (views without features share an offset)
+__device__ __forceinline__ uint32_t trk_view_of(const uint32_t *__restrict__ view_off, uint32_t n_views, uint32_t row) {
+  uint32_t lo = 0, hi = n_views;  // view_off[lo] <= row < view_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (view_off[mid] <= row) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// sfmloc.h "filter": where every component starts, and whether two of its rows lie in one view.  ex = the scanned head
+// flags [m + 1]: position p belongs to component ex[p + 1] - 1.  conf is zero on entry.
+__global__ __launch_bounds__(256) void k_trk_components(const uint32_t *__restrict__ key, const uint32_t *__restrict__ node,
+                                                        const uint32_t *__restrict__ ex, uint32_t m,
+                                                        const uint32_t *__restrict__ view_off, uint32_t n_views,
+                                                        uint32_t *__restrict__ start, uint32_t *conf) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= m) return;
+  const uint32_t c = ex[p + 1] - 1;
+  if (ex[p + 1] != ex[p]) start[c] = p;
+  if (p == m - 1) start[c + 1] = m;
+  if (p > 0 && key[p] == key[p - 1] &&
+      trk_view_of(view_off, n_views, node[p]) == trk_view_of(view_off, n_views, node[p - 1]))
+    atomicOr(conf + c, 1u);
+}
+
+// kept[c] = 1 / size[c] = its rows for a component that stays, 0 / 0 otherwise; entry n_comp = 0 (the scans' totals);
+// counts: conflict, length, kept
+__global__ __launch_bounds__(256) void k_trk_filter(const uint32_t *__restrict__ start, const uint32_t *__restrict__ conf,
+                                                    uint32_t n_comp, uint32_t min_length, uint32_t *__restrict__ kept,
+                                                    uint32_t *__restrict__ size, uint32_t *counts) {
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c > n_comp) return;
+  uint32_t k = 0, sz = 0;
+  if (c < n_comp) {
+    sz = start[c + 1] - start[c];
+    if (conf[c]) atomicAdd(counts + 0, 1u);
+    else if (sz < min_length) atomicAdd(counts + 1, 1u);
+    else {
+      atomicAdd(counts + 2, 1u);
+      k = 1;
+    }
+  }
+  kept[c] = k;
+  size[c] = k ? sz : 0u;
+}
+
+// sfmloc.h "order": the rows of the kept components as (view, feature), track t at toff[c] .. ; tid / toff = the scanned
+// kept flags and sizes [n_comp + 1]
+__global__ __launch_bounds__(256) void k_trk_emit(const uint32_t *__restrict__ node, const uint32_t *__restrict__ ex,
+                                                  uint32_t m, const uint32_t *__restrict__ start,
+                                                  const uint32_t *__restrict__ tid, const uint32_t *__restrict__ toff,
+                                                  const uint32_t *__restrict__ view_off, uint32_t n_views,
+                                                  uint32_t *__restrict__ out_off, uint32_t *__restrict__ out_view,
+                                                  uint32_t *__restrict__ out_feat) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= m) return;
+  const uint32_t c = ex[p + 1] - 1;
+  if (tid[c + 1] == tid[c]) return;
+  const uint32_t at = toff[c] + (p - start[c]);
+  const uint32_t row = node[p], v = trk_view_of(view_off, n_views, row);
+  out_view[at] = v;
+  out_feat[at] = row - view_off[v];
+  if (p == start[c]) out_off[tid[c]] = toff[c];
+}
+
+int scan_excl(uint32_t *a, uint32_t n, uint32_t *sums, hipStream_t s) {
+  const uint32_t nb = (n + 1023) / 1024;
+  hipLaunchKernelGGL(k_trk_scan_block, dim3(nb), dim3(1024), 0, s, a, n, sums);
+  hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, sums, nb);
+  hipLaunchKernelGGL(k_trk_scan_add, dim3(nb), dim3(1024), 0, s, a, n, (const uint32_t *)sums);
+  SFM_HIP(hipGetLastError());
+  return SFMLOC_OK;
+}
+
+int read_u32(uint32_t *out, const uint32_t *d, hipStream_t s) {
+  SFM_HIP(hipMemcpyAsync(out, d, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  return SFMLOC_OK;
+}
+
+#define TRK_TRY(x)      \
+  do {                  \
+    const int rc_ = (x); \
+    if (rc_) return rc_; \
+  } while (0)
+
+int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint32_t n, const std::vector<uint32_t> &ea,
+                  const std::vector<uint32_t> &eb, uint32_t min_length, hipStream_t s, Tracks *t) {
+  (void)device;
+  const uint32_t m_edges = (uint32_t)ea.size();
+  std::vector<uint32_t> voff((size_t)n_views + 1);
+  for (uint32_t v = 0; v <= n_views; ++v) voff[v] = (uint32_t)view_off64[v];
+  DevBuf<uint32_t> d_voff, d_ea, d_eb, d_parent, d_touched, d_sums, d_flag;
+  TRK_TRY(d_voff.alloc(nullptr, voff.size()));
+  TRK_TRY(d_ea.alloc(nullptr, m_edges));
+  TRK_TRY(d_eb.alloc(nullptr, m_edges));
+  TRK_TRY(d_parent.alloc(nullptr, n));
+  TRK_TRY(d_touched.alloc(nullptr, (size_t)n + 1));
+  TRK_TRY(d_sums.alloc(nullptr, (size_t)n / 1024 + 2));
+  TRK_TRY(d_flag.alloc(nullptr, 4));  // changed, then the three counts of the filter
+  SFM_HIP(hipMemcpyAsync(d_voff, voff.data(), voff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  SFM_HIP(hipMemcpyAsync(d_ea, ea.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  SFM_HIP(hipMemcpyAsync(d_eb, eb.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  const dim3 gn((n + 1 + 255) / 256), ge((m_edges + 255) / 256), b256(256);
+  hipLaunchKernelGGL(k_trk_init, gn, b256, 0, s, d_parent.get(), d_touched.get(), n);
+  hipLaunchKernelGGL(k_trk_mark, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_touched.get());
+  SFM_HIP(hipGetLastError());
+  for (;;) {  // sfmloc.h "components": until a pass hooks nothing
+    SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_trk_hook, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_parent.get(),
+                       d_flag.get());
+    hipLaunchKernelGGL(k_trk_jump, gn, b256, 0, s, d_parent.get(), n);
+    SFM_HIP(hipGetLastError());
+    uint32_t changed = 0;
+    TRK_TRY(read_u32(&changed, d_flag, s));
+    if (!changed) break;
+  }
+  d_ea.reset();
+  d_eb.reset();
+  // the touched rows, ascending, with their labels
+  TRK_TRY(scan_excl(d_touched, n + 1, d_sums, s));
+  uint32_t m = 0;
+  TRK_TRY(read_u32(&m, d_touched.get() + n, s));
+  DevBuf<uint32_t> d_key, d_node, d_key2, d_node2, d_hist, d_ex;
+  TRK_TRY(d_key.alloc(nullptr, m));
+  TRK_TRY(d_node.alloc(nullptr, m));
+  TRK_TRY(d_key2.alloc(nullptr, m));
+  TRK_TRY(d_node2.alloc(nullptr, m));
+  TRK_TRY(d_hist.alloc(nullptr, radix_hist_entries(m)));
+  TRK_TRY(d_ex.alloc(nullptr, (size_t)m + 1));
+  hipLaunchKernelGGL(k_trk_compact, gn, b256, 0, s, (const uint32_t *)d_touched, (const uint32_t *)d_parent, n,
+                     d_key.get(), d_node.get());
+  SFM_HIP(hipGetLastError());
+  const bool swapped =
+      radix_sort_pairs(d_key, d_node, d_key2, d_node2, m, radix_key_bits(n - 1), d_hist, s);
+  SFM_HIP(hipGetLastError());
+  const uint32_t *key = swapped ? d_key2.get() : d_key.get(), *node = swapped ? d_node2.get() : d_node.get();
+  const dim3 gm((m + 1 + 255) / 256);
+  hipLaunchKernelGGL(k_trk_heads, gm, b256, 0, s, key, m, d_ex.get());
+  SFM_HIP(hipGetLastError());
+  TRK_TRY(scan_excl(d_ex, m + 1, d_sums, s));
+  uint32_t n_comp = 0;
+  TRK_TRY(read_u32(&n_comp, d_ex.get() + m, s));
+  d_parent.reset();
+  d_touched.reset();
+  DevBuf<uint32_t> d_start, d_conf, d_tid, d_toff;
+  TRK_TRY(d_start.alloc(nullptr, (size_t)n_comp + 1));
+  TRK_TRY(d_conf.alloc(nullptr, n_comp));
+  TRK_TRY(d_tid.alloc(nullptr, (size_t)n_comp + 1));
+  TRK_TRY(d_toff.alloc(nullptr, (size_t)n_comp + 1));
+  SFM_HIP(hipMemsetAsync(d_conf, 0, (size_t)n_comp * sizeof(uint32_t), s));
+  SFM_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(k_trk_components, gm, b256, 0, s, key, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_voff,
+                     n_views, d_start.get(), d_conf.get());
+  hipLaunchKernelGGL(k_trk_filter, dim3((n_comp + 1 + 255) / 256), b256, 0, s, (const uint32_t *)d_start,
+                     (const uint32_t *)d_conf, n_comp, min_length, d_tid.get(), d_toff.get(), d_flag.get() + 1);
+  SFM_HIP(hipGetLastError());
+  TRK_TRY(scan_excl(d_tid, n_comp + 1, d_sums, s));
+  TRK_TRY(scan_excl(d_toff, n_comp + 1, d_sums, s));
+  uint32_t n_tracks = 0, n_rows = 0, cnt[4] = {0, 0, 0, 0};
+  SFM_HIP(hipMemcpyAsync(cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, s));
+  TRK_TRY(read_u32(&n_tracks, d_tid.get() + n_comp, s));
+  TRK_TRY(read_u32(&n_rows, d_toff.get() + n_comp, s));
+  DevBuf<uint32_t> d_off, d_view, d_feat;
+  TRK_TRY(d_off.alloc(nullptr, n_tracks));
+  TRK_TRY(d_view.alloc(nullptr, n_rows));
+  TRK_TRY(d_feat.alloc(nullptr, n_rows));
+  hipLaunchKernelGGL(k_trk_emit, gm, b256, 0, s, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_start,
+                     (const uint32_t *)d_tid, (const uint32_t *)d_toff, (const uint32_t *)d_voff, n_views, d_off.get(),
+                     d_view.get(), d_feat.get());
+  SFM_HIP(hipGetLastError());
+  std::vector<uint32_t> off32(n_tracks);
+  t->view.resize(n_rows);
+  t->feat.resize(n_rows);
+  if (n_tracks) SFM_HIP(hipMemcpyAsync(off32.data(), d_off, (size_t)n_tracks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (n_rows) {
+    SFM_HIP(hipMemcpyAsync(t->view.data(), d_view, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(t->feat.data(), d_feat, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  SFM_HIP(hipStreamSynchronize(s));
+  t->off.assign(off32.begin(), off32.end());
+  t->off.push_back(n_rows);
+  t->counts[0] = n_comp;
+  t->counts[1] = cnt[1];
+  t->counts[2] = cnt[2];
+  t->counts[3] = cnt[3];
+  return SFMLOC_OK;
+}
+
+int tracks_build_impl(int device, const uint64_t *view_off, uint32_t n_views, const uint8_t *view_use,
+                      const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i,
+                      const uint32_t *match_j, uint32_t min_length, Tracks *t) {
+  std::vector<uint32_t> ea, eb;
+  uint64_t n_nodes = 0;
+  std::string err;
+  const int rc = tracks_host::flatten(view_off, n_views, view_use, pairs, n_pairs, offsets, match_i, match_j, &ea, &eb,
+                                      &n_nodes, &err);
+  SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
+  SFM_CHECK(device >= 0 && device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", device, ndev - 1);
+  g_tracks_last_ms = 0.0;
+  t->off.assign(1, 0);
+  if (ea.empty() || n_nodes == 0) return SFMLOC_OK;  // no match: no track, nothing to launch
+  SFM_HIP(hipSetDevice(device));
+  hipStream_t s = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SFM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  int rc_run = SFMLOC_EHIP;
+  if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
+    hipEventRecord(e0, s);
+    rc_run = tracks_device(device, view_off, n_views, (uint32_t)n_nodes, ea, eb, min_length < 1 ? 1 : min_length, s, t);
+    float ms = 0.f;
+    if (rc_run == SFMLOC_OK && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+        hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+      g_tracks_last_ms = ms;
+  } else {
+    set_error("sfmloc_tracks_build: hipEventCreate failed");
+  }
+  hipStreamSynchronize(s);
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  hipStreamDestroy(s);
+  return rc_run;
+}
+
+}  // namespace
+}  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" {
+
+int sfmloc_tracks_build(int device, const uint64_t *view_off, uint32_t n_views, const uint8_t *view_use,
+                        const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i,
+                        const uint32_t *match_j, uint32_t min_length, sfmloc_tracks **out) {
+  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_tracks_build: null argument");
+  *out = nullptr;
+  Tracks *t = new (std::nothrow) Tracks();
+  SFM_CHECK(t, SFMLOC_ENOMEM, "out of host memory");
+  int rc;
+  try {
+    rc = tracks_build_impl(device, view_off, n_views, view_use, pairs, n_pairs, offsets, match_i, match_j, min_length, t);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_tracks_build: out of host memory");
+    rc = SFMLOC_ENOMEM;
+  }
+  if (rc) {
+    delete t;
+    return rc;
+  }
+  *out = reinterpret_cast<sfmloc_tracks *>(t);
+  return SFMLOC_OK;
+}
+
+int sfmloc_tracks_counts(const sfmloc_tracks *tt, uint64_t *counts) {
+  SFM_CHECK(tt && counts, SFMLOC_EINVAL, "sfmloc_tracks_counts: null argument");
+  memcpy(counts, reinterpret_cast<const Tracks *>(tt)->counts, 4 * sizeof(uint64_t));
+  return SFMLOC_OK;
+}
+
+int sfmloc_tracks_read(const sfmloc_tracks *tt, uint64_t *off, uint32_t *view, uint32_t *feat) {
+  SFM_CHECK(tt, SFMLOC_EINVAL, "sfmloc_tracks_read: null handle");
+  const Tracks *t = reinterpret_cast<const Tracks *>(tt);
+  if (off) memcpy(off, t->off.data(), t->off.size() * sizeof(uint64_t));
+  if (view && !t->view.empty()) memcpy(view, t->view.data(), t->view.size() * sizeof(uint32_t));
+  if (feat && !t->feat.empty()) memcpy(feat, t->feat.data(), t->feat.size() * sizeof(uint32_t));
+  return SFMLOC_OK;
+}
+
+void sfmloc_tracks_destroy(sfmloc_tracks *t) { delete reinterpret_cast<Tracks *>(t); }
+
+double sfmloc_tracks_last_ms(void) { return g_tracks_last_ms; }
+
+}  // extern "C"
