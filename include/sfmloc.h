@@ -1204,6 +1204,9 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
 /* Test hook: allocation k (0..11) of the NEXT regrowth of a context's P3P workspace fails with SFMLOC_ENOMEM (one shot;
  * -1 disarms).  The regrowth has no counterpart in the reference (localization.cpp:479-509 has no size limit). */
 void sfmloc_debug_fail_p3p_alloc(int k);
+/* Test hook: the calling thread's k-th device allocation from now on (0 = the next) fails once with SFMLOC_ENOMEM, in
+ * whatever call makes it; -1 disarms.  An armed sfmloc_debug_fail_p3p_alloc takes the countdown over for its regrowth. */
+void sfmloc_debug_fail_next_alloc(int k);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement (params.profile = 1): accumulated HIP-event time per kernel on  */

@@ -58,59 +58,40 @@ struct Sfm {
   std::vector<std::vector<uint32_t>> inliers;
   bool resected = false, cleaned = false;
   // device
-  uint32_t *d_view_id = nullptr, *d_view_intr = nullptr, *d_view_pose = nullptr, *d_intr_type = nullptr;
-  double *d_intr = nullptr;
-  uint8_t *d_pose_valid = nullptr;
-  double *d_pose_R = nullptr, *d_pose_C = nullptr;
-  uint32_t *d_lm_id = nullptr;
-  double *d_lm_X = nullptr;
-  uint64_t *d_obs_off = nullptr;
-  uint32_t *d_obs_view = nullptr, *d_obs_lm = nullptr;
-  double *d_obs_x = nullptr;
-  uint32_t *d_vlist = nullptr, *d_vkey = nullptr, *d_view_off = nullptr, *d_hist = nullptr;
-  uint32_t *d_tmp_k = nullptr, *d_tmp_v = nullptr;
-  double *d_res = nullptr, *d_ray = nullptr, *d_mincos = nullptr;
-  uint8_t *d_obs_keep = nullptr, *d_lm_stage = nullptr;
-  uint32_t *d_pose_cnt = nullptr, *d_passes = nullptr;
+  DevBuf<uint32_t> d_view_id, d_view_intr, d_view_pose, d_intr_type;
+  DevBuf<double> d_intr;
+  DevBuf<uint8_t> d_pose_valid;
+  DevBuf<double> d_pose_R, d_pose_C;
+  DevBuf<uint32_t> d_lm_id;
+  DevBuf<double> d_lm_X;
+  DevBuf<uint64_t> d_obs_off;
+  DevBuf<uint32_t> d_obs_view, d_obs_lm;
+  DevBuf<double> d_obs_x;
+  DevBuf<uint32_t> d_vlist, d_vkey, d_view_off, d_hist;
+  DevBuf<uint32_t> d_tmp_k, d_tmp_v;
+  DevBuf<double> d_res, d_ray, d_mincos;
+  DevBuf<uint8_t> d_obs_keep, d_lm_stage;
+  DevBuf<uint32_t> d_pose_cnt, d_passes;
   // the separable adjustment (ba_separable.hip): t = -R C per pose, every pose's views (CSR by pose, ascending view
   // index), a block's costs and outcome; host copies of the keep masks for the pose check of a call after a cleanup
-  double *d_pose_t = nullptr, *d_blk_cost = nullptr;
-  uint32_t *d_pose_view_off = nullptr, *d_pose_views = nullptr, *d_blk_info = nullptr;
+  DevBuf<double> d_pose_t, d_blk_cost;
+  DevBuf<uint32_t> d_pose_view_off, d_pose_views, d_blk_info;
   std::vector<uint8_t> h_obs_keep, h_lm_stage;
   // K5's contexts hang off a map without descriptors: its log10 table, parameters and launch heuristics
   sfmloc_map *map = nullptr;
   std::vector<sfmloc_context *> ctx;
 };
 
-template <class T>
-int sfm_alloc(T **p, size_t n) {
-  SFM_HIP(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-  return SFMLOC_OK;
-}
-template <class T>
-int sfm_upload(T **p, const T *h, size_t n, hipStream_t s) {
-  int rc = sfm_alloc(p, n);
-  if (rc) return rc;
-  if (n) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-  return SFMLOC_OK;
-}
-
+// (the stream is drained before the handle's buffers go with it, and destroyed after them)
 void sfm_free(Sfm *h) {
   if (!h) return;
   hipSetDevice(h->device);
   if (h->s) hipStreamSynchronize(h->s);
   for (sfmloc_context *c : h->ctx) sfmloc_context_destroy(c);
   if (h->map) sfmloc_map_destroy(h->map);
-  void *ptrs[] = {h->d_view_id,  h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,     h->d_pose_valid,
-                  h->d_pose_R,   h->d_pose_C,    h->d_lm_id,     h->d_lm_X,      h->d_obs_off,  h->d_obs_view,
-                  h->d_obs_lm,   h->d_obs_x,     h->d_vlist,     h->d_vkey,      h->d_view_off, h->d_hist,
-                  h->d_tmp_k,    h->d_tmp_v,     h->d_res,       h->d_ray,       h->d_mincos,   h->d_obs_keep,
-                  h->d_lm_stage, h->d_pose_cnt,  h->d_passes,    h->d_pose_t,    h->d_blk_cost, h->d_pose_view_off,
-                  h->d_pose_views, h->d_blk_info};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  if (h->s) hipStreamDestroy(h->s);
+  const hipStream_t s = h->s;
   delete h;
+  if (s) hipStreamDestroy(s);
 }
 
 // ---- transpose: observations by landmark -> per-view lists in ascending landmark id (sfmloc.h "views") -------------
@@ -404,46 +385,48 @@ int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *
     rc = (x);          \
     if (rc) return rc; \
   } while (0)
-  ADJ_TRY(sfm_upload(&h->d_view_id, d->view_id, d->n_views, s));
-  ADJ_TRY(sfm_upload(&h->d_view_intr, d->view_intrinsic, d->n_views, s));
-  ADJ_TRY(sfm_upload(&h->d_view_pose, d->view_pose, d->n_views, s));
-  ADJ_TRY(sfm_upload(&h->d_intr_type, d->intrinsic_type, d->n_intrinsics, s));
-  ADJ_TRY(sfm_upload(&h->d_intr, d->intrinsic, 6 * (size_t)d->n_intrinsics, s));
-  ADJ_TRY(sfm_upload(&h->d_pose_valid, h->h_pose_valid.data(), d->n_poses, s));
-  ADJ_TRY(sfm_upload(&h->d_pose_R, d->pose_R, 9 * (size_t)d->n_poses, s));
-  ADJ_TRY(sfm_upload(&h->d_pose_C, d->pose_C, 3 * (size_t)d->n_poses, s));
-  ADJ_TRY(sfm_upload(&h->d_lm_id, d->landmark_id, d->n_landmarks, s));
-  ADJ_TRY(sfm_upload(&h->d_lm_X, d->landmark_X, 3 * (size_t)d->n_landmarks, s));
-  ADJ_TRY(sfm_upload(&h->d_obs_off, d->obs_off, (size_t)d->n_landmarks + 1, s));
-  ADJ_TRY(sfm_upload(&h->d_obs_view, d->obs_view, n_obs, s));
-  ADJ_TRY(sfm_upload(&h->d_obs_x, d->obs_x, 2 * n_obs, s));
-  ADJ_TRY(sfm_alloc(&h->d_obs_lm, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_vlist, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_vkey, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_tmp_k, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_tmp_v, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_hist, 256 * ((n_obs + kRadixBlock - 1) / kRadixBlock)));
-  ADJ_TRY(sfm_alloc(&h->d_view_off, (size_t)d->n_views + 1));
-  ADJ_TRY(sfm_alloc(&h->d_res, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_ray, 4 * n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_obs_keep, n_obs));
-  ADJ_TRY(sfm_alloc(&h->d_mincos, d->n_landmarks));
-  ADJ_TRY(sfm_alloc(&h->d_lm_stage, d->n_landmarks));
-  ADJ_TRY(sfm_alloc(&h->d_pose_cnt, d->n_poses));
-  ADJ_TRY(sfm_alloc(&h->d_passes, 1));
+  // (views, intrinsics and poses are not empty; the landmark and observation arrays may be, and still get an address)
+  const size_t lm1 = d->n_landmarks ? d->n_landmarks : 1, obs1 = n_obs ? n_obs : 1;
+  ADJ_TRY(dev_upload(nullptr, h->d_view_id, d->view_id, d->n_views, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_view_intr, d->view_intrinsic, d->n_views, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_view_pose, d->view_pose, d->n_views, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_intr_type, d->intrinsic_type, d->n_intrinsics, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_intr, d->intrinsic, 6 * (size_t)d->n_intrinsics, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_pose_valid, h->h_pose_valid.data(), d->n_poses, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_pose_R, d->pose_R, 9 * (size_t)d->n_poses, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_pose_C, d->pose_C, 3 * (size_t)d->n_poses, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_lm_id, d->landmark_id, d->n_landmarks, s, 1));
+  ADJ_TRY(dev_upload(nullptr, h->d_lm_X, d->landmark_X, 3 * (size_t)d->n_landmarks, s, 1));
+  ADJ_TRY(dev_upload(nullptr, h->d_obs_off, d->obs_off, (size_t)d->n_landmarks + 1, s));
+  ADJ_TRY(dev_upload(nullptr, h->d_obs_view, d->obs_view, n_obs, s, 1));
+  ADJ_TRY(dev_upload(nullptr, h->d_obs_x, d->obs_x, 2 * n_obs, s, 1));
+  ADJ_TRY(h->d_obs_lm.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_vlist.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_vkey.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_tmp_k.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_tmp_v.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_hist.alloc(nullptr, n_obs ? 256 * ((n_obs + kRadixBlock - 1) / kRadixBlock) : 1));
+  ADJ_TRY(h->d_view_off.alloc(nullptr, (size_t)d->n_views + 1));
+  ADJ_TRY(h->d_res.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_ray.alloc(nullptr, 4 * obs1));
+  ADJ_TRY(h->d_obs_keep.alloc(nullptr, obs1));
+  ADJ_TRY(h->d_mincos.alloc(nullptr, lm1));
+  ADJ_TRY(h->d_lm_stage.alloc(nullptr, lm1));
+  ADJ_TRY(h->d_pose_cnt.alloc(nullptr, d->n_poses));
+  ADJ_TRY(h->d_passes.alloc(nullptr, 1));
   {
     std::vector<uint32_t> pv_off((size_t)d->n_poses + 1, 0), pv(d->n_views);
     for (uint32_t v = 0; v < d->n_views; ++v) ++pv_off[d->view_pose[v] + 1];
     for (uint32_t p = 0; p < d->n_poses; ++p) pv_off[p + 1] += pv_off[p];
     std::vector<uint32_t> at(pv_off.begin(), pv_off.end() - 1);
     for (uint32_t v = 0; v < d->n_views; ++v) pv[at[d->view_pose[v]]++] = v;  // (ascending view index inside a pose)
-    ADJ_TRY(sfm_upload(&h->d_pose_view_off, pv_off.data(), pv_off.size(), s));
-    ADJ_TRY(sfm_upload(&h->d_pose_views, pv.data(), pv.size(), s));
+    ADJ_TRY(dev_upload(nullptr, h->d_pose_view_off, pv_off.data(), pv_off.size(), s));
+    ADJ_TRY(dev_upload(nullptr, h->d_pose_views, pv.data(), pv.size(), s));
     SFM_HIP(hipStreamSynchronize(s));  // (the vectors leave scope)
   }
-  ADJ_TRY(sfm_alloc(&h->d_pose_t, 3 * (size_t)d->n_poses));
-  ADJ_TRY(sfm_alloc(&h->d_blk_cost, 2 * (size_t)std::max(d->n_poses, d->n_landmarks)));
-  ADJ_TRY(sfm_alloc(&h->d_blk_info, (size_t)std::max(d->n_poses, d->n_landmarks)));
+  ADJ_TRY(h->d_pose_t.alloc(nullptr, 3 * (size_t)d->n_poses));
+  ADJ_TRY(h->d_blk_cost.alloc(nullptr, 2 * (size_t)std::max(d->n_poses, d->n_landmarks)));
+  ADJ_TRY(h->d_blk_info.alloc(nullptr, (size_t)std::max(d->n_poses, d->n_landmarks)));
   ADJ_TRY(sfm_transpose(h));
   const uint32_t vid0 = 0, voff[2] = {0, 0};
   sfmloc_map_desc md;

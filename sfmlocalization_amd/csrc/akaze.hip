@@ -2146,33 +2146,36 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   float thres = 0.001f;
   AkPlan plan;
   hipStream_t own_stream = nullptr;  // the one created with the extractor (stream may be a context's, see _share_stream)
-  uint8_t *d_gray = nullptr;
-  float *d_img = nullptr, *d_t0 = nullptr, *d_t1 = nullptr, *d_t2 = nullptr, *d_t3 = nullptr;
-  float *d_Lt = nullptr, *d_Lsmooth = nullptr, *d_Lx = nullptr, *d_Ly = nullptr, *d_Ldet = nullptr;  // per-level stacks
-  unsigned int *d_hist = nullptr;             // [0] hmax bits, [1..301] histogram + npoints
-  float *d_kcontrast = nullptr;
-  float *d_half_steps = nullptr;              // [level][64]: 0.5 * tsteps, for k_octave_resident
-  void *d_level_tab = nullptr;                // the LevelTab of this image size (the all-level kernels read it by pointer)
-  void *d_dev_levels = nullptr;               // the DevLevels of this extractor (k_orient_describe reads it by pointer)
+  DevBuf<uint8_t> d_gray;
+  DevBuf<float> d_img, d_t0, d_t1, d_t2, d_t3;
+  DevBuf<float> d_Lt, d_Lsmooth, d_Lx, d_Ly, d_Ldet;  // per-level stacks
+  DevBuf<unsigned int> d_hist;                // [0] hmax bits, [1..301] histogram + npoints
+  DevBuf<float> d_kcontrast;
+  DevBuf<float> d_half_steps;                 // [level][64]: 0.5 * tsteps, for k_octave_resident
+  DevBuf<LevelTab> d_level_tab;               // the LevelTab of this image size (the all-level kernels read it by pointer)
+  DevBuf<DevLevels> d_dev_levels;             // the DevLevels of this extractor (k_orient_describe reads it by pointer)
   // detection tail (k_extrema_seg .. k_suppress): the raster-ordered candidate list and the suppression's state
-  unsigned int *d_ncand = nullptr;            // [0] candidates, [1] keypoints, [2] rounds of the first pass, [3..5] clocks,
+  DevBuf<unsigned int> d_ncand;               // [0] candidates, [1] keypoints, [2] rounds of the first pass, [3..5] clocks,
                                               // [6] spilled A/P records, [7] spilled N records, [8] levels out of global arrays
   unsigned int cand_cap = 1u << 16;
   unsigned int n_seg = 0, segs_per_row = 0;
-  unsigned int *d_seg = nullptr;              // [n_seg + 1] counts, then (k_seg_scan) where each segment starts
-  unsigned int *d_seg_part = nullptr;         // [chunks + 1] k_seg_sum / k_seg_write: the chunks' sums, then arrivals
-  uint8_t *d_seg_x = nullptr;                 // [n_seg x kSegMax]
-  uint32_t *d_cxy = nullptr;
-  uint8_t *d_clevel = nullptr, *d_cstatus = nullptr, *d_cready = nullptr;
-  float *d_cresp = nullptr;
-  float2 *d_csub = nullptr;
+  DevBuf<unsigned int> d_seg;                 // [n_seg + 1] counts, then (k_seg_scan) where each segment starts
+  DevBuf<unsigned int> d_seg_part;            // [chunks + 1] k_seg_sum / k_seg_write: the chunks' sums, then arrivals
+  DevBuf<uint8_t> d_seg_x;                    // [n_seg x kSegMax]
+  DevBuf<uint32_t> d_cxy;
+  DevBuf<uint8_t> d_clevel, d_cstatus, d_cready;
+  DevBuf<float> d_cresp;
+  DevBuf<float2> d_csub;
   unsigned int sup_force_spill = 0, sup_force_global = 0;  // test hooks (SFMLOC_AKAZE_SUPPRESS, read when the extractor is made)
-  uint4 *d_nbr = nullptr;                     // [cand_cap x 2] k_suppress_nbr: the A and P lists
-  uint2 *d_nbr2 = nullptr;                    // [cand_cap] the N lists
-  unsigned int *d_ckey = nullptr;
-  int *d_cslot = nullptr;
-  float *d_resp = nullptr, *d_kp6 = nullptr;  // per keypoint: response; the six-float records of the C ABI
-  float2 *d_qkpt = nullptr, *d_qkpt6 = nullptr;  // the keypoints as a query holds them: (x, y), and after the .feat round trip
+  DevBuf<uint4> d_nbr;                        // [cand_cap x 2] k_suppress_nbr: the A and P lists
+  DevBuf<uint2> d_nbr2;                       // [cand_cap] the N lists
+  DevBuf<unsigned int> d_ckey;
+  DevBuf<int> d_cslot;
+  // the per-keypoint arrays, regrown as one set (ensure_kp_cap; d_angle's size is the capacity): response, the six-float
+  // records of the C ABI, the keypoints as a query holds them ((x, y), and after the .feat round trip), and below d_kp,
+  // d_angle, d_desc
+  DevBuf<float> d_resp, d_kp6;
+  DevBuf<float2> d_qkpt, d_qkpt6;
   unsigned int *h_counts = nullptr;           // pinned copy of d_ncand
   // sfmloc_akaze_detect_and_compute reads the counts and -- in the same transfer batch, before it knows the count -- the
   // first spec_n keypoints and descriptors into pinned memory: an image with no more keypoints than that costs ONE
@@ -2180,11 +2183,10 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   unsigned char *h_spec = nullptr;
   unsigned int spec_n = 512;
   static constexpr unsigned int kSpecMax = 4096;
-  float *d_gauss25 = nullptr, *d_win = nullptr;
-  uint16_t *d_pair = nullptr;
-  float *d_kp = nullptr, *d_angle = nullptr;
-  uint8_t *d_desc = nullptr;
-  unsigned int kp_cap = 0;
+  DevBuf<float> d_gauss25, d_win;
+  DevBuf<uint16_t> d_pair;
+  DevBuf<float> d_kp, d_angle;
+  DevBuf<uint8_t> d_desc;
 };
 
 namespace {
@@ -2406,9 +2408,9 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
   const LevelTab T = level_tab(a);
   // (the rows of the levels that were built: levels come in order; kAllPix pixels of a row per thread)
   const dim3 agrid(((a->w + 127) / 128 + kAllPix - 1) / kAllPix, T.row0[nlev]);
-  sfm_launch<ScharrXyAllBody>(a, k_scharr_xy_all, agrid, dim3(128), (uint32_t)0, a->d_Lsmooth, a->d_Lx, a->d_Ly, reinterpret_cast<const LevelTab *>(a->d_level_tab));
+  sfm_launch<ScharrXyAllBody>(a, k_scharr_xy_all, agrid, dim3(128), (uint32_t)0, a->d_Lsmooth, a->d_Lx, a->d_Ly, (const LevelTab *)a->d_level_tab);
   if (with_det)
-    sfm_launch<HessianDetAllBody>(a, k_hessian_det_all, agrid, dim3(128), (uint32_t)0, a->d_Lx, a->d_Ly, a->d_Ldet, reinterpret_cast<const LevelTab *>(a->d_level_tab));
+    sfm_launch<HessianDetAllBody>(a, k_hessian_det_all, agrid, dim3(128), (uint32_t)0, a->d_Lx, a->d_Ly, a->d_Ldet, (const LevelTab *)a->d_level_tab);
   AK_HIP(hipGetLastError());
   return SFMLOC_OK;
 #undef s
@@ -2432,27 +2434,18 @@ DevLevels dev_levels(const Akaze *a) {
 }
 
 int ensure_kp_cap(Akaze *a, unsigned int n) {
-  if (n <= a->kp_cap) return SFMLOC_OK;
-  if (a->d_kp) hipFree(a->d_kp);
-  if (a->d_angle) hipFree(a->d_angle);
-  if (a->d_desc) hipFree(a->d_desc);
-  a->d_kp = a->d_angle = nullptr;
-  a->d_desc = nullptr;
-  const unsigned int cap = std::max(n, 4096u);
-  if (a->d_resp) hipFree(a->d_resp);
-  if (a->d_kp6) hipFree(a->d_kp6);
-  a->d_resp = a->d_kp6 = nullptr;
-  if (a->d_qkpt) hipFree(a->d_qkpt);
-  if (a->d_qkpt6) hipFree(a->d_qkpt6);
-  a->d_qkpt = a->d_qkpt6 = nullptr;
-  AK_HIP(hipMalloc((void **)&a->d_qkpt, (size_t)cap * sizeof(float2)));
-  AK_HIP(hipMalloc((void **)&a->d_qkpt6, (size_t)cap * sizeof(float2)));
-  AK_HIP(hipMalloc((void **)&a->d_kp, (size_t)cap * 4 * sizeof(float)));
-  AK_HIP(hipMalloc((void **)&a->d_angle, (size_t)cap * sizeof(float)));
-  AK_HIP(hipMalloc((void **)&a->d_desc, ((size_t)cap + 64) * 64));  // (+ the zero rows up to a multiple of 64)
-  AK_HIP(hipMalloc((void **)&a->d_resp, (size_t)cap * sizeof(float)));
-  AK_HIP(hipMalloc((void **)&a->d_kp6, (size_t)cap * 6 * sizeof(float)));
-  a->kp_cap = cap;
+  if ((size_t)n * sizeof(float) <= a->d_angle.bytes()) return SFMLOC_OK;
+  const size_t cap = std::max(n, 4096u);
+  DevGroup g(nullptr);  // (all seven or none: a failure leaves the old set and its capacity)
+  g.add(a->d_qkpt, cap);
+  g.add(a->d_qkpt6, cap);
+  g.add(a->d_kp, cap * 4);
+  g.add(a->d_angle, cap);
+  g.add(a->d_desc, (cap + 64) * 64);  // (+ the zero rows up to a multiple of 64)
+  g.add(a->d_resp, cap);
+  g.add(a->d_kp6, cap * 6);
+  if (!g.ok()) return g.rc();
+  g.commit();
   return SFMLOC_OK;
 }
 
@@ -2468,7 +2461,7 @@ int orient_describe_enqueue(Akaze *a, const std::vector<float> &kin, unsigned in
     // (the keypoints go up ahead of anything recorded: nothing recorded for this extractor in the session reads d_kp)
     if (n) AK_HIP(hipMemcpyAsync(a->d_kp, kin.data(), (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, a->stream.unordered()));
     sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(grid_n), dim3(64), 0,
-                                   reinterpret_cast<const DevLevels *>(a->d_dev_levels), a->d_kp, (int)n, a->d_gauss25, a->d_win,
+                                   (const DevLevels *)a->d_dev_levels, a->d_kp, (int)n, a->d_gauss25, a->d_win,
                                    a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
                                    (const unsigned int *)nullptr, (const float *)nullptr, (float *)nullptr,
                                    (float2 *)nullptr, (float2 *)nullptr);
@@ -2518,7 +2511,7 @@ int akaze_compute_resident(Akaze *a, const float *d_kin, unsigned int n, int nee
   rc = build_scale_space(a, nullptr, need_levels, false);
   if (rc || n == 0) return rc;
   sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(n), dim3(64), 0,
-                                 reinterpret_cast<const DevLevels *>(a->d_dev_levels), d_kin, (int)n, a->d_gauss25, a->d_win,
+                                 (const DevLevels *)a->d_dev_levels, d_kin, (int)n, a->d_gauss25, a->d_win,
                                  a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
                                    (const unsigned int *)nullptr, (const float *)nullptr, (float *)nullptr,
                                    (float2 *)nullptr, (float2 *)nullptr);
@@ -2538,16 +2531,11 @@ void sfmloc_akaze_destroy(sfmloc_akaze *ak) {
   hipSetDevice(a->device);
   if (a->stream.own) hipStreamSynchronize(a->stream.own);
   gang_member_free(a);
-  void *ptrs[] = {a->d_gray, a->d_img, a->d_t0, a->d_t1, a->d_t2, a->d_t3, a->d_Lt, a->d_Lsmooth, a->d_Lx, a->d_Ly,
-                  a->d_Ldet, a->d_hist, a->d_kcontrast, a->d_half_steps, a->d_level_tab, a->d_dev_levels, a->d_ncand,
-                  a->d_gauss25, a->d_win, a->d_pair, a->d_kp, a->d_angle, a->d_desc, a->d_seg, a->d_seg_part, a->d_seg_x, a->d_cxy,
-                  a->d_clevel, a->d_cstatus, a->d_cready, a->d_cresp, a->d_csub, a->d_nbr, a->d_nbr2, a->d_ckey, a->d_cslot, a->d_resp, a->d_kp6, a->d_qkpt, a->d_qkpt6};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
   if (a->h_counts) hipHostFree(a->h_counts);
   if (a->h_spec) hipHostFree(a->h_spec);
-  if (a->own_stream) hipStreamDestroy(a->own_stream);
-  delete a;
+  const hipStream_t s = a->own_stream;
+  delete a;  // (its buffers go before its stream)
+  if (s) hipStreamDestroy(s);
 }
 
 int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_sublevels, float threshold,
@@ -2575,81 +2563,90 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   // (no stream yet: akaze_ensure_stream creates one at the first call that needs it -- an extractor that is given a
   // context's stream right away, or only ever works in sessions led by another, never needs one, and a stream that merely
   // EXISTS shares a hardware queue with streams that work: DESIGN.md 4 Concurrency)
+  int rc = SFMLOC_OK;
   hipError_t he = hipSuccess;
-  auto A = [&](void **p, size_t bytes) {
-    if (he == hipSuccess) he = hipMalloc(p, bytes);
-  };
-  A((void **)&a->d_gray, n0);
-  A((void **)&a->d_img, n0 * 4);
-  A((void **)&a->d_t0, n0 * 4);
-  A((void **)&a->d_t1, n0 * 4);
-  A((void **)&a->d_t2, n0 * 4);
-  A((void **)&a->d_t3, n0 * 4);
-  float **stacks[] = {&a->d_Lt, &a->d_Lsmooth, &a->d_Lx, &a->d_Ly, &a->d_Ldet};
-  for (float **sp : stacks) A((void **)sp, tot * 4);
-  A((void **)&a->d_hist, 304 * 4);
-  A((void **)&a->d_kcontrast, 4);
-  A((void **)&a->d_half_steps, (size_t)kMaxLevels * 64 * 4);
-  A((void **)&a->d_level_tab, sizeof(LevelTab));
-  A((void **)&a->d_dev_levels, sizeof(DevLevels));
+#define AK_NEW(buf, n)                       \
+  do {                                       \
+    if (!rc) rc = a->buf.alloc(nullptr, n);  \
+  } while (0)
+  AK_NEW(d_gray, n0);
+  AK_NEW(d_img, n0);
+  AK_NEW(d_t0, n0);
+  AK_NEW(d_t1, n0);
+  AK_NEW(d_t2, n0);
+  AK_NEW(d_t3, n0);
+  AK_NEW(d_Lt, tot);
+  AK_NEW(d_Lsmooth, tot);
+  AK_NEW(d_Lx, tot);
+  AK_NEW(d_Ly, tot);
+  AK_NEW(d_Ldet, tot);
+  AK_NEW(d_hist, 304);
+  AK_NEW(d_kcontrast, 1);
+  AK_NEW(d_half_steps, (size_t)kMaxLevels * 64);
+  AK_NEW(d_level_tab, 1);
+  AK_NEW(d_dev_levels, 1);
   {
     const LevelTab T0 = level_tab(a);
     a->segs_per_row = 2u * (unsigned int)((width + 127) / 128);
     a->n_seg = (unsigned int)T0.row0[T0.n] * a->segs_per_row;
   }
   const size_t cc = a->cand_cap;
-  A((void **)&a->d_ncand, 160 * sizeof(unsigned int));
-  A((void **)&a->d_seg, ((size_t)a->n_seg + 1) * sizeof(unsigned int));
-  A((void **)&a->d_seg_part, 1025 * sizeof(unsigned int));
-  if (he == hipSuccess) he = hipMemset(a->d_seg_part, 0, 1025 * sizeof(unsigned int));
-  if (he == hipSuccess) he = hipStreamSynchronize(nullptr);  // (null stream: the extractor's streams are not ordered with it)
-  A((void **)&a->d_seg_x, (size_t)a->n_seg * kSegMax);
-  A((void **)&a->d_cxy, cc * sizeof(uint32_t));
-  A((void **)&a->d_clevel, cc);
-  A((void **)&a->d_cstatus, cc);
-  A((void **)&a->d_cready, cc);
-  A((void **)&a->d_cresp, cc * sizeof(float));
-  A((void **)&a->d_csub, cc * sizeof(float2));
-  A((void **)&a->d_nbr, cc * 2 * sizeof(uint4));
-  A((void **)&a->d_nbr2, cc * sizeof(uint2));
+  AK_NEW(d_ncand, 160);
+  AK_NEW(d_seg, (size_t)a->n_seg + 1);
+  AK_NEW(d_seg_part, 1025);
+  if (!rc) he = hipMemset(a->d_seg_part, 0, 1025 * sizeof(unsigned int));
+  if (!rc && he == hipSuccess) he = hipStreamSynchronize(nullptr);  // (null stream: the extractor's streams are not ordered with it)
+  AK_NEW(d_seg_x, (size_t)a->n_seg * kSegMax);
+  AK_NEW(d_cxy, cc);
+  AK_NEW(d_clevel, cc);
+  AK_NEW(d_cstatus, cc);
+  AK_NEW(d_cready, cc);
+  AK_NEW(d_cresp, cc);
+  AK_NEW(d_csub, cc);
+  AK_NEW(d_nbr, cc * 2);
+  AK_NEW(d_nbr2, cc);
   if (const char *e = getenv("SFMLOC_AKAZE_SUPPRESS")) {  // test hooks: "spill" = every record spilled (the band scans
     a->sup_force_spill = strstr(e, "spill") != nullptr;    // decide everything), "global" = no level in LDS
     a->sup_force_global = strstr(e, "global") != nullptr;
   }
-  A((void **)&a->d_ckey, cc * sizeof(unsigned int));
-  A((void **)&a->d_cslot, cc * sizeof(int));
-  if (he == hipSuccess) he = hipHostMalloc((void **)&a->h_counts, 160 * sizeof(unsigned int), hipHostMallocDefault);
-  if (he == hipSuccess) he = hipHostMalloc((void **)&a->h_spec, (size_t)Akaze::kSpecMax * (6 * sizeof(float) + 64), hipHostMallocDefault);
-  if (he == hipSuccess && ensure_kp_cap(a, a->cand_cap) != SFMLOC_OK) he = hipErrorOutOfMemory;  // (never regrown later)
-  if (he == hipSuccess) {  // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
+  AK_NEW(d_ckey, cc);
+  AK_NEW(d_cslot, cc);
+  if (!rc) rc = ensure_kp_cap(a, a->cand_cap);  // (never regrown by a detection: it finds no more than cand_cap)
+  AK_NEW(d_gauss25, 49);
+  AK_NEW(d_win, 64);
+  AK_NEW(d_pair, 486 * 2);
+#undef AK_NEW
+  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_counts, 160 * sizeof(unsigned int), hipHostMallocDefault);
+  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_spec, (size_t)Akaze::kSpecMax * (6 * sizeof(float) + 64), hipHostMallocDefault);
+  if (!rc && he == hipSuccess) {  // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_suppress),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SuppressLds));
     he = attr;
   }
-  A((void **)&a->d_gauss25, 49 * 4);
-  A((void **)&a->d_win, 64 * 4);
-  A((void **)&a->d_pair, 486 * 2 * 2);
-  if (he == hipSuccess) {
+  if (!rc && he == hipSuccess) {
     std::vector<float> hs((size_t)kMaxLevels * 64, 0.0f);
     for (int i = 0; i < a->plan.nlev; ++i)
       for (int k = 0; k < a->plan.lev[i].nsteps && k < 64; ++k) hs[(size_t)i * 64 + k] = 0.5f * a->plan.lev[i].tsteps[k];
     he = hipMemcpy(a->d_half_steps, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
   }
-  if (he == hipSuccess) {
+  if (!rc && he == hipSuccess) {
     const LevelTab T = level_tab(a);
     he = hipMemcpy(a->d_level_tab, &T, sizeof(T), hipMemcpyHostToDevice);
   }
-  if (he == hipSuccess) {
+  if (!rc && he == hipSuccess) {
     const DevLevels LV = dev_levels(a);
     he = hipMemcpy(a->d_dev_levels, &LV, sizeof(LV), hipMemcpyHostToDevice);
   }
-  if (he == hipSuccess) he = hipMemcpy(a->d_gauss25, a->plan.gauss25, 49 * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(a->d_win, a->plan.win_ang1, 64 * 4, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(a->d_pair, a->plan.pair_tab, 486 * 2 * 2, hipMemcpyHostToDevice);
-  if (he != hipSuccess) {
+  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_gauss25, a->plan.gauss25, 49 * 4, hipMemcpyHostToDevice);
+  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_win, a->plan.win_ang1, 64 * 4, hipMemcpyHostToDevice);
+  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_pair, a->plan.pair_tab, 486 * 2 * 2, hipMemcpyHostToDevice);
+  if (!rc && he != hipSuccess) {
     set_error("sfmloc_akaze_create: %s", hipGetErrorString(he));
+    rc = he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
+  }
+  if (rc) {
     sfmloc_akaze_destroy(reinterpret_cast<sfmloc_akaze *>(a));
-    return he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
+    return rc;
   }
   *out = reinterpret_cast<sfmloc_akaze *>(a);
   return SFMLOC_OK;
@@ -2707,7 +2704,7 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   if (rc) return rc;
   const LevelTab T = level_tab(a);
   const dim3 egrid(((a->w + 127) / 128 + kSegPerWave - 1) / kSegPerWave, T.row0[T.n]);  // (kSegPerWave segments per wave)
-  const LevelTab *dT = reinterpret_cast<const LevelTab *>(a->d_level_tab);
+  const LevelTab *dT = (const LevelTab *)a->d_level_tab;
   CandArrays C{a->d_cxy, a->d_clevel, a->d_cresp, a->d_csub};
   sfm_launch<ExtremaSegBody>(a, k_extrema_seg, egrid, dim3(128), 0, a->d_Ldet, dT, a->thres, a->d_seg_x, a->d_seg, a->segs_per_row);
   {
@@ -2751,7 +2748,7 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   unsigned int dgrid = (unsigned int)((size_t)a->w * a->h / 96);
   dgrid = dgrid < 1024u ? 1024u : (dgrid > 16384u ? 16384u : dgrid);
   sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(dgrid), dim3(64), 0,
-                                 reinterpret_cast<const DevLevels *>(a->d_dev_levels), a->d_kp, 0, a->d_gauss25, a->d_win,
+                                 (const DevLevels *)a->d_dev_levels, a->d_kp, 0, a->d_gauss25, a->d_win,
                                  a->plan.n_win, a->d_pair, a->d_angle, a->d_desc, (const unsigned int *)(a->d_ncand + 1),
                                  (const float *)a->d_resp, a->d_kp6, a->d_qkpt, a->d_qkpt6);
   SFM_HIP(hipGetLastError());

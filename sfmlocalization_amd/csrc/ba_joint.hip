@@ -726,14 +726,6 @@ __global__ __launch_bounds__(256) void k_jt_commit(JtDev v) {
   }
 }
 
-template <class T>
-int jt_upload(DevBuf<T> &b, const std::vector<T> &h, hipStream_t s) {
-  const int rc = b.alloc(nullptr, h.size() ? h.size() : 1);
-  if (rc) return rc;
-  if (!h.empty()) SFM_HIP(hipMemcpyAsync(b.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  return SFMLOC_OK;
-}
-
 }  // namespace
 
 int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, const sfmloc_ba_joint_options &opt,
@@ -786,12 +778,12 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
     rc = (x);          \
     if (rc) return rc; \
   } while (0)
-  JT_TRY(jt_upload(d_ent, ent, st));
-  JT_TRY(jt_upload(d_pose_in, pose_in, st));
-  JT_TRY(jt_upload(d_intr_in, intr_in, st));
-  JT_TRY(jt_upload(d_lm_in, lm_in, st));
-  JT_TRY(jt_upload(d_iv_off, iv_off, st));
-  JT_TRY(jt_upload(d_iv, iv, st));
+  JT_TRY(dev_upload(nullptr, d_ent, ent.data(), ent.size(), st, 1));
+  JT_TRY(dev_upload(nullptr, d_pose_in, pose_in.data(), pose_in.size(), st, 1));
+  JT_TRY(dev_upload(nullptr, d_intr_in, intr_in.data(), intr_in.size(), st, 1));
+  JT_TRY(dev_upload(nullptr, d_lm_in, lm_in.data(), lm_in.size(), st, 1));
+  JT_TRY(dev_upload(nullptr, d_iv_off, iv_off.data(), iv_off.size(), st, 1));
+  JT_TRY(dev_upload(nullptr, d_iv, iv.data(), iv.size(), st, 1));
   JT_TRY(d_Rn.alloc(nullptr, 9 * (size_t)s.n_poses));
   JT_TRY(d_tn.alloc(nullptr, 3 * (size_t)s.n_poses));
   JT_TRY(d_Kn.alloc(nullptr, 6 * (size_t)hs.n_intr));

@@ -35,9 +35,10 @@ double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// test hook (sfmloc_debug_fail_p3p_alloc(k)): the k-th allocation of the NEXT regrowth fails; one shot, consumed atomically
-// by the regrowth that sees it (no environment variable: a stray one must not be able to fail a production allocation).
-// That regrowth arms g_fail_countdown for its own allocations (ctx_p3p_reserve).
+// test hooks (no environment variable: a stray one must not be able to fail a production allocation).
+// sfmloc_debug_fail_next_alloc(k) arms the calling thread's g_fail_countdown: its k-th dev_raw_alloc from now fails, once.
+// sfmloc_debug_fail_p3p_alloc(k): the k-th allocation of the NEXT regrowth fails; one shot, consumed atomically by the
+// regrowth that sees it, which arms g_fail_countdown for its own allocations (ctx_p3p_reserve).
 std::atomic<int> g_test_fail_alloc{-1};
 thread_local int g_fail_countdown = -1;
 thread_local hipError_t g_raw_alloc_err = hipSuccess;  // why the last dev_raw_alloc of this thread failed
@@ -66,24 +67,6 @@ namespace {
 template <typename T>
 int dev_alloc(uint64_t *acct, DevBuf<T> &p, size_t n) {
   return p.alloc(acct, n);
-}
-
-template <typename T>
-int dev_upload(uint64_t *acct, DevBuf<T> &p, const T *h, size_t n, hipStream_t s) {
-  int rc = dev_alloc(acct, p, n);
-  if (rc) return rc;
-  if (n) SFM_HIP(hipMemcpyAsync(p.get(), h, n * sizeof(T), hipMemcpyHostToDevice, s));
-  return SFMLOC_OK;
-}
-
-// BofModel (bow.hip) keeps raw pointers; h null: allocate only
-template <typename T>
-int bof_upload(T **p, const T *h, size_t n, hipStream_t s) {
-  *p = nullptr;
-  if (n == 0) return SFMLOC_OK;
-  SFM_HIP(hipMalloc((void **)p, n * sizeof(T)));
-  if (h) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-  return SFMLOC_OK;
 }
 
 // The P3P arrays that grow with a query's feature count, for `cap` correspondences, as one all-or-nothing set: a new
@@ -619,9 +602,10 @@ int ctx_p3p_reserve(Ctx *c, uint32_t n) {
   if (n <= c->p3p_cap) return SFMLOC_OK;
   uint32_t cap = c->p3p_cap;
   while (cap < n) cap <<= 1;
-  g_fail_countdown = g_test_fail_alloc.exchange(-1, std::memory_order_relaxed);
+  const int k = g_test_fail_alloc.exchange(-1, std::memory_order_relaxed);
+  if (k >= 0) g_fail_countdown = k;  // (the P3P hook; unarmed, the thread's own countdown stands)
   const int rc = ctx_p3p_workspace(c, cap);
-  g_fail_countdown = -1;
+  if (k >= 0) g_fail_countdown = -1;
   return rc;
 }
 
@@ -1031,9 +1015,9 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
   if (n_pad) {
     MAP_HIP(hipMemsetAsync(m->d_bank, 0, n_pad * 64, s));
     const uint64_t chunk = 16ull << 20;  // rows per staging chunk (1 GiB)
-    uint4 *d_stage = nullptr;
+    DevBuf<uint4> d_stage;
     const uint64_t stage_rows = std::min<uint64_t>(chunk, d->n_rows);
-    if (stage_rows) MAP_HIP(hipMalloc((void **)&d_stage, stage_rows * 64));
+    SFM_TRY(d_stage.alloc(nullptr, stage_rows * 4));
     for (uint64_t r0 = 0; r0 < d->n_rows; r0 += chunk) {
       const uint64_t n = std::min<uint64_t>(chunk, d->n_rows - r0);
       hipError_t ce = hipMemcpyAsync(d_stage, d->desc + r0 * 64, n * 64, hipMemcpyHostToDevice, s);
@@ -1046,13 +1030,12 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
           set_error("bank upload: %s", hipGetErrorString(ce));
           rc = SFMLOC_EHIP;
         }
-        hipFree(d_stage);
+        d_stage.reset();
         hipStreamDestroy(s);
         free_map(m);
         return rc;
       }
     }
-    if (d_stage) hipFree(d_stage);
   }
 
   {  // view tables + the phantom (empty) view at index n_views (sfmloc_internal.h)
@@ -1961,14 +1944,14 @@ int sfmloc_bof_create(const sfmloc_bof_desc *d, int device, sfmloc_bof **out) {
   // (the model's own stream is created by the first sfmloc_bof_compute: a model inside a sfmloc_imgbow works on that
   // object's stream and needs none -- an idle stream still shares a hardware queue with streams that work; the uploads
   // here go through the null stream)
-  if (!rc) rc = bof_upload(&b->d_centers, d->centers, (size_t)d->K * b->cdim, b->stream);
+  if (!rc) rc = dev_upload(nullptr, b->d_centers, d->centers, (size_t)d->K * b->cdim, b->stream);
   if (!rc && d->n_pca > 0) {
-    rc = bof_upload(&b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, b->stream);
-    if (!rc) rc = bof_upload(&b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, b->stream);
-    if (!rc) rc = bof_upload(&b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, b->stream);
+    rc = dev_upload(nullptr, b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, b->stream);
+    if (!rc) rc = dev_upload(nullptr, b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, b->stream);
+    if (!rc) rc = dev_upload(nullptr, b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, b->stream);
   }
-  if (!rc) rc = bof_upload(&b->d_counts, (const uint32_t *)nullptr, (size_t)b->K * b->cells, b->stream);
-  if (!rc) rc = bof_upload(&b->d_out, (const double *)nullptr, (size_t)b->K * b->cells, b->stream);
+  if (!rc) rc = b->d_counts.alloc(nullptr, (size_t)b->K * b->cells);
+  if (!rc) rc = b->d_out.alloc(nullptr, (size_t)b->K * b->cells);
   if (!rc && hipStreamSynchronize(b->stream) != hipSuccess) rc = SFMLOC_EHIP;
   if (rc) {
     sfmloc_bof_destroy(reinterpret_cast<sfmloc_bof *>(b));
@@ -1983,11 +1966,9 @@ void sfmloc_bof_destroy(sfmloc_bof *bof) {
   if (!b) return;
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  void *ptrs[] = {b->d_centers, b->d_pca_mean, b->d_pca_evec, b->d_pca_eval, b->d_counts, b->d_out, b->d_desc, b->d_kxy};
-  for (void *p : ptrs)
-    if (p) hipFree(p);
-  if (b->stream) hipStreamDestroy(b->stream);
-  delete b;
+  const hipStream_t s = b->stream;
+  delete b;  // (its buffers go before its stream)
+  if (s) hipStreamDestroy(s);
 }
 
 int sfmloc_bof_dim(const sfmloc_bof *bof) {
@@ -1999,14 +1980,12 @@ int sfmloc_bof_compute(sfmloc_bof *bof, const float *desc, const float *kpt_xy, 
   SFM_CHECK(bof && out_bow && (n == 0 || (desc && kpt_xy)), SFMLOC_EINVAL, "sfmloc_bof_compute: null argument");
   BofModel *b = reinterpret_cast<BofModel *>(bof);
   SFM_HIP(hipSetDevice(b->device));
-  if ((int)n > b->cap_n) {
-    if (b->d_desc) hipFree(b->d_desc);
-    if (b->d_kxy) hipFree(b->d_kxy);
-    b->d_desc = nullptr;
-    b->d_kxy = nullptr;
-    SFM_HIP(hipMalloc((void **)&b->d_desc, (size_t)n * b->in_dim * sizeof(float)));
-    SFM_HIP(hipMalloc((void **)&b->d_kxy, (size_t)n * 2 * sizeof(float)));
-    b->cap_n = (int)n;
+  if ((size_t)n * 2 * sizeof(float) > b->d_kxy.bytes()) {  // (the pair grows together or not at all)
+    DevGroup g(nullptr);
+    g.add(b->d_desc, (size_t)n * b->in_dim);
+    g.add(b->d_kxy, (size_t)n * 2);
+    if (!g.ok()) return g.rc();
+    g.commit();
   }
   if (!b->stream) SFM_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   if (n) {
@@ -2130,6 +2109,7 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
 }
 
 void sfmloc_debug_fail_p3p_alloc(int k) { sfmloc::g_test_fail_alloc.store(k, std::memory_order_relaxed); }
+void sfmloc_debug_fail_next_alloc(int k) { sfmloc::g_fail_countdown = k; }
 
 int sfmloc_debug_math(int device, int op, const double *in, int n, int in_stride, double *out, int out_stride) {
   SFM_CHECK(in && out && n > 0 && in_stride > 0 && out_stride > 0, SFMLOC_EINVAL, "sfmloc_debug_math: bad argument");
@@ -2137,23 +2117,16 @@ int sfmloc_debug_math(int device, int op, const double *in, int n, int in_stride
   hipError_t e = hipGetDeviceCount(&ndev);
   SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
   SFM_HIP(hipSetDevice(device));
-  double *d_in = nullptr, *d_out = nullptr;
-  SFM_HIP(hipMalloc((void **)&d_in, (size_t)n * in_stride * sizeof(double)));
-  hipError_t e2 = hipMalloc((void **)&d_out, (size_t)n * out_stride * sizeof(double));
-  if (e2 != hipSuccess) {
-    hipFree(d_in);
-    set_error("hipMalloc: %s", hipGetErrorString(e2));
-    return SFMLOC_ENOMEM;
-  }
-  int rc = SFMLOC_OK;
+  DevBuf<double> d_in, d_out;
+  int rc = d_in.alloc(nullptr, (size_t)n * in_stride);
+  if (!rc) rc = d_out.alloc(nullptr, (size_t)n * out_stride);
+  if (rc) return rc;
   e = hipMemcpy(d_in, in, (size_t)n * in_stride * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(d_out, 0, (size_t)n * out_stride * sizeof(double));
   if (e == hipSuccess) rc = launch_debug_math(op, d_in, n, in_stride, d_out, out_stride, nullptr);
   if (e == hipSuccess && rc == SFMLOC_OK) e = hipDeviceSynchronize();
   if (e == hipSuccess && rc == SFMLOC_OK)
     e = hipMemcpy(out, d_out, (size_t)n * out_stride * sizeof(double), hipMemcpyDeviceToHost);
-  hipFree(d_in);
-  hipFree(d_out);
   if (e != hipSuccess) {
     set_error("sfmloc_debug_math: %s", hipGetErrorString(e));
     return SFMLOC_EHIP;

@@ -121,40 +121,20 @@ __global__ __launch_bounds__(kUpdateThreads) void k_color_update(
   if (threadIdx.x == 0 && coloured) atomicSub(&st->remaining, coloured);
 }
 
-struct ColorDev {  // a call's device state: freed on every way out
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  void *ptrs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~ColorDev() {
-    if (s) hipStreamSynchronize(s);
-    for (void *p : ptrs)
-      if (p) hipFree(p);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-  }
-};
-
 int color_plan_impl(const SfmColorView &V, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs) {
-  ColorDev d;
-  d.s = V.s;
-  uint32_t *d_card = nullptr, *d_order = nullptr, *d_iter = nullptr;
-  unsigned long long *d_obs = nullptr;
-  ColorState *d_st = nullptr;
-  SFM_HIP(hipMalloc(&d.ptrs[0], (size_t)V.n_views * sizeof(uint32_t)));
-  SFM_HIP(hipMalloc(&d.ptrs[1], (size_t)V.n_views * sizeof(uint32_t)));
-  SFM_HIP(hipMalloc(&d.ptrs[2], (size_t)(V.n_lm ? V.n_lm : 1) * sizeof(uint32_t)));
-  SFM_HIP(hipMalloc(&d.ptrs[3], (size_t)(V.n_lm ? V.n_lm : 1) * sizeof(unsigned long long)));
-  SFM_HIP(hipMalloc(&d.ptrs[4], sizeof(ColorState)));
-  d_card = (uint32_t *)d.ptrs[0];
-  d_order = (uint32_t *)d.ptrs[1];
-  d_iter = (uint32_t *)d.ptrs[2];
-  d_obs = (unsigned long long *)d.ptrs[3];
-  d_st = (ColorState *)d.ptrs[4];
-  SFM_HIP(hipEventCreate(&d.e0));
-  SFM_HIP(hipEventCreate(&d.e1));
+  CallScope d;  // (on the handle's stream; before the buffers: destroyed after them)
+  DevBuf<uint32_t> d_card, d_order, d_iter;
+  DevBuf<unsigned long long> d_obs;
+  DevBuf<ColorState> d_st;
+  int rc;
+  if ((rc = d_card.alloc(nullptr, V.n_views)) || (rc = d_order.alloc(nullptr, V.n_views)) ||
+      (rc = d_iter.alloc(nullptr, V.n_lm ? V.n_lm : 1)) || (rc = d_obs.alloc(nullptr, V.n_lm ? V.n_lm : 1)) ||
+      (rc = d_st.alloc(nullptr, 1)))
+    return rc;
+  if ((rc = d.open(true, &g_color_last_ms, V.s))) return rc;
   SFM_HIP(hipMemsetAsync(d_st, 0, sizeof(ColorState), d.s));
   SFM_HIP(hipMemsetAsync(d_order, 0, (size_t)V.n_views * sizeof(uint32_t), d.s));
-  SFM_HIP(hipEventRecord(d.e0, d.s));
+  if ((rc = d.time_begin())) return rc;
   const uint32_t n_init = V.n_views > V.n_lm ? V.n_views : V.n_lm;
   hipLaunchKernelGGL(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.d_view_off, d_card, V.n_lm,
                      V.d_obs_off, d_iter, d_obs, d_st);
@@ -173,16 +153,13 @@ int color_plan_impl(const SfmColorView &V, uint32_t *order, uint32_t *n_order, u
     }
     SFM_HIP(hipGetLastError());
   }
-  SFM_HIP(hipEventRecord(d.e1, d.s));
+  if ((rc = d.time_end())) return rc;
   SFM_HIP(hipMemcpyAsync(order, d_order, (size_t)st.n_order * sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
   if (V.n_lm) {
     SFM_HIP(hipMemcpyAsync(lm_iter, d_iter, (size_t)V.n_lm * sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
     SFM_HIP(hipMemcpyAsync(lm_obs, d_obs, (size_t)V.n_lm * sizeof(uint64_t), hipMemcpyDeviceToHost, d.s));
   }
   SFM_HIP(hipStreamSynchronize(d.s));
-  float ms = 0.f;
-  SFM_HIP(hipEventElapsedTime(&ms, d.e0, d.e1));
-  g_color_last_ms = ms;
   *n_order = st.n_order;
   return SFMLOC_OK;
 }

@@ -1,6 +1,7 @@
-// Ownership of device memory for Map, Ctx and Query (sfmloc_internal.h): one owner per array, so that freeing and the
-// memory figures (sfmloc_map_info::hbm_bytes) need no list kept in step by hand.  No HIP here: raw allocation goes
-// through two functions that capi.hip defines over hipMalloc / hipFree (and tests/cpp/devmem.cpp over malloc).
+// Ownership of device memory, for every handle and call of the library: one owner per array, so that freeing and the
+// memory figures (sfmloc_map_info::hbm_bytes: Map and Ctx charge an account, nothing else does) need no list kept in
+// step by hand.  No HIP here: raw allocation goes through two functions that capi.hip defines over hipMalloc / hipFree
+// (and tests/cpp/devmem.cpp over malloc).
 #pragma once
 
 #include <stddef.h>

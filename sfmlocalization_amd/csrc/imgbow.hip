@@ -31,14 +31,14 @@ struct ImgBow {
   sfmloc_bof *bof = nullptr;       // the model (owned)
   sfmloc_akaze *ak = nullptr;      // size x size extractor, cv::AKAZE::create() defaults (owned)
   DenseGrayPlan plan;
-  uint8_t *d_src = nullptr;        // [h*w*channels]
+  DevBuf<uint8_t> d_src;           // [h*w*channels]
   uint8_t *h_src = nullptr;        // pinned staging of the same size
-  float *d_grid = nullptr;         // [n_grid x 4] x, y, size, class_id
-  float *d_kxy = nullptr;          // [n_grid x 2]
+  DevBuf<float> d_grid;            // [n_grid x 4] x, y, size, class_id
+  DevBuf<float> d_kxy;             // [n_grid x 2]
   uint32_t n_grid = 0;
-  uint32_t *d_counts = nullptr;
-  double *d_out = nullptr;         // [dim] the reference's float64 vector
-  float *d_out_f32 = nullptr;      // [dim] as the shortlist reads it (BoFUtils.cpp:51-54 converts to CV_32F)
+  DevBuf<uint32_t> d_counts;
+  DevBuf<double> d_out;            // [dim] the reference's float64 vector
+  DevBuf<float> d_out_f32;         // [dim] as the shortlist reads it (BoFUtils.cpp:51-54 converts to CV_32F)
   double *h_out = nullptr;         // pinned [dim]
   hipEvent_t ordered = nullptr;    // sfmloc_imgbow_order_before
   hipEvent_t staged = nullptr;     // the previous call's H2D out of h_src has completed
@@ -78,17 +78,15 @@ void sfmloc_imgbow_destroy(sfmloc_imgbow *p) {
     hipStream_t s = akaze_stream_now(reinterpret_cast<Akaze *>(ib->ak));
     if (s) (void)hipStreamSynchronize(s);
   }
-  dense_gray_plan_destroy(&ib->plan);
-  void *ptrs[] = {ib->d_src, ib->d_grid, ib->d_kxy, ib->d_counts, ib->d_out, ib->d_out_f32};
-  for (void *q : ptrs)
-    if (q) (void)hipFree(q);
   if (ib->h_src) (void)hipHostFree(ib->h_src);
   if (ib->h_out) (void)hipHostFree(ib->h_out);
   if (ib->staged) (void)hipEventDestroy(ib->staged);
   if (ib->ordered) (void)hipEventDestroy(ib->ordered);
-  if (ib->ak) sfmloc_akaze_destroy(ib->ak);
-  if (ib->bof) sfmloc_bof_destroy(ib->bof);
-  delete ib;
+  sfmloc_akaze *ak = ib->ak;
+  sfmloc_bof *bof = ib->bof;
+  delete ib;  // (its buffers go before the extractor's stream)
+  if (ak) sfmloc_akaze_destroy(ak);
+  if (bof) sfmloc_bof_destroy(bof);
 }
 
 int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t width, uint32_t height, uint32_t channels,
@@ -123,18 +121,19 @@ int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t widt
     ib->n_grid = (uint32_t)(grid.size() / 4);
     const BofModel *b = reinterpret_cast<const BofModel *>(ib->bof);
     const size_t dim = (size_t)b->K * b->cells, n_src = (size_t)width * height * channels;
-    hipError_t he = hipMalloc((void **)&ib->d_src, n_src);
-    if (he == hipSuccess) he = hipHostMalloc((void **)&ib->h_src, n_src, hipHostMallocDefault);
-    if (he == hipSuccess) he = hipMalloc((void **)&ib->d_grid, grid.size() * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc((void **)&ib->d_kxy, kxy.size() * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc((void **)&ib->d_counts, dim * sizeof(uint32_t));
-    if (he == hipSuccess) he = hipMalloc((void **)&ib->d_out, dim * sizeof(double));
-    if (he == hipSuccess) he = hipMalloc((void **)&ib->d_out_f32, dim * sizeof(float));
-    if (he == hipSuccess) he = hipHostMalloc((void **)&ib->h_out, dim * sizeof(double), hipHostMallocDefault);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&ib->staged, hipEventDisableTiming);
-    if (he == hipSuccess) he = hipMemcpy(ib->d_grid, grid.data(), grid.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(ib->d_kxy, kxy.data(), kxy.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (he != hipSuccess) {
+    rc = ib->d_src.alloc(nullptr, n_src);
+    if (!rc) rc = ib->d_counts.alloc(nullptr, dim);
+    if (!rc) rc = ib->d_out.alloc(nullptr, dim);
+    if (!rc) rc = ib->d_out_f32.alloc(nullptr, dim);
+    if (!rc) rc = dev_upload(nullptr, ib->d_grid, grid.data(), grid.size(), nullptr);
+    if (!rc) rc = dev_upload(nullptr, ib->d_kxy, kxy.data(), kxy.size(), nullptr);
+    // (the two uploads are waited for at once; if the second fails, grid outlives the destroy below, whose frees wait)
+    hipError_t he = hipSuccess;
+    if (!rc) he = hipStreamSynchronize(nullptr);
+    if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&ib->h_src, n_src, hipHostMallocDefault);
+    if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&ib->h_out, dim * sizeof(double), hipHostMallocDefault);
+    if (!rc && he == hipSuccess) he = hipEventCreateWithFlags(&ib->staged, hipEventDisableTiming);
+    if (!rc && he != hipSuccess) {
       set_error("sfmloc_imgbow_create: %s", hipGetErrorString(he));
       rc = he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
     }
@@ -154,7 +153,7 @@ int sfmloc_imgbow_dim(const sfmloc_imgbow *p) {
 
 const void *sfmloc_imgbow_vector_dev(const sfmloc_imgbow *p) {
   const ImgBow *ib = reinterpret_cast<const ImgBow *>(p);
-  return ib ? ib->d_out_f32 : nullptr;
+  return ib ? ib->d_out_f32.get() : nullptr;
 }
 
 // the context's stream waits for what this extractor has queued so far (an extractor on a stream of its own runs beside
@@ -208,7 +207,7 @@ int sfmloc_imgbow_compute(sfmloc_imgbow *p, const uint8_t *image, sfmloc_query *
   if (!rc) rc = akaze_compute_resident(a, ib->d_grid, ib->n_grid, 4);  // (the grid's four scales are levels 0 .. 3)
   if (rc) return rc;
   s = akaze_stream_now(a);
-  rc = launch_bof(b, s, nullptr, ib->d_kxy, (int)ib->n_grid, ib->d_counts, ib->d_out, q ? q->d_bow : ib->d_out_f32,
+  rc = launch_bof(b, s, nullptr, ib->d_kxy, (int)ib->n_grid, ib->d_counts, ib->d_out, q ? q->d_bow.get() : ib->d_out_f32.get(),
                   akaze_desc_dev(a));
   if (rc) return rc;
   ib->last_stream = s;

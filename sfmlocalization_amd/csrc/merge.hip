@@ -545,60 +545,14 @@ __global__ __launch_bounds__(256) void k_merge_transform(Mat34 T, double *__rest
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
-struct Dev {  // a call's device state: freed on every way out
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<void *> ptrs;
-  ~Dev() {
-    if (s) hipStreamSynchronize(s);
-    for (void *p : ptrs) hipFree(p);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (s) hipStreamDestroy(s);
-  }
-  template <class T>
-  int alloc(T **p, size_t n) {
-    SFM_HIP(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return SFMLOC_OK;
-  }
-  template <class T>
-  int upload(T **p, const T *h, size_t n) {
-    const int rc = alloc(p, n);
-    if (rc) return rc;
-    if (n) SFM_HIP(hipMemcpyAsync(*p, h, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return SFMLOC_OK;
-  }
-};
-
-int merge_open(const sfmloc_merge_params *params, sfmloc_merge_params *p, Dev *d) {
-  if (params) *p = *params;
-  else sfmloc_merge_default_params(p);
-  int ndev = 0;
-  const hipError_t e = hipGetDeviceCount(&ndev);
-  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
-  SFM_CHECK(p->device >= 0 && p->device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", p->device, ndev - 1);
-  SFM_HIP(hipSetDevice(p->device));
-  SFM_HIP(hipStreamCreateWithFlags(&d->s, hipStreamNonBlocking));
-  if (p->profile) {
-    SFM_HIP(hipEventCreate(&d->e0));
-    SFM_HIP(hipEventCreate(&d->e1));
-  }
-  g_merge_last_ms = 0.0;
-  return SFMLOC_OK;
+sfmloc_merge_params merge_params(const sfmloc_merge_params *params) {
+  sfmloc_merge_params p;
+  if (params) p = *params;
+  else sfmloc_merge_default_params(&p);
+  return p;
 }
 
-int merge_time_end(Dev *d) {
-  if (!d->e0) return SFMLOC_OK;
-  SFM_HIP(hipEventRecord(d->e1, d->s));
-  SFM_HIP(hipEventSynchronize(d->e1));
-  float ms = 0.f;
-  SFM_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
-  g_merge_last_ms = ms;
-  return SFMLOC_OK;
-}
-
-int launch_inliers(Dev *d, const double *dA, const double *dB, uint32_t n, const double *dM, const uint32_t *d_has,
+int launch_inliers(CallScope *d, const double *dA, const double *dB, uint32_t n, const double *dM, const uint32_t *d_has,
                    double thres, uint32_t *d_idx, uint32_t *d_n) {
   hipLaunchKernelGGL(k_merge_inliers, dim3(1), dim3(1024), 0, d->s, dA, dB, n, dM, d_has, thres, d_idx, d_n);
   SFM_HIP(hipGetLastError());
@@ -606,7 +560,7 @@ int launch_inliers(Dev *d, const double *dA, const double *dB, uint32_t n, const
 }
 
 template <int MODEL>
-int ransac_impl(Dev *d, const sfmloc_merge_params &p, const double *A, const double *B, uint32_t n, double thres,
+int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, const double *B, uint32_t n, double thres,
                 uint64_t rounds, double svd_ratio, uint32_t stream, sfmloc_merge_result *out, uint32_t *inliers,
                 uint32_t cap) {
   int lds = 0;
@@ -614,26 +568,26 @@ int ransac_impl(Dev *d, const sfmloc_merge_params &p, const double *A, const dou
   uint32_t tile = std::min<uint32_t>(kMergeTile, (uint32_t)lds / 48u);
   SFM_CHECK(tile >= 64, SFMLOC_EHIP, "sfmloc_merge_ransac: the device reports %d bytes of LDS per workgroup", lds);
   tile &= ~63u;
-  double *dA = nullptr, *dB = nullptr, *dM = nullptr, *dMf = nullptr;
-  unsigned long long *d_best = nullptr;
-  uint32_t *d_info = nullptr, *d_idx = nullptr, *d_n = nullptr, *d_ok = nullptr;
+  DevBuf<double> dA, dB, dM, dMf;
+  DevBuf<unsigned long long> d_best;
+  DevBuf<uint32_t> d_info, d_idx, d_n, d_ok;
   int rc;
 #define MRG_TRY(x)     \
   do {                 \
     rc = (x);          \
     if (rc) return rc; \
   } while (0)
-  MRG_TRY(d->upload(&dA, A, 3 * (size_t)n));
-  MRG_TRY(d->upload(&dB, B, 3 * (size_t)n));
-  MRG_TRY(d->alloc(&dM, 12));
-  MRG_TRY(d->alloc(&dMf, 12));
-  MRG_TRY(d->alloc(&d_best, 1));
-  MRG_TRY(d->alloc(&d_info, 3));
-  MRG_TRY(d->alloc(&d_idx, n));
-  MRG_TRY(d->alloc(&d_n, 1));
-  MRG_TRY(d->alloc(&d_ok, 1));
+  MRG_TRY(dev_upload(nullptr, dA, A, 3 * (size_t)n, d->s));
+  MRG_TRY(dev_upload(nullptr, dB, B, 3 * (size_t)n, d->s));
+  MRG_TRY(dM.alloc(nullptr, 12));
+  MRG_TRY(dMf.alloc(nullptr, 12));
+  MRG_TRY(d_best.alloc(nullptr, 1));
+  MRG_TRY(d_info.alloc(nullptr, 3));
+  MRG_TRY(d_idx.alloc(nullptr, n));
+  MRG_TRY(d_n.alloc(nullptr, 1));
+  MRG_TRY(d_ok.alloc(nullptr, 1));
   SFM_HIP(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), d->s));
-  if (d->e0) SFM_HIP(hipEventRecord(d->e0, d->s));
+  MRG_TRY(d->time_begin());
   const uint64_t per = p.rounds_per_launch ? p.rounds_per_launch : kMergeLaunchRounds;
   for (uint64_t r0 = 0; r0 < rounds; r0 += per) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(per, rounds - r0);
@@ -664,7 +618,7 @@ int ransac_impl(Dev *d, const sfmloc_merge_params &p, const double *A, const dou
     SFM_HIP(hipStreamSynchronize(d->s));
     out->has_model = ok;
   }
-  MRG_TRY(merge_time_end(d));
+  MRG_TRY(d->time_end());
   SFM_CHECK(!inliers || cap >= n_inl, SFMLOC_ECAP, "sfmloc_merge_ransac: %u entries, %u inliers", cap, n_inl);
   if (inliers && n_inl) SFM_HIP(hipMemcpy(inliers, d_idx, n_inl * sizeof(uint32_t), hipMemcpyDeviceToHost));
 #undef MRG_TRY
@@ -678,7 +632,7 @@ bool all_finite(const double *x, size_t n) {
 }
 
 // the k-th smallest (0-based) of n positive doubles as bit patterns: 8 passes over one byte each
-int radix_select(Dev *d, const uint64_t *dv, uint32_t n, uint32_t k, uint32_t *d_hist, uint64_t *out) {
+int radix_select(CallScope *d, const uint64_t *dv, uint32_t n, uint32_t k, uint32_t *d_hist, uint64_t *out) {
   uint64_t prefix = 0;
   uint32_t h[256];
   const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 1024);
@@ -728,10 +682,10 @@ int sfmloc_merge_ransac(const double *A, const double *B, uint64_t n, double thr
             (unsigned long long)rounds);
   if (n < 4 || rounds == 0) return SFMLOC_OK;  // no sample of 4: no model
   SFM_CHECK(A && B, SFMLOC_EINVAL, "sfmloc_merge_ransac: null points");
-  Dev d;
-  sfmloc_merge_params p;
-  int rc = merge_open(params, &p, &d);
-  if (rc) return rc;
+  const sfmloc_merge_params p = merge_params(params);
+  CallScope d;  // (before the buffers: destroyed after them)
+  int rc;
+  if ((rc = CallScope::use_device(p.device)) || (rc = d.open(p.profile, &g_merge_last_ms))) return rc;
   return model == SFMLOC_MERGE_AFFINE
              ? ransac_impl<SFMLOC_MERGE_AFFINE>(&d, p, A, B, (uint32_t)n, thres, rounds, svd_ratio, stream, out, inliers, cap)
              : ransac_impl<SFMLOC_MERGE_SIMILARITY>(&d, p, A, B, (uint32_t)n, thres, rounds, svd_ratio, stream, out, inliers,
@@ -745,19 +699,19 @@ int sfmloc_merge_inliers(const double *A, const double *B, uint64_t n, const dou
   SFM_CHECK(n <= kMergeMaxN, SFMLOC_ECAP, "sfmloc_merge_inliers: %llu matches (at most 2^24)", (unsigned long long)n);
   if (n == 0) return SFMLOC_OK;
   SFM_CHECK(A && B, SFMLOC_EINVAL, "sfmloc_merge_inliers: null points");
-  Dev d;
-  sfmloc_merge_params p;
-  int rc = merge_open(params, &p, &d);
-  if (rc) return rc;
-  double *dA = nullptr, *dB = nullptr, *dM = nullptr;
-  uint32_t *d_idx = nullptr, *d_n = nullptr;
-  if ((rc = d.upload(&dA, A, 3 * (size_t)n)) || (rc = d.upload(&dB, B, 3 * (size_t)n)) || (rc = d.upload(&dM, M, 12)) ||
-      (rc = d.alloc(&d_idx, n)) || (rc = d.alloc(&d_n, 1)))
+  const sfmloc_merge_params p = merge_params(params);
+  CallScope d;  // (before the buffers: destroyed after them)
+  int rc;
+  if ((rc = CallScope::use_device(p.device)) || (rc = d.open(p.profile, &g_merge_last_ms))) return rc;
+  DevBuf<double> dA, dB, dM;
+  DevBuf<uint32_t> d_idx, d_n;
+  if ((rc = dev_upload(nullptr, dA, A, 3 * (size_t)n, d.s)) || (rc = dev_upload(nullptr, dB, B, 3 * (size_t)n, d.s)) ||
+      (rc = dev_upload(nullptr, dM, M, 12, d.s)) || (rc = d_idx.alloc(nullptr, n)) || (rc = d_n.alloc(nullptr, 1)))
     return rc;
-  if (d.e0) SFM_HIP(hipEventRecord(d.e0, d.s));
+  if ((rc = d.time_begin())) return rc;
   rc = launch_inliers(&d, dA, dB, (uint32_t)n, dM, nullptr, thres, d_idx, d_n);
   if (rc) return rc;
-  if ((rc = merge_time_end(&d))) return rc;
+  if ((rc = d.time_end())) return rc;
   SFM_HIP(hipMemcpyAsync(n_out, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));
   SFM_CHECK(!idx || cap >= *n_out, SFMLOC_ECAP, "sfmloc_merge_inliers: %u entries, %u inliers", cap, *n_out);
@@ -772,25 +726,27 @@ int sfmloc_merge_median_nn(const double *X, uint64_t n, const sfmloc_merge_param
   if (n < 2) return SFMLOC_OK;
   SFM_CHECK(X, SFMLOC_EINVAL, "sfmloc_merge_median_nn: null points");
   SFM_CHECK(all_finite(X, 3 * (size_t)n), SFMLOC_EINVAL, "sfmloc_merge_median_nn: a coordinate is not finite");
-  Dev d;
-  sfmloc_merge_params p;
-  int rc = merge_open(params, &p, &d);
-  if (rc) return rc;
-  double *dX = nullptr, *d_dist = nullptr;
-  uint32_t *d_hist = nullptr;
-  if ((rc = d.upload(&dX, X, 3 * (size_t)n)) || (rc = d.alloc(&d_dist, n)) || (rc = d.alloc(&d_hist, 256))) return rc;
-  if (d.e0) SFM_HIP(hipEventRecord(d.e0, d.s));
+  const sfmloc_merge_params p = merge_params(params);
+  CallScope d;  // (before the buffers: destroyed after them)
+  int rc;
+  if ((rc = CallScope::use_device(p.device)) || (rc = d.open(p.profile, &g_merge_last_ms))) return rc;
+  DevBuf<double> dX, d_dist;
+  DevBuf<uint32_t> d_hist;
+  if ((rc = dev_upload(nullptr, dX, X, 3 * (size_t)n, d.s)) || (rc = d_dist.alloc(nullptr, n)) ||
+      (rc = d_hist.alloc(nullptr, 256)))
+    return rc;
+  if ((rc = d.time_begin())) return rc;
   hipLaunchKernelGGL(k_merge_nn, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, d.s, dX, (uint32_t)n, d_dist);
   SFM_HIP(hipGetLastError());
   // (distances are >= 0 and finite or +inf on overflow: they order as their bit patterns)
   uint64_t lo = 0, hi = 0;
   const uint32_t k_hi = (uint32_t)(n / 2);
-  if ((rc = radix_select(&d, reinterpret_cast<const uint64_t *>(d_dist), (uint32_t)n, k_hi, d_hist, &hi))) return rc;
+  if ((rc = radix_select(&d, reinterpret_cast<const uint64_t *>(d_dist.get()), (uint32_t)n, k_hi, d_hist, &hi))) return rc;
   lo = hi;
   if (n % 2 == 0 &&
-      (rc = radix_select(&d, reinterpret_cast<const uint64_t *>(d_dist), (uint32_t)n, k_hi - 1, d_hist, &lo)))
+      (rc = radix_select(&d, reinterpret_cast<const uint64_t *>(d_dist.get()), (uint32_t)n, k_hi - 1, d_hist, &lo)))
     return rc;
-  if ((rc = merge_time_end(&d))) return rc;
+  if ((rc = d.time_end())) return rc;
   double dlo, dhi;
   memcpy(&dlo, &lo, 8);
   memcpy(&dhi, &hi, 8);
@@ -804,20 +760,21 @@ int sfmloc_merge_transform(const double *M, double *R, uint64_t nR, double *X, u
   SFM_CHECK(nR <= kMergeMaxN && nX <= kMergeMaxN, SFMLOC_ECAP, "sfmloc_merge_transform: at most 2^24 rotations and points");
   SFM_CHECK((nR == 0 || R) && (nX == 0 || X), SFMLOC_EINVAL, "sfmloc_merge_transform: null array");
   if (nR + nX == 0) return SFMLOC_OK;
-  Dev d;
-  sfmloc_merge_params p;
-  int rc = merge_open(params, &p, &d);
-  if (rc) return rc;
-  double *dR = nullptr, *dX = nullptr;
-  if ((rc = d.upload(&dR, (const double *)R, 9 * (size_t)nR)) || (rc = d.upload(&dX, (const double *)X, 3 * (size_t)nX)))
+  const sfmloc_merge_params p = merge_params(params);
+  CallScope d;  // (before the buffers: destroyed after them)
+  int rc;
+  if ((rc = CallScope::use_device(p.device)) || (rc = d.open(p.profile, &g_merge_last_ms))) return rc;
+  DevBuf<double> dR, dX;  // (either may be empty and still has an address)
+  if ((rc = dev_upload(nullptr, dR, (const double *)R, 9 * (size_t)nR, d.s, 1)) ||
+      (rc = dev_upload(nullptr, dX, (const double *)X, 3 * (size_t)nX, d.s, 1)))
     return rc;
   Mat34 T;
   memcpy(T.m, M, sizeof T.m);
-  if (d.e0) SFM_HIP(hipEventRecord(d.e0, d.s));
+  if ((rc = d.time_begin())) return rc;
   hipLaunchKernelGGL(k_merge_transform, dim3((uint32_t)((nR + nX + 255) / 256)), dim3(256), 0, d.s, T, dR, (uint32_t)nR, dX,
                      (uint32_t)nX);
   SFM_HIP(hipGetLastError());
-  if ((rc = merge_time_end(&d))) return rc;
+  if ((rc = d.time_end())) return rc;
   if (nR) SFM_HIP(hipMemcpyAsync(R, dR, 9 * (size_t)nR * sizeof(double), hipMemcpyDeviceToHost, d.s));
   if (nX) SFM_HIP(hipMemcpyAsync(X, dX, 3 * (size_t)nX * sizeof(double), hipMemcpyDeviceToHost, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));

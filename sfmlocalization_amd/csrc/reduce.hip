@@ -331,47 +331,29 @@ __global__ __launch_bounds__(256) void k_reduce_order(uint32_t n, const uint32_t
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
-struct Dev {  // a call's device state: freed on every way out
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  std::vector<void *> ptrs;
-  ~Dev() {
-    if (s) hipStreamSynchronize(s);
-    for (void *p : ptrs) hipFree(p);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (s) hipStreamDestroy(s);
-  }
-  template <class T>
-  int alloc(T **p, size_t n) {
-    SFM_HIP(hipMalloc((void **)p, (n ? n : 1) * sizeof(T)));
-    ptrs.push_back(*p);
-    return SFMLOC_OK;
-  }
-  template <class T>
-  int zeros(T **p, size_t n) {
-    const int rc = alloc(p, n);
-    if (rc) return rc;
-    SFM_HIP(hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), s));
-    return SFMLOC_OK;
-  }
-};
+int zeros(CallScope *d, DevBuf<uint32_t> &b, size_t n) {
+  const int rc = b.alloc(nullptr, n);
+  if (rc) return rc;
+  SFM_HIP(hipMemsetAsync(b, 0, n * sizeof(uint32_t), d->s));
+  return SFMLOC_OK;
+}
 
 inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
-// v[0..n) becomes its exclusive prefix sums, in place (n <= 2^26: three levels of kScanChunk)
-int scan_exclusive(Dev *d, uint32_t *v, uint32_t n) {
+// v[0..n) becomes its exclusive prefix sums, in place (n <= 2^26: three levels of kScanChunk).  sums: the caller's, one
+// array of partial sums per level, which the kernels read after this has returned
+constexpr int kScanLevels = 3;
+int scan_exclusive(CallScope *d, uint32_t *v, uint32_t n, DevBuf<uint32_t> *sums) {
   if (n == 0) return SFMLOC_OK;
   const uint32_t blocks = (n + kScanChunk - 1) / kScanChunk;
-  uint32_t *sums = nullptr;
-  const int rc = d->alloc(&sums, blocks);
+  const int rc = sums->alloc(nullptr, blocks);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_reduce_scan_chunk, dim3(blocks), dim3(256), 0, d->s, v, n, sums);
+  hipLaunchKernelGGL(k_reduce_scan_chunk, dim3(blocks), dim3(256), 0, d->s, v, n, sums->get());
   SFM_HIP(hipGetLastError());
   if (blocks > 1) {
-    const int rc2 = scan_exclusive(d, sums, blocks);
+    const int rc2 = scan_exclusive(d, *sums, blocks, sums + 1);
     if (rc2) return rc2;
-    hipLaunchKernelGGL(k_reduce_scan_add, lanes(n), dim3(256), 0, d->s, v, n, sums);
+    hipLaunchKernelGGL(k_reduce_scan_add, lanes(n), dim3(256), 0, d->s, v, n, sums->get());
     SFM_HIP(hipGetLastError());
   }
   return SFMLOC_OK;
@@ -390,7 +372,7 @@ double from_ordered(uint64_t u) {
   return x;
 }
 
-int reduce_impl(Dev *d, const sfmloc_merge_params &p, const double *X, uint32_t n, const Mat34 &T, double thres, uint32_t knn,
+int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uint32_t n, const Mat34 &T, double thres, uint32_t knn,
                 uint32_t *owner, uint32_t *order, double *dist, sfmloc_reduce_result *out) {
   int rc;
 #define RDC_TRY(x)     \
@@ -398,19 +380,17 @@ int reduce_impl(Dev *d, const sfmloc_merge_params &p, const double *X, uint32_t 
     rc = (x);          \
     if (rc) return rc; \
   } while (0)
-  double *dX = nullptr, *dG = nullptr, *dsG = nullptr, *d_dist = nullptr;
-  unsigned long long *d_box = nullptr;
-  uint64_t *d_key = nullptr, *d_skey = nullptr, *d_dtmp = nullptr, *d_dbits = nullptr;
-  uint32_t *d_start = nullptr, *d_fill = nullptr, *d_sidx = nullptr, *d_rowoff = nullptr, *d_ctmp = nullptr, *d_col = nullptr;
-  uint32_t *d_roff = nullptr, *d_rfill = nullptr, *d_rlist = nullptr, *d_stamp = nullptr, *d_owner = nullptr;
-  uint32_t *d_state = nullptr, *d_ooff = nullptr, *d_order = nullptr;
-  RDC_TRY(d->alloc(&dX, 3 * (size_t)n));
-  SFM_HIP(hipMemcpyAsync(dX, X, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, d->s));
-  RDC_TRY(d->alloc(&dG, 3 * (size_t)n));
-  RDC_TRY(d->alloc(&d_box, 6));
+  DevBuf<double> dX, dG, dsG, d_dist;
+  DevBuf<unsigned long long> d_box;
+  DevBuf<uint64_t> d_key, d_skey, d_dtmp, d_dbits;
+  DevBuf<uint32_t> d_start, d_fill, d_sidx, d_rowoff, d_ctmp, d_col, d_roff, d_rfill, d_rlist, d_stamp, d_owner, d_state,
+      d_ooff, d_order, scan_tmp[4][kScanLevels];
+  RDC_TRY(dev_upload(nullptr, dX, X, 3 * (size_t)n, d->s));
+  RDC_TRY(dG.alloc(nullptr, 3 * (size_t)n));
+  RDC_TRY(d_box.alloc(nullptr, 6));
   SFM_HIP(hipMemsetAsync(d_box, 0xFF, 3 * sizeof(unsigned long long), d->s));
   SFM_HIP(hipMemsetAsync(d_box + 3, 0x00, 3 * sizeof(unsigned long long), d->s));
-  if (d->e0) SFM_HIP(hipEventRecord(d->e0, d->s));
+  RDC_TRY(d->time_begin());
   hipLaunchKernelGGL(k_reduce_global, lanes(n), dim3(256), 0, d->s, T, dX, n, dG, d_box);
   SFM_HIP(hipGetLastError());
   unsigned long long box[6];
@@ -431,19 +411,19 @@ int reduce_impl(Dev *d, const sfmloc_merge_params &p, const double *X, uint32_t 
   while (buckets < n) buckets <<= 1;
   gr.mask = buckets - 1;
 
-  RDC_TRY(d->alloc(&d_key, n));
-  RDC_TRY(d->zeros(&d_start, (size_t)buckets + 1));
+  RDC_TRY(d_key.alloc(nullptr, n));
+  RDC_TRY(zeros(d, d_start, (size_t)buckets + 1));
   hipLaunchKernelGGL(k_reduce_cell, lanes(n), dim3(256), 0, d->s, gr, dG, n, d_key, d_start);
   SFM_HIP(hipGetLastError());
-  RDC_TRY(scan_exclusive(d, d_start, buckets + 1));
-  RDC_TRY(d->zeros(&d_fill, buckets));
-  RDC_TRY(d->alloc(&dsG, 3 * (size_t)n));
-  RDC_TRY(d->alloc(&d_skey, n));
-  RDC_TRY(d->alloc(&d_sidx, n));
+  RDC_TRY(scan_exclusive(d, d_start, buckets + 1, scan_tmp[0]));
+  RDC_TRY(zeros(d, d_fill, buckets));
+  RDC_TRY(dsG.alloc(nullptr, 3 * (size_t)n));
+  RDC_TRY(d_skey.alloc(nullptr, n));
+  RDC_TRY(d_sidx.alloc(nullptr, n));
   hipLaunchKernelGGL(k_reduce_scatter, lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, d_start, d_fill, dsG, d_skey, d_sidx);
   SFM_HIP(hipGetLastError());
 
-  RDC_TRY(d->zeros(&d_rowoff, (size_t)n + 1));
+  RDC_TRY(zeros(d, d_rowoff, (size_t)n + 1));
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_rows<false>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn, d_start,
                      dsG, d_skey, d_sidx, d_rowoff, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
   SFM_HIP(hipGetLastError());
@@ -456,27 +436,28 @@ int reduce_impl(Dev *d, const sfmloc_merge_params &p, const double *X, uint32_t 
   for (uint32_t i = 0; i < n; ++i) n_pairs += rowcnt[i];
   SFM_CHECK(n_pairs <= kReduceMaxPairs, SFMLOC_ECAP, "sfmloc_reduce_points: %llu close pairs (at most 2^28)",
             (unsigned long long)n_pairs);
-  RDC_TRY(scan_exclusive(d, d_rowoff, n + 1));
-  RDC_TRY(d->alloc(&d_ctmp, n_pairs));
-  RDC_TRY(d->alloc(&d_dtmp, n_pairs));
-  RDC_TRY(d->alloc(&d_col, n_pairs));
-  RDC_TRY(d->alloc(&d_dbits, n_pairs));
+  RDC_TRY(scan_exclusive(d, d_rowoff, n + 1, scan_tmp[1]));
+  const size_t pairs1 = n_pairs ? n_pairs : 1;  // (no close pair: the arrays still have an address)
+  RDC_TRY(d_ctmp.alloc(nullptr, pairs1));
+  RDC_TRY(d_dtmp.alloc(nullptr, pairs1));
+  RDC_TRY(d_col.alloc(nullptr, pairs1));
+  RDC_TRY(d_dbits.alloc(nullptr, pairs1));
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_rows<true>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn, d_start,
                      dsG, d_skey, d_sidx, (uint32_t *)nullptr, d_rowoff, d_ctmp, d_dtmp);
   SFM_HIP(hipGetLastError());
-  RDC_TRY(d->zeros(&d_roff, (size_t)n + 1));
+  RDC_TRY(zeros(d, d_roff, (size_t)n + 1));
   hipLaunchKernelGGL(k_reduce_rowsort, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_ctmp, d_dtmp, d_col, d_dbits, d_roff);
   SFM_HIP(hipGetLastError());
-  RDC_TRY(scan_exclusive(d, d_roff, n + 1));
-  RDC_TRY(d->zeros(&d_rfill, n));
-  RDC_TRY(d->alloc(&d_rlist, n_pairs));
+  RDC_TRY(scan_exclusive(d, d_roff, n + 1, scan_tmp[2]));
+  RDC_TRY(zeros(d, d_rfill, n));
+  RDC_TRY(d_rlist.alloc(nullptr, pairs1));
   hipLaunchKernelGGL(k_reduce_transpose, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_roff, d_rfill, d_rlist);
   SFM_HIP(hipGetLastError());
 
-  RDC_TRY(d->zeros(&d_stamp, n));
-  RDC_TRY(d->alloc(&d_owner, n));
-  RDC_TRY(d->alloc(&d_dist, n));
-  RDC_TRY(d->alloc(&d_state, 2));
+  RDC_TRY(zeros(d, d_stamp, n));
+  RDC_TRY(d_owner.alloc(nullptr, n));
+  RDC_TRY(d_dist.alloc(nullptr, n));
+  RDC_TRY(d_state.alloc(nullptr, 2));
   uint32_t state[2] = {n, 0};
   SFM_HIP(hipMemcpyAsync(d_state, state, sizeof state, hipMemcpyHostToDevice, d->s));
   const uint32_t per = p.rounds_per_launch ? p.rounds_per_launch : kResolvePasses;
@@ -491,23 +472,17 @@ int reduce_impl(Dev *d, const sfmloc_merge_params &p, const double *X, uint32_t 
     SFM_CHECK(pass <= n + per, SFMLOC_EHIP, "sfmloc_reduce_points: %u points undecided after %u passes", state[0], pass - 1);
   }
 
-  RDC_TRY(d->zeros(&d_ooff, (size_t)n + 1));
-  RDC_TRY(d->alloc(&d_order, n));
+  RDC_TRY(zeros(d, d_ooff, (size_t)n + 1));
+  RDC_TRY(d_order.alloc(nullptr, n));
   SFM_HIP(hipMemsetAsync(d_order, 0xFF, (size_t)n * sizeof(uint32_t), d->s));
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_order<false>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner, d_ooff,
                      (const uint32_t *)nullptr, (uint32_t *)nullptr);
   SFM_HIP(hipGetLastError());
-  RDC_TRY(scan_exclusive(d, d_ooff, n + 1));
+  RDC_TRY(scan_exclusive(d, d_ooff, n + 1, scan_tmp[3]));
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_order<true>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner,
                      (uint32_t *)nullptr, d_ooff, d_order);
   SFM_HIP(hipGetLastError());
-  if (d->e0) {
-    SFM_HIP(hipEventRecord(d->e1, d->s));
-    SFM_HIP(hipEventSynchronize(d->e1));
-    float ms = 0.f;
-    SFM_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
-    g_reduce_last_ms = ms;
-  }
+  RDC_TRY(d->time_end());
   // the outputs, into the call's own buffers first: nothing of the caller's is written before every step has succeeded
   std::vector<uint32_t> h_owner(n), h_order(n);
   std::vector<double> h_dist(n);
@@ -563,17 +538,9 @@ int sfmloc_reduce_points(const double *X, uint64_t n, const double *A, double th
   sfmloc_merge_params p;
   if (params) p = *params;
   else sfmloc_merge_default_params(&p);
-  int ndev = 0;
-  const hipError_t e = hipGetDeviceCount(&ndev);
-  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
-  SFM_CHECK(p.device >= 0 && p.device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", p.device, ndev - 1);
-  SFM_HIP(hipSetDevice(p.device));
-  Dev d;
-  SFM_HIP(hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking));
-  if (p.profile) {
-    SFM_HIP(hipEventCreate(&d.e0));
-    SFM_HIP(hipEventCreate(&d.e1));
-  }
+  CallScope d;
+  int rc;
+  if ((rc = CallScope::use_device(p.device)) || (rc = d.open(p.profile, &g_reduce_last_ms))) return rc;
   return reduce_impl(&d, p, X, (uint32_t)n, T, thres, knn, owner, order, dist, out);
 }
 

@@ -134,6 +134,72 @@ struct HostResult {
   uint32_t pair_landmark[kP3pMaxN];
 };
 
+// One array into device memory: allocated (at least min_alloc elements, for an array that must have an address when it
+// is empty) and filled from the host on stream s.  acct: devmem.h.
+template <class T>
+inline int dev_upload(uint64_t *acct, DevBuf<T> &p, const T *h, size_t n, hipStream_t s, size_t min_alloc = 0) {
+  const int rc = p.alloc(acct, n > min_alloc ? n : min_alloc);
+  if (rc) return rc;
+  if (n) SFM_HIP(hipMemcpyAsync(p.get(), h, n * sizeof(T), hipMemcpyHostToDevice, s));
+  return SFMLOC_OK;
+}
+
+// A call's stream and its two timing events, let go on every way out.  Declare it before the call's DevBuf locals: they
+// are destroyed first, while kernels on the stream may still run, which is safe because hipFree waits for the device;
+// the stream is drained and destroyed after them.
+struct CallScope {
+  hipStream_t s = nullptr;
+  CallScope() = default;
+  CallScope(const CallScope &) = delete;
+  CallScope &operator=(const CallScope &) = delete;
+  ~CallScope() {
+    if (s) hipStreamSynchronize(s);
+    if (e0_) hipEventDestroy(e0_);
+    if (e1_) hipEventDestroy(e1_);
+    if (own_ && s) hipStreamDestroy(s);
+  }
+  // `device` exists and is the current one
+  static int use_device(int device) {
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
+    SFM_CHECK(device >= 0 && device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", device, ndev - 1);
+    SFM_HIP(hipSetDevice(device));
+    return SFMLOC_OK;
+  }
+  // a stream of its own on the current device, or a handle's; *ms: 0 now, and time_end's figure if `timed`
+  int open(bool timed, double *ms, hipStream_t borrowed = nullptr) {
+    own_ = !borrowed;
+    if (borrowed) s = borrowed;
+    else SFM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (timed) {
+      SFM_HIP(hipEventCreate(&e0_));
+      SFM_HIP(hipEventCreate(&e1_));
+    }
+    ms_ = ms;
+    *ms_ = 0.0;
+    return SFMLOC_OK;
+  }
+  int time_begin() {
+    if (e0_) SFM_HIP(hipEventRecord(e0_, s));
+    return SFMLOC_OK;
+  }
+  int time_end() {  // (waits for the work between the two)
+    if (!e0_) return SFMLOC_OK;
+    SFM_HIP(hipEventRecord(e1_, s));
+    SFM_HIP(hipEventSynchronize(e1_));
+    float ms = 0.f;
+    SFM_HIP(hipEventElapsedTime(&ms, e0_, e1_));
+    *ms_ = ms;
+    return SFMLOC_OK;
+  }
+
+ private:
+  hipEvent_t e0_ = nullptr, e1_ = nullptr;
+  bool own_ = false;
+  double *ms_ = nullptr;
+};
+
 struct Ctx;
 
 // Static, read-only after creation: the map as it sits in HBM.
@@ -408,12 +474,11 @@ int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t
 struct BofModel {
   int device = 0;
   int K = 0, cdim = 0, in_dim = 0, n_pca = 0, resized = 300, levels = 2, norm_type = 2, cells = 5;
-  float *d_centers = nullptr, *d_pca_mean = nullptr, *d_pca_evec = nullptr, *d_pca_eval = nullptr;
+  DevBuf<float> d_centers, d_pca_mean, d_pca_evec, d_pca_eval;
   // workspace of one call
-  uint32_t *d_counts = nullptr;
-  double *d_out = nullptr;
-  float *d_desc = nullptr, *d_kxy = nullptr;
-  int cap_n = 0;
+  DevBuf<uint32_t> d_counts;
+  DevBuf<double> d_out;
+  DevBuf<float> d_desc, d_kxy;  // a call's descriptors and points: regrown together (sfmloc_bof_compute)
   hipStream_t stream = nullptr;
 };
 struct ChainArgs;  // chain_device.h: what the shortlist's workgroup does on top of the shortlist (may be null)
@@ -437,9 +502,9 @@ int launch_bof_member(const BofModel *b, GangMember *m, const float *d_kxy, int 
 // for which BGR2GRAY is the identity, so one channel is resized).
 struct DenseGrayPlan {
   int w = 0, h = 0, channels = 3, size = 300;
-  int *d_xo = nullptr, *d_yo = nullptr;
-  short *d_xa = nullptr, *d_ya = nullptr;
-  unsigned int *d_mm = nullptr;
+  DevBuf<int> d_xo, d_yo;
+  DevBuf<short> d_xa, d_ya;
+  DevBuf<unsigned int> d_mm;
 };
 int dense_gray_plan_create(DenseGrayPlan *p, int w, int h, int channels, int size);
 void dense_gray_plan_destroy(DenseGrayPlan *p);

@@ -321,33 +321,15 @@ int tracks_build_impl(int device, const uint64_t *view_off, uint32_t n_views, co
   const int rc = tracks_host::flatten(view_off, n_views, view_use, pairs, n_pairs, offsets, match_i, match_j, &ea, &eb,
                                       &n_nodes, &err);
   SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
-  SFM_CHECK(device >= 0 && device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", device, ndev - 1);
+  int rc_dev = CallScope::use_device(device);
+  if (rc_dev) return rc_dev;
   g_tracks_last_ms = 0.0;
   t->off.assign(1, 0);
   if (ea.empty() || n_nodes == 0) return SFMLOC_OK;  // no match: no track, nothing to launch
-  SFM_HIP(hipSetDevice(device));
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SFM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  int rc_run = SFMLOC_EHIP;
-  if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-    hipEventRecord(e0, s);
-    rc_run = tracks_device(device, view_off, n_views, (uint32_t)n_nodes, ea, eb, min_length < 1 ? 1 : min_length, s, t);
-    float ms = 0.f;
-    if (rc_run == SFMLOC_OK && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-        hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-      g_tracks_last_ms = ms;
-  } else {
-    set_error("sfmloc_tracks_build: hipEventCreate failed");
-  }
-  hipStreamSynchronize(s);
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-  hipStreamDestroy(s);
-  return rc_run;
+  CallScope d;
+  if ((rc_dev = d.open(true, &g_tracks_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
+  rc_dev = tracks_device(device, view_off, n_views, (uint32_t)n_nodes, ea, eb, min_length < 1 ? 1 : min_length, d.s, t);
+  return rc_dev ? rc_dev : d.time_end();
 }
 
 }  // namespace

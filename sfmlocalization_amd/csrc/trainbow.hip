@@ -425,12 +425,6 @@ void jacobi_eigen(std::vector<double> a, int n, std::vector<double> *vals, std::
   }
 }
 
-template <typename T>
-void tb_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 }  // namespace
 
 struct BowTrain {
@@ -440,33 +434,25 @@ struct BowTrain {
   sfmloc_akaze *ak = nullptr;
   DenseGrayPlan plan;
   bool plan_ok = false;
-  float *d_grid = nullptr;
+  DevBuf<float> d_grid;
   uint32_t n_grid = 0;
-  uint8_t *d_src = nullptr;
-  size_t src_cap = 0;
+  DevBuf<uint8_t> d_src;
   std::vector<uint8_t> last_img;  // the image whose descriptors akaze_desc_dev holds
   uint32_t last_w = 0, last_h = 0, last_c = 0;
-  uint32_t *d_idx = nullptr;
-  uint32_t idx_cap = 0;
-  float *d_x = nullptr, *d_y = nullptr;  // the sample [cap x dim0] and the projection target
+  DevBuf<uint32_t> d_idx;
+  DevBuf<float> d_x, d_y;  // the sample [cap x dim0] and the projection target
   // PCA
   bool pca_ok = false;
   std::vector<double> mean, cov, evec, eval;
-  double *d_part = nullptr;
-  size_t part_cap = 0;  // doubles
-  double *d_mom = nullptr;
-  float *d_pmean = nullptr, *d_pevec = nullptr, *d_peval = nullptr;
+  DevBuf<double> d_part, d_mom;
+  DevBuf<float> d_pmean, d_pevec, d_peval;  // the projection's model: allocated together (sfmloc_bowtrain_project)
 };
 
 namespace {
 int tb_part(BowTrain *t, size_t doubles) {
-  if (t->part_cap >= doubles) return SFMLOC_OK;
+  if (t->d_part.bytes() >= doubles * sizeof(double)) return SFMLOC_OK;
   SFM_HIP(hipStreamSynchronize(t->s));
-  tb_free(t->d_part);
-  t->part_cap = 0;
-  SFM_HIP(hipMalloc((void **)&t->d_part, doubles * sizeof(double)));
-  t->part_cap = doubles;
-  return SFMLOC_OK;
+  return t->d_part.alloc(nullptr, doubles);
 }
 
 uint32_t tb_chunks(uint32_t n) { return (n + kTbChunk - 1) / kTbChunk; }
@@ -478,7 +464,7 @@ int tb_moments(BowTrain *t) {
   const uint32_t n_out = dim + dim * (dim + 1) / 2, chunks = tb_chunks(n);
   int rc = tb_part(t, (size_t)chunks * n_out);
   if (rc) return rc;
-  if (!t->d_mom) SFM_HIP(hipMalloc((void **)&t->d_mom, (size_t)(kTbMaxDim + kTbMaxDim * (kTbMaxDim + 1) / 2) * sizeof(double)));
+  if (!t->d_mom && (rc = t->d_mom.alloc(nullptr, (size_t)(kTbMaxDim + kTbMaxDim * (kTbMaxDim + 1) / 2)))) return rc;
   hipLaunchKernelGGL(k_tb_moments, dim3(chunks), dim3(256), 0, t->s, (const float *)t->d_x, n, dim, t->d_part);
   hipLaunchKernelGGL(k_tb_colsum, dim3((n_out + 255) / 256), dim3(256), 0, t->s, (const double *)t->d_part, chunks, n_out, t->d_mom);
   SFM_HIP(hipGetLastError());
@@ -517,35 +503,14 @@ struct TbKernels {
 };
 
 struct KmWork {
-  float *dist[3] = {nullptr, nullptr, nullptr};
-  double *dpart[3] = {nullptr, nullptr, nullptr};
-  PpPick *d_pick = nullptr;
-  int32_t *d_ids = nullptr, *d_labels = nullptr, *d_best_labels = nullptr;
-  float *d_mind = nullptr, *d_best_mind = nullptr, *d_cen[2] = {nullptr, nullptr}, *d_best_cen = nullptr;
-  double *d_psum = nullptr, *d_sum = nullptr, *d_shift = nullptr;
-  uint32_t *d_pcnt = nullptr, *d_cnt = nullptr;
-  ~KmWork() {
-    for (int i = 0; i < 3; ++i) {
-      tb_free(dist[i]);
-      tb_free(dpart[i]);
-    }
-    tb_free(d_pick);
-    tb_free(d_ids);
-    tb_free(d_labels);
-    tb_free(d_best_labels);
-    tb_free(d_mind);
-    tb_free(d_best_mind);
-    tb_free(d_cen[0]);
-    tb_free(d_cen[1]);
-    tb_free(d_best_cen);
-    tb_free(d_psum);
-    tb_free(d_sum);
-    tb_free(d_shift);
-    tb_free(d_pcnt);
-    tb_free(d_cnt);
-  }
+  DevBuf<float> dist[3];
+  DevBuf<double> dpart[3];
+  DevBuf<PpPick> d_pick;
+  DevBuf<int32_t> d_ids, d_labels, d_best_labels;
+  DevBuf<float> d_mind, d_best_mind, d_cen[2], d_best_cen;
+  DevBuf<double> d_psum, d_sum, d_shift;
+  DevBuf<uint32_t> d_pcnt, d_cnt;
 };
-
 
 template <int DMAX>
 int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, double eps, uint64_t seed, float *centers,
@@ -555,23 +520,25 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
   const hipStream_t s = t->s;
   const dim3 g_rows((n + 255) / 256), g_chunks((chunks + 255) / 256);
   KmWork w;
-  for (int i = 0; i < 3; ++i) {
-    SFM_HIP(hipMalloc((void **)&w.dist[i], (size_t)n * sizeof(float)));
-    SFM_HIP(hipMalloc((void **)&w.dpart[i], (size_t)chunks * sizeof(double)));
+  int rc = SFMLOC_OK;
+  for (int i = 0; i < 3 && !rc; ++i) {
+    rc = w.dist[i].alloc(nullptr, n);
+    if (!rc) rc = w.dpart[i].alloc(nullptr, chunks);
   }
-  SFM_HIP(hipMalloc((void **)&w.d_pick, 2 * sizeof(PpPick)));
-  SFM_HIP(hipMalloc((void **)&w.d_ids, (size_t)K * sizeof(int32_t)));
-  SFM_HIP(hipMalloc((void **)&w.d_labels, (size_t)n * sizeof(int32_t)));
-  SFM_HIP(hipMalloc((void **)&w.d_best_labels, (size_t)n * sizeof(int32_t)));
-  SFM_HIP(hipMalloc((void **)&w.d_mind, (size_t)n * sizeof(float)));
-  SFM_HIP(hipMalloc((void **)&w.d_best_mind, (size_t)n * sizeof(float)));
-  for (int i = 0; i < 2; ++i) SFM_HIP(hipMalloc((void **)&w.d_cen[i], (size_t)K * dim * sizeof(float)));
-  SFM_HIP(hipMalloc((void **)&w.d_best_cen, (size_t)K * dim * sizeof(float)));
-  SFM_HIP(hipMalloc((void **)&w.d_psum, (size_t)chunks * K * dim * sizeof(double)));
-  SFM_HIP(hipMalloc((void **)&w.d_sum, (size_t)K * dim * sizeof(double)));
-  SFM_HIP(hipMalloc((void **)&w.d_shift, sizeof(double)));
-  SFM_HIP(hipMalloc((void **)&w.d_pcnt, (size_t)chunks * K * sizeof(uint32_t)));
-  SFM_HIP(hipMalloc((void **)&w.d_cnt, (size_t)K * sizeof(uint32_t)));
+  if (!rc) rc = w.d_pick.alloc(nullptr, 2);
+  if (!rc) rc = w.d_ids.alloc(nullptr, K);
+  if (!rc) rc = w.d_labels.alloc(nullptr, n);
+  if (!rc) rc = w.d_best_labels.alloc(nullptr, n);
+  if (!rc) rc = w.d_mind.alloc(nullptr, n);
+  if (!rc) rc = w.d_best_mind.alloc(nullptr, n);
+  for (int i = 0; i < 2 && !rc; ++i) rc = w.d_cen[i].alloc(nullptr, (size_t)K * dim);
+  if (!rc) rc = w.d_best_cen.alloc(nullptr, (size_t)K * dim);
+  if (!rc) rc = w.d_psum.alloc(nullptr, (size_t)chunks * K * dim);
+  if (!rc) rc = w.d_sum.alloc(nullptr, (size_t)K * dim);
+  if (!rc) rc = w.d_shift.alloc(nullptr, 1);
+  if (!rc) rc = w.d_pcnt.alloc(nullptr, (size_t)chunks * K);
+  if (!rc) rc = w.d_cnt.alloc(nullptr, K);
+  if (rc) return rc;
   uint64_t rng = seed ? seed : 0xffffffffull;
   const double e = eps > 0 ? eps : 0.0, eps2 = e * e;
   const uint32_t iter_end = std::max(max_iter, 2u);
@@ -612,7 +579,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
             // the draw on dist (slot 0), the trial's potential on min(dist, d(x, x_ci)) (slot 1)
             hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[di], chunks,
                                (const float *)w.dist[di], n, u, w.d_pick);
-            Kn::pp_dist(g_rows, s, t->d_x, n, (int)dim, &w.d_pick->ci, 0, w.dist[di], w.dist[t2]);
+            Kn::pp_dist(g_rows, s, t->d_x, n, (int)dim, &w.d_pick.get()->ci, 0, w.dist[di], w.dist[t2]);
             hipLaunchKernelGGL(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, (const float *)w.dist[t2], n, w.dpart[t2]);
             hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[t2], chunks,
                                (const float *)w.dist[t2], n, -1.0, w.d_pick + 1);
@@ -695,19 +662,9 @@ void sfmloc_bowtrain_destroy(sfmloc_bowtrain *p) {
   if (!t) return;
   hipSetDevice(t->device);
   if (t->s) (void)hipStreamSynchronize(t->s);
-  if (t->plan_ok) dense_gray_plan_destroy(&t->plan);
-  tb_free(t->d_grid);
-  tb_free(t->d_src);
-  tb_free(t->d_idx);
-  tb_free(t->d_x);
-  tb_free(t->d_y);
-  tb_free(t->d_part);
-  tb_free(t->d_mom);
-  tb_free(t->d_pmean);
-  tb_free(t->d_pevec);
-  tb_free(t->d_peval);
-  if (t->ak) sfmloc_akaze_destroy(t->ak);
-  delete t;
+  sfmloc_akaze *ak = t->ak;
+  delete t;  // (its buffers go before the extractor's stream, which is the trainer's)
+  if (ak) sfmloc_akaze_destroy(ak);
 }
 
 int sfmloc_bowtrain_create(int device, uint32_t dim, uint32_t cap_rows, sfmloc_bowtrain **out) {
@@ -737,11 +694,10 @@ int sfmloc_bowtrain_create(int device, uint32_t dim, uint32_t cap_rows, sfmloc_b
     }
     t->n_grid = (uint32_t)(grid.size() / 4);
     t->s = akaze_stream_now(reinterpret_cast<Akaze *>(t->ak));
-    hipError_t he = hipMalloc((void **)&t->d_grid, grid.size() * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc((void **)&t->d_x, (size_t)cap_rows * dim * sizeof(float));
-    if (he == hipSuccess) he = hipMalloc((void **)&t->d_y, (size_t)cap_rows * dim * sizeof(float));
-    if (he == hipSuccess) he = hipMemcpyAsync(t->d_grid, grid.data(), grid.size() * sizeof(float), hipMemcpyHostToDevice, t->s);
-    if (he == hipSuccess) he = hipStreamSynchronize(t->s);
+    rc = dev_upload(nullptr, t->d_grid, grid.data(), grid.size(), t->s);
+    if (!rc) rc = t->d_x.alloc(nullptr, (size_t)cap_rows * dim);
+    if (!rc) rc = t->d_y.alloc(nullptr, (size_t)cap_rows * dim);
+    const hipError_t he = rc ? hipSuccess : hipStreamSynchronize(t->s);
     if (he != hipSuccess) {
       set_error("sfmloc_bowtrain_create: %s", hipGetErrorString(he));
       rc = he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
@@ -818,12 +774,10 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
       if (rc) return rc;
       t->plan_ok = true;
     }
-    if (t->src_cap < n_src) {
+    if (t->d_src.bytes() < n_src) {
       SFM_HIP(hipStreamSynchronize(t->s));
-      tb_free(t->d_src);
-      t->src_cap = 0;
-      SFM_HIP(hipMalloc((void **)&t->d_src, n_src));
-      t->src_cap = n_src;
+      const int rc = t->d_src.alloc(nullptr, n_src);
+      if (rc) return rc;
     }
     t->last_w = 0;  // (invalid until the extraction is queued)
     SFM_HIP(hipMemcpyAsync(t->d_src, bgr, n_src, hipMemcpyHostToDevice, t->s));
@@ -843,12 +797,10 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
     uint32_t k = (uint32_t)((float)rows * r);
     idx[j] = k < rows ? k : rows - 1;
   }
-  if (t->idx_cap < n_pick) {
+  if (t->d_idx.bytes() < (size_t)n_pick * sizeof(uint32_t)) {
     SFM_HIP(hipStreamSynchronize(t->s));
-    tb_free(t->d_idx);
-    t->idx_cap = 0;
-    SFM_HIP(hipMalloc((void **)&t->d_idx, (size_t)n_pick * sizeof(uint32_t)));
-    t->idx_cap = n_pick;
+    const int rc = t->d_idx.alloc(nullptr, n_pick);
+    if (rc) return rc;
   }
   SFM_HIP(hipMemcpyAsync(t->d_idx, idx.data(), (size_t)n_pick * sizeof(uint32_t), hipMemcpyHostToDevice, t->s));
   hipLaunchKernelGGL(k_tb_gather8, dim3((n_pick * t->dim + 255) / 256), dim3(256), 0, t->s,
@@ -910,9 +862,12 @@ int sfmloc_bowtrain_project(sfmloc_bowtrain *p, const sfmloc_bof_desc *pca) {
   SFM_HIP(hipSetDevice(t->device));
   const int in_dim = pca->in_dim, np = pca->n_pca;
   if (!t->d_pmean) {
-    SFM_HIP(hipMalloc((void **)&t->d_pmean, kTbMaxDim * sizeof(float)));
-    SFM_HIP(hipMalloc((void **)&t->d_pevec, kTbMaxDim * kTbMaxDim * sizeof(float)));
-    SFM_HIP(hipMalloc((void **)&t->d_peval, kTbMaxDim * sizeof(float)));
+    DevGroup g(nullptr);
+    g.add(t->d_pmean, kTbMaxDim);
+    g.add(t->d_pevec, kTbMaxDim * kTbMaxDim);
+    g.add(t->d_peval, kTbMaxDim);
+    if (!g.ok()) return g.rc();
+    g.commit();
   }
   SFM_HIP(hipMemcpyAsync(t->d_pmean, pca->pca_mean, in_dim * sizeof(float), hipMemcpyHostToDevice, t->s));
   SFM_HIP(hipMemcpyAsync(t->d_pevec, pca->pca_eigvec, (size_t)np * in_dim * sizeof(float), hipMemcpyHostToDevice, t->s));

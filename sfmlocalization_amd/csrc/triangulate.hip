@@ -309,6 +309,7 @@ __global__ __launch_bounds__(kTriBlock) void k_tri_landmarks(TriArgs A) {
 }  // namespace
 
 int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep) {
+  CallScope d;  // (on the handle's stream; before the buffers: destroyed after them)
   hipStream_t s = v.s;
   DevBuf<double> d_P;
   DevBuf<unsigned long long> d_cnt;
@@ -316,63 +317,48 @@ int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, 
   if (rc) return rc;
   rc = d_cnt.alloc(nullptr, 6);
   if (rc) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SFM_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) {
-    hipEventDestroy(e0);
-    set_error("sfmloc_sfm_triangulate: hipEventCreate failed");
-    return SFMLOC_EHIP;
-  }
+  double ms = 0.0;
+  if ((rc = d.open(true, &ms, s)) || (rc = d.time_begin())) return rc;
   unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-  float ms = 0.f;
-  const auto run = [&]() -> int {
-    SFM_HIP(hipEventRecord(e0, s));
-    SFM_HIP(hipMemsetAsync(d_cnt, 0, sizeof cnt, s));
-    hipLaunchKernelGGL(k_tri_views, dim3((v.n_views + 255) / 256), dim3(256), 0, s, v.n_views, v.d_view_intr,
-                       v.d_view_pose, v.d_intr, (const double *)v.d_pose_R, (const double *)v.d_pose_C, d_P.get());
-    if (v.n_obs)
-      hipLaunchKernelGGL(k_tri_pixels, dim3((unsigned)((v.n_obs + 255) / 256)), dim3(256), 0, s, v.n_obs, v.d_obs_view,
-                         v.d_obs_x, v.d_view_intr, v.d_intr_type, v.d_intr, v.d_ud);
-    SFM_HIP(hipGetLastError());
-    TriArgs A;
-    A.n_lm = v.n_lm;
-    A.mode = opt.mode;
-    A.min_inliers = opt.min_inliers;
-    A.allow_pairs = opt.allow_pairs;
-    A.thr = opt.residual_px;
-    A.seed = v.seed;
-    A.view_intr = v.d_view_intr;
-    A.view_pose = v.d_view_pose;
-    A.intr_type = v.d_intr_type;
-    A.intr = v.d_intr;
-    A.pose_valid = v.d_pose_valid;
-    A.pose_R = v.d_pose_R;
-    A.pose_C = v.d_pose_C;
-    A.lm_id = v.d_lm_id;
-    A.obs_off = v.d_obs_off;
-    A.obs_view = v.d_obs_view;
-    A.obs_x = v.d_obs_x;
-    A.ud = v.d_ud;
-    A.P = d_P;
-    A.lm_X = v.d_lm_X;
-    A.obs_keep = v.d_obs_keep;
-    A.lm_stage = v.d_lm_stage;
-    A.counters = d_cnt;
-    if (v.n_lm) {
-      const uint64_t lanes = (uint64_t)v.n_lm * kTriLanes;
-      hipLaunchKernelGGL(k_tri_landmarks, dim3((unsigned)((lanes + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, s, A);
-    }
-    SFM_HIP(hipGetLastError());
-    SFM_HIP(hipEventRecord(e1, s));
-    SFM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipStreamSynchronize(s));
-    SFM_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return SFMLOC_OK;
-  };
-  rc = run();
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (rc) return rc;
+  SFM_HIP(hipMemsetAsync(d_cnt, 0, sizeof cnt, s));
+  hipLaunchKernelGGL(k_tri_views, dim3((v.n_views + 255) / 256), dim3(256), 0, s, v.n_views, v.d_view_intr,
+                     v.d_view_pose, v.d_intr, (const double *)v.d_pose_R, (const double *)v.d_pose_C, d_P.get());
+  if (v.n_obs)
+    hipLaunchKernelGGL(k_tri_pixels, dim3((unsigned)((v.n_obs + 255) / 256)), dim3(256), 0, s, v.n_obs, v.d_obs_view,
+                       v.d_obs_x, v.d_view_intr, v.d_intr_type, v.d_intr, v.d_ud);
+  SFM_HIP(hipGetLastError());
+  TriArgs A;
+  A.n_lm = v.n_lm;
+  A.mode = opt.mode;
+  A.min_inliers = opt.min_inliers;
+  A.allow_pairs = opt.allow_pairs;
+  A.thr = opt.residual_px;
+  A.seed = v.seed;
+  A.view_intr = v.d_view_intr;
+  A.view_pose = v.d_view_pose;
+  A.intr_type = v.d_intr_type;
+  A.intr = v.d_intr;
+  A.pose_valid = v.d_pose_valid;
+  A.pose_R = v.d_pose_R;
+  A.pose_C = v.d_pose_C;
+  A.lm_id = v.d_lm_id;
+  A.obs_off = v.d_obs_off;
+  A.obs_view = v.d_obs_view;
+  A.obs_x = v.d_obs_x;
+  A.ud = v.d_ud;
+  A.P = d_P;
+  A.lm_X = v.d_lm_X;
+  A.obs_keep = v.d_obs_keep;
+  A.lm_stage = v.d_lm_stage;
+  A.counters = d_cnt;
+  if (v.n_lm) {
+    const uint64_t lanes = (uint64_t)v.n_lm * kTriLanes;
+    hipLaunchKernelGGL(k_tri_landmarks, dim3((unsigned)((lanes + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, s, A);
+  }
+  SFM_HIP(hipGetLastError());
+  if ((rc = d.time_end())) return rc;
+  SFM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
   if (rep) {
     rep->landmarks_in = v.n_lm;
     rep->landmarks_kept = cnt[0];

@@ -27,10 +27,9 @@ struct Undistorter {
   int32_t roi[4];               // x y w h
   std::vector<int16_t> h_xy;    // [h*w*2] integer source coordinates
   std::vector<uint16_t> h_frac; // [h*w] (fy << 5) | fx
-  short2 *d_xy = nullptr;
-  uint16_t *d_frac = nullptr;
-  uint8_t *d_src = nullptr, *d_dst = nullptr;
-  size_t src_cap = 0, dst_cap = 0;
+  DevBuf<short2> d_xy;  // the map pair: on the device together or not at all
+  DevBuf<uint16_t> d_frac;
+  DevBuf<uint8_t> d_src, d_dst;
   hipStream_t stream = nullptr;
 };
 
@@ -225,12 +224,10 @@ extern "C" void sfmloc_undistorter_destroy(sfmloc_undistorter *handle) {
   Undistorter *u = reinterpret_cast<Undistorter *>(handle);
   if (!u) return;
   if (u->d_xy || u->d_src || u->stream) hipSetDevice(u->device);
-  if (u->d_xy) hipFree(u->d_xy);
-  if (u->d_frac) hipFree(u->d_frac);
-  if (u->d_src) hipFree(u->d_src);
-  if (u->d_dst) hipFree(u->d_dst);
-  if (u->stream) hipStreamDestroy(u->stream);
-  delete u;
+  const hipStream_t s = u->stream;
+  if (s) hipStreamSynchronize(s);
+  delete u;  // (its buffers go before its stream)
+  if (s) hipStreamDestroy(s);
 }
 
 extern "C" int sfmloc_undistorter_info(const sfmloc_undistorter *handle, double *new_camera, int32_t *roi) {
@@ -264,24 +261,18 @@ extern "C" int sfmloc_undistorter_apply(sfmloc_undistorter *handle, const uint8_
   SFM_HIP(hipSetDevice(u->device));
   if (!u->d_xy) {  // first image: the maps go to the device (the plan itself is host arithmetic and needs none)
     const size_t n = (size_t)u->w * u->h;
-    SFM_HIP(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
-    SFM_HIP(hipMalloc((void **)&u->d_xy, n * sizeof(short2)));
-    SFM_HIP(hipMalloc((void **)&u->d_frac, n * sizeof(uint16_t)));
+    if (!u->stream) SFM_HIP(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
+    DevGroup g(nullptr);
+    g.add(u->d_xy, n);
+    g.add(u->d_frac, n);
+    if (!g.ok()) return g.rc();
+    g.commit();
     SFM_HIP(hipMemcpyAsync(u->d_xy, u->h_xy.data(), n * sizeof(short2), hipMemcpyHostToDevice, u->stream));
     SFM_HIP(hipMemcpyAsync(u->d_frac, u->h_frac.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, u->stream));
   }
-  if (u->src_cap < n_src) {
-    if (u->d_src) SFM_HIP(hipFree(u->d_src));
-    u->d_src = nullptr, u->src_cap = 0;
-    SFM_HIP(hipMalloc((void **)&u->d_src, n_src));
-    u->src_cap = n_src;
-  }
-  if (u->dst_cap < n_dst) {
-    if (u->d_dst) SFM_HIP(hipFree(u->d_dst));
-    u->d_dst = nullptr, u->dst_cap = 0;
-    SFM_HIP(hipMalloc((void **)&u->d_dst, n_dst));
-    u->dst_cap = n_dst;
-  }
+  int rc;
+  if (u->d_src.bytes() < n_src && (rc = u->d_src.alloc(nullptr, n_src))) return rc;
+  if (u->d_dst.bytes() < n_dst && (rc = u->d_dst.alloc(nullptr, n_dst))) return rc;
   SFM_HIP(hipMemcpyAsync(u->d_src, src, n_src, hipMemcpyHostToDevice, u->stream));
   const dim3 grid((u->roi[2] + 63) / 64, (u->roi[3] + 3) / 4), block(256);
   if (channels == 3)

@@ -1,0 +1,220 @@
+"""GPU: a failed device allocation anywhere in a handle's creation or in a call (injected: sfmloc_debug_fail_next_alloc(k),
+the calling thread's k-th allocation from now fails once) returns SFMLOC_ENOMEM, leaves no half-made state behind, and
+the same call succeeds afterwards with the result of a call that never failed.  Every case walks k = 0, 1, 2, ... until
+the call succeeds; the number of failing k must reach the number of typed buffers (csrc/devmem.h DevBuf) the call
+allocates, counted from the code and written here as a literal, so a path that swallows the injected error cannot pass."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+
+import adjust_scene as AS  # noqa: E402
+import merge_scene as MS  # noqa: E402
+from undistort_cameras import CAMERAS  # noqa: E402
+from sfmlocalization_amd import capi as S  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+MAX_K = 64
+
+
+def walk(call, at_least, limit=MAX_K):
+    """call() with allocation k = 0, 1, ... failing, until it succeeds -> its result then.  Every failure is ENOMEM; at
+    least `at_least` values of k fail; more than `limit` iterations is a failure."""
+    try:
+        for k in range(limit):
+            S.debug_fail_next_alloc(k)
+            try:
+                out = call()
+            except S.SfmlocError as e:
+                assert e.code == S.ENOMEM, (k, e)
+                continue
+            print("allocations that failed before the call succeeded:", k, "(at least", at_least, "expected)")
+            assert k >= at_least, "only %d allocations failed, the call makes at least %d" % (k, at_least)
+            return out
+        pytest.fail("still failing after %d injected failures" % limit)
+    finally:
+        S.debug_fail_next_alloc(-1)
+
+
+def same(a, b):
+    """bit for bit: arrays, or tuples / dicts of them (None and scalars compare equal)"""
+    if isinstance(a, dict):
+        assert a.keys() == b.keys()
+        for k in a:
+            same(a[k], b[k])
+    elif isinstance(a, (tuple, list)):
+        assert len(a) == len(b)
+        for x, y in zip(a, b):
+            same(x, y)
+    elif a is None or b is None:
+        assert a is None and b is None
+    else:
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.shape == b.shape and a.dtype == b.dtype
+        assert a.tobytes() == b.tobytes()
+
+
+def test_undistorter_first_image_on_one_handle():
+    """ONE handle takes every failed first apply and then the good one; a map pair that came up half would show in its
+    output.  The first image allocates the map pair (one group of 2), the source and the target image, and what a call
+    completed stays on the handle: k = 0 and k = 1 fail in the group (nothing kept), k = 2 fails at the source image
+    after the pair is committed, and the call armed with k = 3 allocates the source and the target only and succeeds: 3"""
+    K, dist, _ = CAMERAS[0]
+    w, h = 64, 48
+    K = K.copy()
+    K[:2] *= 0.1                                        # the 640 x 480 camera at a tenth of its size
+    img = np.random.default_rng(5).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    with S.Undistorter(K, dist, w, h) as fresh:
+        ref = fresh.apply(img)
+    assert ref.size > 0
+    with S.Undistorter(K, dist, w, h) as u:
+        got = walk(lambda: u.apply(img), 3)
+        same(got, ref)
+        same(u.apply(img), ref)
+
+
+def test_akaze_keypoint_regrowth():
+    """Akaze.compute with more keypoints than the extractor's per-keypoint arrays hold (65 536 after create) regrows the
+    seven of them as one group: 7.  Every failure leaves the old set and its capacity; the same call then gives what a
+    fresh extractor gives"""
+    rng = np.random.default_rng(9)
+    gray = rng.integers(0, 256, (64, 64), dtype=np.uint8)
+    n = 65536 + 1
+    kin = np.stack([rng.uniform(0, 63, n), rng.uniform(0, 63, n), np.full(n, 4.0), rng.integers(0, 4, n)], 1).astype(np.float32)
+    fresh = S.Akaze(64, 64)
+    ref = fresh.compute(gray, kin)
+    fresh.close()
+    ak = S.Akaze(64, 64)
+    small = ak.compute(gray, kin[:100])                 # within the capacity: no allocation
+    got = walk(lambda: ak.compute(gray, kin), 7)
+    same(got, ref)
+    same(ak.compute(gray, kin[:100]), small)
+    same(small, (ref[0][:100], ref[1][:100]))
+    ak.close()
+
+
+def test_sfm_create_then_clean_and_read():
+    """sfmloc_sfm_create uploads 13 arrays and allocates 19 more (adjust.hip sfm_create_impl): 32.  Then it makes the map
+    that K5's contexts hang off, without descriptors (capi.hip sfmloc_map_create: the two view tables, the log10 and the
+    ratio table: 4) and that map's own context (make_ctx with no bank rows: 26 arrays and the P3P group of 7: 33): 69
+    in all.  That is more than the 64 iterations the other walks allow, so this one is bounded by its own count: the
+    create armed with k = 69 must be the first that succeeds, which makes 70 iterations"""
+    a = AS.two_pass_case()
+
+    def run(h):
+        counts = h.clean(rm_unstable=True)
+        out = h.read()
+        h.close()
+        return counts, out
+
+    ref = run(S.Sfm(**a))
+    h = walk(lambda: S.Sfm(**a), 69, limit=70)
+    got = run(h)
+    assert got[0] == ref[0]
+    same(got[1], ref[1])
+
+
+def test_merge_ransac():
+    """two uploads and seven arrays (merge.hip ransac_impl): 9"""
+    A, B, _, _ = MS.planted(seed=7, n=64, n_in=40)
+    ref = S.merge_ransac(A, B, MS.THRES, 256)
+    got = walk(lambda: S.merge_ransac(A, B, MS.THRES, 256), 9)
+    assert (got["round"], got["count"]) == (ref["round"], ref["count"])
+    same(got["M"], ref["M"])
+    same(got["inliers"], ref["inliers"])
+
+
+def test_reduce_points():
+    """23 arrays and the partial sums of four scans, one array each at least (reduce.hip reduce_impl): 27.  The
+    caller's arrays are written by a call that succeeds only"""
+    rng = np.random.default_rng(3)
+    X = rng.uniform(-1.0, 1.0, (200, 3))
+    X[100:150] = X[:50] + rng.uniform(-0.004, 0.004, (50, 3))
+    ref = S.reduce_points(X, thres=0.01, knn=8)
+    assert ref["n_absorbed"] > 0
+    out = (np.full(200, 7, np.uint32), np.full(200, 7, np.uint32), np.full(200, 7.0))
+
+    def call():
+        try:
+            return S.reduce_points(X, thres=0.01, knn=8, out=out)
+        except S.SfmlocError:
+            assert (out[0] == 7).all() and (out[1] == 7).all() and (out[2] == 7.0).all()
+            raise
+
+    got = walk(call, 27)
+    for k in ("n_keep", "n_absorbed", "n_pairs", "rounds"):
+        assert got[k] == ref[k], k
+    for k in ("owner", "order", "dist"):
+        same(got[k], ref[k])
+
+
+def test_bowtrainer_kmeans():
+    """KmWork (trainbow.hip): 3 + 3 distance and partial-sum arrays and 14 more: 20"""
+    x = np.random.default_rng(11).integers(0, 256, (500, 61)).astype(np.float32)
+    with S.BowTrainer(61, 500) as tr:
+        tr.add_rows(x)
+        ref = tr.kmeans(8, attempts=1)
+        got = walk(lambda: tr.kmeans(8, attempts=1), 20)
+        same(got[0], ref[0])
+        same(got[1], ref[1])
+        assert got[2] == ref[2]
+
+
+def _create_walk(create, at_least):
+    """a C create call with allocation k failing -> the handle of the first that succeeds; every failure: ENOMEM, no handle"""
+    try:
+        for k in range(MAX_K):
+            h = C.c_void_p()
+            S.debug_fail_next_alloc(k)
+            rc = create(C.byref(h))
+            S.debug_fail_next_alloc(-1)
+            if rc == 0:
+                assert h.value
+                print("allocations that failed before the create succeeded:", k, "(at least", at_least, "expected)")
+                assert k >= at_least, "only %d allocations failed, the create makes at least %d" % (k, at_least)
+                return h
+            assert rc == S.ENOMEM and not h.value, (k, rc, S._L().sfmloc_last_error())
+        pytest.fail("still failing after %d injected failures" % MAX_K)
+    finally:
+        S.debug_fail_next_alloc(-1)
+
+
+def test_akaze_create_leaves_no_handle():
+    """sfmloc_akaze_create at 64 x 64: 33 arrays and the seven per-keypoint ones (akaze.hip): 40"""
+    L = S._L()
+    gray = np.random.default_rng(2).integers(0, 256, (64, 64), dtype=np.uint8)
+    gray[16:48, 16:48] //= 4
+    fresh = S.Akaze(64, 64)
+    ref = fresh.detect_and_compute(gray)
+    fresh.close()
+    h = _create_walk(lambda out: L.sfmloc_akaze_create(0, 64, 64, 4, 4, C.c_float(0.001), out), 40)
+    ak = S.Akaze.__new__(S.Akaze)
+    ak._h, ak.width, ak.height = h, 64, 64
+    same(ak.detect_and_compute(gray), ref)
+    ak.close()
+
+
+def test_imgbow_create_leaves_no_handle():
+    """sfmloc_imgbow_create at 64 x 64 without a PCA: the model's 3 arrays, the extractor's 40, the resize plan's 5 and
+    its own 6: 54"""
+    L = S._L()
+    rng = np.random.default_rng(4)
+    centers = rng.uniform(0, 255, (8, 61)).astype(np.float32)
+    img = rng.integers(0, 256, (64, 64, 3), dtype=np.uint8)
+    fresh = S.ImgBow(64, 64, 3, centers=centers, in_dim=61)
+    ref = fresh.compute(img)
+    fresh.close()
+    d, keep = S._bof_desc(centers, 61)
+    h = _create_walk(lambda out: L.sfmloc_imgbow_create(C.byref(d), 0, 64, 64, 3, out), 54)
+    ib = S.ImgBow.__new__(S.ImgBow)
+    ib._h, ib.width, ib.height, ib.channels = h, 64, 64, 3
+    ib.dim = int(L.sfmloc_imgbow_dim(h))
+    same(ib.compute(img), ref)
+    ib.close()
