@@ -934,6 +934,97 @@ void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o);
 int sfmloc_sfm_triangulate(sfmloc_sfm *h, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep);
 
 /* ------------------------------------------------------------------------- */
+/* Relative poses (the first stage of openMVG_main_GlobalSfM, reconstructGraph.py:166-171: the essential matrix of      */
+/* every matched view pair by the five-point solver under AC-RANSAC, its decomposition and the cheirality test).        */
+/* Rotation and translation averaging, which consume the result, are not built; neither is OpenMVG's two-view bundle    */
+/* adjustment of the winning pose.  OpenMVG's source was not at hand: every point below is a reading chosen here, and   */
+/* tests/relpose_np.py restates each operation.  The pair list has the layout of sfmloc_geometric_pairs and             */
+/* sfmloc_tracks_build (pair k = views (I, J) = (pairs[2k], pairs[2k+1]) owns match_i/j[offsets[k] .. offsets[k+1]),    */
+/* feature indices inside the view); kpt_xy [view_off[n_views] * 2] the keypoints of all views; intrinsics f, ppx, ppy, */
+/* k1, k2, k3 with type 0 (pinhole) or 3 (pinhole_radial_k3).  Per pair, f64, unfused, only + - * / sqrt:               */
+/*   bearings    the pixel undistorted with get_ud_pixel ("angle" above) when the view's intrinsic is type 3, then      */
+/*               ((x - ppx) / f, (y - ppy) / f).  The two views may have different intrinsics.                           */
+/*   gate        m <= 5 matches: ok = 0, every other field but n_matches zero, no error.                                 */
+/*   sample      five distinct sorted positions by OpenMVG's UniformSample (the insertion of ac_sample) from            */
+/*               Philox4x32-10 keyed by the seed's two halves with the counter (iteration, I, J, 6 | (d >> 2) << 8), d   */
+/*               the draw 0 .. 4 and word d & 3 of the block its value (6: the stage id).  I and J are the call's view  */
+/*               indices: a pair's result depends on (seed, I, J) and its own matches alone, not on the other pairs.    */
+/*   solver      design matrix D [5 x 9], row (u a, u b, u, v a, v b, v, a, b, 1) for the bearings (a, b) in I and       */
+/*               (u, v) in J; G = D^T D, rows added in order; "jacobi" (sfmloc_merge section, N = 9, 10 sweeps).  X, Y,  */
+/*               Z, W = the eigenvectors of the four smallest diagonal entries in ascending order, each time the first  */
+/*               smallest entry not yet taken; no model when the fifth smallest <= 1e-12 * the largest (a repeated      */
+/*               point).  E = x X + y Y + z Z + W row-major.  The ten cubics -- det E, and the nine entries of          */
+/*               (E E^T - tr(E E^T) / 2) E -- in the monomial order x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz */
+/*               x yz^2 yz y z^3 z^2 z 1 (products of linear forms accumulated from 0.0 term by term, csrc/             */
+/*               essential_device.h); Gauss-Jordan on the first ten columns with partial pivoting (the largest          */
+/*               magnitude, the first on ties; a pivot not above 1e-13 in magnitude: no model).  Nister's route: rows   */
+/*               4 .. 9 pairwise as a - z b give the 3 x 3 matrix of polynomials in z (degrees 3, 3, 4), its            */
+/*               determinant p of degree 10.  Real roots: the Sturm chain of p / max|p_i| (every member divided by its  */
+/*               largest magnitude), the Cauchy bound 1 + max |p_i / p_10|, the k-th root by 48 bisections on the       */
+/*               chain's sign-change count, then 3 Newton steps each kept only inside the last bracket, then 2 Newton   */
+/*               steps on the determinant of the matrix itself (entries by Horner, the derivative as the sum of the    */
+/*               three determinants with one row differentiated), each kept when |dz| <= 1e-6 (1 + |z|).  x, y from the */
+/*               cross product of two rows of the matrix at z (of the three pairs the one with the largest third        */
+/*               entry, the first on ties).  Each model is scaled to unit Frobenius norm; a non-finite one is dropped.  */
+/*               Up to 10 models, in ascending z.                                                                        */
+/*   residual    the squared distance in J's undistorted pixels from the point to the line E x_I: the arithmetic of     */
+/*               the F-matrix residual on bearings ((l u)^2 / (l0^2 + l1^2), NaN -> +inf), times f_J f_J.               */
+/*   NFA         logalpha0 = log10(2 D / A) of image J (D the diagonal, A the area, pixels), mult 0.5, loge0 =          */
+/*               log10(10 (m - 5)), upper bound precision_px^2 (+inf: none); the logcombi tables in float as K3's.      */
+/*   AC-RANSAC   K3's loop (OpenMVG ACRANSAC): max_iteration less a 10 % reserve, residuals sorted by (error, index),   */
+/*               a better NFA below 0 (or the last planned iteration) restricts sampling to the inlier set and spends   */
+/*               the reserve.  The models of an iteration are tried in ascending z.                                      */
+/*   decision    nfa >= 0 or no model at all: n_inliers = 0, ok = 0, nfa reported, the rest zero.  Otherwise every      */
+/*               field is filled and ok = (n_inliers > 2.5 * 5) and front[choice] > 0.  error_max_px = the square root  */
+/*               of the last inlier's residual.  The inlier list is in AC-RANSAC's order (ascending residual).          */
+/*               ok does not say that every inlier lies in front: a pair without a baseline (pure rotation) has its     */
+/*               points at infinity, the sign of a depth is then the noise's, and it may end ok with front[choice] <    */
+/*               n_inliers.  A consumer that needs the translation checks front[choice] against n_inliers.              */
+/*   decompose   "jacobi" (N = 3) on E^T E; v1, v2 the columns of the largest and second largest diagonal entry (the    */
+/*               first on ties), sigma_i its square root, u_i = E v_i / sigma_i, v3 = v1 x v2, u3 = u1 x u2 scaled to   */
+/*               unit length (so det U = det V = +1).  Ra = U W V^T = u2 v1^T - u1 v2^T + u3 v3^T, Rb = U W^T V^T =     */
+/*               u1 v2^T - u2 v1^T + u3 v3^T.  Candidates 0 .. 3: (Ra, u3), (Ra, -u3), (Rb, u3), (Rb, -u3).             */
+/*   cheirality  every inlier triangulated from [I | 0] and [R | t] on bearings by "hypothesis" of the structure        */
+/*               section (4 x 4 G, Jacobi, the smallest diagonal entry); front[c] counts those with a point and         */
+/*               X_2 > 0 and (R X + t)_2 > 0.  choice = the largest count, the first on ties.                            */
+/* Pairs of at most 2048 matches run with their arrays in LDS, larger ones (at most 65 536: SFMLOC_ECAP beyond) through  */
+/* global-memory slots with the same arithmetic and bits.  No float atomics: two runs give the same bits.  Errors, all   */
+/* checked before anything is launched: a view or intrinsic index out of range, a pair naming one view twice, a feature  */
+/* index out of range (the text names the pair and the match), an intrinsic type other than 0 or 3: SFMLOC_EINVAL.      */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_relpose sfmloc_relpose;
+typedef struct sfmloc_relpose_options {
+  uint32_t max_iteration;   /* default 256 */
+  uint32_t reserved;
+  double   precision_px;    /* AC-RANSAC upper bound on the residual, default 2.5; +inf = none */
+  uint64_t seed;            /* default: sfmloc_default_params' seed */
+} sfmloc_relpose_options;
+typedef struct sfmloc_relpose_result {
+  uint32_t ok, n_matches, n_inliers;
+  uint32_t sample[5];        /* positions in the pair's match list of the winning minimal sample */
+  uint32_t front[4];         /* inliers in front of both cameras, per decomposition candidate */
+  uint32_t choice;           /* index of the chosen candidate */
+  double   E[9], R[9], t[3]; /* x_J^T E x_I = 0 on bearings; X_J = R X_I + t, |t| = 1 */
+  double   error_max_px, nfa;
+} sfmloc_relpose_result;
+void sfmloc_relpose_default_options(sfmloc_relpose_options *o);
+/* opt NULL = the defaults; n_pairs = 0 gives an empty handle */
+int  sfmloc_relative_poses(int device, const uint64_t *view_off /*[n_views+1]*/, uint32_t n_views, const float *kpt_xy,
+                           const uint32_t *view_wh /*[n_views*2]*/, const uint32_t *view_intrinsic /*[n_views]*/,
+                           const double *intrinsics /*[n*6]*/, const uint32_t *intrinsic_type, uint32_t n_intrinsics,
+                           const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                           const uint32_t *match_i, const uint32_t *match_j,
+                           const sfmloc_relpose_options *opt, sfmloc_relpose **out);
+int  sfmloc_relpose_results(const sfmloc_relpose *r, sfmloc_relpose_result *out /*[n_pairs]*/);
+/* off [n_pairs+1], idx [off[n_pairs]]: positions in each pair's match list, AC-RANSAC's order; either may be NULL */
+int  sfmloc_relpose_inliers(const sfmloc_relpose *r, uint64_t *off /*[n_pairs+1]*/, uint32_t *idx);
+void sfmloc_relpose_destroy(sfmloc_relpose *r);
+/* device milliseconds of the calling thread's last sfmloc_relative_poses (HIP events around its kernels and copies) */
+double sfmloc_relpose_last_ms(void);
+/* parity probe of the solver alone: a row = x1[10], x2[10] (five bearing pairs); out [n * 91] = count, then up to 10 E */
+int  sfmloc_debug_five_point(int device, const double *in, int n, double *out);
+
+/* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */
 /* reference runs after every reconstruction and merge): which view each landmark takes its colour from.  The greedy  */
 /* cover runs on the structure exactly as sfmloc_sfm_create received it (the keep masks of sfmloc_sfm_clean and the   */

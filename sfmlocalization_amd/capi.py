@@ -206,6 +206,8 @@ SYMBOLS = [
     "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
     "sfmloc_tracks_build", "sfmloc_tracks_counts", "sfmloc_tracks_read", "sfmloc_tracks_destroy", "sfmloc_tracks_last_ms",
     "sfmloc_triangulate_default_options", "sfmloc_sfm_triangulate",
+    "sfmloc_relpose_default_options", "sfmloc_relative_poses", "sfmloc_relpose_results", "sfmloc_relpose_inliers",
+    "sfmloc_relpose_destroy", "sfmloc_relpose_last_ms", "sfmloc_debug_five_point",
 ]
 
 _bound = False
@@ -466,6 +468,18 @@ def _L():
         L.sfmloc_triangulate_default_options.restype = None
         L.sfmloc_triangulate_default_options.argtypes = [C.POINTER(TriangulateOptions)]
         L.sfmloc_sfm_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.POINTER(TriangulateReport)]
+        L.sfmloc_relpose_default_options.restype = None
+        L.sfmloc_relpose_default_options.argtypes = [C.POINTER(RelposeOptions)]
+        L.sfmloc_relative_poses.argtypes = [C.c_int, U64P, C.c_uint32, C.POINTER(C.c_float), U32P, U32P, F64P, U32P,
+                                            C.c_uint32, U32P, C.c_uint32, U64P, U32P, U32P, C.POINTER(RelposeOptions),
+                                            C.POINTER(C.c_void_p)]
+        L.sfmloc_relpose_results.argtypes = [C.c_void_p, C.c_void_p]
+        L.sfmloc_relpose_inliers.argtypes = [C.c_void_p, U64P, U32P]
+        L.sfmloc_relpose_destroy.restype = None
+        L.sfmloc_relpose_destroy.argtypes = [C.c_void_p]
+        L.sfmloc_relpose_last_ms.restype = C.c_double
+        L.sfmloc_relpose_last_ms.argtypes = []
+        L.sfmloc_debug_five_point.argtypes = [C.c_int, F64P, C.c_int, F64P]
         MPP = C.POINTER(MergeParams)
         L.sfmloc_merge_default_params.restype = None
         L.sfmloc_merge_default_params.argtypes = [MPP]
@@ -1425,6 +1439,93 @@ class Tracks:
     @property
     def n_tracks(self):
         return self.counts[3]
+
+
+class RelposeOptions(C.Structure):
+    """sfmloc_relpose_options"""
+    _fields_ = [("max_iteration", C.c_uint32), ("reserved", C.c_uint32), ("precision_px", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+# sfmloc_relpose_result as a NumPy record (align=True gives the C layout: 13 uint32, 4 bytes of padding, 23 doubles)
+RELPOSE_RESULT = np.dtype([("ok", np.uint32), ("n_matches", np.uint32), ("n_inliers", np.uint32),
+                           ("sample", np.uint32, 5), ("front", np.uint32, 4), ("choice", np.uint32),
+                           ("E", np.float64, 9), ("R", np.float64, 9), ("t", np.float64, 3),
+                           ("error_max_px", np.float64), ("nfa", np.float64)], align=True)
+
+
+def relpose_default_options(**overrides):
+    """sfmloc_relpose_default_options -> RelposeOptions (256 iterations, 2.5 px, the default seed)"""
+    o = RelposeOptions()
+    _L().sfmloc_relpose_default_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def relpose_last_ms():
+    """device milliseconds of this thread's last RelPoses()"""
+    return float(_L().sfmloc_relpose_last_ms())
+
+
+class RelPoses:
+    """sfmloc_relative_poses: the relative pose of every pair of a pair list (include/sfmloc.h states the semantics).
+    view_off [n_views + 1] feature rows per view, kpt_xy [rows, 2] float32, view_wh [n_views, 2], view_intrinsic
+    [n_views], intrinsics [n, 6] (f, ppx, ppy, k1, k2, k3), intrinsic_type [n] (0 or 3); pairs, offsets, match_i,
+    match_j as pair_arrays returns them; options: the fields of sfmloc_relpose_options.  -> results (RELPOSE_RESULT
+    [n_pairs]), inl_off [n_pairs + 1], inl_idx (positions in each pair's match list, AC-RANSAC's order), ms."""
+
+    def __init__(self, view_off, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i,
+                 match_j, device=0, **options):
+        view_off = np.ascontiguousarray(view_off, np.uint64)
+        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
+        view_wh = np.ascontiguousarray(view_wh, np.uint32).reshape(-1, 2)
+        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
+        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
+        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
+        n_views = len(view_off) - 1
+        if len(view_wh) != n_views or len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
+                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
+            raise ValueError("view arrays differ in length")
+        if len(offsets) != len(pairs) + 1 or len(match_i) != len(match_j) or \
+                (len(pairs) and int(offsets[-1]) != len(match_i)):
+            raise ValueError("pair list arrays differ in length")
+        opt = relpose_default_options(**options)
+        h = C.c_void_p()
+        _check(_L().sfmloc_relative_poses(int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float),
+                                          _ptr(view_wh, C.c_uint32), _ptr(view_intrinsic, C.c_uint32),
+                                          _ptr(intrinsics, C.c_double), _ptr(intrinsic_type, C.c_uint32), len(intrinsics),
+                                          _ptr(pairs, C.c_uint32), len(pairs), _ptr(offsets, C.c_uint64),
+                                          _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32), C.byref(opt), C.byref(h)))
+        try:
+            self.results = np.zeros(len(pairs), RELPOSE_RESULT)
+            _check(_L().sfmloc_relpose_results(h, self.results.ctypes.data_as(C.c_void_p) if len(pairs) else None))
+            self.inl_off = np.zeros(len(pairs) + 1, np.uint64)
+            _check(_L().sfmloc_relpose_inliers(h, _ptr(self.inl_off, C.c_uint64), None))
+            n = int(self.inl_off[-1])
+            idx = np.zeros(max(1, n), np.uint32)
+            _check(_L().sfmloc_relpose_inliers(h, None, _ptr(idx, C.c_uint32)))
+            self.inl_idx = idx[:n]
+            self.ms = relpose_last_ms()
+        finally:
+            _L().sfmloc_relpose_destroy(h)
+
+    def inliers(self, k):
+        """the inlier positions of pair k"""
+        return self.inl_idx[int(self.inl_off[k]):int(self.inl_off[k + 1])]
+
+
+def five_point(rows):
+    """sfmloc_debug_five_point: rows [n, 20] (x1[10], x2[10]: five bearing pairs) -> (count [n], E [n, 10, 9])"""
+    rows = np.ascontiguousarray(rows, np.float64).reshape(-1, 20)
+    out = np.zeros((len(rows), 91))
+    _check(_L().sfmloc_debug_five_point(0, _ptr(rows, C.c_double), len(rows), _ptr(out, C.c_double)))
+    return out[:, 0].astype(np.int64), out[:, 1:].reshape(-1, 10, 9)
 
 
 def merge_default_params(**overrides):

@@ -54,81 +54,7 @@ __device__ unsigned long long g_stamps_f[256 * 64];        // [workgroup][event]
 // ---------------------------------------------------------------------------------------------------
 // block-wide helpers (256 threads)
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool pair_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-  return ka < kb || (ka == kb && ia < ib);
-}
-
-// ascending bitonic sort of (key, idx) pairs, P a power of two
-__device__ void bitonic_sort(uint64_t *key, uint32_t *idx, int P) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += kThreads) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int l = i + j;
-        const bool up = (i & k) == 0;
-        const uint64_t ka = key[i], kb = key[l];
-        const uint32_t ia = idx[i], ib = idx[l];
-        const bool a_gt_b = pair_less(kb, ib, ka, ia);
-        if (a_gt_b == up) {
-          key[i] = kb;
-          key[l] = ka;
-          idx[i] = ib;
-          idx[l] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-struct NfaBest {
-  double nfa;
-  int k;
-};
-
-// bestNFA of OpenMVG over the sorted residuals key[0..n): min over k in (s, n] with e_k <= max_thr of
-//   loge0 + logalpha(e_k) * (k - s) + logc_n[k] + logc_k[k];  first k on ties.  All threads return the result.
-__device__ NfaBest best_nfa_block(const uint64_t *key, int n, int s, double max_thr, double logalpha0, double mult,
-                                  double loge0, const float *logc_n, const float *logc_k, double *red_nfa,
-                                  int *red_k) {
-  double lb = pos_inf();
-  int lk = 0x7FFFFFFF;
-  for (int kk = s + 1 + (int)threadIdx.x; kk <= n; kk += kThreads) {
-    const double ek = u2d(key[kk - 1]);
-    if (ek <= max_thr) {
-      const double logalpha = logalpha0 + mult * det_log10(ek + (double)FLT_EPSILON);
-      const double nfa = loge0 + logalpha * (double)(kk - s) + (double)logc_n[kk] + (double)logc_k[kk];
-      if (nfa < lb) {
-        lb = nfa;
-        lk = kk;
-      }
-    }
-  }
-  // wave reduce (64 lanes), then across the 4 waves through LDS
-  for (int off = 32; off > 0; off >>= 1) {
-    const double ob = __shfl_down(lb, off, 64);
-    const int ok = __shfl_down(lk, off, 64);
-    if (ob < lb || (ob == lb && ok < lk)) {
-      lb = ob;
-      lk = ok;
-    }
-  }
-  __syncthreads();  // red_* may still be read by the previous call's consumers
-  if ((threadIdx.x & 63) == 0) {
-    red_nfa[threadIdx.x >> 6] = lb;
-    red_k[threadIdx.x >> 6] = lk;
-  }
-  __syncthreads();
-  NfaBest r{red_nfa[0], red_k[0]};
-  for (int w = 1; w < kThreads / 64; ++w) {
-    if (red_nfa[w] < r.nfa || (red_nfa[w] == r.nfa && red_k[w] < r.k)) {
-      r.nfa = red_nfa[w];
-      r.k = red_k[w];
-    }
-  }
-  return r;
-}
-
+// (pair_less, bitonic_sort, NfaBest, best_nfa_block, next_pow2: ransac_device.h -- relpose.hip uses them too)
 // bestNFA over one wave's sorted segment; every lane of the wave returns the result
 __device__ NfaBest best_nfa_wave(const uint64_t *key, int n, int s, double max_thr, double logalpha0, double mult,
                                  double loge0, const float *logc_n, const float *logc_k) {
@@ -426,12 +352,6 @@ __device__ __forceinline__ uint64_t sorted_key_at(const uint64_t (&key)[E], int 
   for (int r = 0; r < E; ++r)
     if ((pos >> 6) == r) v = key[r];
   return __shfl(v, pos & 63, 64);
-}
-
-__device__ __forceinline__ int next_pow2(int n) {
-  int p = 64;
-  while (p < n) p <<= 1;
-  return p;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -1,0 +1,661 @@
+// sfmloc_relative_poses: the relative pose of every matched view pair (the first stage of openMVG_main_GlobalSfM): the
+// essential matrix by the five-point solver under AC-RANSAC, its decomposition, the cheirality count.  The semantics
+// are stated in include/sfmloc.h ("Relative poses"); tests/relpose_np.py restates every operation.  f64, only + - * /
+// sqrt, unfused (the library's -ffp-contract=off), every sum in a fixed order, no float atomics.
+//
+//   bearings    k_rp_bearings: (a, b, u, v) per match, once (the undistortion's bisection is the expensive part).
+//   pairs       k_relpose: one workgroup of 256 threads per pair, K3's block-wide AC-RANSAC loop (fmatrix_filter_view of
+//               acransac.hip: residuals -> bitonic sort -> best_nfa_block, the 10 % reserve, the reduction to the inlier
+//               set) with the match arrays, the keys and the logcombi tables in LDS through the same Store abstraction.
+//               While sampling is uniform the hypotheses are solved kRpPre = 16 at a time, one per group of 16 lanes
+//               (essential_device.h); afterwards group 0 solves the iteration's one.  After the rounds thread 0
+//               decomposes the winner and the inliers x 4 candidates are spread over the lanes for the cheirality count
+//               (integer atomics on LDS).
+//   large       k_relpose_large: the pairs with more than kLdsMaxM matches, kRpLargeSlots persistent workgroups each
+//               owning a global-memory slot; the same function, the same bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <string>
+#include <vector>
+
+#include "essential_device.h"
+#include "ransac_device.h"
+#include "relpose_host.h"
+
+namespace sfmloc {
+namespace {
+
+using essential::RpGroupLds;
+
+thread_local double g_relpose_last_ms = 0.0;
+
+constexpr uint32_t STAGE_RELPOSE = 6;  // (geom_device.h's stage ids end at 5)
+constexpr int kRpPre = kThreads / essential::kRpGroup;  // hypotheses solved side by side: one per group of lanes
+constexpr int kRpLdsMaxM = (int)relpose_host::kLdsMaxM;
+constexpr int kRpLargeSlots = 8;
+constexpr int kRpL10 = (int)relpose_host::kLargeMaxM + 2;
+static_assert(kRpLdsMaxM == kFMaxM, "the LDS form holds what K3's does");
+
+struct Relpose {
+  std::vector<sfmloc_relpose_result> res;
+  std::vector<uint64_t> off;  // [n_pairs + 1]
+  std::vector<uint32_t> idx;
+};
+
+struct RpArgs {
+  uint32_t n_pairs;
+  int n_iter;
+  double precision;
+  uint64_t seed;
+  const uint32_t *pairs;
+  const uint64_t *offsets;
+  const double *bear;  // [match][4]: a, b (view I), u, v (view J)
+  const uint32_t *view_wh, *view_intr;
+  const double *intr;
+  const double *L10;
+  sfmloc_relpose_result *res;
+  uint32_t *inl;
+};
+
+struct RpSmall {
+  double pre_models[kRpPre][9 * essential::kRpMaxModels];
+  int pre_nm[kRpPre];
+  int pre_smp[kRpPre][5];
+  double best_model[9];
+  int best_smp[5];
+  double red_nfa[kThreads / 64];
+  int red_k[kThreads / 64];
+  double cand_R[2][9], cand_t[3];
+  int front[4];
+};
+struct RpShared {
+  uint64_t key[kRpLdsMaxM];
+  uint32_t idx[kRpLdsMaxM];
+  int32_t vec_index[kRpLdsMaxM];
+  int32_t best_inl[kRpLdsMaxM];
+  float logc_n[kRpLdsMaxM + 1];
+  float logc_k[kRpLdsMaxM + 1];
+  RpSmall small;
+  RpGroupLds grp[kRpPre];
+};
+static_assert(sizeof(RpShared) <= 160 * 1024, "one workgroup's LDS on gfx950");
+struct RpLargeShared {
+  RpSmall small;
+  RpGroupLds grp[kRpPre];
+};
+struct RpStoreLds {
+  RpShared *S;
+  __device__ __forceinline__ uint64_t *key() const { return S->key; }
+  __device__ __forceinline__ uint32_t *idx() const { return S->idx; }
+  __device__ __forceinline__ int32_t *vec_index() const { return S->vec_index; }
+  __device__ __forceinline__ int32_t *best_inl() const { return S->best_inl; }
+  __device__ __forceinline__ float *logc_n() const { return S->logc_n; }
+  __device__ __forceinline__ float *logc_k() const { return S->logc_k; }
+};
+struct RpStoreGlobal {
+  uint64_t *k;
+  uint32_t *i;
+  int32_t *vi, *bi;
+  float *ln, *lk;
+  __device__ __forceinline__ uint64_t *key() const { return k; }
+  __device__ __forceinline__ uint32_t *idx() const { return i; }
+  __device__ __forceinline__ int32_t *vec_index() const { return vi; }
+  __device__ __forceinline__ int32_t *best_inl() const { return bi; }
+  __device__ __forceinline__ float *logc_n() const { return ln; }
+  __device__ __forceinline__ float *logc_k() const { return lk; }
+};
+struct RpLargeArgs {
+  const uint32_t *list;
+  uint32_t n;
+  uint64_t *key;
+  uint32_t *idx;
+  int32_t *vec_index, *best_inl;
+  float *logc_n, *logc_k;
+  int slot_m;
+};
+
+__global__ void k_rp_fill_log10(double *L10, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) L10[i] = (i == 0) ? 0.0 : det_log10((double)i);
+}
+
+// sfmloc.h "bearings": one workgroup per pair walks the pair's matches
+__global__ __launch_bounds__(256) void k_rp_bearings(uint32_t n_pairs, const uint32_t *__restrict__ pairs,
+                                                     const uint64_t *__restrict__ offsets,
+                                                     const uint64_t *__restrict__ view_off,
+                                                     const float *__restrict__ kpt_xy,
+                                                     const uint32_t *__restrict__ match_i,
+                                                     const uint32_t *__restrict__ match_j,
+                                                     const uint32_t *__restrict__ view_intr,
+                                                     const uint32_t *__restrict__ intr_type,
+                                                     const double *__restrict__ intr, double *__restrict__ bear) {
+  const uint32_t k = blockIdx.x;
+  if (k >= n_pairs) return;
+  const uint32_t v[2] = {pairs[2 * (size_t)k], pairs[2 * (size_t)k + 1]};
+  for (uint64_t t = offsets[k] + threadIdx.x; t < offsets[k + 1]; t += 256) {
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const uint32_t ii = view_intr[v[side]];
+      const double *K = intr + 6 * (size_t)ii;
+      const uint64_t row = view_off[v[side]] + (side ? match_j[t] : match_i[t]);
+      const double x = (double)kpt_xy[2 * row], y = (double)kpt_xy[2 * row + 1];
+      double ux = x, uy = y;
+      if (intr_type[ii] == 3) ud_pixel_k3(K[0], K[1], K[2], K[3], K[4], K[5], x, y, &ux, &uy);
+      bear[4 * t + 2 * side] = (ux - K[1]) / K[0];
+      bear[4 * t + 2 * side + 1] = (uy - K[2]) / K[0];
+    }
+  }
+}
+
+// sfmloc.h "sample": OpenMVG UniformSample over five draws of two Philox blocks; the counter words are (iteration, I,
+// J, stage | block << 8)
+__device__ __forceinline__ void rp_sample5(const int32_t *vec_index, int n, uint64_t seed, uint32_t vi, uint32_t vj,
+                                           uint32_t iter, int32_t *samples) {
+  uint32_t c0[4] = {iter, vi, vj, STAGE_RELPOSE};
+  uint32_t c1[4] = {iter, vi, vj, STAGE_RELPOSE | (1u << 8)};
+  philox4x32_10(c0, (uint32_t)seed, (uint32_t)(seed >> 32));
+  philox4x32_10(c1, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint32_t d[5] = {c0[0], c0[1], c0[2], c0[3], c1[0]};
+  int32_t s[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    int32_t r = (int32_t)(d[i] % (uint32_t)(n - i));
+    int j = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+      if (q < i && j == q && r >= s[q]) {
+        ++r;
+        ++j;
+      }
+#pragma unroll
+    for (int q = 4; q > 0; --q)
+      if (q <= i && q > j) s[q] = s[q - 1];
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+      if (q == j) s[q] = r;
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) samples[i] = vec_index ? vec_index[s[i]] : s[i];
+}
+
+// sfmloc.h "cheirality": the two-view point of one match under (R, t), triangulate.hip's hypothesis on bearings
+__device__ __forceinline__ bool rp_in_front(const double *R, const double *t, double a, double b, double u, double v) {
+  const double P1[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+  const double P2[12] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2]};
+  double G[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) G[i][j] = 0.0;
+#pragma unroll
+  for (int side = 0; side < 2; ++side) {
+    const double *P = side ? P2 : P1;
+    const double bx = side ? u : a, by = side ? v : b;
+    double ra[4], rb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ra[j] = bx * P[8 + j] - P[j];
+      rb[j] = by * P[8 + j] - P[4 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i; j < 4; ++j) {
+        G[i][j] = G[i][j] + ra[i] * ra[j];
+        G[i][j] = G[i][j] + rb[i] * rb[j];
+      }
+  }
+#pragma unroll
+  for (int i = 1; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < i; ++j) G[i][j] = G[j][i];
+  double V[4][4];
+  jacobi_fixed<4>(G, V);
+  double best = G[0][0], x0 = V[0][0], x1 = V[1][0], x2 = V[2][0], w = V[3][0];
+#pragma unroll
+  for (int i = 1; i < 4; ++i) {
+    const bool take = G[i][i] < best;
+    best = take ? G[i][i] : best;
+    x0 = take ? V[0][i] : x0;
+    x1 = take ? V[1][i] : x1;
+    x2 = take ? V[2][i] : x2;
+    w = take ? V[3][i] : w;
+  }
+  const double X0 = x0 / w, X1 = x1 / w, X2 = x2 / w;
+  const bool ok = w != 0.0 && is_finite(w) && is_finite(X0) && is_finite(X1) && is_finite(X2);
+  const double zj = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + t[2];
+  return ok && X2 > 0.0 && zj > 0.0;
+}
+
+// One pair by the whole workgroup; `st` says where the per-match arrays are (they hold the pair's matches: the caller
+// checked).  The loop is fmatrix_filter_view's (acransac.hip) with the five-point kernel.
+template <typename Store>
+__device__ void relpose_pair(const RpArgs &A, uint32_t k, Store st, RpSmall &S, RpGroupLds *grp) {
+  const int tid = threadIdx.x;
+  const uint64_t off = A.offsets[k];
+  const int m = (int)(A.offsets[k + 1] - off);
+  const uint32_t vi = A.pairs[2 * (size_t)k], vj = A.pairs[2 * (size_t)k + 1];
+  sfmloc_relpose_result &R = A.res[k];
+  constexpr int s = 5;
+  if (tid == 0) {
+    R.ok = 0;
+    R.n_matches = (uint32_t)m;
+    R.n_inliers = 0;
+    for (int i = 0; i < 5; ++i) R.sample[i] = 0;
+    for (int i = 0; i < 4; ++i) R.front[i] = 0;
+    R.choice = 0;
+    for (int i = 0; i < 9; ++i) {
+      R.E[i] = 0.0;
+      R.R[i] = 0.0;
+    }
+    for (int i = 0; i < 3; ++i) R.t[i] = 0.0;
+    R.error_max_px = 0.0;
+    R.nfa = 0.0;
+  }
+  if (m <= s) return;  // sfmloc.h "gate"
+  const double *bear = A.bear + 4 * off;
+  const double fj = A.intr[6 * (size_t)A.view_intr[vj]];
+  const double fj2 = fj * fj;
+  const double w2 = (double)A.view_wh[2 * (size_t)vj], h2 = (double)A.view_wh[2 * (size_t)vj + 1];
+  const double Dg = sqrt(w2 * w2 + h2 * h2);
+  const double logalpha0 = det_log10(2.0 * Dg / (w2 * h2));
+  const double max_thr = A.precision * A.precision;
+  const double loge0 = det_log10(10.0 * (double)(m - s));
+  const int P = next_pow2(m);
+  const int g = tid / essential::kRpGroup;
+
+  // the hypothesis of iteration `it` on this lane's group (a group without one runs on zeros); every lane of the group
+  // holds the same sample
+  auto solve = [&](bool have, const int32_t *vec_index, int n_index, long it) {
+    int32_t smp[5] = {0, 0, 0, 0, 0};
+    double x1[10], x2[10];
+#pragma unroll
+    for (int i = 0; i < 10; ++i) x1[i] = x2[i] = 0.0;
+    if (have) {
+      rp_sample5(vec_index, n_index, A.seed, vi, vj, (uint32_t)it, smp);
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        x1[2 * i] = bear[4 * smp[i]];
+        x1[2 * i + 1] = bear[4 * smp[i] + 1];
+        x2[2 * i] = bear[4 * smp[i] + 2];
+        x2[2 * i + 1] = bear[4 * smp[i] + 3];
+      }
+    }
+    const int nm = essential::five_point_group(grp[g], x1, x2, S.pre_models[g]);
+    if ((tid & (essential::kRpGroup - 1)) == 0) {
+      S.pre_nm[g] = have ? nm : 0;
+#pragma unroll
+      for (int i = 0; i < 5; ++i) S.pre_smp[g][i] = smp[i];
+    }
+  };
+
+  logcombi_tables_block(s, m, A.L10, reinterpret_cast<double *>(st.key()), st.logc_n(), st.logc_k());  // the key array is free until the first sort
+
+  double min_nfa = pos_inf();
+  int n_in = 0;
+  long n_iter = A.n_iter;
+  long n_reserve = n_iter / 10;
+  n_iter -= n_reserve;
+  bool identity = true;
+  int n_index = m;
+  long pre_base = -1;
+
+  for (long iter = 0; iter < n_iter; ++iter) {
+    int slot;
+    if (identity) {
+      if (pre_base < 0 || iter >= pre_base + kRpPre) {
+        __syncthreads();
+        pre_base = iter;
+        solve(true, nullptr, m, pre_base + g);
+        __syncthreads();
+      }
+      slot = (int)(iter - pre_base);
+    } else {
+      __syncthreads();
+      solve(g == 0, st.vec_index(), n_index, iter);
+      __syncthreads();
+      slot = 0;
+    }
+    const double *models = S.pre_models[slot];
+    const int nm = S.pre_nm[slot];
+    bool better = false;
+    for (int q = 0; q < nm; ++q) {
+      double M[9];
+      for (int e = 0; e < 9; ++e) M[e] = models[9 * q + e];
+      __syncthreads();  // key/idx of the previous model are no longer read
+      for (int p = tid; p < P; p += kThreads) {
+        uint64_t kv = ~0ull;
+        if (p < m) kv = d2u(err_fmatrix(M, bear[4 * p], bear[4 * p + 1], bear[4 * p + 2], bear[4 * p + 3]) * fj2);
+        st.key()[p] = kv;
+        st.idx()[p] = (uint32_t)p;
+      }
+      __syncthreads();
+      bitonic_sort(st.key(), st.idx(), P);
+      const NfaBest b = best_nfa_block(st.key(), m, s, max_thr, logalpha0, 0.5, loge0, st.logc_n(), st.logc_k(), S.red_nfa,
+                                       S.red_k);
+      if (b.nfa < min_nfa) {
+        better = true;
+        min_nfa = b.nfa;
+        n_in = b.k;
+        for (int p = tid; p < n_in; p += kThreads) st.best_inl()[p] = (int32_t)st.idx()[p];
+        if (tid < 9) S.best_model[tid] = M[tid];
+        if (tid < 5) S.best_smp[tid] = S.pre_smp[slot][tid];
+      }
+    }
+    if ((better && min_nfa < 0.0) || (iter + 1 == n_iter && n_reserve)) {
+      if (n_in == 0) {
+        n_iter++;
+        n_reserve--;
+      } else {
+        __syncthreads();
+        for (int p = tid; p < n_in; p += kThreads) st.vec_index()[p] = st.best_inl()[p];
+        n_index = n_in;
+        identity = false;
+        if (n_reserve) {
+          n_iter = iter + 1 + n_reserve;
+          n_reserve = 0;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (min_nfa >= 0.0) {  // sfmloc.h "decision": nothing meaningful
+    if (tid == 0) R.nfa = min_nfa;
+    return;
+  }
+  // sfmloc.h "decompose", "cheirality"
+  if (tid == 0) {
+    const double *E = S.best_model;
+    double Am[3][3], V[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) Am[i][j] = (E[i] * E[j] + E[3 + i] * E[3 + j]) + E[6 + i] * E[6 + j];
+    jacobi_fixed<3>(Am, V);
+    const double d[3] = {Am[0][0], Am[1][1], Am[2][2]};
+    essential::decompose_from_jacobi(E, d, V, S.cand_R[0], S.cand_R[1], S.cand_t);
+  }
+  if (tid < 4) S.front[tid] = 0;
+  __syncthreads();
+  for (int q = tid; q < 4 * n_in; q += kThreads) {
+    const int c = q & 3, p = st.best_inl()[q >> 2];
+    const double sg = (c & 1) ? -1.0 : 1.0;
+    const double t[3] = {sg * S.cand_t[0], sg * S.cand_t[1], sg * S.cand_t[2]};
+    if (rp_in_front(S.cand_R[c >> 1], t, bear[4 * p], bear[4 * p + 1], bear[4 * p + 2], bear[4 * p + 3]))
+      atomicAdd(&S.front[c], 1);  // (an integer count: the same whatever the order)
+  }
+  for (int p = tid; p < n_in; p += kThreads) A.inl[off + p] = (uint32_t)st.best_inl()[p];
+  __syncthreads();
+  if (tid == 0) {
+    int choice = 0;
+    for (int c = 1; c < 4; ++c)
+      if (S.front[c] > S.front[choice]) choice = c;
+    const int last = st.best_inl()[n_in - 1];
+    const double errmax =
+        err_fmatrix(S.best_model, bear[4 * last], bear[4 * last + 1], bear[4 * last + 2], bear[4 * last + 3]) * fj2;
+    R.n_inliers = (uint32_t)n_in;
+    for (int i = 0; i < 5; ++i) R.sample[i] = (uint32_t)S.best_smp[i];
+    for (int c = 0; c < 4; ++c) R.front[c] = (uint32_t)S.front[c];
+    R.choice = (uint32_t)choice;
+    const double sg = (choice & 1) ? -1.0 : 1.0;
+    for (int i = 0; i < 9; ++i) {
+      R.E[i] = S.best_model[i];
+      R.R[i] = S.cand_R[choice >> 1][i];
+    }
+    for (int i = 0; i < 3; ++i) R.t[i] = sg * S.cand_t[i];
+    R.error_max_px = sqrt(errmax);
+    R.nfa = min_nfa;
+    R.ok = ((double)n_in > 2.5 * s && S.front[choice] > 0) ? 1u : 0u;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_relpose(RpArgs A) {
+  extern __shared__ unsigned char smem_raw[];
+  RpShared &S = *reinterpret_cast<RpShared *>(smem_raw);
+  const uint32_t k = blockIdx.x;
+  if (k >= A.n_pairs) return;
+  if (A.offsets[k + 1] - A.offsets[k] > (uint64_t)kRpLdsMaxM) return;  // k_relpose_large's
+  relpose_pair(A, k, RpStoreLds{&S}, S.small, S.grp);
+}
+
+__global__ __launch_bounds__(kThreads) void k_relpose_large(RpArgs A, RpLargeArgs W) {
+  extern __shared__ unsigned char smem_raw[];
+  RpLargeShared &S = *reinterpret_cast<RpLargeShared *>(smem_raw);
+  const size_t o = (size_t)blockIdx.x * W.slot_m;
+  RpStoreGlobal st{W.key + o, W.idx + o, W.vec_index + o, W.best_inl + o, W.logc_n + (size_t)blockIdx.x * (W.slot_m + 1),
+                   W.logc_k + (size_t)blockIdx.x * (W.slot_m + 1)};
+  for (uint32_t t = blockIdx.x; t < W.n; t += gridDim.x) {
+    const uint32_t k = W.list[t];
+    if (A.offsets[k + 1] - A.offsets[k] <= (uint64_t)W.slot_m) relpose_pair(A, k, st, S.small, S.grp);
+    __syncthreads();
+  }
+}
+
+// sfmloc_debug_five_point: four hypotheses per wave
+__global__ __launch_bounds__(64) void k_debug_five_point(const double *in, int n, double *out) {
+  __shared__ RpGroupLds L[4];
+  __shared__ double models[4][90];
+  const int g = threadIdx.x / essential::kRpGroup;
+  const int h = blockIdx.x * 4 + g;
+  double x1[10], x2[10];
+  for (int i = 0; i < 10; ++i) {
+    x1[i] = h < n ? in[20 * (size_t)h + i] : 0.0;
+    x2[i] = h < n ? in[20 * (size_t)h + 10 + i] : 0.0;
+  }
+  const int nm = essential::five_point_group(L[g], x1, x2, models[g]);
+  if (h < n && (threadIdx.x & (essential::kRpGroup - 1)) == 0) {
+    double *o = out + 91 * (size_t)h;
+    o[0] = (double)nm;
+    for (int i = 0; i < 90; ++i) o[1 + i] = i < 9 * nm ? models[g][i] : 0.0;
+  }
+}
+
+#define RP_TRY(call)         \
+  do {                       \
+    const int rc_ = (call);  \
+    if (rc_) return rc_;     \
+  } while (0)
+
+int relpose_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_wh,
+                   const uint32_t *view_intrinsic, const double *intrinsics, const uint32_t *intrinsic_type,
+                   uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                   const uint32_t *match_i, const uint32_t *match_j, const sfmloc_relpose_options &opt,
+                   const std::vector<uint32_t> &large, uint32_t large_max_m, hipStream_t s, Relpose *r) {
+  const uint64_t total = offsets[n_pairs];
+  DevBuf<uint64_t> d_view_off, d_offsets;
+  DevBuf<float> d_kpt;
+  DevBuf<uint32_t> d_wh, d_vintr, d_itype, d_pairs, d_mi, d_mj, d_inl, d_large;
+  DevBuf<double> d_intr, d_bear, d_L10;
+  DevBuf<sfmloc_relpose_result> d_res;
+  RP_TRY(dev_upload(nullptr, d_view_off, view_off, (size_t)n_views + 1, s));
+  RP_TRY(dev_upload(nullptr, d_kpt, kpt_xy, 2 * (size_t)view_off[n_views], s));
+  RP_TRY(dev_upload(nullptr, d_wh, view_wh, 2 * (size_t)n_views, s));
+  RP_TRY(dev_upload(nullptr, d_vintr, view_intrinsic, (size_t)n_views, s));
+  RP_TRY(dev_upload(nullptr, d_intr, intrinsics, 6 * (size_t)n_intrinsics, s));
+  RP_TRY(dev_upload(nullptr, d_itype, intrinsic_type, (size_t)n_intrinsics, s));
+  RP_TRY(dev_upload(nullptr, d_pairs, pairs, 2 * (size_t)n_pairs, s));
+  RP_TRY(dev_upload(nullptr, d_offsets, offsets, (size_t)n_pairs + 1, s));
+  RP_TRY(dev_upload(nullptr, d_mi, match_i, (size_t)total, s));
+  RP_TRY(dev_upload(nullptr, d_mj, match_j, (size_t)total, s));
+  RP_TRY(d_bear.alloc(nullptr, 4 * (size_t)total));
+  RP_TRY(d_inl.alloc(nullptr, (size_t)total));
+  RP_TRY(d_L10.alloc(nullptr, kRpL10));
+  RP_TRY(d_res.alloc(nullptr, n_pairs));
+  SFM_HIP(hipMemsetAsync(d_res, 0, (size_t)n_pairs * sizeof(sfmloc_relpose_result), s));  // (the records' padding too)
+  hipLaunchKernelGGL(k_rp_fill_log10, dim3((kRpL10 + 255) / 256), dim3(256), 0, s, d_L10.get(), kRpL10);
+  hipLaunchKernelGGL(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, n_pairs, (const uint32_t *)d_pairs,
+                     (const uint64_t *)d_offsets, (const uint64_t *)d_view_off, (const float *)d_kpt,
+                     (const uint32_t *)d_mi, (const uint32_t *)d_mj, (const uint32_t *)d_vintr, (const uint32_t *)d_itype,
+                     (const double *)d_intr, d_bear.get());
+  SFM_HIP(hipGetLastError());
+  RpArgs A;
+  A.n_pairs = n_pairs;
+  A.n_iter = (int)opt.max_iteration;
+  A.precision = opt.precision_px;
+  A.seed = opt.seed;
+  A.pairs = d_pairs;
+  A.offsets = d_offsets;
+  A.bear = d_bear;
+  A.view_wh = d_wh;
+  A.view_intr = d_vintr;
+  A.intr = d_intr;
+  A.L10 = d_L10;
+  A.res = d_res;
+  A.inl = d_inl;
+  // (per call, not once per process: the attribute belongs to the device that is current, and `device` is the call's)
+  SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_relpose), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)sizeof(RpShared)));
+  hipLaunchKernelGGL(k_relpose, dim3(n_pairs), dim3(kThreads), sizeof(RpShared), s, A);
+  SFM_HIP(hipGetLastError());
+  DevBuf<uint64_t> d_key;
+  DevBuf<uint32_t> d_idx;
+  DevBuf<int32_t> d_vi, d_bi;
+  DevBuf<float> d_ln, d_lk;
+  if (!large.empty()) {  // the pairs the LDS form left: slots of a power of two that holds the longest
+    int slot_m = 2 * kRpLdsMaxM;
+    while (slot_m < (int)large_max_m) slot_m <<= 1;
+    const size_t n_slots = large.size() < (size_t)kRpLargeSlots ? large.size() : (size_t)kRpLargeSlots;
+    RP_TRY(dev_upload(nullptr, d_large, large.data(), large.size(), s));
+    RP_TRY(d_key.alloc(nullptr, n_slots * slot_m));
+    RP_TRY(d_idx.alloc(nullptr, n_slots * slot_m));
+    RP_TRY(d_vi.alloc(nullptr, n_slots * slot_m));
+    RP_TRY(d_bi.alloc(nullptr, n_slots * slot_m));
+    RP_TRY(d_ln.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
+    RP_TRY(d_lk.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
+    RpLargeArgs W;
+    W.list = d_large;
+    W.n = (uint32_t)large.size();
+    W.key = d_key;
+    W.idx = d_idx;
+    W.vec_index = d_vi;
+    W.best_inl = d_bi;
+    W.logc_n = d_ln;
+    W.logc_k = d_lk;
+    W.slot_m = slot_m;
+    SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_relpose_large), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(RpLargeShared)));
+    hipLaunchKernelGGL(k_relpose_large, dim3((unsigned)n_slots), dim3(kThreads), sizeof(RpLargeShared), s, A, W);
+    SFM_HIP(hipGetLastError());
+  }
+  std::vector<uint32_t> inl((size_t)total);
+  SFM_HIP(hipMemcpyAsync(r->res.data(), d_res, (size_t)n_pairs * sizeof(sfmloc_relpose_result), hipMemcpyDeviceToHost, s));
+  if (total) SFM_HIP(hipMemcpyAsync(inl.data(), d_inl, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < n_pairs; ++k) {
+    const uint32_t n = r->res[k].n_inliers;
+    r->idx.insert(r->idx.end(), inl.begin() + (size_t)offsets[k], inl.begin() + (size_t)offsets[k] + n);
+    r->off[k + 1] = r->idx.size();
+  }
+  return SFMLOC_OK;
+}
+
+int relpose_impl(int device, const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_wh,
+                 const uint32_t *view_intrinsic, const double *intrinsics, const uint32_t *intrinsic_type,
+                 uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                 const uint32_t *match_i, const uint32_t *match_j, const sfmloc_relpose_options &opt, Relpose *r) {
+  std::vector<uint32_t> large;
+  uint32_t large_max_m = 0;
+  std::string err;
+  const int rc = relpose_host::check(view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type,
+                                     n_intrinsics, pairs, n_pairs, offsets, match_i, match_j, &large, &large_max_m, &err);
+  SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
+  SFM_CHECK(opt.max_iteration <= (1u << 30), SFMLOC_EINVAL, "sfmloc_relative_poses: max_iteration = %u", opt.max_iteration);
+  SFM_CHECK(!(opt.precision_px < 0.0) && opt.precision_px == opt.precision_px, SFMLOC_EINVAL,
+            "sfmloc_relative_poses: precision_px must not be negative");
+  int rc_dev = CallScope::use_device(device);
+  if (rc_dev) return rc_dev;
+  g_relpose_last_ms = 0.0;
+  r->res.assign(n_pairs, sfmloc_relpose_result{});
+  r->off.assign((size_t)n_pairs + 1, 0);
+  if (n_pairs == 0) return SFMLOC_OK;  // nothing to launch
+  CallScope d;
+  if ((rc_dev = d.open(true, &g_relpose_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
+  rc_dev = relpose_device(view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
+                          pairs, n_pairs, offsets, match_i, match_j, opt, large, large_max_m, d.s, r);
+  return rc_dev ? rc_dev : d.time_end();
+}
+
+}  // namespace
+}  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" {
+
+void sfmloc_relpose_default_options(sfmloc_relpose_options *o) {
+  if (!o) return;
+  o->max_iteration = 256;
+  o->reserved = 0;
+  o->precision_px = 2.5;
+  o->seed = 0x5F3759DF12345678ull;
+}
+
+int sfmloc_relative_poses(int device, const uint64_t *view_off, uint32_t n_views, const float *kpt_xy,
+                          const uint32_t *view_wh, const uint32_t *view_intrinsic, const double *intrinsics,
+                          const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs,
+                          const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
+                          const sfmloc_relpose_options *opt, sfmloc_relpose **out) {
+  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_relative_poses: null argument");
+  *out = nullptr;
+  sfmloc_relpose_options o;
+  if (opt) o = *opt;
+  else sfmloc_relpose_default_options(&o);
+  Relpose *r = new (std::nothrow) Relpose();
+  SFM_CHECK(r, SFMLOC_ENOMEM, "out of host memory");
+  int rc;
+  try {
+    rc = relpose_impl(device, view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
+                      pairs, n_pairs, offsets, match_i, match_j, o, r);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_relative_poses: out of host memory");
+    rc = SFMLOC_ENOMEM;
+  }
+  if (rc) {
+    delete r;
+    return rc;
+  }
+  *out = reinterpret_cast<sfmloc_relpose *>(r);
+  return SFMLOC_OK;
+}
+
+int sfmloc_relpose_results(const sfmloc_relpose *rr, sfmloc_relpose_result *out) {
+  SFM_CHECK(rr, SFMLOC_EINVAL, "sfmloc_relpose_results: null handle");
+  const Relpose *r = reinterpret_cast<const Relpose *>(rr);
+  SFM_CHECK(out || r->res.empty(), SFMLOC_EINVAL, "sfmloc_relpose_results: null argument");
+  if (!r->res.empty()) memcpy(out, r->res.data(), r->res.size() * sizeof(sfmloc_relpose_result));
+  return SFMLOC_OK;
+}
+
+int sfmloc_relpose_inliers(const sfmloc_relpose *rr, uint64_t *off, uint32_t *idx) {
+  SFM_CHECK(rr, SFMLOC_EINVAL, "sfmloc_relpose_inliers: null handle");
+  const Relpose *r = reinterpret_cast<const Relpose *>(rr);
+  if (off) memcpy(off, r->off.data(), r->off.size() * sizeof(uint64_t));
+  if (idx && !r->idx.empty()) memcpy(idx, r->idx.data(), r->idx.size() * sizeof(uint32_t));
+  return SFMLOC_OK;
+}
+
+void sfmloc_relpose_destroy(sfmloc_relpose *r) { delete reinterpret_cast<Relpose *>(r); }
+
+double sfmloc_relpose_last_ms(void) { return g_relpose_last_ms; }
+
+int sfmloc_debug_five_point(int device, const double *in, int n, double *out) {
+  SFM_CHECK(in && out && n > 0, SFMLOC_EINVAL, "sfmloc_debug_five_point: bad argument");
+  int rc = CallScope::use_device(device);
+  if (rc) return rc;
+  CallScope d;
+  double ms = 0.0;
+  if ((rc = d.open(false, &ms))) return rc;
+  DevBuf<double> d_in, d_out;
+  if ((rc = dev_upload(nullptr, d_in, in, 20 * (size_t)n, d.s))) return rc;
+  if ((rc = d_out.alloc(nullptr, 91 * (size_t)n))) return rc;
+  hipLaunchKernelGGL(k_debug_five_point, dim3((n + 3) / 4), dim3(64), 0, d.s, (const double *)d_in, n, d_out.get());
+  SFM_HIP(hipGetLastError());
+  SFM_HIP(hipMemcpyAsync(out, d_out, 91 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, d.s));
+  SFM_HIP(hipStreamSynchronize(d.s));
+  return SFMLOC_OK;
+}
+
+}  // extern "C"

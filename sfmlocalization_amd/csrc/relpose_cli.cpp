@@ -1,0 +1,312 @@
+// ComputeRelativePoses as a C++ host program over the C ABI (plain g++):
+//
+//   ComputeRelativePoses -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>] [-o <matches.e.txt>]
+//                        [-p <relative_poses.json>] [-n <iterations = 256>] [-t <precision px = 2.5>] [--seed N] [--device 0]
+//
+// The same program as sfmlocalization_amd/relpose.py and the same bytes in both output files: the relative pose of every
+// matched view pair (sfmloc_relative_poses, the first stage of openMVG_main_GlobalSfM).  The essential matches hold the ok
+// pairs only, each with its inliers in ascending (i, j); the poses file lists them in ascending (I, J).
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../include/sfmloc.h"
+#include "sfm_doc.h"
+#include "sfm_json.h"
+
+using sfmdoc::Doc;
+using sfmjson::Value;
+
+namespace {
+
+const char *kName = "ComputeRelativePoses";
+
+void usage() {
+  fprintf(stderr,
+          "Usage: %s\n"
+          "[-i|--input_file] path to a SfM_Data scene\n"
+          "[-m|--match_dir] path to the features and matches that correspond to the provided SfM_Data scene\n"
+          "\n[Optional]\n"
+          "[-f|--match_file] path to a matches file (default: matches.f.txt in the match directory)\n"
+          "[-o|--output_file] essential matches to write (default: matches.e.txt in the match directory)\n"
+          "[-p|--poses_file] relative poses to write (default: relative_poses.json in the match directory)\n"
+          "[-n|--max_iteration] AC-RANSAC iterations per pair (256)\n"
+          "[-t|--precision] upper bound on the residual in pixels (2.5)\n"
+          "[--seed] sampling seed\n"
+          "[--device] HIP device (0)\n",
+          kName);
+}
+
+// os.path.join(root, name)
+std::string join(const std::string &root, const std::string &name) {
+  if (root.empty() || (!name.empty() && name[0] == '/')) return name;
+  return root + (root.back() == '/' ? "" : "/") + name;
+}
+
+// os.path.splitext(os.path.basename(name))[0]
+std::string stem_of(const std::string &name) {
+  const size_t slash = name.rfind('/');
+  std::string base = slash == std::string::npos ? name : name.substr(slash + 1);
+  size_t lead = 0;
+  while (lead < base.size() && base[lead] == '.') ++lead;
+  const size_t dot = base.rfind('.');
+  if (dot != std::string::npos && dot > lead) base.resize(dot);
+  return base;
+}
+
+void set_key(Value *obj, const char *k, Value v) {
+  Value *slot = obj->get(k);
+  if (slot) *slot = std::move(v);
+  else obj->o.emplace_back(k, std::move(v));
+}
+
+// "x y size angle" per line, read as float32; stops at the first short line (fileio.read_feat)
+bool read_feat(const std::string &path, std::vector<float> *xy) {
+  std::ifstream f(path);
+  if (!f) return false;
+  std::string line;
+  while (std::getline(f, line)) {
+    std::istringstream ss(line);
+    std::string t[4];
+    if (!(ss >> t[0] >> t[1] >> t[2] >> t[3])) break;
+    xy->push_back(strtof(t[0].c_str(), nullptr));
+    xy->push_back(strtof(t[1].c_str(), nullptr));
+  }
+  return true;
+}
+
+struct PairList {
+  std::vector<uint32_t> pairs, mi, mj;
+  std::vector<uint64_t> offsets{0};
+};
+
+// "I J\nn\ni j\n..." with view ids as keys (fileio.read_matches_txt), into the layout of sfmloc_tracks_build in ascending
+// (I, J); the same pair twice: the later entry replaces the earlier, as a dictionary does
+bool read_matches(const std::string &path, const std::map<uint32_t, uint32_t> &view_index, PairList *out, std::string *err) {
+  std::ifstream f(path);
+  if (!f) return *err = "cannot be read", false;
+  std::map<std::pair<uint32_t, uint32_t>, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> all;
+  std::string ta, tb, tn;
+  while (f >> ta) {
+    if (!(f >> tb >> tn)) return *err = "truncated", false;
+    char *e1, *e2, *e3;
+    const long long a = strtoll(ta.c_str(), &e1, 10), b = strtoll(tb.c_str(), &e2, 10), n = strtoll(tn.c_str(), &e3, 10);
+    if (*e1 || *e2 || *e3 || a < 0 || b < 0 || n < 0 || a > 0xFFFFFFFFll || b > 0xFFFFFFFFll) return *err = "malformed", false;
+    auto &dst = all[{(uint32_t)a, (uint32_t)b}];
+    dst.first.clear();
+    dst.second.clear();
+    for (long long t = 0; t < n; ++t) {
+      std::string ti, tj;
+      if (!(f >> ti >> tj)) return *err = "truncated", false;
+      const long long i = strtoll(ti.c_str(), &e1, 10), j = strtoll(tj.c_str(), &e2, 10);
+      if (*e1 || *e2 || i < 0 || j < 0 || i > 0xFFFFFFFFll || j > 0xFFFFFFFFll) return *err = "malformed", false;
+      dst.first.push_back((uint32_t)i);
+      dst.second.push_back((uint32_t)j);
+    }
+  }
+  for (const auto &kv : all) {
+    const auto ia = view_index.find(kv.first.first), ib = view_index.find(kv.first.second);
+    if (ia == view_index.end() || ib == view_index.end()) return *err = "a pair names an unknown view", false;
+    out->pairs.push_back(ia->second);
+    out->pairs.push_back(ib->second);
+    out->mi.insert(out->mi.end(), kv.second.first.begin(), kv.second.first.end());
+    out->mj.insert(out->mj.end(), kv.second.second.begin(), kv.second.second.end());
+    out->offsets.push_back(out->mi.size());
+  }
+  return true;
+}
+
+Value make_int(uint64_t v) {
+  Value x;
+  x.kind = Value::Int;
+  x.s = std::to_string(v);
+  return x;
+}
+
+Value floats(const double *v, int n) {
+  Value a = Value::make_arr();
+  for (int i = 0; i < n; ++i) a.a.push_back(Value::make_float(v[i]));
+  return a;
+}
+
+Value rows3(const double *v) {
+  Value a = Value::make_arr();
+  for (int i = 0; i < 3; ++i) a.a.push_back(floats(v + 3 * i, 3));
+  return a;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  std::string in, match_dir, match_file = "matches.f.txt", out_file = "matches.e.txt", poses_file = "relative_poses.json",
+              n_txt = "256", t_txt = "2.5", seed_txt, dev_txt = "0";
+  for (int i = 1; i < argc; ++i) {
+    std::string a = argv[i];
+    std::string *dst = nullptr;
+    const size_t eq = a.find('=');
+    if (eq != std::string::npos && (a.substr(0, eq) == "--seed" || a.substr(0, eq) == "--device")) {
+      (a.substr(0, eq) == "--seed" ? seed_txt : dev_txt) = a.substr(eq + 1);
+      continue;
+    }
+    if (a == "-i" || a == "--input_file") dst = &in;
+    else if (a == "-m" || a == "--match_dir") dst = &match_dir;
+    else if (a == "-f" || a == "--match_file") dst = &match_file;
+    else if (a == "-o" || a == "--output_file") dst = &out_file;
+    else if (a == "-p" || a == "--poses_file") dst = &poses_file;
+    else if (a == "-n" || a == "--max_iteration") dst = &n_txt;
+    else if (a == "-t" || a == "--precision") dst = &t_txt;
+    else if (a == "--seed") dst = &seed_txt;
+    else if (a == "--device") dst = &dev_txt;
+    if (!dst || i + 1 >= argc) {
+      usage();
+      return 1;
+    }
+    *dst = argv[++i];
+  }
+  char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr, *e4 = nullptr;
+  const long long max_iteration = strtoll(n_txt.c_str(), &e1, 10);
+  const double precision = strtod(t_txt.c_str(), &e2);
+  const unsigned long long seed = strtoull(seed_txt.c_str(), &e3, 0);
+  const long device = strtol(dev_txt.c_str(), &e4, 10);
+  if (n_txt.empty() || t_txt.empty() || dev_txt.empty() || *e1 || *e2 || *e3 || *e4 || in.empty() || match_dir.empty() ||
+      max_iteration < 0 || !(precision >= 0.0)) {
+    usage();
+    return 1;
+  }
+  Doc d;
+  std::string err, text;
+  bool ok = sfmjson::read_file(in.c_str(), &text);
+  if (!ok) err = "cannot be read";
+  ok = ok && sfmjson::parse(text, &d.root, &err);
+  if (ok && d.root.kind == Value::Obj) set_key(&d.root, "structure", Value::make_arr());
+  ok = ok && sfmdoc::build(&d, &err);
+  const uint32_t n_views = ok ? (uint32_t)d.view_id.size() : 0;
+  const Value *views = ok ? d.root.get("views") : nullptr;
+  std::vector<uint32_t> view_wh(2 * (size_t)n_views);
+  for (uint32_t k = 0; ok && k < n_views; ++k) {
+    const Value *data = sfmdoc::ptr_data(views->a[k].get("value"));
+    if (!data || !sfmdoc::num_u32(data->get("width"), &view_wh[2 * k]) ||
+        !sfmdoc::num_u32(data->get("height"), &view_wh[2 * k + 1])) {
+      ok = false;
+      err = "a view without width or height";
+    }
+  }
+  if (!ok) {
+    fprintf(stderr, "\nThe input SfM_Data file \"%s\" cannot be read. (%s)\n", in.c_str(), err.c_str());
+    return 1;
+  }
+  std::vector<float> kpt;
+  std::vector<uint64_t> view_off(1, 0);
+  for (uint32_t k = 0; k < n_views; ++k) {
+    const Value *data = sfmdoc::ptr_data(views->a[k].get("value"));
+    const Value *fn = data ? data->get("filename") : nullptr;
+    const std::string path = join(match_dir, stem_of((fn && fn->kind == Value::Str) ? fn->s : std::string()) + ".feat");
+    if (!read_feat(path, &kpt)) {
+      fprintf(stderr, "\nInvalid features. (%s cannot be read)\n", path.c_str());
+      return 1;
+    }
+    view_off.push_back(kpt.size() / 2);
+  }
+  std::map<uint32_t, uint32_t> view_index;
+  for (uint32_t k = 0; k < n_views; ++k) view_index[d.view_id[k]] = k;
+  PairList all, pl;
+  const std::string mpath = join(match_dir, match_file);
+  if (!read_matches(mpath, view_index, &all, &err)) {
+    fprintf(stderr, "\nInvalid matches file. (%s: %s)\n", mpath.c_str(), err.c_str());
+    return 1;
+  }
+  std::vector<uint32_t> itype(d.intr_type);
+  const auto usable = [&](uint32_t v) { return d.intr_type[d.view_intr[v]] == 0 || d.intr_type[d.view_intr[v]] == 3; };
+  size_t skipped = 0;
+  for (size_t k = 0; k + 1 < all.offsets.size(); ++k) {  // pairs with a view without a usable intrinsic are left out
+    const uint32_t a = all.pairs[2 * k], b = all.pairs[2 * k + 1];
+    if (!usable(a) || !usable(b)) {
+      ++skipped;
+      continue;
+    }
+    pl.pairs.push_back(a);
+    pl.pairs.push_back(b);
+    pl.mi.insert(pl.mi.end(), all.mi.begin() + all.offsets[k], all.mi.begin() + all.offsets[k + 1]);
+    pl.mj.insert(pl.mj.end(), all.mj.begin() + all.offsets[k], all.mj.begin() + all.offsets[k + 1]);
+    pl.offsets.push_back(pl.mi.size());
+  }
+  if (skipped) fprintf(stderr, "%s: %zu pairs skipped: a view without a usable intrinsic\n", kName, skipped);
+  for (uint32_t &t : itype)
+    if (t != 0 && t != 3) t = 0;
+  const uint32_t n_pairs = (uint32_t)(pl.pairs.size() / 2);
+  printf("#views: %u; #pairs: %u, #matches: %zu\n", n_views, n_pairs, pl.mi.size());
+  fflush(stdout);
+  sfmloc_relpose_options opt;
+  sfmloc_relpose_default_options(&opt);
+  opt.max_iteration = (uint32_t)max_iteration;
+  opt.precision_px = precision;
+  if (!seed_txt.empty()) opt.seed = seed;
+  sfmloc_relpose *h = nullptr;
+  if (sfmloc_relative_poses((int)device, view_off.data(), n_views, kpt.data(), view_wh.data(), d.view_intr.data(),
+                            d.intr.data(), itype.data(), (uint32_t)itype.size(), pl.pairs.data(), n_pairs, pl.offsets.data(),
+                            pl.mi.data(), pl.mj.data(), &opt, &h)) {
+    fprintf(stderr, "%s: %s\n", kName, sfmloc_last_error());
+    return 1;
+  }
+  std::vector<sfmloc_relpose_result> res(n_pairs ? n_pairs : 1);
+  std::vector<uint64_t> off((size_t)n_pairs + 1, 0);
+  sfmloc_relpose_results(h, res.data());
+  sfmloc_relpose_inliers(h, off.data(), nullptr);
+  std::vector<uint32_t> idx(off[n_pairs] ? off[n_pairs] : 1);
+  sfmloc_relpose_inliers(h, nullptr, idx.data());
+  sfmloc_relpose_destroy(h);
+  size_t n_ok = 0, n_ess = 0;
+  for (uint32_t k = 0; k < n_pairs; ++k)
+    if (res[k].ok) {
+      ++n_ok;
+      n_ess += res[k].n_inliers;
+    }
+  printf("Relative poses: %zu of %u pairs; %zu essential matches; device %.3f ms\n", n_ok, n_pairs, n_ess,
+         sfmloc_relpose_last_ms());
+  fflush(stdout);
+  std::string etxt;
+  Value list = Value::make_arr();
+  for (uint32_t k = 0; k < n_pairs; ++k) {  // (the pair list ascends by (I, J): view ids ascend with the view index)
+    const sfmloc_relpose_result &r = res[k];
+    if (!r.ok) continue;
+    const uint32_t a = pl.pairs[2 * k], b = pl.pairs[2 * k + 1];
+    std::vector<std::pair<uint32_t, uint32_t>> ij;
+    for (uint64_t p = off[k]; p < off[k + 1]; ++p) ij.emplace_back(pl.mi[pl.offsets[k] + idx[p]], pl.mj[pl.offsets[k] + idx[p]]);
+    std::sort(ij.begin(), ij.end());
+    etxt += std::to_string(d.view_id[a]) + " " + std::to_string(d.view_id[b]) + "\n" + std::to_string(ij.size()) + "\n";
+    for (const auto &m : ij) etxt += std::to_string(m.first) + " " + std::to_string(m.second) + "\n";
+    Value front = Value::make_arr();
+    for (int c = 0; c < 4; ++c) front.a.push_back(make_int(r.front[c]));
+    Value e;
+    e.kind = Value::Obj;
+    e.o.emplace_back("I", make_int(d.view_id[a]));
+    e.o.emplace_back("J", make_int(d.view_id[b]));
+    e.o.emplace_back("n_matches", make_int(r.n_matches));
+    e.o.emplace_back("n_inliers", make_int(r.n_inliers));
+    e.o.emplace_back("R", rows3(r.R));
+    e.o.emplace_back("t", floats(r.t, 3));
+    e.o.emplace_back("E", rows3(r.E));
+    e.o.emplace_back("error_max", Value::make_float(r.error_max_px));
+    e.o.emplace_back("front", front);
+    e.o.emplace_back("choice", make_int(r.choice));
+    list.a.push_back(e);
+  }
+  Value doc;
+  doc.kind = Value::Obj;
+  doc.o.emplace_back("relative_poses", list);
+  std::string jtxt;
+  sfmjson::dump(doc, &jtxt);
+  const std::string epath = join(match_dir, out_file), ppath = join(match_dir, poses_file);
+  if (!sfmjson::write_file(epath.c_str(), etxt) || !sfmjson::write_file(ppath.c_str(), jtxt)) {
+    fprintf(stderr, "%s: %s or %s cannot be written\n", kName, epath.c_str(), ppath.c_str());
+    return 1;
+  }
+  return 0;
+}
