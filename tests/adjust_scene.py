@@ -193,3 +193,56 @@ def two_pass_case():
                 landmark_id=np.arange(len(lm_X), dtype=np.uint32) * 4 + 2, landmark_X=np.array(lm_X),
                 obs_off=np.array(obs_off, np.uint64), obs_view=np.array(obs_view, np.uint32),
                 obs_x=np.array(obs_x, np.float64))
+
+
+SPARSE_OBSERVED = (0, 1, 254, 255, 256)    # with the last view: the only views of sparse_views_case that see anything
+SPARSE_FEW = {0: 12, 1: 10}                # view 0 is resected on 12 observations, view 1 (10) is not
+
+
+def radix_key_bits(max_key):
+    """csrc/radix_sort.h radix_key_bits: the key bits the transpose's sort looks at for view indices 0..max_key"""
+    return int(max_key).bit_length()
+
+
+def sparse_views_case(n_views, seed=7):
+    """arrays (as two_pass_case) for the transpose's sort as adjust.hip compiles it: n_views views on one pinhole
+    intrinsic, cameras on an arc looking at a cloud of landmarks, every view with a pose; only the views
+    SPARSE_OBSERVED and n_views - 1 (those that exist) have observations, exact projections plus 0.3 px of noise.
+    Views 0 and 1 see 12 and 10 landmarks; every other observed view sees q of 2 q landmarks, q = 200 or, where that
+    leaves the total under 1025, the smallest q that reaches it (with four such views 251): the sort then runs over
+    more than one block, with radix_key_bits(n_views - 1) = 8 or 9 key bits -- one pass, or two whose second one sorts on
+    the bit that parts view 256 and later from the rest.  n_views = 1: a single view with 200 observations, zero key
+    bits, no pass."""
+    rng = np.random.Generator(np.random.PCG64(seed + n_views))
+    f, ppx, ppy = 800.0, 320.0, 240.0
+    observed = sorted({v for v in SPARSE_OBSERVED + (n_views - 1,) if v < n_views})
+    full = [v for v in observed if v not in SPARSE_FEW or n_views == 1]
+    q = 200 if n_views == 1 else max(200, -(-(1025 - sum(SPARSE_FEW.values())) // len(full)))
+    X = rng.uniform([-2.0, -1.5, -2.0], [2.0, 1.5, 2.0], (2 * q, 3))
+    ang = np.linspace(-0.6, 0.6, n_views) if n_views > 1 else np.zeros(1)
+    pose_C = np.stack([12.0 * np.sin(ang), 0.3 * np.cos(5.0 * ang), -12.0 * np.cos(ang)], 1)
+    pose_R = np.zeros((n_views, 3, 3))
+    for k in range(n_views):                                    # rows: right, down, forward (towards the origin)
+        fw = -pose_C[k] / np.linalg.norm(pose_C[k])
+        right = np.cross([0.0, 1.0, 0.0], fw)
+        right /= np.linalg.norm(right)
+        pose_R[k] = np.stack([right, np.cross(fw, right), fw])
+    sees = {v: set(rng.permutation(2 * q)[:(q if v in full else SPARSE_FEW[v])].tolist()) for v in observed}
+    lm_X, obs_off, obs_view, obs_x = [], [0], [], []
+    for l in range(2 * q):
+        views = [v for v in observed if l in sees[v]]
+        if not views:
+            continue
+        lm_X.append(X[l])
+        for v in views:
+            Xc = pose_R[v] @ (X[l] - pose_C[v])
+            obs_view.append(v)
+            obs_x.append(f * Xc[:2] / Xc[2] + np.array([ppx, ppy]) + rng.normal(0, 0.3, 2))
+        obs_off.append(len(obs_view))
+    return dict(view_id=np.arange(n_views, dtype=np.uint32), view_intrinsic=np.zeros(n_views, np.uint32),
+                view_pose=np.arange(n_views, dtype=np.uint32), intrinsic_type=np.zeros(1, np.uint32),
+                intrinsic=np.array([[f, ppx, ppy, 0.0, 0.0, 0.0]]), pose_valid=np.ones(n_views, np.uint8),
+                pose_R=pose_R.reshape(n_views, 9), pose_C=pose_C,
+                landmark_id=np.arange(len(lm_X), dtype=np.uint32) * 3 + 1, landmark_X=np.array(lm_X),
+                obs_off=np.array(obs_off, np.uint64), obs_view=np.array(obs_view, np.uint32),
+                obs_x=np.array(obs_x, np.float64))

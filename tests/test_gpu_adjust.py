@@ -39,9 +39,8 @@ def scene():
     return doc, a, exp, pv, R, C, oracle_c
 
 
-def test_resection_matches_oracle(scene):
-    doc, a, exp, pv, R, C, oracle_c = scene
-    h = S.Sfm(**a)
+def resect_and_compare(h, exp):
+    """h.resect() against the oracle's resection of every view (adjust_scene.oracle_resect) -> resect_read()"""
     ran, ok = h.resect()
     res = h.resect_read()
     assert ran == sum(e["ran"] for e in exp) and ok == sum(e["ok"] for e in exp)
@@ -70,6 +69,13 @@ def test_resection_matches_oracle(scene):
             np.testing.assert_array_equal(bits(np.array(r.center)), bits(e["center"]))
         else:                           # sfmloc.h: R and centre only on success
             assert not np.any(np.array(r.R)) and not np.any(np.array(r.center)), k
+    return res
+
+
+def test_resection_matches_oracle(scene):
+    doc, a, exp, pv, R, C, oracle_c = scene
+    h = S.Sfm(**a)
+    res = resect_and_compare(h, exp)
     p = h.read(masks=False)
     np.testing.assert_array_equal(p["pose_valid"], pv)
     np.testing.assert_array_equal(bits(p["pose_R"].reshape(-1, 9)), bits(R))
@@ -89,6 +95,36 @@ def test_resection_matches_oracle(scene):
     ud = np.array([AN.ud_pixel_k3(*K, *xy) for xy in a["obs_x"][idx]])
     u = oracle_c.p3p_localize(ud, a["landmark_X"][obs_lm[idx]], K[0], K[1], K[2], 4096, AS.SEED, stream=int(a["view_id"][k]))
     assert not np.array_equal(bits(u["P"].ravel()), bits(np.array(res[k].P)))
+    h.close()
+
+
+@pytest.mark.parametrize("n_views,key_bits", [(1, 0), (256, 8), (257, 9), (300, 9)])
+def test_resection_on_sparse_view_lists(n_views, key_bits):
+    """The transpose's sort (radix_sort.h as adjust.hip compiles it) with zero, one and two passes over more than one
+    block, and view indices above 255: a view's P depends on which observations are in its list and in which order, and
+    n_obs of every view, the empty ones too, on k_adj_view_off."""
+    from oracle import oracle_c
+    oracle_c.build()
+    a = AS.sparse_views_case(n_views)
+    assert AS.radix_key_bits(n_views - 1) == key_bits
+    n_obs = np.bincount(a["obs_view"], minlength=n_views)
+    observed = [v for v in AS.SPARSE_OBSERVED + (n_views - 1,) if v < n_views]
+    assert set(np.nonzero(n_obs)[0].tolist()) == set(observed)
+    if n_views == 1:
+        assert n_obs.tolist() == [200]
+    else:
+        assert len(a["obs_view"]) > 1024 and n_obs[0] == 12 and n_obs[1] == 10 and n_obs[observed[2:]].min() >= 200
+    exp, pv, R, C = AS.oracle_resect(a, oracle_c)
+    h = S.Sfm(**a)
+    res = resect_and_compare(h, exp)
+    assert [r.n_obs for r in res] == n_obs.tolist()
+    assert res[0].ran and res[0].ok and all(res[v].ok for v in observed[2:])
+    if n_views > 1:
+        assert not res[1].ran
+    p = h.read(masks=False)
+    np.testing.assert_array_equal(p["pose_valid"], pv)
+    np.testing.assert_array_equal(bits(p["pose_R"].reshape(-1, 9)), bits(R))
+    np.testing.assert_array_equal(bits(p["pose_C"]), bits(C))
     h.close()
 
 
