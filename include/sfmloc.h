@@ -471,6 +471,11 @@ int sfmloc_bof_compute(sfmloc_bof *bof, const float *desc, const float *kpt_xy, 
 /* (AKAZEOpenCV.cpp:44-46,67); sfmloc_akaze_compute replaces extractor->compute(gray, keypoints, desc) on given  */
 /* keypoints (DenseLocalFeatureWrapper.cpp:146; class_id = evolution level, octave 0).                           */
 /* An extractor is bound to one image size (it owns the scale-space buffers).                                    */
+/*   limits (sfmloc_akaze_create, SFMLOC_EINVAL beyond): width 16 .. 16384, height 16 .. 4096; n_octaves 1 .. 8,    */
+/*   n_sublevels >= 1, n_octaves * n_sublevels <= 32; and no evolution level may need more than 64 diffusion (FED)  */
+/*   steps -- the steps of a level depend on its octave and sub-level alone: octaves 0 .. 4 never do (63 at most),  */
+/*   an octave 5 that survives the cut (a frame of 2560 x 1280 or more with n_octaves >= 6) does; the text names    */
+/*   the level and its step count.  More than 65 536 extrema candidates in one image: SFMLOC_ECAP from the call.    */
 /*   kpts [cap*6]: x, y, size (diameter), angle (radians), response, class_id                                    */
 /*   desc64 [cap*64]: rows exactly as saveAKAZEBin stores them (61 M-LDB bytes + 3 zero bytes, FileUtils.cpp:77-92) */
 /* ------------------------------------------------------------------------- */

@@ -301,8 +301,34 @@ def refine_pose(pt2d, pt3d, inliers, focal, ppx, ppy, R, t, max_iter=20):
 # ---------------------------------------------------------------------------------------------------
 def akaze_levels(w, h, omax=4, nsub=4):
     wh = np.zeros(64, np.int32)
+    lib().orc_akaze_levels.restype = C.c_int
     n = lib().orc_akaze_levels(C.c_int(w), C.c_int(h), C.c_int(omax), C.c_int(nsub), _p(wh, C.c_int32))
+    if n < 0:
+        raise ValueError(_akaze_refusal(w, h, omax, nsub))
     return wh[:2 * n].reshape(n, 2)
+
+
+def _akaze_refusal(w, h, omax, nsub):
+    try:
+        akaze_plan(w, h, omax, nsub)
+    except ValueError as e:
+        return str(e)
+    return f"AKAZE plan {w}x{h} nOct {omax} nOctLay {nsub} refused"
+
+
+def akaze_plan(w, h, omax=4, nsub=4):
+    """orc_akaze_plan_read -> lev [n x 6] int32 (w, h, octave, sublevel, sigma_size, nsteps), tsteps [n x 64] float32;
+    ValueError for a schedule with more than 64 FED steps at one level (the library refuses it too)."""
+    lev = np.zeros((32, 6), np.int32)
+    ts = np.zeros((32, 64), np.float32)
+    bad = np.zeros(2, np.int32)
+    lib().orc_akaze_plan_read.restype = C.c_int
+    n = lib().orc_akaze_plan_read(C.c_int(w), C.c_int(h), C.c_int(omax), C.c_int(nsub), _p(lev, C.c_int32),
+                                  _p(ts, C.c_float), _p(bad, C.c_int32))
+    if n < 0:
+        raise ValueError(f"AKAZE plan {w}x{h} nOct {omax} nOctLay {nsub}: {int(bad[1])} diffusion steps at level "
+                         f"{int(bad[0])} (at most 64 per level)")
+    return lev[:n].copy(), ts[:n].copy()
 
 
 def akaze_detect_and_compute(gray, thres=0.001, omax=4, nsub=4, cap=20000, want_levels=False):
@@ -320,6 +346,8 @@ def akaze_detect_and_compute(gray, thres=0.001, omax=4, nsub=4, cap=20000, want_
     n = lib().orc_akaze_detect_and_compute(_p(gray, C.c_uint8), C.c_int(w), C.c_int(h), C.c_int(omax), C.c_int(nsub),
                                            C.c_float(thres), _p(kp, C.c_float), _p(desc, C.c_uint8), C.c_int(cap),
                                            _p(ldet, C.c_float), _p(lt, C.c_float))
+    if n == -2 ** 31:
+        raise ValueError(_akaze_refusal(w, h, omax, nsub))
     if n < 0:
         raise OverflowError(f"{-n} keypoints > cap {cap}")
     if want_levels:
@@ -334,8 +362,10 @@ def akaze_compute(gray, kin, omax=4, nsub=4):
     kin = np.ascontiguousarray(kin, np.float32).reshape(-1, 4)
     desc = np.zeros((kin.shape[0], 61), np.uint8)
     ang = np.zeros(kin.shape[0], np.float32)
-    lib().orc_akaze_compute(_p(gray, C.c_uint8), C.c_int(w), C.c_int(h), C.c_int(omax), C.c_int(nsub),
-                            _p(kin, C.c_float), C.c_int(kin.shape[0]), _p(desc, C.c_uint8), _p(ang, C.c_float))
+    lib().orc_akaze_compute.restype = C.c_int
+    if lib().orc_akaze_compute(_p(gray, C.c_uint8), C.c_int(w), C.c_int(h), C.c_int(omax), C.c_int(nsub),
+                               _p(kin, C.c_float), C.c_int(kin.shape[0]), _p(desc, C.c_uint8), _p(ang, C.c_float)) < 0:
+        raise ValueError(_akaze_refusal(w, h, omax, nsub))
     return desc, ang
 
 

@@ -11,18 +11,20 @@
  * atan / sin / cos, NaN-free angle for a zero gradient) are marked "BUILD-DEFINED"; the HIP kernels follow the same
  * operation order so that keypoints and descriptor bits can be compared exactly.
  */
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
 #define AKZ_MAX_LEVELS 32
+#define AKZ_MAX_FED_STEPS 64 /* the longest FED cycle of a level the plan holds (tsteps) */
 #define AKZ_PI_F 3.14159265358979323846f
 
 typedef struct {
   int w, h, octave, sublevel, sigma_size, nsteps;
   float esigma, etime;
-  float tsteps[64];
+  float tsteps[AKZ_MAX_FED_STEPS];
 } akz_level;
 
 typedef struct {
@@ -44,16 +46,24 @@ static int is_prime(int n) {
   return 1;
 }
 
+/* -> the cycle's length n, tau[0 .. n) filled; a cycle longer than AKZ_MAX_FED_STEPS is reported by its length alone */
 static int fed_tau(float T, float tau_max, float *tau) {
   const int n = (int)(ceilf(sqrtf(3.0f * T / tau_max + 0.25f) - 0.5f - 1.0e-8f) + 0.5f);
   if (n <= 0) return 0;
+  if (n > AKZ_MAX_FED_STEPS) return n;
   const float scale = 3.0f * T / (tau_max * (float)(n * (n + 1)));
-  float tauh[64];
+  float tauh[AKZ_MAX_FED_STEPS];
   const float c = 1.0f / (4.0f * (float)n + 2.0f);
   const float d = scale * tau_max / 2.0f;
   for (int k = 0; k < n; ++k) {
     const float hh = cosf(AKZ_PI_F * (2.0f * (float)k + 1.0f) * c);
     tauh[k] = d / (hh * hh);
+  }
+  /* BUILD-DEFINED: a cycle of one step has nothing to reorder, and kappa = 0 would make the index below -1 for every k
+   * (a read before tauh; OpenCV's own code does that).  Sub-level counts of about 11 and more have such levels. */
+  if (n == 1) {
+    tau[0] = tauh[0];
+    return 1;
   }
   const int kappa = n / 2;
   int prime = n + 1;
@@ -79,14 +89,16 @@ static void gaussian_kernel(int ksize, float sigma, float *cf) {
   for (int i = 0; i < ksize; ++i) cf[i] = (float)(cf[i] * sum);
 }
 
-void orc_akaze_plan(int w, int h, int omax, int nsublevels, akz_plan *P) {
+/* -> 0; or the (1-based) number i + 1 of the first level i whose FED cycle is longer than AKZ_MAX_FED_STEPS (its length
+ * is in lev[i].nsteps): such a plan is refused by every entry point below, as sfmloc_akaze_create refuses it. */
+int orc_akaze_plan(int w, int h, int omax, int nsublevels, akz_plan *P) {
   const float soffset = 1.6f, derivative_factor = 1.5f;
   P->nlev = 0;
   for (int i = 0; i < omax; ++i) {
     const float rfactor = 1.0f / powf(2.0f, (float)i);
     const int lh = (int)(h * rfactor), lw = (int)(w * rfactor);
     if ((lw < 80 || lh < 40) && i != 0) break;
-    for (int j = 0; j < nsublevels; ++j) {
+    for (int j = 0; j < nsublevels && P->nlev < AKZ_MAX_LEVELS; ++j) {
       akz_level *L = &P->lev[P->nlev++];
       memset(L, 0, sizeof(*L));
       L->w = lw;
@@ -101,12 +113,14 @@ void orc_akaze_plan(int w, int h, int omax, int nsublevels, akz_plan *P) {
   for (int i = 1; i < P->nlev; ++i) {
     const float ttime = P->lev[i].etime - P->lev[i - 1].etime;
     P->lev[i].nsteps = fed_tau(ttime, 0.25f, P->lev[i].tsteps);
+    if (P->lev[i].nsteps > AKZ_MAX_FED_STEPS) return i + 1;
   }
   gaussian_kernel(9, 1.6f, P->g16);
   gaussian_kernel(5, 1.0f, P->g10);
   for (int i = 0; i < 7; ++i)
     for (int j = 0; j < 7; ++j)
       P->gauss25[i][j] = (float)(exp(-(double)(i * i + j * j) / 12.5) / (2.0 * 3.14159265358979323846 * 6.25));
+  return 0;
 }
 
 /* ---- BUILD-DEFINED fixed-order float math -------------------------------------------------------------------- */
@@ -276,7 +290,9 @@ static float k_percentile(const float *img, int w, int h, const akz_plan *P, flo
   const int nthreshold = (int)((float)npoints * 0.7f);
   int nelements = 0, k = 0;
   for (k = 0; nelements < nthreshold && k < 300; k++) nelements += hist[k];
-  if (nelements < nthreshold) return 0.03f;
+  /* BUILD-DEFINED: no gradient anywhere (a constant frame) -- OpenCV's expression gives 0 here, a conductivity of
+   * 1 / (1 + 0 * inf) and NaN in every level above the first; the fallback it has for a thin histogram serves */
+  if (nelements < nthreshold || npoints == 0) return 0.03f;
   return hmax * ((float)k / 300.0f);
 }
 
@@ -593,13 +609,13 @@ static void mldb_descriptor(const akz_plan *P, const akz_bufs *B, const akz_kpt 
 
 /*
  * detectAndCompute.  kpts_out [cap x 6] = x, y, size, angle (radians), response, class_id ; desc_out [cap x 61].
- * Returns the number of keypoints (<= cap), or -needed when cap is too small.
+ * Returns the number of keypoints (<= cap), -needed when cap is too small, or INT_MIN for a plan that is refused.
  * levels_out (optional, may be NULL): concatenated Ldet of every level, for stage-wise comparisons.
  */
 int orc_akaze_detect_and_compute(const uint8_t *gray, int w, int h, int omax, int nsublevels, float dthreshold,
                                  float *kpts_out, uint8_t *desc_out, int cap, float *ldet_out, float *lt_out) {
   akz_plan P;
-  orc_akaze_plan(w, h, omax, nsublevels, &P);
+  if (orc_akaze_plan(w, h, omax, nsublevels, &P)) return INT_MIN;
   akz_bufs B[AKZ_MAX_LEVELS];
   build_scale_space(gray, w, h, &P, B);
   if (ldet_out || lt_out) {
@@ -635,11 +651,11 @@ int orc_akaze_detect_and_compute(const uint8_t *gray, int w, int h, int omax, in
   return m <= cap ? m : -m;
 }
 
-/* compute() on given keypoints (dense BoW features): kin [n x 4] = x, y, size, class_id (octave 0) */
+/* compute() on given keypoints (dense BoW features): kin [n x 4] = x, y, size, class_id (octave 0); -1: plan refused */
 int orc_akaze_compute(const uint8_t *gray, int w, int h, int omax, int nsublevels, const float *kin, int n,
                       uint8_t *desc_out, float *angle_out) {
   akz_plan P;
-  orc_akaze_plan(w, h, omax, nsublevels, &P);
+  if (orc_akaze_plan(w, h, omax, nsublevels, &P)) return -1;
   akz_bufs B[AKZ_MAX_LEVELS];
   build_scale_space(gray, w, h, &P, B);
   for (int i = 0; i < n; ++i) {
@@ -659,12 +675,32 @@ int orc_akaze_compute(const uint8_t *gray, int w, int h, int omax, int nsublevel
   return n;
 }
 
+/* -> the number of levels, or -1 for a plan that is refused */
 int orc_akaze_levels(int w, int h, int omax, int nsublevels, int *wh_out /*[32*2]*/) {
   akz_plan P;
-  orc_akaze_plan(w, h, omax, nsublevels, &P);
+  if (orc_akaze_plan(w, h, omax, nsublevels, &P)) return -1;
   for (int i = 0; i < P.nlev; ++i) {
     wh_out[2 * i] = P.lev[i].w;
     wh_out[2 * i + 1] = P.lev[i].h;
+  }
+  return P.nlev;
+}
+
+/* The plan itself, for tests of the library's host-side plan: lev_out [32 x 6] = w, h, octave, sublevel, sigma_size,
+ * nsteps ; tsteps_out [32 x 64] ; bad_out [2] = level and step count of a refused plan.  -> levels, or -1 refused. */
+int orc_akaze_plan_read(int w, int h, int omax, int nsublevels, int *lev_out, float *tsteps_out, int *bad_out) {
+  akz_plan P;
+  const int bad = orc_akaze_plan(w, h, omax, nsublevels, &P);
+  if (bad) {
+    bad_out[0] = bad - 1;
+    bad_out[1] = P.lev[bad - 1].nsteps;
+    return -1;
+  }
+  for (int i = 0; i < P.nlev; ++i) {
+    const akz_level *L = &P.lev[i];
+    const int v[6] = {L->w, L->h, L->octave, L->sublevel, L->sigma_size, L->nsteps};
+    memcpy(lev_out + 6 * i, v, sizeof(v));
+    memcpy(tsteps_out + AKZ_MAX_FED_STEPS * i, L->tsteps, sizeof(L->tsteps));
   }
   return P.nlev;
 }

@@ -75,7 +75,7 @@ def contrast_factor(img):
     hist = np.bincount(nbin, minlength=300)
     nth = int(len(m) * 0.7)
     c = np.cumsum(hist)
-    if c[-1] < nth:
+    if c[-1] < nth or len(m) == 0:   # (no gradient anywhere: the thin histogram's fallback, as the C restatement)
         return 0.03
     k = int(np.searchsorted(c, nth, side="left")) + 1 if nth > 0 else 0
     return hmax * k / 300.0

@@ -22,123 +22,13 @@
 
 #include "sfmloc_internal.h"
 #include "geom_device.h"
+#include "akaze_plan.h"
 
 namespace sfmloc {
 namespace {
 
-constexpr int kMaxLevels = 32;
-constexpr float kPiF = 3.14159265358979323846f;
-
-struct AkLevel {
-  int w, h, octave, sublevel, sigma_size, nsteps;
-  float esigma, etime;
-  float tsteps[64];
-  size_t off;  // offset (floats) of this level inside each per-level image stack
-};
-
-struct AkPlan {
-  int nlev = 0;
-  AkLevel lev[kMaxLevels];
-  float g16[9], g10[5];
-  float gauss25[49];
-  float win_ang1[64];
-  int n_win = 0;
-  uint16_t pair_tab[486 * 2];
-  size_t total = 0;
-};
-
-int fround_h(float f) { return (int)(f + 0.5f); }
-
-bool is_prime(int n) {
-  if (n <= 3) return n > 1;
-  if (n % 2 == 0 || n % 3 == 0) return false;
-  for (int i = 5; i * i <= n; i += 6)
-    if (n % i == 0 || n % (i + 2) == 0) return false;
-  return true;
-}
-
-// fed_tau_by_process_time(T, 1, 0.25, reordering = true) of OpenCV's fed.cpp
-int fed_tau(float T, float tau_max, float *tau) {
-  const int n = (int)(ceilf(sqrtf(3.0f * T / tau_max + 0.25f) - 0.5f - 1.0e-8f) + 0.5f);
-  if (n <= 0) return 0;
-  const float scale = 3.0f * T / (tau_max * (float)(n * (n + 1)));
-  float tauh[64];
-  const float c = 1.0f / (4.0f * (float)n + 2.0f);
-  const float d = scale * tau_max / 2.0f;
-  for (int k = 0; k < n; ++k) {
-    const float hh = cosf(kPiF * (2.0f * (float)k + 1.0f) * c);
-    tauh[k] = d / (hh * hh);
-  }
-  const int kappa = n / 2;
-  int prime = n + 1;
-  while (!is_prime(prime)) prime++;
-  for (int k = 0, l = 0; l < n; ++k, ++l) {
-    int index;
-    while ((index = ((k + 1) * kappa) % prime - 1) >= n) k++;
-    tau[l] = tauh[index];
-  }
-  return n;
-}
-
-void gaussian_kernel(int ksize, float sigma, float *cf) {  // cv::getGaussianKernel(ksize, sigma, CV_32F)
-  const double scale2x = -0.5 / ((double)sigma * sigma);
-  double sum = 0;
-  for (int i = 0; i < ksize; ++i) {
-    const double x = i - (ksize - 1) * 0.5;
-    cf[i] = (float)exp(scale2x * x * x);
-    sum += cf[i];
-  }
-  sum = 1.0 / sum;
-  for (int i = 0; i < ksize; ++i) cf[i] = (float)(cf[i] * sum);
-}
-
-// Allocate_Memory_Evolution + FED schedule + constant tables
-void make_plan(int w, int h, int omax, int nsub, AkPlan &P) {
-  const float soffset = 1.6f, derivative_factor = 1.5f;
-  P.nlev = 0;
-  P.total = 0;
-  for (int i = 0; i < omax; ++i) {
-    const float rfactor = 1.0f / powf(2.0f, (float)i);
-    const int lh = (int)(h * rfactor), lw = (int)(w * rfactor);
-    if ((lw < 80 || lh < 40) && i != 0) break;
-    for (int j = 0; j < nsub && P.nlev < kMaxLevels; ++j) {
-      AkLevel &L = P.lev[P.nlev++];
-      memset(&L, 0, sizeof(L));
-      L.w = lw;
-      L.h = lh;
-      L.esigma = soffset * powf(2.0f, (float)j / (float)nsub + (float)i);
-      L.sigma_size = fround_h(L.esigma * derivative_factor / powf(2.0f, (float)i));
-      L.etime = 0.5f * (L.esigma * L.esigma);
-      L.octave = i;
-      L.sublevel = j;
-      L.off = P.total;
-      P.total += (size_t)lw * lh;
-    }
-  }
-  for (int i = 1; i < P.nlev; ++i)
-    P.lev[i].nsteps = fed_tau(P.lev[i].etime - P.lev[i - 1].etime, 0.25f, P.lev[i].tsteps);
-  gaussian_kernel(9, 1.6f, P.g16);
-  gaussian_kernel(5, 1.0f, P.g10);
-  for (int i = 0; i < 7; ++i)
-    for (int j = 0; j < 7; ++j)
-      P.gauss25[7 * i + j] = (float)(exp(-(double)(i * i + j * j) / 12.5) / (2.0 * 3.14159265358979323846 * 6.25));
-  P.n_win = 0;
-  for (float a = 0.0f; a < 2.0f * kPiF; a += 0.15f) P.win_ang1[P.n_win++] = a;
-  // M-LDB comparison pairs: bit dpos compares values[a] > values[b]; values are laid out [cell][channel] with the
-  // cells of the three grids back to back (4 + 9 + 16)
-  int dpos = 0, cell0 = 0;
-  const int counts[3] = {4, 9, 16};
-  for (int lvl = 0; lvl < 3; ++lvl) {
-    for (int pos = 0; pos < 3; ++pos)
-      for (int a = 0; a < counts[lvl]; ++a)
-        for (int b = a + 1; b < counts[lvl]; ++b) {
-          P.pair_tab[2 * dpos] = (uint16_t)((cell0 + a) * 3 + pos);
-          P.pair_tab[2 * dpos + 1] = (uint16_t)((cell0 + b) * 3 + pos);
-          ++dpos;
-        }
-    cell0 += counts[lvl];
-  }
-}
+// the plan of one image size (levels, FED schedule, constant tables): host code of its own, akaze_plan.h
+using namespace akaze_plan;
 
 // ---- fixed-order float math shared with the restatement -------------------------------------------------------
 __device__ __forceinline__ int fround_d(float f) { return (int)(f + 0.5f); }
@@ -464,7 +354,9 @@ struct PreHistBody {
     const int nthreshold = (int)((float)npoints * 0.7f);
     int nelements = 0, k = 0;
     for (k = 0; nelements < nthreshold && k < 300; k++) nelements += (int)lh[k];
-    *kcontrast = (nelements < nthreshold) ? 0.03f : hmax * ((float)k / 300.0f);
+    // (no gradient anywhere -- a constant frame --: OpenCV's expression gives 0 here, a conductivity of 1 / (1 + 0 * inf) and
+    // every level above the first NaN; the fallback it has for a thin histogram serves: the levels stay the constant)
+    *kcontrast = (nelements < nthreshold || npoints == 0) ? 0.03f : hmax * ((float)k / 300.0f);
   }
 };
 __global__ __launch_bounds__(128) void k_pre_hist(const float *__restrict__ mag, int w, int h,
@@ -479,7 +371,7 @@ __global__ void k_kcontrast(const unsigned int *hmax_bits, const unsigned int *h
   const int nthreshold = (int)((float)npoints * 0.7f);
   int nelements = 0, k = 0;
   for (k = 0; nelements < nthreshold && k < 300; k++) nelements += (int)hist[k];
-  *kcontrast = (nelements < nthreshold) ? 0.03f : hmax * ((float)k / 300.0f);
+  *kcontrast = (nelements < nthreshold || npoints == 0) ? 0.03f : hmax * ((float)k / 300.0f);  // (as k_pre_hist)
 }
 
 // nld_step_scalar: Ld_out = Ld + half_step * flux, zero flux across the image border -- up to K steps in one launch
@@ -2151,7 +2043,7 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   DevBuf<float> d_Lt, d_Lsmooth, d_Lx, d_Ly, d_Ldet;  // per-level stacks
   DevBuf<unsigned int> d_hist;                // [0] hmax bits, [1..301] histogram + npoints
   DevBuf<float> d_kcontrast;
-  DevBuf<float> d_half_steps;                 // [level][64]: 0.5 * tsteps, for k_octave_resident
+  DevBuf<float> d_half_steps;                 // [level][kMaxFedSteps]: 0.5 * tsteps, for k_octave_resident
   DevBuf<LevelTab> d_level_tab;               // the LevelTab of this image size (the all-level kernels read it by pointer)
   DevBuf<DevLevels> d_dev_levels;             // the DevLevels of this extractor (k_orient_describe reads it by pointer)
   // detection tail (k_extrema_seg .. k_suppress): the raster-ordered candidate list and the suppression's state
@@ -2318,7 +2210,7 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
         for (int q = i; q <= j; ++q) {
           R.off[q - i] = (unsigned int)P.lev[q].off;
           R.nsteps[q - i] = P.lev[q].nsteps;
-          R.step0[q - i] = q * 64;
+          R.step0[q - i] = q * kMaxFedSteps;
         }
         Taps t5;
         for (int k = 0; k < 9; ++k) t5.k[k] = k < 5 ? P.g10[k] : 0.0f;
@@ -2546,6 +2438,12 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
             "sfmloc_akaze_create: image size %dx%d (at most 16384 x %d)", width, height, kSupMaxRows - 1);
   SFM_CHECK(n_octaves >= 1 && n_octaves <= 8 && n_sublevels >= 1 && n_octaves * n_sublevels <= kMaxLevels,
             SFMLOC_EINVAL, "sfmloc_akaze_create: nOct %d nOctLay %d", n_octaves, n_sublevels);
+  // (the plan is host arithmetic: a schedule the tables cannot hold is refused before anything touches a device)
+  AkPlan plan;
+  int bad_level = 0, bad_steps = 0;
+  SFM_CHECK(make_plan(width, height, n_octaves, n_sublevels, plan, &bad_level, &bad_steps), SFMLOC_EINVAL,
+            "sfmloc_akaze_create: %dx%d with nOct %d nOctLay %d needs %d diffusion steps at level %d (at most %d per level)",
+            width, height, n_octaves, n_sublevels, bad_steps, bad_level, kMaxFedSteps);
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
@@ -2558,7 +2456,7 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   a->omax = n_octaves;
   a->nsub = n_sublevels;
   a->thres = threshold;
-  make_plan(width, height, n_octaves, n_sublevels, a->plan);
+  a->plan = plan;
   const size_t n0 = (size_t)width * height, tot = a->plan.total;
   // (no stream yet: akaze_ensure_stream creates one at the first call that needs it -- an extractor that is given a
   // context's stream right away, or only ever works in sessions led by another, never needs one, and a stream that merely
@@ -2582,7 +2480,7 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   AK_NEW(d_Ldet, tot);
   AK_NEW(d_hist, 304);
   AK_NEW(d_kcontrast, 1);
-  AK_NEW(d_half_steps, (size_t)kMaxLevels * 64);
+  AK_NEW(d_half_steps, (size_t)kMaxLevels * kMaxFedSteps);
   AK_NEW(d_level_tab, 1);
   AK_NEW(d_dev_levels, 1);
   {
@@ -2624,9 +2522,9 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
     he = attr;
   }
   if (!rc && he == hipSuccess) {
-    std::vector<float> hs((size_t)kMaxLevels * 64, 0.0f);
-    for (int i = 0; i < a->plan.nlev; ++i)
-      for (int k = 0; k < a->plan.lev[i].nsteps && k < 64; ++k) hs[(size_t)i * 64 + k] = 0.5f * a->plan.lev[i].tsteps[k];
+    std::vector<float> hs((size_t)kMaxLevels * kMaxFedSteps, 0.0f);
+    for (int i = 0; i < a->plan.nlev; ++i)  // (nsteps <= kMaxFedSteps: make_plan)
+      for (int k = 0; k < a->plan.lev[i].nsteps; ++k) hs[(size_t)i * kMaxFedSteps + k] = 0.5f * a->plan.lev[i].tsteps[k];
     he = hipMemcpy(a->d_half_steps, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
   }
   if (!rc && he == hipSuccess) {
