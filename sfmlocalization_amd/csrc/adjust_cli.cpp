@@ -34,6 +34,7 @@
 #include "sfm_json.h"
 
 using sfmdoc::Doc;
+using sfmdoc::set_key;
 using sfmjson::Value;
 
 namespace {
@@ -53,12 +54,6 @@ void usage() {
           "one joint bundle adjustment\n");
 }
 
-void set_key(Value *obj, const char *k, Value v) {
-  Value *slot = obj->get(k);
-  if (slot) *slot = std::move(v);
-  else obj->o.emplace_back(k, std::move(v));
-}
-
 // extrinsics: the valid poses in ascending id; an input pose untouched keeps its JSON value as it was
 Value extrinsics(const Doc &d, const std::vector<uint8_t> &valid, const std::vector<double> &R,
                  const std::vector<double> &C, const std::vector<uint8_t> &replaced) {
@@ -67,10 +62,7 @@ Value extrinsics(const Doc &d, const std::vector<uint8_t> &valid, const std::vec
     if (!valid[p]) continue;
     Value e;
     e.kind = Value::Obj;
-    Value key;
-    key.kind = Value::Int;
-    key.s = std::to_string(d.pose_id[p]);
-    e.o.emplace_back("key", key);
+    e.o.emplace_back("key", sfmdoc::make_int(d.pose_id[p]));
     if (!replaced[p] && d.pose_src[p]) {
       e.o.emplace_back("value", *d.pose_src[p]);
     } else {
@@ -199,7 +191,7 @@ int main(int argc, char **argv) {
   fflush(stdout);
   Doc d;
   std::string err;
-  if (!sfmdoc::load(in, &d, &err)) {
+  if (!sfmdoc::load(in, false, &d, &err)) {
     fprintf(stderr, "\nThe input sfm_data.json file \"%s\" cannot be read. (%s)\n", in.c_str(), err.c_str());
     return EXIT_FAILURE;
   }

@@ -21,9 +21,11 @@
 
 #include "../../include/sfmloc.h"
 #include "sfm_doc.h"
+#include "sfm_files.h"
 #include "sfm_json.h"
 
 using sfmdoc::Doc;
+using sfmfiles::join;
 using sfmjson::Value;
 
 namespace {
@@ -36,12 +38,6 @@ void usage() {
           "[-i|--input_file] path to the input SfM_Data scene\n"
           "[-o|--output_file] path to the output PLY file\n",
           kName);
-}
-
-// os.path.join(root, name)
-std::string join(const std::string &root, const std::string &name) {
-  if (root.empty() || (!name.empty() && name[0] == '/')) return name;
-  return root + (root.back() == '/' ? "" : "/") + name;
 }
 
 // (int)c clamped to [0, n - 1]; the cast truncates toward zero, a NaN gives 0
@@ -91,7 +87,7 @@ int main(int argc, char **argv) {
   }
   Doc d;
   std::string err;
-  if (!sfmdoc::load(in, &d, &err)) {
+  if (!sfmdoc::load(in, false, &d, &err)) {
     fprintf(stderr, "\nThe input SfM_Data file \"%s\" cannot be read. (%s)\n", in.c_str(), err.c_str());
     return 1;
   }

@@ -26,63 +26,13 @@
 #include <vector>
 
 #include "../../include/sfmloc.h"
+#include "sfm_files.h"
+
+// the command line, paths, .desc, .feat and the match files; a view's stem is basename_part, as the library's loader's
+using namespace sfmfiles;
 
 namespace {
 
-bool is_number(const std::string &s) {
-  char *end = nullptr;
-  std::strtod(s.c_str(), &end);
-  return !s.empty() && end && *end == '\0';
-}
-
-// cv::CommandLineParser syntax: positionals, -k=v / --key=v, bare flags
-struct Args {
-  std::vector<std::string> pos;
-  std::map<std::string, std::string> opt;
-  std::string get(std::initializer_list<const char *> names, const char *def) const {
-    std::string v = def;
-    for (const char *n : names) {
-      auto it = opt.find(n);
-      if (it != opt.end()) v = it->second;
-    }
-    return v;
-  }
-  bool flag(std::initializer_list<const char *> names) const {
-    std::string v = get(names, "false");
-    for (char &c : v) c = (char)tolower(c);
-    return v == "1" || v == "true" || v == "yes";
-  }
-};
-
-Args parse_args(int argc, char **argv) {
-  Args a;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    if (s.size() > 1 && s[0] == '-' && !is_number(s)) {
-      size_t p = s.find_first_not_of('-');
-      std::string kv = s.substr(p == std::string::npos ? s.size() : p);
-      size_t eq = kv.find('=');
-      if (eq == std::string::npos)
-        a.opt[kv] = "true";
-      else
-        a.opt[kv.substr(0, eq)] = kv.substr(eq + 1);
-    } else {
-      a.pos.push_back(s);
-    }
-  }
-  return a;
-}
-
-std::string join(const std::string &a, const std::string &b) {
-  if (a.empty()) return b;
-  return a.back() == '/' ? a + b : a + "/" + b;
-}
-std::string stem_of(const std::string &p) {
-  size_t s = p.find_last_of('/');
-  std::string b = s == std::string::npos ? p : p.substr(s + 1);
-  size_t d = b.find_last_of('.');
-  return d == std::string::npos ? b : b.substr(0, d);
-}
 bool exists(const std::string &p) {
   struct stat st;
   return stat(p.c_str(), &st) == 0;
@@ -121,65 +71,6 @@ bool write_features(const View &v, const float *kp, const uint8_t *desc, uint32_
   return ok && ff.good();
 }
 
-bool read_desc(const std::string &p, std::vector<uint8_t> *rows) {
-  FILE *f = fopen(p.c_str(), "rb");
-  if (!f) return false;
-  uint64_t n = 0;
-  bool ok = fread(&n, 8, 1, f) == 1 && n < (1ull << 32);
-  if (ok) {
-    const size_t at = rows->size();
-    rows->resize(at + (size_t)n * 64);
-    ok = n == 0 || fread(rows->data() + at, 64, (size_t)n, f) == (size_t)n;
-  }
-  fclose(f);
-  return ok;
-}
-
-bool read_feat(const std::string &p, std::vector<float> *xy, size_t *n_rows) {
-  FILE *f = fopen(p.c_str(), "r");
-  if (!f) return false;
-  double x, y, s, a;
-  *n_rows = 0;
-  while (fscanf(f, "%lf %lf %lf %lf", &x, &y, &s, &a) == 4) {
-    xy->push_back((float)x);
-    xy->push_back((float)y);
-    ++*n_rows;
-  }
-  fclose(f);
-  return true;
-}
-
-typedef std::map<std::pair<uint32_t, uint32_t>, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> PairMatches;
-
-// PairWiseMatches text: "I J\nN\n" then N lines "i j" (matching/indMatch_utils.hpp PairedIndMatchToStream)
-bool write_matches(const std::string &path, const PairMatches &m) {
-  FILE *f = fopen(path.c_str(), "w");
-  if (!f) return false;
-  for (const auto &kv : m) {
-    fprintf(f, "%u %u\n%zu\n", kv.first.first, kv.first.second, kv.second.first.size());
-    for (size_t k = 0; k < kv.second.first.size(); ++k) fprintf(f, "%u %u\n", kv.second.first[k], kv.second.second[k]);
-  }
-  return fclose(f) == 0;
-}
-
-bool read_matches(const std::string &path, PairMatches *m) {
-  FILE *f = fopen(path.c_str(), "r");
-  if (!f) return false;
-  unsigned a, b;
-  unsigned long n;
-  while (fscanf(f, "%u %u %lu", &a, &b, &n) == 3) {
-    auto &e = (*m)[std::make_pair(a, b)];
-    for (unsigned long k = 0; k < n; ++k) {
-      unsigned i, j;
-      if (fscanf(f, "%u %u", &i, &j) != 2) break;
-      e.first.push_back(i);
-      e.second.push_back(j);
-    }
-  }
-  fclose(f);
-  return true;
-}
-
 // sfmloc_matches (view INDICES) -> PairMatches keyed by view ids
 bool take_matches(sfmloc_matches *h, const std::vector<View> &views, PairMatches *out) {
   const uint32_t np = sfmloc_matches_pairs(h);
@@ -197,17 +88,17 @@ bool take_matches(sfmloc_matches *h, const std::vector<View> &views, PairMatches
   return ok;
 }
 
-typedef std::vector<std::pair<uint32_t, uint32_t>> PairList;
+typedef std::vector<std::pair<uint32_t, uint32_t>> ViewPairs;
 
-PairList generate_all_pairs(const std::vector<uint32_t> &ids) {  // SfMDataUtils.cpp:128-141
-  PairList p;
+ViewPairs generate_all_pairs(const std::vector<uint32_t> &ids) {  // SfMDataUtils.cpp:128-141
+  ViewPairs p;
   for (size_t i = 0; i < ids.size(); ++i)
     for (size_t j = i + 1; j < ids.size(); ++j) p.emplace_back(ids[i], ids[j]);
   return p;
 }
 
-PairList generate_video_match_pairs(const std::vector<uint32_t> &ids, int frame) {  // SfMDataUtils.cpp:144-157
-  PairList p;
+ViewPairs generate_video_match_pairs(const std::vector<uint32_t> &ids, int frame) {  // SfMDataUtils.cpp:144-157
+  ViewPairs p;
   for (size_t i = 0; i < ids.size(); ++i)
     for (size_t j = i + 1; j < std::min(ids.size(), i + (size_t)frame + 1); ++j) p.emplace_back(ids[i], ids[j]);
   return p;
@@ -215,7 +106,7 @@ PairList generate_video_match_pairs(const std::vector<uint32_t> &ids, int frame)
 
 // SfMDataUtils.cpp:168-187, literally: scanning from the back, earlier entries get ordered (first <= second) as a side
 // effect, a later duplicate of an earlier pair is dropped
-void remove_dup_pairs(PairList *pairs) {
+void remove_dup_pairs(ViewPairs *pairs) {
   std::vector<size_t> dup;
   for (size_t i = pairs->size(); i-- > 1;)
     for (size_t j = i; j-- > 0;) {
@@ -230,8 +121,8 @@ void remove_dup_pairs(PairList *pairs) {
   for (size_t i : dup) pairs->erase(pairs->begin() + (long)i);  // descending indices
 }
 
-PairList read_pair_file(const std::string &path) {  // FileUtils.cpp:180-194
-  PairList p;
+ViewPairs read_pair_file(const std::string &path) {  // FileUtils.cpp:180-194
+  ViewPairs p;
   FILE *f = fopen(path.c_str(), "r");
   if (!f) return p;
   char line[512];
@@ -284,8 +175,8 @@ int main(int argc, char **argv) {
     const char *img = nullptr;
     sfmloc_view_list_get(vl, k, &views[k].id, &views[k].w, &views[k].h, &img);
     views[k].image = img;
-    views[k].feat = join(match_dir, stem_of(views[k].image) + ".feat");
-    views[k].desc = join(match_dir, stem_of(views[k].image) + ".desc");
+    views[k].feat = join(match_dir, basename_part(views[k].image) + ".feat");
+    views[k].desc = join(match_dir, basename_part(views[k].image) + ".desc");
     ids[k] = views[k].id;
   }
   sfmloc_view_list_close(vl);
@@ -345,10 +236,9 @@ int main(int argc, char **argv) {
   std::vector<float> kxy;
   std::vector<uint32_t> off(n_views + 1, 0), wh(2 * (size_t)n_views);
   for (uint32_t k = 0; k < n_views; ++k) {
-    size_t n_feat = 0;
-    const size_t before = bank.size();
-    if (!read_desc(views[k].desc, &bank) || !read_feat(views[k].feat, &kxy, &n_feat) ||
-        (bank.size() - before) / 64 != n_feat) {
+    const size_t before = bank.size(), before_xy = kxy.size();
+    if (!read_desc(views[k].desc, &bank) || !read_feat(views[k].feat, &kxy) ||
+        (bank.size() - before) / 64 != (kxy.size() - before_xy) / 2) {
       fprintf(stderr, "cannot read the features of view %u (%s)\n", views[k].id, views[k].desc.c_str());
       return 1;
     }
@@ -389,7 +279,7 @@ int main(int argc, char **argv) {
       rc = sfmloc_track(map, (uint32_t)max_frame_dist, &h);
     } else {
       printf("Generating pairs\n");
-      PairList pairs;
+      ViewPairs pairs;
       if (!pair_file.empty()) {
         pairs = read_pair_file(pair_file);
       } else if (video_frame > 0) {
@@ -419,7 +309,12 @@ int main(int argc, char **argv) {
   printf("Start Geometric Matching...\n");
   if (!exists(f_path)) {
     PairMatches put;
-    read_matches(put_path, &put);
+    std::string err;
+    if (!read_matches(put_path, &put, &err)) {  // (fileio.read_matches_txt raises)
+      fprintf(stderr, "geometric matching failed: %s: %s\n", put_path.c_str(), err.c_str());
+      sfmloc_map_destroy(map);
+      return 1;
+    }
     std::vector<uint32_t> pairs, mi, mj;
     std::vector<uint64_t> offsets(1, 0);
     size_t n_kept = 0;

@@ -24,120 +24,14 @@
 #include <vector>
 
 #include "../../include/sfmloc.h"
+#include "sfm_files.h"
+
+using namespace sfmfiles;  // the command line, paths, .desc and .feat; a file's stem is basename_part, as the reference's
 
 namespace {
 
-// ---------------------------------------------------------------------------------------------------------
-// cv::CommandLineParser syntax: positionals, -k=v / --key=v, bare flags
-// ---------------------------------------------------------------------------------------------------------
-bool is_number(const std::string &s) {
-  char *end = nullptr;
-  std::strtod(s.c_str(), &end);
-  return !s.empty() && end && *end == '\0';
-}
-
-struct Args {
-  std::vector<std::string> pos;
-  std::map<std::string, std::string> opt;
-  std::string get(std::initializer_list<const char *> names, const char *def) const {
-    std::string v = def;
-    for (const char *n : names) {
-      auto it = opt.find(n);
-      if (it != opt.end()) v = it->second;
-    }
-    return v;
-  }
-};
-
-Args parse_args(int argc, char **argv) {
-  Args a;
-  for (int i = 1; i < argc; ++i) {
-    std::string s = argv[i];
-    if (s.size() > 1 && s[0] == '-' && !is_number(s)) {
-      size_t p = s.find_first_not_of('-');
-      std::string kv = s.substr(p == std::string::npos ? s.size() : p);
-      size_t eq = kv.find('=');
-      if (eq == std::string::npos)
-        a.opt[kv] = "true";
-      else
-        a.opt[kv.substr(0, eq)] = kv.substr(eq + 1);
-    } else {
-      a.pos.push_back(s);
-    }
-  }
-  return a;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// paths and files
-// ---------------------------------------------------------------------------------------------------------
-std::string join(const std::string &a, const std::string &b) {
-  if (a.empty()) return b;
-  return a.back() == '/' ? a + b : a + "/" + b;
-}
-std::string basename_of(const std::string &p) {
-  size_t s = p.find_last_of('/');
-  return s == std::string::npos ? p : p.substr(s + 1);
-}
-std::string dirname_of(const std::string &p) {
-  size_t s = p.find_last_of('/');
-  return s == std::string::npos ? std::string("") : p.substr(0, s);
-}
-std::string stem_of(const std::string &p) {
-  std::string b = basename_of(p);
-  size_t d = b.find_last_of('.');
-  return d == std::string::npos ? b : b.substr(0, d);
-}
-std::string ext_of(const std::string &p) {
-  std::string b = basename_of(p);
-  size_t d = b.find_last_of('.');
-  return d == std::string::npos ? std::string("") : b.substr(d + 1);
-}
-bool is_file(const std::string &p) {
-  struct stat st;
-  return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
-bool is_dir(const std::string &p) {
-  struct stat st;
-  return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
 bool image_ext(const std::string &e) {  // localization.cpp:204-206
   return e == "jpg" || e == "JPG" || e == "jpeg" || e == "JPEG" || e == "png" || e == "PNG";
-}
-bool read_all(const std::string &p, std::vector<uint8_t> *out) {
-  FILE *f = fopen(p.c_str(), "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  out->resize(n > 0 ? (size_t)n : 0);
-  const bool ok = n >= 0 && fread(out->data(), 1, out->size(), f) == out->size();
-  fclose(f);
-  return ok;
-}
-
-// .desc: [u64 N][N x 64 B]  (FileUtils.cpp:77-103)
-bool read_desc(const std::string &p, std::vector<uint8_t> *rows) {
-  std::vector<uint8_t> raw;
-  if (!read_all(p, &raw) || raw.size() < 8) return false;
-  uint64_t n;
-  memcpy(&n, raw.data(), 8);
-  if (raw.size() != 8 + n * 64) return false;
-  rows->assign(raw.begin() + 8, raw.end());
-  return true;
-}
-// .feat: "x y size angle" per line (AKAZEOpenCV.cpp:80-81)
-bool read_feat(const std::string &p, std::vector<float> *xy) {
-  FILE *f = fopen(p.c_str(), "r");
-  if (!f) return false;
-  xy->clear();
-  double x, y, s, a;
-  while (fscanf(f, "%lf %lf %lf %lf", &x, &y, &s, &a) == 4) {
-    xy->push_back((float)x);
-    xy->push_back((float)y);
-  }
-  fclose(f);
-  return true;
 }
 // .bow: [i32 rows][i32 cols][i32 type][data], CV_64F or CV_32F (FileUtils.cpp:43-75)
 bool read_bow(const std::string &p, std::vector<float> *v) {
@@ -342,7 +236,7 @@ std::string eigen_format(const double *m, int rows, int cols, const char *row_pr
 // saveResultJson (localization.cpp:84-153)
 bool write_result_json(const std::string &out_dir, const std::string &query, const std::string &sfm_json,
                        const std::string &match_dir, const sfmloc_pose *pose, const uint32_t *pq, const uint32_t *pl) {
-  const std::string path = join(out_dir, stem_of(query) + ".json");
+  const std::string path = join(out_dir, basename_part(query) + ".json");
   FILE *f = fopen(path.c_str(), "w");
   if (!f) return false;
   fprintf(f, "{\n\t\"filename\": \"%s\",\n\t\"sfm_data\": \"%s\",\n", query.c_str(), sfm_json.c_str());
@@ -386,17 +280,11 @@ int main(int argc, char **argv) {
   const std::string pca_model = a.get({"p", "pcaModelFile"}, "");
   int every = atoi(a.get({"i", "locEvryNFrame"}, "1").c_str());
   const double geom = atof(a.get({"g", "geomLimit"}, "4.0").c_str());
-  std::string wm = a.get({"w", "writematch"}, "false");
-  for (char &ch : wm) ch = (char)tolower(ch);
-  const bool write_match = wm == "1" || wm == "true" || wm == "yes";
-  std::string gm = a.get({"gm", "guidedMatch"}, "false");   // localization.cpp:82,183
-  for (char &ch : gm) ch = (char)tolower(ch);
-  const bool guided = gm == "1" || gm == "true" || gm == "yes";
+  const bool write_match = a.flag({"w", "writematch"});
+  const bool guided = a.flag({"gm", "guidedMatch"});  // localization.cpp:82,183
   // -u: the query images come from a camera nobody calibrated -- six-point resection, the result's K is the recovered
   // one (sfmloc.h "Uncalibrated queries"); not in the reference's tool, whose Localize call always passes the intrinsic
-  std::string un = a.get({"u", "uncalibrated"}, "false");
-  for (char &ch : un) ch = (char)tolower(ch);
-  const bool uncalibrated = un == "1" || un == "true" || un == "yes";
+  const bool uncalibrated = a.flag({"u", "uncalibrated"});
   const std::string featdir_opt = a.get({"featdir"}, "");
   const int device = atoi(a.get({"device"}, "0").c_str());
   if (every <= 0) every = 1;
@@ -473,7 +361,7 @@ int main(int argc, char **argv) {
     } else {
       --match_next;
     }
-    const std::string base = stem_of(img);
+    const std::string base = basename_part(img);
     const std::string fdir = featdir_opt.empty() ? dirname_of(img) : featdir_opt;
     int w = info.n_views ? (int)view_wh[0] : 0, h = info.n_views ? (int)view_wh[1] : 0;
     std::vector<uint8_t> desc;

@@ -1,6 +1,7 @@
-// The sfm_data.json document as the map-side tools read it (host code only; shared by adjust_cli.cpp and
-// colorize_cli.cpp): the parsed JSON and the arrays of sfmloc_sfm_desc built from it -- views ascending, a pose table
-// (every extrinsic key and every view's id_pose, ascending), landmarks ascending with their observations in CSR.
+// The sfm_data.json document as the map-side tools read it (host code only; shared by adjust_cli.cpp, colorize_cli.cpp,
+// structure_cli.cpp and relpose_cli.cpp): the parsed JSON and the arrays of sfmloc_sfm_desc built from it -- views
+// ascending, a pose table (every extrinsic key and every view's id_pose, ascending), landmarks ascending with their
+// observations in CSR.
 #pragma once
 
 #include <cstdint>
@@ -8,6 +9,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/sfmloc.h"
@@ -39,6 +41,19 @@ inline const Value *ptr_data(const Value *value) {  // cereal's polymorphic poin
   const Value *pw = value ? value->get("ptr_wrapper") : nullptr;
   return pw ? pw->get("data") : nullptr;
 }
+// obj[k] = v as a Python dict assigns it: a key already there keeps its place.  (These two would sit beside Value in
+// sfm_json.h, which the library includes too; they are for the tools alone.)
+inline void set_key(Value *obj, const char *k, Value v) {
+  Value *slot = obj->get(k);
+  if (slot) *slot = std::move(v);
+  else obj->o.emplace_back(k, std::move(v));
+}
+inline Value make_int(uint64_t v) {
+  Value x;
+  x.kind = Value::Int;
+  x.s = std::to_string(v);
+  return x;
+}
 
 struct Doc {
   Value root;
@@ -56,7 +71,7 @@ struct Doc {
   std::vector<double> obs_x;
 };
 
-// the arrays of a document already parsed into d->root (structure_cli.cpp empties `structure` first)
+// the arrays of a document already parsed into d->root
 inline bool build(Doc *d, std::string *err) {
   const Value &r = d->root;
   const Value *views = r.get("views"), *intrs = r.get("intrinsics"), *exts = r.get("extrinsics"),
@@ -166,10 +181,13 @@ inline bool build(Doc *d, std::string *err) {
   return true;
 }
 
-inline bool load(const std::string &path, Doc *d, std::string *err) {
+// read, parse, build; drop_structure: the input's own `structure` is emptied first (the tools that rebuild it, or never
+// look at it: the key keeps its place in the document)
+inline bool load(const std::string &path, bool drop_structure, Doc *d, std::string *err) {
   std::string text;
   if (!sfmjson::read_file(path.c_str(), &text)) return *err = "cannot be read", false;
   if (!sfmjson::parse(text, &d->root, err)) return false;
+  if (drop_structure && d->root.kind == Value::Obj) set_key(&d->root, "structure", Value::make_arr());
   return build(d, err);
 }
 

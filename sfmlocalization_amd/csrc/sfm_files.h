@@ -1,0 +1,234 @@
+// The on-disk contract as the C++ tools read and write it (host code only, no HIP; shared by the *_cli.cpp programs):
+// what sfmlocalization_amd/fileio.py is for the Python tools.  Every reader mirrors one function of fileio.py or of
+// os.path, named at its definition; where a damaged file could be read in more than one way, fileio.py decides.
+// tests/test_sfm_files.py holds these functions against their Python twins (tests/cpp/sfm_files.cpp).
+#pragma once
+
+#include <sys/stat.h>
+
+#include <cctype>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <initializer_list>
+#include <map>
+#include <sstream>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace sfmfiles {
+
+// ---- paths ----
+// os.path.join(root, name)
+inline std::string join(const std::string &root, const std::string &name) {
+  if (root.empty() || (!name.empty() && name[0] == '/')) return name;
+  return root + (root.back() == '/' ? "" : "/") + name;
+}
+// os.path.basename(p)
+inline std::string basename_of(const std::string &p) {
+  const size_t s = p.rfind('/');
+  return s == std::string::npos ? p : p.substr(s + 1);
+}
+// os.path.dirname(p)
+inline std::string dirname_of(const std::string &p) {
+  const size_t s = p.rfind('/');
+  if (s == std::string::npos) return std::string();
+  std::string head = p.substr(0, s + 1);
+  if (head.find_first_not_of('/') != std::string::npos)
+    while (head.back() == '/') head.pop_back();
+  return head;
+}
+// os.path.splitext(os.path.basename(p))[0]: leading dots belong to the name (the tools whose Python twin names a
+// view's files this way: structure, relpose)
+inline std::string stem_of(const std::string &p) {
+  std::string base = basename_of(p);
+  size_t lead = 0;
+  while (lead < base.size() && base[lead] == '.') ++lead;
+  const size_t dot = base.rfind('.');
+  if (dot != std::string::npos && dot > lead) base.resize(dot);
+  return base;
+}
+// stlplus::basename_part(p), the reference's form and the library loader's (map_io.hip): everything before the last
+// dot, so ".hidden" gives "".  The tools that name files the loader or the reference's own programs look up use this
+// one (extfeat, localize, trainbow); it differs from stem_of only for a name whose dots all lead it.
+inline std::string basename_part(const std::string &p) {
+  const std::string base = basename_of(p);
+  const size_t dot = base.rfind('.');
+  return dot == std::string::npos ? base : base.substr(0, dot);
+}
+// what follows the last dot of the base name, "" without one (the image filter of localization.cpp:204-206)
+inline std::string ext_of(const std::string &p) {
+  const std::string base = basename_of(p);
+  const size_t dot = base.rfind('.');
+  return dot == std::string::npos ? std::string() : base.substr(dot + 1);
+}
+// os.path.isfile(p), os.path.isdir(p)
+inline bool is_file(const std::string &p) {
+  struct stat st;
+  return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+inline bool is_dir(const std::string &p) {
+  struct stat st;
+  return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
+}
+
+inline bool read_all(const std::string &p, std::vector<uint8_t> *out) {
+  FILE *f = fopen(p.c_str(), "rb");
+  if (!f) return false;
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  out->resize(n > 0 ? (size_t)n : 0);
+  const bool ok = n >= 0 && fread(out->data(), 1, out->size(), f) == out->size();
+  fclose(f);
+  return ok;
+}
+
+// ---- <base>.desc: [u64 N][N x 64 B] (fileio.read_desc) ----
+// Appends the N rows to *rows.  N is held against the file's length before anything is allocated; a short header or a
+// body shorter than N rows is refused with *rows as it was, bytes after the rows are ignored.
+inline bool read_desc(const std::string &p, std::vector<uint8_t> *rows) {
+  FILE *f = fopen(p.c_str(), "rb");
+  if (!f) return false;
+  uint64_t n = 0;
+  struct stat st;
+  bool ok = fstat(fileno(f), &st) == 0 && st.st_size >= 8 && fread(&n, 8, 1, f) == 1 && n <= ((uint64_t)st.st_size - 8) / 64;
+  if (ok && n) {
+    const size_t at = rows->size();
+    rows->resize(at + (size_t)n * 64);
+    ok = fread(rows->data() + at, 64, (size_t)n, f) == (size_t)n;
+    if (!ok) rows->resize(at);
+  }
+  fclose(f);
+  return ok;
+}
+
+// ---- <base>.feat: "x y size angle" per line (fileio.read_feat) ----
+// Appends x, y of every line as float32 and stops at the first line with fewer than four tokens.  (A token that
+// write_feat or `ostream << float` emits has at most six significant digits; strtof of it and the float of its strtod,
+// which is how the older tools read it, are the same number.)
+inline bool read_feat(const std::string &p, std::vector<float> *xy) {
+  std::ifstream f(p);
+  if (!f) return false;
+  std::string line;
+  while (std::getline(f, line)) {
+    std::istringstream ss(line);
+    std::string t[4];
+    if (!(ss >> t[0] >> t[1] >> t[2] >> t[3])) break;
+    xy->push_back(strtof(t[0].c_str(), nullptr));
+    xy->push_back(strtof(t[1].c_str(), nullptr));
+  }
+  return true;
+}
+
+// ---- matches.*.txt: "I J\nn\ni j\n..." per pair, view ids as keys (fileio.read_matches_txt / write_matches_txt) ----
+typedef std::map<std::pair<uint32_t, uint32_t>, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> PairMatches;
+
+// the same pair twice: the later entry replaces the earlier, as a dictionary does.  A file that ends inside an entry is
+// "truncated"; a token that is not a number, or not one of 32 bits without a sign, is "malformed" (fileio raises on the
+// first two and wraps the last silently into uint32, which no well-formed file means).
+inline bool read_matches(const std::string &path, PairMatches *out, std::string *err) {
+  std::ifstream f(path);
+  if (!f) return *err = "cannot be read", false;
+  PairMatches all;
+  std::string ta, tb, tn;
+  while (f >> ta) {
+    if (!(f >> tb >> tn)) return *err = "truncated", false;
+    char *e1, *e2, *e3;
+    const long long a = strtoll(ta.c_str(), &e1, 10), b = strtoll(tb.c_str(), &e2, 10), n = strtoll(tn.c_str(), &e3, 10);
+    if (*e1 || *e2 || *e3 || a < 0 || b < 0 || n < 0 || a > 0xFFFFFFFFll || b > 0xFFFFFFFFll) return *err = "malformed", false;
+    auto &dst = all[{(uint32_t)a, (uint32_t)b}];
+    dst.first.clear();
+    dst.second.clear();
+    for (long long t = 0; t < n; ++t) {
+      std::string ti, tj;
+      if (!(f >> ti >> tj)) return *err = "truncated", false;
+      const long long i = strtoll(ti.c_str(), &e1, 10), j = strtoll(tj.c_str(), &e2, 10);
+      if (*e1 || *e2 || i < 0 || j < 0 || i > 0xFFFFFFFFll || j > 0xFFFFFFFFll) return *err = "malformed", false;
+      dst.first.push_back((uint32_t)i);
+      dst.second.push_back((uint32_t)j);
+    }
+  }
+  out->swap(all);
+  return true;
+}
+
+inline bool write_matches(const std::string &path, const PairMatches &m) {
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) return false;
+  for (const auto &kv : m) {
+    fprintf(f, "%u %u\n%zu\n", kv.first.first, kv.first.second, kv.second.first.size());
+    for (size_t k = 0; k < kv.second.first.size(); ++k) fprintf(f, "%u %u\n", kv.second.first[k], kv.second.second[k]);
+  }
+  return fclose(f) == 0;
+}
+
+// the pair list layout of sfmloc_tracks_build and sfmloc_relative_poses (capi.pair_arrays): pairs as view indices in
+// ascending (I, J), the matches of pair k at [offsets[k], offsets[k + 1])
+struct PairList {
+  std::vector<uint32_t> pairs, mi, mj;
+  std::vector<uint64_t> offsets{0};
+};
+
+inline bool read_matches(const std::string &path, const std::map<uint32_t, uint32_t> &view_index, PairList *out, std::string *err) {
+  PairMatches all;
+  if (!read_matches(path, &all, err)) return false;
+  for (const auto &kv : all) {
+    const auto ia = view_index.find(kv.first.first), ib = view_index.find(kv.first.second);
+    if (ia == view_index.end() || ib == view_index.end()) return *err = "a pair names an unknown view", false;
+    out->pairs.push_back(ia->second);
+    out->pairs.push_back(ib->second);
+    out->mi.insert(out->mi.end(), kv.second.first.begin(), kv.second.first.end());
+    out->mj.insert(out->mj.end(), kv.second.second.begin(), kv.second.second.end());
+    out->offsets.push_back(out->mi.size());
+  }
+  return true;
+}
+
+// ---- cv::CommandLineParser syntax: positionals, -k=v / --key=v, bare flags (engine.parse_cv_args) ----
+inline bool is_number(const std::string &s) {
+  char *end = nullptr;
+  std::strtod(s.c_str(), &end);
+  return !s.empty() && end && *end == '\0';
+}
+
+struct Args {
+  std::vector<std::string> pos;
+  std::map<std::string, std::string> opt;
+  std::string get(std::initializer_list<const char *> names, const char *def) const {
+    std::string v = def;
+    for (const char *n : names) {
+      auto it = opt.find(n);
+      if (it != opt.end()) v = it->second;
+    }
+    return v;
+  }
+  bool flag(std::initializer_list<const char *> names) const {
+    std::string v = get(names, "false");
+    for (char &c : v) c = (char)tolower(c);
+    return v == "1" || v == "true" || v == "yes";
+  }
+};
+
+inline Args parse_args(int argc, char **argv) {
+  Args a;
+  for (int i = 1; i < argc; ++i) {
+    std::string s = argv[i];
+    if (s.size() > 1 && s[0] == '-' && !is_number(s)) {
+      size_t p = s.find_first_not_of('-');
+      std::string kv = s.substr(p == std::string::npos ? s.size() : p);
+      size_t eq = kv.find('=');
+      if (eq == std::string::npos)
+        a.opt[kv] = "true";
+      else
+        a.opt[kv.substr(0, eq)] = kv.substr(eq + 1);
+    } else {
+      a.pos.push_back(s);
+    }
+  }
+  return a;
+}
+
+}  // namespace sfmfiles

@@ -15,17 +15,19 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <map>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "../../include/sfmloc.h"
 #include "sfm_doc.h"
+#include "sfm_files.h"
 #include "sfm_json.h"
 
+using namespace sfmfiles;
 using sfmdoc::Doc;
+using sfmdoc::make_int;
+using sfmdoc::set_key;
 using sfmjson::Value;
 
 namespace {
@@ -45,92 +47,6 @@ void usage() {
           "[-a|--min_angle] minimal triangulation angle in degrees (2.0)\n"
           "[--blind] (switch) triangulate every track from all its views, no robust rounds\n",
           kName);
-}
-
-// os.path.join(root, name)
-std::string join(const std::string &root, const std::string &name) {
-  if (root.empty() || (!name.empty() && name[0] == '/')) return name;
-  return root + (root.back() == '/' ? "" : "/") + name;
-}
-
-// os.path.splitext(os.path.basename(name))[0]
-std::string stem_of(const std::string &name) {
-  const size_t slash = name.rfind('/');
-  std::string base = slash == std::string::npos ? name : name.substr(slash + 1);
-  size_t lead = 0;
-  while (lead < base.size() && base[lead] == '.') ++lead;
-  const size_t dot = base.rfind('.');
-  if (dot != std::string::npos && dot > lead) base.resize(dot);
-  return base;
-}
-
-void set_key(Value *obj, const char *k, Value v) {
-  Value *slot = obj->get(k);
-  if (slot) *slot = std::move(v);
-  else obj->o.emplace_back(k, std::move(v));
-}
-
-Value make_int(uint64_t v) {
-  Value x;
-  x.kind = Value::Int;
-  x.s = std::to_string(v);
-  return x;
-}
-
-// "x y size angle" per line, read as float32; stops at the first short line (fileio.read_feat)
-bool read_feat(const std::string &path, std::vector<float> *xy) {
-  std::ifstream f(path);
-  if (!f) return false;
-  std::string line;
-  while (std::getline(f, line)) {
-    std::istringstream ss(line);
-    std::string t[4];
-    if (!(ss >> t[0] >> t[1] >> t[2] >> t[3])) break;
-    xy->push_back(strtof(t[0].c_str(), nullptr));
-    xy->push_back(strtof(t[1].c_str(), nullptr));
-  }
-  return true;
-}
-
-struct PairList {
-  std::vector<uint32_t> pairs, mi, mj;
-  std::vector<uint64_t> offsets{0};
-};
-
-// "I J\nn\ni j\n..." with view ids as keys (fileio.read_matches_txt), into the layout of sfmloc_tracks_build in ascending
-// (I, J); the same pair twice: the later entry replaces the earlier, as a dictionary does
-bool read_matches(const std::string &path, const std::map<uint32_t, uint32_t> &view_index, PairList *out, std::string *err) {
-  std::ifstream f(path);
-  if (!f) return *err = "cannot be read", false;
-  std::map<std::pair<uint32_t, uint32_t>, std::pair<std::vector<uint32_t>, std::vector<uint32_t>>> all;
-  std::string ta, tb, tn;
-  while (f >> ta) {
-    if (!(f >> tb >> tn)) return *err = "truncated", false;
-    char *e1, *e2, *e3;
-    const long long a = strtoll(ta.c_str(), &e1, 10), b = strtoll(tb.c_str(), &e2, 10), n = strtoll(tn.c_str(), &e3, 10);
-    if (*e1 || *e2 || *e3 || a < 0 || b < 0 || n < 0 || a > 0xFFFFFFFFll || b > 0xFFFFFFFFll) return *err = "malformed", false;
-    auto &dst = all[{(uint32_t)a, (uint32_t)b}];
-    dst.first.clear();
-    dst.second.clear();
-    for (long long t = 0; t < n; ++t) {
-      std::string ti, tj;
-      if (!(f >> ti >> tj)) return *err = "truncated", false;
-      const long long i = strtoll(ti.c_str(), &e1, 10), j = strtoll(tj.c_str(), &e2, 10);
-      if (*e1 || *e2 || i < 0 || j < 0 || i > 0xFFFFFFFFll || j > 0xFFFFFFFFll) return *err = "malformed", false;
-      dst.first.push_back((uint32_t)i);
-      dst.second.push_back((uint32_t)j);
-    }
-  }
-  for (const auto &kv : all) {
-    const auto ia = view_index.find(kv.first.first), ib = view_index.find(kv.first.second);
-    if (ia == view_index.end() || ib == view_index.end()) return *err = "a pair names an unknown view", false;
-    out->pairs.push_back(ia->second);
-    out->pairs.push_back(ib->second);
-    out->mi.insert(out->mi.end(), kv.second.first.begin(), kv.second.first.end());
-    out->mj.insert(out->mj.end(), kv.second.second.begin(), kv.second.second.end());
-    out->offsets.push_back(out->mi.size());
-  }
-  return true;
 }
 
 std::string g(double v) {
@@ -178,13 +94,8 @@ int main(int argc, char **argv) {
     return 1;
   }
   Doc d;
-  std::string err, text;
-  bool ok = sfmjson::read_file(in.c_str(), &text);
-  if (!ok) err = "cannot be read";
-  ok = ok && sfmjson::parse(text, &d.root, &err);
-  if (ok && d.root.kind == Value::Obj) set_key(&d.root, "structure", Value::make_arr());  // the input's own: ignored
-  ok = ok && sfmdoc::build(&d, &err);
-  if (!ok) {
+  std::string err;
+  if (!sfmdoc::load(in, true, &d, &err)) {  // the input's own structure: ignored
     fprintf(stderr, "\nThe input SfM_Data file \"%s\" cannot be read. (%s)\n", in.c_str(), err.c_str());
     return 1;
   }

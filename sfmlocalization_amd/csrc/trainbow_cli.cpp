@@ -11,7 +11,6 @@
 // sfm_data.json (saveMatBin, :238-272: sfmloc_imgbow_*).
 //   TrainBoW --format-floats v...   prints each float32 as the YAML writer does (a test hook of the number format)
 #include <dirent.h>
-#include <sys/stat.h>
 
 #include <algorithm>
 #include <cfloat>
@@ -26,7 +25,10 @@
 #include <vector>
 
 #include "../../include/sfmloc.h"
+#include "sfm_files.h"
 #include "sfm_json.h"
+
+using namespace sfmfiles;
 
 namespace {
 
@@ -37,26 +39,10 @@ const int kKmeansIteration = 100, kKmeansAttempts = 3;             // BoFSpatial
 const uint64_t kKmeansSeed = 0xFFFFFFFFull;                        // cv::theRNG() of a fresh process
 const uint32_t kBatch = 8;
 
-bool is_dir(const std::string &p) {
-  struct stat st;
-  return stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode);
-}
-bool is_file(const std::string &p) {
-  struct stat st;
-  return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
-}
-std::string join(const std::string &a, const std::string &b) {
-  return a.empty() ? b : (a.back() == '/' ? a + b : a + "/" + b);
-}
-std::string basename_of(const std::string &p) {
-  std::string s = p;
-  while (s.size() > 1 && s.back() == '/') s.pop_back();
-  const size_t k = s.find_last_of('/');
-  return k == std::string::npos ? s : s.substr(k + 1);
-}
-std::string dirname_of(const std::string &p) {
-  const size_t k = p.find_last_of('/');
-  return k == std::string::npos ? std::string(".") : (k == 0 ? std::string("/") : p.substr(0, k));
+// the last part of a directory's name, however many slashes end it
+std::string folder_name(std::string d) {
+  while (d.size() > 1 && d.back() == '/') d.pop_back();
+  return basename_of(d);
 }
 std::vector<std::string> sorted_entries(const std::string &d) {
   std::vector<std::string> out;
@@ -75,7 +61,7 @@ std::vector<std::string> sorted_entries(const std::string &d) {
 void read_sfm_data_files(const std::string &d, std::vector<std::string> *out) {
   if (!is_dir(d)) return;
   const std::vector<std::string> names = sorted_entries(d);
-  if (basename_of(d) == "matches") {
+  if (folder_name(d) == "matches") {
     for (const std::string &n : names)
       if (n == "sfm_data.json" && is_file(join(d, n))) out->push_back(join(d, n));
   } else {
@@ -266,10 +252,7 @@ int main(int argc, char **argv) {
         sfmloc_view_list_close(vl);
         return fail("sfmloc_view_list_get");
       }
-      std::string base = basename_of(path);
-      const size_t dot = base.find_last_of('.');
-      if (dot != std::string::npos) base = base.substr(0, dot);
-      views.push_back({path, join(dirname_of(f), base + ".bow")});
+      views.push_back({path, join(dirname_of(f), basename_part(path) + ".bow")});
     }
     sfmloc_view_list_close(vl);
   }
