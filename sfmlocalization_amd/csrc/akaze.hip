@@ -92,52 +92,9 @@ __device__ void det_sincosf(float a, float *s, float *c) {
 }
 
 // ---- pixel kernels -----------------------------------------------------------------------------------------------
-constexpr int kGradRows = 16;  // image rows one block of the contrast-factor kernels walks
-
 struct Taps {
   float k[9];
 };
-
-__global__ void k_u8_to_f32(const uint8_t *__restrict__ src, float *__restrict__ dst, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = (float)src[i] / 255.0f;
-}
-
-// one pass of the separable Gaussian, BORDER_REPLICATE; horizontal = 1: along x
-__global__ void k_gauss_pass(const float *__restrict__ src, float *__restrict__ dst, int w, int h, Taps t, int ksize,
-                             int horizontal) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int r = ksize / 2;
-  float acc = 0.0f;
-  for (int i = 0; i < ksize; ++i) {
-    const float v = horizontal ? src[(size_t)y * w + clampi(x + i - r, 0, w - 1)]
-                               : src[(size_t)clampi(y + i - r, 0, h - 1) * w + x];
-    acc = acc + t.k[i] * v;
-  }
-  dst[(size_t)y * w + x] = acc;
-}
-
-__global__ void k_scharr(const float *__restrict__ src, float *__restrict__ dst, int w, int h, int xorder, int scale,
-                         float ws, float wm) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const int xm = reflect101(x - scale, w), xp = reflect101(x + scale, w);
-  const int ym = reflect101(y - scale, h), yp = reflect101(y + scale, h);
-  float d;
-  if (xorder) {
-    const float r0 = src[(size_t)y * w + xp] - src[(size_t)y * w + xm];
-    const float rm = src[(size_t)ym * w + xp] - src[(size_t)ym * w + xm];
-    const float rp = src[(size_t)yp * w + xp] - src[(size_t)yp * w + xm];
-    d = wm * r0 + ws * (rm + rp);
-  } else {
-    const float r0 = src[(size_t)yp * w + x] - src[(size_t)ym * w + x];
-    const float rm = src[(size_t)yp * w + xm] - src[(size_t)ym * w + xm];
-    const float rp = src[(size_t)yp * w + xp] - src[(size_t)ym * w + xp];
-    d = wm * r0 + ws * (rm + rp);
-  }
-  dst[(size_t)y * w + x] = d;
-}
 
 struct HalfsampleBody {
   static constexpr int kGangThreads = 256;
@@ -164,51 +121,13 @@ __global__ void k_halfsample(const float *__restrict__ src, int sw, int sh, floa
   HalfsampleBody::run(src, sw, sh, dst, dw, dh);
 }
 
-// compute_k_percentile: maximum gradient magnitude over the interior, then its 300-bin histogram.
-// One atomic per wave (max) / per block and bin (histogram): a single global word hit by every pixel serialises.
-__global__ __launch_bounds__(128) void k_grad_max(const float *__restrict__ lx, const float *__restrict__ ly, int w,
-                                                  int h, unsigned int *hmax_bits) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  float m = 0.0f;
-  for (int y = blockIdx.y * kGradRows; y < min(h, (int)(blockIdx.y + 1) * kGradRows); ++y)
-    if (x >= 1 && x < w - 1 && y >= 1 && y < h - 1) {
-      const float a = lx[(size_t)y * w + x], b = ly[(size_t)y * w + x];
-      m = fmaxf(m, sqrtf(a * a + b * b));
-    }
-  unsigned int bits = __float_as_uint(m);  // non-negative floats order like their bit patterns
-  for (int off = 32; off > 0; off >>= 1) bits = max(bits, (unsigned int)__shfl_xor((int)bits, off, 64));
-  if ((threadIdx.x & 63) == 0 && bits != 0) atomicMax(hmax_bits, bits);
-}
-
-__global__ __launch_bounds__(128) void k_grad_hist(const float *__restrict__ lx, const float *__restrict__ ly, int w,
-                                                   int h, const unsigned int *hmax_bits,
-                                                   unsigned int *hist /*[301]: 300 bins + npoints*/) {
-  __shared__ unsigned int lh[301];
-  for (int i = threadIdx.x; i < 301; i += blockDim.x) lh[i] = 0;
-  __syncthreads();
-  const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  const float hmax = __uint_as_float(*hmax_bits);
-  unsigned int mine = 0;
-  for (int y = blockIdx.y * kGradRows; y < min(h, (int)(blockIdx.y + 1) * kGradRows); ++y)
-    if (x >= 1 && x < w - 1 && y >= 1 && y < h - 1) {
-      const float a = lx[(size_t)y * w + x], b = ly[(size_t)y * w + x];
-      const float m = sqrtf(a * a + b * b);
-      if (m != 0.0f) {
-        int nbin = (int)floorf(300.0f * (m / hmax));
-        if (nbin == 300) nbin--;
-        atomicAdd(&lh[nbin], 1u);
-        ++mine;
-      }
-    }
-  if (mine) atomicAdd(&lh[300], mine);
-  __syncthreads();
-  for (int i = threadIdx.x; i < 301; i += blockDim.x)
-    if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
-// The start of Create_Nonlinear_Scale_Space in four launches instead of thirteen (u8 -> f32, 2 x 2 Gaussian passes, a
-// copy, two Scharr passes, two fills, maximum, histogram, percentile).  Per pixel the arithmetic is that of the separate
-// kernels above, in the same order, so every image and the contrast factor are the same bit for bit.
+// The start of Create_Nonlinear_Scale_Space in four launches: convertTo(CV_32F, 1 / 255), gaussian_2D_convolution with
+// the 9-tap kernel (sigma 1.6) -> Lt and Lsmooth of level 0, and compute_k_percentile (the 5-tap Gaussian, sigma 1, Scharr
+// x and y at scale 1, the maximum gradient magnitude over the interior, its 300-bin histogram, the 70 % percentile).
+// Per pixel the arithmetic is that of those OpenCV steps as oracle/sfm_oracle_akaze.c restates them (build_scale_space's
+// first lines, gauss_blur, scharr, k_percentile): a separable pass is one sum in tap order with BORDER_REPLICATE, the
+// Scharr sum is wm * r0 + ws * (rm + rp) with BORDER_REFLECT_101 -- every image and the contrast factor are the same bit
+// for bit.
 //  k_pre_rows   image (u8) -> row pass of the 9-tap Gaussian (level 0) and of the 5-tap one (contrast factor); clears
 //               the histogram words
 //  k_pre_cols   column passes -> Lt and Lsmooth of level 0, and the smoothed image of the contrast factor
@@ -343,7 +262,7 @@ struct PreHistBody {
     __syncthreads();
     if (ticket != gridDim.x * gridDim.y - 1) return;
     __threadfence();
-    // compute_k_percentile's tail (k_kcontrast), by the last workgroup; the histogram is read through atomics so that no
+    // compute_k_percentile's tail (the walk to the 70 % bin), by the last workgroup; the histogram is read through atomics so that no
     // stale cached word is used.  (Round 3: all of the workgroup's threads fetch the bins, side by side, and one lane walks
     // them in LDS -- the walk used to be one lane's chain of up to 300 global atomic round trips, most of this kernel's
     // 24 us.  Same integers, same k.)
@@ -365,23 +284,18 @@ __global__ __launch_bounds__(128) void k_pre_hist(const float *__restrict__ mag,
   PreHistBody::run(mag, w, h, hist_all, kcontrast);
 }
 
-__global__ void k_kcontrast(const unsigned int *hmax_bits, const unsigned int *hist, float *kcontrast) {
-  const float hmax = __uint_as_float(*hmax_bits);
-  const int npoints = (int)hist[300];
-  const int nthreshold = (int)((float)npoints * 0.7f);
-  int nelements = 0, k = 0;
-  for (k = 0; nelements < nthreshold && k < 300; k++) nelements += (int)hist[k];
-  *kcontrast = (nelements < nthreshold || npoints == 0) ? 0.03f : hmax * ((float)k / 300.0f);  // (as k_pre_hist)
-}
-
 // nld_step_scalar: Ld_out = Ld + half_step * flux, zero flux across the image border -- up to K steps in one launch
 // (temporal blocking): a 32 x 8 tile is loaded with a halo of K pixels, step s is computed in LDS on the tile grown by
-// K - 1 - s pixels, the last step on the tile itself.  Per pixel the arithmetic is that of a step-per-launch kernel, so
-// the images are the same bit for bit; the scale space of a VGA image is 166 steps, each shorter than a launch
-// (measured: 1.03 -> 0.96 ms per VGA image at 4 steps per launch; 6 and 8 bring nothing more).
-constexpr int kNldFuseMax = 16;
+// K - 1 - s pixels, the last step on the tile itself.  Per pixel the arithmetic is that of one step over the whole image
+// (nld_step_scalar as build_scale_space of oracle/sfm_oracle_akaze.c restates it), so the images are the same bit for
+// bit; the scale space of a VGA image is 166 steps, each shorter than a launch (measured: 1.03 -> 0.96 ms per VGA image
+// at 4 steps per launch; 6 and 8 bring nothing more).  K = 1 .. kNldFuseMax (akaze_plan.h) are instantiated.
+// (More slots than the largest K: the struct is a kernel argument and part of a gang record, so its size sets how many
+// members one gang launch of k_smooth_nld carries; it keeps the size those launches were measured with.)
+constexpr int kNldStepSlots = 16;
+static_assert(kNldFuseMax <= kNldStepSlots, "a launch's half steps do not fit NldSteps");
 struct NldSteps {
-  float half_step[kNldFuseMax];
+  float half_step[kNldStepSlots];
 };
 constexpr int kNldTileX = 32, kNldTileY = 8;  // one output pixel per thread of a 256-thread workgroup
 
@@ -454,82 +368,16 @@ __device__ __forceinline__ float scharr_at(const float *__restrict__ src, int w,
   return wm * r0 + ws * (rm + rp);
 }
 
-// gaussian_2D_convolution(5 x 5, separable, BORDER_REPLICATE) of the level's start image -> Lsmooth, and the
-// Perona-Malik g2 conductivity 1 / (1 + |grad Lsmooth|^2 / k^2) from it (Scharr, scale 1), in one launch: a 32 x 8
-// tile with the source halo in LDS (3 px: 2 for the taps of the column pass's rows / the row pass's columns, 1 for the
-// Scharr stencil on Lsmooth).  The row pass, the column pass and the Scharr sums run in the order a kernel per pass
-// would use, so the images are the same bit for bit.
-struct SmoothFlowBody {
-  static constexpr int kGangThreads = 256;
-  static __device__ __forceinline__ void run(const float *__restrict__ src, float *__restrict__ lsmooth,
-                                             float *__restrict__ g2, int w, int h, const Taps &t,
-                                             const float *kcontrast, int octave) {
-    constexpr int TX = 32, TY = 8;
-    constexpr int SX = TX + 6, SY = TY + 6;  // source region
-    constexpr int MX = TX + 2, MY = TY + 6;  // row-pass region: Lsmooth's columns, the column pass's rows
-    constexpr int LX = TX + 2, LY = TY + 2;  // Lsmooth region
-    __shared__ float sS[SY][SX + 1];
-    __shared__ float sM[MY][MX + 1];
-    __shared__ float sL[LY][LX + 1];
-    const int X0 = blockIdx.x * TX, Y0 = blockIdx.y * TY;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int ly = ty; ly < SY; ly += TY)
-      for (int lx = tx; lx < SX; lx += TX) {
-        const int gx = X0 - 3 + lx, gy = Y0 - 3 + ly;
-        sS[ly][lx] = (gx >= 0 && gx < w && gy >= 0 && gy < h) ? src[(size_t)gy * w + gx] : 0.0f;
-      }
-    __syncthreads();
-    for (int ly = ty; ly < MY; ly += TY)  // row pass at (X0 - 1 + lx, Y0 - 3 + ly)
-      for (int lx = tx; lx < MX; lx += TX) {
-        const int gx = X0 - 1 + lx, gy = Y0 - 3 + ly;
-        if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;
-        float acc = 0.0f;
-        for (int i = 0; i < 5; ++i) acc = acc + t.k[i] * sS[ly][clampi(gx + i - 2, 0, w - 1) - (X0 - 3)];
-        sM[ly][lx] = acc;
-      }
-    __syncthreads();
-    for (int ly = ty; ly < LY; ly += TY)  // column pass at (X0 - 1 + lx, Y0 - 1 + ly)
-      for (int lx = tx; lx < LX; lx += TX) {
-        const int gx = X0 - 1 + lx, gy = Y0 - 1 + ly;
-        if (gx < 0 || gx >= w || gy < 0 || gy >= h) continue;
-        float acc = 0.0f;
-        for (int i = 0; i < 5; ++i) acc = acc + t.k[i] * sM[clampi(gy + i - 2, 0, h - 1) - (Y0 - 3)][lx];
-        sL[ly][lx] = acc;
-        if (lx >= 1 && lx <= TX && ly >= 1 && ly <= TY) lsmooth[(size_t)gy * w + gx] = acc;
-      }
-    __syncthreads();
-    const int x = X0 + tx, y = Y0 + ty;
-    if (x >= w || y >= h) return;
-    const int xm = reflect101(x - 1, w) - (X0 - 1), xp = reflect101(x + 1, w) - (X0 - 1), xc = tx + 1;
-    const int ym = reflect101(y - 1, h) - (Y0 - 1), yp = reflect101(y + 1, h) - (Y0 - 1), yc = ty + 1;
-    const float ws = 3.0f, wm = 10.0f;
-    float lx_, ly_;
-    {
-      const float r0 = sL[yc][xp] - sL[yc][xm], rm = sL[ym][xp] - sL[ym][xm], rp = sL[yp][xp] - sL[yp][xm];
-      lx_ = wm * r0 + ws * (rm + rp);
-    }
-    {
-      const float r0 = sL[yp][xc] - sL[ym][xc], rm = sL[yp][xm] - sL[ym][xm], rp = sL[yp][xp] - sL[ym][xp];
-      ly_ = wm * r0 + ws * (rm + rp);
-    }
-    float kc = *kcontrast;
-    for (int o = 0; o < octave; ++o) kc = kc * 0.75f;
-    const float inv_k = 1.0f / (kc * kc);
-    g2[(size_t)y * w + x] = 1.0f / (1.0f + inv_k * (lx_ * lx_ + ly_ * ly_));
-  }
-};
-__global__ __launch_bounds__(256) void k_smooth_flow(const float *__restrict__ src, float *__restrict__ lsmooth,
-                                             float *__restrict__ g2, int w, int h, Taps t,
-                                             const float *kcontrast, int octave) {
-  SmoothFlowBody::run(src, lsmooth, g2, w, h, t, kcontrast, octave);
-}
-
-// k_smooth_flow and the level's first k_nld_steps in ONE launch: a 32 x 8 tile computes Lsmooth and the conductivity on
-// itself grown by the K pixels of halo the K diffusion steps need (so the smoothing of the halo is done again by the
-// neighbouring tiles: ~3x the arithmetic of a level's cheapest pass, against a dependent launch per level -- the
-// extraction is a chain of launches, and with images in the whole path is bound by launches per second).  Lsmooth and
-// the conductivity of the tile proper go to global memory as before (derivatives later; further step launches of the
-// level).  Per pixel the arithmetic is that of the two kernels, in the same order: the images are the same bit for bit.
+// A level's start in ONE launch: gaussian_2D_convolution(5 x 5, separable, BORDER_REPLICATE) of the level's start image
+// -> Lsmooth, the Perona-Malik g2 conductivity 1 / (1 + |grad Lsmooth|^2 / k^2) from it (Scharr, scale 1,
+// BORDER_REFLECT_101; k = kcontrast * 0.75^octave) and the first K steps of the level's FED cycle.  A 32 x 8 tile computes
+// Lsmooth and the conductivity on itself grown by the K pixels of halo the K diffusion steps need (so the smoothing of
+// the halo is done again by the neighbouring tiles: ~3x the arithmetic of a level's cheapest pass, against a dependent
+// launch per level -- the extraction is a chain of launches, and with images in the whole path is bound by launches per
+// second).  Lsmooth and the conductivity of the tile proper go to global memory (derivatives later; further step launches
+// of the level).  Per pixel the arithmetic is that of Create_Nonlinear_Scale_Space's loop body as build_scale_space of
+// oracle/sfm_oracle_akaze.c restates it -- gauss_blur's row pass, then its column pass, each one sum in tap order;
+// scharr's wm * r0 + ws * (rm + rp); pm_g2; nld_step_scalar -- in that order: the images are the same bit for bit.
 template <int K>
 struct SmoothNldBody {
   static constexpr int kGangThreads = 256;
@@ -643,9 +491,11 @@ __global__ __launch_bounds__(256) void k_smooth_nld(const float *__restrict__ sr
 // 1024-thread workgroup keeps the evolving image, a second copy for the ping-pong and the conductivity resident and
 // walks the octave's levels: 5 x 5 Gaussian (row pass, column pass) -> Lsmooth (stored), Scharr -> conductivity, the
 // level's FED steps, Lt stored; the next level starts from what is already in LDS.  Per pixel the arithmetic is that of
-// k_smooth_flow and k_nld_steps, in the same order, so the images are the same bit for bit.
-constexpr int kOctaveRunMax = 8;  // levels of one octave
-constexpr int kResidentPix = 13;  // pixels per thread: 150 KB / 12 B / 1024 threads
+// Create_Nonlinear_Scale_Space's loop body as build_scale_space of oracle/sfm_oracle_akaze.c restates it (gauss_blur,
+// scharr, pm_g2, nld_step_scalar), in the same order, so the images are the same bit for bit.  Which octaves run this way,
+// and in runs of how many levels (kOctaveRunMax), is the schedule's decision: akaze_plan.h.
+constexpr int kResidentPix = 13;  // pixels per thread: kResidentLdsBytes / 12 B / 1024 threads, rounded up
+static_assert((size_t)kResidentPix * 1024 * 12 >= kResidentLdsBytes, "a resident octave has more pixels than its threads take");
 struct OctaveRun {
   int n_levels, w, h, octave;
   unsigned int off[kOctaveRunMax];  // offset of the level in the per-level image stacks
@@ -928,7 +778,7 @@ __global__ void k_hessian_det_all(const float *__restrict__ lx_all, const float 
 //   k_extrema_place  the candidates (level, x, y, response, 3x3 patch) into that list
 //   k_suppress       the two passes + sub-pixel refinement + ordered compaction, one workgroup per image
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int kSegPx = 64;          // a segment = what one wave of the extrema kernels covers
+// (kSegPx, the pixels of a segment -- what one wave of the extrema kernels covers --: akaze_plan.h)
 constexpr int kSegMax = kSegPx / 2; // strict 3x3 maxima are never horizontal neighbours
 constexpr int kSegPerWave = 4;      // segments of a row one wave of the extrema kernels takes
 
@@ -1050,7 +900,7 @@ struct SegScanBody {
 //   k_seg_sum    workgroup g adds up chunk g -> part[g]; the workgroup that arrives last turns part[] into the chunks'
 //                starting sums (exclusive scan) and writes the total (nobody waits: the k_pre_hist hand-over)
 //   k_seg_write  workgroup g scans chunk g from part[g]
-constexpr unsigned int kSegChunk = 4096;  // 4 entries per thread of a 1 024-thread workgroup
+static_assert(kSegChunk == 4u * 1024u, "4 entries per thread of a 1 024-thread workgroup");
 __device__ __forceinline__ unsigned int block_scan_1024(unsigned int v, unsigned int *wtot /*[16] LDS*/, unsigned int *total) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   unsigned int inc = v;
@@ -1404,7 +1254,7 @@ enum : uint8_t { kUndecided = 0, kHolds = 1, kDropped = 2, kTakenOver = 3 };
 // responses, of the level and of the one before it, plus the row starts (raster index of a row's first candidate; a band
 // of rows is ONE contiguous index range) for the spilled candidates' scans.  A level with more candidates than the LDS
 // arrays hold, or wider than 12 bits of x, works on the global arrays through the same code.
-constexpr int kSupMaxRows = 4096 + 1;  // level rows the row-start tables hold (sfmloc_akaze_create: height <= 4096)
+// (kSupMaxRows, the level rows the row-start tables hold, is a request limit: akaze_plan.h)
 constexpr int kSupLevelCap = 4096;     // candidates of one level kept in LDS
 constexpr int kSupOwn = kSupLevelCap / 1024;  // candidates of an LDS level per thread: their records stay in registers
 constexpr int kSupMaxW = 4096;         // level width the packed word holds
@@ -2039,7 +1889,7 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   AkPlan plan;
   hipStream_t own_stream = nullptr;  // the one created with the extractor (stream may be a context's, see _share_stream)
   DevBuf<uint8_t> d_gray;
-  DevBuf<float> d_img, d_t0, d_t1, d_t2, d_t3;
+  DevBuf<float> d_t0, d_t1, d_t2, d_t3;
   DevBuf<float> d_Lt, d_Lsmooth, d_Lx, d_Ly, d_Ldet;  // per-level stacks
   DevBuf<unsigned int> d_hist;                // [0] hmax bits, [1..301] histogram + npoints
   DevBuf<float> d_kcontrast;
@@ -2049,10 +1899,9 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   // detection tail (k_extrema_seg .. k_suppress): the raster-ordered candidate list and the suppression's state
   DevBuf<unsigned int> d_ncand;               // [0] candidates, [1] keypoints, [2] rounds of the first pass, [3..5] clocks,
                                               // [6] spilled A/P records, [7] spilled N records, [8] levels out of global arrays
-  unsigned int cand_cap = 1u << 16;
-  unsigned int n_seg = 0, segs_per_row = 0;
+  Detection det;                              // the detection's sizes and grids for this image size (akaze_plan.h)
   DevBuf<unsigned int> d_seg;                 // [n_seg + 1] counts, then (k_seg_scan) where each segment starts
-  DevBuf<unsigned int> d_seg_part;            // [chunks + 1] k_seg_sum / k_seg_write: the chunks' sums, then arrivals
+  DevBuf<unsigned int> d_seg_part;            // [kSegChunksMax + 1] k_seg_sum / k_seg_write: the chunks' sums, then arrivals
   DevBuf<uint8_t> d_seg_x;                    // [n_seg x kSegMax]
   DevBuf<uint32_t> d_cxy;
   DevBuf<uint8_t> d_clevel, d_cstatus, d_cready;
@@ -2073,8 +1922,7 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   // first spec_n keypoints and descriptors into pinned memory: an image with no more keypoints than that costs ONE
   // synchronisation instead of two (~45 us); spec_n follows the last image's count
   unsigned char *h_spec = nullptr;
-  unsigned int spec_n = 512;
-  static constexpr unsigned int kSpecMax = 4096;
+  unsigned int spec_n = 0;                    // (det.spec_start at creation, then up to det.spec_max)
   DevBuf<float> d_gauss25, d_win;
   DevBuf<uint16_t> d_pair;
   DevBuf<float> d_kp, d_angle;
@@ -2093,21 +1941,6 @@ namespace {
   } while (0)
 
 dim3 grid2(int w, int h) { return dim3((w + 127) / 128, h); }
-
-int gauss(Akaze *a, const float *src, float *dst, float *tmp, int w, int h, const float *k, int ksize) {
-  Taps t;
-  for (int i = 0; i < 9; ++i) t.k[i] = i < ksize ? k[i] : 0.0f;
-  hipLaunchKernelGGL(k_gauss_pass, grid2(w, h), dim3(128), 0, a->stream, src, tmp, w, h, t, ksize, 1);
-  hipLaunchKernelGGL(k_gauss_pass, grid2(w, h), dim3(128), 0, a->stream, tmp, dst, w, h, t, ksize, 0);
-  AK_HIP(hipGetLastError());
-  return SFMLOC_OK;
-}
-
-int scharr(Akaze *a, const float *src, float *dst, int w, int h, int xorder, int scale, float ws, float wm) {
-  hipLaunchKernelGGL(k_scharr, grid2(w, h), dim3(128), 0, a->stream, src, dst, w, h, xorder, scale, ws, wm);
-  AK_HIP(hipGetLastError());
-  return SFMLOC_OK;
-}
 
 LevelTab level_tab(const Akaze *a) {
   const AkPlan &P = a->plan;
@@ -2139,173 +1972,92 @@ LevelTab level_tab(const Akaze *a) {
 // need: the levels [0, need) are built (0 = all of them) -- a description-only call builds no level above its keypoints'
 // highest (the dense BoW grid lives on levels 0 .. 3: three of the four octaves used to be evolved for nothing) and no
 // Hessian determinant (with_det = false); every level that IS built has the bits it always had.
+// Which launches an image size takes is decided in akaze_plan.h (evolution(), Detection); this function issues them.
 int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is already in d_gray, written on a->stream*/,
                       int need = 0, bool with_det = true) {
   const AkPlan &P = a->plan;
-  const int nlev = (need > 0 && need < P.nlev) ? need : P.nlev;
+  const Detection &D = a->det;
   const int w = a->w, h = a->h;
-  const size_t n0 = (size_t)w * h;
   // (nothing recorded for this image touches d_gray before the upload: it need not wait for a gang session's launches)
-  if (gray) AK_HIP(hipMemcpyAsync(a->d_gray, gray, n0, hipMemcpyHostToDevice, a->stream.unordered()));
-#define s ((hipStream_t)a->stream) /* the few launches below that have no gang form (comparison paths) */
-  int rc = SFMLOC_OK;
-  static const bool kFusedPre = [] {  // SFMLOC_AKAZE_FUSED_PRE=0: the thirteen separate launches (comparison runs)
-    const char *e = getenv("SFMLOC_AKAZE_FUSED_PRE");
-    return !(e && atoi(e) == 0);
-  }();
-  const dim3 ggrid((w + 127) / 128, (h + kGradRows - 1) / kGradRows);
-  if (kFusedPre) {
+  if (gray) AK_HIP(hipMemcpyAsync(a->d_gray, gray, (size_t)w * h, hipMemcpyHostToDevice, a->stream.unordered()));
+  {
     Taps2 t2;
     for (int k = 0; k < 9; ++k) t2.k9[k] = P.g16[k];
     for (int k = 0; k < 5; ++k) t2.k5[k] = P.g10[k];
     sfm_launch<PreRowsBody>(a, k_pre_rows, grid2(w, h), dim3(128), (uint32_t)0, a->d_gray, a->d_t3, a->d_t1, w, h, t2, a->d_hist);
     sfm_launch<PreColsBody>(a, k_pre_cols, grid2(w, h), dim3(128), (uint32_t)0, a->d_t3, a->d_t1, a->d_Lt, a->d_Lsmooth, a->d_t0, w, h, t2);
-    sfm_launch<PreGradBody>(a, k_pre_grad, ggrid, dim3(128), (uint32_t)0, a->d_t0, a->d_t2, w, h, a->d_hist);
-    {
-      unsigned int hy = ggrid.y;
-      if (ggrid.x * hy > 256u) hy = std::max(1u, 256u / ggrid.x);
-      sfm_launch<PreHistBody>(a, k_pre_hist, dim3(ggrid.x, hy), dim3(128), (uint32_t)0, a->d_t2, w, h, a->d_hist, a->d_kcontrast);
-    }
+    sfm_launch<PreGradBody>(a, k_pre_grad, dim3(D.hist_grid_x, D.grad_grid_y), dim3(128), (uint32_t)0, a->d_t0, a->d_t2, w, h, a->d_hist);
+    sfm_launch<PreHistBody>(a, k_pre_hist, dim3(D.hist_grid_x, D.hist_grid_y), dim3(128), (uint32_t)0, a->d_t2, w, h, a->d_hist, a->d_kcontrast);
     AK_HIP(hipGetLastError());
-  } else {
-  hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, s, a->d_gray, a->d_img, n0);
-  rc = gauss(a, a->d_img, a->d_Lt, a->d_t3, w, h, P.g16, 9);
-  if (rc) return rc;
-  AK_HIP(hipMemcpyAsync(a->d_Lsmooth, a->d_Lt, n0 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // contrast factor
-  rc = gauss(a, a->d_img, a->d_t0, a->d_t3, w, h, P.g10, 5);
-  if (!rc) rc = scharr(a, a->d_t0, a->d_t1, w, h, 1, 1, 3.0f, 10.0f);
-  if (!rc) rc = scharr(a, a->d_t0, a->d_t2, w, h, 0, 1, 3.0f, 10.0f);
-  if (rc) return rc;
-  AK_HIP(hipMemsetAsync(a->d_hist, 0, 302 * sizeof(unsigned int), s));
-  hipLaunchKernelGGL(k_grad_max, ggrid, dim3(128), 0, s, a->d_t1, a->d_t2, w, h, a->d_hist);
-  hipLaunchKernelGGL(k_grad_hist, ggrid, dim3(128), 0, s, a->d_t1, a->d_t2, w, h, a->d_hist, a->d_hist + 1);
-  hipLaunchKernelGGL(k_kcontrast, dim3(1), dim3(1), 0, s, a->d_hist, a->d_hist + 1, a->d_kcontrast);
-  AK_HIP(hipGetLastError());
   }
-  static const bool kResident = [] {  // SFMLOC_AKAZE_RESIDENT=0: the per-level kernels everywhere (comparison runs)
-    const char *e = getenv("SFMLOC_AKAZE_RESIDENT");
-    return !(e && atoi(e) == 0);
-  }();
-  for (int i = 1; i < nlev; ++i) {
-    const AkLevel &L = P.lev[i], &Lp = P.lev[i - 1];
-    float *Lt = a->d_Lt + L.off;
-    // an octave whose image fits in LDS three times runs in one launch (k_octave_resident)
-    {
-      int j = i;
-      while (j + 1 < nlev && P.lev[j + 1].octave == L.octave) ++j;
-      const size_t lds = (size_t)3 * L.w * L.h * sizeof(float);
-      const bool whole = i == 1 || Lp.octave != L.octave;  // the octave's first level of the loop
-      if (kResident && whole && lds <= 150u * 1024u && j - i + 1 <= kOctaveRunMax && a->d_half_steps) {
-        const float *start = a->d_Lt + Lp.off;
-        if (L.octave > Lp.octave) {
-          sfm_launch<HalfsampleBody>(a, k_halfsample, grid2(L.w, L.h), dim3(128), (uint32_t)0, a->d_Lt + Lp.off, Lp.w, Lp.h, a->d_t3, L.w, L.h);
-          start = a->d_t3;
-        }
-        OctaveRun R{};
-        R.n_levels = j - i + 1;
-        R.w = L.w;
-        R.h = L.h;
-        R.octave = L.octave;
-        for (int q = i; q <= j; ++q) {
-          R.off[q - i] = (unsigned int)P.lev[q].off;
-          R.nsteps[q - i] = P.lev[q].nsteps;
-          R.step0[q - i] = q * kMaxFedSteps;
-        }
-        Taps t5;
-        for (int k = 0; k < 9; ++k) t5.k[k] = k < 5 ? P.g10[k] : 0.0f;
-        // (a function-local static with an initialiser: set once, safely, whichever host thread gets here first)
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_octave_resident),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        AK_HIP(attr);
-        sfm_launch<OctaveResidentBody>(a, k_octave_resident, dim3(1), dim3(1024), (uint32_t)lds, start, a->d_Lt, a->d_Lsmooth, t5,
-                           a->d_kcontrast, a->d_half_steps, R);
-        AK_HIP(hipGetLastError());
-        i = j;
-        continue;
+  Taps t5;
+  for (int k = 0; k < 9; ++k) t5.k[k] = k < 5 ? P.g10[k] : 0.0f;
+  EvoStep steps[kMaxLevels];
+  const int n_steps = evolution(P, need, steps);
+  for (int e = 0; e < n_steps; ++e) {
+    const EvoStep &E = steps[e];
+    const AkLevel &L = P.lev[E.first], &Lp = P.lev[E.first - 1];
+    // the step starts from the previous level's Lt, half-sampled at an octave change
+    float *Lt = a->d_Lt + L.off, *prev = a->d_Lt + Lp.off;
+    float *start = E.source == kPrevLt ? prev : (E.source == kOwnLt ? Lt : (float *)a->d_t3);
+    if (E.halfsample)
+      sfm_launch<HalfsampleBody>(a, k_halfsample, grid2(L.w, L.h), dim3(128), (uint32_t)0, prev, Lp.w, Lp.h, start, L.w, L.h);
+    if (E.resident) {  // the levels first .. last of the octave in one launch (k_octave_resident)
+      OctaveRun R{};
+      R.n_levels = E.last - E.first + 1;
+      R.w = L.w;
+      R.h = L.h;
+      R.octave = L.octave;
+      for (int q = E.first; q <= E.last; ++q) {
+        R.off[q - E.first] = (unsigned int)P.lev[q].off;
+        R.nsteps[q - E.first] = P.lev[q].nsteps;
+        R.step0[q - E.first] = q * kMaxFedSteps;
       }
+      // (a function-local static with an initialiser: set once, safely, whichever host thread gets here first)
+      static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_octave_resident),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsBytes);
+      AK_HIP(attr);
+      sfm_launch<OctaveResidentBody>(a, k_octave_resident, dim3(1), dim3(1024), (uint32_t)((size_t)3 * L.w * L.h * sizeof(float)),
+                                     start, a->d_Lt, a->d_Lsmooth, t5, a->d_kcontrast, a->d_half_steps, R);
+      AK_HIP(hipGetLastError());
+      continue;
     }
-    // the level starts from the previous level's Lt (half-sampled at an octave change); the FED steps ping-pong
-    // between this level's Lt and a scratch image, arranged so that the last step lands in Lt without a copy
-    const float *start = a->d_Lt + Lp.off;
-    // diffusion steps per launch (k_nld_steps): 4 on the large levels, where the tile halo's redundant work costs more
-    // than a launch; more on the upper octaves (<= 160 x 120), whose steps are each far shorter than a launch boundary and
-    // which hold most of the schedule's steps (133 of 165 at VGA).  SFMLOC_AKAZE_FUSE / _FUSE_SMALL = 1..16 for tuning.
-    static const int kFuseBig = [] {
-      const char *e = getenv("SFMLOC_AKAZE_FUSE");
-      const int v = e ? atoi(e) : 4;
-      return (v >= 1 && v <= kNldFuseMax) ? v : 4;
-    }();
-    static const int kFuseSmall = [] {
-      const char *e = getenv("SFMLOC_AKAZE_FUSE_SMALL");
-      const int v = e ? atoi(e) : 8;
-      return (v >= 1 && v <= kNldFuseMax) ? v : 8;
-    }();
-    // (the 240 x 135 octave of a 1080p frame was tried with the small levels' count: no effect, 1.10 / 1.23 ms either way)
-    const int kFuse = (L.w <= 160) ? kFuseSmall : kFuseBig;
-    const int n_launch = (L.nsteps + kFuse - 1) / kFuse;
-    if (L.octave > Lp.octave) {
-      float *half = (n_launch % 2 == 0) ? Lt : a->d_t3;  // even number of launches: start (and end) in Lt
-      sfm_launch<HalfsampleBody>(a, k_halfsample, grid2(L.w, L.h), dim3(128), (uint32_t)0, a->d_Lt + Lp.off, Lp.w, Lp.h, half, L.w, L.h);
-      start = half;
-    }
-    Taps t5;
-    for (int k = 0; k < 9; ++k) t5.k[k] = k < 5 ? P.g10[k] : 0.0f;
-    static const bool kFuseSmooth = [] {  // SFMLOC_AKAZE_FUSE_SMOOTH=0: k_smooth_flow as a launch of its own (comparison runs)
-      const char *e = getenv("SFMLOC_AKAZE_FUSE_SMOOTH");
-      return !(e && atoi(e) == 0);
-    }();
-    const bool fuse_smooth = kFuseSmooth && L.nsteps > 0;
-    if (!fuse_smooth)
-      sfm_launch<SmoothFlowBody>(a, k_smooth_flow, dim3((L.w + 31) / 32, (L.h + 7) / 8), dim3(256), (uint32_t)0, start,
-                         a->d_Lsmooth + L.off, a->d_t2, L.w, L.h, t5, a->d_kcontrast, L.octave);
+    // a single level: its FED steps ping-pong between the level's Lt and a scratch image so that the last launch lands
+    // in Lt without a copy; `start` is never written.  The first launch smooths and computes the conductivity as well.
     const float *cur = start;
-    // destination of step st: alternate so that step nsteps-1 writes Lt; `start` is never written
     const dim3 tgrid((L.w + kNldTileX - 1) / kNldTileX, (L.h + kNldTileY - 1) / kNldTileY);
-    for (int j = 0, st = 0; j < n_launch; ++j) {
-      float *dst = ((n_launch - 1 - j) % 2 == 0) ? Lt : a->d_t3;
-      if (dst == cur) dst = (dst == Lt) ? a->d_t3 : Lt;  // cannot happen by construction; guards an in-place step
-      const int n = std::min(kFuse, L.nsteps - st);
+    for (int j = 0; j < E.n_launch; ++j) {
+      float *dst = launch_writes_lt(E.n_launch, j) ? Lt : (float *)a->d_t3;
+      const int st = j * E.fuse, n = launch_steps(E, L.nsteps, j);
       NldSteps hs;
-      for (int k = 0; k < kNldFuseMax; ++k) hs.half_step[k] = k < n ? 0.5f * L.tsteps[st + k] : 0.0f;
-      if (j == 0 && fuse_smooth) {  // the level's smoothing + conductivity + first steps in one launch
+      for (int k = 0; k < kNldStepSlots; ++k) hs.half_step[k] = k < n ? 0.5f * L.tsteps[st + k] : 0.0f;
 #define SNLD_CASE(KK)                                                                                                  \
   case KK:                                                                                                             \
     sfm_launch<SmoothNldBody<KK>>(a, k_smooth_nld<KK>, tgrid, dim3(256), 0, cur, a->d_Lsmooth + L.off, a->d_t2, dst, L.w, L.h, t5, \
                        a->d_kcontrast, L.octave, hs, n);                                                               \
     break;
-        switch (n) {
-          SNLD_CASE(1) SNLD_CASE(2) SNLD_CASE(3) SNLD_CASE(4) SNLD_CASE(5) SNLD_CASE(6) SNLD_CASE(7) SNLD_CASE(8)
-          SNLD_CASE(9) SNLD_CASE(10) SNLD_CASE(11) SNLD_CASE(12) SNLD_CASE(13) SNLD_CASE(14) SNLD_CASE(15) SNLD_CASE(16)
-        }
-#undef SNLD_CASE
-        st += n;
-        cur = dst;
-        continue;
-      }
 #define NLD_CASE(KK) \
   case KK: sfm_launch<NldStepsBody<KK>>(a, k_nld_steps<KK>, tgrid, dim3(256), 0, cur, a->d_t2, dst, L.w, L.h, hs, n); break;
-      switch (n) {
-        NLD_CASE(1) NLD_CASE(2) NLD_CASE(3) NLD_CASE(4) NLD_CASE(5) NLD_CASE(6) NLD_CASE(7) NLD_CASE(8)
-        NLD_CASE(9) NLD_CASE(10) NLD_CASE(11) NLD_CASE(12) NLD_CASE(13) NLD_CASE(14) NLD_CASE(15) NLD_CASE(16)
+      static_assert(kNldFuseMax == 8, "one case per K up to kNldFuseMax");
+      if (j == 0) {
+        switch (n) { SNLD_CASE(1) SNLD_CASE(2) SNLD_CASE(3) SNLD_CASE(4) SNLD_CASE(5) SNLD_CASE(6) SNLD_CASE(7) SNLD_CASE(8) }
+      } else {
+        switch (n) { NLD_CASE(1) NLD_CASE(2) NLD_CASE(3) NLD_CASE(4) NLD_CASE(5) NLD_CASE(6) NLD_CASE(7) NLD_CASE(8) }
       }
+#undef SNLD_CASE
 #undef NLD_CASE
-      st += n;
       cur = dst;
     }
     AK_HIP(hipGetLastError());
-    if (L.nsteps == 0 && start != Lt)
-      AK_HIP(hipMemcpyAsync(Lt, start, (size_t)L.w * L.h * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
-  const LevelTab T = level_tab(a);
   // (the rows of the levels that were built: levels come in order; kAllPix pixels of a row per thread)
-  const dim3 agrid(((a->w + 127) / 128 + kAllPix - 1) / kAllPix, T.row0[nlev]);
+  const LevelTab T = level_tab(a);
+  const dim3 agrid(((a->w + 127) / 128 + kAllPix - 1) / kAllPix, T.row0[levels_built(P, need)]);
   sfm_launch<ScharrXyAllBody>(a, k_scharr_xy_all, agrid, dim3(128), (uint32_t)0, a->d_Lsmooth, a->d_Lx, a->d_Ly, (const LevelTab *)a->d_level_tab);
   if (with_det)
     sfm_launch<HessianDetAllBody>(a, k_hessian_det_all, agrid, dim3(128), (uint32_t)0, a->d_Lx, a->d_Ly, a->d_Ldet, (const LevelTab *)a->d_level_tab);
   AK_HIP(hipGetLastError());
   return SFMLOC_OK;
-#undef s
 }
 
 // the per-level image pointers and sizes k_orient_describe works on (constant for an extractor: uploaded once)
@@ -2434,10 +2186,10 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
                         sfmloc_akaze **out) {
   SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_akaze_create: null argument");
   *out = nullptr;
-  SFM_CHECK(width >= 16 && height >= 16 && width <= 16384 && height <= kSupMaxRows - 1, SFMLOC_EINVAL,
-            "sfmloc_akaze_create: image size %dx%d (at most 16384 x %d)", width, height, kSupMaxRows - 1);
-  SFM_CHECK(n_octaves >= 1 && n_octaves <= 8 && n_sublevels >= 1 && n_octaves * n_sublevels <= kMaxLevels,
-            SFMLOC_EINVAL, "sfmloc_akaze_create: nOct %d nOctLay %d", n_octaves, n_sublevels);
+  const Request req = check_request(width, height, n_octaves, n_sublevels);
+  SFM_CHECK(req != kRequestSize, SFMLOC_EINVAL, "sfmloc_akaze_create: image size %dx%d (at most %d x %d)", width, height,
+            kMaxWidth, kSupMaxRows - 1);
+  SFM_CHECK(req == kRequestOk, SFMLOC_EINVAL, "sfmloc_akaze_create: nOct %d nOctLay %d", n_octaves, n_sublevels);
   // (the plan is host arithmetic: a schedule the tables cannot hold is refused before anything touches a device)
   AkPlan plan;
   int bad_level = 0, bad_steps = 0;
@@ -2468,7 +2220,6 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
     if (!rc) rc = a->buf.alloc(nullptr, n);  \
   } while (0)
   AK_NEW(d_gray, n0);
-  AK_NEW(d_img, n0);
   AK_NEW(d_t0, n0);
   AK_NEW(d_t1, n0);
   AK_NEW(d_t2, n0);
@@ -2483,18 +2234,15 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   AK_NEW(d_half_steps, (size_t)kMaxLevels * kMaxFedSteps);
   AK_NEW(d_level_tab, 1);
   AK_NEW(d_dev_levels, 1);
-  {
-    const LevelTab T0 = level_tab(a);
-    a->segs_per_row = 2u * (unsigned int)((width + 127) / 128);
-    a->n_seg = (unsigned int)T0.row0[T0.n] * a->segs_per_row;
-  }
-  const size_t cc = a->cand_cap;
+  a->det = detection(a->plan, width, height);
+  a->spec_n = a->det.spec_start;
+  const size_t cc = a->det.cand_cap;
   AK_NEW(d_ncand, 160);
-  AK_NEW(d_seg, (size_t)a->n_seg + 1);
-  AK_NEW(d_seg_part, 1025);
-  if (!rc) he = hipMemset(a->d_seg_part, 0, 1025 * sizeof(unsigned int));
+  AK_NEW(d_seg, (size_t)a->det.n_seg + 1);
+  AK_NEW(d_seg_part, kSegChunksMax + 1);
+  if (!rc) he = hipMemset(a->d_seg_part, 0, (kSegChunksMax + 1) * sizeof(unsigned int));
   if (!rc && he == hipSuccess) he = hipStreamSynchronize(nullptr);  // (null stream: the extractor's streams are not ordered with it)
-  AK_NEW(d_seg_x, (size_t)a->n_seg * kSegMax);
+  AK_NEW(d_seg_x, (size_t)a->det.n_seg * kSegMax);
   AK_NEW(d_cxy, cc);
   AK_NEW(d_clevel, cc);
   AK_NEW(d_cstatus, cc);
@@ -2509,13 +2257,13 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   }
   AK_NEW(d_ckey, cc);
   AK_NEW(d_cslot, cc);
-  if (!rc) rc = ensure_kp_cap(a, a->cand_cap);  // (never regrown by a detection: it finds no more than cand_cap)
+  if (!rc) rc = ensure_kp_cap(a, a->det.cand_cap);  // (never regrown by a detection: it finds no more than cand_cap)
   AK_NEW(d_gauss25, 49);
   AK_NEW(d_win, 64);
   AK_NEW(d_pair, 486 * 2);
 #undef AK_NEW
   if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_counts, 160 * sizeof(unsigned int), hipHostMallocDefault);
-  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_spec, (size_t)Akaze::kSpecMax * (6 * sizeof(float) + 64), hipHostMallocDefault);
+  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_spec, (size_t)a->det.spec_max * (6 * sizeof(float) + 64), hipHostMallocDefault);
   if (!rc && he == hipSuccess) {  // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_suppress),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SuppressLds));
@@ -2600,37 +2348,31 @@ int sfmloc_akaze_suppress_stats(sfmloc_akaze *ak, uint32_t *out9) {
 static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   int rc = build_scale_space(a, gray);
   if (rc) return rc;
-  const LevelTab T = level_tab(a);
-  const dim3 egrid(((a->w + 127) / 128 + kSegPerWave - 1) / kSegPerWave, T.row0[T.n]);  // (kSegPerWave segments per wave)
+  const Detection &D = a->det;
+  const dim3 egrid(((a->w + 127) / 128 + kSegPerWave - 1) / kSegPerWave, D.rows);  // (kSegPerWave segments per wave)
   const LevelTab *dT = (const LevelTab *)a->d_level_tab;
   CandArrays C{a->d_cxy, a->d_clevel, a->d_cresp, a->d_csub};
-  sfm_launch<ExtremaSegBody>(a, k_extrema_seg, egrid, dim3(128), 0, a->d_Ldet, dT, a->thres, a->d_seg_x, a->d_seg, a->segs_per_row);
-  {
-    const unsigned int chunks = (a->n_seg + kSegChunk - 1u) / kSegChunk;
-    if (a->n_seg > 65536u && chunks <= 1024u && a->d_seg_part) {  // a large image: two launches over many compute units
-      sfm_launch<SegSumBody>(a, k_seg_sum, dim3(chunks), dim3(1024), 0, a->d_seg, a->n_seg, a->d_seg_part, a->d_ncand);
-      sfm_launch<SegWriteBody>(a, k_seg_write, dim3(chunks), dim3(1024), 0, a->d_seg, a->n_seg, (const unsigned int *)a->d_seg_part);
-    } else {
-      sfm_launch<SegScanBody>(a, k_seg_scan, dim3(1), dim3(1024), 0, a->d_seg, a->n_seg, a->cand_cap, a->d_ncand);
-    }
+  sfm_launch<ExtremaSegBody>(a, k_extrema_seg, egrid, dim3(128), 0, a->d_Ldet, dT, a->thres, a->d_seg_x, a->d_seg, a->det.segs_per_row);
+  if (D.scan_two_launches) {  // a large image: two launches over many compute units
+    sfm_launch<SegSumBody>(a, k_seg_sum, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg, a->d_seg_part, a->d_ncand);
+    sfm_launch<SegWriteBody>(a, k_seg_write, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg, (const unsigned int *)a->d_seg_part);
+  } else {
+    sfm_launch<SegScanBody>(a, k_seg_scan, dim3(1), dim3(1024), 0, a->d_seg, D.n_seg, D.cand_cap, a->d_ncand);
   }
-  sfm_launch<ExtremaPlaceBody>(a, k_extrema_place, egrid, dim3(128), 0, a->d_Ldet, dT, a->d_seg_x, a->d_seg, a->cand_cap, C,
-                               a->segs_per_row);
-  {  // the neighbour lists: one wave per candidate, a fixed grid that strides over them (their number is on the device)
-    unsigned int ngrid = (unsigned int)((size_t)a->w * a->h / 384);
-    ngrid = ngrid < 256u ? 256u : (ngrid > 4096u ? 4096u : ngrid);
-    sfm_launch<NbrBody>(a, k_suppress_nbr, dim3(ngrid), dim3(256), 0, dT, (const unsigned int *)a->d_seg, a->segs_per_row,
-                        a->cand_cap, (const unsigned int *)a->d_ncand, (const uint32_t *)a->d_cxy, (const uint8_t *)a->d_clevel,
-                        (const float *)a->d_cresp, a->d_nbr, a->d_nbr2, a->d_ncand + 6, a->sup_force_spill);
-  }
+  sfm_launch<ExtremaPlaceBody>(a, k_extrema_place, egrid, dim3(128), 0, a->d_Ldet, dT, a->d_seg_x, a->d_seg, a->det.cand_cap, C,
+                               a->det.segs_per_row);
+  // the neighbour lists: one wave per candidate, a fixed grid that strides over them (their number is on the device)
+  sfm_launch<NbrBody>(a, k_suppress_nbr, dim3(D.nbr_grid), dim3(256), 0, dT, (const unsigned int *)a->d_seg, D.segs_per_row,
+                      D.cand_cap, (const unsigned int *)a->d_ncand, (const uint32_t *)a->d_cxy, (const uint8_t *)a->d_clevel,
+                      (const float *)a->d_cresp, a->d_nbr, a->d_nbr2, a->d_ncand + 6, a->sup_force_spill);
   SuppressArgs S;
   S.T = dT;
   S.nbr = a->d_nbr;
   S.nbr2 = a->d_nbr2;
   S.force_global = a->sup_force_global;
   S.seg_base = a->d_seg;
-  S.segs_per_row = a->segs_per_row;
-  S.cap = a->cand_cap;
+  S.segs_per_row = a->det.segs_per_row;
+  S.cap = a->det.cand_cap;
   S.C = C;
   S.status = a->d_cstatus;
   S.ready = a->d_cready;
@@ -2643,9 +2385,7 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   S.rounds_out = a->d_ncand + 2;
   sfm_launch<SuppressBody>(a, k_suppress, dim3(1), dim3(1024), (uint32_t)sizeof(SuppressLds), S);
   // orientation + M-LDB: a fixed grid that strides over the keypoints (their number is on the device)
-  unsigned int dgrid = (unsigned int)((size_t)a->w * a->h / 96);
-  dgrid = dgrid < 1024u ? 1024u : (dgrid > 16384u ? 16384u : dgrid);
-  sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(dgrid), dim3(64), 0,
+  sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(D.desc_grid), dim3(64), 0,
                                  (const DevLevels *)a->d_dev_levels, a->d_kp, 0, a->d_gauss25, a->d_win,
                                  a->plan.n_win, a->d_pair, a->d_angle, a->d_desc, (const unsigned int *)(a->d_ncand + 1),
                                  (const float *)a->d_resp, a->d_kp6, a->d_qkpt, a->d_qkpt6);
@@ -2661,7 +2401,7 @@ static int akaze_counts_enqueue(Akaze *a, hipStream_t s) {
 }
 static int akaze_outputs_enqueue(Akaze *a, float *kpts, uint8_t *desc64, uint32_t cap, uint32_t *n_out, hipStream_t s) {
   const unsigned int nc = a->h_counts[0], n = a->h_counts[1];
-  SFM_CHECK(nc <= a->cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)", nc, a->cand_cap);
+  SFM_CHECK(nc <= a->det.cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)", nc, a->det.cand_cap);
   *n_out = n;
   SFM_CHECK(n <= cap, SFMLOC_ECAP, "AKAZE: %u keypoints, caller buffers hold %u", n, cap);
   if (n && kpts) SFM_HIP(hipMemcpyAsync(kpts, a->d_kp6, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -2686,7 +2426,7 @@ int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float
   // (speculative: the first spec_n records with the counts -- see Akaze::h_spec)
   const unsigned int spec = a->spec_n < cap ? a->spec_n : cap;
   float *const h_kp = reinterpret_cast<float *>(a->h_spec);
-  uint8_t *const h_desc = a->h_spec + (size_t)Akaze::kSpecMax * 6 * sizeof(float);
+  uint8_t *const h_desc = a->h_spec + (size_t)a->det.spec_max * 6 * sizeof(float);
   if (spec && kpts) SFM_HIP(hipMemcpyAsync(h_kp, a->d_kp6, (size_t)spec * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
   if (spec && desc64) SFM_HIP(hipMemcpyAsync(h_desc, a->d_desc, (size_t)spec * 64, hipMemcpyDeviceToHost, s));
   SFM_HIP(hipStreamSynchronize(s));
@@ -2694,8 +2434,8 @@ int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float
   {
     const unsigned int n = a->h_counts[1];
     unsigned int next = ((n + n / 4 + 255u) / 256u) * 256u;  // a quarter of headroom, in steps of 256
-    a->spec_n = next < 256u ? 256u : (next > Akaze::kSpecMax ? Akaze::kSpecMax : next);
-    if (a->h_counts[0] <= a->cand_cap && n <= cap && n <= spec) {  // everything is here already
+    a->spec_n = next < 256u ? 256u : (next > a->det.spec_max ? a->det.spec_max : next);
+    if (a->h_counts[0] <= a->det.cand_cap && n <= cap && n <= spec) {  // everything is here already
       *n_out = n;
       if (n && kpts) memcpy(kpts, h_kp, (size_t)n * 6 * sizeof(float));
       if (n && desc64) memcpy(desc64, h_desc, (size_t)n * 64);
@@ -2795,8 +2535,8 @@ int sfmloc_akaze_detect_resident_batch(sfmloc_akaze *const *aks, const uint8_t *
   SFM_HIP(hipStreamSynchronize(s0));
   for (uint32_t i = 0; i < n; ++i) {
     Akaze *a = reinterpret_cast<Akaze *>(aks[i]);
-    SFM_CHECK(a->h_counts[0] <= a->cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)",
-              a->h_counts[0], a->cand_cap);
+    SFM_CHECK(a->h_counts[0] <= a->det.cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)",
+              a->h_counts[0], a->det.cand_cap);
     n_out[i] = a->h_counts[1];
   }
   return SFMLOC_OK;

@@ -1,7 +1,9 @@
 // The host side of sfmloc_akaze_create (akaze.hip): everything OpenCV's AKAZE computes once per image size -- the
 // evolution levels (Allocate_Memory_Evolution), each level's Fast Explicit Diffusion cycle (fed_tau_by_process_time) and
-// the constant tables of orientation and M-LDB.  Host code only, no HIP: tests/cpp/akaze_plan.cpp runs it under the host
-// sanitizers and tests/test_akaze_plan.py compares it with the CPU restatement's plan, bit for bit.
+// the constant tables of orientation and M-LDB -- and, below them, the launch schedule: which kernel form every part of an
+// extraction takes, with every threshold.  Host code only, no HIP: tests/cpp/akaze_plan.cpp runs it under the host
+// sanitizers, tests/test_akaze_plan.py compares the plan with the CPU restatement's, bit for bit, and
+// tests/test_akaze_cases_cpu.py the schedule with what every boundary case promises.
 #pragma once
 
 #include <math.h>
@@ -90,8 +92,9 @@ inline void gaussian_kernel(int ksize, float sigma, float *cf) {  // cv::getGaus
   for (int i = 0; i < ksize; ++i) cf[i] = (float)(cf[i] * sum);
 }
 
-// Allocate_Memory_Evolution + FED schedule + constant tables.  -> true; or false when a level's FED cycle is longer than
-// kMaxFedSteps, with that level in *bad_level and its step count in *bad_steps (the plan is then not to be used).
+// Allocate_Memory_Evolution + FED schedule + constant tables.  -> true; or false when an evolved level's FED cycle is
+// longer than kMaxFedSteps or has no step at all (the launch schedule below has no form for either), with that level in
+// *bad_level and its step count in *bad_steps (the plan is then not to be used).
 inline bool make_plan(int w, int h, int omax, int nsub, AkPlan &P, int *bad_level, int *bad_steps) {
   const float soffset = 1.6f, derivative_factor = 1.5f;
   P.nlev = 0;
@@ -116,7 +119,7 @@ inline bool make_plan(int w, int h, int omax, int nsub, AkPlan &P, int *bad_leve
   }
   for (int i = 1; i < P.nlev; ++i) {
     P.lev[i].nsteps = fed_tau(P.lev[i].etime - P.lev[i - 1].etime, 0.25f, P.lev[i].tsteps);
-    if (P.lev[i].nsteps > kMaxFedSteps) {
+    if (P.lev[i].nsteps > kMaxFedSteps || P.lev[i].nsteps < 1) {
       *bad_level = i;
       *bad_steps = P.lev[i].nsteps;
       return false;
@@ -144,6 +147,133 @@ inline bool make_plan(int w, int h, int omax, int nsub, AkPlan &P, int *bad_leve
     cell0 += counts[lvl];
   }
   return true;
+}
+
+// ---- the launch schedule ------------------------------------------------------------------------------------------
+// Which kernel form every part of an extraction takes, as pure functions of the plan and of the number of levels a call
+// builds.  akaze.hip launches what these say and sizes its buffers from them; every threshold is a named constant here
+// and nowhere else.  tests/cpp/akaze_plan.cpp prints the schedule, and tests/test_akaze_cases_cpu.py holds it against the
+// restatement of these conditions in tests/akaze_cases.py, so that a boundary case stays on its boundary.
+
+// -- what sfmloc_akaze_create accepts
+constexpr int kMinSide = 16;           // width and height from this ...
+constexpr int kMaxWidth = 16384;       // ... to this width (the x a candidate's packed word holds)
+constexpr int kSupMaxRows = 4096 + 1;  // level rows the row-start tables of k_suppress hold: height <= kSupMaxRows - 1
+constexpr int kMaxOctaves = 8;
+enum Request { kRequestOk = 0, kRequestSize, kRequestOctaves };
+inline Request check_request(int w, int h, int omax, int nsub) {
+  if (w < kMinSide || h < kMinSide || w > kMaxWidth || h > kSupMaxRows - 1) return kRequestSize;
+  if (omax < 1 || omax > kMaxOctaves || nsub < 1 || omax * nsub > kMaxLevels) return kRequestOctaves;
+  return kRequestOk;
+}
+
+// the levels [0, levels_built) are built by a call that needs `need` of them (0: all; a description-only call asks for
+// the levels up to its keypoints' highest)
+inline int levels_built(const AkPlan &P, int need) { return (need > 0 && need < P.nlev) ? need : P.nlev; }
+
+// -- the start: the contrast factor's kernels walk kGradRows image rows per workgroup; the histogram's grid is clamped to
+// about kHistGridMax workgroups (each ends in atomics on the same 301 words) by giving a workgroup several such chunks
+constexpr int kGradRows = 16;
+constexpr unsigned int kHistGridMax = 256;
+
+// -- evolution: the loop over the levels 1 .. levels_built - 1 goes in steps, each a resident run or a single level
+constexpr unsigned int kResidentLdsBytes = 150u * 1024u;  // k_octave_resident: three float images of the octave in LDS
+constexpr int kOctaveRunMax = 8;                          // levels of one octave k_octave_resident evolves in a launch
+// diffusion steps per launch of k_smooth_nld / k_nld_steps: 4 on the large levels, where the tile halo's redundant work
+// costs more than a launch; 8 on the upper octaves (<= 160 wide), whose steps are each far shorter than a launch boundary
+// and which hold most of the schedule's steps (133 of 165 at VGA).  (The 240 x 135 octave of a 1080p frame was tried with
+// the small levels' count: no effect, 1.10 / 1.23 ms either way.)
+constexpr int kNldStepsLarge = 4, kNldStepsSmall = 8;
+constexpr int kNldSmallWidth = 160;
+constexpr int kNldFuseMax = 8;  // the largest K the step kernels are instantiated for
+static_assert(kNldStepsLarge <= kNldFuseMax && kNldStepsSmall <= kNldFuseMax, "a launch with no kernel instantiated for it");
+
+enum Source { kPrevLt, kOwnLt, kScratch };  // the previous level's Lt; this level's Lt; the scratch image
+struct EvoStep {
+  bool resident;     // levels first .. last of one octave in one k_octave_resident launch; else: the level `first` alone
+  bool halfsample;   // `first` opens its octave: the previous level's Lt is half-sampled into `source` first
+  int first, last;
+  Source source;     // what the step's first launch reads
+  // a single level: its FED cycle in n_launch launches of up to `fuse` steps, the first k_smooth_nld, the others
+  // k_nld_steps, ping-ponging between the level's Lt and the scratch image
+  int fuse, n_launch;
+};
+// launch j of n_launch writes the level's Lt (else the scratch image): alternating, so that the last one writes Lt.  The
+// half-sampled start lands where launch 0 does not write (evolution() below); any other start is another level's Lt.
+inline bool launch_writes_lt(int n_launch, int j) { return (n_launch - 1 - j) % 2 == 0; }
+inline int launch_steps(const EvoStep &E, int nsteps, int j) {
+  const int left = nsteps - j * E.fuse;
+  return left < E.fuse ? left : E.fuse;
+}
+
+// -> the number of steps, steps[0 .. n) filled (at most kMaxLevels - 1)
+inline int evolution(const AkPlan &P, int need, EvoStep *steps) {
+  const int nlev = levels_built(P, need);
+  int n = 0;
+  for (int i = 1; i < nlev; ++i) {
+    const AkLevel &L = P.lev[i], &Lp = P.lev[i - 1];
+    EvoStep &E = steps[n++];
+    E = EvoStep{};
+    E.first = E.last = i;
+    E.halfsample = L.octave > Lp.octave;
+    // an octave whose image fits in LDS three times runs in one launch, from its first level of the loop to the last
+    // level of it that is built, if that run is short enough
+    int j = i;
+    while (j + 1 < nlev && P.lev[j + 1].octave == L.octave) ++j;
+    const bool opens = i == 1 || Lp.octave != L.octave;
+    if (opens && (size_t)3 * L.w * L.h * sizeof(float) <= kResidentLdsBytes && j - i + 1 <= kOctaveRunMax) {
+      E.resident = true;
+      E.last = j;
+      E.source = E.halfsample ? kScratch : kPrevLt;
+      i = j;
+      continue;
+    }
+    E.fuse = L.w <= kNldSmallWidth ? kNldStepsSmall : kNldStepsLarge;
+    E.n_launch = (L.nsteps + E.fuse - 1) / E.fuse;
+    E.source = !E.halfsample ? kPrevLt : (launch_writes_lt(E.n_launch, 0) ? kScratch : kOwnLt);
+  }
+  return n;
+}
+
+// -- detection and its buffers: functions of the frame's size and the plan alone
+constexpr int kSegPx = 64;                         // a segment = what one wave of the extrema kernels covers
+constexpr unsigned int kSegChunk = 4096;           // segments one workgroup of k_seg_sum / k_seg_write scans
+constexpr unsigned int kSegScanOneLaunch = 65536;  // n_seg up to this: k_seg_scan, one workgroup; above, the two kernels
+constexpr unsigned int kSegChunksMax = 1024;       // ... if their chunks fit the partial sums' array
+constexpr unsigned int kCandCap = 1u << 16;        // extrema candidates the workspace holds
+constexpr unsigned int kSpecStart = 512, kSpecMax = 4096;  // the speculative download: records at first, at most
+// the fixed grids that stride over candidates / keypoints whose number is on the device: a workgroup per so many pixels
+constexpr unsigned int kNbrPixPerGroup = 384, kNbrGridMin = 256, kNbrGridMax = 4096;
+constexpr unsigned int kDescPixPerGroup = 96, kDescGridMin = 1024, kDescGridMax = 16384;
+
+struct Detection {
+  unsigned int rows;                   // rows of all levels, one under the other
+  unsigned int segs_per_row, n_seg;    // segments per row of the FRAME's width, for every row of every level
+  unsigned int seg_chunks;
+  bool scan_two_launches;              // k_seg_sum + k_seg_write instead of k_seg_scan
+  unsigned int hist_grid_x, grad_grid_y, hist_grid_y;  // k_pre_grad (x, grad y), k_pre_hist (x, hist y: clamped)
+  unsigned int nbr_grid, desc_grid;    // k_suppress_nbr, k_orient_describe
+  unsigned int cand_cap, spec_start, spec_max;
+};
+inline unsigned int clamp_u(size_t v, unsigned int lo, unsigned int hi) {
+  return v < lo ? lo : (v > hi ? hi : (unsigned int)v);
+}
+inline Detection detection(const AkPlan &P, int w, int h) {
+  Detection D{};
+  for (int i = 0; i < P.nlev; ++i) D.rows += (unsigned int)P.lev[i].h;
+  D.segs_per_row = (unsigned int)(128 / kSegPx) * (unsigned int)((w + 127) / 128);
+  D.n_seg = D.rows * D.segs_per_row;
+  D.seg_chunks = (D.n_seg + kSegChunk - 1u) / kSegChunk;
+  D.scan_two_launches = D.n_seg > kSegScanOneLaunch && D.seg_chunks <= kSegChunksMax;
+  D.hist_grid_x = (unsigned int)((w + 127) / 128);
+  D.grad_grid_y = D.hist_grid_y = (unsigned int)((h + kGradRows - 1) / kGradRows);
+  if (D.hist_grid_x * D.hist_grid_y > kHistGridMax) D.hist_grid_y = clamp_u(kHistGridMax / D.hist_grid_x, 1u, kHistGridMax);
+  D.nbr_grid = clamp_u((size_t)w * h / kNbrPixPerGroup, kNbrGridMin, kNbrGridMax);
+  D.desc_grid = clamp_u((size_t)w * h / kDescPixPerGroup, kDescGridMin, kDescGridMax);
+  D.cand_cap = kCandCap;
+  D.spec_start = kSpecStart;
+  D.spec_max = kSpecMax;
+  return D;
 }
 
 }  // namespace akaze_plan

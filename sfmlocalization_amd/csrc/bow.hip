@@ -616,8 +616,7 @@ int launch_bof(const BofModel *b, hipStream_t s, const float *d_desc, const floa
   SFM_HIP(hipMemsetAsync(d_counts, 0, (size_t)b->K * cells * sizeof(uint32_t), s));
   if (n > 0) {
     const size_t lds = BofTileLds::floats(b->in_dim, b->n_pca, b->cdim, b->K) * sizeof(float);
-    static const bool tiled_ok = [] { const char *e = getenv("SFMLOC_BOF_TILED"); return !(e && atoi(e) == 0); }();
-    if (tiled_ok && lds <= 60 * 1024) {  // the model fits the LDS layout (the reference's does: 45 KB)
+    if (lds <= 60 * 1024) {  // the model fits the LDS layout (the reference's does: 45 KB)
       hipLaunchKernelGGL(k_bof_assign_tiled, dim3((n + kBofTile - 1) / kBofTile), dim3(256), lds, s, d_desc, d_kxy, n,
                          b->in_dim, b->d_pca_mean, b->d_pca_evec, b->d_pca_eval, b->n_pca, b->d_centers, b->K, b->resized,
                          b->levels, d_counts, d_desc8);

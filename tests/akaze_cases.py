@@ -4,9 +4,11 @@ the largest and smallest frames sfmloc_akaze_create accepts, the segment scan at
 output paths around their keypoint counts.  No device here: the cases are inputs, what each is for is asserted with the
 CPU restatement alone in test_akaze_cases_cpu.py, and test_gpu_akaze_shapes.py runs them on the device.
 
-The form conditions below restate akaze.hip (build_scale_space, akaze_detect_enqueue, sfmloc_akaze_detect_and_compute)
-over the level sizes the RESTATEMENT plans (oracle_c.akaze_levels): a case stays on its side of a boundary whatever the
-library does."""
+The form conditions below restate the launch schedule of csrc/akaze_plan.h (what build_scale_space, akaze_detect_enqueue
+and sfmloc_akaze_detect_and_compute launch by) over the level sizes the RESTATEMENT plans (oracle_c.akaze_levels): a case
+stays on its side of a boundary whatever the library does.  They are the independent side: test_akaze_cases_cpu.py holds
+these constants and conditions against the header's own (tests/cpp/akaze_plan.cpp prints them), so that a threshold
+moved in the header alone turns the cases red instead of leaving them green off their boundary."""
 from collections import namedtuple
 
 import numpy as np
@@ -17,7 +19,18 @@ RUN_MAX = 8                       # kOctaveRunMax: levels one k_octave_resident 
 MAX_LEVELS = 32                   # kMaxLevels
 SCAN_ONE_LAUNCH = 65536           # akaze_detect_enqueue: n_seg above this takes k_seg_sum + k_seg_write
 SPEC_START, SPEC_MAX = 512, 4096  # Akaze::spec_n at creation, kSpecMax
-CAND_CAP = 65536                  # Akaze::cand_cap
+CAND_CAP = 65536                  # kCandCap
+STEPS_LARGE, STEPS_SMALL, SMALL_WIDTH = 4, 8, 160  # FED steps per launch of a level evolved by the per-level kernels
+NBR_GRID = (384, 256, 4096)       # k_suppress_nbr: a workgroup per so many pixels, at least, at most
+DESC_GRID = (96, 1024, 16384)     # k_orient_describe in a detection: the same
+MIN_SIDE, MAX_W, MAX_H, MAX_OCTAVES = 16, 16384, 4096, 8  # what sfmloc_akaze_create accepts
+# the constants above by the names csrc/akaze_plan.h gives them (test_akaze_cases_cpu.py: equal)
+HEADER_NAMES = dict(kResidentLdsBytes=LDS_BYTES, kOctaveRunMax=RUN_MAX, kMaxLevels=MAX_LEVELS,
+                    kSegScanOneLaunch=SCAN_ONE_LAUNCH, kSpecStart=SPEC_START, kSpecMax=SPEC_MAX, kCandCap=CAND_CAP,
+                    kNldStepsLarge=STEPS_LARGE, kNldStepsSmall=STEPS_SMALL, kNldSmallWidth=SMALL_WIDTH,
+                    kNbrPixPerGroup=NBR_GRID[0], kNbrGridMin=NBR_GRID[1], kNbrGridMax=NBR_GRID[2],
+                    kDescPixPerGroup=DESC_GRID[0], kDescGridMin=DESC_GRID[1], kDescGridMax=DESC_GRID[2],
+                    kMinSide=MIN_SIDE, kMaxWidth=MAX_W, kSupMaxRows=MAX_H + 1, kMaxOctaves=MAX_OCTAVES)
 
 
 def blocks(seed, w, h, block=5, lo=30, hi=225):
@@ -169,14 +182,31 @@ def octaves(levels):
     return out
 
 
-def resident_plan(levels):
+def resident_plan(levels, need=None):
     """-> per octave (run, resident): the levels the evolution loop builds in it (octave 0: all but level 0, which the
-    Gaussian gives) and whether build_scale_space hands them to k_octave_resident in one launch"""
+    Gaussian gives) and whether build_scale_space hands them to k_octave_resident in one launch.  need: only the levels
+    [0, need) are built (a description-only call whose keypoints stop at level need - 1)"""
     out = []
-    for i, (w, h, n) in enumerate(octaves(levels)):
+    for i, (w, h, n) in enumerate(octaves(levels[:need])):
         run = n - 1 if i == 0 else n
         out.append((run, run >= 1 and 3 * w * h * 4 <= LDS_BYTES and run <= RUN_MAX))
     return out
+
+
+def fixed_grid(w, h, grid):
+    """the workgroups of a kernel that strides over candidates / keypoints whose number only the device knows"""
+    per, lo, hi = grid
+    return min(max(w * h // per, lo), hi)
+
+
+# ---- the description-only path cut short: the schedule's second input is the number of levels a call builds, and a run
+# cut short can change form.  (name, frame, octave settings, levels the cut call builds, resident_plan of the cut call
+# and of the whole one); test_gpu_akaze_shapes.py describes dense_keypoints on one extractor, cut short and whole.
+NeedCase = namedtuple("NeedCase", "name w h n_octaves n_sublevels need cut whole")
+NEED_CASES = [
+    NeedCase("160x80_levels0-5", 160, 80, 4, 4, 6, [(3, True), (2, True)], [(3, True), (4, True)]),
+    NeedCase("128x100_o1s10_levels0-8", 128, 100, 1, 10, 9, [(8, True)], [(9, False)]),
+]
 
 
 def n_seg(levels, w):

@@ -2,11 +2,14 @@
 in runs of what length, the side of the segment scan's one-launch limit, the side of the output paths' keypoint counts,
 keypoints at the far edge -- by the CPU restatement alone (oracle_c.akaze_levels / akaze_detect_and_compute).  These are
 conditions on the inputs, not measurements of the library: test_gpu_akaze_shapes.py runs the same cases on the device,
-and a case that drifted off its boundary would leave a kernel form untested with everything green."""
+and a case that drifted off its boundary would leave a kernel form untested with everything green.  The conditions are
+restated in akaze_cases.py; the library's own are in csrc/akaze_plan.h, and a host program over that header
+(akaze_header.py) says here that both put every case on the same side, with the same constants."""
 import numpy as np
 import pytest
 
 import akaze_cases as A
+import akaze_header as H
 
 
 def detect(oracle_c, c):
@@ -31,6 +34,87 @@ def test_case_is_what_it_is_for(oracle_c, c):
         assert (kp[:, 0] >= c.w - 64).any(), float(kp[:, 0].max())
     if len(kp):  # every level the plan has is a level a keypoint can name
         assert 0 <= kp[:, 5].min() and kp[:, 5].max() < c.levels
+
+
+@pytest.fixture(scope="module")
+def header(tmp_path_factory):
+    """-> (the constants of csrc/akaze_plan.h, {request: its plan and launch schedule by that header})"""
+    reqs = [(c.w, c.h, c.n_octaves, c.n_sublevels) for c in A.CASES + A.NEED_CASES]
+    return H.run(H.build(tmp_path_factory.mktemp("akaze_schedule")), list(dict.fromkeys(reqs)))
+
+
+def header_resident_plan(plan, need):
+    """the header's evolution steps of a call that builds `need` levels -> per octave (run, resident), as
+    A.resident_plan gives it; on the way: the steps cover the loop's levels 1 .. need - 1 once and in order, a run stays in
+    its octave, and a single level's launches never run in place and end in the level's Lt"""
+    built, steps = plan.evo[need]
+    assert built == need
+    octave = [ints[2] for ints, _ in plan.levels[:need]]
+    out = [[0, False] for _ in range(octave[-1] + 1)]
+    nxt = 1
+    for s in steps:
+        assert s.first == nxt and s.last >= s.first and len(set(octave[s.first:s.last + 1])) == 1
+        nxt = s.last + 1
+        assert s.halfsample == (octave[s.first] > octave[s.first - 1])
+        o = out[octave[s.first]]
+        o[0] += s.last - s.first + 1
+        w, nsteps = plan.levels[s.first][0][0], plan.levels[s.first][0][5]
+        if s.resident:
+            assert o[0] == s.last - s.first + 1 and s.source == ("scratch" if s.halfsample else "prev")
+            o[1] = True
+        else:
+            assert s.first == s.last and not o[1]
+            assert s.fuse == (A.STEPS_SMALL if w <= A.SMALL_WIDTH else A.STEPS_LARGE)
+            assert s.n_launch == -(-nsteps // s.fuse) >= 1
+            assert (s.source == "prev") == (not s.halfsample)
+            cur = s.source
+            for j in range(s.n_launch):  # build_scale_space: launch j writes Lt when an even number of launches follow
+                dst = "own" if (s.n_launch - 1 - j) % 2 == 0 else "scratch"
+                assert dst != cur
+                cur = dst
+            assert cur == "own"
+    assert nxt == need
+    return [tuple(o) for o in out]
+
+
+@pytest.mark.parametrize("c", A.CASES, ids=lambda c: c.name)
+def test_header_schedules_what_the_case_promises(header, c):
+    """the launch schedule the LIBRARY goes by (csrc/akaze_plan.h) puts the case where akaze_cases.py's restatement of it
+    does: resident runs per octave, the side of the segment scan, the fixed grids"""
+    constants, plans = header
+    plan = plans[(c.w, c.h, c.n_octaves, c.n_sublevels)]
+    assert plan.kind == "plan" and len(plan.levels) == c.levels
+    assert header_resident_plan(plan, c.levels) == c.resident, c.what
+    d = plan.detect
+    assert d.n_seg == A.n_seg([ints[:2] for ints, _ in plan.levels], c.w) == d.rows * d.segs_per_row
+    assert {"<": d.n_seg < constants["kSegScanOneLaunch"], "==": d.n_seg == constants["kSegScanOneLaunch"],
+            ">": d.n_seg > constants["kSegScanOneLaunch"]}[c.seg], d.n_seg
+    assert d.scan_two_launches == (c.seg == ">") and d.seg_chunks * constants["kSegChunk"] >= d.n_seg
+    assert d.seg_chunks <= constants["kSegChunksMax"]
+    assert (d.nbr_grid, d.desc_grid) == (A.fixed_grid(c.w, c.h, A.NBR_GRID), A.fixed_grid(c.w, c.h, A.DESC_GRID))
+    assert (d.cand_cap, d.spec_start, d.spec_max) == (A.CAND_CAP, A.SPEC_START, A.SPEC_MAX)
+    assert 1 <= d.hist_grid_y <= d.grad_grid_y == -(-c.h // constants["kGradRows"])
+    assert d.hist_grid_y == 1 or d.hist_grid_x * d.hist_grid_y <= constants["kHistGridMax"]
+
+
+def test_constants_equal_the_headers(header):
+    """akaze_cases.py restates the thresholds by hand; csrc/akaze_plan.h is where the library has them"""
+    constants = header[0]
+    assert {k: constants[k] for k in A.HEADER_NAMES} == A.HEADER_NAMES
+
+
+@pytest.mark.parametrize("n", A.NEED_CASES, ids=lambda n: n.name)
+def test_need_cases_change_the_run(oracle_c, header, n):
+    """a description-only call that stops below the plan's top level: the last octave's run is shorter, and at 128 x 100
+    with ten sub-levels that moves it from the per-level kernels into LDS -- by the restatement and by the header"""
+    levels = oracle_c.akaze_levels(n.w, n.h, n.n_octaves, n.n_sublevels)
+    plan = header[1][(n.w, n.h, n.n_octaves, n.n_sublevels)]
+    assert n.need < len(levels) == len(plan.levels) and n.cut != n.whole
+    assert A.resident_plan(levels, n.need) == header_resident_plan(plan, n.need) == n.cut
+    assert A.resident_plan(levels) == header_resident_plan(plan, len(levels)) == n.whole
+    kin = A.dense_keypoints(levels, n.w, n.h)
+    per_level = np.bincount(kin[:, 3].astype(int))
+    assert len(per_level) == len(levels) and 100 <= per_level.min() and per_level.max() <= 1000
 
 
 def test_table_covers_the_boundaries():

@@ -6,16 +6,11 @@ sizes, octave, sub-level, sigma_size, nsteps and the bits of every step time.  A
 A FED cycle of more than 64 steps does not fit the plan's tables (nor the device's): both sides refuse such a request
 and name the level.  A cycle of ONE step (sub-level counts from about 11 up) has nothing to reorder: both sides take the
 step as it is (OpenCV's reordering reads in front of its array there)."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import akaze_cases as A
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import akaze_header as H
 
 REFUSED = [(2560, 1280, 6, 4), (2560, 1280, 6, 1), (5120, 2560, 7, 4)]
 ACCEPTED = (
@@ -35,36 +30,15 @@ GRID = list(dict.fromkeys(ACCEPTED + REFUSED))
 
 @pytest.fixture(scope="module")
 def header_plans(tmp_path_factory):
-    """-> {(w, h, n_octaves, n_sublevels): ("plan", total, [level rows]) or ("refused", level, steps)}"""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.fail("no host C++ compiler (g++ / c++) to build tests/cpp/akaze_plan.cpp")
-    exe = str(tmp_path_factory.mktemp("akaze_plan") / "akaze_plan")
-    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "cpp", "akaze_plan.cpp")],
-                   check=True, timeout=300)
-    r = subprocess.run([exe] + [str(v) for q in GRID for v in q], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    plans, cur = {}, None
-    for line in r.stdout.splitlines():
-        f = line.split()
-        if f[0] == "plan":
-            cur = ("plan", int(f[6]), [])
-            plans[tuple(int(v) for v in f[1:5])] = cur
-            assert int(f[5]) >= 1
-        elif f[0] == "refused":
-            plans[tuple(int(v) for v in f[1:5])] = ("refused", int(f[5]), int(f[6]))
-        else:
-            assert f[0] == "level" and int(f[1]) == len(cur[2])
-            cur[2].append(([int(v) for v in f[2:9]], np.array([int(v, 16) for v in f[9:]], np.uint32)))
-    assert set(plans) == set(GRID)
-    return plans
+    """-> {(w, h, n_octaves, n_sublevels): akaze_header.Plan or akaze_header.Refused}"""
+    return H.run(H.build(tmp_path_factory.mktemp("akaze_plan")), GRID)[1]
 
 
 @pytest.mark.parametrize("req", ACCEPTED, ids=lambda q: "%dx%d-o%d-s%d" % q)
 def test_plan_equals_the_restatements(oracle_c, header_plans, req):
     w, h, omax, nsub = req
     lev, ts = oracle_c.akaze_plan(w, h, omax, nsub)
-    kind, total, levels = header_plans[req]
+    kind, total, levels = header_plans[req][:3]
     assert kind == "plan"
     assert len(levels) == len(lev) <= A.MAX_LEVELS
     off = 0
@@ -111,7 +85,7 @@ def test_long_fed_cycles_are_refused_by_both(oracle_c, header_plans, req):
 
 
 def test_57_steps_are_accepted(oracle_c, header_plans):
-    kind, _, levels = header_plans[(2560, 1280, 5, 4)]
+    kind, _, levels = header_plans[(2560, 1280, 5, 4)][:3]
     assert kind == "plan" and max(ints[5] for ints, _ in levels) == 57
     assert int(oracle_c.akaze_plan(2560, 1280, 5, 4)[0][:, 5].max()) == 57
 

@@ -126,6 +126,29 @@ def test_dense_compute_with_other_octave_settings(oracle_c):
         ak.close()
 
 
+@pytest.mark.parametrize("n", A.NEED_CASES, ids=lambda n: n.name)
+def test_dense_compute_cut_short_and_whole(oracle_c, n):
+    """a description-only call builds no level above its keypoints' highest, and an octave's run cut short can change form
+    (test_akaze_cases_cpu.py::test_need_cases_change_the_run: a resident run of 2 instead of 4; a resident run of 8
+    instead of nine levels by the per-level kernels): one extractor, first cut short, then whole -- the restatement's
+    angles and descriptors both times"""
+    g = A.blocks(9, n.w, n.h, 5)
+    ak = S.Akaze(n.w, n.h, n_octaves=n.n_octaves, n_sublevels=n.n_sublevels)
+    try:
+        kin = A.dense_keypoints(ak.levels, n.w, n.h)
+        edesc, eang = oracle_c.akaze_compute(g, kin, omax=n.n_octaves, nsub=n.n_sublevels)
+        assert n.need < len(ak.levels) and len(np.unique(eang)) > 100
+        for top in (n.need, len(ak.levels)):
+            sel = kin[:, 3] < top
+            assert sorted(set(kin[sel, 3].astype(int))) == list(range(top))
+            desc, ang = ak.compute(g, kin[sel])
+            np.testing.assert_array_equal(bits32(ang), bits32(eang[sel]), err_msg=f"levels 0 .. {top - 1}")
+            np.testing.assert_array_equal(desc[:, :61], edesc[sel], err_msg=f"levels 0 .. {top - 1}")
+            assert (desc[:, 61:] == 0).all()
+    finally:
+        ak.close()
+
+
 def test_long_fed_schedule_is_refused():
     """a level whose FED cycle has more than 64 steps does not fit the plan's tables (nor the device's): refused at
     creation, with the level and its step count in the text; 57 steps are fine"""

@@ -187,14 +187,14 @@ def _create_walk(create, at_least):
 
 
 def test_akaze_create_leaves_no_handle():
-    """sfmloc_akaze_create at 64 x 64: 33 arrays and the seven per-keypoint ones (akaze.hip): 40"""
+    """sfmloc_akaze_create at 64 x 64: 32 arrays and the seven per-keypoint ones (akaze.hip): 39"""
     L = S._L()
     gray = np.random.default_rng(2).integers(0, 256, (64, 64), dtype=np.uint8)
     gray[16:48, 16:48] //= 4
     fresh = S.Akaze(64, 64)
     ref = fresh.detect_and_compute(gray)
     fresh.close()
-    h = _create_walk(lambda out: L.sfmloc_akaze_create(0, 64, 64, 4, 4, C.c_float(0.001), out), 40)
+    h = _create_walk(lambda out: L.sfmloc_akaze_create(0, 64, 64, 4, 4, C.c_float(0.001), out), 39)
     ak = S.Akaze.__new__(S.Akaze)
     ak._h, ak.width, ak.height = h, 64, 64
     same(ak.detect_and_compute(gray), ref)
@@ -202,8 +202,8 @@ def test_akaze_create_leaves_no_handle():
 
 
 def test_imgbow_create_leaves_no_handle():
-    """sfmloc_imgbow_create at 64 x 64 without a PCA: the model's 3 arrays, the extractor's 40, the resize plan's 5 and
-    its own 6: 54"""
+    """sfmloc_imgbow_create at 64 x 64 without a PCA: the model's 3 arrays, the extractor's 39, the resize plan's 5 and
+    its own 6: 53"""
     L = S._L()
     rng = np.random.default_rng(4)
     centers = rng.uniform(0, 255, (8, 61)).astype(np.float32)
@@ -212,7 +212,7 @@ def test_imgbow_create_leaves_no_handle():
     ref = fresh.compute(img)
     fresh.close()
     d, keep = S._bof_desc(centers, 61)
-    h = _create_walk(lambda out: L.sfmloc_imgbow_create(C.byref(d), 0, 64, 64, 3, out), 54)
+    h = _create_walk(lambda out: L.sfmloc_imgbow_create(C.byref(d), 0, 64, 64, 3, out), 53)
     ib = S.ImgBow.__new__(S.ImgBow)
     ib._h, ib.width, ib.height, ib.channels = h, 64, 64, 3
     ib.dim = int(L.sfmloc_imgbow_dim(h))
