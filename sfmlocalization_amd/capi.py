@@ -5,12 +5,17 @@ import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
 
-NOMATCH = 0xFFFFFFFF
-K_HAMMING, K_COMPACT, K_FMATRIX, K_MATCHSET, K_P3P, K_BOW, K_COUNT = 0, 1, 2, 3, 4, 5, 8
-
-OK, EINVAL, ENODEV, EHIP, EIO, ECAP, ENOMEM = 0, -1, -2, -3, -4, -5, -6
+NOMATCH, COLOR_CHUNK = _abi.constants("NOMATCH", "COLOR_CHUNK")
+K_HAMMING, K_COMPACT, K_FMATRIX, K_MATCHSET, K_P3P, K_BOW, K_COUNT = _abi.constants(
+    "K_HAMMING", "K_COMPACT", "K_FMATRIX", "K_MATCHSET", "K_P3P", "K_BOW", "K_COUNT")
+OK, EINVAL, ENODEV, EHIP, EIO, ECAP, ENOMEM = _abi.constants("OK", "EINVAL", "ENODEV", "EHIP", "EIO", "ECAP", "ENOMEM")
+BA_ROTATION, BA_TRANSLATION, BA_INTRINSICS, BA_STRUCTURE = _abi.constants(
+    "BA_ROTATION", "BA_TRANSLATION", "BA_INTRINSICS", "BA_STRUCTURE")
+TRI_ROBUST, TRI_BLIND = _abi.constants("TRI_ROBUST", "TRI_BLIND")
+MERGE_SIMILARITY, MERGE_AFFINE = _abi.constants("MERGE_SIMILARITY", "MERGE_AFFINE")
+MERGE_MODELS = {"similarity": MERGE_SIMILARITY, "affine": MERGE_AFFINE}
 
 
 class SfmlocError(RuntimeError):
@@ -20,195 +25,29 @@ class SfmlocError(RuntimeError):
         self.message = msg  # the library's text alone (sfmloc_last_error)
 
 
-class Params(C.Structure):
-    _fields_ = [
-        ("dist_ratio", C.c_float),
-        ("ransac_round", C.c_int),
-        ("geom_precision", C.c_double),
-        ("bow_knn", C.c_int),
-        ("min_putative", C.c_int),
-        ("min_resection_points", C.c_int),
-        ("min_inliers", C.c_int),
-        ("p3p_max_iteration", C.c_int),
-        ("seed", C.c_uint64),
-        ("refine_pose", C.c_int),
-        ("device", C.c_int),
-        ("profile", C.c_int),
-        ("exact_rows", C.c_int),
-        ("guided_matching", C.c_int),
-        ("k1_mfma", C.c_int),  # 1 = view-list scans on the matrix cores (default), 0 = the popcount form; same matches
-    ]
+# the structs of include/sfmloc.h, fields by the header's names
+Params = _abi.struct("sfmloc_params")
+MapDesc = _abi.struct("sfmloc_map_desc")
+MapInfo = _abi.struct("sfmloc_map_info")
+Pose = _abi.struct("sfmloc_pose")
+BofDesc = _abi.struct("sfmloc_bof_desc")
+ScanInfo = _abi.struct("sfmloc_scan_info")
+SfmDesc = _abi.struct("sfmloc_sfm_desc")
+SfmViewResult = _abi.struct("sfmloc_sfm_view_result")
+BaReport = _abi.struct("sfmloc_ba_report")
+BaJointOptions = _abi.struct("sfmloc_ba_joint_options")
+BaJointReport = _abi.struct("sfmloc_ba_joint_report")
+TriangulateOptions = _abi.struct("sfmloc_triangulate_options")
+TriangulateReport = _abi.struct("sfmloc_triangulate_report")
+RelposeOptions = _abi.struct("sfmloc_relpose_options")
+RelposeResult = _abi.struct("sfmloc_relpose_result")
+MergeParams = _abi.struct("sfmloc_merge_params")
+MergeResult = _abi.struct("sfmloc_merge_result")
+ReduceResult = _abi.struct("sfmloc_reduce_result")
+KernelStats = _abi.struct("sfmloc_kernel_stats")
 
-
-class MapDesc(C.Structure):
-    _fields_ = [
-        ("n_views", C.c_uint32),
-        ("view_id", C.POINTER(C.c_uint32)),
-        ("view_off", C.POINTER(C.c_uint32)),
-        ("view_wh", C.POINTER(C.c_uint32)),
-        ("n_rows", C.c_uint64),
-        ("desc", C.POINTER(C.c_uint8)),
-        ("kpt_xy", C.POINTER(C.c_float)),
-        ("row_landmark", C.POINTER(C.c_int32)),
-        ("n_landmarks", C.c_uint32),
-        ("landmark_id", C.POINTER(C.c_uint32)),
-        ("landmark_X", C.POINTER(C.c_double)),
-        ("focal", C.c_double), ("ppx", C.c_double), ("ppy", C.c_double),
-        ("k1", C.c_double), ("k2", C.c_double), ("k3", C.c_double),
-        ("bow_dim", C.c_uint32),
-        ("bow", C.POINTER(C.c_float)),
-        ("intrinsic_type", C.c_uint32),
-    ]
-
-
-class MapInfo(C.Structure):
-    _fields_ = [("n_rows", C.c_uint64), ("n_views", C.c_uint32), ("n_landmarks", C.c_uint32),
-                ("hbm_bytes", C.c_uint64), ("device", C.c_int)]
-
-
-class Pose(C.Structure):
-    _fields_ = [("ok", C.c_int32), ("n_inliers", C.c_int32), ("n_matches_2d3d", C.c_int32),
-                ("iterations", C.c_int32), ("status", C.c_int32), ("n_putative_views", C.c_int32),
-                ("n_geometric_views", C.c_int32), ("reserved", C.c_int32),
-                ("nfa", C.c_double), ("error_max", C.c_double),
-                ("P", C.c_double * 12), ("K", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3),
-                ("center", C.c_double * 3), ("stage_seconds", C.c_double * 7)]
-
-
-class BofDesc(C.Structure):
-    _fields_ = [("K", C.c_int), ("in_dim", C.c_int), ("centers", C.POINTER(C.c_float)),
-                ("resized_image_size", C.c_int), ("use_spatial_pyramid", C.c_int), ("pyramid_level", C.c_int),
-                ("norm_type", C.c_int), ("n_pca", C.c_int), ("pca_mean", C.POINTER(C.c_float)),
-                ("pca_eigvec", C.POINTER(C.c_float)), ("pca_eigval", C.POINTER(C.c_float))]
-
-
-class ScanInfo(C.Structure):
-    _fields_ = [("n_views_total", C.c_uint32), ("n_views_posed", C.c_uint32), ("n_rows", C.c_uint64),
-                ("n_landmarks", C.c_uint32), ("n_observations", C.c_uint32), ("bow_dim", C.c_uint32),
-                ("focal", C.c_double), ("ppx", C.c_double), ("ppy", C.c_double),
-                ("k1", C.c_double), ("k2", C.c_double), ("k3", C.c_double),
-                ("desc_fnv1a", C.c_uint64), ("kpt_sum", C.c_double), ("row_landmark_sum", C.c_int64)]
-
-
-class SfmDesc(C.Structure):
-    _fields_ = [("n_views", C.c_uint32), ("view_id", C.POINTER(C.c_uint32)), ("view_intrinsic", C.POINTER(C.c_uint32)),
-                ("view_pose", C.POINTER(C.c_uint32)), ("n_intrinsics", C.c_uint32),
-                ("intrinsic_type", C.POINTER(C.c_uint32)), ("intrinsic", C.POINTER(C.c_double)),
-                ("n_poses", C.c_uint32), ("pose_valid", C.POINTER(C.c_uint8)), ("pose_R", C.POINTER(C.c_double)),
-                ("pose_C", C.POINTER(C.c_double)), ("n_landmarks", C.c_uint32), ("landmark_id", C.POINTER(C.c_uint32)),
-                ("landmark_X", C.POINTER(C.c_double)), ("obs_off", C.POINTER(C.c_uint64)),
-                ("obs_view", C.POINTER(C.c_uint32)), ("obs_x", C.POINTER(C.c_double))]
-
-
-class SfmViewResult(C.Structure):
-    _fields_ = [("ran", C.c_int32), ("ok", C.c_int32), ("n_obs", C.c_int32), ("n_inliers", C.c_int32),
-                ("iterations", C.c_int32), ("reserved", C.c_int32), ("error_max", C.c_double), ("nfa", C.c_double),
-                ("P", C.c_double * 12), ("R", C.c_double * 9), ("center", C.c_double * 3)]
-
-
-class BaReport(C.Structure):
-    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_blocks", C.c_uint32),
-                ("n_at_cap", C.c_uint32), ("n_unchanged", C.c_uint32), ("max_iterations", C.c_uint32)]
-
-
-BA_ROTATION, BA_TRANSLATION, BA_INTRINSICS, BA_STRUCTURE = 1, 2, 4, 8
-
-
-class BaJointOptions(C.Structure):
-    _fields_ = [("max_steps", C.c_uint32), ("max_pcg", C.c_uint32), ("function_tolerance", C.c_double),
-                ("pcg_tolerance", C.c_double)]
-
-
-class BaJointReport(C.Structure):
-    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("n_pose_blocks", C.c_uint32),
-                ("n_intrinsic_blocks", C.c_uint32), ("n_landmark_blocks", C.c_uint32), ("steps_tried", C.c_uint32),
-                ("steps_accepted", C.c_uint32), ("pcg_total", C.c_uint32), ("pcg_max", C.c_uint32), ("stop", C.c_uint32)]
-
-
-TRI_ROBUST, TRI_BLIND = 0, 1
-
-
-class TriangulateOptions(C.Structure):
-    _fields_ = [("mode", C.c_uint32), ("min_inliers", C.c_uint32), ("allow_pairs", C.c_uint32), ("reserved", C.c_uint32),
-                ("residual_px", C.c_double)]
-
-
-class TriangulateReport(C.Structure):
-    _fields_ = [("landmarks_in", C.c_uint64), ("landmarks_kept", C.c_uint64), ("failed_posed", C.c_uint64),
-                ("failed_hypothesis", C.c_uint64), ("failed_inliers", C.c_uint64), ("obs_in", C.c_uint64),
-                ("obs_kept", C.c_uint64), ("rounds", C.c_uint64), ("device_ms", C.c_double)]
-
-
-class MergeParams(C.Structure):
-    _fields_ = [("seed", C.c_uint64), ("device", C.c_int), ("rounds_per_launch", C.c_uint32), ("profile", C.c_int),
-                ("reserved", C.c_int)]
-
-
-class MergeResult(C.Structure):
-    _fields_ = [("M", C.c_double * 12), ("has_model", C.c_uint32), ("round", C.c_uint32), ("count", C.c_uint32),
-                ("n_inliers", C.c_uint32)]
-
-
-class ReduceResult(C.Structure):
-    _fields_ = [("n_keep", C.c_uint64), ("n_absorbed", C.c_uint64), ("n_pairs", C.c_uint64), ("rounds", C.c_uint32),
-                ("reserved", C.c_uint32)]
-
-
-MERGE_SIMILARITY, MERGE_AFFINE = 0, 1
-MERGE_MODELS = {"similarity": MERGE_SIMILARITY, "affine": MERGE_AFFINE}
-
-
-class KernelStats(C.Structure):
-    _fields_ = [("total_ms", C.c_double * K_COUNT), ("launches", C.c_uint64 * K_COUNT),
-                ("hamming_pairs", C.c_uint64), ("hamming_alg_bytes", C.c_uint64),
-                ("hamming_lane_ops", C.c_uint64), ("hamming_pairs_finished", C.c_uint64),
-                ("hamming_rows_flagged", C.c_uint64)]
-
-
-# every symbol include/sfmloc.h declares (tests check the library exports each one)
-SYMBOLS = [
-    "sfmloc_last_error", "sfmloc_abi_version", "sfmloc_device_count", "sfmloc_default_params",
-    "sfmloc_map_create", "sfmloc_map_destroy", "sfmloc_map_get_info", "sfmloc_open", "sfmloc_scan",
-    "sfmloc_map_views", "sfmloc_map_view_sizes",
-    "sfmloc_query_create", "sfmloc_query_destroy",
-    "sfmloc_match_putative", "sfmloc_putative_read", "sfmloc_putative_read_rows", "sfmloc_sync",
-    "sfmloc_geometric_filter", "sfmloc_geometric_read", "sfmloc_match_set", "sfmloc_match_set_read",
-    "sfmloc_resection", "sfmloc_pose_read", "sfmloc_localize", "sfmloc_debug_math", "sfmloc_debug_fail_p3p_alloc", "sfmloc_debug_fail_next_alloc",
-    "sfmloc_context_create", "sfmloc_context_destroy", "sfmloc_localize_begin", "sfmloc_localize_end",
-    "sfmloc_dense_gray", "sfmloc_bow_distances", "sfmloc_query_from_view", "sfmloc_match_one_to_one", "sfmloc_match_pairs", "sfmloc_track", "sfmloc_geometric_pairs",
-    "sfmloc_matches_pairs", "sfmloc_matches_pair", "sfmloc_matches_read", "sfmloc_matches_destroy",
-    "sfmloc_localize_batch", "sfmloc_part_bytes", "sfmloc_shard_begin", "sfmloc_shard_export",
-    "sfmloc_context_sync", "sfmloc_merge_begin", "sfmloc_bow_select", "sfmloc_bof_create", "sfmloc_bof_destroy",
-    "sfmloc_bof_dim", "sfmloc_bof_compute", "sfmloc_akaze_create", "sfmloc_akaze_destroy",
-    "sfmloc_akaze_detect_and_compute", "sfmloc_akaze_compute", "sfmloc_akaze_levels", "sfmloc_akaze_read_levels", "sfmloc_akaze_suppress_stats",
-    "sfmloc_akaze_share_stream", "sfmloc_akaze_detect_and_compute_batch",
-    "sfmloc_stats_read", "sfmloc_stats_reset", "sfmloc_set_profile", "sfmloc_image_decode", "sfmloc_image_read",
-    "sfmloc_view_list_open", "sfmloc_view_list_get", "sfmloc_view_list_close", "sfmloc_localize_bow_begin", "sfmloc_localize_bow",
-    "sfmloc_pack", "sfmloc_scan_packed", "sfmloc_open_packed",
-    "sfmloc_undistorter_create", "sfmloc_undistorter_destroy", "sfmloc_undistorter_info", "sfmloc_undistorter_maps",
-    "sfmloc_undistorter_apply",
-    "sfmloc_query_set_bow", "sfmloc_context_signal", "sfmloc_context_wait", "sfmloc_shard_bow_keys",
-    "sfmloc_geometric_read_pairs", "sfmloc_shard_begin_bow", "sfmloc_packed_bytes", "sfmloc_shard_export_packed", "sfmloc_merge_begin_packed",
-    "sfmloc_gang_begin", "sfmloc_gang_end", "sfmloc_gang_counters", "sfmloc_context_create_sharing", "sfmloc_context_create_merge",
-    "sfmloc_query_create_view", "sfmloc_feat_round_trip",
-    "sfmloc_imgbow_create", "sfmloc_imgbow_destroy", "sfmloc_imgbow_dim", "sfmloc_imgbow_share_stream", "sfmloc_imgbow_compute", "sfmloc_imgbow_compute_batch", "sfmloc_imgbow_vector_read",
-    "sfmloc_shard_batch_bow_keys", "sfmloc_shard_batch_begin_bow", "sfmloc_shard_batch_begin", "sfmloc_merge_batch_begin",
-    "sfmloc_imgbow_vector_dev", "sfmloc_imgbow_order_before", "sfmloc_akaze_detect_resident", "sfmloc_akaze_detect_resident_batch", "sfmloc_akaze_resident_arrays",
-    "sfmloc_bowtrain_create", "sfmloc_bowtrain_destroy", "sfmloc_bowtrain_reset", "sfmloc_bowtrain_add_rows",
-    "sfmloc_bowtrain_add_image", "sfmloc_bowtrain_size", "sfmloc_bowtrain_read", "sfmloc_bowtrain_pca64",
-    "sfmloc_bowtrain_pca", "sfmloc_bowtrain_project", "sfmloc_bowtrain_kmeans",
-    "sfmloc_sfm_default_params", "sfmloc_sfm_create", "sfmloc_sfm_destroy", "sfmloc_sfm_resect", "sfmloc_sfm_resect_read",
-    "sfmloc_sfm_resect_inliers", "sfmloc_sfm_clean", "sfmloc_sfm_read", "sfmloc_sfm_debug_read", "sfmloc_sfm_json_rewrite",
-    "sfmloc_sfm_color_plan", "sfmloc_sfm_color_last_ms", "sfmloc_sfm_adjust", "sfmloc_sfm_read_structure",
-    "sfmloc_ba_joint_default_options", "sfmloc_sfm_adjust_joint", "sfmloc_sfm_read_intrinsics",
-    "sfmloc_merge_default_params", "sfmloc_merge_ransac", "sfmloc_merge_inliers", "sfmloc_merge_median_nn",
-    "sfmloc_merge_transform", "sfmloc_merge_last_ms", "sfmloc_reduce_points", "sfmloc_reduce_last_ms",
-    "sfmloc_query_set_uncalibrated", "sfmloc_debug_resect6",
-    "sfmloc_tracks_build", "sfmloc_tracks_counts", "sfmloc_tracks_read", "sfmloc_tracks_destroy", "sfmloc_tracks_last_ms",
-    "sfmloc_triangulate_default_options", "sfmloc_sfm_triangulate",
-    "sfmloc_relpose_default_options", "sfmloc_relative_poses", "sfmloc_relpose_results", "sfmloc_relpose_inliers",
-    "sfmloc_relpose_destroy", "sfmloc_relpose_last_ms", "sfmloc_debug_five_point",
-]
+# every entry point include/sfmloc.h declares (tests check the library exports each one)
+SYMBOLS = list(_abi.PROTOTYPES)
 
 _bound = False
 
@@ -282,10 +121,7 @@ def feat_round_trip(kpt_xy):
     """sfmloc_feat_round_trip: the keypoints after the reference's `.feat` text round trip (6 significant digits)."""
     k = np.ascontiguousarray(kpt_xy, dtype=np.float32)
     out = np.empty_like(k)
-    L = _L()
-    L.sfmloc_feat_round_trip.restype = None
-    L.sfmloc_feat_round_trip.argtypes = [C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float)]
-    L.sfmloc_feat_round_trip(_ptr(k, C.c_float), k.size, _ptr(out, C.c_float))
+    _L().sfmloc_feat_round_trip(_ptr(k, C.c_float), k.size, _ptr(out, C.c_float))
     return out
 
 
@@ -300,200 +136,9 @@ def _L():
     global _bound
     L = _lib.load()
     if not _bound:
-        L.sfmloc_last_error.restype = C.c_char_p
-        L.sfmloc_abi_version.restype = C.c_int
-        L.sfmloc_device_count.restype = C.c_int
-        L.sfmloc_default_params.restype = None
-        L.sfmloc_default_params.argtypes = [C.POINTER(Params)]
-        L.sfmloc_map_create.argtypes = [C.POINTER(MapDesc), C.POINTER(Params), C.POINTER(C.c_void_p)]
-        L.sfmloc_map_destroy.restype = None
-        L.sfmloc_map_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_map_get_info.argtypes = [C.c_void_p, C.POINTER(MapInfo)]
-        L.sfmloc_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Params), C.POINTER(C.c_void_p)]
-        L.sfmloc_scan.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(ScanInfo)]
-        L.sfmloc_map_views.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                       C.POINTER(C.c_double)]
-        L.sfmloc_query_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_uint32,
-                                          C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_query_destroy.restype = None
-        L.sfmloc_query_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_match_putative.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
-        L.sfmloc_putative_read.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint32)] * 4 + [C.c_uint64]
-        L.sfmloc_putative_read_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.sfmloc_bow_distances.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.sfmloc_dense_gray.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32,
-                                        C.POINTER(C.c_uint8)]
-        L.sfmloc_query_from_view.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_match_one_to_one.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
-        L.sfmloc_match_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_track.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_geometric_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint64),
-                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
-        L.sfmloc_matches_pairs.argtypes = [C.c_void_p]
-        L.sfmloc_matches_pairs.restype = C.c_uint32
-        L.sfmloc_matches_pair.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                          C.POINTER(C.c_uint32)]
-        L.sfmloc_matches_read.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32]
-        L.sfmloc_matches_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_matches_destroy.restype = None
-        L.sfmloc_sync.argtypes = [C.c_void_p]
-        U32P, F64P = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-        L.sfmloc_geometric_filter.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_geometric_read.argtypes = [C.c_void_p, U32P, U32P, C.c_uint64]
-        L.sfmloc_geometric_read_pairs.argtypes = [C.c_void_p, U32P, U32P, U32P, C.c_uint64]
-        L.sfmloc_match_set.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_match_set_read.argtypes = [C.c_void_p, U32P, U32P, U32P, F64P, F64P, C.c_uint32]
-        L.sfmloc_resection.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_pose_read.argtypes = [C.c_void_p, C.POINTER(Pose), U32P, U32P, U32P, C.c_uint32]
-        L.sfmloc_localize.argtypes = [C.c_void_p, C.c_void_p, U32P, C.c_uint32, C.POINTER(Pose), U32P, U32P,
-                                      C.c_uint32]
-        L.sfmloc_debug_math.argtypes = [C.c_int, C.c_int, F64P, C.c_int, C.c_int, F64P, C.c_int]
-        L.sfmloc_debug_fail_p3p_alloc.argtypes = [C.c_int]
-        L.sfmloc_debug_fail_p3p_alloc.restype = None
-        L.sfmloc_debug_fail_next_alloc.argtypes = [C.c_int]
-        L.sfmloc_debug_fail_next_alloc.restype = None
-        L.sfmloc_context_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.sfmloc_context_destroy.restype = None
-        L.sfmloc_context_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_localize_begin.argtypes = [C.c_void_p, C.c_void_p, U32P, C.c_uint32]
-        L.sfmloc_localize_end.argtypes = [C.c_void_p, C.POINTER(Pose), U32P, U32P, C.c_uint32]
-        L.sfmloc_part_bytes.restype = C.c_uint64
-        L.sfmloc_part_bytes.argtypes = [C.c_uint32]
-        L.sfmloc_shard_begin.argtypes = [C.c_void_p, C.c_void_p, U32P, C.c_uint32]
-        L.sfmloc_shard_export.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-        L.sfmloc_context_sync.argtypes = [C.c_void_p]
-        L.sfmloc_merge_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
-        L.sfmloc_bow_select.argtypes = [C.c_void_p, C.POINTER(C.c_float), U32P, C.c_uint32, C.c_uint32, U32P, U32P]
-        L.sfmloc_bof_create.argtypes = [C.POINTER(BofDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.sfmloc_bof_destroy.restype = None
-        L.sfmloc_bof_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_bof_dim.argtypes = [C.c_void_p]
-        L.sfmloc_bof_compute.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, F64P]
-        L.sfmloc_akaze_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_void_p)]
-        L.sfmloc_akaze_destroy.restype = None
-        L.sfmloc_akaze_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_akaze_detect_and_compute.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_float),
-                                                      C.POINTER(C.c_uint8), C.c_uint32, U32P]
-        L.sfmloc_akaze_compute.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.c_uint32,
-                                           C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
-        L.sfmloc_akaze_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.sfmloc_akaze_share_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_akaze_read_levels.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.sfmloc_akaze_suppress_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-        L.sfmloc_localize_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32,
-                                            C.POINTER(Pose), U32P, U32P, C.c_uint32]
-        L.sfmloc_stats_read.argtypes = [C.c_void_p, C.POINTER(KernelStats)]
-        L.sfmloc_stats_reset.argtypes = [C.c_void_p]
-        L.sfmloc_set_profile.argtypes = [C.c_void_p, C.c_int]
-        L.sfmloc_query_set_bow.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        L.sfmloc_query_set_uncalibrated.argtypes = [C.c_void_p, C.c_int]
-        L.sfmloc_debug_resect6.argtypes = [C.c_void_p, F64P, F64P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Pose),
-                                           C.POINTER(C.c_uint32), C.c_uint32]
-        L.sfmloc_context_signal.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_context_wait.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_shard_bow_keys.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_void_p]
-        L.sfmloc_shard_begin_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32]
-        L.sfmloc_packed_bytes.restype = C.c_uint64
-        L.sfmloc_packed_bytes.argtypes = [C.c_uint32, C.c_uint32]
-        L.sfmloc_shard_export_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
-        L.sfmloc_merge_begin_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
-                                                C.c_uint32, C.c_uint32]
-        L.sfmloc_imgbow_create.argtypes = [C.POINTER(BofDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_imgbow_destroy.restype = None
-        L.sfmloc_imgbow_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_imgbow_dim.argtypes = [C.c_void_p]
-        L.sfmloc_imgbow_share_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_imgbow_compute.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p, F64P]
-        L.sfmloc_imgbow_compute_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_uint32]
-        L.sfmloc_imgbow_vector_read.argtypes = [C.c_void_p, F64P]
-        VPP = C.POINTER(C.c_void_p)
-        L.sfmloc_shard_batch_bow_keys.argtypes = [VPP, C.c_uint32, C.c_uint32, VPP, C.c_uint32, C.c_uint32, C.c_void_p]
-        L.sfmloc_shard_batch_begin_bow.argtypes = [VPP, C.c_uint32, C.c_uint32, VPP, C.c_uint32, C.c_void_p, C.c_uint32,
-                                                   C.c_uint32, C.c_void_p, C.c_uint32]
-        L.sfmloc_shard_batch_begin.argtypes = [VPP, C.c_uint32, C.c_uint32, VPP, C.c_uint32, C.c_void_p, C.c_uint32]
-        L.sfmloc_merge_batch_begin.argtypes = [VPP, C.c_uint32, VPP, U32P, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
-                                               C.c_uint32]
-        L.sfmloc_imgbow_order_before.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_imgbow_vector_dev.restype = C.c_void_p
-        L.sfmloc_imgbow_vector_dev.argtypes = [C.c_void_p]
-        L.sfmloc_akaze_detect_resident.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), U32P]
-        L.sfmloc_akaze_detect_resident_batch.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_uint8)), C.c_uint32, U32P]
-        L.sfmloc_akaze_resident_arrays.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
-        F32P = C.POINTER(C.c_float)
-        L.sfmloc_bowtrain_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_bowtrain_destroy.restype = None
-        L.sfmloc_bowtrain_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_bowtrain_reset.argtypes = [C.c_void_p]
-        L.sfmloc_bowtrain_add_rows.argtypes = [C.c_void_p, F32P, C.c_uint32]
-        L.sfmloc_bowtrain_add_image.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.c_uint32, C.POINTER(C.c_uint64)]
-        L.sfmloc_bowtrain_size.argtypes = [C.c_void_p, U32P, U32P]
-        L.sfmloc_bowtrain_read.argtypes = [C.c_void_p, F32P, C.c_uint64]
-        L.sfmloc_bowtrain_pca64.argtypes = [C.c_void_p, F64P, F64P, F64P, F64P]
-        L.sfmloc_bowtrain_pca.argtypes = [C.c_void_p, F32P, F32P, F32P]
-        L.sfmloc_bowtrain_project.argtypes = [C.c_void_p, C.POINTER(BofDesc)]
-        L.sfmloc_bowtrain_kmeans.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64, F32P,
-                                             C.POINTER(C.c_int32), F32P, F64P, U32P]
-        U8P = C.POINTER(C.c_uint8)
-        L.sfmloc_sfm_default_params.restype = None
-        L.sfmloc_sfm_default_params.argtypes = [C.POINTER(Params)]
-        L.sfmloc_sfm_create.argtypes = [C.POINTER(SfmDesc), C.POINTER(Params), C.POINTER(C.c_void_p)]
-        L.sfmloc_sfm_destroy.restype = None
-        L.sfmloc_sfm_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_sfm_resect.argtypes = [C.c_void_p, U32P, U32P]
-        L.sfmloc_sfm_resect_read.argtypes = [C.c_void_p, C.POINTER(SfmViewResult)]
-        L.sfmloc_sfm_resect_inliers.argtypes = [C.c_void_p, C.c_uint32, U32P, C.c_uint32, U32P]
-        L.sfmloc_sfm_clean.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint64)]
-        L.sfmloc_sfm_read.argtypes = [C.c_void_p, U8P, F64P, F64P, U8P, U8P]
-        L.sfmloc_sfm_debug_read.argtypes = [C.c_void_p, F64P, F64P]
-        L.sfmloc_sfm_json_rewrite.argtypes = [C.c_char_p, C.c_char_p]
-        L.sfmloc_sfm_color_plan.argtypes = [C.c_void_p, U32P, U32P, U32P, C.POINTER(C.c_uint64)]
-        L.sfmloc_sfm_color_last_ms.restype = C.c_double
-        L.sfmloc_sfm_color_last_ms.argtypes = []
-        L.sfmloc_sfm_adjust.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaReport)]
-        L.sfmloc_sfm_read_structure.argtypes = [C.c_void_p, F64P]
-        L.sfmloc_ba_joint_default_options.restype = None
-        L.sfmloc_ba_joint_default_options.argtypes = [C.POINTER(BaJointOptions)]
-        L.sfmloc_sfm_adjust_joint.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BaJointOptions), C.POINTER(BaJointReport)]
-        L.sfmloc_sfm_read_intrinsics.argtypes = [C.c_void_p, F64P]
-        U64P = C.POINTER(C.c_uint64)
-        L.sfmloc_tracks_build.argtypes = [C.c_int, U64P, C.c_uint32, U8P, U32P, C.c_uint32, U64P, U32P, U32P, C.c_uint32,
-                                          C.POINTER(C.c_void_p)]
-        L.sfmloc_tracks_counts.argtypes = [C.c_void_p, U64P]
-        L.sfmloc_tracks_read.argtypes = [C.c_void_p, U64P, U32P, U32P]
-        L.sfmloc_tracks_destroy.restype = None
-        L.sfmloc_tracks_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_tracks_last_ms.restype = C.c_double
-        L.sfmloc_tracks_last_ms.argtypes = []
-        L.sfmloc_triangulate_default_options.restype = None
-        L.sfmloc_triangulate_default_options.argtypes = [C.POINTER(TriangulateOptions)]
-        L.sfmloc_sfm_triangulate.argtypes = [C.c_void_p, C.POINTER(TriangulateOptions), C.POINTER(TriangulateReport)]
-        L.sfmloc_relpose_default_options.restype = None
-        L.sfmloc_relpose_default_options.argtypes = [C.POINTER(RelposeOptions)]
-        L.sfmloc_relative_poses.argtypes = [C.c_int, U64P, C.c_uint32, C.POINTER(C.c_float), U32P, U32P, F64P, U32P,
-                                            C.c_uint32, U32P, C.c_uint32, U64P, U32P, U32P, C.POINTER(RelposeOptions),
-                                            C.POINTER(C.c_void_p)]
-        L.sfmloc_relpose_results.argtypes = [C.c_void_p, C.c_void_p]
-        L.sfmloc_relpose_inliers.argtypes = [C.c_void_p, U64P, U32P]
-        L.sfmloc_relpose_destroy.restype = None
-        L.sfmloc_relpose_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_relpose_last_ms.restype = C.c_double
-        L.sfmloc_relpose_last_ms.argtypes = []
-        L.sfmloc_debug_five_point.argtypes = [C.c_int, F64P, C.c_int, F64P]
-        MPP = C.POINTER(MergeParams)
-        L.sfmloc_merge_default_params.restype = None
-        L.sfmloc_merge_default_params.argtypes = [MPP]
-        L.sfmloc_merge_ransac.argtypes = [F64P, F64P, C.c_uint64, C.c_double, C.c_uint64, C.c_double, C.c_int, C.c_uint32,
-                                          MPP, C.POINTER(MergeResult), U32P, C.c_uint32]
-        L.sfmloc_merge_inliers.argtypes = [F64P, F64P, C.c_uint64, F64P, C.c_double, MPP, U32P, C.c_uint32, U32P]
-        L.sfmloc_merge_median_nn.argtypes = [F64P, C.c_uint64, MPP, F64P]
-        L.sfmloc_merge_transform.argtypes = [F64P, F64P, C.c_uint64, F64P, C.c_uint64, MPP]
-        L.sfmloc_merge_last_ms.restype = C.c_double
-        L.sfmloc_merge_last_ms.argtypes = []
-        L.sfmloc_reduce_points.argtypes = [F64P, C.c_uint64, F64P, C.c_double, C.c_uint32, MPP, U32P, U32P, F64P,
-                                           C.POINTER(ReduceResult)]
-        L.sfmloc_reduce_last_ms.restype = C.c_double
-        L.sfmloc_reduce_last_ms.argtypes = []
+        for name, (restype, argtypes) in _abi.PROTOTYPES.items():   # the header's signatures, every one of them
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
         _bound = True
     return L
 
@@ -542,9 +187,7 @@ def pack(sfm_dir, match_dir, out_path):
 def scan_packed(path):
     """sfmloc_scan_packed: the fields of scan() from a packed map file, no GPU."""
     info = ScanInfo()
-    L = _L()
-    L.sfmloc_scan_packed.argtypes = [C.c_char_p, C.POINTER(ScanInfo)]
-    _check(L.sfmloc_scan_packed(os.fsencode(path), C.byref(info)))
+    _check(_L().sfmloc_scan_packed(os.fsencode(path), C.byref(info)))
     return {f: getattr(info, f) for f, _ in ScanInfo._fields_}
 
 
@@ -577,8 +220,6 @@ def image_decode(data, color=False):
     raw = np.frombuffer(bytes(data), dtype=np.uint8)
     w, h = C.c_int32(0), C.c_int32(0)
     L = _L()
-    L.sfmloc_image_decode.argtypes = [C.POINTER(C.c_uint8), C.c_uint64, C.c_int32, C.POINTER(C.c_uint8), C.c_uint64,
-                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     _check(L.sfmloc_image_decode(_ptr(raw, C.c_uint8), raw.size, int(bool(color)), None, 0, C.byref(w), C.byref(h)))
     out = np.zeros((h.value, w.value, 3) if color else (h.value, w.value), np.uint8)
     _check(L.sfmloc_image_decode(_ptr(raw, C.c_uint8), raw.size, int(bool(color)), _ptr(out, C.c_uint8), out.size,
@@ -590,8 +231,6 @@ def image_size(path):
     """(width, height) of an image file from its header (sfmloc_image_read with a NULL buffer)."""
     w, h = C.c_int32(0), C.c_int32(0)
     L = _L()
-    L.sfmloc_image_read.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_int32),
-                                    C.POINTER(C.c_int32)]
     _check(L.sfmloc_image_read(os.fsencode(path), 0, None, 0, C.byref(w), C.byref(h)))
     return w.value, h.value
 
@@ -600,8 +239,6 @@ def image_read(path, color=False):
     """sfmloc_image_read: cv::imread(path, IMREAD_GRAYSCALE | IMREAD_COLOR) as the reference's tools call it."""
     w, h = C.c_int32(0), C.c_int32(0)
     L = _L()
-    L.sfmloc_image_read.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_int32),
-                                    C.POINTER(C.c_int32)]
     bpath = os.fsencode(path)
     _check(L.sfmloc_image_read(bpath, int(bool(color)), None, 0, C.byref(w), C.byref(h)))
     out = np.zeros((h.value, w.value, 3) if color else (h.value, w.value), np.uint8)
@@ -616,14 +253,6 @@ class Undistorter:
 
     def __init__(self, K, dist, width, height, device=0):
         L = _L()
-        L.sfmloc_undistorter_create.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32,
-                                                C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
-        L.sfmloc_undistorter_destroy.restype = None
-        L.sfmloc_undistorter_destroy.argtypes = [C.c_void_p]
-        L.sfmloc_undistorter_info.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.sfmloc_undistorter_maps.argtypes = [C.c_void_p, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]
-        L.sfmloc_undistorter_apply.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint8),
-                                               C.c_uint64]
         Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
         d = np.ascontiguousarray(dist, dtype=np.float64).ravel()
         self._h = C.c_void_p()
@@ -764,17 +393,15 @@ class Map:
         self._children = weakref.WeakSet()
         self.params = params if params is not None else default_params()
         h = C.c_void_p()
-        L = _L()
-        L.sfmloc_open_packed.argtypes = [C.c_char_p, C.POINTER(Params), C.POINTER(C.c_void_p)]
-        _check(L.sfmloc_open_packed(os.fsencode(path), C.byref(self.params), C.byref(h)))
+        _check(_L().sfmloc_open_packed(os.fsencode(path), C.byref(self.params), C.byref(h)))
         self._h = h
         i = self.info()
         self.n_rows, self.n_views = i["n_rows"], i["n_views"]
         self.view_id = np.zeros(self.n_views, np.uint32)
         self.view_off = np.zeros(self.n_views + 1, np.uint32)
         self.view_center = np.zeros((self.n_views, 3), np.float64)
-        _check(L.sfmloc_map_views(self._h, _ptr(self.view_id, C.c_uint32), _ptr(self.view_off, C.c_uint32),
-                                  _ptr(self.view_center, C.c_double)))
+        _check(_L().sfmloc_map_views(self._h, _ptr(self.view_id, C.c_uint32), _ptr(self.view_off, C.c_uint32),
+                                     _ptr(self.view_center, C.c_double)))
         return self
 
     def close(self):
@@ -990,12 +617,8 @@ class Map:
             sel_p, n_sel = None, 0
         else:
             sel_p, n_sel, keep = _sel(cand_views)
-        L = _L()
-        L.sfmloc_localize_bow.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32),
-                                          C.c_uint32, C.POINTER(Pose), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
-                                          C.c_uint32]
-        _check(L.sfmloc_localize_bow(self._h, q._h, _ptr(b, C.c_float), int(knn), sel_p, n_sel, C.byref(pose),
-                                     _ptr(pq, C.c_uint32), _ptr(pl, C.c_uint32), cap))
+        _check(_L().sfmloc_localize_bow(self._h, q._h, _ptr(b, C.c_float), int(knn), sel_p, n_sel, C.byref(pose),
+                                        _ptr(pq, C.c_uint32), _ptr(pl, C.c_uint32), cap))
         k = pose.n_inliers if pose.ok else 0
         return pose, pq[:k].copy(), pl[:k].copy()
 
@@ -1140,7 +763,7 @@ class ImgBow:
         for e, g in zip(extractors, imgs):
             assert g.size == e.width * e.height * e.channels, g.shape
         hs = (C.c_void_p * n)(*[e._h for e in extractors[:n]])
-        ps = (C.c_void_p * n)(*[g.ctypes.data for g in imgs])
+        ps = (C.POINTER(C.c_uint8) * n)(*[_ptr(g, C.c_uint8) for g in imgs])
         _check(_L().sfmloc_imgbow_compute_batch(hs, ps, n))
 
     def close(self):
@@ -1205,7 +828,7 @@ def sfm_default_params(**overrides):
     return p
 
 
-COLOR_CHUNK = 64                # SFMLOC_COLOR_CHUNK: iterations of the colouring plan enqueued per host read
+# COLOR_CHUNK (SFMLOC_COLOR_CHUNK, above): iterations of the colouring plan enqueued per host read
 COLOR_UNSET = 0xFFFFFFFF        # lm_iter of a landmark without observations
 
 
@@ -1441,12 +1064,6 @@ class Tracks:
         return self.counts[3]
 
 
-class RelposeOptions(C.Structure):
-    """sfmloc_relpose_options"""
-    _fields_ = [("max_iteration", C.c_uint32), ("reserved", C.c_uint32), ("precision_px", C.c_double),
-                ("seed", C.c_uint64)]
-
-
 # sfmloc_relpose_result as a NumPy record (align=True gives the C layout: 13 uint32, 4 bytes of padding, 23 doubles)
 RELPOSE_RESULT = np.dtype([("ok", np.uint32), ("n_matches", np.uint32), ("n_inliers", np.uint32),
                            ("sample", np.uint32, 5), ("front", np.uint32, 4), ("choice", np.uint32),
@@ -1504,7 +1121,7 @@ class RelPoses:
                                           _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32), C.byref(opt), C.byref(h)))
         try:
             self.results = np.zeros(len(pairs), RELPOSE_RESULT)
-            _check(_L().sfmloc_relpose_results(h, self.results.ctypes.data_as(C.c_void_p) if len(pairs) else None))
+            _check(_L().sfmloc_relpose_results(h, _ptr(self.results, RelposeResult) if len(pairs) else None))
             self.inl_off = np.zeros(len(pairs) + 1, np.uint64)
             _check(_L().sfmloc_relpose_inliers(h, _ptr(self.inl_off, C.c_uint64), None))
             n = int(self.inl_off[-1])
@@ -1860,8 +1477,6 @@ class Context:
         path on it, asynchronous, the shortlist never leaving the device.  Finish with end()."""
         b = None if bow is None else np.ascontiguousarray(bow, dtype=np.float32).ravel()   # None: q.set_bow()'s
         L = _L()
-        L.sfmloc_localize_bow_begin.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_uint32,
-                                                C.POINTER(C.c_uint32), C.c_uint32]
         if cand_views is None:
             _check(L.sfmloc_localize_bow_begin(self._h, q._h, _ptr(b, C.c_float), int(knn), None, 0))
         else:

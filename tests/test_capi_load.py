@@ -1,10 +1,8 @@
-"""CPU: the C-ABI library loads, exports every symbol include/sfmloc.h declares, its structs have the
-layout the ctypes mirror assumes, and compute entry points fail loudly without a GPU."""
+"""CPU: the C-ABI library loads, exports every symbol include/sfmloc.h declares, and compute entry
+points fail loudly without a GPU.  (The layout of the structs: tests/test_abi.py.)"""
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -32,33 +30,26 @@ def test_library_exports_every_declared_symbol():
     assert capi._L().sfmloc_abi_version() == 2      # 2: sfmloc_params.guided_matching
 
 
-def test_struct_layout_matches_header():
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "sfmloc.h"
-int main(void){
-  printf("%zu %zu %zu %zu %zu %zu\n", sizeof(sfmloc_params), sizeof(sfmloc_map_desc), sizeof(sfmloc_map_info), sizeof(sfmloc_kernel_stats), sizeof(sfmloc_pose), offsetof(sfmloc_pose, center));
-  printf("%zu %zu %zu %zu\n", offsetof(sfmloc_params, geom_precision), offsetof(sfmloc_params, seed), offsetof(sfmloc_params, profile), offsetof(sfmloc_map_desc, bow));
-  return 0; }
-'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(src)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split()
-    sizes = [int(x) for x in out]
-    assert sizes[0] == ctypes.sizeof(capi.Params)
-    assert sizes[1] == ctypes.sizeof(capi.MapDesc)
-    assert sizes[2] == ctypes.sizeof(capi.MapInfo)
-    assert sizes[3] == ctypes.sizeof(capi.KernelStats)
-    assert sizes[4] == ctypes.sizeof(capi.Pose)
-    assert sizes[5] == capi.Pose.center.offset
-    assert sizes[6] == capi.Params.geom_precision.offset
-    assert sizes[7] == capi.Params.seed.offset
-    assert sizes[8] == capi.Params.profile.offset
-    assert sizes[9] == capi.MapDesc.bow.offset
+def test_host_only_entry_points_without_another_caller(tmp_path):
+    """sfmloc_view_list_open / _get / _close have no Python wrapper (the C++ tools call them); sfmloc_pack on a directory
+    without sfm_data.json is the file contract's refusal.  Both run on the host."""
+    L = capi._L()
+    with pytest.raises(S.SfmlocError) as ei:
+        capi.pack(str(tmp_path), str(tmp_path), str(tmp_path / "map.bin"))
+    assert ei.value.code == capi.EIO
+    (tmp_path / "sfm_data.json").write_text(
+        '{"sfm_data_version": "0.2", "root_path": "/img", "views": [{"key": 3, "value": {"polymorphic_id": 1073741824, '
+        '"ptr_wrapper": {"id": 2147483649, "data": {"local_path": "/", "filename": "a.jpg", "width": 640, "height": 480, '
+        '"id_view": 3, "id_intrinsic": 0, "id_pose": 3}}}}], "intrinsics": [], "extrinsics": [], "structure": [], '
+        '"control_points": []}')
+    lst, n = ctypes.c_void_p(), ctypes.c_uint32()
+    capi._check(L.sfmloc_view_list_open(os.fsencode(tmp_path / "sfm_data.json"), ctypes.byref(lst), ctypes.byref(n)))
+    vid, w, h, path = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_char_p()
+    capi._check(L.sfmloc_view_list_get(lst, 0, ctypes.byref(vid), ctypes.byref(w), ctypes.byref(h), ctypes.byref(path)))
+    assert (n.value, vid.value, w.value, h.value, path.value) == (1, 3, 640, 480, b"/img/a.jpg")
+    assert L.sfmloc_view_list_get(lst, 1, None, None, None, None) == capi.EINVAL
+    assert L.sfmloc_view_list_close(lst) is None
+    assert L.sfmloc_view_list_open(os.fsencode(tmp_path / "none.json"), ctypes.byref(lst), ctypes.byref(n)) == capi.EIO
 
 
 def test_default_params_are_the_reference_defaults():

@@ -23,7 +23,7 @@ import relpose_independent as ind  # noqa: E402
 import relpose_np as tw  # noqa: E402
 import relpose_scene as sc  # noqa: E402
 import sfmlocalization_amd as S  # noqa: E402
-from sfmlocalization_amd import capi, relpose  # noqa: E402
+from sfmlocalization_amd import _abi, capi, relpose  # noqa: E402
 
 EXPECTED = os.path.join(HERE, "golden", "relpose", "expected.json")
 
@@ -121,21 +121,12 @@ def test_new_symbols_are_declared():
     assert L.sfmloc_abi_version() == 2
     o = capi.relpose_default_options()
     assert (o.max_iteration, o.precision_px, o.seed) == (256, 2.5, tw.SEED)
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "sfmloc.h"
-int main(void){ printf("%zu %zu %zu %zu\n", sizeof(sfmloc_relpose_options), sizeof(sfmloc_relpose_result),
-  offsetof(sfmloc_relpose_result, E), offsetof(sfmloc_relpose_result, nfa)); return 0; }
-'''
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "t.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(td, "t.c"), "-o",
-                               os.path.join(td, "t")])
-        sizes = [int(x) for x in subprocess.check_output([os.path.join(td, "t")]).decode().split()]
-    assert sizes == [C.sizeof(capi.RelposeOptions), capi.RELPOSE_RESULT.itemsize, capi.RELPOSE_RESULT.fields["E"][1],
-                     capi.RELPOSE_RESULT.fields["nfa"][1]]
+    # sizes and every field offset of sfmloc_relpose_options / _result (RELPOSE_RESULT's E and nfa among them) against
+    # the compiler: tests/test_abi.py; what stays here is that the record and the bound struct are one layout
+    assert capi.RelposeOptions is _abi.struct("sfmloc_relpose_options")
+    res = _abi.struct("sfmloc_relpose_result")
+    assert [C.sizeof(capi.RelposeOptions), capi.RELPOSE_RESULT.itemsize, capi.RELPOSE_RESULT.fields["E"][1],
+            capi.RELPOSE_RESULT.fields["nfa"][1]] == [24, C.sizeof(res), res.E.offset, res.nfa.offset]
 
 
 def test_refusals_need_no_device():

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import sfmlocalization_amd as S
-from sfmlocalization_amd import capi, structure
+from sfmlocalization_amd import _abi, capi, structure
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import structure_np as tw  # noqa: E402
@@ -197,18 +197,9 @@ def test_new_symbols_are_declared():
     assert (o.mode, o.min_inliers, o.allow_pairs, o.residual_px) == (capi.TRI_ROBUST, 3, 1, 4.0)
     assert L.sfmloc_sfm_triangulate(None, None, None) == -1                  # SFMLOC_EINVAL, no device needed
     assert L.sfmloc_tracks_last_ms.restype is C.c_double and L.sfmloc_tracks_last_ms() >= 0.0
-    src = r'''
-#include <stdio.h>
-#include "sfmloc.h"
-int main(void){ printf("%zu %zu\n", sizeof(sfmloc_triangulate_options), sizeof(sfmloc_triangulate_report)); return 0; }
-'''
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "t.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(td, "t.c"), "-o",
-                               os.path.join(td, "t")])
-        sizes = [int(x) for x in subprocess.check_output([os.path.join(td, "t")]).decode().split()]
-    assert sizes == [C.sizeof(capi.TriangulateOptions), C.sizeof(capi.TriangulateReport)]
+    # sizes and every field offset of sfmloc_triangulate_options / _report against the compiler: tests/test_abi.py
+    assert capi.TriangulateOptions is _abi.struct("sfmloc_triangulate_options")
+    assert capi.TriangulateReport is _abi.struct("sfmloc_triangulate_report")
 
 
 def test_tracks_refusals_need_no_device():
