@@ -941,8 +941,8 @@ int sfmloc_sfm_triangulate(sfmloc_sfm *h, const sfmloc_triangulate_options *opt,
 /* ------------------------------------------------------------------------- */
 /* Relative poses (the first stage of openMVG_main_GlobalSfM, reconstructGraph.py:166-171: the essential matrix of      */
 /* every matched view pair by the five-point solver under AC-RANSAC, its decomposition and the cheirality test).        */
-/* Rotation and translation averaging, which consume the result, are not built; neither is OpenMVG's two-view bundle    */
-/* adjustment of the winning pose.  OpenMVG's source was not at hand: every point below is a reading chosen here, and   */
+/* Rotation and translation averaging consume the result ("Global poses" below); OpenMVG's two-view bundle adjustment  */
+/* of the winning pose is not built.  OpenMVG's source was not at hand: every point below is a reading chosen here, and */
 /* tests/relpose_np.py restates each operation.  The pair list has the layout of sfmloc_geometric_pairs and             */
 /* sfmloc_tracks_build (pair k = views (I, J) = (pairs[2k], pairs[2k+1]) owns match_i/j[offsets[k] .. offsets[k+1]),    */
 /* feature indices inside the view); kpt_xy [view_off[n_views] * 2] the keypoints of all views; intrinsics f, ppx, ppy, */
@@ -1028,6 +1028,103 @@ void sfmloc_relpose_destroy(sfmloc_relpose *r);
 double sfmloc_relpose_last_ms(void);
 /* parity probe of the solver alone: a row = x1[10], x2[10] (five bearing pairs); out [n * 91] = count, then up to 10 E */
 int  sfmloc_debug_five_point(int device, const double *in, int n, double *out);
+
+/* ------------------------------------------------------------------------- */
+/* Global poses (the middle stage of openMVG_main_GlobalSfM: rotation averaging and translation averaging over the     */
+/* relative poses of the section above; its result is what "Structure from known poses" starts from).  OpenMVG's       */
+/* source was not at hand: every point below is a reading chosen here, and tests/globalposes_np.py restates each one.   */
+/* Pair k = views (I, J) = (pairs[2k], pairs[2k+1]) with rel_R[9k..] row-major and rel_t[3k..] in the convention of     */
+/* sfmloc_relpose_result: X_J = R X_I + t, |t| = 1.  use_t[k] = 0 (NULL: all 1) keeps a pair's translation out (the     */
+/* advice of "decision" above: front[choice] < n_inliers).  On the device f64, unfused, only + - * / sqrt; the host     */
+/* computes the cosine of the triplet angle and the tangent of rotation_delta's default.                                */
+/*   adjacency   CSR by view over both directions of every pair, a view's entries ascending by neighbour (built on the  */
+/*               host).  Every sum over a view's pairs below runs in that order, so a result does not depend on the     */
+/*               order of the pair list.  Views of more than 64 pairs are gathered by one wave each (lane-strided, then  */
+/*               the six-level butterfly), the others by one lane each.                                                  */
+/*   triplets    every triangle a < b < c of the pair graph.  R_xy = rel_R of the pair when it is stored as (x, y), its */
+/*               transpose when stored as (y, x).  The cycle rotation is M = R_ca (R_bc R_ab); the triplet passes when  */
+/*               trace M > 1 + 2 cos(triplet_angle_deg) (default 5 degrees, OpenMVG's).  One wave per pair intersects   */
+/*               the two adjacency lists; n_triplets / n_triplets_ok of a pair count the triangles it lies in; nothing  */
+/*               else of a triplet is stored (summed over the wave, integers).  kept = n_triplets_ok > 0.                 */
+/*   component   connected components over the pairs with kept and use_t (the hook / pointer-jump kernels of            */
+/*               sfmloc_tracks, csrc/graph_device.h).  The component with the most views wins, the one with the          */
+/*               smallest view index on a tie; its smallest view is the root, R = I, C = 0.  No component of two views   */
+/*               (no triplet passes): every in_component is 0, the report is filled, no error.  "rotation pairs" = kept  */
+/*               pairs with both views in the component; "translation pairs" = the rotation pairs with use_t.            */
+/*   chordal     minimise sum |R_j - R_ij R_i|_F^2 over the rotation pairs with the root fixed: per view, deg X_v -     */
+/*               sum Off X_n = b_v, Off = R_ij in J's row and R_ij^T in I's, b_v = Off for the pair to the root.  One    */
+/*               conjugate-gradient run on the 9 values per view together ("PCG" below, preconditioner 1 / deg).  Each  */
+/*               X_v to the nearest rotation: "jacobi" (N = 3) on X^T X = V diag(l) V^T, R = X V diag(s_i / sqrt(l_i))   */
+/*               V^T with s = 1, except s = -1 at the smallest l (the first on ties) when det X < 0.                     */
+/*   IRLS        per rotation pair E = R_j^T (R_ij R_i), g = (E21 - E12, E02 - E20, E10 - E01) / (1 + tr E), |g| =       */
+/*               tan(theta / 2); 1 + tr E <= 1e-12: weight 0, g = 0, no cost.  Huber in |g| with delta = rotation_delta */
+/*               (default tan(triplet_angle / 6): half of a third of the triplet bound): w = 1, rho = |g|^2 / 2 up to   */
+/*               delta, then w = delta / |g|, rho = delta (|g| - delta / 2).  Solve sum_e w (x_v - x_n) = sum +-w g     */
+/*               (+ in J's row, - in I's), x_root = 0, by PCG (preconditioner 1 / sum w); R_v <- R_v (I + 2 / (1 + x.x)  */
+/*               ([x]x + [x]x^2)).  A step whose robust cost is not lower is not applied and ends the loop (stop 2);    */
+/*               stop 0 after an applied step with (cost - cost') <= function_tolerance * cost, or at cost 0 or a zero  */
+/*               right-hand side; stop 1 after max_steps.                                                                */
+/*   translation d = -R_j^T t_ij scaled to unit length: the world direction from C_i to C_j.  Per translation pair,     */
+/*               D = C_j - C_i, s = d.D, r = D - max(1, s) d, Huber in |r| with translation_delta (default 0.05, in     */
+/*               units of the bound s >= 1, which is what forbids the collapsed solution), block W = w (I - d d^T) when */
+/*               s > 1, else w I.  Gauss-Newton under "solver" of the joint block (lambda 1e-4, D = diag clamped to     */
+/*               [1e-6, 1e32], acceptance ratio 1e-3, the lambda update, "stopping"), from C = 0, C_root = 0: per view  */
+/*               (sum W + lambda D) x_v - sum W x_n = -+w r, PCG with the inverse of the view's own 3 x 3 block; model  */
+/*               decrease sum_e -(w r).u - u^T W u / 2, u = x_j - x_i.                                                  */
+/*   PCG         from x = 0; stops at |r| <= pcg_tolerance |r0|, after max_pcg iterations, or when r.z or p.Ap is not   */
+/*               positive.  Scalar products are per-workgroup partials summed by a fixed tree (store, then sum); costs  */
+/*               are summed per view over the pairs to a larger neighbour, then the same way.  Iterations are queued 32 */
+/*               at a time with one small read-back per chunk and per step; a finished solve makes the rest of its      */
+/*               chunk return at once.  No float atomics: two runs give the same bits.                                   */
+/* Known limit: pairwise directions do not determine the spacing along a collinear stretch of cameras.  There only the  */
+/* bound s >= 1 and the Huber term act, and one bad pair can fold two centres together.  Relative scales from shared    */
+/* points (OpenMVG's triplet translations) are not built.                                                                */
+/* Refusals, all on the host before any launch, the text naming the pair: a view index out of range, a pair naming one  */
+/* view twice, the same unordered pair listed twice, a non-finite entry, |R^T R - I| (largest entry) or | |t| - 1 |     */
+/* above 1e-6: SFMLOC_EINVAL.  n_pairs = 0 gives an empty handle.                                                        */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_gposes sfmloc_gposes;
+typedef struct sfmloc_gposes_options {
+  double   triplet_angle_deg;   /* default 5 */
+  double   rotation_delta;      /* Huber delta on |g| = tan(theta / 2); <= 0 (the default): tan(triplet_angle / 6) */
+  double   translation_delta;   /* default 0.05 */
+  double   function_tolerance;  /* default 1e-6, both loops */
+  double   pcg_tolerance;       /* default 1e-6 */
+  uint32_t max_steps;           /* default 50, both loops */
+  uint32_t max_pcg;             /* default 20000 iterations per solve */
+} sfmloc_gposes_options;
+typedef struct sfmloc_gposes_pair {
+  uint32_t n_triplets, n_triplets_ok, kept, used_t;  /* used_t: a translation pair */
+  double   rot_residual;    /* |g| at the result, 0 unless a rotation pair */
+  double   trans_residual;  /* |r| at the result, 0 unless a translation pair */
+} sfmloc_gposes_pair;
+typedef struct sfmloc_gposes_report {
+  uint32_t n_views, n_pairs, n_triplets, n_triplets_ok, n_pairs_kept;
+  uint32_t n_component_views, root, n_rotation_pairs, n_translation_pairs;
+  uint32_t chordal_pcg, chordal_stop;            /* PCG stop: 0 tolerance, 1 max_pcg, 2 r.z or p.Ap not positive */
+  uint32_t rot_steps_tried, rot_steps_accepted, rot_pcg_total, rot_stop;
+  uint32_t trans_steps_tried, trans_steps_accepted, trans_pcg_total, trans_stop;  /* stop 2: lambda passed 1e32 */
+  uint32_t launches;                             /* kernels queued by the call */
+  double   chordal_residual;                     /* |r| / |r0| where the chordal PCG stopped */
+  double   chordal_cost;                         /* sum |R_j - R_ij R_i|_F^2 over the rotation pairs at the projected start */
+  double   rot_cost_initial, rot_cost_final;     /* the robust cost at the chordal start and at the result */
+  double   trans_cost_initial, trans_cost_final;
+  double   graph_ms, rotation_ms, translation_ms; /* device time of triplets + component, chordal + IRLS, translation */
+  double   device_ms;                            /* HIP events around the call's kernels and copies */
+} sfmloc_gposes_report;
+void sfmloc_gposes_default_options(sfmloc_gposes_options *o);
+/* opt NULL = the defaults */
+int  sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs,
+                         const double *rel_R /*[n_pairs*9]*/, const double *rel_t /*[n_pairs*3]*/,
+                         const uint8_t *use_t /*[n_pairs], NULL = all*/,
+                         const sfmloc_gposes_options *opt, sfmloc_gposes **out);
+/* any of the three may be NULL; R and C of a view outside the component are zero */
+int  sfmloc_gposes_views(const sfmloc_gposes *g, uint8_t *in_component /*[n]*/, double *R /*[n*9]*/, double *C /*[n*3]*/);
+int  sfmloc_gposes_pairs(const sfmloc_gposes *g, sfmloc_gposes_pair *out /*[n_pairs]*/);
+int  sfmloc_gposes_report_read(const sfmloc_gposes *g, sfmloc_gposes_report *rep);
+void sfmloc_gposes_destroy(sfmloc_gposes *g);
+/* device milliseconds of the calling thread's last sfmloc_global_poses */
+double sfmloc_gposes_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */

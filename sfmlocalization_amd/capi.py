@@ -41,6 +41,9 @@ TriangulateOptions = _abi.struct("sfmloc_triangulate_options")
 TriangulateReport = _abi.struct("sfmloc_triangulate_report")
 RelposeOptions = _abi.struct("sfmloc_relpose_options")
 RelposeResult = _abi.struct("sfmloc_relpose_result")
+GposesOptions = _abi.struct("sfmloc_gposes_options")
+GposesPair = _abi.struct("sfmloc_gposes_pair")
+GposesReport = _abi.struct("sfmloc_gposes_report")
 MergeParams = _abi.struct("sfmloc_merge_params")
 MergeResult = _abi.struct("sfmloc_merge_result")
 ReduceResult = _abi.struct("sfmloc_reduce_result")
@@ -1135,6 +1138,61 @@ class RelPoses:
     def inliers(self, k):
         """the inlier positions of pair k"""
         return self.inl_idx[int(self.inl_off[k]):int(self.inl_off[k + 1])]
+
+
+# sfmloc_gposes_pair as a NumPy record (four uint32, two doubles: no padding)
+GPOSES_PAIR = np.dtype([("n_triplets", np.uint32), ("n_triplets_ok", np.uint32), ("kept", np.uint32),
+                        ("used_t", np.uint32), ("rot_residual", np.float64), ("trans_residual", np.float64)], align=True)
+
+
+def gposes_default_options(**overrides):
+    """sfmloc_gposes_default_options -> GposesOptions (5 degrees, the derived rotation delta, 0.05, 1e-6, 1e-6, 50, 20000)"""
+    o = GposesOptions()
+    _L().sfmloc_gposes_default_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def gposes_last_ms():
+    """device milliseconds of the calling thread's last sfmloc_global_poses"""
+    return float(_L().sfmloc_gposes_last_ms())
+
+
+class GlobalPoses:
+    """sfmloc_global_poses: rotation and translation averaging over relative poses (include/sfmloc.h "Global poses"
+    states the semantics).  pairs [P, 2] view indices, rel_R [P, 3, 3] and rel_t [P, 3] in sfmloc_relpose_result's
+    convention, use_t [P] or None (all); options: the fields of sfmloc_gposes_options.  -> in_component [n] bool,
+    R [n, 3, 3], C [n, 3], pairs (GPOSES_PAIR [P]), report (GposesReport), ms."""
+
+    def __init__(self, n_views, pairs, rel_R, rel_t, use_t=None, device=0, **options):
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
+        rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
+        if use_t is not None:
+            use_t = np.ascontiguousarray(np.asarray(use_t) != 0, np.uint8)
+        if len(rel_R) != len(pairs) or len(rel_t) != len(pairs) or (use_t is not None and len(use_t) != len(pairs)):
+            raise ValueError("pair arrays differ in length")
+        n, P = int(n_views), len(pairs)
+        opt = gposes_default_options(**options)
+        h = C.c_void_p()
+        _check(_L().sfmloc_global_poses(int(device), n, _ptr(pairs, C.c_uint32), P, _ptr(rel_R, C.c_double),
+                                        _ptr(rel_t, C.c_double), None if use_t is None else _ptr(use_t, C.c_uint8),
+                                        C.byref(opt), C.byref(h)))
+        try:
+            inc = np.zeros(max(1, n), np.uint8)
+            self.R, self.C = np.zeros((max(1, n), 3, 3)), np.zeros((max(1, n), 3))
+            _check(_L().sfmloc_gposes_views(h, _ptr(inc, C.c_uint8), _ptr(self.R, C.c_double), _ptr(self.C, C.c_double)))
+            self.in_component, self.R, self.C = inc[:n].astype(bool), self.R[:n], self.C[:n]
+            self.pairs = np.zeros(P, GPOSES_PAIR)
+            _check(_L().sfmloc_gposes_pairs(h, _ptr(self.pairs, GposesPair) if P else None))
+            self.report = GposesReport()
+            _check(_L().sfmloc_gposes_report_read(h, C.byref(self.report)))
+            self.ms = gposes_last_ms()
+        finally:
+            _L().sfmloc_gposes_destroy(h)
 
 
 def five_point(rows):

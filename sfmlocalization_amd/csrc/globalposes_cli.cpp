@@ -1,0 +1,222 @@
+// ComputeGlobalPoses as a C++ host program over the C ABI (plain g++):
+//
+//   ComputeGlobalPoses -i <sfm_data.json> -p <relative_poses.json> -o <out sfm_data.json>
+//                      [--triplet-angle 5] [--device 0] [-r <report.json>]
+//
+// The same program as sfmlocalization_amd/globalposes.py and the same bytes in both output files: rotation and
+// translation averaging over the relative poses of the view pairs (sfmloc_global_poses, the middle stage of
+// openMVG_main_GlobalSfM).  I and J of the poses file are view ids; a pair carries its translation when
+// front[choice] == n_inliers.  The output is the input document with `extrinsics` replaced by the poses of the
+// component's views, keyed by id_pose, and `structure` and `control_points` emptied.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/sfmloc.h"
+#include "sfm_doc.h"
+#include "sfm_json.h"
+
+using sfmdoc::Doc;
+using sfmdoc::make_int;
+using sfmdoc::set_key;
+using sfmjson::Value;
+
+namespace {
+
+const char *kName = "ComputeGlobalPoses";
+
+void usage() {
+  fprintf(stderr,
+          "Usage: %s\n"
+          "[-i|--input_file] path to a SfM_Data scene\n"
+          "[-p|--poses_file] the relative poses of its view pairs (relative_poses.json of ComputeRelativePoses)\n"
+          "[-o|--output_file] the SfM_Data scene to write\n"
+          "\n[Optional]\n"
+          "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
+          "[-r|--report_file] the call's report as JSON\n"
+          "[--device] HIP device (0)\n",
+          kName);
+}
+
+Value floats(const double *v, int n) {
+  Value a = Value::make_arr();
+  for (int i = 0; i < n; ++i) a.a.push_back(Value::make_float(v[i]));
+  return a;
+}
+
+Value rows3(const double *v) {
+  Value a = Value::make_arr();
+  for (int i = 0; i < 3; ++i) a.a.push_back(floats(v + 3 * i, 3));
+  return a;
+}
+
+// the `relative_poses` list -> the call's arrays; false with *err on an entry that cannot be read
+bool pose_arrays(const Value &root, const std::map<uint32_t, uint32_t> &view_index, std::vector<uint32_t> *pairs,
+                 std::vector<double> *R, std::vector<double> *t, std::vector<uint8_t> *use_t, std::string *err) {
+  const Value *list = root.kind == Value::Obj ? root.get("relative_poses") : nullptr;
+  if (!list || list->kind != Value::Arr) return *err = "no relative_poses list", false;
+  for (const Value &e : list->a) {
+    uint32_t I, J, choice, n_inliers, front;
+    double r[9], tt[3];
+    const Value *rot = e.kind == Value::Obj ? e.get("R") : nullptr, *fr = e.kind == Value::Obj ? e.get("front") : nullptr;
+    if (!rot || !sfmdoc::num_u32(e.get("I"), &I) || !sfmdoc::num_u32(e.get("J"), &J) ||
+        !sfmdoc::num_u32(e.get("choice"), &choice) || !sfmdoc::num_u32(e.get("n_inliers"), &n_inliers) ||
+        rot->kind != Value::Arr || rot->a.size() != 3 || !sfmdoc::num_vec(&rot->a[0], 3, r) ||
+        !sfmdoc::num_vec(&rot->a[1], 3, r + 3) || !sfmdoc::num_vec(&rot->a[2], 3, r + 6) ||
+        !sfmdoc::num_vec(e.get("t"), 3, tt) || !fr || fr->kind != Value::Arr || choice >= fr->a.size() ||
+        !sfmdoc::num_u32(&fr->a[choice], &front))
+      return *err = "malformed entry " + std::to_string(pairs->size() / 2), false;
+    const auto a = view_index.find(I), b = view_index.find(J);
+    if (a == view_index.end() || b == view_index.end())
+      return *err = "entry " + std::to_string(pairs->size() / 2) + " names an unknown view", false;
+    pairs->push_back(a->second);
+    pairs->push_back(b->second);
+    R->insert(R->end(), r, r + 9);
+    t->insert(t->end(), tt, tt + 3);
+    use_t->push_back(front == n_inliers ? 1 : 0);
+  }
+  return true;
+}
+
+Value report_json(const sfmloc_gposes_report &r) {
+  Value o;
+  o.kind = Value::Obj;
+  const std::pair<const char *, uint32_t> ints[] = {
+      {"n_views", r.n_views}, {"n_pairs", r.n_pairs}, {"n_triplets", r.n_triplets}, {"n_triplets_ok", r.n_triplets_ok},
+      {"n_pairs_kept", r.n_pairs_kept}, {"n_component_views", r.n_component_views}, {"root", r.root},
+      {"n_rotation_pairs", r.n_rotation_pairs}, {"n_translation_pairs", r.n_translation_pairs},
+      {"chordal_pcg", r.chordal_pcg}, {"chordal_stop", r.chordal_stop}, {"rot_steps_tried", r.rot_steps_tried},
+      {"rot_steps_accepted", r.rot_steps_accepted}, {"rot_pcg_total", r.rot_pcg_total}, {"rot_stop", r.rot_stop},
+      {"trans_steps_tried", r.trans_steps_tried}, {"trans_steps_accepted", r.trans_steps_accepted},
+      {"trans_pcg_total", r.trans_pcg_total}, {"trans_stop", r.trans_stop}, {"launches", r.launches}};
+  for (const auto &kv : ints) o.o.emplace_back(kv.first, make_int(kv.second));
+  const std::pair<const char *, double> doubles[] = {
+      {"chordal_residual", r.chordal_residual}, {"chordal_cost", r.chordal_cost}, {"rot_cost_initial", r.rot_cost_initial},
+      {"rot_cost_final", r.rot_cost_final}, {"trans_cost_initial", r.trans_cost_initial},
+      {"trans_cost_final", r.trans_cost_final}, {"graph_ms", r.graph_ms}, {"rotation_ms", r.rotation_ms},
+      {"translation_ms", r.translation_ms}, {"device_ms", r.device_ms}};
+  for (const auto &kv : doubles) o.o.emplace_back(kv.first, Value::make_float(kv.second));
+  return o;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+  std::string in, poses, out_path, report, angle_txt = "5", dev_txt = "0";
+  for (int i = 1; i < argc; ++i) {
+    std::string a = argv[i];
+    std::string *dst = nullptr;
+    const size_t eq = a.find('=');
+    if (eq != std::string::npos && (a.substr(0, eq) == "--triplet-angle" || a.substr(0, eq) == "--device")) {
+      (a.substr(0, eq) == "--device" ? dev_txt : angle_txt) = a.substr(eq + 1);
+      continue;
+    }
+    if (a == "-i" || a == "--input_file") dst = &in;
+    else if (a == "-p" || a == "--poses_file") dst = &poses;
+    else if (a == "-o" || a == "--output_file") dst = &out_path;
+    else if (a == "-r" || a == "--report_file") dst = &report;
+    else if (a == "--triplet-angle") dst = &angle_txt;
+    else if (a == "--device") dst = &dev_txt;
+    if (!dst || i + 1 >= argc) {
+      usage();
+      return 1;
+    }
+    *dst = argv[++i];
+  }
+  char *e1 = nullptr, *e2 = nullptr;
+  const double angle = strtod(angle_txt.c_str(), &e1);
+  const long device = strtol(dev_txt.c_str(), &e2, 10);
+  if (angle_txt.empty() || dev_txt.empty() || *e1 || *e2 || in.empty() || poses.empty() || out_path.empty() ||
+      !(angle > 0.0 && angle < 180.0)) {
+    usage();
+    return 1;
+  }
+  Doc d;
+  std::string err, text;
+  bool ok = sfmjson::read_file(in.c_str(), &text);
+  if (!ok) err = "cannot be read";
+  ok = ok && sfmjson::parse(text, &d.root, &err);
+  Value out = d.root;  // (the output starts from the document as it was read: its keys keep their places)
+  if (ok && d.root.kind == Value::Obj) set_key(&d.root, "structure", Value::make_arr());
+  ok = ok && sfmdoc::build(&d, &err);
+  if (!ok) {
+    fprintf(stderr, "\nThe input SfM_Data file \"%s\" cannot be read. (%s)\n", in.c_str(), err.c_str());
+    return 1;
+  }
+  const uint32_t n_views = (uint32_t)d.view_id.size();
+  std::map<uint32_t, uint32_t> view_index;
+  for (uint32_t k = 0; k < n_views; ++k) view_index[d.view_id[k]] = k;
+  std::vector<uint32_t> pairs;
+  std::vector<double> rel_R, rel_t;
+  std::vector<uint8_t> use_t;
+  Value pdoc;
+  ok = sfmjson::read_file(poses.c_str(), &text);
+  if (!ok) err = "cannot be read";
+  ok = ok && sfmjson::parse(text, &pdoc, &err) && pose_arrays(pdoc, view_index, &pairs, &rel_R, &rel_t, &use_t, &err);
+  if (!ok) {
+    fprintf(stderr, "\nInvalid relative poses file. (%s: %s)\n", poses.c_str(), err.c_str());
+    return 1;
+  }
+  const uint32_t n_pairs = (uint32_t)use_t.size();
+  size_t with_t = 0;
+  for (uint8_t u : use_t) with_t += u;
+  printf("#views: %u; #pairs: %u, with a translation: %zu\n", n_views, n_pairs, with_t);
+  fflush(stdout);
+  sfmloc_gposes_options opt;
+  sfmloc_gposes_default_options(&opt);
+  opt.triplet_angle_deg = angle;
+  sfmloc_gposes *h = nullptr;
+  if (sfmloc_global_poses((int)device, n_views, pairs.data(), n_pairs, rel_R.data(), rel_t.data(), use_t.data(), &opt, &h)) {
+    fprintf(stderr, "%s: %s\n", kName, sfmloc_last_error());
+    return 1;
+  }
+  std::vector<uint8_t> inc(n_views ? n_views : 1);
+  std::vector<double> R(9 * (size_t)(n_views ? n_views : 1)), C(3 * (size_t)(n_views ? n_views : 1));
+  sfmloc_gposes_report rep;
+  sfmloc_gposes_views(h, inc.data(), R.data(), C.data());
+  sfmloc_gposes_report_read(h, &rep);
+  sfmloc_gposes_destroy(h);
+  if (!report.empty()) {
+    std::string rtxt;
+    sfmjson::dump(report_json(rep), &rtxt);
+    if (!sfmjson::write_file(report.c_str(), rtxt)) {
+      fprintf(stderr, "%s: %s cannot be written\n", kName, report.c_str());
+      return 1;
+    }
+  }
+  if (!rep.n_component_views) {
+    fprintf(stderr, "%s: no triplet of the %u pairs passes: no view can be posed\n", kName, n_pairs);
+    return 1;
+  }
+  printf("Global poses: %u of %u views; %u of %u pairs kept; steps: rotation %u/%u, translation %u/%u; device %.3f ms\n",
+         rep.n_component_views, rep.n_views, rep.n_pairs_kept, rep.n_pairs, rep.rot_steps_accepted, rep.rot_steps_tried,
+         rep.trans_steps_accepted, rep.trans_steps_tried, rep.device_ms);
+  fflush(stdout);
+  std::map<uint32_t, uint32_t> first_view;  // id_pose -> the first view of the component that has it
+  for (uint32_t v = 0; v < n_views; ++v)
+    if (inc[v]) first_view.emplace(d.view_pose_id[v], v);
+  Value ext = Value::make_arr();
+  for (const auto &kv : first_view) {
+    Value val, e;
+    val.kind = e.kind = Value::Obj;
+    val.o.emplace_back("rotation", rows3(R.data() + 9 * (size_t)kv.second));
+    val.o.emplace_back("center", floats(C.data() + 3 * (size_t)kv.second, 3));
+    e.o.emplace_back("key", make_int(kv.first));
+    e.o.emplace_back("value", val);
+    ext.a.push_back(e);
+  }
+  set_key(&out, "extrinsics", ext);
+  set_key(&out, "structure", Value::make_arr());
+  set_key(&out, "control_points", Value::make_arr());
+  std::string otxt;
+  sfmjson::dump(out, &otxt);
+  if (!sfmjson::write_file(out_path.c_str(), otxt)) {
+    fprintf(stderr, "%s: %s cannot be written\n", kName, out_path.c_str());
+    return 1;
+  }
+  return 0;
+}

@@ -1,5 +1,5 @@
 // The sfm_data.json document as the map-side tools read it (host code only; shared by adjust_cli.cpp, colorize_cli.cpp,
-// structure_cli.cpp and relpose_cli.cpp): the parsed JSON and the arrays of sfmloc_sfm_desc built from it -- views
+// structure_cli.cpp, relpose_cli.cpp and globalposes_cli.cpp): the parsed JSON and the arrays of sfmloc_sfm_desc built from it -- views
 // ascending, a pose table (every extrinsic key and every view's id_pose, ascending), landmarks ascending with their
 // observations in CSR.
 #pragma once

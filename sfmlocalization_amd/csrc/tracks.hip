@@ -2,12 +2,8 @@
 // openMVG_main_ComputeStructureFromKnownPoses.  The semantics are stated in include/sfmloc.h ("sfmloc_tracks"); the
 // kernels below name the paragraph they implement.
 //
-//   components  every match is an edge between two global feature rows.  parent[x] <= x always: a pass hooks, for every
-//               edge whose ends have different roots, the larger root under the smaller one (atomicMin on the root's
-//               parent, an integer minimum: the same whatever the order), then every node jumps to its root.  Passes
-//               repeat until one hooks nothing; then every edge has both ends under one root and a root is the smallest
-//               row of its component.  The fixed point does not depend on scheduling; only the number of passes does,
-//               and nothing reports it.
+//   components  every match is an edge between two global feature rows; the hook and pointer-jump passes of
+//               graph_device.h, repeated until one hooks nothing: a root is the smallest row of its component.
 //   order       the touched rows are compacted in ascending row (a scan, no atomic decides a position) and sorted by
 //               label with the stable radix sort of radix_sort.h: components ascend by label, rows ascend inside one.
 //   filter      two neighbours of one component in the same view are a conflict (rows of a view are contiguous, so
@@ -22,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "graph_device.h"
 #include "radix_sort.h"
 #include "sfmloc_internal.h"
 #include "tracks_host.h"
@@ -51,35 +48,6 @@ __global__ __launch_bounds__(256) void k_trk_mark(const uint32_t *__restrict__ e
   if (e >= m) return;
   touched[ea[e]] = 1;
   touched[eb[e]] = 1;
-}
-
-// the root of x; parent[] descends strictly until it, whatever other lanes hook meanwhile
-__device__ __forceinline__ uint32_t trk_find(const uint32_t *parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = __atomic_load_n(parent + x, __ATOMIC_RELAXED);
-    if (p == x) return x;
-    x = p;
-  }
-}
-
-// sfmloc.h "components": hook.  A root that another lane hooks at the same time keeps the smaller of the two parents;
-// the edge that lost is met again in the next pass, which is why the loop ends on a pass without a hook.
-__global__ __launch_bounds__(256) void k_trk_hook(const uint32_t *__restrict__ ea, const uint32_t *__restrict__ eb,
-                                                  uint32_t m, uint32_t *parent, uint32_t *changed) {
-  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= m) return;
-  const uint32_t ra = trk_find(parent, ea[e]), rb = trk_find(parent, eb[e]);
-  if (ra == rb) return;
-  atomicMin(parent + (ra > rb ? ra : rb), ra > rb ? rb : ra);
-  *changed = 1;
-}
-
-// sfmloc.h "components": pointer jumping, all the way (no hook runs beside it: the roots stand still)
-__global__ __launch_bounds__(256) void k_trk_jump(uint32_t *parent, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t r = trk_find(parent, i);
-  __atomic_store_n(parent + i, r, __ATOMIC_RELAXED);
 }
 
 // ---- exclusive scan of a[0..n) in place over several workgroups: per-block scan + block totals, the totals scanned by
@@ -232,9 +200,9 @@ int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint
   SFM_HIP(hipGetLastError());
   for (;;) {  // sfmloc.h "components": until a pass hooks nothing
     SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(k_trk_hook, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_parent.get(),
+    hipLaunchKernelGGL(k_graph_hook, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_parent.get(),
                        d_flag.get());
-    hipLaunchKernelGGL(k_trk_jump, gn, b256, 0, s, d_parent.get(), n);
+    hipLaunchKernelGGL(k_graph_jump, gn, b256, 0, s, d_parent.get(), n);
     SFM_HIP(hipGetLastError());
     uint32_t changed = 0;
     TRK_TRY(read_u32(&changed, d_flag, s));

@@ -13,8 +13,8 @@ sfmloc_relative_poses (include/sfmloc.h "Relative poses" states the semantics) r
 hold the ok pairs only, each with its inliers in ascending (i, j); the poses file is
 {"relative_poses": [{"I", "J", "n_matches", "n_inliers", "R", "t", "E", "error_max", "front", "choice"}, ...]} in
 ascending (I, J), I and J view ids, R and E as three rows, written with json.dump.  bin/ComputeRelativePoses
-(csrc/relpose_cli.cpp) is the same program and writes the same bytes.  Rotation and translation averaging
-and the two-view refinement of OpenMVG are not built.
+(csrc/relpose_cli.cpp) is the same program and writes the same bytes.  sfmlocalization_amd.globalposes consumes the
+poses file (rotation and translation averaging); the two-view refinement of OpenMVG is not built.
 """
 import json
 import os

@@ -72,13 +72,15 @@ def structure_entries(view_id, off, view, feat, obs_x, X, landmark_keep, obs_kee
 
 
 def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.0, angle_deg=2.0, adjust=False,
-        blind=False, device=0, log=print):
-    """The tool's body.  Returns 0, or 1 after an error message on stderr."""
+        blind=False, device=0, log=print, joint=False):
+    """The tool's body.  Returns 0, or 1 after an error message on stderr.  joint (no command-line switch: what
+    sfmlocalization_amd.globalsfm asks for): after the cleanup, rotations, translations and structure adjusted as one
+    problem on the same resident handle (sfmloc_sfm_adjust_joint), cleaned again, and the poses written from it."""
     from . import capi as S
     try:
         with open(in_path) as fh:
             doc = json.load(fh)
-        arrays, _, _ = sfm_arrays({**doc, "structure": []})
+        arrays, pose_id, _ = sfm_arrays({**doc, "structure": []})
         stems = view_files(doc)
     except (OSError, ValueError, KeyError, TypeError, IndexError) as e:
         print(f"\nThe input SfM_Data file \"{in_path}\" cannot be read. ({e})", file=sys.stderr)
@@ -122,6 +124,11 @@ def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.
             ba = h.adjust(S.BA_STRUCTURE)
             log(f"Bundle adjustment over structure: {ba.n_blocks} landmarks, cost {ba.cost_initial:g} -> {ba.cost_final:g}")
             clean()
+        if joint:
+            jr = h.adjust_joint(S.BA_ROTATION | S.BA_TRANSLATION | S.BA_STRUCTURE)
+            log(f"Bundle adjustment over rotations, translations, structure: cost {jr.cost_initial:g} -> "
+                f"{jr.cost_final:g}, {jr.steps_accepted} of {jr.steps_tried} steps")
+            clean()
         q = h.read(masks=True)
         X = h.read_structure()
     except S.SfmlocError as e:
@@ -133,6 +140,10 @@ def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.
     out = dict(doc)
     out["structure"] = structure_entries(arrays["view_id"], t.off, t.view, t.feat, a["obs_x"], X, q["landmark_keep"],
                                          q["obs_keep"])
+    if joint:
+        out["extrinsics"] = [{"key": p, "value": {"rotation": [[float(x) for x in row] for row in q["pose_R"][i]],
+                                                  "center": [float(x) for x in q["pose_C"][i]]}}
+                             for i, p in enumerate(pose_id) if q["pose_valid"][i]]
     out["control_points"] = []
     log(f"#landmark found: {len(out['structure'])}")
     with open(out_path, "w") as fh:
