@@ -1030,6 +1030,74 @@ double sfmloc_relpose_last_ms(void);
 int  sfmloc_debug_five_point(int device, const double *in, int n, double *out);
 
 /* ------------------------------------------------------------------------- */
+/* Wedge scales (the ratio of two pair baselines from the depths of the features the pairs share: what fixes the        */
+/* spacing of cameras along a line, where pairwise directions say nothing; OpenMVG gets it from triplet translations).  */
+/* A wedge is two pairs k < l of the pair list that share a view v.  The arrays are those of sfmloc_relative_poses      */
+/* (view_wh is not needed), rel_R / rel_t and inlier_off / inlier_idx its results (sfmloc_relpose_result's R, t;        */
+/* sfmloc_relpose_inliers), use_pair[k] = 0 (NULL: all 1) leaves a pair out.  tests/pairscales_np.py restates every     */
+/* operation.  f64, unfused, only + - * / sqrt:                                                                          */
+/*   bearings    as "bearings" of the relative poses, for the inlier matches only.                                       */
+/*   depths      every inlier match of a used pair is triangulated from [I | 0] and [R | t] by "cheirality" of the       */
+/*               relative poses.  It yields z_I = X_2 and z_J = (R X + t)_2 when the point exists, z_J is finite and     */
+/*               both are positive; otherwise nothing.                                                                    */
+/*   lists       per pair and side, the yielded depths keyed by the feature index in that side's view, ascending by      */
+/*               feature.  Of the yielding matches of a pair that name the same feature of a view, the first in the      */
+/*               order of the inlier list is kept (each side decides for itself).  Built by two stable radix sorts of    */
+/*               all (pair side, feature) entries at once (csrc/radix_sort.h), so a pair may have any number of inliers. */
+/*   candidates  per view, its used pairs ascending by pair index (built on the host); every two of them are a           */
+/*               candidate.  A view of at most 64 pairs is enumerated by one lane, a larger one by one wave.             */
+/*   count       one wave per candidate: the features of the shorter of v's two lists are looked up in the longer by     */
+/*               binary search; n_shared = the features in both.  A candidate with n_shared < min_shared is not emitted. */
+/*               The others are compacted (flag, scan, scatter) and ordered by (k, l, view) by three stable radix sorts.  */
+/*   ratio       one workgroup per record: the shared features in ascending feature order, the first max_shared of them, */
+/*               give q_f = z_k(f) / z_l(f) (the depths of f in view v); ratio = the lower median of q in the order      */
+/*               (value, feature), element (n - 1) / 2 of n, sorted in LDS.  It estimates b_l / b_k, the two baselines   */
+/*               in one unit, since rel_t has unit length in both pairs.  n_shared reports all shared features, also     */
+/*               beyond max_shared.                                                                                       */
+/* No float atomics; nothing but a selection follows the depths: two runs give the same bits, and a record does not      */
+/* depend on the other pairs or on the order of the pair list (which only decides which pair of a wedge is k).           */
+/* Refusals, all on the host before any launch, the text naming the pair: every check of sfmloc_relative_poses, an       */
+/* inlier position out of its pair's range, inlier offsets that are not monotone, a non-finite rel_R or rel_t,           */
+/* min_shared < 1, max_shared outside 1 .. 2048: SFMLOC_EINVAL; 2^30 pairs, more than 2^31 - 1024 inliers or candidates: */
+/* SFMLOC_ECAP.                                                                                                           */
+/* n_pairs = 0 gives an empty handle.  Consumer: sfmloc_global_poses_scaled ("Scaled global poses" below).              */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_wscales sfmloc_wscales;
+typedef struct sfmloc_wscales_options {
+  uint32_t min_shared;   /* default 8 */
+  uint32_t max_shared;   /* default 2048, which is also the most */
+} sfmloc_wscales_options;
+typedef struct sfmloc_wscale {
+  uint32_t view, k, l, n_shared;   /* k < l: positions in the pair list */
+  double   ratio;                  /* b_l / b_k */
+} sfmloc_wscale;
+typedef struct sfmloc_wscales_report {
+  uint32_t n_pairs, n_pairs_used;
+  uint32_t n_inliers;      /* inlier matches of the used pairs */
+  uint32_t n_depths;       /* of them, the ones that yield depths */
+  uint32_t n_candidates, n_wedges;
+  uint32_t launches, reserved;
+  double   device_ms;      /* HIP events around the call's kernels and copies */
+} sfmloc_wscales_report;
+void sfmloc_wscales_default_options(sfmloc_wscales_options *o);
+/* opt NULL = the defaults */
+int  sfmloc_wedge_scales(int device, const uint64_t *view_off /*[n_views+1]*/, uint32_t n_views, const float *kpt_xy,
+                         const uint32_t *view_intrinsic /*[n_views]*/, const double *intrinsics /*[n*6]*/,
+                         const uint32_t *intrinsic_type, uint32_t n_intrinsics,
+                         const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                         const uint32_t *match_i, const uint32_t *match_j,
+                         const double *rel_R /*[n_pairs*9]*/, const double *rel_t /*[n_pairs*3]*/,
+                         const uint64_t *inlier_off /*[n_pairs+1]*/, const uint32_t *inlier_idx,
+                         const uint8_t *use_pair /*[n_pairs], NULL = all*/,
+                         const sfmloc_wscales_options *opt, sfmloc_wscales **out);
+int  sfmloc_wscales_count(const sfmloc_wscales *w, uint32_t *n_wedges);
+int  sfmloc_wscales_read(const sfmloc_wscales *w, sfmloc_wscale *out /*[n_wedges]*/);
+int  sfmloc_wscales_report_read(const sfmloc_wscales *w, sfmloc_wscales_report *rep);
+void sfmloc_wscales_destroy(sfmloc_wscales *w);
+/* device milliseconds of the calling thread's last sfmloc_wedge_scales */
+double sfmloc_wscales_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
 /* Global poses (the middle stage of openMVG_main_GlobalSfM: rotation averaging and translation averaging over the     */
 /* relative poses of the section above; its result is what "Structure from known poses" starts from).  OpenMVG's       */
 /* source was not at hand: every point below is a reading chosen here, and tests/globalposes_np.py restates each one.   */
@@ -1076,9 +1144,9 @@ int  sfmloc_debug_five_point(int device, const double *in, int n, double *out);
 /*               are summed per view over the pairs to a larger neighbour, then the same way.  Iterations are queued 32 */
 /*               at a time with one small read-back per chunk and per step; a finished solve makes the rest of its      */
 /*               chunk return at once.  No float atomics: two runs give the same bits.                                   */
-/* Known limit: pairwise directions do not determine the spacing along a collinear stretch of cameras.  There only the  */
-/* bound s >= 1 and the Huber term act, and one bad pair can fold two centres together.  Relative scales from shared    */
-/* points (OpenMVG's triplet translations) are not built.                                                                */
+/* Known limit of this call: pairwise directions do not determine the spacing along a collinear stretch of cameras.    */
+/* There only the bound s >= 1 and the Huber term act, and one bad pair can fold two centres together.                  */
+/* sfmloc_global_poses_scaled ("Scaled global poses" below) fixes the spacing from the ratios of sfmloc_wedge_scales.    */
 /* Refusals, all on the host before any launch, the text naming the pair: a view index out of range, a pair naming one  */
 /* view twice, the same unordered pair listed twice, a non-finite entry, |R^T R - I| (largest entry) or | |t| - 1 |     */
 /* above 1e-6: SFMLOC_EINVAL.  n_pairs = 0 gives an empty handle.                                                        */
@@ -1125,6 +1193,68 @@ int  sfmloc_gposes_report_read(const sfmloc_gposes *g, sfmloc_gposes_report *rep
 void sfmloc_gposes_destroy(sfmloc_gposes *g);
 /* device milliseconds of the calling thread's last sfmloc_global_poses */
 double sfmloc_gposes_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
+/* Scaled global poses: sfmloc_global_poses with every translation pair's baseline fixed beforehand from the wedge      */
+/* ratios of sfmloc_wedge_scales, so that cameras along a line keep their spacing.  The arguments of                    */
+/* sfmloc_global_poses, then wedge w = pairs (k, l) = (wedge_kl[2w], wedge_kl[2w+1]) of the pair list with              */
+/* wedge_ratio[w] = b_l / b_k.  "adjacency", "triplets", "component", "chordal" and "IRLS" run exactly as above; the     */
+/* same handle type comes back.  tests/pairscales_np.py restates every point.  The host takes the logarithms and the     */
+/* exponentials; on the device f64, unfused, only + - * / sqrt.                                                          */
+/*   scale graph nodes = the translation pairs of the unscaled call; edges = the wedges with both ends among them and a  */
+/*               finite ratio > 0 ("used").  Connected components by the kernels of csrc/graph_device.h; the one with    */
+/*               the most pairs wins, the one with the smallest pair on a tie.  From here on the translation pairs       */
+/*               (used_t, n_translation_pairs) are the pairs of that component, in_component the views they name (they   */
+/*               are connected, since the two pairs of a wedge share a view), root its smallest view, C_root = 0; the rotations keep   */
+/*               the gauge of "component" (R = I at its root), and R, C of a view outside are zero.  The view component  */
+/*               may be smaller than the unscaled call's: reported (n_scaled_views), not an error.  No used wedge:       */
+/*               every in_component is 0, the reports are filled, no error.                                               */
+/*   scales      y_w = log(ratio_w).  Minimise sum rho(x_l - x_k - y) over the used wedges of the component, Huber in    */
+/*               |x_l - x_k - y| with scale_delta (default 0.1), x of the component's smallest pair fixed at 0, from     */
+/*               x = 0, by "IRLS" as for the rotations: per node sum_w w (dx_v - dx_n) = -+ w r (- in l's row, + in     */
+/*               k's), by "PCG" with one value per node and preconditioner 1 / sum w, over a CSR adjacency of the scale  */
+/*               graph (a node's wedges ascending by neighbour pair, built on the host; nodes of more than 64 wedges     */
+/*               are gathered by a wave); x <- x + dx; the step rule and the stop codes of "IRLS".  Then b = exp(x)      */
+/*               divided by the lower median of exp(x) over the translation pairs (element (n - 1) / 2 of n, sorted);    */
+/*               b of every other pair is 0.                                                                              */
+/*   centres     "translation" with r = (C_j - C_i) - b_k d_k and W = w I: Huber with translation_delta, whose default   */
+/*               keeps its meaning as the median baseline is 1; the same Levenberg-Marquardt loop and PCG.               */
+/* Known limit: a pair with no used wedge in the winning component drops out of the translation stage, and with it a     */
+/* view that only such pairs reach.                                                                                       */
+/* Refusals: those of sfmloc_global_poses; a wedge index out of range, k >= l, the same (k, l) twice, a wedge whose two   */
+/* pairs share no view, scale_delta or a tolerance out of range: SFMLOC_EINVAL, before any launch.                        */
+/* (The accessors are named sfmloc_gpscale_*: the handle is a sfmloc_gposes, and its sfmloc_gposes_* accessors serve it   */
+/* unchanged.)                                                                                                            */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_gpscale_options {
+  double   scale_delta;         /* Huber delta on the log ratio, default 0.1 */
+  double   function_tolerance;  /* default 1e-6 */
+  double   pcg_tolerance;       /* default 1e-6 */
+  uint32_t max_steps;           /* default 50 */
+  uint32_t max_pcg;             /* default 20000 iterations per solve */
+} sfmloc_gpscale_options;
+typedef struct sfmloc_gpscale_report {
+  uint32_t n_wedges, n_wedges_used;      /* given; edges of the scale graph */
+  uint32_t n_scaled_pairs, n_scaled_views; /* the winning component: its pairs, the views they name */
+  uint32_t first_pair;                   /* its smallest pair, x = 0 */
+  uint32_t steps_tried, steps_accepted, pcg_total, stop;   /* as rot_* of sfmloc_gposes_report */
+  uint32_t launches;                     /* of the scale phase; sfmloc_gposes_report::launches counts the whole call */
+  double   cost_initial, cost_final;     /* the robust cost at x = 0 and at the result */
+  double   scale_ms;                     /* device time of the scale graph and the scale averaging */
+  double   centre_ms;                    /* = sfmloc_gposes_report::translation_ms */
+} sfmloc_gpscale_report;
+void sfmloc_gpscale_default_options(sfmloc_gpscale_options *o);
+/* opt, sopt NULL = the defaults */
+int  sfmloc_global_poses_scaled(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs,
+                                const double *rel_R /*[n_pairs*9]*/, const double *rel_t /*[n_pairs*3]*/,
+                                const uint8_t *use_t /*[n_pairs], NULL = all*/, const sfmloc_gposes_options *opt,
+                                const uint32_t *wedge_kl /*[n_wedges*2]*/, const double *wedge_ratio /*[n_wedges]*/,
+                                uint32_t n_wedges, const sfmloc_gpscale_options *sopt, sfmloc_gposes **out);
+/* b [n_pairs]: the baselines, 0 outside the translation pairs; all 0 on a handle of sfmloc_global_poses */
+int  sfmloc_gpscale_baselines(const sfmloc_gposes *g, double *b /*[n_pairs]*/);
+/* w [n_wedges]: the Huber weight of every wedge at the result, 0 for a wedge that is not used or outside the component */
+int  sfmloc_gpscale_weights(const sfmloc_gposes *g, double *w /*[n_wedges]*/);
+int  sfmloc_gpscale_report_read(const sfmloc_gposes *g, sfmloc_gpscale_report *rep);
 
 /* ------------------------------------------------------------------------- */
 /* Colouring plan of a map's landmarks (ColorizeTracks of openMVG_main_ComputeSfM_DataColor, the program the          */

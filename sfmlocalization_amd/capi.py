@@ -41,6 +41,11 @@ TriangulateOptions = _abi.struct("sfmloc_triangulate_options")
 TriangulateReport = _abi.struct("sfmloc_triangulate_report")
 RelposeOptions = _abi.struct("sfmloc_relpose_options")
 RelposeResult = _abi.struct("sfmloc_relpose_result")
+WscalesOptions = _abi.struct("sfmloc_wscales_options")
+Wscale = _abi.struct("sfmloc_wscale")
+WscalesReport = _abi.struct("sfmloc_wscales_report")
+GpscaleOptions = _abi.struct("sfmloc_gpscale_options")
+GpscaleReport = _abi.struct("sfmloc_gpscale_report")
 GposesOptions = _abi.struct("sfmloc_gposes_options")
 GposesPair = _abi.struct("sfmloc_gposes_pair")
 GposesReport = _abi.struct("sfmloc_gposes_report")
@@ -1140,6 +1145,79 @@ class RelPoses:
         return self.inl_idx[int(self.inl_off[k]):int(self.inl_off[k + 1])]
 
 
+# sfmloc_wscale as a NumPy record (four uint32, one double: no padding)
+WSCALE = np.dtype([("view", np.uint32), ("k", np.uint32), ("l", np.uint32), ("n_shared", np.uint32),
+                   ("ratio", np.float64)], align=True)
+
+
+def wscales_default_options(**overrides):
+    """sfmloc_wscales_default_options -> WscalesOptions (min_shared 8, max_shared 2048)"""
+    o = WscalesOptions()
+    _L().sfmloc_wscales_default_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def wscales_last_ms():
+    """device milliseconds of the calling thread's last sfmloc_wedge_scales"""
+    return float(_L().sfmloc_wscales_last_ms())
+
+
+class WedgeScales:
+    """sfmloc_wedge_scales: the ratio of the baselines of every two pairs that share a view, from the depths of the
+    features they share (include/sfmloc.h "Wedge scales" states the semantics).  The view and pair arrays are RelPoses'
+    (without view_wh); rel_R [P, 3, 3], rel_t [P, 3], inl_off [P + 1], inl_idx its results; use_pair [P] or None (all);
+    options: the fields of sfmloc_wscales_options.  -> records (WSCALE [n_wedges], ordered by (k, l, view)), report
+    (WscalesReport), ms."""
+
+    def __init__(self, view_off, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j,
+                 rel_R, rel_t, inl_off, inl_idx, use_pair=None, device=0, **options):
+        view_off = np.ascontiguousarray(view_off, np.uint64)
+        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
+        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
+        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
+        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
+        rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
+        rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
+        inl_off, inl_idx = np.ascontiguousarray(inl_off, np.uint64), np.ascontiguousarray(inl_idx, np.uint32)
+        if use_pair is not None:
+            use_pair = np.ascontiguousarray(np.asarray(use_pair) != 0, np.uint8)
+        n_views, P = len(view_off) - 1, len(pairs)
+        if len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
+                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
+            raise ValueError("view arrays differ in length")
+        if len(offsets) != P + 1 or len(match_i) != len(match_j) or (P and int(offsets[-1]) != len(match_i)):
+            raise ValueError("pair list arrays differ in length")
+        if len(rel_R) != P or len(rel_t) != P or len(inl_off) != P + 1 or (use_pair is not None and len(use_pair) != P) \
+                or (P and int(inl_off[-1]) > len(inl_idx)):
+            raise ValueError("pose or inlier arrays differ in length")
+        opt = wscales_default_options(**options)
+        h = C.c_void_p()
+        _check(_L().sfmloc_wedge_scales(int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float),
+                                        _ptr(view_intrinsic, C.c_uint32), _ptr(intrinsics, C.c_double),
+                                        _ptr(intrinsic_type, C.c_uint32), len(intrinsics), _ptr(pairs, C.c_uint32), P,
+                                        _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32),
+                                        _ptr(rel_R, C.c_double), _ptr(rel_t, C.c_double), _ptr(inl_off, C.c_uint64),
+                                        _ptr(inl_idx, C.c_uint32), None if use_pair is None else _ptr(use_pair, C.c_uint8),
+                                        C.byref(opt), C.byref(h)))
+        try:
+            n = C.c_uint32()
+            _check(_L().sfmloc_wscales_count(h, C.byref(n)))
+            self.records = np.zeros(n.value, WSCALE)
+            _check(_L().sfmloc_wscales_read(h, _ptr(self.records, Wscale) if n.value else None))
+            self.report = WscalesReport()
+            _check(_L().sfmloc_wscales_report_read(h, C.byref(self.report)))
+            self.ms = wscales_last_ms()
+        finally:
+            _L().sfmloc_wscales_destroy(h)
+
+
 # sfmloc_gposes_pair as a NumPy record (four uint32, two doubles: no padding)
 GPOSES_PAIR = np.dtype([("n_triplets", np.uint32), ("n_triplets_ok", np.uint32), ("kept", np.uint32),
                         ("used_t", np.uint32), ("rot_residual", np.float64), ("trans_residual", np.float64)], align=True)
@@ -1161,13 +1239,27 @@ def gposes_last_ms():
     return float(_L().sfmloc_gposes_last_ms())
 
 
+def gpscale_default_options(**overrides):
+    """sfmloc_gpscale_default_options -> GpscaleOptions (0.1, 1e-6, 1e-6, 50, 20000)"""
+    o = GpscaleOptions()
+    _L().sfmloc_gpscale_default_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 class GlobalPoses:
     """sfmloc_global_poses: rotation and translation averaging over relative poses (include/sfmloc.h "Global poses"
     states the semantics).  pairs [P, 2] view indices, rel_R [P, 3, 3] and rel_t [P, 3] in sfmloc_relpose_result's
     convention, use_t [P] or None (all); options: the fields of sfmloc_gposes_options.  -> in_component [n] bool,
-    R [n, 3, 3], C [n, 3], pairs (GPOSES_PAIR [P]), report (GposesReport), ms."""
+    R [n, 3, 3], C [n, 3], pairs (GPOSES_PAIR [P]), report (GposesReport), ms.
+    wedges (a WSCALE array, or (kl [W, 2], ratio [W])): sfmloc_global_poses_scaled ("Scaled global poses") instead, with
+    scale = the fields of sfmloc_gpscale_options; then also baselines [P], wedge_weights [W], scale_report
+    (GpscaleReport)."""
 
-    def __init__(self, n_views, pairs, rel_R, rel_t, use_t=None, device=0, **options):
+    def __init__(self, n_views, pairs, rel_R, rel_t, use_t=None, device=0, wedges=None, scale=None, **options):
         pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
         rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
         rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
@@ -1178,10 +1270,33 @@ class GlobalPoses:
         n, P = int(n_views), len(pairs)
         opt = gposes_default_options(**options)
         h = C.c_void_p()
-        _check(_L().sfmloc_global_poses(int(device), n, _ptr(pairs, C.c_uint32), P, _ptr(rel_R, C.c_double),
-                                        _ptr(rel_t, C.c_double), None if use_t is None else _ptr(use_t, C.c_uint8),
-                                        C.byref(opt), C.byref(h)))
+        if wedges is None:
+            if scale is not None:
+                raise ValueError("scale options without wedges")
+            _check(_L().sfmloc_global_poses(int(device), n, _ptr(pairs, C.c_uint32), P, _ptr(rel_R, C.c_double),
+                                            _ptr(rel_t, C.c_double), None if use_t is None else _ptr(use_t, C.c_uint8),
+                                            C.byref(opt), C.byref(h)))
+        else:
+            if isinstance(wedges, np.ndarray) and wedges.dtype.names:
+                wedges = (np.stack([wedges["k"], wedges["l"]], 1), wedges["ratio"])
+            kl = np.ascontiguousarray(wedges[0], np.uint32).reshape(-1, 2)
+            ratio = np.ascontiguousarray(wedges[1], np.float64).reshape(-1)
+            if len(kl) != len(ratio):
+                raise ValueError("wedge arrays differ in length")
+            sopt = gpscale_default_options(**(scale or {}))
+            _check(_L().sfmloc_global_poses_scaled(int(device), n, _ptr(pairs, C.c_uint32), P, _ptr(rel_R, C.c_double),
+                                                   _ptr(rel_t, C.c_double),
+                                                   None if use_t is None else _ptr(use_t, C.c_uint8), C.byref(opt),
+                                                   _ptr(kl, C.c_uint32) if len(kl) else None,
+                                                   _ptr(ratio, C.c_double) if len(kl) else None, len(kl), C.byref(sopt),
+                                                   C.byref(h)))
         try:
+            if wedges is not None:
+                self.baselines, self.wedge_weights = np.zeros(P), np.zeros(len(kl))
+                _check(_L().sfmloc_gpscale_baselines(h, _ptr(self.baselines, C.c_double) if P else None))
+                _check(_L().sfmloc_gpscale_weights(h, _ptr(self.wedge_weights, C.c_double) if len(kl) else None))
+                self.scale_report = GpscaleReport()
+                _check(_L().sfmloc_gpscale_report_read(h, C.byref(self.scale_report)))
             inc = np.zeros(max(1, n), np.uint8)
             self.R, self.C = np.zeros((max(1, n), 3, 3)), np.zeros((max(1, n), 3))
             _check(_L().sfmloc_gposes_views(h, _ptr(inc, C.c_uint8), _ptr(self.R, C.c_double), _ptr(self.C, C.c_double)))

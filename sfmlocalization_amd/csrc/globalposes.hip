@@ -11,7 +11,8 @@
 //               itself by the same fixed tree (gp_sum): store, then sum.  No kernel waits for another workgroup.
 //   one PCG     k_gp_apply / k_gp_step1 / k_gp_step2, templated on the block kind: 0 the chordal system (3 x 3 blocks
 //               rel_R, 9 values per view), 1 the IRLS system (scalar weights, 3 values per view), 2 the translations
-//               (3 x 3 blocks W, 3 values per view).  The host passes the iteration number; a solve that has stopped at
+//               (3 x 3 blocks W, 3 values per view), 3 the scales of sfmloc_global_poses_scaled (scalar weights, 1 value
+//               per node: there the "views" of GpDev are the pairs and its "pairs" the wedges).  The host passes the iteration number; a solve that has stopped at
 //               iteration done_at makes every later queued launch return at once.  kPcgChunk iterations are queued
 //               between two looks at the state record.
 // f64, unfused (-ffp-contract=off), only + - * / sqrt on the device.
@@ -27,6 +28,7 @@
 #include "geom_device.h"
 #include "globalposes_host.h"
 #include "graph_device.h"
+#include "pairscales_host.h"
 #include "sfmloc_internal.h"
 
 namespace sfmloc {
@@ -46,7 +48,23 @@ struct Gposes {
   std::vector<double> R, C;
   std::vector<sfmloc_gposes_pair> pairs;
   sfmloc_gposes_report rep{};
+  std::vector<double> base, wedge_w;  // sfmloc_global_poses_scaled: per pair, per wedge
+  sfmloc_gpscale_report srep{};
 };
+
+// what sfmloc_global_poses_scaled adds to the arguments
+struct GpScaleIn {
+  const uint32_t *kl;
+  const double *ratio;
+  uint32_t n_wedges;
+  sfmloc_gpscale_options opt;
+};
+
+// values per view (node) of a block kind
+template <int KIND>
+constexpr int gp_nv() {
+  return KIND == 0 ? 9 : KIND == 3 ? 1 : 3;
+}
 
 struct GpState {
   double lam, nu, cost, cost0, cost_new, model, rz[2], rr0, rr, pcg_tol, ftol;
@@ -59,6 +77,7 @@ struct GpDev {
   const uint32_t *adj_off, *adj_nbr, *adj_pe, *heavy, *pairs;
   const double *relR, *relt;
   const uint8_t *use_t, *inc;
+  const double *base;  // sfmloc.h "centres": the fixed baseline per pair; null in sfmloc_global_poses
   uint32_t *ntri, *nok;
   uint8_t *erot, *etr;
   double *R, *Rn, *C, *Cn;
@@ -264,12 +283,13 @@ __device__ __forceinline__ void gp_start(const GpDev &D, uint32_t v, bool active
   }
 }
 
-// KIND 0 "chordal", 1 "IRLS" (after k_gp_rot_edges), 2 "translation" (after k_gp_tr_edges): the view's diagonal, its
+// KIND 0 "chordal", 1 "IRLS" (after k_gp_rot_edges), 2 "translation" (after k_gp_tr_edges), 3 "scales" (after
+// k_gp_sc_edges): the view's diagonal, its
 // preconditioner and right-hand side; partials: r.z, r.r, and the cost over the pairs to a larger neighbour
 template <int KIND>
 __global__ __launch_bounds__(256) void k_gp_setup(GpDev D) {
   __shared__ double sh[4];
-  constexpr int NV = KIND == 0 ? 9 : 3;
+  constexpr int NV = gp_nv<KIND>();
   uint32_t v = 0;
   bool wave = false;
   const bool have = gp_pick(D, &v, &wave);
@@ -319,7 +339,21 @@ __global__ __launch_bounds__(256) void k_gp_setup(GpDev D) {
       if (gp_owner(wave)) D.diag[v] = acc[3];
       cost = acc[4];
     }
-    if constexpr (KIND == 1) if (!active && D.inc[v]) {  // (the root: only its share of the cost)
+    if constexpr (KIND == 3) if (active) {
+      double acc[3];
+      gp_gather(D, v, wave, acc, [&](uint32_t t, double(&a)[3]) {
+        const uint32_t pe = D.adj_pe[t], k = pe & ~kDirBit;
+        if (!D.erot[k]) return;
+        a[1] += D.ew[k];
+        a[0] += ((pe & kDirBit) ? -1.0 : 1.0) * D.ev[k];  // b = -gradient: - in l's row, + in k's
+        if (D.adj_nbr[t] > v) a[2] += D.rho[k];
+      });
+      b[0] = acc[0];
+      z[0] = acc[1] > 0.0 ? acc[0] / acc[1] : 0.0;
+      if (gp_owner(wave)) D.diag[v] = acc[1];
+      cost = acc[2];
+    }
+    if constexpr (KIND == 1 || KIND == 3) if (!active && D.inc[v]) {  // (the root: only its share of the cost)
       double acc[1];
       gp_gather(D, v, wave, acc, [&](uint32_t t, double(&a)[1]) {
         const uint32_t k = D.adj_pe[t] & ~kDirBit;
@@ -407,7 +441,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_gp_apply(GpDev D, uint32_t it) {
   __shared__ double sh[4];
   if (D.st->done_at <= it) return;
-  constexpr int NV = KIND == 0 ? 9 : 3;
+  constexpr int NV = gp_nv<KIND>();
   uint32_t v = 0;
   bool wave = false;
   double pq = 0.0;
@@ -422,10 +456,10 @@ __global__ __launch_bounds__(256) void k_gp_apply(GpDev D, uint32_t it) {
         gp_mul(D.relR + 9 * (size_t)k, !(pe & kDirBit), pn, y);
 #pragma unroll
         for (int i = 0; i < 9; ++i) a[i] += y[i];
-      } else if constexpr (KIND == 1) {
+      } else if constexpr (KIND == 1 || KIND == 3) {
         const double w = D.ew[k];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) a[i] += w * pn[i];
+        for (int i = 0; i < NV; ++i) a[i] += w * pn[i];
       } else {
         double y[3];
         gp_mulv(D.W + 9 * (size_t)k, false, pn, y);
@@ -460,7 +494,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_gp_step1(GpDev D, uint32_t it) {
   __shared__ double sh[4];
   if (D.st->done_at <= it) return;
-  constexpr int NV = KIND == 0 ? 9 : 3;
+  constexpr int NV = gp_nv<KIND>();
   const double pq = gp_sum(D.part, D.n_part, sh);
   const double alpha = D.st->rz[it & 1] / pq;
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
@@ -504,7 +538,7 @@ __global__ __launch_bounds__(256) void k_gp_step2(GpDev D, uint32_t it) {
   __shared__ double sh[4];
   GpState *st = D.st;
   if (st->done_at <= it) return;
-  constexpr int NV = KIND == 0 ? 9 : 3;
+  constexpr int NV = gp_nv<KIND>();
   const double pq = gp_sum(D.part, D.n_part, sh);
   const double rzn = gp_sum(D.part + D.n_part, D.nb_view, sh);
   const double rr = gp_sum(D.part + 2 * D.n_part, D.nb_view, sh);
@@ -653,7 +687,7 @@ __global__ __launch_bounds__(256) void k_gp_tr_edges(GpDev D, const double *Cs, 
 #pragma unroll
     for (int i = 0; i < 3; ++i) dl[i] = Cs[3 * (size_t)J + i] - Cs[3 * (size_t)I + i];
     s = (d[0] * dl[0] + d[1] * dl[1]) + d[2] * dl[2];
-    const double sc = s > 1.0 ? s : 1.0;
+    const double sc = D.base ? D.base[k] : (s > 1.0 ? s : 1.0);  // sfmloc.h "centres": the baseline is given
 #pragma unroll
     for (int i = 0; i < 3; ++i) r[i] = dl[i] - sc * d[i];
     nr = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
@@ -676,17 +710,50 @@ __global__ __launch_bounds__(256) void k_gp_tr_edges(GpDev D, const double *Cs, 
     D.ev[3 * (size_t)k + i] = w * r[i];
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-      D.W[9 * (size_t)k + 3 * i + j] = on ? w * ((i == j ? 1.0 : 0.0) - (s > 1.0 ? d[i] * d[j] : 0.0)) : 0.0;
+      D.W[9 * (size_t)k + 3 * i + j] = on ? w * ((i == j ? 1.0 : 0.0) - ((!D.base && s > 1.0) ? d[i] * d[j] : 0.0)) : 0.0;
   }
+}
+
+// sfmloc.h "scales": per wedge (the "pairs" of this GpDev; its "views" are the pairs k, l) at the log scales xs, y = the
+// log ratios.  trial: only the cost is written
+__global__ __launch_bounds__(256) void k_gp_sc_edges(GpDev D, const double *xs, const double *y, double delta, int trial) {
+  const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= D.n_pairs) return;
+  double r = 0.0, w = 0.0, rho = 0.0, s = 0.0;
+  if (D.erot[e]) {
+    r = (xs[D.pairs[2 * (size_t)e + 1]] - xs[D.pairs[2 * (size_t)e]]) - y[e];
+    s = r < 0.0 ? -r : r;
+    gp_huber(s, delta, &w, &rho);
+  }
+  D.rho[e] = rho;
+  if (trial) return;
+  D.ew[e] = w;
+  D.res[e] = s;
+  D.mterm[e] = 0.0;
+  D.ev[e] = w * r;
+}
+
+// parent[i] = i over the pairs; the edge list of graph_device.h over the wedges: one that is not used joins k to itself
+__global__ __launch_bounds__(256) void k_gp_sc_cc(const uint32_t *kl, const uint8_t *on, uint32_t n_wedges, uint32_t n_pairs,
+                                                  uint32_t *ea, uint32_t *eb, uint32_t *parent) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_pairs) parent[i] = i;
+  if (i >= n_wedges) return;
+  ea[i] = kl[2 * (size_t)i];
+  eb[i] = on[i] ? kl[2 * (size_t)i + 1] : kl[2 * (size_t)i];
 }
 
 // ---- a step: trial, cost, decision, commit ---------------------------------------------------------------------------
 
-// kind 1: Rn = R Cayley(x); kind 2: Cn = C + x
+// kind 1: Rn = R Cayley(x); kind 2: Cn = C + x; kind 3: the same on one value per node
 __global__ __launch_bounds__(256) void k_gp_trial(GpDev D, int kind) {
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v >= D.n) return;
   const bool active = gp_active(D, v);
+  if (kind == 3) {
+    D.Cn[v] = active ? D.C[v] + D.x[v] : D.C[v];
+    return;
+  }
   const double *x = D.x + 3 * (size_t)v;
   if (kind == 2) {
 #pragma unroll
@@ -808,7 +875,9 @@ __global__ __launch_bounds__(256) void k_gp_commit(GpDev D, int kind) {
   if (!D.st->take) return;
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v >= D.n) return;
-  if (kind == 2) {
+  if (kind == 3) {
+    D.C[v] = D.Cn[v];
+  } else if (kind == 2) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) D.C[3 * (size_t)v + i] = D.Cn[3 * (size_t)v + i];
   } else {
@@ -857,7 +926,7 @@ int gp_pcg(const GpDev &D, uint32_t max_pcg, hipStream_t s, uint32_t *launches, 
 
 // the events at the phase boundaries of a call
 struct GpEvents {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   ~GpEvents() {
     for (hipEvent_t x : e)
       if (x) hipEventDestroy(x);
@@ -867,9 +936,10 @@ struct GpEvents {
     SFM_HIP(hipEventRecord(e[i], s));
     return SFMLOC_OK;
   }
-  int between(int i, double *ms) {  // (after the stream has been synchronised)
+  int between(int i, double *ms) { return span(i, i + 1, ms); }
+  int span(int i, int j, double *ms) {  // (after the stream has been synchronised)
     float f = 0.f;
-    SFM_HIP(hipEventElapsedTime(&f, e[i], e[i + 1]));
+    SFM_HIP(hipEventElapsedTime(&f, e[i], e[j]));
     *ms = f;
     return SFMLOC_OK;
   }
@@ -889,9 +959,167 @@ GpState gp_state0(const sfmloc_gposes_options &o) {
   return st;
 }
 
+// sfmloc.h "Scaled global poses": "scale graph" and "scales", after the rotations.  On return the translation pairs
+// (g->pairs[].used_t, *etr), the view component (g->in_comp, the report) and D.inc / D.etr / D.root / D.base are those of
+// the centres; *none: no wedge is used, nothing follows.
+int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpScaleIn &sc, const uint32_t *pairs,
+                   hipStream_t s, uint32_t *launches, Gposes *g, std::vector<uint8_t> *etr, bool *none) {
+  sfmloc_gposes_report &rep = g->rep;
+  sfmloc_gpscale_report &sr = g->srep;
+  const size_t P = D.n_pairs, n = D.n, W = sc.n_wedges;
+  const uint32_t launches0 = *launches;
+  std::vector<uint8_t> on(W ? W : 1, 0);
+  std::vector<double> y(W ? W : 1, 0.0);
+  for (size_t w = 0; w < W; ++w) {
+    const double q = sc.ratio[w];
+    on[w] = g->pairs[sc.kl[2 * w]].used_t && g->pairs[sc.kl[2 * w + 1]].used_t && isfinite(q) && q > 0.0;
+    if (on[w]) y[w] = log(q);
+    sr.n_wedges_used += on[w];
+  }
+  DevBuf<uint32_t> d_kl;
+  DevBuf<uint8_t> d_on;
+  uint32_t first = 0, size = 0;
+  if (sr.n_wedges_used) {
+    DevBuf<uint32_t> d_ea, d_eb, d_parent, d_flag;
+    GP_TRY(dev_upload(nullptr, d_kl, sc.kl, 2 * W, s));
+    GP_TRY(dev_upload(nullptr, d_on, on.data(), W, s));
+    GP_TRY(d_ea.alloc(nullptr, W));
+    GP_TRY(d_eb.alloc(nullptr, W));
+    GP_TRY(d_parent.alloc(nullptr, P));
+    GP_TRY(d_flag.alloc(nullptr, 1));
+    const uint32_t gw = (uint32_t)((W + 255) / 256), gn = (uint32_t)((P + 255) / 256);
+    GP_LAUNCH(k_gp_sc_cc, gw > gn ? gw : gn, (const uint32_t *)d_kl, (const uint8_t *)d_on, (uint32_t)W, (uint32_t)P, d_ea.get(),
+              d_eb.get(), d_parent.get());
+    for (;;) {
+      SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+      GP_LAUNCH(k_graph_hook, gw, (const uint32_t *)d_ea, (const uint32_t *)d_eb, (uint32_t)W, d_parent.get(), d_flag.get());
+      GP_LAUNCH(k_graph_jump, gn, d_parent.get(), (uint32_t)P);
+      SFM_HIP(hipGetLastError());
+      uint32_t changed = 0;
+      SFM_HIP(hipMemcpyAsync(&changed, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      SFM_HIP(hipStreamSynchronize(s));
+      if (!changed) break;
+    }
+    std::vector<uint32_t> label(P);
+    SFM_HIP(hipMemcpyAsync(label.data(), d_parent, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipStreamSynchronize(s));
+    gposes_host::pick_component(label, &first, &size);
+    etr->assign(P, 0);
+    if (size >= 2)
+      for (size_t k = 0; k < P; ++k) (*etr)[k] = label[k] == first;
+  }
+  g->in_comp.assign(n, 0);
+  rep.n_translation_pairs = rep.n_component_views = rep.root = 0;
+  if (size < 2) {
+    for (size_t k = 0; k < P; ++k) g->pairs[k].used_t = 0;
+    sr.launches = *launches - launches0;
+    *none = true;
+    return SFMLOC_OK;
+  }
+  for (size_t k = 0; k < P; ++k) {
+    g->pairs[k].used_t = (*etr)[k];
+    if ((*etr)[k]) g->in_comp[pairs[2 * k]] = g->in_comp[pairs[2 * k + 1]] = 1;
+  }
+  uint32_t root = 0;
+  for (size_t v = n; v-- > 0;)
+    if (g->in_comp[v]) {
+      ++rep.n_component_views;
+      root = (uint32_t)v;
+    }
+  rep.root = root;
+  rep.n_translation_pairs = sr.n_scaled_pairs = size;
+  sr.n_scaled_views = rep.n_component_views;
+  sr.first_pair = first;
+
+  // "scales": the GpDev whose views are the pairs and whose pairs are the wedges
+  for (size_t w = 0; w < W; ++w) on[w] = on[w] && (*etr)[sc.kl[2 * w]];
+  wscales_host::ScaleGraph sg;
+  wscales_host::scale_adjacency((uint32_t)P, sc.kl, on.data(), (uint32_t)W, &sg);
+  GpDev S;
+  memset(&S, 0, sizeof S);
+  S.n = (uint32_t)P;
+  S.n_pairs = (uint32_t)W;
+  S.nb_view = (uint32_t)((P + 255) / 256);
+  S.n_heavy = (uint32_t)sg.heavy.size();
+  S.n_part = S.nb_view + (S.n_heavy + 3) / 4;
+  S.root = first;
+  DevBuf<uint32_t> d_off, d_nbr, d_pe, d_heavy;
+  DevBuf<uint8_t> d_sinc;
+  DevBuf<double> d_y, d_ev, d_ew, d_rho, d_res, d_mterm, d_diag, d_x, d_r, d_z, d_p, d_q, d_xs, d_xn, d_part;
+  GP_TRY(dev_upload(nullptr, d_off, sg.off.data(), P + 1, s));
+  GP_TRY(dev_upload(nullptr, d_nbr, sg.nbr.data(), sg.nbr.size(), s));
+  GP_TRY(dev_upload(nullptr, d_pe, sg.pe.data(), sg.pe.size(), s));
+  GP_TRY(dev_upload(nullptr, d_heavy, sg.heavy.data(), sg.heavy.size(), s, 1));
+  GP_TRY(dev_upload(nullptr, d_on, on.data(), W, s));
+  GP_TRY(dev_upload(nullptr, d_sinc, etr->data(), P, s));
+  GP_TRY(dev_upload(nullptr, d_y, y.data(), W, s));
+  for (DevBuf<double> *b : {std::addressof(d_ev), std::addressof(d_ew), std::addressof(d_rho), std::addressof(d_res),
+                            std::addressof(d_mterm)})
+    GP_TRY(b->alloc(nullptr, W));
+  for (DevBuf<double> *b : {std::addressof(d_diag), std::addressof(d_x), std::addressof(d_r), std::addressof(d_z),
+                            std::addressof(d_p), std::addressof(d_q), std::addressof(d_xs), std::addressof(d_xn)})
+    GP_TRY(b->alloc(nullptr, P));
+  GP_TRY(d_part.alloc(nullptr, 3 * (size_t)S.n_part));
+  SFM_HIP(hipMemsetAsync(d_xs, 0, P * sizeof(double), s));
+  SFM_HIP(hipMemsetAsync(d_xn, 0, P * sizeof(double), s));
+  SFM_HIP(hipMemsetAsync(d_mterm, 0, W * sizeof(double), s));
+  S.adj_off = d_off, S.adj_nbr = d_nbr, S.adj_pe = d_pe, S.heavy = d_heavy, S.pairs = d_kl, S.inc = d_sinc, S.erot = d_on;
+  S.C = d_xs, S.Cn = d_xn, S.ev = d_ev, S.ew = d_ew, S.rho = d_rho, S.res = d_res, S.mterm = d_mterm, S.diag = d_diag;
+  S.x = d_x, S.r = d_r, S.z = d_z, S.p = d_p, S.q = d_q, S.part = d_part, S.st = D.st;
+  sfmloc_gposes_options o{};
+  o.function_tolerance = sc.opt.function_tolerance;
+  o.pcg_tolerance = sc.opt.pcg_tolerance;
+  o.max_steps = sc.opt.max_steps;
+  o.max_pcg = sc.opt.max_pcg;
+  GpState h = gp_state0(o);
+  SFM_HIP(hipMemcpyAsync(S.st, &h, sizeof h, hipMemcpyHostToDevice, s));
+  SFM_HIP(hipStreamSynchronize(s));  // (h is reused below)
+  const uint32_t ge = (uint32_t)((W + 255) / 256), gv = S.nb_view, ga = S.n_part;
+  const double delta = sc.opt.scale_delta;
+  while (h.running) {
+    GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);
+    GP_LAUNCH(k_gp_setup<3>, ga, S);
+    GP_LAUNCH(k_gp_begin, 1, S, 1);
+    GP_TRY(gp_pcg<3>(S, sc.opt.max_pcg, s, launches, &h));
+    GP_LAUNCH(k_gp_trial, gv, S, 3);
+    GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xn, (const double *)d_y, delta, 1);
+    GP_LAUNCH(k_gp_cost, ga, S, 1);
+    GP_LAUNCH(k_gp_decide, 1, S, 1);
+    GP_LAUNCH(k_gp_commit, gv, S, 3);
+    GP_TRY(gp_read_state(S, &h, s));
+  }
+  GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);  // the weights at the result
+  std::vector<double> x(P), ew(W);
+  SFM_HIP(hipGetLastError());
+  SFM_HIP(hipMemcpyAsync(x.data(), d_xs, P * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipMemcpyAsync(ew.data(), d_ew, W * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  std::vector<double> bx;
+  for (size_t k = 0; k < P; ++k)
+    if ((*etr)[k]) bx.push_back(exp(x[k]));
+  const double med = wscales_host::lower_median(bx);
+  for (size_t k = 0; k < P; ++k) g->base[k] = (*etr)[k] ? exp(x[k]) / med : 0.0;
+  for (size_t w = 0; w < W; ++w) g->wedge_w[w] = on[w] ? ew[w] : 0.0;
+  sr.steps_tried = h.steps_tried;
+  sr.steps_accepted = h.steps_accepted;
+  sr.pcg_total = h.pcg_total;
+  sr.stop = h.stop;
+  sr.cost_initial = h.cost0;
+  sr.cost_final = h.cost;
+  sr.launches = *launches - launches0;
+  // "centres": what the translation kernels read
+  GP_TRY(dev_upload(nullptr, d_base, g->base.data(), P, s));
+  SFM_HIP(hipMemcpyAsync(d_inc, g->in_comp.data(), n, hipMemcpyHostToDevice, s));
+  SFM_HIP(hipMemcpyAsync(D.etr, etr->data(), P, hipMemcpyHostToDevice, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  D.base = d_base;
+  D.root = root;
+  return SFMLOC_OK;
+}
+
 int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R, const double *rel_t,
-                  const uint8_t *use_t, const sfmloc_gposes_options &opt, const gposes_host::Adjacency &adj, hipStream_t s,
-                  Gposes *g) {
+                  const uint8_t *use_t, const sfmloc_gposes_options &opt, const gposes_host::Adjacency &adj,
+                  const GpScaleIn *sc, hipStream_t s, Gposes *g) {
   sfmloc_gposes_report &rep = g->rep;
   uint32_t *launches = &rep.launches;
   const size_t n = n_views, P = n_pairs;
@@ -1063,6 +1291,14 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
 
   // sfmloc.h "translation"
   GP_TRY(ev.mark(2, s));
+  DevBuf<double> d_base;
+  std::vector<uint8_t> etr_scaled;
+  if (sc) {
+    bool none = false;
+    GP_TRY(gp_scale_phase(D, d_inc.get(), d_base, *sc, pairs, s, launches, g, &etr_scaled, &none));
+    if (none) return SFMLOC_OK;
+    GP_TRY(ev.mark(4, s));
+  }
   GP_LAUNCH(k_gp_dirs, gp, D);
   SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
   h = h0;
@@ -1087,7 +1323,16 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   SFM_HIP(hipStreamSynchronize(s));
   GP_TRY(ev.between(0, &rep.graph_ms));
   GP_TRY(ev.between(1, &rep.rotation_ms));
-  GP_TRY(ev.between(2, &rep.translation_ms));
+  if (sc) {
+    GP_TRY(ev.span(2, 4, &g->srep.scale_ms));
+    GP_TRY(ev.span(4, 3, &rep.translation_ms));
+    g->srep.centre_ms = rep.translation_ms;
+    for (size_t v = 0; v < n; ++v)
+      if (!g->in_comp[v])
+        for (int i = 0; i < 9; ++i) g->R[9 * v + i] = 0.0;
+  } else {
+    GP_TRY(ev.between(2, &rep.translation_ms));
+  }
   for (size_t k = 0; k < P; ++k) g->pairs[k].trans_residual = res[k];
   rep.trans_steps_tried = h.steps_tried;
   rep.trans_steps_accepted = h.steps_accepted;
@@ -1099,11 +1344,19 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
 }
 
 int gposes_impl(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
-                const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options &opt, Gposes *g) {
+                const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options &opt, const GpScaleIn *sc, Gposes *g) {
   gposes_host::Adjacency adj;
   std::string err;
-  const int rc = gposes_host::check(n_views, pairs, n_pairs, rel_R, rel_t, &adj, &err);
+  int rc = gposes_host::check(n_views, pairs, n_pairs, rel_R, rel_t, &adj, &err);
   SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
+  if (sc) {
+    rc = wscales_host::check_wedges(pairs, n_pairs, sc->kl, sc->ratio, sc->n_wedges, &err);
+    SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
+    SFM_CHECK(sc->opt.scale_delta > 0.0 && sc->opt.function_tolerance >= 0.0 && sc->opt.pcg_tolerance >= 0.0, SFMLOC_EINVAL,
+              "sfmloc_global_poses_scaled: scale_delta or a tolerance is out of range");
+    SFM_CHECK(sc->opt.max_pcg >= 1 && sc->opt.max_pcg <= (1u << 30), SFMLOC_EINVAL,
+              "sfmloc_global_poses_scaled: max_pcg = %u", sc->opt.max_pcg);
+  }
   SFM_CHECK(opt.triplet_angle_deg > 0.0 && opt.triplet_angle_deg < 180.0, SFMLOC_EINVAL,
             "sfmloc_global_poses: triplet_angle_deg must lie in (0, 180)");
   SFM_CHECK(opt.translation_delta > 0.0 && opt.function_tolerance >= 0.0 && opt.pcg_tolerance >= 0.0 &&
@@ -1120,10 +1373,13 @@ int gposes_impl(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_
   g->pairs.assign(n_pairs, sfmloc_gposes_pair{});
   g->rep.n_views = n_views;
   g->rep.n_pairs = n_pairs;
+  g->base.assign(n_pairs, 0.0);
+  g->wedge_w.assign(sc ? sc->n_wedges : 0, 0.0);
+  g->srep.n_wedges = sc ? sc->n_wedges : 0;
   if (n_pairs == 0 || n_views == 0) return SFMLOC_OK;  // nothing to launch
   CallScope d;
   if ((rc_dev = d.open(true, &g_gposes_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = gposes_device(n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, adj, d.s, g);
+  rc_dev = gposes_device(n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, adj, sc, d.s, g);
   if (rc_dev) return rc_dev;
   rc_dev = d.time_end();
   g->rep.device_ms = g_gposes_last_ms;
@@ -1152,8 +1408,18 @@ void sfmloc_gposes_default_options(sfmloc_gposes_options *o) {
   o->max_pcg = 20000;
 }
 
-int sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
-                        const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options *opt, sfmloc_gposes **out) {
+void sfmloc_gpscale_default_options(sfmloc_gpscale_options *o) {
+  if (!o) return;
+  o->scale_delta = 0.1;
+  o->function_tolerance = 1e-6;
+  o->pcg_tolerance = 1e-6;
+  o->max_steps = 50;
+  o->max_pcg = 20000;
+}
+
+static int gposes_call(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
+                       const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options *opt, const GpScaleIn *sc,
+                       sfmloc_gposes **out) {
   SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_global_poses: null argument");
   *out = nullptr;
   sfmloc_gposes_options o;
@@ -1163,7 +1429,7 @@ int sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uin
   SFM_CHECK(g, SFMLOC_ENOMEM, "out of host memory");
   int rc;
   try {
-    rc = gposes_impl(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, o, g);
+    rc = gposes_impl(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, o, sc, g);
   } catch (const std::bad_alloc &) {
     set_error("sfmloc_global_poses: out of host memory");
     rc = SFMLOC_ENOMEM;
@@ -1173,6 +1439,43 @@ int sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uin
     return rc;
   }
   *out = reinterpret_cast<sfmloc_gposes *>(g);
+  return SFMLOC_OK;
+}
+
+int sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
+                        const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options *opt, sfmloc_gposes **out) {
+  return gposes_call(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, nullptr, out);
+}
+
+int sfmloc_global_poses_scaled(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
+                               const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options *opt,
+                               const uint32_t *wedge_kl, const double *wedge_ratio, uint32_t n_wedges,
+                               const sfmloc_gpscale_options *sopt, sfmloc_gposes **out) {
+  GpScaleIn sc{wedge_kl, wedge_ratio, n_wedges, {}};
+  if (sopt) sc.opt = *sopt;
+  else sfmloc_gpscale_default_options(&sc.opt);
+  return gposes_call(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, &sc, out);
+}
+
+int sfmloc_gpscale_baselines(const sfmloc_gposes *gg, double *b) {
+  SFM_CHECK(gg, SFMLOC_EINVAL, "sfmloc_gpscale_baselines: null handle");
+  const Gposes *g = reinterpret_cast<const Gposes *>(gg);
+  SFM_CHECK(b || g->base.empty(), SFMLOC_EINVAL, "sfmloc_gpscale_baselines: null argument");
+  if (!g->base.empty()) memcpy(b, g->base.data(), g->base.size() * sizeof(double));
+  return SFMLOC_OK;
+}
+
+int sfmloc_gpscale_weights(const sfmloc_gposes *gg, double *w) {
+  SFM_CHECK(gg, SFMLOC_EINVAL, "sfmloc_gpscale_weights: null handle");
+  const Gposes *g = reinterpret_cast<const Gposes *>(gg);
+  SFM_CHECK(w || g->wedge_w.empty(), SFMLOC_EINVAL, "sfmloc_gpscale_weights: null argument");
+  if (!g->wedge_w.empty()) memcpy(w, g->wedge_w.data(), g->wedge_w.size() * sizeof(double));
+  return SFMLOC_OK;
+}
+
+int sfmloc_gpscale_report_read(const sfmloc_gposes *gg, sfmloc_gpscale_report *rep) {
+  SFM_CHECK(gg && rep, SFMLOC_EINVAL, "sfmloc_gpscale_report_read: null argument");
+  *rep = reinterpret_cast<const Gposes *>(gg)->srep;
   return SFMLOC_OK;
 }
 

@@ -1,13 +1,14 @@
 // ComputeGlobalPoses as a C++ host program over the C ABI (plain g++):
 //
 //   ComputeGlobalPoses -i <sfm_data.json> -p <relative_poses.json> -o <out sfm_data.json>
-//                      [--triplet-angle 5] [--device 0] [-r <report.json>]
+//                      [--triplet-angle 5] [--device 0] [-r <report.json>] [-s <pair_scales.json>]
 //
 // The same program as sfmlocalization_amd/globalposes.py and the same bytes in both output files: rotation and
 // translation averaging over the relative poses of the view pairs (sfmloc_global_poses, the middle stage of
 // openMVG_main_GlobalSfM).  I and J of the poses file are view ids; a pair carries its translation when
 // front[choice] == n_inliers.  The output is the input document with `extrinsics` replaced by the poses of the
-// component's views, keyed by id_pose, and `structure` and `control_points` emptied.
+// component's views, keyed by id_pose, and `structure` and `control_points` emptied.  -s: the wedge ratios of
+// ComputeRelativePoses -s; sfmloc_global_poses_scaled runs instead, and the report gains `scale` and `baselines`.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +19,7 @@
 
 #include "../../include/sfmloc.h"
 #include "sfm_doc.h"
+#include "sfm_files.h"
 #include "sfm_json.h"
 
 using sfmdoc::Doc;
@@ -38,6 +40,7 @@ void usage() {
           "\n[Optional]\n"
           "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
           "[-r|--report_file] the call's report as JSON\n"
+          "[-s|--scales_file] the wedge ratios (pair_scales.json of ComputeRelativePoses -s): fix the pair baselines from them\n"
           "[--device] HIP device (0)\n",
           kName);
 }
@@ -56,7 +59,8 @@ Value rows3(const double *v) {
 
 // the `relative_poses` list -> the call's arrays; false with *err on an entry that cannot be read
 bool pose_arrays(const Value &root, const std::map<uint32_t, uint32_t> &view_index, std::vector<uint32_t> *pairs,
-                 std::vector<double> *R, std::vector<double> *t, std::vector<uint8_t> *use_t, std::string *err) {
+                 std::vector<double> *R, std::vector<double> *t, std::vector<uint8_t> *use_t,
+                 std::map<std::pair<uint32_t, uint32_t>, uint32_t> *pair_index, std::string *err) {
   const Value *list = root.kind == Value::Obj ? root.get("relative_poses") : nullptr;
   if (!list || list->kind != Value::Arr) return *err = "no relative_poses list", false;
   for (const Value &e : list->a) {
@@ -73,6 +77,7 @@ bool pose_arrays(const Value &root, const std::map<uint32_t, uint32_t> &view_ind
     const auto a = view_index.find(I), b = view_index.find(J);
     if (a == view_index.end() || b == view_index.end())
       return *err = "entry " + std::to_string(pairs->size() / 2) + " names an unknown view", false;
+    (*pair_index)[{I, J}] = (uint32_t)(pairs->size() / 2);  // (by view ids: a later entry of the same ids wins, as in Python)
     pairs->push_back(a->second);
     pairs->push_back(b->second);
     R->insert(R->end(), r, r + 9);
@@ -103,10 +108,24 @@ Value report_json(const sfmloc_gposes_report &r) {
   return o;
 }
 
+Value scale_json(const sfmloc_gpscale_report &r) {
+  Value o;
+  o.kind = Value::Obj;
+  const std::pair<const char *, uint32_t> ints[] = {
+      {"n_wedges", r.n_wedges}, {"n_wedges_used", r.n_wedges_used}, {"n_scaled_pairs", r.n_scaled_pairs},
+      {"n_scaled_views", r.n_scaled_views}, {"first_pair", r.first_pair}, {"steps_tried", r.steps_tried},
+      {"steps_accepted", r.steps_accepted}, {"pcg_total", r.pcg_total}, {"stop", r.stop}, {"launches", r.launches}};
+  for (const auto &kv : ints) o.o.emplace_back(kv.first, make_int(kv.second));
+  const std::pair<const char *, double> doubles[] = {
+      {"cost_initial", r.cost_initial}, {"cost_final", r.cost_final}, {"scale_ms", r.scale_ms}, {"centre_ms", r.centre_ms}};
+  for (const auto &kv : doubles) o.o.emplace_back(kv.first, Value::make_float(kv.second));
+  return o;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-  std::string in, poses, out_path, report, angle_txt = "5", dev_txt = "0";
+  std::string in, poses, out_path, report, scales, angle_txt = "5", dev_txt = "0";
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     std::string *dst = nullptr;
@@ -119,6 +138,7 @@ int main(int argc, char **argv) {
     else if (a == "-p" || a == "--poses_file") dst = &poses;
     else if (a == "-o" || a == "--output_file") dst = &out_path;
     else if (a == "-r" || a == "--report_file") dst = &report;
+    else if (a == "-s" || a == "--scales_file") dst = &scales;
     else if (a == "--triplet-angle") dst = &angle_txt;
     else if (a == "--device") dst = &dev_txt;
     if (!dst || i + 1 >= argc) {
@@ -153,13 +173,35 @@ int main(int argc, char **argv) {
   std::vector<uint32_t> pairs;
   std::vector<double> rel_R, rel_t;
   std::vector<uint8_t> use_t;
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> pair_index;
   Value pdoc;
   ok = sfmjson::read_file(poses.c_str(), &text);
   if (!ok) err = "cannot be read";
-  ok = ok && sfmjson::parse(text, &pdoc, &err) && pose_arrays(pdoc, view_index, &pairs, &rel_R, &rel_t, &use_t, &err);
+  ok = ok && sfmjson::parse(text, &pdoc, &err) && pose_arrays(pdoc, view_index, &pairs, &rel_R, &rel_t, &use_t, &pair_index, &err);
   if (!ok) {
     fprintf(stderr, "\nInvalid relative poses file. (%s: %s)\n", poses.c_str(), err.c_str());
     return 1;
+  }
+  std::vector<uint32_t> wedge_kl;
+  std::vector<double> wedge_ratio;
+  if (!scales.empty()) {
+    sfmfiles::PairScales ps;
+    ok = sfmfiles::read_pair_scales(scales, &ps, &err);
+    for (size_t w = 0; ok && w < ps.rec.size(); ++w) {
+      const auto k = pair_index.find({ps.rec[w].k[0], ps.rec[w].k[1]}), l = pair_index.find({ps.rec[w].l[0], ps.rec[w].l[1]});
+      if (k == pair_index.end() || l == pair_index.end()) {
+        err = "record " + std::to_string(w) + " names an unknown pair";
+        ok = false;
+        break;
+      }
+      wedge_kl.push_back(k->second);
+      wedge_kl.push_back(l->second);
+      wedge_ratio.push_back(ps.rec[w].ratio);
+    }
+    if (!ok) {
+      fprintf(stderr, "\nInvalid pair scales file. (%s: %s)\n", scales.c_str(), err.c_str());
+      return 1;
+    }
   }
   const uint32_t n_pairs = (uint32_t)use_t.size();
   size_t with_t = 0;
@@ -170,7 +212,13 @@ int main(int argc, char **argv) {
   sfmloc_gposes_default_options(&opt);
   opt.triplet_angle_deg = angle;
   sfmloc_gposes *h = nullptr;
-  if (sfmloc_global_poses((int)device, n_views, pairs.data(), n_pairs, rel_R.data(), rel_t.data(), use_t.data(), &opt, &h)) {
+  const int rc = scales.empty()
+                     ? sfmloc_global_poses((int)device, n_views, pairs.data(), n_pairs, rel_R.data(), rel_t.data(), use_t.data(),
+                                           &opt, &h)
+                     : sfmloc_global_poses_scaled((int)device, n_views, pairs.data(), n_pairs, rel_R.data(), rel_t.data(),
+                                                  use_t.data(), &opt, wedge_kl.data(), wedge_ratio.data(),
+                                                  (uint32_t)wedge_ratio.size(), nullptr, &h);
+  if (rc) {
     fprintf(stderr, "%s: %s\n", kName, sfmloc_last_error());
     return 1;
   }
@@ -179,18 +227,33 @@ int main(int argc, char **argv) {
   sfmloc_gposes_report rep;
   sfmloc_gposes_views(h, inc.data(), R.data(), C.data());
   sfmloc_gposes_report_read(h, &rep);
+  sfmloc_gpscale_report srep;
+  std::vector<double> base(n_pairs ? n_pairs : 1);
+  sfmloc_gpscale_report_read(h, &srep);
+  sfmloc_gpscale_baselines(h, base.data());
   sfmloc_gposes_destroy(h);
   if (!report.empty()) {
     std::string rtxt;
-    sfmjson::dump(report_json(rep), &rtxt);
+    Value rj = report_json(rep);
+    if (!scales.empty()) {
+      rj.o.emplace_back("scale", scale_json(srep));
+      rj.o.emplace_back("baselines", floats(base.data(), (int)n_pairs));
+    }
+    sfmjson::dump(rj, &rtxt);
     if (!sfmjson::write_file(report.c_str(), rtxt)) {
       fprintf(stderr, "%s: %s cannot be written\n", kName, report.c_str());
       return 1;
     }
   }
   if (!rep.n_component_views) {
-    fprintf(stderr, "%s: no triplet of the %u pairs passes: no view can be posed\n", kName, n_pairs);
+    fprintf(stderr, "%s: %s of the %u pairs passes: no view can be posed\n", kName,
+            (scales.empty() || !rep.n_pairs_kept) ? "no triplet" : "no wedge", n_pairs);
     return 1;
+  }
+  if (!scales.empty()) {
+    printf("Pair scales: %u of %u wedges used; %u pairs, %u views; steps %u/%u\n", srep.n_wedges_used, srep.n_wedges,
+           srep.n_scaled_pairs, srep.n_scaled_views, srep.steps_accepted, srep.steps_tried);
+    fflush(stdout);
   }
   printf("Global poses: %u of %u views; %u of %u pairs kept; steps: rotation %u/%u, translation %u/%u; device %.3f ms\n",
          rep.n_component_views, rep.n_views, rep.n_pairs_kept, rep.n_pairs, rep.rot_steps_accepted, rep.rot_steps_tried,

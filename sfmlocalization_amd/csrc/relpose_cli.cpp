@@ -2,10 +2,12 @@
 //
 //   ComputeRelativePoses -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>] [-o <matches.e.txt>]
 //                        [-p <relative_poses.json>] [-n <iterations = 256>] [-t <precision px = 2.5>] [--seed N] [--device 0]
+//                        [-s <pair scales = none>]
 //
 // The same program as sfmlocalization_amd/relpose.py and the same bytes in both output files: the relative pose of every
 // matched view pair (sfmloc_relative_poses, the first stage of openMVG_main_GlobalSfM).  The essential matches hold the ok
-// pairs only, each with its inliers in ascending (i, j); the poses file lists them in ascending (I, J).
+// pairs only, each with its inliers in ascending (i, j); the poses file lists them in ascending (I, J).  With -s the
+// records of sfmloc_wedge_scales on the call's results are written by view ids (sfm_files.h write_pair_scales).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -41,7 +43,8 @@ void usage() {
           "[-n|--max_iteration] AC-RANSAC iterations per pair (256)\n"
           "[-t|--precision] upper bound on the residual in pixels (2.5)\n"
           "[--seed] sampling seed\n"
-          "[--device] HIP device (0)\n",
+          "[--device] HIP device (0)\n"
+          "[-s|--scales_file] pair scales to write (default: none)\n",
           kName);
 }
 
@@ -61,7 +64,7 @@ Value rows3(const double *v) {
 
 int main(int argc, char **argv) {
   std::string in, match_dir, match_file = "matches.f.txt", out_file = "matches.e.txt", poses_file = "relative_poses.json",
-              n_txt = "256", t_txt = "2.5", seed_txt, dev_txt = "0";
+              n_txt = "256", t_txt = "2.5", seed_txt, dev_txt = "0", scales_file;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     std::string *dst = nullptr;
@@ -77,6 +80,7 @@ int main(int argc, char **argv) {
     else if (a == "-p" || a == "--poses_file") dst = &poses_file;
     else if (a == "-n" || a == "--max_iteration") dst = &n_txt;
     else if (a == "-t" || a == "--precision") dst = &t_txt;
+    else if (a == "-s" || a == "--scales_file") dst = &scales_file;
     else if (a == "--seed") dst = &seed_txt;
     else if (a == "--device") dst = &dev_txt;
     if (!dst || i + 1 >= argc) {
@@ -173,6 +177,7 @@ int main(int argc, char **argv) {
   std::vector<uint32_t> idx(off[n_pairs] ? off[n_pairs] : 1);
   sfmloc_relpose_inliers(h, nullptr, idx.data());
   sfmloc_relpose_destroy(h);
+  h = nullptr;
   size_t n_ok = 0, n_ess = 0;
   for (uint32_t k = 0; k < n_pairs; ++k)
     if (res[k].ok) {
@@ -218,6 +223,49 @@ int main(int argc, char **argv) {
   if (!sfmjson::write_file(epath.c_str(), etxt) || !sfmjson::write_file(ppath.c_str(), jtxt)) {
     fprintf(stderr, "%s: %s or %s cannot be written\n", kName, epath.c_str(), ppath.c_str());
     return 1;
+  }
+  if (!scales_file.empty()) {  // sfmloc.h "Wedge scales" on the pairs whose translation can be trusted
+    std::vector<double> rel_R(9 * (size_t)n_pairs + 1), rel_t(3 * (size_t)n_pairs + 1);
+    std::vector<uint8_t> use(n_pairs ? n_pairs : 1);
+    for (uint32_t k = 0; k < n_pairs; ++k) {
+      std::copy(res[k].R, res[k].R + 9, rel_R.begin() + 9 * (size_t)k);
+      std::copy(res[k].t, res[k].t + 3, rel_t.begin() + 3 * (size_t)k);
+      use[k] = res[k].ok && res[k].front[res[k].choice] == res[k].n_inliers;
+    }
+    sfmloc_wscales_options wopt;
+    sfmloc_wscales_default_options(&wopt);
+    sfmloc_wscales *w = nullptr;
+    if (sfmloc_wedge_scales((int)device, view_off.data(), n_views, kpt.data(), d.view_intr.data(), d.intr.data(),
+                            itype.data(), (uint32_t)itype.size(), pl.pairs.data(), n_pairs, pl.offsets.data(), pl.mi.data(),
+                            pl.mj.data(), rel_R.data(), rel_t.data(), off.data(), idx.data(), use.data(), &wopt, &w)) {
+      fprintf(stderr, "%s: %s\n", kName, sfmloc_last_error());
+      return 1;
+    }
+    uint32_t n_w = 0;
+    sfmloc_wscales_report rep;
+    sfmloc_wscales_count(w, &n_w);
+    std::vector<sfmloc_wscale> rec(n_w ? n_w : 1);
+    sfmloc_wscales_read(w, rec.data());
+    sfmloc_wscales_report_read(w, &rep);
+    sfmloc_wscales_destroy(w);
+    printf("Pair scales: %u wedges of %u candidates over %u pairs; device %.3f ms\n", n_w, rep.n_candidates,
+           rep.n_pairs_used, sfmloc_wscales_last_ms());
+    fflush(stdout);
+    PairScales ps;
+    ps.min_shared = wopt.min_shared;
+    ps.max_shared = wopt.max_shared;
+    for (uint32_t i = 0; i < n_w; ++i) {
+      const sfmloc_wscale &r = rec[i];
+      ps.rec.push_back(PairScale{d.view_id[r.view],
+                                 {d.view_id[pl.pairs[2 * (size_t)r.k]], d.view_id[pl.pairs[2 * (size_t)r.k + 1]]},
+                                 {d.view_id[pl.pairs[2 * (size_t)r.l]], d.view_id[pl.pairs[2 * (size_t)r.l + 1]]},
+                                 r.n_shared, r.ratio});
+    }
+    const std::string spath = join(match_dir, scales_file);
+    if (!write_pair_scales(spath, ps)) {
+      fprintf(stderr, "%s: %s cannot be written\n", kName, spath.c_str());
+      return 1;
+    }
   }
   return 0;
 }

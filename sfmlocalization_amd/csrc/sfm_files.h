@@ -18,6 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "sfm_json.h"
+
 namespace sfmfiles {
 
 // ---- paths ----
@@ -184,6 +186,91 @@ inline bool read_matches(const std::string &path, const std::map<uint32_t, uint3
     out->mj.insert(out->mj.end(), kv.second.second.begin(), kv.second.second.end());
     out->offsets.push_back(out->mi.size());
   }
+  return true;
+}
+
+// ---- pair_scales.json: the records of sfmloc_wedge_scales by view ids (fileio.read_pair_scales / write_pair_scales) ----
+constexpr int kPairScalesVersion = 1;
+struct PairScale {
+  uint32_t view, k[2], l[2], n_shared;  // k, l: the two view ids of each pair, in the pair list's order
+  double ratio;
+};
+struct PairScales {
+  uint32_t min_shared = 8, max_shared = 2048;
+  std::vector<PairScale> rec;
+};
+
+inline sfmjson::Value json_int(unsigned long long v) {
+  sfmjson::Value x;
+  x.kind = sfmjson::Value::Int;
+  x.s = std::to_string(v);
+  return x;
+}
+
+// the bytes json.dump writes for fileio.write_pair_scales' document
+inline std::string format_pair_scales(const PairScales &ps) {
+  using sfmjson::Value;
+  Value list = Value::make_arr();
+  for (const PairScale &r : ps.rec) {
+    Value e, k = Value::make_arr(), l = Value::make_arr();
+    for (int i = 0; i < 2; ++i) {
+      k.a.push_back(json_int(r.k[i]));
+      l.a.push_back(json_int(r.l[i]));
+    }
+    e.kind = Value::Obj;
+    e.o.emplace_back("view", json_int(r.view));
+    e.o.emplace_back("k", k);
+    e.o.emplace_back("l", l);
+    e.o.emplace_back("n_shared", json_int(r.n_shared));
+    e.o.emplace_back("ratio", Value::make_float(r.ratio));
+    list.a.push_back(e);
+  }
+  Value doc;
+  doc.kind = Value::Obj;
+  doc.o.emplace_back("pair_scales_version", json_int(kPairScalesVersion));
+  doc.o.emplace_back("min_shared", json_int(ps.min_shared));
+  doc.o.emplace_back("max_shared", json_int(ps.max_shared));
+  doc.o.emplace_back("pair_scales", list);
+  std::string text;
+  sfmjson::dump(doc, &text);
+  return text;
+}
+
+inline bool write_pair_scales(const std::string &path, const PairScales &ps) {
+  return sfmjson::write_file(path.c_str(), format_pair_scales(ps));
+}
+
+inline bool read_pair_scales(const std::string &path, PairScales *out, std::string *err) {
+  using sfmjson::Value;
+  std::string text;
+  Value doc;
+  if (!sfmjson::read_file(path.c_str(), &text)) return *err = "cannot be read", false;
+  if (!sfmjson::parse(text, &doc, err)) return false;
+  const auto u32 = [](const Value *v, uint32_t *o) {
+    if (!v || v->kind != Value::Int || v->s.empty() || v->s[0] == '-' || v->s.size() > 10) return false;
+    const unsigned long long x = strtoull(v->s.c_str(), nullptr, 10);
+    *o = (uint32_t)x;
+    return x <= 0xFFFFFFFFull;
+  };
+  uint32_t version = 0;
+  if (doc.kind != Value::Obj || !u32(doc.get("pair_scales_version"), &version) || version != (uint32_t)kPairScalesVersion)
+    return *err = "not a pair_scales file of version 1", false;
+  PairScales ps;
+  const Value *list = doc.get("pair_scales");
+  if (!u32(doc.get("min_shared"), &ps.min_shared) || !u32(doc.get("max_shared"), &ps.max_shared) || !list ||
+      list->kind != Value::Arr)
+    return *err = "malformed pair_scales file", false;
+  for (const Value &e : list->a) {
+    PairScale r;
+    const Value *k = e.get("k"), *l = e.get("l"), *q = e.get("ratio");
+    if (e.kind != Value::Obj || !k || !l || k->kind != Value::Arr || l->kind != Value::Arr || k->a.size() != 2 ||
+        l->a.size() != 2 || !q || !q->is_num() || !u32(e.get("view"), &r.view) || !u32(e.get("n_shared"), &r.n_shared) ||
+        !u32(&k->a[0], &r.k[0]) || !u32(&k->a[1], &r.k[1]) || !u32(&l->a[0], &r.l[0]) || !u32(&l->a[1], &r.l[1]))
+      return *err = "malformed pair_scales file", false;
+    r.ratio = q->num();
+    ps.rec.push_back(r);
+  }
+  *out = std::move(ps);
   return true;
 }
 

@@ -285,3 +285,52 @@ def read_matches_txt(path):
         p += 2 * n
         out[(a, b)] = (arr[:, 0].astype(np.uint32), arr[:, 1].astype(np.uint32))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# pair_scales.json: the records of sfmloc_wedge_scales by view ids (relpose -s writes it).  A pair is named by its two
+# view ids in the pair list's order; json.dump writes the doubles with the digits that read back as the same double.
+# ---------------------------------------------------------------------------------------------------------
+PAIR_SCALES_VERSION = 1
+
+
+def write_pair_scales(path, records, min_shared, max_shared):
+    """records: [(view, (I_k, J_k), (I_l, J_l), n_shared, ratio)], view ids, in the call's order"""
+    doc = {"pair_scales_version": PAIR_SCALES_VERSION, "min_shared": int(min_shared), "max_shared": int(max_shared),
+           "pair_scales": [{"view": int(v), "k": [int(k[0]), int(k[1])], "l": [int(l[0]), int(l[1])], "n_shared": int(n),
+                            "ratio": float(q)} for v, k, l, n, q in records]}
+    with open(path, "w") as fh:
+        json.dump(doc, fh)
+
+
+def read_pair_scales(path):
+    """-> (records as write_pair_scales takes them, min_shared, max_shared); ValueError naming the path for another
+    version or shape.  What sfm_files.h read_pair_scales refuses is refused here: an id or count that is not a JSON
+    integer of 32 bits without a sign, a ratio that is not a JSON number."""
+    with open(path) as fh:
+        doc = json.load(fh)
+
+    def u32(v):
+        if type(v) is not int or not 0 <= v <= 0xFFFFFFFF:
+            raise TypeError(f"{v!r} is not an unsigned 32-bit integer")
+        return v
+
+    def pair(v):
+        if type(v) is not list or len(v) != 2:
+            raise TypeError(f"{v!r} is not a pair of view ids")
+        return u32(v[0]), u32(v[1])
+    if not isinstance(doc, dict) or type(doc.get("pair_scales_version")) is not int or \
+            doc["pair_scales_version"] != PAIR_SCALES_VERSION:
+        raise ValueError(f"{path}: not a pair_scales file of version {PAIR_SCALES_VERSION}")
+    try:
+        lo, hi = u32(doc["min_shared"]), u32(doc["max_shared"])
+        if type(doc["pair_scales"]) is not list:
+            raise TypeError("pair_scales is not a list")
+        rec = []
+        for e in doc["pair_scales"]:
+            if type(e["ratio"]) not in (int, float):
+                raise TypeError(f"{e['ratio']!r} is not a number")
+            rec.append((u32(e["view"]), pair(e["k"]), pair(e["l"]), u32(e["n_shared"]), float(e["ratio"])))
+        return rec, lo, hi
+    except (KeyError, TypeError, IndexError, OverflowError) as e:
+        raise ValueError(f"{path}: malformed pair_scales file ({e})") from e

@@ -3,13 +3,18 @@ middle stage of openMVG_main_GlobalSfM, between sfmlocalization_amd.relpose and 
 
     python -m sfmlocalization_amd.globalposes -i <sfm_data.json> -p <relative_poses.json> -o <out sfm_data.json>
                                               [--triplet-angle 5] [--device 0] [-r <report.json>]
+                                              [-s <pair_scales.json>]
 
 The views come from the input as sfmlocalization_amd.relpose reads them; the poses file is the one that tool writes.  I
 and J are view ids and are mapped to view indices; a pair carries its translation when every inlier lay in front of both
 cameras (front[choice] == n_inliers: the advice of include/sfmloc.h "decision").  sfmloc_global_poses (include/sfmloc.h
 "Global poses" states the semantics and the known limit on collinear cameras) runs on that.  The output is the input
 document with `extrinsics` replaced by the poses of the component's views, keyed by id_pose, as rotation and center,
-and `structure` and `control_points` emptied, written by the writer of sfmlocalization_amd.adjust.  One summary line:
+and `structure` and `control_points` emptied, written by the writer of sfmlocalization_amd.adjust.  -s: the wedge ratios
+that `ComputeRelativePoses -s` wrote; a record's two pairs, named by view ids, are looked up in the poses file, and
+sfmloc_global_poses_scaled ("Scaled global poses": the spacing along a line of cameras is fixed from the ratios; a pair
+with no used wedge drops out of the translations) runs in place of sfmloc_global_poses; the report then also holds
+`scale` (sfmloc_gpscale_report) and `baselines` (per pair, in the poses file's order).  One summary line:
 views in the component, pairs kept, steps, device milliseconds.  No component (no triplet passes): a message, exit 1.
 bin/ComputeGlobalPoses (csrc/globalposes_cli.cpp) is the same program and writes the same bytes.
 """
@@ -28,6 +33,7 @@ USAGE = (f"Usage: {NAME}\n"
          "\n[Optional]\n"
          "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
          "[-r|--report_file] the call's report as JSON\n"
+         "[-s|--scales_file] the wedge ratios (pair_scales.json of ComputeRelativePoses -s): fix the pair baselines from them\n"
          "[--device] HIP device (0)\n")
 
 REPORT_FIELDS = ("n_views", "n_pairs", "n_triplets", "n_triplets_ok", "n_pairs_kept", "n_component_views", "root",
@@ -35,6 +41,18 @@ REPORT_FIELDS = ("n_views", "n_pairs", "n_triplets", "n_triplets_ok", "n_pairs_k
                  "rot_steps_accepted", "rot_pcg_total", "rot_stop", "trans_steps_tried", "trans_steps_accepted",
                  "trans_pcg_total", "trans_stop", "launches", "chordal_residual", "chordal_cost", "rot_cost_initial", "rot_cost_final",
                  "trans_cost_initial", "trans_cost_final", "graph_ms", "rotation_ms", "translation_ms", "device_ms")
+
+
+SCALE_REPORT_FIELDS = ("n_wedges", "n_wedges_used", "n_scaled_pairs", "n_scaled_views", "first_pair", "steps_tried",
+                       "steps_accepted", "pcg_total", "stop", "launches", "cost_initial", "cost_final", "scale_ms", "centre_ms")
+
+
+def wedge_arrays(records, entries):
+    """the records of fileio.read_pair_scales and the `relative_poses` list -> kl [W, 2] (positions in that list),
+    ratio [W]; KeyError on a pair of view ids the list does not have"""
+    index = {(int(e["I"]), int(e["J"])): k for k, e in enumerate(entries)}
+    kl = np.array([[index[tuple(k)], index[tuple(l)]] for _, k, l, _, _ in records], np.uint32).reshape(-1, 2)
+    return kl, np.array([q for _, _, _, _, q in records], np.float64)
 
 
 def pose_arrays(entries, view_id):
@@ -57,9 +75,10 @@ def extrinsics(view_pose_id, in_component, R, C):
     return [{"key": p, "value": poses[p]} for p in sorted(poses)]
 
 
-def run(in_path, poses_path, out_path, triplet_angle=5.0, report_path=None, device=0, log=print):
+def run(in_path, poses_path, out_path, triplet_angle=5.0, report_path=None, device=0, log=print, scales_path=None):
     """The tool's body.  Returns 0, or 1 after an error message on stderr."""
     from . import capi as S
+    from . import fileio
     try:
         with open(in_path) as fh:
             doc = json.load(fh)
@@ -70,24 +89,41 @@ def run(in_path, poses_path, out_path, triplet_angle=5.0, report_path=None, devi
         return 1
     try:
         with open(poses_path) as fh:
-            pairs, rel_R, rel_t, use_t = pose_arrays(json.load(fh)["relative_poses"], arrays["view_id"])
+            entries = json.load(fh)["relative_poses"]
+        pairs, rel_R, rel_t, use_t = pose_arrays(entries, arrays["view_id"])
     except (OSError, ValueError, KeyError, TypeError, IndexError) as e:
         print(f"\nInvalid relative poses file. ({poses_path}: {e})", file=sys.stderr)
         return 1
+    wedges = None
+    if scales_path:
+        try:
+            wedges = wedge_arrays(fileio.read_pair_scales(scales_path)[0], entries)
+        except (OSError, ValueError, KeyError, TypeError, IndexError) as e:
+            print(f"\nInvalid pair scales file. ({scales_path}: {e})", file=sys.stderr)
+            return 1
     log(f"#views: {len(view_pose_id)}; #pairs: {len(pairs)}, with a translation: {int(use_t.sum())}")
     try:
         g = S.GlobalPoses(len(view_pose_id), pairs, rel_R, rel_t, use_t, device=int(device),
-                          triplet_angle_deg=float(triplet_angle))
+                          wedges=wedges, triplet_angle_deg=float(triplet_angle))
     except S.SfmlocError as e:
         print(f"{NAME}: {e.message}", file=sys.stderr)
         return 1
     rep = g.report
     if report_path:
         with open(report_path, "w") as fh:
-            json.dump({k: getattr(rep, k) for k in REPORT_FIELDS}, fh)
+            out = {k: getattr(rep, k) for k in REPORT_FIELDS}
+            if wedges is not None:
+                out["scale"] = {k: getattr(g.scale_report, k) for k in SCALE_REPORT_FIELDS}
+                out["baselines"] = [float(b) for b in g.baselines]
+            json.dump(out, fh)
     if not rep.n_component_views:
-        print(f"{NAME}: no triplet of the {len(pairs)} pairs passes: no view can be posed", file=sys.stderr)
+        why = "no triplet" if wedges is None or not rep.n_pairs_kept else "no wedge"
+        print(f"{NAME}: {why} of the {len(pairs)} pairs passes: no view can be posed", file=sys.stderr)
         return 1
+    if wedges is not None:
+        sr = g.scale_report
+        log(f"Pair scales: {sr.n_wedges_used} of {sr.n_wedges} wedges used; {sr.n_scaled_pairs} pairs, {sr.n_scaled_views} "
+            f"views; steps {sr.steps_accepted}/{sr.steps_tried}")
     log(f"Global poses: {rep.n_component_views} of {rep.n_views} views; {rep.n_pairs_kept} of {rep.n_pairs} pairs kept; "
         f"steps: rotation {rep.rot_steps_accepted}/{rep.rot_steps_tried}, translation "
         f"{rep.trans_steps_accepted}/{rep.trans_steps_tried}; device {rep.device_ms:.3f} ms")
@@ -101,8 +137,9 @@ def run(in_path, poses_path, out_path, triplet_angle=5.0, report_path=None, devi
 
 def parse_args(argv):
     """-> the keyword arguments of run(), or None for a bad command line"""
-    opt = {"-i": "", "-p": "", "-o": "", "-r": "", "--triplet-angle": "5", "--device": "0"}
-    long_names = {"--input_file": "-i", "--poses_file": "-p", "--output_file": "-o", "--report_file": "-r"}
+    opt = {"-i": "", "-p": "", "-o": "", "-r": "", "-s": "", "--triplet-angle": "5", "--device": "0"}
+    long_names = {"--input_file": "-i", "--poses_file": "-p", "--output_file": "-o", "--report_file": "-r",
+                  "--scales_file": "-s"}
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -119,6 +156,8 @@ def parse_args(argv):
     try:
         kw = dict(in_path=opt["-i"], poses_path=opt["-p"], out_path=opt["-o"], triplet_angle=float(opt["--triplet-angle"]),
                   report_path=opt["-r"] or None, device=int(opt["--device"]))
+        if opt["-s"]:
+            kw["scales_path"] = opt["-s"]    # (only when given: without the switch the call is what it was)
     except ValueError:
         return None
     if not kw["in_path"] or not kw["poses_path"] or not kw["out_path"] or not 0.0 < kw["triplet_angle"] < 180.0:

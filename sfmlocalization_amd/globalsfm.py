@@ -2,6 +2,7 @@
 the step PyReconstruct/src/reconstructGraph.py:171 runs and whose <outDir>/sfm_data.json it waits for.
 
     python -m sfmlocalization_amd.globalsfm -i <sfm_data.json> -m <matchDir> -o <outDir> [--triplet-angle 5] [--device 0]
+                                            [--pair-scales]
 
 Three stages, each the run() of its own tool, the files of one the input of the next:
     sfmlocalization_amd.relpose       matches.f.txt -> <outDir>/matches.e.txt, <outDir>/relative_poses.json
@@ -9,6 +10,8 @@ Three stages, each the run() of its own tool, the files of one the input of the 
     sfmlocalization_amd.structure     sfm_data_poses.json + matches.e.txt -> <outDir>/sfm_data.json: tracks, the robust
                                       triangulation, the cleanup at 4.0 px / 2.0 degrees, then rotations, translations and
                                       structure adjusted jointly (rst) on the same resident handle and cleaned again
+--pair-scales: relpose also writes <outDir>/pair_scales.json (its -s) and globalposes reads it (its -s), so that the
+spacing of cameras along a line comes from the depths of shared features; without it the chain is what it was.
 The first stage that fails ends the run with its message and its exit code.  Python only: there is no C++ program for
 the chain (the stages' own C++ programs can be run one after the other).
 """
@@ -24,19 +27,23 @@ USAGE = (f"Usage: {NAME}\n"
          "[-o|--outdir] path where the output data will be stored\n"
          "\n[Optional]\n"
          "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
-         "[--device] HIP device (0)\n")
+         "[--device] HIP device (0)\n"
+         "[--pair-scales] fix the pair baselines from shared features (relpose -s, globalposes -s)\n")
 
 
-def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print):
+def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pair_scales=False):
     """The tool's body.  Returns 0, or the exit code of the stage that failed after its message on stderr."""
     os.makedirs(out_dir, exist_ok=True)
     essential = os.path.join(os.path.abspath(out_dir), "matches.e.txt")
     poses = os.path.join(os.path.abspath(out_dir), "relative_poses.json")
     posed = os.path.join(out_dir, "sfm_data_poses.json")
-    rc = relpose.run(in_path, match_dir, out_file=essential, poses_file=poses, device=device, log=log)
+    scales = os.path.join(os.path.abspath(out_dir), "pair_scales.json") if pair_scales else None
+    extra = dict(scales_file=scales) if pair_scales else {}
+    rc = relpose.run(in_path, match_dir, out_file=essential, poses_file=poses, device=device, log=log, **extra)
     if rc:
         return rc
-    rc = globalposes.run(in_path, poses, posed, triplet_angle=triplet_angle, device=device, log=log)
+    extra = dict(scales_path=scales) if pair_scales else {}
+    rc = globalposes.run(in_path, poses, posed, triplet_angle=triplet_angle, device=device, log=log, **extra)
     if rc:
         return rc
     return structure.run(posed, match_dir, os.path.join(out_dir, "sfm_data.json"), match_file=essential, residual_px=4.0,
@@ -48,8 +55,13 @@ def parse_args(argv):
     opt = {"-i": "", "-m": "", "-o": "", "--triplet-angle": "5", "--device": "0"}
     long_names = {"--input_file": "-i", "--matchdir": "-m", "--outdir": "-o"}
     i = 0
+    flag = False
     while i < len(argv):
         a = argv[i]
+        if a == "--pair-scales":
+            flag = True
+            i += 1
+            continue
         if "=" in a and a.split("=", 1)[0] in ("--triplet-angle", "--device"):
             a, val = a.split("=", 1)
         else:
@@ -63,6 +75,8 @@ def parse_args(argv):
     try:
         kw = dict(in_path=opt["-i"], match_dir=opt["-m"], out_dir=opt["-o"], triplet_angle=float(opt["--triplet-angle"]),
                   device=int(opt["--device"]))
+        if flag:
+            kw["pair_scales"] = True
     except ValueError:
         return None
     if not kw["in_path"] or not kw["match_dir"] or not kw["out_dir"] or not 0.0 < kw["triplet_angle"] < 180.0:

@@ -5,6 +5,7 @@ matches.f.txt to matches.e.txt "because OpenMVG assumes matches.e.txt for global
     python -m sfmlocalization_amd.relpose -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>]
                                           [-o <essential matches = matches.e.txt>] [-p <poses = relative_poses.json>]
                                           [-n <iterations = 256>] [-t <precision px = 2.5>] [--seed N] [--device 0]
+                                          [-s <pair scales = none>]
 
 The views and intrinsics come from the input, <matchDir>/<stem>.feat of every view gives its keypoints, the match file
 (relative to <matchDir> unless absolute, as the two outputs are) the pairs: all read as sfmlocalization_amd.structure
@@ -14,7 +15,9 @@ hold the ok pairs only, each with its inliers in ascending (i, j); the poses fil
 {"relative_poses": [{"I", "J", "n_matches", "n_inliers", "R", "t", "E", "error_max", "front", "choice"}, ...]} in
 ascending (I, J), I and J view ids, R and E as three rows, written with json.dump.  bin/ComputeRelativePoses
 (csrc/relpose_cli.cpp) is the same program and writes the same bytes.  sfmlocalization_amd.globalposes consumes the
-poses file (rotation and translation averaging); the two-view refinement of OpenMVG is not built.
+poses file (rotation and translation averaging); the two-view refinement of OpenMVG is not built.  With -s,
+sfmloc_wedge_scales ("Wedge scales") runs on the call's results -- the pairs with ok and front[choice] == n_inliers -- and
+its records are written by view ids (fileio.write_pair_scales), by both programs with the same bytes.
 """
 import json
 import os
@@ -37,7 +40,8 @@ USAGE = (f"Usage: {NAME}\n"
          "[-n|--max_iteration] AC-RANSAC iterations per pair (256)\n"
          "[-t|--precision] upper bound on the residual in pixels (2.5)\n"
          "[--seed] sampling seed\n"
-         "[--device] HIP device (0)\n")
+         "[--device] HIP device (0)\n"
+         "[-s|--scales_file] pair scales to write (default: none)\n")
 
 
 def view_sizes(doc):
@@ -60,6 +64,19 @@ def pose_entries(view_id, pairs, results):
     return out
 
 
+def scale_pairs(results):
+    """the pairs whose translation can be trusted ("decision" of the relative poses): ok and every inlier in front"""
+    return np.array([int(r["ok"]) and int(r["front"][int(r["choice"])]) == int(r["n_inliers"]) for r in results], np.uint8)
+
+
+def scale_entries(view_id, pairs, records):
+    """the records of WedgeScales by view ids, as fileio.write_pair_scales takes them"""
+    def ids(k):
+        return int(view_id[pairs[k][0]]), int(view_id[pairs[k][1]])
+    return [(int(view_id[r["view"]]), ids(int(r["k"])), ids(int(r["l"])), int(r["n_shared"]), float(r["ratio"]))
+            for r in records]
+
+
 def essential_matches(view_id, pairs, offsets, match_i, match_j, rp):
     """{(I, J): (i[], j[])} of the ok pairs: the inliers, ascending (i, j)"""
     out = {}
@@ -74,7 +91,7 @@ def essential_matches(view_id, pairs, offsets, match_i, match_j, rp):
 
 
 def run(in_path, match_dir, match_file="matches.f.txt", out_file="matches.e.txt", poses_file="relative_poses.json",
-        max_iteration=256, precision_px=2.5, seed=None, device=0, log=print):
+        max_iteration=256, precision_px=2.5, seed=None, device=0, log=print, scales_file=None):
     """The tool's body.  Returns 0, or 1 after an error message on stderr."""
     from . import capi as S
     try:
@@ -125,15 +142,28 @@ def run(in_path, match_dir, match_file="matches.f.txt", out_file="matches.e.txt"
     fileio.write_matches_txt(at(out_file), essential_matches(arrays["view_id"], pairs, offsets, mi, mj, rp))
     with open(at(poses_file), "w") as fh:
         json.dump({"relative_poses": pose_entries(arrays["view_id"], pairs, rp.results)}, fh)
+    if scales_file:
+        try:
+            ws = S.WedgeScales(view_off, kpt, arrays["view_intrinsic"], arrays["intrinsic"], itype, pairs, offsets, mi, mj,
+                               rp.results["R"], rp.results["t"], rp.inl_off, rp.inl_idx, use_pair=scale_pairs(rp.results),
+                               device=int(device))
+        except S.SfmlocError as e:
+            print(f"{NAME}: {e.message}", file=sys.stderr)
+            return 1
+        log(f"Pair scales: {len(ws.records)} wedges of {ws.report.n_candidates} candidates over {ws.report.n_pairs_used} "
+            f"pairs; device {ws.ms:.3f} ms")
+        opt = S.wscales_default_options()
+        fileio.write_pair_scales(at(scales_file), scale_entries(arrays["view_id"], pairs, ws.records), opt.min_shared,
+                                 opt.max_shared)
     return 0
 
 
 def parse_args(argv):
     """-> the keyword arguments of run(), or None for a bad command line"""
     opt = {"-i": "", "-m": "", "-f": "matches.f.txt", "-o": "matches.e.txt", "-p": "relative_poses.json", "-n": "256",
-           "-t": "2.5", "--seed": "", "--device": "0"}
+           "-t": "2.5", "--seed": "", "--device": "0", "-s": ""}
     long_names = {"--input_file": "-i", "--match_dir": "-m", "--match_file": "-f", "--output_file": "-o",
-                  "--poses_file": "-p", "--max_iteration": "-n", "--precision": "-t"}
+                  "--poses_file": "-p", "--max_iteration": "-n", "--precision": "-t", "--scales_file": "-s"}
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -155,6 +185,8 @@ def parse_args(argv):
         return None
     if not kw["in_path"] or not kw["match_dir"] or kw["max_iteration"] < 0 or not kw["precision_px"] >= 0.0:
         return None
+    if opt["-s"]:
+        kw["scales_file"] = opt["-s"]
     return kw
 
 
