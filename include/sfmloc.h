@@ -942,7 +942,8 @@ int sfmloc_sfm_triangulate(sfmloc_sfm *h, const sfmloc_triangulate_options *opt,
 /* Relative poses (the first stage of openMVG_main_GlobalSfM, reconstructGraph.py:166-171: the essential matrix of      */
 /* every matched view pair by the five-point solver under AC-RANSAC, its decomposition and the cheirality test).        */
 /* Rotation and translation averaging consume the result ("Global poses" below); OpenMVG's two-view bundle adjustment  */
-/* of the winning pose is not built.  OpenMVG's source was not at hand: every point below is a reading chosen here, and */
+/* of the winning pose is a call of its own ("Two-view refinement" below): here R and t are the winning sample's.       */
+/* OpenMVG's source was not at hand: every point below is a reading chosen here, and                                    */
 /* tests/relpose_np.py restates each operation.  The pair list has the layout of sfmloc_geometric_pairs and             */
 /* sfmloc_tracks_build (pair k = views (I, J) = (pairs[2k], pairs[2k+1]) owns match_i/j[offsets[k] .. offsets[k+1]),    */
 /* feature indices inside the view); kpt_xy [view_off[n_views] * 2] the keypoints of all views; intrinsics f, ppx, ppy, */
@@ -1028,6 +1029,78 @@ void sfmloc_relpose_destroy(sfmloc_relpose *r);
 double sfmloc_relpose_last_ms(void);
 /* parity probe of the solver alone: a row = x1[10], x2[10] (five bearing pairs); out [n * 91] = count, then up to 10 E */
 int  sfmloc_debug_five_point(int device, const double *in, int n, double *out);
+
+/* ------------------------------------------------------------------------- */
+/* Two-view refinement (what OpenMVG does to every relative pose before it averages them: the pose of the winning       */
+/* minimal sample is adjusted on all of the pair's inliers).  An opt-in stage after sfmloc_relative_poses: per pair it   */
+/* minimises the reprojection error of the inlier matches over the relative pose and the matches' 3D points, one         */
+/* workgroup of 256 threads per pair, the points eliminated as the joint bundle adjustment eliminates landmarks.  The    */
+/* arrays are those of sfmloc_relative_poses (view_wh is not needed), rel_R / rel_t and inlier_off / inlier_idx its      */
+/* results, use_pair[k] = 0 (NULL: all 1) leaves a pair as it is.  OpenMVG's source was not at hand: every point below   */
+/* is a reading chosen here, and tests/relrefine_np.py restates each operation.  f64, unfused, only + - * / sqrt:        */
+/*   bearings    as "bearings" of the relative poses, for the inlier matches only.                                       */
+/*   points      every inlier is triangulated from [I | 0] and [R | t] by "cheirality" of the relative poses.  It is     */
+/*               used when the point X exists, (R X + t)_2 is finite and X_2 and (R X + t)_2 are positive.  A match      */
+/*               listed twice is two used points.  n_used counts the used inliers.                                       */
+/*   status      0: use_pair was 0.  2: n_used < min_points.  4: no step was ever accepted, or a sum of the first        */
+/*               linearisation was not finite.  In these three R and t are copies of the inputs and steps counts the     */
+/*               steps tried (0 for 0 and 2); cost_initial and cost are 0 for 0 and 2 and for a first linearisation      */
+/*               that was not finite.  1: stopped by the rule of "step".  3: max_steps were tried; the last accepted     */
+/*               pose is kept.  Always E = [t]x R of the R and t returned, divided by its Frobenius norm (the nine       */
+/*               squares added in row-major order); all zero where that norm is zero.                                    */
+/*   residual    four values per used inlier, in undistorted pixels: f_I (X_xy / X_2 - b_I) and f_J (Y_xy / Y_2 - b_J),  */
+/*               Y = R X + t, b the bearings, f the focal lengths of the two views' intrinsics.  No robust loss: the     */
+/*               inliers are already selected.  cost = 1/2 sum r^2, r^2 = ((r0^2 + r1^2) + r2^2) + r3^2 per inlier.      */
+/*   parameters  the rotation moves by R <- C(w) R, C(w) = I + 2 / (1 + w.w) ([w]x + w w^T - (w.w) I) (Cayley, as the    */
+/*               rotation averaging); the translation on the unit sphere by t <- (t + B d) / |t + B d|, B [3 x 2] the     */
+/*               tangent basis b1 = (t x e_k) / |t x e_k|, b2 = t x b1, k the axis of the smallest |t_k|, the first on    */
+/*               ties; three values per point.  Derivatives to first order: dY/dw = -2 [R X]x, dY/dd = B, dY/dX = R.     */
+/*   step        the lane that owns a point forms its block V = Jx^T Jx [3 x 3], its coupling W = Jp^T Jx [5 x 3], its   */
+/*               gradient Jx^T r and its part of Jp^T Jp and Jp^T r (Jp the 2 x 5 derivative of the second view's two   */
+/*               residuals by (w, d)).  Vd = V + lambda clamp(diag V, 1e-6, 1e32), inverted by Cholesky.  The reduced    */
+/*               system is A = sum (Jp^T Jp - W Vd^-1 W^T), g = sum (Jp^T r - W Vd^-1 Jx^T r), the difference taken per  */
+/*               point; (A + lambda clamp(diag A, 1e-6, 1e32)) x = -g by Cholesky on thread 0, broadcast through LDS     */
+/*               (ba_solve<5> of csrc/ba_device.h, which also gives the decrease the model promises).  The point's step  */
+/*               is -Vd^-1 (Jx^T r + W^T x).  The trial is costed anew at the trial pose and trial points; it is taken   */
+/*               when every used point has finite positive depth in both views there, the cost is finite and lower and   */
+/*               the decrease is above 1e-3 of the promised one.  lambda starts at 1e-4; acceptance, rejection and the   */
+/*               stopping rule (relative decrease <= 1e-14, the promise itself below that, or lambda >= 1e32) are those  */
+/*               of the separable bundle adjustment (BaLm of csrc/ba_device.h).  steps counts the trials.                */
+/*   reduction   lane l of the 256 adds its points l, l + 256, ... in ascending order from 0; then the butterfly over    */
+/*               the wave's 64 lanes (xor 32, 16, .. 1); then every thread adds the four waves' sums in the order 0 .. 3. */
+/* One form serves any inlier count: bearings, points and trial points live in global memory, one slab per pair at the   */
+/* pair's inlier offset, component by component (lane-consecutive addresses).  Device memory: 80 bytes per inlier        */
+/* (bearings 32, points 24, trial points 24) beside the call's input arrays; a failed allocation is SFMLOC_ENOMEM.      */
+/* No float atomics: two runs give the same bits, and a pair's record depends on its own inputs alone, not on the other */
+/* pairs or on the order of the pair list.  Refusals, all on the host before any launch, the text naming the pair:      */
+/* everything sfmloc_wedge_scales refuses for these arrays; max_steps = 0, min_points < 6: SFMLOC_EINVAL.               */
+/* n_pairs = 0 gives an empty handle.                                                                                    */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_relrefine sfmloc_relrefine;
+typedef struct sfmloc_relrefine_options {
+  uint32_t max_steps;    /* default 100 */
+  uint32_t min_points;   /* default 13: the smallest count above 2.5 x 5, the gate of sfmloc_relpose_result.ok */
+} sfmloc_relrefine_options;
+typedef struct sfmloc_relrefine_result {
+  uint32_t status, n_used, steps, reserved;
+  double   R[9], t[3], E[9];   /* X_J = R X_I + t, |t| = 1; E = [t]x R at unit Frobenius norm */
+  double   cost_initial, cost; /* 1/2 sum r^2 over the used inliers, pixels^2 */
+} sfmloc_relrefine_result;
+void sfmloc_relrefine_default_options(sfmloc_relrefine_options *o);
+/* opt NULL = the defaults */
+int  sfmloc_refine_relative_poses(int device, const uint64_t *view_off /*[n_views+1]*/, uint32_t n_views,
+                                  const float *kpt_xy, const uint32_t *view_intrinsic /*[n_views]*/,
+                                  const double *intrinsics /*[n*6]*/, const uint32_t *intrinsic_type,
+                                  uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                                  const uint32_t *match_i, const uint32_t *match_j,
+                                  const double *rel_R /*[n_pairs*9]*/, const double *rel_t /*[n_pairs*3]*/,
+                                  const uint64_t *inlier_off /*[n_pairs+1]*/, const uint32_t *inlier_idx,
+                                  const uint8_t *use_pair /*[n_pairs], NULL = all*/,
+                                  const sfmloc_relrefine_options *opt, sfmloc_relrefine **out);
+int  sfmloc_relrefine_results(const sfmloc_relrefine *r, sfmloc_relrefine_result *out /*[n_pairs]*/);
+void sfmloc_relrefine_destroy(sfmloc_relrefine *r);
+/* device milliseconds of the calling thread's last sfmloc_refine_relative_poses */
+double sfmloc_relrefine_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
 /* Wedge scales (the ratio of two pair baselines from the depths of the features the pairs share: what fixes the        */

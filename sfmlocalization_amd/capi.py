@@ -41,6 +41,8 @@ TriangulateOptions = _abi.struct("sfmloc_triangulate_options")
 TriangulateReport = _abi.struct("sfmloc_triangulate_report")
 RelposeOptions = _abi.struct("sfmloc_relpose_options")
 RelposeResult = _abi.struct("sfmloc_relpose_result")
+RelrefineOptions = _abi.struct("sfmloc_relrefine_options")
+RelrefineResult = _abi.struct("sfmloc_relrefine_result")
 WscalesOptions = _abi.struct("sfmloc_wscales_options")
 Wscale = _abi.struct("sfmloc_wscale")
 WscalesReport = _abi.struct("sfmloc_wscales_report")
@@ -1143,6 +1145,79 @@ class RelPoses:
     def inliers(self, k):
         """the inlier positions of pair k"""
         return self.inl_idx[int(self.inl_off[k]):int(self.inl_off[k + 1])]
+
+
+# sfmloc_relrefine_result as a NumPy record (four uint32, 23 doubles: no padding)
+RELREFINE_RESULT = np.dtype([("status", np.uint32), ("n_used", np.uint32), ("steps", np.uint32), ("reserved", np.uint32),
+                             ("R", np.float64, 9), ("t", np.float64, 3), ("E", np.float64, 9),
+                             ("cost_initial", np.float64), ("cost", np.float64)], align=True)
+
+
+def relrefine_default_options(**overrides):
+    """sfmloc_relrefine_default_options -> RelrefineOptions (max_steps 100, min_points 13)"""
+    o = RelrefineOptions()
+    _L().sfmloc_relrefine_default_options(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def relrefine_last_ms():
+    """device milliseconds of the calling thread's last sfmloc_refine_relative_poses"""
+    return float(_L().sfmloc_relrefine_last_ms())
+
+
+class RelRefine:
+    """sfmloc_refine_relative_poses: every relative pose adjusted on its inliers (include/sfmloc.h "Two-view refinement"
+    states the semantics).  The arguments are WedgeScales': the view and pair arrays of RelPoses (without view_wh), rel_R
+    [P, 3, 3], rel_t [P, 3], inl_off [P + 1], inl_idx its results; use_pair [P] or None (all); options: the fields of
+    sfmloc_relrefine_options.  -> results (RELREFINE_RESULT [P]; status 1 or 3: a refined pose), ms."""
+
+    def __init__(self, view_off, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j,
+                 rel_R, rel_t, inl_off, inl_idx, use_pair=None, device=0, **options):
+        view_off = np.ascontiguousarray(view_off, np.uint64)
+        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
+        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
+        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
+        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
+        rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
+        rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
+        inl_off, inl_idx = np.ascontiguousarray(inl_off, np.uint64), np.ascontiguousarray(inl_idx, np.uint32)
+        if use_pair is not None:
+            use_pair = np.ascontiguousarray(np.asarray(use_pair) != 0, np.uint8)
+        n_views, P = len(view_off) - 1, len(pairs)
+        if len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
+                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
+            raise ValueError("view arrays differ in length")
+        if len(offsets) != P + 1 or len(match_i) != len(match_j) or (P and int(offsets[-1]) != len(match_i)):
+            raise ValueError("pair list arrays differ in length")
+        if len(rel_R) != P or len(rel_t) != P or len(inl_off) != P + 1 or (use_pair is not None and len(use_pair) != P) \
+                or (P and int(inl_off[-1]) > len(inl_idx)):
+            raise ValueError("pose or inlier arrays differ in length")
+        opt = relrefine_default_options(**options)
+        h = C.c_void_p()
+        _check(_L().sfmloc_refine_relative_poses(
+            int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float), _ptr(view_intrinsic, C.c_uint32),
+            _ptr(intrinsics, C.c_double), _ptr(intrinsic_type, C.c_uint32), len(intrinsics), _ptr(pairs, C.c_uint32), P,
+            _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32), _ptr(rel_R, C.c_double),
+            _ptr(rel_t, C.c_double), _ptr(inl_off, C.c_uint64), _ptr(inl_idx, C.c_uint32),
+            None if use_pair is None else _ptr(use_pair, C.c_uint8), C.byref(opt), C.byref(h)))
+        try:
+            self.results = np.zeros(P, RELREFINE_RESULT)
+            _check(_L().sfmloc_relrefine_results(h, _ptr(self.results, RelrefineResult) if P else None))
+            self.ms = relrefine_last_ms()
+        finally:
+            _L().sfmloc_relrefine_destroy(h)
+
+    @property
+    def refined(self):
+        """[P] bool: the pairs whose R, t and E are the refinement's (status 1 or 3)"""
+        return np.isin(self.results["status"], (1, 3))
 
 
 # sfmloc_wscale as a NumPy record (four uint32, one double: no padding)

@@ -61,11 +61,7 @@ __device__ __forceinline__ void ws_bearing(const WsDev &D, uint32_t v, uint32_t 
   const uint32_t ii = D.view_intr[v];
   const double *K = D.intr + 6 * (size_t)ii;
   const uint64_t row = D.view_off[v] + f;
-  const double x = (double)D.kpt[2 * row], y = (double)D.kpt[2 * row + 1];
-  double ux = x, uy = y;
-  if (D.intr_type[ii] == 3) ud_pixel_k3(K[0], K[1], K[2], K[3], K[4], K[5], x, y, &ux, &uy);
-  *bx = (ux - K[1]) / K[0];
-  *by = (uy - K[2]) / K[0];
+  view_bearing(K, D.intr_type[ii], (double)D.kpt[2 * row], (double)D.kpt[2 * row + 1], bx, by);
 }
 
 // sfmloc.h "depths".  keys / ids: the first sort's input (the feature again, and the entry's own index)

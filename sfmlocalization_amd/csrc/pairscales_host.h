@@ -41,6 +41,37 @@ struct ViewPairs {
   uint32_t n_used = 0, n_inliers = 0;
 };
 
+// the checks of the results of sfmloc_relative_poses a later call takes again (rel_R, rel_t, inlier_off, inlier_idx),
+// shared with sfmloc_refine_relative_poses (relrefine_host.h); the pair list has passed relpose_host::check.  `name` is
+// the entry point the text speaks for.
+inline int check_inliers(const char *name, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                         const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
+                         std::string *err) {
+  const auto bad = [&](int code, const char *fmt, unsigned long long a = 0, unsigned long long b = 0,
+                       unsigned long long c = 0) {
+    fail(err, code, fmt, a, b, c);
+    *err = std::string(name) + ": " + *err;
+    return code;
+  };
+  if (n_pairs && (!rel_R || !rel_t || !inlier_off)) return bad(SFMLOC_EINVAL, "pose or inlier arrays missing");
+  if (n_pairs && inlier_off[0] != 0) return bad(SFMLOC_EINVAL, "inlier_off[0] must be 0");
+  for (uint32_t k = 0; k < n_pairs; ++k) {
+    const uint32_t a = pairs[2 * (size_t)k], b = pairs[2 * (size_t)k + 1];
+    if (inlier_off[k] > inlier_off[k + 1]) return bad(SFMLOC_EINVAL, "inlier_off not monotone at pair %llu", k);
+    const uint64_t n = inlier_off[k + 1] - inlier_off[k], m = offsets[k + 1] - offsets[k];
+    if (inlier_off[k + 1] > kMaxCount)
+      return bad(SFMLOC_ECAP, "%llu inliers up to pair %llu (at most 2^31 - 1024)", inlier_off[k + 1], k);
+    if (n && !inlier_idx) return bad(SFMLOC_EINVAL, "inlier_idx missing");
+    for (uint64_t p = 0; p < n; ++p)
+      if (inlier_idx[inlier_off[k] + p] >= m)
+        return bad(SFMLOC_EINVAL, "pair (%llu, %llu) inlier %llu out of range", a, b, p);
+    for (int i = 0; i < 12; ++i)
+      if (!isfinite(i < 9 ? rel_R[9 * (size_t)k + i] : rel_t[3 * (size_t)k + i - 9]))
+        return bad(SFMLOC_EINVAL, "pair (%llu, %llu) has a non-finite rel_R or rel_t", a, b);
+  }
+  return SFMLOC_OK;
+}
+
 // sfmloc.h "Refusals" -> SFMLOC_OK and the lists, or the code with its text in *err and *vp untouched
 inline int check(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_intrinsic,
                  const double *intrinsics, const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs,
@@ -56,29 +87,16 @@ inline int check(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy
   if (opt.min_shared < 1) return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: min_shared = %llu (at least 1)", opt.min_shared);
   if (opt.max_shared < 1 || opt.max_shared > kMaxShared)
     return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: max_shared = %llu (1 to 2048)", opt.max_shared);
-  if (n_pairs && (!rel_R || !rel_t || !inlier_off))
-    return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: pose or inlier arrays missing");
-  if (n_pairs && inlier_off[0] != 0) return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: inlier_off[0] must be 0");
+  const int rc_inl = check_inliers("sfmloc_wedge_scales", pairs, n_pairs, offsets, rel_R, rel_t, inlier_off, inlier_idx, err);
+  if (rc_inl) return rc_inl;
   std::vector<uint32_t> off((size_t)n_views + 1, 0);
   uint32_t n_used = 0;
   uint64_t n_inl = 0;
   for (uint32_t k = 0; k < n_pairs; ++k) {
     const uint32_t a = pairs[2 * (size_t)k], b = pairs[2 * (size_t)k + 1];
-    if (inlier_off[k] > inlier_off[k + 1])
-      return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: inlier_off not monotone at pair %llu", k);
-    const uint64_t n = inlier_off[k + 1] - inlier_off[k], m = offsets[k + 1] - offsets[k];
-    if (inlier_off[k + 1] > kMaxCount)
-      return fail(err, SFMLOC_ECAP, "sfmloc_wedge_scales: %llu inliers up to pair %llu (at most 2^31 - 1024)", inlier_off[k + 1], k);
-    if (n && !inlier_idx) return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: inlier_idx missing");
-    for (uint64_t p = 0; p < n; ++p)
-      if (inlier_idx[inlier_off[k] + p] >= m)
-        return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: pair (%llu, %llu) inlier %llu out of range", a, b, p);
-    for (int i = 0; i < 12; ++i)
-      if (!isfinite(i < 9 ? rel_R[9 * (size_t)k + i] : rel_t[3 * (size_t)k + i - 9]))
-        return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: pair (%llu, %llu) has a non-finite rel_R or rel_t", a, b);
     if (use_pair && !use_pair[k]) continue;
     ++n_used;
-    n_inl += n;
+    n_inl += inlier_off[k + 1] - inlier_off[k];
     ++off[a + 1];
     ++off[b + 1];
   }

@@ -142,11 +142,8 @@ __global__ __launch_bounds__(256) void k_rp_bearings(uint32_t n_pairs, const uin
       const uint32_t ii = view_intr[v[side]];
       const double *K = intr + 6 * (size_t)ii;
       const uint64_t row = view_off[v[side]] + (side ? match_j[t] : match_i[t]);
-      const double x = (double)kpt_xy[2 * row], y = (double)kpt_xy[2 * row + 1];
-      double ux = x, uy = y;
-      if (intr_type[ii] == 3) ud_pixel_k3(K[0], K[1], K[2], K[3], K[4], K[5], x, y, &ux, &uy);
-      bear[4 * t + 2 * side] = (ux - K[1]) / K[0];
-      bear[4 * t + 2 * side + 1] = (uy - K[2]) / K[0];
+      view_bearing(K, intr_type[ii], (double)kpt_xy[2 * row], (double)kpt_xy[2 * row + 1], &bear[4 * t + 2 * side],
+                   &bear[4 * t + 2 * side + 1]);
     }
   }
 }

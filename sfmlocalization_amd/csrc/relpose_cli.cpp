@@ -2,12 +2,14 @@
 //
 //   ComputeRelativePoses -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>] [-o <matches.e.txt>]
 //                        [-p <relative_poses.json>] [-n <iterations = 256>] [-t <precision px = 2.5>] [--seed N] [--device 0]
-//                        [-s <pair scales = none>]
+//                        [-s <pair scales = none>] [--refine]
 //
 // The same program as sfmlocalization_amd/relpose.py and the same bytes in both output files: the relative pose of every
 // matched view pair (sfmloc_relative_poses, the first stage of openMVG_main_GlobalSfM).  The essential matches hold the ok
-// pairs only, each with its inliers in ascending (i, j); the poses file lists them in ascending (I, J).  With -s the
-// records of sfmloc_wedge_scales on the call's results are written by view ids (sfm_files.h write_pair_scales).
+// pairs only, each with its inliers in ascending (i, j); the poses file lists them in ascending (I, J).  With --refine
+// sfmloc_refine_relative_poses runs on the ok pairs: every entry gains "refine" and carries the refined R, t and E where
+// its status is 1 or 3.  With -s the records of sfmloc_wedge_scales on the call's results (the refined poses after
+// --refine) are written by view ids (sfm_files.h write_pair_scales).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -44,7 +46,8 @@ void usage() {
           "[-t|--precision] upper bound on the residual in pixels (2.5)\n"
           "[--seed] sampling seed\n"
           "[--device] HIP device (0)\n"
-          "[-s|--scales_file] pair scales to write (default: none)\n",
+          "[-s|--scales_file] pair scales to write (default: none)\n"
+          "[--refine] adjust every ok pair's pose on its inliers\n",
           kName);
 }
 
@@ -65,9 +68,14 @@ Value rows3(const double *v) {
 int main(int argc, char **argv) {
   std::string in, match_dir, match_file = "matches.f.txt", out_file = "matches.e.txt", poses_file = "relative_poses.json",
               n_txt = "256", t_txt = "2.5", seed_txt, dev_txt = "0", scales_file;
+  bool refine = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     std::string *dst = nullptr;
+    if (a == "--refine") {
+      refine = true;
+      continue;
+    }
     const size_t eq = a.find('=');
     if (eq != std::string::npos && (a.substr(0, eq) == "--seed" || a.substr(0, eq) == "--device")) {
       (a.substr(0, eq) == "--seed" ? seed_txt : dev_txt) = a.substr(eq + 1);
@@ -187,6 +195,41 @@ int main(int argc, char **argv) {
   printf("Relative poses: %zu of %u pairs; %zu essential matches; device %.3f ms\n", n_ok, n_pairs, n_ess,
          sfmloc_relpose_last_ms());
   fflush(stdout);
+  // the poses the file and the wedge scales carry: the sample's, or after --refine the refinement's where it moved
+  std::vector<double> rel_R(9 * (size_t)n_pairs + 1), rel_t(3 * (size_t)n_pairs + 1), rel_E(9 * (size_t)n_pairs + 1);
+  for (uint32_t k = 0; k < n_pairs; ++k) {
+    std::copy(res[k].R, res[k].R + 9, rel_R.begin() + 9 * (size_t)k);
+    std::copy(res[k].t, res[k].t + 3, rel_t.begin() + 3 * (size_t)k);
+    std::copy(res[k].E, res[k].E + 9, rel_E.begin() + 9 * (size_t)k);
+  }
+  std::vector<sfmloc_relrefine_result> fine;
+  if (refine) {  // sfmloc.h "Two-view refinement" on the ok pairs
+    std::vector<uint8_t> use(n_pairs ? n_pairs : 1);
+    for (uint32_t k = 0; k < n_pairs; ++k) use[k] = res[k].ok ? 1 : 0;
+    sfmloc_relrefine *f = nullptr;
+    if (sfmloc_refine_relative_poses((int)device, view_off.data(), n_views, kpt.data(), d.view_intr.data(), d.intr.data(),
+                                     itype.data(), (uint32_t)itype.size(), pl.pairs.data(), n_pairs, pl.offsets.data(),
+                                     pl.mi.data(), pl.mj.data(), rel_R.data(), rel_t.data(), off.data(), idx.data(),
+                                     use.data(), nullptr, &f)) {
+      fprintf(stderr, "%s: %s\n", kName, sfmloc_last_error());
+      return 1;
+    }
+    fine.resize(n_pairs ? n_pairs : 1);
+    sfmloc_relrefine_results(f, fine.data());
+    sfmloc_relrefine_destroy(f);
+    size_t count[5] = {0, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < n_pairs; ++k) {
+      const sfmloc_relrefine_result &q = fine[k];
+      if (q.status < 5) ++count[q.status];
+      if (q.status != 1 && q.status != 3) continue;
+      std::copy(q.R, q.R + 9, rel_R.begin() + 9 * (size_t)k);
+      std::copy(q.t, q.t + 3, rel_t.begin() + 3 * (size_t)k);
+      std::copy(q.E, q.E + 9, rel_E.begin() + 9 * (size_t)k);
+    }
+    printf("Two-view refinement: %zu converged, %zu at the step limit, %zu with too few points, %zu not moved, %zu not "
+           "asked; device %.3f ms\n", count[1], count[3], count[2], count[4], count[0], sfmloc_relrefine_last_ms());
+    fflush(stdout);
+  }
   std::string etxt;
   Value list = Value::make_arr();
   for (uint32_t k = 0; k < n_pairs; ++k) {  // (the pair list ascends by (I, J): view ids ascend with the view index)
@@ -206,12 +249,23 @@ int main(int argc, char **argv) {
     e.o.emplace_back("J", make_int(d.view_id[b]));
     e.o.emplace_back("n_matches", make_int(r.n_matches));
     e.o.emplace_back("n_inliers", make_int(r.n_inliers));
-    e.o.emplace_back("R", rows3(r.R));
-    e.o.emplace_back("t", floats(r.t, 3));
-    e.o.emplace_back("E", rows3(r.E));
+    e.o.emplace_back("R", rows3(&rel_R[9 * (size_t)k]));
+    e.o.emplace_back("t", floats(&rel_t[3 * (size_t)k], 3));
+    e.o.emplace_back("E", rows3(&rel_E[9 * (size_t)k]));
     e.o.emplace_back("error_max", Value::make_float(r.error_max_px));
     e.o.emplace_back("front", front);
     e.o.emplace_back("choice", make_int(r.choice));
+    if (refine) {
+      const sfmloc_relrefine_result &q = fine[k];
+      Value f;
+      f.kind = Value::Obj;
+      f.o.emplace_back("status", make_int(q.status));
+      f.o.emplace_back("n_used", make_int(q.n_used));
+      f.o.emplace_back("steps", make_int(q.steps));
+      f.o.emplace_back("cost_initial", Value::make_float(q.cost_initial));
+      f.o.emplace_back("cost", Value::make_float(q.cost));
+      e.o.emplace_back("refine", f);
+    }
     list.a.push_back(e);
   }
   Value doc;
@@ -225,13 +279,8 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (!scales_file.empty()) {  // sfmloc.h "Wedge scales" on the pairs whose translation can be trusted
-    std::vector<double> rel_R(9 * (size_t)n_pairs + 1), rel_t(3 * (size_t)n_pairs + 1);
     std::vector<uint8_t> use(n_pairs ? n_pairs : 1);
-    for (uint32_t k = 0; k < n_pairs; ++k) {
-      std::copy(res[k].R, res[k].R + 9, rel_R.begin() + 9 * (size_t)k);
-      std::copy(res[k].t, res[k].t + 3, rel_t.begin() + 3 * (size_t)k);
-      use[k] = res[k].ok && res[k].front[res[k].choice] == res[k].n_inliers;
-    }
+    for (uint32_t k = 0; k < n_pairs; ++k) use[k] = res[k].ok && res[k].front[res[k].choice] == res[k].n_inliers;
     sfmloc_wscales_options wopt;
     sfmloc_wscales_default_options(&wopt);
     sfmloc_wscales *w = nullptr;

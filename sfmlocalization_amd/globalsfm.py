@@ -2,7 +2,7 @@
 the step PyReconstruct/src/reconstructGraph.py:171 runs and whose <outDir>/sfm_data.json it waits for.
 
     python -m sfmlocalization_amd.globalsfm -i <sfm_data.json> -m <matchDir> -o <outDir> [--triplet-angle 5] [--device 0]
-                                            [--pair-scales]
+                                            [--pair-scales] [--refine]
 
 Three stages, each the run() of its own tool, the files of one the input of the next:
     sfmlocalization_amd.relpose       matches.f.txt -> <outDir>/matches.e.txt, <outDir>/relative_poses.json
@@ -12,6 +12,7 @@ Three stages, each the run() of its own tool, the files of one the input of the 
                                       structure adjusted jointly (rst) on the same resident handle and cleaned again
 --pair-scales: relpose also writes <outDir>/pair_scales.json (its -s) and globalposes reads it (its -s), so that the
 spacing of cameras along a line comes from the depths of shared features; without it the chain is what it was.
+--refine: relpose adjusts every ok pair's pose on its inliers (its --refine) before the averaging sees it.
 The first stage that fails ends the run with its message and its exit code.  Python only: there is no C++ program for
 the chain (the stages' own C++ programs can be run one after the other).
 """
@@ -28,10 +29,11 @@ USAGE = (f"Usage: {NAME}\n"
          "\n[Optional]\n"
          "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
          "[--device] HIP device (0)\n"
-         "[--pair-scales] fix the pair baselines from shared features (relpose -s, globalposes -s)\n")
+         "[--pair-scales] fix the pair baselines from shared features (relpose -s, globalposes -s)\n"
+         "[--refine] adjust every relative pose on its inliers before the averaging (relpose --refine)\n")
 
 
-def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pair_scales=False):
+def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pair_scales=False, refine=False):
     """The tool's body.  Returns 0, or the exit code of the stage that failed after its message on stderr."""
     os.makedirs(out_dir, exist_ok=True)
     essential = os.path.join(os.path.abspath(out_dir), "matches.e.txt")
@@ -39,6 +41,8 @@ def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pai
     posed = os.path.join(out_dir, "sfm_data_poses.json")
     scales = os.path.join(os.path.abspath(out_dir), "pair_scales.json") if pair_scales else None
     extra = dict(scales_file=scales) if pair_scales else {}
+    if refine:
+        extra["refine"] = True
     rc = relpose.run(in_path, match_dir, out_file=essential, poses_file=poses, device=device, log=log, **extra)
     if rc:
         return rc
@@ -55,11 +59,11 @@ def parse_args(argv):
     opt = {"-i": "", "-m": "", "-o": "", "--triplet-angle": "5", "--device": "0"}
     long_names = {"--input_file": "-i", "--matchdir": "-m", "--outdir": "-o"}
     i = 0
-    flag = False
+    flag = refine = False
     while i < len(argv):
         a = argv[i]
-        if a == "--pair-scales":
-            flag = True
+        if a in ("--pair-scales", "--refine"):
+            flag, refine = flag or a == "--pair-scales", refine or a == "--refine"
             i += 1
             continue
         if "=" in a and a.split("=", 1)[0] in ("--triplet-angle", "--device"):
@@ -77,6 +81,8 @@ def parse_args(argv):
                   device=int(opt["--device"]))
         if flag:
             kw["pair_scales"] = True
+        if refine:
+            kw["refine"] = True
     except ValueError:
         return None
     if not kw["in_path"] or not kw["match_dir"] or not kw["out_dir"] or not 0.0 < kw["triplet_angle"] < 180.0:

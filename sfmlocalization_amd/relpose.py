@@ -5,7 +5,7 @@ matches.f.txt to matches.e.txt "because OpenMVG assumes matches.e.txt for global
     python -m sfmlocalization_amd.relpose -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>]
                                           [-o <essential matches = matches.e.txt>] [-p <poses = relative_poses.json>]
                                           [-n <iterations = 256>] [-t <precision px = 2.5>] [--seed N] [--device 0]
-                                          [-s <pair scales = none>]
+                                          [-s <pair scales = none>] [--refine]
 
 The views and intrinsics come from the input, <matchDir>/<stem>.feat of every view gives its keypoints, the match file
 (relative to <matchDir> unless absolute, as the two outputs are) the pairs: all read as sfmlocalization_amd.structure
@@ -15,9 +15,13 @@ hold the ok pairs only, each with its inliers in ascending (i, j); the poses fil
 {"relative_poses": [{"I", "J", "n_matches", "n_inliers", "R", "t", "E", "error_max", "front", "choice"}, ...]} in
 ascending (I, J), I and J view ids, R and E as three rows, written with json.dump.  bin/ComputeRelativePoses
 (csrc/relpose_cli.cpp) is the same program and writes the same bytes.  sfmlocalization_amd.globalposes consumes the
-poses file (rotation and translation averaging); the two-view refinement of OpenMVG is not built.  With -s,
-sfmloc_wedge_scales ("Wedge scales") runs on the call's results -- the pairs with ok and front[choice] == n_inliers -- and
-its records are written by view ids (fileio.write_pair_scales), by both programs with the same bytes.
+poses file (rotation and translation averaging).  Without --refine R and t are those of the winning minimal sample.  With
+--refine, sfmloc_refine_relative_poses ("Two-view refinement": OpenMVG's adjustment of every pair on its inliers) runs on
+the ok pairs: every entry gains "refine": {"status", "n_used", "steps", "cost_initial", "cost"} and carries the refined
+R, t and E where the status is 1 or 3; n_inliers, front, choice and the essential matches stay the sample's.  With -s,
+sfmloc_wedge_scales ("Wedge scales") runs on the call's results -- the pairs with ok and front[choice] == n_inliers, under
+the refined poses after --refine -- and its records are written by view ids (fileio.write_pair_scales), by both programs
+with the same bytes.
 """
 import json
 import os
@@ -41,7 +45,8 @@ USAGE = (f"Usage: {NAME}\n"
          "[-t|--precision] upper bound on the residual in pixels (2.5)\n"
          "[--seed] sampling seed\n"
          "[--device] HIP device (0)\n"
-         "[-s|--scales_file] pair scales to write (default: none)\n")
+         "[-s|--scales_file] pair scales to write (default: none)\n"
+         "[--refine] adjust every ok pair's pose on its inliers\n")
 
 
 def view_sizes(doc):
@@ -50,18 +55,30 @@ def view_sizes(doc):
                      for e in doc["views"]], np.uint32).reshape(-1, 2)
 
 
-def pose_entries(view_id, pairs, results):
-    """the `relative_poses` list: the ok pairs, ascending (I, J)"""
+def pose_entries(view_id, pairs, results, refined=None):
+    """the `relative_poses` list: the ok pairs, ascending (I, J).  refined (RELREFINE_RESULT per pair, or None): every
+    entry gains "refine", and R, t and E are the refinement's where its status is 1 or 3"""
     out = []
-    for (a, b), r in zip(pairs, results):
+    for k, ((a, b), r) in enumerate(zip(pairs, results)):
         if not int(r["ok"]):
             continue
+        p = r if refined is None or int(refined[k]["status"]) not in (1, 3) else refined[k]
         out.append({"I": int(view_id[a]), "J": int(view_id[b]), "n_matches": int(r["n_matches"]),
-                    "n_inliers": int(r["n_inliers"]), "R": [[float(x) for x in r["R"][3 * i:3 * i + 3]] for i in range(3)],
-                    "t": [float(x) for x in r["t"]], "E": [[float(x) for x in r["E"][3 * i:3 * i + 3]] for i in range(3)],
+                    "n_inliers": int(r["n_inliers"]), "R": [[float(x) for x in p["R"][3 * i:3 * i + 3]] for i in range(3)],
+                    "t": [float(x) for x in p["t"]], "E": [[float(x) for x in p["E"][3 * i:3 * i + 3]] for i in range(3)],
                     "error_max": float(r["error_max_px"]), "front": [int(x) for x in r["front"]],
                     "choice": int(r["choice"])})
+        if refined is not None:
+            f = refined[k]
+            out[-1]["refine"] = {"status": int(f["status"]), "n_used": int(f["n_used"]), "steps": int(f["steps"]),
+                                 "cost_initial": float(f["cost_initial"]), "cost": float(f["cost"])}
     return out
+
+
+def refined_poses(results, refined):
+    """(R [P, 9], t [P, 3]): the refinement's where its status is 1 or 3, the sample's otherwise"""
+    took = np.isin(refined["status"], (1, 3))
+    return np.where(took[:, None], refined["R"], results["R"]), np.where(took[:, None], refined["t"], results["t"])
 
 
 def scale_pairs(results):
@@ -91,7 +108,7 @@ def essential_matches(view_id, pairs, offsets, match_i, match_j, rp):
 
 
 def run(in_path, match_dir, match_file="matches.f.txt", out_file="matches.e.txt", poses_file="relative_poses.json",
-        max_iteration=256, precision_px=2.5, seed=None, device=0, log=print, scales_file=None):
+        max_iteration=256, precision_px=2.5, seed=None, device=0, log=print, scales_file=None, refine=False):
     """The tool's body.  Returns 0, or 1 after an error message on stderr."""
     from . import capi as S
     try:
@@ -139,13 +156,26 @@ def run(in_path, match_dir, match_file="matches.f.txt", out_file="matches.e.txt"
     n_ok = int(sum(int(r["ok"]) for r in rp.results))
     log(f"Relative poses: {n_ok} of {len(pairs)} pairs; {int(sum(int(r['n_inliers']) for r in rp.results if r['ok']))} "
         f"essential matches; device {rp.ms:.3f} ms")
+    rel_R, rel_t, refined = rp.results["R"], rp.results["t"], None
+    if refine:
+        try:
+            rr = S.RelRefine(view_off, kpt, arrays["view_intrinsic"], arrays["intrinsic"], itype, pairs, offsets, mi, mj,
+                             rel_R, rel_t, rp.inl_off, rp.inl_idx, use_pair=rp.results["ok"], device=int(device))
+        except S.SfmlocError as e:
+            print(f"{NAME}: {e.message}", file=sys.stderr)
+            return 1
+        refined = rr.results
+        rel_R, rel_t = refined_poses(rp.results, refined)
+        count = [int(np.sum(refined["status"] == s)) for s in range(5)]
+        log(f"Two-view refinement: {count[1]} converged, {count[3]} at the step limit, {count[2]} with too few points, "
+            f"{count[4]} not moved, {count[0]} not asked; device {rr.ms:.3f} ms")
     fileio.write_matches_txt(at(out_file), essential_matches(arrays["view_id"], pairs, offsets, mi, mj, rp))
     with open(at(poses_file), "w") as fh:
-        json.dump({"relative_poses": pose_entries(arrays["view_id"], pairs, rp.results)}, fh)
+        json.dump({"relative_poses": pose_entries(arrays["view_id"], pairs, rp.results, refined)}, fh)
     if scales_file:
         try:
             ws = S.WedgeScales(view_off, kpt, arrays["view_intrinsic"], arrays["intrinsic"], itype, pairs, offsets, mi, mj,
-                               rp.results["R"], rp.results["t"], rp.inl_off, rp.inl_idx, use_pair=scale_pairs(rp.results),
+                               rel_R, rel_t, rp.inl_off, rp.inl_idx, use_pair=scale_pairs(rp.results),
                                device=int(device))
         except S.SfmlocError as e:
             print(f"{NAME}: {e.message}", file=sys.stderr)
@@ -164,9 +194,13 @@ def parse_args(argv):
            "-t": "2.5", "--seed": "", "--device": "0", "-s": ""}
     long_names = {"--input_file": "-i", "--match_dir": "-m", "--match_file": "-f", "--output_file": "-o",
                   "--poses_file": "-p", "--max_iteration": "-n", "--precision": "-t", "--scales_file": "-s"}
-    i = 0
+    i, refine = 0, False
     while i < len(argv):
         a = argv[i]
+        if a == "--refine":
+            refine = True
+            i += 1
+            continue
         if "=" in a and a.split("=", 1)[0] in ("--seed", "--device"):
             a, val = a.split("=", 1)
         else:
@@ -187,6 +221,8 @@ def parse_args(argv):
         return None
     if opt["-s"]:
         kw["scales_file"] = opt["-s"]
+    if refine:
+        kw["refine"] = True
     return kw
 
 

@@ -1,0 +1,148 @@
+// Host program over sfmlocalization_amd/csrc/relrefine_host.h, the host side of sfmloc_refine_relative_poses: every
+// refusal with its code and text -- those of the relative poses and of the wedge scales under this call's name, and the
+// options' own.  No HIP, no GPU: meant to be built with -fsanitize=address,undefined and run on the CPU
+// (tests/test_relrefine_cpu.py does).
+#include <cstdio>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../sfmlocalization_amd/csrc/relrefine_host.h"
+
+using namespace sfmloc::relrefine_host;
+
+static int g_fail = 0;
+#define EXPECT(c)                                        \
+  do {                                                   \
+    if (!(c)) {                                          \
+      printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); \
+      ++g_fail;                                          \
+    }                                                    \
+  } while (0)
+
+// five views of four features each; the pairs (3, 1), (0, 1), (1, 2), (4, 0) with two matches each, the second an inlier
+struct Case {
+  uint32_t n_views = 5;
+  std::vector<uint64_t> view_off{0, 4, 8, 12, 16, 20};
+  std::vector<float> kpt = std::vector<float>(40, 1.f);
+  std::vector<uint32_t> view_intr{0, 0, 0, 0, 0}, itype{0};
+  std::vector<double> intr{100, 50, 50, 0, 0, 0};
+  std::vector<uint32_t> pairs{3, 1, 0, 1, 1, 2, 4, 0};
+  std::vector<uint64_t> offsets, inl_off;
+  std::vector<uint32_t> mi, mj, inl;
+  std::vector<double> R, t;
+  sfmloc_relrefine_options opt{100, 13};
+  std::string err;
+  Case() {
+    const size_t P = pairs.size() / 2;
+    offsets.assign(1, 0);
+    inl_off.assign(1, 0);
+    for (size_t k = 0; k < P; ++k) {
+      mi.insert(mi.end(), {0, 3});
+      mj.insert(mj.end(), {1, 2});
+      offsets.push_back(mi.size());
+      inl.push_back(1);
+      inl_off.push_back(inl.size());
+    }
+    R.assign(9 * P, 0.0);
+    t.assign(3 * P, 0.0);
+    for (size_t k = 0; k < P; ++k) R[9 * k] = R[9 * k + 4] = R[9 * k + 8] = t[3 * k] = 1.0;
+  }
+  int run() {
+    return check(view_off.data(), n_views, kpt.data(), view_intr.data(), intr.data(), itype.data(), 1, pairs.data(),
+                 (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(), mj.data(), R.data(), t.data(), inl_off.data(),
+                 inl.data(), opt, &err);
+  }
+  bool refused(int code, const char *text) {
+    const int rc = run();
+    if (rc != code || err.find(text) == std::string::npos) {
+      printf("  got %d `%s`, wanted %d `%s`\n", rc, err.c_str(), code, text);
+      return false;
+    }
+    return true;
+  }
+};
+
+int main() {
+  {  // a good call; the floor of min_points itself; no pairs at all
+    Case c;
+    EXPECT(c.run() == SFMLOC_OK && c.err.empty());
+    c.opt.min_points = kMinPointsFloor;
+    c.opt.max_steps = 1;
+    EXPECT(c.run() == SFMLOC_OK);
+    EXPECT(check(c.view_off.data(), 5, c.kpt.data(), c.view_intr.data(), c.intr.data(), c.itype.data(), 1, nullptr, 0, nullptr,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c.opt, &c.err) == SFMLOC_OK);
+  }
+  {  // the checks of the relative poses, under this call's name
+    Case c;
+    c.pairs[5] = 5;
+    EXPECT(c.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: pair 2 = (1, 5) out of range"));
+    Case d;
+    d.pairs[2] = 1;
+    EXPECT(d.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: pair 1 names view 1 twice"));
+    Case e;
+    e.mj[3] = 4;
+    EXPECT(e.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: pair (0, 1) match 1 out of range"));
+    Case f;
+    f.itype[0] = 2;
+    EXPECT(f.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: intrinsic 0 has type 2"));
+    Case g;
+    g.view_intr[4] = 1;
+    EXPECT(g.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: view 4 names intrinsic 1 of 1"));
+    Case h;
+    h.view_off[0] = 1;
+    EXPECT(h.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: view_off[0] must be 0"));
+    Case i;
+    i.offsets[2] = 1;
+    EXPECT(i.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: offsets not monotone at pair 1"));
+    Case j;
+    EXPECT(check(j.view_off.data(), 5, j.kpt.data(), j.view_intr.data(), j.intr.data(), j.itype.data(), 1, j.pairs.data(),
+                 0x40000000u, j.offsets.data(), j.mi.data(), j.mj.data(), j.R.data(), j.t.data(), j.inl_off.data(),
+                 j.inl.data(), j.opt, &j.err) == SFMLOC_ECAP && j.err.find("1073741824 pairs") != std::string::npos);
+  }
+  {  // those of the wedge scales: an inlier position out of its pair's range; offsets that go back; a missing array
+    Case c;
+    c.inl[2] = 2;
+    EXPECT(c.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: pair (1, 2) inlier 0 out of range"));
+    Case d;
+    d.inl_off = {0, 1, 3, 2, 4};
+    EXPECT(d.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: inlier_off not monotone at pair 2"));
+    Case e;
+    e.inl_off[0] = 1;
+    EXPECT(e.refused(SFMLOC_EINVAL, "inlier_off[0] must be 0"));
+    Case f;
+    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
+                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), nullptr, f.inl_off.data(), f.inl.data(), f.opt,
+                 &f.err) == SFMLOC_EINVAL && f.err.find("pose or inlier arrays missing") != std::string::npos);
+    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
+                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), f.t.data(), f.inl_off.data(), nullptr, f.opt,
+                 &f.err) == SFMLOC_EINVAL && f.err.find("inlier_idx missing") != std::string::npos);
+    Case g;
+    g.inl_off = {0, 1, 2, 3, 0x7FFFFC01ull};  // (refused before the list behind it is read)
+    EXPECT(g.refused(SFMLOC_ECAP, "2147482625 inliers up to pair 3"));
+  }
+  {  // a non-finite rotation or translation
+    Case c;
+    c.R[9 + 4] = std::numeric_limits<double>::quiet_NaN();
+    EXPECT(c.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: pair (0, 1) has a non-finite rel_R or rel_t"));
+    Case d;
+    d.t[3 * 3 + 2] = std::numeric_limits<double>::infinity();
+    EXPECT(d.refused(SFMLOC_EINVAL, "pair (4, 0) has a non-finite rel_R or rel_t"));
+  }
+  {  // the options
+    Case c;
+    c.opt.max_steps = 0;
+    EXPECT(c.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: max_steps = 0"));
+    for (uint32_t m : {0u, 5u}) {
+      Case d;
+      d.opt.min_points = m;
+      EXPECT(d.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: min_points = "));
+    }
+  }
+  if (g_fail) {
+    printf("%d check(s) failed\n", g_fail);
+    return 1;
+  }
+  printf("OK relrefine_host\n");
+  return 0;
+}
