@@ -1603,6 +1603,11 @@ void sfmloc_debug_fail_p3p_alloc(int k);
 /* Test hook: the calling thread's k-th device allocation from now on (0 = the next) fails once with SFMLOC_ENOMEM, in
  * whatever call makes it; -1 disarms.  An armed sfmloc_debug_fail_p3p_alloc takes the countdown over for its regrowth. */
 void sfmloc_debug_fail_next_alloc(int k);
+/* The geometric filter's register forms keep, per wave, the sorted match list of the model the wave evaluated last.
+ * out[0]: how often a view's new best model took its inlier list from there, out[1]: how often one wave had to evaluate
+ * the model again for it, on `device`, by every map of the process since the last reset (reset != 0 clears both after
+ * reading; out may be null).  Synchronises the device.  For tests: the two ways give the same list. */
+int sfmloc_debug_k3_list_counts(int device, uint64_t *out, int reset);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement (params.profile = 1): accumulated HIP-event time per kernel on  */

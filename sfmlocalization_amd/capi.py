@@ -312,6 +312,14 @@ def debug_fail_next_alloc(k):
     _L().sfmloc_debug_fail_next_alloc(int(k))
 
 
+def k3_list_counts(reset=False, device=0):
+    """sfmloc_debug_k3_list_counts: (inlier lists K3's register forms copied from the evaluating wave's segment, lists a
+    wave evaluated the model again for) on `device` since the last reset; reset=True clears both after reading."""
+    out = np.zeros(2, np.uint64)
+    _check(_L().sfmloc_debug_k3_list_counts(int(device), _ptr(out, C.c_uint64), int(bool(reset))))
+    return int(out[0]), int(out[1])
+
+
 def debug_math(op, x, out_stride, device=0):
     """sfmloc_debug_math: run an f64 device building block over the rows of x."""
     x = np.ascontiguousarray(x, dtype=np.float64)

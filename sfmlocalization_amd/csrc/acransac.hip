@@ -724,7 +724,8 @@ __global__ __launch_bounds__(kThreads) void k_fmatrix_large(FFilterArgsPacked P,
 //   * while sampling is still uniform the iterations are independent, so a batch of them is solved and their
 //     models are evaluated speculatively, one MODEL per wave (residuals -> per-wave bitonic sort -> bestNFA), eight
 //     side by side; the sequential acceptance rule of ACRANSAC is then replayed over the results in iteration
-//     order, and the winner's inlier list is rebuilt by evaluating that one model again;
+//     order, and the winner's inlier list is taken from the wave that evaluated it, or, where that wave has
+//     evaluated another model since (or was another workgroup's), rebuilt by evaluating that one model again;
 //   * after the switch to inlier sampling each iteration depends on the previous one: wave 0 solves, waves 0..2
 //     evaluate the (up to 3) models side by side.
 // Results are bit-identical to k_fmatrix_filter (same samples, same arithmetic per value, same tie rules).
@@ -746,6 +747,7 @@ template <int W, int MaxM = kF2MaxM>
 struct F2SharedT {
   static constexpr int kF2MaxM = MaxM;
   uint32_t idx[W][kF2MaxM];  // sorted match indices of the model each wave evaluated last
+  int idx_model[W];          // ... which model: its flattened index in the current batch, or -1 (none of this batch's)
   double pts[4][kF2MaxM];  // normalised x, y of the map keypoint, u, w of the query keypoint (one plane each: a
                            // wave reading element p of 64 consecutive matches hits 64 different banks)
   int32_t vec_index[kF2MaxM];
@@ -761,6 +763,14 @@ struct F2SharedT {
   uint8_t flat_b[kF2Batch * 3], flat_k[kF2Batch * 3];
   unsigned int wide_ticket;  // the wide form: this workgroup's arrival number
 };
+
+// How often a view's best model got its sorted inlier list from the segment of the wave that evaluated it [0] / from
+// wave 0 evaluating the model again [1] (fmatrix_fast.body.inc take_inliers), since the last reset: the tests tell the
+// reuse from a permanent fall-back by it (sfmloc_debug_k3_list_counts).  One relaxed add by one thread per fetched list.
+__device__ unsigned long long g_k3_list_counts[2];
+__device__ __forceinline__ void k3_count_list(bool copied) {
+  __hip_atomic_fetch_add(&g_k3_list_counts[copied ? 0 : 1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2651,6 +2661,7 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
 template <int W, int MaxM, bool kWide>
 static hipError_t launch_fmatrix_fast(Ctx *c, const FFilterArgs &A, int wide_b0) {
   using Sh = F2SharedT<W, MaxM>;
+  static_assert(sizeof(Sh) <= 160 * 1024, "a workgroup's lists must fit a compute unit's LDS (160 KiB on gfx950)");
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<W, MaxM, kWide>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh));
   if (attr != hipSuccess) return attr;
@@ -2735,6 +2746,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec.get());
     A.spec_arrive = c->d_k3_arrive;
     const hipError_t e = P.max_m == kF2HugeM ? launch_fmatrix_fast<4, kF2HugeM, true>(c, A, P.wide_b0)
+                         : P.wide_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, true>(c, A, P.wide_b0)
                                              : launch_fmatrix_fast<4, kF2BigM, true>(c, A, P.wide_b0);
     SFM_HIP(e);
     SFM_HIP(hipGetLastError());
@@ -2893,6 +2905,22 @@ int launch_p3p_finish(Ctx *c) {
 }
 
 
+int debug_k3_list_counts(int device, uint64_t *out, int reset) {
+  SFM_HIP(hipSetDevice(device));
+  SFM_HIP(hipDeviceSynchronize());
+  unsigned long long v[2] = {0, 0};
+  if (out) {
+    SFM_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_k3_list_counts), sizeof(v)));
+    out[0] = v[0];
+    out[1] = v[1];
+  }
+  if (reset) {
+    v[0] = v[1] = 0;
+    SFM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_k3_list_counts), v, sizeof(v)));
+  }
+  return SFMLOC_OK;
+}
+
 #ifdef SFMLOC_STAMPS
 int debug_stamps_read(int which, unsigned long long *out, size_t n) {
   hipDeviceSynchronize();
@@ -2911,6 +2939,10 @@ int debug_stamps_clear() {
 }
 #endif
 }  // namespace sfmloc
+
+extern "C" int sfmloc_debug_k3_list_counts(int device, uint64_t *out, int reset) {
+  return sfmloc::debug_k3_list_counts(device, out, reset);
+}
 
 #ifdef SFMLOC_STAMPS
 extern "C" int sfmloc_debug_stamps_read(int which, unsigned long long *out, unsigned long long n) {

@@ -142,6 +142,7 @@
   bool inl_valid = true;  // S.best_inl holds the inliers of the best model (vacuously: n_in == 0)
   int n_index = m;
   long iter = 0;
+  int best_mi = -1;  // S.best_model as a flattened model of the current batch, or -1: it came from an earlier one
 
   // wave 0 rebuilds the inlier list of S.best_model into best_inl (and vec_index when `to_index`)
   auto rebuild_inliers = [&wave_eval, Sp, wv, lane, &n_in](bool to_index) {
@@ -149,6 +150,7 @@
     __syncthreads();
     if (wv == 0) {
       (void)wave_eval(S.best_model);
+      if (lane == 0) S.idx_model[0] = -1;  // (wave 0's segment holds this list now, no model of the batch's)
       wave_lds_sync();
       for (int p = lane; p < n_in; p += 64) {
         const int32_t q = (int32_t)S.idx[0][p];
@@ -157,6 +159,29 @@
       }
     }
     __syncthreads();
+  };
+  // The inlier list of the batch's flattened model `mi`, which has just become S.best_model (mi < 0: of an earlier
+  // batch's).  The wave that evaluated it left exactly that list -- the same function on the same inputs -- in its
+  // segment of S.idx; unless that wave has evaluated another model since, every thread copies from there.  Otherwise,
+  // and always for the wide form's first batch, which other workgroups evaluated: rebuild_inliers.
+  auto take_inliers = [&rebuild_inliers, Sp, tid, &n_in](int mi, bool to_index) {
+    F2Shared &S = *Sp;
+    int owner = -1;
+    if (mi >= 0)
+      for (int w = 0; w < kF2Waves; ++w)
+        if (S.idx_model[w] == mi) owner = w;
+    if (tid == 0) k3_count_list(owner >= 0);
+    if (owner < 0) {
+      rebuild_inliers(to_index);
+      return;
+    }
+    for (int p = tid; p < n_in; p += kF2Threads) {
+      const int32_t q = (int32_t)S.idx[owner][p];
+      S.best_inl[p] = q;
+      if (to_index) S.vec_index[p] = q;
+    }
+    // (no barrier: nothing reads the two lists, or writes a segment of S.idx, before the next batch's first barrier or
+    // the one behind the loop)
   };
 
   // The WIDE form (a query alone on the GPU): gridDim.y workgroups per view, one per iteration of the first uniform batch.
@@ -215,6 +240,8 @@
     const int32_t *const sample_from = identity ? nullptr : S.vec_index;
     const int n_from = identity ? m : n_index;
     __syncthreads();  // pre_* / res_* of the previous batch are no longer read
+    if (tid < kF2Waves) S.idx_model[tid] = -1;  // flattened indices count from zero again: no segment holds a model of this batch
+    best_mi = -1;
     if (!first_batch_done)
       for (int b = wv; b < B; b += kF2Waves) wave_solve(sample_from, n_from, iter + b, S.pre_models[b], &S.pre_nm[b]);
     __syncthreads();
@@ -254,6 +281,7 @@
         if (better) {
           inl_valid = false;
           if (tid < 9) S.best_model[tid] = S.pre_models[b][9 * bk + tid];
+          best_mi = (b ? S.iter_end[b - 1] : 0) + bk;
         }
         ++b_done;
         const long it = iter + b;
@@ -262,7 +290,9 @@
             n_iter++;
             n_reserve--;  // the iteration budget moved: close this batch here
           } else {
-            rebuild_inliers(true);
+            STAMP_F(6);  // the sampled set changes: the new set's sorted list is fetched (7: there)
+            take_inliers(best_mi, true);
+            STAMP_F(7);
             inl_valid = true;
             n_index = n_in;
             identity = false;
@@ -281,6 +311,7 @@
         const int bb = S.flat_b[mi], kk = S.flat_k[mi];
         const NfaBest r = wave_eval(&S.pre_models[bb][9 * kk]);
         if (lane == 0) {
+          S.idx_model[wv] = mi;  // (this wave's segment of S.idx: that model's sorted matches, until it evaluates again)
           S.res_nfa[bb][kk] = r.nfa;
           S.res_k[bb][kk] = r.k;
         }
@@ -296,7 +327,11 @@
   STAMP_F(8);
   if (min_nfa >= 0.0) n_in = 0;
   if ((double)n_in > 7 * 2.5) {
-    if (!inl_valid) rebuild_inliers(false);
+    if (!inl_valid) {
+      STAMP_F(6);
+      take_inliers(best_mi, false);
+      STAMP_F(7);
+    }
     for (int p = tid; p < n_in; p += kF2Threads) A.geo_idx[off + p] = (uint32_t)S.best_inl[p];
     if (tid == 0) A.geo_count[v] = (uint32_t)n_in;
     __syncthreads();

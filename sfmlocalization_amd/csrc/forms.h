@@ -33,6 +33,7 @@ constexpr int kF2HugeM = 2048;     // ... of its 32-residuals-per-lane instance 
 constexpr int kFMaxM = 2048;       // putative matches per view the block-wide LDS sort holds (k_fmatrix_filter)
 constexpr int kF2Batch = 32;       // uniform iterations solved speculatively per batch
 constexpr int kK3WideViews = 256;  // view lists the wide form takes (its result slots: 2 MB per context)
+constexpr int kK3WideWaves = 4;    // waves per workgroup of the wide form's kF2BigM instance unless the knob says otherwise
 
 // K5
 constexpr int kP3pSmallN = 512;  // correspondences the small form of a round holds
@@ -69,6 +70,7 @@ struct Knobs {
   int k3_wide = 1;                    // SFMLOC_K3_WIDE 0 never, 2 always (tests, campaigns)
   int k3_wide_2048 = 1;               // SFMLOC_K3_WIDE_2048 0 never, 2 always
   int k3_big = 1;                     // SFMLOC_K3_BIG 0 never, 2 always
+  int k3_wide_waves = kK3WideWaves;   // SFMLOC_K3_WIDE_WAVES 4 / 8: waves per workgroup of the wide 1 024-match instance
   int k3_waves_alone = 16;            // SFMLOC_K3_WAVES_ALONE / _SHARED: 16, 4, anything else 8
   int k3_waves_shared = 4;
   int p3p_small = 1;                  // SFMLOC_P3P_SMALL 0 never, 2 always
@@ -93,6 +95,8 @@ inline Knobs read_knobs() {
   k.k3_wide = env_int("SFMLOC_K3_WIDE", 1);
   k.k3_wide_2048 = env_int("SFMLOC_K3_WIDE_2048", 1);
   k.k3_big = env_int("SFMLOC_K3_BIG", 1);
+  const int wide_waves = env_int("SFMLOC_K3_WIDE_WAVES", kK3WideWaves);
+  k.k3_wide_waves = (wide_waves == 4 || wide_waves == 8) ? wide_waves : kK3WideWaves;
   k.k3_waves_alone = env_int("SFMLOC_K3_WAVES_ALONE", 16);
   k.k3_waves_shared = env_int("SFMLOC_K3_WAVES_SHARED", 4);
   k.p3p_small = env_int("SFMLOC_P3P_SMALL", 1);
@@ -258,8 +262,9 @@ struct K3In {
 };
 enum class K3Merge { kDone, kFolded, kInFront };  // K2: ran already / inside k_fmatrix_fast / a launch of its own first
 struct K3Plan {
-  bool wide = false;  // one workgroup per iteration of a view's first batch (fmatrix_fast.body.inc), four waves each
+  bool wide = false;  // one workgroup per iteration of a view's first batch (fmatrix_fast.body.inc)
   int wide_b0 = 0;    // ... that many
+  int wide_waves = 0;  // wide: waves per workgroup (the view's tail runs on them); the kF2HugeM instance has four
   int max_m = kF2MaxM;  // the instance of the first k_fmatrix_fast launch
   K3Merge k2 = K3Merge::kDone;
   int waves = 4;      // plain: waves per view (F2SharedT)
@@ -289,6 +294,11 @@ inline K3Plan plan_k3(const K3In &in, const Knobs &k) {
   if (in.merge_deferred) p.k2 = huge ? K3Merge::kInFront : K3Merge::kFolded;
   if (p.wide) {
     p.max_m = p.skip_le = huge ? kF2HugeM : kF2BigM;
+    // (four waves: at 229 VGPRs an eight-wave workgroup is a compute unit's whole register file, a headline query's ~460
+    // first-batch workgroups then need two generations of the chip and the other queries' kernels wait for whole compute
+    // units -- 4 540 -> 3 940 queries/s -- while the tail it would widen is at most the two reserve iterations at the
+    // default budget: profiles/k3tail_split_after.txt.  Eight stay reachable for larger budgets and the tests.)
+    p.wide_waves = (!huge && k.k3_wide_waves == 8) ? 8 : 4;
     return p;
   }
   // 16 waves per view for a query alone on the GPU, 4 when other contexts have work queued

@@ -94,7 +94,7 @@ def main():
             rows.append((ev[-1][1], b, ev))
         rows.sort(reverse=True)
         print(f"  K3: {len(rows)} active views; the 4 slowest (tag@us: 1 entry 2 prelude 3 solves 4 eval-round 5 batch-closed "
-              f"6 seq-solved 7 seq-done 8 loop-end 9 exit):")
+              f"6 inlier-list-fetch 7 fetched 8 loop-end 9 exit; tools/k3_tail_split.py sums them up):")
         for end, b, ev in rows[:4]:
             print(f"    wg {b:3d} end {end:6.1f}: " + " ".join(f"{t}@{x:.0f}" for t, x in ev))
         ends = np.array([r[0] for r in rows])
