@@ -939,6 +939,70 @@ void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o);
 int sfmloc_sfm_triangulate(sfmloc_sfm *h, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep);
 
 /* ------------------------------------------------------------------------- */
+/* Growing a map (sfmloc_sfm_register): the views the global chain left without a pose are resected against the kept     */
+/* structure, the structure takes in their observations and the landmarks they make triangulable, round after round.     */
+/* The growth step of incremental SfM, seeded by a structure that exists: the handle's keep masks must exist (after      */
+/* sfmloc_sfm_triangulate or sfmloc_sfm_clean; SFMLOC_EINVAL before).  The reference has no such step (it rebuilds the  */
+/* left-over frames as a map of their own and merges, cleanSfM + sfmMergeGraph): every rule below is a reading chosen    */
+/* here, and tests/register_np.py restates each operation.  A round sees the poses, X and the masks as they stood when  */
+/* it began, so its results do not depend on the order of its views.  A round, in this order:                            */
+/*   count       c[v] = the observations of view v whose landmark is kept; the observation's own keep bit does not       */
+/*               matter (an unposed view's observations are all unkept).                                                 */
+/*   candidates  a view whose id_pose has no valid pose, with c[v] > min_points (MINIMUM_VIEW_NUM_TO_ESTIMATAE_CAMERA_   */
+/*               POSE and its test ">", as sfmloc_sfm_resect), and either never tried on this handle or with c[v] larger */
+/*               than at its last try: a failed view with an unchanged list would repeat its result exactly, the stream  */
+/*               being its own id.  c[v] > 65 536: SFMLOC_ECAP, the "limit" of sfmloc_sfm_resect.  No candidate: the     */
+/*               call ends, and this is not a round.                                                                     */
+/*   list        the view's correspondences are its per-view list ("views" of sfmloc_sfm_resect: ascending landmark id)  */
+/*               compacted to the kept landmarks, (pixel, X).  The pixel is undistorted with get_ud_pixel (the bisection */
+/*               of "angle") for pinhole_radial_k3 and raw for pinhole: not the "raw pixels" quirk of sfmloc_sfm_resect, */
+/*               which stays as it is.                                                                                   */
+/*   resection   K5 as sfmloc_sfm_resect runs it: 32 views per gang session, the sampling stream = id_view, K = (f, ppx, */
+/*               ppy) of the view's intrinsic, params.p3p_max_iteration.  Accepted when K5 reports ok (>= 8 inliers) and, */
+/*               with min_inliers > 0, n_inliers >= min_inliers.  pose[id_pose] = Pose3(R, -R^T t) of KRt_From_P(P);     */
+/*               two accepted views of one round sharing an id_pose: the last in ascending id wins ("success").  A view  */
+/*               that is not accepted stays without a pose.                                                              */
+/*   extend      every unkept observation of a kept landmark in a view registered this round becomes kept iff it passes  */
+/*               "inliers" of sfmloc_sfm_triangulate at residual_px (depth > 0, the residual with the distortion applied */
+/*               against the raw pixel, the arithmetic of "residual").  X does not move.                                 */
+/*   landmarks   a landmark that is not kept, has an observation in a view registered this round and now has at least 2 */
+/*               posed observations is triangulated by the per-landmark procedure of sfmloc_sfm_triangulate, robust     */
+/*               mode, stream = its id, with tri_min_inliers, tri_allow_pairs and residual_px: its X, keep bits and      */
+/*               landmark_keep are what a full sfmloc_sfm_triangulate would give it from the same poses (a failure       */
+/*               leaves X = 0 and nothing kept).  No other landmark is touched.                                          */
+/*   stop        after a round that registers no view, or after max_rounds rounds of this call.  Rounds are numbered     */
+/*               over the handle's life: a later call goes on where the earlier one stopped, so max_rounds = 1 called k  */
+/*               times equals one call with max_rounds = k.                                                              */
+/* The call never changes the pose of a view that had one at entry, X or landmark_keep of a landmark kept at entry, or   */
+/* the keep bit of an observation in a view posed at entry.  sfmloc_sfm_read, sfmloc_sfm_clean and the adjustments see   */
+/* the new poses.  No float atomics and no order-dependent atomics: two runs give the same bits, and a handle that holds */
+/* a subset of the candidate views with the same structure gives those views the same first-round results.               */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_register_options {
+  uint32_t max_rounds;       /* default 16; 0 = until a round registers no view */
+  uint32_t min_points;       /* default 10: a view is tried when it has MORE correspondences than this */
+  uint32_t min_inliers;      /* default 0: K5's own gate (>= 8 inliers) alone; else n_inliers >= this as well */
+  uint32_t tri_min_inliers;  /* default 3 (at least 2) */
+  uint32_t tri_allow_pairs;  /* default 1 */
+  uint32_t reserved;
+  double residual_px;        /* default 4.0 */
+} sfmloc_register_options;
+typedef struct sfmloc_register_report {
+  uint32_t rounds, views_unposed_in, views_tried, views_registered; /* of this call; views_tried counts every try */
+  uint64_t obs_extended, landmarks_tried, landmarks_added;
+  double device_ms;          /* HIP events on the handle's stream around the call, the waits between rounds included */
+} sfmloc_register_report;
+void sfmloc_register_default_options(sfmloc_register_options *o);
+/* opt NULL = the defaults; rep may be NULL */
+int sfmloc_sfm_register(sfmloc_sfm *h, const sfmloc_register_options *opt, sfmloc_register_report *rep);
+/* per view: the result of the LAST round that tried it (zeros if never tried; n_obs = c[v] of that round, R and center
+ * only when accepted); round[k] = that round or -1.  Either pointer may be NULL */
+int sfmloc_sfm_register_read(const sfmloc_sfm *h, sfmloc_sfm_view_result *out /*[n_views]*/, int32_t *round /*[n_views]*/);
+/* inliers of view k as indices into the correspondence list of the round that tried it last, AC-RANSAC order (as
+ * sfmloc_sfm_resect_inliers: a failed view's best model included) */
+int sfmloc_sfm_register_inliers(const sfmloc_sfm *h, uint32_t k, uint32_t *idx, uint32_t cap, uint32_t *n);
+
+/* ------------------------------------------------------------------------- */
 /* Relative poses (the first stage of openMVG_main_GlobalSfM, reconstructGraph.py:166-171: the essential matrix of      */
 /* every matched view pair by the five-point solver under AC-RANSAC, its decomposition and the cheirality test).        */
 /* Rotation and translation averaging consume the result ("Global poses" below); OpenMVG's two-view bundle adjustment  */

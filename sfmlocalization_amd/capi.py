@@ -39,6 +39,8 @@ BaJointOptions = _abi.struct("sfmloc_ba_joint_options")
 BaJointReport = _abi.struct("sfmloc_ba_joint_report")
 TriangulateOptions = _abi.struct("sfmloc_triangulate_options")
 TriangulateReport = _abi.struct("sfmloc_triangulate_report")
+RegisterOptions = _abi.struct("sfmloc_register_options")
+RegisterReport = _abi.struct("sfmloc_register_report")
 RelposeOptions = _abi.struct("sfmloc_relpose_options")
 RelposeResult = _abi.struct("sfmloc_relpose_result")
 RelrefineOptions = _abi.struct("sfmloc_relrefine_options")
@@ -972,6 +974,33 @@ class Sfm:
         _check(_L().sfmloc_sfm_triangulate(self._h, C.byref(opt), C.byref(rep)))
         return rep
 
+    def register(self, **options):
+        """sfmloc_sfm_register: the views without a pose resected against the kept structure, the structure extended,
+        round after round -- options = fields of RegisterOptions over the defaults (max_rounds, min_points, min_inliers,
+        tri_min_inliers, tri_allow_pairs, residual_px) -> RegisterReport"""
+        opt = register_default_options()
+        for k, val in options.items():
+            if k not in ("max_rounds", "min_points", "min_inliers", "tri_min_inliers", "tri_allow_pairs", "residual_px"):
+                raise TypeError(f"register: unknown option {k}")
+            setattr(opt, k, val)
+        rep = RegisterReport()
+        _check(_L().sfmloc_sfm_register(self._h, C.byref(opt), C.byref(rep)))
+        return rep
+
+    def register_read(self):
+        """-> (list of SfmViewResult, one per view: the last round that tried it; round [n_views], -1 = never tried)"""
+        out = (SfmViewResult * self.n_views)()
+        rnd = np.full(max(1, self.n_views), -1, np.int32)
+        _check(_L().sfmloc_sfm_register_read(self._h, out, _ptr(rnd, C.c_int32)))
+        return list(out), rnd[:self.n_views]
+
+    def register_inliers(self, k):
+        n = C.c_uint32(0)
+        _check(_L().sfmloc_sfm_register_inliers(self._h, int(k), None, 0, C.byref(n)))
+        idx = np.zeros(max(1, n.value), np.uint32)
+        _check(_L().sfmloc_sfm_register_inliers(self._h, int(k), _ptr(idx, C.c_uint32), idx.size, C.byref(n)))
+        return idx[:n.value].copy()
+
     def read_intrinsics(self):
         """-> the intrinsics [n_intrinsics, 6] (f, ppx, ppy, k1, k2, k3) as they are now"""
         K = np.zeros((len(self._keep["intrinsic_type"]), 6))
@@ -1018,6 +1047,13 @@ def triangulate_default_options():
     """sfmloc_triangulate_default_options -> TriangulateOptions (robust, 3 inliers, pairs allowed, 4 px)"""
     o = TriangulateOptions()
     _L().sfmloc_triangulate_default_options(C.byref(o))
+    return o
+
+
+def register_default_options():
+    """sfmloc_register_default_options -> RegisterOptions (16 rounds, more than 10 points, 4 px)"""
+    o = RegisterOptions()
+    _L().sfmloc_register_default_options(C.byref(o))
     return o
 
 

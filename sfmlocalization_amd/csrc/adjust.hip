@@ -19,6 +19,8 @@
 //               (sfmloc_sfm_adjust_joint) go to ba_joint.hip the same way; that path moves the intrinsics too.
 //   structure   sfmloc_sfm_triangulate: the same hand-over to triangulate.hip, which rebuilds X and the keep masks from
 //               the poses; from then on the handle behaves as after a cleanup.
+//   growth      sfmloc_sfm_register lives in register.hip: sfm_reg_view hands it the resident arrays, the host's pose
+//               tables (both sides are written) and the K5 contexts; what it keeps between rounds is Sfm::reg.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -80,6 +82,7 @@ struct Sfm {
   // K5's contexts hang off a map without descriptors: its log10 table, parameters and launch heuristics
   sfmloc_map *map = nullptr;
   std::vector<sfmloc_context *> ctx;
+  SfmRegState reg;  // sfmloc_sfm_register (register.hip)
 };
 
 // (the stream is drained before the handle's buffers go with it, and destroyed after them)
@@ -701,7 +704,64 @@ int sfm_adjust_joint_impl(Sfm *h, uint32_t what, const sfmloc_ba_joint_options &
   return sfm_fetch_poses(h);
 }
 
+void sfm_tri_view(Sfm *h, SfmTriView *out) {
+  SfmTriView v;
+  v.s = h->s;
+  v.seed = h->params.seed;
+  v.n_views = h->n_views;
+  v.n_lm = h->n_lm;
+  v.n_obs = h->n_obs;
+  v.d_view_intr = h->d_view_intr;
+  v.d_view_pose = h->d_view_pose;
+  v.d_intr_type = h->d_intr_type;
+  v.d_intr = h->d_intr;
+  v.d_pose_valid = h->d_pose_valid;
+  v.d_pose_R = h->d_pose_R;
+  v.d_pose_C = h->d_pose_C;
+  v.d_lm_id = h->d_lm_id;
+  v.d_lm_X = h->d_lm_X;
+  v.d_obs_off = h->d_obs_off;
+  v.d_obs_view = h->d_obs_view;
+  v.d_obs_x = h->d_obs_x;
+  v.d_ud = h->d_ray;  // (the cleanup's ray scratch, 4 doubles per observation: it is rewritten by every cleanup)
+  v.d_obs_keep = h->d_obs_keep;
+  v.d_lm_stage = h->d_lm_stage;
+  *out = v;
+}
+
 }  // namespace
+
+void sfm_reg_view(sfmloc_sfm *hh, SfmRegView *out) {
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  SfmRegView v;
+  v.device = h->device;
+  v.masks = h->cleaned;
+  v.handle = hh;
+  sfm_tri_view(h, &v.tri);
+  v.n_poses = h->n_poses;
+  v.d_obs_lm = h->d_obs_lm;
+  v.d_vlist = h->d_vlist;
+  v.d_view_off = h->d_view_off;
+  v.d_pose_valid = h->d_pose_valid;
+  v.d_pose_R = h->d_pose_R;
+  v.d_pose_C = h->d_pose_C;
+  v.h_view_id = h->h_view_id.data();
+  v.h_view_intr = h->h_view_intr.data();
+  v.h_view_pose = h->h_view_pose.data();
+  v.h_intr = h->h_intr.data();
+  v.h_pose_valid = h->h_pose_valid.data();
+  v.h_pose_R = h->h_pose_R.data();
+  v.h_pose_C = h->h_pose_C.data();
+  v.state = &h->reg;
+  *out = v;
+}
+
+int sfm_reg_contexts(sfmloc_sfm *hh, uint32_t n, sfmloc_context ***ctx) {
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  const int rc = sfm_ensure_contexts(h, n);
+  *ctx = h->ctx.data();
+  return rc;
+}
 
 void sfm_color_view(const sfmloc_sfm *hh, SfmColorView *out) {
   const Sfm *h = reinterpret_cast<const Sfm *>(hh);
@@ -857,26 +917,7 @@ int sfmloc_sfm_triangulate(sfmloc_sfm *hh, const sfmloc_triangulate_options *opt
   if (rep) memset(rep, 0, sizeof *rep);
   SFM_HIP(hipSetDevice(h->device));
   SfmTriView v;
-  v.s = h->s;
-  v.seed = h->params.seed;
-  v.n_views = h->n_views;
-  v.n_lm = h->n_lm;
-  v.n_obs = h->n_obs;
-  v.d_view_intr = h->d_view_intr;
-  v.d_view_pose = h->d_view_pose;
-  v.d_intr_type = h->d_intr_type;
-  v.d_intr = h->d_intr;
-  v.d_pose_valid = h->d_pose_valid;
-  v.d_pose_R = h->d_pose_R;
-  v.d_pose_C = h->d_pose_C;
-  v.d_lm_id = h->d_lm_id;
-  v.d_lm_X = h->d_lm_X;
-  v.d_obs_off = h->d_obs_off;
-  v.d_obs_view = h->d_obs_view;
-  v.d_obs_x = h->d_obs_x;
-  v.d_ud = h->d_ray;  // (the cleanup's ray scratch, 4 doubles per observation: it is rewritten by every cleanup)
-  v.d_obs_keep = h->d_obs_keep;
-  v.d_lm_stage = h->d_lm_stage;
+  sfm_tri_view(h, &v);
   const int rc = triangulate_run(v, o, rep);
   if (rc) return rc;
   h->cleaned = true;  // the masks exist: a cleanup or an adjustment that follows works on what was kept

@@ -622,7 +622,40 @@ struct SfmTriView {
   const double *d_obs_x;
   double *d_ud;
   uint8_t *d_obs_keep, *d_lm_stage;
+  const uint8_t *d_select = nullptr;  // [n_lm] or null (all): a landmark with 0 is not touched (sfmloc_sfm_register)
 };
 int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep);
+
+// register.hip: what sfmloc_sfm_register works on -- adjust.hip's resident sfm_data with the host's copies of the view
+// and pose tables (the pose tables are written on both sides), and what the handle keeps between rounds and calls
+struct SfmRegState {
+  std::vector<sfmloc_sfm_view_result> res;     // per view: the last round that tried it
+  std::vector<int32_t> round;                  // that round, or -1
+  std::vector<uint32_t> last_cnt;              // its correspondence count then
+  std::vector<std::vector<uint32_t>> inliers;
+  uint32_t rounds_done = 0;
+  unsigned long long h_extended = 0;
+  DevBuf<uint32_t> d_clist, d_cnt, d_unposed;  // compacted lists [n_obs], their lengths [n_views], the unposed views
+  DevBuf<uint8_t> d_view_new, d_select;        // [n_views] registered this round, [n_lm] to be triangulated
+  DevBuf<unsigned long long> d_extended;
+};
+struct SfmRegView {
+  int device;
+  bool masks;  // the keep masks exist
+  sfmloc_sfm *handle;
+  SfmTriView tri;
+  uint32_t n_poses;
+  const uint32_t *d_obs_lm, *d_vlist, *d_view_off;
+  uint8_t *d_pose_valid;
+  double *d_pose_R, *d_pose_C;
+  const uint32_t *h_view_id, *h_view_intr, *h_view_pose;
+  const double *h_intr;
+  uint8_t *h_pose_valid;
+  double *h_pose_R, *h_pose_C;
+  SfmRegState *state;
+};
+void sfm_reg_view(sfmloc_sfm *h, SfmRegView *out);
+// adjust.hip: the handle's K5 contexts, at least n of them (the first leads a gang session)
+int sfm_reg_contexts(sfmloc_sfm *h, uint32_t n, sfmloc_context ***ctx);
 
 }  // namespace sfmloc

@@ -2,7 +2,7 @@
 //
 //   openMVG_main_ComputeStructureFromKnownPoses -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>]
 //                                               -o <out sfm_data.json> [-r <residual px = 4.0>] [-a <min angle deg = 2.0>]
-//                                               [-b] [--blind] [--device=0]
+//                                               [-b] [--blind] [--register] [--device=0]
 //
 // The same program as sfmlocalization_amd/structure.py, the same lines on stdout and the same bytes: the structure of a
 // map rebuilt from its poses and the pairwise matches (the last stage of openMVG_main_GlobalSfM).  The input's own
@@ -10,7 +10,8 @@
 // a pose are masked out of the tracks (sfmloc_tracks_build); then, on one resident sfmloc_sfm: sfmloc_sfm_triangulate,
 // sfmloc_sfm_clean(r, a, 0) and, with -b, the structure adjustment followed by a second cleanup.  The output is the input
 // document with `structure` replaced (the kept landmarks, keys 0, 1, 2, ... in track order, every kept observation with
-// its id_feat and the .feat pixel) and control_points [].
+// its id_feat and the .feat pixel) and control_points [].  --register: the tracks over all views, sfmloc_sfm_register (one
+// round per call, at most 16) and a cleanup after the first cleanup, and `extrinsics` written from the handle.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +46,9 @@ void usage() {
           "[-b|--bundle_adjustment] (switch) perform a bundle adjustment on the scene (structure only)\n"
           "[-r|--residual_threshold] maximal pixels reprojection error that will be considered for triangulations (4.0)\n"
           "[-a|--min_angle] minimal triangulation angle in degrees (2.0)\n"
-          "[--blind] (switch) triangulate every track from all its views, no robust rounds\n",
+          "[--blind] (switch) triangulate every track from all its views, no robust rounds\n"
+          "[--register] (switch) resect the views without a pose against the structure and extend it (the tracks are\n"
+          "             built over all views: a wrong match of an unposed view can drop a track the masked build keeps)\n",
           kName);
 }
 
@@ -59,7 +62,7 @@ std::string g(double v) {
 
 int main(int argc, char **argv) {
   std::string in, match_dir, out_path, match_file = "matches.f.txt", r_txt = "4.0", a_txt = "2.0";
-  bool adjust = false, blind = false;
+  bool adjust = false, blind = false, reg = false;
   int device = 0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -80,6 +83,8 @@ int main(int argc, char **argv) {
       adjust = true;
     } else if (a == "--blind") {
       blind = true;
+    } else if (a == "--register") {
+      reg = true;
     } else if (a.rfind("--device=", 0) == 0) {
       device = atoi(a.c_str() + 9);
     } else {
@@ -135,7 +140,7 @@ int main(int argc, char **argv) {
     sfmloc_tracks_destroy(trk);
     return 1;
   };
-  if (sfmloc_tracks_build(device, view_off.data(), n_views, view_use.data(), pl.pairs.data(), (uint32_t)(pl.pairs.size() / 2),
+  if (sfmloc_tracks_build(device, view_off.data(), n_views, reg ? nullptr : view_use.data(), pl.pairs.data(), (uint32_t)(pl.pairs.size() / 2),
                           pl.offsets.data(), pl.mi.data(), pl.mj.data(), 2, &trk))
     return fail();
   uint64_t tc[4];
@@ -188,6 +193,35 @@ int main(int argc, char **argv) {
     return true;
   };
   if (!clean()) return fail();
+  if (reg) {
+    unsigned long long total[5] = {0, 0, 0, 0, 0};
+    sfmloc_register_options ro;
+    sfmloc_register_default_options(&ro);
+    const uint32_t max_rounds = ro.max_rounds;
+    ro.max_rounds = 1;  // (one round per call: the handle numbers them on)
+    ro.residual_px = residual_px;
+    for (uint32_t i = 0; i < max_rounds; ++i) {
+      sfmloc_register_report rr;
+      if (sfmloc_sfm_register(h, &ro, &rr)) return fail();
+      if (rr.rounds == 0) break;
+      printf("Registration round %llu: %u views tried, %u registered, %llu observations extended, %llu of %llu landmarks "
+             "added\n",
+             total[0], rr.views_tried, rr.views_registered, (unsigned long long)rr.obs_extended,
+             (unsigned long long)rr.landmarks_added, (unsigned long long)rr.landmarks_tried);
+      fflush(stdout);
+      total[0] += 1;
+      total[1] += rr.views_tried;
+      total[2] += rr.views_registered;
+      total[3] += rr.obs_extended;
+      total[4] += rr.landmarks_added;
+      if (rr.views_registered == 0) break;
+    }
+    printf("Registration: %llu rounds, %llu views registered in %llu tries, %llu observations extended, %llu landmarks "
+           "added\n",
+           total[0], total[2], total[1], total[3], total[4]);
+    fflush(stdout);
+    if (!clean()) return fail();
+  }
   if (adjust) {
     sfmloc_ba_report ba;
     if (sfmloc_sfm_adjust(h, SFMLOC_BA_STRUCTURE, &ba)) return fail();
@@ -198,7 +232,10 @@ int main(int argc, char **argv) {
   }
   std::vector<uint8_t> obs_keep(n_obs ? n_obs : 1), lm_keep(n_lm ? n_lm : 1);
   std::vector<double> X(3 * (n_lm ? n_lm : 1));
-  if (sfmloc_sfm_read(h, nullptr, nullptr, nullptr, obs_keep.data(), lm_keep.data()) ||
+  const size_t n_poses = d.pose_id.size();
+  std::vector<uint8_t> pose_valid(n_poses ? n_poses : 1);
+  std::vector<double> pose_R(9 * (n_poses ? n_poses : 1)), pose_C(3 * (n_poses ? n_poses : 1));
+  if (sfmloc_sfm_read(h, pose_valid.data(), pose_R.data(), pose_C.data(), obs_keep.data(), lm_keep.data()) ||
       sfmloc_sfm_read_structure(h, X.data()))
     return fail();
   sfmloc_sfm_destroy(h);
@@ -240,6 +277,30 @@ int main(int argc, char **argv) {
   // the key keeps the place it has in the input, as Python's dict does)
   Value outd = d.root;
   set_key(&outd, "structure", st);
+  if (reg) {  // every valid pose of the handle, ascending pose id
+    Value ext = Value::make_arr();
+    for (size_t p = 0; p < n_poses; ++p) {
+      if (!pose_valid[p]) continue;
+      Value rot = Value::make_arr();
+      for (int i = 0; i < 3; ++i) {
+        Value row = Value::make_arr();
+        for (int j = 0; j < 3; ++j) row.a.push_back(Value::make_float(pose_R[9 * p + 3 * i + j]));
+        rot.a.push_back(row);
+      }
+      Value cen = Value::make_arr();
+      for (int j = 0; j < 3; ++j) cen.a.push_back(Value::make_float(pose_C[3 * p + j]));
+      Value v;
+      v.kind = Value::Obj;
+      v.o.emplace_back("rotation", rot);
+      v.o.emplace_back("center", cen);
+      Value e;
+      e.kind = Value::Obj;
+      e.o.emplace_back("key", make_int(d.pose_id[p]));
+      e.o.emplace_back("value", v);
+      ext.a.push_back(e);
+    }
+    set_key(&outd, "extrinsics", ext);
+  }
   set_key(&outd, "control_points", Value::make_arr());
   std::string out;
   sfmjson::dump(outd, &out);

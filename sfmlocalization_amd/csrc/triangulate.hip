@@ -12,6 +12,8 @@
 //               the winner's inliers (the same bits in each, the lanes would idle otherwise) and lane 0 writes.
 //               Tracks are short (2 to 10 observations mostly): one workgroup per track would leave the chip idle and
 //               one lane per track would run its 2 n solves back to back; DESIGN.md has the reasoning and the timings.
+//               With a select mask (sfmloc_sfm_register's new landmarks) only the landmarks it names are worked on and
+//               written; sfmloc_sfm_triangulate passes none.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -40,6 +42,7 @@ struct TriArgs {
   const double *obs_x, *ud, *P;
   double *lm_X;
   uint8_t *obs_keep, *lm_stage;
+  const uint8_t *select;         // null: every landmark; else only those with select[l] != 0, the others untouched
   unsigned long long *counters;  // kept, too few posed, no hypothesis, too few inliers, observations kept, rounds
 };
 
@@ -280,7 +283,7 @@ __global__ __launch_bounds__(kTriBlock) void k_tri_landmarks(TriArgs A) {
   __syncthreads();
   const uint32_t l = (blockIdx.x * (uint32_t)kTriBlock + threadIdx.x) / kTriLanes;
   const int g = threadIdx.x % kTriLanes;
-  if (l < A.n_lm) {
+  if (l < A.n_lm && (!A.select || A.select[l])) {  // (the kTriLanes lanes of a landmark agree)
     double X[3];
     uint32_t rounds;
     const int status = tri_landmark(A, l, g, X, &rounds);
@@ -350,6 +353,7 @@ int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, 
   A.lm_X = v.d_lm_X;
   A.obs_keep = v.d_obs_keep;
   A.lm_stage = v.d_lm_stage;
+  A.select = v.d_select;
   A.counters = d_cnt;
   if (v.n_lm) {
     const uint64_t lanes = (uint64_t)v.n_lm * kTriLanes;

@@ -2,7 +2,7 @@
 the step PyReconstruct/src/reconstructGraph.py:171 runs and whose <outDir>/sfm_data.json it waits for.
 
     python -m sfmlocalization_amd.globalsfm -i <sfm_data.json> -m <matchDir> -o <outDir> [--triplet-angle 5] [--device 0]
-                                            [--pair-scales] [--refine]
+                                            [--pair-scales] [--refine] [--register]
 
 Three stages, each the run() of its own tool, the files of one the input of the next:
     sfmlocalization_amd.relpose       matches.f.txt -> <outDir>/matches.e.txt, <outDir>/relative_poses.json
@@ -13,6 +13,8 @@ Three stages, each the run() of its own tool, the files of one the input of the 
 --pair-scales: relpose also writes <outDir>/pair_scales.json (its -s) and globalposes reads it (its -s), so that the
 spacing of cameras along a line comes from the depths of shared features; without it the chain is what it was.
 --refine: relpose adjusts every ok pair's pose on its inliers (its --refine) before the averaging sees it.
+--register: structure grows the map to the views the averaging left without a pose (its --register): they are resected
+against the triangulated structure and the structure is extended, before the joint adjustment.
 The first stage that fails ends the run with its message and its exit code.  Python only: there is no C++ program for
 the chain (the stages' own C++ programs can be run one after the other).
 """
@@ -30,10 +32,12 @@ USAGE = (f"Usage: {NAME}\n"
          "[--triplet-angle] largest angle of a triplet's cycle rotation in degrees (5)\n"
          "[--device] HIP device (0)\n"
          "[--pair-scales] fix the pair baselines from shared features (relpose -s, globalposes -s)\n"
-         "[--refine] adjust every relative pose on its inliers before the averaging (relpose --refine)\n")
+         "[--refine] adjust every relative pose on its inliers before the averaging (relpose --refine)\n"
+         "[--register] resect the views left without a pose against the structure and extend it (structure --register)\n")
 
 
-def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pair_scales=False, refine=False):
+def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pair_scales=False, refine=False,
+        register=False):
     """The tool's body.  Returns 0, or the exit code of the stage that failed after its message on stderr."""
     os.makedirs(out_dir, exist_ok=True)
     essential = os.path.join(os.path.abspath(out_dir), "matches.e.txt")
@@ -51,7 +55,7 @@ def run(in_path, match_dir, out_dir, triplet_angle=5.0, device=0, log=print, pai
     if rc:
         return rc
     return structure.run(posed, match_dir, os.path.join(out_dir, "sfm_data.json"), match_file=essential, residual_px=4.0,
-                         angle_deg=2.0, device=device, log=log, joint=True)
+                         angle_deg=2.0, device=device, log=log, joint=True, **({"register": True} if register else {}))
 
 
 def parse_args(argv):
@@ -59,11 +63,12 @@ def parse_args(argv):
     opt = {"-i": "", "-m": "", "-o": "", "--triplet-angle": "5", "--device": "0"}
     long_names = {"--input_file": "-i", "--matchdir": "-m", "--outdir": "-o"}
     i = 0
-    flag = refine = False
+    flag = refine = register = False
     while i < len(argv):
         a = argv[i]
-        if a in ("--pair-scales", "--refine"):
+        if a in ("--pair-scales", "--refine", "--register"):
             flag, refine = flag or a == "--pair-scales", refine or a == "--refine"
+            register = register or a == "--register"
             i += 1
             continue
         if "=" in a and a.split("=", 1)[0] in ("--triplet-angle", "--device"):
@@ -83,6 +88,8 @@ def parse_args(argv):
             kw["pair_scales"] = True
         if refine:
             kw["refine"] = True
+        if register:
+            kw["register"] = True
     except ValueError:
         return None
     if not kw["in_path"] or not kw["match_dir"] or not kw["out_dir"] or not 0.0 < kw["triplet_angle"] < 180.0:

@@ -4,7 +4,7 @@ tool here can stand in for: feature tracks from matches.f.txt, every track trian
 
     python -m sfmlocalization_amd.structure -i <sfm_data.json> -m <matchDir> [-f <match file = matches.f.txt>]
                                             -o <out sfm_data.json> [-r <residual px = 4.0>] [-a <min angle deg = 2.0>]
-                                            [-b] [--blind] [--device=0]
+                                            [-b] [--blind] [--register] [--device=0]
 
 The views, intrinsics and extrinsics come from the input; its own structure is ignored.  <matchDir>/<stem>.feat of every
 view gives the view's features and their pixels, the match file (relative to <matchDir> unless absolute) the pairs.
@@ -14,6 +14,13 @@ followed by a second cleanup.  The output is the input document with `structure`
 keys 0, 1, 2, ... in track order, every kept observation with its id_feat and the .feat pixel -- and control_points [],
 written with json.dump.  bin/openMVG_main_ComputeStructureFromKnownPoses (csrc/structure_cli.cpp) is the same program
 and writes the same bytes.  The semantics are stated in include/sfmloc.h.
+
+--register grows the map to the views without a pose (sfmloc_sfm_register): the tracks are built over ALL views, and after
+the triangulation and its cleanup every view without a pose is resected against the kept structure, the structure takes in
+its observations and the landmarks it makes triangulable, round after round (at most 16), and the structure is cleaned
+again; -b and its cleanup follow.  The output's `extrinsics` are then written from the handle: every valid pose, the new
+ones included.  A difference to the masked build: with the unposed views in the tracks, the conflict rule sees their
+features too, so a wrong match of an unposed view can drop a component that the masked build would have kept.
 """
 import json
 import os
@@ -25,6 +32,7 @@ from . import fileio
 from .adjust import sfm_arrays
 
 NAME = "openMVG_main_ComputeStructureFromKnownPoses"
+REGISTER_ROUNDS = 16          # sfmloc_register_options.max_rounds' default
 USAGE = (f"Usage: {NAME}\n"
          "[-i|--input_file] path to a SfM_Data scene\n"
          "[-m|--match_dir] path to the features and descriptors that corresponds to the provided SfM_Data scene\n"
@@ -34,7 +42,9 @@ USAGE = (f"Usage: {NAME}\n"
          "[-b|--bundle_adjustment] (switch) perform a bundle adjustment on the scene (structure only)\n"
          "[-r|--residual_threshold] maximal pixels reprojection error that will be considered for triangulations (4.0)\n"
          "[-a|--min_angle] minimal triangulation angle in degrees (2.0)\n"
-         "[--blind] (switch) triangulate every track from all its views, no robust rounds\n")
+         "[--blind] (switch) triangulate every track from all its views, no robust rounds\n"
+         "[--register] (switch) resect the views without a pose against the structure and extend it (the tracks are\n"
+         "             built over all views: a wrong match of an unposed view can drop a track the masked build keeps)\n")
 
 
 def view_files(doc):
@@ -72,10 +82,11 @@ def structure_entries(view_id, off, view, feat, obs_x, X, landmark_keep, obs_kee
 
 
 def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.0, angle_deg=2.0, adjust=False,
-        blind=False, device=0, log=print, joint=False):
+        blind=False, device=0, log=print, joint=False, register=False):
     """The tool's body.  Returns 0, or 1 after an error message on stderr.  joint (no command-line switch: what
     sfmlocalization_amd.globalsfm asks for): after the cleanup, rotations, translations and structure adjusted as one
-    problem on the same resident handle (sfmloc_sfm_adjust_joint), cleaned again, and the poses written from it."""
+    problem on the same resident handle (sfmloc_sfm_adjust_joint), cleaned again, and the poses written from it.
+    register: the --register switch."""
     from . import capi as S
     try:
         with open(in_path) as fh:
@@ -103,7 +114,8 @@ def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.
     log(f"#views: {len(stems)}, with a pose: {int(view_use.sum())}; #pairs: {len(pairs)}, #matches: {len(mi)}")
     h = None
     try:
-        t = S.Tracks(view_off, pairs, offsets, mi, mj, view_use=view_use, min_length=2, device=int(device))
+        t = S.Tracks(view_off, pairs, offsets, mi, mj, view_use=None if register else view_use, min_length=2,
+                     device=int(device))
         log(f"Tracks: {t.counts[0]} components, {t.counts[1]} dropped for conflict, {t.counts[2]} dropped for length, "
             f"{t.counts[3]} kept")
         a = track_arrays(arrays, feats, t.off, t.view, t.feat)
@@ -120,6 +132,21 @@ def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.
             log(f"Number of points angle error : {counts[2]}")
             log(f"Number of points after cleanup : {counts[3]}")
         clean()
+        if register:
+            total = [0, 0, 0, 0, 0]
+            for _ in range(REGISTER_ROUNDS):        # (one round per call: the handle numbers them on)
+                rr = h.register(max_rounds=1, residual_px=float(residual_px))
+                if rr.rounds == 0:
+                    break
+                log(f"Registration round {total[0]}: {rr.views_tried} views tried, {rr.views_registered} registered, "
+                    f"{rr.obs_extended} observations extended, {rr.landmarks_added} of {rr.landmarks_tried} landmarks added")
+                total = [total[0] + 1, total[1] + rr.views_tried, total[2] + rr.views_registered,
+                         total[3] + rr.obs_extended, total[4] + rr.landmarks_added]
+                if rr.views_registered == 0:
+                    break
+            log(f"Registration: {total[0]} rounds, {total[2]} views registered in {total[1]} tries, {total[3]} "
+                f"observations extended, {total[4]} landmarks added")
+            clean()
         if adjust:
             ba = h.adjust(S.BA_STRUCTURE)
             log(f"Bundle adjustment over structure: {ba.n_blocks} landmarks, cost {ba.cost_initial:g} -> {ba.cost_final:g}")
@@ -140,7 +167,7 @@ def run(in_path, match_dir, out_path, match_file="matches.f.txt", residual_px=4.
     out = dict(doc)
     out["structure"] = structure_entries(arrays["view_id"], t.off, t.view, t.feat, a["obs_x"], X, q["landmark_keep"],
                                          q["obs_keep"])
-    if joint:
+    if joint or register:
         out["extrinsics"] = [{"key": p, "value": {"rotation": [[float(x) for x in row] for row in q["pose_R"][i]],
                                                   "center": [float(x) for x in q["pose_C"][i]]}}
                              for i, p in enumerate(pose_id) if q["pose_valid"][i]]
@@ -156,7 +183,7 @@ def main(argv=None):
     opt = {"-i": "", "-m": "", "-o": "", "-f": "matches.f.txt", "-r": "4.0", "-a": "2.0"}
     long_names = {"--input_file": "-i", "--match_dir": "-m", "--output_file": "-o", "--match_file": "-f",
                   "--residual_threshold": "-r", "--min_angle": "-a"}
-    adjust, blind, device = False, False, 0
+    adjust, blind, device, register = False, False, 0, False
     i = 0
     while i < len(argv):
         a = long_names.get(argv[i], argv[i])
@@ -170,6 +197,8 @@ def main(argv=None):
             adjust = True
         elif a == "--blind":
             blind = True
+        elif a == "--register":
+            register = True
         elif a.startswith("--device="):
             device = int(a.split("=", 1)[1])
         else:
@@ -188,7 +217,7 @@ def main(argv=None):
     def log(s):
         print(s, flush=True)
     return run(opt["-i"], opt["-m"], opt["-o"], match_file=opt["-f"], residual_px=residual_px, angle_deg=angle_deg,
-               adjust=adjust, blind=blind, device=device, log=log)
+               adjust=adjust, blind=blind, device=device, log=log, **({"register": True} if register else {}))
 
 
 if __name__ == "__main__":
