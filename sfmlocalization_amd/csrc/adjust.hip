@@ -7,20 +7,18 @@
 //               per-block digit histogram, one exclusive scan over (digit, block) and a scatter whose rank inside the
 //               block comes from wave ballots -- no atomic decides a position, so two runs give the same lists
 //               (radix_sort.h, shared with tracks.hip).
-//   resection   the lists go straight into the 2D-3D buffers of K5's contexts (k_adj_fill stands where
-//               k_match_set_finish stands on the query path) and K5 runs unchanged: init, rounds, finish; 32 views per
-//               gang session, the view's id_view as the sampling stream and its own intrinsic.
+//   resection   the lists go straight into the 2D-3D buffers of K5's contexts and K5 runs unchanged: init, rounds,
+//               finish (sfm_data.h's sfm_resect_gang, shared with register.hip); every view that has more than 10
+//               observations is tried, and whatever K5 answers is recorded.
 //   cleanup     f64, unfused (the library's -ffp-contract=off): residual per observation, the clamped cosine of every
 //               pair of a landmark's remaining observations (minimum kept), and the -r fixed point as one workgroup's
 //               loop over pose counts (integer atomics: a count does not depend on order).  A later cleanup works on
 //               what the earlier ones kept.
-//   adjustment  the separable commands of -c (sfmloc_sfm_adjust): this file checks the poses and hands the resident
-//               arrays to ba_separable.hip, whose kernels move X or the poses in place.  The joint commands
-//               (sfmloc_sfm_adjust_joint) go to ba_joint.hip the same way; that path moves the intrinsics too.
-//   structure   sfmloc_sfm_triangulate: the same hand-over to triangulate.hip, which rebuilds X and the keep masks from
-//               the poses; from then on the handle behaves as after a cleanup.
-//   growth      sfmloc_sfm_register lives in register.hip: sfm_reg_view hands it the resident arrays, the host's pose
-//               tables (both sides are written) and the K5 contexts; what it keeps between rounds is Sfm::reg.
+//   readers     sfmloc_sfm_read*, and what the other stages share of the handle (sfm_data.h): sfm_dev, the pose check,
+//               the gang resection's contexts.
+// The stages that work on the handle live beside their kernels and reach it through sfm_data.h: sfmloc_sfm_adjust in
+// ba_separable.hip, sfmloc_sfm_adjust_joint in ba_joint.hip, sfmloc_sfm_triangulate in triangulate.hip,
+// sfmloc_sfm_register in register.hip, sfmloc_sfm_color_plan in colorize.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,59 +29,12 @@
 #include <string>
 #include <vector>
 
-#include "geom_device.h"
 #include "radix_sort.h"
+#include "sfm_data.h"
 #include "sfm_json.h"
-#include "sfmloc_internal.h"
 
 namespace sfmloc {
 namespace {
-
-constexpr uint32_t kAdjGang = 32;           // contexts per gang session (kGangMembers)
-constexpr uint32_t kAdjMaxViewObs = 65536;  // a view's list must fit a context's 2D-3D buffers (make_ctx: 65 536)
-
-struct Sfm {
-  int device = 0;
-  sfmloc_params params{};
-  hipStream_t s = nullptr;
-  uint32_t n_views = 0, n_intr = 0, n_poses = 0, n_lm = 0;
-  uint64_t n_obs = 0;
-  // host copies of what the host-side rules need (the pose check of the cleanup, the per-view launches)
-  std::vector<uint32_t> h_view_id, h_view_intr, h_view_pose, h_intr_type;
-  std::vector<double> h_intr;
-  std::vector<uint8_t> h_pose_valid;
-  std::vector<double> h_pose_R, h_pose_C;
-  std::vector<uint64_t> h_obs_off;
-  std::vector<uint32_t> h_obs_view;
-  std::vector<uint32_t> h_view_off;  // per-view list offsets (read back after the device transpose)
-  std::vector<sfmloc_sfm_view_result> res;
-  std::vector<std::vector<uint32_t>> inliers;
-  bool resected = false, cleaned = false;
-  // device
-  DevBuf<uint32_t> d_view_id, d_view_intr, d_view_pose, d_intr_type;
-  DevBuf<double> d_intr;
-  DevBuf<uint8_t> d_pose_valid;
-  DevBuf<double> d_pose_R, d_pose_C;
-  DevBuf<uint32_t> d_lm_id;
-  DevBuf<double> d_lm_X;
-  DevBuf<uint64_t> d_obs_off;
-  DevBuf<uint32_t> d_obs_view, d_obs_lm;
-  DevBuf<double> d_obs_x;
-  DevBuf<uint32_t> d_vlist, d_vkey, d_view_off, d_hist;
-  DevBuf<uint32_t> d_tmp_k, d_tmp_v;
-  DevBuf<double> d_res, d_ray, d_mincos;
-  DevBuf<uint8_t> d_obs_keep, d_lm_stage;
-  DevBuf<uint32_t> d_pose_cnt, d_passes;
-  // the separable adjustment (ba_separable.hip): t = -R C per pose, every pose's views (CSR by pose, ascending view
-  // index), a block's costs and outcome; host copies of the keep masks for the pose check of a call after a cleanup
-  DevBuf<double> d_pose_t, d_blk_cost;
-  DevBuf<uint32_t> d_pose_view_off, d_pose_views, d_blk_info;
-  std::vector<uint8_t> h_obs_keep, h_lm_stage;
-  // K5's contexts hang off a map without descriptors: its log10 table, parameters and launch heuristics
-  sfmloc_map *map = nullptr;
-  std::vector<sfmloc_context *> ctx;
-  SfmRegState reg;  // sfmloc_sfm_register (register.hip)
-};
 
 // (the stream is drained before the handle's buffers go with it, and destroyed after them)
 void sfm_free(Sfm *h) {
@@ -123,34 +74,6 @@ __global__ __launch_bounds__(256) void k_adj_view_off(const uint32_t *__restrict
   view_off[v] = lo;
 }
 
-// ---- resection: a view's list into a context's 2D-3D buffers (sfmloc.h "raw pixels": obs.x as it is) -------------
-struct AdjFillBody {
-  static constexpr int kGangThreads = 256;
-  static __device__ __forceinline__ void run(const uint32_t *vlist, const uint32_t *view_off, uint32_t v,
-                                             const uint32_t *obs_lm, const double *obs_x, const double *lm_X,
-                                             const uint32_t *lm_id, uint32_t *ms_n, uint32_t *ms_qfeat,
-                                             uint32_t *ms_landmark, double *pt2d, double *pt3d) {
-    const uint32_t b = view_off[v], n = view_off[v + 1] - b;
-    for (uint32_t k = threadIdx.x; k < n; k += 256) {
-      const uint32_t o = vlist[b + k], l = obs_lm[o];
-      pt2d[2 * k] = obs_x[2 * (size_t)o];
-      pt2d[2 * k + 1] = obs_x[2 * (size_t)o + 1];
-      pt3d[3 * k] = lm_X[3 * (size_t)l];
-      pt3d[3 * k + 1] = lm_X[3 * (size_t)l + 1];
-      pt3d[3 * k + 2] = lm_X[3 * (size_t)l + 2];
-      ms_qfeat[k] = k;  // the inlier pairs then name positions in the view's list
-      ms_landmark[k] = lm_id[l];
-    }
-    if (threadIdx.x == 0) *ms_n = n;
-  }
-};
-__global__ __launch_bounds__(256) void k_adj_fill(const uint32_t *vlist, const uint32_t *view_off, uint32_t v,
-                                                  const uint32_t *obs_lm, const double *obs_x, const double *lm_X,
-                                                  const uint32_t *lm_id, uint32_t *ms_n, uint32_t *ms_qfeat,
-                                                  uint32_t *ms_landmark, double *pt2d, double *pt3d) {
-  AdjFillBody::run(vlist, view_off, v, obs_lm, obs_x, lm_X, lm_id, ms_n, ms_qfeat, ms_landmark, pt2d, pt3d);
-}
-
 // ---- cleanup --------------------------------------------------------------------------------------------------------
 
 // per observation: the residual norm (sfmloc.h "residual") and the world ray with its norm (sfmloc.h "angle")
@@ -173,19 +96,9 @@ __global__ __launch_bounds__(256) void k_adj_residual(uint64_t n_obs, const uint
   const double f = K[0], ppx = K[1], ppy = K[2];
   const double x = obs_x[2 * o], y = obs_x[2 * o + 1];
   // obs.x - cam2ima(add_disto(hnormalized(R (X - C))))
-  const double d0 = lm_X[3 * (size_t)l] - C[0], d1 = lm_X[3 * (size_t)l + 1] - C[1], d2 = lm_X[3 * (size_t)l + 2] - C[2];
-  const double X0 = (R[0] * d0 + R[1] * d1) + R[2] * d2;
-  const double X1 = (R[3] * d0 + R[4] * d1) + R[5] * d2;
-  const double X2 = (R[6] * d0 + R[7] * d1) + R[8] * d2;
-  double p0 = X0 / X2, p1 = X1 / X2;
-  if (radial) {
-    const double r2 = p0 * p0 + p1 * p1;
-    const double r4 = r2 * r2, r6 = r4 * r2;
-    const double rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
-    p0 = p0 * rc;
-    p1 = p1 * rc;
-  }
-  const double ex = x - (f * p0 + ppx), ey = y - (f * p1 + ppy);
+  double depth, px, py;
+  geom::project_pixel(R, C, K, radial, lm_X + 3 * (size_t)l, &depth, &px, &py);
+  const double ex = x - px, ey = y - py;
   const double nrm = sqrt(ex * ex + ey * ey);
   res[o] = nrm;
   const uint8_t was = again ? keep[o] : 1;  // (a later cleanup: what an earlier one removed stays removed)
@@ -445,18 +358,8 @@ int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *
   return SFMLOC_OK;
 }
 
-int sfm_ensure_contexts(Sfm *h, uint32_t n) {
-  while (h->ctx.size() < n) {  // the first has a stream of its own, the others work on it (gang members)
-    sfmloc_context *c = nullptr;
-    const int rc = sfmloc_context_create_merge(h->map, h->ctx.empty() ? nullptr : h->ctx[0], &c);
-    if (rc) return rc;
-    h->ctx.push_back(c);
-  }
-  return SFMLOC_OK;
-}
-
 int sfm_resect_impl(Sfm *h, uint32_t *n_ran, uint32_t *n_ok) {
-  std::vector<uint32_t> todo;
+  std::vector<uint32_t> todo, todo_n;
   for (uint32_t k = 0; k < h->n_views; ++k) {
     const uint32_t n = h->h_view_off[k + 1] - h->h_view_off[k];
     sfmloc_sfm_view_result &r = h->res[k];
@@ -464,96 +367,38 @@ int sfm_resect_impl(Sfm *h, uint32_t *n_ran, uint32_t *n_ok) {
     r.n_obs = (int32_t)n;
     h->inliers[k].clear();
     if (n > 10) {  // MINIMUM_VIEW_NUM_TO_ESTIMATAE_CAMERA_POSE, test ">" (adjust_sfm_data.cpp:118)
-      SFM_CHECK(n <= kAdjMaxViewObs, SFMLOC_ECAP, "view %u has %u observations (at most %u per view)", h->h_view_id[k],
-                n, kAdjMaxViewObs);
+      SFM_CHECK(n <= kSfmMaxViewObs, SFMLOC_ECAP, "view %u has %u observations (at most %u per view)", h->h_view_id[k],
+                n, kSfmMaxViewObs);
       todo.push_back(k);
+      todo_n.push_back(n);
     }
   }
-  int rc = sfm_ensure_contexts(h, std::min<uint32_t>(kAdjGang, (uint32_t)todo.size()));
-  if (rc) return rc;
   uint32_t ran = 0, ok = 0;
-  for (size_t g0 = 0; g0 < todo.size(); g0 += kAdjGang) {
-    const uint32_t m = (uint32_t)std::min<size_t>(kAdjGang, todo.size() - g0);
-    for (uint32_t i = 0; i < m; ++i) {  // (a regrowth synchronises: before the session records anything)
-      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
-      const uint32_t k = todo[g0 + i];
-      rc = ctx_p3p_reserve(c, h->h_view_off[k + 1] - h->h_view_off[k]);
-      if (rc) return rc;
-      const double *K = &h->h_intr[6 * (size_t)h->h_view_intr[k]];
-      c->p3p_stream = h->h_view_id[k];  // the view's own sampling stream: independent of the batch
-      c->p3p_own_K = true;
-      c->p3p_K[0] = K[0];
-      c->p3p_K[1] = K[1];
-      c->p3p_K[2] = K[2];
-    }
-    rc = sfmloc_gang_begin(h->ctx.data(), m);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < m && rc == SFMLOC_OK; ++i) {
-      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
-      sfm_launch<AdjFillBody>(c, k_adj_fill, dim3(1), dim3(256), 0, (const uint32_t *)h->d_vlist,
-                              (const uint32_t *)h->d_view_off, todo[g0 + i], (const uint32_t *)h->d_obs_lm,
-                              (const double *)h->d_obs_x, (const double *)h->d_lm_X, (const uint32_t *)h->d_lm_id,
-                              c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark, c->d_pt2d, c->d_pt3d);
-      c->p3p_init_fused = false;  // K5's init reads the count k_adj_fill wrote
-      rc = ctx_resection_begin(c);
-    }
-    const int rc_end = sfmloc_gang_end(h->ctx.data(), m);
-    if (rc) return rc;
-    if (rc_end) return rc_end;
-    std::vector<uint32_t> failed;  // members whose view failed with a non-empty inlier set
-    for (uint32_t i = 0; i < m; ++i) {
-      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
-      const uint32_t k = todo[g0 + i];
-      rc = ctx_resection_wait_done(c);
-      if (rc) return rc;
-      const HostResult *hr = reinterpret_cast<const HostResult *>(c->h_result);
-      const Pose &p = hr->pose;
-      SFM_CHECK((p.status & 4) == 0, SFMLOC_ECAP, "view %u: more correspondences than the P3P workspace holds",
-                h->h_view_id[k]);
-      sfmloc_sfm_view_result &r = h->res[k];
-      r.ran = 1;
-      r.ok = p.ok;
-      r.n_inliers = p.n_inliers;
-      r.iterations = p.iterations;
-      r.error_max = p.error_max;
-      r.nfa = p.nfa;
-      memcpy(r.P, p.P, sizeof r.P);
-      memcpy(r.R, p.R, sizeof r.R);
-      memcpy(r.center, p.center, sizeof r.center);
-      ++ran;
-      const uint32_t ni = p.n_inliers > 0 ? (uint32_t)p.n_inliers : 0u;
-      std::vector<uint32_t> &inl = h->inliers[k];
-      inl.resize(ni);
-      if (!p.ok) {
-        // sfmloc.h "failure": the view keeps its input pose (or stays without one).  K5 publishes no pair list for a
-        // failed query; its inlier set is the best model's list, read after the gang's last wait (below)
-        if (ni) failed.push_back(i);
-        continue;
-      }
+  // the transpose's lists as they are (no count array, raw pixels)
+  const int rc = sfm_resect_gang<false>(*h, todo, todo_n, h->d_vlist, nullptr,
+                                        [&](uint32_t k, const Pose &p) -> std::vector<uint32_t> & {
+    sfmloc_sfm_view_result &r = h->res[k];
+    r.ran = 1;
+    r.ok = p.ok;
+    r.n_inliers = p.n_inliers;
+    r.iterations = p.iterations;
+    r.error_max = p.error_max;
+    r.nfa = p.nfa;
+    memcpy(r.P, p.P, sizeof r.P);
+    memcpy(r.R, p.R, sizeof r.R);
+    memcpy(r.center, p.center, sizeof r.center);
+    ++ran;
+    if (p.ok) {  // (sfmloc.h "failure": a failed view keeps its input pose, or stays without one)
       ++ok;
-      if (c->p3p_cap > (uint32_t)kP3pMaxN)  // (a regrown workspace keeps its pair lists outside the result record)
-        SFM_HIP(hipMemcpy(inl.data(), c->d_pair_qfeat, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      else
-        memcpy(inl.data(), hr->pair_qfeat, ni * sizeof(uint32_t));
       // Pose3(R, -R^T t) (adjust_sfm_data.cpp:138-142); a pose id without an entry gets one
       const uint32_t pi = h->h_view_pose[k];
       h->h_pose_valid[pi] = 1;
       memcpy(&h->h_pose_R[9 * (size_t)pi], p.R, 9 * sizeof(double));
       memcpy(&h->h_pose_C[3 * (size_t)pi], p.center, 3 * sizeof(double));
     }
-    // (best_inl holds the final model's inliers in AC-RANSAC order, the list k_p3p_finish turns into pairs on success;
-    // the list positions are the view's correspondence indices.  One wait for the gang's failed views together.)
-    for (uint32_t i : failed) {
-      Ctx *c = reinterpret_cast<Ctx *>(h->ctx[i]);
-      std::vector<uint32_t> &inl = h->inliers[todo[g0 + i]];
-      SFM_HIP(hipMemcpyAsync(inl.data(), c->d_best_inl, inl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s));
-    }
-    if (!failed.empty()) {
-      // (h->s is not the contexts' stream: order it after their work, which the waits above have seen finish)
-      SFM_HIP(hipStreamSynchronize(h->s));
-    }
-  }
-  for (sfmloc_context *cc : h->ctx) reinterpret_cast<Ctx *>(cc)->p3p_own_K = false;
+    return h->inliers[k];
+  });
+  if (rc) return rc;
   SFM_HIP(hipMemcpyAsync(h->d_pose_valid, h->h_pose_valid.data(), h->n_poses, hipMemcpyHostToDevice, h->s));
   SFM_HIP(hipMemcpyAsync(h->d_pose_R, h->h_pose_R.data(), 9 * (size_t)h->n_poses * sizeof(double),
                          hipMemcpyHostToDevice, h->s));
@@ -577,24 +422,8 @@ int sfm_fetch_masks(Sfm *h) {
   return SFMLOC_OK;
 }
 
-// GetPoseOrDie: the first observation (landmark order) still in the structure whose view has no pose
-int sfm_check_poses(Sfm *h, const char *what) {
-  const int rc = sfm_fetch_masks(h);
-  if (rc) return rc;
-  for (uint32_t l = 0; l < h->n_lm; ++l) {
-    if (h->cleaned && h->h_lm_stage[l] != 3) continue;
-    for (uint64_t o = h->h_obs_off[l]; o < h->h_obs_off[l + 1]; ++o) {
-      if (h->cleaned && !h->h_obs_keep[o]) continue;
-      const uint32_t v = h->h_obs_view[o];
-      SFM_CHECK(h->h_pose_valid[h->h_view_pose[v]], SFMLOC_EINVAL,
-                "view %u has observations but no pose (GetPoseOrDie): the structure cannot be %s", h->h_view_id[v], what);
-    }
-  }
-  return SFMLOC_OK;
-}
-
 int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable, uint64_t *counts) {
-  const int rc_pose = sfm_check_poses(h, "cleaned");
+  const int rc_pose = sfm_check_poses(*h, "cleaned");
   if (rc_pose) return rc_pose;
   const int again = h->cleaned ? 1 : 0;  // a later cleanup works on what the earlier ones kept
   hipStream_t s = h->s;
@@ -630,145 +459,77 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
   return SFMLOC_OK;
 }
 
-void sfm_ba_view(Sfm *h, SfmBaView *out) {
-  SfmBaView v;
-  v.s = h->s;
-  v.n_views = h->n_views;
-  v.n_poses = h->n_poses;
-  v.n_lm = h->n_lm;
-  v.d_view_intr = h->d_view_intr;
-  v.d_view_pose = h->d_view_pose;
-  v.d_intr_type = h->d_intr_type;
-  v.d_intr = h->d_intr;
-  v.d_pose_R = h->d_pose_R;
-  v.d_pose_C = h->d_pose_C;
-  v.d_pose_t = h->d_pose_t;
-  v.d_lm_X = h->d_lm_X;
-  v.d_obs_off = h->d_obs_off;
-  v.d_obs_view = h->d_obs_view;
-  v.d_obs_lm = h->d_obs_lm;
-  v.d_vlist = h->d_vlist;
-  v.d_view_off = h->d_view_off;
-  v.d_obs_x = h->d_obs_x;
-  v.d_obs_keep = h->cleaned ? h->d_obs_keep : nullptr;
-  v.d_lm_stage = h->cleaned ? h->d_lm_stage : nullptr;
-  v.d_pose_view_off = h->d_pose_view_off;
-  v.d_pose_views = h->d_pose_views;
-  v.d_blk_cost = h->d_blk_cost;
-  v.d_blk_info = h->d_blk_info;
-  *out = v;
+}  // namespace
+
+SfmDev sfm_dev(const Sfm &h, bool make_masks) {
+  const bool masks = h.cleaned || make_masks;
+  SfmDev d;
+  d.n_views = h.n_views;
+  d.n_intr = h.n_intr;
+  d.n_poses = h.n_poses;
+  d.n_lm = h.n_lm;
+  d.n_obs = h.n_obs;
+  d.view_id = h.d_view_id;
+  d.view_intr = h.d_view_intr;
+  d.view_pose = h.d_view_pose;
+  d.intr_type = h.d_intr_type;
+  d.intr = h.d_intr;
+  d.pose_valid = h.d_pose_valid;
+  d.pose_R = h.d_pose_R;
+  d.pose_C = h.d_pose_C;
+  d.pose_t = h.d_pose_t;
+  d.lm_id = h.d_lm_id;
+  d.lm_X = h.d_lm_X;
+  d.obs_off = h.d_obs_off;
+  d.obs_view = h.d_obs_view;
+  d.obs_lm = h.d_obs_lm;
+  d.vlist = h.d_vlist;
+  d.view_off = h.d_view_off;
+  d.obs_x = h.d_obs_x;
+  d.obs_keep = masks ? h.d_obs_keep.get() : nullptr;  // (before the first cleanup: every observation enters)
+  d.lm_stage = masks ? h.d_lm_stage.get() : nullptr;
+  d.pose_view_off = h.d_pose_view_off;
+  d.pose_views = h.d_pose_views;
+  d.blk_cost = h.d_blk_cost;
+  d.blk_info = h.d_blk_info;
+  return d;
+}
+
+int sfm_ensure_contexts(Sfm &h, uint32_t n) {
+  while (h.ctx.size() < n) {  // the first has a stream of its own, the others work on it (gang members)
+    sfmloc_context *c = nullptr;
+    const int rc = sfmloc_context_create_merge(h.map, h.ctx.empty() ? nullptr : h.ctx[0], &c);
+    if (rc) return rc;
+    h.ctx.push_back(c);
+  }
+  return SFMLOC_OK;
+}
+
+// GetPoseOrDie: the first observation (landmark order) still in the structure whose view has no pose
+int sfm_check_poses(Sfm &h, const char *what) {
+  const int rc = sfm_fetch_masks(&h);
+  if (rc) return rc;
+  for (uint32_t l = 0; l < h.n_lm; ++l) {
+    if (h.cleaned && h.h_lm_stage[l] != 3) continue;
+    for (uint64_t o = h.h_obs_off[l]; o < h.h_obs_off[l + 1]; ++o) {
+      if (h.cleaned && !h.h_obs_keep[o]) continue;
+      const uint32_t v = h.h_obs_view[o];
+      SFM_CHECK(h.h_pose_valid[h.h_view_pose[v]], SFMLOC_EINVAL,
+                "view %u has observations but no pose (GetPoseOrDie): the structure cannot be %s", h.h_view_id[v],
+                what);
+    }
+  }
+  return SFMLOC_OK;
 }
 
 // the host's copy of the pose table follows the device's (sfmloc_sfm_read reads it)
-int sfm_fetch_poses(Sfm *h) {
-  SFM_HIP(hipMemcpyAsync(h->h_pose_R.data(), h->d_pose_R, 9 * (size_t)h->n_poses * sizeof(double),
-                         hipMemcpyDeviceToHost, h->s));
-  SFM_HIP(hipMemcpyAsync(h->h_pose_C.data(), h->d_pose_C, 3 * (size_t)h->n_poses * sizeof(double),
-                         hipMemcpyDeviceToHost, h->s));
-  SFM_HIP(hipStreamSynchronize(h->s));
+int sfm_fetch_poses(Sfm &h) {
+  SFM_HIP(hipMemcpyAsync(h.h_pose_R.data(), h.d_pose_R, 9 * (size_t)h.n_poses * sizeof(double), hipMemcpyDeviceToHost,
+                         h.s));
+  SFM_HIP(hipMemcpyAsync(h.h_pose_C.data(), h.d_pose_C, 3 * (size_t)h.n_poses * sizeof(double), hipMemcpyDeviceToHost,
+                         h.s));
+  SFM_HIP(hipStreamSynchronize(h.s));
   return SFMLOC_OK;
-}
-
-int sfm_adjust_impl(Sfm *h, uint32_t what, sfmloc_ba_report *rep) {
-  const int rc = sfm_check_poses(h, "adjusted");
-  if (rc) return rc;
-  SfmBaView v;
-  sfm_ba_view(h, &v);
-  const int rc_run = ba_separable_run(v, what, rep);
-  if (rc_run) return rc_run;
-  if (what != SFMLOC_BA_STRUCTURE) return sfm_fetch_poses(h);
-  return SFMLOC_OK;
-}
-
-int sfm_adjust_joint_impl(Sfm *h, uint32_t what, const sfmloc_ba_joint_options &opt, sfmloc_ba_joint_report *rep) {
-  const int rc = sfm_check_poses(h, "adjusted");  // (fetches the keep masks of the last cleanup)
-  if (rc) return rc;
-  SfmBaView v;
-  sfm_ba_view(h, &v);
-  SfmJointHost hs;
-  hs.n_intr = h->n_intr;
-  hs.n_obs = h->n_obs;
-  hs.d_intr = h->d_intr;
-  hs.view_intr = h->h_view_intr.data();
-  hs.view_pose = h->h_view_pose.data();
-  hs.obs_view = h->h_obs_view.data();
-  hs.obs_off = h->h_obs_off.data();
-  hs.obs_keep = h->cleaned ? h->h_obs_keep.data() : nullptr;
-  hs.lm_stage = h->cleaned ? h->h_lm_stage.data() : nullptr;
-  const int rc_run = ba_joint_run(v, hs, what, opt, rep);
-  if (rc_run) return rc_run;
-  if (what & SFMLOC_BA_INTRINSICS) {
-    SFM_HIP(hipMemcpyAsync(h->h_intr.data(), h->d_intr, 6 * (size_t)h->n_intr * sizeof(double), hipMemcpyDeviceToHost,
-                           h->s));
-  }
-  return sfm_fetch_poses(h);
-}
-
-void sfm_tri_view(Sfm *h, SfmTriView *out) {
-  SfmTriView v;
-  v.s = h->s;
-  v.seed = h->params.seed;
-  v.n_views = h->n_views;
-  v.n_lm = h->n_lm;
-  v.n_obs = h->n_obs;
-  v.d_view_intr = h->d_view_intr;
-  v.d_view_pose = h->d_view_pose;
-  v.d_intr_type = h->d_intr_type;
-  v.d_intr = h->d_intr;
-  v.d_pose_valid = h->d_pose_valid;
-  v.d_pose_R = h->d_pose_R;
-  v.d_pose_C = h->d_pose_C;
-  v.d_lm_id = h->d_lm_id;
-  v.d_lm_X = h->d_lm_X;
-  v.d_obs_off = h->d_obs_off;
-  v.d_obs_view = h->d_obs_view;
-  v.d_obs_x = h->d_obs_x;
-  v.d_ud = h->d_ray;  // (the cleanup's ray scratch, 4 doubles per observation: it is rewritten by every cleanup)
-  v.d_obs_keep = h->d_obs_keep;
-  v.d_lm_stage = h->d_lm_stage;
-  *out = v;
-}
-
-}  // namespace
-
-void sfm_reg_view(sfmloc_sfm *hh, SfmRegView *out) {
-  Sfm *h = reinterpret_cast<Sfm *>(hh);
-  SfmRegView v;
-  v.device = h->device;
-  v.masks = h->cleaned;
-  v.handle = hh;
-  sfm_tri_view(h, &v.tri);
-  v.n_poses = h->n_poses;
-  v.d_obs_lm = h->d_obs_lm;
-  v.d_vlist = h->d_vlist;
-  v.d_view_off = h->d_view_off;
-  v.d_pose_valid = h->d_pose_valid;
-  v.d_pose_R = h->d_pose_R;
-  v.d_pose_C = h->d_pose_C;
-  v.h_view_id = h->h_view_id.data();
-  v.h_view_intr = h->h_view_intr.data();
-  v.h_view_pose = h->h_view_pose.data();
-  v.h_intr = h->h_intr.data();
-  v.h_pose_valid = h->h_pose_valid.data();
-  v.h_pose_R = h->h_pose_R.data();
-  v.h_pose_C = h->h_pose_C.data();
-  v.state = &h->reg;
-  *out = v;
-}
-
-int sfm_reg_contexts(sfmloc_sfm *hh, uint32_t n, sfmloc_context ***ctx) {
-  Sfm *h = reinterpret_cast<Sfm *>(hh);
-  const int rc = sfm_ensure_contexts(h, n);
-  *ctx = h->ctx.data();
-  return rc;
-}
-
-void sfm_color_view(const sfmloc_sfm *hh, SfmColorView *out) {
-  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
-  uint32_t longest = 0;
-  for (uint32_t v = 0; v < h->n_views; ++v) longest = std::max(longest, h->h_view_off[v + 1] - h->h_view_off[v]);
-  *out = SfmColorView{h->device,    h->s,          h->n_views,  h->n_lm,     longest,
-                      h->d_obs_off, h->d_obs_view, h->d_obs_lm, h->d_vlist, h->d_view_off};
 }
 
 }  // namespace sfmloc
@@ -843,85 +604,6 @@ int sfmloc_sfm_clean(sfmloc_sfm *hh, double residual_px, double angle_deg, int r
   Sfm *h = reinterpret_cast<Sfm *>(hh);
   SFM_HIP(hipSetDevice(h->device));
   return sfm_clean_impl(h, residual_px, angle_deg, rm_unstable, counts);
-}
-
-int sfmloc_sfm_adjust(sfmloc_sfm *hh, uint32_t what, sfmloc_ba_report *rep) {
-  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust: null handle");
-  SFM_CHECK(what == 0 || what == SFMLOC_BA_ROTATION || what == SFMLOC_BA_TRANSLATION ||
-                what == (SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION) || what == SFMLOC_BA_STRUCTURE,
-            SFMLOC_EINVAL,
-            "sfmloc_sfm_adjust: what = %u: only the separable commands (-c) are supported: structure alone, or "
-            "rotations / translations alone; nothing with intrinsics, no structure together with a pose part", what);
-  Sfm *h = reinterpret_cast<Sfm *>(hh);
-  if (rep) memset(rep, 0, sizeof *rep);
-  if (what == 0) return SFMLOC_OK;
-  SFM_HIP(hipSetDevice(h->device));
-  try {
-    return sfm_adjust_impl(h, what, rep);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_sfm_adjust: out of host memory");
-    return SFMLOC_ENOMEM;
-  }
-}
-
-void sfmloc_ba_joint_default_options(sfmloc_ba_joint_options *o) {
-  if (!o) return;
-  o->max_steps = 50;            // Ceres max_num_iterations
-  o->max_pcg = 500;             // Ceres max_linear_solver_iterations
-  o->function_tolerance = 1e-6;
-  o->pcg_tolerance = 0.1;       // Ceres eta
-}
-
-int sfmloc_sfm_adjust_joint(sfmloc_sfm *hh, uint32_t what, const sfmloc_ba_joint_options *opt,
-                            sfmloc_ba_joint_report *rep) {
-  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust_joint: null handle");
-  const uint32_t all = SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION | SFMLOC_BA_INTRINSICS | SFMLOC_BA_STRUCTURE;
-  SFM_CHECK(what != 0 && (what & ~all) == 0, SFMLOC_EINVAL,
-            "sfmloc_sfm_adjust_joint: what = %u: a non-zero combination of the four SFMLOC_BA_ bits (-c's r, t, i, s)",
-            what);
-  sfmloc_ba_joint_options o;
-  if (opt) o = *opt;
-  else sfmloc_ba_joint_default_options(&o);
-  SFM_CHECK(o.max_steps > 0 && o.function_tolerance >= 0.0 && o.pcg_tolerance >= 0.0, SFMLOC_EINVAL,
-            "sfmloc_sfm_adjust_joint: max_steps must be positive and the tolerances not negative");
-  Sfm *h = reinterpret_cast<Sfm *>(hh);
-  if (rep) memset(rep, 0, sizeof *rep);
-  SFM_HIP(hipSetDevice(h->device));
-  try {
-    return sfm_adjust_joint_impl(h, what, o, rep);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_sfm_adjust_joint: out of host memory");
-    return SFMLOC_ENOMEM;
-  }
-}
-
-void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o) {
-  if (!o) return;
-  memset(o, 0, sizeof *o);
-  o->mode = SFMLOC_TRI_ROBUST;
-  o->min_inliers = 3;
-  o->allow_pairs = 1;
-  o->residual_px = 4.0;
-}
-
-int sfmloc_sfm_triangulate(sfmloc_sfm *hh, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep) {
-  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_triangulate: null handle");
-  sfmloc_triangulate_options o;
-  if (opt) o = *opt;
-  else sfmloc_triangulate_default_options(&o);
-  SFM_CHECK(o.mode == SFMLOC_TRI_ROBUST || o.mode == SFMLOC_TRI_BLIND, SFMLOC_EINVAL,
-            "sfmloc_sfm_triangulate: mode = %u (0 robust, 1 blind)", o.mode);
-  SFM_CHECK(o.min_inliers >= 2 && o.residual_px >= 0.0, SFMLOC_EINVAL,
-            "sfmloc_sfm_triangulate: min_inliers must be at least 2 and residual_px not negative");
-  Sfm *h = reinterpret_cast<Sfm *>(hh);
-  if (rep) memset(rep, 0, sizeof *rep);
-  SFM_HIP(hipSetDevice(h->device));
-  SfmTriView v;
-  sfm_tri_view(h, &v);
-  const int rc = triangulate_run(v, o, rep);
-  if (rc) return rc;
-  h->cleaned = true;  // the masks exist: a cleanup or an adjustment that follows works on what was kept
-  return SFMLOC_OK;
 }
 
 int sfmloc_sfm_read_intrinsics(sfmloc_sfm *hh, double *K) {

@@ -1,5 +1,6 @@
-// Device code the bundle adjustment kernels share (ba_separable.hip, ba_joint.hip): one observation's weighted residual
-// and derivatives, the in-wave butterfly, the damped Cholesky solve, the rotation step and the Levenberg-Marquardt state.
+// Device code the bundle adjustment kernels share (ba_separable.hip, ba_joint.hip; relrefine.hip takes the solve and the
+// lambda rules): one observation's weighted residual and derivatives, the in-wave butterfly, the damped Cholesky solve,
+// the rotation step and the Levenberg-Marquardt state.
 // f64, unfused (the library's -ffp-contract=off); every expression is parenthesised explicitly, so both files round alike.
 #pragma once
 
@@ -16,50 +17,13 @@ constexpr double kBaFtol = 1e-14;  // sfmloc.h "stopping"
 constexpr double kHuberA = 16.0;   // HuberLoss(Square(4.0))
 
 // one observation at camera coordinates Xc: the weighted residual r (2), the weighted d r / d Xc (2 x 3, rows J0 J1)
-// and rho / 2 (sfmloc.h "residual", "loss"; first-order reweighting: both times sqrt(rho'))
+// and rho / 2 (sfmloc.h "residual", "loss"; first-order reweighting: both times sqrt(rho')).  kIntr (the joint
+// adjustment): also the weighted d r / d intrinsic (2 x 6, rows I0 I1 over f, ppx, ppy, k1, k2, k3; the k columns are 0
+// for a pinhole); without it I0, I1 are not touched
+template <bool kIntr>
 __device__ __forceinline__ double ba_observation(const double *__restrict__ K, bool radial, const double Xc[3],
-                                                  double ox, double oy, double r[2], double J0[3], double J1[3]) {
-  const double f = K[0];
-  const double iz = 1.0 / Xc[2];
-  const double p0 = Xc[0] / Xc[2], p1 = Xc[1] / Xc[2];
-  double rc = 1.0, drc = 0.0;
-  if (radial) {
-    const double r2 = p0 * p0 + p1 * p1;
-    const double r4 = r2 * r2, r6 = r4 * r2;
-    rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
-    drc = (K[3] + 2.0 * K[4] * r2) + 3.0 * K[5] * r4;
-  }
-  r[0] = (f * (p0 * rc) + K[1]) - ox;
-  r[1] = (f * (p1 * rc) + K[2]) - oy;
-  // d q / d p of q = p rc(|p|^2), then d p / d Xc = [[iz, 0, -p0 iz], [0, iz, -p1 iz]]
-  const double q00 = rc + 2.0 * drc * p0 * p0, q01 = 2.0 * drc * p0 * p1, q11 = rc + 2.0 * drc * p1 * p1;
-  J0[0] = f * q00 * iz;
-  J0[1] = f * q01 * iz;
-  J0[2] = -f * (q00 * p0 + q01 * p1) * iz;
-  J1[0] = f * q01 * iz;
-  J1[1] = f * q11 * iz;
-  J1[2] = -f * (q01 * p0 + q11 * p1) * iz;
-  const double s = r[0] * r[0] + r[1] * r[1];
-  if (s > kHuberA * kHuberA) {
-    const double sq = sqrt(s);
-    const double w = sqrt(kHuberA / sq);
-    r[0] *= w;
-    r[1] *= w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      J0[k] *= w;
-      J1[k] *= w;
-    }
-    return 0.5 * (2.0 * kHuberA * sq - kHuberA * kHuberA);
-  }
-  return 0.5 * s;
-}
-
-// ba_observation's sibling for the joint adjustment: the same r, J0, J1 and rho / 2 from the same p, r2, rc, and the
-// weighted d r / d intrinsic (2 x 6, rows I0 I1 over f, ppx, ppy, k1, k2, k3; the k columns are 0 for a pinhole)
-__device__ __forceinline__ double ba_observation_intr(const double *__restrict__ K, bool radial, const double Xc[3],
-                                                       double ox, double oy, double r[2], double J0[3], double J1[3],
-                                                       double I0[6], double I1[6]) {
+                                                  double ox, double oy, double r[2], double J0[3], double J1[3],
+                                                  double *I0 = nullptr, double *I1 = nullptr) {
   const double f = K[0];
   const double iz = 1.0 / Xc[2];
   const double p0 = Xc[0] / Xc[2], p1 = Xc[1] / Xc[2];
@@ -73,6 +37,7 @@ __device__ __forceinline__ double ba_observation_intr(const double *__restrict__
   }
   r[0] = (f * (p0 * rc) + K[1]) - ox;
   r[1] = (f * (p1 * rc) + K[2]) - oy;
+  // d q / d p of q = p rc(|p|^2), then d p / d Xc = [[iz, 0, -p0 iz], [0, iz, -p1 iz]]
   const double q00 = rc + 2.0 * drc * p0 * p0, q01 = 2.0 * drc * p0 * p1, q11 = rc + 2.0 * drc * p1 * p1;
   J0[0] = f * q00 * iz;
   J0[1] = f * q01 * iz;
@@ -80,19 +45,20 @@ __device__ __forceinline__ double ba_observation_intr(const double *__restrict__
   J1[0] = f * q01 * iz;
   J1[1] = f * q11 * iz;
   J1[2] = -f * (q01 * p0 + q11 * p1) * iz;
-  // d r / d f = p rc, d r / d pp = I, d r / d k_j = f p r2^j
-  I0[0] = p0 * rc;
-  I0[1] = 1.0;
-  I0[2] = 0.0;
-  I0[3] = f * (p0 * r2);
-  I0[4] = f * (p0 * r4);
-  I0[5] = f * (p0 * r6);
-  I1[0] = p1 * rc;
-  I1[1] = 0.0;
-  I1[2] = 1.0;
-  I1[3] = f * (p1 * r2);
-  I1[4] = f * (p1 * r4);
-  I1[5] = f * (p1 * r6);
+  if constexpr (kIntr) {  // d r / d f = p rc, d r / d pp = I, d r / d k_j = f p r2^j
+    I0[0] = p0 * rc;
+    I0[1] = 1.0;
+    I0[2] = 0.0;
+    I0[3] = f * (p0 * r2);
+    I0[4] = f * (p0 * r4);
+    I0[5] = f * (p0 * r6);
+    I1[0] = p1 * rc;
+    I1[1] = 0.0;
+    I1[2] = 1.0;
+    I1[3] = f * (p1 * r2);
+    I1[4] = f * (p1 * r4);
+    I1[5] = f * (p1 * r6);
+  }
   const double s = r[0] * r[0] + r[1] * r[1];
   if (s > kHuberA * kHuberA) {
     const double sq = sqrt(s);
@@ -104,10 +70,12 @@ __device__ __forceinline__ double ba_observation_intr(const double *__restrict__
       J0[k] *= w;
       J1[k] *= w;
     }
+    if constexpr (kIntr) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      I0[k] *= w;
-      I1[k] *= w;
+      for (int k = 0; k < 6; ++k) {
+        I0[k] *= w;
+        I1[k] *= w;
+      }
     }
     return 0.5 * (2.0 * kHuberA * sq - kHuberA * kHuberA);
   }

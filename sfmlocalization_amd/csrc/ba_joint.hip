@@ -38,11 +38,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <new>
 #include <vector>
 
 #include "ba_device.h"
 #include "devmem.h"
-#include "sfmloc_internal.h"
+#include "sfm_data.h"
 
 namespace sfmloc {
 namespace {
@@ -57,16 +58,12 @@ struct JtState {
   uint32_t running, stop, take, zero_grad;
 };
 
-struct JtDev {
-  uint32_t n_views, n_poses, n_intr, n_lm, n_par, nb_obs, what;
-  uint64_t n_obs;
-  const uint32_t *view_intr, *view_pose, *intr_type;
-  const uint64_t *obs_off;
-  const uint32_t *obs_view, *obs_lm, *vlist, *view_off;
-  const double *obs_x;
-  const uint32_t *pose_view_off, *pose_views, *intr_view_off, *intr_views;
+// the resident arrays (SfmDev: R, C, t, K and X are its pose_R, pose_C, pose_t, intr and lm_X) and this call's workspace
+struct JtDev : SfmDev {
+  uint32_t n_par, nb_obs, what;
+  const uint32_t *intr_view_off, *intr_views;
   const uint8_t *ent, *pose_in, *intr_in, *lm_in;  // an observation enters; a block is free and has one that enters
-  double *R, *C, *t, *K, *X, *Rn, *tn, *Kn, *Xn;
+  double *Rn, *tn, *Kn, *Xn;
   double *lin, *lm_Ci, *lm_Cg, *lm_z, *view_part, *blk, *Minv, *D, *x, *r, *z, *p, *q, *pq_part, *red;
   JtState *st;
 };
@@ -124,16 +121,6 @@ __device__ __forceinline__ void jt_inv_spd(const double (&A)[N][N], double (&Ai)
 
 __device__ __forceinline__ double jt_clamp_d(double a) { return fmin(fmax(a, 1e-6), 1e32); }
 
-// t = -R C of every pose (sfmloc.h "blocks")
-__global__ __launch_bounds__(256) void k_jt_pose_t(uint32_t n_poses, const double *__restrict__ R,
-                                                   const double *__restrict__ C, double *__restrict__ t) {
-  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n_poses) return;
-  const double *r = R + 9 * (size_t)p, *c = C + 3 * (size_t)p;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[3 * (size_t)p + i] = -((r[3 * i] * c[0] + r[3 * i + 1] * c[1]) + r[3 * i + 2] * c[2]);
-}
-
 // ---- linearise -------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_jt_lin(JtDev v) {
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(256) void k_jt_lin(JtDev v) {
   if (o < v.n_obs && v.ent[o]) {
     const uint32_t vw = v.obs_view[o], l = v.obs_lm[o];
     const uint32_t pi = v.view_pose[vw], ii = v.view_intr[vw];
-    const double *R = v.R + 9 * (size_t)pi, *t = v.t + 3 * (size_t)pi, *X = v.X + 3 * (size_t)l;
+    const double *R = v.pose_R + 9 * (size_t)pi, *t = v.pose_t + 3 * (size_t)pi, *X = v.lm_X + 3 * (size_t)l;
     double Y[3], Xc[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(256) void k_jt_lin(JtDev v) {
       Xc[i] = Y[i] + t[i];
     }
     double r[2], J0[3], J1[3], I0[6], I1[6];
-    cost = ba_observation_intr(v.K + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
+    cost = ba_observation<true>(v.intr + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
                                J1, I0, I1);
     double *L = v.lin + kLin * o;
     L[0] = r[0];
@@ -570,7 +557,7 @@ __global__ __launch_bounds__(1024) void k_jt_pcg_update(JtDev v, uint32_t n_acti
 __global__ __launch_bounds__(256) void k_jt_trial(JtDev v) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < v.n_poses) {
-    const double *R = v.R + 9 * (size_t)i, *t = v.t + 3 * (size_t)i, *x = v.x + 6 * (size_t)i;
+    const double *R = v.pose_R + 9 * (size_t)i, *t = v.pose_t + 3 * (size_t)i, *x = v.x + 6 * (size_t)i;
     double *Rn = v.Rn + 9 * (size_t)i, *tn = v.tn + 3 * (size_t)i;
     if (v.pose_in[i] && (v.what & SFMLOC_BA_ROTATION)) {
       const double w[3] = {x[0], x[1], x[2]};
@@ -589,14 +576,14 @@ __global__ __launch_bounds__(256) void k_jt_trial(JtDev v) {
     for (int k = 0; k < 3; ++k) tn[k] = trn ? t[k] + x[3 + k] : t[k];
   }
   if (i < v.n_intr) {
-    const double *K = v.K + 6 * (size_t)i, *x = v.x + 6 * (size_t)(v.n_poses + i);
+    const double *K = v.intr + 6 * (size_t)i, *x = v.x + 6 * (size_t)(v.n_poses + i);
     double *Kn = v.Kn + 6 * (size_t)i;
     const int nf = (v.intr_in[i] && (v.what & SFMLOC_BA_INTRINSICS)) ? (v.intr_type[i] == 3 ? 6 : 3) : 0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) Kn[k] = k < nf ? K[k] + x[k] : K[k];
   }
   if (i < v.n_lm) {
-    const double *X = v.X + 3 * (size_t)i;
+    const double *X = v.lm_X + 3 * (size_t)i;
     double *Xn = v.Xn + 3 * (size_t)i;
     if (v.lm_in[i]) {
       double *z = v.lm_z + 3 * (size_t)i;
@@ -627,7 +614,7 @@ __global__ __launch_bounds__(256) void k_jt_eval(JtDev v) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) Xc[i] = ((R[3 * i] * X[0] + R[3 * i + 1] * X[1]) + R[3 * i + 2] * X[2]) + t[i];
     double r[2], J0[3], J1[3], I0[6], I1[6];  // (the function k_jt_lin costs the state with: one rounding for both)
-    cost = ba_observation_intr(v.Kn + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
+    cost = ba_observation<true>(v.Kn + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
                                J1, I0, I1);
     const double *L = v.lin + kLin * o;
     double u[2];
@@ -708,43 +695,46 @@ __global__ __launch_bounds__(256) void k_jt_commit(JtDev v) {
     for (int k = 0; k < 3; ++k) t[k] = v.tn[3 * (size_t)i + k];
     if (v.what & SFMLOC_BA_ROTATION) {
 #pragma unroll
-      for (int k = 0; k < 9; ++k) v.R[9 * (size_t)i + k] = R[k];
+      for (int k = 0; k < 9; ++k) v.pose_R[9 * (size_t)i + k] = R[k];
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      v.t[3 * (size_t)i + k] = t[k];
-      v.C[3 * (size_t)i + k] = -((R[k] * t[0] + R[3 + k] * t[1]) + R[6 + k] * t[2]);
+      v.pose_t[3 * (size_t)i + k] = t[k];
+      v.pose_C[3 * (size_t)i + k] = -((R[k] * t[0] + R[3 + k] * t[1]) + R[6 + k] * t[2]);
     }
   }
   if (i < v.n_intr && v.intr_in[i]) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) v.K[6 * (size_t)i + k] = v.Kn[6 * (size_t)i + k];
+    for (int k = 0; k < 6; ++k) v.intr[6 * (size_t)i + k] = v.Kn[6 * (size_t)i + k];
   }
   if (i < v.n_lm && v.lm_in[i]) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) v.X[3 * (size_t)i + k] = v.Xn[3 * (size_t)i + k];
+    for (int k = 0; k < 3; ++k) v.lm_X[3 * (size_t)i + k] = v.Xn[3 * (size_t)i + k];
   }
 }
 
-}  // namespace
-
-int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, const sfmloc_ba_joint_options &opt,
-                 sfmloc_ba_joint_report *rep) {
+// sfmloc_sfm_adjust_joint's body
+int ba_joint_run(Sfm &s, uint32_t what, const sfmloc_ba_joint_options &opt, sfmloc_ba_joint_report *rep) {
+  const int rc_pose = sfm_check_poses(s, "adjusted");  // (fetches the keep masks of the last cleanup)
+  if (rc_pose) return rc_pose;
+  // the host decides which observations enter: its copies of the index arrays and of the keep masks
+  const uint8_t *obs_keep = s.cleaned ? s.h_obs_keep.data() : nullptr;
+  const uint8_t *lm_stage = s.cleaned ? s.h_lm_stage.data() : nullptr;
   sfmloc_ba_joint_report out{};
   const bool pose = what & (SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION), intr = what & SFMLOC_BA_INTRINSICS;
   const bool stru = what & SFMLOC_BA_STRUCTURE;
   // which observations enter and which blocks they refer to (sfmloc.h "entering"), on the host once per call
-  std::vector<uint8_t> ent(hs.n_obs, 0), pose_in(s.n_poses, 0), intr_in(hs.n_intr, 0), lm_in(s.n_lm, 0);
+  std::vector<uint8_t> ent(s.n_obs, 0), pose_in(s.n_poses, 0), intr_in(s.n_intr, 0), lm_in(s.n_lm, 0);
   uint64_t n_ent = 0;
   for (uint32_t l = 0; l < s.n_lm; ++l) {
-    if (hs.lm_stage && hs.lm_stage[l] != 3) continue;
-    for (uint64_t o = hs.obs_off[l]; o < hs.obs_off[l + 1]; ++o) {
-      if (hs.obs_keep && !hs.obs_keep[o]) continue;
-      const uint32_t vw = hs.obs_view[o];
+    if (lm_stage && lm_stage[l] != 3) continue;
+    for (uint64_t o = s.h_obs_off[l]; o < s.h_obs_off[l + 1]; ++o) {
+      if (obs_keep && !obs_keep[o]) continue;
+      const uint32_t vw = s.h_obs_view[o];
       ent[o] = 1;
       ++n_ent;
-      if (pose) pose_in[hs.view_pose[vw]] = 1;
-      if (intr) intr_in[hs.view_intr[vw]] = 1;
+      if (pose) pose_in[s.h_view_pose[vw]] = 1;
+      if (intr) intr_in[s.h_view_intr[vw]] = 1;
       if (stru) lm_in[l] = 1;
     }
   }
@@ -753,18 +743,18 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
   for (uint8_t b : lm_in) out.n_landmark_blocks += b;
   if (n_ent == 0) {
     if (rep) *rep = out;
-    return SFMLOC_OK;
+    return SFMLOC_OK;  // (nothing moved: the host's copies of the poses and intrinsics hold)
   }
-  std::vector<uint32_t> iv_off((size_t)hs.n_intr + 1, 0), iv(s.n_views);
-  for (uint32_t vw = 0; vw < s.n_views; ++vw) ++iv_off[hs.view_intr[vw] + 1];
-  for (uint32_t i = 0; i < hs.n_intr; ++i) iv_off[i + 1] += iv_off[i];
+  std::vector<uint32_t> iv_off((size_t)s.n_intr + 1, 0), iv(s.n_views);
+  for (uint32_t vw = 0; vw < s.n_views; ++vw) ++iv_off[s.h_view_intr[vw] + 1];
+  for (uint32_t i = 0; i < s.n_intr; ++i) iv_off[i + 1] += iv_off[i];
   {
     std::vector<uint32_t> at(iv_off.begin(), iv_off.end() - 1);
-    for (uint32_t vw = 0; vw < s.n_views; ++vw) iv[at[hs.view_intr[vw]]++] = vw;  // (ascending view index)
+    for (uint32_t vw = 0; vw < s.n_views; ++vw) iv[at[s.h_view_intr[vw]]++] = vw;  // (ascending view index)
   }
 
-  const uint32_t n_par = s.n_poses + hs.n_intr;
-  const uint32_t nb_obs = (uint32_t)((hs.n_obs + 255) / 256);
+  const uint32_t n_par = s.n_poses + s.n_intr;
+  const uint32_t nb_obs = (uint32_t)((s.n_obs + 255) / 256);
   hipStream_t st = s.s;
   // the workspace, before the loop
   DevBuf<uint8_t> d_ent, d_pose_in, d_intr_in, d_lm_in;
@@ -786,9 +776,9 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
   JT_TRY(dev_upload(nullptr, d_iv, iv.data(), iv.size(), st, 1));
   JT_TRY(d_Rn.alloc(nullptr, 9 * (size_t)s.n_poses));
   JT_TRY(d_tn.alloc(nullptr, 3 * (size_t)s.n_poses));
-  JT_TRY(d_Kn.alloc(nullptr, 6 * (size_t)hs.n_intr));
+  JT_TRY(d_Kn.alloc(nullptr, 6 * (size_t)s.n_intr));
   JT_TRY(d_Xn.alloc(nullptr, 3 * (size_t)s.n_lm + 1));
-  JT_TRY(d_lin.alloc(nullptr, kLin * (size_t)hs.n_obs));
+  JT_TRY(d_lin.alloc(nullptr, kLin * (size_t)s.n_obs));
   JT_TRY(d_lm_Ci.alloc(nullptr, 6 * (size_t)s.n_lm + 1));
   JT_TRY(d_lm_Cg.alloc(nullptr, 3 * (size_t)s.n_lm + 1));
   JT_TRY(d_lm_z.alloc(nullptr, 3 * (size_t)s.n_lm + 1));
@@ -823,36 +813,16 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
   SFM_HIP(hipMemsetAsync(d_lm_Cg.get(), 0, (3 * (size_t)s.n_lm + 1) * sizeof(double), st));
 
   JtDev v{};
-  v.n_views = s.n_views;
-  v.n_poses = s.n_poses;
-  v.n_intr = hs.n_intr;
-  v.n_lm = s.n_lm;
+  static_cast<SfmDev &>(v) = sfm_dev(s);
   v.n_par = n_par;
   v.nb_obs = nb_obs;
   v.what = what;
-  v.n_obs = hs.n_obs;
-  v.view_intr = s.d_view_intr;
-  v.view_pose = s.d_view_pose;
-  v.intr_type = s.d_intr_type;
-  v.obs_off = s.d_obs_off;
-  v.obs_view = s.d_obs_view;
-  v.obs_lm = s.d_obs_lm;
-  v.vlist = s.d_vlist;
-  v.view_off = s.d_view_off;
-  v.obs_x = s.d_obs_x;
-  v.pose_view_off = s.d_pose_view_off;
-  v.pose_views = s.d_pose_views;
   v.intr_view_off = d_iv_off;
   v.intr_views = d_iv;
   v.ent = d_ent;
   v.pose_in = d_pose_in;
   v.intr_in = d_intr_in;
   v.lm_in = d_lm_in;
-  v.R = s.d_pose_R;
-  v.C = s.d_pose_C;
-  v.t = s.d_pose_t;
-  v.K = hs.d_intr;
-  v.X = s.d_lm_X;
   v.Rn = d_Rn;
   v.tn = d_tn;
   v.Kn = d_Kn;
@@ -875,11 +845,10 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
   v.st = d_st;
 
   const dim3 b256(256), g_obs(nb_obs), g_lm((s.n_lm + 256 / kBaGroup - 1) / (256 / kBaGroup) + 0);
-  const dim3 g_blocks(((intr ? s.n_poses + s.n_views : s.n_poses) + 3) / 4), g_intr(hs.n_intr);
-  const dim3 g_each((std::max(std::max(s.n_poses, hs.n_intr), s.n_lm) + 255) / 256);
-  hipLaunchKernelGGL(k_jt_pose_t, dim3((s.n_poses + 255) / 256), b256, 0, st, s.n_poses, (const double *)s.d_pose_R,
-                     (const double *)s.d_pose_C, s.d_pose_t);
-  SFM_HIP(hipGetLastError());
+  const dim3 g_blocks(((intr ? s.n_poses + s.n_views : s.n_poses) + 3) / 4), g_intr(s.n_intr);
+  const dim3 g_each((std::max(std::max(s.n_poses, s.n_intr), s.n_lm) + 255) / 256);
+  rc = ba_pose_t(v, st);
+  if (rc) return rc;
   auto read_state = [&]() -> int {
     SFM_HIP(hipMemcpyAsync(&h, d_st.get(), sizeof h, hipMemcpyDeviceToHost, st));
     SFM_HIP(hipStreamSynchronize(st));
@@ -921,7 +890,47 @@ int ba_joint_run(const SfmBaView &s, const SfmJointHost &hs, uint32_t what, cons
   out.pcg_max = h.pcg_max;
   out.stop = h.stop;
   if (rep) *rep = out;
-  return SFMLOC_OK;
+  if (what & SFMLOC_BA_INTRINSICS)
+    SFM_HIP(hipMemcpyAsync(s.h_intr.data(), v.intr, 6 * (size_t)s.n_intr * sizeof(double), hipMemcpyDeviceToHost, st));
+  return sfm_fetch_poses(s);
 }
 
+}  // namespace
 }  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" {
+
+void sfmloc_ba_joint_default_options(sfmloc_ba_joint_options *o) {
+  if (!o) return;
+  o->max_steps = 50;            // Ceres max_num_iterations
+  o->max_pcg = 500;             // Ceres max_linear_solver_iterations
+  o->function_tolerance = 1e-6;
+  o->pcg_tolerance = 0.1;       // Ceres eta
+}
+
+int sfmloc_sfm_adjust_joint(sfmloc_sfm *hh, uint32_t what, const sfmloc_ba_joint_options *opt,
+                            sfmloc_ba_joint_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust_joint: null handle");
+  const uint32_t all = SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION | SFMLOC_BA_INTRINSICS | SFMLOC_BA_STRUCTURE;
+  SFM_CHECK(what != 0 && (what & ~all) == 0, SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust_joint: what = %u: a non-zero combination of the four SFMLOC_BA_ bits (-c's r, t, i, s)",
+            what);
+  sfmloc_ba_joint_options o;
+  if (opt) o = *opt;
+  else sfmloc_ba_joint_default_options(&o);
+  SFM_CHECK(o.max_steps > 0 && o.function_tolerance >= 0.0 && o.pcg_tolerance >= 0.0, SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust_joint: max_steps must be positive and the tolerances not negative");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  SFM_HIP(hipSetDevice(h->device));
+  try {
+    return ba_joint_run(*h, what, o, rep);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_adjust_joint: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+}
+
+}  // extern "C"

@@ -16,32 +16,20 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <new>
 #include <vector>
 
 #include "ba_device.h"
-#include "sfmloc_internal.h"
+#include "sfm_data.h"
 
 namespace sfmloc {
 namespace {
 
 constexpr uint32_t kInfoEntered = 1u << 29, kInfoMoved = 1u << 30, kInfoCap = 1u << 31;
 
-struct BaDev {
-  uint32_t n_views, n_poses, n_lm;
-  const uint32_t *view_intr, *view_pose, *intr_type;
-  const double *intr;
-  double *pose_R, *pose_C, *pose_t, *lm_X;
-  const uint64_t *obs_off;
-  const uint32_t *obs_view, *obs_lm, *vlist, *view_off;
-  const double *obs_x;
-  const uint8_t *obs_keep, *lm_stage;
-  const uint32_t *pose_view_off, *pose_views;
-  double *blk_cost;
-  uint32_t *blk_info;
-};
-
-// t = -R C of every pose (sfmloc.h "blocks")
+// t = -R C of every pose (sfmloc.h "blocks"), before either adjustment (ba_pose_t)
 __global__ __launch_bounds__(256) void k_ba_pose_t(uint32_t n_poses, const double *__restrict__ R,
                                                    const double *__restrict__ C, double *__restrict__ t) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
@@ -54,7 +42,7 @@ __global__ __launch_bounds__(256) void k_ba_pose_t(uint32_t n_poses, const doubl
 // ---- structure -----------------------------------------------------------------------------------------------------
 
 // the group's sums at X over the landmark's entering observations [a, b): A (3 x 3), g (3), cost; *n = how many entered
-__device__ __forceinline__ void ba_structure_eval(const BaDev &v, uint64_t a, uint64_t b, int sub, const double X[3],
+__device__ __forceinline__ void ba_structure_eval(const SfmDev &v, uint64_t a, uint64_t b, int sub, const double X[3],
                                                   double (&A)[3][3], double (&g)[3], double *cost, uint32_t *n) {
   double acc[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   uint32_t cnt = 0;
@@ -67,7 +55,7 @@ __device__ __forceinline__ void ba_structure_eval(const BaDev &v, uint64_t a, ui
 #pragma unroll
     for (int i = 0; i < 3; ++i) Xc[i] = ((R[3 * i] * X[0] + R[3 * i + 1] * X[1]) + R[3 * i + 2] * X[2]) + t[i];
     double r[2], J0[3], J1[3];
-    acc[9] += ba_observation(v.intr + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
+    acc[9] += ba_observation<false>(v.intr + 6 * (size_t)ii, v.intr_type[ii] == 3, Xc, v.obs_x[2 * o], v.obs_x[2 * o + 1], r, J0,
                              J1);
     double j0[3], j1[3];  // d r / d X = (d r / d Xc) R
 #pragma unroll
@@ -104,7 +92,7 @@ __device__ __forceinline__ void ba_structure_eval(const BaDev &v, uint64_t a, ui
   *cost = acc[9];
 }
 
-__global__ __launch_bounds__(256) void k_ba_structure(BaDev v) {
+__global__ __launch_bounds__(256) void k_ba_structure(SfmDev v) {
   const uint32_t l = (blockIdx.x * 256 + threadIdx.x) / kBaGroup;
   const int sub = threadIdx.x & (kBaGroup - 1);
   if (l >= v.n_lm) return;  // (the whole group leaves: its lanes share l)
@@ -169,7 +157,7 @@ __global__ __launch_bounds__(256) void k_ba_structure(BaDev v) {
 // ---- motion ----------------------------------------------------------------------------------------------------------
 
 // the wave's sums at (R, t) over the entering observations of pose p: A (6 x 6 over [rotation, translation]), g, cost
-__device__ __forceinline__ void ba_motion_eval(const BaDev &v, uint32_t p, int lane, const double R[9], const double t[3],
+__device__ __forceinline__ void ba_motion_eval(const SfmDev &v, uint32_t p, int lane, const double R[9], const double t[3],
                                                double (&A)[6][6], double (&g)[6], double *cost, uint32_t *n) {
   double acc[28];
 #pragma unroll
@@ -192,7 +180,7 @@ __device__ __forceinline__ void ba_motion_eval(const BaDev &v, uint32_t p, int l
         Xc[i] = Y[i] + t[i];
       }
       double r[2], J0[3], J1[3];
-      acc[27] += ba_observation(K, radial, Xc, v.obs_x[2 * (size_t)o], v.obs_x[2 * (size_t)o + 1], r, J0, J1);
+      acc[27] += ba_observation<false>(K, radial, Xc, v.obs_x[2 * (size_t)o], v.obs_x[2 * (size_t)o + 1], r, J0, J1);
       // d Xc / d w = -[Y]x for R <- exp([w]x) R, d Xc / d t = I
       const double j0[6] = {J0[2] * Y[1] - J0[1] * Y[2], J0[0] * Y[2] - J0[2] * Y[0], J0[1] * Y[0] - J0[0] * Y[1],
                             J0[0],                       J0[1],                       J0[2]};
@@ -230,7 +218,7 @@ __device__ __forceinline__ void ba_motion_eval(const BaDev &v, uint32_t p, int l
 
 // N free parameters starting at row kOff of [rotation (3), translation (3)]: (3, 0) = r, (3, 3) = t, (6, 0) = rt
 template <int N, int kOff>
-__global__ __launch_bounds__(256) void k_ba_motion(BaDev v) {
+__global__ __launch_bounds__(256) void k_ba_motion(SfmDev v) {
   const uint32_t p = (blockIdx.x * 256 + threadIdx.x) / 64;
   const int lane = threadIdx.x & 63;
   if (p >= v.n_poses) return;  // (the whole wave leaves)
@@ -313,55 +301,32 @@ __global__ __launch_bounds__(256) void k_ba_motion(BaDev v) {
   }
 }
 
-}  // namespace
-
-int ba_separable_run(const SfmBaView &s, uint32_t what, sfmloc_ba_report *rep) {
-  BaDev v;
-  v.n_views = s.n_views;
-  v.n_poses = s.n_poses;
-  v.n_lm = s.n_lm;
-  v.view_intr = s.d_view_intr;
-  v.view_pose = s.d_view_pose;
-  v.intr_type = s.d_intr_type;
-  v.intr = s.d_intr;
-  v.pose_R = s.d_pose_R;
-  v.pose_C = s.d_pose_C;
-  v.pose_t = s.d_pose_t;
-  v.lm_X = s.d_lm_X;
-  v.obs_off = s.d_obs_off;
-  v.obs_view = s.d_obs_view;
-  v.obs_lm = s.d_obs_lm;
-  v.vlist = s.d_vlist;
-  v.view_off = s.d_view_off;
-  v.obs_x = s.d_obs_x;
-  v.obs_keep = s.d_obs_keep;
-  v.lm_stage = s.d_lm_stage;
-  v.pose_view_off = s.d_pose_view_off;
-  v.pose_views = s.d_pose_views;
-  v.blk_cost = s.d_blk_cost;
-  v.blk_info = s.d_blk_info;
+// sfmloc_sfm_adjust's body: the blocks of `what` on the handle's stream, then the report from the blocks' records
+int ba_separable_run(Sfm &h, uint32_t what, sfmloc_ba_report *rep) {
+  const int rc = sfm_check_poses(h, "adjusted");
+  if (rc) return rc;
+  const SfmDev v = sfm_dev(h);
   const bool structure = what == SFMLOC_BA_STRUCTURE;
-  const uint32_t nb = structure ? s.n_lm : s.n_poses;
+  const uint32_t nb = structure ? h.n_lm : h.n_poses;
   sfmloc_ba_report r{};
   if (nb) {
-    hipLaunchKernelGGL(k_ba_pose_t, dim3((s.n_poses + 255) / 256), dim3(256), 0, s.s, s.n_poses,
-                       (const double *)s.d_pose_R, (const double *)s.d_pose_C, s.d_pose_t);
-    SFM_HIP(hipGetLastError());
+    const int rc_t = ba_pose_t(v, h.s);
+    if (rc_t) return rc_t;
     if (structure) {
       const uint32_t per = 256 / kBaGroup;
-      hipLaunchKernelGGL(k_ba_structure, dim3((nb + per - 1) / per), dim3(256), 0, s.s, v);
+      hipLaunchKernelGGL(k_ba_structure, dim3((nb + per - 1) / per), dim3(256), 0, h.s, v);
     } else {
       const dim3 grid((nb + 3) / 4);
-      if (what == SFMLOC_BA_ROTATION) hipLaunchKernelGGL((k_ba_motion<3, 0>), grid, dim3(256), 0, s.s, v);
-      else if (what == SFMLOC_BA_TRANSLATION) hipLaunchKernelGGL((k_ba_motion<3, 3>), grid, dim3(256), 0, s.s, v);
-      else hipLaunchKernelGGL((k_ba_motion<6, 0>), grid, dim3(256), 0, s.s, v);
+      if (what == SFMLOC_BA_ROTATION) hipLaunchKernelGGL((k_ba_motion<3, 0>), grid, dim3(256), 0, h.s, v);
+      else if (what == SFMLOC_BA_TRANSLATION) hipLaunchKernelGGL((k_ba_motion<3, 3>), grid, dim3(256), 0, h.s, v);
+      else hipLaunchKernelGGL((k_ba_motion<6, 0>), grid, dim3(256), 0, h.s, v);
     }
     SFM_HIP(hipGetLastError());
     std::vector<double> cost(2 * (size_t)nb);
     std::vector<uint32_t> info(nb);
-    SFM_HIP(hipMemcpyAsync(cost.data(), s.d_blk_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost, s.s));
-    SFM_HIP(hipMemcpyAsync(info.data(), s.d_blk_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s.s));
-    SFM_HIP(hipStreamSynchronize(s.s));
+    SFM_HIP(hipMemcpyAsync(cost.data(), v.blk_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost, h.s));
+    SFM_HIP(hipMemcpyAsync(info.data(), v.blk_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h.s));
+    SFM_HIP(hipStreamSynchronize(h.s));
     for (uint32_t b = 0; b < nb; ++b) {  // (ascending block index: the totals' order is fixed)
       if (!(info[b] & kInfoEntered)) continue;
       ++r.n_blocks;
@@ -374,7 +339,38 @@ int ba_separable_run(const SfmBaView &s, uint32_t what, sfmloc_ba_report *rep) {
     }
   }
   if (rep) *rep = r;
+  if (!structure) return sfm_fetch_poses(h);
+  return SFMLOC_OK;
+}
+
+}  // namespace
+
+int ba_pose_t(const SfmDev &v, hipStream_t s) {
+  hipLaunchKernelGGL(k_ba_pose_t, dim3((v.n_poses + 255) / 256), dim3(256), 0, s, v.n_poses, (const double *)v.pose_R,
+                     (const double *)v.pose_C, v.pose_t);
+  SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }
 
 }  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" int sfmloc_sfm_adjust(sfmloc_sfm *hh, uint32_t what, sfmloc_ba_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_adjust: null handle");
+  SFM_CHECK(what == 0 || what == SFMLOC_BA_ROTATION || what == SFMLOC_BA_TRANSLATION ||
+                what == (SFMLOC_BA_ROTATION | SFMLOC_BA_TRANSLATION) || what == SFMLOC_BA_STRUCTURE,
+            SFMLOC_EINVAL,
+            "sfmloc_sfm_adjust: what = %u: only the separable commands (-c) are supported: structure alone, or "
+            "rotations / translations alone; nothing with intrinsics, no structure together with a pose part", what);
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  if (what == 0) return SFMLOC_OK;
+  SFM_HIP(hipSetDevice(h->device));
+  try {
+    return ba_separable_run(*h, what, rep);
+  } catch (const std::bad_alloc &) {
+    set_error("sfmloc_sfm_adjust: out of host memory");
+    return SFMLOC_ENOMEM;
+  }
+}

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sfmloc_internal.h"
+#include "sfm_data.h"
 
 namespace sfmloc {
 namespace {
@@ -121,8 +121,11 @@ __global__ __launch_bounds__(kUpdateThreads) void k_color_update(
   if (threadIdx.x == 0 && coloured) atomicSub(&st->remaining, coloured);
 }
 
-int color_plan_impl(const SfmColorView &V, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs) {
+int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs) {
   CallScope d;  // (on the handle's stream; before the buffers: destroyed after them)
+  const SfmDev V = sfm_dev(h);
+  uint32_t max_view_obs = 0;  // the longest per-view list
+  for (uint32_t v = 0; v < h.n_views; ++v) max_view_obs = std::max(max_view_obs, h.h_view_off[v + 1] - h.h_view_off[v]);
   DevBuf<uint32_t> d_card, d_order, d_iter;
   DevBuf<unsigned long long> d_obs;
   DevBuf<ColorState> d_st;
@@ -131,15 +134,15 @@ int color_plan_impl(const SfmColorView &V, uint32_t *order, uint32_t *n_order, u
       (rc = d_iter.alloc(nullptr, V.n_lm ? V.n_lm : 1)) || (rc = d_obs.alloc(nullptr, V.n_lm ? V.n_lm : 1)) ||
       (rc = d_st.alloc(nullptr, 1)))
     return rc;
-  if ((rc = d.open(true, &g_color_last_ms, V.s))) return rc;
+  if ((rc = d.open(true, &g_color_last_ms, h.s))) return rc;
   SFM_HIP(hipMemsetAsync(d_st, 0, sizeof(ColorState), d.s));
   SFM_HIP(hipMemsetAsync(d_order, 0, (size_t)V.n_views * sizeof(uint32_t), d.s));
   if ((rc = d.time_begin())) return rc;
   const uint32_t n_init = V.n_views > V.n_lm ? V.n_views : V.n_lm;
-  hipLaunchKernelGGL(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.d_view_off, d_card, V.n_lm,
-                     V.d_obs_off, d_iter, d_obs, d_st);
+  hipLaunchKernelGGL(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.view_off, d_card, V.n_lm,
+                     V.obs_off, d_iter, d_obs, d_st);
   SFM_HIP(hipGetLastError());
-  uint32_t blocks = (V.max_view_obs + kUpdateThreads - 1) / kUpdateThreads;
+  uint32_t blocks = (max_view_obs + kUpdateThreads - 1) / kUpdateThreads;
   blocks = blocks < 1 ? 1 : (blocks > kUpdateMaxBlocks ? kUpdateMaxBlocks : blocks);
   ColorState st;
   for (;;) {
@@ -148,8 +151,8 @@ int color_plan_impl(const SfmColorView &V, uint32_t *order, uint32_t *n_order, u
     if (st.remaining == 0) break;
     for (uint32_t i = 0; i < SFMLOC_COLOR_CHUNK; ++i) {
       hipLaunchKernelGGL(k_color_argmax, dim3(1), dim3(kArgmaxThreads), 0, d.s, V.n_views, d_card, d_st, d_order);
-      hipLaunchKernelGGL(k_color_update, dim3(blocks), dim3(kUpdateThreads), 0, d.s, V.d_view_off, V.d_vlist, V.d_obs_lm,
-                         V.d_obs_off, V.d_obs_view, d_card, d_iter, d_obs, d_st);
+      hipLaunchKernelGGL(k_color_update, dim3(blocks), dim3(kUpdateThreads), 0, d.s, V.view_off, V.vlist, V.obs_lm,
+                         V.obs_off, V.obs_view, d_card, d_iter, d_obs, d_st);
     }
     SFM_HIP(hipGetLastError());
   }
@@ -173,15 +176,14 @@ extern "C" {
 
 double sfmloc_sfm_color_last_ms(void) { return g_color_last_ms; }
 
-int sfmloc_sfm_color_plan(sfmloc_sfm *h, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs) {
-  SFM_CHECK(h, SFMLOC_EINVAL, "sfmloc_sfm_color_plan: null handle");
-  SfmColorView V;
-  sfm_color_view(h, &V);
-  SFM_CHECK(order && n_order && (V.n_lm == 0 || (lm_iter && lm_obs)), SFMLOC_EINVAL,
+int sfmloc_sfm_color_plan(sfmloc_sfm *hh, uint32_t *order, uint32_t *n_order, uint32_t *lm_iter, uint64_t *lm_obs) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_color_plan: null handle");
+  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
+  SFM_CHECK(order && n_order && (h->n_lm == 0 || (lm_iter && lm_obs)), SFMLOC_EINVAL,
             "sfmloc_sfm_color_plan: null argument");
   g_color_last_ms = 0.0;
-  SFM_HIP(hipSetDevice(V.device));
-  return color_plan_impl(V, order, n_order, lm_iter, lm_obs);
+  SFM_HIP(hipSetDevice(h->device));
+  return color_plan_impl(*h, order, n_order, lm_iter, lm_obs);
 }
 
 }  // extern "C"

@@ -796,6 +796,28 @@ GD void ud_pixel_k3(double f, double ppx, double ppy, double k1, double k2, doub
   *oy = f * (radius * py) + ppy;
 }
 
+// cam2ima(add_disto(hnormalized(R (X - C)))) for K = (f, ppx, ppy, k1, k2, k3), radial = pinhole_radial_k3: the pixel
+// (*px, *py) of X and its camera-frame depth.  The cleanup's residual, the triangulation's inlier test and the growth
+// step's extension compare against this one expression tree, so they round alike.
+GD void project_pixel(const double *R, const double *C, const double *K, bool radial, const double *X, double *depth,
+                      double *px, double *py) {
+  const double d0 = X[0] - C[0], d1 = X[1] - C[1], d2 = X[2] - C[2];
+  const double X0 = (R[0] * d0 + R[1] * d1) + R[2] * d2;
+  const double X1 = (R[3] * d0 + R[4] * d1) + R[5] * d2;
+  const double X2 = (R[6] * d0 + R[7] * d1) + R[8] * d2;
+  double p0 = X0 / X2, p1 = X1 / X2;
+  if (radial) {
+    const double r2 = p0 * p0 + p1 * p1;
+    const double r4 = r2 * r2, r6 = r4 * r2;
+    const double rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
+    p0 = p0 * rc;
+    p1 = p1 * rc;
+  }
+  *depth = X2;
+  *px = K[0] * p0 + K[1];
+  *py = K[0] * p1 + K[2];
+}
+
 // EpipolarDistanceError: squared distance of x2 = (u,v) to the line F (x,y,1)
 GD double err_fmatrix(const double *M, double x, double y, double u, double v) {
   const double l0 = (M[0] * x + M[1] * y) + M[2];

@@ -559,103 +559,4 @@ int ctx_resection_wait_done(Ctx *c);
 int ctx_set_query_camera(Ctx *c, const Query *q, const char *who);
 void ctx_set_uncalibrated_camera(Ctx *c, uint32_t width, uint32_t height);  // ... from here on uncalibrated, image w x h
 
-// adjust.hip: what the colouring plan (colorize.hip) reads of a device-resident sfm_data -- the structure as
-// sfmloc_sfm_create received it: the CSR by landmark and the per-view lists of the transpose (vlist = observation
-// indices sorted by view, ascending inside a view; view_off [n_views + 1]; obs_lm = an observation's landmark)
-struct SfmColorView {
-  int device;
-  hipStream_t s;
-  uint32_t n_views, n_lm, max_view_obs;  // max_view_obs: the longest per-view list
-  const uint64_t *d_obs_off;
-  const uint32_t *d_obs_view, *d_obs_lm, *d_vlist, *d_view_off;
-};
-void sfm_color_view(const sfmloc_sfm *h, SfmColorView *out);
-
-// ba_separable.hip: what the separable adjustment (sfmloc_sfm_adjust) works on -- adjust.hip's resident sfm_data.
-// obs_keep / lm_stage are null before the first cleanup (every observation enters); pose_view_off / pose_views list
-// every pose's views in ascending view index (CSR by pose).  pose_t [n_poses*3] is scratch.
-struct SfmBaView {
-  hipStream_t s;
-  uint32_t n_views, n_poses, n_lm;
-  const uint32_t *d_view_intr, *d_view_pose, *d_intr_type;
-  const double *d_intr;
-  double *d_pose_R, *d_pose_C, *d_pose_t, *d_lm_X;
-  const uint64_t *d_obs_off;
-  const uint32_t *d_obs_view, *d_obs_lm, *d_vlist, *d_view_off;
-  const double *d_obs_x;
-  const uint8_t *d_obs_keep, *d_lm_stage;
-  const uint32_t *d_pose_view_off, *d_pose_views;
-  double *d_blk_cost;   // [2 * n_blocks] a block's cost before and after
-  uint32_t *d_blk_info;  // [n_blocks] steps tried | entered << 29 | moved << 30 | at the cap << 31
-};
-int ba_separable_run(const SfmBaView &v, uint32_t what, sfmloc_ba_report *rep);
-
-// ba_joint.hip: the joint adjustment (sfmloc_sfm_adjust_joint) works on the same resident arrays, moves the intrinsics
-// too (d_intr: the handle's array, not const on this path) and decides on the host which observations enter: the
-// host's copies of the index arrays and of the keep masks (null before the first cleanup)
-struct SfmJointHost {
-  uint32_t n_intr;
-  uint64_t n_obs;
-  double *d_intr;
-  const uint32_t *view_intr, *view_pose, *obs_view;
-  const uint64_t *obs_off;
-  const uint8_t *obs_keep, *lm_stage;
-};
-int ba_joint_run(const SfmBaView &v, const SfmJointHost &hs, uint32_t what, const sfmloc_ba_joint_options &opt,
-                 sfmloc_ba_joint_report *rep);
-
-// triangulate.hip: what sfmloc_sfm_triangulate works on -- adjust.hip's resident sfm_data.  It overwrites lm_X and the
-// keep masks (obs_keep, lm_stage in the cleanup's coding: 3 = kept, 0 = not); ud [2 * n_obs] is scratch.
-struct SfmTriView {
-  hipStream_t s;
-  uint64_t seed;  // the sampling key (sfmloc_params.seed of the handle)
-  uint32_t n_views, n_lm;
-  uint64_t n_obs;
-  const uint32_t *d_view_intr, *d_view_pose, *d_intr_type;
-  const double *d_intr;
-  const uint8_t *d_pose_valid;
-  const double *d_pose_R, *d_pose_C;
-  const uint32_t *d_lm_id;
-  double *d_lm_X;
-  const uint64_t *d_obs_off;
-  const uint32_t *d_obs_view;
-  const double *d_obs_x;
-  double *d_ud;
-  uint8_t *d_obs_keep, *d_lm_stage;
-  const uint8_t *d_select = nullptr;  // [n_lm] or null (all): a landmark with 0 is not touched (sfmloc_sfm_register)
-};
-int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep);
-
-// register.hip: what sfmloc_sfm_register works on -- adjust.hip's resident sfm_data with the host's copies of the view
-// and pose tables (the pose tables are written on both sides), and what the handle keeps between rounds and calls
-struct SfmRegState {
-  std::vector<sfmloc_sfm_view_result> res;     // per view: the last round that tried it
-  std::vector<int32_t> round;                  // that round, or -1
-  std::vector<uint32_t> last_cnt;              // its correspondence count then
-  std::vector<std::vector<uint32_t>> inliers;
-  uint32_t rounds_done = 0;
-  unsigned long long h_extended = 0;
-  DevBuf<uint32_t> d_clist, d_cnt, d_unposed;  // compacted lists [n_obs], their lengths [n_views], the unposed views
-  DevBuf<uint8_t> d_view_new, d_select;        // [n_views] registered this round, [n_lm] to be triangulated
-  DevBuf<unsigned long long> d_extended;
-};
-struct SfmRegView {
-  int device;
-  bool masks;  // the keep masks exist
-  sfmloc_sfm *handle;
-  SfmTriView tri;
-  uint32_t n_poses;
-  const uint32_t *d_obs_lm, *d_vlist, *d_view_off;
-  uint8_t *d_pose_valid;
-  double *d_pose_R, *d_pose_C;
-  const uint32_t *h_view_id, *h_view_intr, *h_view_pose;
-  const double *h_intr;
-  uint8_t *h_pose_valid;
-  double *h_pose_R, *h_pose_C;
-  SfmRegState *state;
-};
-void sfm_reg_view(sfmloc_sfm *h, SfmRegView *out);
-// adjust.hip: the handle's K5 contexts, at least n of them (the first leads a gang session)
-int sfm_reg_contexts(sfmloc_sfm *h, uint32_t n, sfmloc_context ***ctx);
-
 }  // namespace sfmloc

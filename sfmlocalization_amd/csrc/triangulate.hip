@@ -18,8 +18,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "geom_device.h"
-#include "sfmloc_internal.h"
+#include "sfm_data.h"
 
 namespace sfmloc {
 namespace {
@@ -27,21 +26,12 @@ namespace {
 constexpr int kTriLanes = 8;    // lanes per landmark (a power of two, at most 64)
 constexpr int kTriBlock = 256;  // 32 landmarks per workgroup
 
-struct TriArgs {
-  uint32_t n_lm;
+// the resident arrays (SfmDev; the masks are written) and this call's options and workspace
+struct TriArgs : SfmDev {
   uint32_t mode, min_inliers, allow_pairs;
   double thr;
-  uint64_t seed;
-  const uint32_t *view_intr, *view_pose, *intr_type;
-  const double *intr;
-  const uint8_t *pose_valid;
-  const double *pose_R, *pose_C;
-  const uint32_t *lm_id;
-  const uint64_t *obs_off;
-  const uint32_t *obs_view;
-  const double *obs_x, *ud, *P;
-  double *lm_X;
-  uint8_t *obs_keep, *lm_stage;
+  uint64_t seed;  // the sampling key (sfmloc_params.seed of the handle)
+  const double *ud, *P;
   const uint8_t *select;         // null: every landmark; else only those with select[l] != 0, the others untouched
   unsigned long long *counters;  // kept, too few posed, no hypothesis, too few inliers, observations kept, rounds
 };
@@ -146,28 +136,17 @@ __device__ __forceinline__ bool tri_solve(double (&G)[4][4], double *X) {
   return w != 0.0 && geom::is_finite(w) && geom::is_finite(X[0]) && geom::is_finite(X[1]) && geom::is_finite(X[2]);
 }
 
-// sfmloc.h "inliers": depth and pixel residual of X in observation o, the arithmetic of the cleanup's residual
-// (adjust.hip k_adj_residual); *sq = the squared residual
+// sfmloc.h "inliers": depth and pixel residual of X in observation o, on the projection the cleanup's residual uses
+// (geom::project_pixel); *sq = the squared residual
 __device__ __forceinline__ bool tri_inlier(const TriArgs &A, uint64_t o, const double *X, bool depth_only, double *sq) {
   const uint32_t v = A.obs_view[o];
   const uint32_t ii = A.view_intr[v];
   const double *R = A.pose_R + 9 * (size_t)A.view_pose[v];
   const double *C = A.pose_C + 3 * (size_t)A.view_pose[v];
   const double *K = A.intr + 6 * (size_t)ii;
-  const double f = K[0], ppx = K[1], ppy = K[2];
-  const double d0 = X[0] - C[0], d1 = X[1] - C[1], d2 = X[2] - C[2];
-  const double X0 = (R[0] * d0 + R[1] * d1) + R[2] * d2;
-  const double X1 = (R[3] * d0 + R[4] * d1) + R[5] * d2;
-  const double X2 = (R[6] * d0 + R[7] * d1) + R[8] * d2;
-  double p0 = X0 / X2, p1 = X1 / X2;
-  if (A.intr_type[ii] == 3) {
-    const double r2 = p0 * p0 + p1 * p1;
-    const double r4 = r2 * r2, r6 = r4 * r2;
-    const double rc = ((1.0 + K[3] * r2) + K[4] * r4) + K[5] * r6;
-    p0 = p0 * rc;
-    p1 = p1 * rc;
-  }
-  const double ex = A.obs_x[2 * o] - (f * p0 + ppx), ey = A.obs_x[2 * o + 1] - (f * p1 + ppy);
+  double X2, px, py;
+  geom::project_pixel(R, C, K, A.intr_type[ii] == 3, X, &X2, &px, &py);
+  const double ex = A.obs_x[2 * o] - px, ey = A.obs_x[2 * o + 1] - py;
   const double s = ex * ex + ey * ey;
   *sq = s;
   return X2 > 0.0 && (depth_only || sqrt(s) <= A.thr);  // (a NaN residual is not <= thr)
@@ -311,12 +290,13 @@ __global__ __launch_bounds__(kTriBlock) void k_tri_landmarks(TriArgs A) {
 
 }  // namespace
 
-int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep) {
+int triangulate_run(Sfm &h, const sfmloc_triangulate_options &opt, sfmloc_triangulate_report *rep,
+                    const uint8_t *d_select) {
   CallScope d;  // (on the handle's stream; before the buffers: destroyed after them)
-  hipStream_t s = v.s;
+  hipStream_t s = h.s;
   DevBuf<double> d_P;
   DevBuf<unsigned long long> d_cnt;
-  int rc = d_P.alloc(nullptr, 12 * (size_t)v.n_views);
+  int rc = d_P.alloc(nullptr, 12 * (size_t)h.n_views);
   if (rc) return rc;
   rc = d_cnt.alloc(nullptr, 6);
   if (rc) return rc;
@@ -324,39 +304,25 @@ int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, 
   if ((rc = d.open(true, &ms, s)) || (rc = d.time_begin())) return rc;
   unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
   SFM_HIP(hipMemsetAsync(d_cnt, 0, sizeof cnt, s));
-  hipLaunchKernelGGL(k_tri_views, dim3((v.n_views + 255) / 256), dim3(256), 0, s, v.n_views, v.d_view_intr,
-                     v.d_view_pose, v.d_intr, (const double *)v.d_pose_R, (const double *)v.d_pose_C, d_P.get());
-  if (v.n_obs)
-    hipLaunchKernelGGL(k_tri_pixels, dim3((unsigned)((v.n_obs + 255) / 256)), dim3(256), 0, s, v.n_obs, v.d_obs_view,
-                       v.d_obs_x, v.d_view_intr, v.d_intr_type, v.d_intr, v.d_ud);
-  SFM_HIP(hipGetLastError());
   TriArgs A;
-  A.n_lm = v.n_lm;
+  static_cast<SfmDev &>(A) = sfm_dev(h, true);  // (this call makes the masks)
   A.mode = opt.mode;
   A.min_inliers = opt.min_inliers;
   A.allow_pairs = opt.allow_pairs;
   A.thr = opt.residual_px;
-  A.seed = v.seed;
-  A.view_intr = v.d_view_intr;
-  A.view_pose = v.d_view_pose;
-  A.intr_type = v.d_intr_type;
-  A.intr = v.d_intr;
-  A.pose_valid = v.d_pose_valid;
-  A.pose_R = v.d_pose_R;
-  A.pose_C = v.d_pose_C;
-  A.lm_id = v.d_lm_id;
-  A.obs_off = v.d_obs_off;
-  A.obs_view = v.d_obs_view;
-  A.obs_x = v.d_obs_x;
-  A.ud = v.d_ud;
+  A.seed = h.params.seed;
+  A.ud = h.d_ray;  // (the cleanup's ray scratch, 4 doubles per observation: every cleanup rewrites it)
   A.P = d_P;
-  A.lm_X = v.d_lm_X;
-  A.obs_keep = v.d_obs_keep;
-  A.lm_stage = v.d_lm_stage;
-  A.select = v.d_select;
+  A.select = d_select;
   A.counters = d_cnt;
-  if (v.n_lm) {
-    const uint64_t lanes = (uint64_t)v.n_lm * kTriLanes;
+  hipLaunchKernelGGL(k_tri_views, dim3((h.n_views + 255) / 256), dim3(256), 0, s, h.n_views, A.view_intr, A.view_pose,
+                     (const double *)A.intr, (const double *)A.pose_R, (const double *)A.pose_C, d_P.get());
+  if (h.n_obs)
+    hipLaunchKernelGGL(k_tri_pixels, dim3((unsigned)((h.n_obs + 255) / 256)), dim3(256), 0, s, h.n_obs, A.obs_view,
+                       A.obs_x, A.view_intr, A.intr_type, (const double *)A.intr, h.d_ray.get());
+  SFM_HIP(hipGetLastError());
+  if (h.n_lm) {
+    const uint64_t lanes = (uint64_t)h.n_lm * kTriLanes;
     hipLaunchKernelGGL(k_tri_landmarks, dim3((unsigned)((lanes + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, s, A);
   }
   SFM_HIP(hipGetLastError());
@@ -364,12 +330,12 @@ int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, 
   SFM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
   SFM_HIP(hipStreamSynchronize(s));
   if (rep) {
-    rep->landmarks_in = v.n_lm;
+    rep->landmarks_in = h.n_lm;
     rep->landmarks_kept = cnt[0];
     rep->failed_posed = cnt[1];
     rep->failed_hypothesis = cnt[2];
     rep->failed_inliers = cnt[3];
-    rep->obs_in = v.n_obs;
+    rep->obs_in = h.n_obs;
     rep->obs_kept = cnt[4];
     rep->rounds = cnt[5];
     rep->device_ms = ms;
@@ -378,3 +344,36 @@ int triangulate_run(const SfmTriView &v, const sfmloc_triangulate_options &opt, 
 }
 
 }  // namespace sfmloc
+
+using namespace sfmloc;
+
+extern "C" {
+
+void sfmloc_triangulate_default_options(sfmloc_triangulate_options *o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->mode = SFMLOC_TRI_ROBUST;
+  o->min_inliers = 3;
+  o->allow_pairs = 1;
+  o->residual_px = 4.0;
+}
+
+int sfmloc_sfm_triangulate(sfmloc_sfm *hh, const sfmloc_triangulate_options *opt, sfmloc_triangulate_report *rep) {
+  SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_triangulate: null handle");
+  sfmloc_triangulate_options o;
+  if (opt) o = *opt;
+  else sfmloc_triangulate_default_options(&o);
+  SFM_CHECK(o.mode == SFMLOC_TRI_ROBUST || o.mode == SFMLOC_TRI_BLIND, SFMLOC_EINVAL,
+            "sfmloc_sfm_triangulate: mode = %u (0 robust, 1 blind)", o.mode);
+  SFM_CHECK(o.min_inliers >= 2 && o.residual_px >= 0.0, SFMLOC_EINVAL,
+            "sfmloc_sfm_triangulate: min_inliers must be at least 2 and residual_px not negative");
+  Sfm *h = reinterpret_cast<Sfm *>(hh);
+  if (rep) memset(rep, 0, sizeof *rep);
+  SFM_HIP(hipSetDevice(h->device));
+  const int rc = triangulate_run(*h, o, rep);
+  if (rc) return rc;
+  h->cleaned = true;  // the masks exist: a cleanup or an adjustment that follows works on what was kept
+  return SFMLOC_OK;
+}
+
+}  // extern "C"

@@ -64,7 +64,7 @@ def trace_split(path):
     with open(path) as fh:
         for row in csv.DictReader(fh):
             name, ns = row["Name"], float(row["TotalDurationNs"])
-            if "k_reg_" in name or "RegFillBody" in name:
+            if "k_reg_" in name or "SfmFillBody" in name or "k_sfm_fill" in name:
                 groups["register_new"] += ns
             elif "k_tri_" in name:
                 groups["triangulate"] += ns
