@@ -1071,6 +1071,65 @@ def pair_arrays(matches, view_index=None):
     return pairs, off, cat(0), cat(1)
 
 
+def _options(struct, default_fn, overrides):
+    """a fresh `struct` filled by the library's default_fn, then the caller's fields; an unknown field is an error"""
+    o = struct()
+    getattr(_L(), default_fn)(C.byref(o))
+    for k, v in overrides.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def _pair_list(pairs, offsets, match_i, match_j):
+    """the pair list of pair_arrays, coerced and length-checked -> (pairs [P, 2], offsets, match_i, match_j)"""
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
+    if len(offsets) != len(pairs) + 1 or len(match_i) != len(match_j) or \
+            (len(pairs) and int(offsets[-1]) != len(match_i)):
+        raise ValueError("pair list arrays differ in length")
+    return pairs, offsets, match_i, match_j
+
+
+def _pair_scene(view_off, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j):
+    """the two-view scene of RelPoses, RelRefine and WedgeScales, coerced and length-checked -> (the arrays, which the
+    caller keeps alive over the call; the C arguments from view_off to match_j, with view_wh where it is not None)"""
+    view_off = np.ascontiguousarray(view_off, np.uint64)
+    kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
+    view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
+    intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
+    intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
+    n_views = len(view_off) - 1
+    wh = () if view_wh is None else (np.ascontiguousarray(view_wh, np.uint32).reshape(-1, 2),)
+    if any(len(a) != n_views for a in wh) or len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
+            (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
+        raise ValueError("view arrays differ in length")
+    pairs, offsets, match_i, match_j = _pair_list(pairs, offsets, match_i, match_j)
+    args = (_ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float), *(_ptr(a, C.c_uint32) for a in wh),
+            _ptr(view_intrinsic, C.c_uint32), _ptr(intrinsics, C.c_double), _ptr(intrinsic_type, C.c_uint32),
+            len(intrinsics), _ptr(pairs, C.c_uint32), len(pairs), _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32),
+            _ptr(match_j, C.c_uint32))
+    return (view_off, kpt_xy, wh, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j), args
+
+
+def _pair_poses(P, rel_R, rel_t, inl_off, inl_idx, use_pair):
+    """the results of RelPoses for P pairs that RelRefine and WedgeScales take, coerced and length-checked -> (the
+    arrays, the C arguments from rel_R to use_pair)"""
+    rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
+    rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
+    inl_off, inl_idx = np.ascontiguousarray(inl_off, np.uint64), np.ascontiguousarray(inl_idx, np.uint32)
+    if use_pair is not None:
+        use_pair = np.ascontiguousarray(np.asarray(use_pair) != 0, np.uint8)
+    if len(rel_R) != P or len(rel_t) != P or len(inl_off) != P + 1 or (use_pair is not None and len(use_pair) != P) \
+            or (P and int(inl_off[-1]) > len(inl_idx)):
+        raise ValueError("pose or inlier arrays differ in length")
+    args = (_ptr(rel_R, C.c_double), _ptr(rel_t, C.c_double), _ptr(inl_off, C.c_uint64), _ptr(inl_idx, C.c_uint32),
+            None if use_pair is None else _ptr(use_pair, C.c_uint8))
+    return (rel_R, rel_t, inl_off, inl_idx, use_pair), args
+
+
 def tracks_last_ms():
     """device milliseconds of this thread's last Tracks()"""
     return float(_L().sfmloc_tracks_last_ms())
@@ -1084,16 +1143,11 @@ class Tracks:
 
     def __init__(self, view_off, pairs, offsets, match_i, match_j, view_use=None, min_length=2, device=0):
         view_off = np.ascontiguousarray(view_off, np.uint64)
-        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
         if view_use is not None:
             view_use = np.ascontiguousarray(view_use, np.uint8)
             if len(view_use) != len(view_off) - 1:
                 raise ValueError("view_use must have one entry per view")
-        if len(offsets) != len(pairs) + 1 or len(match_i) != len(match_j) or \
-                (len(pairs) and int(offsets[-1]) != len(match_i)):
-            raise ValueError("pair list arrays differ in length")
+        pairs, offsets, match_i, match_j = _pair_list(pairs, offsets, match_i, match_j)
         h = C.c_void_p()
         _check(_L().sfmloc_tracks_build(int(device), _ptr(view_off, C.c_uint64), len(view_off) - 1,
                                         _ptr(view_use, C.c_uint8), _ptr(pairs.reshape(-1), C.c_uint32), len(pairs),
@@ -1127,13 +1181,7 @@ RELPOSE_RESULT = np.dtype([("ok", np.uint32), ("n_matches", np.uint32), ("n_inli
 
 def relpose_default_options(**overrides):
     """sfmloc_relpose_default_options -> RelposeOptions (256 iterations, 2.5 px, the default seed)"""
-    o = RelposeOptions()
-    _L().sfmloc_relpose_default_options(C.byref(o))
-    for k, v in overrides.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(RelposeOptions, "sfmloc_relpose_default_options", overrides)
 
 
 def relpose_last_ms():
@@ -1150,29 +1198,12 @@ class RelPoses:
 
     def __init__(self, view_off, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i,
                  match_j, device=0, **options):
-        view_off = np.ascontiguousarray(view_off, np.uint64)
-        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
-        view_wh = np.ascontiguousarray(view_wh, np.uint32).reshape(-1, 2)
-        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
-        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
-        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
-        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
-        n_views = len(view_off) - 1
-        if len(view_wh) != n_views or len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
-                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
-            raise ValueError("view arrays differ in length")
-        if len(offsets) != len(pairs) + 1 or len(match_i) != len(match_j) or \
-                (len(pairs) and int(offsets[-1]) != len(match_i)):
-            raise ValueError("pair list arrays differ in length")
+        keep, scene = _pair_scene(view_off, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets,
+                                  match_i, match_j)
+        pairs = keep[6]
         opt = relpose_default_options(**options)
         h = C.c_void_p()
-        _check(_L().sfmloc_relative_poses(int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float),
-                                          _ptr(view_wh, C.c_uint32), _ptr(view_intrinsic, C.c_uint32),
-                                          _ptr(intrinsics, C.c_double), _ptr(intrinsic_type, C.c_uint32), len(intrinsics),
-                                          _ptr(pairs, C.c_uint32), len(pairs), _ptr(offsets, C.c_uint64),
-                                          _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32), C.byref(opt), C.byref(h)))
+        _check(_L().sfmloc_relative_poses(int(device), *scene, C.byref(opt), C.byref(h)))
         try:
             self.results = np.zeros(len(pairs), RELPOSE_RESULT)
             _check(_L().sfmloc_relpose_results(h, _ptr(self.results, RelposeResult) if len(pairs) else None))
@@ -1199,13 +1230,7 @@ RELREFINE_RESULT = np.dtype([("status", np.uint32), ("n_used", np.uint32), ("ste
 
 def relrefine_default_options(**overrides):
     """sfmloc_relrefine_default_options -> RelrefineOptions (max_steps 100, min_points 13)"""
-    o = RelrefineOptions()
-    _L().sfmloc_relrefine_default_options(C.byref(o))
-    for k, v in overrides.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(RelrefineOptions, "sfmloc_relrefine_default_options", overrides)
 
 
 def relrefine_last_ms():
@@ -1221,36 +1246,13 @@ class RelRefine:
 
     def __init__(self, view_off, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j,
                  rel_R, rel_t, inl_off, inl_idx, use_pair=None, device=0, **options):
-        view_off = np.ascontiguousarray(view_off, np.uint64)
-        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
-        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
-        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
-        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
-        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
-        rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
-        rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
-        inl_off, inl_idx = np.ascontiguousarray(inl_off, np.uint64), np.ascontiguousarray(inl_idx, np.uint32)
-        if use_pair is not None:
-            use_pair = np.ascontiguousarray(np.asarray(use_pair) != 0, np.uint8)
-        n_views, P = len(view_off) - 1, len(pairs)
-        if len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
-                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
-            raise ValueError("view arrays differ in length")
-        if len(offsets) != P + 1 or len(match_i) != len(match_j) or (P and int(offsets[-1]) != len(match_i)):
-            raise ValueError("pair list arrays differ in length")
-        if len(rel_R) != P or len(rel_t) != P or len(inl_off) != P + 1 or (use_pair is not None and len(use_pair) != P) \
-                or (P and int(inl_off[-1]) > len(inl_idx)):
-            raise ValueError("pose or inlier arrays differ in length")
+        keep, scene = _pair_scene(view_off, kpt_xy, None, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets,
+                                  match_i, match_j)
+        P = len(keep[6])
+        keep_poses, poses = _pair_poses(P, rel_R, rel_t, inl_off, inl_idx, use_pair)
         opt = relrefine_default_options(**options)
         h = C.c_void_p()
-        _check(_L().sfmloc_refine_relative_poses(
-            int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float), _ptr(view_intrinsic, C.c_uint32),
-            _ptr(intrinsics, C.c_double), _ptr(intrinsic_type, C.c_uint32), len(intrinsics), _ptr(pairs, C.c_uint32), P,
-            _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32), _ptr(rel_R, C.c_double),
-            _ptr(rel_t, C.c_double), _ptr(inl_off, C.c_uint64), _ptr(inl_idx, C.c_uint32),
-            None if use_pair is None else _ptr(use_pair, C.c_uint8), C.byref(opt), C.byref(h)))
+        _check(_L().sfmloc_refine_relative_poses(int(device), *scene, *poses, C.byref(opt), C.byref(h)))
         try:
             self.results = np.zeros(P, RELREFINE_RESULT)
             _check(_L().sfmloc_relrefine_results(h, _ptr(self.results, RelrefineResult) if P else None))
@@ -1271,13 +1273,7 @@ WSCALE = np.dtype([("view", np.uint32), ("k", np.uint32), ("l", np.uint32), ("n_
 
 def wscales_default_options(**overrides):
     """sfmloc_wscales_default_options -> WscalesOptions (min_shared 8, max_shared 2048)"""
-    o = WscalesOptions()
-    _L().sfmloc_wscales_default_options(C.byref(o))
-    for k, v in overrides.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(WscalesOptions, "sfmloc_wscales_default_options", overrides)
 
 
 def wscales_last_ms():
@@ -1294,37 +1290,12 @@ class WedgeScales:
 
     def __init__(self, view_off, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j,
                  rel_R, rel_t, inl_off, inl_idx, use_pair=None, device=0, **options):
-        view_off = np.ascontiguousarray(view_off, np.uint64)
-        kpt_xy = np.ascontiguousarray(kpt_xy, np.float32).reshape(-1, 2)
-        view_intrinsic = np.ascontiguousarray(view_intrinsic, np.uint32)
-        intrinsics = np.ascontiguousarray(intrinsics, np.float64).reshape(-1, 6)
-        intrinsic_type = np.ascontiguousarray(intrinsic_type, np.uint32)
-        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        match_i, match_j = np.ascontiguousarray(match_i, np.uint32), np.ascontiguousarray(match_j, np.uint32)
-        rel_R = np.ascontiguousarray(rel_R, np.float64).reshape(-1, 9)
-        rel_t = np.ascontiguousarray(rel_t, np.float64).reshape(-1, 3)
-        inl_off, inl_idx = np.ascontiguousarray(inl_off, np.uint64), np.ascontiguousarray(inl_idx, np.uint32)
-        if use_pair is not None:
-            use_pair = np.ascontiguousarray(np.asarray(use_pair) != 0, np.uint8)
-        n_views, P = len(view_off) - 1, len(pairs)
-        if len(view_intrinsic) != n_views or len(intrinsic_type) != len(intrinsics) or \
-                (n_views >= 0 and len(kpt_xy) != int(view_off[-1])):
-            raise ValueError("view arrays differ in length")
-        if len(offsets) != P + 1 or len(match_i) != len(match_j) or (P and int(offsets[-1]) != len(match_i)):
-            raise ValueError("pair list arrays differ in length")
-        if len(rel_R) != P or len(rel_t) != P or len(inl_off) != P + 1 or (use_pair is not None and len(use_pair) != P) \
-                or (P and int(inl_off[-1]) > len(inl_idx)):
-            raise ValueError("pose or inlier arrays differ in length")
+        keep, scene = _pair_scene(view_off, kpt_xy, None, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets,
+                                  match_i, match_j)
+        keep_poses, poses = _pair_poses(len(keep[6]), rel_R, rel_t, inl_off, inl_idx, use_pair)
         opt = wscales_default_options(**options)
         h = C.c_void_p()
-        _check(_L().sfmloc_wedge_scales(int(device), _ptr(view_off, C.c_uint64), n_views, _ptr(kpt_xy, C.c_float),
-                                        _ptr(view_intrinsic, C.c_uint32), _ptr(intrinsics, C.c_double),
-                                        _ptr(intrinsic_type, C.c_uint32), len(intrinsics), _ptr(pairs, C.c_uint32), P,
-                                        _ptr(offsets, C.c_uint64), _ptr(match_i, C.c_uint32), _ptr(match_j, C.c_uint32),
-                                        _ptr(rel_R, C.c_double), _ptr(rel_t, C.c_double), _ptr(inl_off, C.c_uint64),
-                                        _ptr(inl_idx, C.c_uint32), None if use_pair is None else _ptr(use_pair, C.c_uint8),
-                                        C.byref(opt), C.byref(h)))
+        _check(_L().sfmloc_wedge_scales(int(device), *scene, *poses, C.byref(opt), C.byref(h)))
         try:
             n = C.c_uint32()
             _check(_L().sfmloc_wscales_count(h, C.byref(n)))
@@ -1344,13 +1315,7 @@ GPOSES_PAIR = np.dtype([("n_triplets", np.uint32), ("n_triplets_ok", np.uint32),
 
 def gposes_default_options(**overrides):
     """sfmloc_gposes_default_options -> GposesOptions (5 degrees, the derived rotation delta, 0.05, 1e-6, 1e-6, 50, 20000)"""
-    o = GposesOptions()
-    _L().sfmloc_gposes_default_options(C.byref(o))
-    for k, v in overrides.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(GposesOptions, "sfmloc_gposes_default_options", overrides)
 
 
 def gposes_last_ms():
@@ -1360,13 +1325,7 @@ def gposes_last_ms():
 
 def gpscale_default_options(**overrides):
     """sfmloc_gpscale_default_options -> GpscaleOptions (0.1, 1e-6, 1e-6, 50, 20000)"""
-    o = GpscaleOptions()
-    _L().sfmloc_gpscale_default_options(C.byref(o))
-    for k, v in overrides.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(GpscaleOptions, "sfmloc_gpscale_default_options", overrides)
 
 
 class GlobalPoses:

@@ -21,7 +21,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
@@ -888,11 +887,6 @@ __global__ __launch_bounds__(256) void k_gp_commit(GpDev D, int kind) {
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 
-#define GP_TRY(call)        \
-  do {                      \
-    const int rc_ = (call); \
-    if (rc_) return rc_;    \
-  } while (0)
 
 // a launch on the call's stream, counted
 #define GP_LAUNCH(kernel, grid, ...)                                          \
@@ -918,7 +912,7 @@ int gp_pcg(const GpDev &D, uint32_t max_pcg, hipStream_t s, uint32_t *launches, 
       GP_LAUNCH(k_gp_step1<KIND>, gv, D, k);
       GP_LAUNCH(k_gp_step2<KIND>, gv, D, k);
     }
-    GP_TRY(gp_read_state(D, h, s));
+    SFM_RC(gp_read_state(D, h, s));
     if (h->done_at != kNever) break;
   }
   return SFMLOC_OK;
@@ -981,12 +975,12 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   uint32_t first = 0, size = 0;
   if (sr.n_wedges_used) {
     DevBuf<uint32_t> d_ea, d_eb, d_parent, d_flag;
-    GP_TRY(dev_upload(nullptr, d_kl, sc.kl, 2 * W, s));
-    GP_TRY(dev_upload(nullptr, d_on, on.data(), W, s));
-    GP_TRY(d_ea.alloc(nullptr, W));
-    GP_TRY(d_eb.alloc(nullptr, W));
-    GP_TRY(d_parent.alloc(nullptr, P));
-    GP_TRY(d_flag.alloc(nullptr, 1));
+    SFM_RC(dev_upload(nullptr, d_kl, sc.kl, 2 * W, s));
+    SFM_RC(dev_upload(nullptr, d_on, on.data(), W, s));
+    SFM_RC(d_ea.alloc(nullptr, W));
+    SFM_RC(d_eb.alloc(nullptr, W));
+    SFM_RC(d_parent.alloc(nullptr, P));
+    SFM_RC(d_flag.alloc(nullptr, 1));
     const uint32_t gw = (uint32_t)((W + 255) / 256), gn = (uint32_t)((P + 255) / 256);
     GP_LAUNCH(k_gp_sc_cc, gw > gn ? gw : gn, (const uint32_t *)d_kl, (const uint8_t *)d_on, (uint32_t)W, (uint32_t)P, d_ea.get(),
               d_eb.get(), d_parent.get());
@@ -1046,20 +1040,20 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   DevBuf<uint32_t> d_off, d_nbr, d_pe, d_heavy;
   DevBuf<uint8_t> d_sinc;
   DevBuf<double> d_y, d_ev, d_ew, d_rho, d_res, d_mterm, d_diag, d_x, d_r, d_z, d_p, d_q, d_xs, d_xn, d_part;
-  GP_TRY(dev_upload(nullptr, d_off, sg.off.data(), P + 1, s));
-  GP_TRY(dev_upload(nullptr, d_nbr, sg.nbr.data(), sg.nbr.size(), s));
-  GP_TRY(dev_upload(nullptr, d_pe, sg.pe.data(), sg.pe.size(), s));
-  GP_TRY(dev_upload(nullptr, d_heavy, sg.heavy.data(), sg.heavy.size(), s, 1));
-  GP_TRY(dev_upload(nullptr, d_on, on.data(), W, s));
-  GP_TRY(dev_upload(nullptr, d_sinc, etr->data(), P, s));
-  GP_TRY(dev_upload(nullptr, d_y, y.data(), W, s));
+  SFM_RC(dev_upload(nullptr, d_off, sg.off.data(), P + 1, s));
+  SFM_RC(dev_upload(nullptr, d_nbr, sg.nbr.data(), sg.nbr.size(), s));
+  SFM_RC(dev_upload(nullptr, d_pe, sg.pe.data(), sg.pe.size(), s));
+  SFM_RC(dev_upload(nullptr, d_heavy, sg.heavy.data(), sg.heavy.size(), s, 1));
+  SFM_RC(dev_upload(nullptr, d_on, on.data(), W, s));
+  SFM_RC(dev_upload(nullptr, d_sinc, etr->data(), P, s));
+  SFM_RC(dev_upload(nullptr, d_y, y.data(), W, s));
   for (DevBuf<double> *b : {std::addressof(d_ev), std::addressof(d_ew), std::addressof(d_rho), std::addressof(d_res),
                             std::addressof(d_mterm)})
-    GP_TRY(b->alloc(nullptr, W));
+    SFM_RC(b->alloc(nullptr, W));
   for (DevBuf<double> *b : {std::addressof(d_diag), std::addressof(d_x), std::addressof(d_r), std::addressof(d_z),
                             std::addressof(d_p), std::addressof(d_q), std::addressof(d_xs), std::addressof(d_xn)})
-    GP_TRY(b->alloc(nullptr, P));
-  GP_TRY(d_part.alloc(nullptr, 3 * (size_t)S.n_part));
+    SFM_RC(b->alloc(nullptr, P));
+  SFM_RC(d_part.alloc(nullptr, 3 * (size_t)S.n_part));
   SFM_HIP(hipMemsetAsync(d_xs, 0, P * sizeof(double), s));
   SFM_HIP(hipMemsetAsync(d_xn, 0, P * sizeof(double), s));
   SFM_HIP(hipMemsetAsync(d_mterm, 0, W * sizeof(double), s));
@@ -1080,13 +1074,13 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
     GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);
     GP_LAUNCH(k_gp_setup<3>, ga, S);
     GP_LAUNCH(k_gp_begin, 1, S, 1);
-    GP_TRY(gp_pcg<3>(S, sc.opt.max_pcg, s, launches, &h));
+    SFM_RC(gp_pcg<3>(S, sc.opt.max_pcg, s, launches, &h));
     GP_LAUNCH(k_gp_trial, gv, S, 3);
     GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xn, (const double *)d_y, delta, 1);
     GP_LAUNCH(k_gp_cost, ga, S, 1);
     GP_LAUNCH(k_gp_decide, 1, S, 1);
     GP_LAUNCH(k_gp_commit, gv, S, 3);
-    GP_TRY(gp_read_state(S, &h, s));
+    SFM_RC(gp_read_state(S, &h, s));
   }
   GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);  // the weights at the result
   std::vector<double> x(P), ew(W);
@@ -1108,7 +1102,7 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   sr.cost_final = h.cost;
   sr.launches = *launches - launches0;
   // "centres": what the translation kernels read
-  GP_TRY(dev_upload(nullptr, d_base, g->base.data(), P, s));
+  SFM_RC(dev_upload(nullptr, d_base, g->base.data(), P, s));
   SFM_HIP(hipMemcpyAsync(d_inc, g->in_comp.data(), n, hipMemcpyHostToDevice, s));
   SFM_HIP(hipMemcpyAsync(D.etr, etr->data(), P, hipMemcpyHostToDevice, s));
   SFM_HIP(hipStreamSynchronize(s));
@@ -1124,30 +1118,30 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   uint32_t *launches = &rep.launches;
   const size_t n = n_views, P = n_pairs;
   GpEvents ev;
-  GP_TRY(ev.mark(0, s));
+  SFM_RC(ev.mark(0, s));
   std::vector<uint8_t> use(P, 1);
   if (use_t)
     for (size_t k = 0; k < P; ++k) use[k] = use_t[k] ? 1 : 0;
   DevBuf<uint32_t> d_off, d_nbr, d_pe, d_heavy, d_pairs, d_ntri, d_nok, d_ea, d_eb, d_parent, d_flag;
   DevBuf<double> d_relR, d_relt;
   DevBuf<uint8_t> d_use, d_inc, d_erot, d_etr;
-  GP_TRY(dev_upload(nullptr, d_off, adj.off.data(), n + 1, s));
-  GP_TRY(dev_upload(nullptr, d_nbr, adj.nbr.data(), 2 * P, s));
-  GP_TRY(dev_upload(nullptr, d_pe, adj.pe.data(), 2 * P, s));
-  GP_TRY(dev_upload(nullptr, d_heavy, adj.heavy.data(), adj.heavy.size(), s, 1));
-  GP_TRY(dev_upload(nullptr, d_pairs, pairs, 2 * P, s));
-  GP_TRY(dev_upload(nullptr, d_relR, rel_R, 9 * P, s));
-  GP_TRY(dev_upload(nullptr, d_relt, rel_t, 3 * P, s));
-  GP_TRY(dev_upload(nullptr, d_use, use.data(), P, s));
-  GP_TRY(d_ntri.alloc(nullptr, P));
-  GP_TRY(d_nok.alloc(nullptr, P));
-  GP_TRY(d_ea.alloc(nullptr, P));
-  GP_TRY(d_eb.alloc(nullptr, P));
-  GP_TRY(d_parent.alloc(nullptr, n));
-  GP_TRY(d_flag.alloc(nullptr, 1));
-  GP_TRY(d_inc.alloc(nullptr, n));
-  GP_TRY(d_erot.alloc(nullptr, P));
-  GP_TRY(d_etr.alloc(nullptr, P));
+  SFM_RC(dev_upload(nullptr, d_off, adj.off.data(), n + 1, s));
+  SFM_RC(dev_upload(nullptr, d_nbr, adj.nbr.data(), 2 * P, s));
+  SFM_RC(dev_upload(nullptr, d_pe, adj.pe.data(), 2 * P, s));
+  SFM_RC(dev_upload(nullptr, d_heavy, adj.heavy.data(), adj.heavy.size(), s, 1));
+  SFM_RC(dev_upload(nullptr, d_pairs, pairs, 2 * P, s));
+  SFM_RC(dev_upload(nullptr, d_relR, rel_R, 9 * P, s));
+  SFM_RC(dev_upload(nullptr, d_relt, rel_t, 3 * P, s));
+  SFM_RC(dev_upload(nullptr, d_use, use.data(), P, s));
+  SFM_RC(d_ntri.alloc(nullptr, P));
+  SFM_RC(d_nok.alloc(nullptr, P));
+  SFM_RC(d_ea.alloc(nullptr, P));
+  SFM_RC(d_eb.alloc(nullptr, P));
+  SFM_RC(d_parent.alloc(nullptr, n));
+  SFM_RC(d_flag.alloc(nullptr, 1));
+  SFM_RC(d_inc.alloc(nullptr, n));
+  SFM_RC(d_erot.alloc(nullptr, P));
+  SFM_RC(d_etr.alloc(nullptr, P));
   GpDev D;
   memset(&D, 0, sizeof D);
   D.n = n_views;
@@ -1217,33 +1211,33 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
     rep.n_translation_pairs += g->pairs[k].used_t;
   }
   D.root = root;
-  GP_TRY(ev.mark(1, s));
+  SFM_RC(ev.mark(1, s));
   SFM_HIP(hipMemcpyAsync(d_inc, g->in_comp.data(), n, hipMemcpyHostToDevice, s));
   GP_LAUNCH(k_gp_flags, gp, D);
 
   DevBuf<double> d_R, d_Rn, d_C, d_Cn, d_dir, d_ev, d_W, d_ew, d_rho, d_res, d_mterm, d_diag, d_Minv, d_x, d_r, d_z, d_p,
       d_q, d_part;
   DevBuf<GpState> d_st;
-  GP_TRY(d_R.alloc(nullptr, 9 * n));
-  GP_TRY(d_Rn.alloc(nullptr, 9 * n));
-  GP_TRY(d_C.alloc(nullptr, 3 * n));
-  GP_TRY(d_Cn.alloc(nullptr, 3 * n));
-  GP_TRY(d_dir.alloc(nullptr, 3 * P));
-  GP_TRY(d_ev.alloc(nullptr, 3 * P));
-  GP_TRY(d_W.alloc(nullptr, 9 * P));
-  GP_TRY(d_ew.alloc(nullptr, P));
-  GP_TRY(d_rho.alloc(nullptr, P));
-  GP_TRY(d_res.alloc(nullptr, P));
-  GP_TRY(d_mterm.alloc(nullptr, P));
-  GP_TRY(d_diag.alloc(nullptr, 9 * n));
-  GP_TRY(d_Minv.alloc(nullptr, 9 * n));
-  GP_TRY(d_x.alloc(nullptr, 9 * n));
-  GP_TRY(d_r.alloc(nullptr, 9 * n));
-  GP_TRY(d_z.alloc(nullptr, 9 * n));
-  GP_TRY(d_p.alloc(nullptr, 9 * n));
-  GP_TRY(d_q.alloc(nullptr, 9 * n));
-  GP_TRY(d_part.alloc(nullptr, 3 * (size_t)D.n_part));
-  GP_TRY(d_st.alloc(nullptr, 1));
+  SFM_RC(d_R.alloc(nullptr, 9 * n));
+  SFM_RC(d_Rn.alloc(nullptr, 9 * n));
+  SFM_RC(d_C.alloc(nullptr, 3 * n));
+  SFM_RC(d_Cn.alloc(nullptr, 3 * n));
+  SFM_RC(d_dir.alloc(nullptr, 3 * P));
+  SFM_RC(d_ev.alloc(nullptr, 3 * P));
+  SFM_RC(d_W.alloc(nullptr, 9 * P));
+  SFM_RC(d_ew.alloc(nullptr, P));
+  SFM_RC(d_rho.alloc(nullptr, P));
+  SFM_RC(d_res.alloc(nullptr, P));
+  SFM_RC(d_mterm.alloc(nullptr, P));
+  SFM_RC(d_diag.alloc(nullptr, 9 * n));
+  SFM_RC(d_Minv.alloc(nullptr, 9 * n));
+  SFM_RC(d_x.alloc(nullptr, 9 * n));
+  SFM_RC(d_r.alloc(nullptr, 9 * n));
+  SFM_RC(d_z.alloc(nullptr, 9 * n));
+  SFM_RC(d_p.alloc(nullptr, 9 * n));
+  SFM_RC(d_q.alloc(nullptr, 9 * n));
+  SFM_RC(d_part.alloc(nullptr, 3 * (size_t)D.n_part));
+  SFM_RC(d_st.alloc(nullptr, 1));
   SFM_HIP(hipMemsetAsync(d_mterm, 0, P * sizeof(double), s));
   D.R = d_R, D.Rn = d_Rn, D.C = d_C, D.Cn = d_Cn, D.dir = d_dir, D.ev = d_ev, D.W = d_W, D.ew = d_ew, D.rho = d_rho;
   D.res = d_res, D.mterm = d_mterm, D.diag = d_diag, D.Minv = d_Minv, D.x = d_x, D.r = d_r, D.z = d_z, D.p = d_p, D.q = d_q;
@@ -1254,7 +1248,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
   GP_LAUNCH(k_gp_setup<0>, ga, D);
   GP_LAUNCH(k_gp_begin, 1, D, 0);
-  GP_TRY(gp_pcg<0>(D, opt.max_pcg, s, launches, &h));
+  SFM_RC(gp_pcg<0>(D, opt.max_pcg, s, launches, &h));
   rep.chordal_pcg = h.pcg_iter;
   rep.chordal_stop = h.pcg_stop;
   rep.chordal_residual = h.rr0 > 0.0 ? sqrt(h.rr / h.rr0) : 0.0;
@@ -1268,13 +1262,13 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
     GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);
     GP_LAUNCH(k_gp_setup<1>, ga, D);
     GP_LAUNCH(k_gp_begin, 1, D, 1);
-    GP_TRY(gp_pcg<1>(D, opt.max_pcg, s, launches, &h));
+    SFM_RC(gp_pcg<1>(D, opt.max_pcg, s, launches, &h));
     GP_LAUNCH(k_gp_trial, gv, D, 1);
     GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_Rn, rdelta, 1);
     GP_LAUNCH(k_gp_cost, ga, D, 1);
     GP_LAUNCH(k_gp_decide, 1, D, 1);
     GP_LAUNCH(k_gp_commit, gv, D, 1);
-    GP_TRY(gp_read_state(D, &h, s));
+    SFM_RC(gp_read_state(D, &h, s));
     if (h.steps_tried == 1) rep.chordal_cost = h.model;  // (at the first step's start: the projected chordal solution)
   }
   GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);  // the residuals at the result
@@ -1290,14 +1284,14 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   rep.rot_cost_final = h.cost;
 
   // sfmloc.h "translation"
-  GP_TRY(ev.mark(2, s));
+  SFM_RC(ev.mark(2, s));
   DevBuf<double> d_base;
   std::vector<uint8_t> etr_scaled;
   if (sc) {
     bool none = false;
-    GP_TRY(gp_scale_phase(D, d_inc.get(), d_base, *sc, pairs, s, launches, g, &etr_scaled, &none));
+    SFM_RC(gp_scale_phase(D, d_inc.get(), d_base, *sc, pairs, s, launches, g, &etr_scaled, &none));
     if (none) return SFMLOC_OK;
-    GP_TRY(ev.mark(4, s));
+    SFM_RC(ev.mark(4, s));
   }
   GP_LAUNCH(k_gp_dirs, gp, D);
   SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
@@ -1306,32 +1300,32 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
     GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
     GP_LAUNCH(k_gp_setup<2>, ga, D);
     GP_LAUNCH(k_gp_begin, 1, D, 1);
-    GP_TRY(gp_pcg<2>(D, opt.max_pcg, s, launches, &h));
+    SFM_RC(gp_pcg<2>(D, opt.max_pcg, s, launches, &h));
     GP_LAUNCH(k_gp_trial, gv, D, 2);
     GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_Cn, opt.translation_delta, 1);
     GP_LAUNCH(k_gp_cost, ga, D, 2);
     GP_LAUNCH(k_gp_decide, 1, D, 2);
     GP_LAUNCH(k_gp_commit, gv, D, 2);
-    GP_TRY(gp_read_state(D, &h, s));
+    SFM_RC(gp_read_state(D, &h, s));
   }
   GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
   SFM_HIP(hipGetLastError());
   SFM_HIP(hipMemcpyAsync(res.data(), d_res, P * sizeof(double), hipMemcpyDeviceToHost, s));
   SFM_HIP(hipMemcpyAsync(g->R.data(), d_R, 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
   SFM_HIP(hipMemcpyAsync(g->C.data(), d_C, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  GP_TRY(ev.mark(3, s));
+  SFM_RC(ev.mark(3, s));
   SFM_HIP(hipStreamSynchronize(s));
-  GP_TRY(ev.between(0, &rep.graph_ms));
-  GP_TRY(ev.between(1, &rep.rotation_ms));
+  SFM_RC(ev.between(0, &rep.graph_ms));
+  SFM_RC(ev.between(1, &rep.rotation_ms));
   if (sc) {
-    GP_TRY(ev.span(2, 4, &g->srep.scale_ms));
-    GP_TRY(ev.span(4, 3, &rep.translation_ms));
+    SFM_RC(ev.span(2, 4, &g->srep.scale_ms));
+    SFM_RC(ev.span(4, 3, &rep.translation_ms));
     g->srep.centre_ms = rep.translation_ms;
     for (size_t v = 0; v < n; ++v)
       if (!g->in_comp[v])
         for (int i = 0; i < 9; ++i) g->R[9 * v + i] = 0.0;
   } else {
-    GP_TRY(ev.between(2, &rep.translation_ms));
+    SFM_RC(ev.between(2, &rep.translation_ms));
   }
   for (size_t k = 0; k < P; ++k) g->pairs[k].trans_residual = res[k];
   rep.trans_steps_tried = h.steps_tried;
@@ -1363,9 +1357,6 @@ int gposes_impl(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_
                 opt.rotation_delta == opt.rotation_delta,
             SFMLOC_EINVAL, "sfmloc_global_poses: a tolerance or delta is out of range");
   SFM_CHECK(opt.max_pcg >= 1 && opt.max_pcg <= (1u << 30), SFMLOC_EINVAL, "sfmloc_global_poses: max_pcg = %u", opt.max_pcg);
-  int rc_dev = CallScope::use_device(device);
-  if (rc_dev) return rc_dev;
-  g_gposes_last_ms = 0.0;
   g->n_views = n_views;
   g->in_comp.assign(n_views, 0);
   g->R.assign(9 * (size_t)n_views, 0.0);
@@ -1376,18 +1367,15 @@ int gposes_impl(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_
   g->base.assign(n_pairs, 0.0);
   g->wedge_w.assign(sc ? sc->n_wedges : 0, 0.0);
   g->srep.n_wedges = sc ? sc->n_wedges : 0;
-  if (n_pairs == 0 || n_views == 0) return SFMLOC_OK;  // nothing to launch
-  CallScope d;
-  if ((rc_dev = d.open(true, &g_gposes_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = gposes_device(n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, adj, sc, d.s, g);
-  if (rc_dev) return rc_dev;
-  rc_dev = d.time_end();
+  SFM_RC(timed_call(device, &g_gposes_last_ms, n_pairs != 0 && n_views != 0, [&](hipStream_t s) {
+    return gposes_device(n_views, pairs, n_pairs, rel_R, rel_t, use_t, opt, adj, sc, s, g);
+  }));
   g->rep.device_ms = g_gposes_last_ms;
   if (!g->rep.n_component_views) {  // (what the device wrote for a component that does not exist)
     g->R.assign(9 * (size_t)n_views, 0.0);
     g->C.assign(3 * (size_t)n_views, 0.0);
   }
-  return rc_dev;
+  return SFMLOC_OK;
 }
 
 }  // namespace
@@ -1420,26 +1408,10 @@ void sfmloc_gpscale_default_options(sfmloc_gpscale_options *o) {
 static int gposes_call(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,
                        const double *rel_t, const uint8_t *use_t, const sfmloc_gposes_options *opt, const GpScaleIn *sc,
                        sfmloc_gposes **out) {
-  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_global_poses: null argument");
-  *out = nullptr;
-  sfmloc_gposes_options o;
-  if (opt) o = *opt;
-  else sfmloc_gposes_default_options(&o);
-  Gposes *g = new (std::nothrow) Gposes();
-  SFM_CHECK(g, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = gposes_impl(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, o, sc, g);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_global_poses: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    delete g;
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_gposes *>(g);
-  return SFMLOC_OK;
+  const sfmloc_gposes_options o = options_or(opt, sfmloc_gposes_default_options);
+  return make_handle<Gposes>("sfmloc_global_poses", out, [&](Gposes *g) {
+    return gposes_impl(device, n_views, pairs, n_pairs, rel_R, rel_t, use_t, o, sc, g);
+  });
 }
 
 int sfmloc_global_poses(int device, uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, const double *rel_R,

@@ -1,7 +1,8 @@
 // sfmloc_wedge_scales: the ratio of the baselines of two pairs that share a view, from the depths of the features they
 // share.  The semantics are stated in include/sfmloc.h ("Wedge scales"); tests/pairscales_np.py restates every operation.
 // f64, unfused (the library's -ffp-contract=off), only + - * / sqrt; after the depths nothing but comparisons and one
-// division per shared feature, no float atomics: the records are the restatement's bits.
+// division per shared feature, no float atomics: the records are the restatement's bits.  Scene and poses: PairScene and
+// PairPoses on the host (pair_scene.h), PairDev and PairPosesDev on the device (twoview_device.h), the bases of WsDev.
 //
 //   depths      k_ws_depths: one workgroup per pair walks its inlier list; a match gives one entry per side (pair side,
 //               feature, depth), the pair side of a match that yields nothing being one past the last.
@@ -18,7 +19,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
@@ -41,13 +41,8 @@ struct Wscales {
   sfmloc_wscales_report rep{};
 };
 
-struct WsDev {
-  uint32_t n_views, n_pairs, n_ent, nb_view, n_heavy;
-  const uint64_t *view_off, *offsets, *inl_off;
-  const float *kpt;
-  const uint32_t *view_intr, *intr_type, *pairs, *match_i, *match_j, *inl_idx;
-  const double *intr, *relR, *relt;
-  const uint8_t *use;
+struct WsDev : PairDev, PairPosesDev {
+  uint32_t n_ent, nb_view, n_heavy;
   const uint32_t *voff, *vent, *vcand, *heavy;
   uint32_t *feat, *seg;    // per entry, entry 2 t + side of inlier t
   double *z;
@@ -55,14 +50,6 @@ struct WsDev {
   const double *z_s;
   const uint32_t *seg_begin;  // [2 n_pairs + 1]
 };
-
-// sfmloc.h "bearings" of one feature of view v
-__device__ __forceinline__ void ws_bearing(const WsDev &D, uint32_t v, uint32_t f, double *bx, double *by) {
-  const uint32_t ii = D.view_intr[v];
-  const double *K = D.intr + 6 * (size_t)ii;
-  const uint64_t row = D.view_off[v] + f;
-  view_bearing(K, D.intr_type[ii], (double)D.kpt[2 * row], (double)D.kpt[2 * row + 1], bx, by);
-}
 
 // sfmloc.h "depths".  keys / ids: the first sort's input (the feature again, and the entry's own index)
 __global__ __launch_bounds__(256) void k_ws_depths(WsDev D, uint32_t *keys, uint32_t *ids) {
@@ -79,8 +66,8 @@ __global__ __launch_bounds__(256) void k_ws_depths(WsDev D, uint32_t *keys, uint
     bool ok = false;
     if (used) {
       double a, b, u, v;
-      ws_bearing(D, vi, fi, &a, &b);
-      ws_bearing(D, vj, fj, &u, &v);
+      feature_bearing(D, view_cam(D, vi), fi, &a, &b);
+      feature_bearing(D, view_cam(D, vj), fj, &u, &v);
       ok = two_view_depths(R, t, a, b, u, v, &zi, &zj) && is_finite(zj) && zi > 0.0 && zj > 0.0;
     }
     const uint32_t e = 2 * (uint32_t)p;
@@ -261,82 +248,54 @@ __global__ __launch_bounds__(kThreads) void k_ws_ratio(WsDev D, const sfmloc_wsc
   if (threadIdx.x == 0) rec[c].ratio = u2d(key[(n - 1) / 2]);
 }
 
-#define WS_TRY(call)        \
-  do {                      \
-    const int rc_ = (call); \
-    if (rc_) return rc_;    \
-  } while (0)
-
 #define WS_LAUNCH(kernel, grid, block, ...)                                   \
   do {                                                                        \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, __VA_ARGS__);   \
     ++rep.launches;                                                           \
   } while (0)
 
-int wscales_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_intrinsic,
-                   const double *intrinsics, const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs,
-                   uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
-                   const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
-                   const uint8_t *use_pair, const sfmloc_wscales_options &opt, const wscales_host::ViewPairs &vp,
-                   hipStream_t s, Wscales *w) {
+int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscales_options &opt,
+                   const wscales_host::ViewPairs &vp, hipStream_t s, Wscales *w) {
   sfmloc_wscales_report &rep = w->rep;
-  const size_t P = n_pairs, n = n_views, n_inl = (size_t)inlier_off[n_pairs], n_ent = 2 * n_inl;
+  const uint32_t n_views = sc.n_views, n_pairs = sc.n_pairs;
+  const size_t P = n_pairs, n = n_views, n_inl = (size_t)po.inlier_off[n_pairs], n_ent = 2 * n_inl;
   const uint32_t n_cand = vp.cand[n_views];
   rep.n_candidates = n_cand;
   if (n_ent == 0 || n_cand == 0) return SFMLOC_OK;  // no depth, or no two pairs at one view: no wedge
-  std::vector<uint8_t> use(P, 1);
-  if (use_pair)
-    for (size_t k = 0; k < P; ++k) use[k] = use_pair[k] ? 1 : 0;
   uint32_t max_feat = 0;
   for (size_t v = 0; v < n; ++v)
-    if (view_off[v + 1] - view_off[v] > max_feat) max_feat = (uint32_t)(view_off[v + 1] - view_off[v]);
-  DevBuf<uint64_t> d_view_off, d_offsets, d_inl_off;
-  DevBuf<float> d_kpt;
-  DevBuf<uint32_t> d_vintr, d_itype, d_pairs, d_mi, d_mj, d_inl, d_voff, d_vent, d_vcand, d_heavy;
+    if (sc.view_off[v + 1] - sc.view_off[v] > max_feat) max_feat = (uint32_t)(sc.view_off[v + 1] - sc.view_off[v]);
+  PairSceneBufs scene;
+  PairPosesBufs poses;
+  DevBuf<uint32_t> d_voff, d_vent, d_vcand, d_heavy;
   DevBuf<uint32_t> d_feat, d_seg, d_ka, d_va, d_kb, d_vb, d_hist, d_feat_s, d_seg_begin;
-  DevBuf<double> d_intr, d_relR, d_relt, d_z, d_z_s;
-  DevBuf<uint8_t> d_use;
+  DevBuf<double> d_z, d_z_s;
   DevBuf<sfmloc_wscale> d_rec, d_out;
-  WS_TRY(dev_upload(nullptr, d_view_off, view_off, n + 1, s));
-  WS_TRY(dev_upload(nullptr, d_kpt, kpt_xy, 2 * (size_t)view_off[n_views], s));
-  WS_TRY(dev_upload(nullptr, d_vintr, view_intrinsic, n, s));
-  WS_TRY(dev_upload(nullptr, d_intr, intrinsics, 6 * (size_t)n_intrinsics, s));
-  WS_TRY(dev_upload(nullptr, d_itype, intrinsic_type, (size_t)n_intrinsics, s));
-  WS_TRY(dev_upload(nullptr, d_pairs, pairs, 2 * P, s));
-  WS_TRY(dev_upload(nullptr, d_offsets, offsets, P + 1, s));
-  WS_TRY(dev_upload(nullptr, d_mi, match_i, (size_t)offsets[n_pairs], s));
-  WS_TRY(dev_upload(nullptr, d_mj, match_j, (size_t)offsets[n_pairs], s));
-  WS_TRY(dev_upload(nullptr, d_relR, rel_R, 9 * P, s));
-  WS_TRY(dev_upload(nullptr, d_relt, rel_t, 3 * P, s));
-  WS_TRY(dev_upload(nullptr, d_inl_off, inlier_off, P + 1, s));
-  WS_TRY(dev_upload(nullptr, d_inl, inlier_idx, n_inl, s));
-  WS_TRY(dev_upload(nullptr, d_use, use.data(), P, s));
-  WS_TRY(dev_upload(nullptr, d_voff, vp.off.data(), n + 1, s));
-  WS_TRY(dev_upload(nullptr, d_vent, vp.ent.data(), vp.ent.size(), s));
-  WS_TRY(dev_upload(nullptr, d_vcand, vp.cand.data(), n + 1, s));
-  WS_TRY(dev_upload(nullptr, d_heavy, vp.heavy.data(), vp.heavy.size(), s, 1));
-  WS_TRY(d_feat.alloc(nullptr, n_ent));
-  WS_TRY(d_seg.alloc(nullptr, n_ent));
-  WS_TRY(d_z.alloc(nullptr, n_ent));
-  WS_TRY(d_ka.alloc(nullptr, n_ent));
-  WS_TRY(d_va.alloc(nullptr, n_ent));
-  WS_TRY(d_kb.alloc(nullptr, n_ent));
-  WS_TRY(d_vb.alloc(nullptr, n_ent));
-  WS_TRY(d_hist.alloc(nullptr, radix_hist_entries(n_ent)));
-  WS_TRY(d_feat_s.alloc(nullptr, n_ent));
-  WS_TRY(d_z_s.alloc(nullptr, n_ent));
-  WS_TRY(d_seg_begin.alloc(nullptr, 2 * P + 1));
-  WS_TRY(d_rec.alloc(nullptr, n_cand));
-  WsDev D;
-  memset(&D, 0, sizeof D);
-  D.n_views = n_views;
-  D.n_pairs = n_pairs;
+  SFM_RC(scene.upload(sc, s));
+  SFM_RC(poses.upload(sc, po, s));
+  SFM_RC(dev_upload(nullptr, d_voff, vp.off.data(), n + 1, s));
+  SFM_RC(dev_upload(nullptr, d_vent, vp.ent.data(), vp.ent.size(), s));
+  SFM_RC(dev_upload(nullptr, d_vcand, vp.cand.data(), n + 1, s));
+  SFM_RC(dev_upload(nullptr, d_heavy, vp.heavy.data(), vp.heavy.size(), s, 1));
+  SFM_RC(d_feat.alloc(nullptr, n_ent));
+  SFM_RC(d_seg.alloc(nullptr, n_ent));
+  SFM_RC(d_z.alloc(nullptr, n_ent));
+  SFM_RC(d_ka.alloc(nullptr, n_ent));
+  SFM_RC(d_va.alloc(nullptr, n_ent));
+  SFM_RC(d_kb.alloc(nullptr, n_ent));
+  SFM_RC(d_vb.alloc(nullptr, n_ent));
+  SFM_RC(d_hist.alloc(nullptr, radix_hist_entries(n_ent)));
+  SFM_RC(d_feat_s.alloc(nullptr, n_ent));
+  SFM_RC(d_z_s.alloc(nullptr, n_ent));
+  SFM_RC(d_seg_begin.alloc(nullptr, 2 * P + 1));
+  SFM_RC(d_rec.alloc(nullptr, n_cand));
+  WsDev D{};
+  static_cast<PairDev &>(D) = scene.dev();
+  static_cast<PairPosesDev &>(D) = poses.dev();
   D.n_ent = (uint32_t)n_ent;
   D.nb_view = (n_views + 255) / 256;
   D.n_heavy = (uint32_t)vp.heavy.size();
-  D.view_off = d_view_off, D.offsets = d_offsets, D.inl_off = d_inl_off, D.kpt = d_kpt, D.view_intr = d_vintr;
-  D.intr_type = d_itype, D.pairs = d_pairs, D.match_i = d_mi, D.match_j = d_mj, D.inl_idx = d_inl, D.intr = d_intr;
-  D.relR = d_relR, D.relt = d_relt, D.use = d_use, D.voff = d_voff, D.vent = d_vent, D.vcand = d_vcand, D.heavy = d_heavy;
+  D.voff = d_voff, D.vent = d_vent, D.vcand = d_vcand, D.heavy = d_heavy;
   D.feat = d_feat, D.seg = d_seg, D.z = d_z, D.feat_s = d_feat_s, D.z_s = d_z_s, D.seg_begin = d_seg_begin;
   const uint32_t ge = ((uint32_t)n_ent + 255) / 256;
 
@@ -362,8 +321,8 @@ int wscales_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_
   // the choice and the order of the records, on the device: flag, scan, compact; then three stable sorts of the kept
   // records' places, by view, by l and by k
   DevBuf<uint32_t> d_place;
-  WS_TRY(d_place.alloc(nullptr, (size_t)n_cand + 1));
-  WS_TRY(d_out.alloc(nullptr, n_cand));
+  SFM_RC(d_place.alloc(nullptr, (size_t)n_cand + 1));
+  SFM_RC(d_out.alloc(nullptr, n_cand));
   WS_LAUNCH(k_ws_flag, n_cand / 256 + 1, 256, (const sfmloc_wscale *)d_rec, n_cand, opt.min_shared, d_place.get());
   WS_LAUNCH(k_scan_excl, 1, 1024, d_place.get(), n_cand + 1);
   WS_LAUNCH(k_ws_compact, (n_cand + 255) / 256, 256, (const sfmloc_wscale *)d_rec, n_cand, opt.min_shared,
@@ -378,12 +337,12 @@ int wscales_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_
   if (n_rec) {
     DevBuf<uint32_t> d_k0, d_v0, d_k1, d_v1, d_h;
     DevBuf<sfmloc_wscale> d_final;
-    WS_TRY(d_k0.alloc(nullptr, n_rec));
-    WS_TRY(d_v0.alloc(nullptr, n_rec));
-    WS_TRY(d_k1.alloc(nullptr, n_rec));
-    WS_TRY(d_v1.alloc(nullptr, n_rec));
-    WS_TRY(d_h.alloc(nullptr, radix_hist_entries(n_rec)));
-    WS_TRY(d_final.alloc(nullptr, n_rec));
+    SFM_RC(d_k0.alloc(nullptr, n_rec));
+    SFM_RC(d_v0.alloc(nullptr, n_rec));
+    SFM_RC(d_k1.alloc(nullptr, n_rec));
+    SFM_RC(d_v1.alloc(nullptr, n_rec));
+    SFM_RC(d_h.alloc(nullptr, radix_hist_entries(n_rec)));
+    SFM_RC(d_final.alloc(nullptr, n_rec));
     uint32_t *rk = d_k0, *rv = d_v0, *ok = d_k1, *ov = d_v1;  // (rk, rv): keys and places in the order so far
     const int bits[3] = {radix_key_bits(n_views - 1), radix_key_bits(n_pairs - 1), radix_key_bits(n_pairs - 1)};
     for (int field = 0; field < 3; ++field) {
@@ -407,34 +366,18 @@ int wscales_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_
   return SFMLOC_OK;
 }
 
-int wscales_impl(int device, const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_intrinsic,
-                 const double *intrinsics, const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs,
-                 uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
-                 const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
-                 const uint8_t *use_pair, const sfmloc_wscales_options &opt, Wscales *w) {
+int wscales_impl(int device, const PairScene &sc, const PairPoses &po, const sfmloc_wscales_options &opt, Wscales *w) {
   wscales_host::ViewPairs vp;
   std::string err;
-  SFM_CHECK(n_pairs <= 0x3FFFFFFFu, SFMLOC_ECAP, "sfmloc_wedge_scales: %u pairs (at most 2^30 - 1)", n_pairs);
-  const int rc = wscales_host::check(view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
-                                     pairs, n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx,
-                                     use_pair, opt, &vp, &err);
+  const int rc = wscales_host::check(sc, po, opt, &vp, &err);
   SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
-  int rc_dev = CallScope::use_device(device);
-  if (rc_dev) return rc_dev;
-  g_wscales_last_ms = 0.0;
-  w->rep.n_pairs = n_pairs;
+  w->rep.n_pairs = sc.n_pairs;
   w->rep.n_pairs_used = vp.n_used;
   w->rep.n_inliers = vp.n_inliers;
-  if (n_pairs == 0) return SFMLOC_OK;  // nothing to launch
-  CallScope d;
-  if ((rc_dev = d.open(true, &g_wscales_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = wscales_device(view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics, pairs,
-                          n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx, use_pair, opt, vp, d.s,
-                          w);
-  if (rc_dev) return rc_dev;
-  rc_dev = d.time_end();
+  SFM_RC(timed_call(device, &g_wscales_last_ms, sc.n_pairs != 0,
+                    [&](hipStream_t s) { return wscales_device(sc, po, opt, vp, s, w); }));
   w->rep.device_ms = g_wscales_last_ms;
-  return rc_dev;
+  return SFMLOC_OK;
 }
 
 }  // namespace
@@ -456,27 +399,11 @@ int sfmloc_wedge_scales(int device, const uint64_t *view_off, uint32_t n_views, 
                         const uint32_t *match_i, const uint32_t *match_j, const double *rel_R, const double *rel_t,
                         const uint64_t *inlier_off, const uint32_t *inlier_idx, const uint8_t *use_pair,
                         const sfmloc_wscales_options *opt, sfmloc_wscales **out) {
-  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_wedge_scales: null argument");
-  *out = nullptr;
-  sfmloc_wscales_options o;
-  if (opt) o = *opt;
-  else sfmloc_wscales_default_options(&o);
-  Wscales *w = new (std::nothrow) Wscales();
-  SFM_CHECK(w, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = wscales_impl(device, view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics, pairs,
-                      n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx, use_pair, o, w);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_wedge_scales: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    delete w;
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_wscales *>(w);
-  return SFMLOC_OK;
+  const PairScene sc{view_off,     n_views, kpt_xy,  nullptr, view_intrinsic, intrinsics, intrinsic_type,
+                     n_intrinsics, pairs,   n_pairs, offsets, match_i,        match_j};
+  const PairPoses po{rel_R, rel_t, inlier_off, inlier_idx, use_pair};
+  const sfmloc_wscales_options o = options_or(opt, sfmloc_wscales_default_options);
+  return make_handle<Wscales>("sfmloc_wedge_scales", out, [&](Wscales *w) { return wscales_impl(device, sc, po, o, w); });
 }
 
 int sfmloc_wscales_count(const sfmloc_wscales *ww, uint32_t *n_wedges) {

@@ -1,10 +1,9 @@
-// The host side of sfmloc_wedge_scales (pairscales.hip): every check the call makes before anything is launched, the
-// per-view lists of pairs the kernels enumerate candidates from; and of sfmloc_global_poses_scaled (globalposes.hip): the
-// checks of its wedge list and the adjacency of the scale graph.  Host code only, no HIP: tests/cpp/pairscales_host.cpp
-// runs it under the host sanitizers.
+// The host side of sfmloc_wedge_scales (pairscales.hip): every check the call makes before anything is launched (the
+// scene's and the poses' are pair_scene.h's, the options' are here), the per-view lists of pairs the kernels enumerate
+// candidates from; and of sfmloc_global_poses_scaled (globalposes.hip): the checks of its wedge list and the adjacency
+// of the scale graph.  Host code only, no HIP: tests/cpp/pairscales_host.cpp runs it under the host sanitizers.
 #pragma once
 
-#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -13,7 +12,7 @@
 #include <vector>
 
 #include "../../include/sfmloc.h"
-#include "relpose_host.h"
+#include "pair_scene.h"
 
 namespace sfmloc {
 namespace wscales_host {
@@ -21,17 +20,8 @@ namespace wscales_host {
 constexpr uint32_t kWaveDegree = 64;       // a view of more used pairs than this is enumerated by a wave, not by a lane
 constexpr uint32_t kSideBit = 0x80000000u;  // in ViewPairs::ent: the view is the pair's J
 constexpr uint32_t kMaxShared = 2048;      // the ratios one workgroup sorts in LDS
-// inliers, candidates: every grid and block count the kernels derive from twice this number (two entries per inlier,
-// rounded up to a radix block of 1024) stays inside 32 bits
-constexpr uint64_t kMaxCount = 0x7FFFFC00ull;
-
-inline int fail(std::string *err, int code, const char *fmt, unsigned long long a = 0, unsigned long long b = 0,
-                unsigned long long c = 0) {
-  char buf[256];
-  snprintf(buf, sizeof buf, fmt, a, b, c);
-  *err = buf;
-  return code;
-}
+using pair_host::fail;
+using pair_host::kMaxCount;
 
 // sfmloc.h "candidates": the entries of view v are off[v] .. off[v + 1], the used pairs that name v ascending by pair
 // index, with kSideBit when v is the pair's J.  cand[v] = the candidates of the views before v (d (d - 1) / 2 each);
@@ -41,62 +31,27 @@ struct ViewPairs {
   uint32_t n_used = 0, n_inliers = 0;
 };
 
-// the checks of the results of sfmloc_relative_poses a later call takes again (rel_R, rel_t, inlier_off, inlier_idx),
-// shared with sfmloc_refine_relative_poses (relrefine_host.h); the pair list has passed relpose_host::check.  `name` is
-// the entry point the text speaks for.
-inline int check_inliers(const char *name, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
-                         const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
-                         std::string *err) {
-  const auto bad = [&](int code, const char *fmt, unsigned long long a = 0, unsigned long long b = 0,
-                       unsigned long long c = 0) {
-    fail(err, code, fmt, a, b, c);
-    *err = std::string(name) + ": " + *err;
-    return code;
-  };
-  if (n_pairs && (!rel_R || !rel_t || !inlier_off)) return bad(SFMLOC_EINVAL, "pose or inlier arrays missing");
-  if (n_pairs && inlier_off[0] != 0) return bad(SFMLOC_EINVAL, "inlier_off[0] must be 0");
-  for (uint32_t k = 0; k < n_pairs; ++k) {
-    const uint32_t a = pairs[2 * (size_t)k], b = pairs[2 * (size_t)k + 1];
-    if (inlier_off[k] > inlier_off[k + 1]) return bad(SFMLOC_EINVAL, "inlier_off not monotone at pair %llu", k);
-    const uint64_t n = inlier_off[k + 1] - inlier_off[k], m = offsets[k + 1] - offsets[k];
-    if (inlier_off[k + 1] > kMaxCount)
-      return bad(SFMLOC_ECAP, "%llu inliers up to pair %llu (at most 2^31 - 1024)", inlier_off[k + 1], k);
-    if (n && !inlier_idx) return bad(SFMLOC_EINVAL, "inlier_idx missing");
-    for (uint64_t p = 0; p < n; ++p)
-      if (inlier_idx[inlier_off[k] + p] >= m)
-        return bad(SFMLOC_EINVAL, "pair (%llu, %llu) inlier %llu out of range", a, b, p);
-    for (int i = 0; i < 12; ++i)
-      if (!isfinite(i < 9 ? rel_R[9 * (size_t)k + i] : rel_t[3 * (size_t)k + i - 9]))
-        return bad(SFMLOC_EINVAL, "pair (%llu, %llu) has a non-finite rel_R or rel_t", a, b);
-  }
-  return SFMLOC_OK;
-}
-
 // sfmloc.h "Refusals" -> SFMLOC_OK and the lists, or the code with its text in *err and *vp untouched
-inline int check(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_intrinsic,
-                 const double *intrinsics, const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs,
-                 uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
-                 const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
-                 const uint8_t *use_pair, const sfmloc_wscales_options &opt, ViewPairs *vp, std::string *err) {
-  std::vector<uint32_t> large;
-  uint32_t large_max_m = 0;
-  const int rc = relpose_host::check(view_off, n_views, kpt_xy, nullptr, view_intrinsic, intrinsics, intrinsic_type,
-                                     n_intrinsics, pairs, n_pairs, offsets, match_i, match_j, &large, &large_max_m, err,
-                                     "sfmloc_wedge_scales", false);
+inline int check(const PairScene &sc, const PairPoses &po, const sfmloc_wscales_options &opt, ViewPairs *vp,
+                 std::string *err) {
+  static const char *const name = "sfmloc_wedge_scales";
+  const uint32_t n_views = sc.n_views, n_pairs = sc.n_pairs;
+  if (n_pairs > 0x3FFFFFFFu) return fail(err, SFMLOC_ECAP, "sfmloc_wedge_scales: %llu pairs (at most 2^30 - 1)", n_pairs);
+  const int rc = pair_host::walk(name, sc, true, false, true, err);
   if (rc) return rc;
   if (opt.min_shared < 1) return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: min_shared = %llu (at least 1)", opt.min_shared);
   if (opt.max_shared < 1 || opt.max_shared > kMaxShared)
     return fail(err, SFMLOC_EINVAL, "sfmloc_wedge_scales: max_shared = %llu (1 to 2048)", opt.max_shared);
-  const int rc_inl = check_inliers("sfmloc_wedge_scales", pairs, n_pairs, offsets, rel_R, rel_t, inlier_off, inlier_idx, err);
+  const int rc_inl = pair_host::check_poses(name, sc, po, err);
   if (rc_inl) return rc_inl;
   std::vector<uint32_t> off((size_t)n_views + 1, 0);
   uint32_t n_used = 0;
   uint64_t n_inl = 0;
   for (uint32_t k = 0; k < n_pairs; ++k) {
-    const uint32_t a = pairs[2 * (size_t)k], b = pairs[2 * (size_t)k + 1];
-    if (use_pair && !use_pair[k]) continue;
+    const uint32_t a = sc.pairs[2 * (size_t)k], b = sc.pairs[2 * (size_t)k + 1];
+    if (po.use_pair && !po.use_pair[k]) continue;
     ++n_used;
-    n_inl += inlier_off[k + 1] - inlier_off[k];
+    n_inl += po.inlier_off[k + 1] - po.inlier_off[k];
     ++off[a + 1];
     ++off[b + 1];
   }
@@ -113,9 +68,9 @@ inline int check(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy
   }
   std::vector<uint32_t> ent(2 * (size_t)n_used), at(off.begin(), off.end() - 1);
   for (uint32_t k = 0; k < n_pairs; ++k) {  // (ascending k: every view's entries come out ascending)
-    if (use_pair && !use_pair[k]) continue;
-    ent[at[pairs[2 * (size_t)k]]++] = k;
-    ent[at[pairs[2 * (size_t)k + 1]]++] = k | kSideBit;
+    if (po.use_pair && !po.use_pair[k]) continue;
+    ent[at[sc.pairs[2 * (size_t)k]]++] = k;
+    ent[at[sc.pairs[2 * (size_t)k + 1]]++] = k | kSideBit;
   }
   vp->off.swap(off);
   vp->ent.swap(ent);

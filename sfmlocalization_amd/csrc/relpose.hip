@@ -1,7 +1,8 @@
 // sfmloc_relative_poses: the relative pose of every matched view pair (the first stage of openMVG_main_GlobalSfM): the
 // essential matrix by the five-point solver under AC-RANSAC, its decomposition, the cheirality count.  The semantics
 // are stated in include/sfmloc.h ("Relative poses"); tests/relpose_np.py restates every operation.  f64, only + - * /
-// sqrt, unfused (the library's -ffp-contract=off), every sum in a fixed order, no float atomics.
+// sqrt, unfused (the library's -ffp-contract=off), every sum in a fixed order, no float atomics.  The call's scene is a
+// PairScene on the host (pair_scene.h: its checks) and a PairDev on the device (twoview_device.h: its upload).
 //
 //   bearings    k_rp_bearings: (a, b, u, v) per match, once (the undistortion's bisection is the expensive part).
 //   pairs       k_relpose: one workgroup of 256 threads per pair, K3's block-wide AC-RANSAC loop (fmatrix_filter_view of
@@ -17,7 +18,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
@@ -46,16 +46,11 @@ struct Relpose {
   std::vector<uint32_t> idx;
 };
 
-struct RpArgs {
-  uint32_t n_pairs;
+struct RpArgs : PairDev {
   int n_iter;
   double precision;
   uint64_t seed;
-  const uint32_t *pairs;
-  const uint64_t *offsets;
   const double *bear;  // [match][4]: a, b (view I), u, v (view J)
-  const uint32_t *view_wh, *view_intr;
-  const double *intr;
   const double *L10;
   sfmloc_relpose_result *res;
   uint32_t *inl;
@@ -124,27 +119,13 @@ __global__ void k_rp_fill_log10(double *L10, int n) {
 }
 
 // sfmloc.h "bearings": one workgroup per pair walks the pair's matches
-__global__ __launch_bounds__(256) void k_rp_bearings(uint32_t n_pairs, const uint32_t *__restrict__ pairs,
-                                                     const uint64_t *__restrict__ offsets,
-                                                     const uint64_t *__restrict__ view_off,
-                                                     const float *__restrict__ kpt_xy,
-                                                     const uint32_t *__restrict__ match_i,
-                                                     const uint32_t *__restrict__ match_j,
-                                                     const uint32_t *__restrict__ view_intr,
-                                                     const uint32_t *__restrict__ intr_type,
-                                                     const double *__restrict__ intr, double *__restrict__ bear) {
+__global__ __launch_bounds__(256) void k_rp_bearings(PairDev D, double *__restrict__ bear) {
   const uint32_t k = blockIdx.x;
-  if (k >= n_pairs) return;
-  const uint32_t v[2] = {pairs[2 * (size_t)k], pairs[2 * (size_t)k + 1]};
-  for (uint64_t t = offsets[k] + threadIdx.x; t < offsets[k + 1]; t += 256) {
-#pragma unroll
-    for (int side = 0; side < 2; ++side) {
-      const uint32_t ii = view_intr[v[side]];
-      const double *K = intr + 6 * (size_t)ii;
-      const uint64_t row = view_off[v[side]] + (side ? match_j[t] : match_i[t]);
-      view_bearing(K, intr_type[ii], (double)kpt_xy[2 * row], (double)kpt_xy[2 * row + 1], &bear[4 * t + 2 * side],
-                   &bear[4 * t + 2 * side + 1]);
-    }
+  if (k >= D.n_pairs) return;
+  const ViewCam ci = view_cam(D, D.pairs[2 * (size_t)k]), cj = view_cam(D, D.pairs[2 * (size_t)k + 1]);
+  for (uint64_t t = D.offsets[k] + threadIdx.x; t < D.offsets[k + 1]; t += 256) {
+    feature_bearing(D, ci, D.match_i[t], &bear[4 * t], &bear[4 * t + 1]);
+    feature_bearing(D, cj, D.match_j[t], &bear[4 * t + 2], &bear[4 * t + 3]);
   }
 }
 
@@ -409,55 +390,30 @@ __global__ __launch_bounds__(64) void k_debug_five_point(const double *in, int n
   }
 }
 
-#define RP_TRY(call)         \
-  do {                       \
-    const int rc_ = (call);  \
-    if (rc_) return rc_;     \
-  } while (0)
-
-int relpose_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_wh,
-                   const uint32_t *view_intrinsic, const double *intrinsics, const uint32_t *intrinsic_type,
-                   uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
-                   const uint32_t *match_i, const uint32_t *match_j, const sfmloc_relpose_options &opt,
-                   const std::vector<uint32_t> &large, uint32_t large_max_m, hipStream_t s, Relpose *r) {
+int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const std::vector<uint32_t> &large,
+                   uint32_t large_max_m, hipStream_t s, Relpose *r) {
+  const uint32_t n_pairs = sc.n_pairs;
+  const uint64_t *offsets = sc.offsets;
   const uint64_t total = offsets[n_pairs];
-  DevBuf<uint64_t> d_view_off, d_offsets;
-  DevBuf<float> d_kpt;
-  DevBuf<uint32_t> d_wh, d_vintr, d_itype, d_pairs, d_mi, d_mj, d_inl, d_large;
-  DevBuf<double> d_intr, d_bear, d_L10;
+  PairSceneBufs scene;
+  DevBuf<uint32_t> d_inl, d_large;
+  DevBuf<double> d_bear, d_L10;
   DevBuf<sfmloc_relpose_result> d_res;
-  RP_TRY(dev_upload(nullptr, d_view_off, view_off, (size_t)n_views + 1, s));
-  RP_TRY(dev_upload(nullptr, d_kpt, kpt_xy, 2 * (size_t)view_off[n_views], s));
-  RP_TRY(dev_upload(nullptr, d_wh, view_wh, 2 * (size_t)n_views, s));
-  RP_TRY(dev_upload(nullptr, d_vintr, view_intrinsic, (size_t)n_views, s));
-  RP_TRY(dev_upload(nullptr, d_intr, intrinsics, 6 * (size_t)n_intrinsics, s));
-  RP_TRY(dev_upload(nullptr, d_itype, intrinsic_type, (size_t)n_intrinsics, s));
-  RP_TRY(dev_upload(nullptr, d_pairs, pairs, 2 * (size_t)n_pairs, s));
-  RP_TRY(dev_upload(nullptr, d_offsets, offsets, (size_t)n_pairs + 1, s));
-  RP_TRY(dev_upload(nullptr, d_mi, match_i, (size_t)total, s));
-  RP_TRY(dev_upload(nullptr, d_mj, match_j, (size_t)total, s));
-  RP_TRY(d_bear.alloc(nullptr, 4 * (size_t)total));
-  RP_TRY(d_inl.alloc(nullptr, (size_t)total));
-  RP_TRY(d_L10.alloc(nullptr, kRpL10));
-  RP_TRY(d_res.alloc(nullptr, n_pairs));
+  SFM_RC(scene.upload(sc, s));
+  SFM_RC(d_bear.alloc(nullptr, 4 * (size_t)total));
+  SFM_RC(d_inl.alloc(nullptr, (size_t)total));
+  SFM_RC(d_L10.alloc(nullptr, kRpL10));
+  SFM_RC(d_res.alloc(nullptr, n_pairs));
   SFM_HIP(hipMemsetAsync(d_res, 0, (size_t)n_pairs * sizeof(sfmloc_relpose_result), s));  // (the records' padding too)
   hipLaunchKernelGGL(k_rp_fill_log10, dim3((kRpL10 + 255) / 256), dim3(256), 0, s, d_L10.get(), kRpL10);
-  hipLaunchKernelGGL(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, n_pairs, (const uint32_t *)d_pairs,
-                     (const uint64_t *)d_offsets, (const uint64_t *)d_view_off, (const float *)d_kpt,
-                     (const uint32_t *)d_mi, (const uint32_t *)d_mj, (const uint32_t *)d_vintr, (const uint32_t *)d_itype,
-                     (const double *)d_intr, d_bear.get());
+  hipLaunchKernelGGL(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, scene.dev(), d_bear.get());
   SFM_HIP(hipGetLastError());
-  RpArgs A;
-  A.n_pairs = n_pairs;
+  RpArgs A{};
+  static_cast<PairDev &>(A) = scene.dev();
   A.n_iter = (int)opt.max_iteration;
   A.precision = opt.precision_px;
   A.seed = opt.seed;
-  A.pairs = d_pairs;
-  A.offsets = d_offsets;
   A.bear = d_bear;
-  A.view_wh = d_wh;
-  A.view_intr = d_vintr;
-  A.intr = d_intr;
   A.L10 = d_L10;
   A.res = d_res;
   A.inl = d_inl;
@@ -474,13 +430,13 @@ int relpose_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_
     int slot_m = 2 * kRpLdsMaxM;
     while (slot_m < (int)large_max_m) slot_m <<= 1;
     const size_t n_slots = large.size() < (size_t)kRpLargeSlots ? large.size() : (size_t)kRpLargeSlots;
-    RP_TRY(dev_upload(nullptr, d_large, large.data(), large.size(), s));
-    RP_TRY(d_key.alloc(nullptr, n_slots * slot_m));
-    RP_TRY(d_idx.alloc(nullptr, n_slots * slot_m));
-    RP_TRY(d_vi.alloc(nullptr, n_slots * slot_m));
-    RP_TRY(d_bi.alloc(nullptr, n_slots * slot_m));
-    RP_TRY(d_ln.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
-    RP_TRY(d_lk.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
+    SFM_RC(dev_upload(nullptr, d_large, large.data(), large.size(), s));
+    SFM_RC(d_key.alloc(nullptr, n_slots * slot_m));
+    SFM_RC(d_idx.alloc(nullptr, n_slots * slot_m));
+    SFM_RC(d_vi.alloc(nullptr, n_slots * slot_m));
+    SFM_RC(d_bi.alloc(nullptr, n_slots * slot_m));
+    SFM_RC(d_ln.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
+    SFM_RC(d_lk.alloc(nullptr, n_slots * ((size_t)slot_m + 1)));
     RpLargeArgs W;
     W.list = d_large;
     W.n = (uint32_t)large.size();
@@ -508,30 +464,17 @@ int relpose_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_
   return SFMLOC_OK;
 }
 
-int relpose_impl(int device, const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_wh,
-                 const uint32_t *view_intrinsic, const double *intrinsics, const uint32_t *intrinsic_type,
-                 uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
-                 const uint32_t *match_i, const uint32_t *match_j, const sfmloc_relpose_options &opt, Relpose *r) {
+int relpose_impl(int device, const PairScene &sc, const sfmloc_relpose_options &opt, Relpose *r) {
+  std::string err;
+  const int rc = relpose_host::check(sc, opt, &err);
+  SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
   std::vector<uint32_t> large;
   uint32_t large_max_m = 0;
-  std::string err;
-  const int rc = relpose_host::check(view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type,
-                                     n_intrinsics, pairs, n_pairs, offsets, match_i, match_j, &large, &large_max_m, &err);
-  SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
-  SFM_CHECK(opt.max_iteration <= (1u << 30), SFMLOC_EINVAL, "sfmloc_relative_poses: max_iteration = %u", opt.max_iteration);
-  SFM_CHECK(!(opt.precision_px < 0.0) && opt.precision_px == opt.precision_px, SFMLOC_EINVAL,
-            "sfmloc_relative_poses: precision_px must not be negative");
-  int rc_dev = CallScope::use_device(device);
-  if (rc_dev) return rc_dev;
-  g_relpose_last_ms = 0.0;
-  r->res.assign(n_pairs, sfmloc_relpose_result{});
-  r->off.assign((size_t)n_pairs + 1, 0);
-  if (n_pairs == 0) return SFMLOC_OK;  // nothing to launch
-  CallScope d;
-  if ((rc_dev = d.open(true, &g_relpose_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = relpose_device(view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
-                          pairs, n_pairs, offsets, match_i, match_j, opt, large, large_max_m, d.s, r);
-  return rc_dev ? rc_dev : d.time_end();
+  relpose_host::split_large(sc, &large, &large_max_m);
+  r->res.assign(sc.n_pairs, sfmloc_relpose_result{});
+  r->off.assign((size_t)sc.n_pairs + 1, 0);
+  return timed_call(device, &g_relpose_last_ms, sc.n_pairs != 0,
+                    [&](hipStream_t s) { return relpose_device(sc, opt, large, large_max_m, s, r); });
 }
 
 }  // namespace
@@ -554,27 +497,10 @@ int sfmloc_relative_poses(int device, const uint64_t *view_off, uint32_t n_views
                           const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs,
                           const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
                           const sfmloc_relpose_options *opt, sfmloc_relpose **out) {
-  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_relative_poses: null argument");
-  *out = nullptr;
-  sfmloc_relpose_options o;
-  if (opt) o = *opt;
-  else sfmloc_relpose_default_options(&o);
-  Relpose *r = new (std::nothrow) Relpose();
-  SFM_CHECK(r, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = relpose_impl(device, view_off, n_views, kpt_xy, view_wh, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
-                      pairs, n_pairs, offsets, match_i, match_j, o, r);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_relative_poses: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    delete r;
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_relpose *>(r);
-  return SFMLOC_OK;
+  const PairScene sc{view_off,     n_views, kpt_xy,  view_wh, view_intrinsic, intrinsics, intrinsic_type,
+                     n_intrinsics, pairs,   n_pairs, offsets, match_i,        match_j};
+  const sfmloc_relpose_options o = options_or(opt, sfmloc_relpose_default_options);
+  return make_handle<Relpose>("sfmloc_relative_poses", out, [&](Relpose *r) { return relpose_impl(device, sc, o, r); });
 }
 
 int sfmloc_relpose_results(const sfmloc_relpose *rr, sfmloc_relpose_result *out) {

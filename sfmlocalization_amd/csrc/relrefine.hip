@@ -1,7 +1,8 @@
 // sfmloc_refine_relative_poses: the two-view adjustment of every relative pose on its inliers (what OpenMVG does to a
 // pair before it averages).  The semantics are stated in include/sfmloc.h ("Two-view refinement");
 // tests/relrefine_np.py restates every operation.  f64, unfused (the library's -ffp-contract=off), only + - * / sqrt,
-// every sum in a fixed order, no float atomics: the records are the restatement's bits.
+// every sum in a fixed order, no float atomics: the records are the restatement's bits.  Scene and poses: PairScene and
+// PairPoses on the host (pair_scene.h), PairDev and PairPosesDev on the device (twoview_device.h), the bases of RrDev.
 //
 //   k_relrefine   one workgroup of 256 threads per pair, the whole Levenberg-Marquardt loop inside the kernel.  Lane l
 //                 owns the inliers l, l + 256, ... from the triangulation to the end: nobody reads a point another
@@ -18,7 +19,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
@@ -39,16 +39,13 @@ struct Relrefine {
   std::vector<sfmloc_relrefine_result> res;
 };
 
-struct RrDev {
-  uint32_t n_pairs, max_steps, min_points;
-  const uint64_t *view_off, *offsets, *inl_off;
-  const float *kpt;
-  const uint32_t *view_intr, *intr_type, *pairs, *match_i, *match_j, *inl_idx;
-  const double *intr, *relR, *relt;
-  const uint8_t *use;
+struct RrDev : PairDev, PairPosesDev {
   double *bear;         // [4][n] per pair at 4 inl_off[k]: a, b (view I), u, v (view J)
   double *pts, *trial;  // [3][n] per pair at 3 inl_off[k]; X_2 = 0 marks an inlier that is not used
   sfmloc_relrefine_result *res;
+  // (behind the pointers: the kernel sits at the register limit, and with these two between the bases and the
+  // pointers it measured 1 % slower -- profiles/pair_scene_time.json)
+  uint32_t max_steps, min_points;
 };
 
 // sfmloc.h "reduction": v[k] over the workgroup, the same bits in every thread.  sh [N][4].
@@ -267,21 +264,18 @@ __global__ __launch_bounds__(kRrThreads) void k_relrefine(RrDev D) {
   double c0 = 0.0, c = 0.0;
   if (D.use[k]) {  // (the same in every thread of the workgroup, as every branch on the way to a barrier below)
     const uint32_t vi = D.pairs[2 * (size_t)k], vj = D.pairs[2 * (size_t)k + 1];
-    const uint32_t ii = D.view_intr[vi], ij = D.view_intr[vj];
-    const double *Ki = D.intr + 6 * (size_t)ii, *Kj = D.intr + 6 * (size_t)ij;
-    const uint32_t ti = D.intr_type[ii], tj = D.intr_type[ij];
-    const double fi = Ki[0], fj = Kj[0];
-    const uint64_t m0 = D.offsets[k], ri = D.view_off[vi], rj = D.view_off[vj];
+    const ViewCam ci = view_cam(D, vi), cj = view_cam(D, vj);
+    const double fi = ci.K[0], fj = cj.K[0];
+    const uint64_t m0 = D.offsets[k];
     if (tid == 0) s_used = 0;
     __syncthreads();
     // sfmloc.h "bearings", "points"
     uint32_t mine = 0;
     for (size_t p = tid; p < n; p += kRrThreads) {
       const uint64_t mt = m0 + D.inl_idx[i0 + p];
-      const uint64_t rowi = ri + D.match_i[mt], rowj = rj + D.match_j[mt];
       double b[4], P[3], zi, zj;
-      view_bearing(Ki, ti, (double)D.kpt[2 * rowi], (double)D.kpt[2 * rowi + 1], &b[0], &b[1]);
-      view_bearing(Kj, tj, (double)D.kpt[2 * rowj], (double)D.kpt[2 * rowj + 1], &b[2], &b[3]);
+      feature_bearing(D, ci, D.match_i[mt], &b[0], &b[1]);
+      feature_bearing(D, cj, D.match_j[mt], &b[2], &b[3]);
       const bool ok =
           two_view_point(R, t, b[0], b[1], b[2], b[3], P, &zi, &zj) && geom::is_finite(zj) && zi > 0.0 && zj > 0.0;
 #pragma unroll
@@ -419,82 +413,40 @@ __global__ __launch_bounds__(kRrThreads) void k_relrefine(RrDev D) {
   }
 }
 
-#define RR_TRY(call)        \
-  do {                      \
-    const int rc_ = (call); \
-    if (rc_) return rc_;    \
-  } while (0)
-
-int relrefine_device(const uint64_t *view_off, uint32_t n_views, const float *kpt_xy, const uint32_t *view_intrinsic,
-                     const double *intrinsics, const uint32_t *intrinsic_type, uint32_t n_intrinsics, const uint32_t *pairs,
-                     uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i, const uint32_t *match_j,
-                     const double *rel_R, const double *rel_t, const uint64_t *inlier_off, const uint32_t *inlier_idx,
-                     const uint8_t *use_pair, const sfmloc_relrefine_options &opt, hipStream_t s, Relrefine *r) {
-  const size_t P = n_pairs, n = n_views, n_inl = (size_t)inlier_off[n_pairs];
-  std::vector<uint8_t> use(P, 1);
-  if (use_pair)
-    for (size_t k = 0; k < P; ++k) use[k] = use_pair[k] ? 1 : 0;
-  DevBuf<uint64_t> d_view_off, d_offsets, d_inl_off;
-  DevBuf<float> d_kpt;
-  DevBuf<uint32_t> d_vintr, d_itype, d_pairs, d_mi, d_mj, d_inl;
-  DevBuf<double> d_intr, d_relR, d_relt, d_bear, d_pts, d_trial;
-  DevBuf<uint8_t> d_use;
+int relrefine_device(const PairScene &sc, const PairPoses &po, const sfmloc_relrefine_options &opt, hipStream_t s,
+                     Relrefine *r) {
+  const size_t P = sc.n_pairs, n_inl = (size_t)po.inlier_off[P];
+  PairSceneBufs scene;
+  PairPosesBufs poses;
+  DevBuf<double> d_bear, d_pts, d_trial;
   DevBuf<sfmloc_relrefine_result> d_res;
-  RR_TRY(dev_upload(nullptr, d_view_off, view_off, n + 1, s));
-  RR_TRY(dev_upload(nullptr, d_kpt, kpt_xy, 2 * (size_t)view_off[n_views], s));
-  RR_TRY(dev_upload(nullptr, d_vintr, view_intrinsic, n, s));
-  RR_TRY(dev_upload(nullptr, d_intr, intrinsics, 6 * (size_t)n_intrinsics, s));
-  RR_TRY(dev_upload(nullptr, d_itype, intrinsic_type, (size_t)n_intrinsics, s));
-  RR_TRY(dev_upload(nullptr, d_pairs, pairs, 2 * P, s));
-  RR_TRY(dev_upload(nullptr, d_offsets, offsets, P + 1, s));
-  RR_TRY(dev_upload(nullptr, d_mi, match_i, (size_t)offsets[n_pairs], s));
-  RR_TRY(dev_upload(nullptr, d_mj, match_j, (size_t)offsets[n_pairs], s));
-  RR_TRY(dev_upload(nullptr, d_relR, rel_R, 9 * P, s));
-  RR_TRY(dev_upload(nullptr, d_relt, rel_t, 3 * P, s));
-  RR_TRY(dev_upload(nullptr, d_inl_off, inlier_off, P + 1, s));
-  RR_TRY(dev_upload(nullptr, d_inl, inlier_idx, n_inl, s));
-  RR_TRY(dev_upload(nullptr, d_use, use.data(), P, s));
-  RR_TRY(d_bear.alloc(nullptr, 4 * n_inl));
-  RR_TRY(d_pts.alloc(nullptr, 3 * n_inl));
-  RR_TRY(d_trial.alloc(nullptr, 3 * n_inl));
-  RR_TRY(d_res.alloc(nullptr, P));
+  SFM_RC(scene.upload(sc, s));
+  SFM_RC(poses.upload(sc, po, s));
+  SFM_RC(d_bear.alloc(nullptr, 4 * n_inl));
+  SFM_RC(d_pts.alloc(nullptr, 3 * n_inl));
+  SFM_RC(d_trial.alloc(nullptr, 3 * n_inl));
+  SFM_RC(d_res.alloc(nullptr, P));
   SFM_HIP(hipMemsetAsync(d_res, 0, P * sizeof(sfmloc_relrefine_result), s));
-  RrDev D;
-  memset(&D, 0, sizeof D);
-  D.n_pairs = n_pairs;
+  RrDev D{};
+  static_cast<PairDev &>(D) = scene.dev();
+  static_cast<PairPosesDev &>(D) = poses.dev();
   D.max_steps = opt.max_steps;
   D.min_points = opt.min_points;
-  D.view_off = d_view_off, D.offsets = d_offsets, D.inl_off = d_inl_off, D.kpt = d_kpt, D.view_intr = d_vintr;
-  D.intr_type = d_itype, D.pairs = d_pairs, D.match_i = d_mi, D.match_j = d_mj, D.inl_idx = d_inl, D.intr = d_intr;
-  D.relR = d_relR, D.relt = d_relt, D.use = d_use, D.bear = d_bear, D.pts = d_pts, D.trial = d_trial, D.res = d_res;
-  hipLaunchKernelGGL(k_relrefine, dim3(n_pairs), dim3(kRrThreads), 0, s, D);
+  D.bear = d_bear, D.pts = d_pts, D.trial = d_trial, D.res = d_res;
+  hipLaunchKernelGGL(k_relrefine, dim3(sc.n_pairs), dim3(kRrThreads), 0, s, D);
   SFM_HIP(hipGetLastError());
   SFM_HIP(hipMemcpyAsync(r->res.data(), d_res, P * sizeof(sfmloc_relrefine_result), hipMemcpyDeviceToHost, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
 
-int relrefine_impl(int device, const uint64_t *view_off, uint32_t n_views, const float *kpt_xy,
-                   const uint32_t *view_intrinsic, const double *intrinsics, const uint32_t *intrinsic_type,
-                   uint32_t n_intrinsics, const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
-                   const uint32_t *match_i, const uint32_t *match_j, const double *rel_R, const double *rel_t,
-                   const uint64_t *inlier_off, const uint32_t *inlier_idx, const uint8_t *use_pair,
-                   const sfmloc_relrefine_options &opt, Relrefine *r) {
+int relrefine_impl(int device, const PairScene &sc, const PairPoses &po, const sfmloc_relrefine_options &opt, Relrefine *r) {
   std::string err;
-  const int rc = relrefine_host::check(view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics,
-                                       pairs, n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx, opt,
-                                       &err);
+  const int rc = relrefine_host::check(sc, po, opt, &err);
   SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
-  int rc_dev = CallScope::use_device(device);
-  if (rc_dev) return rc_dev;
-  g_relrefine_last_ms = 0.0;
-  r->res.assign(n_pairs, sfmloc_relrefine_result{});
-  if (n_pairs == 0) return SFMLOC_OK;  // nothing to launch
-  CallScope d;
-  if ((rc_dev = d.open(true, &g_relrefine_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = relrefine_device(view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics, pairs,
-                            n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx, use_pair, opt, d.s, r);
-  return rc_dev ? rc_dev : d.time_end();
+  r->res.assign(sc.n_pairs, sfmloc_relrefine_result{});
+  return timed_call(device, &g_relrefine_last_ms, sc.n_pairs != 0,
+                    [&](hipStream_t s) { return relrefine_device(sc, po, opt, s, r); });
 }
 
 }  // namespace
@@ -516,27 +468,12 @@ int sfmloc_refine_relative_poses(int device, const uint64_t *view_off, uint32_t 
                                  const uint32_t *match_i, const uint32_t *match_j, const double *rel_R, const double *rel_t,
                                  const uint64_t *inlier_off, const uint32_t *inlier_idx, const uint8_t *use_pair,
                                  const sfmloc_relrefine_options *opt, sfmloc_relrefine **out) {
-  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_refine_relative_poses: null argument");
-  *out = nullptr;
-  sfmloc_relrefine_options o;
-  if (opt) o = *opt;
-  else sfmloc_relrefine_default_options(&o);
-  Relrefine *r = new (std::nothrow) Relrefine();
-  SFM_CHECK(r, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = relrefine_impl(device, view_off, n_views, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, n_intrinsics, pairs,
-                        n_pairs, offsets, match_i, match_j, rel_R, rel_t, inlier_off, inlier_idx, use_pair, o, r);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_refine_relative_poses: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    delete r;
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_relrefine *>(r);
-  return SFMLOC_OK;
+  const PairScene sc{view_off,     n_views, kpt_xy,  nullptr, view_intrinsic, intrinsics, intrinsic_type,
+                     n_intrinsics, pairs,   n_pairs, offsets, match_i,        match_j};
+  const PairPoses po{rel_R, rel_t, inlier_off, inlier_idx, use_pair};
+  const sfmloc_relrefine_options o = options_or(opt, sfmloc_relrefine_default_options);
+  return make_handle<Relrefine>("sfmloc_refine_relative_poses", out,
+                                [&](Relrefine *r) { return relrefine_impl(device, sc, po, o, r); });
 }
 
 int sfmloc_relrefine_results(const sfmloc_relrefine *rr, sfmloc_relrefine_result *out) {

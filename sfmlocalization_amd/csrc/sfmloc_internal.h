@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <new>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string>
@@ -45,6 +46,46 @@ inline int env_int(const char *name, int dflt) {
       return (code);                   \
     }                                  \
   } while (0)
+
+// a step that answers an SFMLOC code: on anything but SFMLOC_OK the function returns it
+#define SFM_RC(call)        \
+  do {                      \
+    const int rc_ = (call); \
+    if (rc_) return rc_;    \
+  } while (0)
+
+// The shell of an entry point that hands out a fresh handle: `fill` fills a new host-side Handle and answers an SFMLOC
+// code; *out is the handle on SFMLOC_OK and null otherwise, and no exception crosses the C ABI.  `name`: the entry
+// point the texts speak for.
+template <class Handle, class Opaque, class Fill>
+inline int make_handle(const char *name, Opaque **out, Fill &&fill) {
+  SFM_CHECK(out, SFMLOC_EINVAL, "%s: null argument", name);
+  *out = nullptr;
+  Handle *h = new (std::nothrow) Handle();
+  SFM_CHECK(h, SFMLOC_ENOMEM, "out of host memory");
+  int rc;
+  try {
+    rc = fill(h);
+  } catch (const std::bad_alloc &) {
+    set_error("%s: out of host memory", name);
+    rc = SFMLOC_ENOMEM;
+  }
+  if (rc) {
+    delete h;
+    return rc;
+  }
+  *out = reinterpret_cast<Opaque *>(h);
+  return SFMLOC_OK;
+}
+
+// the caller's options, or the entry point's defaults where it passed none
+template <class Options>
+inline Options options_or(const Options *opt, void (*defaults)(Options *)) {
+  Options o;
+  if (opt) o = *opt;
+  else defaults(&o);
+  return o;
+}
 
 // ---------------------------------------------------------------------------
 // HBM layout of the descriptor bank ("tiled64").
@@ -199,6 +240,20 @@ struct CallScope {
   bool own_ = false;
   double *ms_ = nullptr;
 };
+
+// The timed part of a one-shot call on `device`: *last_ms is zeroed; with `work`, body(stream) runs between the two
+// events of a stream of its own and *last_ms is their distance.  The body's DevBufs go before the stream does.
+template <class Body>
+inline int timed_call(int device, double *last_ms, bool work, Body &&body) {
+  SFM_RC(CallScope::use_device(device));
+  *last_ms = 0.0;
+  if (!work) return SFMLOC_OK;  // nothing to launch
+  CallScope d;
+  SFM_RC(d.open(true, last_ms));
+  SFM_RC(d.time_begin());
+  SFM_RC(body(d.s));
+  return d.time_end();
+}
 
 struct Ctx;
 

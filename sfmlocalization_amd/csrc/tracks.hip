@@ -14,7 +14,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <new>
 #include <string>
 #include <vector>
 
@@ -171,26 +170,19 @@ int read_u32(uint32_t *out, const uint32_t *d, hipStream_t s) {
   return SFMLOC_OK;
 }
 
-#define TRK_TRY(x)      \
-  do {                  \
-    const int rc_ = (x); \
-    if (rc_) return rc_; \
-  } while (0)
-
-int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint32_t n, const std::vector<uint32_t> &ea,
+int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, const std::vector<uint32_t> &ea,
                   const std::vector<uint32_t> &eb, uint32_t min_length, hipStream_t s, Tracks *t) {
-  (void)device;
   const uint32_t m_edges = (uint32_t)ea.size();
   std::vector<uint32_t> voff((size_t)n_views + 1);
   for (uint32_t v = 0; v <= n_views; ++v) voff[v] = (uint32_t)view_off64[v];
   DevBuf<uint32_t> d_voff, d_ea, d_eb, d_parent, d_touched, d_sums, d_flag;
-  TRK_TRY(d_voff.alloc(nullptr, voff.size()));
-  TRK_TRY(d_ea.alloc(nullptr, m_edges));
-  TRK_TRY(d_eb.alloc(nullptr, m_edges));
-  TRK_TRY(d_parent.alloc(nullptr, n));
-  TRK_TRY(d_touched.alloc(nullptr, (size_t)n + 1));
-  TRK_TRY(d_sums.alloc(nullptr, (size_t)n / 1024 + 2));
-  TRK_TRY(d_flag.alloc(nullptr, 4));  // changed, then the three counts of the filter
+  SFM_RC(d_voff.alloc(nullptr, voff.size()));
+  SFM_RC(d_ea.alloc(nullptr, m_edges));
+  SFM_RC(d_eb.alloc(nullptr, m_edges));
+  SFM_RC(d_parent.alloc(nullptr, n));
+  SFM_RC(d_touched.alloc(nullptr, (size_t)n + 1));
+  SFM_RC(d_sums.alloc(nullptr, (size_t)n / 1024 + 2));
+  SFM_RC(d_flag.alloc(nullptr, 4));  // changed, then the three counts of the filter
   SFM_HIP(hipMemcpyAsync(d_voff, voff.data(), voff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   SFM_HIP(hipMemcpyAsync(d_ea, ea.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   SFM_HIP(hipMemcpyAsync(d_eb, eb.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -205,22 +197,22 @@ int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint
     hipLaunchKernelGGL(k_graph_jump, gn, b256, 0, s, d_parent.get(), n);
     SFM_HIP(hipGetLastError());
     uint32_t changed = 0;
-    TRK_TRY(read_u32(&changed, d_flag, s));
+    SFM_RC(read_u32(&changed, d_flag, s));
     if (!changed) break;
   }
   d_ea.reset();
   d_eb.reset();
   // the touched rows, ascending, with their labels
-  TRK_TRY(scan_excl(d_touched, n + 1, d_sums, s));
+  SFM_RC(scan_excl(d_touched, n + 1, d_sums, s));
   uint32_t m = 0;
-  TRK_TRY(read_u32(&m, d_touched.get() + n, s));
+  SFM_RC(read_u32(&m, d_touched.get() + n, s));
   DevBuf<uint32_t> d_key, d_node, d_key2, d_node2, d_hist, d_ex;
-  TRK_TRY(d_key.alloc(nullptr, m));
-  TRK_TRY(d_node.alloc(nullptr, m));
-  TRK_TRY(d_key2.alloc(nullptr, m));
-  TRK_TRY(d_node2.alloc(nullptr, m));
-  TRK_TRY(d_hist.alloc(nullptr, radix_hist_entries(m)));
-  TRK_TRY(d_ex.alloc(nullptr, (size_t)m + 1));
+  SFM_RC(d_key.alloc(nullptr, m));
+  SFM_RC(d_node.alloc(nullptr, m));
+  SFM_RC(d_key2.alloc(nullptr, m));
+  SFM_RC(d_node2.alloc(nullptr, m));
+  SFM_RC(d_hist.alloc(nullptr, radix_hist_entries(m)));
+  SFM_RC(d_ex.alloc(nullptr, (size_t)m + 1));
   hipLaunchKernelGGL(k_trk_compact, gn, b256, 0, s, (const uint32_t *)d_touched, (const uint32_t *)d_parent, n,
                      d_key.get(), d_node.get());
   SFM_HIP(hipGetLastError());
@@ -231,16 +223,16 @@ int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint
   const dim3 gm((m + 1 + 255) / 256);
   hipLaunchKernelGGL(k_trk_heads, gm, b256, 0, s, key, m, d_ex.get());
   SFM_HIP(hipGetLastError());
-  TRK_TRY(scan_excl(d_ex, m + 1, d_sums, s));
+  SFM_RC(scan_excl(d_ex, m + 1, d_sums, s));
   uint32_t n_comp = 0;
-  TRK_TRY(read_u32(&n_comp, d_ex.get() + m, s));
+  SFM_RC(read_u32(&n_comp, d_ex.get() + m, s));
   d_parent.reset();
   d_touched.reset();
   DevBuf<uint32_t> d_start, d_conf, d_tid, d_toff;
-  TRK_TRY(d_start.alloc(nullptr, (size_t)n_comp + 1));
-  TRK_TRY(d_conf.alloc(nullptr, n_comp));
-  TRK_TRY(d_tid.alloc(nullptr, (size_t)n_comp + 1));
-  TRK_TRY(d_toff.alloc(nullptr, (size_t)n_comp + 1));
+  SFM_RC(d_start.alloc(nullptr, (size_t)n_comp + 1));
+  SFM_RC(d_conf.alloc(nullptr, n_comp));
+  SFM_RC(d_tid.alloc(nullptr, (size_t)n_comp + 1));
+  SFM_RC(d_toff.alloc(nullptr, (size_t)n_comp + 1));
   SFM_HIP(hipMemsetAsync(d_conf, 0, (size_t)n_comp * sizeof(uint32_t), s));
   SFM_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(uint32_t), s));
   hipLaunchKernelGGL(k_trk_components, gm, b256, 0, s, key, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_voff,
@@ -248,16 +240,16 @@ int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint
   hipLaunchKernelGGL(k_trk_filter, dim3((n_comp + 1 + 255) / 256), b256, 0, s, (const uint32_t *)d_start,
                      (const uint32_t *)d_conf, n_comp, min_length, d_tid.get(), d_toff.get(), d_flag.get() + 1);
   SFM_HIP(hipGetLastError());
-  TRK_TRY(scan_excl(d_tid, n_comp + 1, d_sums, s));
-  TRK_TRY(scan_excl(d_toff, n_comp + 1, d_sums, s));
+  SFM_RC(scan_excl(d_tid, n_comp + 1, d_sums, s));
+  SFM_RC(scan_excl(d_toff, n_comp + 1, d_sums, s));
   uint32_t n_tracks = 0, n_rows = 0, cnt[4] = {0, 0, 0, 0};
   SFM_HIP(hipMemcpyAsync(cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, s));
-  TRK_TRY(read_u32(&n_tracks, d_tid.get() + n_comp, s));
-  TRK_TRY(read_u32(&n_rows, d_toff.get() + n_comp, s));
+  SFM_RC(read_u32(&n_tracks, d_tid.get() + n_comp, s));
+  SFM_RC(read_u32(&n_rows, d_toff.get() + n_comp, s));
   DevBuf<uint32_t> d_off, d_view, d_feat;
-  TRK_TRY(d_off.alloc(nullptr, n_tracks));
-  TRK_TRY(d_view.alloc(nullptr, n_rows));
-  TRK_TRY(d_feat.alloc(nullptr, n_rows));
+  SFM_RC(d_off.alloc(nullptr, n_tracks));
+  SFM_RC(d_view.alloc(nullptr, n_rows));
+  SFM_RC(d_feat.alloc(nullptr, n_rows));
   hipLaunchKernelGGL(k_trk_emit, gm, b256, 0, s, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_start,
                      (const uint32_t *)d_tid, (const uint32_t *)d_toff, (const uint32_t *)d_voff, n_views, d_off.get(),
                      d_view.get(), d_feat.get());
@@ -280,24 +272,17 @@ int tracks_device(int device, const uint64_t *view_off64, uint32_t n_views, uint
   return SFMLOC_OK;
 }
 
-int tracks_build_impl(int device, const uint64_t *view_off, uint32_t n_views, const uint8_t *view_use,
-                      const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i,
-                      const uint32_t *match_j, uint32_t min_length, Tracks *t) {
+int tracks_build_impl(int device, const PairScene &sc, const uint8_t *view_use, uint32_t min_length, Tracks *t) {
   std::vector<uint32_t> ea, eb;
   uint64_t n_nodes = 0;
   std::string err;
-  const int rc = tracks_host::flatten(view_off, n_views, view_use, pairs, n_pairs, offsets, match_i, match_j, &ea, &eb,
-                                      &n_nodes, &err);
+  const int rc = tracks_host::flatten(sc, view_use, &ea, &eb, &n_nodes, &err);
   SFM_CHECK(rc == SFMLOC_OK, rc, "%s", err.c_str());
-  int rc_dev = CallScope::use_device(device);
-  if (rc_dev) return rc_dev;
-  g_tracks_last_ms = 0.0;
   t->off.assign(1, 0);
-  if (ea.empty() || n_nodes == 0) return SFMLOC_OK;  // no match: no track, nothing to launch
-  CallScope d;
-  if ((rc_dev = d.open(true, &g_tracks_last_ms)) || (rc_dev = d.time_begin())) return rc_dev;
-  rc_dev = tracks_device(device, view_off, n_views, (uint32_t)n_nodes, ea, eb, min_length < 1 ? 1 : min_length, d.s, t);
-  return rc_dev ? rc_dev : d.time_end();
+  // (no match: no track, nothing to launch)
+  return timed_call(device, &g_tracks_last_ms, !ea.empty() && n_nodes != 0, [&](hipStream_t s) {
+    return tracks_device(sc.view_off, sc.n_views, (uint32_t)n_nodes, ea, eb, min_length < 1 ? 1 : min_length, s, t);
+  });
 }
 
 }  // namespace
@@ -310,23 +295,11 @@ extern "C" {
 int sfmloc_tracks_build(int device, const uint64_t *view_off, uint32_t n_views, const uint8_t *view_use,
                         const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets, const uint32_t *match_i,
                         const uint32_t *match_j, uint32_t min_length, sfmloc_tracks **out) {
-  SFM_CHECK(out, SFMLOC_EINVAL, "sfmloc_tracks_build: null argument");
-  *out = nullptr;
-  Tracks *t = new (std::nothrow) Tracks();
-  SFM_CHECK(t, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = tracks_build_impl(device, view_off, n_views, view_use, pairs, n_pairs, offsets, match_i, match_j, min_length, t);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_tracks_build: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    delete t;
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_tracks *>(t);
-  return SFMLOC_OK;
+  PairScene sc{};  // (the views' offsets and the pair list: tracks know nothing of the cameras)
+  sc.view_off = view_off, sc.n_views = n_views, sc.pairs = pairs, sc.n_pairs = n_pairs, sc.offsets = offsets;
+  sc.match_i = match_i, sc.match_j = match_j;
+  return make_handle<Tracks>("sfmloc_tracks_build", out,
+                             [&](Tracks *t) { return tracks_build_impl(device, sc, view_use, min_length, t); });
 }
 
 int sfmloc_tracks_counts(const sfmloc_tracks *tt, uint64_t *counts) {

@@ -10,6 +10,8 @@
 #include "../../sfmlocalization_amd/csrc/pairscales_host.h"
 
 using namespace sfmloc::wscales_host;
+using sfmloc::PairPoses;
+using sfmloc::PairScene;
 
 static int g_fail = 0;
 #define EXPECT(c)                                        \
@@ -52,11 +54,17 @@ struct Case {
     t.assign(3 * P, 0.0);
     for (size_t k = 0; k < P; ++k) R[9 * k] = R[9 * k + 4] = R[9 * k + 8] = t[3 * k] = 1.0;
   }
-  int run() {
-    return check(view_off.data(), n_views, kpt.data(), view_intr.data(), intr.data(), itype.data(), 1, pairs.data(),
-                 (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(), mj.data(), R.data(), t.data(), inl_off.data(),
-                 inl.data(), use.empty() ? nullptr : use.data(), opt, &vp, &err);
+  PairScene scene() const {
+    return PairScene{view_off.data(), n_views,      kpt.data(), nullptr,
+                     view_intr.data(), intr.data(), itype.data(), 1,
+                     pairs.data(),    (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(),
+                     mj.data()};
   }
+  PairPoses poses() const {
+    return PairPoses{R.data(), t.data(), inl_off.data(), inl.data(), use.empty() ? nullptr : use.data()};
+  }
+  int run(const PairScene &sc, const PairPoses &po) { return check(sc, po, opt, &vp, &err); }
+  int run() { return run(scene(), poses()); }
   bool untouched() const { return vp.off.empty() && vp.ent.empty() && vp.cand.empty(); }
   bool refused(int code, const char *text) {
     const int rc = run();
@@ -87,8 +95,9 @@ int main() {
   }
   {  // no pairs at all
     Case c;
-    EXPECT(check(c.view_off.data(), 5, c.kpt.data(), c.view_intr.data(), c.intr.data(), c.itype.data(), 1, nullptr, 0,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c.opt, &c.vp, &c.err) == SFMLOC_OK);
+    PairScene sc = c.scene();
+    sc.pairs = nullptr, sc.n_pairs = 0, sc.offsets = nullptr, sc.match_i = sc.match_j = nullptr;
+    EXPECT(c.run(sc, PairPoses{}) == SFMLOC_OK);
     EXPECT((c.vp.off == std::vector<uint32_t>(6, 0)) && c.vp.ent.empty() && c.vp.cand.back() == 0 && c.vp.n_used == 0);
   }
   {  // the checks of the relative poses, under this call's name
@@ -119,12 +128,11 @@ int main() {
     e.inl_off[0] = 1;
     EXPECT(e.refused(SFMLOC_EINVAL, "inlier_off[0] must be 0"));
     Case f;
-    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
-                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), nullptr, f.inl_off.data(), f.inl.data(), nullptr,
-                 f.opt, &f.vp, &f.err) == SFMLOC_EINVAL && f.untouched());
-    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
-                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), f.t.data(), f.inl_off.data(), nullptr, nullptr,
-                 f.opt, &f.vp, &f.err) == SFMLOC_EINVAL && f.err.find("inlier_idx missing") != std::string::npos);
+    PairPoses no_t = f.poses(), no_idx = f.poses();
+    no_t.rel_t = nullptr;
+    no_idx.inlier_idx = nullptr;
+    EXPECT(f.run(f.scene(), no_t) == SFMLOC_EINVAL && f.untouched());
+    EXPECT(f.run(f.scene(), no_idx) == SFMLOC_EINVAL && f.err.find("inlier_idx missing") != std::string::npos);
   }
   {  // a non-finite rotation or translation, also of a pair that is left out
     Case c;

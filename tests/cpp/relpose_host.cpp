@@ -1,5 +1,6 @@
 // Host program over sfmlocalization_amd/csrc/relpose_host.h, the host side of sfmloc_relative_poses: every refusal with
-// its code and text, and the split of the pair list into the LDS form's pairs and the large ones.  No HIP, no GPU: meant
+// its code and text (the scene's are pair_scene.h's, under this call's name), and the split of the pair list into the LDS
+// form's pairs and the large ones.  No HIP, no GPU: meant
 // to be built with -fsanitize=address,undefined and run on the CPU (tests/test_relpose_cpu.py does).
 #include <cstdio>
 #include <cstring>
@@ -8,7 +9,9 @@
 
 #include "../../sfmlocalization_amd/csrc/relpose_host.h"
 
+using sfmloc::PairScene;
 using sfmloc::relpose_host::check;
+using sfmloc::relpose_host::split_large;
 
 static int g_fail = 0;
 #define EXPECT(c)                                          \
@@ -31,12 +34,21 @@ struct Case {
   std::vector<uint32_t> mi{0, 2, 3, 1, 1}, mj{1, 3, 0, 0, 1};
   std::vector<uint32_t> large{77};
   uint32_t large_max = 555;
+  sfmloc_relpose_options opt{256, 0, 2.5, 1};
   std::string err;
-  int run() {
-    return check(view_off.data(), (uint32_t)view_off.size() - 1, kpt.data(), wh.data(), vintr.data(), intr.data(),
-                 itype.data(), (uint32_t)itype.size(), pairs.data(), (uint32_t)(pairs.size() / 2), offsets.data(),
-                 mi.data(), mj.data(), &large, &large_max, &err);
+  PairScene scene() const {
+    return PairScene{view_off.data(), (uint32_t)view_off.size() - 1, kpt.data(),   wh.data(),
+                     vintr.data(),    intr.data(),                   itype.data(), (uint32_t)itype.size(),
+                     pairs.data(),    (uint32_t)(pairs.size() / 2),  offsets.data(), mi.data(),
+                     mj.data()};
   }
+  // the call's host side: the checks, then the split of a scene that passed them
+  int run(const PairScene &sc) {
+    const int rc = check(sc, opt, &err);
+    if (rc == SFMLOC_OK) split_large(sc, &large, &large_max);
+    return rc;
+  }
+  int run() { return run(scene()); }
   bool untouched() const { return large == std::vector<uint32_t>{77} && large_max == 555; }
 };
 
@@ -48,8 +60,9 @@ int main() {
   }
   {  // no pairs at all
     Case c;
-    EXPECT(check(c.view_off.data(), 4, c.kpt.data(), c.wh.data(), c.vintr.data(), c.intr.data(), c.itype.data(), 2, nullptr,
-                 0, nullptr, nullptr, nullptr, &c.large, &c.large_max, &c.err) == SFMLOC_OK);
+    PairScene sc = c.scene();
+    sc.pairs = nullptr, sc.n_pairs = 0, sc.offsets = nullptr, sc.match_i = sc.match_j = nullptr;
+    EXPECT(c.run(sc) == SFMLOC_OK);
     EXPECT(c.large.empty());
   }
   {  // a view index out of range: the text names the pair
@@ -103,17 +116,15 @@ int main() {
   }
   {  // null arrays
     Case c;
-    EXPECT(check(nullptr, 4, c.kpt.data(), c.wh.data(), c.vintr.data(), c.intr.data(), c.itype.data(), 2, c.pairs.data(), 3,
-                 c.offsets.data(), c.mi.data(), c.mj.data(), &c.large, &c.large_max, &c.err) == SFMLOC_EINVAL);
-    EXPECT(check(c.view_off.data(), 4, nullptr, c.wh.data(), c.vintr.data(), c.intr.data(), c.itype.data(), 2,
-                 c.pairs.data(), 3, c.offsets.data(), c.mi.data(), c.mj.data(), &c.large, &c.large_max, &c.err) ==
-           SFMLOC_EINVAL);
-    EXPECT(check(c.view_off.data(), 4, c.kpt.data(), c.wh.data(), c.vintr.data(), nullptr, c.itype.data(), 2,
-                 c.pairs.data(), 3, c.offsets.data(), c.mi.data(), c.mj.data(), &c.large, &c.large_max, &c.err) ==
-           SFMLOC_EINVAL);
-    EXPECT(check(c.view_off.data(), 4, c.kpt.data(), c.wh.data(), c.vintr.data(), c.intr.data(), c.itype.data(), 2,
-                 c.pairs.data(), 3, c.offsets.data(), nullptr, c.mj.data(), &c.large, &c.large_max, &c.err) ==
-           SFMLOC_EINVAL);
+    PairScene a = c.scene(), b = c.scene(), d = c.scene(), e = c.scene();
+    a.view_off = nullptr;
+    b.kpt_xy = nullptr;
+    d.intrinsics = nullptr;
+    e.match_i = nullptr;
+    EXPECT(c.run(a) == SFMLOC_EINVAL);
+    EXPECT(c.run(b) == SFMLOC_EINVAL);
+    EXPECT(c.run(d) == SFMLOC_EINVAL);
+    EXPECT(c.run(e) == SFMLOC_EINVAL);
     EXPECT(c.untouched());
   }
   {  // 2048 matches stay with the LDS form, 2049 and 65 536 are large, 65 537 is SFMLOC_ECAP (the text names the pair)

@@ -10,6 +10,8 @@
 #include "../../sfmlocalization_amd/csrc/relrefine_host.h"
 
 using namespace sfmloc::relrefine_host;
+using sfmloc::PairPoses;
+using sfmloc::PairScene;
 
 static int g_fail = 0;
 #define EXPECT(c)                                        \
@@ -48,11 +50,15 @@ struct Case {
     t.assign(3 * P, 0.0);
     for (size_t k = 0; k < P; ++k) R[9 * k] = R[9 * k + 4] = R[9 * k + 8] = t[3 * k] = 1.0;
   }
-  int run() {
-    return check(view_off.data(), n_views, kpt.data(), view_intr.data(), intr.data(), itype.data(), 1, pairs.data(),
-                 (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(), mj.data(), R.data(), t.data(), inl_off.data(),
-                 inl.data(), opt, &err);
+  PairScene scene() const {
+    return PairScene{view_off.data(), n_views,      kpt.data(), nullptr,
+                     view_intr.data(), intr.data(), itype.data(), 1,
+                     pairs.data(),    (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(),
+                     mj.data()};
   }
+  PairPoses poses() const { return PairPoses{R.data(), t.data(), inl_off.data(), inl.data(), nullptr}; }
+  int run(const PairScene &sc, const PairPoses &po) { return check(sc, po, opt, &err); }
+  int run() { return run(scene(), poses()); }
   bool refused(int code, const char *text) {
     const int rc = run();
     if (rc != code || err.find(text) == std::string::npos) {
@@ -70,8 +76,9 @@ int main() {
     c.opt.min_points = kMinPointsFloor;
     c.opt.max_steps = 1;
     EXPECT(c.run() == SFMLOC_OK);
-    EXPECT(check(c.view_off.data(), 5, c.kpt.data(), c.view_intr.data(), c.intr.data(), c.itype.data(), 1, nullptr, 0, nullptr,
-                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c.opt, &c.err) == SFMLOC_OK);
+    PairScene sc = c.scene();
+    sc.pairs = nullptr, sc.n_pairs = 0, sc.offsets = nullptr, sc.match_i = sc.match_j = nullptr;
+    EXPECT(c.run(sc, PairPoses{}) == SFMLOC_OK);
   }
   {  // the checks of the relative poses, under this call's name
     Case c;
@@ -96,9 +103,9 @@ int main() {
     i.offsets[2] = 1;
     EXPECT(i.refused(SFMLOC_EINVAL, "sfmloc_refine_relative_poses: offsets not monotone at pair 1"));
     Case j;
-    EXPECT(check(j.view_off.data(), 5, j.kpt.data(), j.view_intr.data(), j.intr.data(), j.itype.data(), 1, j.pairs.data(),
-                 0x40000000u, j.offsets.data(), j.mi.data(), j.mj.data(), j.R.data(), j.t.data(), j.inl_off.data(),
-                 j.inl.data(), j.opt, &j.err) == SFMLOC_ECAP && j.err.find("1073741824 pairs") != std::string::npos);
+    PairScene many = j.scene();
+    many.n_pairs = 0x40000000u;
+    EXPECT(j.run(many, j.poses()) == SFMLOC_ECAP && j.err.find("1073741824 pairs") != std::string::npos);
   }
   {  // those of the wedge scales: an inlier position out of its pair's range; offsets that go back; a missing array
     Case c;
@@ -111,12 +118,11 @@ int main() {
     e.inl_off[0] = 1;
     EXPECT(e.refused(SFMLOC_EINVAL, "inlier_off[0] must be 0"));
     Case f;
-    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
-                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), nullptr, f.inl_off.data(), f.inl.data(), f.opt,
-                 &f.err) == SFMLOC_EINVAL && f.err.find("pose or inlier arrays missing") != std::string::npos);
-    EXPECT(check(f.view_off.data(), 5, f.kpt.data(), f.view_intr.data(), f.intr.data(), f.itype.data(), 1, f.pairs.data(), 4,
-                 f.offsets.data(), f.mi.data(), f.mj.data(), f.R.data(), f.t.data(), f.inl_off.data(), nullptr, f.opt,
-                 &f.err) == SFMLOC_EINVAL && f.err.find("inlier_idx missing") != std::string::npos);
+    PairPoses no_t = f.poses(), no_idx = f.poses();
+    no_t.rel_t = nullptr;
+    no_idx.inlier_idx = nullptr;
+    EXPECT(f.run(f.scene(), no_t) == SFMLOC_EINVAL && f.err.find("pose or inlier arrays missing") != std::string::npos);
+    EXPECT(f.run(f.scene(), no_idx) == SFMLOC_EINVAL && f.err.find("inlier_idx missing") != std::string::npos);
     Case g;
     g.inl_off = {0, 1, 2, 3, 0x7FFFFC01ull};  // (refused before the list behind it is read)
     EXPECT(g.refused(SFMLOC_ECAP, "2147482625 inliers up to pair 3"));

@@ -8,6 +8,7 @@
 
 #include "../../sfmlocalization_amd/csrc/tracks_host.h"
 
+using sfmloc::PairScene;
 using sfmloc::tracks_host::flatten;
 
 static int g_fail = 0;
@@ -28,10 +29,15 @@ struct Case {
   std::vector<uint32_t> ea{99}, eb{98};
   uint64_t n_nodes = 12345;
   std::string err;
-  int run() {
-    return flatten(view_off.data(), (uint32_t)view_off.size() - 1, use.empty() ? nullptr : use.data(), pairs.data(),
-                   (uint32_t)(pairs.size() / 2), offsets.data(), mi.data(), mj.data(), &ea, &eb, &n_nodes, &err);
+  PairScene scene() const {  // (nothing of the cameras)
+    PairScene sc{};
+    sc.view_off = view_off.data(), sc.n_views = (uint32_t)view_off.size() - 1;
+    sc.pairs = pairs.data(), sc.n_pairs = (uint32_t)(pairs.size() / 2), sc.offsets = offsets.data();
+    sc.match_i = mi.data(), sc.match_j = mj.data();
+    return sc;
   }
+  int run(const PairScene &sc) { return flatten(sc, use.empty() ? nullptr : use.data(), &ea, &eb, &n_nodes, &err); }
+  int run() { return run(scene()); }
   bool untouched() const { return ea == std::vector<uint32_t>{99} && eb == std::vector<uint32_t>{98} && n_nodes == 12345; }
 };
 
@@ -61,8 +67,9 @@ int main() {
     c.offsets = {0};
     c.mi.clear();
     c.mj.clear();
-    EXPECT(flatten(c.view_off.data(), 4, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &c.ea, &c.eb, &c.n_nodes, &c.err) ==
-           SFMLOC_OK);
+    PairScene sc{};
+    sc.view_off = c.view_off.data(), sc.n_views = 4;
+    EXPECT(c.run(sc) == SFMLOC_OK);
     EXPECT(c.ea.empty() && c.eb.empty() && c.n_nodes == 9);
   }
   {  // a view index out of range: the text names the pair
@@ -105,12 +112,13 @@ int main() {
   }
   {  // null arrays
     Case c;
-    EXPECT(flatten(nullptr, 4, nullptr, c.pairs.data(), 3, c.offsets.data(), c.mi.data(), c.mj.data(), &c.ea, &c.eb,
-                   &c.n_nodes, &c.err) == SFMLOC_EINVAL);
-    EXPECT(flatten(c.view_off.data(), 4, nullptr, nullptr, 3, c.offsets.data(), c.mi.data(), c.mj.data(), &c.ea, &c.eb,
-                   &c.n_nodes, &c.err) == SFMLOC_EINVAL);
-    EXPECT(flatten(c.view_off.data(), 4, nullptr, c.pairs.data(), 3, c.offsets.data(), nullptr, c.mj.data(), &c.ea, &c.eb,
-                   &c.n_nodes, &c.err) == SFMLOC_EINVAL);
+    PairScene a = c.scene(), b = c.scene(), d = c.scene();
+    a.view_off = nullptr;
+    b.pairs = nullptr;
+    d.match_i = nullptr;
+    EXPECT(c.run(a) == SFMLOC_EINVAL);
+    EXPECT(c.run(b) == SFMLOC_EINVAL);
+    EXPECT(c.run(d) == SFMLOC_EINVAL);
     EXPECT(c.untouched());
   }
   {  // more than 2^32 - 2 feature rows: SFMLOC_ECAP before any match is looked at; 2^32 - 2 rows pass

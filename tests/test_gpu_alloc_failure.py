@@ -186,6 +186,66 @@ def _create_walk(create, at_least):
         S.debug_fail_next_alloc(-1)
 
 
+def free_device_bytes():
+    """hipMemGetInfo's free figure, asked of the HIP runtime the library itself is linked to"""
+    free, total = C.c_size_t(0), C.c_size_t(0)
+    assert S._L().hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+    return free.value
+
+
+def walk_pair_call(call, at_least):
+    """walk() for a one-shot call that hands out a handle: every refused call leaves the device's free memory where it was
+    before it (measured after one good call, so that what the runtime keeps for itself is there already), which it could
+    not with a handle or an array of the failed call still alive; -> (the good call's result, the walked call's)"""
+    ref = call()
+    start = free_device_bytes()
+
+    def checked():
+        try:
+            return call()
+        except S.SfmlocError:
+            assert free_device_bytes() == start
+            raise
+
+    got = walk(checked, at_least)
+    assert free_device_bytes() == start
+    return ref, got
+
+
+def test_pair_side_calls_leave_nothing_behind():
+    """The five one-shot calls of the pair side on pairscales_scene.scene_triplet (three views, three pairs of 40 matches,
+    every array non-empty), counted from the code:
+    sfmloc_relative_poses    the scene's ten arrays (twoview_device.h PairSceneBufs, view_wh among them), the bearings,
+                             the inlier positions, the log10 table and the records: 14
+    sfmloc_refine_relative_poses   nine arrays of the scene, five of the poses (PairPosesBufs), the bearings, two point
+                             slabs and the records: 18
+    sfmloc_wedge_scales      those fourteen, the four per-view lists, twelve arrays of the lists and candidates, two of
+                             the choice and six of the order and the ratios (pairscales.hip wscales_device): 38
+    sfmloc_tracks_build      7 + 6 + 4 + 3 arrays (tracks.hip tracks_device): 20
+    sfmloc_global_poses      eight uploads, nine arrays of the graph and twenty of the two solves (globalposes.hip
+                             gposes_device): 37"""
+    import pairscales_scene
+    s = pairscales_scene.scene_triplet()
+    c = s["call"]
+    scene = {k: c[k] for k in ("view_off", "kpt_xy", "view_intrinsic", "intrinsics", "intrinsic_type", "pairs", "offsets",
+                               "match_i", "match_j")}
+    wh = np.tile(np.array([640, 480], np.uint32), (3, 1))
+    ref, got = walk_pair_call(lambda: S.RelPoses(view_wh=wh, **scene), 14)
+    assert got.results.tobytes() == ref.results.tobytes() and np.array_equal(got.inl_idx, ref.inl_idx)
+    assert np.array_equal(got.inl_off, ref.inl_off) and ref.results["ok"].all()
+    ref, got = walk_pair_call(lambda: S.RelRefine(**c), 18)
+    assert got.results.tobytes() == ref.results.tobytes() and ref.refined.all()
+    ref, got = walk_pair_call(lambda: S.WedgeScales(**c), 38)
+    assert got.records.tobytes() == ref.records.tobytes() and len(ref.records) == 3
+    pl = (c["pairs"], c["offsets"], c["match_i"], c["match_j"])
+    ref, got = walk_pair_call(lambda: S.Tracks(c["view_off"], *pl), 20)
+    assert got.counts == ref.counts and ref.n_tracks > 0
+    same((got.off, got.view, got.feat), (ref.off, ref.view, ref.feat))
+    ref, got = walk_pair_call(lambda: S.GlobalPoses(3, s["pairs"], s["rel_R"], s["rel_t"]), 37)
+    assert ref.in_component.all()
+    same((got.in_component, got.R, got.C, got.pairs), (ref.in_component, ref.R, ref.C, ref.pairs))
+
+
 def test_akaze_create_leaves_no_handle():
     """sfmloc_akaze_create at 64 x 64: 32 arrays and the seven per-keypoint ones (akaze.hip): 39"""
     L = S._L()

@@ -162,6 +162,21 @@ def test_host_side_under_the_host_sanitizers(tmp_path):
     assert r.stdout.startswith("OK")
 
 
+def test_shared_scene_checks_under_the_host_sanitizers(tmp_path):
+    """tests/cpp/pair_scene.cpp: csrc/pair_scene.h, the checks the four pair-side calls share, under each caller's name
+    and switches and with two faults at once; a stand-alone host program, CPU only, built as the one above"""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler (g++ / c++) to build tests/cpp/pair_scene.cpp")
+    san = [] if S.device_count() > 0 else ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    exe = str(tmp_path / "pair_scene")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", *san, "-o", exe,
+                    os.path.join(ROOT, "tests", "cpp", "pair_scene.cpp")], check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert r.stdout.startswith("OK")
+
+
 def test_host_instantiation_of_the_solver_gives_the_twins_bits(tmp_path, expected):
     """tests/cpp/essential_host.cpp: csrc/essential_device.h compiled for the host (the lanes of a group one after the
     other), unfused as the library is, on the fixture's samples and a seeded batch: the restatement's counts and bits"""
