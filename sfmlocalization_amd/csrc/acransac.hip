@@ -2800,7 +2800,7 @@ P3pArgs make_p3p_args(Ctx *c, const K5In &in) {
   A.state = c->d_p3p_state;
   A.result = c->d_pose;
   A.record = reinterpret_cast<const HostResult *>(c->d_result.get());
-  A.host = reinterpret_cast<HostResult *>(c->h_result);
+  A.host = c->h_result;
   A.ms_n = c->d_ms_n;
   A.ms_qfeat = c->d_ms_qfeat;
   A.ms_landmark = c->d_ms_landmark;

@@ -36,18 +36,6 @@
 namespace sfmloc {
 namespace {
 
-// (the stream is drained before the handle's buffers go with it, and destroyed after them)
-void sfm_free(Sfm *h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  if (h->s) hipStreamSynchronize(h->s);
-  for (sfmloc_context *c : h->ctx) sfmloc_context_destroy(c);
-  if (h->map) sfmloc_map_destroy(h->map);
-  const hipStream_t s = h->s;
-  delete h;
-  if (s) hipStreamDestroy(s);
-}
-
 // ---- transpose: observations by landmark -> per-view lists in ascending landmark id (sfmloc.h "views") -------------
 
 __global__ __launch_bounds__(256) void k_adj_obs_landmark(const uint64_t *__restrict__ obs_off, uint32_t n_lm,
@@ -293,57 +281,51 @@ int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *
   h->h_pose_C.assign(d->pose_C, d->pose_C + 3 * (size_t)d->n_poses);
   h->h_obs_off.assign(d->obs_off, d->obs_off + (size_t)d->n_landmarks + 1);
   h->h_obs_view.assign(d->obs_view, d->obs_view + n_obs);
-  SFM_HIP(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking));
+  SFM_RC(h->s.create());
   hipStream_t s = h->s;
-  int rc = SFMLOC_OK;
-#define ADJ_TRY(x)     \
-  do {                 \
-    rc = (x);          \
-    if (rc) return rc; \
-  } while (0)
   // (views, intrinsics and poses are not empty; the landmark and observation arrays may be, and still get an address)
   const size_t lm1 = d->n_landmarks ? d->n_landmarks : 1, obs1 = n_obs ? n_obs : 1;
-  ADJ_TRY(dev_upload(nullptr, h->d_view_id, d->view_id, d->n_views, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_view_intr, d->view_intrinsic, d->n_views, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_view_pose, d->view_pose, d->n_views, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_intr_type, d->intrinsic_type, d->n_intrinsics, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_intr, d->intrinsic, 6 * (size_t)d->n_intrinsics, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_pose_valid, h->h_pose_valid.data(), d->n_poses, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_pose_R, d->pose_R, 9 * (size_t)d->n_poses, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_pose_C, d->pose_C, 3 * (size_t)d->n_poses, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_lm_id, d->landmark_id, d->n_landmarks, s, 1));
-  ADJ_TRY(dev_upload(nullptr, h->d_lm_X, d->landmark_X, 3 * (size_t)d->n_landmarks, s, 1));
-  ADJ_TRY(dev_upload(nullptr, h->d_obs_off, d->obs_off, (size_t)d->n_landmarks + 1, s));
-  ADJ_TRY(dev_upload(nullptr, h->d_obs_view, d->obs_view, n_obs, s, 1));
-  ADJ_TRY(dev_upload(nullptr, h->d_obs_x, d->obs_x, 2 * n_obs, s, 1));
-  ADJ_TRY(h->d_obs_lm.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_vlist.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_vkey.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_tmp_k.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_tmp_v.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_hist.alloc(nullptr, n_obs ? 256 * ((n_obs + kRadixBlock - 1) / kRadixBlock) : 1));
-  ADJ_TRY(h->d_view_off.alloc(nullptr, (size_t)d->n_views + 1));
-  ADJ_TRY(h->d_res.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_ray.alloc(nullptr, 4 * obs1));
-  ADJ_TRY(h->d_obs_keep.alloc(nullptr, obs1));
-  ADJ_TRY(h->d_mincos.alloc(nullptr, lm1));
-  ADJ_TRY(h->d_lm_stage.alloc(nullptr, lm1));
-  ADJ_TRY(h->d_pose_cnt.alloc(nullptr, d->n_poses));
-  ADJ_TRY(h->d_passes.alloc(nullptr, 1));
+  SFM_RC(dev_upload(nullptr, h->d_view_id, d->view_id, d->n_views, s));
+  SFM_RC(dev_upload(nullptr, h->d_view_intr, d->view_intrinsic, d->n_views, s));
+  SFM_RC(dev_upload(nullptr, h->d_view_pose, d->view_pose, d->n_views, s));
+  SFM_RC(dev_upload(nullptr, h->d_intr_type, d->intrinsic_type, d->n_intrinsics, s));
+  SFM_RC(dev_upload(nullptr, h->d_intr, d->intrinsic, 6 * (size_t)d->n_intrinsics, s));
+  SFM_RC(dev_upload(nullptr, h->d_pose_valid, h->h_pose_valid.data(), d->n_poses, s));
+  SFM_RC(dev_upload(nullptr, h->d_pose_R, d->pose_R, 9 * (size_t)d->n_poses, s));
+  SFM_RC(dev_upload(nullptr, h->d_pose_C, d->pose_C, 3 * (size_t)d->n_poses, s));
+  SFM_RC(dev_upload(nullptr, h->d_lm_id, d->landmark_id, d->n_landmarks, s, 1));
+  SFM_RC(dev_upload(nullptr, h->d_lm_X, d->landmark_X, 3 * (size_t)d->n_landmarks, s, 1));
+  SFM_RC(dev_upload(nullptr, h->d_obs_off, d->obs_off, (size_t)d->n_landmarks + 1, s));
+  SFM_RC(dev_upload(nullptr, h->d_obs_view, d->obs_view, n_obs, s, 1));
+  SFM_RC(dev_upload(nullptr, h->d_obs_x, d->obs_x, 2 * n_obs, s, 1));
+  SFM_RC(h->d_obs_lm.alloc(nullptr, obs1));
+  SFM_RC(h->d_vlist.alloc(nullptr, obs1));
+  SFM_RC(h->d_vkey.alloc(nullptr, obs1));
+  SFM_RC(h->d_tmp_k.alloc(nullptr, obs1));
+  SFM_RC(h->d_tmp_v.alloc(nullptr, obs1));
+  SFM_RC(h->d_hist.alloc(nullptr, n_obs ? 256 * ((n_obs + kRadixBlock - 1) / kRadixBlock) : 1));
+  SFM_RC(h->d_view_off.alloc(nullptr, (size_t)d->n_views + 1));
+  SFM_RC(h->d_res.alloc(nullptr, obs1));
+  SFM_RC(h->d_ray.alloc(nullptr, 4 * obs1));
+  SFM_RC(h->d_obs_keep.alloc(nullptr, obs1));
+  SFM_RC(h->d_mincos.alloc(nullptr, lm1));
+  SFM_RC(h->d_lm_stage.alloc(nullptr, lm1));
+  SFM_RC(h->d_pose_cnt.alloc(nullptr, d->n_poses));
+  SFM_RC(h->d_passes.alloc(nullptr, 1));
   {
     std::vector<uint32_t> pv_off((size_t)d->n_poses + 1, 0), pv(d->n_views);
     for (uint32_t v = 0; v < d->n_views; ++v) ++pv_off[d->view_pose[v] + 1];
     for (uint32_t p = 0; p < d->n_poses; ++p) pv_off[p + 1] += pv_off[p];
     std::vector<uint32_t> at(pv_off.begin(), pv_off.end() - 1);
     for (uint32_t v = 0; v < d->n_views; ++v) pv[at[d->view_pose[v]]++] = v;  // (ascending view index inside a pose)
-    ADJ_TRY(dev_upload(nullptr, h->d_pose_view_off, pv_off.data(), pv_off.size(), s));
-    ADJ_TRY(dev_upload(nullptr, h->d_pose_views, pv.data(), pv.size(), s));
+    SFM_RC(dev_upload(nullptr, h->d_pose_view_off, pv_off.data(), pv_off.size(), s));
+    SFM_RC(dev_upload(nullptr, h->d_pose_views, pv.data(), pv.size(), s));
     SFM_HIP(hipStreamSynchronize(s));  // (the vectors leave scope)
   }
-  ADJ_TRY(h->d_pose_t.alloc(nullptr, 3 * (size_t)d->n_poses));
-  ADJ_TRY(h->d_blk_cost.alloc(nullptr, 2 * (size_t)std::max(d->n_poses, d->n_landmarks)));
-  ADJ_TRY(h->d_blk_info.alloc(nullptr, (size_t)std::max(d->n_poses, d->n_landmarks)));
-  ADJ_TRY(sfm_transpose(h));
+  SFM_RC(h->d_pose_t.alloc(nullptr, 3 * (size_t)d->n_poses));
+  SFM_RC(h->d_blk_cost.alloc(nullptr, 2 * (size_t)std::max(d->n_poses, d->n_landmarks)));
+  SFM_RC(h->d_blk_info.alloc(nullptr, (size_t)std::max(d->n_poses, d->n_landmarks)));
+  SFM_RC(sfm_transpose(h));
   const uint32_t vid0 = 0, voff[2] = {0, 0};
   sfmloc_map_desc md;
   memset(&md, 0, sizeof md);
@@ -351,8 +333,7 @@ int sfm_create_impl(const sfmloc_sfm_desc *d, const sfmloc_params *params, Sfm *
   md.view_id = &vid0;
   md.view_off = voff;
   md.focal = 1.0;
-  ADJ_TRY(sfmloc_map_create(&md, &h->params, &h->map));
-#undef ADJ_TRY
+  SFM_RC(sfmloc_map_create(&md, &h->params, &h->map));
   h->res.assign(d->n_views, sfmloc_sfm_view_result{});
   h->inliers.assign(d->n_views, std::vector<uint32_t>());
   return SFMLOC_OK;
@@ -548,25 +529,10 @@ void sfmloc_sfm_default_params(sfmloc_params *p) {
 
 int sfmloc_sfm_create(const sfmloc_sfm_desc *desc, const sfmloc_params *params, sfmloc_sfm **out) {
   SFM_CHECK(desc && out, SFMLOC_EINVAL, "sfmloc_sfm_create: null argument");
-  *out = nullptr;
-  Sfm *h = new (std::nothrow) Sfm();
-  SFM_CHECK(h, SFMLOC_ENOMEM, "out of host memory");
-  int rc;
-  try {
-    rc = sfm_create_impl(desc, params, h);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_sfm_create: out of host memory");
-    rc = SFMLOC_ENOMEM;
-  }
-  if (rc) {
-    sfm_free(h);
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_sfm *>(h);
-  return SFMLOC_OK;
+  return make_handle<Sfm>("sfmloc_sfm_create", out, [&](Sfm *h) { return sfm_create_impl(desc, params, h); });
 }
 
-void sfmloc_sfm_destroy(sfmloc_sfm *h) { sfm_free(reinterpret_cast<Sfm *>(h)); }
+void sfmloc_sfm_destroy(sfmloc_sfm *h) { delete reinterpret_cast<Sfm *>(h); }
 
 int sfmloc_sfm_resect(sfmloc_sfm *hh, uint32_t *n_ran, uint32_t *n_ok) {
   SFM_CHECK(hh, SFMLOC_EINVAL, "sfmloc_sfm_resect: null handle");

@@ -1887,7 +1887,7 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   int w = 0, h = 0, omax = 4, nsub = 4;
   float thres = 0.001f;
   AkPlan plan;
-  hipStream_t own_stream = nullptr;  // the one created with the extractor (stream may be a context's, see _share_stream)
+  Stream own_stream;  // its own, created at first use (stream may be a context's, see _share_stream); before the buffers
   DevBuf<uint8_t> d_gray;
   DevBuf<float> d_t0, d_t1, d_t2, d_t3;
   DevBuf<float> d_Lt, d_Lsmooth, d_Lx, d_Ly, d_Ldet;  // per-level stacks
@@ -1917,11 +1917,11 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
   // d_angle, d_desc
   DevBuf<float> d_resp, d_kp6;
   DevBuf<float2> d_qkpt, d_qkpt6;
-  unsigned int *h_counts = nullptr;           // pinned copy of d_ncand
+  HostBuf<unsigned int> h_counts;             // pinned copy of d_ncand
   // sfmloc_akaze_detect_and_compute reads the counts and -- in the same transfer batch, before it knows the count -- the
   // first spec_n keypoints and descriptors into pinned memory: an image with no more keypoints than that costs ONE
   // synchronisation instead of two (~45 us); spec_n follows the last image's count
-  unsigned char *h_spec = nullptr;
+  HostBuf<unsigned char> h_spec;
   unsigned int spec_n = 0;                    // (det.spec_start at creation, then up to det.spec_max)
   DevBuf<float> d_gauss25, d_win;
   DevBuf<uint16_t> d_pair;
@@ -2136,7 +2136,7 @@ static int akaze_ensure_stream(Akaze *a) {
   if (a->stream.own || a->stream.gang) return SFMLOC_OK;  // (recording for a session: the leader's stream carries it)
   if (!a->own_stream) {
     SFM_HIP(hipSetDevice(a->device));
-    SFM_HIP(hipStreamCreateWithFlags(&a->own_stream, hipStreamNonBlocking));
+    SFM_RC(a->own_stream.create());
     if (a->ever_ganged) SFM_HIP(hipDeviceSynchronize());
   }
   a->stream.own = a->own_stream;
@@ -2173,13 +2173,8 @@ void sfmloc_akaze_destroy(sfmloc_akaze *ak) {
   Akaze *a = reinterpret_cast<Akaze *>(ak);
   if (!a) return;
   hipSetDevice(a->device);
-  if (a->stream.own) hipStreamSynchronize(a->stream.own);
-  gang_member_free(a);
-  if (a->h_counts) hipHostFree(a->h_counts);
-  if (a->h_spec) hipHostFree(a->h_spec);
-  const hipStream_t s = a->own_stream;
-  delete a;  // (its buffers go before its stream)
-  if (s) hipStreamDestroy(s);
+  if (a->stream.own) hipStreamSynchronize(a->stream.own);  // (a context's too)
+  delete a;  // (devmem.h, order of destruction: its buffers, then its stream)
 }
 
 int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_sublevels, float threshold,
@@ -2200,102 +2195,79 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
   hipError_t e = hipGetDeviceCount(&ndev);
   SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
   SFM_HIP(hipSetDevice(device));
-  Akaze *a = new (std::nothrow) Akaze();
-  SFM_CHECK(a, SFMLOC_ENOMEM, "out of host memory");
-  a->device = device;
-  a->w = width;
-  a->h = height;
-  a->omax = n_octaves;
-  a->nsub = n_sublevels;
-  a->thres = threshold;
-  a->plan = plan;
-  const size_t n0 = (size_t)width * height, tot = a->plan.total;
-  // (no stream yet: akaze_ensure_stream creates one at the first call that needs it -- an extractor that is given a
-  // context's stream right away, or only ever works in sessions led by another, never needs one, and a stream that merely
-  // EXISTS shares a hardware queue with streams that work: DESIGN.md 4 Concurrency)
-  int rc = SFMLOC_OK;
-  hipError_t he = hipSuccess;
-#define AK_NEW(buf, n)                       \
-  do {                                       \
-    if (!rc) rc = a->buf.alloc(nullptr, n);  \
-  } while (0)
-  AK_NEW(d_gray, n0);
-  AK_NEW(d_t0, n0);
-  AK_NEW(d_t1, n0);
-  AK_NEW(d_t2, n0);
-  AK_NEW(d_t3, n0);
-  AK_NEW(d_Lt, tot);
-  AK_NEW(d_Lsmooth, tot);
-  AK_NEW(d_Lx, tot);
-  AK_NEW(d_Ly, tot);
-  AK_NEW(d_Ldet, tot);
-  AK_NEW(d_hist, 304);
-  AK_NEW(d_kcontrast, 1);
-  AK_NEW(d_half_steps, (size_t)kMaxLevels * kMaxFedSteps);
-  AK_NEW(d_level_tab, 1);
-  AK_NEW(d_dev_levels, 1);
-  a->det = detection(a->plan, width, height);
-  a->spec_n = a->det.spec_start;
-  const size_t cc = a->det.cand_cap;
-  AK_NEW(d_ncand, 160);
-  AK_NEW(d_seg, (size_t)a->det.n_seg + 1);
-  AK_NEW(d_seg_part, kSegChunksMax + 1);
-  if (!rc) he = hipMemset(a->d_seg_part, 0, (kSegChunksMax + 1) * sizeof(unsigned int));
-  if (!rc && he == hipSuccess) he = hipStreamSynchronize(nullptr);  // (null stream: the extractor's streams are not ordered with it)
-  AK_NEW(d_seg_x, (size_t)a->det.n_seg * kSegMax);
-  AK_NEW(d_cxy, cc);
-  AK_NEW(d_clevel, cc);
-  AK_NEW(d_cstatus, cc);
-  AK_NEW(d_cready, cc);
-  AK_NEW(d_cresp, cc);
-  AK_NEW(d_csub, cc);
-  AK_NEW(d_nbr, cc * 2);
-  AK_NEW(d_nbr2, cc);
-  if (const char *e = getenv("SFMLOC_AKAZE_SUPPRESS")) {  // test hooks: "spill" = every record spilled (the band scans
-    a->sup_force_spill = strstr(e, "spill") != nullptr;    // decide everything), "global" = no level in LDS
-    a->sup_force_global = strstr(e, "global") != nullptr;
-  }
-  AK_NEW(d_ckey, cc);
-  AK_NEW(d_cslot, cc);
-  if (!rc) rc = ensure_kp_cap(a, a->det.cand_cap);  // (never regrown by a detection: it finds no more than cand_cap)
-  AK_NEW(d_gauss25, 49);
-  AK_NEW(d_win, 64);
-  AK_NEW(d_pair, 486 * 2);
-#undef AK_NEW
-  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_counts, 160 * sizeof(unsigned int), hipHostMallocDefault);
-  if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&a->h_spec, (size_t)a->det.spec_max * (6 * sizeof(float) + 64), hipHostMallocDefault);
-  if (!rc && he == hipSuccess) {  // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
+  return make_handle<Akaze>("sfmloc_akaze_create", out, [&](Akaze *a) -> int {
+    a->device = device;
+    a->w = width;
+    a->h = height;
+    a->omax = n_octaves;
+    a->nsub = n_sublevels;
+    a->thres = threshold;
+    a->plan = plan;
+    const size_t n0 = (size_t)width * height, tot = a->plan.total;
+    // (no stream yet: akaze_ensure_stream creates one at the first call that needs it -- an extractor that is given a
+    // context's stream right away, or only ever works in sessions led by another, never needs one, and a stream that merely
+    // EXISTS shares a hardware queue with streams that work: DESIGN.md 4 Concurrency)
+    SFM_RC(a->d_gray.alloc(nullptr, n0));
+    SFM_RC(a->d_t0.alloc(nullptr, n0));
+    SFM_RC(a->d_t1.alloc(nullptr, n0));
+    SFM_RC(a->d_t2.alloc(nullptr, n0));
+    SFM_RC(a->d_t3.alloc(nullptr, n0));
+    SFM_RC(a->d_Lt.alloc(nullptr, tot));
+    SFM_RC(a->d_Lsmooth.alloc(nullptr, tot));
+    SFM_RC(a->d_Lx.alloc(nullptr, tot));
+    SFM_RC(a->d_Ly.alloc(nullptr, tot));
+    SFM_RC(a->d_Ldet.alloc(nullptr, tot));
+    SFM_RC(a->d_hist.alloc(nullptr, 304));
+    SFM_RC(a->d_kcontrast.alloc(nullptr, 1));
+    SFM_RC(a->d_half_steps.alloc(nullptr, (size_t)kMaxLevels * kMaxFedSteps));
+    SFM_RC(a->d_level_tab.alloc(nullptr, 1));
+    SFM_RC(a->d_dev_levels.alloc(nullptr, 1));
+    a->det = detection(a->plan, width, height);
+    a->spec_n = a->det.spec_start;
+    const size_t cc = a->det.cand_cap;
+    SFM_RC(a->d_ncand.alloc(nullptr, 160));
+    SFM_RC(a->d_seg.alloc(nullptr, (size_t)a->det.n_seg + 1));
+    SFM_RC(a->d_seg_part.alloc(nullptr, kSegChunksMax + 1));
+    SFM_HIP(hipMemset(a->d_seg_part, 0, (kSegChunksMax + 1) * sizeof(unsigned int)));
+    SFM_HIP(hipStreamSynchronize(nullptr));  // (null stream: the extractor's streams are not ordered with it)
+    SFM_RC(a->d_seg_x.alloc(nullptr, (size_t)a->det.n_seg * kSegMax));
+    SFM_RC(a->d_cxy.alloc(nullptr, cc));
+    SFM_RC(a->d_clevel.alloc(nullptr, cc));
+    SFM_RC(a->d_cstatus.alloc(nullptr, cc));
+    SFM_RC(a->d_cready.alloc(nullptr, cc));
+    SFM_RC(a->d_cresp.alloc(nullptr, cc));
+    SFM_RC(a->d_csub.alloc(nullptr, cc));
+    SFM_RC(a->d_nbr.alloc(nullptr, cc * 2));
+    SFM_RC(a->d_nbr2.alloc(nullptr, cc));
+    if (const char *e = getenv("SFMLOC_AKAZE_SUPPRESS")) {  // test hooks: "spill" = every record spilled (the band scans
+      a->sup_force_spill = strstr(e, "spill") != nullptr;    // decide everything), "global" = no level in LDS
+      a->sup_force_global = strstr(e, "global") != nullptr;
+    }
+    SFM_RC(a->d_ckey.alloc(nullptr, cc));
+    SFM_RC(a->d_cslot.alloc(nullptr, cc));
+    SFM_RC(ensure_kp_cap(a, a->det.cand_cap));  // (never regrown by a detection: it finds no more than cand_cap)
+    SFM_RC(a->d_gauss25.alloc(nullptr, 49));
+    SFM_RC(a->d_win.alloc(nullptr, 64));
+    SFM_RC(a->d_pair.alloc(nullptr, 486 * 2));
+    SFM_RC(a->h_counts.alloc(160));
+    SFM_RC(a->h_spec.alloc((size_t)a->det.spec_max * (6 * sizeof(float) + 64)));
+    // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_suppress),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SuppressLds));
-    he = attr;
-  }
-  if (!rc && he == hipSuccess) {
+    SFM_HIP(attr);
     std::vector<float> hs((size_t)kMaxLevels * kMaxFedSteps, 0.0f);
     for (int i = 0; i < a->plan.nlev; ++i)  // (nsteps <= kMaxFedSteps: make_plan)
       for (int k = 0; k < a->plan.lev[i].nsteps; ++k) hs[(size_t)i * kMaxFedSteps + k] = 0.5f * a->plan.lev[i].tsteps[k];
-    he = hipMemcpy(a->d_half_steps, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
-  }
-  if (!rc && he == hipSuccess) {
+    SFM_HIP(hipMemcpy(a->d_half_steps, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
     const LevelTab T = level_tab(a);
-    he = hipMemcpy(a->d_level_tab, &T, sizeof(T), hipMemcpyHostToDevice);
-  }
-  if (!rc && he == hipSuccess) {
+    SFM_HIP(hipMemcpy(a->d_level_tab, &T, sizeof(T), hipMemcpyHostToDevice));
     const DevLevels LV = dev_levels(a);
-    he = hipMemcpy(a->d_dev_levels, &LV, sizeof(LV), hipMemcpyHostToDevice);
-  }
-  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_gauss25, a->plan.gauss25, 49 * 4, hipMemcpyHostToDevice);
-  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_win, a->plan.win_ang1, 64 * 4, hipMemcpyHostToDevice);
-  if (!rc && he == hipSuccess) he = hipMemcpy(a->d_pair, a->plan.pair_tab, 486 * 2 * 2, hipMemcpyHostToDevice);
-  if (!rc && he != hipSuccess) {
-    set_error("sfmloc_akaze_create: %s", hipGetErrorString(he));
-    rc = he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
-  }
-  if (rc) {
-    sfmloc_akaze_destroy(reinterpret_cast<sfmloc_akaze *>(a));
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_akaze *>(a);
-  return SFMLOC_OK;
+    SFM_HIP(hipMemcpy(a->d_dev_levels, &LV, sizeof(LV), hipMemcpyHostToDevice));
+    SFM_HIP(hipMemcpy(a->d_gauss25, a->plan.gauss25, 49 * 4, hipMemcpyHostToDevice));
+    SFM_HIP(hipMemcpy(a->d_win, a->plan.win_ang1, 64 * 4, hipMemcpyHostToDevice));
+    SFM_HIP(hipMemcpy(a->d_pair, a->plan.pair_tab, 486 * 2 * 2, hipMemcpyHostToDevice));
+    return SFMLOC_OK;
+  });
 }
 
 int sfmloc_akaze_share_stream(sfmloc_akaze *ak, sfmloc_context *ctx) {
@@ -2305,7 +2277,7 @@ int sfmloc_akaze_share_stream(sfmloc_akaze *ak, sfmloc_context *ctx) {
   SFM_CHECK(!c || c->map->device == a->device, SFMLOC_EINVAL, "sfmloc_akaze_share_stream: extractor and context on different devices");
   hipSetDevice(a->device);
   if (a->stream.own) hipStreamSynchronize(a->stream);
-  a->stream.own = c ? c->stream.own : a->own_stream;  // (nullptr: created when first needed, akaze_ensure_stream)
+  a->stream.own = c ? c->stream.own : a->own_stream.get();  // (nullptr: created when first needed, akaze_ensure_stream)
   return SFMLOC_OK;
 }
 
@@ -2425,7 +2397,7 @@ int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float
   if (rc) return rc;
   // (speculative: the first spec_n records with the counts -- see Akaze::h_spec)
   const unsigned int spec = a->spec_n < cap ? a->spec_n : cap;
-  float *const h_kp = reinterpret_cast<float *>(a->h_spec);
+  float *const h_kp = reinterpret_cast<float *>(a->h_spec.get());
   uint8_t *const h_desc = a->h_spec + (size_t)a->det.spec_max * 6 * sizeof(float);
   if (spec && kpts) SFM_HIP(hipMemcpyAsync(h_kp, a->d_kp6, (size_t)spec * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
   if (spec && desc64) SFM_HIP(hipMemcpyAsync(h_desc, a->d_desc, (size_t)spec * 64, hipMemcpyDeviceToHost, s));

@@ -55,12 +55,38 @@ int dev_raw_alloc(void **p, size_t bytes) {
   if (!injected) (void)hipGetLastError();
   *p = nullptr;
   set_error("hipMalloc(%zu bytes) -> %s", bytes, hipGetErrorString(e));
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SFMLOC_ENODEV
-         : (e == hipErrorOutOfMemory)                          ? SFMLOC_ENOMEM
-                                                               : SFMLOC_EHIP;
+  return hip_code(e);
 }
 void dev_raw_free(void *p) { (void)hipFree(p); }
 hipError_t dev_raw_alloc_error() { return g_raw_alloc_err; }
+
+// ... and every Stream, Event and HostBuf is created and let go through these (the only places that do)
+static int raw_created(const char *what, hipError_t e, void **h) {
+  if (e == hipSuccess) return SFMLOC_OK;
+  (void)hipGetLastError();
+  *h = nullptr;
+  set_error("%s -> %s", what, hipGetErrorString(e));
+  return hip_code(e);
+}
+int stream_raw_create(void **s) {
+  hipStream_t h = nullptr;
+  const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking);
+  *s = h;
+  return raw_created("hipStreamCreateWithFlags(hipStreamNonBlocking)", e, s);
+}
+void stream_raw_sync(void *s) { (void)hipStreamSynchronize(static_cast<hipStream_t>(s)); }
+void stream_raw_destroy(void *s) { (void)hipStreamDestroy(static_cast<hipStream_t>(s)); }
+int event_raw_create(void **ev, bool timing) {
+  hipEvent_t h = nullptr;
+  const hipError_t e = hipEventCreateWithFlags(&h, timing ? hipEventDefault : hipEventDisableTiming);
+  *ev = h;
+  return raw_created(timing ? "hipEventCreate" : "hipEventCreateWithFlags(hipEventDisableTiming)", e, ev);
+}
+void event_raw_destroy(void *e) { (void)hipEventDestroy(static_cast<hipEvent_t>(e)); }
+int host_raw_alloc(void **p, size_t bytes) {
+  return raw_created("hipHostMalloc", hipHostMalloc(p, bytes, hipHostMallocDefault), p);
+}
+void host_raw_free(void *p) { (void)hipHostFree(p); }
 
 namespace {
 
@@ -135,26 +161,25 @@ void build_ratio_table(float ratio, uint16_t *cnt) {
 struct EventScope {
   Ctx *c;
   int which;
-  hipEvent_t a = nullptr, b = nullptr;
+  EventPair ev;
   bool on;
   EventScope(Ctx *c_, int which_)
       : c(c_), which(which_),
         on(c_->map->params.profile == 1 || (c_->map->params.profile == 2 && which_ == SFMLOC_K_HAMMING)) {
     if (!on) return;
     if (!c->event_pool.empty()) {
-      a = c->event_pool.back().first;
-      b = c->event_pool.back().second;
+      ev = std::move(c->event_pool.back());
       c->event_pool.pop_back();
-    } else if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+    } else if (ev.a.create(kTimingEvent) || ev.b.create(kTimingEvent)) {
       on = false;
       return;
     }
-    hipEventRecord(a, c->stream);
+    hipEventRecord(ev.a, c->stream);
   }
   ~EventScope() {
     if (!on) return;
-    hipEventRecord(b, c->stream);
-    c->pending_events.push_back({which, {a, b}});
+    hipEventRecord(ev.b, c->stream);
+    c->pending_events.emplace_back(which, std::move(ev));
   }
 };
 
@@ -162,12 +187,12 @@ struct EventScope {
 int drain_events(Ctx *c, double *per_kind_ms = nullptr) {
   for (auto &pe : c->pending_events) {
     float ms = 0.f;
-    SFM_HIP(hipEventSynchronize(pe.second.second));
-    SFM_HIP(hipEventElapsedTime(&ms, pe.second.first, pe.second.second));
+    SFM_HIP(hipEventSynchronize(pe.second.b));
+    SFM_HIP(hipEventElapsedTime(&ms, pe.second.a, pe.second.b));
     c->stats.total_ms[pe.first] += ms;
     if (per_kind_ms) per_kind_ms[pe.first] += ms;
     c->stats.launches[pe.first] += 1;
-    c->event_pool.push_back(pe.second);
+    c->event_pool.push_back(std::move(pe.second));
   }
   c->pending_events.clear();
   return SFMLOC_OK;
@@ -179,89 +204,60 @@ void free_ctx(Ctx *c) {
     c->zombie = true;
     return;
   }
-  if (c->stream.own) hipStreamSynchronize(c->stream.own);
-  for (auto &pe : c->pending_events) {
-    hipEventDestroy(pe.second.first);
-    hipEventDestroy(pe.second.second);
-  }
-  for (auto &e : c->event_pool) {
-    hipEventDestroy(e.first);
-    hipEventDestroy(e.second);
-  }
-  if (c->h_pinned) hipHostFree(c->h_pinned);
-  if (c->h_result) hipHostFree(c->h_result);
-  if (c->pinned_busy) hipEventDestroy(c->pinned_busy);
-  if (c->xev_out) hipEventDestroy(c->xev_out);
-  if (c->xev_in) hipEventDestroy(c->xev_in);
-  gang_member_free(c);
-  hipStream_t own = c->stream_borrowed ? nullptr : c->stream.own;
+  if (c->stream.own) hipStreamSynchronize(c->stream.own);  // (a borrowed one too)
   Ctx *lender = c->lender;
-  delete c;  // (every DevBuf frees its array here: before the stream goes)
-  if (own) hipStreamDestroy(own);
+  delete c;  // (devmem.h, order of destruction: events and pinned blocks, every DevBuf, then a stream of its own)
   if (lender && --lender->borrowers == 0 && lender->zombie) free_ctx(lender);
 }
 
+struct CtxFree {
+  void operator()(Ctx *c) const { free_ctx(c); }
+};
+
 int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
   *out = nullptr;
-  Ctx *c = new (std::nothrow) Ctx();
+  std::unique_ptr<Ctx, CtxFree> owner(new (std::nothrow) Ctx());  // (let go, as far as it got, on every early return)
+  Ctx *c = owner.get();
   SFM_CHECK(c, SFMLOC_ENOMEM, "out of host memory");
   c->map = m;
-  int rc = SFMLOC_OK;
-#define CTX_TRY(x)   \
-  do {               \
-    rc = (x);        \
-    if (rc) {        \
-      free_ctx(c);   \
-      return rc;     \
-    }                \
-  } while (0)
-#define CTX_HIP(x)                                              \
-  do {                                                          \
-    hipError_t e_ = (x);                                        \
-    if (e_ != hipSuccess) {                                     \
-      set_error("%s -> %s", #x, hipGetErrorString(e_));         \
-      free_ctx(c);                                              \
-      return e_ == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP; \
-    }                                                           \
-  } while (0)
   if (share) {  // no stream (hardware queue) of its own: work is queued on the lender's
-    c->stream.own = share->stream.own;
-    c->stream_borrowed = true;
+    c->own_stream.borrow(share->stream.own);
     c->lender = share;
     ++share->borrowers;
   } else {
-    CTX_HIP(hipStreamCreateWithFlags(&c->stream.own, hipStreamNonBlocking));
+    SFM_RC(c->own_stream.create());
   }
+  c->stream.own = c->own_stream;
   const uint64_t n_pad = (uint64_t)m->n_blocks * kBlockRows;
   uint64_t *acct = &c->hbm_bytes;
   c->merge_only = merge_only;
   // a context that only ever merges candidate parts and runs P3P (sfmloc_context_create_merge) has no use for the
   // per-bank-row arrays of the matching stages: 30 B per row and the 32 MB of the flagged-row pass
   const bool full = !merge_only;
-  if (full) CTX_TRY(dev_alloc(acct, c->d_part, (size_t)n_pad));
-  CTX_TRY(dev_alloc(acct, c->d_view_sel, (size_t)m->n_views + 1));
-  CTX_TRY(dev_alloc(acct, c->d_view_widx0, (size_t)m->n_views + 1));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_block_list, (size_t)m->n_blocks));
-  CTX_TRY(dev_alloc(acct, c->d_view_count, (size_t)m->n_views + 1));  // + the phantom view (sfmloc_internal.h)
-  if (full) CTX_TRY(dev_alloc(acct, c->d_match_i, (size_t)m->n_rows));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_match_key, (size_t)m->n_rows));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_flagged, (size_t)n_pad));
-  CTX_TRY(dev_alloc(acct, c->d_n_flagged, (size_t)1));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_flagmask, (size_t)m->n_blocks + 1));
+  if (full) SFM_RC(dev_alloc(acct, c->d_part, (size_t)n_pad));
+  SFM_RC(dev_alloc(acct, c->d_view_sel, (size_t)m->n_views + 1));
+  SFM_RC(dev_alloc(acct, c->d_view_widx0, (size_t)m->n_views + 1));
+  if (full) SFM_RC(dev_alloc(acct, c->d_block_list, (size_t)m->n_blocks));
+  SFM_RC(dev_alloc(acct, c->d_view_count, (size_t)m->n_views + 1));  // + the phantom view (sfmloc_internal.h)
+  if (full) SFM_RC(dev_alloc(acct, c->d_match_i, (size_t)m->n_rows));
+  if (full) SFM_RC(dev_alloc(acct, c->d_match_key, (size_t)m->n_rows));
+  if (full) SFM_RC(dev_alloc(acct, c->d_flagged, (size_t)n_pad));
+  SFM_RC(dev_alloc(acct, c->d_n_flagged, (size_t)1));
+  if (full) SFM_RC(dev_alloc(acct, c->d_flagmask, (size_t)m->n_blocks + 1));
   c->rows_chunk_cap = m->n_blocks < 4096 ? (m->n_blocks ? m->n_blocks : 1) : 4096;  // 4096 chunks = 262 k flagged rows, 16 MB
   if (full) {
-    CTX_TRY(dev_alloc(acct, c->d_rows_scratch, (size_t)c->rows_chunk_cap * 8 * 64));
-    CTX_TRY(dev_alloc(acct, c->d_rows_arrivals, (size_t)c->rows_chunk_cap));
-    CTX_TRY(dev_alloc(acct, c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
-    CTX_HIP(hipMemset(c->d_rows_arrivals, 0, (size_t)c->rows_chunk_cap * sizeof(uint32_t)));
+    SFM_RC(dev_alloc(acct, c->d_rows_scratch, (size_t)c->rows_chunk_cap * 8 * 64));
+    SFM_RC(dev_alloc(acct, c->d_rows_arrivals, (size_t)c->rows_chunk_cap));
+    SFM_RC(dev_alloc(acct, c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
+    SFM_HIP(hipMemset(c->d_rows_arrivals, 0, (size_t)c->rows_chunk_cap * sizeof(uint32_t)));
   }
-  CTX_TRY(dev_alloc(acct, c->d_k1_counters, (size_t)2 * kK1CounterSlots));
-  CTX_HIP(hipMemset(c->d_k1_counters, 0, 2 * kK1CounterSlots * sizeof(unsigned long long)));
-  CTX_TRY(dev_alloc(acct, c->d_geo_count, (size_t)m->n_views + 1));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_geo_idx, (size_t)m->n_rows));
-  CTX_TRY(dev_alloc(acct, c->d_geo_model, ((size_t)m->n_views + 1) * 10));
+  SFM_RC(dev_alloc(acct, c->d_k1_counters, (size_t)2 * kK1CounterSlots));
+  SFM_HIP(hipMemset(c->d_k1_counters, 0, 2 * kK1CounterSlots * sizeof(unsigned long long)));
+  SFM_RC(dev_alloc(acct, c->d_geo_count, (size_t)m->n_views + 1));
+  if (full) SFM_RC(dev_alloc(acct, c->d_geo_idx, (size_t)m->n_rows));
+  SFM_RC(dev_alloc(acct, c->d_geo_model, ((size_t)m->n_views + 1) * 10));
   // everything a finished query reports lives in ONE device record laid out as HostResult: one D2H copy per query
-  CTX_TRY(dev_alloc(acct, c->d_result, sizeof(HostResult)));
+  SFM_RC(dev_alloc(acct, c->d_result, sizeof(HostResult)));
   {
     HostResult *r = reinterpret_cast<HostResult *>(c->d_result.get());
     c->d_p3p_state = &r->state;
@@ -271,50 +267,47 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
     c->d_pair_qfeat = r->pair_qfeat;
     c->d_pair_landmark = r->pair_landmark;
   }
-  CTX_TRY(dev_alloc(acct, c->d_cand_part, (size_t)kPartHeaderBytes + (size_t)c->cand_cap * sizeof(Candidate)));
-  if (full) CTX_TRY(dev_alloc(acct, c->d_geo_dist, (size_t)m->n_rows));
-  CTX_TRY(dev_alloc(acct, c->d_best64, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, c->d_winner, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, c->d_ms_n, (size_t)1));
-  CTX_TRY(dev_alloc(acct, c->d_ms_qfeat, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, c->d_ms_landmark, (size_t)65536));
-  CTX_TRY(dev_alloc(acct, c->d_pt2d, (size_t)65536 * 2));
-  CTX_TRY(dev_alloc(acct, c->d_pt3d, (size_t)65536 * 3));
-  CTX_TRY(dev_alloc(acct, c->d_hyp_nfa, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, c->d_hyp_err, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, c->d_hyp_model, (size_t)kP3pSlots * 12));
-  CTX_TRY(dev_alloc(acct, c->d_hyp_k, (size_t)kP3pSlots));
-  CTX_TRY(dev_alloc(acct, c->d_prep_models, (size_t)kP3pBatchMax * 48));
-  CTX_TRY(dev_alloc(acct, c->d_prep_nm, (size_t)kP3pBatchMax));
-  CTX_TRY(ctx_p3p_workspace(c, kP3pMaxN));  // the arrays that ctx_p3p_reserve regrows
+  SFM_RC(dev_alloc(acct, c->d_cand_part, (size_t)kPartHeaderBytes + (size_t)c->cand_cap * sizeof(Candidate)));
+  if (full) SFM_RC(dev_alloc(acct, c->d_geo_dist, (size_t)m->n_rows));
+  SFM_RC(dev_alloc(acct, c->d_best64, (size_t)65536));
+  SFM_RC(dev_alloc(acct, c->d_winner, (size_t)65536));
+  SFM_RC(dev_alloc(acct, c->d_ms_n, (size_t)1));
+  SFM_RC(dev_alloc(acct, c->d_ms_qfeat, (size_t)65536));
+  SFM_RC(dev_alloc(acct, c->d_ms_landmark, (size_t)65536));
+  SFM_RC(dev_alloc(acct, c->d_pt2d, (size_t)65536 * 2));
+  SFM_RC(dev_alloc(acct, c->d_pt3d, (size_t)65536 * 3));
+  SFM_RC(dev_alloc(acct, c->d_hyp_nfa, (size_t)kP3pSlots));
+  SFM_RC(dev_alloc(acct, c->d_hyp_err, (size_t)kP3pSlots));
+  SFM_RC(dev_alloc(acct, c->d_hyp_model, (size_t)kP3pSlots * 12));
+  SFM_RC(dev_alloc(acct, c->d_hyp_k, (size_t)kP3pSlots));
+  SFM_RC(dev_alloc(acct, c->d_prep_models, (size_t)kP3pBatchMax * 48));
+  SFM_RC(dev_alloc(acct, c->d_prep_nm, (size_t)kP3pBatchMax));
+  SFM_RC(ctx_p3p_workspace(c, kP3pMaxN));  // the arrays that ctx_p3p_reserve regrows
   if (m->bow_dim) {
-    CTX_TRY(dev_alloc(acct, c->d_bow_query, (size_t)m->bow_dim));
-    CTX_TRY(dev_alloc(acct, c->d_bow_dist, (size_t)m->n_views));
-    CTX_TRY(dev_alloc(acct, c->d_bow_cand, (size_t)m->n_views));
-    CTX_TRY(dev_alloc(acct, c->d_bow_sel, (size_t)m->n_views + 1));
+    SFM_RC(dev_alloc(acct, c->d_bow_query, (size_t)m->bow_dim));
+    SFM_RC(dev_alloc(acct, c->d_bow_dist, (size_t)m->n_views));
+    SFM_RC(dev_alloc(acct, c->d_bow_cand, (size_t)m->n_views));
+    SFM_RC(dev_alloc(acct, c->d_bow_sel, (size_t)m->n_views + 1));
   }
-  CTX_HIP(hipHostMalloc((void **)&c->h_pinned, ((size_t)2 * m->n_views + m->n_blocks + 16) * sizeof(uint32_t),
-                        hipHostMallocDefault));
-  CTX_HIP(hipHostMalloc(&c->h_result, sizeof(HostResult), hipHostMallocDefault));
+  SFM_RC(c->h_pinned.alloc((size_t)2 * m->n_views + m->n_blocks + 16));
+  SFM_RC(c->h_result.alloc(1));
   memset(c->h_result, 0, sizeof(HostResult));
-  CTX_HIP(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));
-  CTX_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
-  CTX_HIP(hipMemsetAsync(c->d_geo_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
-  CTX_HIP(hipMemsetAsync(c->d_ms_n, 0, sizeof(uint32_t), c->stream));
-  CTX_HIP(hipEventCreateWithFlags(&c->xev_out, hipEventDisableTiming));
-  CTX_HIP(hipEventCreateWithFlags(&c->xev_in, hipEventDisableTiming));
-  CTX_HIP(hipMemsetAsync(c->d_pose, 0, sizeof(Pose), c->stream));
-  CTX_HIP(hipMemsetAsync(c->d_p3p_state, 0, sizeof(P3pState), c->stream));
-  CTX_HIP(hipMemsetAsync(c->d_view_stats, 0, 3 * sizeof(uint32_t), c->stream));
-  CTX_HIP(hipStreamSynchronize(c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_geo_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_ms_n, 0, sizeof(uint32_t), c->stream));
+  SFM_RC(c->xev_out.create(kOrderingEvent));
+  SFM_RC(c->xev_in.create(kOrderingEvent));
+  SFM_HIP(hipMemsetAsync(c->d_pose, 0, sizeof(Pose), c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_p3p_state, 0, sizeof(P3pState), c->stream));
+  SFM_HIP(hipMemsetAsync(c->d_view_stats, 0, 3 * sizeof(uint32_t), c->stream));
+  SFM_HIP(hipStreamSynchronize(c->stream));
   // (the two hipMemset above -- the arrival counters of k_hamming_rows, K1's statistics -- run on the NULL stream, which the
   // context's non-blocking stream is not ordered with, and hipMemset of device memory may return before it has run: a first
   // scan that overtook the memset found garbage arrival counters, merged nothing and left the head pass's seeds to K2 --
   // the one wrong first scan of round 4, profiles/r04_pytest_gpu_failed_run_excerpt.txt)
-  CTX_HIP(hipStreamSynchronize(nullptr));
-#undef CTX_TRY
-#undef CTX_HIP
-  *out = c;
+  SFM_HIP(hipStreamSynchronize(nullptr));
+  *out = owner.release();
   return SFMLOC_OK;
 }
 
@@ -460,7 +453,7 @@ int ctx_match_putative(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
       SFM_HIP(hipMemcpyAsync(c->d_view_widx0, h_w0, n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
     if (nb) SFM_HIP(hipMemcpyAsync(c->d_block_list, h_blk, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if (!c->pinned_busy) SFM_HIP(hipEventCreateWithFlags(&c->pinned_busy, hipEventDisableTiming));
+    SFM_RC(c->pinned_busy.ensure(kOrderingEvent));
     SFM_HIP(hipEventRecord(c->pinned_busy, c->stream));
   }
 
@@ -615,13 +608,13 @@ namespace {
 // ctx_resection_enqueue ends with; a copy is only needed when the chain stops before K5 (measurements).
 int ctx_fetch_result(Ctx *c, bool no_p3p = false) {
   if (!no_p3p) return SFMLOC_OK;
-  HostResult *h = reinterpret_cast<HostResult *>(c->h_result);
+  HostResult *h = c->h_result;
   SFM_HIP(hipMemcpyAsync(h, c->d_result, sizeof(HostResult), hipMemcpyDeviceToHost, c->stream));
   return SFMLOC_OK;
 }
 
 int ctx_resection_wait(Ctx *c) {
-  HostResult *h = reinterpret_cast<HostResult *>(c->h_result);
+  HostResult *h = c->h_result;
   for (int guard = 0; guard < 64; ++guard) {
     SFM_HIP(hipStreamSynchronize(c->stream));
     c->stream.dirty = false;
@@ -696,7 +689,7 @@ int ctx_localize_end(Ctx *c, sfmloc_pose *out, uint32_t *pair_qfeat, uint32_t *p
   }
   int rc = ctx_resection_wait(c);
   if (rc) return rc;
-  HostResult *h = reinterpret_cast<HostResult *>(c->h_result);
+  HostResult *h = c->h_result;
   *out = h->pose;
   out->status |= h->status;
   out->n_putative_views = (int32_t)h->view_stats[0];
@@ -811,11 +804,11 @@ int gang_flush(GangState *g) {
 int gang_open(GangMember *const *members, int n) {
   GangMember *lead = members[0];
   if (!lead->gang_owned) {
-    lead->gang_owned = new (std::nothrow) GangState();
+    lead->gang_owned.reset(new (std::nothrow) GangState());
     SFM_CHECK(lead->gang_owned, SFMLOC_ENOMEM, "out of host memory");
-    SFM_HIP(hipEventCreateWithFlags(&lead->gang_owned->done, hipEventDisableTiming));
   }
-  GangState *g = lead->gang_owned;
+  GangState *g = lead->gang_owned.get();
+  SFM_RC(g->done.ensure(kOrderingEvent));
   SFM_CHECK(lead->stream.own, SFMLOC_EINVAL, "gang session: the leading member has no stream");
   g->stream = lead->stream.own;
   g->members.clear();
@@ -824,7 +817,7 @@ int gang_open(GangMember *const *members, int n) {
     c->ever_ganged = true;
     // (own == nullptr: a member that has no stream of its own yet -- an extractor that only ever worked in sessions)
     if (i > 0 && c->stream.own && c->stream.dirty && c->stream.own != g->stream) {  // the member's own earlier work comes first
-      if (!c->gang_ev) SFM_HIP(hipEventCreateWithFlags(&c->gang_ev, hipEventDisableTiming));
+      SFM_RC(c->gang_ev.ensure(kOrderingEvent));
       SFM_HIP(hipEventRecord(c->gang_ev, c->stream.own));
       SFM_HIP(hipStreamWaitEvent(g->stream, c->gang_ev, 0));
       c->stream.dirty = false;
@@ -856,16 +849,6 @@ int gang_close(GangMember *lead) {
       }
   }
   return rc;  // (gang_flush has set the message)
-}
-
-void gang_member_free(GangMember *m) {
-  if (m->gang_ev) hipEventDestroy(m->gang_ev);
-  if (m->gang_owned) {
-    if (m->gang_owned->done) hipEventDestroy(m->gang_owned->done);
-    delete m->gang_owned;
-  }
-  m->gang_ev = nullptr;
-  m->gang_owned = nullptr;
 }
 
 int match_putative_on(Ctx *c, Query *q, const uint32_t *view_sel, uint32_t n_sel) {
@@ -907,23 +890,8 @@ void sfmloc_default_params(sfmloc_params *p) {
   p->guided_matching = 0;       // -gm: false (localization.cpp:82, computeFeaturesAndMatches.cpp:63)
 }
 
-static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params, sfmloc_map **out);
-
-int sfmloc_map_create(const sfmloc_map_desc *d, const sfmloc_params *params, sfmloc_map **out) {
-  try {  // host-side containers are sized by the caller's counts: no exception may cross the C ABI
-    return map_create_impl(d, params, out);
-  } catch (const std::bad_alloc &) {
-    set_error("sfmloc_map_create: out of host memory");
-    return SFMLOC_ENOMEM;
-  } catch (const std::exception &e) {
-    set_error("sfmloc_map_create: %s", e.what());
-    return SFMLOC_EINVAL;
-  }
-}
-
-static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params, sfmloc_map **out) {
-  SFM_CHECK(d && out, SFMLOC_EINVAL, "sfmloc_map_create: null argument");
-  *out = nullptr;
+// what sfmloc_map_create accepts (nothing here touches a device)
+static int map_desc_check(const sfmloc_map_desc *d) {
   SFM_CHECK(d->n_views > 0 && d->view_id && d->view_off, SFMLOC_EINVAL, "sfmloc_map_create: no views");
   SFM_CHECK(d->view_off[0] == 0 && d->view_off[d->n_views] == d->n_rows, SFMLOC_EINVAL,
             "sfmloc_map_create: view_off must start at 0 and end at n_rows");
@@ -942,49 +910,17 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
       SFM_CHECK(d->row_landmark[r] >= -1 && d->row_landmark[r] < (int64_t)d->n_landmarks, SFMLOC_EINVAL,
                 "sfmloc_map_create: row_landmark[%llu] out of range", (unsigned long long)r);
   }
+  return SFMLOC_OK;
+}
 
-  sfmloc_params p;
-  if (params)
-    p = *params;
-  else
-    sfmloc_default_params(&p);
-
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV,
-            "no HIP device visible (%s); this library has no CPU fallback",
-            e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-  SFM_CHECK(p.device >= 0 && p.device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", p.device, ndev - 1);
-  SFM_HIP(hipSetDevice(p.device));
-
-  Map *m = new (std::nothrow) Map();
-  SFM_CHECK(m, SFMLOC_ENOMEM, "out of host memory");
+// a new map's tables and its own context, on the current device (p.device); on an error the map is deleted as it stands
+static int map_fill(Map *m, const sfmloc_map_desc *d, const sfmloc_params &p) {
   m->device = p.device;
   m->params = p;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, p.device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
-  int rc = SFMLOC_OK;
-  hipStream_t s = nullptr;  // upload stream
-#define SFM_TRY(x)                   \
-  do {                               \
-    rc = (x);                        \
-    if (rc) {                        \
-      if (s) hipStreamDestroy(s);    \
-      free_map(m);                   \
-      return rc;                     \
-    }                                \
-  } while (0)
-#define MAP_HIP(x)                                                    \
-  do {                                                                \
-    hipError_t e_ = (x);                                              \
-    if (e_ != hipSuccess) {                                           \
-      set_error("%s -> %s", #x, hipGetErrorString(e_));               \
-      if (s) hipStreamDestroy(s);                                     \
-      free_map(m);                                                    \
-      return e_ == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP; \
-    }                                                                 \
-  } while (0)
-  MAP_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  Stream s;  // upload stream (a local: gone before the map's buffers are, on every way out)
+  SFM_RC(s.create());
   m->n_rows = d->n_rows;
   m->n_blocks = (uint32_t)((d->n_rows + kBlockRows - 1) / kBlockRows);
   m->max_view_blocks = 0;
@@ -1011,30 +947,18 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
 
   // bank: upload row-major chunks and re-tile on the device
   const uint64_t n_pad = (uint64_t)m->n_blocks * kBlockRows;
-  SFM_TRY(dev_alloc(acct, m->d_bank, (size_t)n_pad * 4));
+  SFM_RC(dev_alloc(acct, m->d_bank, (size_t)n_pad * 4));
   if (n_pad) {
-    MAP_HIP(hipMemsetAsync(m->d_bank, 0, n_pad * 64, s));
+    SFM_HIP(hipMemsetAsync(m->d_bank, 0, n_pad * 64, s));
     const uint64_t chunk = 16ull << 20;  // rows per staging chunk (1 GiB)
     DevBuf<uint4> d_stage;
     const uint64_t stage_rows = std::min<uint64_t>(chunk, d->n_rows);
-    SFM_TRY(d_stage.alloc(nullptr, stage_rows * 4));
+    SFM_RC(d_stage.alloc(nullptr, stage_rows * 4));
     for (uint64_t r0 = 0; r0 < d->n_rows; r0 += chunk) {
       const uint64_t n = std::min<uint64_t>(chunk, d->n_rows - r0);
-      hipError_t ce = hipMemcpyAsync(d_stage, d->desc + r0 * 64, n * 64, hipMemcpyHostToDevice, s);
-      if (ce == hipSuccess) {
-        rc = launch_tile_bank(d_stage, r0, n, m->d_bank, s);
-        if (!rc) ce = hipStreamSynchronize(s);
-      }
-      if (ce != hipSuccess || rc) {
-        if (ce != hipSuccess) {
-          set_error("bank upload: %s", hipGetErrorString(ce));
-          rc = SFMLOC_EHIP;
-        }
-        d_stage.reset();
-        hipStreamDestroy(s);
-        free_map(m);
-        return rc;
-      }
+      SFM_HIP(hipMemcpyAsync(d_stage, d->desc + r0 * 64, n * 64, hipMemcpyHostToDevice, s));
+      SFM_RC(launch_tile_bank(d_stage, r0, n, m->d_bank, s));
+      SFM_HIP(hipStreamSynchronize(s));
     }
   }
 
@@ -1042,46 +966,57 @@ static int map_create_impl(const sfmloc_map_desc *d, const sfmloc_params *params
     std::vector<uint32_t> off(d->view_off, d->view_off + d->n_views + 1), id(d->view_id, d->view_id + d->n_views);
     off.push_back((uint32_t)d->n_rows);
     id.push_back(0xFFFFFFu);
-    SFM_TRY(dev_upload(acct, m->d_view_off, off.data(), off.size(), s));
-    SFM_TRY(dev_upload(acct, m->d_view_id, id.data(), id.size(), s));
+    SFM_RC(dev_upload(acct, m->d_view_off, off.data(), off.size(), s));
+    SFM_RC(dev_upload(acct, m->d_view_id, id.data(), id.size(), s));
     if (d->view_wh) {
       std::vector<uint32_t> wh(d->view_wh, d->view_wh + 2 * (size_t)d->n_views);
       wh.push_back(1);
       wh.push_back(1);
-      SFM_TRY(dev_upload(acct, m->d_view_wh, wh.data(), wh.size(), s));
+      SFM_RC(dev_upload(acct, m->d_view_wh, wh.data(), wh.size(), s));
     }
-    MAP_HIP(hipStreamSynchronize(s));  // the staging vectors go out of scope
+    SFM_HIP(hipStreamSynchronize(s));  // the staging vectors go out of scope
   }
   if (d->kpt_xy)
-    SFM_TRY(dev_upload(acct, m->d_kpt, reinterpret_cast<const float2 *>(d->kpt_xy), (size_t)d->n_rows, s));
+    SFM_RC(dev_upload(acct, m->d_kpt, reinterpret_cast<const float2 *>(d->kpt_xy), (size_t)d->n_rows, s));
   if (d->row_landmark) {
-    SFM_TRY(dev_upload(acct, m->d_row_landmark, d->row_landmark, (size_t)d->n_rows, s));
-    SFM_TRY(dev_upload(acct, m->d_landmark_id, d->landmark_id, (size_t)d->n_landmarks, s));
-    SFM_TRY(dev_upload(acct, m->d_landmark_X, d->landmark_X, (size_t)d->n_landmarks * 3, s));
+    SFM_RC(dev_upload(acct, m->d_row_landmark, d->row_landmark, (size_t)d->n_rows, s));
+    SFM_RC(dev_upload(acct, m->d_landmark_id, d->landmark_id, (size_t)d->n_landmarks, s));
+    SFM_RC(dev_upload(acct, m->d_landmark_X, d->landmark_X, (size_t)d->n_landmarks * 3, s));
   }
   if (d->bow && d->bow_dim) {
     m->bow_dim = d->bow_dim;
-    SFM_TRY(dev_upload(acct, m->d_bow, d->bow, (size_t)d->n_views * d->bow_dim, s));
+    SFM_RC(dev_upload(acct, m->d_bow, d->bow, (size_t)d->n_views * d->bow_dim, s));
   }
   m->have_geometry = d->view_wh && d->kpt_xy && d->row_landmark && d->focal > 0.0;
-  SFM_TRY(dev_alloc(acct, m->d_L10, (size_t)65538));
-  SFM_TRY(launch_fill_log10(m->d_L10, 65538, s));
+  SFM_RC(dev_alloc(acct, m->d_L10, (size_t)65538));
+  SFM_RC(launch_fill_log10(m->d_L10, 65538, s));
   {
     uint16_t tab[513];
     build_ratio_table(p.dist_ratio, tab);
-    SFM_TRY(dev_alloc(acct, m->d_ratio_cnt, (size_t)513));
-    MAP_HIP(hipMemcpyAsync(m->d_ratio_cnt, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-    MAP_HIP(hipStreamSynchronize(s));  // tab lives on the stack
+    SFM_RC(dev_alloc(acct, m->d_ratio_cnt, (size_t)513));
+    SFM_HIP(hipMemcpyAsync(m->d_ratio_cnt, tab, sizeof(tab), hipMemcpyHostToDevice, s));
+    SFM_HIP(hipStreamSynchronize(s));  // tab lives on the stack
     m->ratio_cnt_for = p.dist_ratio;
   }
-  MAP_HIP(hipStreamSynchronize(s));
-  hipStreamDestroy(s);
-  s = nullptr;
-  SFM_TRY(make_ctx(m, &m->ctx0));
-#undef SFM_TRY
-#undef MAP_HIP
-  *out = reinterpret_cast<sfmloc_map *>(m);
-  return SFMLOC_OK;
+  SFM_HIP(hipStreamSynchronize(s));
+  s.reset();  // (before the context's stream comes into being)
+  return make_ctx(m, &m->ctx0);
+}
+
+int sfmloc_map_create(const sfmloc_map_desc *d, const sfmloc_params *params, sfmloc_map **out) {
+  SFM_CHECK(d && out, SFMLOC_EINVAL, "sfmloc_map_create: null argument");
+  *out = nullptr;
+  SFM_RC(map_desc_check(d));
+  const sfmloc_params p = options_or(params, sfmloc_default_params);
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV,
+            "no HIP device visible (%s); this library has no CPU fallback",
+            e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+  SFM_CHECK(p.device >= 0 && p.device < ndev, SFMLOC_EINVAL, "device %d out of range (0..%d)", p.device, ndev - 1);
+  SFM_HIP(hipSetDevice(p.device));
+  // (the map has no context yet when filling it fails, so deleting it lets everything go)
+  return make_handle<Map>("sfmloc_map_create", out, [&](Map *m) { return map_fill(m, d, p); });
 }
 
 void sfmloc_map_destroy(sfmloc_map *map) { free_map(reinterpret_cast<Map *>(map)); }
@@ -1159,42 +1094,33 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
             SFMLOC_MAX_QUERY_ROWS);
   Map *m = reinterpret_cast<Map *>(map);
   SFM_HIP(hipSetDevice(m->device));
-  Query *q = new (std::nothrow) Query();
-  SFM_CHECK(q, SFMLOC_ENOMEM, "out of host memory");
-  q->map = m;
-  q->n = n;
-  q->width = width;
-  q->height = height;
-  const size_t n_pad = ((size_t)n + 63) / 64 * 64;
-  hipError_t e = hipSuccess;
-  hipStream_t s = m->ctx0->stream;
-  if (n_pad) {
-    e = query_array(q->d_desc, n_pad * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(q->d_desc, 0, n_pad * 64, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_desc, desc, (size_t)n * 64, hipMemcpyHostToDevice, s);
+  return make_handle<Query>("sfmloc_query_create", out, [&](Query *q) -> int {
+    q->map = m;
+    q->n = n;
+    q->width = width;
+    q->height = height;
+    const size_t n_pad = ((size_t)n + 63) / 64 * 64;
+    if (!n_pad) return SFMLOC_OK;
+    hipStream_t s = m->ctx0->stream;
+    SFM_RC(q->d_desc.alloc(nullptr, n_pad * 4));
+    SFM_HIP(hipMemsetAsync(q->d_desc, 0, n_pad * 64, s));
+    SFM_HIP(hipMemcpyAsync(q->d_desc, desc, (size_t)n * 64, hipMemcpyHostToDevice, s));
     std::vector<float> k6;
-    if (e == hipSuccess && kpt_xy) {
+    if (kpt_xy) {
       q->h_kpt.assign(kpt_xy, kpt_xy + 2 * (size_t)n);
       // The reference writes the query's keypoints to <tmp>/<base>.feat with `ostream << float`
       // (6 significant digits, AKAZEOpenCV.cpp:80-81) and the F-matrix filter reads them back through
       // Regions::Load (:106-111); pt2D keeps the unrounded values (:77-79).  Reproduce the round trip.
       k6.resize(2 * (size_t)n);
       sfmloc_feat_round_trip(kpt_xy, 2 * (uint64_t)n, k6.data());
-      e = query_array(q->d_kpt, n);
-      if (e == hipSuccess) e = query_array(q->d_kpt6, n);
-      if (e == hipSuccess) e = hipMemcpyAsync(q->d_kpt, kpt_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(q->d_kpt6, k6.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s);
+      SFM_RC(q->d_kpt.alloc(nullptr, n));
+      SFM_RC(q->d_kpt6.alloc(nullptr, n));
+      SFM_HIP(hipMemcpyAsync(q->d_kpt, kpt_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s));
+      SFM_HIP(hipMemcpyAsync(q->d_kpt6, k6.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-  }
-  if (e != hipSuccess) {
-    set_error("sfmloc_query_create: %s", hipGetErrorString(e));
-    delete q;  // (with the arrays it owns)
-    return e == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
-  }
-  *out = reinterpret_cast<sfmloc_query *>(q);
-  return SFMLOC_OK;
+    SFM_HIP(hipStreamSynchronize(s));
+    return SFMLOC_OK;
+  });
 }
 
 void sfmloc_feat_round_trip(const float *kpt_xy, uint64_t n_values, float *out) {
@@ -1694,7 +1620,7 @@ int sfmloc_gang_end(sfmloc_context *const *ctxs, uint32_t n) {
   Ctx *lead = reinterpret_cast<Ctx *>(ctxs[0]);
   GangState *g = lead->stream.gang;
   if (!g) return SFMLOC_OK;  // the session recorded nothing (one member, or profiling)
-  SFM_CHECK(g == lead->gang_owned && g->members.size() == n, SFMLOC_EINVAL, "sfmloc_gang_end: not the contexts of the session");
+  SFM_CHECK(g == lead->gang_owned.get() && g->members.size() == n, SFMLOC_EINVAL, "sfmloc_gang_end: not the contexts of the session");
   SFM_HIP(hipSetDevice(lead->map->device));
   return gang_close(lead);
 }
@@ -1726,25 +1652,6 @@ int sfmloc_shard_export_packed(sfmloc_context *ctx, void *packed_dev, uint32_t n
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   SFM_HIP(hipSetDevice(c->map->device));
   return launch_export_packed(c, packed_dev, n_queries, budget, query_index);
-}
-
-static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void *parts_dev, uint32_t n_parts,
-                            uint32_t cap, uint64_t part_stride, uint32_t packed_b, uint32_t packed_qi);
-
-int sfmloc_merge_begin(sfmloc_context *ctx, sfmloc_query *query, const void *parts_dev, uint32_t n_parts,
-                       uint32_t cap, uint64_t part_stride) {
-  return merge_begin_impl(ctx, query, parts_dev, n_parts, cap, part_stride, 0, 0);
-}
-
-int sfmloc_merge_begin_packed(sfmloc_context *ctx, sfmloc_query *query, const void *packed_dev, uint32_t n_parts,
-                              uint64_t part_stride, uint32_t n_queries, uint32_t budget, uint32_t query_index) {
-  SFM_CHECK(n_queries > 0 && query_index < n_queries && budget > 0, SFMLOC_EINVAL,
-            "sfmloc_merge_begin_packed: bad argument");
-  if (part_stride == 0) part_stride = packed_part_bytes(n_queries, budget);
-  SFM_CHECK(part_stride >= packed_part_bytes(n_queries, budget), SFMLOC_EINVAL,
-            "sfmloc_merge_begin_packed: part_stride too small");
-  SFM_CHECK((uint64_t)n_parts * budget < (1ull << 32), SFMLOC_EINVAL, "sfmloc_merge_begin_packed: n_parts * budget >= 2^32");
-  return merge_begin_impl(ctx, query, packed_dev, n_parts, budget, part_stride, n_queries, query_index);
 }
 
 static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void *parts_dev, uint32_t n_parts,
@@ -1788,6 +1695,22 @@ static int merge_begin_impl(sfmloc_context *ctx, sfmloc_query *query, const void
   }
   c->in_flight = q;
   return SFMLOC_OK;
+}
+
+int sfmloc_merge_begin(sfmloc_context *ctx, sfmloc_query *query, const void *parts_dev, uint32_t n_parts,
+                       uint32_t cap, uint64_t part_stride) {
+  return merge_begin_impl(ctx, query, parts_dev, n_parts, cap, part_stride, 0, 0);
+}
+
+int sfmloc_merge_begin_packed(sfmloc_context *ctx, sfmloc_query *query, const void *packed_dev, uint32_t n_parts,
+                              uint64_t part_stride, uint32_t n_queries, uint32_t budget, uint32_t query_index) {
+  SFM_CHECK(n_queries > 0 && query_index < n_queries && budget > 0, SFMLOC_EINVAL,
+            "sfmloc_merge_begin_packed: bad argument");
+  if (part_stride == 0) part_stride = packed_part_bytes(n_queries, budget);
+  SFM_CHECK(part_stride >= packed_part_bytes(n_queries, budget), SFMLOC_EINVAL,
+            "sfmloc_merge_begin_packed: part_stride too small");
+  SFM_CHECK((uint64_t)n_parts * budget < (1ull << 32), SFMLOC_EINVAL, "sfmloc_merge_begin_packed: n_parts * budget >= 2^32");
+  return merge_begin_impl(ctx, query, packed_dev, n_parts, budget, part_stride, n_queries, query_index);
 }
 
 int sfmloc_localize(sfmloc_map *map, sfmloc_query *query, const uint32_t *view_sel, uint32_t n_sel,
@@ -1928,37 +1851,31 @@ int sfmloc_bof_create(const sfmloc_bof_desc *d, int device, sfmloc_bof **out) {
   hipError_t e = hipGetDeviceCount(&ndev);
   SFM_CHECK(e == hipSuccess && ndev > 0, SFMLOC_ENODEV, "no HIP device visible; this library has no CPU fallback");
   SFM_HIP(hipSetDevice(device));
-  BofModel *b = new (std::nothrow) BofModel();
-  SFM_CHECK(b, SFMLOC_ENOMEM, "out of host memory");
-  b->device = device;
-  b->K = d->K;
-  b->in_dim = d->in_dim;
-  b->n_pca = d->n_pca;
-  b->cdim = d->n_pca > 0 ? d->n_pca : d->in_dim;
-  b->resized = d->resized_image_size;
-  b->levels = d->use_spatial_pyramid ? d->pyramid_level : 1;
-  b->norm_type = d->norm_type;
-  b->cells = 0;
-  for (int l = 0; l < b->levels; ++l) b->cells += (l == 0) ? 1 : (l == 2 ? 3 : (l + 1) * (l + 1));
-  int rc = SFMLOC_OK;
-  // (the model's own stream is created by the first sfmloc_bof_compute: a model inside a sfmloc_imgbow works on that
-  // object's stream and needs none -- an idle stream still shares a hardware queue with streams that work; the uploads
-  // here go through the null stream)
-  if (!rc) rc = dev_upload(nullptr, b->d_centers, d->centers, (size_t)d->K * b->cdim, b->stream);
-  if (!rc && d->n_pca > 0) {
-    rc = dev_upload(nullptr, b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, b->stream);
-    if (!rc) rc = dev_upload(nullptr, b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, b->stream);
-    if (!rc) rc = dev_upload(nullptr, b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, b->stream);
-  }
-  if (!rc) rc = b->d_counts.alloc(nullptr, (size_t)b->K * b->cells);
-  if (!rc) rc = b->d_out.alloc(nullptr, (size_t)b->K * b->cells);
-  if (!rc && hipStreamSynchronize(b->stream) != hipSuccess) rc = SFMLOC_EHIP;
-  if (rc) {
-    sfmloc_bof_destroy(reinterpret_cast<sfmloc_bof *>(b));
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_bof *>(b);
-  return SFMLOC_OK;
+  return make_handle<BofModel>("sfmloc_bof_create", out, [&](BofModel *b) -> int {
+    b->device = device;
+    b->K = d->K;
+    b->in_dim = d->in_dim;
+    b->n_pca = d->n_pca;
+    b->cdim = d->n_pca > 0 ? d->n_pca : d->in_dim;
+    b->resized = d->resized_image_size;
+    b->levels = d->use_spatial_pyramid ? d->pyramid_level : 1;
+    b->norm_type = d->norm_type;
+    b->cells = 0;
+    for (int l = 0; l < b->levels; ++l) b->cells += (l == 0) ? 1 : (l == 2 ? 3 : (l + 1) * (l + 1));
+    // (the model's own stream is created by the first sfmloc_bof_compute: a model inside a sfmloc_imgbow works on that
+    // object's stream and needs none -- an idle stream still shares a hardware queue with streams that work; the uploads
+    // here go through the null stream)
+    SFM_RC(dev_upload(nullptr, b->d_centers, d->centers, (size_t)d->K * b->cdim, nullptr));
+    if (d->n_pca > 0) {
+      SFM_RC(dev_upload(nullptr, b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, nullptr));
+      SFM_RC(dev_upload(nullptr, b->d_pca_evec, d->pca_eigvec, (size_t)d->n_pca * d->in_dim, nullptr));
+      SFM_RC(dev_upload(nullptr, b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, nullptr));
+    }
+    SFM_RC(b->d_counts.alloc(nullptr, (size_t)b->K * b->cells));
+    SFM_RC(b->d_out.alloc(nullptr, (size_t)b->K * b->cells));
+    SFM_HIP(hipStreamSynchronize(nullptr));
+    return SFMLOC_OK;
+  });
 }
 
 void sfmloc_bof_destroy(sfmloc_bof *bof) {
@@ -1966,9 +1883,7 @@ void sfmloc_bof_destroy(sfmloc_bof *bof) {
   if (!b) return;
   hipSetDevice(b->device);
   if (b->stream) hipStreamSynchronize(b->stream);
-  const hipStream_t s = b->stream;
-  delete b;  // (its buffers go before its stream)
-  if (s) hipStreamDestroy(s);
+  delete b;  // (devmem.h, order of destruction: its buffers, then its stream)
 }
 
 int sfmloc_bof_dim(const sfmloc_bof *bof) {
@@ -1987,7 +1902,7 @@ int sfmloc_bof_compute(sfmloc_bof *bof, const float *desc, const float *kpt_xy, 
     if (!g.ok()) return g.rc();
     g.commit();
   }
-  if (!b->stream) SFM_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+  SFM_RC(b->stream.ensure());
   if (n) {
     SFM_HIP(hipMemcpyAsync(b->d_desc, desc, (size_t)n * b->in_dim * sizeof(float), hipMemcpyHostToDevice, b->stream));
     SFM_HIP(hipMemcpyAsync(b->d_kxy, kpt_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, b->stream));
@@ -2098,7 +2013,7 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
   if (!rc) rc = ctx_resection_wait_done(c);
   c->p3p_uncal = false;
   if (rc) return rc;
-  const HostResult *h = reinterpret_cast<const HostResult *>(c->h_result);
+  const HostResult *h = c->h_result;
   *out = h->pose;
   SFM_CHECK((out->status & 4) == 0, SFMLOC_ECAP, "more than %u 2D-3D correspondences (P3P workspace)", c->p3p_cap);
   if (inlier_idx && out->ok && out->n_inliers > 0) {

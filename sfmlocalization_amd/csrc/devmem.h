@@ -1,13 +1,16 @@
 // Ownership of device memory, for every handle and call of the library: one owner per array, so that freeing and the
 // memory figures (sfmloc_map_info::hbm_bytes: Map and Ctx charge an account, nothing else does) need no list kept in
 // step by hand.  No HIP here: raw allocation goes through two functions that capi.hip defines over hipMalloc / hipFree
-// (and tests/cpp/devmem.cpp over malloc).
+// (and tests/cpp/devmem.cpp over malloc).  Below the device arrays: the owners of streams, events and pinned host memory.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 #include <memory>
 #include <utility>
+
+struct ihipStream_t;  // what hipStream_t and hipEvent_t point to: opaque here as they are in HIP's own headers
+struct ihipEvent_t;
 
 namespace sfmloc {
 
@@ -121,6 +124,110 @@ class DevGroup {
   DevMem *owner_[kMax] = {};
   int n_ = 0, rc_ = 0;
   size_t failed_bytes_ = 0;
+};
+
+// ---------------------------------------------------------------------------
+// The other three resources a handle or a call holds: a stream, an event, a block of pinned host memory.  Same rules as
+// above (move-only, no address, empty after a failed creation, released exactly once), and raw creation goes through
+// capi.hip / tests/cpp/devmem.cpp in the same way; it never counts as a typed device buffer for failure injection.
+// Nothing is created in a constructor: a stream that merely exists shares a hardware queue with streams that work.
+//
+// Order of destruction, stated once: a handle (or a call) declares its Stream BEFORE its DevBufs, so the buffers are
+// freed first -- kernels on the stream may still run then, which is safe because freeing waits for the device -- and
+// the stream is drained and destroyed after them.
+// ---------------------------------------------------------------------------
+int stream_raw_create(void **s);  // a non-blocking stream; codes and *s as dev_raw_alloc
+void stream_raw_sync(void *s);
+void stream_raw_destroy(void *s);
+int event_raw_create(void **e, bool timing);
+void event_raw_destroy(void *e);
+int host_raw_alloc(void **p, size_t bytes);
+void host_raw_free(void *p);
+
+// one raw handle H*: owned (let go through Drop, once) or borrowed (never let go); reads as the H* it replaces
+template <class H, void (*Drop)(void *)>
+class RawOwner {
+ public:
+  RawOwner() = default;
+  RawOwner(const RawOwner &) = delete;
+  RawOwner &operator=(const RawOwner &) = delete;
+  RawOwner(RawOwner &&o) noexcept : h_(std::exchange(o.h_, nullptr)), own_(std::exchange(o.own_, false)) {}
+  RawOwner &operator=(RawOwner &&o) noexcept {
+    if (this != std::addressof(o)) {
+      reset();
+      h_ = std::exchange(o.h_, nullptr);
+      own_ = std::exchange(o.own_, false);
+    }
+    return *this;
+  }
+  ~RawOwner() { reset(); }
+  RawOwner *operator&() = delete;
+  void borrow(H *h) {  // somebody else's: never let go here
+    reset();
+    h_ = h;
+  }
+  void reset() {
+    if (own_) Drop(h_);
+    h_ = nullptr;
+    own_ = false;
+  }
+  H *get() const { return h_; }
+  operator H *() const { return h_; }
+
+ protected:
+  int adopt(int rc, void *h) {  // what a raw creation answered, after reset(): owned on SFMLOC_OK, empty otherwise
+    if (rc) return rc;
+    h_ = static_cast<H *>(h);
+    own_ = true;
+    return 0;
+  }
+  H *h_ = nullptr;
+  bool own_ = false;
+};
+
+inline void stream_drain_destroy(void *s) {
+  stream_raw_sync(s);
+  stream_raw_destroy(s);
+}
+// a non-blocking stream (reads as hipStream_t): an owned one is synchronised, then destroyed; a borrowed one neither
+class Stream : public RawOwner<ihipStream_t, stream_drain_destroy> {
+ public:
+  int create() {
+    reset();  // (first: a previous one goes before the new one comes into being)
+    void *s = nullptr;
+    const int rc = stream_raw_create(&s);
+    return adopt(rc, s);
+  }
+  int ensure() { return h_ ? 0 : create(); }  // created at first use
+};
+
+constexpr bool kTimingEvent = true, kOrderingEvent = false;  // (an ordering event cannot be timed and is cheaper)
+// an event (reads as hipEvent_t)
+class Event : public RawOwner<ihipEvent_t, event_raw_destroy> {
+ public:
+  int create(bool timing) {
+    reset();
+    void *e = nullptr;
+    const int rc = event_raw_create(&e, timing);
+    return adopt(rc, e);
+  }
+  int ensure(bool timing) { return h_ ? 0 : create(timing); }
+};
+struct EventPair {  // the two ends of a timed bracket
+  Event a, b;
+};
+
+// pinned host memory, typed like DevBuf<T>.  Zero elements: an empty block, no error.
+template <class T>
+class HostBuf : public RawOwner<T, host_raw_free> {
+ public:
+  int alloc(size_t n) {
+    this->reset();
+    if (n == 0) return 0;
+    void *p = nullptr;
+    const int rc = host_raw_alloc(&p, n * sizeof(T));
+    return this->adopt(rc, p);
+  }
 };
 
 }  // namespace sfmloc

@@ -18,10 +18,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <memory>
 #include <new>
 #include <type_traits>
 #include <utility>
 #include <vector>
+
+#include "devmem.h"
 
 namespace sfmloc {
 
@@ -90,7 +93,7 @@ struct GangRec {
 struct GangMember;
 struct GangState {
   hipStream_t stream = nullptr;  // the first member's own stream
-  hipEvent_t done = nullptr;
+  Event done;
   std::vector<GangMember *> members;
   uint64_t launches = 0, gang_launches = 0;  // issued by flushes (all kinds / with more than one member)
 };
@@ -128,16 +131,15 @@ struct GangMember {
   size_t gang_head = 0;
   bool gang_oom = false;            // a record could not be stored (host memory): the session's flush returns ENOMEM
   bool ever_ganged = false;         // has taken part in a session (a stream created for it LATER must wait for that work)
-  GangState *gang_owned = nullptr;  // this member has led a gang: its state (stream = this member's own)
-  hipEvent_t gang_ev = nullptr;     // orders the gang's stream after this member's own earlier work
+  std::unique_ptr<GangState> gang_owned;  // this member has led a gang: its state (stream = this member's own)
+  Event gang_ev;                    // orders the gang's stream after this member's own earlier work
 };
 
 // capi.hip.  gang_open: the members (the first leads: its stream carries the session) start recording; the gang's stream
 // first waits for whatever a member still has queued on a stream of its own.  gang_close: everything recorded is issued
-// and the members' own streams continue after it.  gang_member_free: the events / state a member may own.
+// and the members' own streams continue after it.
 int gang_open(GangMember *const *members, int n);
 int gang_close(GangMember *lead);
-void gang_member_free(GangMember *m);
 
 template <class Body, class... Ts>
 struct GangLaunch {

@@ -920,13 +920,9 @@ int gp_pcg(const GpDev &D, uint32_t max_pcg, hipStream_t s, uint32_t *launches, 
 
 // the events at the phase boundaries of a call
 struct GpEvents {
-  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~GpEvents() {
-    for (hipEvent_t x : e)
-      if (x) hipEventDestroy(x);
-  }
+  Event e[5];
   int mark(int i, hipStream_t s) {
-    if (!e[i]) SFM_HIP(hipEventCreate(&e[i]));
+    SFM_RC(e[i].ensure(kTimingEvent));
     SFM_HIP(hipEventRecord(e[i], s));
     return SFMLOC_OK;
   }

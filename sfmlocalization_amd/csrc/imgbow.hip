@@ -25,23 +25,31 @@
 
 namespace sfmloc {
 
-struct ImgBow {
+// the two handles an ImgBow owns.  A base, so that they go after ImgBow's own members: its buffers are freed before the
+// extractor (whose stream its work is queued on) and the model are
+struct ImgBowParts {
+  sfmloc_bof *bof = nullptr;       // the model
+  sfmloc_akaze *ak = nullptr;      // size x size extractor, cv::AKAZE::create() defaults
+  ~ImgBowParts() {
+    sfmloc_akaze_destroy(ak);  // (null: nothing)
+    sfmloc_bof_destroy(bof);
+  }
+};
+struct ImgBow : ImgBowParts {
   int device = 0;
   uint32_t w = 0, h = 0, channels = 3;
-  sfmloc_bof *bof = nullptr;       // the model (owned)
-  sfmloc_akaze *ak = nullptr;      // size x size extractor, cv::AKAZE::create() defaults (owned)
   DenseGrayPlan plan;
   DevBuf<uint8_t> d_src;           // [h*w*channels]
-  uint8_t *h_src = nullptr;        // pinned staging of the same size
+  HostBuf<uint8_t> h_src;          // pinned staging of the same size
   DevBuf<float> d_grid;            // [n_grid x 4] x, y, size, class_id
   DevBuf<float> d_kxy;             // [n_grid x 2]
   uint32_t n_grid = 0;
   DevBuf<uint32_t> d_counts;
   DevBuf<double> d_out;            // [dim] the reference's float64 vector
   DevBuf<float> d_out_f32;         // [dim] as the shortlist reads it (BoFUtils.cpp:51-54 converts to CV_32F)
-  double *h_out = nullptr;         // pinned [dim]
-  hipEvent_t ordered = nullptr;    // sfmloc_imgbow_order_before
-  hipEvent_t staged = nullptr;     // the previous call's H2D out of h_src has completed
+  HostBuf<double> h_out;           // pinned [dim]
+  Event ordered;                   // sfmloc_imgbow_order_before
+  Event staged;                    // the previous call's H2D out of h_src has completed
   bool staged_pending = false;
   hipStream_t last_stream = nullptr;  // where the last call's work was queued (a batch: the leading extractor's stream)
 };
@@ -78,15 +86,7 @@ void sfmloc_imgbow_destroy(sfmloc_imgbow *p) {
     hipStream_t s = akaze_stream_now(reinterpret_cast<Akaze *>(ib->ak));
     if (s) (void)hipStreamSynchronize(s);
   }
-  if (ib->h_src) (void)hipHostFree(ib->h_src);
-  if (ib->h_out) (void)hipHostFree(ib->h_out);
-  if (ib->staged) (void)hipEventDestroy(ib->staged);
-  if (ib->ordered) (void)hipEventDestroy(ib->ordered);
-  sfmloc_akaze *ak = ib->ak;
-  sfmloc_bof *bof = ib->bof;
-  delete ib;  // (its buffers go before the extractor's stream)
-  if (ak) sfmloc_akaze_destroy(ak);
-  if (bof) sfmloc_bof_destroy(bof);
+  delete ib;  // (its buffers, then the extractor with its stream, then the model: ImgBowParts)
 }
 
 int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t width, uint32_t height, uint32_t channels,
@@ -99,51 +99,31 @@ int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t widt
             model->in_dim);
   const int size = model->resized_image_size;
   SFM_CHECK(size >= 16 && size <= 4096, SFMLOC_EINVAL, "sfmloc_imgbow_create: ResizedImageSize %d", size);
-  ImgBow *ib = new (std::nothrow) ImgBow();
-  SFM_CHECK(ib, SFMLOC_ENOMEM, "out of host memory");
-  ib->device = device;
-  ib->w = width;
-  ib->h = height;
-  ib->channels = channels;
-  int rc = sfmloc_bof_create(model, device, &ib->bof);
-  if (!rc) rc = sfmloc_akaze_create(device, size, size, 4, 4, 0.001f, &ib->ak);  // DenseLocalFeatureWrapper.cpp:42
-  if (!rc) rc = dense_gray_plan_create(&ib->plan, (int)width, (int)height, (int)channels, size);
-  std::vector<float> grid, kxy;
-  if (!rc) {
-    try {
-      dense_grid_build(size, &grid, &kxy);
-    } catch (const std::bad_alloc &) {
-      set_error("sfmloc_imgbow_create: out of host memory");
-      rc = SFMLOC_ENOMEM;
-    }
-  }
-  if (!rc) {
+  return make_handle<ImgBow>("sfmloc_imgbow_create", out, [&](ImgBow *ib) -> int {
+    ib->device = device;
+    ib->w = width;
+    ib->h = height;
+    ib->channels = channels;
+    SFM_RC(sfmloc_bof_create(model, device, &ib->bof));
+    SFM_RC(sfmloc_akaze_create(device, size, size, 4, 4, 0.001f, &ib->ak));  // DenseLocalFeatureWrapper.cpp:42
+    SFM_RC(dense_gray_plan_create(&ib->plan, (int)width, (int)height, (int)channels, size));
+    std::vector<float> grid, kxy;
+    dense_grid_build(size, &grid, &kxy);
     ib->n_grid = (uint32_t)(grid.size() / 4);
     const BofModel *b = reinterpret_cast<const BofModel *>(ib->bof);
     const size_t dim = (size_t)b->K * b->cells, n_src = (size_t)width * height * channels;
-    rc = ib->d_src.alloc(nullptr, n_src);
-    if (!rc) rc = ib->d_counts.alloc(nullptr, dim);
-    if (!rc) rc = ib->d_out.alloc(nullptr, dim);
-    if (!rc) rc = ib->d_out_f32.alloc(nullptr, dim);
-    if (!rc) rc = dev_upload(nullptr, ib->d_grid, grid.data(), grid.size(), nullptr);
-    if (!rc) rc = dev_upload(nullptr, ib->d_kxy, kxy.data(), kxy.size(), nullptr);
-    // (the two uploads are waited for at once; if the second fails, grid outlives the destroy below, whose frees wait)
-    hipError_t he = hipSuccess;
-    if (!rc) he = hipStreamSynchronize(nullptr);
-    if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&ib->h_src, n_src, hipHostMallocDefault);
-    if (!rc && he == hipSuccess) he = hipHostMalloc((void **)&ib->h_out, dim * sizeof(double), hipHostMallocDefault);
-    if (!rc && he == hipSuccess) he = hipEventCreateWithFlags(&ib->staged, hipEventDisableTiming);
-    if (!rc && he != hipSuccess) {
-      set_error("sfmloc_imgbow_create: %s", hipGetErrorString(he));
-      rc = he == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
-    }
-  }
-  if (rc) {
-    sfmloc_imgbow_destroy(reinterpret_cast<sfmloc_imgbow *>(ib));
-    return rc;
-  }
-  *out = reinterpret_cast<sfmloc_imgbow *>(ib);
-  return SFMLOC_OK;
+    SFM_RC(ib->d_src.alloc(nullptr, n_src));
+    SFM_RC(ib->d_counts.alloc(nullptr, dim));
+    SFM_RC(ib->d_out.alloc(nullptr, dim));
+    SFM_RC(ib->d_out_f32.alloc(nullptr, dim));
+    SFM_RC(dev_upload(nullptr, ib->d_grid, grid.data(), grid.size(), nullptr));
+    SFM_RC(dev_upload(nullptr, ib->d_kxy, kxy.data(), kxy.size(), nullptr));
+    // (the two uploads are waited for at once; if the second fails, grid outlives the handle's frees, which wait)
+    SFM_HIP(hipStreamSynchronize(nullptr));
+    SFM_RC(ib->h_src.alloc(n_src));
+    SFM_RC(ib->h_out.alloc(dim));
+    return ib->staged.create(kOrderingEvent);
+  });
 }
 
 int sfmloc_imgbow_dim(const sfmloc_imgbow *p) {
@@ -167,7 +147,7 @@ int sfmloc_imgbow_order_before(sfmloc_imgbow *p, sfmloc_context *ctx) {
   hipStream_t s = ib->last_stream ? ib->last_stream : akaze_stream_now(reinterpret_cast<Akaze *>(ib->ak));
   hipStream_t cs = c->stream;
   if (s == cs) return SFMLOC_OK;  // (shared: stream order already)
-  if (!ib->ordered) SFM_HIP(hipEventCreateWithFlags(&ib->ordered, hipEventDisableTiming));
+  SFM_RC(ib->ordered.ensure(kOrderingEvent));
   SFM_HIP(hipEventRecord(ib->ordered, s));
   SFM_HIP(hipStreamWaitEvent(cs, ib->ordered, 0));
   return SFMLOC_OK;

@@ -141,16 +141,9 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
     S.inliers.assign(n_views, std::vector<uint32_t>());
     S.res.assign(n_views, sfmloc_sfm_view_result{});  // (last: a failed allocation leaves the state unmade)
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  SFM_HIP(hipEventCreate(&e0));
-  SFM_HIP(hipEventCreate(&e1));
-  struct Events {
-    hipEvent_t &a, &b;
-    ~Events() {
-      hipEventDestroy(a);
-      hipEventDestroy(b);
-    }
-  } events{e0, e1};
+  Event e0, e1;
+  SFM_RC(e0.create(kTimingEvent));
+  SFM_RC(e1.create(kTimingEvent));
   SFM_HIP(hipEventRecord(e0, s));
   SFM_HIP(hipMemsetAsync(S.d_extended, 0, sizeof(unsigned long long), s));
   sfmloc_register_report R;

@@ -34,7 +34,7 @@ struct SfmRegState {
 struct Sfm {
   int device = 0;
   sfmloc_params params{};
-  hipStream_t s = nullptr;
+  Stream s;  // (before the buffers: devmem.h, order of destruction)
   uint32_t n_views = 0, n_intr = 0, n_poses = 0, n_lm = 0;
   uint64_t n_obs = 0;
   // host copies of what the host-side rules need (the pose check of the cleanup, the per-view launches)
@@ -72,6 +72,13 @@ struct Sfm {
   sfmloc_map *map = nullptr;
   std::vector<sfmloc_context *> ctx;
   SfmRegState reg;
+  // the stream is drained, then K5's contexts and their map go; the buffers and the stream follow as members
+  ~Sfm() {
+    hipSetDevice(device);
+    if (s) hipStreamSynchronize(s);
+    for (sfmloc_context *c : ctx) sfmloc_context_destroy(c);
+    sfmloc_map_destroy(map);  // (null: nothing)
+  }
 };
 
 // The resident arrays as kernels take them, by value.  vlist = observation indices sorted by view, ascending landmark
@@ -207,7 +214,7 @@ int sfm_resect_gang(Sfm &h, const std::vector<uint32_t> &todo, const std::vector
       const uint32_t k = todo[g0 + i];
       rc = ctx_resection_wait_done(c);
       if (rc) return rc;
-      const HostResult *hr = reinterpret_cast<const HostResult *>(c->h_result);
+      const HostResult *hr = c->h_result;
       const Pose &p = hr->pose;
       SFM_CHECK((p.status & 4) == 0, SFMLOC_ECAP, "view %u: more correspondences than the P3P workspace holds",
                 h.h_view_id[k]);

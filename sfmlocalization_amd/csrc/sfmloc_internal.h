@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <exception>
 #include <new>
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,14 +29,19 @@ inline int env_int(const char *name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+// the SFMLOC code of a failed HIP call
+inline int hip_code(hipError_t e) {
+  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SFMLOC_ENODEV
+         : (e == hipErrorOutOfMemory)                          ? SFMLOC_ENOMEM
+                                                               : SFMLOC_EHIP;
+}
+
 #define SFM_HIP(call)                                                                          \
   do {                                                                                         \
     hipError_t e_ = (call);                                                                    \
     if (e_ != hipSuccess) {                                                                    \
       ::sfmloc::set_error("%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e_)); \
-      return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? SFMLOC_ENODEV           \
-             : (e_ == hipErrorOutOfMemory)                            ? SFMLOC_ENOMEM          \
-                                                                      : SFMLOC_EHIP;           \
+      return ::sfmloc::hip_code(e_);                                                           \
     }                                                                                          \
   } while (0)
 
@@ -69,6 +75,9 @@ inline int make_handle(const char *name, Opaque **out, Fill &&fill) {
   } catch (const std::bad_alloc &) {
     set_error("%s: out of host memory", name);
     rc = SFMLOC_ENOMEM;
+  } catch (const std::exception &e) {  // (host-side containers sized by the caller's counts: std::length_error)
+    set_error("%s: %s", name, e.what());
+    rc = SFMLOC_EINVAL;
   }
   if (rc) {
     delete h;
@@ -185,19 +194,12 @@ inline int dev_upload(uint64_t *acct, DevBuf<T> &p, const T *h, size_t n, hipStr
   return SFMLOC_OK;
 }
 
-// A call's stream and its two timing events, let go on every way out.  Declare it before the call's DevBuf locals: they
-// are destroyed first, while kernels on the stream may still run, which is safe because hipFree waits for the device;
-// the stream is drained and destroyed after them.
+// A call's stream and its two timing events, let go on every way out.  Declare it before the call's DevBuf locals
+// (devmem.h, order of destruction).
 struct CallScope {
-  hipStream_t s = nullptr;
-  CallScope() = default;
-  CallScope(const CallScope &) = delete;
-  CallScope &operator=(const CallScope &) = delete;
+  hipStream_t s = nullptr;  // (what the launchers read: own_'s, or the handle's)
   ~CallScope() {
-    if (s) hipStreamSynchronize(s);
-    if (e0_) hipEventDestroy(e0_);
-    if (e1_) hipEventDestroy(e1_);
-    if (own_ && s) hipStreamDestroy(s);
+    if (s) hipStreamSynchronize(s);  // a handle's stream too; then the events go, then a stream of its own
   }
   // `device` exists and is the current one
   static int use_device(int device) {
@@ -210,12 +212,11 @@ struct CallScope {
   }
   // a stream of its own on the current device, or a handle's; *ms: 0 now, and time_end's figure if `timed`
   int open(bool timed, double *ms, hipStream_t borrowed = nullptr) {
-    own_ = !borrowed;
-    if (borrowed) s = borrowed;
-    else SFM_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (!borrowed) SFM_RC(own_.create());
+    s = borrowed ? borrowed : own_.get();
     if (timed) {
-      SFM_HIP(hipEventCreate(&e0_));
-      SFM_HIP(hipEventCreate(&e1_));
+      SFM_RC(e0_.create(kTimingEvent));
+      SFM_RC(e1_.create(kTimingEvent));
     }
     ms_ = ms;
     *ms_ = 0.0;
@@ -236,8 +237,8 @@ struct CallScope {
   }
 
  private:
-  hipEvent_t e0_ = nullptr, e1_ = nullptr;
-  bool own_ = false;
+  Stream own_;
+  Event e0_, e1_;
   double *ms_ = nullptr;
 };
 
@@ -305,9 +306,9 @@ struct Map {
 // of one map run concurrently (the latency-bound RANSAC stages of one query overlap the VALU-bound
 // Hamming kernel of another).
 struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
+  Stream own_stream;  // what stream.own reads: its own, or borrowed from `lender` (first: devmem.h, order of destruction)
   Map *map = nullptr;
-  bool stream_borrowed = false;    // stream.own belongs to `lender` (sfmloc_context_create_sharing)
-  Ctx *lender = nullptr;
+  Ctx *lender = nullptr;           // the context whose stream this one works on (sfmloc_context_create_sharing)
   bool merge_only = false;         // no workspace of the matching stages (sfmloc_context_create_merge)
   int borrowers = 0;               // contexts working on this one's stream
   bool zombie = false;             // destroyed while lent out: freed with its last borrower
@@ -319,7 +320,7 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   DevBuf<uint32_t> d_view_sel;  // [n_views] selected view indices
   DevBuf<uint32_t> d_view_widx0;  // [n_views] work-block index of each selected view's first bank block
   DevBuf<uint32_t> d_block_list;  // [n_blocks]
-  uint32_t *h_pinned = nullptr;     // pinned staging: view_sel | view_widx0 | block_list
+  HostBuf<uint32_t> h_pinned;  // pinned staging: view_sel | view_widx0 | block_list
   DevBuf<uint32_t> d_view_count;  // [n_views]
   DevBuf<uint32_t> d_match_i;  // [n_rows]
   DevBuf<uint32_t> d_match_key;  // [n_rows]  (d0<<16)|j0
@@ -398,9 +399,9 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   DevBuf<uint32_t> d_bow_dist;  // [n_views]
   DevBuf<uint32_t> d_bow_cand;  // [n_views]
   DevBuf<uint32_t> d_bow_sel;  // [n_views]
-  void *h_result = nullptr;  // pinned: what a finished query copies back in one go (capi.hip HostResult)
-  hipEvent_t pinned_busy = nullptr;  // recorded after the last upload out of h_pinned
-  hipEvent_t xev_out = nullptr, xev_in = nullptr;  // ordering against a caller's stream (sfmloc_context_signal / _wait)
+  HostBuf<HostResult> h_result;  // pinned: what a finished query copies back in one go
+  Event pinned_busy;  // recorded after the last upload out of h_pinned
+  Event xev_out, xev_in;  // ordering against a caller's stream (sfmloc_context_signal / _wait)
 
   // What the context remembers from one call to the next.  last_*: the last putative call, which the staged API's
   // later stages and readers work on.  k1_may_slice (and p3p_small above) hold from a query's begin to its end;
@@ -424,8 +425,8 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
 
   // --- measurement ---
   sfmloc_kernel_stats stats{};
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_events;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
+  std::vector<std::pair<int, EventPair>> pending_events;
+  std::vector<EventPair> event_pool;
 };
 
 // A launch of a kernel that has a gang form (Body: the kernel's body, gang.h): issued at once on the context's stream,
@@ -527,6 +528,7 @@ int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t
 
 // bow.hip
 struct BofModel {
+  Stream stream;  // created by the first sfmloc_bof_compute (a model inside a sfmloc_imgbow works on that object's)
   int device = 0;
   int K = 0, cdim = 0, in_dim = 0, n_pca = 0, resized = 300, levels = 2, norm_type = 2, cells = 5;
   DevBuf<float> d_centers, d_pca_mean, d_pca_evec, d_pca_eval;
@@ -534,7 +536,6 @@ struct BofModel {
   DevBuf<uint32_t> d_counts;
   DevBuf<double> d_out;
   DevBuf<float> d_desc, d_kxy;  // a call's descriptors and points: regrown together (sfmloc_bof_compute)
-  hipStream_t stream = nullptr;
 };
 struct ChainArgs;  // chain_device.h: what the shortlist's workgroup does on top of the shortlist (may be null)
 int launch_bow_select(Ctx *c, const float *d_query, const uint32_t *d_cand, uint32_t n_cand,

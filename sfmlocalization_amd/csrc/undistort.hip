@@ -21,6 +21,7 @@ namespace {
 constexpr int kInterBits = 5, kInterTab = 1 << kInterBits;
 
 struct Undistorter {
+  Stream stream;  // created with the maps' upload, at the first image (before the buffers: devmem.h)
   int device = 0;
   uint32_t w = 0, h = 0;
   double new_camera[9];
@@ -30,7 +31,6 @@ struct Undistorter {
   DevBuf<short2> d_xy;  // the map pair: on the device together or not at all
   DevBuf<uint16_t> d_frac;
   DevBuf<uint8_t> d_src, d_dst;
-  hipStream_t stream = nullptr;
 };
 
 void dist8(const double *dist, uint32_t n, double *k) {
@@ -204,30 +204,27 @@ extern "C" int sfmloc_undistorter_create(int device, const double *K, const doub
   SFM_CHECK(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8, SFMLOC_EINVAL,
             "sfmloc_undistorter_create: %u distortion coefficients (4, 5 or 8: k1 k2 p1 p2 [k3 [k4 k5 k6]])", n_dist);
   SFM_CHECK(K[0] != 0.0 && K[4] != 0.0, SFMLOC_EINVAL, "sfmloc_undistorter_create: zero focal length");
-  Undistorter *u = new (std::nothrow) Undistorter;
-  SFM_CHECK(u, SFMLOC_ENOMEM, "sfmloc_undistorter_create: out of host memory");
-  u->device = device;
-  u->w = width;
-  u->h = height;
-  double k[8];
-  dist8(dist, n_dist, k);
-  optimal_new_camera(K, k, (int)width, (int)height, 1.0, u->new_camera, u->roi);
-  const size_t n = (size_t)width * height;
-  u->h_xy.resize(2 * n);
-  u->h_frac.resize(n);
-  build_maps(K, k, u->new_camera, (int)width, (int)height, u->h_xy.data(), u->h_frac.data());
-  *out = reinterpret_cast<sfmloc_undistorter *>(u);
-  return SFMLOC_OK;
+  return make_handle<Undistorter>("sfmloc_undistorter_create", out, [&](Undistorter *u) -> int {
+    u->device = device;
+    u->w = width;
+    u->h = height;
+    double k[8];
+    dist8(dist, n_dist, k);
+    optimal_new_camera(K, k, (int)width, (int)height, 1.0, u->new_camera, u->roi);
+    const size_t n = (size_t)width * height;
+    u->h_xy.resize(2 * n);
+    u->h_frac.resize(n);
+    build_maps(K, k, u->new_camera, (int)width, (int)height, u->h_xy.data(), u->h_frac.data());
+    return SFMLOC_OK;
+  });
 }
 
 extern "C" void sfmloc_undistorter_destroy(sfmloc_undistorter *handle) {
   Undistorter *u = reinterpret_cast<Undistorter *>(handle);
   if (!u) return;
   if (u->d_xy || u->d_src || u->stream) hipSetDevice(u->device);
-  const hipStream_t s = u->stream;
-  if (s) hipStreamSynchronize(s);
+  if (u->stream) hipStreamSynchronize(u->stream);
   delete u;  // (its buffers go before its stream)
-  if (s) hipStreamDestroy(s);
 }
 
 extern "C" int sfmloc_undistorter_info(const sfmloc_undistorter *handle, double *new_camera, int32_t *roi) {
@@ -261,7 +258,7 @@ extern "C" int sfmloc_undistorter_apply(sfmloc_undistorter *handle, const uint8_
   SFM_HIP(hipSetDevice(u->device));
   if (!u->d_xy) {  // first image: the maps go to the device (the plan itself is host arithmetic and needs none)
     const size_t n = (size_t)u->w * u->h;
-    if (!u->stream) SFM_HIP(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking));
+    SFM_RC(u->stream.ensure());
     DevGroup g(nullptr);
     g.add(u->d_xy, n);
     g.add(u->d_frac, n);

@@ -1,10 +1,15 @@
 // Host check of the device-memory owners (sfmlocalization_amd/csrc/devmem.h, the header Map, Ctx and Query are built
 // from): raw allocation is supplied here over malloc, with a count of live allocations, the account the buffers are
 // charged to, and an index at which the next allocations fail -- so every expectation below is a literal.
+// The owners of streams, events and pinned host memory (same header) are checked the same way: their raw functions are
+// counters here, and every raw call -- dev_raw_free included -- leaves a letter in a log, so the order of a struct's
+// destruction reads as a string.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../sfmlocalization_amd/csrc/devmem.h"
 
@@ -22,10 +27,56 @@ int dev_raw_alloc(void **p, size_t bytes) {
   ++g_live;
   return 0;
 }
+}  // namespace sfmloc
+
+// streams, events, pinned blocks: live counts, and the log of raw calls -- 'F' dev_raw_free, 'S' stream created, 'y'
+// synchronised, 's' destroyed, 'E' / 'e' event created / destroyed, 'H' / 'h' pinned block allocated / freed
+static int g_streams = 0, g_events = 0, g_blocks = 0;
+static int g_timing_events = 0;  // events created with the timing flag
+static int g_fail_raw = 0;       // the next raw creation of a stream, event or pinned block fails with this code
+static std::string g_log;
+static int raw_create(void **h, int *live, char letter, size_t bytes) {
+  *h = nullptr;
+  if (g_fail_raw) {
+    const int rc = g_fail_raw;
+    g_fail_raw = 0;
+    return rc;
+  }
+  *h = malloc(bytes);  // (a distinct address per handle; a double release is a double free under a sanitizer)
+  ++*live;
+  g_log += letter;
+  return 0;
+}
+
+namespace sfmloc {
 void dev_raw_free(void *p) {
   g_last_freed = p;
   ++g_frees;
   --g_live;
+  g_log += 'F';
+  free(p);
+}
+int stream_raw_create(void **s) { return raw_create(s, &g_streams, 'S', 1); }
+void stream_raw_sync(void *) { g_log += 'y'; }
+void stream_raw_destroy(void *s) {
+  --g_streams;
+  g_log += 's';
+  free(s);
+}
+int event_raw_create(void **e, bool timing) {
+  const int rc = raw_create(e, &g_events, 'E', 1);
+  if (!rc && timing) ++g_timing_events;
+  return rc;
+}
+void event_raw_destroy(void *e) {
+  --g_events;
+  g_log += 'e';
+  free(e);
+}
+int host_raw_alloc(void **p, size_t bytes) { return raw_create(p, &g_blocks, 'H', bytes); }
+void host_raw_free(void *p) {
+  --g_blocks;
+  g_log += 'h';
   free(p);
 }
 }  // namespace sfmloc
@@ -39,6 +90,12 @@ template <class T>
 struct AddressTaken<T, std::void_t<decltype(&std::declval<T &>())>> : std::true_type {};
 static_assert(AddressTaken<int>::value && !AddressTaken<DevBuf<int>>::value && !AddressTaken<DevMem>::value,
               "operator& of a device buffer is deleted");
+static_assert(!AddressTaken<Stream>::value && !AddressTaken<Event>::value && !AddressTaken<HostBuf<double>>::value,
+              "operator& of a stream, an event or a pinned block is deleted");
+static_assert(!std::is_copy_constructible<Stream>::value && !std::is_copy_assignable<Event>::value &&
+                  !std::is_copy_constructible<HostBuf<int>>::value && std::is_nothrow_move_constructible<Event>::value &&
+                  std::is_nothrow_move_constructible<EventPair>::value,
+              "the owners are move-only");
 
 static int g_failed = 0;
 #define CHECK(cond)                                                 \
@@ -198,7 +255,176 @@ static void test_zero_length() {
   CHECK(a.get() == nullptr && a.bytes() == 0 && acct == 0 && g_live == 0);
 }
 
+// ---- streams, events, pinned host memory ----
+
+// (a) each owner releases exactly once: at scope exit, after reset() and after a move; a moved-from owner releases nothing
+static void test_owners_release_once() {
+  g_log.clear();
+  {
+    Stream s;
+    Event e;
+    HostBuf<double> h;
+    CHECK(!s && !e && !h && g_log.empty());  // nothing is created by a constructor
+    CHECK(s.create() == 0 && e.create(kTimingEvent) == 0 && h.alloc(4) == 0);
+    CHECK(s && e && h && g_streams == 1 && g_events == 1 && g_blocks == 1 && g_timing_events == 1);
+    ihipStream_t *raw_s = s;  // read as the raw handles they replace
+    ihipEvent_t *raw_e = e;
+    double *raw_h = h;
+    CHECK(raw_s == s.get() && raw_e == e.get() && raw_h == h.get());
+    h[3] = 2.5;  // (a pinned block is host memory of that many elements)
+    CHECK(h.get()[3] == 2.5);
+    CHECK(s.ensure() == 0 && e.ensure(kTimingEvent) == 0 && s.get() == raw_s && e.get() == raw_e);  // ensure: once
+  }
+  CHECK(g_log == "SEHheys");  // scope exit, in reverse: the block, the event, the stream synchronised then destroyed
+  CHECK(g_streams == 0 && g_events == 0 && g_blocks == 0);
+  g_log.clear();
+  {
+    Stream s;
+    Event e;
+    HostBuf<int> h;
+    CHECK(s.ensure() == 0 && e.ensure(kOrderingEvent) == 0 && h.alloc(1) == 0 && g_timing_events == 1);
+    s.reset();
+    e.reset();
+    h.reset();
+    CHECK(g_log == "SEHyseh" && !s && !e && !h);
+    s.reset();
+    e.reset();
+    h.reset();
+  }
+  CHECK(g_log == "SEHyseh");  // reset twice and the destructors: nothing more
+  g_log.clear();
+  {
+    Stream a;
+    Event b;
+    HostBuf<int> c;
+    CHECK(a.create() == 0 && b.create(kOrderingEvent) == 0 && c.alloc(2) == 0);
+    ihipStream_t *const ra = a;
+    {
+      Stream a2(std::move(a));
+      Event b2;
+      b2 = std::move(b);
+      HostBuf<int> c2(std::move(c));
+      CHECK(!a && !b && !c && a2.get() == ra && b2 && c2 && g_log == "SEH");
+      a.reset();
+      b.reset();
+      c.reset();
+      CHECK(g_log == "SEH");  // moved-from: nothing to release
+      Event b3;
+      CHECK(b3.create(kOrderingEvent) == 0);
+      b3 = std::move(b2);  // over a live owner: its own event goes, the other moves in
+      CHECK(g_log == "SEHEe" && g_events == 1 && !b2);
+    }
+    CHECK(g_log == "SEHEe" "ehys");  // b3, c2, a2 -- and b2 released nothing
+  }
+  CHECK(g_log == "SEHEe" "ehys" && g_streams == 0 && g_events == 0 && g_blocks == 0);
+  g_log.clear();
+  {
+    Stream s;
+    CHECK(s.create() == 0 && s.create() == 0);  // creating again lets the previous one go
+    CHECK(g_log == "SysS" && g_streams == 1);
+  }
+  CHECK(g_streams == 0);
+}
+
+// (b) a failed creation answers the raw function's code and leaves the owner empty
+static void test_owner_failed_creation() {
+  g_log.clear();
+  Stream s;
+  Event e;
+  HostBuf<float> h;
+  g_fail_raw = -5;
+  CHECK(s.create() == -5 && !s);
+  g_fail_raw = -6;
+  CHECK(e.ensure(kTimingEvent) == -6 && !e);
+  g_fail_raw = -2;
+  CHECK(h.alloc(8) == -2 && !h);
+  CHECK(g_log.empty() && g_streams == 0 && g_events == 0 && g_blocks == 0);
+  CHECK(s.create() == 0);  // ... also over a live owner: the old handle goes, the owner is empty, nothing leaks
+  g_fail_raw = -5;
+  CHECK(s.create() == -5 && !s && g_log == "Sys" && g_streams == 0);
+  CHECK(s.ensure() == 0 && s);  // (and an empty owner can be created later)
+}
+
+// (c) a borrowed stream is never synchronised or destroyed
+static void test_borrowed_stream() {
+  g_log.clear();
+  {
+    Stream lender;
+    CHECK(lender.create() == 0);
+    {
+      Stream b;
+      b.borrow(lender);
+      CHECK(b.get() == lender.get() && b.ensure() == 0 && g_log == "S");  // (ensure: it has one)
+      Stream b2(std::move(b));
+      CHECK(!b && b2.get() == lender.get());
+      b2.reset();
+      b2.borrow(lender);
+    }
+    CHECK(g_log == "S" && g_streams == 1);
+    Stream own;
+    CHECK(own.create() == 0);
+    own.borrow(lender);  // (its own stream goes, the borrowed one is not its to release)
+    CHECK(g_log == "SSys" && g_streams == 1);
+  }
+  CHECK(g_log == "SSysys" && g_streams == 0);  // only the lender's own
+}
+
+// (d) a handle's stream is declared before its buffers: both are freed before the stream is synchronised and destroyed
+static void test_destruction_order() {
+  struct Handle {
+    Stream stream;
+    DevBuf<float> a;
+    DevBuf<int> b;
+  };
+  g_log.clear();
+  {
+    Handle h;
+    CHECK(h.stream.create() == 0 && h.a.alloc(nullptr, 3) == 0 && h.b.alloc(nullptr, 5) == 0);
+  }
+  CHECK(g_log == "SFFys" && g_live == 0 && g_streams == 0);
+}
+
+// (e) a vector of event pairs: all destroyed when the vector goes, none twice after push_back reallocates
+static void test_event_pairs() {
+  g_log.clear();
+  {
+    std::vector<EventPair> pool;
+    for (int i = 0; i < 9; ++i) {  // (capacity 1, 2, 4, 8, 16: four reallocations)
+      EventPair p;
+      CHECK(p.a.create(kTimingEvent) == 0 && p.b.create(kTimingEvent) == 0);
+      pool.push_back(std::move(p));
+    }
+    CHECK(g_events == 18 && g_log == std::string(18, 'E'));  // moved, never released, by the reallocations
+    std::vector<std::pair<int, EventPair>> pending;
+    pending.emplace_back(3, std::move(pool.back()));
+    pool.pop_back();
+    CHECK(g_events == 18 && pool.size() == 8 && pending[0].second.a && pending[0].second.b);
+    pool.push_back(std::move(pending[0].second));  // (drained: back into the pool; the moved-from entry is cleared later)
+    pending.clear();
+    CHECK(g_events == 18 && g_log == std::string(18, 'E'));
+  }
+  CHECK(g_events == 0 && g_log == std::string(18, 'E') + std::string(18, 'e'));
+}
+
+// (f) a pinned block of zero length is empty, and no error
+static void test_pinned_zero_length() {
+  g_log.clear();
+  HostBuf<uint32_t> z;
+  g_fail_raw = -2;  // (the raw allocator is not even asked)
+  CHECK(z.alloc(0) == 0 && !z && g_fail_raw == -2);
+  g_fail_raw = 0;
+  CHECK(z.alloc(3) == 0 && z && z.alloc(0) == 0 && !z);  // ... and lets a previous block go
+  CHECK(g_log == "Hh" && g_blocks == 0);
+}
+
 int main() {
+  test_owners_release_once();
+  test_owner_failed_creation();
+  test_borrowed_stream();
+  test_destruction_order();
+  test_event_pairs();
+  test_pinned_zero_length();
+  g_log.clear();
   test_charge_and_refund();
   test_moved_from();
   test_borrowed();

@@ -1,7 +1,10 @@
 """CPU: the owners of device memory that Map, Ctx and Query are built from (sfmlocalization_amd/csrc/devmem.h: DevBuf,
 DevGroup) charge and refund their account, never free a borrowed pointer, and a group that fails part-way leaves its
 owners, the account and the count of live allocations exactly as they were -- checked by a host program
-(tests/cpp/devmem.cpp) that includes the header the library includes and supplies raw allocation over malloc."""
+(tests/cpp/devmem.cpp) that includes the header the library includes and supplies raw allocation over malloc.  The same
+program checks the header's owners of streams, events and pinned host memory (Stream, Event, HostBuf) over counters and a
+log of raw calls: released exactly once, empty after a failed creation, a borrowed stream never touched, a handle's
+buffers freed before its stream goes."""
 import os
 import shutil
 import subprocess

@@ -167,10 +167,11 @@ def test_bowtrainer_kmeans():
         assert got[2] == ref[2]
 
 
-def _create_walk(create, at_least):
-    """a C create call with allocation k failing -> the handle of the first that succeeds; every failure: ENOMEM, no handle"""
+def _create_walk(create, at_least, limit=MAX_K, start=None):
+    """a C create call with allocation k failing -> the handle of the first that succeeds; every failure: ENOMEM, no handle
+    and, with `start`, the device's free memory at that figure again (nothing of the refused create is left)"""
     try:
-        for k in range(MAX_K):
+        for k in range(limit):
             h = C.c_void_p()
             S.debug_fail_next_alloc(k)
             rc = create(C.byref(h))
@@ -181,7 +182,9 @@ def _create_walk(create, at_least):
                 assert k >= at_least, "only %d allocations failed, the create makes at least %d" % (k, at_least)
                 return h
             assert rc == S.ENOMEM and not h.value, (k, rc, S._L().sfmloc_last_error())
-        pytest.fail("still failing after %d injected failures" % MAX_K)
+            if start is not None:
+                assert free_device_bytes() == start, (k, free_device_bytes() - start)
+        pytest.fail("still failing after %d injected failures" % limit)
     finally:
         S.debug_fail_next_alloc(-1)
 
@@ -278,3 +281,189 @@ def test_imgbow_create_leaves_no_handle():
     ib.dim = int(L.sfmloc_imgbow_dim(h))
     same(ib.compute(img), ref)
     ib.close()
+
+
+# ---- the handles a query runs on: sfmloc_map_create, the three context creates, sfmloc_query_create ----
+
+class _QuerySide:
+    """Six views of 100 rows (600 rows: nine full 64-row blocks and one of 24, so the padded paths run) with every
+    optional array of a map and 4-entry BoW vectors; one query of 150 rows that localises on it.  `ref`: the query's
+    fingerprint on a map and a context that no injected failure ever touched, `ref_merged`: the same through one exported
+    candidate part and a merge-only context; computed once, never changed."""
+    CAP = 4096                                          # candidates a part holds (the query has 150 features)
+
+    def __init__(self):
+        import torch
+        import synthdata as synth
+        self.m = m = synth.make_map(61, n_views=6, desc_per_view=100, views_per_place=6, landmarks_per_place=150,
+                                    obs_per_view=90)
+        assert m.n_rows == 600
+        self.bow = np.random.default_rng(61).uniform(0, 1, (6, 4)).astype(np.float32)
+        self.q = synth.make_query(m, 62, n_feat=150, n_copies=110, outlier_frac=0.2)
+        self.params = S.default_params(ransac_round=25)
+        self.part = torch.zeros(S.part_bytes(self.CAP), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        with self.fresh_map() as dm:
+            dq = self.query(dm)
+            c = dm.context()
+            self.ref = self.localise(c, dq)
+            pose = dm.localize(dq)[0]
+            assert pose.ok and pose.n_inliers >= 10      # the map is small, not degenerate
+            assert S.result_fingerprint(*dm.localize(dq)) == self.ref
+            mc = dm.context(merge_only=True)
+            self.ref_merged = self.localise_merged(c, mc, dq)
+            for h in (mc, c, dq):
+                h.close()
+        print("query-side reference fingerprints:", self.ref.hex(), self.ref_merged.hex())
+
+    def map_arrays(self):
+        m = self.m
+        return dict(view_id=m.view_id, view_off=m.view_off, desc=m.desc, view_wh=m.view_wh, kpt_xy=m.kpt_xy,
+                    row_landmark=m.row_landmark, landmark_id=m.landmark_id, landmark_X=m.landmark_X, intrinsic=m.intrinsic,
+                    bow=self.bow)
+
+    def fresh_map(self):
+        return S.Map(params=self.params, **self.map_arrays())
+
+    def map_desc(self):
+        """-> (sfmloc_map_desc of map_arrays(), the arrays it points into), as capi.Map fills it"""
+        a = self.map_arrays()
+        keep = [np.ascontiguousarray(a["view_id"], np.uint32), np.ascontiguousarray(a["view_off"], np.uint32),
+                np.ascontiguousarray(a["desc"], np.uint8).reshape(-1, 64), np.ascontiguousarray(a["view_wh"], np.uint32),
+                np.ascontiguousarray(a["kpt_xy"], np.float32), np.ascontiguousarray(a["row_landmark"], np.int32),
+                np.ascontiguousarray(a["landmark_id"], np.uint32), np.ascontiguousarray(a["landmark_X"], np.float64),
+                np.ascontiguousarray(a["bow"], np.float32)]
+        d = S.MapDesc()
+        d.n_views, d.n_rows, d.n_landmarks, d.bow_dim = 6, 600, keep[6].shape[0], 4
+        d.view_id, d.view_off = S._ptr(keep[0], C.c_uint32), S._ptr(keep[1], C.c_uint32)
+        d.desc, d.view_wh = S._ptr(keep[2], C.c_uint8), S._ptr(keep[3], C.c_uint32)
+        d.kpt_xy, d.row_landmark = S._ptr(keep[4], C.c_float), S._ptr(keep[5], C.c_int32)
+        d.landmark_id, d.landmark_X = S._ptr(keep[6], C.c_uint32), S._ptr(keep[7], C.c_double)
+        d.bow = S._ptr(keep[8], C.c_float)
+        d.focal, d.ppx, d.ppy = a["intrinsic"][:3]
+        return d, keep
+
+    def query(self, dm):
+        return dm.query(self.q.desc, self.q.kpt_xy, self.q.width, self.q.height)
+
+    @staticmethod
+    def localise(c, dq):
+        c.begin(dq)
+        return S.result_fingerprint(*c.end())
+
+    def localise_merged(self, c, mc, dq):
+        """K1 .. K3 and the candidates on `c`, the merge and the resection on the merge-only context `mc`"""
+        c.shard_begin(dq)
+        c.shard_export(self.part.data_ptr(), self.CAP)
+        c.sync()
+        mc.merge_begin(dq, self.part.data_ptr(), 1, self.CAP)
+        return S.result_fingerprint(*mc.end())
+
+
+@pytest.fixture(scope="module")
+def query_side():
+    return _QuerySide()
+
+
+def _adopt(cls, m, h):
+    """the capi object of a handle that a C create call handed out"""
+    o = cls.__new__(cls)
+    o._h, o.map = h, m
+    m._children.add(o)
+    return o
+
+
+def test_map_create_leaves_nothing_behind(query_side):
+    """(Free memory is compared after refusals only: a first localisation on a new stream makes the runtime keep scratch
+    memory for its hardware queue, which is no array of the library's.)  sfmloc_map_create with every optional array: the bank and its staging copy, the three view tables, the keypoints,
+    the three landmark arrays, the BoW vectors, the log10 and the ratio table (capi.hip map_fill): 12; then the map's own
+    context as in test_context_creates_leave_nothing_behind: 44; fifty-six in all: 56"""
+    import weakref
+    w = query_side
+    L = S._L()
+    w.fresh_map().close()                               # (what the runtime keeps for itself is there after one good create)
+    start = free_device_bytes()
+    d, keep = w.map_desc()
+    h = _create_walk(lambda out: L.sfmloc_map_create(C.byref(d), C.byref(w.params), out), 56, start=start)
+    dm = S.Map.__new__(S.Map)
+    dm._h, dm._children, dm.params = h, weakref.WeakSet(), w.params
+    dm.view_id, dm.view_off, dm.n_rows, dm.n_views = keep[0], keep[1], 600, 6
+    dq = w.query(dm)
+    assert S.result_fingerprint(*dm.localize(dq)) == w.ref
+    dq.close()
+    dm.close()
+
+
+def test_context_creates_leave_nothing_behind(query_side):
+    """make_ctx (capi.hip) on a map with bank rows and BoW vectors: 33 arrays, the P3P group of seven and the four of the
+    shortlist: 44, for sfmloc_context_create and for sfmloc_context_create_sharing alike (a borrowed stream changes no
+    array).  sfmloc_context_create_merge leaves out the eleven per-bank-row arrays of the matching stages: 33"""
+    w = query_side
+    L = S._L()
+    with w.fresh_map() as dm:
+        dq = w.query(dm)
+        lead = dm.context()
+        for c in (dm.context(), dm.context(share=lead), dm.context(share=lead, merge_only=True)):
+            c.close()                                   # one good create / destroy of each kind
+        start = free_device_bytes()
+        h = _create_walk(lambda out: L.sfmloc_context_create(dm._h, out), 44, start=start)
+        plain = _adopt(S.Context, dm, h)
+        assert w.localise(plain, dq) == w.ref
+        plain.close()
+        start = free_device_bytes()                     # (again: see test_map_create_leaves_nothing_behind)
+        h = _create_walk(lambda out: L.sfmloc_context_create_sharing(dm._h, lead._h, out), 44, start=start)
+        sharing = _adopt(S.Context, dm, h)
+        assert w.localise(sharing, dq) == w.ref
+        sharing.close()
+        start = free_device_bytes()
+        h = _create_walk(lambda out: L.sfmloc_context_create_merge(dm._h, lead._h, out), 33, start=start)
+        merging = _adopt(S.Context, dm, h)
+        assert w.localise_merged(lead, merging, dq) == w.ref_merged
+        merging.close()
+        lead.close()
+        dq.close()
+
+
+def test_query_create_leaves_nothing_behind(query_side):
+    """sfmloc_query_create with keypoints: the descriptors and the keypoints before and after the .feat round trip: 3"""
+    w = query_side
+    L = S._L()
+    desc = np.ascontiguousarray(w.q.desc, np.uint8).reshape(-1, 64)
+    kpt = np.ascontiguousarray(w.q.kpt_xy, np.float32).reshape(-1, 2)
+    assert desc.shape[0] == 150                         # (not a multiple of 64: the descriptors are padded to 192 rows)
+    with w.fresh_map() as dm:
+        w.query(dm).close()
+        start = free_device_bytes()
+        h = _create_walk(lambda out: L.sfmloc_query_create(dm._h, S._ptr(desc, C.c_uint8), S._ptr(kpt, C.c_float), 150,
+                                                           w.q.width, w.q.height, out), 3, start=start)
+        dq = _adopt(S.Query, dm, h)
+        dq.n = 150
+        assert S.result_fingerprint(*dm.localize(dq)) == w.ref
+        dq.close()
+
+
+def test_lender_destroyed_before_its_borrower(query_side):
+    """A lends its stream to B and is destroyed first: B still localises, bit for bit as a plain context does, and when B
+    goes the lender's arrays and stream go with it -- the device's free memory is back where it started.
+    (tests/test_gpu_gang.py destroys a lender before its borrowers too, but looks at neither the bits nor the memory.)"""
+    w = query_side
+    with w.fresh_map() as dm:
+        dq = w.query(dm)
+
+        def round_trip():
+            a = dm.context()
+            b = dm.context(share=a)
+            a.close()
+            held = free_device_bytes()                  # (the lender is kept while its stream is lent out)
+            got = w.localise(b, dq)
+            b.close()
+            return held, got
+
+        # one good round first: what the runtime keeps for itself from then on (the scratch memory of the hardware queue
+        # the lender's stream runs on comes with the first resection there) is in the starting figure
+        assert round_trip()[1] == w.ref
+        start = free_device_bytes()
+        held, got = round_trip()
+        assert got == w.ref and held < start
+        assert free_device_bytes() == start
+        dq.close()
