@@ -101,16 +101,22 @@ def shard_candidates(m, q_desc, q_kpt, q_wh, v0, v1, view_sel=None, **kw):
     out = []
     if r is not None:
         cnt, mi, mj, md = r["put_count"], r["put_i"], r["put_j"], r["put_d"]
+        guided = bool(kw.get("guided", False))
         for v in (int(x) for x in sel):
             gc = int(r["geo_count"][v])
             off = int(m.view_off[v])
             for p in range(gc):
-                pp = int(r["geo_idx"][off + p])
-                i, j = int(mi[off + pp]), int(mj[off + pp])
+                if guided:      # -gm: (geo_idx, geo_j) = (map feature, query feature) of the view's p-th guided match
+                    i, j = int(r["geo_idx"][off + p]), int(r["geo_j"][off + p])
+                else:
+                    pp = int(r["geo_idx"][off + p])
+                    i, j = int(mi[off + pp]), int(mj[off + pp])
                 lm = int(m.row_landmark[off + i])
                 if lm < 0:
                     continue
                 same = np.nonzero(mj[off:off + int(cnt[v])] == j)[0]
+                if len(same) == 0:      # only a guided match: featDist has no entry for j (SfMDataUtils.cpp:105-106)
+                    continue
                 dist = int(md[off + same[-1]])                      # featDist: last putative with this j
                 out.append((D.order_key(dist, int(m.view_id[v]), p), j, int(m.landmark_id[lm]), tuple(m.landmark_X[lm])))
     return np.array(out, dtype=D.CANDIDATE_DTYPE)

@@ -240,9 +240,10 @@ def guided_match(F_norm, errmax_norm, wh1, wh2, xy1, desc1, xy2, desc2, dist_rat
     lines = x1 @ F.T                                   # epipolar line of every feature of image 1 in image 2
     num = lines @ x2.T                                 # [n1, n2]
     e = num * num / (lines[:, 0] ** 2 + lines[:, 1] ** 2)[:, None]
-    b1 = np.unpackbits(np.asarray(desc1, np.uint8).reshape(-1, 64), axis=1).astype(np.int32)
-    b2 = np.unpackbits(np.asarray(desc2, np.uint8).reshape(-1, 64), axis=1).astype(np.int32)
-    ham = b1.sum(1)[:, None] + b2.sum(1)[None, :] - 2 * (b1 @ b2.T)
+    # (bit counts are at most 512, so the float32 product is exact -- and a BLAS call, where an integer one is a loop)
+    b1 = np.unpackbits(np.asarray(desc1, np.uint8).reshape(-1, 64), axis=1).astype(np.float32)
+    b2 = np.unpackbits(np.asarray(desc2, np.uint8).reshape(-1, 64), axis=1).astype(np.float32)
+    ham = (b1.sum(1)[:, None] + b2.sum(1)[None, :] - 2.0 * (b1 @ b2.T)).astype(np.int64)
     d2 = np.where(e < thr, (ham * ham).astype(np.float64), np.inf)
     oi, oj = [], []
     for i in range(d2.shape[0]):

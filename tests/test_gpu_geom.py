@@ -500,7 +500,9 @@ def test_guided_matching_in_the_query_path(oracle_c):
     """params.guided_matching (-gm, localization.cpp:82,183,451 / LocalizeEngine.cc:459): every view that passes the
     F-matrix filter gets OpenMVG's guided matches under its estimated F; the 2D-3D set then keeps a guided match only when
     its query feature has a putative distance for that view (featDist, SfMDataUtils.cpp:105-106).  Stage lists, the
-    2D-3D set, inliers and pose against the oracle, bit for bit; a radial intrinsic and the sharded path included."""
+    2D-3D set, inliers and pose against the oracle, bit for bit; a radial intrinsic included.  (One scene shape, the whole
+    map, one context: the K3 forms, tile edges, K4 look-ups, the sharded export, gang sessions and the pair path with guided
+    matching on are tests/test_gpu_guided.py's.)"""
     for seed, radial in ((61, False), (62, True)):
         m = make_scene(seed)
         if radial:
