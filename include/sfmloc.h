@@ -1672,6 +1672,12 @@ void sfmloc_debug_fail_next_alloc(int k);
  * the model again for it, on `device`, by every map of the process since the last reset (reset != 0 clears both after
  * reading; out may be null).  Synchronises the device.  For tests: the two ways give the same list. */
 int sfmloc_debug_k3_list_counts(int device, uint64_t *out, int reset);
+/* The view list the context's last begin (sfmloc_localize[_bow]_begin, sfmloc_shard_begin[_bow], inside a finished gang
+ * session or not) worked on, read back after synchronising the context's stream: *n entries into views -- ascending view
+ * indices; a sharded shortlist's padding appears as written, as the phantom index n_views; every view in order when the
+ * begin took all views.  SFMLOC_ECAP, with *n set, when cap < *n.  For tests: the selection a shortlist built on the
+ * device never reaches the host otherwise. */
+int sfmloc_debug_context_views(sfmloc_context *ctx, uint32_t *views, uint32_t cap, uint32_t *n);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement (params.profile = 1): accumulated HIP-event time per kernel on  */

@@ -1774,6 +1774,14 @@ class Context:
     def sync(self):
         _check(_L().sfmloc_context_sync(self._h))
 
+    def debug_views(self):
+        """sfmloc_debug_context_views: the view list the last begin worked on (a sharded shortlist's phantom padding,
+        index n_views, as written)."""
+        n = C.c_uint32()
+        out = np.zeros(self.map.n_views + 1, np.uint32)
+        _check(_L().sfmloc_debug_context_views(self._h, _ptr(out, C.c_uint32), out.shape[0], C.byref(n)))
+        return out[:n.value].copy()
+
     def merge_begin(self, q, parts_dev_ptr, n_parts, cap, part_stride=0):
         _check(_L().sfmloc_merge_begin(self._h, q._h, C.c_void_p(parts_dev_ptr), n_parts, cap, part_stride))
 

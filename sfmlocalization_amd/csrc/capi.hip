@@ -251,8 +251,8 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
     SFM_RC(dev_alloc(acct, c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
     SFM_HIP(hipMemset(c->d_rows_arrivals, 0, (size_t)c->rows_chunk_cap * sizeof(uint32_t)));
   }
-  SFM_RC(dev_alloc(acct, c->d_k1_counters, (size_t)2 * kK1CounterSlots));
-  SFM_HIP(hipMemset(c->d_k1_counters, 0, 2 * kK1CounterSlots * sizeof(unsigned long long)));
+  SFM_RC(dev_alloc(acct, c->d_k1_counters, (size_t)kSelPairsSlot + 1));
+  SFM_HIP(hipMemset(c->d_k1_counters, 0, (kSelPairsSlot + 1) * sizeof(unsigned long long)));
   SFM_RC(dev_alloc(acct, c->d_geo_count, (size_t)m->n_views + 1));
   if (full) SFM_RC(dev_alloc(acct, c->d_geo_idx, (size_t)m->n_rows));
   SFM_RC(dev_alloc(acct, c->d_geo_model, ((size_t)m->n_views + 1) * 10));
@@ -378,6 +378,8 @@ ChainArgs make_chain_args(Ctx *c, const Query *q, const uint32_t *d_sel, uint32_
   C.blocks.block_list = c->d_block_list;
   C.blocks.bound = (uint32_t)std::min<uint64_t>(m->n_blocks, (uint64_t)n_sel * m->max_view_blocks);
   C.blocks.flagmask = c->d_flagmask;
+  C.blocks.pairs_out = c->d_k1_counters + kSelPairsSlot;
+  C.blocks.nq = q->n;
   return C;
 }
 
@@ -482,7 +484,10 @@ int ctx_match_putative(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
     rc = launch_hamming_top2(c, q, pass, n_work_blocks, !all_views, split);
   }
   if (rc) return rc;
-  c->stats.hamming_pairs += (uint64_t)n_work_blocks * kBlockRows * q->n;
+  // (the shortlist's workgroup counts the blocks of the list it builds, chain_device.h: n_work_blocks is only its launch
+  // bound, and a shard that owns none of the shortlist scans nothing)
+  if (!(sel.kind == ViewSel::kDevice && pass.chain_done))
+    c->stats.hamming_pairs += (uint64_t)n_work_blocks * kBlockRows * q->n;
   c->stats.hamming_alg_bytes += (uint64_t)n_work_blocks * kBlockRows * 64 + (uint64_t)q->n * 64;
   {
     EventScope ev(c, SFMLOC_K_COMPACT);
@@ -2026,6 +2031,22 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
 void sfmloc_debug_fail_p3p_alloc(int k) { sfmloc::g_test_fail_alloc.store(k, std::memory_order_relaxed); }
 void sfmloc_debug_fail_next_alloc(int k) { sfmloc::g_fail_countdown = k; }
 
+int sfmloc_debug_context_views(sfmloc_context *ctx, uint32_t *views, uint32_t cap, uint32_t *n) {
+  SFM_CHECK(ctx && n && (views || cap == 0), SFMLOC_EINVAL, "sfmloc_debug_context_views: bad argument");
+  Ctx *c = reinterpret_cast<Ctx *>(ctx);
+  SFM_CHECK(!c->stream.gang, SFMLOC_EINVAL, "sfmloc_debug_context_views: the context is recording a gang session");
+  SFM_HIP(hipSetDevice(c->map->device));
+  SFM_HIP(hipStreamSynchronize(c->stream));
+  *n = c->last_n_sel;
+  SFM_CHECK(cap >= c->last_n_sel, SFMLOC_ECAP, "sfmloc_debug_context_views: cap %u < %u views", cap, c->last_n_sel);
+  if (c->last_all_views) {  // (no list on the device: every view, in order)
+    for (uint32_t v = 0; v < c->last_n_sel; ++v) views[v] = v;
+  } else if (c->last_n_sel) {
+    SFM_HIP(hipMemcpy(views, c->d_view_sel, (size_t)c->last_n_sel * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  return SFMLOC_OK;
+}
+
 int sfmloc_debug_math(int device, int op, const double *in, int n, int in_stride, double *out, int out_stride) {
   SFM_CHECK(in && out && n > 0 && in_stride > 0 && out_stride > 0, SFMLOC_EINVAL, "sfmloc_debug_math: bad argument");
   int ndev = 0;
@@ -2075,7 +2096,7 @@ int sfmloc_stats_read(sfmloc_map *map, sfmloc_kernel_stats *out) {
     }
     out->hamming_pairs += c->stats.hamming_pairs;
     out->hamming_alg_bytes += c->stats.hamming_alg_bytes;
-    unsigned long long k1s[2 * kK1CounterSlots], k1c[2] = {0, 0};
+    unsigned long long k1s[kSelPairsSlot + 1], k1c[2] = {0, 0};
     SFM_HIP(hipMemcpy(k1s, c->d_k1_counters, sizeof(k1s), hipMemcpyDeviceToHost));
     for (int q = 0; q < kK1CounterSlots; ++q) {
       k1c[0] += k1s[2 * q];
@@ -2084,6 +2105,7 @@ int sfmloc_stats_read(sfmloc_map *map, sfmloc_kernel_stats *out) {
     out->hamming_lane_ops += c->stats.hamming_lane_ops + 64ull * k1c[0] * (uint64_t)c->k1_finish_ops;
     out->hamming_pairs_finished += 64ull * k1c[0];
     out->hamming_rows_flagged += k1c[1];
+    out->hamming_pairs += k1s[kSelPairsSlot];
   }
   return SFMLOC_OK;
 }
@@ -2106,7 +2128,7 @@ int sfmloc_stats_reset(sfmloc_map *map) {
     int rc = drain_events(c);
     if (rc) return rc;
     memset(&c->stats, 0, sizeof(c->stats));
-    SFM_HIP(hipMemset(c->d_k1_counters, 0, 2 * kK1CounterSlots * sizeof(unsigned long long)));
+    SFM_HIP(hipMemset(c->d_k1_counters, 0, (kSelPairsSlot + 1) * sizeof(unsigned long long)));
   }
   return SFMLOC_OK;
 }

@@ -50,6 +50,10 @@ struct BlocksArgs {
   uint32_t *view_sel_out, *widx0, *block_list;
   uint32_t bound;
   unsigned long long *flagmask;
+  // the list is built where the host cannot see it: the bank rows x query rows its scan really compares are added here
+  // (sfmloc_kernel_stats.hamming_pairs; the host knows `bound` only, and a list of padding alone scans nothing)
+  unsigned long long *pairs_out;
+  uint32_t nq;
 };
 // inclusive scan of one value per thread over a 1024-thread workgroup, OP = max or +: shuffles inside a wave, the sixteen
 // wave totals through LDS (two barriers; the log-step scan through LDS this replaces took twenty, twice per call -- 10 of
@@ -121,6 +125,8 @@ __device__ __forceinline__ void blocks_from_views_block(const BlocksArgs &B) {
   for (uint32_t w = s_carry_cnt + tid; w < B.bound; w += 1024) B.block_list[w] = kChainNoBlock;
   // a sliced scan ORs its row flags into the per-block masks: clear them here rather than with one more launch
   for (uint32_t w = tid; w < B.bound; w += 1024) B.flagmask[w] = 0ull;
+  if (tid == 0 && B.pairs_out && s_carry_cnt && B.nq)
+    atomicAdd(B.pairs_out, (unsigned long long)min(s_carry_cnt, B.bound) * kRows * B.nq);
 }
 
 // K2 after a screened scan (k_merge_ratio_masked), one wave per selected view: only rows whose mask bit is set can be

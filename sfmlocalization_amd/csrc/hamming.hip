@@ -378,7 +378,8 @@ struct BlocksFromViewsBody {
                                                     uint32_t *__restrict__ view_sel_out,
                                                     uint32_t *__restrict__ widx0, uint32_t *__restrict__ block_list,
                                                     uint32_t bound, unsigned long long *__restrict__ flagmask) {
-    BlocksArgs B{sel, n_sel, view_off, view_sel_out, widx0, block_list, bound, flagmask};
+    BlocksArgs B{sel, n_sel, view_off, view_sel_out, widx0, block_list, bound, flagmask,
+                 /*pairs_out (the host counts `bound`)*/ nullptr, 0};
     blocks_from_views_block(B);  // chain_device.h
   }
 };

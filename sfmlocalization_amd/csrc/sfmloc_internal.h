@@ -109,6 +109,7 @@ inline Options options_or(const Options *opt, void (*defaults)(Options *)) {
 // ---------------------------------------------------------------------------
 constexpr uint32_t kBlockRows = 64;
 constexpr int kK1CounterSlots = 64;  // Ctx::d_k1_counters
+constexpr int kSelPairsSlot = 2 * kK1CounterSlots;  // the word after them: pairs scanned for device-built view lists
 constexpr int kP3pMaxN = 4096;     // 2D-3D correspondences the P3P LDS sort holds
 constexpr int kP3pBatchMax = 512;  // hypotheses evaluated per round
 // (kP3pSlots, the batch sizes of a round and every other threshold the choice of a kernel form depends on: forms.h)
@@ -333,7 +334,8 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   DevBuf<uint4> d_flagged_desc;  // [rows_chunk_cap][4][64] descriptors of the flagged rows (tiled like the bank)
   uint32_t rows_chunk_cap = 0;          // chunks of 64 flagged rows the sliced pass has scratch for (rest: fallback)
   // [kK1CounterSlots][2] finished wave-pairs, flagged rows (since stats reset): a wave adds to slot (its block & 63) -- one
-  // pair of words for every wave of a scan was 300 000 atomics on the same address per full-bank scan
+  // pair of words for every wave of a scan was 300 000 atomics on the same address per full-bank scan; then one word
+  // (kSelPairsSlot): bank rows x query rows of the scans whose block list a shortlist's workgroup built
   DevBuf<unsigned long long> d_k1_counters;
   int k1_finish_ops = 0;
 
