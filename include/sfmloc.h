@@ -1672,6 +1672,13 @@ void sfmloc_debug_fail_next_alloc(int k);
  * the model again for it, on `device`, by every map of the process since the last reset (reset != 0 clears both after
  * reading; out may be null).  Synchronises the device.  For tests: the two ways give the same list. */
 int sfmloc_debug_k3_list_counts(int device, uint64_t *out, int reset);
+/* The launch forms the P3P AC-RANSAC rounds were queued in, by every context of the process since the last reset:
+ * out[0] small rounds (k_p3p_round_small), out[1] plain rounds (k_p3p_round, one workgroup per hypothesis), out[2] wide
+ * rounds (k_p3p_round, one workgroup per model).  Counted on the host where a round is queued, inside a gang session or
+ * not -- a round that finds the stage finished, or a small round that leaves a larger set to the full form, counts all
+ * the same; six-point rounds are not counted.  reset != 0 clears the three after reading; out may be null.
+ * Synchronises the device.  For tests: every form gives the same bits, so nothing else shows which one ran. */
+int sfmloc_debug_k5_round_counts(int device, uint64_t *out, int reset);
 /* The view list the context's last begin (sfmloc_localize[_bow]_begin, sfmloc_shard_begin[_bow], inside a finished gang
  * session or not) worked on, read back after synchronising the context's stream: *n entries into views -- ascending view
  * indices; a sharded shortlist's padding appears as written, as the phantom index n_views; every view in order when the

@@ -322,6 +322,14 @@ def k3_list_counts(reset=False, device=0):
     return int(out[0]), int(out[1])
 
 
+def k5_round_counts(reset=False, device=0):
+    """sfmloc_debug_k5_round_counts: the P3P rounds queued in the (small, plain, wide) launch form by every context of
+    the process since the last reset; reset=True clears the three after reading."""
+    out = np.zeros(3, np.uint64)
+    _check(_L().sfmloc_debug_k5_round_counts(int(device), _ptr(out, C.c_uint64), int(bool(reset))))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def debug_math(op, x, out_stride, device=0):
     """sfmloc_debug_math: run an f64 device building block over the rows of x."""
     x = np.ascontiguousarray(x, dtype=np.float64)

@@ -2864,6 +2864,10 @@ int launch_p3p_init(Ctx *c) {
   return SFMLOC_OK;
 }
 
+// Which launch form the P3P rounds went out in (sfmloc_debug_k5_round_counts): small, plain, wide.  Host side, one
+// relaxed add per queued round; a six-point round is not counted.
+static std::atomic<uint64_t> g_k5_round_counts[3];
+
 int launch_p3p_round(Ctx *c, int batch) {
   const K5In in = k5_in(c);
   P3pArgs A = make_p3p_args(c, in);
@@ -2888,8 +2892,10 @@ int launch_p3p_round(Ctx *c, int batch) {
     else
       hipLaunchKernelGGL(k_resect6_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, s, A, P.batch, 0);
   } else if (P.form == K5Form::kSmall) {
+    g_k5_round_counts[0].fetch_add(1, std::memory_order_relaxed);
     sfm_launch<P3pRoundSmallBody>(c, k_p3p_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, A, P.batch, 0);
   } else {  // either launch shape gives the same bits
+    g_k5_round_counts[P.form == K5Form::kWide ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
     sfm_launch<P3pRoundBody>(c, k_p3p_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, A, P.batch,
                              P.form == K5Form::kWide ? 1 : 0);
   }
@@ -2921,6 +2927,17 @@ int debug_k3_list_counts(int device, uint64_t *out, int reset) {
   return SFMLOC_OK;
 }
 
+int debug_k5_round_counts(int device, uint64_t *out, int reset) {
+  SFM_HIP(hipSetDevice(device));
+  SFM_HIP(hipDeviceSynchronize());
+  for (int i = 0; i < 3; ++i) {
+    const uint64_t v = reset ? g_k5_round_counts[i].exchange(0, std::memory_order_relaxed)
+                             : g_k5_round_counts[i].load(std::memory_order_relaxed);
+    if (out) out[i] = v;
+  }
+  return SFMLOC_OK;
+}
+
 #ifdef SFMLOC_STAMPS
 int debug_stamps_read(int which, unsigned long long *out, size_t n) {
   hipDeviceSynchronize();
@@ -2942,6 +2959,9 @@ int debug_stamps_clear() {
 
 extern "C" int sfmloc_debug_k3_list_counts(int device, uint64_t *out, int reset) {
   return sfmloc::debug_k3_list_counts(device, out, reset);
+}
+extern "C" int sfmloc_debug_k5_round_counts(int device, uint64_t *out, int reset) {
+  return sfmloc::debug_k5_round_counts(device, out, reset);
 }
 
 #ifdef SFMLOC_STAMPS

@@ -75,9 +75,11 @@ def main():
             print(f"{i + 1} scenes, {len(a)} queries, correspondences {a.min()} .. {a.max()} (median {int(np.median(a))}), "
                   f"{int((a > 512).sum())} above 512, {int((a > 4096).sum())} above 4096, {time.time() - t0:.0f} s", flush=True)
     a = np.array(stats)
+    rounds = S.capi.k5_round_counts()       # the launch forms the campaign's rounds were queued in
     print(f"OK: {n} scenes, {len(a)} queries, every pose and inlier set bit-exact; correspondences {a.min()} .. {a.max()}, "
           f"{int((a > 256).sum())} above 256 (filter), {int((a > 512).sum())} above 512 (one workgroup per model), "
-          f"{int((a > 4096).sum())} above 4096 ({time.time() - t0:.0f} s)")
+          f"{int((a > 4096).sum())} above 4096; rounds small {rounds[0]} plain {rounds[1]} wide {rounds[2]} "
+          f"({time.time() - t0:.0f} s)")
     return 0
 
 
