@@ -1001,6 +1001,10 @@ int sfmloc_sfm_register_read(const sfmloc_sfm *h, sfmloc_sfm_view_result *out /*
 /* inliers of view k as indices into the correspondence list of the round that tried it last, AC-RANSAC order (as
  * sfmloc_sfm_resect_inliers: a failed view's best model included) */
 int sfmloc_sfm_register_inliers(const sfmloc_sfm *h, uint32_t k, uint32_t *idx, uint32_t cap, uint32_t *n);
+/* "count" of a round as it would stand now, for every view (posed or not): c[v] = the observations of view v whose
+ * landmark is kept.  Read-only: nothing on the handle changes, no round is counted.  SFMLOC_EINVAL before the keep
+ * masks exist.  What a driver needs for OpenMVG's "views close to the best" rule (sfmlocalization_amd.incrementalsfm) */
+int sfmloc_sfm_register_counts(const sfmloc_sfm *h, uint32_t *c /*[n_views]*/);
 
 /* ------------------------------------------------------------------------- */
 /* Relative poses (the first stage of openMVG_main_GlobalSfM, reconstructGraph.py:166-171: the essential matrix of      */
@@ -1233,6 +1237,68 @@ int  sfmloc_wscales_report_read(const sfmloc_wscales *w, sfmloc_wscales_report *
 void sfmloc_wscales_destroy(sfmloc_wscales *w);
 /* device milliseconds of the calling thread's last sfmloc_wedge_scales */
 double sfmloc_wscales_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
+/* Seed scores (the initial pair of incremental SfM, OpenMVG's AutomaticInitialPairChoice: per matched pair the median  */
+/* angle between the two rays of its inlier matches; the pair with the largest one starts the map).  The arrays are     */
+/* those of sfmloc_wedge_scales: the scene of sfmloc_relative_poses (view_wh is not needed), rel_R / rel_t and          */
+/* inlier_off / inlier_idx its results, use_pair[k] = 0 (NULL: all 1) leaves a pair out.  OpenMVG's source was not at   */
+/* hand: every point below is a reading chosen here, and tests/seed_np.py restates each operation.  Per used pair, f64, */
+/* unfused, only + - * / sqrt:                                                                                           */
+/*   bearings    as "bearings" of the relative poses, for the inlier matches, in the order of the inlier list.           */
+/*   point       every inlier is triangulated from [I | 0] and [R | t] by "cheirality" of the relative poses.  It is     */
+/*               used under the rule of "points" of the two-view refinement: the point X exists, (R X + t)_2 is finite   */
+/*               and X_2 and (R X + t)_2 are positive.  A match listed twice is two used inliers.                         */
+/*   cosine      r1 = (u_I, v_I, 1), r2 = R^T (u_J, v_J, 1) (each component (R_0c u + R_1c v) + R_2c), the bearings of   */
+/*               the match; c = dot / (|r1| |r2|), dot and the squared norms summed x, y, z in order, |r| = sqrt.  c is  */
+/*               clamped as "angle" of sfmloc_sfm_clean clamps: max(lo, min(c, hi)), lo = -1 + 1e-8, hi = 1 - 1e-8, a    */
+/*               NaN cosine becomes lo.                                                                                   */
+/*   key         the cosine's 64 bits as an unsigned key that orders doubles ascending: all bits flipped when the sign   */
+/*               bit is set, the top bit set otherwise.  Order is by key: -0.0 comes before +0.0.                        */
+/*   median      of the n_used keys in DESCENDING order, the element of rank n_used / 2 counted from 0 (OpenMVG's        */
+/*               nth_element index on ascending angles).  cos_median = that element's double; 0.0 when n_used = 0.       */
+/*   record      candidate = n_used >= min_used && cos_median < max_cos && cos_median > min_cos.  The thresholds are     */
+/*               cosines: no acos runs on the device and no libm call stands between tests/seed_np.py and the kernel.    */
+/*               A pair with use_pair = 0 has an all-zero record.                                                         */
+/* One form serves any inlier count (a pair may hold 65 536): one workgroup of 256 threads per pair writes every         */
+/* inlier's key, or 0 for one that is not used (no clamped cosine has the key 0), to a slab in global memory at the pair's */
+/* inlier offset, 8 bytes per inlier, lane-consecutive; then a radix select, 8 passes of 8 bits from the top, a          */
+/* 256-bin integer histogram in LDS per pass: the bin that holds the wanted rank narrows the prefix.  Integer LDS        */
+/* atomics are order-free and a selection gives the same element whatever the order of ties: two runs give the same      */
+/* bits, and a record depends on its own pair alone, not on the other pairs or on the order of the pair list.  No float  */
+/* atomics.  Device memory: 8 bytes per inlier beside the call's input arrays.                                           */
+/* Refusals, all on the host before any launch, the text naming the pair: everything sfmloc_wedge_scales refuses for    */
+/* these arrays; min_used = 0, a threshold that is not finite or outside (-1, 1], min_cos >= max_cos: SFMLOC_EINVAL.     */
+/* n_pairs = 0 gives an empty handle.  The choice among the candidates is the host's (csrc/seed_host.h choose, restated  */
+/* by tests/seed_np.py): two views of different id_pose, the smallest cos_median, then the larger n_used, then the       */
+/* smaller pair index.  Consumer: sfmlocalization_amd.incrementalsfm.                                                    */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_seed sfmloc_seed;
+typedef struct sfmloc_seed_options {
+  uint32_t min_used;     /* default 100 */
+  uint32_t reserved;
+  double   max_cos;      /* default cos 3 degrees = 0.9986295347545738: a smaller median angle is no baseline */
+  double   min_cos;      /* default cos 60 degrees = 0.5 */
+} sfmloc_seed_options;
+typedef struct sfmloc_seed_score {
+  uint32_t n_inliers, n_used, candidate, reserved;
+  double   cos_median;
+} sfmloc_seed_score;
+void sfmloc_seed_default_options(sfmloc_seed_options *o);
+/* opt NULL = the defaults */
+int  sfmloc_seed_scores(int device, const uint64_t *view_off /*[n_views+1]*/, uint32_t n_views, const float *kpt_xy,
+                        const uint32_t *view_intrinsic /*[n_views]*/, const double *intrinsics /*[n*6]*/,
+                        const uint32_t *intrinsic_type, uint32_t n_intrinsics,
+                        const uint32_t *pairs, uint32_t n_pairs, const uint64_t *offsets,
+                        const uint32_t *match_i, const uint32_t *match_j,
+                        const double *rel_R /*[n_pairs*9]*/, const double *rel_t /*[n_pairs*3]*/,
+                        const uint64_t *inlier_off /*[n_pairs+1]*/, const uint32_t *inlier_idx,
+                        const uint8_t *use_pair /*[n_pairs], NULL = all*/,
+                        const sfmloc_seed_options *opt, sfmloc_seed **out);
+int  sfmloc_seed_read(const sfmloc_seed *s, sfmloc_seed_score *out /*[n_pairs]*/);
+void sfmloc_seed_destroy(sfmloc_seed *s);
+/* device milliseconds of the calling thread's last sfmloc_seed_scores */
+double sfmloc_seed_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
 /* Global poses (the middle stage of openMVG_main_GlobalSfM: rotation averaging and translation averaging over the     */

@@ -48,6 +48,8 @@ RelrefineResult = _abi.struct("sfmloc_relrefine_result")
 WscalesOptions = _abi.struct("sfmloc_wscales_options")
 Wscale = _abi.struct("sfmloc_wscale")
 WscalesReport = _abi.struct("sfmloc_wscales_report")
+SeedOptions = _abi.struct("sfmloc_seed_options")
+SeedScore = _abi.struct("sfmloc_seed_score")
 GpscaleOptions = _abi.struct("sfmloc_gpscale_options")
 GpscaleReport = _abi.struct("sfmloc_gpscale_report")
 GposesOptions = _abi.struct("sfmloc_gposes_options")
@@ -1002,6 +1004,13 @@ class Sfm:
         _check(_L().sfmloc_sfm_register_read(self._h, out, _ptr(rnd, C.c_int32)))
         return list(out), rnd[:self.n_views]
 
+    def register_counts(self):
+        """sfmloc_sfm_register_counts -> [n_views] uint32: per view the observations whose landmark is kept, as a
+        registration round would count them now; nothing on the handle changes"""
+        c = np.zeros(max(1, self.n_views), np.uint32)
+        _check(_L().sfmloc_sfm_register_counts(self._h, _ptr(c, C.c_uint32)))
+        return c[:self.n_views]
+
     def register_inliers(self, k):
         n = C.c_uint32(0)
         _check(_L().sfmloc_sfm_register_inliers(self._h, int(k), None, 0, C.byref(n)))
@@ -1314,6 +1323,63 @@ class WedgeScales:
             self.ms = wscales_last_ms()
         finally:
             _L().sfmloc_wscales_destroy(h)
+
+
+# sfmloc_seed_score as a NumPy record (four uint32, one double: no padding)
+SEED_SCORE = np.dtype([("n_inliers", np.uint32), ("n_used", np.uint32), ("candidate", np.uint32), ("reserved", np.uint32),
+                       ("cos_median", np.float64)], align=True)
+
+
+def seed_default_options(**overrides):
+    """sfmloc_seed_default_options -> SeedOptions (min_used 100, max_cos cos 3 degrees, min_cos cos 60 degrees)"""
+    return _options(SeedOptions, "sfmloc_seed_default_options", overrides)
+
+
+def seed_last_ms():
+    """device milliseconds of the calling thread's last sfmloc_seed_scores"""
+    return float(_L().sfmloc_seed_last_ms())
+
+
+def seed_choose(scores, pairs, view_pose):
+    """the seed pair among the records (csrc/seed_host.h choose): a candidate whose two views have different id_pose,
+    the smallest cos_median, then the larger n_used, then the smaller pair index -> its index, or -1"""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    view_pose = np.asarray(view_pose, np.int64)
+    best = -1
+    for k, s in enumerate(scores):
+        if not int(s["candidate"]) or view_pose[pairs[k, 0]] == view_pose[pairs[k, 1]]:
+            continue
+        if best < 0 or s["cos_median"] < scores[best]["cos_median"] or \
+                (s["cos_median"] == scores[best]["cos_median"] and s["n_used"] > scores[best]["n_used"]):
+            best = k
+    return best
+
+
+class SeedScores:
+    """sfmloc_seed_scores: per pair the median cosine between the two rays of its inlier matches, and whether the pair
+    may start an incremental reconstruction (include/sfmloc.h "Seed scores" states the semantics).  The arguments are
+    WedgeScales'; options: the fields of sfmloc_seed_options.  -> scores (SEED_SCORE [P]), ms; choose(view_pose) -> the
+    seed pair's index or -1."""
+
+    def __init__(self, view_off, kpt_xy, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets, match_i, match_j,
+                 rel_R, rel_t, inl_off, inl_idx, use_pair=None, device=0, **options):
+        keep, scene = _pair_scene(view_off, kpt_xy, None, view_intrinsic, intrinsics, intrinsic_type, pairs, offsets,
+                                  match_i, match_j)
+        self.pairs = keep[6]
+        P = len(self.pairs)
+        keep_poses, poses = _pair_poses(P, rel_R, rel_t, inl_off, inl_idx, use_pair)
+        opt = seed_default_options(**options)
+        h = C.c_void_p()
+        _check(_L().sfmloc_seed_scores(int(device), *scene, *poses, C.byref(opt), C.byref(h)))
+        try:
+            self.scores = np.zeros(P, SEED_SCORE)
+            _check(_L().sfmloc_seed_read(h, _ptr(self.scores, SeedScore) if P else None))
+            self.ms = seed_last_ms()
+        finally:
+            _L().sfmloc_seed_destroy(h)
+
+    def choose(self, view_pose):
+        return seed_choose(self.scores, self.pairs, view_pose)
 
 
 # sfmloc_gposes_pair as a NumPy record (four uint32, two doubles: no padding)

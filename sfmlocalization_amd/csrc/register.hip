@@ -69,6 +69,25 @@ __global__ __launch_bounds__(kRegBlock) void k_reg_compact(const uint32_t *__res
   if (threadIdx.x == 0) cnt[v] = run;
 }
 
+// sfmloc.h "count" alone, for every view: one workgroup per view over its slice of the transpose; nothing is written
+// but c[v] (sfmloc_sfm_register_counts)
+__global__ __launch_bounds__(kRegBlock) void k_reg_counts(uint32_t n_views, const uint32_t *__restrict__ vlist,
+                                                          const uint32_t *__restrict__ view_off,
+                                                          const uint32_t *__restrict__ obs_lm,
+                                                          const uint8_t *__restrict__ lm_stage, uint32_t *__restrict__ c) {
+  __shared__ uint32_t s_cnt;
+  const uint32_t v = blockIdx.x;
+  if (v >= n_views) return;
+  const uint32_t b = view_off[v], n = view_off[v + 1] - b;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint32_t i = threadIdx.x; i < n; i += kRegBlock) mine += lm_stage[obs_lm[vlist[b + i]]] == 3 ? 1u : 0u;
+  if (mine) atomicAdd(&s_cnt, mine);  // (an integer count: order-free)
+  __syncthreads();
+  if (threadIdx.x == 0) c[v] = s_cnt;
+}
+
 // the resident arrays (SfmDev; obs_keep is written) and the round's lists
 struct RegExtendArgs : SfmDev {
   const uint32_t *unposed, *clist, *cnt;
@@ -320,6 +339,25 @@ int sfmloc_sfm_register_read(const sfmloc_sfm *hh, sfmloc_sfm_view_result *out, 
     }
     if (round) round[k] = have ? S.round[k] : -1;
   }
+  return SFMLOC_OK;
+}
+
+int sfmloc_sfm_register_counts(const sfmloc_sfm *hh, uint32_t *c) {
+  SFM_CHECK(hh && c, SFMLOC_EINVAL, "sfmloc_sfm_register_counts: null argument");
+  const Sfm *h = reinterpret_cast<const Sfm *>(hh);
+  SFM_CHECK(h->cleaned, SFMLOC_EINVAL,
+            "sfmloc_sfm_register_counts: the keep masks do not exist yet (after sfmloc_sfm_triangulate or sfmloc_sfm_clean)");
+  if (h->n_views == 0) return SFMLOC_OK;
+  SFM_HIP(hipSetDevice(h->device));
+  DevBuf<uint32_t> d_c;  // (the call's own: the handle keeps nothing of it)
+  SFM_RC(d_c.alloc(nullptr, h->n_views));
+  const SfmDev D = sfm_dev(*h);
+  hipStream_t s = h->s;
+  hipLaunchKernelGGL(k_reg_counts, dim3(h->n_views), dim3(kRegBlock), 0, s, h->n_views, D.vlist, D.view_off, D.obs_lm,
+                     (const uint8_t *)D.lm_stage, d_c.get());
+  SFM_HIP(hipGetLastError());
+  SFM_HIP(hipMemcpyAsync(c, d_c, h->n_views * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
 
