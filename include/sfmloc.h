@@ -532,6 +532,46 @@ int sfmloc_image_decode(const uint8_t *bytes, uint64_t n_bytes, int32_t color, u
                         int32_t *width, int32_t *height);
 int sfmloc_image_read(const char *path, int32_t color, uint8_t *out, uint64_t cap, int32_t *width, int32_t *height);
 
+/* cv::imread whose pixels are born on the device.  A JPEG's header parsing and entropy stage (Huffman: serial) run on
+ * the host exactly as in sfmloc_image_decode, once per file; the coefficient blocks cross PCIe in one upload and two
+ * kernels reconstruct (dequantisation + islow IDCT; fancy upsampling + colour).  Up to three images stay resident,
+ * chosen by the mask `want`; every pixel equals what sfmloc_image_decode returns for the same bytes:
+ *   SFMLOC_IMREAD_GRAY      h x w       imread(IMREAD_GRAYSCALE)
+ *   SFMLOC_IMREAD_BGR       h x w x 3   imread(IMREAD_COLOR)
+ *   SFMLOC_IMREAD_BGR2GRAY  h x w       cvtColor(imread(IMREAD_COLOR), COLOR_BGR2GRAY) (localizeImage.cc:463)
+ * PNG and binary PGM / PPM files are decoded on the host as sfmloc_image_decode does and uploaded, so that a consumer
+ * has one route for every format.  _create: frames of at most max_width x max_height (each 1 .. 16384); everything is
+ * allocated here, a JPEG call allocates nothing.  _decode / _file: all parsing happens before anything is queued -- a
+ * file sfmloc_image_decode refuses gives its code and its text after "sfmloc_imread_decode: ", nothing is launched and
+ * the previous images stand; a frame larger than the reader's maximum is SFMLOC_ECAP.  The calls queue their work on
+ * the reader's stream and return: the one host wait is for the PREVIOUS call's upload to have left the pinned staging
+ * buffer.  _read waits and copies one image out (parity tests, host consumers); _dev is its device address (NULL when
+ * the last decode did not leave it), valid until the next decode; its contents are ordered on the reader's stream --
+ * the consumers below order themselves behind it with an event.  _share_stream: as sfmloc_akaze_share_stream.
+ * _timing: enable != 0 makes the following JPEG decodes record events; out4 (may be NULL) = the last timed decode's
+ * host milliseconds (header + entropy stage + staging) and device milliseconds of the upload, the IDCT launch and the
+ * upsampling / colour launch, after waiting for them. */
+#define SFMLOC_IMREAD_GRAY 1
+#define SFMLOC_IMREAD_BGR 2
+#define SFMLOC_IMREAD_BGR2GRAY 4
+typedef struct sfmloc_imread sfmloc_imread;
+int sfmloc_imread_create(int device, uint32_t max_width, uint32_t max_height, sfmloc_imread **out);
+void sfmloc_imread_destroy(sfmloc_imread *r);
+int sfmloc_imread_decode(sfmloc_imread *r, const uint8_t *bytes, uint64_t n_bytes, uint32_t want, int32_t *width,
+                         int32_t *height);
+int sfmloc_imread_file(sfmloc_imread *r, const char *path, uint32_t want, int32_t *width, int32_t *height);
+int sfmloc_imread_read(sfmloc_imread *r, uint32_t which, uint8_t *out, uint64_t cap);
+const void *sfmloc_imread_dev(const sfmloc_imread *r, uint32_t which);
+int sfmloc_imread_share_stream(sfmloc_imread *r, sfmloc_context *ctx);
+int sfmloc_imread_timing(sfmloc_imread *r, int32_t enable, double *out4);
+/* The extractors on a reader's resident image instead of a host pointer: `which` names ONE image of the reader's last
+ * decode (a gray one), whose size must be the extractor's (SFMLOC_EINVAL otherwise).  The extractor's stream is ordered
+ * behind the reader's work with an event, not a host wait; otherwise as sfmloc_akaze_detect_resident /
+ * sfmloc_akaze_detect_and_compute: one host synchronisation per frame, for the keypoint count. */
+int sfmloc_akaze_detect_resident_dev(sfmloc_akaze *ak, sfmloc_imread *r, uint32_t which, uint32_t *n_out);
+int sfmloc_akaze_detect_and_compute_dev(sfmloc_akaze *ak, sfmloc_imread *r, uint32_t which, float *kpts, uint8_t *desc64,
+                                        uint32_t cap, uint32_t *n_out);
+
 /* The server's per-user image undistortion in front of LocalizeEngine::localize (localizeImage.cc:149-177, SURVEY
  * 8f-4).  _create = the once-per-camera part, host arithmetic only (no device needed):
  *   newCameraMat = getOptimalNewCameraMatrix(K, dist, size, 1.0, size, &validRoi)  +  cv::undistort's CV_16SC2 maps;
@@ -575,6 +615,10 @@ void sfmloc_imgbow_destroy(sfmloc_imgbow *ib);
 int sfmloc_imgbow_dim(const sfmloc_imgbow *ib);
 int sfmloc_imgbow_share_stream(sfmloc_imgbow *ib, sfmloc_context *ctx); /* NULL: back on its own stream */
 int sfmloc_imgbow_compute(sfmloc_imgbow *ib, const uint8_t *image, sfmloc_query *query, double *out_bow);
+/* the same from a reader's resident image (sfmloc_imread_decode): `which` = SFMLOC_IMREAD_BGR for a 3-channel
+ * extractor, a gray image for a 1-channel one; the frame's size must be the extractor's (SFMLOC_EINVAL otherwise).
+ * Nothing crosses PCIe; the extractor's stream waits for the reader's work through an event. */
+int sfmloc_imgbow_compute_dev(sfmloc_imgbow *ib, sfmloc_imread *r, uint32_t which, sfmloc_query *query, double *out_bow);
 /* The vectors of n frames (1..32) in ONE gang session on the first extractor's stream: one launch per kernel for all of
  * them; the float32 vectors stay on the device (sfmloc_imgbow_vector_dev of each extractor).  The reference computes the
  * vector per query image (localization.cpp:346-361, LocalizeEngine.cc:205-232); same bits as n single calls. */

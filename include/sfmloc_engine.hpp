@@ -97,6 +97,7 @@ class LocalizeEngine {
   ~LocalizeEngine() {
     for (auto &kv : mAkaze)
       if (kv.second) sfmloc_akaze_destroy(kv.second);
+    sfmloc_imread_destroy(mImread);
     if (mMap) sfmloc_map_destroy(mMap);
   }
 
@@ -106,6 +107,16 @@ class LocalizeEngine {
                                std::vector<int> &pointsInlier, bool bReturnTime, std::vector<double> &times,
                                const std::vector<double> &center = std::vector<double>(), double radius = -1.0,
                                const std::vector<float> *bow = nullptr) {
+    return localizeFrom(gray, nullptr, 0, width, height, bReturnKeypoints, points2D, points3D, pointsInlier, bReturnTime,
+                        times, center, radius, bow);
+  }
+
+ private:
+  // extraction from a host gray image, or (gray null) from a reader's resident one, then localizeFeatures
+  std::vector<double> localizeFrom(const uint8_t *gray, sfmloc_imread *reader, uint32_t which, int width, int height,
+                                   bool bReturnKeypoints, std::vector<double> &points2D, std::vector<double> &points3D,
+                                   std::vector<int> &pointsInlier, bool bReturnTime, std::vector<double> &times,
+                                   const std::vector<double> &center, double radius, const std::vector<float> *bow) {
     sfmloc_akaze *&ak = mAkaze[std::make_pair(width, height)];
     if (!ak && sfmloc_akaze_create(mDevice, width, height, mNOct, mNOctLay, mThres, &ak))
       throw std::runtime_error(sfmloc_last_error());
@@ -114,7 +125,8 @@ class LocalizeEngine {
     std::vector<uint8_t> desc((size_t)cap * 64);
     uint32_t n = 0;
     const auto tFeat = std::chrono::steady_clock::now();
-    if (sfmloc_akaze_detect_and_compute(ak, gray, kp.data(), desc.data(), cap, &n))
+    if (gray ? sfmloc_akaze_detect_and_compute(ak, gray, kp.data(), desc.data(), cap, &n)
+             : sfmloc_akaze_detect_and_compute_dev(ak, reader, which, kp.data(), desc.data(), cap, &n))
       throw std::runtime_error(sfmloc_last_error());
     const double featSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tFeat).count();
     std::vector<float> xy((size_t)n * 2);
@@ -127,6 +139,8 @@ class LocalizeEngine {
     if (bReturnTime && times.size() == 6) times[2] = featSeconds;  // "Extract feature from query image"
     return r;
   }
+
+ public:
   double lastTotalSeconds() const { return mLastTotal; }
 
   // the server's calls: a decoded colour image (B G R, what cv::imdecode / cv::imread(IMREAD_COLOR) hand to
@@ -143,14 +157,30 @@ class LocalizeEngine {
                     center, radius, bow);
   }
 
-  // ... and an image file (JPEG / PNG / PGM / PPM) through the library's own imread
+  // ... and an image file (JPEG / PNG / PGM / PPM) through the library's own imread.  deviceDecode: the file is
+  // entropy-decoded once on the host and the colour read's gray (BGR2GRAY) reconstructed and kept on the device
+  // (sfmloc_imread), extraction reads it there -- no host pixels, the same result
   std::vector<double> localizeImageFile(const std::string &path, bool bReturnKeypoints, std::vector<double> &points2D,
                                         std::vector<double> &points3D, std::vector<int> &pointsInlier,
                                         bool bReturnTime, std::vector<double> &times,
                                         const std::vector<double> &center = std::vector<double>(),
-                                        double radius = -1.0, const std::vector<float> *bow = nullptr) {
+                                        double radius = -1.0, const std::vector<float> *bow = nullptr,
+                                        bool deviceDecode = false) {
     int32_t w = 0, h = 0;
     if (sfmloc_image_read(path.c_str(), 1, nullptr, 0, &w, &h)) throw std::runtime_error(sfmloc_last_error());
+    if (deviceDecode) {
+      if (!mImread || w > mImreadW || h > mImreadH) {  // made, or remade larger, for the file's size
+        sfmloc_imread_destroy(mImread);
+        mImread = nullptr;
+        mImreadW = w > mImreadW ? w : mImreadW;
+        mImreadH = h > mImreadH ? h : mImreadH;
+        if (sfmloc_imread_create(mDevice, (uint32_t)mImreadW, (uint32_t)mImreadH, &mImread))
+          throw std::runtime_error(sfmloc_last_error());
+      }
+      if (sfmloc_imread_file(mImread, path.c_str(), SFMLOC_IMREAD_BGR2GRAY, &w, &h)) throw std::runtime_error(sfmloc_last_error());
+      return localizeFrom(nullptr, mImread, SFMLOC_IMREAD_BGR2GRAY, w, h, bReturnKeypoints, points2D, points3D, pointsInlier,
+                          bReturnTime, times, center, radius, bow);
+    }
     std::vector<uint8_t> bgr((size_t)w * h * 3);
     if (sfmloc_image_read(path.c_str(), 1, bgr.data(), bgr.size(), &w, &h)) throw std::runtime_error(sfmloc_last_error());
     return localizeBGR(bgr.data(), w, h, bReturnKeypoints, points2D, points3D, pointsInlier, bReturnTime, times, center,
@@ -312,6 +342,8 @@ class LocalizeEngine {
   float mThres = 0.001f;
   int mNOct = 4, mNOctLay = 4;
   std::map<std::pair<int, int>, sfmloc_akaze *> mAkaze;
+  sfmloc_imread *mImread = nullptr;  // localizeImageFile(deviceDecode): the reader and the frame size it was made for
+  int32_t mImreadW = 0, mImreadH = 0;
 };
 
 // One rank of a map sharded by view over N GPUs (include/sfmloc.h "A rank's whole batch per call"): the

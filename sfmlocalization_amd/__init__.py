@@ -7,9 +7,9 @@ reference's interface for that path.  There is no CPU fallback.
 from . import _lib  # noqa: F401
 from .capi import (  # noqa: F401
     SfmlocError, Params, MapDesc, Map, Query, Context, BofModel, ImgBow, Akaze, KernelStats, Pose, default_params, device_count, NOMATCH, debug_math, dense_gray,
-    Undistorter, image_read, image_decode, image_size,
+    Undistorter, image_read, image_decode, image_size, DeviceImread, IMREAD_GRAY, IMREAD_BGR, IMREAD_BGR2GRAY,
 )
 
 __all__ = ["SfmlocError", "Params", "MapDesc", "Map", "Query", "Context", "BofModel", "ImgBow", "Akaze", "KernelStats", "default_params",
            "device_count", "NOMATCH", "Pose", "debug_math", "dense_gray", "Undistorter", "image_read", "image_decode",
-           "image_size"]
+           "image_size", "DeviceImread", "IMREAD_GRAY", "IMREAD_BGR", "IMREAD_BGR2GRAY"]

@@ -260,6 +260,68 @@ def image_read(path, color=False):
     return out
 
 
+IMREAD_GRAY, IMREAD_BGR, IMREAD_BGR2GRAY = _abi.constants("IMREAD_GRAY", "IMREAD_BGR", "IMREAD_BGR2GRAY")
+
+
+class DeviceImread:
+    """sfmloc_imread: cv::imread whose pixels are born on the device.  A JPEG is entropy-decoded once on the host and
+    reconstructed by two kernels; the images asked for (a mask of IMREAD_GRAY, IMREAD_BGR, IMREAD_BGR2GRAY) stay resident
+    for Akaze.detect_and_compute_dev / detect_resident_dev and ImgBow.compute_dev.  Every pixel equals image_decode's."""
+
+    def __init__(self, max_width, max_height, device=0):
+        self._h = None
+        h = C.c_void_p()
+        _check(_L().sfmloc_imread_create(device, int(max_width), int(max_height), C.byref(h)))
+        self._h = h
+        self.max_width, self.max_height = int(max_width), int(max_height)
+        self.width = self.height = 0
+
+    def decode(self, data, want=IMREAD_GRAY):
+        """the bytes of a JPEG / PNG / PGM / PPM file -> (width, height); asynchronous on the reader's stream"""
+        raw = np.frombuffer(bytes(data), dtype=np.uint8)
+        w, h = C.c_int32(0), C.c_int32(0)
+        _check(_L().sfmloc_imread_decode(self._h, _ptr(raw, C.c_uint8), raw.size, int(want), C.byref(w), C.byref(h)))
+        self.width, self.height = w.value, h.value
+        return w.value, h.value
+
+    def file(self, path, want=IMREAD_GRAY):
+        w, h = C.c_int32(0), C.c_int32(0)
+        _check(_L().sfmloc_imread_file(self._h, os.fsencode(path), int(want), C.byref(w), C.byref(h)))
+        self.width, self.height = w.value, h.value
+        return w.value, h.value
+
+    def read(self, which):
+        """one image of the last decode as u8 [h, w] (or [h, w, 3] for IMREAD_BGR); waits for it"""
+        out = np.zeros((self.height, self.width, 3) if which == IMREAD_BGR else (self.height, self.width), np.uint8)
+        _check(_L().sfmloc_imread_read(self._h, int(which), _ptr(out, C.c_uint8), out.size))
+        return out
+
+    def dev(self, which):
+        """device address of one image of the last decode (0 when it did not leave that image)"""
+        return int(_L().sfmloc_imread_dev(self._h, int(which)) or 0)
+
+    def share_stream(self, ctx):
+        _check(_L().sfmloc_imread_share_stream(self._h, None if ctx is None else ctx._h))
+
+    def timing(self, enable=True, read=False):
+        """sfmloc_imread_timing: switch event timing of JPEG decodes; read=True -> (host ms, upload ms, IDCT ms,
+        upsampling + colour ms) of the last timed decode"""
+        out = np.zeros(4, np.float64) if read else None
+        _check(_L().sfmloc_imread_timing(self._h, int(bool(enable)), _ptr(out, C.c_double)))
+        return None if out is None else tuple(float(v) for v in out)
+
+    def close(self):
+        if self._h is not None:
+            _L().sfmloc_imread_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Undistorter:
     """sfmloc_undistorter: the server's per-user undistortion (localizeImage.cc:149-177).  new_camera (3x3) and roi
     (x, y, w, h) are what getOptimalNewCameraMatrix(K, dist, size, 1.0, size, &validRoi) returns; apply() is
@@ -774,6 +836,14 @@ class ImgBow:
         out = np.zeros(self.dim, np.float64) if want else None
         _check(_L().sfmloc_imgbow_compute(self._h, _ptr(img, C.c_uint8), None if query is None else query._h,
                                           _ptr(out, C.c_double)))
+        return out
+
+    def compute_dev(self, reader, which=IMREAD_BGR, query=None, want_vector=None):
+        """sfmloc_imgbow_compute_dev: compute() on a DeviceImread's resident image (nothing crosses PCIe)"""
+        want = (query is None) if want_vector is None else want_vector
+        out = np.zeros(self.dim, np.float64) if want else None
+        _check(_L().sfmloc_imgbow_compute_dev(self._h, reader._h, int(which), None if query is None else query._h,
+                                              _ptr(out, C.c_double)))
         return out
 
     def vector_read(self):
@@ -1685,6 +1755,24 @@ class Akaze:
         _check(_L().sfmloc_akaze_detect_and_compute(self._h, _ptr(gray, C.c_uint8), _ptr(kp, C.c_float),
                                                     _ptr(desc, C.c_uint8), cap, C.byref(n)))
         return kp[:n.value].copy(), desc[:n.value].copy()
+
+    def detect_and_compute_dev(self, reader, which=IMREAD_GRAY, cap=65536):
+        """sfmloc_akaze_detect_and_compute_dev: detect_and_compute on a DeviceImread's resident gray image"""
+        if getattr(self, "_out_cap", 0) != cap:
+            self._out_kp = np.zeros((cap, 6), np.float32)
+            self._out_desc = np.zeros((cap, 64), np.uint8)
+            self._out_cap = cap
+        kp, desc = self._out_kp, self._out_desc
+        n = C.c_uint32()
+        _check(_L().sfmloc_akaze_detect_and_compute_dev(self._h, reader._h, int(which), _ptr(kp, C.c_float),
+                                                        _ptr(desc, C.c_uint8), cap, C.byref(n)))
+        return kp[:n.value].copy(), desc[:n.value].copy()
+
+    def detect_resident_dev(self, reader, which=IMREAD_GRAY):
+        """sfmloc_akaze_detect_resident_dev: detect_resident on a DeviceImread's resident gray image -> keypoints"""
+        n = C.c_uint32()
+        _check(_L().sfmloc_akaze_detect_resident_dev(self._h, reader._h, int(which), C.byref(n)))
+        return int(n.value)
 
     @staticmethod
     def detect_and_compute_batch(extractors, grays, cap=65536):

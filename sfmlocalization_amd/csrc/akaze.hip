@@ -2381,15 +2381,30 @@ static int akaze_outputs_enqueue(Akaze *a, float *kpts, uint8_t *desc64, uint32_
   return SFMLOC_OK;
 }
 
-int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float *kpts /*[cap*6]*/,
-                                    uint8_t *desc64 /*[cap*64]*/, uint32_t cap, uint32_t *n_out) {
-  SFM_CHECK(ak && gray && n_out, SFMLOC_EINVAL, "sfmloc_akaze_detect_and_compute: null argument");
-  Akaze *a = reinterpret_cast<Akaze *>(ak);
+// a reader's resident gray image (imread_dev.hip) becomes the extractor's: its stream waits for the reader's work, copies
+// the image into d_gray (device to device) and tells the reader when that read is done
+static int akaze_take_resident(Akaze *a, sfmloc_imread *reader, uint32_t which, const char *who) {
+  Imread *r = reinterpret_cast<Imread *>(reader);
+  SFM_CHECK(which != SFMLOC_IMREAD_BGR, SFMLOC_EINVAL, "%s: the extractor takes a gray image (GRAY or BGR2GRAY)", who);
+  hipStream_t s = a->stream;
+  const uint8_t *src = nullptr;
+  SFM_RC(imread_feed(r, which, a->device, (uint32_t)a->w, (uint32_t)a->h, s, &src, who));
+  SFM_HIP(hipMemcpyAsync(a->d_gray, src, (size_t)a->w * a->h, hipMemcpyDeviceToDevice, s));
+  return imread_consumed(r, s);
+}
+
+// sfmloc_akaze_detect_and_compute on a host image (gray), or on a reader's resident one (gray null)
+static int akaze_detect_and_compute_one(Akaze *a, const uint8_t *gray, sfmloc_imread *reader, uint32_t which, float *kpts,
+                                        uint8_t *desc64, uint32_t cap, uint32_t *n_out) {
   SFM_HIP(hipSetDevice(a->device));
   static const bool timing = getenv("SFMLOC_AKAZE_TIMING") != nullptr;
   const double t_0 = timing ? now_s() : 0.0;
   int rc = akaze_ensure_stream(a);
   if (rc) return rc;
+  if (!gray) {
+    rc = akaze_take_resident(a, reader, which, "sfmloc_akaze_detect_and_compute_dev");
+    if (rc) return rc;
+  }
   rc = akaze_detect_enqueue(a, gray);
   if (rc) return rc;
   hipStream_t s = a->stream;
@@ -2427,6 +2442,38 @@ int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float
       fprintf(stderr, "  level %2d: %5u candidates, %2u rounds, fill %.1f us, rounds %.1f us (a %.1f b %.1f)\n", l, a->h_counts[10 + 4 * l],
               a->h_counts[11 + 4 * l], a->h_counts[12 + 4 * l] * 0.01, a->h_counts[13 + 4 * l] * 0.01, a->h_counts[82 + 2 * l] * 0.01, a->h_counts[83 + 2 * l] * 0.01);
   }
+  return SFMLOC_OK;
+}
+
+int sfmloc_akaze_detect_and_compute(sfmloc_akaze *ak, const uint8_t *gray, float *kpts /*[cap*6]*/,
+                                    uint8_t *desc64 /*[cap*64]*/, uint32_t cap, uint32_t *n_out) {
+  SFM_CHECK(ak && gray && n_out, SFMLOC_EINVAL, "sfmloc_akaze_detect_and_compute: null argument");
+  return akaze_detect_and_compute_one(reinterpret_cast<Akaze *>(ak), gray, nullptr, 0, kpts, desc64, cap, n_out);
+}
+
+int sfmloc_akaze_detect_and_compute_dev(sfmloc_akaze *ak, sfmloc_imread *r, uint32_t which, float *kpts /*[cap*6]*/,
+                                        uint8_t *desc64 /*[cap*64]*/, uint32_t cap, uint32_t *n_out) {
+  SFM_CHECK(ak && r && n_out, SFMLOC_EINVAL, "sfmloc_akaze_detect_and_compute_dev: null argument");
+  Akaze *a = reinterpret_cast<Akaze *>(ak);
+  SFM_CHECK(a->stream.gang == nullptr, SFMLOC_EINVAL, "sfmloc_akaze_detect_and_compute_dev: the extractor is in a session");
+  return akaze_detect_and_compute_one(a, nullptr, r, which, kpts, desc64, cap, n_out);
+}
+
+// sfmloc_akaze_detect_resident on a reader's resident image: the outputs stay on the device, only the count comes back
+int sfmloc_akaze_detect_resident_dev(sfmloc_akaze *ak, sfmloc_imread *r, uint32_t which, uint32_t *n_out) {
+  SFM_CHECK(ak && r && n_out, SFMLOC_EINVAL, "sfmloc_akaze_detect_resident_dev: null argument");
+  Akaze *a = reinterpret_cast<Akaze *>(ak);
+  SFM_CHECK(a->stream.gang == nullptr, SFMLOC_EINVAL, "sfmloc_akaze_detect_resident_dev: the extractor is in a session");
+  SFM_HIP(hipSetDevice(a->device));
+  SFM_RC(akaze_ensure_stream(a));
+  SFM_RC(akaze_take_resident(a, r, which, "sfmloc_akaze_detect_resident_dev"));
+  SFM_RC(akaze_detect_enqueue(a, nullptr));
+  hipStream_t s = a->stream;
+  SFM_RC(akaze_counts_enqueue(a, s));
+  SFM_HIP(hipStreamSynchronize(s));
+  SFM_CHECK(a->h_counts[0] <= a->det.cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)",
+            a->h_counts[0], a->det.cand_cap);
+  *n_out = a->h_counts[1];
   return SFMLOC_OK;
 }
 

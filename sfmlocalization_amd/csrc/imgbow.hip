@@ -199,6 +199,48 @@ int sfmloc_imgbow_compute(sfmloc_imgbow *p, const uint8_t *image, sfmloc_query *
   return SFMLOC_OK;
 }
 
+// sfmloc_imgbow_compute on a reader's resident image (imread_dev.hip): the chain reads the reader's buffer where it is
+int sfmloc_imgbow_compute_dev(sfmloc_imgbow *p, sfmloc_imread *reader, uint32_t which, sfmloc_query *query, double *out_bow) {
+  SFM_CHECK(p && reader, SFMLOC_EINVAL, "sfmloc_imgbow_compute_dev: null argument");
+  ImgBow *ib = reinterpret_cast<ImgBow *>(p);
+  Query *q = reinterpret_cast<Query *>(query);
+  const BofModel *b = reinterpret_cast<const BofModel *>(ib->bof);
+  const size_t dim = (size_t)b->K * b->cells;
+  if (q) {
+    SFM_CHECK(q->map && q->map->bow_dim == dim, SFMLOC_EINVAL,
+              "sfmloc_imgbow_compute_dev: the model's vector has %zu entries, the map's .bow vectors %u", dim,
+              q->map ? q->map->bow_dim : 0u);
+    SFM_CHECK(!q->is_view, SFMLOC_EINVAL, "sfmloc_imgbow_compute_dev: a view's BoW vector belongs to the caller");
+    SFM_CHECK(q->map->device == ib->device, SFMLOC_EINVAL, "sfmloc_imgbow_compute_dev: query and extractor on different devices");
+  }
+  SFM_CHECK((which == SFMLOC_IMREAD_BGR) == (ib->channels == 3), SFMLOC_EINVAL,
+            "sfmloc_imgbow_compute_dev: a %u-channel extractor takes %s", ib->channels,
+            ib->channels == 3 ? "the BGR image" : "a gray image (GRAY or BGR2GRAY)");
+  SFM_HIP(hipSetDevice(ib->device));
+  if (q && !q->d_bow) SFM_HIP(query_array(q->d_bow, dim));  // (once per query object)
+  Akaze *a = reinterpret_cast<Akaze *>(ib->ak);
+  Imread *r = reinterpret_cast<Imread *>(reader);
+  hipStream_t s = akaze_stream_now(a);
+  const uint8_t *src = nullptr;
+  SFM_RC(imread_feed(r, which, ib->device, ib->w, ib->h, s, &src, "sfmloc_imgbow_compute_dev"));
+  int rc = dense_gray_enqueue(&ib->plan, s, src, akaze_gray_dev(a));
+  if (rc) return rc;
+  SFM_RC(imread_consumed(r, s));
+  rc = akaze_compute_resident(a, ib->d_grid, ib->n_grid, 4);  // (the grid's four scales are levels 0 .. 3)
+  if (rc) return rc;
+  s = akaze_stream_now(a);
+  rc = launch_bof(b, s, nullptr, ib->d_kxy, (int)ib->n_grid, ib->d_counts, ib->d_out, q ? q->d_bow.get() : ib->d_out_f32.get(),
+                  akaze_desc_dev(a));
+  if (rc) return rc;
+  ib->last_stream = s;
+  if (out_bow) {
+    SFM_HIP(hipMemcpyAsync(ib->h_out, ib->d_out, dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipStreamSynchronize(s));
+    memcpy(out_bow, ib->h_out, dim * sizeof(double));
+  }
+  return SFMLOC_OK;
+}
+
 // the float64 vector of the extractor's last call (single or batch), after waiting for it
 int sfmloc_imgbow_vector_read(sfmloc_imgbow *p, double *out_bow) {
   SFM_CHECK(p && out_bow, SFMLOC_EINVAL, "sfmloc_imgbow_vector_read: null argument");

@@ -3,13 +3,17 @@
 //
 //   OpenMVGLocalization_AKAZE <queryImage|dir> <sfmDataDir> <matchDir> <outputFolder>
 //        [-f=0.6] [-r=200] [-k=0] [-x= -y= -z= -d=-1] [-a=BOWfile.yml] [-p=PCAfile.yml] [-i=1] [-g=4.0] [--featdir=DIR]
+//        [--device-decode]
 //
 // Same arguments, console messages and output files (<outputFolder>/<base>.json with the reference's keys and
 // Eigen IOFormat(6) matrices; the failure form has the first three keys only, localization.cpp:84-153).
 // Images are decoded by the library's own cv::imread (sfmloc_image_read: JPEG, PNG, binary PGM/PPM); when the image
 // cannot be decoded the query's features are taken from <featdir>/<base>.desc/.feat (the files extractAKAZESingleImg writes, AKAZEOpenCV.cpp:80-111); the BoW shortlist
 // (-k) uses <featdir>/<base>.bow if present, else the dense-feature chain on the decoded colour image; -w writes
-// <matchDir>/matches.fQ.txt as the reference does; -gm = guided matching in the geometric stage (:82,183,451).  The Python mirror (sfmlocalization_amd/engine.py) covers the same contract.
+// <matchDir>/matches.fQ.txt as the reference does; -gm = guided matching in the geometric stage (:82,183,451).
+// --device-decode (not the reference's): a query file is entropy-decoded ONCE on the host and reconstructed on the device
+// (sfmloc_imread: GRAY, and BGR when the BoW vector has to come from the image); extraction and the dense BoW chain read
+// the resident images.  The output files are the same bytes.  The Python mirror (sfmlocalization_amd/engine.py) covers the same contract.
 #include <dirent.h>
 #include <sys/stat.h>
 
@@ -61,6 +65,28 @@ bool read_bow(const std::string &p, std::vector<float> *v) {
 // ---------------------------------------------------------------------------------------------------------
 // image decoding = the library's cv::imread (sfmloc_image_read: JPEG, PNG, binary PGM/PPM)
 // ---------------------------------------------------------------------------------------------------------
+// --device-decode: one reader for the run, made (or remade larger) for the file's size; the file's images stay resident
+struct DeviceReader {
+  sfmloc_imread *r = nullptr;
+  int max_w = 0, max_h = 0;
+  bool read(const std::string &path, int device, uint32_t want, int *w, int *h) {
+    int32_t iw = 0, ih = 0;
+    if (sfmloc_image_read(path.c_str(), 0, nullptr, 0, &iw, &ih)) return false;
+    if (!r || iw > max_w || ih > max_h) {
+      sfmloc_imread_destroy(r);
+      r = nullptr;
+      max_w = std::max(max_w, (int)iw);
+      max_h = std::max(max_h, (int)ih);
+      if (sfmloc_imread_create(device, (uint32_t)max_w, (uint32_t)max_h, &r)) return false;
+    }
+    if (sfmloc_imread_file(r, path.c_str(), want, &iw, &ih)) return false;
+    *w = iw;
+    *h = ih;
+    return true;
+  }
+  ~DeviceReader() { sfmloc_imread_destroy(r); }
+};
+
 bool load_image(const std::string &path, bool color, std::vector<uint8_t> *px, int *w, int *h) {
   int32_t iw = 0, ih = 0;
   if (sfmloc_image_read(path.c_str(), color ? 1 : 0, nullptr, 0, &iw, &ih)) return false;
@@ -202,6 +228,16 @@ struct DenseBow {
     out->assign(bow.begin(), bow.end());
     return true;
   }
+  // the same from a reader's resident colour image (sfmloc_imread_decode with SFMLOC_IMREAD_BGR)
+  bool compute_dev(sfmloc_imread *reader, int w, int h, std::vector<float> *out) {
+    if (!ready) return false;
+    sfmloc_imgbow *&ib = by_size[std::make_pair(w, h)];
+    if (!ib && sfmloc_imgbow_create(&d, device, (uint32_t)w, (uint32_t)h, 3, &ib)) return false;
+    std::vector<double> bow((size_t)sfmloc_imgbow_dim(ib));
+    if (sfmloc_imgbow_compute_dev(ib, reader, SFMLOC_IMREAD_BGR, nullptr, bow.data())) return false;
+    out->assign(bow.begin(), bow.end());
+    return true;
+  }
   ~DenseBow() {
     for (auto &kv : by_size)
       if (kv.second) sfmloc_imgbow_destroy(kv.second);
@@ -267,7 +303,7 @@ int main(int argc, char **argv) {
   const Args a = parse_args(argc, argv);
   if (a.pos.size() < 4 || a.opt.count("h") || a.opt.count("help")) {
     printf("usage: OpenMVGLocalization_AKAZE <queryImage|dir> <sfmDataDir> <matchDir> <outputFolder> [-f=0.6] [-r=200] "
-           "[-k=0] [-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated]\n");
+           "[-k=0] [-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated] [--device-decode]\n");
     return 1;
   }
   const std::string query = a.pos[0], sfm_dir = a.pos[1], match_dir = a.pos[2], out_dir = a.pos[3];
@@ -285,6 +321,7 @@ int main(int argc, char **argv) {
   // -u: the query images come from a camera nobody calibrated -- six-point resection, the result's K is the recovered
   // one (sfmloc.h "Uncalibrated queries"); not in the reference's tool, whose Localize call always passes the intrinsic
   const bool uncalibrated = a.flag({"u", "uncalibrated"});
+  const bool device_decode = a.flag({"device-decode"});
   const std::string featdir_opt = a.get({"featdir"}, "");
   const int device = atoi(a.get({"device"}, "0").c_str());
   if (every <= 0) every = 1;
@@ -352,6 +389,7 @@ int main(int argc, char **argv) {
 
   std::map<std::pair<int, int>, sfmloc_akaze *> extractors;
   DenseBow dense;
+  DeviceReader reader;  // (declared after the extractors' map and `dense`; all are released before the map below)
   int n_img = 0, match_next = 0, rc_all = 0;
   for (const std::string &img : images) {
     ++n_img;
@@ -368,7 +406,11 @@ int main(int argc, char **argv) {
     std::vector<float> xy;
     std::vector<uint8_t> gray, bgr;
     int gw = 0, gh = 0;
-    const bool have_img = load_image(img, false, &gray, &gw, &gh);  // imread(IMREAD_GRAYSCALE), AKAZEOpenCV.cpp:60
+    // the BoW vector has to come from the image: asked for, and no precomputed <base>.bow
+    const bool bow_from_image = knn_bow > 0 && !bow_model.empty() && !is_file(join(fdir, base + ".bow"));
+    const bool have_img =  // imread(IMREAD_GRAYSCALE), AKAZEOpenCV.cpp:60 (and the colour read with it, on the device)
+        device_decode ? reader.read(img, device, SFMLOC_IMREAD_GRAY | (bow_from_image ? SFMLOC_IMREAD_BGR : 0), &gw, &gh)
+                      : load_image(img, false, &gray, &gw, &gh);
     if (have_img) {
       w = gw;
       h = gh;
@@ -397,7 +439,8 @@ int main(int argc, char **argv) {
       std::vector<float> kp((size_t)cap * 6);
       desc.assign((size_t)cap * 64, 0);
       uint32_t n = 0;
-      if (sfmloc_akaze_detect_and_compute(ak, gray.data(), kp.data(), desc.data(), cap, &n)) {
+      if (device_decode ? sfmloc_akaze_detect_and_compute_dev(ak, reader.r, SFMLOC_IMREAD_GRAY, kp.data(), desc.data(), cap, &n)
+                        : sfmloc_akaze_detect_and_compute(ak, gray.data(), kp.data(), desc.data(), cap, &n)) {
         fprintf(stderr, "%s\n", sfmloc_last_error());
         rc_all = 1;
         break;
@@ -439,7 +482,10 @@ int main(int argc, char **argv) {
             break;
           }
           int cw = 0, ch = 0;  // imread(IMREAD_COLOR), DenseLocalFeatureWrapper.cpp:85
-          have_bow = load_image(img, true, &bgr, &cw, &ch) && dense.compute(bgr, cw, ch, &bow);
+          // (a <base>.bow that is there but unreadable: the colour image is read now)
+          have_bow = device_decode ? ((bow_from_image || reader.read(img, device, SFMLOC_IMREAD_BGR, &cw, &ch)) &&
+                                      dense.compute_dev(reader.r, w, h, &bow))
+                                   : (load_image(img, true, &bgr, &cw, &ch) && dense.compute(bgr, cw, ch, &bow));
         }
       }
       sfmloc_query *q = nullptr;

@@ -582,6 +582,14 @@ int akaze_compute_resident(Akaze *a, const float *d_kin, unsigned int n, int nee
 // throws std::bad_alloc
 void dense_grid_build(int size, std::vector<float> *grid, std::vector<float> *kxy);
 
+// imread_dev.hip: a reader's resident image for a consumer inside the library (akaze.hip, imgbow.hip).
+// imread_feed: checks that `which` is one image of the reader's last decode, on `device` and w x h (SFMLOC_EINVAL, text
+// starting with `who`), makes stream s wait for the reader's work and gives the image's address.  imread_consumed: called
+// once the consumer's reads are queued on s, so that the reader's next decode does not overwrite the image under them.
+struct Imread;
+int imread_feed(Imread *r, uint32_t which, int device, uint32_t w, uint32_t h, hipStream_t s, const uint8_t **dev, const char *who);
+int imread_consumed(Imread *r, hipStream_t s);
+
 // acransac.hip
 int launch_fill_log10(double *d_L10, int n, hipStream_t s);
 int launch_debug_math(int op, const double *d_in, int n, int in_stride, double *d_out, int out_stride, hipStream_t s);

@@ -75,6 +75,9 @@ class LocalizeEngine:
     def close(self):
         for ak in getattr(self, "_akaze", {}).values():
             ak.close()
+        if getattr(self, "_imread", None) is not None:
+            self._imread.close()
+            self._imread = None
         self.map.close()
 
     def extract(self, gray):
@@ -82,6 +85,27 @@ class LocalizeEngine:
         image_describer.txt options (AKAZEOption.cpp:44-55): -> desc [n x 64], kpts [n x 4] (x, y, size, angle)."""
         gray = np.ascontiguousarray(gray, np.uint8)
         h, w = gray.shape
+        kp, desc = self._extractor(w, h).detect_and_compute(gray)
+        return desc, kp[:, :4]
+
+    def extract_dev(self, reader, which=capi.IMREAD_GRAY):
+        """extract() on a DeviceImread's resident gray image: no host pixels"""
+        kp, desc = self._extractor(reader.width, reader.height).detect_and_compute_dev(reader, which)
+        return desc, kp[:, :4]
+
+    def device_read(self, path, want):
+        """the file through the engine's DeviceImread (made, or remade larger, for the file's size) -> the reader"""
+        w, h = capi.image_size(path)
+        r = getattr(self, "_imread", None)
+        if r is None or w > r.max_width or h > r.max_height:
+            mw, mh = (w, h) if r is None else (max(w, r.max_width), max(h, r.max_height))
+            if r is not None:
+                r.close()
+            r = self._imread = capi.DeviceImread(mw, mh, device=int(self.params.device))
+        r.file(path, want)
+        return r
+
+    def _extractor(self, w, h):
         if not hasattr(self, "_akaze"):
             self._akaze = {}
             self._akaze_opt = fileio.read_image_describer(os.path.join(self.match_dir, "image_describer.txt"))
@@ -91,8 +115,7 @@ class LocalizeEngine:
             o = self._akaze_opt
             self._akaze[(w, h)] = capi.Akaze(w, h, int(o["nOct"]), int(o["nOctLay"]), float(o["thres"]),
                                              device=int(self.params.device))
-        kp, desc = self._akaze[(w, h)].detect_and_compute(gray)
-        return desc, kp[:, :4]
+        return self._akaze[(w, h)]
 
     def localize_image(self, gray, **kw):
         """LocalizeEngine::localize on an image (LocalizeEngine.cc:288-661): extract, then localize().  A colour
@@ -112,9 +135,21 @@ class LocalizeEngine:
             ex["times"][2] = t_feat
         return res, ex
 
-    def localize_file(self, path, **kw):
-        """The server's entry point on a stored image (localizeImage.cc:463: imread(path, IMREAD_COLOR) -> localize)."""
-        return self.localize_image(capi.image_read(path, color=True), **kw)
+    def localize_file(self, path, device_decode=False, **kw):
+        """The server's entry point on a stored image (localizeImage.cc:463: imread(path, IMREAD_COLOR) -> localize).
+        device_decode=True: one entropy pass on the host, the colour read's gray (BGR2GRAY) reconstructed and kept on the
+        device, extraction from it -- no host pixels; the same result."""
+        if not device_decode:
+            return self.localize_image(capi.image_read(path, color=True), **kw)
+        t_feat = time.perf_counter()
+        reader = self.device_read(path, capi.IMREAD_BGR2GRAY)
+        desc, kp = self.extract_dev(reader, capi.IMREAD_BGR2GRAY)
+        t_feat = time.perf_counter() - t_feat
+        res, ex = self.localize(desc, kp[:, :2], reader.width, reader.height, **kw)
+        ex["n_features"] = len(desc)
+        if "times" in ex:
+            ex["times"][2] = t_feat
+        return res, ex
 
     # getLocalViews (SfMDataUtils.cpp:210-227 / LocalizeEngine.cc:200-): NOTE the reference compares the SQUARED
     # distance with the un-squared radius; reproduced.
@@ -241,6 +276,14 @@ class DenseBow:
             ib = self._resident[(w, h)] = capi.ImgBow.from_files(self._files[0], self._files[1], w, h, 3, device=self.device)
         return ib.compute(bgr)
 
+    def compute_dev(self, reader):
+        """compute() on a DeviceImread's resident colour image (capi.IMREAD_BGR): the same bits"""
+        w, h = reader.width, reader.height
+        ib = self._resident.get((w, h))
+        if ib is None:
+            ib = self._resident[(w, h)] = capi.ImgBow.from_files(self._files[0], self._files[1], w, h, 3, device=self.device)
+        return ib.compute_dev(reader, capi.IMREAD_BGR)
+
     def close(self):
         for ib in self._resident.values():
             ib.close()
@@ -287,6 +330,8 @@ KEYS = [  # localization.cpp:64-82
     (("p", "pcaModelFile"), "", str), (("i", "locEvryNFrame"), "1", int), (("g", "geomLimit"), "4.0", float),
     (("gm", "guidedMatch"), "false", _b), (("featdir",), "", str), (("device",), "0", int),
     (("u", "uncalibrated"), "false", _b),
+    # not the reference's: a query file is entropy-decoded once and reconstructed on the device (capi.DeviceImread)
+    (("device-decode",), "false", _b),
 ]
 
 
@@ -295,7 +340,7 @@ def main(argv=None):
     pos, o = parse_cv_args(argv, KEYS)
     if len(pos) < 4 or "h" in argv or "--help" in argv:
         print("usage: localize <queryImage|dir> <sfmDataDir> <matchDir> <outputFolder> [-f=0.6] [-r=200] [-k=0] "
-              "[-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated]")
+              "[-x= -y= -z= -d=-1] [-i=1] [-g=4.0] [--featdir=DIR] [-u|--uncalibrated] [--device-decode]")
         return 1
     query, sfm_dir, match_dir, out_dir = pos[:4]
     print("Start localizing input image.")
@@ -346,22 +391,46 @@ def main(argv=None):
         base = os.path.splitext(os.path.basename(img))[0]
         fdir = o["featdir"] or os.path.dirname(img)
         w, h = _image_size(img, default_wh)
+        # the BoW vector has to come from the image: no precomputed <base>.bow (below)
+        bow_from_image = (o["knnbow"] > 0 and bool(o["bowModelFile"])
+                          and not os.path.exists(os.path.join(fdir, base + ".bow")))
+        reader = None        # --device-decode: the file's resident images, read ONCE for extraction and the BoW chain
         try:
             desc = fileio.read_desc(os.path.join(fdir, base + ".desc"))
             feat = fileio.read_feat(os.path.join(fdir, base + ".feat"))
         except (IOError, OSError) as e:
-            gray = _load_gray(img)
-            if gray is None:
+            gray = None
+            if o["device-decode"]:
+                try:
+                    reader = eng.device_read(img, capi.IMREAD_GRAY | (capi.IMREAD_BGR if bow_from_image else 0))
+                except capi.SfmlocError:
+                    reader = None
+            else:
+                gray = _load_gray(img)
+            if gray is None and reader is None:
                 print(f"cannot read {img} nor precomputed features for it: {e}", file=sys.stderr)
                 fileio.write_result_json(out_dir, img, sfm_json, match_dir)
                 continue
             print("Extract features from query image")          # localization.cpp:313
-            desc, feat = eng.extract(gray)
+            if reader is not None:
+                desc, feat = eng.extract_dev(reader, capi.IMREAD_GRAY)
+                w, h = reader.width, reader.height
+            else:
+                desc, feat = eng.extract(gray)
+                h, w = gray.shape
             feat = synth_round6(feat)                            # what the reference reads back from its .feat
-            h, w = gray.shape
         center = (o["cenLocX"], o["cenLocY"], o["cenLocZ"]) if o["cenRadius"] > 0 else None
         bow = None
-        if o["knnbow"] > 0 and o["bowModelFile"]:
+        if bow_from_image and o["device-decode"]:
+            if dense is None:
+                dense = DenseBow(o["bowModelFile"], o["pcaModelFile"] or None, device=o["device"])
+            try:
+                if reader is None:                               # (features were precomputed: the colour image alone)
+                    reader = eng.device_read(img, capi.IMREAD_BGR)
+                bow = dense.compute_dev(reader)
+            except capi.SfmlocError:
+                bow = None                                       # as an undecodable colour read: no shortlist
+        elif o["knnbow"] > 0 and o["bowModelFile"]:
             # the query's BoW vector (localization.cpp:346-361): a precomputed <base>.bow next to its features if
             # there is one (what TrainBoW's calcBoF writes per view, TrainBoW.cpp:256-271), else computed from the
             # colour image as the reference does (DenseLocalFeatureWrapper -> PcaWrapper -> BoFSpatialPyramids)
