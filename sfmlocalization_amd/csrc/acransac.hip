@@ -2591,9 +2591,7 @@ static int ensure_fmatrix_large(Ctx *c) {
   g.add(c->fl_list, (size_t)m->n_views + 1);
   if (!g.ok()) return g.rc();
   g.commit();
-  SFM_HIP(hipMemset(c->fl_count, 0, sizeof(uint32_t)));  // (from the next query on the query's reset kernel clears it)
-  SFM_HIP(hipStreamSynchronize(nullptr));                // (null stream: not ordered with the context's stream otherwise)
-  return SFMLOC_OK;
+  return c->fl_count.zero(c->stream);  // (ahead of the launch that follows; later queries' reset kernel clears it)
 }
 
 // the argument list as the kernels take it (FFilterArgsPacked): the context's block on the device is rewritten when its
@@ -2636,7 +2634,7 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
     // (ahead of whatever a recording member has recorded -- nothing recorded reads the block before this call's launches
     // -- and without issuing it: a plain use of the stream would end the session's sharing for this member)
     hipStream_t s = c->stream.unordered();
-    SFM_HIP(hipMemcpyAsync(c->d_k3_static, c->k3_static_host, sizeof(T), hipMemcpyHostToDevice, s));
+    SFM_RC(c->d_k3_static.upload(c->k3_static_host, sizeof(T), s));
     SFM_HIP(hipStreamSynchronize(s));
     c->k3_static_valid = true;
   }
@@ -2707,7 +2705,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     // (a memset on the context's stream would end a gang session's recording: every real map has views above 2 048 rows,
     // and with this line a session of image-in frames issued 93 launches, none of them shared -- the query's reset
     // kernel clears the counter; only the staged API, which has no reset kernel, clears it here)
-    if (!pass.cleared && !fresh) SFM_HIP(hipMemsetAsync(c->fl_count, 0, sizeof(uint32_t), c->stream));
+    if (!pass.cleared && !fresh) SFM_RC(c->fl_count.zero(1, c->stream));
     A.large_count = c->fl_count;
     A.large_list = c->fl_list;
   }
@@ -2741,7 +2739,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
       g.commit();
       // (the last arrival clears its slot.  On the stream the launch below goes to, so that nothing waits for the device:
       // every context of a busy map gets here once.  Nothing a gang member has recorded touches the new buffer.)
-      SFM_HIP(hipMemsetAsync(c->d_k3_arrive, 0, (size_t)kK3WideViews * sizeof(unsigned int), c->stream.unordered()));
+      SFM_RC(c->d_k3_arrive.zero(kK3WideViews, c->stream.unordered()));
     }
     A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec.get());
     A.spec_arrive = c->d_k3_arrive;

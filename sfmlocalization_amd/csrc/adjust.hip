@@ -207,7 +207,7 @@ int sfm_transpose(Sfm *h) {
     hipLaunchKernelGGL(k_adj_obs_landmark, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->d_obs_off, h->n_lm,
                        h->d_obs_lm, h->d_vlist);
   SFM_HIP(hipGetLastError());
-  if (n) SFM_HIP(hipMemcpyAsync(h->d_vkey, h->d_obs_view, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  if (n) SFM_RC(h->d_vkey.copy_from(h->d_obs_view, n, s));
   // (an odd number of passes leaves the result in the scratch pair)
   if (radix_sort_pairs(h->d_vkey, h->d_vlist, h->d_tmp_k, h->d_tmp_v, n, radix_key_bits(h->n_views - 1), h->d_hist, s)) {
     std::swap(h->d_vkey, h->d_tmp_k);
@@ -218,8 +218,7 @@ int sfm_transpose(Sfm *h) {
                      h->d_view_off);
   SFM_HIP(hipGetLastError());
   h->h_view_off.assign((size_t)h->n_views + 1, 0);
-  SFM_HIP(hipMemcpyAsync(h->h_view_off.data(), h->d_view_off, ((size_t)h->n_views + 1) * sizeof(uint32_t),
-                         hipMemcpyDeviceToHost, s));
+  SFM_RC(h->d_view_off.download(h->h_view_off.data(), (size_t)h->n_views + 1, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
@@ -380,11 +379,9 @@ int sfm_resect_impl(Sfm *h, uint32_t *n_ran, uint32_t *n_ok) {
     return h->inliers[k];
   });
   if (rc) return rc;
-  SFM_HIP(hipMemcpyAsync(h->d_pose_valid, h->h_pose_valid.data(), h->n_poses, hipMemcpyHostToDevice, h->s));
-  SFM_HIP(hipMemcpyAsync(h->d_pose_R, h->h_pose_R.data(), 9 * (size_t)h->n_poses * sizeof(double),
-                         hipMemcpyHostToDevice, h->s));
-  SFM_HIP(hipMemcpyAsync(h->d_pose_C, h->h_pose_C.data(), 3 * (size_t)h->n_poses * sizeof(double),
-                         hipMemcpyHostToDevice, h->s));
+  SFM_RC(h->d_pose_valid.upload(h->h_pose_valid.data(), h->n_poses, h->s));
+  SFM_RC(h->d_pose_R.upload(h->h_pose_R.data(), 9 * (size_t)h->n_poses, h->s));
+  SFM_RC(h->d_pose_C.upload(h->h_pose_C.data(), 3 * (size_t)h->n_poses, h->s));
   SFM_HIP(hipStreamSynchronize(h->s));
   h->resected = true;
   if (n_ran) *n_ran = ran;
@@ -397,8 +394,8 @@ int sfm_fetch_masks(Sfm *h) {
   if (!h->cleaned) return SFMLOC_OK;
   h->h_obs_keep.resize(h->n_obs);
   h->h_lm_stage.resize(h->n_lm);
-  if (h->n_obs) SFM_HIP(hipMemcpyAsync(h->h_obs_keep.data(), h->d_obs_keep, h->n_obs, hipMemcpyDeviceToHost, h->s));
-  if (h->n_lm) SFM_HIP(hipMemcpyAsync(h->h_lm_stage.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost, h->s));
+  if (h->n_obs) SFM_RC(h->d_obs_keep.download(h->h_obs_keep.data(), h->n_obs, h->s));
+  if (h->n_lm) SFM_RC(h->d_lm_stage.download(h->h_lm_stage.data(), h->n_lm, h->s));
   SFM_HIP(hipStreamSynchronize(h->s));
   return SFMLOC_OK;
 }
@@ -423,8 +420,8 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
     SFM_HIP(hipGetLastError());
   }
   std::vector<uint8_t> stage(h->n_lm);
-  if (h->n_lm) SFM_HIP(hipMemcpyAsync(stage.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(h->h_pose_valid.data(), h->d_pose_valid, h->n_poses, hipMemcpyDeviceToHost, s));
+  if (h->n_lm) SFM_RC(h->d_lm_stage.download(stage.data(), h->n_lm, s));
+  SFM_RC(h->d_pose_valid.download(h->h_pose_valid.data(), h->n_poses, s));
   SFM_HIP(hipStreamSynchronize(s));
   if (counts) {
     counts[0] = counts[1] = counts[2] = counts[3] = 0;
@@ -505,10 +502,8 @@ int sfm_check_poses(Sfm &h, const char *what) {
 
 // the host's copy of the pose table follows the device's (sfmloc_sfm_read reads it)
 int sfm_fetch_poses(Sfm &h) {
-  SFM_HIP(hipMemcpyAsync(h.h_pose_R.data(), h.d_pose_R, 9 * (size_t)h.n_poses * sizeof(double), hipMemcpyDeviceToHost,
-                         h.s));
-  SFM_HIP(hipMemcpyAsync(h.h_pose_C.data(), h.d_pose_C, 3 * (size_t)h.n_poses * sizeof(double), hipMemcpyDeviceToHost,
-                         h.s));
+  SFM_RC(h.d_pose_R.download(h.h_pose_R.data(), 9 * (size_t)h.n_poses, h.s));
+  SFM_RC(h.d_pose_C.download(h.h_pose_C.data(), 3 * (size_t)h.n_poses, h.s));
   SFM_HIP(hipStreamSynchronize(h.s));
   return SFMLOC_OK;
 }
@@ -576,7 +571,7 @@ int sfmloc_sfm_read_intrinsics(sfmloc_sfm *hh, double *K) {
   SFM_CHECK(hh && K, SFMLOC_EINVAL, "sfmloc_sfm_read_intrinsics: null argument");
   Sfm *h = reinterpret_cast<Sfm *>(hh);
   SFM_HIP(hipSetDevice(h->device));
-  SFM_HIP(hipMemcpy(K, h->d_intr, 6 * (size_t)h->n_intr * sizeof(double), hipMemcpyDeviceToHost));
+  SFM_RC(h->d_intr.read(K, 6 * (size_t)h->n_intr, h->s));
   return SFMLOC_OK;
 }
 
@@ -584,7 +579,7 @@ int sfmloc_sfm_read_structure(sfmloc_sfm *hh, double *X) {
   SFM_CHECK(hh && X, SFMLOC_EINVAL, "sfmloc_sfm_read_structure: null argument");
   Sfm *h = reinterpret_cast<Sfm *>(hh);
   SFM_HIP(hipSetDevice(h->device));
-  if (h->n_lm) SFM_HIP(hipMemcpy(X, h->d_lm_X, 3 * (size_t)h->n_lm * sizeof(double), hipMemcpyDeviceToHost));
+  if (h->n_lm) SFM_RC(h->d_lm_X.read(X, 3 * (size_t)h->n_lm, h->s));
   return SFMLOC_OK;
 }
 
@@ -598,10 +593,10 @@ int sfmloc_sfm_read(sfmloc_sfm *hh, uint8_t *pose_valid, double *pose_R, double 
   if (pose_valid) memcpy(pose_valid, h->h_pose_valid.data(), h->n_poses);
   if (pose_R) memcpy(pose_R, h->h_pose_R.data(), 9 * (size_t)h->n_poses * sizeof(double));
   if (pose_C) memcpy(pose_C, h->h_pose_C.data(), 3 * (size_t)h->n_poses * sizeof(double));
-  if (obs_keep && h->n_obs) SFM_HIP(hipMemcpy(obs_keep, h->d_obs_keep, h->n_obs, hipMemcpyDeviceToHost));
+  if (obs_keep && h->n_obs) SFM_RC(h->d_obs_keep.read(obs_keep, h->n_obs, h->s));
   if (landmark_keep && h->n_lm) {
     std::vector<uint8_t> st(h->n_lm);
-    SFM_HIP(hipMemcpy(st.data(), h->d_lm_stage, h->n_lm, hipMemcpyDeviceToHost));
+    SFM_RC(h->d_lm_stage.read(st.data(), h->n_lm, h->s));
     for (uint32_t l = 0; l < h->n_lm; ++l) landmark_keep[l] = st[l] == 3 ? 1 : 0;
   }
   return SFMLOC_OK;
@@ -612,8 +607,8 @@ int sfmloc_sfm_debug_read(sfmloc_sfm *hh, double *residual, double *min_cos) {
   Sfm *h = reinterpret_cast<Sfm *>(hh);
   SFM_CHECK(h->cleaned, SFMLOC_EINVAL, "sfmloc_sfm_debug_read: after the cleanup only");
   SFM_HIP(hipSetDevice(h->device));
-  if (residual && h->n_obs) SFM_HIP(hipMemcpy(residual, h->d_res, h->n_obs * sizeof(double), hipMemcpyDeviceToHost));
-  if (min_cos && h->n_lm) SFM_HIP(hipMemcpy(min_cos, h->d_mincos, h->n_lm * sizeof(double), hipMemcpyDeviceToHost));
+  if (residual && h->n_obs) SFM_RC(h->d_res.read(residual, h->n_obs, h->s));
+  if (min_cos && h->n_lm) SFM_RC(h->d_mincos.read(min_cos, h->n_lm, h->s));
   return SFMLOC_OK;
 }
 

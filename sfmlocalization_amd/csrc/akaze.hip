@@ -1979,7 +1979,7 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
   const Detection &D = a->det;
   const int w = a->w, h = a->h;
   // (nothing recorded for this image touches d_gray before the upload: it need not wait for a gang session's launches)
-  if (gray) AK_HIP(hipMemcpyAsync(a->d_gray, gray, (size_t)w * h, hipMemcpyHostToDevice, a->stream.unordered()));
+  if (gray) SFM_RC(a->d_gray.upload(gray, (size_t)w * h, a->stream.unordered()));
   {
     Taps2 t2;
     for (int k = 0; k < 9; ++k) t2.k9[k] = P.g16[k];
@@ -2103,7 +2103,7 @@ int orient_describe_enqueue(Akaze *a, const std::vector<float> &kin, unsigned in
   if (rc) return rc;
   if (phase != 2) {
     // (the keypoints go up ahead of anything recorded: nothing recorded for this extractor in the session reads d_kp)
-    if (n) AK_HIP(hipMemcpyAsync(a->d_kp, kin.data(), (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, a->stream.unordered()));
+    if (n) SFM_RC(a->d_kp.upload(kin.data(), (size_t)n * 4, a->stream.unordered()));
     sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(grid_n), dim3(64), 0,
                                    (const DevLevels *)a->d_dev_levels, a->d_kp, (int)n, a->d_gauss25, a->d_win,
                                    a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
@@ -2112,8 +2112,8 @@ int orient_describe_enqueue(Akaze *a, const std::vector<float> &kin, unsigned in
     AK_HIP(hipGetLastError());
   }
   if (phase != 1 && n) {
-    if (angle_out) AK_HIP(hipMemcpyAsync(angle_out, a->d_angle, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-    if (desc64) AK_HIP(hipMemcpyAsync(desc64, a->d_desc, (size_t)n * 64, hipMemcpyDeviceToHost, a->stream));
+    if (angle_out) SFM_RC(a->d_angle.download(angle_out, n, a->stream));
+    if (desc64) SFM_RC(a->d_desc.download(desc64, (size_t)n * 64, a->stream));
   }
   return SFMLOC_OK;
 }
@@ -2228,8 +2228,7 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
     SFM_RC(a->d_ncand.alloc(nullptr, 160));
     SFM_RC(a->d_seg.alloc(nullptr, (size_t)a->det.n_seg + 1));
     SFM_RC(a->d_seg_part.alloc(nullptr, kSegChunksMax + 1));
-    SFM_HIP(hipMemset(a->d_seg_part, 0, (kSegChunksMax + 1) * sizeof(unsigned int)));
-    SFM_HIP(hipStreamSynchronize(nullptr));  // (null stream: the extractor's streams are not ordered with it)
+    SFM_RC(a->d_seg_part.zero(nullptr));  // (no stream yet -- akaze_ensure_stream -- so done on return: devmem.h)
     SFM_RC(a->d_seg_x.alloc(nullptr, (size_t)a->det.n_seg * kSegMax));
     SFM_RC(a->d_cxy.alloc(nullptr, cc));
     SFM_RC(a->d_clevel.alloc(nullptr, cc));
@@ -2258,14 +2257,14 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
     std::vector<float> hs((size_t)kMaxLevels * kMaxFedSteps, 0.0f);
     for (int i = 0; i < a->plan.nlev; ++i)  // (nsteps <= kMaxFedSteps: make_plan)
       for (int k = 0; k < a->plan.lev[i].nsteps; ++k) hs[(size_t)i * kMaxFedSteps + k] = 0.5f * a->plan.lev[i].tsteps[k];
-    SFM_HIP(hipMemcpy(a->d_half_steps, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    SFM_RC(a->d_half_steps.upload(hs.data(), hs.size(), nullptr));
     const LevelTab T = level_tab(a);
-    SFM_HIP(hipMemcpy(a->d_level_tab, &T, sizeof(T), hipMemcpyHostToDevice));
+    SFM_RC(a->d_level_tab.upload(&T, 1, nullptr));
     const DevLevels LV = dev_levels(a);
-    SFM_HIP(hipMemcpy(a->d_dev_levels, &LV, sizeof(LV), hipMemcpyHostToDevice));
-    SFM_HIP(hipMemcpy(a->d_gauss25, a->plan.gauss25, 49 * 4, hipMemcpyHostToDevice));
-    SFM_HIP(hipMemcpy(a->d_win, a->plan.win_ang1, 64 * 4, hipMemcpyHostToDevice));
-    SFM_HIP(hipMemcpy(a->d_pair, a->plan.pair_tab, 486 * 2 * 2, hipMemcpyHostToDevice));
+    SFM_RC(a->d_dev_levels.upload(&LV, 1, nullptr));
+    SFM_RC(a->d_gauss25.upload(a->plan.gauss25, 49, nullptr));
+    SFM_RC(a->d_win.upload(a->plan.win_ang1, 64, nullptr));
+    SFM_RC(a->d_pair.upload(a->plan.pair_tab, 486 * 2, nullptr));
     return SFMLOC_OK;
   });
 }
@@ -2297,9 +2296,9 @@ int sfmloc_akaze_read_levels(sfmloc_akaze *ak, float *ldet, float *lt) {
   SFM_CHECK(ak, SFMLOC_EINVAL, "sfmloc_akaze_read_levels: null argument");
   Akaze *a = reinterpret_cast<Akaze *>(ak);
   SFM_HIP(hipSetDevice(a->device));
-  if (a->stream.own) SFM_HIP(hipStreamSynchronize(a->stream));
-  if (ldet) SFM_HIP(hipMemcpy(ldet, a->d_Ldet, a->plan.total * sizeof(float), hipMemcpyDeviceToHost));
-  if (lt) SFM_HIP(hipMemcpy(lt, a->d_Lt, a->plan.total * sizeof(float), hipMemcpyDeviceToHost));
+  const hipStream_t s = a->stream;  // (none yet: nothing was queued, and the read is done on return)
+  if (ldet) SFM_RC(a->d_Ldet.read(ldet, a->plan.total, s));
+  if (lt) SFM_RC(a->d_Lt.read(lt, a->plan.total, s));
   return SFMLOC_OK;
 }
 
@@ -2307,8 +2306,7 @@ int sfmloc_akaze_suppress_stats(sfmloc_akaze *ak, uint32_t *out9) {
   SFM_CHECK(ak && out9, SFMLOC_EINVAL, "sfmloc_akaze_suppress_stats: null argument");
   Akaze *a = reinterpret_cast<Akaze *>(ak);
   SFM_HIP(hipSetDevice(a->device));
-  if (a->stream.own) SFM_HIP(hipStreamSynchronize(a->stream));
-  SFM_HIP(hipMemcpy(out9, a->d_ncand, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SFM_RC(a->d_ncand.read(out9, 9, a->stream));
   return SFMLOC_OK;
 }
 
@@ -2368,7 +2366,7 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
 // the counts of one or more extractions (asynchronous on stream s; the caller synchronises), then their outputs
 static int akaze_counts_enqueue(Akaze *a, hipStream_t s) {
   static const bool timing_counts = getenv("SFMLOC_AKAZE_TIMING") != nullptr;
-  SFM_HIP(hipMemcpyAsync(a->h_counts, a->d_ncand, (timing_counts ? 160 : 9) * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+  SFM_RC(a->d_ncand.download(a->h_counts.get(), timing_counts ? 160 : 9, s));
   return SFMLOC_OK;
 }
 static int akaze_outputs_enqueue(Akaze *a, float *kpts, uint8_t *desc64, uint32_t cap, uint32_t *n_out, hipStream_t s) {
@@ -2376,8 +2374,8 @@ static int akaze_outputs_enqueue(Akaze *a, float *kpts, uint8_t *desc64, uint32_
   SFM_CHECK(nc <= a->det.cand_cap, SFMLOC_ECAP, "AKAZE: %u extrema candidates exceed the workspace (%u)", nc, a->det.cand_cap);
   *n_out = n;
   SFM_CHECK(n <= cap, SFMLOC_ECAP, "AKAZE: %u keypoints, caller buffers hold %u", n, cap);
-  if (n && kpts) SFM_HIP(hipMemcpyAsync(kpts, a->d_kp6, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (n && desc64) SFM_HIP(hipMemcpyAsync(desc64, a->d_desc, (size_t)n * 64, hipMemcpyDeviceToHost, s));
+  if (n && kpts) SFM_RC(a->d_kp6.download(kpts, (size_t)n * 6, s));
+  if (n && desc64) SFM_RC(a->d_desc.download(desc64, (size_t)n * 64, s));
   return SFMLOC_OK;
 }
 
@@ -2389,7 +2387,7 @@ static int akaze_take_resident(Akaze *a, sfmloc_imread *reader, uint32_t which, 
   hipStream_t s = a->stream;
   const uint8_t *src = nullptr;
   SFM_RC(imread_feed(r, which, a->device, (uint32_t)a->w, (uint32_t)a->h, s, &src, who));
-  SFM_HIP(hipMemcpyAsync(a->d_gray, src, (size_t)a->w * a->h, hipMemcpyDeviceToDevice, s));
+  SFM_RC(a->d_gray.copy_from(src, (size_t)a->w * a->h, s));
   return imread_consumed(r, s);
 }
 
@@ -2414,8 +2412,8 @@ static int akaze_detect_and_compute_one(Akaze *a, const uint8_t *gray, sfmloc_im
   const unsigned int spec = a->spec_n < cap ? a->spec_n : cap;
   float *const h_kp = reinterpret_cast<float *>(a->h_spec.get());
   uint8_t *const h_desc = a->h_spec + (size_t)a->det.spec_max * 6 * sizeof(float);
-  if (spec && kpts) SFM_HIP(hipMemcpyAsync(h_kp, a->d_kp6, (size_t)spec * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (spec && desc64) SFM_HIP(hipMemcpyAsync(h_desc, a->d_desc, (size_t)spec * 64, hipMemcpyDeviceToHost, s));
+  if (spec && kpts) SFM_RC(a->d_kp6.download(h_kp, (size_t)spec * 6, s));
+  if (spec && desc64) SFM_RC(a->d_desc.download(h_desc, (size_t)spec * 64, s));
   SFM_HIP(hipStreamSynchronize(s));
   const double t_1 = timing ? now_s() : 0.0;
   {

@@ -804,13 +804,13 @@ int ba_joint_run(Sfm &s, uint32_t what, const sfmloc_ba_joint_options &opt, sfml
   h.max_steps = opt.max_steps;
   h.running = 1;
   h.stop = 1;
-  SFM_HIP(hipMemcpyAsync(d_st.get(), &h, sizeof h, hipMemcpyHostToDevice, st));
+  SFM_RC(d_st.upload(&h, 1, st));
   // (without i the intrinsics' blocks stay out of the vectors the update pass walks: their p, q are never written)
   const uint32_t n_active = intr ? n_par : s.n_poses;
-  SFM_HIP(hipMemsetAsync(d_blk.get(), 0, kBlk * (size_t)n_par * sizeof(double), st));
-  SFM_HIP(hipMemsetAsync(d_x.get(), 0, 6 * (size_t)n_par * sizeof(double), st));
-  SFM_HIP(hipMemsetAsync(d_p.get(), 0, 6 * (size_t)n_par * sizeof(double), st));
-  SFM_HIP(hipMemsetAsync(d_lm_Cg.get(), 0, (3 * (size_t)s.n_lm + 1) * sizeof(double), st));
+  SFM_RC(d_blk.zero(kBlk * (size_t)n_par, st));
+  SFM_RC(dev_zero(d_x.get(), 6 * (size_t)n_par, st));
+  SFM_RC(d_p.zero(6 * (size_t)n_par, st));
+  SFM_RC(d_lm_Cg.zero(3 * (size_t)s.n_lm + 1, st));
 
   JtDev v{};
   static_cast<SfmDev &>(v) = sfm_dev(s);
@@ -850,7 +850,7 @@ int ba_joint_run(Sfm &s, uint32_t what, const sfmloc_ba_joint_options &opt, sfml
   rc = ba_pose_t(v, st);
   if (rc) return rc;
   auto read_state = [&]() -> int {
-    SFM_HIP(hipMemcpyAsync(&h, d_st.get(), sizeof h, hipMemcpyDeviceToHost, st));
+    SFM_RC(d_st.download(&h, 1, st));
     SFM_HIP(hipStreamSynchronize(st));
     return SFMLOC_OK;
   };
@@ -891,7 +891,7 @@ int ba_joint_run(Sfm &s, uint32_t what, const sfmloc_ba_joint_options &opt, sfml
   out.stop = h.stop;
   if (rep) *rep = out;
   if (what & SFMLOC_BA_INTRINSICS)
-    SFM_HIP(hipMemcpyAsync(s.h_intr.data(), v.intr, 6 * (size_t)s.n_intr * sizeof(double), hipMemcpyDeviceToHost, st));
+    SFM_RC(dev_download(s.h_intr.data(), v.intr, 6 * (size_t)s.n_intr, st));
   return sfm_fetch_poses(s);
 }
 

@@ -324,8 +324,8 @@ int ba_separable_run(Sfm &h, uint32_t what, sfmloc_ba_report *rep) {
     SFM_HIP(hipGetLastError());
     std::vector<double> cost(2 * (size_t)nb);
     std::vector<uint32_t> info(nb);
-    SFM_HIP(hipMemcpyAsync(cost.data(), v.blk_cost, cost.size() * sizeof(double), hipMemcpyDeviceToHost, h.s));
-    SFM_HIP(hipMemcpyAsync(info.data(), v.blk_info, info.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h.s));
+    SFM_RC(dev_download(cost.data(), v.blk_cost, cost.size(), h.s));
+    SFM_RC(dev_download(info.data(), v.blk_info, info.size(), h.s));
     SFM_HIP(hipStreamSynchronize(h.s));
     for (uint32_t b = 0; b < nb; ++b) {  // (ascending block index: the totals' order is fixed)
       if (!(info[b] & kInfoEntered)) continue;

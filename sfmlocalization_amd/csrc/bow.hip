@@ -613,7 +613,7 @@ int launch_bof_member(const BofModel *b, GangMember *m, const float *d_kxy, int 
 int launch_bof(const BofModel *b, hipStream_t s, const float *d_desc, const float *d_kxy, int n, uint32_t *d_counts,
                double *d_out, float *d_out_f32, const uint8_t *d_desc8) {
   const int cells = b->cells;
-  SFM_HIP(hipMemsetAsync(d_counts, 0, (size_t)b->K * cells * sizeof(uint32_t), s));
+  SFM_RC(dev_zero(d_counts, (size_t)b->K * cells, s));
   if (n > 0) {
     const size_t lds = BofTileLds::floats(b->in_dim, b->n_pca, b->cdim, b->K) * sizeof(float);
     if (lds <= 60 * 1024) {  // the model fits the LDS layout (the reference's does: 45 KB)

@@ -74,6 +74,11 @@ int stream_raw_create(void **s) {
   *s = h;
   return raw_created("hipStreamCreateWithFlags(hipStreamNonBlocking)", e, s);
 }
+static int raw_done(const char *what, hipError_t e) {  // (as SFM_HIP answers: the error stays with the runtime)
+  if (e == hipSuccess) return SFMLOC_OK;
+  set_error("%s -> %s", what, hipGetErrorString(e));
+  return hip_code(e);
+}
 void stream_raw_sync(void *s) { (void)hipStreamSynchronize(static_cast<hipStream_t>(s)); }
 void stream_raw_destroy(void *s) { (void)hipStreamDestroy(static_cast<hipStream_t>(s)); }
 int event_raw_create(void **ev, bool timing) {
@@ -87,6 +92,19 @@ int host_raw_alloc(void **p, size_t bytes) {
   return raw_created("hipHostMalloc", hipHostMalloc(p, bytes, hipHostMallocDefault), p);
 }
 void host_raw_free(void *p) { (void)hipHostFree(p); }
+
+// ... and every transfer is issued by these two (devmem.h "Transfers": a null stream means done on return)
+int dev_raw_copy(void *dst, const void *src, size_t bytes, CopyKind kind, hipStream_t s) {
+  const hipMemcpyKind k = kind == CopyKind::kHostToDevice   ? hipMemcpyHostToDevice
+                          : kind == CopyKind::kDeviceToHost ? hipMemcpyDeviceToHost
+                                                            : hipMemcpyDeviceToDevice;
+  const int rc = raw_done("hipMemcpyAsync", hipMemcpyAsync(dst, src, bytes, k, s));
+  return rc || s ? rc : raw_done("hipStreamSynchronize(null stream)", hipStreamSynchronize(nullptr));
+}
+int dev_raw_fill(void *dst, int byte, size_t bytes, hipStream_t s) {
+  const int rc = raw_done("hipMemsetAsync", hipMemsetAsync(dst, byte, bytes, s));
+  return rc || s ? rc : raw_done("hipStreamSynchronize(null stream)", hipStreamSynchronize(nullptr));
+}
 
 namespace {
 
@@ -228,6 +246,7 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
     SFM_RC(c->own_stream.create());
   }
   c->stream.own = c->own_stream;
+  const hipStream_t s = c->stream;  // every clear below is queued on it, and waited for before the context is handed out
   const uint64_t n_pad = (uint64_t)m->n_blocks * kBlockRows;
   uint64_t *acct = &c->hbm_bytes;
   c->merge_only = merge_only;
@@ -249,10 +268,10 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
     SFM_RC(dev_alloc(acct, c->d_rows_scratch, (size_t)c->rows_chunk_cap * 8 * 64));
     SFM_RC(dev_alloc(acct, c->d_rows_arrivals, (size_t)c->rows_chunk_cap));
     SFM_RC(dev_alloc(acct, c->d_flagged_desc, (size_t)c->rows_chunk_cap * 4 * 64));
-    SFM_HIP(hipMemset(c->d_rows_arrivals, 0, (size_t)c->rows_chunk_cap * sizeof(uint32_t)));
+    SFM_RC(c->d_rows_arrivals.zero(s));
   }
   SFM_RC(dev_alloc(acct, c->d_k1_counters, (size_t)kSelPairsSlot + 1));
-  SFM_HIP(hipMemset(c->d_k1_counters, 0, (kSelPairsSlot + 1) * sizeof(unsigned long long)));
+  SFM_RC(c->d_k1_counters.zero(s));
   SFM_RC(dev_alloc(acct, c->d_geo_count, (size_t)m->n_views + 1));
   if (full) SFM_RC(dev_alloc(acct, c->d_geo_idx, (size_t)m->n_rows));
   SFM_RC(dev_alloc(acct, c->d_geo_model, ((size_t)m->n_views + 1) * 10));
@@ -292,21 +311,19 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
   SFM_RC(c->h_pinned.alloc((size_t)2 * m->n_views + m->n_blocks + 16));
   SFM_RC(c->h_result.alloc(1));
   memset(c->h_result, 0, sizeof(HostResult));
-  SFM_HIP(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));
-  SFM_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
-  SFM_HIP(hipMemsetAsync(c->d_geo_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
-  SFM_HIP(hipMemsetAsync(c->d_ms_n, 0, sizeof(uint32_t), c->stream));
+  SFM_RC(dev_zero(c->d_status, 1, s));
+  SFM_RC(c->d_view_count.zero(s));
+  SFM_RC(c->d_geo_count.zero(s));
+  SFM_RC(c->d_ms_n.zero(s));
   SFM_RC(c->xev_out.create(kOrderingEvent));
   SFM_RC(c->xev_in.create(kOrderingEvent));
-  SFM_HIP(hipMemsetAsync(c->d_pose, 0, sizeof(Pose), c->stream));
-  SFM_HIP(hipMemsetAsync(c->d_p3p_state, 0, sizeof(P3pState), c->stream));
-  SFM_HIP(hipMemsetAsync(c->d_view_stats, 0, 3 * sizeof(uint32_t), c->stream));
-  SFM_HIP(hipStreamSynchronize(c->stream));
-  // (the two hipMemset above -- the arrival counters of k_hamming_rows, K1's statistics -- run on the NULL stream, which the
-  // context's non-blocking stream is not ordered with, and hipMemset of device memory may return before it has run: a first
-  // scan that overtook the memset found garbage arrival counters, merged nothing and left the head pass's seeds to K2 --
-  // the one wrong first scan of round 4, profiles/r04_pytest_gpu_failed_run_excerpt.txt)
-  SFM_HIP(hipStreamSynchronize(nullptr));
+  SFM_RC(dev_zero(c->d_pose, 1, s));
+  SFM_RC(dev_zero(c->d_p3p_state, 1, s));
+  SFM_RC(dev_zero(c->d_view_stats, 3, s));
+  // (the arrival counters of k_hamming_rows and K1's statistics among them: a first scan that met garbage arrival counters
+  // merged nothing and left the head pass's seeds to K2 -- the one wrong first scan of round 4,
+  // profiles/r04_pytest_gpu_failed_run_excerpt.txt -- so no clear of a context goes anywhere but its own stream)
+  SFM_HIP(hipStreamSynchronize(s));
   *out = owner.release();
   return SFMLOC_OK;
 }
@@ -451,10 +468,10 @@ int ctx_match_putative(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
     n_work_blocks = nb;
     c->last_blocks.assign(h_blk, h_blk + nb);
     if (n_sel) {
-      SFM_HIP(hipMemcpyAsync(c->d_view_sel, h_sel, n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-      SFM_HIP(hipMemcpyAsync(c->d_view_widx0, h_w0, n_sel * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+      SFM_RC(c->d_view_sel.upload(h_sel, n_sel, c->stream));
+      SFM_RC(c->d_view_widx0.upload(h_w0, n_sel, c->stream));
     }
-    if (nb) SFM_HIP(hipMemcpyAsync(c->d_block_list, h_blk, nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nb) SFM_RC(c->d_block_list.upload(h_blk, nb, c->stream));
     SFM_RC(c->pinned_busy.ensure(kOrderingEvent));
     SFM_HIP(hipEventRecord(c->pinned_busy, c->stream));
   }
@@ -469,7 +486,7 @@ int ctx_match_putative(Ctx *c, Query *q, QueryPass &pass, const ViewSel &sel) {
       split *= 2;
   }
 
-  if (!pass.cleared) SFM_HIP(hipMemsetAsync(c->d_view_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
+  if (!pass.cleared) SFM_RC(c->d_view_count.zero((size_t)m->n_views + 1, c->stream));
   c->last_split = split;
   c->last_nq = q->n;
   c->last_n_sel = n_sel;
@@ -511,8 +528,8 @@ int check_stage(Ctx *c, Query *q, const char *who) {
 int ctx_geometric_filter(Ctx *c, Query *q, QueryPass &pass) {
   Map *m = c->map;
   if (!pass.cleared) {
-    SFM_HIP(hipMemsetAsync(c->d_geo_count, 0, ((size_t)m->n_views + 1) * sizeof(uint32_t), c->stream));
-    SFM_HIP(hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream));
+    SFM_RC(c->d_geo_count.zero((size_t)m->n_views + 1, c->stream));
+    SFM_RC(dev_zero(c->d_status, 1, c->stream));
   }
   if (q->n == 0 || c->last_n_sel == 0) return SFMLOC_OK;
   EventScope ev(c, SFMLOC_K_FMATRIX);
@@ -614,7 +631,7 @@ namespace {
 int ctx_fetch_result(Ctx *c, bool no_p3p = false) {
   if (!no_p3p) return SFMLOC_OK;
   HostResult *h = c->h_result;
-  SFM_HIP(hipMemcpyAsync(h, c->d_result, sizeof(HostResult), hipMemcpyDeviceToHost, c->stream));
+  SFM_RC(c->d_result.download(h, sizeof(HostResult), c->stream));
   return SFMLOC_OK;
 }
 
@@ -709,8 +726,9 @@ int ctx_localize_end(Ctx *c, sfmloc_pose *out, uint32_t *pair_qfeat, uint32_t *p
     const uint32_t k = (uint32_t)out->n_inliers;
     SFM_CHECK(cap >= k, SFMLOC_ECAP, "pair buffers hold %u entries, %u inliers", cap, k);
     if (c->p3p_cap > (uint32_t)kP3pMaxN) {  // the pair lists live outside the HostResult record
-      if (pair_qfeat) SFM_HIP(hipMemcpy(pair_qfeat, c->d_pair_qfeat, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      if (pair_landmark) SFM_HIP(hipMemcpy(pair_landmark, c->d_pair_landmark, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      const hipStream_t cs = c->stream;
+      if (pair_qfeat) SFM_RC(dev_read(pair_qfeat, c->d_pair_qfeat, k, cs));
+      if (pair_landmark) SFM_RC(dev_read(pair_landmark, c->d_pair_landmark, k, cs));
     } else {
       if (pair_qfeat) memcpy(pair_qfeat, h->pair_qfeat, k * sizeof(uint32_t));
       if (pair_landmark) memcpy(pair_landmark, h->pair_landmark, k * sizeof(uint32_t));
@@ -954,14 +972,14 @@ static int map_fill(Map *m, const sfmloc_map_desc *d, const sfmloc_params &p) {
   const uint64_t n_pad = (uint64_t)m->n_blocks * kBlockRows;
   SFM_RC(dev_alloc(acct, m->d_bank, (size_t)n_pad * 4));
   if (n_pad) {
-    SFM_HIP(hipMemsetAsync(m->d_bank, 0, n_pad * 64, s));
+    SFM_RC(m->d_bank.zero(s));
     const uint64_t chunk = 16ull << 20;  // rows per staging chunk (1 GiB)
     DevBuf<uint4> d_stage;
     const uint64_t stage_rows = std::min<uint64_t>(chunk, d->n_rows);
     SFM_RC(d_stage.alloc(nullptr, stage_rows * 4));
     for (uint64_t r0 = 0; r0 < d->n_rows; r0 += chunk) {
       const uint64_t n = std::min<uint64_t>(chunk, d->n_rows - r0);
-      SFM_HIP(hipMemcpyAsync(d_stage, d->desc + r0 * 64, n * 64, hipMemcpyHostToDevice, s));
+      SFM_RC(d_stage.upload(d->desc + r0 * 64, n * 4, s)  /* (64-byte rows as four uint4) */);
       SFM_RC(launch_tile_bank(d_stage, r0, n, m->d_bank, s));
       SFM_HIP(hipStreamSynchronize(s));
     }
@@ -999,7 +1017,7 @@ static int map_fill(Map *m, const sfmloc_map_desc *d, const sfmloc_params &p) {
     uint16_t tab[513];
     build_ratio_table(p.dist_ratio, tab);
     SFM_RC(dev_alloc(acct, m->d_ratio_cnt, (size_t)513));
-    SFM_HIP(hipMemcpyAsync(m->d_ratio_cnt, tab, sizeof(tab), hipMemcpyHostToDevice, s));
+    SFM_RC(m->d_ratio_cnt.upload(tab, 513, s));
     SFM_HIP(hipStreamSynchronize(s));  // tab lives on the stack
     m->ratio_cnt_for = p.dist_ratio;
   }
@@ -1108,8 +1126,8 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
     if (!n_pad) return SFMLOC_OK;
     hipStream_t s = m->ctx0->stream;
     SFM_RC(q->d_desc.alloc(nullptr, n_pad * 4));
-    SFM_HIP(hipMemsetAsync(q->d_desc, 0, n_pad * 64, s));
-    SFM_HIP(hipMemcpyAsync(q->d_desc, desc, (size_t)n * 64, hipMemcpyHostToDevice, s));
+    SFM_RC(q->d_desc.zero(s));
+    SFM_RC(q->d_desc.upload(desc, (size_t)n * 4, s));
     std::vector<float> k6;
     if (kpt_xy) {
       q->h_kpt.assign(kpt_xy, kpt_xy + 2 * (size_t)n);
@@ -1120,8 +1138,8 @@ int sfmloc_query_create(sfmloc_map *map, const uint8_t *desc, const float *kpt_x
       sfmloc_feat_round_trip(kpt_xy, 2 * (uint64_t)n, k6.data());
       SFM_RC(q->d_kpt.alloc(nullptr, n));
       SFM_RC(q->d_kpt6.alloc(nullptr, n));
-      SFM_HIP(hipMemcpyAsync(q->d_kpt, kpt_xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s));
-      SFM_HIP(hipMemcpyAsync(q->d_kpt6, k6.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice, s));
+      SFM_RC(q->d_kpt.upload(kpt_xy, n, s));
+      SFM_RC(q->d_kpt6.upload(k6.data(), n, s));
     }
     SFM_HIP(hipStreamSynchronize(s));
     return SFMLOC_OK;
@@ -1187,7 +1205,7 @@ int sfmloc_query_set_bow(sfmloc_query *query, const float *query_bow) {
   SFM_CHECK(!q->is_view, SFMLOC_EINVAL, "sfmloc_query_set_bow: a view's BoW vector is given to sfmloc_query_create_view");
   SFM_HIP(hipSetDevice(m->device));
   if (!q->d_bow) SFM_HIP(query_array(q->d_bow, m->bow_dim));
-  SFM_HIP(hipMemcpy(q->d_bow, query_bow, (size_t)m->bow_dim * sizeof(float), hipMemcpyHostToDevice));
+  SFM_RC(q->d_bow.upload(query_bow, m->bow_dim, nullptr));
   return SFMLOC_OK;
 }
 
@@ -1216,16 +1234,16 @@ int sfmloc_putative_read(sfmloc_map *map, uint32_t *view_count, uint32_t *match_
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
   std::vector<uint32_t> cnt(m->n_views);
-  SFM_HIP(hipMemcpy(cnt.data(), c->d_view_count, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SFM_RC(c->d_view_count.read(cnt.data(), cnt.size(), cs));
   if (view_count) memcpy(view_count, cnt.data(), cnt.size() * sizeof(uint32_t));
   if (match_i || match_j || match_d) {
     SFM_CHECK(cap >= m->n_rows, SFMLOC_ECAP, "sfmloc_putative_read: cap %llu < n_rows %llu", (unsigned long long)cap,
               (unsigned long long)m->n_rows);
     std::vector<uint32_t> hi(m->n_rows), hk(m->n_rows);
-    SFM_HIP(hipMemcpy(hi.data(), c->d_match_i, hi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SFM_HIP(hipMemcpy(hk.data(), c->d_match_key, hk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_match_i.read(hi.data(), hi.size(), cs));
+    SFM_RC(c->d_match_key.read(hk.data(), hk.size(), cs));
     for (uint32_t v = 0; v < m->n_views; ++v) {
       const uint32_t off = m->h_view_off[v];
       for (uint32_t k = 0; k < cnt[v]; ++k) {
@@ -1243,7 +1261,8 @@ int sfmloc_putative_read_rows(sfmloc_map *map, uint32_t *best0, uint32_t *best1)
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
+  SFM_HIP(hipStreamSynchronize(cs));
   for (uint64_t r = 0; r < m->n_rows; ++r) {
     if (best0) best0[r] = SFMLOC_NOMATCH;
     if (best1) best1[r] = SFMLOC_NOMATCH;
@@ -1251,11 +1270,11 @@ int sfmloc_putative_read_rows(sfmloc_map *map, uint32_t *best0, uint32_t *best1)
   if (c->last_nq == 0 || c->last_n_sel == 0 || c->last_split == 0 || c->last_n_work_blocks == 0) return SFMLOC_OK;
   const uint64_t nwb = c->last_n_work_blocks;
   std::vector<uint2> part((size_t)c->last_split * nwb * 64);
-  SFM_HIP(hipMemcpy(part.data(), c->d_part, part.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+  SFM_RC(c->d_part.read(part.data(), part.size(), cs));
   std::vector<unsigned long long> mask;
   if (c->last_screened) {  // only the rows the screening scan could not reject have a pair; the others stay NOMATCH
     mask.resize(nwb);
-    SFM_HIP(hipMemcpy(mask.data(), c->d_flagmask, nwb * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_flagmask.read(mask.data(), nwb, cs));
   }
   auto push = [](uint32_t &b0, uint32_t &b1, uint32_t k) {
     if (k < b0) {
@@ -1267,7 +1286,7 @@ int sfmloc_putative_read_rows(sfmloc_map *map, uint32_t *best0, uint32_t *best1)
   };
   if (c->last_blocks_on_device) {  // the list was built on the device (BoW shortlist); padding names no block
     c->last_blocks.resize(nwb);
-    SFM_HIP(hipMemcpy(c->last_blocks.data(), c->d_block_list, nwb * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_block_list.read(c->last_blocks.data(), nwb, cs));
     c->last_blocks_on_device = false;
   }
   for (uint64_t w = 0; w < nwb; ++w) {
@@ -1306,21 +1325,21 @@ int sfmloc_geometric_read(sfmloc_map *map, uint32_t *geo_count, uint32_t *geo_id
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
   std::vector<uint32_t> cnt(m->n_views);
-  SFM_HIP(hipMemcpy(cnt.data(), c->d_geo_count, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SFM_RC(c->d_geo_count.read(cnt.data(), cnt.size(), cs));
   if (geo_count) memcpy(geo_count, cnt.data(), cnt.size() * sizeof(uint32_t));
   if (geo_idx) {
     SFM_CHECK(!c->geo_is_pairs, SFMLOC_EINVAL,
               "sfmloc_geometric_read: guided matches are not indices into the putative lists; use sfmloc_geometric_read_pairs");
     SFM_CHECK(cap >= m->n_rows, SFMLOC_ECAP, "sfmloc_geometric_read: cap too small");
     std::vector<uint32_t> gi(m->n_rows);
-    SFM_HIP(hipMemcpy(gi.data(), c->d_geo_idx, gi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_geo_idx.read(gi.data(), gi.size(), cs));
     for (uint32_t v = 0; v < m->n_views; ++v)
       for (uint32_t k = 0; k < cnt[v]; ++k) geo_idx[m->h_view_off[v] + k] = gi[m->h_view_off[v] + k];
   }
   int st = 0;
-  SFM_HIP(hipMemcpy(&st, c->d_status, sizeof(int), hipMemcpyDeviceToHost));
+  SFM_RC(dev_read(&st, c->d_status, 1, cs));
   SFM_CHECK((st & 1) == 0, SFMLOC_ECAP, "a view has more than 65536 putative matches");
   return SFMLOC_OK;
 }
@@ -1330,23 +1349,23 @@ int sfmloc_geometric_read_pairs(sfmloc_map *map, uint32_t *geo_count, uint32_t *
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
   std::vector<uint32_t> cnt(m->n_views);
-  SFM_HIP(hipMemcpy(cnt.data(), c->d_geo_count, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SFM_RC(c->d_geo_count.read(cnt.data(), cnt.size(), cs));
   if (geo_count) memcpy(geo_count, cnt.data(), cnt.size() * sizeof(uint32_t));
   if (geo_i || geo_j) {
     SFM_CHECK(cap >= m->n_rows, SFMLOC_ECAP, "sfmloc_geometric_read_pairs: cap too small");
     std::vector<uint32_t> gi(m->n_rows), gj;
-    SFM_HIP(hipMemcpy(gi.data(), c->d_geo_idx, gi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_geo_idx.read(gi.data(), gi.size(), cs));
     std::vector<uint32_t> pi, pk;
     if (c->geo_is_pairs) {
       gj.resize(m->n_rows);
-      SFM_HIP(hipMemcpy(gj.data(), c->d_geo_j, gj.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      SFM_RC(c->d_geo_j.read(gj.data(), gj.size(), cs));
     } else {  // indices into the putative lists: resolve them
       pi.resize(m->n_rows);
       pk.resize(m->n_rows);
-      SFM_HIP(hipMemcpy(pi.data(), c->d_match_i, pi.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      SFM_HIP(hipMemcpy(pk.data(), c->d_match_key, pk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      SFM_RC(c->d_match_i.read(pi.data(), pi.size(), cs));
+      SFM_RC(c->d_match_key.read(pk.data(), pk.size(), cs));
     }
     for (uint32_t v = 0; v < m->n_views; ++v) {
       const uint32_t off = m->h_view_off[v];
@@ -1380,19 +1399,19 @@ int sfmloc_match_set_read(sfmloc_map *map, uint32_t *n, uint32_t *qfeat, uint32_
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
   uint32_t k = 0;
-  SFM_HIP(hipMemcpy(&k, c->d_ms_n, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SFM_RC(c->d_ms_n.read(&k, 1, cs));
   *n = k;
   int st = 0;
-  SFM_HIP(hipMemcpy(&st, c->d_status, sizeof(int), hipMemcpyDeviceToHost));
+  SFM_RC(dev_read(&st, c->d_status, 1, cs));
   SFM_CHECK((st & 2) == 0, SFMLOC_ECAP, "more than %u 2D-3D candidates (match-set workspace)", c->cand_cap);
   if (k == 0) return SFMLOC_OK;
   SFM_CHECK(cap >= k, SFMLOC_ECAP, "sfmloc_match_set_read: cap %u < %u", cap, k);
-  if (qfeat) SFM_HIP(hipMemcpy(qfeat, c->d_ms_qfeat, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (landmark_id) SFM_HIP(hipMemcpy(landmark_id, c->d_ms_landmark, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (pt2d) SFM_HIP(hipMemcpy(pt2d, c->d_pt2d, (size_t)k * 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (pt3d) SFM_HIP(hipMemcpy(pt3d, c->d_pt3d, (size_t)k * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (qfeat) SFM_RC(c->d_ms_qfeat.read(qfeat, k, cs));
+  if (landmark_id) SFM_RC(c->d_ms_landmark.read(landmark_id, k, cs));
+  if (pt2d) SFM_RC(c->d_pt2d.read(pt2d, (size_t)k * 2, cs));
+  if (pt3d) SFM_RC(c->d_pt3d.read(pt3d, (size_t)k * 3, cs));
   return SFMLOC_OK;
 }
 
@@ -1424,17 +1443,17 @@ int sfmloc_pose_read(sfmloc_map *map, sfmloc_pose *out, uint32_t *pair_qfeat, ui
   Map *m = reinterpret_cast<Map *>(map);
   Ctx *c = m->ctx0;
   SFM_HIP(hipSetDevice(m->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
-  SFM_HIP(hipMemcpy(out, c->d_pose, sizeof(Pose), hipMemcpyDeviceToHost));
+  const hipStream_t cs = c->stream;
+  SFM_RC(dev_read(out, c->d_pose, 1, cs));
   SFM_CHECK((out->status & 4) == 0, SFMLOC_ECAP, "more than %u 2D-3D correspondences (P3P workspace)", c->p3p_cap);
   if (out->ok && out->n_inliers > 0) {
     const uint32_t k = (uint32_t)out->n_inliers;
     if (pair_qfeat || pair_landmark || inlier_idx)
       SFM_CHECK(cap >= k, SFMLOC_ECAP, "sfmloc_pose_read: cap %u < %u inliers", cap, k);
-    if (pair_qfeat) SFM_HIP(hipMemcpy(pair_qfeat, c->d_pair_qfeat, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (pair_qfeat) SFM_RC(dev_read(pair_qfeat, c->d_pair_qfeat, k, cs));
     if (pair_landmark)
-      SFM_HIP(hipMemcpy(pair_landmark, c->d_pair_landmark, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (inlier_idx) SFM_HIP(hipMemcpy(inlier_idx, c->d_inlier_idx, k * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      SFM_RC(dev_read(pair_landmark, c->d_pair_landmark, k, cs));
+    if (inlier_idx) SFM_RC(c->d_inlier_idx.read(inlier_idx, k, cs));
   }
   return SFMLOC_OK;
 }
@@ -1476,10 +1495,10 @@ int sfmloc_localize_bow_begin(sfmloc_context *ctx, sfmloc_query *query, const fl
       SFM_CHECK(i == 0 || cand_views[i - 1] < cand_views[i], SFMLOC_EINVAL,
                 "sfmloc_localize_bow_begin: candidate views must be strictly ascending");
     }
-    SFM_HIP(hipMemcpyAsync(c->d_bow_cand, cand_views, n_cand * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SFM_RC(c->d_bow_cand.upload(cand_views, n_cand, c->stream));
   }
   if (query_bow)
-    SFM_HIP(hipMemcpyAsync(c->d_bow_query, query_bow, m->bow_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SFM_RC(c->d_bow_query.upload(query_bow, m->bow_dim, c->stream));
   int rc;
   {
     EventScope ev(c, SFMLOC_K_BOW);
@@ -1544,7 +1563,7 @@ int sfmloc_shard_bow_keys(sfmloc_context *ctx, sfmloc_query *query, const float 
   SFM_HIP(hipSetDevice(m->device));
   ctx_mark_busy(c);
   if (query_bow)
-    SFM_HIP(hipMemcpyAsync(c->d_bow_query, query_bow, m->bow_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    SFM_RC(c->d_bow_query.upload(query_bow, m->bow_dim, c->stream));
   EventScope ev(c, SFMLOC_K_BOW);
   return launch_bow_keys(c, query_bow ? c->d_bow_query : q->d_bow, knn, c->d_bow_dist, c->d_bow_cand,
                          reinterpret_cast<unsigned long long *>(keys_dev));
@@ -1808,9 +1827,9 @@ int sfmloc_bow_select(sfmloc_map *map, const float *query_bow, const uint32_t *c
       SFM_CHECK(i == 0 || cand_views[i - 1] < cand_views[i], SFMLOC_EINVAL,
                 "sfmloc_bow_select: candidate views must be strictly ascending");
     }
-    SFM_HIP(hipMemcpyAsync(c->d_bow_cand, cand_views, n_cand * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SFM_RC(c->d_bow_cand.upload(cand_views, n_cand, c->stream));
   }
-  SFM_HIP(hipMemcpyAsync(c->d_bow_query, query_bow, m->bow_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  SFM_RC(c->d_bow_query.upload(query_bow, m->bow_dim, c->stream));
   int rc;
   {
     EventScope ev(c, SFMLOC_K_BOW);
@@ -1818,7 +1837,7 @@ int sfmloc_bow_select(sfmloc_map *map, const float *query_bow, const uint32_t *c
                            c->d_bow_dist, c->d_bow_sel);
   }
   if (rc) return rc;
-  SFM_HIP(hipMemcpyAsync(out_sel, c->d_bow_sel, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  SFM_RC(c->d_bow_sel.download(out_sel, k, c->stream));
   SFM_HIP(hipStreamSynchronize(c->stream));
   *n_out = k;
   return SFMLOC_OK;
@@ -1831,7 +1850,7 @@ int sfmloc_bow_distances(sfmloc_map *map, const float *query_bow, float *out_dis
   SFM_CHECK(m->bow_dim > 0 && m->d_bow, SFMLOC_EINVAL, "sfmloc_bow_distances: the map has no .bow vectors");
   SFM_HIP(hipSetDevice(m->device));
   if (m->n_views == 0) return SFMLOC_OK;
-  SFM_HIP(hipMemcpyAsync(c->d_bow_query, query_bow, m->bow_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  SFM_RC(c->d_bow_query.upload(query_bow, m->bow_dim, c->stream));
   int rc;
   {
     EventScope ev(c, SFMLOC_K_BOW);
@@ -1839,7 +1858,7 @@ int sfmloc_bow_distances(sfmloc_map *map, const float *query_bow, float *out_dis
   }
   if (rc) return rc;
   // the kernel stores the float32 distance's bit pattern (non-negative floats order like their bits)
-  SFM_HIP(hipMemcpyAsync(out_dist, c->d_bow_dist, (size_t)m->n_views * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  SFM_RC(c->d_bow_dist.download(out_dist, m->n_views, c->stream));
   SFM_HIP(hipStreamSynchronize(c->stream));
   return SFMLOC_OK;
 }
@@ -1869,7 +1888,7 @@ int sfmloc_bof_create(const sfmloc_bof_desc *d, int device, sfmloc_bof **out) {
     for (int l = 0; l < b->levels; ++l) b->cells += (l == 0) ? 1 : (l == 2 ? 3 : (l + 1) * (l + 1));
     // (the model's own stream is created by the first sfmloc_bof_compute: a model inside a sfmloc_imgbow works on that
     // object's stream and needs none -- an idle stream still shares a hardware queue with streams that work; the uploads
-    // here go through the null stream)
+    // here name no stream, so each has completed when it returns: devmem.h "Transfers")
     SFM_RC(dev_upload(nullptr, b->d_centers, d->centers, (size_t)d->K * b->cdim, nullptr));
     if (d->n_pca > 0) {
       SFM_RC(dev_upload(nullptr, b->d_pca_mean, d->pca_mean, (size_t)d->in_dim, nullptr));
@@ -1877,9 +1896,7 @@ int sfmloc_bof_create(const sfmloc_bof_desc *d, int device, sfmloc_bof **out) {
       SFM_RC(dev_upload(nullptr, b->d_pca_eval, d->pca_eigval, (size_t)d->n_pca, nullptr));
     }
     SFM_RC(b->d_counts.alloc(nullptr, (size_t)b->K * b->cells));
-    SFM_RC(b->d_out.alloc(nullptr, (size_t)b->K * b->cells));
-    SFM_HIP(hipStreamSynchronize(nullptr));
-    return SFMLOC_OK;
+    return b->d_out.alloc(nullptr, (size_t)b->K * b->cells);
   });
 }
 
@@ -1909,12 +1926,12 @@ int sfmloc_bof_compute(sfmloc_bof *bof, const float *desc, const float *kpt_xy, 
   }
   SFM_RC(b->stream.ensure());
   if (n) {
-    SFM_HIP(hipMemcpyAsync(b->d_desc, desc, (size_t)n * b->in_dim * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    SFM_HIP(hipMemcpyAsync(b->d_kxy, kpt_xy, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    SFM_RC(b->d_desc.upload(desc, (size_t)n * b->in_dim, b->stream));
+    SFM_RC(b->d_kxy.upload(kpt_xy, (size_t)n * 2, b->stream));
   }
   int rc = launch_bof(b, b->stream, b->d_desc, b->d_kxy, (int)n, b->d_counts, b->d_out, nullptr);  // (stream: created above)
   if (rc) return rc;
-  SFM_HIP(hipMemcpyAsync(out_bow, b->d_out, (size_t)b->K * b->cells * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  SFM_RC(b->d_out.download(out_bow, (size_t)b->K * b->cells, b->stream));
   SFM_HIP(hipStreamSynchronize(b->stream));
   return SFMLOC_OK;
 }
@@ -2006,12 +2023,13 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
   if (rc) return rc;
   std::vector<uint32_t> iota(n);
   for (uint32_t i = 0; i < n; ++i) iota[i] = i;
-  SFM_HIP(hipStreamSynchronize(c->stream));
-  SFM_HIP(hipMemcpy(c->d_pt2d, pt2d, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice));
-  SFM_HIP(hipMemcpy(c->d_pt3d, pt3d, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice));
-  SFM_HIP(hipMemcpy(c->d_ms_qfeat, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SFM_HIP(hipMemcpy(c->d_ms_landmark, iota.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SFM_HIP(hipMemcpy(c->d_ms_n, &n, sizeof(uint32_t), hipMemcpyHostToDevice));
+  const hipStream_t cs = c->stream;
+  SFM_RC(c->d_pt2d.upload(pt2d, (size_t)n * 2, cs));
+  SFM_RC(c->d_pt3d.upload(pt3d, (size_t)n * 3, cs));
+  SFM_RC(c->d_ms_qfeat.upload(iota.data(), n, cs));
+  SFM_RC(c->d_ms_landmark.upload(iota.data(), n, cs));
+  SFM_RC(c->d_ms_n.upload(&n, 1, cs));
+  SFM_HIP(hipStreamSynchronize(cs));  // (the caller's arrays, iota and n are pageable host memory)
   ctx_set_uncalibrated_camera(c, width, height);
   c->p3p_init_fused = false;  // K5's init reads the count written above
   rc = ctx_resection_begin(c);
@@ -2023,7 +2041,7 @@ int sfmloc_debug_resect6(sfmloc_map *map, const double *pt2d, const double *pt3d
   SFM_CHECK((out->status & 4) == 0, SFMLOC_ECAP, "more than %u 2D-3D correspondences (P3P workspace)", c->p3p_cap);
   if (inlier_idx && out->ok && out->n_inliers > 0) {
     SFM_CHECK(cap >= (uint32_t)out->n_inliers, SFMLOC_ECAP, "sfmloc_debug_resect6: cap %u < %d inliers", cap, out->n_inliers);
-    SFM_HIP(hipMemcpy(inlier_idx, c->d_inlier_idx, (size_t)out->n_inliers * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_inlier_idx.read(inlier_idx, out->n_inliers, cs));
   }
   return SFMLOC_OK;
 }
@@ -2036,13 +2054,14 @@ int sfmloc_debug_context_views(sfmloc_context *ctx, uint32_t *views, uint32_t ca
   Ctx *c = reinterpret_cast<Ctx *>(ctx);
   SFM_CHECK(!c->stream.gang, SFMLOC_EINVAL, "sfmloc_debug_context_views: the context is recording a gang session");
   SFM_HIP(hipSetDevice(c->map->device));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t cs = c->stream;
+  SFM_HIP(hipStreamSynchronize(cs));
   *n = c->last_n_sel;
   SFM_CHECK(cap >= c->last_n_sel, SFMLOC_ECAP, "sfmloc_debug_context_views: cap %u < %u views", cap, c->last_n_sel);
   if (c->last_all_views) {  // (no list on the device: every view, in order)
     for (uint32_t v = 0; v < c->last_n_sel; ++v) views[v] = v;
   } else if (c->last_n_sel) {
-    SFM_HIP(hipMemcpy(views, c->d_view_sel, (size_t)c->last_n_sel * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_view_sel.read(views, c->last_n_sel, cs));
   }
   return SFMLOC_OK;
 }
@@ -2057,16 +2076,10 @@ int sfmloc_debug_math(int device, int op, const double *in, int n, int in_stride
   int rc = d_in.alloc(nullptr, (size_t)n * in_stride);
   if (!rc) rc = d_out.alloc(nullptr, (size_t)n * out_stride);
   if (rc) return rc;
-  e = hipMemcpy(d_in, in, (size_t)n * in_stride * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_out, 0, (size_t)n * out_stride * sizeof(double));
-  if (e == hipSuccess) rc = launch_debug_math(op, d_in, n, in_stride, d_out, out_stride, nullptr);
-  if (e == hipSuccess && rc == SFMLOC_OK) e = hipDeviceSynchronize();
-  if (e == hipSuccess && rc == SFMLOC_OK)
-    e = hipMemcpy(out, d_out, (size_t)n * out_stride * sizeof(double), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("sfmloc_debug_math: %s", hipGetErrorString(e));
-    return SFMLOC_EHIP;
-  }
+  rc = d_in.upload(in, (size_t)n * in_stride, nullptr);  // (a one-shot call without a stream: all of it on the null stream)
+  if (!rc) rc = d_out.zero(nullptr);
+  if (!rc) rc = launch_debug_math(op, d_in, n, in_stride, d_out, out_stride, nullptr);
+  if (!rc) rc = d_out.read(out, (size_t)n * out_stride, nullptr);
   return rc;
 }
 
@@ -2087,7 +2100,8 @@ int sfmloc_stats_read(sfmloc_map *map, sfmloc_kernel_stats *out) {
   std::vector<Ctx *> all = m->pool;
   all.push_back(m->ctx0);
   for (Ctx *c : all) {
-    SFM_HIP(hipStreamSynchronize(c->stream));
+    const hipStream_t cs = c->stream;
+    SFM_HIP(hipStreamSynchronize(cs));
     int rc = drain_events(c);
     if (rc) return rc;
     for (int k = 0; k < SFMLOC_K_COUNT; ++k) {
@@ -2097,7 +2111,7 @@ int sfmloc_stats_read(sfmloc_map *map, sfmloc_kernel_stats *out) {
     out->hamming_pairs += c->stats.hamming_pairs;
     out->hamming_alg_bytes += c->stats.hamming_alg_bytes;
     unsigned long long k1s[kSelPairsSlot + 1], k1c[2] = {0, 0};
-    SFM_HIP(hipMemcpy(k1s, c->d_k1_counters, sizeof(k1s), hipMemcpyDeviceToHost));
+    SFM_RC(c->d_k1_counters.read(k1s, kSelPairsSlot + 1, cs));
     for (int q = 0; q < kK1CounterSlots; ++q) {
       k1c[0] += k1s[2 * q];
       k1c[1] += k1s[2 * q + 1];
@@ -2124,11 +2138,12 @@ int sfmloc_stats_reset(sfmloc_map *map) {
   std::vector<Ctx *> all = m->pool;
   all.push_back(m->ctx0);
   for (Ctx *c : all) {
-    SFM_HIP(hipStreamSynchronize(c->stream));
+    const hipStream_t cs = c->stream;
+    SFM_HIP(hipStreamSynchronize(cs));
     int rc = drain_events(c);
     if (rc) return rc;
     memset(&c->stats, 0, sizeof(c->stats));
-    SFM_HIP(hipMemset(c->d_k1_counters, 0, (kSelPairsSlot + 1) * sizeof(unsigned long long)));
+    SFM_RC(c->d_k1_counters.zero(cs));  // (on the context's stream: a scan queued next is ordered behind the clear)
   }
   return SFMLOC_OK;
 }

@@ -135,8 +135,8 @@ int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *
       (rc = d_st.alloc(nullptr, 1)))
     return rc;
   if ((rc = d.open(true, &g_color_last_ms, h.s))) return rc;
-  SFM_HIP(hipMemsetAsync(d_st, 0, sizeof(ColorState), d.s));
-  SFM_HIP(hipMemsetAsync(d_order, 0, (size_t)V.n_views * sizeof(uint32_t), d.s));
+  SFM_RC(d_st.zero(d.s));
+  SFM_RC(d_order.zero(V.n_views, d.s));
   if ((rc = d.time_begin())) return rc;
   const uint32_t n_init = V.n_views > V.n_lm ? V.n_views : V.n_lm;
   hipLaunchKernelGGL(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.view_off, d_card, V.n_lm,
@@ -146,7 +146,7 @@ int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *
   blocks = blocks < 1 ? 1 : (blocks > kUpdateMaxBlocks ? kUpdateMaxBlocks : blocks);
   ColorState st;
   for (;;) {
-    SFM_HIP(hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, d.s));
+    SFM_RC(d_st.download(&st, 1, d.s));
     SFM_HIP(hipStreamSynchronize(d.s));
     if (st.remaining == 0) break;
     for (uint32_t i = 0; i < SFMLOC_COLOR_CHUNK; ++i) {
@@ -157,10 +157,10 @@ int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *
     SFM_HIP(hipGetLastError());
   }
   if ((rc = d.time_end())) return rc;
-  SFM_HIP(hipMemcpyAsync(order, d_order, (size_t)st.n_order * sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
+  SFM_RC(d_order.download(order, st.n_order, d.s));
   if (V.n_lm) {
-    SFM_HIP(hipMemcpyAsync(lm_iter, d_iter, (size_t)V.n_lm * sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
-    SFM_HIP(hipMemcpyAsync(lm_obs, d_obs, (size_t)V.n_lm * sizeof(uint64_t), hipMemcpyDeviceToHost, d.s));
+    SFM_RC(d_iter.download(lm_iter, V.n_lm, d.s));
+    SFM_RC(d_obs.download(lm_obs, V.n_lm, d.s));
   }
   SFM_HIP(hipStreamSynchronize(d.s));
   *n_order = st.n_order;

@@ -1,12 +1,16 @@
 // Ownership of device memory, for every handle and call of the library: one owner per array, so that freeing and the
 // memory figures (sfmloc_map_info::hbm_bytes: Map and Ctx charge an account, nothing else does) need no list kept in
 // step by hand.  No HIP here: raw allocation goes through two functions that capi.hip defines over hipMalloc / hipFree
-// (and tests/cpp/devmem.cpp over malloc).  Below the device arrays: the owners of streams, events and pinned host memory.
+// (and tests/cpp/devmem.cpp over malloc), and every transfer through two more ("Transfers" below states their rules).
+// Below the device arrays: the owners of streams, events and pinned host memory.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "../../include/sfmloc.h"
 #include <memory>
+#include <type_traits>
 #include <utility>
 
 struct ihipStream_t;  // what hipStream_t and hipEvent_t point to: opaque here as they are in HIP's own headers
@@ -16,6 +20,59 @@ namespace sfmloc {
 
 int dev_raw_alloc(void **p, size_t bytes);  // SFMLOC_OK, or an error code with the error text set; *p null on failure
 void dev_raw_free(void *p);
+void set_error(const char *fmt, ...);  // (capi.hip: the calling thread's error text)
+
+// ---------------------------------------------------------------------------
+// Transfers: every copy into, out of or between device arrays, and every clear, goes through the two raw functions
+// below (capi.hip: hipMemcpyAsync / hipMemsetAsync, the only places that name them) and names its stream.
+//   - A stream: asynchronous on that stream, ordered with the rest of its work.
+//   - A NULL stream: the operation HAS COMPLETED when the call returns (the raw function issues it on the null stream
+//     and waits for that stream).  For an object that has no stream yet and must not create one just to fill its
+//     tables; nothing else may rely on the null stream, which no non-blocking stream is ordered with.
+// Counts are elements of the device array's type, so no site restates a sizeof; zero elements: no raw call, no error.
+// A host pointer is void, or its elements make up the device array's (float for float2), or the device array is bytes.
+// The members of an owned DevBuf refuse a span outside the array (SFMLOC_EINVAL, nothing issued); a pointer into a
+// record or a borrowed array has no size to check.
+// ---------------------------------------------------------------------------
+enum class CopyKind { kHostToDevice, kDeviceToHost, kDeviceToDevice };
+int dev_raw_copy(void *dst, const void *src, size_t bytes, CopyKind kind, ihipStream_t *s);  // codes as dev_raw_alloc
+int dev_raw_fill(void *dst, int byte, size_t bytes, ihipStream_t *s);
+void stream_raw_sync(void *s);  // (one of the owners' raw functions, below: waits for everything queued on s)
+
+template <class T, class H>
+constexpr bool host_type_fits() {
+  if constexpr (std::is_void_v<H>) return true;
+  else return sizeof(T) % sizeof(H) == 0 || sizeof(T) == 1;
+}
+template <class T>
+inline int dev_fill(T *d, int byte, size_t n, ihipStream_t *s) {
+  return n ? dev_raw_fill(d, byte, n * sizeof(T), s) : 0;
+}
+template <class T>
+inline int dev_zero(T *d, size_t n, ihipStream_t *s) {
+  return dev_fill(d, 0, n, s);
+}
+template <class T, class H>
+inline int dev_upload(T *d, const H *h, size_t n, ihipStream_t *s) {
+  static_assert(host_type_fits<T, H>(), "host elements that make up the device array's");
+  return n ? dev_raw_copy(d, h, n * sizeof(T), CopyKind::kHostToDevice, s) : 0;
+}
+template <class T, class H>
+inline int dev_download(H *h, const T *d, size_t n, ihipStream_t *s) {
+  static_assert(host_type_fits<T, H>(), "host elements that make up the device array's");
+  return n ? dev_raw_copy(h, d, n * sizeof(T), CopyKind::kDeviceToHost, s) : 0;
+}
+template <class T>
+inline int dev_copy(T *d, const T *src, size_t n, ihipStream_t *s) {
+  return n ? dev_raw_copy(d, src, n * sizeof(T), CopyKind::kDeviceToDevice, s) : 0;
+}
+// the blocking read: downloaded on s, and s waited for -- the host may read h when this returns SFMLOC_OK
+template <class T, class H>
+inline int dev_read(H *h, const T *d, size_t n, ihipStream_t *s) {
+  const int rc = dev_download(h, d, n, s);
+  if (!rc && n) stream_raw_sync(s);
+  return rc;
+}
 
 // One device array, untyped: owned (freed here, its bytes charged to an account while held) or borrowed (never freed,
 // never charged).  Move-only, and its address cannot be taken: an array gets in through alloc / borrow only, never
@@ -67,6 +124,13 @@ class DevMem {
   size_t bytes() const { return bytes_; }
 
  protected:
+  // elements off .. off + n of an owned array of `elem`-byte elements lie inside it (a borrowed one is not checked)
+  int span_inside(size_t elem, size_t off, size_t n) const {
+    const size_t size = bytes_ / elem;
+    if (!bytes_ || (off <= size && n <= size - off)) return 0;
+    set_error("transfer of %zu elements from element %zu of a device array of %zu", n, off, size);
+    return SFMLOC_EINVAL;
+  }
   void *p_ = nullptr;
 
  private:
@@ -88,6 +152,35 @@ class DevBuf : public DevMem {
   void borrow(const void *p) { borrow_raw(const_cast<void *>(p)); }  // the caller's array: never freed here
   T *get() const { return static_cast<T *>(p_); }
   operator T *() const { return get(); }
+
+  // transfers (rules: above) of n elements from element `off` on; without a count: the whole owned array
+  size_t size() const { return bytes() / sizeof(T); }
+  int fill(int byte, size_t n, ihipStream_t *s, size_t off = 0) {
+    const int rc = span_inside(sizeof(T), off, n);
+    return rc ? rc : dev_fill(get() + off, byte, n, s);
+  }
+  int fill(int byte, ihipStream_t *s) { return fill(byte, size(), s); }
+  int zero(size_t n, ihipStream_t *s, size_t off = 0) { return fill(0, n, s, off); }
+  int zero(ihipStream_t *s) { return fill(0, size(), s); }
+  template <class H>
+  int upload(const H *h, size_t n, ihipStream_t *s, size_t off = 0) {
+    const int rc = span_inside(sizeof(T), off, n);
+    return rc ? rc : dev_upload(get() + off, h, n, s);
+  }
+  template <class H>
+  int download(H *h, size_t n, ihipStream_t *s, size_t off = 0) const {
+    const int rc = span_inside(sizeof(T), off, n);
+    return rc ? rc : dev_download(h, get() + off, n, s);
+  }
+  int copy_from(const T *src, size_t n, ihipStream_t *s, size_t off = 0) {
+    const int rc = span_inside(sizeof(T), off, n);
+    return rc ? rc : dev_copy(get() + off, src, n, s);
+  }
+  template <class H>
+  int read(H *h, size_t n, ihipStream_t *s, size_t off = 0) const {  // the blocking read
+    const int rc = span_inside(sizeof(T), off, n);
+    return rc ? rc : dev_read(h, get() + off, n, s);
+  }
 };
 
 // All or nothing: the arrays of a set are allocated into the group and reach their owners (whose previous arrays are
@@ -136,8 +229,7 @@ class DevGroup {
 // freed first -- kernels on the stream may still run then, which is safe because freeing waits for the device -- and
 // the stream is drained and destroyed after them.
 // ---------------------------------------------------------------------------
-int stream_raw_create(void **s);  // a non-blocking stream; codes and *s as dev_raw_alloc
-void stream_raw_sync(void *s);
+int stream_raw_create(void **s);  // a non-blocking stream; codes and *s as dev_raw_alloc (stream_raw_sync: above)
 void stream_raw_destroy(void *s);
 int event_raw_create(void **e, bool timing);
 void event_raw_destroy(void *e);

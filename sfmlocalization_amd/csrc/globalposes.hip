@@ -897,7 +897,7 @@ __global__ __launch_bounds__(256) void k_gp_commit(GpDev D, int kind) {
 
 int gp_read_state(const GpDev &D, GpState *h, hipStream_t s) {
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(h, D.st, sizeof(GpState), hipMemcpyDeviceToHost, s));
+  SFM_RC(dev_download(h, D.st, 1, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
@@ -981,17 +981,17 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
     GP_LAUNCH(k_gp_sc_cc, gw > gn ? gw : gn, (const uint32_t *)d_kl, (const uint8_t *)d_on, (uint32_t)W, (uint32_t)P, d_ea.get(),
               d_eb.get(), d_parent.get());
     for (;;) {
-      SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+      SFM_RC(d_flag.zero(1, s));
       GP_LAUNCH(k_graph_hook, gw, (const uint32_t *)d_ea, (const uint32_t *)d_eb, (uint32_t)W, d_parent.get(), d_flag.get());
       GP_LAUNCH(k_graph_jump, gn, d_parent.get(), (uint32_t)P);
       SFM_HIP(hipGetLastError());
       uint32_t changed = 0;
-      SFM_HIP(hipMemcpyAsync(&changed, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      SFM_RC(d_flag.download(&changed, 1, s));
       SFM_HIP(hipStreamSynchronize(s));
       if (!changed) break;
     }
     std::vector<uint32_t> label(P);
-    SFM_HIP(hipMemcpyAsync(label.data(), d_parent, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_RC(d_parent.download(label.data(), P, s));
     SFM_HIP(hipStreamSynchronize(s));
     gposes_host::pick_component(label, &first, &size);
     etr->assign(P, 0);
@@ -1050,9 +1050,9 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
                             std::addressof(d_p), std::addressof(d_q), std::addressof(d_xs), std::addressof(d_xn)})
     SFM_RC(b->alloc(nullptr, P));
   SFM_RC(d_part.alloc(nullptr, 3 * (size_t)S.n_part));
-  SFM_HIP(hipMemsetAsync(d_xs, 0, P * sizeof(double), s));
-  SFM_HIP(hipMemsetAsync(d_xn, 0, P * sizeof(double), s));
-  SFM_HIP(hipMemsetAsync(d_mterm, 0, W * sizeof(double), s));
+  SFM_RC(d_xs.zero(P, s));
+  SFM_RC(d_xn.zero(P, s));
+  SFM_RC(d_mterm.zero(W, s));
   S.adj_off = d_off, S.adj_nbr = d_nbr, S.adj_pe = d_pe, S.heavy = d_heavy, S.pairs = d_kl, S.inc = d_sinc, S.erot = d_on;
   S.C = d_xs, S.Cn = d_xn, S.ev = d_ev, S.ew = d_ew, S.rho = d_rho, S.res = d_res, S.mterm = d_mterm, S.diag = d_diag;
   S.x = d_x, S.r = d_r, S.z = d_z, S.p = d_p, S.q = d_q, S.part = d_part, S.st = D.st;
@@ -1062,7 +1062,7 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   o.max_steps = sc.opt.max_steps;
   o.max_pcg = sc.opt.max_pcg;
   GpState h = gp_state0(o);
-  SFM_HIP(hipMemcpyAsync(S.st, &h, sizeof h, hipMemcpyHostToDevice, s));
+  SFM_RC(dev_upload(S.st, &h, 1, s));
   SFM_HIP(hipStreamSynchronize(s));  // (h is reused below)
   const uint32_t ge = (uint32_t)((W + 255) / 256), gv = S.nb_view, ga = S.n_part;
   const double delta = sc.opt.scale_delta;
@@ -1081,8 +1081,8 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);  // the weights at the result
   std::vector<double> x(P), ew(W);
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(x.data(), d_xs, P * sizeof(double), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(ew.data(), d_ew, W * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_xs.download(x.data(), P, s));
+  SFM_RC(d_ew.download(ew.data(), W, s));
   SFM_HIP(hipStreamSynchronize(s));
   std::vector<double> bx;
   for (size_t k = 0; k < P; ++k)
@@ -1099,8 +1099,8 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   sr.launches = *launches - launches0;
   // "centres": what the translation kernels read
   SFM_RC(dev_upload(nullptr, d_base, g->base.data(), P, s));
-  SFM_HIP(hipMemcpyAsync(d_inc, g->in_comp.data(), n, hipMemcpyHostToDevice, s));
-  SFM_HIP(hipMemcpyAsync(D.etr, etr->data(), P, hipMemcpyHostToDevice, s));
+  SFM_RC(dev_upload(d_inc, g->in_comp.data(), n, s));
+  SFM_RC(dev_upload(D.etr, etr->data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   D.base = d_base;
   D.root = root;
@@ -1168,19 +1168,19 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   GP_LAUNCH(k_gp_cc_edges, gboth, D, d_ea.get(), d_eb.get(), d_parent.get());
   SFM_HIP(hipGetLastError());
   for (;;) {
-    SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    SFM_RC(d_flag.zero(1, s));
     GP_LAUNCH(k_graph_hook, gp, (const uint32_t *)d_ea, (const uint32_t *)d_eb, n_pairs, d_parent.get(), d_flag.get());
     GP_LAUNCH(k_graph_jump, gv, d_parent.get(), n_views);
     SFM_HIP(hipGetLastError());
     uint32_t changed = 0;
-    SFM_HIP(hipMemcpyAsync(&changed, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_RC(d_flag.download(&changed, 1, s));
     SFM_HIP(hipStreamSynchronize(s));
     if (!changed) break;
   }
   std::vector<uint32_t> label(n), ntri(P), nok(P);
-  SFM_HIP(hipMemcpyAsync(label.data(), d_parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(ntri.data(), d_ntri, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(nok.data(), d_nok, P * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_parent.download(label.data(), n, s));
+  SFM_RC(d_ntri.download(ntri.data(), P, s));
+  SFM_RC(d_nok.download(nok.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   uint32_t root = 0, size = 0;
   gposes_host::pick_component(label, &root, &size);
@@ -1208,7 +1208,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   }
   D.root = root;
   SFM_RC(ev.mark(1, s));
-  SFM_HIP(hipMemcpyAsync(d_inc, g->in_comp.data(), n, hipMemcpyHostToDevice, s));
+  SFM_RC(d_inc.upload(g->in_comp.data(), n, s));
   GP_LAUNCH(k_gp_flags, gp, D);
 
   DevBuf<double> d_R, d_Rn, d_C, d_Cn, d_dir, d_ev, d_W, d_ew, d_rho, d_res, d_mterm, d_diag, d_Minv, d_x, d_r, d_z, d_p,
@@ -1234,14 +1234,14 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   SFM_RC(d_q.alloc(nullptr, 9 * n));
   SFM_RC(d_part.alloc(nullptr, 3 * (size_t)D.n_part));
   SFM_RC(d_st.alloc(nullptr, 1));
-  SFM_HIP(hipMemsetAsync(d_mterm, 0, P * sizeof(double), s));
+  SFM_RC(d_mterm.zero(P, s));
   D.R = d_R, D.Rn = d_Rn, D.C = d_C, D.Cn = d_Cn, D.dir = d_dir, D.ev = d_ev, D.W = d_W, D.ew = d_ew, D.rho = d_rho;
   D.res = d_res, D.mterm = d_mterm, D.diag = d_diag, D.Minv = d_Minv, D.x = d_x, D.r = d_r, D.z = d_z, D.p = d_p, D.q = d_q;
   D.part = d_part, D.st = d_st;
   GpState h = gp_state0(opt), h0 = h;
 
   // sfmloc.h "chordal"
-  SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
+  SFM_RC(d_st.upload(&h0, 1, s));
   GP_LAUNCH(k_gp_setup<0>, ga, D);
   GP_LAUNCH(k_gp_begin, 1, D, 0);
   SFM_RC(gp_pcg<0>(D, opt.max_pcg, s, launches, &h));
@@ -1252,7 +1252,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
 
   // sfmloc.h "IRLS"
   const double rdelta = opt.rotation_delta > 0.0 ? opt.rotation_delta : tan(opt.triplet_angle_deg * (M_PI / 180.0) / 6.0);
-  SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
+  SFM_RC(d_st.upload(&h0, 1, s));
   h = h0;
   while (h.running) {
     GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);
@@ -1269,7 +1269,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   }
   GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);  // the residuals at the result
   std::vector<double> res(P);
-  SFM_HIP(hipMemcpyAsync(res.data(), d_res, P * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_res.download(res.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   for (size_t k = 0; k < P; ++k) g->pairs[k].rot_residual = res[k];
   rep.rot_steps_tried = h.steps_tried;
@@ -1290,7 +1290,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
     SFM_RC(ev.mark(4, s));
   }
   GP_LAUNCH(k_gp_dirs, gp, D);
-  SFM_HIP(hipMemcpyAsync(d_st, &h0, sizeof h0, hipMemcpyHostToDevice, s));
+  SFM_RC(d_st.upload(&h0, 1, s));
   h = h0;
   while (h.running) {
     GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
@@ -1306,9 +1306,9 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   }
   GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(res.data(), d_res, P * sizeof(double), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(g->R.data(), d_R, 9 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(g->C.data(), d_C, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_res.download(res.data(), P, s));
+  SFM_RC(d_R.download(g->R.data(), 9 * n, s));
+  SFM_RC(d_C.download(g->C.data(), 3 * n, s));
   SFM_RC(ev.mark(3, s));
   SFM_HIP(hipStreamSynchronize(s));
   SFM_RC(ev.between(0, &rep.graph_ms));

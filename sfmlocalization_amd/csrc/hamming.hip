@@ -330,7 +330,7 @@ static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, cons
   constexpr int WAVES = kScreenWaves, NW = kScreenNW;
   const uint32_t lds_rows = 512;
   const size_t lds_bytes = (size_t)lds_rows * 64;
-  if (!pass.cleared) SFM_HIP(hipMemsetAsync(c->d_n_flagged, 0, sizeof(uint32_t), c->stream));
+  if (!pass.cleared) SFM_RC(c->d_n_flagged.zero(1, c->stream));
   const uint2 *head_part = nullptr;
   if (P.shared_head) {
     int rc = launch_hamming_t<1, 8>(c, q, n_work_blocks, use_list, 1, 512, P.head);
@@ -338,7 +338,7 @@ static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, cons
     head_part = c->d_part;
   }
   if (P.clear_flagmask && !pass.flagmask_zeroed)
-    SFM_HIP(hipMemsetAsync(c->d_flagmask, 0, (size_t)n_work_blocks * sizeof(unsigned long long), c->stream));
+    SFM_RC(c->d_flagmask.zero(n_work_blocks, c->stream));
   pass.flagmask_zeroed = false;  // (this scan writes it)
   auto screen = [&](auto body, auto kern, size_t lds) {
     sfm_launch<decltype(body)>(c, kern, dim3((n_work_blocks + WAVES - 1) / WAVES, P.slices), dim3(WAVES * 64), (uint32_t)lds,

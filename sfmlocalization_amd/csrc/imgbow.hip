@@ -118,8 +118,7 @@ int sfmloc_imgbow_create(const sfmloc_bof_desc *model, int device, uint32_t widt
     SFM_RC(ib->d_out_f32.alloc(nullptr, dim));
     SFM_RC(dev_upload(nullptr, ib->d_grid, grid.data(), grid.size(), nullptr));
     SFM_RC(dev_upload(nullptr, ib->d_kxy, kxy.data(), kxy.size(), nullptr));
-    // (the two uploads are waited for at once; if the second fails, grid outlives the handle's frees, which wait)
-    SFM_HIP(hipStreamSynchronize(nullptr));
+    // (no stream is named: each upload has completed when it returns, so grid and kxy may go -- devmem.h "Transfers")
     SFM_RC(ib->h_src.alloc(n_src));
     SFM_RC(ib->h_out.alloc(dim));
     return ib->staged.create(kOrderingEvent);
@@ -180,7 +179,7 @@ int sfmloc_imgbow_compute(sfmloc_imgbow *p, const uint8_t *image, sfmloc_query *
   if (ib->staged_pending) SFM_HIP(hipEventSynchronize(ib->staged));
   memcpy(ib->h_src, image, n_src);
   hipStream_t s = akaze_stream_now(a);
-  SFM_HIP(hipMemcpyAsync(ib->d_src, ib->h_src, n_src, hipMemcpyHostToDevice, s));
+  SFM_RC(ib->d_src.upload(ib->h_src.get(), n_src, s));
   SFM_HIP(hipEventRecord(ib->staged, s));
   ib->staged_pending = true;
   int rc = dense_gray_enqueue(&ib->plan, s, ib->d_src, akaze_gray_dev(a));
@@ -192,7 +191,7 @@ int sfmloc_imgbow_compute(sfmloc_imgbow *p, const uint8_t *image, sfmloc_query *
   if (rc) return rc;
   ib->last_stream = s;
   if (out_bow) {
-    SFM_HIP(hipMemcpyAsync(ib->h_out, ib->d_out, dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    SFM_RC(ib->d_out.download(ib->h_out.get(), dim, s));
     SFM_HIP(hipStreamSynchronize(s));
     memcpy(out_bow, ib->h_out, dim * sizeof(double));
   }
@@ -234,7 +233,7 @@ int sfmloc_imgbow_compute_dev(sfmloc_imgbow *p, sfmloc_imread *reader, uint32_t 
   if (rc) return rc;
   ib->last_stream = s;
   if (out_bow) {
-    SFM_HIP(hipMemcpyAsync(ib->h_out, ib->d_out, dim * sizeof(double), hipMemcpyDeviceToHost, s));
+    SFM_RC(ib->d_out.download(ib->h_out.get(), dim, s));
     SFM_HIP(hipStreamSynchronize(s));
     memcpy(out_bow, ib->h_out, dim * sizeof(double));
   }
@@ -249,7 +248,7 @@ int sfmloc_imgbow_vector_read(sfmloc_imgbow *p, double *out_bow) {
   const BofModel *b = reinterpret_cast<const BofModel *>(ib->bof);
   const size_t dim = (size_t)b->K * b->cells;
   SFM_HIP(hipSetDevice(ib->device));
-  SFM_HIP(hipMemcpyAsync(ib->h_out, ib->d_out, dim * sizeof(double), hipMemcpyDeviceToHost, ib->last_stream));
+  SFM_RC(ib->d_out.download(ib->h_out.get(), dim, ib->last_stream));
   SFM_HIP(hipStreamSynchronize(ib->last_stream));
   memcpy(out_bow, ib->h_out, dim * sizeof(double));
   return SFMLOC_OK;
@@ -290,7 +289,7 @@ int sfmloc_imgbow_compute_batch(sfmloc_imgbow *const *ibs, const uint8_t *const 
     const BofModel *b = reinterpret_cast<const BofModel *>(ib->bof);
     // the upload depends on nothing recorded so far: queued at once, ahead of the session's launches
     hipStream_t su = ms[i]->stream.unordered();
-    SFM_HIP(hipMemcpyAsync(ib->d_src, ib->h_src, n_src, hipMemcpyHostToDevice, su));
+    SFM_RC(ib->d_src.upload(ib->h_src.get(), n_src, su));
     SFM_HIP(hipEventRecord(ib->staged, su));
     ib->staged_pending = true;
     rc = dense_gray_enqueue_member(&ib->plan, ms[i], ib->d_src, akaze_gray_dev(a));

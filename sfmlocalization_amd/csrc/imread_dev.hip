@@ -291,9 +291,9 @@ int decode_other(Imread *r, const uint8_t *bytes, size_t n, uint32_t want, int32
       s_b2g[i] = (uint8_t)((s_bgr[3 * i + 2] * 4899 + s_bgr[3 * i + 1] * 9617 + s_bgr[3 * i] * 1868 + 8192) >> 14);
   SFM_RC(wait_for_consumers(r));
   hipStream_t s = r->stream;
-  if (want & kGray) SFM_HIP(hipMemcpyAsync(r->d_gray, s_gray, np, hipMemcpyHostToDevice, s));
-  if (want & kBgr) SFM_HIP(hipMemcpyAsync(r->d_bgr, s_bgr, 3 * np, hipMemcpyHostToDevice, s));
-  if (want & kBgr2Gray) SFM_HIP(hipMemcpyAsync(r->d_bgr2gray, s_b2g, np, hipMemcpyHostToDevice, s));
+  if (want & kGray) SFM_RC(r->d_gray.upload(s_gray, np, s));
+  if (want & kBgr) SFM_RC(r->d_bgr.upload(s_bgr, 3 * np, s));
+  if (want & kBgr2Gray) SFM_RC(r->d_bgr2gray.upload(s_b2g, np, s));
   SFM_HIP(hipEventRecord(r->staged, s));
   r->staged_pending = true;
   SFM_HIP(hipEventRecord(r->done, s));
@@ -362,7 +362,7 @@ int decode_jpeg(Imread *r, const uint8_t *bytes, size_t n, uint32_t want, int32_
   hipStream_t s = r->stream;
   if (r->timing) SFM_HIP(hipEventRecord(r->t0, s));
   const size_t up = kHdrBytes + (size_t)H->n_blocks * 64 * sizeof(int16_t);
-  SFM_HIP(hipMemcpyAsync(r->d_stage, r->h_stage, up, hipMemcpyHostToDevice, s));
+  SFM_RC(r->d_stage.upload(r->h_stage.get(), up, s));
   SFM_HIP(hipEventRecord(r->staged, s));
   r->staged_pending = true;
   if (r->timing) SFM_HIP(hipEventRecord(r->t1, s));
@@ -510,7 +510,7 @@ int sfmloc_imread_read(sfmloc_imread *p, uint32_t which, uint8_t *out, uint64_t 
   SFM_CHECK(cap >= nb, SFMLOC_ECAP, "sfmloc_imread_read: buffer holds %llu bytes, the image needs %llu", (unsigned long long)cap,
             (unsigned long long)nb);
   SFM_HIP(hipSetDevice(r->device));
-  SFM_HIP(hipMemcpyAsync(out, src, nb, hipMemcpyDeviceToHost, r->stream));
+  SFM_RC(dev_download(out, src, nb, r->stream));
   SFM_HIP(hipStreamSynchronize(r->stream));
   return SFMLOC_OK;
 }

@@ -360,9 +360,9 @@ __global__ __launch_bounds__(1024) void k_match_set_finish(const unsigned char *
 int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32_t n_sel, bool all_views) {
   Map *m = c->map;
   if (!pass.cleared) {
-    SFM_HIP(hipMemsetAsync(c->d_cand_part, 0, kPartHeaderBytes, c->stream));
-    SFM_HIP(hipMemsetAsync(c->d_view_stats, 0, 3 * sizeof(uint32_t), c->stream));
-    SFM_HIP(hipMemsetAsync(c->d_best64, 0xFF, (size_t)(q->n ? q->n : 1) * sizeof(unsigned long long), c->stream));
+    SFM_RC(c->d_cand_part.zero(kPartHeaderBytes, c->stream));
+    SFM_RC(dev_zero(c->d_view_stats, 3, c->stream));
+    SFM_RC(c->d_best64.fill(0xFF, (size_t)(q->n ? q->n : 1), c->stream));
   }
   if (n_sel == 0 || q->n == 0) return SFMLOC_OK;
   const uint32_t *sel = all_views ? nullptr : c->d_view_sel;

@@ -110,6 +110,7 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
   q->height = m->h_view_wh.size() > 2 * (size_t)v + 1 ? m->h_view_wh[2 * v + 1] : 0;
   const uint32_t n_pad = (n + 63) / 64 * 64;
   hipError_t e = hipSuccess;
+  int rc = SFMLOC_OK;  // (of the copies, which set their own error text)
   hipStream_t s = m->ctx0->stream;
   if (n_pad) {
     e = query_array(q->d_desc, (size_t)n_pad * 4);
@@ -122,19 +123,25 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
       // the map's keypoints are the .feat values already (6 significant digits), for both uses
       e = query_array(q->d_kpt, n);
       if (e == hipSuccess) e = query_array(q->d_kpt6, n);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(q->d_kpt, m->d_kpt + r0, (size_t)n * sizeof(float2), hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(q->d_kpt6, m->d_kpt + r0, (size_t)n * sizeof(float2), hipMemcpyDeviceToDevice, s);
+      if (e == hipSuccess) rc = q->d_kpt.copy_from(m->d_kpt + r0, n, s);
+      if (e == hipSuccess && !rc) rc = q->d_kpt6.copy_from(m->d_kpt + r0, n, s);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && !rc) e = hipStreamSynchronize(s);
   }
   if (e != hipSuccess) {
     set_error("sfmloc_query_from_view: %s", hipGetErrorString(e));
+    rc = e == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
+  }
+  if (rc) {
     delete q;  // (with the arrays it owns)
-    return e == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;
+    return rc;
   }
   *out = q;
+  return SFMLOC_OK;
+}
+
+int wait_for(hipStream_t s) {  // (a checked wait, for the chains of codes below)
+  SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
 
@@ -158,15 +165,14 @@ int match_one_to_one(Map *m, Query *q, const uint32_t *view_sel, uint32_t n_sel)
 int read_view_list(Map *m, uint32_t v, std::vector<uint32_t> *mi, std::vector<uint32_t> *mj) {
   Ctx *c = m->ctx0;
   uint32_t n = 0;
-  SFM_HIP(hipMemcpyAsync(&n, c->d_view_count + v, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  const hipStream_t s = c->stream;
+  SFM_RC(c->d_view_count.read(&n, 1, s, v));
   mi->resize(n);
   mj->resize(n);
   if (n == 0) return SFMLOC_OK;
   const uint32_t off = m->h_view_off[v];
-  SFM_HIP(hipMemcpyAsync(mi->data(), c->d_match_i + off, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  SFM_HIP(hipMemcpyAsync(mj->data(), c->d_match_key + off, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  SFM_HIP(hipStreamSynchronize(c->stream));
+  SFM_RC(c->d_match_i.download(mi->data(), n, s, off));
+  SFM_RC(c->d_match_key.read(mj->data(), n, s, off));
   for (uint32_t k = 0; k < n; ++k) (*mj)[k] &= 0xFFFFu;
   return SFMLOC_OK;
 }
@@ -346,8 +352,7 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
     int rc = query_from_view(m, b, &q);
     if (rc) return rc;
     std::vector<uint32_t> sel;
-    std::vector<uint32_t> zero(1, 0);
-    rc = SFMLOC_OK;
+    const hipStream_t s = c->stream;  // (the map's own context: never a member of a gang session)
     for (auto &fp : first_to_pair) {
       const uint32_t a = fp.first, k = fp.second;
       const uint32_t n = (uint32_t)(offsets[k + 1] - offsets[k]);
@@ -359,18 +364,17 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
         }
       if (rc) break;
       sel.push_back(a);
-      if (n) {
-        hipMemcpyAsync(c->d_match_i + off, match_i + offsets[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        hipMemcpyAsync(c->d_match_key + off, match_j + offsets[k], n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-      }
-      hipMemcpyAsync(c->d_view_count + a, &n, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-      hipStreamSynchronize(c->stream);  // `n` and the caller's arrays are pageable host memory
+      rc = c->d_match_i.upload(match_i + offsets[k], n, s, off);
+      if (!rc) rc = c->d_match_key.upload(match_j + offsets[k], n, s, off);
+      if (!rc) rc = c->d_view_count.upload(&n, 1, s, a);
+      if (!rc) rc = wait_for(s);  // `n` and the caller's arrays are pageable host memory
+      if (rc) break;
     }
+    if (rc == SFMLOC_OK) rc = c->d_view_sel.upload(sel.data(), sel.size(), s);
+    if (rc == SFMLOC_OK) rc = wait_for(s);
+    for (size_t t = 0; rc == SFMLOC_OK && t < sel.size(); ++t) rc = c->d_geo_count.zero(1, s, sel[t]);
+    if (rc == SFMLOC_OK) rc = dev_zero(c->d_status, 1, s);
     if (rc == SFMLOC_OK) {
-      hipMemcpyAsync(c->d_view_sel, sel.data(), sel.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-      hipStreamSynchronize(c->stream);
-      for (uint32_t a : sel) hipMemsetAsync(c->d_geo_count + a, 0, sizeof(uint32_t), c->stream);
-      hipMemsetAsync(c->d_status, 0, sizeof(int), c->stream);
       // no >=16 rule here: OpenMVG's Robust_model_estimation takes every pair it is given (the caller has applied
       // ExtFeatAndMatch's minMatch, computeFeaturesAndMatches.cpp:211-221)
       QueryPass pass;  // (a stage on its own: the memsets above are its reset)
@@ -381,32 +385,29 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
     if (rc == SFMLOC_OK && guided) {
       // which pairs passed the filter must be read before the guided lists replace the inlier counts: a pair whose
       // guided list comes out empty keeps its (empty) entry
-      for (size_t t = 0; t < sel.size(); ++t)
-        hipMemcpyAsync(&passed[t], c->d_geo_count + sel[t], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-      hipStreamSynchronize(c->stream);
-      rc = launch_guided_matching(c, q, (uint32_t)sel.size(), false);
+      for (size_t t = 0; rc == SFMLOC_OK && t < sel.size(); ++t) rc = c->d_geo_count.download(&passed[t], 1, s, sel[t]);
+      if (rc == SFMLOC_OK) rc = wait_for(s);
+      if (rc == SFMLOC_OK) rc = launch_guided_matching(c, q, (uint32_t)sel.size(), false);
     }
     for (size_t t = 0; rc == SFMLOC_OK && t < sel.size(); ++t) {
       const uint32_t a = sel[t], k = first_to_pair[a];
       uint32_t ng = 0;
-      hipMemcpyAsync(&ng, c->d_geo_count + a, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-      hipStreamSynchronize(c->stream);
+      if ((rc = c->d_geo_count.read(&ng, 1, s, a))) break;
       if (guided) {
         if (passed[t] == 0) continue;
         auto &pr = pm[{a, b}];
         if (ng == 0) continue;
         std::vector<uint32_t> gi(ng), gj(ng);
-        hipMemcpyAsync(gi.data(), c->d_geo_idx + m->h_view_off[a], ng * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        hipMemcpyAsync(gj.data(), c->d_geo_j + m->h_view_off[a], ng * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-        hipStreamSynchronize(c->stream);
+        rc = c->d_geo_idx.download(gi.data(), ng, s, m->h_view_off[a]);
+        if (!rc) rc = c->d_geo_j.read(gj.data(), ng, s, m->h_view_off[a]);
+        if (rc) break;
         pr.first.assign(gi.begin(), gi.end());
         pr.second.assign(gj.begin(), gj.end());
         continue;
       }
       if (ng == 0) continue;  // pairs that fail the filter get no entry
       std::vector<uint32_t> gi(ng);
-      hipMemcpyAsync(gi.data(), c->d_geo_idx + m->h_view_off[a], ng * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-      hipStreamSynchronize(c->stream);
+      if ((rc = c->d_geo_idx.read(gi.data(), ng, s, m->h_view_off[a]))) break;
       auto &pr = pm[{a, b}];
       for (uint32_t g : gi) {  // AC-RANSAC's inlier order, indices into the putative list
         pr.first.push_back(match_i[offsets[k] + g]);
@@ -414,10 +415,11 @@ int sfmloc_geometric_pairs(sfmloc_map *map, const uint32_t *pairs, uint32_t n_pa
       }
     }
     int status = 0;
-    hipMemcpy(&status, c->d_status, sizeof(int), hipMemcpyDeviceToHost);
+    const int rc_status = dev_read(&status, c->d_status, 1, s);  // (on the context's stream: behind everything above)
     if (c->last_query == q) c->last_query = nullptr;
     delete q;
     if (rc) return rc;
+    if (rc_status) return rc_status;
     SFM_CHECK((status & 1) == 0, SFMLOC_ECAP, "a pair has more than 65536 putative matches");
   }
   Matches *M = flatten(pm);

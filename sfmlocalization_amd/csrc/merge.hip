@@ -586,7 +586,7 @@ int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, con
   MRG_TRY(d_idx.alloc(nullptr, n));
   MRG_TRY(d_n.alloc(nullptr, 1));
   MRG_TRY(d_ok.alloc(nullptr, 1));
-  SFM_HIP(hipMemsetAsync(d_best, 0, sizeof(unsigned long long), d->s));
+  SFM_RC(d_best.zero(1, d->s));
   MRG_TRY(d->time_begin());
   const uint64_t per = p.rounds_per_launch ? p.rounds_per_launch : kMergeLaunchRounds;
   for (uint64_t r0 = 0; r0 < rounds; r0 += per) {
@@ -601,8 +601,8 @@ int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, con
   SFM_HIP(hipGetLastError());
   MRG_TRY(launch_inliers(d, dA, dB, n, dM, d_info, thres, d_idx, d_n));
   uint32_t info[3] = {0, 0, 0}, n_inl = 0;
-  SFM_HIP(hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, d->s));
-  SFM_HIP(hipMemcpyAsync(&n_inl, d_n, sizeof n_inl, hipMemcpyDeviceToHost, d->s));
+  SFM_RC(d_info.download(info, 3, d->s));
+  SFM_RC(d_n.download(&n_inl, 1, d->s));
   SFM_HIP(hipStreamSynchronize(d->s));
   out->round = info[1];
   out->count = info[2];
@@ -613,14 +613,14 @@ int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, con
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_fit<MODEL>), dim3(1), dim3(256), 0, d->s, dA, dB, d_idx, n_inl, dMf, d_ok);
     SFM_HIP(hipGetLastError());
     uint32_t ok = 0;
-    SFM_HIP(hipMemcpyAsync(out->M, dMf, 12 * sizeof(double), hipMemcpyDeviceToHost, d->s));
-    SFM_HIP(hipMemcpyAsync(&ok, d_ok, sizeof ok, hipMemcpyDeviceToHost, d->s));
+    SFM_RC(dMf.download(out->M, 12, d->s));
+    SFM_RC(d_ok.download(&ok, 1, d->s));
     SFM_HIP(hipStreamSynchronize(d->s));
     out->has_model = ok;
   }
   MRG_TRY(d->time_end());
   SFM_CHECK(!inliers || cap >= n_inl, SFMLOC_ECAP, "sfmloc_merge_ransac: %u entries, %u inliers", cap, n_inl);
-  if (inliers && n_inl) SFM_HIP(hipMemcpy(inliers, d_idx, n_inl * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (inliers && n_inl) SFM_RC(d_idx.read(inliers, n_inl, d->s));
 #undef MRG_TRY
   return SFMLOC_OK;
 }
@@ -637,10 +637,10 @@ int radix_select(CallScope *d, const uint64_t *dv, uint32_t n, uint32_t k, uint3
   uint32_t h[256];
   const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 1024);
   for (int shift = 56; shift >= 0; shift -= 8) {
-    SFM_HIP(hipMemsetAsync(d_hist, 0, 256 * sizeof(uint32_t), d->s));
+    SFM_RC(dev_zero(d_hist, 256, d->s));
     hipLaunchKernelGGL(k_merge_hist, dim3(blocks), dim3(256), 0, d->s, dv, n, prefix, shift, d_hist);
     SFM_HIP(hipGetLastError());
-    SFM_HIP(hipMemcpyAsync(h, d_hist, sizeof h, hipMemcpyDeviceToHost, d->s));
+    SFM_RC(dev_download(h, d_hist, 256, d->s));
     SFM_HIP(hipStreamSynchronize(d->s));
     uint32_t b = 0;
     while (b < 255 && k >= h[b]) k -= h[b++];
@@ -712,10 +712,10 @@ int sfmloc_merge_inliers(const double *A, const double *B, uint64_t n, const dou
   rc = launch_inliers(&d, dA, dB, (uint32_t)n, dM, nullptr, thres, d_idx, d_n);
   if (rc) return rc;
   if ((rc = d.time_end())) return rc;
-  SFM_HIP(hipMemcpyAsync(n_out, d_n, sizeof(uint32_t), hipMemcpyDeviceToHost, d.s));
+  SFM_RC(d_n.download(n_out, 1, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));
   SFM_CHECK(!idx || cap >= *n_out, SFMLOC_ECAP, "sfmloc_merge_inliers: %u entries, %u inliers", cap, *n_out);
-  if (idx && *n_out) SFM_HIP(hipMemcpy(idx, d_idx, *n_out * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (idx && *n_out) SFM_RC(d_idx.read(idx, *n_out, d.s));
   return SFMLOC_OK;
 }
 
@@ -775,8 +775,8 @@ int sfmloc_merge_transform(const double *M, double *R, uint64_t nR, double *X, u
                      (uint32_t)nX);
   SFM_HIP(hipGetLastError());
   if ((rc = d.time_end())) return rc;
-  if (nR) SFM_HIP(hipMemcpyAsync(R, dR, 9 * (size_t)nR * sizeof(double), hipMemcpyDeviceToHost, d.s));
-  if (nX) SFM_HIP(hipMemcpyAsync(X, dX, 3 * (size_t)nX * sizeof(double), hipMemcpyDeviceToHost, d.s));
+  if (nR) SFM_RC(dR.download(R, 9 * (size_t)nR, d.s));
+  if (nX) SFM_RC(dX.download(X, 3 * (size_t)nX, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));
   return SFMLOC_OK;
 }

@@ -329,8 +329,8 @@ int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscale
             (const uint32_t *)d_place, d_out.get());
   SFM_HIP(hipGetLastError());
   uint32_t n_yield = 0, n_rec = 0;
-  SFM_HIP(hipMemcpyAsync(&n_rec, d_place.get() + n_cand, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  SFM_HIP(hipMemcpyAsync(&n_yield, d_seg_begin.get() + 2 * P, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_place.download(&n_rec, 1, s, n_cand));
+  SFM_RC(d_seg_begin.download(&n_yield, 1, s, 2 * P));
   SFM_HIP(hipStreamSynchronize(s));
   rep.n_depths = n_yield / 2;
   std::vector<sfmloc_wscale> rec(n_rec);
@@ -358,7 +358,7 @@ int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscale
     WS_LAUNCH(k_ws_ratio, n_rec, kThreads, D, (const sfmloc_wscale *)d_out, (const uint32_t *)rv, d_final.get(), n_rec,
               opt.max_shared);
     SFM_HIP(hipGetLastError());
-    SFM_HIP(hipMemcpyAsync(rec.data(), d_final, rec.size() * sizeof(sfmloc_wscale), hipMemcpyDeviceToHost, s));
+    SFM_RC(d_final.download(rec.data(), rec.size(), s));
     SFM_HIP(hipStreamSynchronize(s));
   }
   w->rec.swap(rec);

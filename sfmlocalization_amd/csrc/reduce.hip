@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void k_reduce_order(uint32_t n, const uint32_t
 int zeros(CallScope *d, DevBuf<uint32_t> &b, size_t n) {
   const int rc = b.alloc(nullptr, n);
   if (rc) return rc;
-  SFM_HIP(hipMemsetAsync(b, 0, n * sizeof(uint32_t), d->s));
+  SFM_RC(b.zero(n, d->s));
   return SFMLOC_OK;
 }
 
@@ -388,13 +388,13 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   RDC_TRY(dev_upload(nullptr, dX, X, 3 * (size_t)n, d->s));
   RDC_TRY(dG.alloc(nullptr, 3 * (size_t)n));
   RDC_TRY(d_box.alloc(nullptr, 6));
-  SFM_HIP(hipMemsetAsync(d_box, 0xFF, 3 * sizeof(unsigned long long), d->s));
-  SFM_HIP(hipMemsetAsync(d_box + 3, 0x00, 3 * sizeof(unsigned long long), d->s));
+  SFM_RC(d_box.fill(0xFF, 3, d->s));
+  SFM_RC(d_box.zero(3, d->s, 3));
   RDC_TRY(d->time_begin());
   hipLaunchKernelGGL(k_reduce_global, lanes(n), dim3(256), 0, d->s, T, dX, n, dG, d_box);
   SFM_HIP(hipGetLastError());
   unsigned long long box[6];
-  SFM_HIP(hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, d->s));
+  SFM_RC(d_box.download(box, 6, d->s));
   SFM_HIP(hipStreamSynchronize(d->s));
 
   Grid gr;
@@ -430,7 +430,7 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   // (row counts sum to at most n (knn - 1) or n (n - 1) / 2: the total may pass 2^32, so it is added up here in 64 bits
   // before the 32-bit scan runs)
   std::vector<uint32_t> rowcnt(n);
-  SFM_HIP(hipMemcpyAsync(rowcnt.data(), d_rowoff, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->s));
+  SFM_RC(d_rowoff.download(rowcnt.data(), n, d->s));
   SFM_HIP(hipStreamSynchronize(d->s));
   uint64_t n_pairs = 0;
   for (uint32_t i = 0; i < n; ++i) n_pairs += rowcnt[i];
@@ -459,7 +459,7 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   RDC_TRY(d_dist.alloc(nullptr, n));
   RDC_TRY(d_state.alloc(nullptr, 2));
   uint32_t state[2] = {n, 0};
-  SFM_HIP(hipMemcpyAsync(d_state, state, sizeof state, hipMemcpyHostToDevice, d->s));
+  SFM_RC(d_state.upload(state, 2, d->s));
   const uint32_t per = p.rounds_per_launch ? p.rounds_per_launch : kResolvePasses;
   for (uint32_t pass = 1; state[0] != 0;) {  // each pass decides at least the smallest undecided index
     for (uint32_t k = 0; k < per; ++k, ++pass) {
@@ -467,14 +467,14 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
                          d_state);
       SFM_HIP(hipGetLastError());
     }
-    SFM_HIP(hipMemcpyAsync(state, d_state, sizeof state, hipMemcpyDeviceToHost, d->s));
+    SFM_RC(d_state.download(state, 2, d->s));
     SFM_HIP(hipStreamSynchronize(d->s));
     SFM_CHECK(pass <= n + per, SFMLOC_EHIP, "sfmloc_reduce_points: %u points undecided after %u passes", state[0], pass - 1);
   }
 
   RDC_TRY(zeros(d, d_ooff, (size_t)n + 1));
   RDC_TRY(d_order.alloc(nullptr, n));
-  SFM_HIP(hipMemsetAsync(d_order, 0xFF, (size_t)n * sizeof(uint32_t), d->s));
+  SFM_RC(d_order.fill(0xFF, n, d->s));
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_order<false>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner, d_ooff,
                      (const uint32_t *)nullptr, (uint32_t *)nullptr);
   SFM_HIP(hipGetLastError());
@@ -487,10 +487,10 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   std::vector<uint32_t> h_owner(n), h_order(n);
   std::vector<double> h_dist(n);
   uint32_t n_absorbed = 0;
-  SFM_HIP(hipMemcpyAsync(h_owner.data(), d_owner, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->s));
-  SFM_HIP(hipMemcpyAsync(h_order.data(), d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->s));
-  SFM_HIP(hipMemcpyAsync(h_dist.data(), d_dist, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, d->s));
-  SFM_HIP(hipMemcpyAsync(&n_absorbed, d_ooff + n, sizeof(uint32_t), hipMemcpyDeviceToHost, d->s));
+  SFM_RC(d_owner.download(h_owner.data(), n, d->s));
+  SFM_RC(d_order.download(h_order.data(), n, d->s));
+  SFM_RC(d_dist.download(h_dist.data(), n, d->s));
+  SFM_RC(d_ooff.download(&n_absorbed, 1, d->s, n));
   SFM_HIP(hipStreamSynchronize(d->s));
   memcpy(owner, h_owner.data(), (size_t)n * sizeof(uint32_t));
   memcpy(order, h_order.data(), (size_t)n * sizeof(uint32_t));

@@ -164,7 +164,7 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
   SFM_RC(e0.create(kTimingEvent));
   SFM_RC(e1.create(kTimingEvent));
   SFM_HIP(hipEventRecord(e0, s));
-  SFM_HIP(hipMemsetAsync(S.d_extended, 0, sizeof(unsigned long long), s));
+  SFM_RC(S.d_extended.zero(1, s));
   sfmloc_register_report R;
   memset(&R, 0, sizeof R);
   for (uint32_t v = 0; v < n_views; ++v) R.views_unposed_in += h.h_pose_valid[h.h_view_pose[v]] ? 0u : 1u;
@@ -179,13 +179,13 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
     for (uint32_t v = 0; v < n_views; ++v)
       if (!h.h_pose_valid[h.h_view_pose[v]]) unposed.push_back(v);
     if (unposed.empty()) break;
-    SFM_HIP(hipMemcpyAsync(S.d_unposed, unposed.data(), unposed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    SFM_RC(S.d_unposed.upload(unposed.data(), unposed.size(), s));
     const SfmDev D = sfm_dev(h);
     hipLaunchKernelGGL(k_reg_compact, dim3((unsigned)unposed.size()), dim3(kRegBlock), 0, s,
                        (const uint32_t *)S.d_unposed, D.vlist, D.view_off, D.obs_lm, (const uint8_t *)D.lm_stage,
                        S.d_clist.get(), S.d_cnt.get());
     SFM_HIP(hipGetLastError());
-    SFM_HIP(hipMemcpyAsync(cnt.data(), S.d_cnt, n_views * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_RC(S.d_cnt.download(cnt.data(), n_views, s));
     SFM_HIP(hipStreamSynchronize(s));
     // candidates
     todo.clear();
@@ -240,12 +240,10 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
     R.views_tried += (uint32_t)todo.size();
     R.views_registered += n_ok;
     if (n_ok == 0) break;
-    SFM_HIP(hipMemcpyAsync(D.pose_valid, h.h_pose_valid.data(), h.n_poses, hipMemcpyHostToDevice, s));
-    SFM_HIP(hipMemcpyAsync(D.pose_R, h.h_pose_R.data(), 9 * (size_t)h.n_poses * sizeof(double), hipMemcpyHostToDevice,
-                           s));
-    SFM_HIP(hipMemcpyAsync(D.pose_C, h.h_pose_C.data(), 3 * (size_t)h.n_poses * sizeof(double), hipMemcpyHostToDevice,
-                           s));
-    SFM_HIP(hipMemcpyAsync(S.d_view_new, is_new.data(), n_views, hipMemcpyHostToDevice, s));
+    SFM_RC(dev_upload(D.pose_valid, h.h_pose_valid.data(), h.n_poses, s));
+    SFM_RC(dev_upload(D.pose_R, h.h_pose_R.data(), 9 * (size_t)h.n_poses, s));
+    SFM_RC(dev_upload(D.pose_C, h.h_pose_C.data(), 3 * (size_t)h.n_poses, s));
+    SFM_RC(S.d_view_new.upload(is_new.data(), n_views, s));
     // extend
     RegExtendArgs E;
     static_cast<SfmDev &>(E) = D;
@@ -265,7 +263,7 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
                          D.view_pose, (const uint8_t *)D.pose_valid, (const uint8_t *)S.d_view_new,
                          (const uint8_t *)D.lm_stage, S.d_select.get());
     SFM_HIP(hipGetLastError());
-    SFM_HIP(hipMemcpyAsync(&S.h_extended, S.d_extended, sizeof S.h_extended, hipMemcpyDeviceToHost, s));
+    SFM_RC(S.d_extended.download(&S.h_extended, 1, s));
     sfmloc_triangulate_options to;
     memset(&to, 0, sizeof to);
     to.mode = SFMLOC_TRI_ROBUST;
@@ -356,7 +354,7 @@ int sfmloc_sfm_register_counts(const sfmloc_sfm *hh, uint32_t *c) {
   hipLaunchKernelGGL(k_reg_counts, dim3(h->n_views), dim3(kRegBlock), 0, s, h->n_views, D.vlist, D.view_off, D.obs_lm,
                      (const uint8_t *)D.lm_stage, d_c.get());
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(c, d_c, h->n_views * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_c.download(c, h->n_views, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }

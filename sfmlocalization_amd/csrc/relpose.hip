@@ -404,7 +404,7 @@ int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const
   SFM_RC(d_inl.alloc(nullptr, (size_t)total));
   SFM_RC(d_L10.alloc(nullptr, kRpL10));
   SFM_RC(d_res.alloc(nullptr, n_pairs));
-  SFM_HIP(hipMemsetAsync(d_res, 0, (size_t)n_pairs * sizeof(sfmloc_relpose_result), s));  // (the records' padding too)
+  SFM_RC(d_res.zero(n_pairs, s));  // (the records' padding too)
   hipLaunchKernelGGL(k_rp_fill_log10, dim3((kRpL10 + 255) / 256), dim3(256), 0, s, d_L10.get(), kRpL10);
   hipLaunchKernelGGL(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, scene.dev(), d_bear.get());
   SFM_HIP(hipGetLastError());
@@ -453,8 +453,8 @@ int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const
     SFM_HIP(hipGetLastError());
   }
   std::vector<uint32_t> inl((size_t)total);
-  SFM_HIP(hipMemcpyAsync(r->res.data(), d_res, (size_t)n_pairs * sizeof(sfmloc_relpose_result), hipMemcpyDeviceToHost, s));
-  if (total) SFM_HIP(hipMemcpyAsync(inl.data(), d_inl, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_res.download(r->res.data(), n_pairs, s));
+  if (total) SFM_RC(d_inl.download(inl.data(), total, s));
   SFM_HIP(hipStreamSynchronize(s));
   for (uint32_t k = 0; k < n_pairs; ++k) {
     const uint32_t n = r->res[k].n_inliers;
@@ -535,7 +535,7 @@ int sfmloc_debug_five_point(int device, const double *in, int n, double *out) {
   if ((rc = d_out.alloc(nullptr, 91 * (size_t)n))) return rc;
   hipLaunchKernelGGL(k_debug_five_point, dim3((n + 3) / 4), dim3(64), 0, d.s, (const double *)d_in, n, d_out.get());
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(out, d_out, 91 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, d.s));
+  SFM_RC(d_out.download(out, 91 * (size_t)n, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));
   return SFMLOC_OK;
 }

@@ -426,7 +426,7 @@ int relrefine_device(const PairScene &sc, const PairPoses &po, const sfmloc_relr
   SFM_RC(d_pts.alloc(nullptr, 3 * n_inl));
   SFM_RC(d_trial.alloc(nullptr, 3 * n_inl));
   SFM_RC(d_res.alloc(nullptr, P));
-  SFM_HIP(hipMemsetAsync(d_res, 0, P * sizeof(sfmloc_relrefine_result), s));
+  SFM_RC(d_res.zero(P, s));
   RrDev D{};
   static_cast<PairDev &>(D) = scene.dev();
   static_cast<PairPosesDev &>(D) = poses.dev();
@@ -435,7 +435,7 @@ int relrefine_device(const PairScene &sc, const PairPoses &po, const sfmloc_relr
   D.bear = d_bear, D.pts = d_pts, D.trial = d_trial, D.res = d_res;
   hipLaunchKernelGGL(k_relrefine, dim3(sc.n_pairs), dim3(kRrThreads), 0, s, D);
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(r->res.data(), d_res, P * sizeof(sfmloc_relrefine_result), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_res.download(r->res.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }

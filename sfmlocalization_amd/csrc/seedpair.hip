@@ -165,7 +165,7 @@ int seed_device(const PairScene &sc, const PairPoses &po, const sfmloc_seed_opti
   SFM_RC(poses.upload(sc, po, s));
   SFM_RC(d_key.alloc(nullptr, n_inl));
   SFM_RC(d_rec.alloc(nullptr, P));
-  SFM_HIP(hipMemsetAsync(d_rec, 0, P * sizeof(sfmloc_seed_score), s));
+  SFM_RC(d_rec.zero(P, s));
   SdDev D{};
   static_cast<PairDev &>(D) = scene.dev();
   static_cast<PairPosesDev &>(D) = poses.dev();
@@ -174,7 +174,7 @@ int seed_device(const PairScene &sc, const PairPoses &po, const sfmloc_seed_opti
   D.max_cos = opt.max_cos, D.min_cos = opt.min_cos;
   hipLaunchKernelGGL(k_seed_scores, dim3(sc.n_pairs), dim3(kSdThreads), 0, s, D);
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(r->rec.data(), d_rec, P * sizeof(sfmloc_seed_score), hipMemcpyDeviceToHost, s));
+  SFM_RC(d_rec.download(r->rec.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }

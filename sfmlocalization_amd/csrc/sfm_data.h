@@ -224,15 +224,14 @@ int sfm_resect_gang(Sfm &h, const std::vector<uint32_t> &todo, const std::vector
       if (!p.ok) {  // K5 publishes no pair list for a failed query: its best model's list, after the gang's last wait
         if (ni) failed.emplace_back(c, &inl);
       } else if (c->p3p_cap > (uint32_t)kP3pMaxN) {  // (a regrown workspace keeps its pair lists outside the record)
-        SFM_HIP(hipMemcpy(inl.data(), c->d_pair_qfeat, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        SFM_RC(dev_read(inl.data(), c->d_pair_qfeat, ni, c->stream));
       } else {
         memcpy(inl.data(), hr->pair_qfeat, ni * sizeof(uint32_t));
       }
     }
     // (h.s is not the contexts' stream: the waits above have seen their work finish.  One wait for all failed views.)
     for (const auto &f : failed)
-      SFM_HIP(hipMemcpyAsync(f.second->data(), f.first->d_best_inl, f.second->size() * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, h.s));
+      SFM_RC(f.first->d_best_inl.download(f.second->data(), f.second->size(), h.s));
     if (!failed.empty()) SFM_HIP(hipStreamSynchronize(h.s));
   }
   for (sfmloc_context *cc : h.ctx) reinterpret_cast<Ctx *>(cc)->p3p_own_K = false;

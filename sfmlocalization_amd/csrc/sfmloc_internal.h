@@ -189,10 +189,8 @@ struct HostResult {
 // is empty) and filled from the host on stream s.  acct: devmem.h.
 template <class T>
 inline int dev_upload(uint64_t *acct, DevBuf<T> &p, const T *h, size_t n, hipStream_t s, size_t min_alloc = 0) {
-  const int rc = p.alloc(acct, n > min_alloc ? n : min_alloc);
-  if (rc) return rc;
-  if (n) SFM_HIP(hipMemcpyAsync(p.get(), h, n * sizeof(T), hipMemcpyHostToDevice, s));
-  return SFMLOC_OK;
+  SFM_RC(p.alloc(acct, n > min_alloc ? n : min_alloc));
+  return p.upload(h, n, s);
 }
 
 // A call's stream and its two timing events, let go on every way out.  Declare it before the call's DevBuf locals

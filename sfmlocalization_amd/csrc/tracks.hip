@@ -165,7 +165,7 @@ int scan_excl(uint32_t *a, uint32_t n, uint32_t *sums, hipStream_t s) {
 }
 
 int read_u32(uint32_t *out, const uint32_t *d, hipStream_t s) {
-  SFM_HIP(hipMemcpyAsync(out, d, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  SFM_RC(dev_download(out, d, 1, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
 }
@@ -183,15 +183,15 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_touched.alloc(nullptr, (size_t)n + 1));
   SFM_RC(d_sums.alloc(nullptr, (size_t)n / 1024 + 2));
   SFM_RC(d_flag.alloc(nullptr, 4));  // changed, then the three counts of the filter
-  SFM_HIP(hipMemcpyAsync(d_voff, voff.data(), voff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  SFM_HIP(hipMemcpyAsync(d_ea, ea.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-  SFM_HIP(hipMemcpyAsync(d_eb, eb.data(), (size_t)m_edges * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  SFM_RC(d_voff.upload(voff.data(), voff.size(), s));
+  SFM_RC(d_ea.upload(ea.data(), m_edges, s));
+  SFM_RC(d_eb.upload(eb.data(), m_edges, s));
   const dim3 gn((n + 1 + 255) / 256), ge((m_edges + 255) / 256), b256(256);
   hipLaunchKernelGGL(k_trk_init, gn, b256, 0, s, d_parent.get(), d_touched.get(), n);
   hipLaunchKernelGGL(k_trk_mark, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_touched.get());
   SFM_HIP(hipGetLastError());
   for (;;) {  // sfmloc.h "components": until a pass hooks nothing
-    SFM_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+    SFM_RC(d_flag.zero(1, s));
     hipLaunchKernelGGL(k_graph_hook, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_parent.get(),
                        d_flag.get());
     hipLaunchKernelGGL(k_graph_jump, gn, b256, 0, s, d_parent.get(), n);
@@ -233,8 +233,8 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_conf.alloc(nullptr, n_comp));
   SFM_RC(d_tid.alloc(nullptr, (size_t)n_comp + 1));
   SFM_RC(d_toff.alloc(nullptr, (size_t)n_comp + 1));
-  SFM_HIP(hipMemsetAsync(d_conf, 0, (size_t)n_comp * sizeof(uint32_t), s));
-  SFM_HIP(hipMemsetAsync(d_flag, 0, 4 * sizeof(uint32_t), s));
+  SFM_RC(d_conf.zero(n_comp, s));
+  SFM_RC(d_flag.zero(4, s));
   hipLaunchKernelGGL(k_trk_components, gm, b256, 0, s, key, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_voff,
                      n_views, d_start.get(), d_conf.get());
   hipLaunchKernelGGL(k_trk_filter, dim3((n_comp + 1 + 255) / 256), b256, 0, s, (const uint32_t *)d_start,
@@ -243,7 +243,7 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(scan_excl(d_tid, n_comp + 1, d_sums, s));
   SFM_RC(scan_excl(d_toff, n_comp + 1, d_sums, s));
   uint32_t n_tracks = 0, n_rows = 0, cnt[4] = {0, 0, 0, 0};
-  SFM_HIP(hipMemcpyAsync(cnt, d_flag, sizeof cnt, hipMemcpyDeviceToHost, s));
+  SFM_RC(d_flag.download(cnt, 4, s));
   SFM_RC(read_u32(&n_tracks, d_tid.get() + n_comp, s));
   SFM_RC(read_u32(&n_rows, d_toff.get() + n_comp, s));
   DevBuf<uint32_t> d_off, d_view, d_feat;
@@ -257,10 +257,10 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   std::vector<uint32_t> off32(n_tracks);
   t->view.resize(n_rows);
   t->feat.resize(n_rows);
-  if (n_tracks) SFM_HIP(hipMemcpyAsync(off32.data(), d_off, (size_t)n_tracks * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (n_tracks) SFM_RC(d_off.download(off32.data(), n_tracks, s));
   if (n_rows) {
-    SFM_HIP(hipMemcpyAsync(t->view.data(), d_view, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(t->feat.data(), d_feat, (size_t)n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    SFM_RC(d_view.download(t->view.data(), n_rows, s));
+    SFM_RC(d_feat.download(t->feat.data(), n_rows, s));
   }
   SFM_HIP(hipStreamSynchronize(s));
   t->off.assign(off32.begin(), off32.end());

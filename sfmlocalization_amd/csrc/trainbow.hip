@@ -469,7 +469,7 @@ int tb_moments(BowTrain *t) {
   hipLaunchKernelGGL(k_tb_colsum, dim3((n_out + 255) / 256), dim3(256), 0, t->s, (const double *)t->d_part, chunks, n_out, t->d_mom);
   SFM_HIP(hipGetLastError());
   std::vector<double> mom(n_out);
-  SFM_HIP(hipMemcpyAsync(mom.data(), t->d_mom, n_out * sizeof(double), hipMemcpyDeviceToHost, t->s));
+  SFM_RC(t->d_mom.download(mom.data(), n_out, t->s));
   SFM_HIP(hipStreamSynchronize(t->s));
   const double N = (double)n;
   t->mean.assign(dim, 0.0);
@@ -567,7 +567,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
           hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[di], chunks,
                              (const float *)w.dist[di], n, -1.0, w.d_pick + 1);
           PpPick p{};
-          SFM_HIP(hipMemcpyAsync(&p, w.d_pick + 1, sizeof(PpPick), hipMemcpyDeviceToHost, s));
+          SFM_RC(w.d_pick.download(&p, 1, s, 1));
           SFM_HIP(hipStreamSynchronize(s));
           sum0 = p.total;
         }
@@ -585,7 +585,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
                                (const float *)w.dist[t2], n, -1.0, w.d_pick + 1);
             SFM_HIP(hipGetLastError());
             PpPick p[2];
-            SFM_HIP(hipMemcpyAsync(p, w.d_pick, sizeof(p), hipMemcpyDeviceToHost, s));
+            SFM_RC(w.d_pick.download(p, 2, s));
             SFM_HIP(hipStreamSynchronize(s));
             if (p[1].total < best_sum) {
               best_sum = p[1].total;
@@ -599,7 +599,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
           std::swap(di, ti);
         }
         (void)sum0;
-        SFM_HIP(hipMemcpyAsync(w.d_ids, ids.data(), (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        SFM_RC(w.d_ids.upload(ids.data(), K, s));
         hipLaunchKernelGGL(k_tb_gather_rows, dim3((K * dim + 255) / 256), dim3(256), 0, s, (const float *)t->d_x,
                            (const int32_t *)w.d_ids, K, dim, w.d_cen[cur]);
         SFM_HIP(hipGetLastError());
@@ -617,7 +617,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
                            (int)K, (int)dim, (const float *)w.d_cen[cur], w.d_cen[cur ^ 1], w.d_shift);
         SFM_HIP(hipGetLastError());
         cur ^= 1;
-        SFM_HIP(hipMemcpyAsync(&max_shift, w.d_shift, sizeof(double), hipMemcpyDeviceToHost, s));
+        SFM_RC(w.d_shift.download(&max_shift, 1, s));
         SFM_HIP(hipStreamSynchronize(s));
       }
       if (++iter == iter_end || max_shift <= eps2) break;
@@ -631,19 +631,19 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
                        n, -1.0, w.d_pick + 1);
     SFM_HIP(hipGetLastError());
     PpPick p{};
-    SFM_HIP(hipMemcpyAsync(&p, w.d_pick + 1, sizeof(PpPick), hipMemcpyDeviceToHost, s));
+    SFM_RC(w.d_pick.download(&p, 1, s, 1));
     SFM_HIP(hipStreamSynchronize(s));
     compact = p.total;
     if (compact < best) {
       best = compact;
-      SFM_HIP(hipMemcpyAsync(w.d_best_cen, w.d_cen[cur], (size_t)K * dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-      SFM_HIP(hipMemcpyAsync(w.d_best_labels, w.d_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-      SFM_HIP(hipMemcpyAsync(w.d_best_mind, w.d_mind, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+      SFM_RC(w.d_best_cen.copy_from(w.d_cen[cur], (size_t)K * dim, s));
+      SFM_RC(w.d_best_labels.copy_from(w.d_labels, n, s));
+      SFM_RC(w.d_best_mind.copy_from(w.d_mind, n, s));
     }
   }
-  SFM_HIP(hipMemcpyAsync(centers, w.d_best_cen, (size_t)K * dim * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (labels) SFM_HIP(hipMemcpyAsync(labels, w.d_best_labels, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (min_dist) SFM_HIP(hipMemcpyAsync(min_dist, w.d_best_mind, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+  SFM_RC(w.d_best_cen.download(centers, (size_t)K * dim, s));
+  if (labels) SFM_RC(w.d_best_labels.download(labels, n, s));
+  if (min_dist) SFM_RC(w.d_best_mind.download(min_dist, n, s));
   SFM_HIP(hipStreamSynchronize(s));
   if (compactness) *compactness = best;
   if (iterations) *iterations = n_iter;
@@ -735,7 +735,7 @@ int sfmloc_bowtrain_add_rows(sfmloc_bowtrain *p, const float *rows, uint32_t n) 
   SFM_CHECK((uint64_t)t->n + n <= t->cap, SFMLOC_ECAP, "sfmloc_bowtrain_add_rows: %u + %u rows > capacity %u", t->n, n, t->cap);
   if (n == 0) return SFMLOC_OK;
   SFM_HIP(hipSetDevice(t->device));
-  SFM_HIP(hipMemcpyAsync(t->d_x + (size_t)t->n * t->dim, rows, (size_t)n * t->dim * sizeof(float), hipMemcpyHostToDevice, t->s));
+  SFM_RC(dev_upload(t->d_x + (size_t)t->n * t->dim, rows, (size_t)n * t->dim, t->s));
   SFM_HIP(hipStreamSynchronize(t->s));  // (the caller's rows may go once this returns)
   t->n += n;
   t->pca_ok = false;
@@ -753,7 +753,7 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
   SFM_HIP(hipSetDevice(t->device));
   float *dst = t->d_x + (size_t)t->n * t->dim;
   if (!bgr) {  // no descriptors (TrainBoW.cpp:114-116): the rows stay zero, nothing is drawn
-    if (n_pick) SFM_HIP(hipMemsetAsync(dst, 0, (size_t)n_pick * t->dim * sizeof(float), t->s));
+    if (n_pick) SFM_RC(dev_zero(dst, (size_t)n_pick * t->dim, t->s));
     t->n += n_pick;
     t->pca_ok = false;
     return SFMLOC_OK;
@@ -780,7 +780,7 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
       if (rc) return rc;
     }
     t->last_w = 0;  // (invalid until the extraction is queued)
-    SFM_HIP(hipMemcpyAsync(t->d_src, bgr, n_src, hipMemcpyHostToDevice, t->s));
+    SFM_RC(t->d_src.upload(bgr, n_src, t->s));
     int rc = dense_gray_enqueue(&t->plan, t->s, t->d_src, akaze_gray_dev(a));
     if (!rc) rc = akaze_compute_resident(a, t->d_grid, t->n_grid, 4);  // (the grid's four scales are levels 0 .. 3)
     if (rc) return rc;
@@ -802,7 +802,7 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
     const int rc = t->d_idx.alloc(nullptr, n_pick);
     if (rc) return rc;
   }
-  SFM_HIP(hipMemcpyAsync(t->d_idx, idx.data(), (size_t)n_pick * sizeof(uint32_t), hipMemcpyHostToDevice, t->s));
+  SFM_RC(t->d_idx.upload(idx.data(), n_pick, t->s));
   hipLaunchKernelGGL(k_tb_gather8, dim3((n_pick * t->dim + 255) / 256), dim3(256), 0, t->s,
                      (const uint8_t *)akaze_desc_dev(a), (const uint32_t *)t->d_idx, n_pick, t->dim, dst);
   SFM_HIP(hipGetLastError());
@@ -818,7 +818,7 @@ int sfmloc_bowtrain_read(sfmloc_bowtrain *p, float *rows, uint64_t cap_floats) {
   const uint64_t need = (uint64_t)t->n * t->dim;
   SFM_CHECK(cap_floats >= need, SFMLOC_ECAP, "sfmloc_bowtrain_read: %llu floats needed", (unsigned long long)need);
   SFM_HIP(hipSetDevice(t->device));
-  if (need) SFM_HIP(hipMemcpyAsync(rows, t->d_x, need * sizeof(float), hipMemcpyDeviceToHost, t->s));
+  if (need) SFM_RC(t->d_x.download(rows, need, t->s));
   SFM_HIP(hipStreamSynchronize(t->s));
   return SFMLOC_OK;
 }
@@ -869,9 +869,9 @@ int sfmloc_bowtrain_project(sfmloc_bowtrain *p, const sfmloc_bof_desc *pca) {
     if (!g.ok()) return g.rc();
     g.commit();
   }
-  SFM_HIP(hipMemcpyAsync(t->d_pmean, pca->pca_mean, in_dim * sizeof(float), hipMemcpyHostToDevice, t->s));
-  SFM_HIP(hipMemcpyAsync(t->d_pevec, pca->pca_eigvec, (size_t)np * in_dim * sizeof(float), hipMemcpyHostToDevice, t->s));
-  SFM_HIP(hipMemcpyAsync(t->d_peval, pca->pca_eigval, np * sizeof(float), hipMemcpyHostToDevice, t->s));
+  SFM_RC(t->d_pmean.upload(pca->pca_mean, in_dim, t->s));
+  SFM_RC(t->d_pevec.upload(pca->pca_eigvec, (size_t)np * in_dim, t->s));
+  SFM_RC(t->d_peval.upload(pca->pca_eigval, np, t->s));
   const uint64_t total = (uint64_t)t->n * np;
   if (total)
     hipLaunchKernelGGL(k_tb_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, t->s, (const float *)t->d_x, t->n,

@@ -303,7 +303,7 @@ int triangulate_run(Sfm &h, const sfmloc_triangulate_options &opt, sfmloc_triang
   double ms = 0.0;
   if ((rc = d.open(true, &ms, s)) || (rc = d.time_begin())) return rc;
   unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-  SFM_HIP(hipMemsetAsync(d_cnt, 0, sizeof cnt, s));
+  SFM_RC(d_cnt.zero(6, s));
   TriArgs A;
   static_cast<SfmDev &>(A) = sfm_dev(h, true);  // (this call makes the masks)
   A.mode = opt.mode;
@@ -327,7 +327,7 @@ int triangulate_run(Sfm &h, const sfmloc_triangulate_options &opt, sfmloc_triang
   }
   SFM_HIP(hipGetLastError());
   if ((rc = d.time_end())) return rc;
-  SFM_HIP(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+  SFM_RC(d_cnt.download(cnt, 6, s));
   SFM_HIP(hipStreamSynchronize(s));
   if (rep) {
     rep->landmarks_in = h.n_lm;

@@ -264,13 +264,13 @@ extern "C" int sfmloc_undistorter_apply(sfmloc_undistorter *handle, const uint8_
     g.add(u->d_frac, n);
     if (!g.ok()) return g.rc();
     g.commit();
-    SFM_HIP(hipMemcpyAsync(u->d_xy, u->h_xy.data(), n * sizeof(short2), hipMemcpyHostToDevice, u->stream));
-    SFM_HIP(hipMemcpyAsync(u->d_frac, u->h_frac.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, u->stream));
+    SFM_RC(u->d_xy.upload(u->h_xy.data(), n, u->stream));
+    SFM_RC(u->d_frac.upload(u->h_frac.data(), n, u->stream));
   }
   int rc;
   if (u->d_src.bytes() < n_src && (rc = u->d_src.alloc(nullptr, n_src))) return rc;
   if (u->d_dst.bytes() < n_dst && (rc = u->d_dst.alloc(nullptr, n_dst))) return rc;
-  SFM_HIP(hipMemcpyAsync(u->d_src, src, n_src, hipMemcpyHostToDevice, u->stream));
+  SFM_RC(u->d_src.upload(src, n_src, u->stream));
   const dim3 grid((u->roi[2] + 63) / 64, (u->roi[3] + 3) / 4), block(256);
   if (channels == 3)
     hipLaunchKernelGGL(k_undistort_remap<3>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy, u->d_frac,
@@ -279,7 +279,7 @@ extern "C" int sfmloc_undistorter_apply(sfmloc_undistorter *handle, const uint8_
     hipLaunchKernelGGL(k_undistort_remap<1>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy, u->d_frac,
                        u->roi[0], u->roi[1], u->roi[2], u->roi[3], u->d_dst);
   SFM_HIP(hipGetLastError());
-  SFM_HIP(hipMemcpyAsync(dst, u->d_dst, n_dst, hipMemcpyDeviceToHost, u->stream));
+  SFM_RC(u->d_dst.download(dst, n_dst, u->stream));
   SFM_HIP(hipStreamSynchronize(u->stream));
   return SFMLOC_OK;
 }

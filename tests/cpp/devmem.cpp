@@ -4,9 +4,13 @@
 // The owners of streams, events and pinned host memory (same header) are checked the same way: their raw functions are
 // counters here, and every raw call -- dev_raw_free included -- leaves a letter in a log, so the order of a struct's
 // destruction reads as a string.
+// Transfers (same header): the two raw functions are memcpy / memset here and leave 'c' (copy) and 'f' (fill) in the log;
+// a null stream adds the wait's 'y', as the library's do.
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -78,6 +82,35 @@ void host_raw_free(void *p) {
   --g_blocks;
   g_log += 'h';
   free(p);
+}
+}  // namespace sfmloc
+
+// transfers: the bytes and the direction of the last raw copy, the byte value of the last raw fill, the last error text
+static size_t g_raw_bytes = 0;
+static int g_raw_kind = -1, g_raw_byte = -1;
+static char g_err[256] = "";
+namespace sfmloc {
+void set_error(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
+int dev_raw_copy(void *dst, const void *src, size_t bytes, CopyKind kind, ihipStream_t *s) {
+  memcpy(dst, src, bytes);
+  g_raw_bytes = bytes;
+  g_raw_kind = (int)kind;
+  g_log += 'c';
+  if (!s) stream_raw_sync(nullptr);
+  return 0;
+}
+int dev_raw_fill(void *dst, int byte, size_t bytes, ihipStream_t *s) {
+  memset(dst, byte, bytes);
+  g_raw_bytes = bytes;
+  g_raw_byte = byte;
+  g_log += 'f';
+  if (!s) stream_raw_sync(nullptr);
+  return 0;
 }
 }  // namespace sfmloc
 
@@ -417,7 +450,160 @@ static void test_pinned_zero_length() {
   CHECK(g_log == "Hh" && g_blocks == 0);
 }
 
+// ---- transfers ----
+
+// (a) upload then download of a DevBuf<double>: n * 8 bytes each way; with an offset the elements outside the span keep
+// their sentinel on both sides
+static void test_transfer_round_trip() {
+  Stream st;
+  CHECK(st.create() == 0);
+  DevBuf<double> d;
+  CHECK(d.alloc(nullptr, 6) == 0 && d.size() == 6);
+  for (int i = 0; i < 6; ++i) d.get()[i] = -1.0;  // (the "device" array is host memory here)
+  const double src[3] = {1.5, 2.5, 3.5};
+  g_log.clear();
+  CHECK(d.upload(src, 3, st) == 0);
+  CHECK(g_log == "c" && g_raw_bytes == 24 && g_raw_kind == (int)CopyKind::kHostToDevice);
+  CHECK(d.get()[0] == 1.5 && d.get()[2] == 3.5 && d.get()[3] == -1.0);
+  CHECK(d.upload(src, 2, st, 4) == 0 && g_raw_bytes == 16);
+  CHECK(d.get()[3] == -1.0 && d.get()[4] == 1.5 && d.get()[5] == 2.5);
+  double back[5] = {-7.0, -7.0, -7.0, -7.0, -7.0};
+  CHECK(d.download(back + 1, 3, st, 2) == 0);
+  CHECK(g_log == "ccc" && g_raw_bytes == 24 && g_raw_kind == (int)CopyKind::kDeviceToHost);
+  CHECK(back[0] == -7.0 && back[1] == 3.5 && back[2] == -1.0 && back[3] == 1.5 && back[4] == -7.0);
+  DevBuf<double> e;
+  CHECK(e.alloc(nullptr, 2) == 0);
+  CHECK(e.copy_from(d.get() + 4, 2, st) == 0 && g_raw_kind == (int)CopyKind::kDeviceToDevice && g_raw_bytes == 16);
+  CHECK(e.get()[0] == 1.5 && e.get()[1] == 2.5);
+}
+
+// (b) whole-buffer zero and fill(0xFF) of 1 and of 3 elements
+static void test_transfer_fill() {
+  Stream st;
+  CHECK(st.create() == 0);
+  const size_t sizes[2] = {1, 3};
+  for (size_t n : sizes) {
+    DevBuf<uint64_t> d;
+    CHECK(d.alloc(nullptr, n) == 0);
+    for (size_t i = 0; i < n; ++i) d.get()[i] = 0x1234;
+    g_log.clear();
+    CHECK(d.zero(st) == 0 && g_log == "f" && g_raw_bytes == 8 * n && g_raw_byte == 0);
+    for (size_t i = 0; i < n; ++i) CHECK(d.get()[i] == 0);
+    CHECK(d.fill(0xFF, st) == 0 && g_log == "ff" && g_raw_bytes == 8 * n && g_raw_byte == 0xFF);
+    for (size_t i = 0; i < n; ++i) CHECK(d.get()[i] == ~0ull);
+  }
+  DevBuf<uint64_t> d;
+  CHECK(d.alloc(nullptr, 3) == 0);
+  CHECK(d.fill(0xFF, st) == 0 && d.zero(1, st, 1) == 0 && g_raw_bytes == 8);  // one element in the middle
+  CHECK(d.get()[0] == ~0ull && d.get()[1] == 0 && d.get()[2] == ~0ull);
+}
+
+// (c) an owned buffer refuses a span outside it: nothing issued, the array unchanged, both numbers in the text.
+// An offset beyond the array is refused for zero elements too (decided here: such an offset is a bug whatever the count).
+static void test_transfer_bounds() {
+  Stream st;
+  CHECK(st.create() == 0);
+  DevBuf<uint32_t> d;
+  CHECK(d.alloc(nullptr, 4) == 0);
+  for (int i = 0; i < 4; ++i) d.get()[i] = 9;
+  const uint32_t src[5] = {1, 2, 3, 4, 5};
+  uint32_t back[5] = {0, 0, 0, 0, 0};
+  g_log.clear();
+  CHECK(d.upload(src, 1, st, 3) == 0 && g_log == "c" && d.get()[3] == 1);  // offset + n == size
+  d.get()[3] = 9;
+  g_log.clear();
+  g_err[0] = 0;
+  CHECK(d.upload(src, 5, st) == SFMLOC_EINVAL && g_log.empty());  // size + 1
+  CHECK(strstr(g_err, "5 elements") && strstr(g_err, "array of 4"));
+  CHECK(d.upload(src, 2, st, 3) == SFMLOC_EINVAL && d.download(back, 5, st) == SFMLOC_EINVAL);
+  CHECK(d.zero(5, st) == SFMLOC_EINVAL && d.fill(0xFF, 1, st, 4) == SFMLOC_EINVAL && d.read(back, 5, st) == SFMLOC_EINVAL);
+  CHECK(d.copy_from(d.get(), (size_t)-1, st, 2) == SFMLOC_EINVAL);  // (offset + n wraps around)
+  CHECK(d.upload(src, 0, st, 4) == 0);                 // nothing, at the end: fine
+  CHECK(d.upload(src, 0, st, 5) == SFMLOC_EINVAL);     // nothing, beyond the end: refused
+  CHECK(g_log.empty() && back[0] == 0);
+  for (int i = 0; i < 4; ++i) CHECK(d.get()[i] == 9);
+}
+
+// (d) zero elements: no raw call, no error -- members and free forms, an empty buffer's whole-buffer zero too
+static void test_transfer_nothing() {
+  DevBuf<float> d, empty;
+  CHECK(d.alloc(nullptr, 2) == 0);
+  float h[2] = {1.f, 2.f};
+  g_log.clear();
+  CHECK(d.upload(h, 0, nullptr) == 0 && d.download(h, 0, nullptr) == 0 && d.zero(0, nullptr) == 0 && d.read(h, 0, nullptr) == 0);
+  CHECK(d.copy_from(d.get(), 0, nullptr) == 0 && empty.zero(nullptr) == 0 && empty.fill(0xFF, nullptr) == 0);
+  CHECK(dev_upload(d.get(), h, 0, nullptr) == 0 && dev_download(h, d.get(), 0, nullptr) == 0 && dev_zero(d.get(), 0, nullptr) == 0 &&
+        dev_fill(d.get(), 1, 0, nullptr) == 0 && dev_copy(d.get(), d.get(), 0, nullptr) == 0 && dev_read(h, d.get(), 0, nullptr) == 0);
+  CHECK(g_log.empty());
+}
+
+// (e) the stream argument: a null stream is waited for inside the raw call, a stream is not; the blocking read copies on
+// the named stream and then waits for it
+static void test_transfer_streams() {
+  Stream st;
+  CHECK(st.create() == 0);
+  DevBuf<int32_t> d;
+  CHECK(d.alloc(nullptr, 2) == 0);
+  int32_t h[2] = {4, 5};
+  g_log.clear();
+  CHECK(d.upload(h, 2, nullptr) == 0 && g_log == "cy");
+  CHECK(d.zero(nullptr) == 0 && g_log == "cyfy");
+  CHECK(d.download(h, 2, nullptr) == 0 && g_log == "cyfycy" && h[0] == 0);
+  g_log.clear();
+  CHECK(d.upload(h, 2, st) == 0 && d.zero(st) == 0 && d.download(h, 2, st) == 0 && d.fill(1, st) == 0 && g_log == "cfcf");
+  g_log.clear();
+  CHECK(d.read(h, 2, st) == 0 && g_log == "cy" && h[1] == 0x01010101);
+  g_log.clear();
+  CHECK(dev_read(h, d.get(), 1, st.get()) == 0 && g_log == "cy" && g_raw_bytes == 4);
+}
+
+// (f) a borrowed buffer has no size: it transfers without a bounds refusal
+static void test_transfer_borrowed() {
+  static uint16_t callers[8];
+  DevBuf<uint16_t> b;
+  b.borrow(callers);
+  const uint16_t src[3] = {7, 8, 9};
+  g_log.clear();
+  CHECK(b.upload(src, 3, nullptr, 5) == 0 && g_log == "cy" && g_raw_bytes == 6);
+  CHECK(callers[4] == 0 && callers[5] == 7 && callers[7] == 9);
+  CHECK(b.zero(2, nullptr, 6) == 0 && callers[5] == 7 && callers[6] == 0 && callers[7] == 0);
+}
+
+// (g) the free forms over a T * into a record touch exactly sizeof(member) bytes
+static void test_transfer_record_members() {
+  struct Record {
+    int32_t before;
+    double pose[3];
+    int32_t status;
+    uint32_t stats[3];
+    int32_t after;
+  };
+  Record dev;  // (stands for a record in device memory, as Ctx::d_result)
+  memset(&dev, 0x55, sizeof dev);
+  Stream st;
+  CHECK(st.create() == 0);
+  g_log.clear();
+  CHECK(dev_zero(&dev.status, 1, st.get()) == 0 && g_raw_bytes == sizeof dev.status);
+  CHECK(dev_zero(dev.stats, 3, st.get()) == 0 && g_raw_bytes == sizeof dev.stats);
+  CHECK(dev_fill(dev.pose, 0xFF, 3, st.get()) == 0 && g_raw_bytes == sizeof dev.pose);
+  CHECK(dev.before == 0x55555555 && dev.after == 0x55555555 && dev.status == 0 && dev.stats[0] == 0 && dev.stats[2] == 0);
+  const double one_pose[3] = {1.0, 2.0, 3.0};
+  CHECK(dev_upload(dev.pose, one_pose, 3, st.get()) == 0 && g_raw_bytes == sizeof dev.pose);
+  double back[3] = {0, 0, 0};
+  CHECK(dev_download(back, dev.pose, 3, st.get()) == 0 && back[0] == 1.0 && back[2] == 3.0);
+  int32_t status = -1;
+  CHECK(dev_read(&status, &dev.status, 1, st.get()) == 0 && status == 0 && g_raw_bytes == sizeof dev.status);
+  CHECK(dev.before == 0x55555555 && dev.after == 0x55555555 && g_log == "fffcccy");
+}
+
 int main() {
+  test_transfer_round_trip();
+  test_transfer_fill();
+  test_transfer_bounds();
+  test_transfer_nothing();
+  test_transfer_streams();
+  test_transfer_borrowed();
+  test_transfer_record_members();
   test_owners_release_once();
   test_owner_failed_creation();
   test_borrowed_stream();
