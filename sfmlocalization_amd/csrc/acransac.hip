@@ -2487,7 +2487,7 @@ __global__ __launch_bounds__(64) void k_debug_wave7(const double *in, int n, int
   if (lane < 27) o[1 + lane] = (lane < 9 * nm) ? f : 0.0;
 }
 
-// op 9: wave_sort_fast, one wave per row of P + 1 doubles (P = 64, 128, ... 1024 keys, then n: elements >= n are
+// op 9: wave_sort_fast, one wave per row of P + 1 doubles (P = 64, 128, ... 2048 keys, then n: elements >= n are
 // padding); out[p] = index of the element at sorted position p, out[P + p] = its key as a double
 template <int E>
 __device__ void debug_sort_row(const double *x, double *o, int n, uint32_t *low) {
@@ -2509,7 +2509,7 @@ __device__ void debug_sort_row(const double *x, double *o, int n, uint32_t *low)
   }
 }
 __global__ __launch_bounds__(64) void k_debug_sort(const double *in, int n_rows, int in_stride, double *out, int out_stride) {
-  __shared__ uint32_t low[1024];
+  __shared__ uint32_t low[2048];
   const int i = blockIdx.x;
   if (i >= n_rows) return;
   const double *x = in + (size_t)i * in_stride;
@@ -2522,6 +2522,7 @@ __global__ __launch_bounds__(64) void k_debug_sort(const double *in, int n_rows,
     case 4: debug_sort_row<4>(x, o, n, low); break;
     case 8: debug_sort_row<8>(x, o, n, low); break;
     case 16: debug_sort_row<16>(x, o, n, low); break;
+    case 32: debug_sort_row<32>(x, o, n, low); break;
     default: break;
   }
 }

@@ -40,9 +40,11 @@ def test_f64_primitives_bit_exact(oracle_c):
 
 def test_wave_sort_fast_is_the_exact_order():
     """K3 / K5 sort a model's residuals with the index packed into the key's low bits (acransac.hip wave_sort_fast);
-    the order must be the exact (key bits, index) order in every case, including the ones that force its fallback."""
+    the order must be the exact (key bits, index) order in every case, including the ones that force its fallback.
+    P = 2 048 is the instance that packs 11 index bits (K3's wide 2 048-match form)."""
     rng = np.random.default_rng(77)
-    for P in (64, 128, 256, 512, 1024):
+    rng2 = np.random.default_rng(78)                     # the kinds added with P = 2 048 (the draws above stay as they were)
+    for P in (64, 128, 256, 512, 1024, 2048):
         rows = []
         for case in range(24):
             n = int(rng.integers(1, P + 1)) if case % 3 else P
@@ -58,6 +60,24 @@ def test_wave_sort_fast_is_the_exact_order():
                 v[rng.integers(0, P, 5)] = 0.0
                 v[rng.integers(0, P, 5)] = np.inf
             rows.append(np.concatenate([v, [float(n)]]))
+        for case in range(6):      # keys that agree above bit 10 and in the ten bits below it: only bit 10 differs.  Up to
+            # P = 1 024 it is a kept bit and must order the keys; at 2 048 the index displaces it, the fallback restores it
+            n = int(rng2.integers(P // 2, P + 1)) if case % 2 else P
+            v = rng2.random(P) * 10.0 ** rng2.integers(-12, 6)
+            share = rng2.permutation(P)[:P // 2 if case < 4 else P]
+            base = v[share[:1 + case]].view(np.uint64) & ~np.uint64(2047)     # 1 .. 6 values the keys gather on
+            bit10 = rng2.integers(0, 2, len(share)).astype(np.uint64) << np.uint64(10)
+            key = base[rng2.integers(0, len(base), len(share))] | bit10
+            v[share] = key.view(np.float64)
+            rows.append(np.concatenate([v, [float(n)]]))
+        for r in sorted({1, P // 128, P // 64 - 1} & set(range(1, P // 64))):
+            # ascending keys whose one descent, in the displaced bits, lies across lane rows r - 1 | r (prev_last)
+            v = np.sort(rng2.random(P) * 1e3)
+            k = v.view(np.uint64)
+            k[64 * r - 1] = (k[64 * r - 1] & ~np.uint64(2047)) | np.uint64(1)
+            k[64 * r] = k[64 * r - 1] & ~np.uint64(2047)
+            assert k[64 * r - 2] < k[64 * r] and k[64 * r - 1] < k[64 * r + 1]
+            rows.append(np.concatenate([v, [float(P)]]))
         x = np.array(rows)
         got = S.debug_math(9, x, 2 * P)
         for row, out in zip(x, got):
