@@ -2553,23 +2553,20 @@ __global__ __launch_bounds__(64) void k_debug_resect6(const double *in, int n, i
 // launchers
 // ---------------------------------------------------------------------------------------------------
 int launch_fill_log10(double *d_L10, int n, hipStream_t s) {
-  hipLaunchKernelGGL(k_fill_log10, dim3((n + 255) / 256), dim3(256), 0, s, d_L10, n);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return dev_launch(k_fill_log10, dim3((n + 255) / 256), dim3(256), 0, s, d_L10, n);
 }
 
 int launch_debug_math(int op, const double *d_in, int n, int in_stride, double *d_out, int out_stride,
                       hipStream_t s) {
   if (op == 8)
-    hipLaunchKernelGGL(k_debug_wave7, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride);
+    SFM_RC(dev_launch(k_debug_wave7, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride));
   else if (op == 9)
-    hipLaunchKernelGGL(k_debug_sort, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride);
+    SFM_RC(dev_launch(k_debug_sort, dim3(n), dim3(64), 0, s, d_in, n, in_stride, d_out, out_stride));
   else if (op == 11)
-    hipLaunchKernelGGL(k_debug_resect6, dim3((n + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, d_in, n, in_stride, d_out,
-                       out_stride);
+    SFM_RC(dev_launch(k_debug_resect6, dim3((n + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, d_in, n, in_stride,
+                      d_out, out_stride));
   else
-    hipLaunchKernelGGL(k_debug_math, dim3((n + 63) / 64), dim3(64), 0, s, op, d_in, n, in_stride, d_out, out_stride);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_debug_math, dim3((n + 63) / 64), dim3(64), 0, s, op, d_in, n, in_stride, d_out, out_stride));
   return SFMLOC_OK;
 }
 
@@ -2658,17 +2655,14 @@ static int k3_pack(Ctx *c, const FFilterArgs &A, FFilterArgsPacked *P) {
 
 // one launch of k_fmatrix_fast<W, MaxM, kWide>: a workgroup per view, or (wide) per view and iteration of its first batch
 template <int W, int MaxM, bool kWide>
-static hipError_t launch_fmatrix_fast(Ctx *c, const FFilterArgs &A, int wide_b0) {
+static int launch_fmatrix_fast(Ctx *c, const FFilterArgs &A, int wide_b0) {
   using Sh = F2SharedT<W, MaxM>;
   static_assert(sizeof(Sh) <= 160 * 1024, "a workgroup's lists must fit a compute unit's LDS (160 KiB on gfx950)");
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_fast<W, MaxM, kWide>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Sh));
-  if (attr != hipSuccess) return attr;
   FFilterArgsPacked P;
-  if (k3_pack(c, A, &P) != SFMLOC_OK) return hipErrorOutOfMemory;
-  sfm_launch<FmatrixFastBody<W, MaxM, kWide>>(c, k_fmatrix_fast<W, MaxM, kWide>, dim3(A.n_sel, (unsigned)wide_b0),
-                                              dim3(W * 64), (uint32_t)sizeof(Sh), P);
-  return hipSuccess;
+  SFM_RC(k3_pack(c, A, &P));
+  return sfm_launch<FmatrixFastBody<W, MaxM, kWide>>(c, k_fmatrix_fast<W, MaxM, kWide>,
+                                                     dim3(A.n_sel, (unsigned)wide_b0), dim3(W * 64),
+                                                     (uint32_t)sizeof(Sh), P);
 }
 
 int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_sel, bool all_views, int min_putative) {
@@ -2744,39 +2738,26 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     }
     A.spec = reinterpret_cast<K3Spec *>(c->d_k3_spec.get());
     A.spec_arrive = c->d_k3_arrive;
-    const hipError_t e = P.max_m == kF2HugeM ? launch_fmatrix_fast<4, kF2HugeM, true>(c, A, P.wide_b0)
-                         : P.wide_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, true>(c, A, P.wide_b0)
-                                             : launch_fmatrix_fast<4, kF2BigM, true>(c, A, P.wide_b0);
-    SFM_HIP(e);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(P.max_m == kF2HugeM ? launch_fmatrix_fast<4, kF2HugeM, true>(c, A, P.wide_b0)
+           : P.wide_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, true>(c, A, P.wide_b0)
+                               : launch_fmatrix_fast<4, kF2BigM, true>(c, A, P.wide_b0));
   } else {
-    const hipError_t e = P.waves == 16  ? launch_fmatrix_fast<16, kF2MaxM, false>(c, A, 1)
-                         : P.waves == 4 ? launch_fmatrix_fast<4, kF2MaxM, false>(c, A, 1)
-                                        : launch_fmatrix_fast<8, kF2MaxM, false>(c, A, 1);
-    SFM_HIP(e);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(P.waves == 16  ? launch_fmatrix_fast<16, kF2MaxM, false>(c, A, 1)
+           : P.waves == 4 ? launch_fmatrix_fast<4, kF2MaxM, false>(c, A, 1)
+                          : launch_fmatrix_fast<8, kF2MaxM, false>(c, A, 1));
     if (P.big) {
       FFilterArgs B = A;
       B.merge.enabled = 0;  // (the lists exist: the launch above built them)
       B.fast_min = kF2MaxM;
-      const hipError_t eb = P.big_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, false>(c, B, 1)
-                                             : launch_fmatrix_fast<4, kF2BigM, false>(c, B, 1);
-      SFM_HIP(eb);
-      SFM_HIP(hipGetLastError());
+      SFM_RC(P.big_waves == 8 ? launch_fmatrix_fast<8, kF2BigM, false>(c, B, 1)
+                              : launch_fmatrix_fast<4, kF2BigM, false>(c, B, 1));
     }
   }
   const size_t lds = sizeof(FShared);
-  static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fmatrix_filter),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FShared));
-  SFM_HIP(attr1);
   A.merge.enabled = 0;  // (the lists exist by now)
   FFilterArgsPacked PF;
-  {
-    int rc = k3_pack(c, A, &PF);
-    if (rc) return rc;
-  }
-  sfm_launch<FmatrixFilterBody>(c, k_fmatrix_filter, dim3(n_sel), dim3(kThreads), (uint32_t)lds, PF);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(k3_pack(c, A, &PF));
+  SFM_RC(sfm_launch<FmatrixFilterBody>(c, k_fmatrix_filter, dim3(n_sel), dim3(kThreads), (uint32_t)lds, PF));
   if (A.large_list) {  // some view of this map can have more than kFMaxM matches: the queue's consumer
     FLargeArgs W;
     W.key = c->fl_key;
@@ -2786,8 +2767,7 @@ int launch_fmatrix_filter(Ctx *c, const Query *q, QueryPass &pass, uint32_t n_se
     W.logc_n = c->fl_logc_n;
     W.logc_k = c->fl_logc_k;
     W.slot_m = c->fl_slot_m;
-    sfm_launch<FmatrixLargeBody>(c, k_fmatrix_large, dim3(kFLargeSlots), dim3(kThreads), 0, PF, W);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<FmatrixLargeBody>(c, k_fmatrix_large, dim3(kFLargeSlots), dim3(kThreads), 0, PF, W));
   }
   return SFMLOC_OK;
 }
@@ -2858,9 +2838,7 @@ int launch_p3p_init(Ctx *c) {
     return SFMLOC_OK;
   }
   P3pArgs A = make_p3p_args(c, k5_in(c));
-  sfm_launch<P3pInitBody>(c, k_p3p_init, dim3(1), dim3(kThreads), 0, A);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<P3pInitBody>(c, k_p3p_init, dim3(1), dim3(kThreads), 0, A);
 }
 
 // Which launch form the P3P rounds went out in (sfmloc_debug_k5_round_counts): small, plain, wide.  Host side, one
@@ -2873,40 +2851,31 @@ int launch_p3p_round(Ctx *c, int batch) {
   const size_t lds = sizeof(P3pShared);
   constexpr size_t lds_small = std::max(offsetof(P3pShared, idx) + 4 * kP3pSmallN * sizeof(uint32_t), sizeof(P3pReplayShared));
   static_assert(sizeof(P3pReplayShared) <= sizeof(P3pShared), "the replay reuses the round's LDS");
-  // (a function-local static with an initialiser: set once, safely, whichever host thread gets here first)
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p3p_round),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
-  SFM_HIP(attr);
   const K5RoundPlan P = plan_k5_round(in, batch, knobs());
   if (P.six_point) {
     // an uncalibrated query (never in a gang session: capi.hip refuses): its round's models first, sixteen hypotheses
     // per wave, then the round
-    static const hipError_t attr6 = hipFuncSetAttribute(reinterpret_cast<const void *>(k_resect6_round),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(P3pShared));
-    SFM_HIP(attr6);
     hipStream_t s = (hipStream_t)c->stream;
-    hipLaunchKernelGGL(k_resect6_prepare, dim3((P.batch + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, A, P.batch);
+    SFM_RC(dev_launch(k_resect6_prepare, dim3((P.batch + kR6PerWave - 1) / kR6PerWave), dim3(64), 0, s, A, P.batch));
     if (P.form == K5Form::kSmall)
-      hipLaunchKernelGGL(k_resect6_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, s, A, P.batch, 0);
+      SFM_RC(dev_launch(k_resect6_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, s, A, P.batch, 0));
     else
-      hipLaunchKernelGGL(k_resect6_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, s, A, P.batch, 0);
+      SFM_RC(dev_launch(k_resect6_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, s, A, P.batch, 0));
   } else if (P.form == K5Form::kSmall) {
     g_k5_round_counts[0].fetch_add(1, std::memory_order_relaxed);
-    sfm_launch<P3pRoundSmallBody>(c, k_p3p_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, A, P.batch, 0);
+    SFM_RC(sfm_launch<P3pRoundSmallBody>(c, k_p3p_round_small, dim3(P.grid), dim3(kThreads), (uint32_t)lds_small, A,
+                                         P.batch, 0));
   } else {  // either launch shape gives the same bits
     g_k5_round_counts[P.form == K5Form::kWide ? 2 : 1].fetch_add(1, std::memory_order_relaxed);
-    sfm_launch<P3pRoundBody>(c, k_p3p_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, A, P.batch,
-                             P.form == K5Form::kWide ? 1 : 0);
+    SFM_RC(sfm_launch<P3pRoundBody>(c, k_p3p_round, dim3(P.grid), dim3(kThreads), (uint32_t)lds, A, P.batch,
+                                    P.form == K5Form::kWide ? 1 : 0));
   }
-  SFM_HIP(hipGetLastError());
   return SFMLOC_OK;
 }
 
 int launch_p3p_finish(Ctx *c) {
   P3pArgs A = make_p3p_args(c, k5_in(c));
-  sfm_launch<P3pFinishBody>(c, k_p3p_finish, dim3(1), dim3(kThreads), 0, A);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<P3pFinishBody>(c, k_p3p_finish, dim3(1), dim3(kThreads), 0, A);
 }
 
 

@@ -204,19 +204,19 @@ int sfm_transpose(Sfm *h) {
   const uint32_t n = (uint32_t)h->n_obs;
   hipStream_t s = h->s;
   if (h->n_lm)
-    hipLaunchKernelGGL(k_adj_obs_landmark, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->d_obs_off, h->n_lm,
-                       h->d_obs_lm, h->d_vlist);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_adj_obs_landmark, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->d_obs_off, h->n_lm,
+                      h->d_obs_lm, h->d_vlist));
   if (n) SFM_RC(h->d_vkey.copy_from(h->d_obs_view, n, s));
   // (an odd number of passes leaves the result in the scratch pair)
-  if (radix_sort_pairs(h->d_vkey, h->d_vlist, h->d_tmp_k, h->d_tmp_v, n, radix_key_bits(h->n_views - 1), h->d_hist, s)) {
+  bool swapped = false;
+  SFM_RC(radix_sort_pairs(h->d_vkey, h->d_vlist, h->d_tmp_k, h->d_tmp_v, n, radix_key_bits(h->n_views - 1), h->d_hist, s,
+                          &swapped));
+  if (swapped) {
     std::swap(h->d_vkey, h->d_tmp_k);
     std::swap(h->d_vlist, h->d_tmp_v);
   }
-  SFM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_adj_view_off, dim3((h->n_views + 1 + 255) / 256), dim3(256), 0, s, h->d_vkey, n, h->n_views,
-                     h->d_view_off);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_adj_view_off, dim3((h->n_views + 1 + 255) / 256), dim3(256), 0, s, h->d_vkey, n, h->n_views,
+                    h->d_view_off));
   h->h_view_off.assign((size_t)h->n_views + 1, 0);
   SFM_RC(h->d_view_off.download(h->h_view_off.data(), (size_t)h->n_views + 1, s));
   SFM_HIP(hipStreamSynchronize(s));
@@ -406,18 +406,15 @@ int sfm_clean_impl(Sfm *h, double residual_px, double angle_deg, int rm_unstable
   const int again = h->cleaned ? 1 : 0;  // a later cleanup works on what the earlier ones kept
   hipStream_t s = h->s;
   if (h->n_obs)
-    hipLaunchKernelGGL(k_adj_residual, dim3((unsigned)((h->n_obs + 255) / 256)), dim3(256), 0, s, h->n_obs, h->d_obs_lm,
-                       h->d_obs_view, h->d_obs_x, h->d_lm_X, h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,
-                       h->d_pose_R, h->d_pose_C, residual_px, again, h->d_res, h->d_ray, h->d_obs_keep);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_adj_residual, dim3((unsigned)((h->n_obs + 255) / 256)), dim3(256), 0, s, h->n_obs, h->d_obs_lm,
+                      h->d_obs_view, h->d_obs_x, h->d_lm_X, h->d_view_intr, h->d_view_pose, h->d_intr_type, h->d_intr,
+                      h->d_pose_R, h->d_pose_C, residual_px, again, h->d_res, h->d_ray, h->d_obs_keep));
   if (h->n_lm)
-    hipLaunchKernelGGL(k_adj_landmarks, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->n_lm, h->d_obs_off,
-                       h->d_obs_keep, h->d_ray, angle_deg, again, h->d_mincos, h->d_lm_stage);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_adj_landmarks, dim3((h->n_lm + 255) / 256), dim3(256), 0, s, h->n_lm, h->d_obs_off,
+                      h->d_obs_keep, h->d_ray, angle_deg, again, h->d_mincos, h->d_lm_stage));
   if (rm_unstable) {
-    hipLaunchKernelGGL(k_adj_unstable, dim3(1), dim3(1024), 0, s, h->n_lm, h->d_obs_off, h->d_obs_view, h->d_view_pose,
-                       h->n_poses, h->d_pose_valid, h->d_pose_cnt, h->d_obs_keep, h->d_lm_stage, 6u, 2u, h->d_passes);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_adj_unstable, dim3(1), dim3(1024), 0, s, h->n_lm, h->d_obs_off, h->d_obs_view, h->d_view_pose,
+                      h->n_poses, h->d_pose_valid, h->d_pose_cnt, h->d_obs_keep, h->d_lm_stage, 6u, 2u, h->d_passes));
   }
   std::vector<uint8_t> stage(h->n_lm);
   if (h->n_lm) SFM_RC(h->d_lm_stage.download(stage.data(), h->n_lm, s));

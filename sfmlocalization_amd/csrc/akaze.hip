@@ -1883,7 +1883,6 @@ static double now_s() {
 }
 
 struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue on now; an extractor can record for a gang)
-  int device = 0;
   int w = 0, h = 0, omax = 4, nsub = 4;
   float thres = 0.001f;
   AkPlan plan;
@@ -1931,15 +1930,6 @@ struct Akaze : GangMember {  // (gang.h: `stream` reads as the stream to queue o
 
 namespace {
 
-#define AK_HIP(x)                                                              \
-  do {                                                                         \
-    hipError_t e_ = (x);                                                       \
-    if (e_ != hipSuccess) {                                                    \
-      set_error("%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
-      return e_ == hipErrorOutOfMemory ? SFMLOC_ENOMEM : SFMLOC_EHIP;          \
-    }                                                                          \
-  } while (0)
-
 dim3 grid2(int w, int h) { return dim3((w + 127) / 128, h); }
 
 LevelTab level_tab(const Akaze *a) {
@@ -1984,11 +1974,14 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
     Taps2 t2;
     for (int k = 0; k < 9; ++k) t2.k9[k] = P.g16[k];
     for (int k = 0; k < 5; ++k) t2.k5[k] = P.g10[k];
-    sfm_launch<PreRowsBody>(a, k_pre_rows, grid2(w, h), dim3(128), (uint32_t)0, a->d_gray, a->d_t3, a->d_t1, w, h, t2, a->d_hist);
-    sfm_launch<PreColsBody>(a, k_pre_cols, grid2(w, h), dim3(128), (uint32_t)0, a->d_t3, a->d_t1, a->d_Lt, a->d_Lsmooth, a->d_t0, w, h, t2);
-    sfm_launch<PreGradBody>(a, k_pre_grad, dim3(D.hist_grid_x, D.grad_grid_y), dim3(128), (uint32_t)0, a->d_t0, a->d_t2, w, h, a->d_hist);
-    sfm_launch<PreHistBody>(a, k_pre_hist, dim3(D.hist_grid_x, D.hist_grid_y), dim3(128), (uint32_t)0, a->d_t2, w, h, a->d_hist, a->d_kcontrast);
-    AK_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<PreRowsBody>(a, k_pre_rows, grid2(w, h), dim3(128), (uint32_t)0, a->d_gray, a->d_t3, a->d_t1, w,
+                                   h, t2, a->d_hist));
+    SFM_RC(sfm_launch<PreColsBody>(a, k_pre_cols, grid2(w, h), dim3(128), (uint32_t)0, a->d_t3, a->d_t1, a->d_Lt,
+                                   a->d_Lsmooth, a->d_t0, w, h, t2));
+    SFM_RC(sfm_launch<PreGradBody>(a, k_pre_grad, dim3(D.hist_grid_x, D.grad_grid_y), dim3(128), (uint32_t)0, a->d_t0,
+                                   a->d_t2, w, h, a->d_hist));
+    SFM_RC(sfm_launch<PreHistBody>(a, k_pre_hist, dim3(D.hist_grid_x, D.hist_grid_y), dim3(128), (uint32_t)0, a->d_t2,
+                                   w, h, a->d_hist, a->d_kcontrast));
   }
   Taps t5;
   for (int k = 0; k < 9; ++k) t5.k[k] = k < 5 ? P.g10[k] : 0.0f;
@@ -2001,7 +1994,8 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
     float *Lt = a->d_Lt + L.off, *prev = a->d_Lt + Lp.off;
     float *start = E.source == kPrevLt ? prev : (E.source == kOwnLt ? Lt : (float *)a->d_t3);
     if (E.halfsample)
-      sfm_launch<HalfsampleBody>(a, k_halfsample, grid2(L.w, L.h), dim3(128), (uint32_t)0, prev, Lp.w, Lp.h, start, L.w, L.h);
+      SFM_RC(sfm_launch<HalfsampleBody>(a, k_halfsample, grid2(L.w, L.h), dim3(128), (uint32_t)0, prev, Lp.w, Lp.h,
+                                        start, L.w, L.h));
     if (E.resident) {  // the levels first .. last of the octave in one launch (k_octave_resident)
       OctaveRun R{};
       R.n_levels = E.last - E.first + 1;
@@ -2013,13 +2007,9 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
         R.nsteps[q - E.first] = P.lev[q].nsteps;
         R.step0[q - E.first] = q * kMaxFedSteps;
       }
-      // (a function-local static with an initialiser: set once, safely, whichever host thread gets here first)
-      static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_octave_resident),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResidentLdsBytes);
-      AK_HIP(attr);
-      sfm_launch<OctaveResidentBody>(a, k_octave_resident, dim3(1), dim3(1024), (uint32_t)((size_t)3 * L.w * L.h * sizeof(float)),
-                                     start, a->d_Lt, a->d_Lsmooth, t5, a->d_kcontrast, a->d_half_steps, R);
-      AK_HIP(hipGetLastError());
+      SFM_RC(sfm_launch<OctaveResidentBody>(a, k_octave_resident, dim3(1), dim3(1024),
+                                            (uint32_t)((size_t)3 * L.w * L.h * sizeof(float)), start, a->d_Lt,
+                                            a->d_Lsmooth, t5, a->d_kcontrast, a->d_half_steps, R));
       continue;
     }
     // a single level: its FED steps ping-pong between the level's Lt and a scratch image so that the last launch lands
@@ -2033,11 +2023,11 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
       for (int k = 0; k < kNldStepSlots; ++k) hs.half_step[k] = k < n ? 0.5f * L.tsteps[st + k] : 0.0f;
 #define SNLD_CASE(KK)                                                                                                  \
   case KK:                                                                                                             \
-    sfm_launch<SmoothNldBody<KK>>(a, k_smooth_nld<KK>, tgrid, dim3(256), 0, cur, a->d_Lsmooth + L.off, a->d_t2, dst, L.w, L.h, t5, \
-                       a->d_kcontrast, L.octave, hs, n);                                                               \
+    SFM_RC(sfm_launch<SmoothNldBody<KK>>(a, k_smooth_nld<KK>, tgrid, dim3(256), 0, cur, a->d_Lsmooth + L.off, a->d_t2, \
+                                         dst, L.w, L.h, t5, a->d_kcontrast, L.octave, hs, n));                         \
     break;
 #define NLD_CASE(KK) \
-  case KK: sfm_launch<NldStepsBody<KK>>(a, k_nld_steps<KK>, tgrid, dim3(256), 0, cur, a->d_t2, dst, L.w, L.h, hs, n); break;
+  case KK: SFM_RC(sfm_launch<NldStepsBody<KK>>(a, k_nld_steps<KK>, tgrid, dim3(256), 0, cur, a->d_t2, dst, L.w, L.h, hs, n)); break;
       static_assert(kNldFuseMax == 8, "one case per K up to kNldFuseMax");
       if (j == 0) {
         switch (n) { SNLD_CASE(1) SNLD_CASE(2) SNLD_CASE(3) SNLD_CASE(4) SNLD_CASE(5) SNLD_CASE(6) SNLD_CASE(7) SNLD_CASE(8) }
@@ -2048,15 +2038,15 @@ int build_scale_space(Akaze *a, const uint8_t *gray /*host; null: the image is a
 #undef NLD_CASE
       cur = dst;
     }
-    AK_HIP(hipGetLastError());
   }
   // (the rows of the levels that were built: levels come in order; kAllPix pixels of a row per thread)
   const LevelTab T = level_tab(a);
   const dim3 agrid(((a->w + 127) / 128 + kAllPix - 1) / kAllPix, T.row0[levels_built(P, need)]);
-  sfm_launch<ScharrXyAllBody>(a, k_scharr_xy_all, agrid, dim3(128), (uint32_t)0, a->d_Lsmooth, a->d_Lx, a->d_Ly, (const LevelTab *)a->d_level_tab);
+  SFM_RC(sfm_launch<ScharrXyAllBody>(a, k_scharr_xy_all, agrid, dim3(128), (uint32_t)0, a->d_Lsmooth, a->d_Lx, a->d_Ly,
+                                     a->d_level_tab));
   if (with_det)
-    sfm_launch<HessianDetAllBody>(a, k_hessian_det_all, agrid, dim3(128), (uint32_t)0, a->d_Lx, a->d_Ly, a->d_Ldet, (const LevelTab *)a->d_level_tab);
-  AK_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<HessianDetAllBody>(a, k_hessian_det_all, agrid, dim3(128), (uint32_t)0, a->d_Lx, a->d_Ly,
+                                         a->d_Ldet, a->d_level_tab));
   return SFMLOC_OK;
 }
 
@@ -2104,12 +2094,9 @@ int orient_describe_enqueue(Akaze *a, const std::vector<float> &kin, unsigned in
   if (phase != 2) {
     // (the keypoints go up ahead of anything recorded: nothing recorded for this extractor in the session reads d_kp)
     if (n) SFM_RC(a->d_kp.upload(kin.data(), (size_t)n * 4, a->stream.unordered()));
-    sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(grid_n), dim3(64), 0,
-                                   (const DevLevels *)a->d_dev_levels, a->d_kp, (int)n, a->d_gauss25, a->d_win,
-                                   a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
-                                   (const unsigned int *)nullptr, (const float *)nullptr, (float *)nullptr,
-                                   (float2 *)nullptr, (float2 *)nullptr);
-    AK_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(grid_n), dim3(64), 0, a->d_dev_levels, a->d_kp,
+                                          (int)n, a->d_gauss25, a->d_win, a->plan.n_win, a->d_pair, a->d_angle,
+                                          a->d_desc, nullptr, nullptr, nullptr, nullptr, nullptr));
   }
   if (phase != 1 && n) {
     if (angle_out) SFM_RC(a->d_angle.download(angle_out, n, a->stream));
@@ -2121,7 +2108,7 @@ int orient_describe_enqueue(Akaze *a, const std::vector<float> &kin, unsigned in
 int orient_describe(Akaze *a, const std::vector<float> &kin, unsigned int n, float *angle_out, uint8_t *desc64) {
   int rc = orient_describe_enqueue(a, kin, n, angle_out, desc64, 0);
   if (rc) return rc;
-  AK_HIP(hipStreamSynchronize(a->stream));
+  SFM_HIP(hipStreamSynchronize(a->stream));
   return SFMLOC_OK;
 }
 
@@ -2154,13 +2141,9 @@ int akaze_compute_resident(Akaze *a, const float *d_kin, unsigned int n, int nee
   if (rc) return rc;
   rc = build_scale_space(a, nullptr, need_levels, false);
   if (rc || n == 0) return rc;
-  sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(n), dim3(64), 0,
-                                 (const DevLevels *)a->d_dev_levels, d_kin, (int)n, a->d_gauss25, a->d_win,
-                                 a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
-                                   (const unsigned int *)nullptr, (const float *)nullptr, (float *)nullptr,
-                                   (float2 *)nullptr, (float2 *)nullptr);
-  AK_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(n), dim3(64), 0, a->d_dev_levels, d_kin, (int)n,
+                                        a->d_gauss25, a->d_win, a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
+                                        nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 }  // namespace sfmloc
@@ -2250,10 +2233,6 @@ int sfmloc_akaze_create(int device, int width, int height, int n_octaves, int n_
     SFM_RC(a->d_pair.alloc(nullptr, 486 * 2));
     SFM_RC(a->h_counts.alloc(160));
     SFM_RC(a->h_spec.alloc((size_t)a->det.spec_max * (6 * sizeof(float) + 64)));
-    // (k_suppress keeps two levels' candidates in LDS: more than the default 64 KB per workgroup)
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_suppress),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SuppressLds));
-    SFM_HIP(attr);
     std::vector<float> hs((size_t)kMaxLevels * kMaxFedSteps, 0.0f);
     for (int i = 0; i < a->plan.nlev; ++i)  // (nsteps <= kMaxFedSteps: make_plan)
       for (int k = 0; k < a->plan.lev[i].nsteps; ++k) hs[(size_t)i * kMaxFedSteps + k] = 0.5f * a->plan.lev[i].tsteps[k];
@@ -2322,19 +2301,22 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   const dim3 egrid(((a->w + 127) / 128 + kSegPerWave - 1) / kSegPerWave, D.rows);  // (kSegPerWave segments per wave)
   const LevelTab *dT = (const LevelTab *)a->d_level_tab;
   CandArrays C{a->d_cxy, a->d_clevel, a->d_cresp, a->d_csub};
-  sfm_launch<ExtremaSegBody>(a, k_extrema_seg, egrid, dim3(128), 0, a->d_Ldet, dT, a->thres, a->d_seg_x, a->d_seg, a->det.segs_per_row);
+  SFM_RC(sfm_launch<ExtremaSegBody>(a, k_extrema_seg, egrid, dim3(128), 0, a->d_Ldet, dT, a->thres, a->d_seg_x,
+                                    a->d_seg, a->det.segs_per_row));
   if (D.scan_two_launches) {  // a large image: two launches over many compute units
-    sfm_launch<SegSumBody>(a, k_seg_sum, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg, a->d_seg_part, a->d_ncand);
-    sfm_launch<SegWriteBody>(a, k_seg_write, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg, (const unsigned int *)a->d_seg_part);
+    SFM_RC(sfm_launch<SegSumBody>(a, k_seg_sum, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg, a->d_seg_part,
+                                  a->d_ncand));
+    SFM_RC(sfm_launch<SegWriteBody>(a, k_seg_write, dim3(D.seg_chunks), dim3(1024), 0, a->d_seg, D.n_seg,
+                                    a->d_seg_part));
   } else {
-    sfm_launch<SegScanBody>(a, k_seg_scan, dim3(1), dim3(1024), 0, a->d_seg, D.n_seg, D.cand_cap, a->d_ncand);
+    SFM_RC(sfm_launch<SegScanBody>(a, k_seg_scan, dim3(1), dim3(1024), 0, a->d_seg, D.n_seg, D.cand_cap, a->d_ncand));
   }
-  sfm_launch<ExtremaPlaceBody>(a, k_extrema_place, egrid, dim3(128), 0, a->d_Ldet, dT, a->d_seg_x, a->d_seg, a->det.cand_cap, C,
-                               a->det.segs_per_row);
+  SFM_RC(sfm_launch<ExtremaPlaceBody>(a, k_extrema_place, egrid, dim3(128), 0, a->d_Ldet, dT, a->d_seg_x, a->d_seg,
+                                      a->det.cand_cap, C, a->det.segs_per_row));
   // the neighbour lists: one wave per candidate, a fixed grid that strides over them (their number is on the device)
-  sfm_launch<NbrBody>(a, k_suppress_nbr, dim3(D.nbr_grid), dim3(256), 0, dT, (const unsigned int *)a->d_seg, D.segs_per_row,
-                      D.cand_cap, (const unsigned int *)a->d_ncand, (const uint32_t *)a->d_cxy, (const uint8_t *)a->d_clevel,
-                      (const float *)a->d_cresp, a->d_nbr, a->d_nbr2, a->d_ncand + 6, a->sup_force_spill);
+  SFM_RC(sfm_launch<NbrBody>(a, k_suppress_nbr, dim3(D.nbr_grid), dim3(256), 0, dT, a->d_seg, D.segs_per_row,
+                             D.cand_cap, a->d_ncand, a->d_cxy, a->d_clevel, a->d_cresp, a->d_nbr, a->d_nbr2,
+                             a->d_ncand + 6, a->sup_force_spill));
   SuppressArgs S;
   S.T = dT;
   S.nbr = a->d_nbr;
@@ -2353,14 +2335,11 @@ static int akaze_detect_enqueue(Akaze *a, const uint8_t *gray) {
   S.n_kp = a->d_ncand + 1;
   S.n_cand = a->d_ncand;
   S.rounds_out = a->d_ncand + 2;
-  sfm_launch<SuppressBody>(a, k_suppress, dim3(1), dim3(1024), (uint32_t)sizeof(SuppressLds), S);
+  SFM_RC(sfm_launch<SuppressBody>(a, k_suppress, dim3(1), dim3(1024), (uint32_t)sizeof(SuppressLds), S));
   // orientation + M-LDB: a fixed grid that strides over the keypoints (their number is on the device)
-  sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(D.desc_grid), dim3(64), 0,
-                                 (const DevLevels *)a->d_dev_levels, a->d_kp, 0, a->d_gauss25, a->d_win,
-                                 a->plan.n_win, a->d_pair, a->d_angle, a->d_desc, (const unsigned int *)(a->d_ncand + 1),
-                                 (const float *)a->d_resp, a->d_kp6, a->d_qkpt, a->d_qkpt6);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<OrientDescribeBody>(a, k_orient_describe, dim3(D.desc_grid), dim3(64), 0, a->d_dev_levels, a->d_kp,
+                                        0, a->d_gauss25, a->d_win, a->plan.n_win, a->d_pair, a->d_angle, a->d_desc,
+                                        (a->d_ncand + 1), a->d_resp, a->d_kp6, a->d_qkpt, a->d_qkpt6);
 }
 
 // the counts of one or more extractions (asynchronous on stream s; the caller synchronises), then their outputs

@@ -855,30 +855,27 @@ int ba_joint_run(Sfm &s, uint32_t what, const sfmloc_ba_joint_options &opt, sfml
     return SFMLOC_OK;
   };
   while (h.running) {
-    hipLaunchKernelGGL(k_jt_lin, g_obs, b256, 0, st, v);
-    if (stru) hipLaunchKernelGGL(k_jt_landmark, g_lm, b256, 0, st, v);
-    hipLaunchKernelGGL(k_jt_blocks, g_blocks, b256, 0, st, v);
-    if (intr) hipLaunchKernelGGL(k_jt_intr_sum, g_intr, b256, 0, st, v);
-    hipLaunchKernelGGL(k_jt_setup, dim3(1), dim3(1024), 0, st, v);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_jt_lin, g_obs, b256, 0, st, v));
+    if (stru) SFM_RC(dev_launch(k_jt_landmark, g_lm, b256, 0, st, v));
+    SFM_RC(dev_launch(k_jt_blocks, g_blocks, b256, 0, st, v));
+    if (intr) SFM_RC(dev_launch(k_jt_intr_sum, g_intr, b256, 0, st, v));
+    SFM_RC(dev_launch(k_jt_setup, dim3(1), dim3(1024), 0, st, v));
     for (uint32_t it = 0; it < opt.max_pcg; it += kPcgChunk) {
       for (int k = 0; k < kPcgChunk; ++k) {
-        if (stru) hipLaunchKernelGGL(k_jt_pcg_landmark, g_lm, b256, 0, st, v, (const double *)d_p.get(), 1);
-        hipLaunchKernelGGL(k_jt_pcg_blocks, g_blocks, b256, 0, st, v);
-        if (intr) hipLaunchKernelGGL(k_jt_pcg_intr, g_intr, b256, 0, st, v);
-        hipLaunchKernelGGL(k_jt_pcg_update, dim3(1), dim3(1024), 0, st, v, n_active);
+        if (stru) SFM_RC(dev_launch(k_jt_pcg_landmark, g_lm, b256, 0, st, v, d_p, 1));
+        SFM_RC(dev_launch(k_jt_pcg_blocks, g_blocks, b256, 0, st, v));
+        if (intr) SFM_RC(dev_launch(k_jt_pcg_intr, g_intr, b256, 0, st, v));
+        SFM_RC(dev_launch(k_jt_pcg_update, dim3(1), dim3(1024), 0, st, v, n_active));
       }
-      SFM_HIP(hipGetLastError());
       rc = read_state();
       if (rc) return rc;
       if (h.pcg_done) break;
     }
-    if (stru) hipLaunchKernelGGL(k_jt_pcg_landmark, g_lm, b256, 0, st, v, (const double *)d_x.get(), 0);
-    hipLaunchKernelGGL(k_jt_trial, g_each, b256, 0, st, v);
-    hipLaunchKernelGGL(k_jt_eval, g_obs, b256, 0, st, v);
-    hipLaunchKernelGGL(k_jt_decide, dim3(1), dim3(1024), 0, st, v);
-    hipLaunchKernelGGL(k_jt_commit, g_each, b256, 0, st, v);
-    SFM_HIP(hipGetLastError());
+    if (stru) SFM_RC(dev_launch(k_jt_pcg_landmark, g_lm, b256, 0, st, v, d_x, 0));
+    SFM_RC(dev_launch(k_jt_trial, g_each, b256, 0, st, v));
+    SFM_RC(dev_launch(k_jt_eval, g_obs, b256, 0, st, v));
+    SFM_RC(dev_launch(k_jt_decide, dim3(1), dim3(1024), 0, st, v));
+    SFM_RC(dev_launch(k_jt_commit, g_each, b256, 0, st, v));
     rc = read_state();
     if (rc) return rc;
   }

@@ -314,14 +314,13 @@ int ba_separable_run(Sfm &h, uint32_t what, sfmloc_ba_report *rep) {
     if (rc_t) return rc_t;
     if (structure) {
       const uint32_t per = 256 / kBaGroup;
-      hipLaunchKernelGGL(k_ba_structure, dim3((nb + per - 1) / per), dim3(256), 0, h.s, v);
+      SFM_RC(dev_launch(k_ba_structure, dim3((nb + per - 1) / per), dim3(256), 0, h.s, v));
     } else {
       const dim3 grid((nb + 3) / 4);
-      if (what == SFMLOC_BA_ROTATION) hipLaunchKernelGGL((k_ba_motion<3, 0>), grid, dim3(256), 0, h.s, v);
-      else if (what == SFMLOC_BA_TRANSLATION) hipLaunchKernelGGL((k_ba_motion<3, 3>), grid, dim3(256), 0, h.s, v);
-      else hipLaunchKernelGGL((k_ba_motion<6, 0>), grid, dim3(256), 0, h.s, v);
+      if (what == SFMLOC_BA_ROTATION) SFM_RC(dev_launch(k_ba_motion<3, 0>, grid, dim3(256), 0, h.s, v));
+      else if (what == SFMLOC_BA_TRANSLATION) SFM_RC(dev_launch(k_ba_motion<3, 3>, grid, dim3(256), 0, h.s, v));
+      else SFM_RC(dev_launch(k_ba_motion<6, 0>, grid, dim3(256), 0, h.s, v));
     }
-    SFM_HIP(hipGetLastError());
     std::vector<double> cost(2 * (size_t)nb);
     std::vector<uint32_t> info(nb);
     SFM_RC(dev_download(cost.data(), v.blk_cost, cost.size(), h.s));
@@ -346,10 +345,8 @@ int ba_separable_run(Sfm &h, uint32_t what, sfmloc_ba_report *rep) {
 }  // namespace
 
 int ba_pose_t(const SfmDev &v, hipStream_t s) {
-  hipLaunchKernelGGL(k_ba_pose_t, dim3((v.n_poses + 255) / 256), dim3(256), 0, s, v.n_poses, (const double *)v.pose_R,
-                     (const double *)v.pose_C, v.pose_t);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return dev_launch(k_ba_pose_t, dim3((v.n_poses + 255) / 256), dim3(256), 0, s, v.n_poses, v.pose_R, v.pose_C,
+                    v.pose_t);
 }
 
 }  // namespace sfmloc

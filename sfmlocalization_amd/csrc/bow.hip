@@ -528,12 +528,9 @@ int launch_bow_select(Ctx *c, const float *d_query, const uint32_t *d_cand, uint
   Map *m = c->map;
   ChainArgs C{};
   if (chain) C = *chain;
-  sfm_launch<BowDistBody>(c, k_bow_dist, dim3((n_cand + 3) / 4), dim3(256), 0, m->d_bow, m->bow_dim, d_cand, n_cand, d_query,
-                          d_dist_bits);
-  SFM_HIP(hipGetLastError());
-  sfm_launch<BowTopkBody>(c, k_bow_topk, dim3(1), dim3(1024), 0, d_dist_bits, n_cand, d_cand, k, d_out_sel, C);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  SFM_RC(sfm_launch<BowDistBody>(c, k_bow_dist, dim3((n_cand + 3) / 4), dim3(256), 0, m->d_bow, m->bow_dim, d_cand,
+                                 n_cand, d_query, d_dist_bits));
+  return sfm_launch<BowTopkBody>(c, k_bow_topk, dim3(1), dim3(1024), 0, d_dist_bits, n_cand, d_cand, k, d_out_sel, C);
 }
 
 int launch_bow_keys(Ctx *c, const float *d_query, uint32_t k, uint32_t *d_dist_bits, uint32_t *d_sel_tmp,
@@ -546,18 +543,14 @@ int launch_bow_keys(Ctx *c, const float *d_query, uint32_t k, uint32_t *d_dist_b
     C.keys_out = d_keys_out;
     C.key_view_id = m->d_view_id;
     C.k_out = k;
-    sfm_launch<BowDistBody>(c, k_bow_dist, dim3((m->n_views + 3) / 4), dim3(256), 0, m->d_bow, m->bow_dim,
-                            (const uint32_t *)nullptr, m->n_views, d_query, d_dist_bits);
-    SFM_HIP(hipGetLastError());
-    sfm_launch<BowTopkBody>(c, k_bow_topk, dim3(1), dim3(1024), 0, d_dist_bits, m->n_views, (const uint32_t *)nullptr, kk,
-                            d_sel_tmp, C);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<BowDistBody>(c, k_bow_dist, dim3((m->n_views + 3) / 4), dim3(256), 0, m->d_bow, m->bow_dim,
+                                   nullptr, m->n_views, d_query, d_dist_bits));
+    SFM_RC(sfm_launch<BowTopkBody>(c, k_bow_topk, dim3(1), dim3(1024), 0, d_dist_bits, m->n_views, nullptr, kk,
+                                   d_sel_tmp, C));
     return SFMLOC_OK;
   }
-  sfm_launch<BowKeysBody>(c, k_bow_keys, dim3((k + 255) / 256), dim3(256), 0, d_dist_bits, d_sel_tmp, kk, m->d_view_id,
-                     k, d_keys_out);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<BowKeysBody>(c, k_bow_keys, dim3((k + 255) / 256), dim3(256), 0, d_dist_bits, d_sel_tmp, kk,
+                                 m->d_view_id, k, d_keys_out);
 }
 
 int launch_bow_merge_select(Ctx *c, const unsigned long long *d_keys, uint32_t n_parts,
@@ -570,14 +563,8 @@ int launch_bow_merge_select(Ctx *c, const unsigned long long *d_keys, uint32_t n
   SFM_CHECK(n > 0 && n <= kBowMergeMaxKeys && k <= 1024, SFMLOC_EINVAL,
             "sharded shortlist: %u parts x %u keys (at most %u keys in all, k <= 1024)", n_parts, k, kBowMergeMaxKeys);
   const size_t lds = (size_t)((n + 1) & ~1ull) * 8 + 1024 * 4 + 16;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bow_merge_select),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     (int)(kBowMergeMaxKeys * 8 + 1024 * 4 + 16));
-  SFM_HIP(attr);
-  sfm_launch<BowMergeSelectBody>(c, k_bow_merge_select, dim3(1), dim3(1024), (uint32_t)lds, d_keys, n_parts, part_stride_keys,
-                                 k, m->d_view_id, m->n_views, n_pad, d_sel_out, C);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<BowMergeSelectBody>(c, k_bow_merge_select, dim3(1), dim3(1024), (uint32_t)lds, d_keys, n_parts,
+                                        part_stride_keys, k, m->d_view_id, m->n_views, n_pad, d_sel_out, C);
 }
 
 struct BofZeroBody {
@@ -599,15 +586,13 @@ int launch_bof_member(const BofModel *b, GangMember *m, const float *d_kxy, int 
   const size_t lds = BofTileLds::floats(b->in_dim, b->n_pca, b->cdim, b->K) * sizeof(float);
   if (n <= 0 || lds > 48 * 1024 || (size_t)b->K * sizeof(double) > 48 * 1024) return SFMLOC_EINVAL;
   const int nc = b->K * cells;
-  sfm_launch<BofZeroBody>(m, k_bof_zero, dim3((nc + 255) / 256), dim3(256), 0, d_counts, nc);
-  sfm_launch<BofAssignTiledBody>(m, k_bof_assign_tiled, dim3((n + kBofTile - 1) / kBofTile), dim3(256), (uint32_t)lds,
-                                 (const float *)nullptr, d_kxy, n, b->in_dim, (const float *)b->d_pca_mean,
-                                 (const float *)b->d_pca_evec, (const float *)b->d_pca_eval, b->n_pca,
-                                 (const float *)b->d_centers, b->K, b->resized, b->levels, d_counts, d_desc8);
-  sfm_launch<BofFinishBody>(m, k_bof_finish, dim3(cells), dim3(64), (uint32_t)((size_t)b->K * sizeof(double)),
-                            (const uint32_t *)d_counts, n, b->K, cells, b->norm_type, d_out, d_out_f32);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  SFM_RC(sfm_launch<BofZeroBody>(m, k_bof_zero, dim3((nc + 255) / 256), dim3(256), 0, d_counts, nc));
+  SFM_RC(sfm_launch<BofAssignTiledBody>(m, k_bof_assign_tiled, dim3((n + kBofTile - 1) / kBofTile), dim3(256),
+                                        (uint32_t)lds, nullptr, d_kxy, n, b->in_dim, b->d_pca_mean, b->d_pca_evec,
+                                        b->d_pca_eval, b->n_pca, b->d_centers, b->K, b->resized, b->levels, d_counts,
+                                        d_desc8));
+  return sfm_launch<BofFinishBody>(m, k_bof_finish, dim3(cells), dim3(64), (uint32_t)((size_t)b->K * sizeof(double)),
+                                   d_counts, n, b->K, cells, b->norm_type, d_out, d_out_f32);
 }
 
 int launch_bof(const BofModel *b, hipStream_t s, const float *d_desc, const float *d_kxy, int n, uint32_t *d_counts,
@@ -617,22 +602,21 @@ int launch_bof(const BofModel *b, hipStream_t s, const float *d_desc, const floa
   if (n > 0) {
     const size_t lds = BofTileLds::floats(b->in_dim, b->n_pca, b->cdim, b->K) * sizeof(float);
     if (lds <= 60 * 1024) {  // the model fits the LDS layout (the reference's does: 45 KB)
-      hipLaunchKernelGGL(k_bof_assign_tiled, dim3((n + kBofTile - 1) / kBofTile), dim3(256), lds, s, d_desc, d_kxy, n,
-                         b->in_dim, b->d_pca_mean, b->d_pca_evec, b->d_pca_eval, b->n_pca, b->d_centers, b->K, b->resized,
-                         b->levels, d_counts, d_desc8);
+      SFM_RC(dev_launch(k_bof_assign_tiled, dim3((n + kBofTile - 1) / kBofTile), dim3(256), lds, s, d_desc, d_kxy, n,
+                        b->in_dim, b->d_pca_mean, b->d_pca_evec, b->d_pca_eval, b->n_pca, b->d_centers, b->K,
+                        b->resized, b->levels, d_counts, d_desc8));
     } else {
-      hipLaunchKernelGGL(k_bof_assign, dim3((n + 255) / 256), dim3(256), 0, s, d_desc, d_kxy, n, b->in_dim, b->d_pca_mean,
-                         b->d_pca_evec, b->d_pca_eval, b->n_pca, b->d_centers, b->K, b->resized, b->levels, d_counts, d_desc8);
+      SFM_RC(dev_launch(k_bof_assign, dim3((n + 255) / 256), dim3(256), 0, s, d_desc, d_kxy, n, b->in_dim,
+                        b->d_pca_mean, b->d_pca_evec, b->d_pca_eval, b->n_pca, b->d_centers, b->K, b->resized,
+                        b->levels, d_counts, d_desc8));
     }
-    SFM_HIP(hipGetLastError());
   }
   if ((size_t)b->K * sizeof(double) <= 48 * 1024)
-    hipLaunchKernelGGL(k_bof_finish, dim3(cells), dim3(64), (size_t)b->K * sizeof(double), s, d_counts, n > 0 ? n : 1, b->K,
-                       cells, b->norm_type, d_out, d_out_f32);
+    SFM_RC(dev_launch(k_bof_finish, dim3(cells), dim3(64), (size_t)b->K * sizeof(double), s, d_counts, n > 0 ? n : 1,
+                      b->K, cells, b->norm_type, d_out, d_out_f32));
   else
-    hipLaunchKernelGGL(k_bof_finish_serial, dim3(1), dim3(64), 0, s, d_counts, n > 0 ? n : 1, b->K, cells, b->norm_type, d_out,
-                       d_out_f32);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_bof_finish_serial, dim3(1), dim3(64), 0, s, d_counts, n > 0 ? n : 1, b->K, cells, b->norm_type,
+                      d_out, d_out_f32));
   return SFMLOC_OK;
 }
 

@@ -93,6 +93,16 @@ int host_raw_alloc(void **p, size_t bytes) {
 }
 void host_raw_free(void *p) { (void)hipHostFree(p); }
 
+// ... and a kernel's dynamic-LDS limit is raised, on the device that is current, by this one (devmem.h "Dynamic-LDS
+// limits"; nothing is launched after a failure, so the error does not stay with the runtime for a later launch's check)
+int dev_raw_lds_limit(const void *kernel, uint32_t bytes) {
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) return SFMLOC_OK;
+  (void)hipGetLastError();
+  set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %u bytes) -> %s", bytes, hipGetErrorString(e));
+  return hip_code(e);
+}
+
 // ... and every transfer is issued by these two (devmem.h "Transfers": a null stream means done on return)
 int dev_raw_copy(void *dst, const void *src, size_t bytes, CopyKind kind, hipStream_t s) {
   const hipMemcpyKind k = kind == CopyKind::kHostToDevice   ? hipMemcpyHostToDevice
@@ -238,6 +248,7 @@ int make_ctx(Map *m, Ctx **out, Ctx *share = nullptr, bool merge_only = false) {
   Ctx *c = owner.get();
   SFM_CHECK(c, SFMLOC_ENOMEM, "out of host memory");
   c->map = m;
+  c->device = m->device;
   if (share) {  // no stream (hardware queue) of its own: work is queued on the lender's
     c->own_stream.borrow(share->stream.own);
     c->lender = share;
@@ -375,8 +386,7 @@ int ctx_reset_for_query(Ctx *c, const Query *q, QueryPass &pass) {
   }
   const uint32_t nq = q->n ? q->n : 1;
   const uint32_t n = m->n_views + 1 > nq ? m->n_views + 1 : nq;
-  sfm_launch<QueryResetBody>(c, k_query_reset, dim3((n + 255) / 256), dim3(256), 0, make_reset_args(c, q));
-  SFM_HIP(hipGetLastError());
+  SFM_RC(sfm_launch<QueryResetBody>(c, k_query_reset, dim3((n + 255) / 256), dim3(256), 0, make_reset_args(c, q)));
   pass.cleared = true;
   return SFMLOC_OK;
 }
@@ -802,20 +812,20 @@ int gang_flush(GangState *g) {
       if (n == lead->cap) break;
     }
     const bool together = n > 1 && lead->grid.z == 1;
+    int lrc = SFMLOC_OK;  // (a launch that fails leaves its text; the rest of the chain is still issued, as before)
+    const LaunchStream on(g->stream, LaunchSite{__FILE__, __LINE__}, g->members[0]->device);
     if (together) {
       lead->shmem = shmem;
-      lead->launch_many(grp, n, g->stream);
+      lrc = lead->launch_many(grp, n, on);
     } else {
-      for (int i = 0; i < n; ++i) grp[i]->launch_one(*grp[i], g->stream);
+      for (int i = 0; i < n; ++i) {
+        const int one = grp[i]->launch_one(*grp[i], on);
+        lrc = lrc ? lrc : one;
+      }
     }
     g->launches += together ? 1 : n;
     g->gang_launches += together ? 1 : 0;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-      set_error("gang launch (%d members, grid %u x %u, %u threads, %u B LDS): %s", n, lead->grid.x, lead->grid.y,
-                lead->block.x, lead->shmem, hipGetErrorString(e));
-      rc = SFMLOC_EHIP;
-    }
+    rc = lrc ? lrc : rc;
   }
   for (GangMember *m : g->members) {
     m->gang_recs.clear();

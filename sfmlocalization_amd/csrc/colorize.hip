@@ -139,9 +139,8 @@ int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *
   SFM_RC(d_order.zero(V.n_views, d.s));
   if ((rc = d.time_begin())) return rc;
   const uint32_t n_init = V.n_views > V.n_lm ? V.n_views : V.n_lm;
-  hipLaunchKernelGGL(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.view_off, d_card, V.n_lm,
-                     V.obs_off, d_iter, d_obs, d_st);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_color_init, dim3((n_init + 255) / 256), dim3(256), 0, d.s, V.n_views, V.view_off, d_card, V.n_lm,
+                    V.obs_off, d_iter, d_obs, d_st));
   uint32_t blocks = (max_view_obs + kUpdateThreads - 1) / kUpdateThreads;
   blocks = blocks < 1 ? 1 : (blocks > kUpdateMaxBlocks ? kUpdateMaxBlocks : blocks);
   ColorState st;
@@ -150,11 +149,10 @@ int color_plan_impl(const Sfm &h, uint32_t *order, uint32_t *n_order, uint32_t *
     SFM_HIP(hipStreamSynchronize(d.s));
     if (st.remaining == 0) break;
     for (uint32_t i = 0; i < SFMLOC_COLOR_CHUNK; ++i) {
-      hipLaunchKernelGGL(k_color_argmax, dim3(1), dim3(kArgmaxThreads), 0, d.s, V.n_views, d_card, d_st, d_order);
-      hipLaunchKernelGGL(k_color_update, dim3(blocks), dim3(kUpdateThreads), 0, d.s, V.view_off, V.vlist, V.obs_lm,
-                         V.obs_off, V.obs_view, d_card, d_iter, d_obs, d_st);
+      SFM_RC(dev_launch(k_color_argmax, dim3(1), dim3(kArgmaxThreads), 0, d.s, V.n_views, d_card, d_st, d_order));
+      SFM_RC(dev_launch(k_color_update, dim3(blocks), dim3(kUpdateThreads), 0, d.s, V.view_off, V.vlist, V.obs_lm,
+                        V.obs_off, V.obs_view, d_card, d_iter, d_obs, d_st));
     }
-    SFM_HIP(hipGetLastError());
   }
   if ((rc = d.time_end())) return rc;
   SFM_RC(d_order.download(order, st.n_order, d.s));

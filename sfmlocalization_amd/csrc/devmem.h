@@ -2,13 +2,14 @@
 // memory figures (sfmloc_map_info::hbm_bytes: Map and Ctx charge an account, nothing else does) need no list kept in
 // step by hand.  No HIP here: raw allocation goes through two functions that capi.hip defines over hipMalloc / hipFree
 // (and tests/cpp/devmem.cpp over malloc), and every transfer through two more ("Transfers" below states their rules).
-// Below the device arrays: the owners of streams, events and pinned host memory.
+// Below the device arrays: the kernels' dynamic-LDS limits, then the owners of streams, events and pinned host memory.
 #pragma once
 
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sfmloc.h"
+#include <atomic>
 #include <memory>
 #include <type_traits>
 #include <utility>
@@ -218,6 +219,51 @@ class DevGroup {
   int n_ = 0, rc_ = 0;
   size_t failed_bytes_ = 0;
 };
+
+// ---------------------------------------------------------------------------
+// Dynamic-LDS limits: before a launch that asks for more dynamic LDS than the default 48 KiB, the kernel's limit is
+// raised through the raw function below (capi.hip: hipFuncSetAttribute on the device that is current, the only place
+// that names it).  One rule for every kernel (launch.h applies it to every launch): remembered per kernel AND per device
+// ordinal is the mark, the largest size for which the raw call has succeeded, 48 KiB to begin with.  A launch asking for
+// more than the mark makes one raw call and raises the mark; one asking for that much or less makes none; a raw call
+// that fails answers its code, leaves the mark, and the launch does not happen.
+// Whether the runtime needs the call at all has not been measured: HIP's own header calls the function attributes of AMD
+// devices "hints and controls" that "are ignored".  Per device is the conservative reading, nothing more is claimed.
+// No lock: two host threads may both make the raw call for one kernel, which is harmless, and the lower of two marks
+// stored at once only costs a later call.  A kernel the table has no slot left for, or a device ordinal beyond it, has
+// no mark: the raw call is made before each of its launches above 48 KiB -- correct, but one runtime call per launch
+// and nothing reports it, so kLdsKernels stays well above the number of such kernels (their gang forms included).
+// ---------------------------------------------------------------------------
+int dev_raw_lds_limit(const void *kernel, uint32_t bytes);  // codes as dev_raw_alloc
+
+constexpr uint32_t kLdsDefaultLimit = 48 * 1024;
+constexpr int kLdsDevices = 16, kLdsKernels = 256;  // (a dozen kernels and their gang forms ask for more than the default)
+struct LdsMarks {
+  std::atomic<const void *> kernel;
+  std::atomic<uint32_t> mark[kLdsDevices];  // 0: nothing raised yet
+};
+inline LdsMarks g_lds_marks[kLdsKernels];  // (static storage: zeroed)
+
+inline std::atomic<uint32_t> *lds_mark(const void *kernel, int device) {
+  if (device < 0 || device >= kLdsDevices) return nullptr;
+  const size_t h = (size_t)((reinterpret_cast<uintptr_t>(kernel) >> 3) * 0x9E3779B97F4A7C15ull >> 40);
+  for (int probe = 0; probe < kLdsKernels; ++probe) {
+    LdsMarks &e = g_lds_marks[(h + probe) % kLdsKernels];
+    const void *k = e.kernel.load(std::memory_order_relaxed);
+    if (!k && e.kernel.compare_exchange_strong(k, kernel, std::memory_order_relaxed)) k = kernel;  // (else k: who won)
+    if (k == kernel) return &e.mark[device];
+  }
+  return nullptr;
+}
+// the limit of `kernel` on device ordinal `device` (the current one) allows `bytes` of dynamic LDS from here on
+inline int lds_allow(const void *kernel, int device, uint32_t bytes) {
+  if (bytes <= kLdsDefaultLimit) return 0;
+  std::atomic<uint32_t> *mark = lds_mark(kernel, device);
+  if (mark && bytes <= mark->load(std::memory_order_relaxed)) return 0;
+  const int rc = dev_raw_lds_limit(kernel, bytes);
+  if (!rc && mark) mark->store(bytes, std::memory_order_relaxed);
+  return rc;
+}
 
 // ---------------------------------------------------------------------------
 // The other three resources a handle or a call holds: a stream, an event, a block of pinned host memory.  Same rules as

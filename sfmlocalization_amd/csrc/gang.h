@@ -17,7 +17,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <atomic>
 #include <memory>
 #include <new>
 #include <type_traits>
@@ -25,6 +24,7 @@
 #include <vector>
 
 #include "devmem.h"
+#include "launch.h"
 
 namespace sfmloc {
 
@@ -82,8 +82,8 @@ __global__ __launch_bounds__(Body::kGangThreads, GangMinWaves<Body>::value) void
 struct GangRec {
   const void *key;  // the gang kernel: same key = same body and argument types
   const void *single;
-  void (*launch_one)(const GangRec &, hipStream_t);
-  void (*launch_many)(GangRec *const *, int, hipStream_t);
+  int (*launch_one)(const GangRec &, LaunchStream);  // (both: dev_launch's answer)
+  int (*launch_many)(GangRec *const *, int, LaunchStream);
   dim3 grid, block;
   uint32_t shmem;
   int cap;  // members one launch of this kernel carries
@@ -127,6 +127,7 @@ struct CtxStream {
 // what takes part in gang sessions: a context (sfmloc_internal.h) or an AKAZE extractor (akaze.hip)
 struct GangMember {
   CtxStream stream;  // reads as the stream to queue on now (the member's own, or its gang's while recording)
+  int device = -1;   // the ordinal of the device the member works on, current whenever it launches (-1: not known)
   std::vector<GangRec> gang_recs;  // launches recorded for the gang session in progress
   size_t gang_head = 0;
   bool gang_oom = false;            // a record could not be stored (host memory): the session's flush returns ENOMEM
@@ -149,24 +150,18 @@ struct GangLaunch {
   static_assert(kCap >= 2, "argument list too long for a gang launch");
   static const void *key() { return reinterpret_cast<const void *>(&k_gang<Body, kCap, Ts...>); }
   template <size_t... Is>
-  static void one_impl(const GangRec &r, hipStream_t s, std::index_sequence<Is...>) {
+  static int one_impl(const GangRec &r, LaunchStream s, std::index_sequence<Is...>) {
     const T &t = *reinterpret_cast<const T *>(r.args);
     auto k = reinterpret_cast<void (*)(Ts...)>(const_cast<void *>(r.single));
-    hipLaunchKernelGGL(k, r.grid, r.block, r.shmem, s, tup_get<Is>(t)...);
+    return dev_launch(k, r.grid, r.block, r.shmem, s, tup_get<Is>(t)...);
   }
-  static void one(const GangRec &r, hipStream_t s) { one_impl(r, s, std::index_sequence_for<Ts...>{}); }
-  static void many(GangRec *const *rs, int n, hipStream_t s) {
+  static int one(const GangRec &r, LaunchStream s) { return one_impl(r, s, std::index_sequence_for<Ts...>{}); }
+  static int many(GangRec *const *rs, int n, LaunchStream s) {
     const GangRec &r = *rs[0];
-    static std::atomic<uint32_t> lds_allowed{48 * 1024};  // (dynamic LDS beyond the default needs the attribute)
-    if (r.shmem > lds_allowed.load(std::memory_order_relaxed)) {
-      if (hipFuncSetAttribute(key(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.shmem) != hipSuccess)
-        return;  // (the error stays for the caller's hipGetLastError)
-      lds_allowed.store(r.shmem, std::memory_order_relaxed);
-    }
     GangArgs<kCap, Ts...> g;
     for (int i = 0; i < n; ++i) g.a[i] = *reinterpret_cast<const T *>(rs[i]->args);
     for (int i = n; i < kCap; ++i) g.a[i] = g.a[0];
-    hipLaunchKernelGGL((k_gang<Body, kCap, Ts...>), dim3(r.grid.x, r.grid.y, n), r.block, r.shmem, s, g);
+    return dev_launch(k_gang<Body, kCap, Ts...>, dim3(r.grid.x, r.grid.y, n), r.block, r.shmem, s, g);
   }
 };
 

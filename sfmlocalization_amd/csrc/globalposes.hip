@@ -888,15 +888,14 @@ __global__ __launch_bounds__(256) void k_gp_commit(GpDev D, int kind) {
 // ---- host ------------------------------------------------------------------------------------------------------------
 
 
-// a launch on the call's stream, counted
-#define GP_LAUNCH(kernel, grid, ...)                                          \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, __VA_ARGS__);     \
-    ++*launches;                                                              \
-  } while (0)
+// a launch of 256-thread blocks, counted
+template <class... Ts, class... As>
+int gp_launch(uint32_t *launches, void (*kernel)(Ts...), uint32_t grid, LaunchStream on, As &&...as) {
+  ++*launches;
+  return dev_launch(kernel, dim3(grid), dim3(256), 0, on, as...);
+}
 
 int gp_read_state(const GpDev &D, GpState *h, hipStream_t s) {
-  SFM_HIP(hipGetLastError());
   SFM_RC(dev_download(h, D.st, 1, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;
@@ -908,9 +907,9 @@ int gp_pcg(const GpDev &D, uint32_t max_pcg, hipStream_t s, uint32_t *launches, 
   const uint32_t gv = D.nb_view, ga = D.n_part;
   for (uint32_t it = 0; it < max_pcg; it += kPcgChunk) {
     for (uint32_t k = it; k < it + kPcgChunk && k < max_pcg; ++k) {
-      GP_LAUNCH(k_gp_apply<KIND>, ga, D, k);
-      GP_LAUNCH(k_gp_step1<KIND>, gv, D, k);
-      GP_LAUNCH(k_gp_step2<KIND>, gv, D, k);
+      SFM_RC(gp_launch(launches, k_gp_apply<KIND>, ga, s, D, k));
+      SFM_RC(gp_launch(launches, k_gp_step1<KIND>, gv, s, D, k));
+      SFM_RC(gp_launch(launches, k_gp_step2<KIND>, gv, s, D, k));
     }
     SFM_RC(gp_read_state(D, h, s));
     if (h->done_at != kNever) break;
@@ -978,13 +977,12 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
     SFM_RC(d_parent.alloc(nullptr, P));
     SFM_RC(d_flag.alloc(nullptr, 1));
     const uint32_t gw = (uint32_t)((W + 255) / 256), gn = (uint32_t)((P + 255) / 256);
-    GP_LAUNCH(k_gp_sc_cc, gw > gn ? gw : gn, (const uint32_t *)d_kl, (const uint8_t *)d_on, (uint32_t)W, (uint32_t)P, d_ea.get(),
-              d_eb.get(), d_parent.get());
+    SFM_RC(gp_launch(launches, k_gp_sc_cc, gw > gn ? gw : gn, s, d_kl, d_on, (uint32_t)W, (uint32_t)P, d_ea, d_eb,
+                     d_parent));
     for (;;) {
       SFM_RC(d_flag.zero(1, s));
-      GP_LAUNCH(k_graph_hook, gw, (const uint32_t *)d_ea, (const uint32_t *)d_eb, (uint32_t)W, d_parent.get(), d_flag.get());
-      GP_LAUNCH(k_graph_jump, gn, d_parent.get(), (uint32_t)P);
-      SFM_HIP(hipGetLastError());
+      SFM_RC(gp_launch(launches, k_graph_hook, gw, s, d_ea, d_eb, (uint32_t)W, d_parent, d_flag));
+      SFM_RC(gp_launch(launches, k_graph_jump, gn, s, d_parent, (uint32_t)P));
       uint32_t changed = 0;
       SFM_RC(d_flag.download(&changed, 1, s));
       SFM_HIP(hipStreamSynchronize(s));
@@ -1067,20 +1065,19 @@ int gp_scale_phase(GpDev &D, uint8_t *d_inc, DevBuf<double> &d_base, const GpSca
   const uint32_t ge = (uint32_t)((W + 255) / 256), gv = S.nb_view, ga = S.n_part;
   const double delta = sc.opt.scale_delta;
   while (h.running) {
-    GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);
-    GP_LAUNCH(k_gp_setup<3>, ga, S);
-    GP_LAUNCH(k_gp_begin, 1, S, 1);
+    SFM_RC(gp_launch(launches, k_gp_sc_edges, ge, s, S, d_xs, d_y, delta, 0));
+    SFM_RC(gp_launch(launches, k_gp_setup<3>, ga, s, S));
+    SFM_RC(gp_launch(launches, k_gp_begin, 1, s, S, 1));
     SFM_RC(gp_pcg<3>(S, sc.opt.max_pcg, s, launches, &h));
-    GP_LAUNCH(k_gp_trial, gv, S, 3);
-    GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xn, (const double *)d_y, delta, 1);
-    GP_LAUNCH(k_gp_cost, ga, S, 1);
-    GP_LAUNCH(k_gp_decide, 1, S, 1);
-    GP_LAUNCH(k_gp_commit, gv, S, 3);
+    SFM_RC(gp_launch(launches, k_gp_trial, gv, s, S, 3));
+    SFM_RC(gp_launch(launches, k_gp_sc_edges, ge, s, S, d_xn, d_y, delta, 1));
+    SFM_RC(gp_launch(launches, k_gp_cost, ga, s, S, 1));
+    SFM_RC(gp_launch(launches, k_gp_decide, 1, s, S, 1));
+    SFM_RC(gp_launch(launches, k_gp_commit, gv, s, S, 3));
     SFM_RC(gp_read_state(S, &h, s));
   }
-  GP_LAUNCH(k_gp_sc_edges, ge, S, (const double *)d_xs, (const double *)d_y, delta, 0);  // the weights at the result
+  SFM_RC(gp_launch(launches, k_gp_sc_edges, ge, s, S, d_xs, d_y, delta, 0));  // the weights at the result
   std::vector<double> x(P), ew(W);
-  SFM_HIP(hipGetLastError());
   SFM_RC(d_xs.download(x.data(), P, s));
   SFM_RC(d_ew.download(ew.data(), W, s));
   SFM_HIP(hipStreamSynchronize(s));
@@ -1163,15 +1160,13 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
 
   // sfmloc.h "triplets"
   const double thr = 1.0 + 2.0 * cos(opt.triplet_angle_deg * (M_PI / 180.0));
-  GP_LAUNCH(k_gp_triplets, (n_pairs + 3) / 4, D, thr);
+  SFM_RC(gp_launch(launches, k_gp_triplets, (n_pairs + 3) / 4, s, D, thr));
   // sfmloc.h "component"
-  GP_LAUNCH(k_gp_cc_edges, gboth, D, d_ea.get(), d_eb.get(), d_parent.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(gp_launch(launches, k_gp_cc_edges, gboth, s, D, d_ea, d_eb, d_parent));
   for (;;) {
     SFM_RC(d_flag.zero(1, s));
-    GP_LAUNCH(k_graph_hook, gp, (const uint32_t *)d_ea, (const uint32_t *)d_eb, n_pairs, d_parent.get(), d_flag.get());
-    GP_LAUNCH(k_graph_jump, gv, d_parent.get(), n_views);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(gp_launch(launches, k_graph_hook, gp, s, d_ea, d_eb, n_pairs, d_parent, d_flag));
+    SFM_RC(gp_launch(launches, k_graph_jump, gv, s, d_parent, n_views));
     uint32_t changed = 0;
     SFM_RC(d_flag.download(&changed, 1, s));
     SFM_HIP(hipStreamSynchronize(s));
@@ -1209,7 +1204,7 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
   D.root = root;
   SFM_RC(ev.mark(1, s));
   SFM_RC(d_inc.upload(g->in_comp.data(), n, s));
-  GP_LAUNCH(k_gp_flags, gp, D);
+  SFM_RC(gp_launch(launches, k_gp_flags, gp, s, D));
 
   DevBuf<double> d_R, d_Rn, d_C, d_Cn, d_dir, d_ev, d_W, d_ew, d_rho, d_res, d_mterm, d_diag, d_Minv, d_x, d_r, d_z, d_p,
       d_q, d_part;
@@ -1242,32 +1237,32 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
 
   // sfmloc.h "chordal"
   SFM_RC(d_st.upload(&h0, 1, s));
-  GP_LAUNCH(k_gp_setup<0>, ga, D);
-  GP_LAUNCH(k_gp_begin, 1, D, 0);
+  SFM_RC(gp_launch(launches, k_gp_setup<0>, ga, s, D));
+  SFM_RC(gp_launch(launches, k_gp_begin, 1, s, D, 0));
   SFM_RC(gp_pcg<0>(D, opt.max_pcg, s, launches, &h));
   rep.chordal_pcg = h.pcg_iter;
   rep.chordal_stop = h.pcg_stop;
   rep.chordal_residual = h.rr0 > 0.0 ? sqrt(h.rr / h.rr0) : 0.0;
-  GP_LAUNCH(k_gp_project, gv, D);
+  SFM_RC(gp_launch(launches, k_gp_project, gv, s, D));
 
   // sfmloc.h "IRLS"
   const double rdelta = opt.rotation_delta > 0.0 ? opt.rotation_delta : tan(opt.triplet_angle_deg * (M_PI / 180.0) / 6.0);
   SFM_RC(d_st.upload(&h0, 1, s));
   h = h0;
   while (h.running) {
-    GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);
-    GP_LAUNCH(k_gp_setup<1>, ga, D);
-    GP_LAUNCH(k_gp_begin, 1, D, 1);
+    SFM_RC(gp_launch(launches, k_gp_rot_edges, gp, s, D, d_R, rdelta, 0));
+    SFM_RC(gp_launch(launches, k_gp_setup<1>, ga, s, D));
+    SFM_RC(gp_launch(launches, k_gp_begin, 1, s, D, 1));
     SFM_RC(gp_pcg<1>(D, opt.max_pcg, s, launches, &h));
-    GP_LAUNCH(k_gp_trial, gv, D, 1);
-    GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_Rn, rdelta, 1);
-    GP_LAUNCH(k_gp_cost, ga, D, 1);
-    GP_LAUNCH(k_gp_decide, 1, D, 1);
-    GP_LAUNCH(k_gp_commit, gv, D, 1);
+    SFM_RC(gp_launch(launches, k_gp_trial, gv, s, D, 1));
+    SFM_RC(gp_launch(launches, k_gp_rot_edges, gp, s, D, d_Rn, rdelta, 1));
+    SFM_RC(gp_launch(launches, k_gp_cost, ga, s, D, 1));
+    SFM_RC(gp_launch(launches, k_gp_decide, 1, s, D, 1));
+    SFM_RC(gp_launch(launches, k_gp_commit, gv, s, D, 1));
     SFM_RC(gp_read_state(D, &h, s));
     if (h.steps_tried == 1) rep.chordal_cost = h.model;  // (at the first step's start: the projected chordal solution)
   }
-  GP_LAUNCH(k_gp_rot_edges, gp, D, (const double *)d_R, rdelta, 0);  // the residuals at the result
+  SFM_RC(gp_launch(launches, k_gp_rot_edges, gp, s, D, d_R, rdelta, 0));  // the residuals at the result
   std::vector<double> res(P);
   SFM_RC(d_res.download(res.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
@@ -1289,23 +1284,22 @@ int gposes_device(uint32_t n_views, const uint32_t *pairs, uint32_t n_pairs, con
     if (none) return SFMLOC_OK;
     SFM_RC(ev.mark(4, s));
   }
-  GP_LAUNCH(k_gp_dirs, gp, D);
+  SFM_RC(gp_launch(launches, k_gp_dirs, gp, s, D));
   SFM_RC(d_st.upload(&h0, 1, s));
   h = h0;
   while (h.running) {
-    GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
-    GP_LAUNCH(k_gp_setup<2>, ga, D);
-    GP_LAUNCH(k_gp_begin, 1, D, 1);
+    SFM_RC(gp_launch(launches, k_gp_tr_edges, gp, s, D, d_C, opt.translation_delta, 0));
+    SFM_RC(gp_launch(launches, k_gp_setup<2>, ga, s, D));
+    SFM_RC(gp_launch(launches, k_gp_begin, 1, s, D, 1));
     SFM_RC(gp_pcg<2>(D, opt.max_pcg, s, launches, &h));
-    GP_LAUNCH(k_gp_trial, gv, D, 2);
-    GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_Cn, opt.translation_delta, 1);
-    GP_LAUNCH(k_gp_cost, ga, D, 2);
-    GP_LAUNCH(k_gp_decide, 1, D, 2);
-    GP_LAUNCH(k_gp_commit, gv, D, 2);
+    SFM_RC(gp_launch(launches, k_gp_trial, gv, s, D, 2));
+    SFM_RC(gp_launch(launches, k_gp_tr_edges, gp, s, D, d_Cn, opt.translation_delta, 1));
+    SFM_RC(gp_launch(launches, k_gp_cost, ga, s, D, 2));
+    SFM_RC(gp_launch(launches, k_gp_decide, 1, s, D, 2));
+    SFM_RC(gp_launch(launches, k_gp_commit, gv, s, D, 2));
     SFM_RC(gp_read_state(D, &h, s));
   }
-  GP_LAUNCH(k_gp_tr_edges, gp, D, (const double *)d_C, opt.translation_delta, 0);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(gp_launch(launches, k_gp_tr_edges, gp, s, D, d_C, opt.translation_delta, 0));
   SFM_RC(d_res.download(res.data(), P, s));
   SFM_RC(d_R.download(g->R.data(), 9 * n, s));
   SFM_RC(d_C.download(g->C.data(), 3 * n, s));

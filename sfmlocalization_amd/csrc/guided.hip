@@ -200,12 +200,9 @@ int launch_guided_matching(Ctx *c, const Query *q, uint32_t n_sel, bool all_view
   const double r = 0.6;  // Robust_model_estimation's d_distance_ratio default; hulo::geometricMatch does not pass one
   A.ratio2 = r * r;
   A.guided_row = c->d_guided_row;
-  sfm_launch<GuidedRowsBody>(c, k_guided_rows, dim3(n_sel, (m->max_view_rows + 255) / 256), dim3(256), 0, A);
-  SFM_HIP(hipGetLastError());
-  sfm_launch<GuidedCompactBody>(c, k_guided_compact, dim3((n_sel + 3) / 4), dim3(256), 0, A.view_sel, n_sel, m->d_view_off,
-                     c->d_guided_row, c->d_geo_count, c->d_geo_idx, c->d_geo_j);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  SFM_RC(sfm_launch<GuidedRowsBody>(c, k_guided_rows, dim3(n_sel, (m->max_view_rows + 255) / 256), dim3(256), 0, A));
+  return sfm_launch<GuidedCompactBody>(c, k_guided_compact, dim3((n_sel + 3) / 4), dim3(256), 0, A.view_sel, n_sel,
+                                       m->d_view_off, c->d_guided_row, c->d_geo_count, c->d_geo_idx, c->d_geo_j);
 }
 
 }  // namespace sfmloc

@@ -302,15 +302,10 @@ int launch_hamming_t(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_li
   uint32_t lds_rows = q_chunk < lds_rows_cap ? q_chunk : lds_rows_cap;
   if (lds_rows == 0) lds_rows = 1;
   const size_t lds_bytes = (size_t)lds_rows * 64;
-  auto kern = k_hamming_top2<R, WAVES>;
-  SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_bytes));
   dim3 grid((n_work_blocks + WAVES * R - 1) / (WAVES * R), split);
-  sfm_launch<HammingTop2Body<R, WAVES>>(c, kern, grid, dim3(WAVES * 64), (uint32_t)lds_bytes, m->d_bank,
-                                        use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, nq, q_chunk,
-                                        lds_rows, c->d_part);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<HammingTop2Body<R, WAVES>>(c, k_hamming_top2<R, WAVES>, grid, dim3(WAVES * 64), (uint32_t)lds_bytes,
+                                               m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks,
+                                               q->d_desc, nq, q_chunk, lds_rows, c->d_part);
 }
 
 }  // namespace
@@ -318,10 +313,8 @@ int launch_hamming_t(Ctx *c, const Query *q, uint32_t n_work_blocks, bool use_li
 int launch_tile_bank(const uint4 *d_rows, uint64_t row0, uint64_t n_rows_chunk, uint4 *d_bank, hipStream_t s) {
   if (n_rows_chunk == 0) return SFMLOC_OK;
   const uint64_t n = n_rows_chunk * 4;
-  hipLaunchKernelGGL(k_tile_bank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_rows, row0, n_rows_chunk,
-                     d_bank);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return dev_launch(k_tile_bank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_rows, row0, n_rows_chunk,
+                    d_bank);
 }
 
 static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, const K1Plan &P, uint32_t n_work_blocks,
@@ -341,30 +334,30 @@ static int launch_hamming_screened(Ctx *c, const Query *q, QueryPass &pass, cons
     SFM_RC(c->d_flagmask.zero(n_work_blocks, c->stream));
   pass.flagmask_zeroed = false;  // (this scan writes it)
   auto screen = [&](auto body, auto kern, size_t lds) {
-    sfm_launch<decltype(body)>(c, kern, dim3((n_work_blocks + WAVES - 1) / WAVES, P.slices), dim3(WAVES * 64), (uint32_t)lds,
-                               m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
-                               m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, P.head,
-                               c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);
+    return sfm_launch<decltype(body)>(c, kern, dim3((n_work_blocks + WAVES - 1) / WAVES, P.slices), dim3(WAVES * 64), (uint32_t)lds,
+                                      m->d_bank, use_list ? c->d_block_list : nullptr, n_work_blocks, q->d_desc, q->n, lds_rows,
+                                      m->d_ratio_cnt, c->d_flagmask, c->d_flagged, c->d_n_flagged, c->d_k1_counters, P.head,
+                                      c->d_flagged_desc, c->rows_chunk_cap * 64, head_part);
   };
+  int rc;
   switch (P.form) {
-    case K1Form::kBatchedTail: screen(HammingScreenBody<WAVES, NW, 4>{}, k_hamming_screen<WAVES, NW, 4>, lds_bytes); break;
+    case K1Form::kBatchedTail: rc = screen(HammingScreenBody<WAVES, NW, 4>{}, k_hamming_screen<WAVES, NW, 4>, lds_bytes); break;
     // (four planes of lds_rows + 1 sixteen-byte pieces)
-    case K1Form::kMfma: screen(HammingScreenMfmaBody{}, k_hamming_screen_mfma, (size_t)(lds_rows + 1) * 64); break;
-    case K1Form::kShortlist: screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen_shortlist, lds_bytes); break;
-    default: screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen<WAVES, NW, 1>, lds_bytes); break;
+    case K1Form::kMfma: rc = screen(HammingScreenMfmaBody{}, k_hamming_screen_mfma, (size_t)(lds_rows + 1) * 64); break;
+    case K1Form::kShortlist: rc = screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen_shortlist, lds_bytes); break;
+    default: rc = screen(HammingScreenBody<WAVES, NW, 1>{}, k_hamming_screen<WAVES, NW, 1>, lds_bytes); break;
   }
+  SFM_RC(rc);
   c->k1_finish_ops = P.finish_ops;
-  SFM_HIP(hipGetLastError());
   // the exact pass over the flagged rows: chunks of 64 rows x kRowSlices query slices, see k_hamming_rows
   constexpr int RW = 4, RS = 8;
   const uint32_t per = (q->n + RS - 1) / RS;
   const uint32_t rows_lds = per < 1024 ? per : 1024;  // 64 KiB of LDS at most; a longer slice does not fit ...
   const uint32_t chunk_cap = per <= 1024 ? c->rows_chunk_cap : 0;  // ... and then every chunk takes the walking path
-  sfm_launch<HammingRowsBody<RW, RS>>(c, k_hamming_rows<RW, RS>, dim3(128 * RS), dim3(RW * 64), rows_lds * 64, m->d_bank,
-                                      q->d_desc, q->n, c->d_flagged, c->d_n_flagged, c->d_rows_scratch, c->d_rows_arrivals,
-                                      chunk_cap, rows_lds, c->d_flagged_desc, c->d_part);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<HammingRowsBody<RW, RS>>(c, k_hamming_rows<RW, RS>, dim3(128 * RS), dim3(RW * 64), rows_lds * 64,
+                                             m->d_bank, q->d_desc, q->n, c->d_flagged, c->d_n_flagged,
+                                             c->d_rows_scratch, c->d_rows_arrivals, chunk_cap, rows_lds,
+                                             c->d_flagged_desc, c->d_part);
 }
 
 // The host loop of ctx_match_putative on the device, for a view selection that never leaves the GPU (the BoW
@@ -393,9 +386,8 @@ __global__ __launch_bounds__(1024) void k_blocks_from_views(const uint32_t *__re
 
 int launch_blocks_from_views(Ctx *c, QueryPass &pass, const uint32_t *d_sel, uint32_t n_sel, uint32_t bound) {
   Map *m = c->map;
-  sfm_launch<BlocksFromViewsBody>(c, k_blocks_from_views, dim3(1), dim3(1024), 0, d_sel, n_sel, m->d_view_off,
-                                  c->d_view_sel, c->d_view_widx0, c->d_block_list, bound, c->d_flagmask);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(sfm_launch<BlocksFromViewsBody>(c, k_blocks_from_views, dim3(1), dim3(1024), 0, d_sel, n_sel, m->d_view_off,
+                                         c->d_view_sel, c->d_view_widx0, c->d_block_list, bound, c->d_flagmask));
   pass.flagmask_zeroed = true;
   return SFMLOC_OK;
 }
@@ -442,22 +434,18 @@ int launch_merge_ratio_compact(Ctx *c, const Query *q, QueryPass &pass, uint32_t
       pass.merge_deferred = true;
       return SFMLOC_OK;
     }
-    sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel));
     return SFMLOC_OK;
   }
-  sfm_launch<MergeRatioCompactBody>(c, k_merge_ratio_compact, dim3((n_sel + 3) / 4), dim3(256), 0, c->d_part,
-                     c->last_screened ? c->d_flagmask : nullptr, n_work_blocks, split, all_views ? nullptr : c->d_view_sel,
-                     all_views ? nullptr : c->d_view_widx0, n_sel, m->d_view_off, m->d_ratio_cnt, c->d_view_count,
-                     c->d_match_i, c->d_match_key);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<MergeRatioCompactBody>(c, k_merge_ratio_compact, dim3((n_sel + 3) / 4), dim3(256), 0, c->d_part,
+                                           c->last_screened ? c->d_flagmask : nullptr, n_work_blocks, split,
+                                           all_views ? nullptr : c->d_view_sel, all_views ? nullptr : c->d_view_widx0,
+                                           n_sel, m->d_view_off, m->d_ratio_cnt, c->d_view_count, c->d_match_i,
+                                           c->d_match_key);
 }
 
 int launch_merge_masked_now(Ctx *c, const MergeMaskedArgs &M, uint32_t n_sel) {
-  sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<MergeRatioMaskedBody>(c, k_merge_ratio_masked, dim3((n_sel + 3) / 4), dim3(256), 0, M, n_sel);
 }
 
 }  // namespace sfmloc

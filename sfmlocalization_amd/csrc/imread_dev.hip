@@ -368,12 +368,11 @@ int decode_jpeg(Imread *r, const uint8_t *bytes, size_t n, uint32_t want, int32_
   if (r->timing) SFM_HIP(hipEventRecord(r->t1, s));
   const ImreadHdr *dH = reinterpret_cast<const ImreadHdr *>(r->d_stage.get());
   const int16_t *d_coef = reinterpret_cast<const int16_t *>(r->d_stage.get() + kHdrBytes);
-  hipLaunchKernelGGL(k_idct, dim3((H->n_blocks + kIdctBlocksPerGroup - 1) / kIdctBlocksPerGroup), dim3(256), 0, s, dH, d_coef,
-                     r->d_plane.get());
+  SFM_RC(dev_launch(k_idct, dim3((H->n_blocks + kIdctBlocksPerGroup - 1) / kIdctBlocksPerGroup), dim3(256), 0, s, dH,
+                    d_coef, r->d_plane));
   if (r->timing) SFM_HIP(hipEventRecord(r->t2, s));
-  hipLaunchKernelGGL(k_upsample_color, dim3((j.w + 255) / 256, j.h), dim3(256), 0, s, dH, (const uint8_t *)r->d_plane.get(),
-                     r->d_gray.get(), r->d_bgr.get(), r->d_bgr2gray.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_upsample_color, dim3((j.w + 255) / 256, j.h), dim3(256), 0, s, dH, r->d_plane, r->d_gray,
+                    r->d_bgr, r->d_bgr2gray));
   if (r->timing) SFM_HIP(hipEventRecord(r->t3, s));
   SFM_HIP(hipEventRecord(r->done, s));
   r->w = j.w;

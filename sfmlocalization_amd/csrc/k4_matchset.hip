@@ -367,17 +367,15 @@ int launch_emit_candidates(Ctx *c, const Query *q, const QueryPass &pass, uint32
   if (n_sel == 0 || q->n == 0) return SFMLOC_OK;
   const uint32_t *sel = all_views ? nullptr : c->d_view_sel;
   const uint32_t *gj = c->geo_is_pairs ? c->d_geo_j : nullptr;
-  sfm_launch<EmitMinBody>(c, k_emit_min, dim3(n_sel), dim3(256), 0, sel, n_sel, m->d_view_off, m->d_view_id,
-                          c->d_view_count, c->d_match_i, c->d_match_key, c->d_geo_count, c->d_geo_idx, gj,
-                          m->d_row_landmark, c->d_best64, c->d_geo_dist, (uint32_t)m->params.min_putative, c->d_view_stats);
-  SFM_HIP(hipGetLastError());
-  sfm_launch<EmitWinBody>(c, k_emit_win, dim3(n_sel), dim3(256), 0, sel, n_sel, m->d_view_off, m->d_view_id, c->d_match_i,
-                          c->d_match_key, c->d_geo_count, c->d_geo_idx, gj, m->d_row_landmark, m->d_landmark_id,
-                          m->d_landmark_X, c->d_best64, c->d_geo_dist,
-                          reinterpret_cast<Candidate *>(c->d_cand_part + kPartHeaderBytes), c->cand_cap,
-                          reinterpret_cast<uint32_t *>(c->d_cand_part.get()), c->d_status);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  SFM_RC(sfm_launch<EmitMinBody>(c, k_emit_min, dim3(n_sel), dim3(256), 0, sel, n_sel, m->d_view_off, m->d_view_id,
+                                 c->d_view_count, c->d_match_i, c->d_match_key, c->d_geo_count, c->d_geo_idx, gj,
+                                 m->d_row_landmark, c->d_best64, c->d_geo_dist, (uint32_t)m->params.min_putative,
+                                 c->d_view_stats));
+  return sfm_launch<EmitWinBody>(c, k_emit_win, dim3(n_sel), dim3(256), 0, sel, n_sel, m->d_view_off, m->d_view_id,
+                                 c->d_match_i, c->d_match_key, c->d_geo_count, c->d_geo_idx, gj, m->d_row_landmark,
+                                 m->d_landmark_id, m->d_landmark_X, c->d_best64, c->d_geo_dist,
+                                 reinterpret_cast<Candidate *>(c->d_cand_part + kPartHeaderBytes), c->cand_cap,
+                                 reinterpret_cast<uint32_t *>(c->d_cand_part.get()), c->d_status);
 }
 
 // a context's candidate part -> a caller's buffer: the 16-byte header (true count) and the candidates that exist, at
@@ -400,10 +398,8 @@ __global__ __launch_bounds__(256) void k_export_part(const unsigned char *__rest
 }
 
 int launch_export_part(Ctx *c, void *dst_dev, uint32_t cap) {
-  sfm_launch<ExportPartBody>(c, k_export_part, dim3(8), dim3(256), 0, c->d_cand_part,
-                     reinterpret_cast<unsigned char *>(dst_dev), cap);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<ExportPartBody>(c, k_export_part, dim3(8), dim3(256), 0, c->d_cand_part,
+                                    reinterpret_cast<unsigned char *>(dst_dev), cap);
 }
 
 // a context's candidates appended to a batch's packed part (layout: PartLayout above).  One workgroup: lane 0 claims
@@ -447,10 +443,8 @@ uint64_t packed_part_bytes(uint32_t n_queries, uint32_t budget) {
 }
 
 int launch_export_packed(Ctx *c, void *dst_dev, uint32_t n_queries, uint32_t budget, uint32_t qi) {
-  sfm_launch<ExportPackedBody>(c, k_export_packed, dim3(1), dim3(256), 0, c->d_cand_part, c->cand_cap,
-                               reinterpret_cast<unsigned char *>(dst_dev), n_queries, budget, qi);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return sfm_launch<ExportPackedBody>(c, k_export_packed, dim3(1), dim3(256), 0, c->d_cand_part, c->cand_cap,
+                                      reinterpret_cast<unsigned char *>(dst_dev), n_queries, budget, qi);
 }
 
 // what a query's 2D-3D selection starts from when no k_query_reset ran for it (sfmloc_merge_begin, the staged API)
@@ -478,9 +472,8 @@ int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, cons
   L.qi = packed_qi;
   if (!pass.cleared) {  // (one launch, and one that a gang session can carry, instead of three memsets)
     const uint32_t nq1 = q->n ? q->n : 1;
-    sfm_launch<SelectResetBody>(c, k_select_reset, dim3((nq1 + 255) / 256), dim3(256), 0, c->d_best64, nq1, c->d_ms_n,
-                                reset_status ? c->d_status : (int *)nullptr);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<SelectResetBody>(c, k_select_reset, dim3((nq1 + 255) / 256), dim3(256), 0, c->d_best64, nq1,
+                                       c->d_ms_n, reset_status ? c->d_status : nullptr));
   }
   if (q->n == 0 || n_parts == 0) return SFMLOC_OK;
   const dim3 grid(16, n_parts < 64 ? n_parts : 64);
@@ -488,15 +481,15 @@ int launch_select_candidates(Ctx *c, const Query *q, const QueryPass &pass, cons
   // d_best64 their keys, so the minimum pass would change nothing
   const bool own_part = (parts == c->d_cand_part && n_parts == 1 && packed_b == 0 && pass.cleared);
   if (!own_part) {
-    sfm_launch<CandidatesMinBody>(c, k_candidates_min, grid, dim3(256), 0, parts, n_parts, part_bytes, cap, q->n,
-                                  c->d_best64, c->d_status, L);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(sfm_launch<CandidatesMinBody>(c, k_candidates_min, grid, dim3(256), 0, parts, n_parts, part_bytes, cap, q->n,
+                                         c->d_best64, c->d_status, L));
   }
-  sfm_launch<MatchSetFinishBody>(c, k_match_set_finish, dim3(1), dim3(1024), 0, parts, n_parts, part_bytes, cap,
-                                 c->d_best64, c->d_winner, q->n, q->d_kpt, c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark,
-                                 c->d_pt2d, c->d_pt3d, (c->map->intrinsic_type == 3 && !c->p3p_uncal) ? 1 : 0, c->map->focal, c->map->ppx,
-                                 c->map->ppy, c->map->k1, c->map->k2, c->map->k3, L, make_p3p_args(c, k5_in(c)));
-  SFM_HIP(hipGetLastError());
+  SFM_RC(sfm_launch<MatchSetFinishBody>(c, k_match_set_finish, dim3(1), dim3(1024), 0, parts, n_parts, part_bytes, cap,
+                                        c->d_best64, c->d_winner, q->n, q->d_kpt, c->d_ms_n, c->d_ms_qfeat,
+                                        c->d_ms_landmark, c->d_pt2d, c->d_pt3d,
+                                        (c->map->intrinsic_type == 3 && !c->p3p_uncal) ? 1 : 0, c->map->focal,
+                                        c->map->ppx, c->map->ppy, c->map->k1, c->map->k2, c->map->k3, L,
+                                        make_p3p_args(c, k5_in(c))));
   c->p3p_init_fused = true;  // launch_p3p_init is then a no-op for this query
   return SFMLOC_OK;
 }

@@ -110,16 +110,14 @@ int query_from_view(Map *m, uint32_t v, Query **out) {
   q->height = m->h_view_wh.size() > 2 * (size_t)v + 1 ? m->h_view_wh[2 * v + 1] : 0;
   const uint32_t n_pad = (n + 63) / 64 * 64;
   hipError_t e = hipSuccess;
-  int rc = SFMLOC_OK;  // (of the copies, which set their own error text)
+  int rc = SFMLOC_OK;  // (of the launch and the copies, which set their own error text)
   hipStream_t s = m->ctx0->stream;
   if (n_pad) {
     e = query_array(q->d_desc, (size_t)n_pad * 4);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_untile_view, dim3((n_pad * 4 + 255) / 256), dim3(256), 0, s, m->d_bank, r0, n, n_pad,
-                         q->d_desc);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && m->d_kpt) {
+    if (e == hipSuccess)
+      rc = dev_launch(k_untile_view, dim3((n_pad * 4 + 255) / 256), dim3(256), 0, s, m->d_bank, r0, n, n_pad,
+                      q->d_desc);
+    if (e == hipSuccess && !rc && m->d_kpt) {
       // the map's keypoints are the .feat values already (6 significant digits), for both uses
       e = query_array(q->d_kpt, n);
       if (e == hipSuccess) e = query_array(q->d_kpt6, n);
@@ -154,11 +152,9 @@ int match_one_to_one(Map *m, Query *q, const uint32_t *view_sel, uint32_t n_sel)
   if (all) n_sel = m->n_views;
   if (n_sel == 0 || q->n == 0) return SFMLOC_OK;
   const uint32_t words = (q->n + 31) / 32;
-  hipLaunchKernelGGL(k_one_to_one, dim3(n_sel), dim3(256), 2 * words * sizeof(uint32_t), c->stream,
-                     all ? nullptr : c->d_view_sel, n_sel, m->d_view_off, q->n, c->d_view_count, c->d_match_i,
-                     c->d_match_key);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return dev_launch(k_one_to_one, dim3(n_sel), dim3(256), 2 * words * sizeof(uint32_t), c->stream,
+                    all ? nullptr : c->d_view_sel, n_sel, m->d_view_off, q->n, c->d_view_count, c->d_match_i,
+                    c->d_match_key);
 }
 
 // the (filtered) list of one view from the map's context -> host vectors

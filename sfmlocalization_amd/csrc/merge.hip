@@ -554,9 +554,7 @@ sfmloc_merge_params merge_params(const sfmloc_merge_params *params) {
 
 int launch_inliers(CallScope *d, const double *dA, const double *dB, uint32_t n, const double *dM, const uint32_t *d_has,
                    double thres, uint32_t *d_idx, uint32_t *d_n) {
-  hipLaunchKernelGGL(k_merge_inliers, dim3(1), dim3(1024), 0, d->s, dA, dB, n, dM, d_has, thres, d_idx, d_n);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  return dev_launch(k_merge_inliers, dim3(1), dim3(1024), 0, d->s, dA, dB, n, dM, d_has, thres, d_idx, d_n);
 }
 
 template <int MODEL>
@@ -591,14 +589,12 @@ int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, con
   const uint64_t per = p.rounds_per_launch ? p.rounds_per_launch : kMergeLaunchRounds;
   for (uint64_t r0 = 0; r0 < rounds; r0 += per) {
     const uint32_t m = (uint32_t)std::min<uint64_t>(per, rounds - r0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_rounds<MODEL>), dim3((m + kMergeBlock - 1) / kMergeBlock), dim3(kMergeBlock),
-                       6 * tile * sizeof(double), d->s, dA, dB, n, thres, svd_ratio, (uint64_t)p.seed, stream, (uint32_t)r0, m,
-                       tile, d_best);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(HIP_KERNEL_NAME(k_merge_rounds<MODEL>), dim3((m + kMergeBlock - 1) / kMergeBlock),
+                      dim3(kMergeBlock), 6 * tile * sizeof(double), d->s, dA, dB, n, thres, svd_ratio, (uint64_t)p.seed,
+                      stream, (uint32_t)r0, m, tile, d_best));
   }
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_winner<MODEL>), dim3(1), dim3(64), 0, d->s, dA, dB, n, svd_ratio, (uint64_t)p.seed,
-                     stream, d_best, dM, d_info);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(HIP_KERNEL_NAME(k_merge_winner<MODEL>), dim3(1), dim3(64), 0, d->s, dA, dB, n, svd_ratio,
+                    (uint64_t)p.seed, stream, d_best, dM, d_info));
   MRG_TRY(launch_inliers(d, dA, dB, n, dM, d_info, thres, d_idx, d_n));
   uint32_t info[3] = {0, 0, 0}, n_inl = 0;
   SFM_RC(d_info.download(info, 3, d->s));
@@ -610,8 +606,8 @@ int ransac_impl(CallScope *d, const sfmloc_merge_params &p, const double *A, con
   SFM_CHECK(!info[0] || n_inl == info[2], SFMLOC_EHIP,
             "sfmloc_merge_ransac: the winner's model gives %u inliers where its round counted %u", n_inl, info[2]);
   if (info[0] && n_inl >= 4) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_fit<MODEL>), dim3(1), dim3(256), 0, d->s, dA, dB, d_idx, n_inl, dMf, d_ok);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(HIP_KERNEL_NAME(k_merge_fit<MODEL>), dim3(1), dim3(256), 0, d->s, dA, dB, d_idx, n_inl, dMf,
+                      d_ok));
     uint32_t ok = 0;
     SFM_RC(dMf.download(out->M, 12, d->s));
     SFM_RC(d_ok.download(&ok, 1, d->s));
@@ -638,8 +634,7 @@ int radix_select(CallScope *d, const uint64_t *dv, uint32_t n, uint32_t k, uint3
   const uint32_t blocks = std::min<uint32_t>((n + 255) / 256, 1024);
   for (int shift = 56; shift >= 0; shift -= 8) {
     SFM_RC(dev_zero(d_hist, 256, d->s));
-    hipLaunchKernelGGL(k_merge_hist, dim3(blocks), dim3(256), 0, d->s, dv, n, prefix, shift, d_hist);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_merge_hist, dim3(blocks), dim3(256), 0, d->s, dv, n, prefix, shift, d_hist));
     SFM_RC(dev_download(h, d_hist, 256, d->s));
     SFM_HIP(hipStreamSynchronize(d->s));
     uint32_t b = 0;
@@ -736,8 +731,7 @@ int sfmloc_merge_median_nn(const double *X, uint64_t n, const sfmloc_merge_param
       (rc = d_hist.alloc(nullptr, 256)))
     return rc;
   if ((rc = d.time_begin())) return rc;
-  hipLaunchKernelGGL(k_merge_nn, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, d.s, dX, (uint32_t)n, d_dist);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_merge_nn, dim3(((uint32_t)n + 255) / 256), dim3(256), 0, d.s, dX, (uint32_t)n, d_dist));
   // (distances are >= 0 and finite or +inf on overflow: they order as their bit patterns)
   uint64_t lo = 0, hi = 0;
   const uint32_t k_hi = (uint32_t)(n / 2);
@@ -771,9 +765,8 @@ int sfmloc_merge_transform(const double *M, double *R, uint64_t nR, double *X, u
   Mat34 T;
   memcpy(T.m, M, sizeof T.m);
   if ((rc = d.time_begin())) return rc;
-  hipLaunchKernelGGL(k_merge_transform, dim3((uint32_t)((nR + nX + 255) / 256)), dim3(256), 0, d.s, T, dR, (uint32_t)nR, dX,
-                     (uint32_t)nX);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_merge_transform, dim3((uint32_t)((nR + nX + 255) / 256)), dim3(256), 0, d.s, T, dR, (uint32_t)nR,
+                    dX, (uint32_t)nX));
   if ((rc = d.time_end())) return rc;
   if (nR) SFM_RC(dR.download(R, 9 * (size_t)nR, d.s));
   if (nX) SFM_RC(dX.download(X, 3 * (size_t)nX, d.s));

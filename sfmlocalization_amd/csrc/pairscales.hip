@@ -248,11 +248,12 @@ __global__ __launch_bounds__(kThreads) void k_ws_ratio(WsDev D, const sfmloc_wsc
   if (threadIdx.x == 0) rec[c].ratio = u2d(key[(n - 1) / 2]);
 }
 
-#define WS_LAUNCH(kernel, grid, block, ...)                                   \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, __VA_ARGS__);   \
-    ++rep.launches;                                                           \
-  } while (0)
+// a launch, counted in the call's report
+template <class... Ts, class... As>
+int ws_launch(sfmloc_wscales_report &rep, void (*kernel)(Ts...), uint32_t grid, uint32_t block, LaunchStream on, As &&...as) {
+  ++rep.launches;
+  return dev_launch(kernel, dim3(grid), dim3(block), 0, on, as...);
+}
 
 int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscales_options &opt,
                    const wscales_host::ViewPairs &vp, hipStream_t s, Wscales *w) {
@@ -300,34 +301,35 @@ int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscale
   const uint32_t ge = ((uint32_t)n_ent + 255) / 256;
 
   // sfmloc.h "depths", "lists"
-  WS_LAUNCH(k_ws_depths, n_pairs, 256, D, d_ka.get(), d_va.get());
+  SFM_RC(ws_launch(rep, k_ws_depths, n_pairs, 256, s, D, d_ka, d_va));
   uint32_t *ks = d_ka, *vs = d_va, *ko = d_kb, *vo = d_vb;  // (ks, vs): where the sorted pairs are; (ko, vo): the scratch
   auto sort = [&](int bits) {
     rep.launches += 3 * (uint32_t)((bits + 7) / 8);
-    if (radix_sort_pairs(ks, vs, ko, vo, (uint32_t)n_ent, bits, d_hist, s)) {
+    bool swapped = false;
+    SFM_RC(radix_sort_pairs(ks, vs, ko, vo, (uint32_t)n_ent, bits, d_hist, s, &swapped));
+    if (swapped) {
       std::swap(ks, ko);
       std::swap(vs, vo);
     }
+    return (int)SFMLOC_OK;
   };
-  sort(radix_key_bits(max_feat ? max_feat - 1 : 0));
-  WS_LAUNCH(k_ws_segkeys, ge, 256, D, (const uint32_t *)vs, ko);
+  SFM_RC(sort(radix_key_bits(max_feat ? max_feat - 1 : 0)));
+  SFM_RC(ws_launch(rep, k_ws_segkeys, ge, 256, s, D, vs, ko));
   std::swap(ks, ko);  // (the sorted features are not needed again: k_ws_gather reads the entries')
-  sort(radix_key_bits(2 * n_pairs));
-  WS_LAUNCH(k_ws_gather, ge, 256, D, (const uint32_t *)vs, d_feat_s.get(), d_z_s.get());
-  WS_LAUNCH(k_ws_bounds, (2 * n_pairs + 1 + 255) / 256, 256, D, (const uint32_t *)ks, d_seg_begin.get());
+  SFM_RC(sort(radix_key_bits(2 * n_pairs)));
+  SFM_RC(ws_launch(rep, k_ws_gather, ge, 256, s, D, vs, d_feat_s, d_z_s));
+  SFM_RC(ws_launch(rep, k_ws_bounds, (2 * n_pairs + 1 + 255) / 256, 256, s, D, ks, d_seg_begin));
   // sfmloc.h "candidates", "count"
-  WS_LAUNCH(k_ws_enum, D.nb_view + (D.n_heavy + 3) / 4, 256, D, d_rec.get());
-  WS_LAUNCH(k_ws_count, (n_cand + 3) / 4, 256, D, d_rec.get(), n_cand);
+  SFM_RC(ws_launch(rep, k_ws_enum, D.nb_view + (D.n_heavy + 3) / 4, 256, s, D, d_rec));
+  SFM_RC(ws_launch(rep, k_ws_count, (n_cand + 3) / 4, 256, s, D, d_rec, n_cand));
   // the choice and the order of the records, on the device: flag, scan, compact; then three stable sorts of the kept
   // records' places, by view, by l and by k
   DevBuf<uint32_t> d_place;
   SFM_RC(d_place.alloc(nullptr, (size_t)n_cand + 1));
   SFM_RC(d_out.alloc(nullptr, n_cand));
-  WS_LAUNCH(k_ws_flag, n_cand / 256 + 1, 256, (const sfmloc_wscale *)d_rec, n_cand, opt.min_shared, d_place.get());
-  WS_LAUNCH(k_scan_excl, 1, 1024, d_place.get(), n_cand + 1);
-  WS_LAUNCH(k_ws_compact, (n_cand + 255) / 256, 256, (const sfmloc_wscale *)d_rec, n_cand, opt.min_shared,
-            (const uint32_t *)d_place, d_out.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(ws_launch(rep, k_ws_flag, n_cand / 256 + 1, 256, s, d_rec, n_cand, opt.min_shared, d_place));
+  SFM_RC(ws_launch(rep, k_scan_excl, 1, 1024, s, d_place, n_cand + 1));
+  SFM_RC(ws_launch(rep, k_ws_compact, (n_cand + 255) / 256, 256, s, d_rec, n_cand, opt.min_shared, d_place, d_out));
   uint32_t n_yield = 0, n_rec = 0;
   SFM_RC(d_place.download(&n_rec, 1, s, n_cand));
   SFM_RC(d_seg_begin.download(&n_yield, 1, s, 2 * P));
@@ -346,18 +348,17 @@ int wscales_device(const PairScene &sc, const PairPoses &po, const sfmloc_wscale
     uint32_t *rk = d_k0, *rv = d_v0, *ok = d_k1, *ov = d_v1;  // (rk, rv): keys and places in the order so far
     const int bits[3] = {radix_key_bits(n_views - 1), radix_key_bits(n_pairs - 1), radix_key_bits(n_pairs - 1)};
     for (int field = 0; field < 3; ++field) {
-      WS_LAUNCH(k_ws_keys, (n_rec + 255) / 256, 256, (const sfmloc_wscale *)d_out, n_rec,
-                field ? (const uint32_t *)rv : (const uint32_t *)nullptr, field, rk, rv);
+      SFM_RC(ws_launch(rep, k_ws_keys, (n_rec + 255) / 256, 256, s, d_out, n_rec, field ? rv : nullptr, field, rk, rv));
       rep.launches += 3 * (uint32_t)((bits[field] + 7) / 8);
-      if (radix_sort_pairs(rk, rv, ok, ov, n_rec, bits[field], d_h, s)) {
+      bool swapped = false;
+      SFM_RC(radix_sort_pairs(rk, rv, ok, ov, n_rec, bits[field], d_h, s, &swapped));
+      if (swapped) {
         std::swap(rk, ok);
         std::swap(rv, ov);
       }
     }
     // sfmloc.h "ratio"
-    WS_LAUNCH(k_ws_ratio, n_rec, kThreads, D, (const sfmloc_wscale *)d_out, (const uint32_t *)rv, d_final.get(), n_rec,
-              opt.max_shared);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(ws_launch(rep, k_ws_ratio, n_rec, kThreads, s, D, d_out, rv, d_final, n_rec, opt.max_shared));
     SFM_RC(d_final.download(rec.data(), rec.size(), s));
     SFM_HIP(hipStreamSynchronize(s));
   }

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sfmloc_internal.h"
+
 namespace sfmloc {
 namespace {
 
@@ -92,15 +94,15 @@ inline int radix_key_bits(uint32_t max_key) {
 inline size_t radix_hist_entries(uint64_t n) { return 256 * (size_t)((n + kRadixBlock - 1) / kRadixBlock); }
 
 // sorts n pairs by the low `bits` bits of the key, ping-ponging between (k0, v0) and the scratch pair (k1, v1); hist holds
-// radix_hist_entries(n).  Returns true when the result ended in (k1, v1).  Launch errors: hipGetLastError afterwards.
-inline bool radix_sort_pairs(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint32_t n, int bits, uint32_t *hist,
-                             hipStream_t s) {
+// radix_hist_entries(n).  *in_scratch: the result ended in (k1, v1).
+inline int radix_sort_pairs(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint32_t n, int bits, uint32_t *hist,
+                            hipStream_t s, bool *in_scratch) {
   const uint32_t nb = (n + kRadixBlock - 1) / kRadixBlock;
   uint32_t *kin = k0, *vin = v0, *kout = k1, *vout = v1;
   for (int shift = 0; shift < bits && n > 0; shift += 8) {
-    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(kRadixBlock), 0, s, kin, n, shift, hist, nb);
-    hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, hist, 256u * nb);
-    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(kRadixBlock), 0, s, kin, vin, n, shift, hist, nb, kout, vout);
+    SFM_RC(dev_launch(k_radix_hist, dim3(nb), dim3(kRadixBlock), 0, s, kin, n, shift, hist, nb));
+    SFM_RC(dev_launch(k_scan_excl, dim3(1), dim3(1024), 0, s, hist, 256u * nb));
+    SFM_RC(dev_launch(k_radix_scatter, dim3(nb), dim3(kRadixBlock), 0, s, kin, vin, n, shift, hist, nb, kout, vout));
     uint32_t *t = kin;
     kin = kout;
     kout = t;
@@ -108,7 +110,8 @@ inline bool radix_sort_pairs(uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t 
     vin = vout;
     vout = t;
   }
-  return kin != k0;
+  *in_scratch = kin != k0;
+  return SFMLOC_OK;
 }
 
 }  // namespace

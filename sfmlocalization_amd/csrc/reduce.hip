@@ -348,13 +348,11 @@ int scan_exclusive(CallScope *d, uint32_t *v, uint32_t n, DevBuf<uint32_t> *sums
   const uint32_t blocks = (n + kScanChunk - 1) / kScanChunk;
   const int rc = sums->alloc(nullptr, blocks);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_reduce_scan_chunk, dim3(blocks), dim3(256), 0, d->s, v, n, sums->get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_scan_chunk, dim3(blocks), dim3(256), 0, d->s, v, n, sums->get()));
   if (blocks > 1) {
     const int rc2 = scan_exclusive(d, *sums, blocks, sums + 1);
     if (rc2) return rc2;
-    hipLaunchKernelGGL(k_reduce_scan_add, lanes(n), dim3(256), 0, d->s, v, n, sums->get());
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_reduce_scan_add, lanes(n), dim3(256), 0, d->s, v, n, sums->get()));
   }
   return SFMLOC_OK;
 }
@@ -391,8 +389,7 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   SFM_RC(d_box.fill(0xFF, 3, d->s));
   SFM_RC(d_box.zero(3, d->s, 3));
   RDC_TRY(d->time_begin());
-  hipLaunchKernelGGL(k_reduce_global, lanes(n), dim3(256), 0, d->s, T, dX, n, dG, d_box);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_global, lanes(n), dim3(256), 0, d->s, T, dX, n, dG, d_box));
   unsigned long long box[6];
   SFM_RC(d_box.download(box, 6, d->s));
   SFM_HIP(hipStreamSynchronize(d->s));
@@ -413,20 +410,18 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
 
   RDC_TRY(d_key.alloc(nullptr, n));
   RDC_TRY(zeros(d, d_start, (size_t)buckets + 1));
-  hipLaunchKernelGGL(k_reduce_cell, lanes(n), dim3(256), 0, d->s, gr, dG, n, d_key, d_start);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_cell, lanes(n), dim3(256), 0, d->s, gr, dG, n, d_key, d_start));
   RDC_TRY(scan_exclusive(d, d_start, buckets + 1, scan_tmp[0]));
   RDC_TRY(zeros(d, d_fill, buckets));
   RDC_TRY(dsG.alloc(nullptr, 3 * (size_t)n));
   RDC_TRY(d_skey.alloc(nullptr, n));
   RDC_TRY(d_sidx.alloc(nullptr, n));
-  hipLaunchKernelGGL(k_reduce_scatter, lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, d_start, d_fill, dsG, d_skey, d_sidx);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_scatter, lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, d_start, d_fill, dsG, d_skey,
+                    d_sidx));
 
   RDC_TRY(zeros(d, d_rowoff, (size_t)n + 1));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_rows<false>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn, d_start,
-                     dsG, d_skey, d_sidx, d_rowoff, (const uint32_t *)nullptr, (uint32_t *)nullptr, (uint64_t *)nullptr);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(HIP_KERNEL_NAME(k_reduce_rows<false>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn,
+                    d_start, dsG, d_skey, d_sidx, d_rowoff, nullptr, nullptr, nullptr));
   // (row counts sum to at most n (knn - 1) or n (n - 1) / 2: the total may pass 2^32, so it is added up here in 64 bits
   // before the 32-bit scan runs)
   std::vector<uint32_t> rowcnt(n);
@@ -442,17 +437,15 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   RDC_TRY(d_dtmp.alloc(nullptr, pairs1));
   RDC_TRY(d_col.alloc(nullptr, pairs1));
   RDC_TRY(d_dbits.alloc(nullptr, pairs1));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_rows<true>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn, d_start,
-                     dsG, d_skey, d_sidx, (uint32_t *)nullptr, d_rowoff, d_ctmp, d_dtmp);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(HIP_KERNEL_NAME(k_reduce_rows<true>), lanes(n), dim3(256), 0, d->s, gr, dG, d_key, n, thres, knn,
+                    d_start, dsG, d_skey, d_sidx, nullptr, d_rowoff, d_ctmp, d_dtmp));
   RDC_TRY(zeros(d, d_roff, (size_t)n + 1));
-  hipLaunchKernelGGL(k_reduce_rowsort, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_ctmp, d_dtmp, d_col, d_dbits, d_roff);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_rowsort, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_ctmp, d_dtmp, d_col, d_dbits,
+                    d_roff));
   RDC_TRY(scan_exclusive(d, d_roff, n + 1, scan_tmp[2]));
   RDC_TRY(zeros(d, d_rfill, n));
   RDC_TRY(d_rlist.alloc(nullptr, pairs1));
-  hipLaunchKernelGGL(k_reduce_transpose, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_roff, d_rfill, d_rlist);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reduce_transpose, lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_roff, d_rfill, d_rlist));
 
   RDC_TRY(zeros(d, d_stamp, n));
   RDC_TRY(d_owner.alloc(nullptr, n));
@@ -463,9 +456,8 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   const uint32_t per = p.rounds_per_launch ? p.rounds_per_launch : kResolvePasses;
   for (uint32_t pass = 1; state[0] != 0;) {  // each pass decides at least the smallest undecided index
     for (uint32_t k = 0; k < per; ++k, ++pass) {
-      hipLaunchKernelGGL(k_reduce_resolve, lanes(n), dim3(256), 0, d->s, n, pass, d_roff, d_rlist, dG, d_stamp, d_owner, d_dist,
-                         d_state);
-      SFM_HIP(hipGetLastError());
+      SFM_RC(dev_launch(k_reduce_resolve, lanes(n), dim3(256), 0, d->s, n, pass, d_roff, d_rlist, dG, d_stamp, d_owner,
+                        d_dist, d_state));
     }
     SFM_RC(d_state.download(state, 2, d->s));
     SFM_HIP(hipStreamSynchronize(d->s));
@@ -475,13 +467,11 @@ int reduce_impl(CallScope *d, const sfmloc_merge_params &p, const double *X, uin
   RDC_TRY(zeros(d, d_ooff, (size_t)n + 1));
   RDC_TRY(d_order.alloc(nullptr, n));
   SFM_RC(d_order.fill(0xFF, n, d->s));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_order<false>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner, d_ooff,
-                     (const uint32_t *)nullptr, (uint32_t *)nullptr);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(HIP_KERNEL_NAME(k_reduce_order<false>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner,
+                    d_ooff, nullptr, nullptr));
   RDC_TRY(scan_exclusive(d, d_ooff, n + 1, scan_tmp[3]));
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_reduce_order<true>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner,
-                     (uint32_t *)nullptr, d_ooff, d_order);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(HIP_KERNEL_NAME(k_reduce_order<true>), lanes(n), dim3(256), 0, d->s, n, d_rowoff, d_col, d_owner,
+                    nullptr, d_ooff, d_order));
   RDC_TRY(d->time_end());
   // the outputs, into the call's own buffers first: nothing of the caller's is written before every step has succeeded
   std::vector<uint32_t> h_owner(n), h_order(n);

@@ -181,10 +181,8 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
     if (unposed.empty()) break;
     SFM_RC(S.d_unposed.upload(unposed.data(), unposed.size(), s));
     const SfmDev D = sfm_dev(h);
-    hipLaunchKernelGGL(k_reg_compact, dim3((unsigned)unposed.size()), dim3(kRegBlock), 0, s,
-                       (const uint32_t *)S.d_unposed, D.vlist, D.view_off, D.obs_lm, (const uint8_t *)D.lm_stage,
-                       S.d_clist.get(), S.d_cnt.get());
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_reg_compact, dim3((unsigned)unposed.size()), dim3(kRegBlock), 0, s, S.d_unposed, D.vlist,
+                      D.view_off, D.obs_lm, D.lm_stage, S.d_clist, S.d_cnt));
     SFM_RC(S.d_cnt.download(cnt.data(), n_views, s));
     SFM_HIP(hipStreamSynchronize(s));
     // candidates
@@ -254,15 +252,12 @@ int reg_run(Sfm &h, const sfmloc_register_options &opt, sfmloc_register_report *
     E.thr = opt.residual_px;
     E.extended = S.d_extended;
     if (longest)
-      hipLaunchKernelGGL(k_reg_extend, dim3((longest + kRegBlock - 1) / kRegBlock, (unsigned)unposed.size()),
-                         dim3(kRegBlock), 0, s, E);
-    SFM_HIP(hipGetLastError());
+      SFM_RC(dev_launch(k_reg_extend, dim3((longest + kRegBlock - 1) / kRegBlock, (unsigned)unposed.size()),
+                        dim3(kRegBlock), 0, s, E));
     // new landmarks
     if (n_lm)
-      hipLaunchKernelGGL(k_reg_select, dim3((n_lm + 255) / 256), dim3(256), 0, s, n_lm, D.obs_off, D.obs_view,
-                         D.view_pose, (const uint8_t *)D.pose_valid, (const uint8_t *)S.d_view_new,
-                         (const uint8_t *)D.lm_stage, S.d_select.get());
-    SFM_HIP(hipGetLastError());
+      SFM_RC(dev_launch(k_reg_select, dim3((n_lm + 255) / 256), dim3(256), 0, s, n_lm, D.obs_off, D.obs_view,
+                        D.view_pose, D.pose_valid, S.d_view_new, D.lm_stage, S.d_select));
     SFM_RC(S.d_extended.download(&S.h_extended, 1, s));
     sfmloc_triangulate_options to;
     memset(&to, 0, sizeof to);
@@ -351,9 +346,8 @@ int sfmloc_sfm_register_counts(const sfmloc_sfm *hh, uint32_t *c) {
   SFM_RC(d_c.alloc(nullptr, h->n_views));
   const SfmDev D = sfm_dev(*h);
   hipStream_t s = h->s;
-  hipLaunchKernelGGL(k_reg_counts, dim3(h->n_views), dim3(kRegBlock), 0, s, h->n_views, D.vlist, D.view_off, D.obs_lm,
-                     (const uint8_t *)D.lm_stage, d_c.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_reg_counts, dim3(h->n_views), dim3(kRegBlock), 0, s, h->n_views, D.vlist, D.view_off, D.obs_lm,
+                    D.lm_stage, d_c));
   SFM_RC(d_c.download(c, h->n_views, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;

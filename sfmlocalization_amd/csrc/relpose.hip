@@ -405,9 +405,8 @@ int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const
   SFM_RC(d_L10.alloc(nullptr, kRpL10));
   SFM_RC(d_res.alloc(nullptr, n_pairs));
   SFM_RC(d_res.zero(n_pairs, s));  // (the records' padding too)
-  hipLaunchKernelGGL(k_rp_fill_log10, dim3((kRpL10 + 255) / 256), dim3(256), 0, s, d_L10.get(), kRpL10);
-  hipLaunchKernelGGL(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, scene.dev(), d_bear.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_rp_fill_log10, dim3((kRpL10 + 255) / 256), dim3(256), 0, s, d_L10, kRpL10));
+  SFM_RC(dev_launch(k_rp_bearings, dim3(n_pairs), dim3(256), 0, s, scene.dev(), d_bear));
   RpArgs A{};
   static_cast<PairDev &>(A) = scene.dev();
   A.n_iter = (int)opt.max_iteration;
@@ -417,11 +416,7 @@ int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const
   A.L10 = d_L10;
   A.res = d_res;
   A.inl = d_inl;
-  // (per call, not once per process: the attribute belongs to the device that is current, and `device` is the call's)
-  SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_relpose), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)sizeof(RpShared)));
-  hipLaunchKernelGGL(k_relpose, dim3(n_pairs), dim3(kThreads), sizeof(RpShared), s, A);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_relpose, dim3(n_pairs), dim3(kThreads), sizeof(RpShared), s, A));
   DevBuf<uint64_t> d_key;
   DevBuf<uint32_t> d_idx;
   DevBuf<int32_t> d_vi, d_bi;
@@ -447,10 +442,7 @@ int relpose_device(const PairScene &sc, const sfmloc_relpose_options &opt, const
     W.logc_n = d_ln;
     W.logc_k = d_lk;
     W.slot_m = slot_m;
-    SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_relpose_large), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(RpLargeShared)));
-    hipLaunchKernelGGL(k_relpose_large, dim3((unsigned)n_slots), dim3(kThreads), sizeof(RpLargeShared), s, A, W);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_relpose_large, dim3((unsigned)n_slots), dim3(kThreads), sizeof(RpLargeShared), s, A, W));
   }
   std::vector<uint32_t> inl((size_t)total);
   SFM_RC(d_res.download(r->res.data(), n_pairs, s));
@@ -533,8 +525,7 @@ int sfmloc_debug_five_point(int device, const double *in, int n, double *out) {
   DevBuf<double> d_in, d_out;
   if ((rc = dev_upload(nullptr, d_in, in, 20 * (size_t)n, d.s))) return rc;
   if ((rc = d_out.alloc(nullptr, 91 * (size_t)n))) return rc;
-  hipLaunchKernelGGL(k_debug_five_point, dim3((n + 3) / 4), dim3(64), 0, d.s, (const double *)d_in, n, d_out.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_debug_five_point, dim3((n + 3) / 4), dim3(64), 0, d.s, d_in, n, d_out));
   SFM_RC(d_out.download(out, 91 * (size_t)n, d.s));
   SFM_HIP(hipStreamSynchronize(d.s));
   return SFMLOC_OK;

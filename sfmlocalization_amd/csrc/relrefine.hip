@@ -433,8 +433,7 @@ int relrefine_device(const PairScene &sc, const PairPoses &po, const sfmloc_relr
   D.max_steps = opt.max_steps;
   D.min_points = opt.min_points;
   D.bear = d_bear, D.pts = d_pts, D.trial = d_trial, D.res = d_res;
-  hipLaunchKernelGGL(k_relrefine, dim3(sc.n_pairs), dim3(kRrThreads), 0, s, D);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_relrefine, dim3(sc.n_pairs), dim3(kRrThreads), 0, s, D));
   SFM_RC(d_res.download(r->res.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;

@@ -172,8 +172,7 @@ int seed_device(const PairScene &sc, const PairPoses &po, const sfmloc_seed_opti
   D.key = d_key, D.rec = d_rec;
   D.min_used = opt.min_used;
   D.max_cos = opt.max_cos, D.min_cos = opt.min_cos;
-  hipLaunchKernelGGL(k_seed_scores, dim3(sc.n_pairs), dim3(kSdThreads), 0, s, D);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_seed_scores, dim3(sc.n_pairs), dim3(kSdThreads), 0, s, D));
   SFM_RC(d_rec.download(r->rec.data(), P, s));
   SFM_HIP(hipStreamSynchronize(s));
   return SFMLOC_OK;

@@ -198,10 +198,10 @@ int sfm_resect_gang(Sfm &h, const std::vector<uint32_t> &todo, const std::vector
     for (uint32_t i = 0; i < m && rc == SFMLOC_OK; ++i) {
       Ctx *c = member(i);
       const uint32_t k = todo[g0 + i];
-      sfm_launch<SfmFillBody<kUndistort>>(c, k_sfm_fill<kUndistort>, dim3(1), dim3(256), 0, d_list, d.view_off, d_cnt,
-                                          k, h.h_view_intr[k], d.obs_lm, d.obs_x, (const double *)d.lm_X, d.lm_id,
-                                          d.intr_type, (const double *)d.intr, c->d_ms_n, c->d_ms_qfeat,
-                                          c->d_ms_landmark, c->d_pt2d, c->d_pt3d);
+      SFM_RC(sfm_launch<SfmFillBody<kUndistort>>(c, k_sfm_fill<kUndistort>, dim3(1), dim3(256), 0, d_list, d.view_off,
+                                                 d_cnt, k, h.h_view_intr[k], d.obs_lm, d.obs_x, d.lm_X, d.lm_id,
+                                                 d.intr_type, d.intr, c->d_ms_n, c->d_ms_qfeat, c->d_ms_landmark,
+                                                 c->d_pt2d, c->d_pt3d));
       c->p3p_init_fused = false;  // K5's init reads the count the fill wrote
       rc = ctx_resection_begin(c);
     }

@@ -17,6 +17,7 @@
 #include "devmem.h"
 #include "forms.h"
 #include "gang.h"
+#include "launch.h"
 
 namespace sfmloc {
 
@@ -29,13 +30,7 @@ inline int env_int(const char *name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
-// the SFMLOC code of a failed HIP call
-inline int hip_code(hipError_t e) {
-  return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SFMLOC_ENODEV
-         : (e == hipErrorOutOfMemory)                          ? SFMLOC_ENOMEM
-                                                               : SFMLOC_EHIP;
-}
-
+// (hip_code, the SFMLOC code of a failed HIP call: launch.h)
 #define SFM_HIP(call)                                                                          \
   do {                                                                                         \
     hipError_t e_ = (call);                                                                    \
@@ -53,11 +48,12 @@ inline int hip_code(hipError_t e) {
     }                                  \
   } while (0)
 
-// a step that answers an SFMLOC code: on anything but SFMLOC_OK the function returns it
-#define SFM_RC(call)        \
-  do {                      \
-    const int rc_ = (call); \
-    if (rc_) return rc_;    \
+// a step that answers an SFMLOC code: on anything but SFMLOC_OK the function returns it (variadic only so that the
+// commas of a template argument list need no parentheses)
+#define SFM_RC(...)               \
+  do {                            \
+    const int rc_ = (__VA_ARGS__); \
+    if (rc_) return rc_;          \
   } while (0)
 
 // The shell of an entry point that hands out a fresh handle: `fill` fills a new host-side Handle and answers an SFMLOC
@@ -429,23 +425,27 @@ struct Ctx : GangMember {  // (gang.h: stream, gang_recs, gang_head)
   std::vector<EventPair> event_pool;
 };
 
-// A launch of a kernel that has a gang form (Body: the kernel's body, gang.h): issued at once on the context's stream,
-// or recorded when the context is a member of a gang session.  `single` is the kernel itself.
+// The gang form of dev_launch (launch.h), for a kernel that has one (Body: the kernel's body, gang.h): dev_launch on the
+// member's stream, or -- while the member records for a gang session -- a record, which answers SFMLOC_OK: gang_flush
+// launches it and reports.  `single` is the kernel itself.
 template <class... Ts, size_t... Is, class... As>
 inline void gang_store_args(void *dst, std::index_sequence<Is...>, As &&...as) {
   new (dst) Tup<Ts...>{TupLeaf<Is, Ts>{static_cast<Ts>(as)}...};
 }
+struct LaunchMember {  // the member, and where the launch is written (LaunchSite, launch.h)
+  GangMember *m;
+  LaunchSite at;
+  LaunchMember(GangMember *m_, const char *file = __builtin_FILE(), int line = __builtin_LINE()) : m(m_), at{file, line} {}
+};
 template <class Body, class... Ts, class... As>
-inline void sfm_launch(GangMember *c, void (*single)(Ts...), dim3 grid, dim3 block, uint32_t shmem, As &&...as) {
-  if (!c->stream.gang) {
-    hipLaunchKernelGGL(single, grid, block, shmem, (hipStream_t)c->stream, static_cast<Ts>(as)...);
-    return;
-  }
+inline int sfm_launch(LaunchMember on, void (*single)(Ts...), dim3 grid, dim3 block, uint32_t shmem, As &&...as) {
+  GangMember *c = on.m;
+  if (!c->stream.gang) return dev_launch(single, grid, block, shmem, LaunchStream((hipStream_t)c->stream, on.at, c->device), as...);
   try {  // (a record is ~2 KB; no exception may cross the C ABI: the session's end reports it -- gang_flush)
     c->gang_recs.emplace_back();
   } catch (const std::bad_alloc &) {
     c->gang_oom = true;
-    return;
+    return SFMLOC_OK;
   }
   GangRec &r = c->gang_recs.back();
   r.key = GangLaunch<Body, Ts...>::key();
@@ -457,6 +457,7 @@ inline void sfm_launch(GangMember *c, void (*single)(Ts...), dim3 grid, dim3 blo
   r.block = block;
   r.shmem = shmem;
   gang_store_args<Ts...>(r.args, std::index_sequence_for<Ts...>{}, as...);
+  return SFMLOC_OK;
 }
 
 // what K5's plans (forms.h) are made from: the query the context is about to resect for

@@ -157,11 +157,9 @@ __global__ __launch_bounds__(256) void k_trk_emit(const uint32_t *__restrict__ n
 
 int scan_excl(uint32_t *a, uint32_t n, uint32_t *sums, hipStream_t s) {
   const uint32_t nb = (n + 1023) / 1024;
-  hipLaunchKernelGGL(k_trk_scan_block, dim3(nb), dim3(1024), 0, s, a, n, sums);
-  hipLaunchKernelGGL(k_scan_excl, dim3(1), dim3(1024), 0, s, sums, nb);
-  hipLaunchKernelGGL(k_trk_scan_add, dim3(nb), dim3(1024), 0, s, a, n, (const uint32_t *)sums);
-  SFM_HIP(hipGetLastError());
-  return SFMLOC_OK;
+  SFM_RC(dev_launch(k_trk_scan_block, dim3(nb), dim3(1024), 0, s, a, n, sums));
+  SFM_RC(dev_launch(k_scan_excl, dim3(1), dim3(1024), 0, s, sums, nb));
+  return dev_launch(k_trk_scan_add, dim3(nb), dim3(1024), 0, s, a, n, sums);
 }
 
 int read_u32(uint32_t *out, const uint32_t *d, hipStream_t s) {
@@ -187,15 +185,12 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_ea.upload(ea.data(), m_edges, s));
   SFM_RC(d_eb.upload(eb.data(), m_edges, s));
   const dim3 gn((n + 1 + 255) / 256), ge((m_edges + 255) / 256), b256(256);
-  hipLaunchKernelGGL(k_trk_init, gn, b256, 0, s, d_parent.get(), d_touched.get(), n);
-  hipLaunchKernelGGL(k_trk_mark, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_touched.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_trk_init, gn, b256, 0, s, d_parent, d_touched, n));
+  SFM_RC(dev_launch(k_trk_mark, ge, b256, 0, s, d_ea, d_eb, m_edges, d_touched));
   for (;;) {  // sfmloc.h "components": until a pass hooks nothing
     SFM_RC(d_flag.zero(1, s));
-    hipLaunchKernelGGL(k_graph_hook, ge, b256, 0, s, (const uint32_t *)d_ea, (const uint32_t *)d_eb, m_edges, d_parent.get(),
-                       d_flag.get());
-    hipLaunchKernelGGL(k_graph_jump, gn, b256, 0, s, d_parent.get(), n);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_graph_hook, ge, b256, 0, s, d_ea, d_eb, m_edges, d_parent, d_flag));
+    SFM_RC(dev_launch(k_graph_jump, gn, b256, 0, s, d_parent, n));
     uint32_t changed = 0;
     SFM_RC(read_u32(&changed, d_flag, s));
     if (!changed) break;
@@ -213,16 +208,12 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_node2.alloc(nullptr, m));
   SFM_RC(d_hist.alloc(nullptr, radix_hist_entries(m)));
   SFM_RC(d_ex.alloc(nullptr, (size_t)m + 1));
-  hipLaunchKernelGGL(k_trk_compact, gn, b256, 0, s, (const uint32_t *)d_touched, (const uint32_t *)d_parent, n,
-                     d_key.get(), d_node.get());
-  SFM_HIP(hipGetLastError());
-  const bool swapped =
-      radix_sort_pairs(d_key, d_node, d_key2, d_node2, m, radix_key_bits(n - 1), d_hist, s);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_trk_compact, gn, b256, 0, s, d_touched, d_parent, n, d_key, d_node));
+  bool swapped = false;
+  SFM_RC(radix_sort_pairs(d_key, d_node, d_key2, d_node2, m, radix_key_bits(n - 1), d_hist, s, &swapped));
   const uint32_t *key = swapped ? d_key2.get() : d_key.get(), *node = swapped ? d_node2.get() : d_node.get();
   const dim3 gm((m + 1 + 255) / 256);
-  hipLaunchKernelGGL(k_trk_heads, gm, b256, 0, s, key, m, d_ex.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_trk_heads, gm, b256, 0, s, key, m, d_ex));
   SFM_RC(scan_excl(d_ex, m + 1, d_sums, s));
   uint32_t n_comp = 0;
   SFM_RC(read_u32(&n_comp, d_ex.get() + m, s));
@@ -235,11 +226,9 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_toff.alloc(nullptr, (size_t)n_comp + 1));
   SFM_RC(d_conf.zero(n_comp, s));
   SFM_RC(d_flag.zero(4, s));
-  hipLaunchKernelGGL(k_trk_components, gm, b256, 0, s, key, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_voff,
-                     n_views, d_start.get(), d_conf.get());
-  hipLaunchKernelGGL(k_trk_filter, dim3((n_comp + 1 + 255) / 256), b256, 0, s, (const uint32_t *)d_start,
-                     (const uint32_t *)d_conf, n_comp, min_length, d_tid.get(), d_toff.get(), d_flag.get() + 1);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_trk_components, gm, b256, 0, s, key, node, d_ex, m, d_voff, n_views, d_start, d_conf));
+  SFM_RC(dev_launch(k_trk_filter, dim3((n_comp + 1 + 255) / 256), b256, 0, s, d_start, d_conf, n_comp, min_length,
+                    d_tid, d_toff, d_flag.get() + 1));
   SFM_RC(scan_excl(d_tid, n_comp + 1, d_sums, s));
   SFM_RC(scan_excl(d_toff, n_comp + 1, d_sums, s));
   uint32_t n_tracks = 0, n_rows = 0, cnt[4] = {0, 0, 0, 0};
@@ -250,10 +239,8 @@ int tracks_device(const uint64_t *view_off64, uint32_t n_views, uint32_t n, cons
   SFM_RC(d_off.alloc(nullptr, n_tracks));
   SFM_RC(d_view.alloc(nullptr, n_rows));
   SFM_RC(d_feat.alloc(nullptr, n_rows));
-  hipLaunchKernelGGL(k_trk_emit, gm, b256, 0, s, node, (const uint32_t *)d_ex, m, (const uint32_t *)d_start,
-                     (const uint32_t *)d_tid, (const uint32_t *)d_toff, (const uint32_t *)d_voff, n_views, d_off.get(),
-                     d_view.get(), d_feat.get());
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_trk_emit, gm, b256, 0, s, node, d_ex, m, d_start, d_tid, d_toff, d_voff, n_views, d_off, d_view,
+                    d_feat));
   std::vector<uint32_t> off32(n_tracks);
   t->view.resize(n_rows);
   t->feat.resize(n_rows);

@@ -465,9 +465,8 @@ int tb_moments(BowTrain *t) {
   int rc = tb_part(t, (size_t)chunks * n_out);
   if (rc) return rc;
   if (!t->d_mom && (rc = t->d_mom.alloc(nullptr, (size_t)(kTbMaxDim + kTbMaxDim * (kTbMaxDim + 1) / 2)))) return rc;
-  hipLaunchKernelGGL(k_tb_moments, dim3(chunks), dim3(256), 0, t->s, (const float *)t->d_x, n, dim, t->d_part);
-  hipLaunchKernelGGL(k_tb_colsum, dim3((n_out + 255) / 256), dim3(256), 0, t->s, (const double *)t->d_part, chunks, n_out, t->d_mom);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_tb_moments, dim3(chunks), dim3(256), 0, t->s, t->d_x, n, dim, t->d_part));
+  SFM_RC(dev_launch(k_tb_colsum, dim3((n_out + 255) / 256), dim3(256), 0, t->s, t->d_part, chunks, n_out, t->d_mom));
   std::vector<double> mom(n_out);
   SFM_RC(t->d_mom.download(mom.data(), n_out, t->s));
   SFM_HIP(hipStreamSynchronize(t->s));
@@ -487,21 +486,6 @@ int tb_moments(BowTrain *t) {
   return SFMLOC_OK;
 }
 
-template <int DMAX>
-struct TbKernels {
-  static void pp_dist(dim3 g, hipStream_t s, const float *x, uint32_t n, int dim, const int32_t *dci, int32_t ci,
-                      const float *prev, float *out) {
-    hipLaunchKernelGGL(k_tb_pp_dist<DMAX>, g, dim3(256), 0, s, x, n, dim, dci, ci, prev, out);
-  }
-  static void assign(dim3 g, size_t lds, hipStream_t s, const float *x, uint32_t n, int dim, const float *c, int K,
-                     int32_t *labels, float *mind) {
-    hipLaunchKernelGGL(k_tb_assign<DMAX>, g, dim3(256), lds, s, x, n, dim, c, K, labels, mind);
-  }
-  static void empty(hipStream_t s, const float *x, uint32_t n, int dim, int K, int32_t *labels, double *sum, uint32_t *cnt) {
-    hipLaunchKernelGGL(k_tb_empty<DMAX>, dim3(1), dim3(kTbEmptyThreads), 0, s, x, n, dim, K, labels, sum, cnt);
-  }
-};
-
 struct KmWork {
   DevBuf<float> dist[3];
   DevBuf<double> dpart[3];
@@ -515,7 +499,6 @@ struct KmWork {
 template <int DMAX>
 int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, double eps, uint64_t seed, float *centers,
               int32_t *labels, float *min_dist, double *compactness, uint32_t *iterations) {
-  using Kn = TbKernels<DMAX>;
   const uint32_t n = t->n, dim = t->dim, chunks = tb_chunks(n);
   const hipStream_t s = t->s;
   const dim3 g_rows((n + 255) / 256), g_chunks((chunks + 255) / 256);
@@ -544,10 +527,7 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
   const uint32_t iter_end = std::max(max_iter, 2u);
   const size_t lds_assign = (size_t)K * dim * sizeof(float);
   const size_t lds_csum = (size_t)K * dim * sizeof(double) + (size_t)K * sizeof(uint32_t);
-  // (k_tb_csum_part takes up to 64 KB of dynamic LDS -- 49 KB for the reference's K = 100 x 61 -- above the default
-  // 48 KB launch limit; the attribute belongs to the current device, so it is set on every call)
-  SFM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tb_csum_part), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              64 * 1024));
+  // (lds_csum: up to 64 KB -- 49 KB for the reference's K = 100 x 61 --, above the default limit of a launch)
   uint32_t n_iter = 0;
   double best = DBL_MAX;
   std::vector<int32_t> ids(K);
@@ -559,13 +539,13 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
         // generateCentersPP: dist = d(x, x_c0); per centre three trials, the one of the smallest potential is kept
         int di = 0, ti = 1, t2 = 2;
         ids[0] = (int32_t)(rng_next(&rng) % n);
-        Kn::pp_dist(g_rows, s, t->d_x, n, (int)dim, nullptr, ids[0], nullptr, w.dist[di]);
-        hipLaunchKernelGGL(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, (const float *)w.dist[di], n, w.dpart[di]);
-        SFM_HIP(hipGetLastError());
+        SFM_RC(dev_launch(k_tb_pp_dist<DMAX>, g_rows, dim3(256), 0, s, t->d_x, n, (int)dim, nullptr, ids[0], nullptr,
+                          w.dist[di]));
+        SFM_RC(dev_launch(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, w.dist[di], n, w.dpart[di]));
         double sum0 = 0.0;
         {
-          hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[di], chunks,
-                             (const float *)w.dist[di], n, -1.0, w.d_pick + 1);
+          SFM_RC(dev_launch(k_tb_pp_pick, dim3(1), dim3(64), 0, s, w.dpart[di], chunks, w.dist[di], n, -1.0,
+                            w.d_pick + 1));
           PpPick p{};
           SFM_RC(w.d_pick.download(&p, 1, s, 1));
           SFM_HIP(hipStreamSynchronize(s));
@@ -577,13 +557,12 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
           for (int trial = 0; trial < 3; ++trial) {
             const double u = rng_double(&rng);
             // the draw on dist (slot 0), the trial's potential on min(dist, d(x, x_ci)) (slot 1)
-            hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[di], chunks,
-                               (const float *)w.dist[di], n, u, w.d_pick);
-            Kn::pp_dist(g_rows, s, t->d_x, n, (int)dim, &w.d_pick.get()->ci, 0, w.dist[di], w.dist[t2]);
-            hipLaunchKernelGGL(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, (const float *)w.dist[t2], n, w.dpart[t2]);
-            hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[t2], chunks,
-                               (const float *)w.dist[t2], n, -1.0, w.d_pick + 1);
-            SFM_HIP(hipGetLastError());
+            SFM_RC(dev_launch(k_tb_pp_pick, dim3(1), dim3(64), 0, s, w.dpart[di], chunks, w.dist[di], n, u, w.d_pick));
+            SFM_RC(dev_launch(k_tb_pp_dist<DMAX>, g_rows, dim3(256), 0, s, t->d_x, n, (int)dim, &w.d_pick.get()->ci, 0,
+                              w.dist[di], w.dist[t2]));
+            SFM_RC(dev_launch(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, w.dist[t2], n, w.dpart[t2]));
+            SFM_RC(dev_launch(k_tb_pp_pick, dim3(1), dim3(64), 0, s, w.dpart[t2], chunks, w.dist[t2], n, -1.0,
+                              w.d_pick + 1));
             PpPick p[2];
             SFM_RC(w.d_pick.download(p, 2, s));
             SFM_HIP(hipStreamSynchronize(s));
@@ -600,36 +579,32 @@ int tb_kmeans(BowTrain *t, uint32_t K, uint32_t attempts, uint32_t max_iter, dou
         }
         (void)sum0;
         SFM_RC(w.d_ids.upload(ids.data(), K, s));
-        hipLaunchKernelGGL(k_tb_gather_rows, dim3((K * dim + 255) / 256), dim3(256), 0, s, (const float *)t->d_x,
-                           (const int32_t *)w.d_ids, K, dim, w.d_cen[cur]);
-        SFM_HIP(hipGetLastError());
+        SFM_RC(dev_launch(k_tb_gather_rows, dim3((K * dim + 255) / 256), dim3(256), 0, s, t->d_x, w.d_ids, K, dim,
+                          w.d_cen[cur]));
         SFM_HIP(hipStreamSynchronize(s));  // (ids is read by the copy above)
       } else {
         // centres from the labels: per-chunk f64 sums, chunks in order, the empty-cluster rule, the division
-        hipLaunchKernelGGL(k_tb_csum_part, dim3(chunks), dim3(64), lds_csum, s, (const float *)t->d_x, n, (int)dim,
-                           (const int32_t *)w.d_labels, (int)K, w.d_psum, w.d_pcnt);
-        hipLaunchKernelGGL(k_tb_colsum, dim3((K * dim + 255) / 256), dim3(256), 0, s, (const double *)w.d_psum, chunks,
-                           K * dim, w.d_sum);
-        hipLaunchKernelGGL(k_tb_cnt_sum, dim3((K + 255) / 256), dim3(256), 0, s, (const uint32_t *)w.d_pcnt, chunks,
-                           (int)K, w.d_cnt);
-        Kn::empty(s, t->d_x, n, (int)dim, (int)K, w.d_labels, w.d_sum, w.d_cnt);
-        hipLaunchKernelGGL(k_tb_divide, dim3(1), dim3(1024), 0, s, (const double *)w.d_sum, (const uint32_t *)w.d_cnt,
-                           (int)K, (int)dim, (const float *)w.d_cen[cur], w.d_cen[cur ^ 1], w.d_shift);
-        SFM_HIP(hipGetLastError());
+        SFM_RC(dev_launch(k_tb_csum_part, dim3(chunks), dim3(64), lds_csum, s, t->d_x, n, (int)dim, w.d_labels, (int)K,
+                          w.d_psum, w.d_pcnt));
+        SFM_RC(dev_launch(k_tb_colsum, dim3((K * dim + 255) / 256), dim3(256), 0, s, w.d_psum, chunks, K * dim,
+                          w.d_sum));
+        SFM_RC(dev_launch(k_tb_cnt_sum, dim3((K + 255) / 256), dim3(256), 0, s, w.d_pcnt, chunks, (int)K, w.d_cnt));
+        SFM_RC(dev_launch(k_tb_empty<DMAX>, dim3(1), dim3(kTbEmptyThreads), 0, s, t->d_x, n, (int)dim, (int)K,
+                          w.d_labels, w.d_sum, w.d_cnt));
+        SFM_RC(dev_launch(k_tb_divide, dim3(1), dim3(1024), 0, s, w.d_sum, w.d_cnt, (int)K, (int)dim, w.d_cen[cur],
+                          w.d_cen[cur ^ 1], w.d_shift));
         cur ^= 1;
         SFM_RC(w.d_shift.download(&max_shift, 1, s));
         SFM_HIP(hipStreamSynchronize(s));
       }
       if (++iter == iter_end || max_shift <= eps2) break;
       ++n_iter;  // (one more assignment: the Lloyd iterations of all attempts)
-      Kn::assign(g_rows, lds_assign, s, t->d_x, n, (int)dim, w.d_cen[cur], (int)K, w.d_labels, w.d_mind);
-      SFM_HIP(hipGetLastError());
+      SFM_RC(dev_launch(k_tb_assign<DMAX>, g_rows, dim3(256), lds_assign, s, t->d_x, n, (int)dim, w.d_cen[cur], (int)K,
+                        w.d_labels, w.d_mind));
     }
     // compactness: the min distances of the last assignment, chunked f64 sum
-    hipLaunchKernelGGL(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, (const float *)w.d_mind, n, w.dpart[0]);
-    hipLaunchKernelGGL(k_tb_pp_pick, dim3(1), dim3(64), 0, s, (const double *)w.dpart[0], chunks, (const float *)w.d_mind,
-                       n, -1.0, w.d_pick + 1);
-    SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_tb_chunk_sum, g_chunks, dim3(256), 0, s, w.d_mind, n, w.dpart[0]));
+    SFM_RC(dev_launch(k_tb_pp_pick, dim3(1), dim3(64), 0, s, w.dpart[0], chunks, w.d_mind, n, -1.0, w.d_pick + 1));
     PpPick p{};
     SFM_RC(w.d_pick.download(&p, 1, s, 1));
     SFM_HIP(hipStreamSynchronize(s));
@@ -803,9 +778,8 @@ int sfmloc_bowtrain_add_image(sfmloc_bowtrain *p, const uint8_t *bgr, uint32_t w
     if (rc) return rc;
   }
   SFM_RC(t->d_idx.upload(idx.data(), n_pick, t->s));
-  hipLaunchKernelGGL(k_tb_gather8, dim3((n_pick * t->dim + 255) / 256), dim3(256), 0, t->s,
-                     (const uint8_t *)akaze_desc_dev(a), (const uint32_t *)t->d_idx, n_pick, t->dim, dst);
-  SFM_HIP(hipGetLastError());
+  SFM_RC(dev_launch(k_tb_gather8, dim3((n_pick * t->dim + 255) / 256), dim3(256), 0, t->s, akaze_desc_dev(a), t->d_idx,
+                    n_pick, t->dim, dst));
   SFM_HIP(hipStreamSynchronize(t->s));  // (idx is a host vector; the image may be reused by the caller at once)
   t->n += n_pick;
   t->pca_ok = false;
@@ -874,9 +848,8 @@ int sfmloc_bowtrain_project(sfmloc_bowtrain *p, const sfmloc_bof_desc *pca) {
   SFM_RC(t->d_peval.upload(pca->pca_eigval, np, t->s));
   const uint64_t total = (uint64_t)t->n * np;
   if (total)
-    hipLaunchKernelGGL(k_tb_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, t->s, (const float *)t->d_x, t->n,
-                       in_dim, (const float *)t->d_pmean, (const float *)t->d_pevec, (const float *)t->d_peval, np, t->d_y);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_tb_project, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, t->s, t->d_x, t->n, in_dim,
+                      t->d_pmean, t->d_pevec, t->d_peval, np, t->d_y));
   SFM_HIP(hipStreamSynchronize(t->s));  // (the model arrays are the caller's)
   std::swap(t->d_x, t->d_y);
   t->dim = (uint32_t)np;

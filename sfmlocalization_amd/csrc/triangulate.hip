@@ -315,17 +315,16 @@ int triangulate_run(Sfm &h, const sfmloc_triangulate_options &opt, sfmloc_triang
   A.P = d_P;
   A.select = d_select;
   A.counters = d_cnt;
-  hipLaunchKernelGGL(k_tri_views, dim3((h.n_views + 255) / 256), dim3(256), 0, s, h.n_views, A.view_intr, A.view_pose,
-                     (const double *)A.intr, (const double *)A.pose_R, (const double *)A.pose_C, d_P.get());
+  SFM_RC(dev_launch(k_tri_views, dim3((h.n_views + 255) / 256), dim3(256), 0, s, h.n_views, A.view_intr, A.view_pose,
+                    A.intr, A.pose_R, A.pose_C, d_P));
   if (h.n_obs)
-    hipLaunchKernelGGL(k_tri_pixels, dim3((unsigned)((h.n_obs + 255) / 256)), dim3(256), 0, s, h.n_obs, A.obs_view,
-                       A.obs_x, A.view_intr, A.intr_type, (const double *)A.intr, h.d_ray.get());
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_tri_pixels, dim3((unsigned)((h.n_obs + 255) / 256)), dim3(256), 0, s, h.n_obs, A.obs_view,
+                      A.obs_x, A.view_intr, A.intr_type, A.intr, h.d_ray));
   if (h.n_lm) {
     const uint64_t lanes = (uint64_t)h.n_lm * kTriLanes;
-    hipLaunchKernelGGL(k_tri_landmarks, dim3((unsigned)((lanes + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, s, A);
+    SFM_RC(dev_launch(k_tri_landmarks, dim3((unsigned)((lanes + kTriBlock - 1) / kTriBlock)), dim3(kTriBlock), 0, s,
+                      A));
   }
-  SFM_HIP(hipGetLastError());
   if ((rc = d.time_end())) return rc;
   SFM_RC(d_cnt.download(cnt, 6, s));
   SFM_HIP(hipStreamSynchronize(s));

@@ -273,12 +273,11 @@ extern "C" int sfmloc_undistorter_apply(sfmloc_undistorter *handle, const uint8_
   SFM_RC(u->d_src.upload(src, n_src, u->stream));
   const dim3 grid((u->roi[2] + 63) / 64, (u->roi[3] + 3) / 4), block(256);
   if (channels == 3)
-    hipLaunchKernelGGL(k_undistort_remap<3>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy, u->d_frac,
-                       u->roi[0], u->roi[1], u->roi[2], u->roi[3], u->d_dst);
+    SFM_RC(dev_launch(k_undistort_remap<3>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy,
+                      u->d_frac, u->roi[0], u->roi[1], u->roi[2], u->roi[3], u->d_dst));
   else
-    hipLaunchKernelGGL(k_undistort_remap<1>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy, u->d_frac,
-                       u->roi[0], u->roi[1], u->roi[2], u->roi[3], u->d_dst);
-  SFM_HIP(hipGetLastError());
+    SFM_RC(dev_launch(k_undistort_remap<1>, grid, block, 0, u->stream, u->d_src, (int)u->w, (int)u->h, u->d_xy,
+                      u->d_frac, u->roi[0], u->roi[1], u->roi[2], u->roi[3], u->d_dst));
   SFM_RC(u->d_dst.download(dst, n_dst, u->stream));
   SFM_HIP(hipStreamSynchronize(u->stream));
   return SFMLOC_OK;
