@@ -1653,6 +1653,51 @@ int sfmloc_reduce_points(const double *X /*[n*3]*/, uint64_t n, const double *A 
 double sfmloc_reduce_last_ms(void);
 
 /* ------------------------------------------------------------------------- */
+/* All-views BoW k-NN (the pair list of a map under construction: for every view the k views nearest to it in BoW     */
+/* space, which sfmlocalization_amd.bowpairs / ComputeBoWPairs turn into the pair file ExtFeatAndMatch -p reads).  Row */
+/* i is what sfmloc_bow_select answers for the query bow[i] over the candidates cand(i); the call takes no handle and  */
+/* works on host arrays, bow [n * dim] float32 row-major.                                                              */
+/*   distance    d(i, j) = the float32 squared L2 distance of sfmloc_bow_select (oracle/sfm_oracle_bow.c orc_bow_dist): */
+/*               64 partial sums, partial l adds (a - b) * (a - b) for the elements l, l + 64, ... in index order,      */
+/*               unfused; then partial[l] + partial[l ^ stride] for the strides 32, 16, 8, 4, 2, 1.  d(i, j) and        */
+/*               d(j, i) have equal bits.                                                                              */
+/*   candidates  cand(i) = { j : |j - i| > window }: window = 0 leaves out only i itself; a caller that already pairs  */
+/*               every view with its `window` neighbours in sequence spends k on the other views.                      */
+/*               count[i] = min(k, |cand(i)|).                                                                          */
+/*   selection   the count[i] candidates smallest in (distance bits, index): ties go to the lower index.  nbr[i*k ..]  */
+/*               holds them in ASCENDING INDEX (as sfmloc_bow_select returns a shortlist), dist[i*k + s] the distance  */
+/*               of nbr[i*k + s]; the slots from count[i] on hold 0xFFFFFFFF and +inf.                                  */
+/*   +inf        a distance that overflows to +inf from finite vectors is a distance like any other: above every       */
+/*               finite one, below an entry that is no candidate.                                                       */
+/*   nothing     n < 2 or window >= n - 1: every count is 0, every slot padding, SFMLOC_OK, nothing is launched.        */
+/*   refusals    all before anything is allocated or launched (they come back on a machine without a GPU), no output   */
+/*               written: k = 0, dim = 0, a NULL array with n > 0, a NaN or infinite entry of bow ("row 3 has a         */
+/*               non-finite value"): SFMLOC_EINVAL.  n > 2^22, n * k > 2^32 entries: SFMLOC_ECAP.                        */
+/*   memory      the n x n distances never exist at once: a pass computes the distances of rows_per_launch query rows   */
+/*               to all n views into a scratch of rows_per_launch * n uint32 and selects from it, then the next pass.   */
+/*               rows_per_launch = 0: the library's, 2^26 / n rows rounded down to a multiple of 16 (at least 1, at     */
+/*               most n): a scratch of at most 256 MB, two passes at n = 10 000.  Beside it: bow itself and the         */
+/*               results of one pass.  No bit of any output depends on rows_per_launch.                                 */
+/*   profile     1: sfmloc_bowknn_last_ms is the device time between two events around the passes (the kernels and the */
+/*               copies of each pass's results to the host); 0 otherwise.                                               */
+/* FLANN's approximate KD-tree search of the reference (BoFUtils.cpp:46-59) is replaced by the exact search, as in       */
+/* sfmloc_bow_select.                                                                                                    */
+/* ------------------------------------------------------------------------- */
+typedef struct sfmloc_bowknn_options {
+  uint32_t k;                /* neighbours per view, >= 1 */
+  uint32_t window;           /* candidates of row i: every j with |j - i| > window; 0 excludes only i itself */
+  uint32_t rows_per_launch;  /* query rows per distance/select pass; 0 = the library's; no output depends on it */
+  uint32_t profile;          /* 1: time the call between two events */
+} sfmloc_bowknn_options;
+void   sfmloc_bowknn_default_options(sfmloc_bowknn_options *o);   /* k 20, window 0, 0, 0 */
+/* opt NULL = the defaults */
+int    sfmloc_bow_knn(int device, const float *bow /*[n*dim]*/, uint32_t n, uint32_t dim,
+                      const sfmloc_bowknn_options *opt,
+                      uint32_t *nbr /*[n*k]*/, float *dist /*[n*k]*/, uint32_t *count /*[n]*/);
+/* device milliseconds of the calling thread's last sfmloc_bow_knn made with profile = 1 */
+double sfmloc_bowknn_last_ms(void);
+
+/* ------------------------------------------------------------------------- */
 /* Map-side matching: the reference's matchAKAZE /         */
 /* trackAKAZE on the same kernels.  Views are addressed by their index in the  */
 /* map's view table (ascending view id).                                       */

@@ -58,6 +58,7 @@ GposesReport = _abi.struct("sfmloc_gposes_report")
 MergeParams = _abi.struct("sfmloc_merge_params")
 MergeResult = _abi.struct("sfmloc_merge_result")
 ReduceResult = _abi.struct("sfmloc_reduce_result")
+BowknnOptions = _abi.struct("sfmloc_bowknn_options")
 KernelStats = _abi.struct("sfmloc_kernel_stats")
 
 # every entry point include/sfmloc.h declares (tests check the library exports each one)
@@ -1624,6 +1625,34 @@ def reduce_points(X, A=None, thres=0.01, knn=1000, params=None, out=None):
 
 def reduce_last_ms():
     return float(_L().sfmloc_reduce_last_ms())
+
+
+def bowknn_default_options(**overrides):
+    """sfmloc_bowknn_default_options -> BowknnOptions (k 20, window 0, rows_per_launch 0, profile 0)"""
+    return _options(BowknnOptions, "sfmloc_bowknn_default_options", overrides)
+
+
+def bow_knn(bow, k, window=0, rows_per_launch=0, device=0, profile=False, out=None):
+    """sfmloc_bow_knn on the BoW vectors bow[n, dim]: for every view the k views nearest to it among those more than
+    `window` places away (include/sfmloc.h "All-views BoW k-NN") -> (nbr uint32 [n, k] ascending per row, padded with
+    0xFFFFFFFF; dist float32 [n, k], padded with +inf; count uint32 [n]).  out: (nbr, dist, count) arrays to write into
+    (the tests watch them on a refused call)."""
+    bow = np.ascontiguousarray(bow, np.float32)
+    if bow.ndim != 2:
+        raise ValueError("bow: an [n, dim] matrix")
+    n, dim = bow.shape
+    opt = bowknn_default_options(k=int(k), window=min(int(window), 0xFFFFFFFF), rows_per_launch=int(rows_per_launch), profile=int(bool(profile)))
+    kk = max(int(k), 0)
+    nbr, dist, count = out if out is not None else (np.empty((n, kk), np.uint32), np.empty((n, kk), np.float32),
+                                                   np.empty(n, np.uint32))
+    _check(_L().sfmloc_bow_knn(int(device), _ptr(bow, C.c_float), n, dim, C.byref(opt), _ptr(nbr, C.c_uint32),
+                               _ptr(dist, C.c_float), _ptr(count, C.c_uint32)))
+    return nbr, dist, count
+
+
+def bowknn_last_ms():
+    """device milliseconds of the calling thread's last sfmloc_bow_knn made with profile"""
+    return float(_L().sfmloc_bowknn_last_ms())
 
 
 class BowTrainer:

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <initializer_list>
 #include <map>
@@ -105,6 +106,49 @@ inline bool read_desc(const std::string &p, std::vector<uint8_t> *rows) {
   }
   fclose(f);
   return ok;
+}
+
+// ---- <base>.bow and the other saveMatBin files: [i32 rows][i32 cols][i32 cv depth][rows x cols values]
+// (fileio.read_mat_bin; hulo::readMatBin, FileUtils.cpp:43-75) ----
+// The values row-major as doubles, which hold every depth's values exactly (0 u8, 1 i8, 2 u16, 3 i16, 4 i32, 5 f32,
+// 6 f64).  rows = 0 is an empty matrix with nothing after it.  A short header, an unknown depth, a negative size or a
+// body shorter than rows x cols values is refused with *values as it was; bytes after the values are ignored.
+inline bool read_mat_bin(const std::string &p, int32_t *rows, int32_t *cols, std::vector<double> *values) {
+  static const size_t kDepthBytes[7] = {1, 1, 2, 2, 4, 4, 8};
+  FILE *f = fopen(p.c_str(), "rb");
+  if (!f) return false;
+  int32_t head[3] = {0, 0, 0};
+  struct stat st;
+  bool ok = fstat(fileno(f), &st) == 0 && fread(&head[0], 4, 1, f) == 1;
+  std::vector<double> v;
+  if (ok && head[0] != 0) {
+    ok = fread(&head[1], 4, 2, f) == 2 && head[0] > 0 && head[1] > 0 && head[2] >= 0 && head[2] <= 6;
+    const uint64_t count = ok ? (uint64_t)head[0] * (uint64_t)head[1] : 0;
+    ok = ok && count <= ((uint64_t)st.st_size - 12) / kDepthBytes[head[2]];
+    if (ok) {
+      std::vector<uint8_t> raw((size_t)count * kDepthBytes[head[2]]);
+      ok = fread(raw.data(), 1, raw.size(), f) == raw.size();
+      v.resize(ok ? (size_t)count : 0);
+      for (size_t i = 0; ok && i < (size_t)count; ++i) {
+        const uint8_t *at = raw.data() + i * kDepthBytes[head[2]];
+        switch (head[2]) {
+          case 0: v[i] = *at; break;
+          case 1: v[i] = *reinterpret_cast<const int8_t *>(at); break;
+          case 2: { uint16_t x; memcpy(&x, at, 2); v[i] = x; break; }
+          case 3: { int16_t x; memcpy(&x, at, 2); v[i] = x; break; }
+          case 4: { int32_t x; memcpy(&x, at, 4); v[i] = x; break; }
+          case 5: { float x; memcpy(&x, at, 4); v[i] = x; break; }
+          default: { double x; memcpy(&x, at, 8); v[i] = x; break; }
+        }
+      }
+    }
+  }
+  fclose(f);
+  if (!ok) return false;
+  *rows = head[0];
+  *cols = head[0] ? head[1] : 0;
+  values->swap(v);
+  return true;
 }
 
 // ---- <base>.feat: "x y size angle" per line (fileio.read_feat) ----
